@@ -1,8 +1,12 @@
 #!/usr/bin/env python3
 """bench.py -- snowfall-augmentation throughput on MI355X, BASELINE.json's metric on its config C2.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--frames F] [--workload C2|C2far|C1|C4|C3|C5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--frames F] [--workload C2|C2far|C1|C4|C3|C5] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps (and with --dump-outputs writes what the last one computed) and prints the line.
+The side measurements below -- value_pcie_inclusive, single_frame, batches in flight, the counter passes of roofline.traffic / valu,
+cpu_baseline / cpu_twin -- take runs and processes of their own and are made with --full only.
 
 `--gpus N` with N > 1 and no launcher environment (WORLD_SIZE unset) re-executes itself under torch.distributed.run with
 N ranks on 127.0.0.1, one rank per GPU; it fails loudly if the node has fewer devices.
@@ -22,7 +26,8 @@ Prints ONE JSON line on rank 0:
   single_frame           one sweep end to end (upload, all kernels, download, synchronise): through the C ABI with page-locked
                          buffers, and through the Python augment() with a pageable array, as the reference's callers have it
   roofline               per-beam region: achieved = algorithmic bytes / HIP-event time; `traffic` and `valu` from rocprofv3
-                         --pmc passes of this same command, run as child processes (N = 1 only; --no-pmc skips them)
+                         --pmc passes of this same command, run as child processes (--full, N = 1 only; --no-pmc skips them;
+                         otherwise `traffic` is the committed profiles/hbm_traffic.json figure where it matches the run)
   cpu_baseline           the CPU oracle on four frames of the same workload (all host cores, and one core)
 """
 import argparse
@@ -72,9 +77,17 @@ REGION_KERNELS = ("k_beams", "k_power", "k_tier")    # the per-beam region of ro
 FETCH_FACTOR, WRITE_FACTOR = 2.0, 1.0
 
 
-def make_tables(n_lines=64, snowfall=SNOWFALL, velocity=VELOCITY, distinct=None):
+def dart_line(occ, rate, line):
+    from lidar_snow_sim_amd.tools.snowfall import sampling as smp
+    return smp.dart_throwing(occ, rate, 80.0, np.random.default_rng(42 + line), "gunn")
+
+
+def make_tables(n_lines=64, snowfall=SNOWFALL, velocity=VELOCITY, distinct=None, workers=1):
     """dart_throwing(occupancy, rain rate, 80 m, default_rng(42 + line), 'gunn') per line (SURVEY 8 d); cached on disk for
-    the child processes of the counter passes (same seeds, same tables)."""
+    the child processes of the counter passes (same seeds, same tables).  workers > 1 throws the lines in that many fresh
+    (spawned) worker processes side by side -- each line has a generator of its own, so the tables do not depend on the split;
+    one core takes ~0.2 s per C2 line.  Only main() asks for it: a spawned worker re-imports its parent's __main__ module,
+    which for a script without an `if __name__ == "__main__"` guard would run that script (and open the GPU) again."""
     from lidar_snow_sim_amd.tools.snowfall import sampling as smp
     occ = smp.compute_occupancy(snowfall, velocity)
     rate = smp.snowfall_rate_to_rainfall_rate(snowfall, velocity)
@@ -92,7 +105,15 @@ def make_tables(n_lines=64, snowfall=SNOWFALL, velocity=VELOCITY, distinct=None)
         except Exception:
             tabs = None
     if tabs is None:
-        tabs = [smp.dart_throwing(occ, rate, 80.0, np.random.default_rng(42 + line), "gunn") for line in range(1, distinct + 1)]
+        lines = list(range(1, distinct + 1))
+        workers = min(workers, distinct)
+        if workers > 1:
+            import multiprocessing
+            from concurrent.futures import ProcessPoolExecutor
+            with ProcessPoolExecutor(workers, mp_context=multiprocessing.get_context("spawn")) as ex:   # (spawn: no fork of a process that holds the GPU)
+                tabs = list(ex.map(dart_line, [occ] * distinct, [rate] * distinct, lines))
+        else:
+            tabs = [dart_line(occ, rate, line) for line in lines]
         try:
             tmp = cache.with_suffix(f".{os.getpid()}.npz")
             np.savez(tmp, **{f"t{i}": t for i, t in enumerate(tabs)})
@@ -564,12 +585,40 @@ def cpu_legs(W):
     return out
 
 
+DUMP_BUDGET = 48 << 20      # bytes of sampled rows + source indices; counts, stats and flags of every frame come on top (a few KB)
+
+
+def dump_outputs(r, F, n_per, out):
+    """--dump-outputs: what the caller of augment_batch(..., sync=False) receives from the last timed step (a DeviceResult, the device
+    synchronised): counts.npy and stats.npy of all F frames, flags.npy with the fused wet ground, and for a seeded sample of frames
+    (frames.npy, ascending) their kept rows (rows.npy, the result's dtype) and the frame-local source row of each (src.npy)."""
+    out.mkdir(parents=True, exist_ok=True)
+    counts = r.counts.cpu().numpy()
+    rows_bytes = n_per * (5 * r.rows.element_size() + 8)
+    sel = np.sort(np.random.default_rng(0).choice(F, max(1, min(F, DUMP_BUDGET // rows_bytes)), replace=False))
+    kept = [(int(r.offsets[f]), int(counts[f])) for f in sel]
+    arrays = {"counts": counts.astype(np.float64), "stats": r.stats.cpu().numpy().astype(np.float64), "frames": sel.astype(np.float64),
+              "rows": np.concatenate([r.rows[a:a + n].cpu().numpy() for a, n in kept]),
+              "src": np.concatenate([r.src[a:a + n].cpu().numpy() for a, n in kept]).astype(np.float64)}
+    if r.flags is not None:
+        arrays["flags"] = r.flags.cpu().numpy().astype(np.float64)
+    for name, a in arrays.items():
+        np.save(out / f"{name}.npy", a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--frames", type=int, default=None, help=f"frames per batch and GPU (default {DEFAULT_FRAMES}); C5: frames of the whole stream (default 10000)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the side measurements: batches in flight and host entry (PCIe-inclusive) and single frame (both dropped by --no-pcie), "
+                         "rocprofv3 counter passes (--no-pmc), CPU oracle and CPU twin (--no-cpu-baseline); without it a run times the steps and "
+                         "prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32 / float64, rank 0's batch): "
+                         "counts and stats of every frame, the kept rows and source indices of a fixed, seeded sample of frames")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 counter passes (roofline.traffic / valu from profiles/)")
     ap.add_argument("--no-pcie", action="store_true", help="skip the host-entry (PCIe-inclusive) and single-frame measurements")
@@ -584,10 +633,14 @@ def main():
                     help="host: dart_throwing on the host (bit-exact mirror of sampling.py), uploaded once; device: sampled and filed on the GPU "
                          "(snowgpu_sample_table, seed = f(prefix, line)): no table ever crosses the link; reports sampler throughput")
     args = ap.parse_args()
-    if args.inner:
+    if args.inner or not args.full:
         args.no_cpu_baseline = args.no_pmc = args.no_pcie = True
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
+    if args.dump_outputs and (args.dry or args.workload == "C5"):
+        raise SystemExit("--dump-outputs: a --dry run computes nothing, and C5 writes its outputs as .bin files (--c5-dir, --c5-keep)")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus, args.dry))
 
@@ -654,6 +707,7 @@ def main():
 
     layers, azimuths, snowfall, velocity, rscale = WORKLOADS[args.workload]
     fused_wet = args.workload == "C3"
+    host_workers = max(1, min(16, usable_cpus()[0]) // world)       # set-up threads / processes: this rank's share of a 16-CPU grant
     eng = engine.get_engine(local_rank)
     if layers != 64:                                       # SURVEY 8 d: 128-entry laser table = the 64-entry one tiled
         eng.set_lasers(engine.load_lasers() * (layers // 64))
@@ -677,15 +731,18 @@ def main():
         if tables is not None:
             tables = [tables[i % len(tables)] for i in range(layers)]
     else:
-        tables = make_tables(layers, snowfall, velocity, distinct=min(layers, 64))
+        tables = make_tables(layers, snowfall, velocity, distinct=min(layers, 64), workers=host_workers)
         ktot = sum(t.shape[0] for t in tables)
     F = args.frames
     import random
     frames, orders, table_ids, planes, polys = [], [], [], [], []
     plane = ([0.0, 0.0, -1.0], -1.7)
+    from concurrent.futures import ThreadPoolExecutor
+    with ThreadPoolExecutor(host_workers) as ex:                       # (the sweep generator is NumPy array work: it releases the GIL)
+        made = list(ex.map(lambda f: make_frame(layers, azimuths, 1000 + rank * F + f, rscale, args.workload in FIRING_ORDER), range(F)))
     for f in range(F):
         seed = 1000 + rank * F + f
-        pc = make_frame(layers, azimuths, seed, rscale, args.workload in FIRING_ORDER)
+        pc = made[f]
         random.seed(seed)
         order = list(range(layers))
         random.shuffle(order)
@@ -775,6 +832,8 @@ def main():
     st = status.cpu().numpy()
     if st[0] != 0:
         raise RuntimeError(f"device status {st} after the timed region")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(res[(step_no[0] - 1) % L], F, n_per, Path(args.dump_outputs))
     if args.inner:
         return
 

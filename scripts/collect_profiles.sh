@@ -21,10 +21,10 @@ python scripts/trace_timeline.py $O/stats > $O/timeline.txt
 python scripts/trace_timeline.py $O/stats_serial > $O/timeline_serial.txt
 python scripts/probe/single_timeline.py $O/single > $O/single_sweep_timeline.txt 2>/dev/null; tail -1 $O/single.log >> $O/single_sweep_timeline.txt
 # 4. the bench line itself (its own FETCH_SIZE / WRITE_SIZE / SQ child passes; per-kernel byte table dumped on the way)
-SNOWGPU_BENCH_PMC_DUMP=$O/pmc_fetch_write_per_kernel.csv timeout 400 python bench.py > $O/bench_C2.json 2> $O/bench_C2.err
+SNOWGPU_BENCH_PMC_DUMP=$O/pmc_fetch_write_per_kernel.csv timeout 400 python bench.py --full > $O/bench_C2.json 2> $O/bench_C2.err
 # 5. the other workloads of BASELINE.json
-for w in ${WORKLOADS:-C4 C3 C2fire}; do timeout 200 python bench.py --workload $w --no-pmc --no-cpu-baseline $( [ $w = C4 ] && echo --frames 128 ) > $O/bench_$w.json 2> $O/bench_$w.err; done
-timeout 200 python bench.py --tables device --no-pmc --no-pcie > $O/bench_C2_device_tables.json 2> $O/bench_C2_device_tables.err
+for w in ${WORKLOADS:-C4 C3 C2fire}; do timeout 200 python bench.py --full --workload $w --no-pmc --no-cpu-baseline $( [ $w = C4 ] && echo --frames 128 ) > $O/bench_$w.json 2> $O/bench_$w.err; done
+timeout 200 python bench.py --full --tables device --no-pmc --no-pcie > $O/bench_C2_device_tables.json 2> $O/bench_C2_device_tables.err
 timeout 300 python bench.py --workload C5 --frames ${C5_FRAMES:-10000} > $O/bench_C5.json 2> $O/bench_C5.err
 # 6. the pipeline's own event trace (upload / compute / download per chunk)
 SNOWGPU_PIPE_TRACE=1 timeout 120 python scripts/pcie_bench.py --reps 1 --fast 2>&1 | grep "^pipe" > $O/pipeline_trace_all.txt

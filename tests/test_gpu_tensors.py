@@ -218,3 +218,45 @@ def test_reference_exception_types_from_the_status_words(tables):
         augment_batch([torch.from_numpy(pc).cuda()], "unused", BD, planes=[PLANE], particles=tl, q8="numpy")
     (st, aug), = augment_batch([torch.empty((0, 5), dtype=torch.float32, device="cuda")], "unused", BD, planes=[PLANE], particles=tl)   # an empty frame
     assert tuple(int(v) for v in st) == (0, 0, 0) and tuple(aug.shape) == (0, 5) and aug.is_cuda
+
+
+def test_bench_dump_outputs_hold_what_the_timed_path_returns(tmp_path):
+    """`bench.py --dump-outputs`: the line reports the steps asked for, the arrays do not depend on --steps / --warmup, and they are
+    what augment_batch() on a DeviceBatch returns in this process for bench's inputs (its frames, permutations, tables and plane)."""
+    import json
+    import subprocess
+    import sys
+    from pathlib import Path
+    import bench
+    from lidar_snow_sim_amd.tensors import DeviceBatch, augment_batch
+    root = Path(bench.__file__).resolve().parent
+    F = 8
+    dumps = {}
+    for steps, warmup in ((3, 1), (1, 0)):
+        d = tmp_path / f"steps{steps}"
+        r = subprocess.run([sys.executable, str(root / "bench.py"), "--frames", str(F), "--steps", str(steps), "--warmup", str(warmup),
+                            "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+        assert line["steps"] == steps and line["warmup"] == warmup and line["ms_per_step"] > 0
+        dumps[steps] = {p.stem: np.load(p) for p in sorted(d.glob("*.npy"))}
+    assert sorted(dumps[3]) == ["counts", "frames", "rows", "src", "stats"]
+    for k, a in dumps[3].items():
+        assert a.dtype == dumps[1][k].dtype and np.array_equal(a, dumps[1][k]), k
+    dump = dumps[3]
+    frames, orders = [], []
+    for f in range(F):
+        frames.append(bench.make_frame(64, 2048, 1000 + f, 1.0))
+        random.seed(1000 + f)
+        order = list(range(64))
+        random.shuffle(order)
+        orders.append(order)
+    n = frames[0].shape[0]
+    planes = np.asarray([[0.0, 0.0, -1.0, -1.7]] * F, np.float64)
+    res = augment_batch(DeviceBatch(torch.from_numpy(np.concatenate(frames)).cuda(), frame_rows=n), "unused", bench.BEAM_DIV, noise_floor=0.7,
+                        particles=bench.make_tables(64), orders=np.asarray(orders, np.int64), planes=planes, return_src=True)
+    assert np.array_equal(dump["counts"], [aug.shape[0] for _, aug, _ in res])
+    assert np.array_equal(dump["stats"], [[float(v) for v in st] for st, _, _ in res])
+    sel = dump["frames"].astype(np.int64)
+    assert np.array_equal(dump["rows"], np.concatenate([res[f][1].cpu().numpy() for f in sel]))
+    assert np.array_equal(dump["src"], np.concatenate([res[f][2].cpu().numpy() for f in sel]))

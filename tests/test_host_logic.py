@@ -265,6 +265,54 @@ def test_bench_gpus_2_spawns_two_ranks_over_gloo():
     assert r.returncode != 0 and "must agree" in r.stderr
 
 
+def test_bench_tables_thrown_side_by_side_are_the_serial_ones(tmp_path, monkeypatch):
+    """bench.make_tables(..., workers=3) throws its lines in worker processes: the tables are dart_throwing's with default_rng(42 + line),
+    line by line.  By default it throws them in the calling process: a script that imports bench and calls it at its top level, with
+    no `if __name__ == "__main__"` guard (scripts/gpu_graph.py and the probes), runs that top level once."""
+    import tempfile
+    import bench
+    from lidar_snow_sim_amd.tools.snowfall import sampling as smp
+    script = tmp_path / "unguarded.py"
+    script.write_text(f"import sys\nsys.path.insert(0, {str(ROOT)!r})\nimport bench\nprint('top level')\nbench.make_tables(2, 2.5, 1.6)\n")
+    r = subprocess.run([sys.executable, str(script)], capture_output=True, text=True, timeout=300, env=dict(os.environ, TMPDIR=str(tmp_path)))
+    assert r.returncode == 0 and r.stdout.count("top level") == 1, (r.stdout, r.stderr[-2000:])
+    monkeypatch.setattr(tempfile, "tempdir", str(tmp_path / "cold"))          # no cached tables
+    (tmp_path / "cold").mkdir()
+    got = bench.make_tables(3, 2.5, 1.6, workers=3)
+    occ, rate = smp.compute_occupancy(2.5, 1.6), smp.snowfall_rate_to_rainfall_rate(2.5, 1.6)
+    for line in (1, 2, 3):
+        want = smp.dart_throwing(occ, rate, 80.0, np.random.default_rng(42 + line), "gunn")
+        assert got[line - 1].dtype == want.dtype and np.array_equal(got[line - 1], want)
+
+
+def test_bench_dump_outputs_layout(tmp_path):
+    """--dump-outputs on a stand-in for the DeviceResult (CPU tensors): every frame's counts and stats, the kept rows and source
+    rows of a seeded sample of frames in ascending order, float32 / float64 only, within 64 MB."""
+    import types
+    import torch
+    import bench
+    F, n = 40, 131072
+    g = torch.Generator().manual_seed(0)
+    r = types.SimpleNamespace(rows=torch.randn(F * n, 5, generator=g), src=torch.randint(0, n, (F * n,), dtype=torch.int32, generator=g),
+                              counts=torch.randint(0, n + 1, (F,), generator=g), stats=torch.randint(0, 1000, (F, 3), generator=g),
+                              offsets=np.arange(F + 1) * n, flags=None)
+    for d in ("a", "b"):
+        bench.dump_outputs(r, F, n, tmp_path / d)
+    files = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert files == ["counts.npy", "frames.npy", "rows.npy", "src.npy", "stats.npy"]
+    assert sum((tmp_path / "a" / f).stat().st_size for f in files) <= 64 << 20
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in files}
+    for f in files:
+        assert np.array_equal(got[f[:-4]], np.load(tmp_path / "b" / f))           # the same sample every time
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    sel = got["frames"].astype(np.int64)
+    assert 1 < len(sel) < F and np.all(np.diff(sel) > 0)
+    counts = r.counts.numpy()
+    assert np.array_equal(got["counts"], counts) and np.array_equal(got["stats"], r.stats.numpy())
+    assert np.array_equal(got["rows"], np.concatenate([r.rows[f * n:f * n + counts[f]].numpy() for f in sel]))
+    assert np.array_equal(got["src"], np.concatenate([r.src[f * n:f * n + counts[f]].numpy() for f in sel]))
+
+
 def test_stream_driver_bookkeeping(tmp_path):
     """precompute.py's frame order, (rate, velocity) combos and output layout -- no GPU involved."""
     from lidar_snow_sim_amd import stream
