@@ -103,8 +103,6 @@ struct SgBeamArgs {
     int32_t *tier_hint;          // page-locked host words the device can write (or null): beams per later tier of THIS batch, read by the host when it schedules a later one
     unsigned long long *diff2;   // per frame: sum over attenuated rows of 2 * (0.9 * max_intensity - new_i)
     int32_t exact_math;          // 1: libm sin / tan + true division (validation mode)
-    int32_t per_lane_scan;       // candidate scan: >= 0: the wave flattens it in the pass over all rows, one beam per lane in the tiers;
-                                 // -1 = flattened everywhere (SNOWGPU_PER_LANE_SCAN)
     // tier classes: a beam of the first pass that met more flakes than its list holds is flagged with the first later
     // tier whose capacity takes all of them (the scan keeps COUNTING after the list is full, so the count is exact)
     int32_t n_cls;               // later tiers (the last one is the global-list tier, capacity = table size)
@@ -134,12 +132,7 @@ struct SgBeamArgs {
     uint16_t *dq_sc;             // per slot: flakes in the list | channel << 8
     unsigned long long *qn;      // per region
     int2_t *pw_items;            // work items of k_power (k_power_plan): {first slot, count | (frame + 1) << 10}
-    int32_t *pw_count;           // [0] items planned, [1] items of k_power_few, [2] beams on back_list, [3] k_power_all's item ticket (reset per chunk)
-    // One work list for the received-power phase (k_power_all): the multi-flake beams of ALL regions closed up -- back_list[i] = queue slot,
-    // region r's back run at bbase[r] (k_power_plan) copied by k_tier_gather -- so that a wave's 64 lanes are 64 beams whatever region they
-    // came from (per region the back run is ~80 slots at C2: a round of 64 and a round of 16).  null: the regions' runs are the items.
-    int32_t *back_list;
-    int32_t *bbase;
+    int32_t *pw_count;           // [0] items planned, [1] items of k_power_few (reset per chunk)
     int2_t *pw_items1;           // work items of k_power_few (the front of every region's slice), or null: k_power takes them too
     int32_t front_max;           // beams with up to this many flakes fill a region's slice from the front (1 .. 3 with pw_items1; else 1)
     int64_t n_regions_ub;        // host: upper bound of the regions (segments / linear chunks)
@@ -162,11 +155,10 @@ struct SgBeamArgs {
     // second instantiation through this list (laid out like tier_list: class k at k * tier_stride) and its per-class counters
     int32_t *redo_list;
     int32_t *redo_cnt;
-    // dict hand-over of a list-mode pass: entry i of the class -> slot i (planes of tq_cap entries)
+    // dict hand-over of a later tier's scan (k_tier_scan_direct): entry i of the class -> slot i, flakes in scan order (planes of tq_cap entries)
     double *tq;
     uint16_t *tq_sc;
     int32_t tq_cap;
-    int32_t tq_unsorted;
     // Overflow slots of the pass over all rows, one per sorted position (SG_OV_STRIDE doubles, touched only by beams that over-fill
     // their LDS list): range, azimuth, (a1, a2, rho) of every flake met, in arrival order; ov_sc[g] = flakes | channel << 8.
     // k_power<.., LISTQ> of a class reads them instead of a hand-over buffer when ov_list is set (and sorts by range as it loads).
@@ -198,11 +190,6 @@ struct SgFov {
 #ifdef __cplusplus
 extern "C" {
 #endif
-// ONE persistent kernel for everything k_power_few left: the 16-entry class (overflow slots), the 8-entry class (overflow slots) and the
-// multi-flake beams of the main queue (a->back_list), in that order -- longest lists first -- from one item space; waves_per_cu persistent
-// one-wave blocks per CU; ticket: items by an atomic cursor (a->pw_count[3]) instead of striding.  cls8 / cls16: the classes' indices in
-// the tier lists, or -1.
-int sg_launch_power_all(const SgBeamArgs *a, int dtype, int cls8, int cls16, int waves_per_cu, int ticket, void *stream);
 // compact input: (x, y, z, intensity) float32 rows + channel bytes -> (x, y, z, intensity, channel) float32 rows
 int sg_launch_expand_rows(const void *xyzi, const uint8_t *ch, void *rows, int64_t n, void *stream);
 int sg_launch_sort(const void *rows, int dtype, const int64_t *frame_off, int n_frames, int64_t n_total,
@@ -213,15 +200,14 @@ int sg_launch_sort(const void *rows, int dtype, const int64_t *frame_off, int n_
 // a caller-supplied permutation: the sorted copy by a plain gather, every frame flagged unsorted
 int sg_launch_gather_rows(const void *rows, int dtype, const int64_t *frame_off, int n_frames, int64_t n_total, int64_t max_frame,
                           const int32_t *perm, void *srows, int32_t *frame_unsorted, int32_t *status, void *stream);
-// direct == 1: the pass over all rows (dict hand-over to sg_launch_power); else list mode over class a->cls,
-// dict_only == 1: hand the dicts to sg_launch_power_list, 0: received power in place
-int sg_launch_beams(const SgBeamArgs *args, int dtype, int lmax, int direct, int dict_only, void *stream);
+// direct == 1: the pass over all rows (dict hand-over to sg_launch_power); else list mode over class a->cls, received power in place
+int sg_launch_beams(const SgBeamArgs *args, int dtype, int lmax, int direct, void *stream);
 int sg_launch_power(const SgBeamArgs *args, int dtype, int lmax, void *stream, int plan_only /* 1: k_power_plan alone; 0: the kernels it feeds */,
                     void *ev_few /* hipEvent_t recorded behind k_power_few, or null */, int which /* 1: k_power_few alone, 2: k_power alone, 3: both */);
 int sg_launch_tier_gather(const SgBeamArgs *args, void *stream);
 int sg_launch_power_list(const SgBeamArgs *args, int dtype, int lmax, void *stream);
 int sg_launch_huge(const SgBeamArgs *args, int dtype, void *stream);
-// the scan of a later tier without LDS lists: hits go to the tier's hand-over buffer in scan order (args->tq_unsorted must be 1 for its k_power)
+// the scan of a later tier without LDS lists: hits go to the tier's hand-over buffer in scan order (its k_power sorts them as it loads)
 int sg_launch_tier_scan(const SgBeamArgs *args, int dtype, int lmax, void *stream);
 // class args->cls of the tier lists (capacity lmax) as a row kernel: G lanes per beam, scan + dict + received power in one pass
 int sg_launch_rows(const SgBeamArgs *args, int dtype, int lmax, void *stream);

@@ -219,24 +219,17 @@ struct snowgpu_ctx {
     DevBuf<uint16_t> dq_sc;
     DevBuf<unsigned long long> qn;    // per region: front | back << 32
     DevBuf<int2_t> pw_items;          // work items of k_power
-    DevBuf<int32_t> back_list, bbase; // k_power_all: the multi-flake beams of all regions closed up; where each region's run goes
     DevBuf<double> ov;                // overflow slots of the pass over all rows (SG_OV_STRIDE doubles per sorted position)
     DevBuf<uint16_t> ov_sc;
     DevBuf<int32_t> tier_list, tier_sparse, tbase, redo_list;
     DevBuf<double> tq[SG_MAX_CLASSES];        // dict hand-over buffers of the list-mode tiers
     DevBuf<uint16_t> tq_sc[SG_MAX_CLASSES];
     DevBuf<double> h_lists;           // global-list tier: per-lane lists
-    bool linear_order = false;   // experiments: SNOWGPU_LINEAR_ORDER=1 keeps the first pass in sorted-row order
     int64_t tier_cap_override = 0;    // tests: SNOWGPU_TIER_CAP=<entries> shrinks the hand-over buffers (in-place fallback runs)
     int first_tier_override = 0;      // tests: SNOWGPU_FIRST_TIER=4|8|16|63
     int few = 2;                      // SNOWGPU_FEW=0..3: beams with up to this many flakes go through k_power_few (0: all through k_power)
-    int kp_all = 0;                   // SNOWGPU_KP_ALL=1: large batches run ONE work queue / persistent kernel (k_power_all) for what k_power_few leaves instead of k_power<4> / <8> / <16> side by side (A/B; same bytes)
-    int kp_all_waves = 6;             // SNOWGPU_KP_ALL_WAVES: persistent one-wave blocks of k_power_all per CU (8 fit; the prepass runs beside it)
-    int kp_all_ticket = 0;            // SNOWGPU_KP_ALL_TICKET=1: its waves draw items from an atomic cursor instead of striding
     int heavy_tail = -1;              // SNOWGPU_HEAVY_TAIL=0 / 1: never / always the long-tail order of the received-power phase (default: by the last batches' tier counts)
-    int per_lane_scan = 0;            // experiments / validation: SNOWGPU_PER_LANE_SCAN=-1 wave scan in the tiers too
-    bool tier_rows_auto = true;       // row kernels for the tiers of small batches (SNOWGPU_TIER_ROWS=0 switches that off too)
-    bool tier_rows = false;           // SNOWGPU_TIER_ROWS=1: the later tiers as row kernels (snowgpu_rows.hip: G lanes per beam) -- measured slower, kept for A/B
+    int tier_rows = -1;               // SNOWGPU_TIER_ROWS=1 / 0: always / never the later tiers as row kernels (snowgpu_rows.hip: G lanes per beam; default: small batches only)
     hipStream_t lane_stream[3] = {nullptr, nullptr, nullptr};     // snowgpu_lane_stream: one per priority level, made on demand
     int stats_early = -1;             // SNOWGPU_STATS_EARLY=0 / 1: the prepass' per-tile statistics inside the sort's first pass / as a kernel of their own on the prepass stream (default: the latter for batches of more than 16 frames)
     int prepass_with_few = -1;        // SNOWGPU_PREPASS_WITH_FEW=0 / 1: never / always start the prepass beside k_power_few (default: long-tail batches only)
@@ -423,7 +416,6 @@ extern "C" int snowgpu_create(int device, snowgpu_ctx **out)
     if (hipGetDeviceCount(&n) != hipSuccess || device < 0 || device >= n) return SNOWGPU_E_NO_DEVICE;
     snowgpu_ctx *ctx = new snowgpu_ctx();
     ctx->device = device;
-    { const char *lo = std::getenv("SNOWGPU_LINEAR_ORDER"); ctx->linear_order = lo && lo[0] == '1'; }
     *out = ctx;   // hand the context back even on failure so that last_error is readable
     HIPCHK(ctx, hipSetDevice(device));
     { const char *v = std::getenv("SNOWGPU_TIER_CAP"); ctx->tier_cap_override = v ? std::atoll(v) : 0; }
@@ -433,11 +425,7 @@ extern "C" int snowgpu_create(int device, snowgpu_ctx **out)
     { const char *v = std::getenv("SNOWGPU_SERIAL"); ctx->serial = v && v[0] == '1'; }
     { const char *v = std::getenv("SNOWGPU_STATS_EARLY"); ctx->stats_early = v ? (v[0] == '1' ? 1 : 0) : -1; }
     { const char *v = std::getenv("SNOWGPU_PREPASS_WITH_FEW"); ctx->prepass_with_few = v ? (v[0] == '1' ? 1 : 0) : -1; }
-    { const char *v = std::getenv("SNOWGPU_KP_ALL"); if (v) ctx->kp_all = v[0] != '0'; }
-    { const char *v = std::getenv("SNOWGPU_KP_ALL_WAVES"); if (v) ctx->kp_all_waves = std::min(std::max(std::atoi(v), 1), 8); }
-    { const char *v = std::getenv("SNOWGPU_KP_ALL_TICKET"); if (v) ctx->kp_all_ticket = v[0] == '1'; }
-    { const char *v = std::getenv("SNOWGPU_PER_LANE_SCAN"); ctx->per_lane_scan = v ? std::atoi(v) : 0; }
-    { const char *v = std::getenv("SNOWGPU_TIER_ROWS"); ctx->tier_rows = v && v[0] == '1'; ctx->tier_rows_auto = !v; }
+    { const char *v = std::getenv("SNOWGPU_TIER_ROWS"); ctx->tier_rows = v ? (v[0] == '1' ? 1 : 0) : -1; }
     // In a process that has loaded PyTorch's HIP runtime layer the runtime moves device-to-host copies with a full-grid blit
     // kernel, which stalls whatever computes beside it: one lane and larger chunks lose least there (1.8 instead of 1.3 G
     // points/s in-process).  SNOWGPU_PIPE_LANES / snowgpu_set_pipeline override either way.
@@ -492,7 +480,7 @@ extern "C" void snowgpu_destroy(snowgpu_ctx *ctx)
     ctx->seg_tbl_cnt.release(); ctx->seg_tbl_base.release(); ctx->seg_blk.release(); ctx->seg_cnt.release(); ctx->seg_frame.release();
     ctx->seg_n.release(); ctx->seg_start.release(); ctx->seg_of_blk.release(); ctx->chunk_blk.release();
     ctx->rec.release(); ctx->rec_q.release(); ctx->rng.release(); ctx->dq.release(); ctx->dq_g.release(); ctx->dq_sc.release(); ctx->qn.release(); ctx->pw_items.release(); ctx->ov.release(); ctx->ov_sc.release();
-    ctx->redo_list.release(); ctx->back_list.release(); ctx->bbase.release(); ctx->rows_c4.release(); ctx->rows_ch.release();
+    ctx->redo_list.release(); ctx->rows_c4.release(); ctx->rows_ch.release();
     ctx->tier_list.release(); ctx->tier_sparse.release(); ctx->tbase.release(); ctx->h_lists.release();
     for (int k = 0; k < SG_MAX_CLASSES; ++k) { ctx->tq[k].release(); ctx->tq_sc[k].release(); }
     ctx->ctile_cnt.release(); ctx->ctile_base.release(); ctx->table_ids.release(); ctx->out_src.release();
@@ -925,7 +913,7 @@ static int run_batch(snowgpu_ctx *ctx, BatchDev &b)
     int tiers[4], n_tiers = 0;
     choose_tiers(R, b.beam_div_deg, tiers, &n_tiers);
     const int first_block = sg_beams_block(tiers[0]);
-    const bool use_seg = !b.perm && !R->linear_order && R->tables.size() <= 65536 && b.n_frames <= (1 << 22)
+    const bool use_seg = !b.perm && R->tables.size() <= 65536 && b.n_frames <= (1 << 22)
                          && b.n_total < ((int64_t)1 << 31);
     if (use_seg) {
         const size_t P = (size_t)b.n_frames * 256;
@@ -997,16 +985,14 @@ static int run_batch(snowgpu_ctx *ctx, BatchDev &b)
     a.rng = ctx->rng.p;
     a.dbg_count = b.dbg_count; a.dbg_rj = b.dbg_rj; a.dbg_ratio = b.dbg_ratio; a.dbg_cap = b.dbg_cap;
     a.exact_math = R->exact_math;
-    a.per_lane_scan = R->per_lane_scan;
     // Later capacity tiers = classes of the tier lists; the last class is the global-list tier, whose lists hold a whole
     // table if need be (capped at 8192 flakes in one beam).
     const int n_cls = n_tiers;
     // Small batches (up to four sweeps): a tier holds a few hundred beams -- one or two waves' worth for one beam per lane, a chain of
     // dependent latencies 100 us long -- and the row kernels (snowgpu_rows.hip: G lanes per beam; scan, dict and received power in one
     // pass, no hand-over buffers) finish them in a third of that (0.334 -> 0.306 ms per single sweep); from 16 sweeps on they lose
-    // (2-3x the instructions).  SNOWGPU_TIER_ROWS=1 / 0 forces either (tests/test_gpu_parity.py::test_tier_rows_switch).
-    const bool rows_small = R->tier_rows_auto && b.n_total <= ((int64_t)1 << 19);
-    const bool tier_rows = (R->tier_rows || rows_small) && R->tier_cap_override <= 0 && R->per_lane_scan >= 0;
+    // (2-3x the instructions).  SNOWGPU_TIER_ROWS=1 / 0 forces either (tests/test_gpu_parity.py::test_remaining_environment_switches_change_no_byte).
+    const bool tier_rows = (R->tier_rows < 0 ? b.n_total <= ((int64_t)1 << 19) : R->tier_rows == 1) && R->tier_cap_override <= 0;
     const int h_lanes = 256;
     const int h_cap = (int)std::min<uint32_t>(std::max<uint32_t>(R->max_flakes, 64u), 8192u);
     a.n_cls = n_cls;
@@ -1022,7 +1008,7 @@ static int run_batch(snowgpu_ctx *ctx, BatchDev &b)
     // Overflow slots: a beam of the pass over all rows that over-fills its LDS list, up to SG_OV_CAP flakes, leaves all of them in
     // the slot of its sorted position, and the tiers up to that capacity run no second scan (400 bytes per sorted position, touched
     // by the few per cent of beams that overflow: 13 GB of address space for a 256-sweep batch, 0.6 GB per chunk of the pipeline).
-    const bool use_ov = tiers[0] < SG_OV_CAP && n_cls >= 2 && R->per_lane_scan >= 0 && !tier_rows &&
+    const bool use_ov = tiers[0] < SG_OV_CAP && n_cls >= 2 && !tier_rows &&
                         R->tier_cap_override <= 0 && n * SG_OV_STRIDE * sizeof(double) <= ((size_t)40 << 30);
     int64_t tq_caps[SG_MAX_CLASSES] = {0, 0, 0, 0};
     for (int k = 0; k + 1 < n_cls && !tier_rows; ++k) {
@@ -1068,17 +1054,6 @@ static int run_batch(snowgpu_ctx *ctx, BatchDev &b)
         a.seg_n = ctx->seg_n.p; a.seg_of_blk = ctx->seg_of_blk.p; a.chunk_blk = ctx->chunk_blk.p;
     }
     const bool few_first = a.pw_items1 && !serial && b.n_total > ((int64_t)1 << 19);
-    // Large batches: ONE work queue and ONE persistent kernel (k_power_all) for everything k_power_few leaves -- the 16-entry class, the
-    // 8-entry class (both from the overflow slots) and the multi-flake beams of the main queue, closed up over all regions -- instead of
-    // k_power<4> / <8> / <16> side by side on three streams, each with a grid sized for a chip of its own.
-    int cls8 = -1, cls16 = -1;
-    for (int k = 0; k + 1 < n_cls; ++k) { if (tiers[k + 1] == 8) cls8 = k; if (tiers[k + 1] == 16) cls16 = k; }
-    const bool kp_all = R->kp_all && few_first && use_ov && tiers[0] == 4 && !b.dbg_count && !tier_rows && b.n_total < ((int64_t)1 << 31);
-    if (kp_all) {
-        ENSURE(ctx, ctx->back_list, n + 64);
-        ENSURE(ctx, ctx->bbase, regions);
-        a.back_list = ctx->back_list.p; a.bbase = ctx->bbase.p;
-    }
     // Where k_power<4> goes when the rare tiers are not rare.  The 63-entry and the global-list tier run behind k_power on its stream; with
     // 71 000 beams in them (C1: 40 k flakes per line) that chain -- 3.8 ms -- is the last thing to finish, and it only starts when k_power is
     // through.  The device leaves every batch's tier counts in page-locked memory (k_tier_gather); if the most recent ones that have landed
@@ -1108,19 +1083,12 @@ static int run_batch(snowgpu_ctx *ctx, BatchDev &b)
             a.blk_lo = 0; a.blk_hi = lin_blocks;
             a.grid_blocks = lin_blocks;
         }
-        e = sg_launch_beams(&a, b.dtype, tiers[0], 1, 1, st);
+        e = sg_launch_beams(&a, b.dtype, tiers[0], 1, st);
         // The plan of what the pass queued (work items of k_power_few / k_power; where each region's slice of the tier lists goes)
         // runs behind it on the same stream -- the tiers then start with one short kernel (k_tier_gather) and no hop between streams --
         // and the received-power kernels it feeds on a side stream, next to the later capacity tiers.
         if (!e) e = sg_launch_power(&a, b.dtype, tiers[0], st, 1, nullptr, 3);
-        if (!e && kp_all) {
-            // One work queue: the lists are closed up AHEAD of k_power_few (beside it, k_tier_gather's 4096 short blocks sat on the CUs when
-            // k_power_few's persistent blocks arrived; those that found no room started when others had ended and walked their whole share
-            // then: 0.78 instead of 0.54 ms), and k_power_few stays on the caller's stream -- it has the chip to itself anyway; what runs
-            // beside k_power_all (the 63-entry / global-list chain, the prepass) forks behind it.
-            e = sg_launch_tier_gather(&a, st);
-            if (!e) e = sg_launch_power(&a, b.dtype, tiers[0], st, 0, ctx->ev_few, 1);
-        } else if (!e) {
+        if (!e) {
             HIPCHK(ctx, hipEventRecord(ctx->ev_fp, st));
             HIPCHK(ctx, hipStreamWaitEvent(s_aux, ctx->ev_fp, 0));
             e = sg_launch_power(&a, b.dtype, tiers[0], s_aux, 0, few_first ? ctx->ev_few : nullptr, heavy_tail ? 1 : 3);
@@ -1137,9 +1105,9 @@ static int run_batch(snowgpu_ctx *ctx, BatchDev &b)
             // 0.11 ms) and stand in the chain's way -- C1 7.39 -> 7.14 ms; where the tail is short the prepass is better off behind
             // k_power_few (C2 3.91 -> 3.95 the other way, C2far the same).  SNOWGPU_PREPASS_WITH_FEW=0 / 1 overrides.
             const bool pre_with_few = R->prepass_with_few < 0 ? heavy_tail : R->prepass_with_few == 1;
-            if (pre_with_few && few_first && !kp_all && !b.thr_poly && !b.defer_thr && !pre_forked) { int prc = launch_prepass(); if (prc) return prc; }
-            if (few_first && !kp_all) HIPCHK(ctx, hipStreamWaitEvent(st, ctx->ev_few, 0));
-            if (!kp_all) e = sg_launch_tier_gather(&a, st);
+            if (pre_with_few && few_first && !b.thr_poly && !b.defer_thr && !pre_forked) { int prc = launch_prepass(); if (prc) return prc; }
+            if (few_first) HIPCHK(ctx, hipStreamWaitEvent(st, ctx->ev_few, 0));
+            e = sg_launch_tier_gather(&a, st);
         }
     }
     if (e) return fail(ctx, SNOWGPU_E_HIP, std::string("beam launch: ") + hipGetErrorString((hipError_t)e));
@@ -1157,13 +1125,8 @@ static int run_batch(snowgpu_ctx *ctx, BatchDev &b)
     const bool tail_aux = n_cls >= 3 && !serial && !tail_main;
     if (side3) { HIPCHK(ctx, hipEventRecord(ctx->ev_lists, st)); HIPCHK(ctx, hipStreamWaitEvent(s_aux3, ctx->ev_lists, 0)); }
     if (tail_aux) HIPCHK(ctx, hipStreamWaitEvent(s_aux, ctx->ev_lists, 0));
-    if (heavy_tail && !kp_all) {                         // (behind the event the other tiers' streams wait for: they start with it, not after it)
+    if (heavy_tail) {                                    // (behind the event the other tiers' streams wait for: they start with it, not after it)
         e = sg_launch_power(&a, b.dtype, tiers[0], st, 0, nullptr, 2);
-    }
-    if (kp_all) {
-        a.seg_blk = nullptr; a.tq = nullptr; a.tq_sc = nullptr; a.tq_cap = 0; a.tq_unsorted = 0;
-        a.work_lo = 0; a.work_hi = (int32_t)std::min<int64_t>(b.n_total, INT32_MAX);
-        e = sg_launch_power_all(&a, b.dtype, cls8, cls16, R->kp_all_waves, R->kp_all_ticket, st);
     }
     // what the classes held in a recent batch (page-locked words the device leaves behind, scaled to this batch's size): grids of the rare tiers
     int32_t cls_hint[SG_MAX_CLASSES] = {0, 0, 0, 0};
@@ -1175,7 +1138,6 @@ static int run_batch(snowgpu_ctx *ctx, BatchDev &b)
                 cls_hint[k] = (int32_t)std::min<int64_t>(INT32_MAX / 8, ((int64_t)hint[k] * ((b.n_total >> 10) + 1)) / then_k + 64);
     }
     for (int k = 0; k < n_cls && !e; ++k) {
-        if (kp_all && (k == cls8 || k == cls16)) continue;            // (taken by k_power_all)
         a.work_hint = k >= 2 ? cls_hint[k] : 0;
         hipStream_t sk = (k == 0 || (tail_main && k >= 2)) ? st : ((tail_aux && k >= 2) ? s_aux : s_aux3);
         a.seg_blk = nullptr;
@@ -1186,7 +1148,7 @@ static int run_batch(snowgpu_ctx *ctx, BatchDev &b)
         }
         const int lmax = tiers[k + 1];
         if (use_ov && lmax <= SG_OV_CAP) {               // its lists are in the overflow slots: received power only, no second scan
-            a.tq = nullptr; a.tq_sc = nullptr; a.tq_cap = 0; a.ov_list = 1; a.tq_unsorted = 0;
+            a.tq = nullptr; a.tq_sc = nullptr; a.tq_cap = 0; a.ov_list = 1;
             a.work_lo = 0; a.work_hi = (int32_t)std::min<int64_t>(b.n_total, INT32_MAX);
             e = sg_launch_power_list(&a, b.dtype, lmax, sk);
             a.ov_list = 0;
@@ -1199,13 +1161,11 @@ static int run_batch(snowgpu_ctx *ctx, BatchDev &b)
         }
         a.tq = ctx->tq[k].p; a.tq_sc = ctx->tq_sc[k].p; a.tq_cap = (int32_t)tq_caps[k];
         a.work_lo = 0; a.work_hi = (int32_t)tq_caps[k];
-        a.tq_unsorted = 0;
-        if (R->per_lane_scan < 0) e = sg_launch_beams(&a, b.dtype, lmax, 0, 1, sk);   // the wave scan in the tiers too: lists sorted in LDS (validation)
-        else { a.tq_unsorted = 1; e = sg_launch_tier_scan(&a, b.dtype, lmax, sk); }   // one beam per lane, no LDS: k_power sorts as it loads
+        e = sg_launch_tier_scan(&a, b.dtype, lmax, sk);                  // one beam per lane, no LDS: k_power sorts as it loads
         if (!e) e = sg_launch_power_list(&a, b.dtype, lmax, sk);
         if (!e && tq_caps[k] < b.n_total) {              // entries beyond the hand-over buffer: received power in place
             a.work_lo = (int32_t)tq_caps[k]; a.work_hi = (int32_t)std::min<int64_t>(b.n_total, INT32_MAX);
-            e = sg_launch_beams(&a, b.dtype, lmax, 0, 0, sk);
+            e = sg_launch_beams(&a, b.dtype, lmax, 0, sk);
         }
     }
     if (e) return fail(ctx, SNOWGPU_E_HIP, std::string("tier launch: ") + hipGetErrorString((hipError_t)e));

@@ -288,34 +288,34 @@ __device__ __forceinline__ int64_t sg_qaddr(int64_t slot, int plane)
 
 // ------------------------------------------------------------------------------------------------
 // The per-beam kernel.  Dynamic LDS: per-thread lists, strided by the block size -- four of LMAX + 1 float64 entries where phases 1-3 run
-// in place, three of LMAX where the list is handed on, and in the pass over all rows one float64 (range) and one 4-byte word per entry.
-//   DICT          0: phases 1-3 in place; 1: the list is handed to k_power; 2: as 1, every distance test by the reference's expression
-//                 (exact-math mode of the pass over all rows: see sg_beam.h, sg_near_ray).
+// in place, and in the pass over all rows one float64 (range) and one 4-byte word per entry.
+//   DICT          0: phases 1-3 in place (list mode); 1: the list is handed to k_power; 2: as 1, every distance test by the reference's
+//                 expression (exact-math mode of the pass over all rows: see sg_beam.h, sg_near_ray).
 //   LIST = false  direct mode, the pass over all rows: phase 1 (scan).  A beam without flakes is
 //                 finished (record written); a beam with flakes hands its flake list to k_power (which builds the dict: phase 2) through its region's slice
 //                 of the dict queue; a beam with more flakes than the list holds is appended to the list of the capacity tier that
 //                 takes all of them (the scan counts on, so the count is exact).
-//   LIST = true   a later capacity tier over its class of the tier lists; DICT = true: dict hand-over to
-//                 k_power<.., LISTQ> (entry i of the class -> slot i), DICT = false: phases 1-3 in place (the entries
-//                 beyond the hand-over buffer).  A fixed grid strides over the list, whose length only the device knows.
+//   LIST = true   a later capacity tier over its class of the tier lists, phases 1-3 in place: the entries beyond the hand-over
+//                 buffer of k_tier_scan_direct.  A fixed grid strides over the list, whose length only the device knows.
 //   BLOCK         beams per block = stride of the LDS lists.  BLOCK = 16 (the 63-entry tier) still launches one wave: 16
 //                 live lanes, 32 KB of LDS per block instead of 131 KB -- a block that needs most of a CU's LDS waits until
 //                 one has drained, and meanwhile holds up everything queued behind it.
 template <typename T, int LMAX, int BLOCK, bool LIST, int DICT>
 __global__ __launch_bounds__(BLOCK < 64 ? 64 : BLOCK, (!LIST && DICT == 1 && BLOCK == 256) ? SG_FP_WAVES : 1) void k_beams(SgBeamArgs a)
 {
+    static_assert(!LIST || DICT == 0, "a list-mode pass runs phases 1-3 in place");
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    // hand-over passes keep three LMAX-entry lists (interval angles, range); the in-place passes four of LMAX + 1 entries
+    // the hand-over pass keeps LMAX-entry lists; the in-place passes four of LMAX + 1 entries
     // (the dict and the scatterer list of phase 3 carry the hard target as entry n_flakes <= LMAX)
     constexpr int ROWS = DICT ? LMAX : LMAX + 1;
     // the pass over all rows keeps ONE word per listed flake instead of its two interval angles (sg_beam.h: sg_wave_scan, COMPACT): ranges,
     // words, scan order, counts, bin starts = 19 KB per 256 beams (three double columns: 31 KB, and a fifth of the waves the registers allow)
-    constexpr bool COMPACT = !LIST && DICT != 0;
+    constexpr bool COMPACT = DICT != 0;
     double *s_rho = COMPACT ? (double *)smem : (double *)smem + 2 * ROWS * BLOCK;
     double *s_a1 = COMPACT ? s_rho + ROWS * BLOCK : (double *)smem;       // COMPACT: the words (uint32_t), half a double column
     double *s_a2 = COMPACT ? nullptr : s_a1 + ROWS * BLOCK;
     double *s_ratio = DICT ? nullptr : s_rho + ROWS * BLOCK;
-    int *s_cnt = DICT ? (COMPACT ? (int *)(reinterpret_cast<uint32_t *>(s_a1) + ROWS * BLOCK) : (int *)(s_rho + ROWS * BLOCK)) : nullptr;   // wave scan: flakes met per beam ...
+    int *s_cnt = DICT ? (int *)(reinterpret_cast<uint32_t *>(s_a1) + ROWS * BLOCK) : nullptr;     // wave scan: flakes met per beam ...
     int *s_key = DICT ? s_cnt + (BLOCK < 64 ? 64 : BLOCK) : nullptr;      // ... and the scan order of the stored ones
     int *s_st = DICT ? s_key + LMAX * BLOCK : nullptr;                    // ... and where its two bins start (two ints per lane)
     int *s_mark = DICT ? s_st + 2 * (BLOCK < 64 ? 64 : BLOCK) : nullptr;  // ... and the owner marks of a trip of its pair loop (sg_pair_owner)
@@ -409,42 +409,28 @@ __global__ __launch_bounds__(BLOCK < 64 ? 64 : BLOCK, (!LIST && DICT == 1 && BLO
     if constexpr (DICT) {
         // The pass over all rows scans as a wave (every lane takes part, whether it has a beam or not): its beams' lists
         // differ 20-fold in length.  The later tiers hold beams with long lists of similar length; one beam per lane is a
-        // little faster there (measured 0.37 vs 0.41 ms for tier 8).
-        if (LIST && a.per_lane_scan >= 0) {
-            if (act) L = sg_beam_scan<T, LMAX, BLOCK>(px, py, pz, tab, a.beam_div_deg, s_a1, s_a2, s_rho, tid, o, d_t, theta_c, a.exact_math != 0);
-        } else {
-            // overflow slot of this block's column 0 (sorted positions follow the columns) -- the pass over all rows only
-            double *ov_blk = nullptr;
-            if constexpr (!LIST) {
-                if (a.ov_cap > 0) ov_blk = a.ov + (size_t)(seg_f >= 0 ? q_base + (blk - seg_blk0) * BLOCK : chunk) * SG_OV_STRIDE;
-            }
-            // DICT == 1: distance tests too close to call are not decided here (sg_beam.h: sg_near_ray); DICT == 2 (exact-math mode) and the
-            // wave scan in a tier: every test by the reference's expression, in place
-            L = sg_wave_scan<T, LMAX, BLOCK, !LIST && DICT == 1, COMPACT>(act, px, py, pz, tab, a.beam_div_deg, s_a1, s_a2, s_rho, s_cnt, s_key, s_st, tid, o, d_t, theta_c,
-                                                                          a.exact_math != 0, ov_blk, ov_blk ? a.ov_cap : 0, s_mark);
-            if (ov_blk && act && o.overflow && o.n_hits <= a.ov_cap) {   // header and the flakes the LDS list holds: the slot is complete
-                double *sp = ov_blk + (size_t)tid * SG_OV_STRIDE;
-                sp[0] = (double)d_t; sp[1] = theta_c;
-                if constexpr (COMPACT) {
-                    double th_r, th_l;
-                    sg_beam_limits(theta_c, a.beam_div_deg, th_r, th_l);
+        // little faster there (k_tier_scan_direct; measured 0.37 vs 0.41 ms for tier 8).
+        // overflow slot of this block's column 0 (sorted positions follow the columns)
+        double *ov_blk = nullptr;
+        if (a.ov_cap > 0) ov_blk = a.ov + (size_t)(seg_f >= 0 ? q_base + (blk - seg_blk0) * BLOCK : chunk) * SG_OV_STRIDE;
+        // DICT == 1: distance tests too close to call are not decided here (sg_beam.h: sg_near_ray); DICT == 2 (exact-math mode): every
+        // test by the reference's expression, in place
+        L = sg_wave_scan<T, LMAX, BLOCK, DICT == 1, COMPACT>(act, px, py, pz, tab, a.beam_div_deg, s_a1, s_a2, s_rho, s_cnt, s_key, s_st, tid, o, d_t, theta_c,
+                                                             a.exact_math != 0, ov_blk, ov_blk ? a.ov_cap : 0, s_mark);
+        if (ov_blk && act && o.overflow && o.n_hits <= a.ov_cap) {   // header and the flakes the LDS list holds: the slot is complete
+            double *sp = ov_blk + (size_t)tid * SG_OV_STRIDE;
+            sp[0] = (double)d_t; sp[1] = theta_c;
+            double th_r, th_l;
+            sg_beam_limits(theta_c, a.beam_div_deg, th_r, th_l);
 #pragma unroll
-                    for (int j = 0; j < LMAX; ++j) {
-                        double x1, x2;
-                        sg_hit_angles(reinterpret_cast<const uint32_t *>(s_a1)[j * BLOCK + tid], tab.entries, th_r, th_l, x1, x2);
-                        sp[2 + 3 * j] = x1; sp[3 + 3 * j] = x2; sp[4 + 3 * j] = s_rho[j * BLOCK + tid];
-                    }
-                } else {
-                    for (int j = 0; j < LMAX; ++j) {
-                        sp[2 + 3 * j] = s_a1[j * BLOCK + tid]; sp[3 + 3 * j] = s_a2[j * BLOCK + tid]; sp[4 + 3 * j] = s_rho[j * BLOCK + tid];
-                    }
-                }
-                a.ov_sc[g] = (uint16_t)(o.n_hits | (ch << 8));
+            for (int j = 0; j < LMAX; ++j) {
+                double x1, x2;
+                sg_hit_angles(reinterpret_cast<const uint32_t *>(s_a1)[j * BLOCK + tid], tab.entries, th_r, th_l, x1, x2);
+                sp[2 + 3 * j] = x1; sp[3 + 3 * j] = x2; sp[4 + 3 * j] = s_rho[j * BLOCK + tid];
             }
+            a.ov_sc[g] = (uint16_t)(o.n_hits | (ch << 8));
         }
-        if constexpr (!LIST) {
-            if (act && a.rng) ((T *)a.rng)[g] = d_t;  // simulation.py:89, for the noise-floor pass (:465-469, :518-520)
-        }
+        if (act && a.rng) ((T *)a.rng)[g] = d_t;      // simulation.py:89, for the noise-floor pass (:465-469, :518-520)
         if (act) {
             o.has_power = !o.overflow && L > 0;       // k_power builds the dict (phase 2) and everything after it
             if (!o.overflow && L == 0 && a.dbg_count) {   // debug tap: the dict of a clear beam is its hard target alone
@@ -503,72 +489,53 @@ __global__ __launch_bounds__(BLOCK < 64 ? 64 : BLOCK, (!LIST && DICT == 1 && BLO
         auto hand_over = [&](double *q, int64_t slot) {
             q[sg_qaddr<P>(slot, 0)] = (double)d_t;
             q[sg_qaddr<P>(slot, 1)] = theta_c;
-            if constexpr (COMPACT) {
-                // the interval angles from the words: the beam's limits, or the records' tangent angles (read here, by the few beams that
-                // listed a flake -- the records' lines are what the scan just read)
-                double th_r, th_l;
-                sg_beam_limits(theta_c, a.beam_div_deg, th_r, th_l);
-                if constexpr (LMAX <= 4) {
-                    double x1[LMAX], x2[LMAX];
-                    uint32_t hw[LMAX];
+            // the interval angles from the words: the beam's limits, or the records' tangent angles (read here, by the few beams that
+            // listed a flake -- the records' lines are what the scan just read)
+            double th_r, th_l;
+            sg_beam_limits(theta_c, a.beam_div_deg, th_r, th_l);
+            if constexpr (LMAX <= 4) {
+                double x1[LMAX], x2[LMAX];
+                uint32_t hw[LMAX];
 #pragma unroll
-                    for (int j = 0; j < LMAX; ++j) hw[j] = reinterpret_cast<const uint32_t *>(s_a1)[j * BLOCK + tid];
-                    sg_hit_angles_all<LMAX>(hw, L, tab.entries, th_r, th_l, x1, x2);
+                for (int j = 0; j < LMAX; ++j) hw[j] = reinterpret_cast<const uint32_t *>(s_a1)[j * BLOCK + tid];
+                sg_hit_angles_all<LMAX>(hw, L, tab.entries, th_r, th_l, x1, x2);
 #pragma unroll
-                    for (int j = 0; j < LMAX; ++j)
-                        if (j < L) {
-                            q[sg_qaddr<P>(slot, 2 + 3 * j)] = x1[j];
-                            q[sg_qaddr<P>(slot, 3 + 3 * j)] = x2[j];
-                            q[sg_qaddr<P>(slot, 4 + 3 * j)] = s_rho[j * BLOCK + tid];
-                        }
-                } else {
-                    for (int j = 0; j < L; ++j) {
-                        double x1, x2;
-                        sg_hit_angles(reinterpret_cast<const uint32_t *>(s_a1)[j * BLOCK + tid], tab.entries, th_r, th_l, x1, x2);
-                        q[sg_qaddr<P>(slot, 2 + 3 * j)] = x1;
-                        q[sg_qaddr<P>(slot, 3 + 3 * j)] = x2;
+                for (int j = 0; j < LMAX; ++j)
+                    if (j < L) {
+                        q[sg_qaddr<P>(slot, 2 + 3 * j)] = x1[j];
+                        q[sg_qaddr<P>(slot, 3 + 3 * j)] = x2[j];
                         q[sg_qaddr<P>(slot, 4 + 3 * j)] = s_rho[j * BLOCK + tid];
                     }
-                }
             } else {
                 for (int j = 0; j < L; ++j) {
-                    q[sg_qaddr<P>(slot, 2 + 3 * j)] = s_a1[j * BLOCK + tid];
-                    q[sg_qaddr<P>(slot, 3 + 3 * j)] = s_a2[j * BLOCK + tid];
+                    double x1, x2;
+                    sg_hit_angles(reinterpret_cast<const uint32_t *>(s_a1)[j * BLOCK + tid], tab.entries, th_r, th_l, x1, x2);
+                    q[sg_qaddr<P>(slot, 2 + 3 * j)] = x1;
+                    q[sg_qaddr<P>(slot, 3 + 3 * j)] = x2;
                     q[sg_qaddr<P>(slot, 4 + 3 * j)] = s_rho[j * BLOCK + tid];
                 }
             }
         };
-        if constexpr (!LIST) {
-            // The region's slice of the queue: beams with one flake from the front, the others from the back -- one
-            // packed 64-bit atomic per wave on the region's counter (thousands of distinct addresses: no serialisation).
-            const bool front = o.has_power && L <= a.front_max, back = o.has_power && L > a.front_max;
-            const unsigned long long mf = __ballot(front), mb = __ballot(back);
-            if (mf | mb) {
-                const int leader = __ffsll((long long)(mf | mb)) - 1;
-                unsigned long long base = 0;
-                if ((tid & 63) == leader)
-                    base = atomicAdd(&a.qn[__builtin_amdgcn_readfirstlane(region)], (unsigned long long)__popcll(mf) | ((unsigned long long)__popcll(mb) << 32));
-                const unsigned blo = __shfl((unsigned)(base & 0xffffffffull), leader), bhi = __shfl((unsigned)(base >> 32), leader);
-                if (o.has_power) {
-                    const int64_t slot = front ? q_base + (int)blo + (int)__popcll(mf & sg_lanemask_lt())
-                                               : q_base + q_size - 1 - ((int)bhi + (int)__popcll(mb & sg_lanemask_lt()));
-                    hand_over(a.dq, slot);
-                    a.dq_g[slot] = (int32_t)g;
-                    a.dq_sc[slot] = (uint16_t)(L | (ch << 8));
-                    // this row's record is a reference to its queue slot: k_power writes its result there, slot after slot
-                    // (a 4-byte store per beam scattered over the sorted positions costs a whole memory sector each)
-                    rec = SG_REC_SLOT | (uint32_t)slot;
-                }
-            }
-        } else if (live) {
-            const int64_t slot = chunk + tid;         // entry i of the class -> slot i
-            uint16_t sc = 0xffff;                     // no flake list: the record below is final
+        // The region's slice of the queue: beams with one flake from the front, the others from the back -- one
+        // packed 64-bit atomic per wave on the region's counter (thousands of distinct addresses: no serialisation).
+        const bool front = o.has_power && L <= a.front_max, back = o.has_power && L > a.front_max;
+        const unsigned long long mf = __ballot(front), mb = __ballot(back);
+        if (mf | mb) {
+            const int leader = __ffsll((long long)(mf | mb)) - 1;
+            unsigned long long base = 0;
+            if ((tid & 63) == leader)
+                base = atomicAdd(&a.qn[__builtin_amdgcn_readfirstlane(region)], (unsigned long long)__popcll(mf) | ((unsigned long long)__popcll(mb) << 32));
+            const unsigned blo = __shfl((unsigned)(base & 0xffffffffull), leader), bhi = __shfl((unsigned)(base >> 32), leader);
             if (o.has_power) {
-                hand_over(a.tq, slot);
-                sc = (uint16_t)(L | (ch << 8));
-                pending = true;
+                const int64_t slot = front ? q_base + (int)blo + (int)__popcll(mf & sg_lanemask_lt())
+                                           : q_base + q_size - 1 - ((int)bhi + (int)__popcll(mb & sg_lanemask_lt()));
+                hand_over(a.dq, slot);
+                a.dq_g[slot] = (int32_t)g;
+                a.dq_sc[slot] = (uint16_t)(L | (ch << 8));
+                // this row's record is a reference to its queue slot: k_power writes its result there, slot after slot
+                // (a 4-byte store per beam scattered over the sorted positions costs a whole memory sector each)
+                rec = SG_REC_SLOT | (uint32_t)slot;
             }
-            a.tq_sc[slot] = sc;
         }
     } else {
         // ---- phases 3b / 3c in place (s_ratio is dead after phase 3a and carries the work lists) -----------------
@@ -585,7 +552,7 @@ __global__ __launch_bounds__(BLOCK < 64 ? 64 : BLOCK, (!LIST && DICT == 1 && BLO
         }
         sg_add_diff2(a.diff2, live, f, (long long)o.diff2);
     }
-    if constexpr (!LIST && DICT) {
+    if constexpr (DICT) {
         // a beam this pass finishes itself (no flake met: label 0) carries its original intensity in the record, if that is an
         // integer in [0, 255] as in every STF sweep: together with the range above the noise-floor pass then never reads the row
         if (live && !pending && rec == 0u && act && a.rng) {
@@ -726,12 +693,6 @@ __global__ __launch_bounds__(256) void k_power_plan(SgBeamArgs a, int lanes, int
         if ((threadIdx.x & 63) == 63 && total > 0) b = atomicAdd(counter, total);
         return __shfl(b, 63) + inc - n;
     };
-    if (a.back_list) {                                // one list for k_power_all: the region's back run goes to bbase[r] (k_tier_gather copies it)
-        const int bb = reserve(nb, a.pw_count + 2);
-        if (mine) a.bbase[r] = bb;
-        n_items -= (nb + lanes_back - 1) / lanes_back;
-        nb = 0;                                       // (no per-region items for the back runs)
-    }
     int base = reserve(n_items, a.pw_count);
     if (a.pw_items1) {
         int base1 = reserve(n_one, a.pw_count + 1);
@@ -762,12 +723,6 @@ __global__ __launch_bounds__(256) void k_tier_gather(SgBeamArgs a, int n_regions
         int32_t *dst = a.tier_list + (int64_t)k * a.tier_stride + a.tbase[(int64_t)r * SG_MAX_CLASSES + k];
         for (int i = lane; i < c; i += 64) dst[i] = src[i];
     }
-    if (a.back_list) {                                // the region's multi-flake beams: the last nb slots of its slice of the queue
-        const int nb = (int)(a.qn[r] >> 32);
-        int32_t *dst = a.back_list + a.bbase[r];
-        const int first = (int)(q_base + q_size - nb);
-        for (int i = lane; i < nb; i += 64) dst[i] = first + i;
-    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -778,15 +733,13 @@ __global__ __launch_bounds__(256) void k_tier_gather(SgBeamArgs a, int n_regions
 //                  window of SG_KP_WIN x 64 multi-flake slots)
 //   LISTQ = true   a list-mode pass's hand-over buffer: item i = window i of the class
 // ONE work item of the received-power phase: `cnt` hand-over slots from `start` on (a run of live slots of the direct-mode queue, LISTQ = false;
-// a window of a list-mode class, LISTQ = true, whose lists lie in the overflow slots (ov_list) or in the class' hand-over buffer, in scan
-// order if tq_unsorted), by the calling WAVE, whose LDS columns start at `smem` (BLOCK >= 64: the block's columns, the wave takes its 64).
-// item_f: the item's frame (direct-mode items carry it), or -1.  Called by k_power -- one capacity per launch -- and by k_power_all, where a
-// wave takes items of any capacity from one list.
+// a window of a list-mode class, LISTQ = true, whose lists lie in the overflow slots (ov_list) or in the class' hand-over buffer -- either way
+// in scan order), by the calling WAVE, whose LDS columns start at `smem` (BLOCK >= 64: the block's columns, the wave takes its 64).
+// item_f: the item's frame (direct-mode items carry it), or -1.
 template <typename T, int LMAX, int BLOCK, bool LISTQ>
-__device__ __forceinline__ void sg_kp_item(const SgBeamArgs &a, char *smem, const int ov_list, const int tq_unsorted, const int64_t work_off,
-                                           const int start, const int cnt, const int item_f, const int32_t *__restrict__ slot_list = nullptr)
+__device__ __forceinline__ void sg_kp_item(const SgBeamArgs &a, char *smem, const int ov_list, const int64_t work_off,
+                                           const int start, const int cnt, const int item_f)
 {
-    // slot_list (LISTQ = false): the item is entries [start, start + cnt) of this list of queue slots (k_power_all: the closed-up back runs)
     constexpr int LANES = BLOCK < 64 ? BLOCK : 64;
     constexpr int WIN = BLOCK < 64 ? 1 : SG_KP_WIN;       // waves' worth of slots per work item
     constexpr int P = SG_QPLANES(LMAX);
@@ -826,10 +779,6 @@ __device__ __forceinline__ void sg_kp_item(const SgBeamArgs &a, char *smem, cons
 #pragma unroll
                 for (int r = 0; r < WIN; ++r) scw[r] = (unsigned)a.ov_sc[at[r]];
             } else {
-                if (!LISTQ && slot_list) {
-#pragma unroll
-                    for (int r = 0; r < WIN; ++r) at[r] = (int64_t)slot_list[at[r]];
-                }
 #pragma unroll
                 for (int r = 0; r < WIN; ++r) scw[r] = (unsigned)scs[at[r]];
             }
@@ -870,8 +819,7 @@ __device__ __forceinline__ void sg_kp_item(const SgBeamArgs &a, char *smem, cons
                 for (int q = 0; q < WIN; ++q) if (q == r) pos = perm[q];
             }
         }
-        int64_t slot = (int64_t)start + pos;
-        if constexpr (!LISTQ) { if (slot_list && in) slot = slot_list[slot]; }
+        const int64_t slot = (int64_t)start + pos;
         unsigned sc = 0xffffu;
         int32_t g = 0;
         double d = 0.0, tc = 0.0, f_a1 = 0.0, f_a2 = 0.0, f_rho = 0.0;
@@ -899,7 +847,7 @@ __device__ __forceinline__ void sg_kp_item(const SgBeamArgs &a, char *smem, cons
             f = item_f >= 0 ? item_f : sg_frame_of(a, g);
             // ord: 4 bits per list entry -- the hit (scan order) it came from; identity unless the scan left the flakes unsorted
             unsigned long long ord = 0xfedcba9876543210ull;
-            if (LISTQ && (tq_unsorted || ov_list)) {
+            if (LISTQ) {
                 // the flakes as the scan met them: insertion by range, scan order on equal ranges (simulation.py:413-417).  The
                 // ranges pass through the ratio / range column (free until the dict); THREE: they go back to being fetched from
                 // the queue afterwards, through `ord`.
@@ -1051,66 +999,7 @@ __global__ __launch_bounds__(BLOCK < 64 ? 64 : BLOCK, LMAX <= 4 ? SG_KP_WAVES : 
             const int dy = __builtin_amdgcn_readfirstlane(d.y);
             cnt = dy & 1023; item_f = (dy >> 10) - 1;
         }
-        sg_kp_item<T, LMAX, BLOCK, LISTQ>(a, smem, a.ov_list, a.tq_unsorted, work_off, start, cnt, item_f);
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// ONE work queue for everything k_power_few left (large batches).  Rounds 2 - 5 ran k_power<4> (main queue, half of every CU), k_power<8> and
-// k_power<16> (overflow slots) as three persistent kernels on three streams: each sized its grid for a chip of its own, and whichever got
-// to a CU first kept it -- the 16-entry class' waves lived 0.1 ms of a kernel 1 ms long, the rest of which it queued for CUs
-// (profiles/r05_timeline_one_step.txt).  Here one grid of one-wave blocks takes the items of all three from one item space, longest
-// lists first (a long item started last is the tail of the phase):
-//     [0, it16)            the 16-entry class: L16 lanes per item (3 x 17 x L16 doubles of LDS: 19.6 KB at 48 lanes -- eight waves per CU)
-//     [it16, it16 + it8)   the 8-entry class: windows of SG_KP_WIN x 64 entries, taken in order of flake count
-//     [.., + it4)          the multi-flake beams of the main queue: windows of the CLOSED-UP back list (SgBeamArgs::back_list) -- per
-//                          region a back run is ~80 slots at C2, a round of 64 and a round of 16 lanes: a third of k_power<4>'s rounds
-//                          ran a quarter full
-// Items by striding, or (ticket) by an atomic cursor: a wave that drew short items takes more of them.
-struct SgKpAll {
-    int32_t cls8, cls16;         // index of the class in the tier lists, -1: none
-    int32_t ticket;
-};
-
-template <typename T, int L16>
-__global__ __launch_bounds__(64, 2) void k_power_all(SgBeamArgs a, SgKpAll u)
-{
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int WIN = SG_KP_WIN;
-    const int n_waves = (int)gridDim.x;
-    const int lane = (int)(threadIdx.x & 63);
-    int n16 = u.cls16 >= 0 ? a.tier_info[u.cls16] : 0, n8 = u.cls8 >= 0 ? a.tier_info[u.cls8] : 0;
-    if (n16 > a.work_hi) n16 = a.work_hi;
-    if (n8 > a.work_hi) n8 = a.work_hi;
-    const int n4 = a.back_list ? a.pw_count[2] : 0;
-    // (a class the resident waves take in one round of single-wave items gains nothing from windows: see k_power)
-    const int slots8 = n8 <= n_waves * 64 ? 64 : 64 * WIN, slots4 = n4 <= n_waves * 64 ? 64 : 64 * WIN;
-    const int it16 = (n16 + L16 - 1) / L16, it8 = (n8 + slots8 - 1) / slots8, it4 = (n4 + slots4 - 1) / slots4;
-    const int total = it16 + it8 + it4;
-    int i = (int)blockIdx.x;
-    if (u.ticket) {
-        int t = 0;
-        if (lane == 0) t = atomicAdd(&a.pw_count[3], 1);
-        i = __builtin_amdgcn_readfirstlane(t);
-    }
-    while (i < total) {
-        if (i < it16) {
-            const int start = i * L16;
-            sg_kp_item<T, 16, L16, true>(a, smem, 1, 0, (int64_t)u.cls16 * a.tier_stride, start, n16 - start < L16 ? n16 - start : L16, -1);
-        } else if (i < it16 + it8) {
-            const int start = (i - it16) * slots8;
-            sg_kp_item<T, 8, 64, true>(a, smem, 1, 0, (int64_t)u.cls8 * a.tier_stride, start, n8 - start < slots8 ? n8 - start : slots8, -1);
-        } else {
-            const int start = (i - it16 - it8) * slots4;
-            sg_kp_item<T, 4, 64, false>(a, smem, 0, 0, 0, start, n4 - start < slots4 ? n4 - start : slots4, -1, a.back_list);
-        }
-        if (u.ticket) {
-            int t = 0;
-            if (lane == 0) t = atomicAdd(&a.pw_count[3], 1);
-            i = __builtin_amdgcn_readfirstlane(t);
-        } else {
-            i += n_waves;
-        }
+        sg_kp_item<T, LMAX, BLOCK, LISTQ>(a, smem, a.ov_list, work_off, start, cnt, item_f);
     }
 }
 
@@ -1901,8 +1790,8 @@ static int sg_set_lds(K kernel, size_t lds, bool *attr_set)
 template <typename T, int LMAX, int BLOCK, bool LIST, int DICT>
 static int launch_beams_t(const SgBeamArgs *a, hipStream_t st)
 {
-    // (the pass over all rows: ranges + one word per listed flake; a list-mode scan: three double columns -- see k_beams)
-    const size_t lds = DICT ? (LIST ? sizeof(double) * (size_t)BLOCK * 3 * (size_t)LMAX : (sizeof(double) + sizeof(uint32_t)) * (size_t)BLOCK * (size_t)LMAX)
+    // (the pass over all rows: ranges + one word per listed flake; the in-place passes: four double columns -- see k_beams)
+    const size_t lds = DICT ? (sizeof(double) + sizeof(uint32_t)) * (size_t)BLOCK * (size_t)LMAX
                                   + sizeof(int) * (4 * (size_t)(BLOCK < 64 ? 64 : BLOCK) + (size_t)LMAX * BLOCK)
                             : sizeof(double) * (size_t)BLOCK * 4 * ((size_t)LMAX + 1);
     static bool attr_set[64] = {};
@@ -1918,7 +1807,7 @@ static int launch_beams_t(const SgBeamArgs *a, hipStream_t st)
         blocks = (unsigned)std::min<int64_t>((n + BLOCK - 1) / BLOCK, (int64_t)sg_cu_count(dev_id) * per_cu);
         // the in-place pass only sees the entries beyond the hand-over buffer, i.e. normally none: a small grid (its LDS-heavy
         // blocks would otherwise queue for CU space just to find that out)
-        if (!DICT) blocks = std::min(blocks, 128u);
+        blocks = std::min(blocks, 128u);
     } else {
         blocks = (unsigned)a->grid_blocks;               // blocks [blk_lo, blk_hi) or chunk a->chunk of the segment order
     }
@@ -1929,13 +1818,13 @@ static int launch_beams_t(const SgBeamArgs *a, hipStream_t st)
 }
 
 template <typename T, int LMAX, int BLOCK>
-static int launch_beams_m(const SgBeamArgs *a, int direct, int dict_only, hipStream_t st)
+static int launch_beams_m(const SgBeamArgs *a, int direct, hipStream_t st)
 {
     if (direct) {
         if (a->exact_math) return launch_beams_t<T, LMAX, BLOCK, false, 2>(a, st);   // (registers to spare for tangent, root and quotient in its loop)
         return launch_beams_t<T, LMAX, BLOCK, false, 1>(a, st);
     }
-    return dict_only ? launch_beams_t<T, LMAX, BLOCK, true, 1>(a, st) : launch_beams_t<T, LMAX, BLOCK, true, 0>(a, st);
+    return launch_beams_t<T, LMAX, BLOCK, true, 0>(a, st);
 }
 
 template <typename T, int LMAX, int BLOCK, bool LISTQ>
@@ -2017,20 +1906,20 @@ extern "C" int sg_launch_tier_scan(const SgBeamArgs *a, int dtype, int lmax, voi
 extern "C" int sg_beams_block(int lmax) { return lmax == 4 ? 256 : (lmax == 8 ? SG_LANES_8 : (lmax == 16 ? SG_LANES_16 : SG_LANES_63)); }
 
 // lmax = per-beam list capacity of this pass: 4 (160 B of LDS per beam: 16 waves per CU), 8, 16 or 63 (the largest
-// LDS list).  direct: the pass over all rows, dict hand-over to sg_launch_power; else list mode over class a->cls.
-extern "C" int sg_launch_beams(const SgBeamArgs *a, int dtype, int lmax, int direct, int dict_only, void *stream)
+// LDS list).  direct: the pass over all rows, dict hand-over to sg_launch_power; else list mode over class a->cls, in place.
+extern "C" int sg_launch_beams(const SgBeamArgs *a, int dtype, int lmax, int direct, void *stream)
 {
     hipStream_t st = (hipStream_t)stream;
     if (dtype == 0) {
-        if (lmax == 4) return launch_beams_m<float, 4, 256>(a, direct, dict_only, st);
-        if (lmax == 8) return launch_beams_m<float, 8, SG_LANES_8>(a, direct, dict_only, st);
-        if (lmax == 16) return launch_beams_m<float, 16, SG_LANES_16>(a, direct, dict_only, st);
-        return launch_beams_m<float, SG_LCAP, SG_LANES_63>(a, direct, dict_only, st);
+        if (lmax == 4) return launch_beams_m<float, 4, 256>(a, direct, st);
+        if (lmax == 8) return launch_beams_m<float, 8, SG_LANES_8>(a, direct, st);
+        if (lmax == 16) return launch_beams_m<float, 16, SG_LANES_16>(a, direct, st);
+        return launch_beams_m<float, SG_LCAP, SG_LANES_63>(a, direct, st);
     }
-    if (lmax == 4) return launch_beams_m<double, 4, 256>(a, direct, dict_only, st);
-    if (lmax == 8) return launch_beams_m<double, 8, SG_LANES_8>(a, direct, dict_only, st);
-    if (lmax == 16) return launch_beams_m<double, 16, SG_LANES_16>(a, direct, dict_only, st);
-    return launch_beams_m<double, SG_LCAP, SG_LANES_63>(a, direct, dict_only, st);
+    if (lmax == 4) return launch_beams_m<double, 4, 256>(a, direct, st);
+    if (lmax == 8) return launch_beams_m<double, 8, SG_LANES_8>(a, direct, st);
+    if (lmax == 16) return launch_beams_m<double, 16, SG_LANES_16>(a, direct, st);
+    return launch_beams_m<double, SG_LCAP, SG_LANES_63>(a, direct, st);
 }
 
 // the received-power kernel for the queue a direct-mode pass of capacity lmax filled
@@ -2050,30 +1939,6 @@ extern "C" int sg_launch_power(const SgBeamArgs *a, int dtype, int lmax, void *s
     if (lmax == 8) return launch_power_t<double, 8, SG_LANES_8, false>(a, st, po, ef, which);
     if (lmax == 16) return launch_power_t<double, 16, SG_LANES_16, false>(a, st, po, ef, which);
     return launch_power_t<double, SG_LCAP, SG_LANES_63, false>(a, st, po, ef, which);
-}
-
-template <typename T>
-static int launch_power_all_t(const SgBeamArgs *a, int cls8, int cls16, int waves_per_cu, int ticket, hipStream_t st)
-{
-    constexpr int L16 = 48;
-    const size_t lds = sizeof(double) * std::max<size_t>(std::max<size_t>((size_t)64 * 4 * 5, (size_t)64 * 3 * 9), (size_t)L16 * 3 * 17);
-    static bool attr_set[64] = {};
-    if (int e = sg_set_lds(k_power_all<T, L16>, lds, attr_set)) return e;
-    int dev_id = 0;
-    (void)hipGetDevice(&dev_id);
-    const int per_cu = std::max(1, std::min(waves_per_cu, (int)((size_t)(160 * 1024) / lds)));
-    const int64_t blocks = std::min<int64_t>((int64_t)sg_cu_count(dev_id) * per_cu, a->n_total / 48 + 3);
-    if (blocks <= 0) return 0;
-    SgKpAll u{cls8, cls16, ticket};
-    hipLaunchKernelGGL((k_power_all<T, L16>), dim3((unsigned)blocks), dim3(64), lds, st, *a, u);
-    SG_CHECK_LAUNCH();
-    return 0;
-}
-
-extern "C" int sg_launch_power_all(const SgBeamArgs *a, int dtype, int cls8, int cls16, int waves_per_cu, int ticket, void *stream)
-{
-    return dtype == 0 ? launch_power_all_t<float>(a, cls8, cls16, waves_per_cu, ticket, (hipStream_t)stream)
-                      : launch_power_all_t<double>(a, cls8, cls16, waves_per_cu, ticket, (hipStream_t)stream);
 }
 
 extern "C" int sg_launch_tier_gather(const SgBeamArgs *a, void *stream)

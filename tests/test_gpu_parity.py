@@ -556,10 +556,10 @@ def test_error_paths_report_instead_of_computing_garbage(eng, tables):
         eng.ctx.augment_batch(pc.astype(np.int32), [0, 8], [[0] * 64], 0.17, thr_poly=[[0, 0, 0.0]])
 
 
-def test_table_ordered_launch_equals_sorted_row_order(tables, monkeypatch):
-    """The first capacity tier walks (table, frame, channel) segments; SNOWGPU_LINEAR_ORDER=1 keeps sorted-row order.
-    Same bytes either way -- ragged frames, an empty frame, channels without lasers (Q5) and rows of several
-    channels that share one table included."""
+def test_table_ordered_launch_equals_sorted_row_order(tables):
+    """The first capacity tier walks (table, frame, channel) segments; with a caller permutation (here the one the device sort
+    makes: per frame a stable argsort by channel) it keeps sorted-row order.  Same bytes either way -- ragged frames, an empty
+    frame, channels without lasers (Q5) and rows of several channels that share one table included."""
     from lidar_snow_sim_amd import engine
     from lidar_snow_sim_amd.synthetic import synthetic_sweep
     rng = np.random.default_rng(77)
@@ -576,16 +576,16 @@ def test_table_ordered_launch_equals_sorted_row_order(tables, monkeypatch):
     tl = _tables64(tables)
     bd = float(np.degrees(3e-3))
     polys = [[0.0, 0.01, 2.0]] * 4
+    perm = np.concatenate([np.argsort(f[:, 4], kind="stable") for f in frames]).astype(np.int32)
     results = []
-    for linear in ("0", "1"):
-        monkeypatch.setenv("SNOWGPU_LINEAR_ORDER", linear)
-        e = engine.Engine(0)
-        try:
-            orders = [list(np.random.default_rng(5 + i).permutation(64)) for i in range(len(frames))]
-            tids = [e.table_ids_from_arrays(tl, o) for o in orders]
-            results.append(e.ctx.augment_batch(rows, off, tids, bd, thr_poly=polys))
-        finally:
-            e.ctx.close()
+    e = engine.Engine(0)
+    try:
+        orders = [list(np.random.default_rng(5 + i).permutation(64)) for i in range(len(frames))]
+        tids = [e.table_ids_from_arrays(tl, o) for o in orders]
+        for pm in (None, perm):
+            results.append(e.ctx.augment_batch(rows, off, tids, bd, thr_poly=polys, perm=pm))
+    finally:
+        e.ctx.close()
     (o0, s0, c0, st0, _), (o1, s1, c1, st1, _) = results
     assert np.array_equal(c0, c1) and np.array_equal(st0, st1)
     for f in range(len(frames)):
@@ -998,30 +998,24 @@ def test_pre_augment_crop_on_device_matches_crop_then_augment(eng, so, tables):
         assert (int(st[0]), int(st[1]), int(st[2])) == (int(s0[0]), int(s0[1]) + int((~flag2).sum()), int(s0[2]))
 
 
-@pytest.mark.parametrize("mode", ["-1"])
-def test_per_lane_and_wave_scan_give_the_same_rows(so, tables, monkeypatch, mode):
-    """The candidate scan has two forms: one beam per lane, and the wave-flattened one (every lane tests one (beam, record)
-    pair, hits appended through LDS counters, each beam's entries ordered afterwards).  The pass over all rows uses the
-    second and the tiers, by default, the first; SNOWGPU_PER_LANE_SCAN=-1 makes the tiers use the second too -- same bytes,
-    and both equal the oracle.  Wide beams (30 mrad: wedges of ten bins) exercise the per-lane part behind the first two
-    bins; SNOWGPU_FIRST_TIER=8 ... 63 (test_every_first_tier_gives_the_same_rows) runs every capacity in both forms."""
+def test_tier_scan_matches_the_oracle_for_narrow_and_wide_beams(so, tables):
+    """The pass over all rows scans wave-flattened (every lane tests one (beam, record) pair, hits appended through LDS
+    counters, each beam's entries ordered afterwards); the later tiers scan their beams again on their own (row kernels at
+    this size; SNOWGPU_TIER_ROWS=0 in test_remaining_environment_switches_change_no_byte for the other form).  Narrow
+    (3 mrad) and wide beams (30 mrad: wedges of ten bins, which exercise the per-lane part behind the first two bins) equal
+    the oracle; SNOWGPU_FIRST_TIER=8 ... 63 (test_every_first_tier_gives_the_same_rows) runs every capacity in the first pass."""
     from lidar_snow_sim_amd import engine
     tl = _tables64(tables)
     order = list(range(64))
     poly = [0.0, 0.01, 2.0]
     for bd in (float(np.degrees(3e-3)), float(np.degrees(3e-2))):
         pc = _stretched_subsweep(step=16 if bd < 0.5 else 64, seed=1080)
-        outs = []
-        for env in ("0", mode):
-            monkeypatch.setenv("SNOWGPU_PER_LANE_SCAN", env)
-            e = engine.Engine(0)
-            try:
-                outs.append(e.ctx.augment_batch(pc, [0, pc.shape[0]], [e.table_ids_from_arrays(tl, order)], bd, thr_poly=[poly]))
-            finally:
-                e.ctx.close()
-        (o0, s0, c0, st0, _), (o1, s1, c1, st1, _) = outs
+        e = engine.Engine(0)
+        try:
+            o0, s0, c0, st0, _ = e.ctx.augment_batch(pc, [0, pc.shape[0]], [e.table_ids_from_arrays(tl, order)], bd, thr_poly=[poly])
+        finally:
+            e.ctx.close()
         n = int(c0[0])
-        assert np.array_equal(c0, c1) and np.array_equal(st0, st1) and np.array_equal(s0[:n], s1[:n]) and o0[:n].tobytes() == o1[:n].tobytes()
         r_stats, r_aug, r_src = so.augment(pc, tl, bd, order, thr_poly=np.array(poly))
         assert tuple(int(v) for v in st0[0]) == tuple(int(v) for v in r_stats)
         assert np.array_equal(s0[:n], r_src) and np.array_equal(o0[:n, 3:], r_aug[:, 3:])
