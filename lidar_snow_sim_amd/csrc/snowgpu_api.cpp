@@ -1441,6 +1441,9 @@ static int host_batch_pipelined(snowgpu_ctx *ctx, int n_frames, const int64_t *f
     int rc = SNOWGPU_OK;
     // ---- packed result transfer: downloads sized by the counts, and the host threads that put the rows together ----------------------
     int pk_enq = 0, pk_asm = 0;                      // chunks whose compute and download are enqueued / whose rows are with the pool
+    // chunks that stopped at their prepass status (finish(): no compaction, no downloads): never assembled -- their pk_ev and staging
+    // words are an earlier call's
+    std::vector<char> pk_skip((size_t)n_chunks, 0);
     auto pk_mv_head = [](size_t chunk_rows) { return std::min(chunk_rows, std::max<size_t>(4096, chunk_rows / 8)); };
     auto assemble_frame = [=](int f, int64_t kept_dev, int64_t mv_at) {
         // out row j of frame f = the caller's input row src_j with the device's intensity and label; label-2 rows take their moved coordinates
@@ -1502,6 +1505,7 @@ static int host_batch_pipelined(snowgpu_ctx *ctx, int n_frames, const int64_t *f
     auto pk_progress = [&](bool wait) -> hipError_t {
         while (pk_asm < pk_enq) {
             const int c = pk_asm;
+            if (pk_skip[(size_t)c]) { ++pk_asm; continue; }
             hipEvent_t ev = ctx->pk_ev[2 * (size_t)c];
             hipError_t q = wait ? hipEventSynchronize(ev) : hipEventQuery(ev);
             if (q == hipErrorNotReady) { (void)hipGetLastError(); return hipSuccess; }     // ("not ready" must not be what the next launch check finds)
@@ -1509,8 +1513,10 @@ static int host_batch_pipelined(snowgpu_ctx *ctx, int n_frames, const int64_t *f
             // the chunk's words, intensities, the head of its moved-coordinates list and its counts are here
             const int f0 = c_first[(size_t)c], f1 = c_first[(size_t)c + 1];
             const size_t o = (size_t)frame_offsets[f0], head = pk_mv_head((size_t)(frame_offsets[f1] - frame_offsets[f0]));
+            // (a frame's moved rows clamped to its row count, as assemble_frame clamps kept: no copy or read past the chunk's rows)
+            auto mv_rows = [&](int f) { return std::min<int64_t>(std::max<int64_t>(st_mvcnt[f], 0), frame_offsets[f + 1] - frame_offsets[f]); };
             size_t n_mv = 0;
-            for (int f = f0; f < f1; ++f) n_mv += (size_t)st_mvcnt[f];
+            for (int f = f0; f < f1; ++f) n_mv += (size_t)mv_rows(f);
             if (n_mv > head) {                        // a list longer than its head (more than one row in eight scattered): the rest now, waited for
                 hipError_t e = hipMemcpyAsync(st_mv + (o + head) * 3 * esz, ctx->pk_mv.p + (o + head) * 3 * esz, (n_mv - head) * 3 * esz, hipMemcpyDeviceToHost, ctx->s_d2h);
                 if (e == hipSuccess) e = hipEventRecord(ctx->pk_ev[2 * (size_t)c + 1], ctx->s_d2h);
@@ -1522,7 +1528,7 @@ static int host_batch_pipelined(snowgpu_ctx *ctx, int n_frames, const int64_t *f
             for (int f = f0; f < f1; ++f) {
                 const int64_t kept = st_cnt[f];
                 if (kept > 0) ctx->pool->push([=]() { assemble_frame(f, kept, mv_at); });
-                mv_at += st_mvcnt[f];
+                mv_at += mv_rows(f);
             }
             ++pk_asm;
         }
@@ -1640,6 +1646,7 @@ static int host_batch_pipelined(snowgpu_ctx *ctx, int n_frames, const int64_t *f
             const int32_t *s8 = sg_stat + 8 * (size_t)c;
             if (s8[0] != 0) {                                  // (fewer than 3 ground rows in a frame: reported as the device prepass reports it)
                 PIPECHK(hipMemcpyAsync(b.status, k.lc->d_status, 32, hipMemcpyDeviceToDevice, cs));
+                pk_skip[(size_t)c] = 1;                        // (a later chunk's finish moves pk_enq past this one: nothing of it to assemble)
                 return SNOWGPU_OK;                             // the chunk's status words carry the error to the end of the call
             }
             const int crc = ctx->thr_fn(ctx->thr_user, f0, cf, sg_hist + (size_t)f0 * HIST, sg_rec + (size_t)f0 * SG_PRE_REC, sg_thr + 3 * (size_t)f0);

@@ -254,22 +254,22 @@ def augment_batch(frames: Sequence[np.ndarray], particle_file_prefix: str, beam_
             else:
                 flat[...] = rows[0][:, :5]
         resident = False
-        if q8_device:
-            # q8='numpy': the library hands the device half of the prepass (histograms, sums) to this callback group by group WHILE the
-            # per-beam kernels of the group run (snowgpu_set_threshold_callback); the row minima are taken here, with this process' NumPy
-            # (np.argpartition verbatim, quirk Q8), and the polynomials go back for the compaction.  One crossing of the rows, one call.
-            eng.ctx.set_threshold_callback(lambda first, hist, rec: noise_polys_from_device_stats(hist, rec, noise_floor))
-        out_rows, out_src = eng.result_buffers(int(offsets[-1]), dt)
         # The device counting sort handles integer channel values 0..255 and reports anything else
         # (SNOWGPU_E_CHANNELS); only then is the batch sorted here and run again with the permutation.
         perm = None
         crop_idx = None
-        if calib is not None:
-            eng.ctx.set_fov(calib, (1024, 1920), pre_crop=pre_crop)              # simulation.py:536
         device_plane = not polys and not plane_rows                              # neither given: calculate_plane on the device
-        if device_plane:
-            eng.ctx.set_plane_method(plane_method, seed=plane_seed, trials=plane_trials, min_rows=ncols)
-        try:
+        try:                                         # (the settings below go on the engine's shared context: the finally takes them off)
+            if q8_device:
+                # q8='numpy': the library hands the device half of the prepass (histograms, sums) to this callback group by group WHILE the
+                # per-beam kernels of the group run (snowgpu_set_threshold_callback); the row minima are taken here, with this process' NumPy
+                # (np.argpartition verbatim, quirk Q8), and the polynomials go back for the compaction.  One crossing of the rows, one call.
+                eng.ctx.set_threshold_callback(lambda first, hist, rec: noise_polys_from_device_stats(hist, rec, noise_floor))
+            out_rows, out_src = eng.result_buffers(int(offsets[-1]), dt)
+            if calib is not None:
+                eng.ctx.set_fov(calib, (1024, 1920), pre_crop=pre_crop)          # simulation.py:536
+            if device_plane:
+                eng.ctx.set_plane_method(plane_method, seed=plane_seed, trials=plane_trials, min_rows=ncols)
             for attempt in (0, 1):
                 try:
                     out, src, counts, stats, _ = eng.ctx.augment_batch(
