@@ -96,7 +96,7 @@ int augment_batch(int n_frames, const int64_t *off, const T *rows, int n_tables,
     });
     if (err.load()) { status[0] = err.load(); status[1] = err_row.load(); return status[0]; }
     for (int t = 0; t < n_tables; ++t) max_flakes = std::max<uint32_t>(max_flakes, (uint32_t)tk[t]);
-    const int cap = (int)std::min<uint32_t>(std::max<uint32_t>(max_flakes, 64u), 8192u);      // the global-list tier's capacity (snowgpu_api.cpp: h_cap)
+    const int cap = (int)std::min<uint32_t>(std::max<uint32_t>(max_flakes, 64u), 8192u);      // the global-list tier's capacity (snowgpu_batch.cpp: h_cap)
     std::vector<double> R(SG_RBINS);
     for (int k = 0; k < SG_RBINS; ++k) R[k] = sg_range_bin(k);
     const int64_t n_total = off[n_frames];

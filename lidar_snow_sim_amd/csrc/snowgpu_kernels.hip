@@ -1697,7 +1697,7 @@ __global__ void k_resolve_tables(const SgTable *__restrict__ tables, int n_table
 }
 
 // ------------------------------------------------------------------------------------------------
-// launch wrappers (C linkage, called from snowgpu_api.cpp)
+// launch wrappers (C linkage, called from snowgpu_batch.cpp and snowgpu_host.cpp)
 
 #define SG_CHECK_LAUNCH()                                  \
     do {                                                   \

@@ -6,7 +6,7 @@ cd "$(dirname "$0")/.."
 N=$1; shift
 C=lidar_snow_sim_amd/csrc; V=lidar_snow_sim_amd/_variants; O=$C/_obj_$N; mkdir -p $V $O
 F="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-unused-function"
-for s in snowgpu_kernels.hip snowgpu_rows.hip snowgpu_prepass.hip snowgpu_plane.hip snowgpu_sampler.hip snowgpu_tables.hip snowgpu_api.cpp; do
+for s in snowgpu_kernels.hip snowgpu_rows.hip snowgpu_prepass.hip snowgpu_plane.hip snowgpu_sampler.hip snowgpu_tables.hip snowgpu_api.cpp snowgpu_batch.cpp snowgpu_host.cpp; do
   hipcc $F "$@" -x hip -c $C/$s -o $O/${s%.*}.o &
 done
 wait

@@ -481,7 +481,7 @@ def test_threshold_callback_inside_the_pipelined_call_equals_the_two_call_form(c
 
 def test_long_tail_order_of_the_received_power_phase_changes_no_byte(monkeypatch, capsys):
     """Large batches run k_power_few first; where k_power<4> goes after it depends on how many beams the 63-entry / global-list tiers held in
-    the batches before (page-locked words the device leaves behind: snowgpu_api.cpp, `heavy_tail`): behind k_power_few with those tiers
+    the batches before (page-locked words the device leaves behind: snowgpu_batch.cpp, `heavy_tail`): behind k_power_few with those tiers
     behind it, or on the caller's stream ahead of the 8-entry tier with those tiers right behind k_power_few.  SNOWGPU_HEAVY_TAIL=0 / 1 forces
     either.  Six C1 sweeps (40 k flakes per line: thousands of beams in the 63-entry tier) in one device-entry batch: both orders, and the
     default called three times in a row (the third call sees the first calls' counts), give the same rows, sources, counts and statistics."""

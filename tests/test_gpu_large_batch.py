@@ -255,7 +255,7 @@ def test_C1_and_C4_as_device_batches_of_32(workload, capsys):
     _assert_oracle(tot, stat_bad)
     if workload == "C1":
         assert tail > 500, st
-        # the second call's choice (snowgpu_api.cpp, heavy_tail): tail >= 4096 and tail * 22 > beams of the 16-entry tier
+        # the second call's choice (snowgpu_batch.cpp, heavy_tail): tail >= 4096 and tail * 22 > beams of the 16-entry tier
         assert tail >= 4096 and tail * 22 > int(st[3]), st
         assert repeat_differ == 0
 
@@ -473,7 +473,9 @@ def test_ground_error_in_a_pipelined_chunk_leaves_the_callers_rows_alone(capsys)
     without ground rows stops before its compaction and downloads.  Its frames must not be assembled from staging words an earlier call
     left behind.  40 C2 sweeps, a good call first (it fills the staging counts), then frame 0 lifted off the ground with out_rows pre-filled
     with a NaN sentinel: E_GROUND, and every row of the failing chunk -- not the batch's last chunk -- is still the sentinel.  The same call
-    with the rows transfer raises E_GROUND too, and a third good call gives the first call's bytes."""
+    with the rows transfer raises E_GROUND too, and a third good call gives the first call's bytes.  Then an error the caller causes: the
+    callback raises on its second group.  The call re-raises it, and nothing of the call is in flight once it has returned -- out_rows
+    overwritten with the sentinel right away is intact after a device synchronisation -- and a good call gives the first call's bytes."""
     from lidar_snow_sim_amd import _native, engine
     from lidar_snow_sim_amd.tools.wet_ground.augmentation import noise_polys_from_device_stats
     tables = _tables("C2")
@@ -510,6 +512,23 @@ def test_ground_error_in_a_pipelined_chunk_leaves_the_callers_rows_alone(capsys)
             assert err_rows.value.code == _native.E_GROUND
             eng.ctx.set_result_transfer("packed")
             third = eng.ctx.augment_batch(rows, off, tids, BD, plane=planes)
+            seen = []
+
+            def fit_raises(first, h, r):
+                seen.append(first)
+                if len(seen) == 2:
+                    raise RuntimeError("the second group's fit failed")
+                return noise_polys_from_device_stats(h, r, 0.7)
+
+            eng.ctx.set_threshold_callback(fit_raises)
+            overwritten = np.zeros((int(off[-1]), 5), np.float32)
+            with pytest.raises(RuntimeError, match="second group"):
+                eng.ctx.augment_batch(rows, off, tids, BD, plane=planes, out_rows=overwritten)
+            overwritten[...] = np.nan                     # whatever the call left in flight would now land on top of this
+            torch.cuda.synchronize()
+            in_flight = int((~np.isnan(overwritten)).any(axis=1).sum())
+            eng.ctx.set_threshold_callback(fit)
+            fourth = eng.ctx.augment_batch(rows, off, tids, BD, plane=planes)
         finally:
             eng.ctx.set_threshold_callback(None)
             eng.ctx.set_result_transfer("rows")
@@ -521,15 +540,19 @@ def test_ground_error_in_a_pipelined_chunk_leaves_the_callers_rows_alone(capsys)
     assert chunk0 < n and all(g[0] != 0 for g in bad_groups)          # not the last chunk; its callback did not run
     untouched = int(np.isnan(sentinel[:off[chunk0]]).all(axis=1).sum())
     rows_chunk0 = int(off[chunk0])
-    third_differ = int(not (np.array_equal(third[2], good[2]) and np.array_equal(third[3], good[3])))
+    third_differ, fourth_differ = (int(not (np.array_equal(res[2], good[2]) and np.array_equal(res[3], good[3]))) for res in (third, fourth))
     for f in range(n):
         a, m = int(off[f]), int(good[2][f])
         third_differ += not (third[0][a:a + m].tobytes() == good[0][a:a + m].tobytes() and np.array_equal(third[1][a:a + m], good[1][a:a + m]))
+        fourth_differ += not (fourth[0][a:a + m].tobytes() == good[0][a:a + m].tobytes() and np.array_equal(fourth[1][a:a + m], good[1][a:a + m]))
     _report(capsys, {"test": "E_GROUND in a pipelined chunk (callback, packed transfer)", "frames": n, "chunk0_frames": chunk0,
                      "groups_good_call": len(good_groups), "chunk0_rows": rows_chunk0, "chunk0_rows_untouched": untouched,
-                     "third_call_frames_differ": third_differ})
+                     "third_call_frames_differ": third_differ, "groups_seen_by_the_raising_callback": len(seen),
+                     "rows_written_after_the_raising_call_returned": in_flight, "call_after_the_raising_one_frames_differ": fourth_differ})
     assert untouched == rows_chunk0
     assert third_differ == 0
+    assert len(seen) == 2 and in_flight == 0
+    assert fourth_differ == 0
 
 
 # ---- 7. a failed call takes its threshold callback off the shared context ----------------------------------------------------------

@@ -554,6 +554,22 @@ def test_error_paths_report_instead_of_computing_garbage(eng, tables):
                               thr_poly=[[0, 0, 0.0]])
     with pytest.raises(TypeError):                                   # integer rows
         eng.ctx.augment_batch(pc.astype(np.int32), [0, 8], [[0] * 64], 0.17, thr_poly=[[0, 0, 0.0]])
+    # a caller's permutation with the pre-augment crop: refused before anything is uploaded; the next call on the engine is correct
+    from lidar_snow_sim_amd.calibration import Calibration
+    tids = [eng.table_ids_from_arrays(_tables64(tables), list(range(64)))]
+    bd, poly = float(np.degrees(3e-3)), [[0.0, 0.01, 2.0]]
+    want = [np.copy(a) for a in eng.ctx.augment_batch(pc, [0, 8], tids, bd, thr_poly=poly)[:4]]
+    eng.ctx.set_fov(Calibration(V2C=np.eye(3, 4), R0=np.eye(3), P2=np.eye(3, 4)), pre_crop=True)
+    try:
+        with pytest.raises(_native.SnowGPUError) as e:
+            eng.ctx.augment_batch(pc, [0, 8], tids, bd, thr_poly=poly, perm=np.arange(8, dtype=np.int32))
+        assert e.value.code == _native.E_INVALID
+    finally:
+        eng.ctx.set_fov(None)
+    got = eng.ctx.augment_batch(pc, [0, 8], tids, bd, thr_poly=poly)[:4]
+    m = int(want[2][0])
+    assert np.array_equal(got[2], want[2]) and np.array_equal(got[3], want[3]) and np.array_equal(got[1][:m], want[1][:m])
+    assert m > 0 and got[0][:m].tobytes() == want[0][:m].tobytes()
 
 
 def test_table_ordered_launch_equals_sorted_row_order(tables):

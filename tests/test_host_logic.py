@@ -955,3 +955,94 @@ def test_sorting_networks_of_the_dict_are_the_generator_s_and_sort():
         net = gen.network(n)
         assert all(0 <= i < j < n for i, j in net)
         gen.check(n, net)
+
+
+# ---- packed result transfer: the host threads' assembly (csrc/sg_assemble.h) on fabricated device words -------------------------------------
+def _packed_case(rng, kind, want_src):
+    """One ragged batch as the device would leave it, and the rows the host must make of it -- from the statement of the format (word m:
+    code = m >> 30, src = min(m & 0x3fffffff, n_rows - 1); x, y, z of input row src, for code 2 the next unused triple of the frame's
+    moved list; column 3 the intensity; column 4 the code, for code 3 the input row's channel), not from the C++."""
+    T = np.float64 if kind == 2 else np.float32
+    in_w = 4 if kind == 1 else 5
+    sizes = np.array([0, 1, 37, 300, 5, 0, 1200, 64, 2, 511, 90, 1, 700, 33], dtype=np.int64)
+    n_frames, off = len(sizes), np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    n = int(off[-1])
+    kept = np.array([int(rng.integers(0, s + 1)) for s in sizes], dtype=np.int64)
+    kept[2] = sizes[2]                      # every row kept
+    kept[3] = sizes[3] + 5                  # the device's count above the frame's rows: clamped
+    kept[4] = 0                             # nothing kept of a frame that has rows
+    kept[5] = 3                             # ... and a count for a frame that has none
+    kept[9] = -2
+    code = rng.integers(0, 4, n).astype(np.uint32)
+    src = np.concatenate([rng.integers(0, max(s, 1), s) for s in sizes]).astype(np.uint32)
+    wild = rng.random(n) < 0.05             # source rows beyond the frame: clamped to its last row
+    src[wild] = rng.integers(0, 1 << 30, int(wild.sum())).astype(np.uint32)
+    src[off[6] + 1] = (1 << 30) - 1
+    meta = (code << np.uint32(30)) | src
+    rows = rng.standard_normal((n, in_w)).astype(T)
+    chn = rng.integers(0, 256, n).astype(np.uint8)
+    if kind != 1:
+        rows[:, 4] = chn
+    inten = rng.random(n).astype(T)
+    mvcnt = np.zeros(n_frames, dtype=np.int64)
+    for f in range(n_frames):
+        k = min(max(int(kept[f]), 0), int(sizes[f]))
+        mvcnt[f] = int((code[off[f]:off[f] + k] == 2).sum())
+    mvcnt[7] += 3                           # triples nobody reads
+    mvcnt[10] = sizes[10] + 9               # a count above the frame's rows: sg_moved_rows clamps it
+    mvcnt[5] = 4
+    mv_rows = np.minimum(np.maximum(mvcnt, 0), sizes)
+    mv_at = np.concatenate([[0], np.cumsum(mv_rows)])
+    mv = rng.standard_normal((int(mv_at[-1]), 3)).astype(T)
+    out_rows = np.full((n, 5), np.nan, dtype=T)
+    out_src = np.full(n, -7, dtype=np.int32)
+    want_rows, want_idx = out_rows.copy(), out_src.copy()
+    for f in range(n_frames):
+        o, s = int(off[f]), int(sizes[f])
+        k = min(max(int(kept[f]), 0), s)
+        if k == 0:
+            continue
+        c, sr = code[o:o + k], np.minimum(src[o:o + k], s - 1).astype(np.int64)
+        blk = np.empty((k, 5), dtype=T)
+        blk[:, :3] = rows[o + sr, :3]
+        moved = c == 2
+        blk[moved, :3] = mv[mv_at[f]:mv_at[f] + int(moved.sum())]
+        blk[:, 3] = inten[o:o + k]
+        blk[:, 4] = np.where(c == 3, chn[o + sr].astype(T) if kind == 1 else rows[o + sr, 4], c.astype(T))
+        want_rows[o:o + k] = blk
+        if want_src:
+            want_idx[o:o + k] = sr
+    files = {"head": np.array([kind, n_frames, int(want_src)], dtype=np.int64), "offsets": off, "kept": kept, "mvcnt": mvcnt, "rows": rows,
+             "chn": chn if kind == 1 else chn[:0], "meta": meta, "inten": inten, "mv": mv, "out_rows": out_rows, "out_src": out_src}
+    return files, want_rows, want_idx
+
+
+@pytest.mark.parametrize("build", ["plain", "address,undefined", "thread"])
+def test_packed_assembly_on_fabricated_device_words(tmp_path, build):
+    """tests/host_harness/assemble_frames.cpp: float32, float32 compact and float64 batches of 14 ragged frames (an empty frame, a
+    one-row frame, counts above a frame's rows, a count of zero, source rows beyond the frame, all four codes, with and without out_src)
+    through sg_assemble_frame on an AsmPool of 3 threads -- byte for byte what the format says, rows beyond the kept ones untouched;
+    built plain, with AddressSanitizer + UBSan (every buffer has its exact size) and with ThreadSanitizer.  A sanitizer build skips only
+    where it does not compile or link; a report of either fails the test."""
+    exe = tmp_path / "assemble_frames"
+    cmd = ["g++", "-std=c++17", "-O1", "-g", "-pthread", "-o", str(exe), str(ROOT / "tests" / "host_harness" / "assemble_frames.cpp")]
+    if build != "plain":
+        cmd.insert(5, "-fsanitize=" + build)
+    cc = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    if cc.returncode != 0 and build != "plain":
+        pytest.skip(f"-fsanitize={build} does not compile or link here: {cc.stderr.strip()[-300:]}")
+    assert cc.returncode == 0, cc.stderr[-2000:]
+    env = dict(os.environ, ASAN_OPTIONS="halt_on_error=1:exitcode=66", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1:exitcode=66",
+               TSAN_OPTIONS="halt_on_error=1:exitcode=66")
+    rng = np.random.default_rng(20240607)
+    for kind in (0, 1, 2):
+        for want_src in (True, False):
+            files, want_rows, want_idx = _packed_case(rng, kind, want_src)
+            d = tmp_path / f"case_{kind}_{int(want_src)}"
+            d.mkdir()
+            for name, arr in files.items():
+                (d / f"{name}.bin").write_bytes(np.ascontiguousarray(arr).tobytes())
+            r = subprocess.run([str(exe), str(d)], capture_output=True, text=True, timeout=300, env=env)
+            assert r.returncode == 0 and "Sanitizer" not in r.stderr and "runtime error" not in r.stderr, (build, kind, want_src, r.stderr[-3000:])
+            assert (d / "out_rows.out").read_bytes() == want_rows.tobytes(), (build, kind, want_src)
+            assert (d / "out_src.out").read_bytes() == want_idx.tobytes(), (build, kind, want_src)
