@@ -186,7 +186,9 @@ struct SgFov {
     double img_h, img_w;
 };
 
-// Launch wrappers implemented in snowgpu_kernels.hip (hipStream_t passed as void*).
+// Launch wrappers (hipStream_t passed as void*), each implemented in the file that defines its kernels: snowgpu_sort.hip (expand_rows, sort,
+// gather_rows, segments*, resolve_tables), snowgpu_kernels.hip (beams, power*, tier_*, huge, sg_beams_block), snowgpu_rows.hip (rows),
+// snowgpu_compact.hip (compact, crop_*).  Every one of these files includes this header, so a definition cannot drift from its declaration.
 #ifdef __cplusplus
 extern "C" {
 #endif

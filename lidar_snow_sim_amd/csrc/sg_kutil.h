@@ -1,8 +1,10 @@
-// sg_kutil.h -- small device helpers shared by the kernel files (snowgpu_kernels.hip, snowgpu_rows.hip).
+// sg_kutil.h -- small device helpers shared by the kernel files (snowgpu_sort.hip, snowgpu_kernels.hip, snowgpu_compact.hip, snowgpu_rows.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include "sg_common.h"
 #include "sg_beam.h"
+
+#define SG_BLOCK 256      /* threads per block of the kernels that walk a frame by 1024-row tiles (four rows per thread) */
 
 __device__ __forceinline__ int sg_find_frame(const int64_t *__restrict__ off, int n_frames, int64_t g)
 {

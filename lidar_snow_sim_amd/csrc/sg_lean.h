@@ -1,5 +1,5 @@
 // sg_lean.h -- the per-tile statistics of the lean snowfall prepass (snowgpu_prepass.hip), shared with the channel sort's first
-// kernel (snowgpu_kernels.hip: k_sort_hist<T, true>), which streams the same rows and can take them on the way.
+// kernel (snowgpu_sort.hip: k_sort_hist<T, true>), which streams the same rows and can take them on the way.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>

@@ -1,5 +1,6 @@
 // sg_prepass.h -- device noise-threshold prepass (simulation.py:449-467; wet_ground/augmentation.py:195-266)
-// and the wet-ground model (wet_ground/augmentation.py:25-161).  Implemented in snowgpu_prepass.hip.
+// and the wet-ground model (wet_ground/augmentation.py:25-161).  Implemented in snowgpu_prepass.hip (the snowfall path's
+// prepass, the scratch pool) and snowgpu_wet.hip (sg_wet_run, sg_launch_compose_src, sg_debug_ransac_quad).
 #pragma once
 #include <stdint.h>
 

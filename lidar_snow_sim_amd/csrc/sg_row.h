@@ -1,5 +1,5 @@
 // sg_row.h -- an output row of augment() from the ORIGINAL row and the beam's 4-byte result record (simulation.py:176-180, :516): what the
-// compaction kernels (snowgpu_kernels.hip) and the CPU twin of the per-beam path (snowcpu.cpp) both do.  Device code that also compiles for
+// compaction kernels (snowgpu_compact.hip) and the CPU twin of the per-beam path (snowcpu.cpp) both do.  Device code that also compiles for
 // the host (see sg_beam.h).
 #pragma once
 #include "sg_beam.h"

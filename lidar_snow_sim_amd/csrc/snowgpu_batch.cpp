@@ -1,6 +1,7 @@
 // snowgpu_batch.cpp -- the launch sequence of one augment batch, everything on device pointers: which kernel goes to which stream in
 // which order, and the scratch it needs.  Every order and every stream choice below is a measurement; the comments say which.
 #include "sg_host.h"
+#include "sg_launch.h"      // sg_tiles
 
 static int sync_tables(snowgpu_ctx *ctx)
 {
@@ -63,7 +64,7 @@ int run_batch(snowgpu_ctx *ctx, BatchDev &b)
         return fail(ctx, SNOWGPU_E_INVALID, "beam divergence must be in (0, 45) degrees");
     int rc = sync_tables(R);
     if (rc) { if (R != ctx) ctx->err = R->err; return rc; }
-    const int64_t max_tiles = std::max<int64_t>(1, (b.max_frame + SG_TILE - 1) / SG_TILE);
+    const int64_t max_tiles = sg_tiles(b.max_frame);
     const size_t n = (size_t)b.n_total;
     const size_t esz = b.dtype == 0 ? 4 : 8;
     hipStream_t st = b.stream;
@@ -477,7 +478,7 @@ int run_compaction(snowgpu_ctx *ctx, BatchDev &b)
     snowgpu_ctx *R = ctx->root ? ctx->root : ctx;
     if (!b.thr_poly) return fail(ctx, SNOWGPU_E_INVALID, "run_compaction without threshold polynomials");
     if (b.n_total == 0) return SNOWGPU_OK;                        // (run_batch filled counts and statistics)
-    const int64_t max_tiles = std::max<int64_t>(1, (b.max_frame + SG_TILE - 1) / SG_TILE);
+    const int64_t max_tiles = sg_tiles(b.max_frame);
     int tiers[4], n_tiers = 0;
     choose_tiers(R, b.beam_div_deg, tiers, &n_tiers);
     const size_t q_chunk = 8 * (size_t)sg_beams_block(tiers[0]);

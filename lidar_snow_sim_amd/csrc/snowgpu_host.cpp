@@ -4,6 +4,7 @@
 #include <chrono>
 
 #include "sg_host.h"
+#include "sg_launch.h"      // sg_tiles
 
 constexpr size_t SG_THR_HIST = (size_t)50 * 2555;      // words of one frame's histogram of (range, I / cos) (snowgpu_prepass_stats)
 
@@ -571,7 +572,7 @@ static int host_batch(snowgpu_ctx *ctx, int n_frames, const int64_t *frame_offse
     const int64_t *d_off_used = d_frame_off;
     int64_t n_used = n_total, max_frame_used = max_frame;
     if (precrop) {
-        const int64_t max_tiles = std::max<int64_t>(1, (max_frame + SG_TILE - 1) / SG_TILE);
+        const int64_t max_tiles = sg_tiles(max_frame);
         ENSURE(ctx, ctx->keep, n);
         ENSURE(ctx, ctx->ctile_cnt, (size_t)n_frames * (size_t)max_tiles + 1);
         ENSURE(ctx, ctx->ctile_base, (size_t)n_frames * (size_t)max_tiles + 1);

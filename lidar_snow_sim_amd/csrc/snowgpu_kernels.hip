@@ -1,26 +1,23 @@
-// snowgpu_kernels.hip -- gfx950 kernels of the snowfall-augmentation engine and their launch wrappers.
+// snowgpu_kernels.hip -- the per-beam kernels of the snowfall-augmentation engine on gfx950, with their tunables and launch wrappers.
 //
-//   k_sort_*     stable counting sort of every frame's rows by channel                      (simulation.py:447)
-//   k_seg_*      launch order of the first pass: (table, frame, channel) segments
 //   k_beams      one thread per beam: candidate scan + occlusion dict; beams with flakes hand their dict to k_power
 //                through a compact queue, beams with more flakes than the list holds go on the list of the capacity
 //                tier that takes them                                                       (simulation.py:50-424)
 //   k_tier_scan_direct  the scan of a later tier whose lists the first pass could not keep
+//   k_power_plan, k_tier_gather  work items of k_power / k_power_few; the tier lists closed up
 //   k_power      received power on the 10 cm grid, first maximum, attenuate-or-scatter        (simulation.py:135-188)
+//   k_power_few  the same for the beams with one to three flakes
 //   k_beams_huge the global-list tier (more than 63 flakes in one beam)
-//   k_compact_*  output rows from original rows + 4-byte result records, noise-floor filter, camera-FOV crop, stable
-//                stream compaction, stats                                                   (simulation.py:516-540)
 //
+// The rows come channel-sorted and in segment order from snowgpu_sort.hip; snowgpu_compact.hip turns the result records into output rows.
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off (see lidar_snow_sim_amd/build.py).
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include "sg_beam.h"
 #include "sg_few.h"
 #include "sg_kutil.h"
-#include "sg_lean.h"
-#include "sg_row.h"
+#include "sg_launch.h"
 
-#define SG_BLOCK 256
 #ifndef SG_NB4
 #define SG_NB4 4          /* bins of the power profile evaluated together by the 4-entry tier (1, 2, 3 measured slower) ... */
 #endif
@@ -66,212 +63,27 @@
 #define SG_LANES_63 16
 #endif
 
-// ------------------------------------------------------------------------------------------------
-// Stable counting sort by channel, per frame.  grid = (tiles per frame, frames), 256 threads, a tile
-// is 1024 consecutive rows; wave w owns rows [256 w, 256 w + 256) of the tile in 4 rounds of 64 so
-// that "earlier row" == "earlier (wave, round, lane)".
-// STATS: the tile's rows are here anyway -- the per-tile statistics of the noise-threshold prepass (sg_lean.h; needs the ground plane,
-// i.e. a plane that is known when the sort starts) ride along: one pass over the rows less per step (0.67 GB of 256 sweeps).
-// Ranks: every lane finds the lanes of its wave that hold the same channel by eight ballots, one per bit of the channel byte -- the
-// same cost whether the 64 rows are of one channel (a channel-major sweep) or of 64 (firing order: an STF .bin interleaves the
-// channels, precompute.py:78).  A loop with one round per DISTINCT channel of the wave took 1.23 ms of a 256-sweep step on firing-order
-// rows against 0.35 ms on channel-major ones (profiles/r05_C2fire_*).
-// tile_unsorted: 1 if a row of this tile has a smaller channel than the row before it (k_sort_scan folds the tiles of a frame: a
-// frame without such a row is channel-sorted as it stands, its permutation is the identity and nobody makes or reads a copy of it).
-template <typename T, bool STATS>
-__global__ __launch_bounds__(SG_BLOCK) void k_sort_hist(const T *__restrict__ rows, const int64_t *__restrict__ frame_off,
-                                                        int32_t *__restrict__ tile_hist, uint16_t *__restrict__ rank,
-                                                        uint8_t *__restrict__ ch8, int32_t *__restrict__ status, int64_t max_tiles, SgLeanTile lean,
-                                                        int32_t *__restrict__ tile_unsorted)
+// The capacity tiers of the per-beam kernels: list capacity lmax -> <LMAX, BLOCK> (BLOCK: beams per block = stride of the LDS lists).
+// f takes an SgTier value:
+//     sg_by_tier<true>(lmax, [&](auto tier) { constexpr int LMAX = tier.LMAX, BLOCK = tier.BLOCK; ... })
+// WITH4 = false: the caller has no 4-entry case (the later tiers: 8, 16, SG_LCAP) -- none is instantiated.
+template <int LMAX_, int BLOCK_>
+struct SgTier { static constexpr int LMAX = LMAX_, BLOCK = BLOCK_; };
+
+template <bool WITH4, class F>
+static inline int sg_by_tier(int lmax, F &&f)
 {
-    const int f = blockIdx.y;
-    // status[1] ("first offending row", -1 = none: nobody writes it before the per-beam kernels) is set here, so that ONE fill clears the
-    // status words of a batch instead of two (each fill is a launch on the chain of a small batch)
-    if (blockIdx.x == 0 && f == 0 && threadIdx.x == 0) status[1] = -1;
-    const int64_t base = frame_off[f], n = frame_off[f + 1] - base;
-    const int64_t tile0 = (int64_t)blockIdx.x * SG_TILE;
-    if (tile0 >= n) return;
-    __shared__ volatile int cnt[4][256];
-    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
-    for (int i = tid; i < 4 * 256; i += SG_BLOCK) ((volatile int *)cnt)[i] = 0;
-    __syncthreads();
-    int my_bucket[4], my_rank[4];
-    [[maybe_unused]] T sx[4], sy[4], sz[4], si[4];
-    [[maybe_unused]] bool sv[4];
-    int descends = 0;
-    // every load of the thread's four rows first (the rounds below are chains of ballots and LDS updates: a load inside one waits its turn)
-    T sc[4], scp[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const int64_t r = tile0 + w * 256 + q * 64 + lane;
-        const bool valid = r < n;
-        const T *p = rows + (base + (valid ? r : 0)) * 5;
-        if constexpr (STATS) { sx[q] = p[0]; sy[q] = p[1]; sz[q] = p[2]; si[q] = p[3]; sv[q] = valid; }
-        sc[q] = p[4];
-        scp[q] = (valid && lane == 0 && r > 0) ? p[-1] : (T)0;        // lane 0: the channel of the row before this round's first (earlier round, wave or tile)
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const int64_t r = tile0 + w * 256 + q * 64 + lane;
-        const bool valid = r < n;
-        int bucket = -1;
-        const T c_prev = scp[q];
-        if (valid) {
-            const T c = sc[q];
-            const int ci = (int)c;
-            if ((T)ci == c && ci >= 0 && ci < 256) bucket = ci;
-            else { atomicCAS(&status[0], 0, 5 /* SNOWGPU_E_CHANNELS */); bucket = 255; }
-        }
-        {
-            int before_b = __shfl_up(bucket, 1);
-            if (lane == 0) before_b = r > 0 ? (int)c_prev : bucket;
-            if (valid && bucket < before_b) descends = 1;
-        }
-        my_bucket[q] = bucket;
-        my_rank[q] = 0;
-        if (valid) ch8[base + r] = (uint8_t)bucket;     // the scatter pass reads 1 byte per row instead of the row again
-        unsigned long long same = __ballot(valid);      // lanes of this wave with my channel
-#pragma unroll
-        for (int bit = 0; bit < 8; ++bit) {
-            const bool set = (bucket >> bit) & 1;
-            const unsigned long long bb = __ballot(set);
-            same &= set ? bb : ~bb;
-        }
-        if (valid) {
-            const int before = cnt[w][bucket];          // (a wave's LDS operations keep their order: every read precedes the leaders' writes)
-            my_rank[q] = before + __popcll(same & sg_lanemask_lt());
-            if ((same & sg_lanemask_lt()) == 0) cnt[w][bucket] = before + __popcll(same);
-        }
-    }
-    const int any_descends = __syncthreads_or(descends);
-    for (int q = 0; q < 4; ++q) {
-        const int64_t r = tile0 + w * 256 + q * 64 + lane;
-        if (r < n) {
-            int off = my_rank[q];
-            for (int ww = 0; ww < w; ++ww) off += cnt[ww][my_bucket[q]];
-            rank[base + r] = (uint16_t)off;
-        }
-    }
-    int32_t *h = tile_hist + ((int64_t)f * max_tiles + blockIdx.x) * 256;
-    h[tid] = cnt[0][tid] + cnt[1][tid] + cnt[2][tid] + cnt[3][tid];
-    if (tid == 0) tile_unsorted[(int64_t)f * max_tiles + blockIdx.x] = any_descends ? 1 : 0;
-    if constexpr (STATS) {
-        __shared__ double sm[58];
-        lean_tile_stats<T>(lean, f, blockIdx.x, sx, sy, sz, si, sv, sm);
-    }
+    if constexpr (WITH4) { if (lmax == 4) return f(SgTier<4, 256>{}); }
+    if (lmax == 8) return f(SgTier<8, SG_LANES_8>{});
+    if (lmax == 16) return f(SgTier<16, SG_LANES_16>{});
+    return f(SgTier<SG_LCAP, SG_LANES_63>{});
 }
 
-// One block per frame, thread v owns bucket v: tile_base[t][v] = (rows of smaller buckets) + (rows of
-// bucket v in earlier tiles); frame_unsorted[f] = some tile of the frame saw a descending channel.
-__global__ __launch_bounds__(SG_BLOCK) void k_sort_scan(const int64_t *__restrict__ frame_off,
-                                                        const int32_t *__restrict__ tile_hist,
-                                                        int32_t *__restrict__ tile_base, int64_t max_tiles,
-                                                        const int32_t *__restrict__ tile_unsorted, int32_t *__restrict__ frame_unsorted)
+// both at once: f(row type value, tier)
+template <bool WITH4, class F>
+static inline int sg_by_dtype_tier(int dtype, int lmax, F &&f)
 {
-    const int f = blockIdx.x, v = threadIdx.x;
-    const int64_t n = frame_off[f + 1] - frame_off[f];
-    const int64_t tiles = (n + SG_TILE - 1) / SG_TILE;
-    const int32_t *h = tile_hist + (int64_t)f * max_tiles * 256;
-    int32_t *b = tile_base + (int64_t)f * max_tiles * 256;
-    int total = 0, uns = 0;
-    for (int64_t t = v; t < tiles; t += SG_BLOCK) uns |= tile_unsorted[(int64_t)f * max_tiles + t];
-#pragma unroll 8                                  // eight loads in flight: the loop is a chain of global-load latencies otherwise
-    for (int64_t t = 0; t < tiles; ++t) total += h[t * 256 + v];
-    __shared__ int s[256];
-    s[v] = total;
-    uns = __syncthreads_or(uns);
-    if (v == 0) frame_unsorted[f] = uns ? 1 : 0;
-    for (int d = 1; d < 256; d <<= 1) {          // Hillis-Steele inclusive scan over the 256 buckets
-        int add = v >= d ? s[v - d] : 0;
-        __syncthreads();
-        s[v] += add;
-        __syncthreads();
-    }
-    int run = s[v] - total;
-#pragma unroll 8
-    for (int64_t t = 0; t < tiles; ++t) { b[t * 256 + v] = run; run += h[t * 256 + v]; }
-}
-
-// Second pass of the sort, for the frames that need it (frame_unsorted[f]; a channel-sorted frame is read in place): the tile's rows
-// go to their places in the SORTED COPY of the frame, and perm gets their source rows.  The tile is staged through LDS in sorted
-// order first, so that the stores walk whole runs -- in firing order a tile holds 16 rows of each of 64 channels, i.e. 64 runs of
-// 320 contiguous bytes -- instead of scattering 20-byte rows lane by lane.  The per-beam kernels and the compaction then read sorted
-// position g as row g of the copy: no gather through perm anywhere (measured on firing-order rows before this: the scan 1.83 instead of
-// 1.60 ms, the compaction's scatter 0.69 instead of 0.36 ms, this pass -- 4-byte stores scattered over 64 channel runs -- 0.32 ms).
-// identity_perm: the debug tap wants the permutation of every frame, sorted ones too.
-template <typename T>
-__global__ __launch_bounds__(SG_BLOCK) void k_sort_scatter(const T *__restrict__ rows, const uint8_t *__restrict__ ch8, const int64_t *__restrict__ frame_off,
-                                                           const int32_t *__restrict__ tile_hist, const int32_t *__restrict__ tile_base,
-                                                           const uint16_t *__restrict__ rank, int32_t *__restrict__ perm, T *__restrict__ srows,
-                                                           const int32_t *__restrict__ frame_unsorted, int identity_perm, int64_t max_tiles)
-{
-    const int f = blockIdx.y;
-    const int64_t base = frame_off[f], n = frame_off[f + 1] - base;
-    const int64_t tile0 = (int64_t)blockIdx.x * SG_TILE;
-    if (tile0 >= n) return;
-    const int tid = threadIdx.x;
-    if (!frame_unsorted[f]) {
-        if (identity_perm)
-            for (int q = 0; q < 4; ++q) { const int64_t r = tile0 + q * SG_BLOCK + tid; if (r < n) perm[base + r] = (int32_t)r; }
-        return;
-    }
-    __shared__ T stage[SG_TILE * 5];
-    __shared__ int s_dest[SG_TILE];
-    __shared__ uint16_t s_src[SG_TILE];
-    __shared__ int s_start[256];
-    const int32_t *b = tile_base + ((int64_t)f * max_tiles + blockIdx.x) * 256;
-    {   // where each channel's run starts inside the tile's sorted image: exclusive scan of the tile's histogram
-        const int c = tile_hist[((int64_t)f * max_tiles + blockIdx.x) * 256 + tid];
-        s_start[tid] = c;
-        __syncthreads();
-        for (int d = 1; d < 256; d <<= 1) {
-            const int add = tid >= d ? s_start[tid - d] : 0;
-            __syncthreads();
-            s_start[tid] += add;
-            __syncthreads();
-        }
-        const int excl = s_start[tid] - c;
-        __syncthreads();
-        s_start[tid] = excl;
-        __syncthreads();
-    }
-    const int m = (int)(n - tile0 < SG_TILE ? n - tile0 : SG_TILE);      // rows of this tile
-    for (int q = 0; q < 4; ++q) {
-        const int i = q * SG_BLOCK + tid;
-        if (i < m) {
-            const int64_t r = tile0 + i;
-            const int ch = ch8[base + r], rk = rank[base + r];
-            const int sp = s_start[ch] + rk;                                 // position in the tile's sorted image
-            const T *p = rows + (base + r) * 5;
-            const T v0 = p[0], v1 = p[1], v2 = p[2], v3 = p[3], v4 = p[4];
-            T *d = stage + sp * 5;
-            d[0] = v0; d[1] = v1; d[2] = v2; d[3] = v3; d[4] = v4;
-            s_dest[sp] = b[ch] + rk;                                         // frame-local sorted position
-            s_src[sp] = (uint16_t)i;
-        }
-    }
-    __syncthreads();
-    for (int idx = tid; idx < m * 5; idx += SG_BLOCK) {
-        const int sp = idx / 5, j = idx - sp * 5;
-        srows[(base + s_dest[sp]) * 5 + j] = stage[idx];
-    }
-    for (int sp = tid; sp < m; sp += SG_BLOCK) perm[base + s_dest[sp]] = (int32_t)(tile0 + s_src[sp]);
-}
-
-// The sorted copy for a caller-supplied permutation (no device sort): a plain gather; every frame counts as unsorted.
-template <typename T>
-__global__ __launch_bounds__(SG_BLOCK) void k_gather_rows(const T *__restrict__ rows, const int64_t *__restrict__ frame_off, const int32_t *__restrict__ perm,
-                                                          T *__restrict__ srows, int32_t *__restrict__ frame_unsorted, int32_t *__restrict__ status)
-{
-    const int f = blockIdx.y;
-    const int64_t base = frame_off[f], n = frame_off[f + 1] - base;
-    if (blockIdx.x == 0 && threadIdx.x == 0) frame_unsorted[f] = 1;
-    if (blockIdx.x == 0 && f == 0 && threadIdx.x == 0) status[1] = -1;       // (see k_sort_hist)
-    for (int64_t r = (int64_t)blockIdx.x * SG_BLOCK + threadIdx.x; r < n; r += (int64_t)gridDim.x * SG_BLOCK) {
-        const T *p = rows + (base + perm[base + r]) * 5;
-        T *d = srows + (base + r) * 5;
-        d[0] = p[0]; d[1] = p[1]; d[2] = p[2]; d[3] = p[3]; d[4] = p[4];
-    }
+    return sg_by_dtype(dtype, [&](auto t) { return sg_by_tier<WITH4>(lmax, [&](auto tier) { return f(t, tier); }); });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1202,590 +1014,7 @@ __global__ __launch_bounds__(64) void k_beams_huge(SgBeamArgs a)
 }
 
 // ------------------------------------------------------------------------------------------------
-// Segment order of the first pass.  A segment = the rows of one (frame, channel) pair in the channel-sorted order,
-// i.e. all beams of a frame that look up the same flake table.  Segments are ordered by table, so that the ~1000
-// blocks resident at any moment use one or two tables (2-3 MB each: L2-resident) instead of all 64 of a frame.
-// Three small kernels over the n_frames * 256 pairs: count segments and blocks per table (one packed 64-bit atomic
-// per pair: segments << 32 | blocks), exclusive scan over the tables, place every pair (a second packed atomic gives
-// its segment slot and its first block inside the table's range).  The order inside a table is whatever the atomics
-// give -- results do not depend on the launch order.
-struct SgPair { int64_t start; int rows; int key; };
-
-__device__ __forceinline__ SgPair sg_pair(int p, const int64_t *__restrict__ frame_off, const int32_t *__restrict__ tile_base, int64_t max_tiles,
-                                          const int32_t *__restrict__ table_ids, int n_las, int n_tables)
-{
-    SgPair r;
-    const int f = p >> 8, c = p & 255;
-    const int64_t n = frame_off[f + 1] - frame_off[f];
-    r.start = frame_off[f]; r.rows = 0; r.key = n_tables;
-    if (n <= 0) return r;                             // the sort wrote nothing for an empty frame
-    const int32_t *b = tile_base + (int64_t)f * max_tiles * 256;
-    const int64_t s0 = b[c], s1 = c < 255 ? (int64_t)b[c + 1] : n;
-    r.start += s0;
-    r.rows = (int)(s1 - s0);
-    if (c < n_las) {
-        const int id = table_ids[(int64_t)f * n_las + c];
-        if (id >= 0 && id < n_tables) r.key = id;     // unknown ids and channels without a laser go last
-    }
-    return r;
-}
-
-__global__ __launch_bounds__(256) void k_seg_count(const int64_t *__restrict__ frame_off, int n_frames, const int32_t *__restrict__ tile_base,
-                                                   int64_t max_tiles, const int32_t *__restrict__ table_ids, int n_las, int n_tables, int blk,
-                                                   unsigned long long *__restrict__ tbl_cnt, const SgTable *__restrict__ tables,
-                                                   SgTable *__restrict__ resolved)
-{
-    const int p = blockIdx.x * 256 + threadIdx.x;
-    if (p >= n_frames * 256) return;
-    if (resolved && (p & 255) < n_las) {              // table descriptor of (frame, channel): what k_resolve_tables does, one launch less
-        const int64_t i = (int64_t)(p >> 8) * n_las + (p & 255);
-        const int t = table_ids[i];
-        SgTable d{};
-        if (t >= 0 && t < n_tables) d = tables[t];
-        resolved[i] = d;
-    }
-    const SgPair r = sg_pair(p, frame_off, tile_base, max_tiles, table_ids, n_las, n_tables);
-    if (r.rows > 0) atomicAdd(&tbl_cnt[(size_t)r.key * SG_TBL_STRIDE], (1ull << 32) | (unsigned long long)((r.rows + blk - 1) / blk));
-}
-
-// exclusive scan of the packed per-table counts (both halves at once: neither overflows 32 bits); leaves the counts zero
-// so that k_seg_place can use them as cursors
-__global__ __launch_bounds__(1024) void k_seg_scan(unsigned long long *__restrict__ tbl_cnt, unsigned long long *__restrict__ tbl_base, int n,
-                                                   int32_t *__restrict__ seg_n, int32_t *__restrict__ one_chunk_blk)
-{
-    __shared__ unsigned long long sc[1024];
-    const int t = threadIdx.x;
-    const int per = (n + 1023) / 1024, b0 = t * per, b1 = b0 + per < n ? b0 + per : n;
-    unsigned long long sum = 0;
-    for (int k = b0; k < b1; ++k) sum += tbl_cnt[(size_t)k * SG_TBL_STRIDE];
-    sc[t] = sum;
-    __syncthreads();
-    for (int d = 1; d < 1024; d <<= 1) { const unsigned long long add = t >= d ? sc[t - d] : 0; __syncthreads(); sc[t] += add; __syncthreads(); }
-    unsigned long long run = sc[t] - sum;
-    for (int k = b0; k < b1; ++k) { const unsigned long long c = tbl_cnt[(size_t)k * SG_TBL_STRIDE]; tbl_base[k] = run; run += c; tbl_cnt[(size_t)k * SG_TBL_STRIDE] = 0; }
-    if (t == 1023) {
-        seg_n[0] = (int32_t)(sc[1023] >> 32); seg_n[1] = (int32_t)(sc[1023] & 0xffffffffull);
-        if (one_chunk_blk) { one_chunk_blk[0] = 0; one_chunk_blk[1] = (int32_t)(sc[1023] & 0xffffffffull); }   // the pass as ONE launch: all blocks
-    }
-}
-
-__global__ __launch_bounds__(256) void k_seg_place(const int64_t *__restrict__ frame_off, int n_frames, const int32_t *__restrict__ tile_base,
-                                                   int64_t max_tiles, const int32_t *__restrict__ table_ids, int n_las, int n_tables, int blk,
-                                                   const unsigned long long *__restrict__ tbl_base, unsigned long long *__restrict__ tbl_cur,
-                                                   int64_t *__restrict__ seg_start, int32_t *__restrict__ seg_cnt, int32_t *__restrict__ seg_frame,
-                                                   int32_t *__restrict__ seg_blk, int32_t *__restrict__ seg_of_blk)
-{
-    const int p = blockIdx.x * 256 + threadIdx.x;
-    if (p >= n_frames * 256) return;
-    const SgPair r = sg_pair(p, frame_off, tile_base, max_tiles, table_ids, n_las, n_tables);
-    if (r.rows <= 0) return;
-    const int nb = (r.rows + blk - 1) / blk;
-    const unsigned long long c = atomicAdd(&tbl_cur[(size_t)r.key * SG_TBL_STRIDE], (1ull << 32) | (unsigned long long)nb), base = tbl_base[r.key];
-    const int slot = (int)(base >> 32) + (int)(c >> 32);
-    const int b0 = (int)(base & 0xffffffffull) + (int)(c & 0xffffffffull);
-    seg_start[slot] = r.start; seg_cnt[slot] = r.rows; seg_frame[slot] = (p >> 8) | ((p & 255) << 22); seg_blk[slot] = b0;
-    for (int q = 0; q < nb; ++q) {                               // block -> what k_beams needs of its segment: one round trip per block there
-        int32_t *br = seg_of_blk + (int64_t)(b0 + q) * SG_BLKREC;
-        br[0] = slot; br[1] = (int32_t)r.start; br[2] = r.rows; br[3] = (p >> 8) | ((p & 255) << 22); br[4] = b0;
-    }
-}
-
-// The three kernels above as ONE block for batches of up to four frames (1024 (frame, channel) pairs) and up to SG_SEG_SMALL_TABLES
-// tables: per-table counts, their scan and the placement through LDS, and on the way the fill that clears everything the step counts up
-// from zero (`zero`, n_zero 64-bit words).  A small batch is bound by its chain of dependent launches: this is one link instead of five
-// (fill, three kernels, fill) and it runs on the caller's stream, so the scan needs no hop to a side stream and back (55 us between the
-// end of the sort and the start of the scan in a single sweep's trace, ~10 us now).  Same segments as the three kernels build (the order
-// inside a table is whatever the atomics give, there as here).
-#define SG_SEG_SMALL_TABLES 4096
-__global__ __launch_bounds__(1024) void k_seg_small(const int64_t *__restrict__ frame_off, int n_frames, const int32_t *__restrict__ tile_base,
-                                                    int64_t max_tiles, const int32_t *__restrict__ table_ids, int n_las, int n_tables, int blk,
-                                                    int64_t *__restrict__ seg_start, int32_t *__restrict__ seg_cnt, int32_t *__restrict__ seg_frame,
-                                                    int32_t *__restrict__ seg_blk, int32_t *__restrict__ seg_of_blk, int32_t *__restrict__ seg_n,
-                                                    int32_t *__restrict__ one_chunk_blk, const SgTable *__restrict__ tables, SgTable *__restrict__ resolved,
-                                                    unsigned long long *__restrict__ zero, int64_t n_zero)
-{
-    __shared__ unsigned long long cnt[SG_SEG_SMALL_TABLES + 1], sc[1024];
-    const int t = threadIdx.x, p = t;
-    for (int64_t i = t; i < n_zero; i += 1024) zero[i] = 0ull;
-    for (int i = t; i <= n_tables; i += 1024) cnt[i] = 0ull;
-    __syncthreads();
-    const bool mine = p < n_frames * 256;
-    SgPair r{};
-    int nb = 0;
-    if (mine) {
-        if ((p & 255) < n_las) {                      // table descriptor of (frame, channel)
-            const int64_t i = (int64_t)(p >> 8) * n_las + (p & 255);
-            const int id = table_ids[i];
-            SgTable d{};
-            if (id >= 0 && id < n_tables) d = tables[id];
-            resolved[i] = d;
-        }
-        r = sg_pair(p, frame_off, tile_base, max_tiles, table_ids, n_las, n_tables);
-        nb = (r.rows + blk - 1) / blk;
-        if (r.rows > 0) atomicAdd(&cnt[r.key], (1ull << 32) | (unsigned long long)nb);
-    }
-    __syncthreads();
-    // exclusive scan of the packed per-table counts (segments << 32 | blocks)
-    const int n = n_tables + 1, per = (n + 1023) / 1024, b0 = t * per, b1 = b0 + per < n ? b0 + per : n;
-    unsigned long long sum = 0;
-    for (int k = b0; k < b1; ++k) sum += cnt[k];
-    sc[t] = sum;
-    __syncthreads();
-    for (int d = 1; d < 1024; d <<= 1) { const unsigned long long add = t >= d ? sc[t - d] : 0; __syncthreads(); sc[t] += add; __syncthreads(); }
-    unsigned long long run = sc[t] - sum;
-    for (int k = b0; k < b1; ++k) { const unsigned long long c = cnt[k]; cnt[k] = run; run += c; }     // cnt: now the table's base, bumped below as its cursor
-    if (t == 1023) {
-        seg_n[0] = (int32_t)(sc[1023] >> 32); seg_n[1] = (int32_t)(sc[1023] & 0xffffffffull);
-        one_chunk_blk[0] = 0; one_chunk_blk[1] = (int32_t)(sc[1023] & 0xffffffffull);
-    }
-    __syncthreads();
-    if (mine && r.rows > 0) {
-        const unsigned long long c = atomicAdd(&cnt[r.key], (1ull << 32) | (unsigned long long)nb);
-        const int slot = (int)(c >> 32), bb = (int)(c & 0xffffffffull);
-        seg_start[slot] = r.start; seg_cnt[slot] = r.rows; seg_frame[slot] = (p >> 8) | ((p & 255) << 22); seg_blk[slot] = bb;
-        for (int q = 0; q < nb; ++q) {
-            int32_t *br = seg_of_blk + (int64_t)(bb + q) * SG_BLKREC;
-            br[0] = slot; br[1] = (int32_t)r.start; br[2] = r.rows; br[3] = (p >> 8) | ((p & 255) << 22); br[4] = bb;
-        }
-    }
-}
-
-// get_fov_flag(calib.lidar_to_rect(xyz), (h, w), calib) (simulation.py:39-47, :535-536) in float64, fixed operation order.
-// The projection is OpenPCDet's (pcdet/utils/calibration_kitti.py, the reference's un-vendored submodule lib/OpenPCDet:
-// parity unpinned, SURVEY 8 c): rect_to_img divides the image coordinates by the RECTIFIED point's z, not by the third
-// homogeneous coordinate -- the two differ by P2[2][3], which real KITTI files carry (~ 3e-3) --, and the depth is that
-// coordinate minus P2[2][3].
-__device__ __forceinline__ bool sg_in_fov(const SgFov &v, double x, double y, double z)
-{
-    double r[3];
-    for (int j = 0; j < 3; ++j) r[j] = ((x * v.m[j] + y * v.m[3 + j]) + z * v.m[6 + j]) + v.m[9 + j];
-    double h[3];
-    for (int j = 0; j < 3; ++j) h[j] = ((r[0] * v.p[4 * j] + r[1] * v.p[4 * j + 1]) + r[2] * v.p[4 * j + 2]) + v.p[4 * j + 3];
-    const double u = h[0] / r[2], w = h[1] / r[2];
-    const double depth = h[2] - v.p[11];
-    return u >= 0 && u < v.img_w && w >= 0 && w < v.img_h && depth >= 0;
-}
-
-// per frame: tile offsets of the kept rows and the statistics (simulation.py:522-530).  diff2 (per frame: twice the intensity-
-// difference sum of the attenuated beams, final once the per-beam kernels are through) may be null: the pre-augment crop has none.
-// One WAVE (all 64 lanes call it): lane l takes tiles l, l + 64, .. -- the counts come in one round of loads per 64 tiles and are summed by
-// shuffles (one thread walking the tiles waited for every load in turn: 21 us for a sweep's 47 tiles, a tenth of a single sweep's chain).
-// tile_cnt / tile_mv may have been written by other blocks of the running launch (k_compact_count's last block): read past the L1.
-__device__ __forceinline__ void sg_compact_scan_frame(int f, int64_t n, const int32_t *tile_cnt, int32_t *__restrict__ tile_base, int64_t *__restrict__ out_counts,
-                                                      int64_t *__restrict__ out_stats, const unsigned long long *diff2, int64_t max_tiles,
-                                                      const int32_t *tile_mv, int32_t *__restrict__ tile_mv_base, int64_t *__restrict__ out_mv_counts)
-{
-    const int lane = threadIdx.x & 63;
-    const int64_t tiles = (n + SG_TILE - 1) / SG_TILE;
-    const volatile int32_t *vc = tile_cnt + (int64_t)f * max_tiles, *vm = tile_mv ? tile_mv + (int64_t)f * max_tiles : nullptr;
-    int run = 0, mrun = 0;
-    int64_t att = 0;
-    for (int64_t t0 = 0; t0 < tiles; t0 += 64) {
-        const int64_t t = t0 + lane;
-        const int c = t < tiles ? vc[t] : 0;
-        const int m = (vm && t < tiles) ? vm[t] : 0;
-        const int kc = c & 0xffff;
-        int ik = kc, im = m, ia = c >> 16;       // inclusive prefix of the kept / moved counts, total of the attenuated
-        for (int o = 1; o < 64; o <<= 1) {
-            const int a = __shfl_up(ik, o), b = __shfl_up(im, o);
-            if (lane >= o) { ik += a; im += b; }
-            ia += __shfl_xor(ia, o);
-        }
-        if (t < tiles) {
-            tile_base[(int64_t)f * max_tiles + t] = run + ik - kc;
-            if (vm) tile_mv_base[(int64_t)f * max_tiles + t] = mrun + im - m;
-        }
-        run += __shfl(ik, 63); mrun += __shfl(im, 63); att += ia;
-    }
-    if (lane != 0) return;
-    if (out_mv_counts) out_mv_counts[f] = mrun;
-    out_counts[f] = run;
-    out_stats[f * 3 + 0] = att;              // num_attenuated (:525)
-    out_stats[f * 3 + 1] = n - run;          // num_removed (simulation.py:522, + the camera crop :538)
-    const double diff_sum = diff2 ? (double)(long long)((const volatile unsigned long long *)diff2)[f] / 2.0 : 0.0;
-    out_stats[f * 3 + 2] = att > 0 ? (int64_t)(diff_sum / (double)att) : 0;   // :527-530 int()
-}
-
-__global__ __launch_bounds__(64) void k_compact_scan(const int64_t *__restrict__ frame_off,
-                                                     const int32_t *__restrict__ tile_cnt,
-                                                     int32_t *__restrict__ tile_base, int64_t *__restrict__ out_counts,
-                                                     int64_t *__restrict__ out_stats, const unsigned long long *__restrict__ diff2, int64_t max_tiles,
-                                                     const int32_t *__restrict__ tile_mv, int32_t *__restrict__ tile_mv_base, int64_t *__restrict__ out_mv_counts)
-{
-    const int f = blockIdx.x;
-    sg_compact_scan_frame(f, frame_off[f + 1] - frame_off[f], tile_cnt, tile_base, out_counts, out_stats, diff2, max_tiles, tile_mv, tile_mv_base, out_mv_counts);
-}
-
-// Stable compaction of kept rows, per frame.  keep byte: bit 0 = row is in the output, bit 1 = row passed the noise filter
-// (num_attenuated counts those, before the camera crop: simulation.py:525 precedes :532-540).
-template <typename T>
-__global__ __launch_bounds__(SG_BLOCK) void k_compact_count(const T *__restrict__ rows_in, const T *__restrict__ srows, const int32_t *__restrict__ frame_unsorted,
-                                                            const uint32_t *__restrict__ rec,
-                                                            const uint32_t *__restrict__ rec_q, const T *__restrict__ rng, const double *__restrict__ thr_poly,
-                                                            uint8_t *__restrict__ keep, const int64_t *__restrict__ frame_off,
-                                                            int32_t *__restrict__ tile_cnt, int64_t max_tiles, SgFov fov, int32_t *__restrict__ tile_mv,
-                                                            unsigned long long *__restrict__ tiles_done, int32_t *__restrict__ tile_base, int64_t *__restrict__ out_counts,
-                                                            int64_t *__restrict__ out_stats, const unsigned long long *__restrict__ diff2,
-                                                            int32_t *__restrict__ tile_mv_base, int64_t *__restrict__ out_mv_counts)
-{
-    const int f = blockIdx.y;
-    const int64_t base = frame_off[f], n = frame_off[f + 1] - base;
-    const int64_t tile0 = (int64_t)blockIdx.x * SG_TILE;
-    if (tile0 >= n) {
-        if (tiles_done && blockIdx.x == 0 && threadIdx.x == 0) {       // an empty frame has no tile to complete it: its counts here
-            out_counts[f] = 0; out_stats[f * 3 + 0] = 0; out_stats[f * 3 + 1] = 0; out_stats[f * 3 + 2] = 0;
-            if (out_mv_counts) out_mv_counts[f] = 0;
-        }
-        return;
-    }
-    const T *rows = frame_unsorted[f] ? srows : rows_in;            // sorted position g = row g (see k_sort_scatter)
-    const double p0 = thr_poly[(int64_t)f * 3], p1 = thr_poly[(int64_t)f * 3 + 1], p2 = thr_poly[(int64_t)f * 3 + 2];
-    int c = 0, mv = 0;                               // mv: kept rows with label 2 (packed result transfer: their coordinates travel apart)
-    // the four rows of a thread side by side: records and ranges first, then the records behind queue slots (a dependent gather for a third
-    // of the rows), then the decisions -- row after row the kernel was a chain of up to twelve latencies per thread (1.9 TB/s)
-    uint32_t rcs[4];
-    T dds[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const int64_t r = tile0 + q * SG_BLOCK + threadIdx.x;
-        rcs[q] = r < n ? rec[base + r] : 0u;
-        dds[q] = (r < n && rng != nullptr) ? rng[base + r] : (T)0;      // (unused for rows the pass over all rows did not simulate)
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-        if (rcs[q] & SG_REC_SLOT) rcs[q] = rec_q[rcs[q] & ~SG_REC_SLOT];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const int64_t r = tile0 + q * SG_BLOCK + threadIdx.x;
-        if (r >= n) continue;
-        // keep = (label == 2) | (intensity > p0 d^2 + p1 d + p2), d the ORIGINAL range, d^2 in the row dtype
-        // (simulation.py:465, :469, :518-520)
-        const uint32_t rc = rcs[q];
-        const int lab_i = (int)((rc >> SG_REC_LABEL_SHIFT) & 3u);
-        // Without the camera crop the decision needs the label, the (new or original) intensity and the original range only: a
-        // beam the pass over all rows simulated left its range in rng, and the record holds the intensity unless the beam came
-        // back unchanged from a later kernel -- those, and rows without a laser, read the row as before.
-        const bool from_rec = rng != nullptr && !fov.enabled && !(rc & SG_REC_COPY) && (lab_i != 0 || (rc & SG_REC_HAS_I));
-        bool noise_ok, is_att;
-        bool k;
-        if (from_rec) {
-            const T dd = dds[q];
-            const T dd2 = dd * dd;
-            const double thr = (p0 * (double)dd2 + p1 * (double)dd) + p2;
-            noise_ok = (lab_i == 2) || ((double)(T)(int)(rc & 255u) > thr);
-            is_att = lab_i == 1;
-            k = noise_ok;
-        } else {
-            const SgRow<T> o = sg_rebuild_row<T>(rows + (base + r) * 5, rc);
-            const T dd2 = o.dd * o.dd;
-            const double thr = (p0 * (double)dd2 + p1 * (double)o.dd) + p2;
-            noise_ok = (o.lab == (T)2) || ((double)o.i > thr);
-            is_att = o.lab == (T)1;
-            k = noise_ok;
-            if (fov.enabled && k) k = sg_in_fov(fov, (double)o.x, (double)o.y, (double)o.z);   // :532-540
-        }
-        keep[base + r] = (uint8_t)((k ? 1 : 0) | (noise_ok ? 2 : 0));
-        c += k;
-        mv += (k && lab_i == 2) ? 1 : 0;
-        c += (noise_ok && is_att) ? (1 << 16) : 0;                          // high half: rows that count in num_attenuated (:525, before the crop)
-    }
-    __shared__ int s[4], s2[4], s_last;
-    for (int o = 32; o > 0; o >>= 1) { c += __shfl_down(c, o); mv += __shfl_down(mv, o); }
-    if ((threadIdx.x & 63) == 0) { s[threadIdx.x >> 6] = c; s2[threadIdx.x >> 6] = mv; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        tile_cnt[(int64_t)f * max_tiles + blockIdx.x] = s[0] + s[1] + s[2] + s[3];   // kept | attenuated << 16 (a tile has 1024 rows)
-        if (tile_mv) tile_mv[(int64_t)f * max_tiles + blockIdx.x] = s2[0] + s2[1] + s2[2] + s2[3];
-        // Small batches (tiles_done != null): the block that completes a frame scans its tiles -- what k_compact_scan does as a launch of its
-        // own: one link less on the chain.  Not for large batches: the device-scope fence this needs writes back the L2 of the block's XCD
-        // (eight XCDs, eight L2s), and 32 768 of them made this kernel 1.37 ms long on 256 sweeps instead of 0.15.
-        if (tiles_done) {
-            __threadfence();
-            const unsigned long long tiles = (unsigned long long)((n + SG_TILE - 1) / SG_TILE);
-            s_last = atomicAdd(&tiles_done[f], 1ull) == tiles - 1;
-            if (s_last) __threadfence();
-        }
-    }
-    if (tiles_done) {                                 // (kernel argument: uniform)
-        __syncthreads();
-        if (s_last && threadIdx.x < 64)
-            sg_compact_scan_frame(f, n, tile_cnt, tile_base, out_counts, out_stats, diff2, max_tiles, tile_mv, tile_mv_base, out_mv_counts);
-    }
-}
-
-// PACK (packed result transfer, snowgpu_set_result_transfer): instead of the 5-column output row, per kept row a 4-byte word -- source row
-// (30 bits) | label 0 / 1 / 2, or 3 = "column 4 keeps the input's channel value" (Q5) -- and its output intensity (row dtype); the moved
-// coordinates of the label-2 rows (simulation.py:176-180), a small minority, go to a list of their own in output order.  The host side of
-// the library copies x, y, z (and the channel of code-3 rows) from the caller's INPUT rows: 8 instead of 24 bytes per point cross the link.
-struct SgPack { uint32_t *meta; void *inten; void *mv; const int32_t *tile_mv_base; const int64_t *mv_counts; };
-
-template <typename T, bool PACK>
-__global__ __launch_bounds__(SG_BLOCK) void k_compact_scatter(const T *__restrict__ rows_in, const T *__restrict__ srows, const int32_t *__restrict__ frame_unsorted,
-                                                              const uint32_t *__restrict__ rec,
-                                                              const uint32_t *__restrict__ rec_q, const uint8_t *__restrict__ keep, const int32_t *__restrict__ perm,
-                                                              const int64_t *__restrict__ frame_off,
-                                                              const int32_t *__restrict__ tile_base, T *__restrict__ out_rows,
-                                                              int32_t *__restrict__ out_src, int64_t *__restrict__ out_stats,
-                                                              int64_t max_tiles, SgPack pk)
-{
-    const int f = blockIdx.y;
-    const int64_t base = frame_off[f], n = frame_off[f + 1] - base;
-    const int64_t tile0 = (int64_t)blockIdx.x * SG_TILE;
-    if (tile0 >= n) return;
-    const bool uns = frame_unsorted[f] != 0;
-    const T *rows = uns ? srows : rows_in;
-    __shared__ int wave_cnt[4][4];               // [round][wave]
-    [[maybe_unused]] __shared__ int wave_mv[4][4];
-    const int tid = threadIdx.x, w = tid >> 6;
-    bool k[4];
-    int pre[4];
-    uint32_t rcs[4];
-    [[maybe_unused]] int pre_mv[4];
-    // keep flags, then the kept rows' records, then the records behind queue slots: each kind for the thread's four rows at once (row after
-    // row they were a chain of dependent loads; see k_compact_count)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const int64_t r = tile0 + q * SG_BLOCK + tid;
-        k[q] = r < n && (keep[base + r] & 1);
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) rcs[q] = k[q] ? rec[base + tile0 + q * SG_BLOCK + tid] : 0u;
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-        if (rcs[q] & SG_REC_SLOT) rcs[q] = rec_q[rcs[q] & ~SG_REC_SLOT];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const unsigned long long m = __ballot(k[q]);
-        pre[q] = __popcll(m & sg_lanemask_lt());
-        if ((tid & 63) == 0) wave_cnt[q][w] = __popcll(m);
-        if constexpr (PACK) {
-            const unsigned long long mm = __ballot(k[q] && ((rcs[q] >> SG_REC_LABEL_SHIFT) & 3u) == 2u);
-            pre_mv[q] = __popcll(mm & sg_lanemask_lt());
-            if ((tid & 63) == 0) wave_mv[q][w] = __popcll(mm);
-        }
-    }
-    __syncthreads();
-    int run = tile_base[(int64_t)f * max_tiles + blockIdx.x];
-    [[maybe_unused]] int64_t mrun = 0;
-    if constexpr (PACK) {
-        // the moved coordinates of a batch form ONE list in output order (one copy down the link): this frame's part starts behind
-        // those of the frames before it (a handful of frames per call: summed here rather than scanned by another launch)
-        for (int g = 0; g < f; ++g) mrun += pk.mv_counts[g];
-        mrun += pk.tile_mv_base[(int64_t)f * max_tiles + blockIdx.x];
-    }
-    for (int q = 0; q < 4; ++q) {
-        int off = run;
-        for (int ww = 0; ww < w; ++ww) off += wave_cnt[q][ww];
-        if (k[q]) {
-            const int64_t r = base + tile0 + q * SG_BLOCK + tid;
-            const int64_t dst = base + off + pre[q];
-            const int32_t src = uns ? perm[r] : (int32_t)(r - base);
-            if constexpr (PACK) {
-                const uint32_t rc = rcs[q];
-                const SgRow<T> o = sg_rebuild_row<T>(rows + r * 5, rc);
-                const uint32_t label = (rc >> SG_REC_LABEL_SHIFT) & 3u;
-                const uint32_t code = (label == 0 && (rc & SG_REC_COPY)) ? 3u : label;
-                pk.meta[dst] = (uint32_t)src | (code << 30);
-                ((T *)pk.inten)[dst] = o.i;
-                if (label == 2) {
-                    int64_t moff = mrun + pre_mv[q];
-                    for (int ww = 0; ww < w; ++ww) moff += wave_mv[q][ww];
-                    T *d = (T *)pk.mv + moff * 3;
-                    d[0] = o.x; d[1] = o.y; d[2] = o.z;
-                }
-            } else {
-                const SgRow<T> o = sg_rebuild_row<T>(rows + r * 5, rcs[q]);
-                T *d = out_rows + dst * 5;
-                d[0] = o.x; d[1] = o.y; d[2] = o.z; d[3] = o.i; d[4] = o.lab;
-                out_src[dst] = src;
-            }
-        }
-        run += wave_cnt[q][0] + wave_cnt[q][1] + wave_cnt[q][2] + wave_cnt[q][3];
-        if constexpr (PACK) mrun += wave_mv[q][0] + wave_mv[q][1] + wave_mv[q][2] + wave_mv[q][3];
-    }
-}
-
-// ---- pre-augment camera crop (precompute.py:96-99): pc = pc[get_fov_flag(lidar_to_rect(pc[:, 0:3]), (1024, 1920))] -----
-// Stable compaction of the INPUT rows of every frame by the FOV test on their original coordinates: flag + tile counts,
-// per-frame scan (k_compact_scan), then scatter to the frame's new offset.
-template <typename T>
-__global__ __launch_bounds__(SG_BLOCK) void k_crop_flag(const T *__restrict__ rows, const int64_t *__restrict__ frame_off,
-                                                        uint8_t *__restrict__ keep, int32_t *__restrict__ tile_cnt, int64_t max_tiles, SgFov fov)
-{
-    const int f = blockIdx.y;
-    const int64_t base = frame_off[f], n = frame_off[f + 1] - base;
-    const int64_t tile0 = (int64_t)blockIdx.x * SG_TILE;
-    if (tile0 >= n) return;
-    int c = 0;
-    for (int q = 0; q < 4; ++q) {
-        const int64_t r = tile0 + q * SG_BLOCK + threadIdx.x;
-        if (r >= n) continue;
-        const T *row = rows + (base + r) * 5;
-        const bool k = sg_in_fov(fov, (double)row[0], (double)row[1], (double)row[2]);
-        keep[base + r] = k ? 1 : 0;
-        c += k;
-    }
-    __shared__ int s[4];
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o);
-    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) tile_cnt[(int64_t)f * max_tiles + blockIdx.x] = s[0] + s[1] + s[2] + s[3];
-}
-
-template <typename T>
-__global__ __launch_bounds__(SG_BLOCK) void k_crop_scatter(const T *__restrict__ rows, const uint8_t *__restrict__ keep,
-                                                           const int64_t *__restrict__ frame_off, const int64_t *__restrict__ new_off,
-                                                           const int32_t *__restrict__ tile_base, T *__restrict__ out_rows,
-                                                           int32_t *__restrict__ crop_src, int64_t max_tiles)
-{
-    const int f = blockIdx.y;
-    const int64_t base = frame_off[f], n = frame_off[f + 1] - base;
-    const int64_t tile0 = (int64_t)blockIdx.x * SG_TILE;
-    if (tile0 >= n) return;
-    __shared__ int wave_cnt[4][4];
-    const int tid = threadIdx.x, w = tid >> 6;
-    bool k[4];
-    int pre[4];
-    for (int q = 0; q < 4; ++q) {
-        const int64_t r = tile0 + q * SG_BLOCK + tid;
-        k[q] = r < n && keep[base + r];
-        const unsigned long long m = __ballot(k[q]);
-        pre[q] = __popcll(m & sg_lanemask_lt());
-        if ((tid & 63) == 0) wave_cnt[q][w] = __popcll(m);
-    }
-    __syncthreads();
-    int run = tile_base[(int64_t)f * max_tiles + blockIdx.x];
-    const int64_t nbase = new_off[f];
-    for (int q = 0; q < 4; ++q) {
-        int off = run;
-        for (int ww = 0; ww < w; ++ww) off += wave_cnt[q][ww];
-        if (k[q]) {
-            const int64_t r = tile0 + q * SG_BLOCK + tid;
-            const T *sr = rows + (base + r) * 5;
-            T *d = out_rows + (nbase + off + pre[q]) * 5;
-            d[0] = sr[0]; d[1] = sr[1]; d[2] = sr[2]; d[3] = sr[3]; d[4] = sr[4];
-            crop_src[nbase + off + pre[q]] = (int32_t)r;
-        }
-        run += wave_cnt[q][0] + wave_cnt[q][1] + wave_cnt[q][2] + wave_cnt[q][3];
-    }
-}
-// ------------------------------------------------------------------------------------------------
-// Compact input (snowgpu_augment_batch_compact): rows that crossed the link as (x, y, z, intensity) float32 + one channel BYTE -- 17 bytes
-// per point instead of the STF row's 20 (precompute.py:78 keeps the channel as a fifth float32) -- become the (x, y, z, intensity,
-// channel) rows every kernel reads.  One thread per row; the batch's only pass that exists for the link's sake (0.67 GB written per
-// 256 sweeps, spread over the chunks of the pipeline).
-__global__ __launch_bounds__(256) void k_expand_rows(const float4 *__restrict__ xyzi, const uint8_t *__restrict__ ch, float *__restrict__ rows, int64_t n)
-{
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const float4 v = xyzi[i];
-    float *r = rows + i * 5;
-    r[0] = v.x; r[1] = v.y; r[2] = v.z; r[3] = v.w; r[4] = (float)ch[i];
-}
-
-
-// table_ids[frame][channel] -> the table descriptor itself, so that a beam needs one load instead of two dependent ones
-__global__ void k_resolve_tables(const SgTable *__restrict__ tables, int n_tables, const int32_t *__restrict__ table_ids,
-                                 int64_t n, SgTable *__restrict__ out)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int t = table_ids[i];
-    SgTable d{};
-    if (t >= 0 && t < n_tables) d = tables[t];
-    out[i] = d;
-}
-
-// ------------------------------------------------------------------------------------------------
 // launch wrappers (C linkage, called from snowgpu_batch.cpp and snowgpu_host.cpp)
-
-#define SG_CHECK_LAUNCH()                                  \
-    do {                                                   \
-        hipError_t e__ = hipGetLastError();                \
-        if (e__ != hipSuccess) return (int)e__;            \
-    } while (0)
-
-extern "C" int sg_launch_expand_rows(const void *xyzi, const uint8_t *ch, void *rows, int64_t n, void *stream)
-{
-    if (n <= 0) return 0;
-    hipLaunchKernelGGL(k_expand_rows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const float4 *)xyzi, ch, (float *)rows, n);
-    SG_CHECK_LAUNCH();
-    return 0;
-}
-
-extern "C" int sg_launch_resolve_tables(const SgTable *tables, int n_tables, const int32_t *table_ids, int64_t n, SgTable *out,
-                                        void *stream)
-{
-    if (n <= 0) return 0;
-    hipLaunchKernelGGL(k_resolve_tables, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, tables, n_tables,
-                       table_ids, n, out);
-    SG_CHECK_LAUNCH();
-    return 0;
-}
-
-// lean_plane / lean_part: optional -- the ground planes (n_frames x 4) and the tile-partials buffer of the noise-threshold prepass
-// (sg_prepass_reserve_tiles): the first kernel then leaves the prepass' per-tile statistics on its way over the rows
-extern "C" int sg_launch_sort(const void *rows, int dtype, const int64_t *frame_off, int n_frames, int64_t n_total,
-                              int32_t *tile_hist, int32_t *tile_base, uint16_t *rank, uint8_t *ch8, int32_t *perm, int32_t *status,
-                              int64_t max_tiles, const double *lean_plane, double *lean_part, int32_t *tile_unsorted, int32_t *frame_unsorted,
-                              void *srows, int identity_perm, int phase /* 1: histogram + scan; 2: scatter; 3: both */, void *stream)
-{
-    (void)n_total;
-    hipStream_t st = (hipStream_t)stream;
-    dim3 grid((unsigned)max_tiles, (unsigned)n_frames);
-    SgLeanTile lt{};
-    lt.plane = lean_plane; lt.delta = 0.5; lt.part = lean_part; lt.max_tiles = max_tiles;
-    if (!(phase & 1)) goto scatter;
-    if (lean_plane && lean_part) {
-        if (dtype == 0) hipLaunchKernelGGL((k_sort_hist<float, true>), grid, dim3(SG_BLOCK), 0, st, (const float *)rows, frame_off, tile_hist, rank, ch8, status, max_tiles, lt, tile_unsorted);
-        else hipLaunchKernelGGL((k_sort_hist<double, true>), grid, dim3(SG_BLOCK), 0, st, (const double *)rows, frame_off, tile_hist, rank, ch8, status, max_tiles, lt, tile_unsorted);
-    } else {
-        if (dtype == 0) hipLaunchKernelGGL((k_sort_hist<float, false>), grid, dim3(SG_BLOCK), 0, st, (const float *)rows, frame_off, tile_hist, rank, ch8, status, max_tiles, lt, tile_unsorted);
-        else hipLaunchKernelGGL((k_sort_hist<double, false>), grid, dim3(SG_BLOCK), 0, st, (const double *)rows, frame_off, tile_hist, rank, ch8, status, max_tiles, lt, tile_unsorted);
-    }
-    SG_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_sort_scan, dim3(n_frames), dim3(SG_BLOCK), 0, st, frame_off, tile_hist, tile_base, max_tiles, tile_unsorted, frame_unsorted);
-    SG_CHECK_LAUNCH();
-scatter:
-    if (!(phase & 2)) return 0;
-    if (dtype == 0) hipLaunchKernelGGL(k_sort_scatter<float>, grid, dim3(SG_BLOCK), 0, st, (const float *)rows, ch8, frame_off, tile_hist, tile_base, rank, perm, (float *)srows, frame_unsorted, identity_perm, max_tiles);
-    else hipLaunchKernelGGL(k_sort_scatter<double>, grid, dim3(SG_BLOCK), 0, st, (const double *)rows, ch8, frame_off, tile_hist, tile_base, rank, perm, (double *)srows, frame_unsorted, identity_perm, max_tiles);
-    SG_CHECK_LAUNCH();
-    return 0;
-}
-
-extern "C" int sg_launch_gather_rows(const void *rows, int dtype, const int64_t *frame_off, int n_frames, int64_t n_total, int64_t max_frame,
-                                     const int32_t *perm, void *srows, int32_t *frame_unsorted, int32_t *status, void *stream)
-{
-    (void)n_total;
-    if (n_frames <= 0) return 0;
-    hipStream_t st = (hipStream_t)stream;
-    dim3 grid((unsigned)std::max<int64_t>(1, std::min<int64_t>((max_frame + SG_BLOCK - 1) / SG_BLOCK, 256)), (unsigned)n_frames);
-    if (dtype == 0) hipLaunchKernelGGL(k_gather_rows<float>, grid, dim3(SG_BLOCK), 0, st, (const float *)rows, frame_off, perm, (float *)srows, frame_unsorted, status);
-    else hipLaunchKernelGGL(k_gather_rows<double>, grid, dim3(SG_BLOCK), 0, st, (const double *)rows, frame_off, perm, (double *)srows, frame_unsorted, status);
-    SG_CHECK_LAUNCH();
-    return 0;
-}
-
-static int sg_cu_count(int dev_id)
-{
-    int cus = 256;
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev_id);
-    return cus > 0 ? cus : 256;
-}
-
-template <typename K>
-static int sg_set_lds(K kernel, size_t lds, bool *attr_set)
-{
-    int dev_id = 0;
-    (void)hipGetDevice(&dev_id);
-    if (dev_id < 0 || dev_id >= 64 || !attr_set[dev_id]) {          // per device: several contexts may live in one process
-        hipError_t e = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-        if (dev_id >= 0 && dev_id < 64) attr_set[dev_id] = true;
-    }
-    return 0;
-}
 
 template <typename T, int LMAX, int BLOCK, bool LIST, int DICT>
 static int launch_beams_t(const SgBeamArgs *a, hipStream_t st)
@@ -1801,10 +1030,8 @@ static int launch_beams_t(const SgBeamArgs *a, hipStream_t st)
     if (LIST) {                                          // list mode: at most what the chip can hold at once
         const int64_t n = (int64_t)a->work_hi - a->work_lo;
         if (n <= 0) return 0;
-        int dev_id = 0;
-        (void)hipGetDevice(&dev_id);
         const unsigned per_cu = (unsigned)std::min<size_t>(32 * 64 / THREADS, std::max<size_t>(1, (size_t)(160 * 1024) / lds));
-        blocks = (unsigned)std::min<int64_t>((n + BLOCK - 1) / BLOCK, (int64_t)sg_cu_count(dev_id) * per_cu);
+        blocks = (unsigned)std::min<int64_t>((n + BLOCK - 1) / BLOCK, (int64_t)sg_cu_count() * per_cu);
         // the in-place pass only sees the entries beyond the hand-over buffer, i.e. normally none: a small grid (its LDS-heavy
         // blocks would otherwise queue for CU space just to find that out)
         blocks = std::min(blocks, 128u);
@@ -1817,16 +1044,6 @@ static int launch_beams_t(const SgBeamArgs *a, hipStream_t st)
     return 0;
 }
 
-template <typename T, int LMAX, int BLOCK>
-static int launch_beams_m(const SgBeamArgs *a, int direct, hipStream_t st)
-{
-    if (direct) {
-        if (a->exact_math) return launch_beams_t<T, LMAX, BLOCK, false, 2>(a, st);   // (registers to spare for tangent, root and quotient in its loop)
-        return launch_beams_t<T, LMAX, BLOCK, false, 1>(a, st);
-    }
-    return launch_beams_t<T, LMAX, BLOCK, true, 0>(a, st);
-}
-
 template <typename T, int LMAX, int BLOCK, bool LISTQ>
 static int launch_power_t(const SgBeamArgs *a, hipStream_t st, bool plan_only = false, hipEvent_t ev_few = nullptr, int which = 3)
 {
@@ -1834,16 +1051,15 @@ static int launch_power_t(const SgBeamArgs *a, hipStream_t st, bool plan_only = 
     static bool attr_set[64] = {};
     if (int e = sg_set_lds(k_power<T, LMAX, BLOCK, LISTQ>, lds, attr_set)) return e;
     constexpr int THREADS = BLOCK < 64 ? 64 : BLOCK, LANES = BLOCK < 64 ? BLOCK : 64;
-    int dev_id = 0;
-    (void)hipGetDevice(&dev_id);
+    const int cus = sg_cu_count();
     // persistent waves: what the chip holds at once (LDS and the 32-waves-per-CU limit), fewer if the queue cannot be longer
     unsigned per_cu = (unsigned)std::min<size_t>(32 * 64 / THREADS, std::max<size_t>(1, (size_t)(160 * 1024) / lds));
     // the queue of the pass over all rows: its persistent blocks would hold every CU's LDS until they are done, while the
     // later tiers and the prepass run beside it -- it takes a share (in quarters) of what fits
     if (!LISTQ && a->kp_lds_quarters > 0 && a->kp_lds_quarters < 4) per_cu = std::max(1u, per_cu * (unsigned)a->kp_lds_quarters / 4u);
-    int64_t blocks = (int64_t)sg_cu_count(dev_id) * per_cu;
+    int64_t blocks = (int64_t)cus * per_cu;
     int64_t items_ub = LISTQ ? ((int64_t)a->work_hi + LANES - 1) / LANES : (a->n_total + LANES - 1) / LANES + 2 * a->n_regions_ub;
-    if (LISTQ && a->work_hint > 0) items_ub = std::min<int64_t>(items_ub, (4 * (int64_t)a->work_hint + LANES - 1) / LANES + 8);   // (see launch_tier_scan_t)
+    if (LISTQ && a->work_hint > 0) items_ub = std::min<int64_t>(items_ub, (4 * (int64_t)a->work_hint + LANES - 1) / LANES + 8);   // (see sg_launch_tier_scan)
     blocks = std::min<int64_t>(blocks, (items_ub + THREADS / 64 - 1) / (THREADS / 64));
     if (blocks <= 0) return 0;
     if (!LISTQ) {
@@ -1861,7 +1077,7 @@ static int launch_power_t(const SgBeamArgs *a, hipStream_t st, bool plan_only = 
         }
         if (a->pw_items1 && (which & 1)) {            // the beams with few flakes: ahead of k_power on its stream (beside it, on the
             hipStream_t s1 = st;                      // tiers' stream, was measured: 4.67 instead of 4.59 ms)
-            const unsigned g1 = (unsigned)std::min<int64_t>((int64_t)sg_cu_count(dev_id) * 4, (a->n_total / LANES + a->n_regions_ub + 3) / 4);
+            const unsigned g1 = (unsigned)std::min<int64_t>((int64_t)cus * 4, (a->n_total / LANES + a->n_regions_ub + 3) / 4);
             if (g1 > 0) {
                 if (a->front_max == 1) hipLaunchKernelGGL((k_power_few<T, 1>), dim3(g1), dim3(256), 0, s1, *a, SG_QPLANES(LMAX));
                 else if (a->front_max == 2) hipLaunchKernelGGL((k_power_few<T, 2>), dim3(g1), dim3(256), 0, s1, *a, SG_QPLANES(LMAX));
@@ -1878,67 +1094,49 @@ static int launch_power_t(const SgBeamArgs *a, hipStream_t st, bool plan_only = 
 }
 
 // the LDS-free scan of a later tier (class a->cls, capacity lmax = 8, 16 or 63): fills the tier's hand-over buffer, flakes in scan order
-template <typename T>
-static int launch_tier_scan_t(const SgBeamArgs *a, int lmax, hipStream_t st)
+extern "C" int sg_launch_tier_scan(const SgBeamArgs *a, int dtype, int lmax, void *stream)
 {
     const int64_t n = (int64_t)a->work_hi - a->work_lo;
     if (n <= 0) return 0;
-    int dev_id = 0;
-    (void)hipGetDevice(&dev_id);
     int64_t want = (n + 255) / 256;
     // (a class that held a handful of beams in the batches before gets a grid for four times that, not one for its buffer: 8192 waves queued
     // for CUs beside the persistent kernels of the phase to find 23 beams -- 0.36 ms; the fixed grid strides, so a low guess only costs time)
     if (a->work_hint > 0) want = std::min<int64_t>(want, (4 * (int64_t)a->work_hint + 255) / 256 + 8);
-    const unsigned blocks = (unsigned)std::min<int64_t>(want, (int64_t)sg_cu_count(dev_id) * 8);
-    if (lmax == 8) hipLaunchKernelGGL((k_tier_scan_direct<T, 8>), dim3(blocks), dim3(256), 0, st, *a);
-    else if (lmax == 16) hipLaunchKernelGGL((k_tier_scan_direct<T, 16>), dim3(blocks), dim3(256), 0, st, *a);
-    else hipLaunchKernelGGL((k_tier_scan_direct<T, SG_LCAP>), dim3(blocks), dim3(256), 0, st, *a);
-    SG_CHECK_LAUNCH();
-    return 0;
-}
-
-extern "C" int sg_launch_tier_scan(const SgBeamArgs *a, int dtype, int lmax, void *stream)
-{
-    return dtype == 0 ? launch_tier_scan_t<float>(a, lmax, (hipStream_t)stream) : launch_tier_scan_t<double>(a, lmax, (hipStream_t)stream);
+    const unsigned blocks = (unsigned)std::min<int64_t>(want, (int64_t)sg_cu_count() * 8);
+    return sg_by_dtype_tier<false>(dtype, lmax, [&](auto t, auto tier) {
+        hipLaunchKernelGGL((k_tier_scan_direct<decltype(t), decltype(tier)::LMAX>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, *a);
+        SG_CHECK_LAUNCH();
+        return 0;
+    });
 }
 
 // threads per block of the pass with list capacity lmax (the segment builder counts blocks of this size)
-extern "C" int sg_beams_block(int lmax) { return lmax == 4 ? 256 : (lmax == 8 ? SG_LANES_8 : (lmax == 16 ? SG_LANES_16 : SG_LANES_63)); }
+extern "C" int sg_beams_block(int lmax)
+{
+    return sg_by_tier<true>(lmax, [](auto tier) { return decltype(tier)::BLOCK; });
+}
 
 // lmax = per-beam list capacity of this pass: 4 (160 B of LDS per beam: 16 waves per CU), 8, 16 or 63 (the largest
 // LDS list).  direct: the pass over all rows, dict hand-over to sg_launch_power; else list mode over class a->cls, in place.
 extern "C" int sg_launch_beams(const SgBeamArgs *a, int dtype, int lmax, int direct, void *stream)
 {
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == 0) {
-        if (lmax == 4) return launch_beams_m<float, 4, 256>(a, direct, st);
-        if (lmax == 8) return launch_beams_m<float, 8, SG_LANES_8>(a, direct, st);
-        if (lmax == 16) return launch_beams_m<float, 16, SG_LANES_16>(a, direct, st);
-        return launch_beams_m<float, SG_LCAP, SG_LANES_63>(a, direct, st);
-    }
-    if (lmax == 4) return launch_beams_m<double, 4, 256>(a, direct, st);
-    if (lmax == 8) return launch_beams_m<double, 8, SG_LANES_8>(a, direct, st);
-    if (lmax == 16) return launch_beams_m<double, 16, SG_LANES_16>(a, direct, st);
-    return launch_beams_m<double, SG_LCAP, SG_LANES_63>(a, direct, st);
+    return sg_by_dtype_tier<true>(dtype, lmax, [&](auto t, auto tier) {
+        using T = decltype(t);
+        constexpr int LMAX = decltype(tier)::LMAX, BLOCK = decltype(tier)::BLOCK;
+        if (!direct) return launch_beams_t<T, LMAX, BLOCK, true, 0>(a, st);
+        if (a->exact_math) return launch_beams_t<T, LMAX, BLOCK, false, 2>(a, st);   // (registers to spare for tangent, root and quotient in its loop)
+        return launch_beams_t<T, LMAX, BLOCK, false, 1>(a, st);
+    });
 }
 
 // the received-power kernel for the queue a direct-mode pass of capacity lmax filled
 // plan_only = 1: k_power_plan alone (work items of k_power / k_power_few, places of the tier lists' slices); 0: k_power_few and k_power
 extern "C" int sg_launch_power(const SgBeamArgs *a, int dtype, int lmax, void *stream, int plan_only, void *ev_few, int which)
 {
-    hipStream_t st = (hipStream_t)stream;
-    const bool po = plan_only != 0;
-    hipEvent_t ef = (hipEvent_t)ev_few;
-    if (dtype == 0) {
-        if (lmax == 4) return launch_power_t<float, 4, 256, false>(a, st, po, ef, which);
-        if (lmax == 8) return launch_power_t<float, 8, SG_LANES_8, false>(a, st, po, ef, which);
-        if (lmax == 16) return launch_power_t<float, 16, SG_LANES_16, false>(a, st, po, ef, which);
-        return launch_power_t<float, SG_LCAP, SG_LANES_63, false>(a, st, po, ef, which);
-    }
-    if (lmax == 4) return launch_power_t<double, 4, 256, false>(a, st, po, ef, which);
-    if (lmax == 8) return launch_power_t<double, 8, SG_LANES_8, false>(a, st, po, ef, which);
-    if (lmax == 16) return launch_power_t<double, 16, SG_LANES_16, false>(a, st, po, ef, which);
-    return launch_power_t<double, SG_LCAP, SG_LANES_63, false>(a, st, po, ef, which);
+    return sg_by_dtype_tier<true>(dtype, lmax, [&](auto t, auto tier) {
+        return launch_power_t<decltype(t), decltype(tier)::LMAX, decltype(tier)::BLOCK, false>(a, (hipStream_t)stream, plan_only != 0, (hipEvent_t)ev_few, which);
+    });
 }
 
 extern "C" int sg_launch_tier_gather(const SgBeamArgs *a, void *stream)
@@ -1953,121 +1151,18 @@ extern "C" int sg_launch_tier_gather(const SgBeamArgs *a, void *stream)
 // ... and for the hand-over buffer of a list-mode pass
 extern "C" int sg_launch_power_list(const SgBeamArgs *a, int dtype, int lmax, void *stream)
 {
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == 0) {
-        if (lmax == 8) return launch_power_t<float, 8, SG_LANES_8, true>(a, st);
-        if (lmax == 16) return launch_power_t<float, 16, SG_LANES_16, true>(a, st);
-        return launch_power_t<float, SG_LCAP, SG_LANES_63, true>(a, st);
-    }
-    if (lmax == 8) return launch_power_t<double, 8, SG_LANES_8, true>(a, st);
-    if (lmax == 16) return launch_power_t<double, 16, SG_LANES_16, true>(a, st);
-    return launch_power_t<double, SG_LCAP, SG_LANES_63, true>(a, st);
+    return sg_by_dtype_tier<false>(dtype, lmax, [&](auto t, auto tier) {
+        return launch_power_t<decltype(t), decltype(tier)::LMAX, decltype(tier)::BLOCK, true>(a, (hipStream_t)stream);
+    });
 }
 
 extern "C" int sg_launch_huge(const SgBeamArgs *a, int dtype, void *stream)
 {
-    hipStream_t st = (hipStream_t)stream;
     const unsigned blocks = (unsigned)(a->h_lanes / 64);
     if (blocks == 0) return 0;
-    if (dtype == 0) hipLaunchKernelGGL(k_beams_huge<float>, dim3(blocks), dim3(64), 0, st, *a);
-    else hipLaunchKernelGGL(k_beams_huge<double>, dim3(blocks), dim3(64), 0, st, *a);
-    SG_CHECK_LAUNCH();
-    return 0;
-}
-
-// the same for a small batch (see k_seg_small); returns -1 if the batch is not small (nothing launched)
-extern "C" int sg_launch_segments_small(const int64_t *frame_off, int n_frames, const int32_t *tile_base, int64_t max_tiles, const int32_t *table_ids,
-                                        int n_las, int n_tables, int block, int32_t *seg_blk, int64_t *seg_start, int32_t *seg_cnt, int32_t *seg_frame,
-                                        int32_t *seg_n, int32_t *seg_of_blk, int32_t *chunk_blk, const SgTable *tables, SgTable *resolved,
-                                        unsigned long long *zero, int64_t n_zero, void *stream)
-{
-    if (n_frames * 256 > 1024 || n_tables + 1 > SG_SEG_SMALL_TABLES || n_zero > (1 << 16)) return -1;
-    hipLaunchKernelGGL(k_seg_small, dim3(1), dim3(1024), 0, (hipStream_t)stream, frame_off, n_frames, tile_base, max_tiles, table_ids, n_las, n_tables, block,
-                       seg_start, seg_cnt, seg_frame, seg_blk, seg_of_blk, seg_n, chunk_blk, tables, resolved, zero, n_zero);
-    SG_CHECK_LAUNCH();
-    return 0;
-}
-
-extern "C" int sg_launch_segments(const int64_t *frame_off, int n_frames, const int32_t *tile_base, int64_t max_tiles, const int32_t *table_ids,
-                                  int n_las, int n_tables, int block, unsigned long long *tbl_cnt, unsigned long long *tbl_base, int32_t *seg_blk,
-                                  int64_t *seg_start, int32_t *seg_cnt, int32_t *seg_frame, int32_t *seg_n, int32_t *seg_of_blk,
-                                  int32_t *chunk_blk, const SgTable *tables, SgTable *resolved, void *stream)
-{
-    hipStream_t st = (hipStream_t)stream;
-    const unsigned grid = (unsigned)n_frames;         // 256 pairs per frame, one thread each
-    if (hipMemsetAsync(tbl_cnt, 0, sizeof(unsigned long long) * ((size_t)n_tables + 1) * SG_TBL_STRIDE, st) != hipSuccess) return (int)hipGetLastError();
-    hipLaunchKernelGGL(k_seg_count, dim3(grid), dim3(256), 0, st, frame_off, n_frames, tile_base, max_tiles, table_ids, n_las, n_tables, block, tbl_cnt,
-                       tables, resolved);
-    SG_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_seg_scan, dim3(1), dim3(1024), 0, st, tbl_cnt, tbl_base, n_tables + 1, seg_n, chunk_blk);
-    SG_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_seg_place, dim3(grid), dim3(256), 0, st, frame_off, n_frames, tile_base, max_tiles, table_ids, n_las, n_tables, block,
-                       tbl_base, tbl_cnt, seg_start, seg_cnt, seg_frame, seg_blk, seg_of_blk);
-    SG_CHECK_LAUNCH();
-    return 0;
-}
-
-extern "C" int sg_launch_compact(const void *rows, const void *srows, const int32_t *frame_unsorted, int dtype, const uint32_t *rec, const uint32_t *rec_q, const void *rng, const double *thr_poly, uint8_t *keep, const int32_t *perm,
-                                 const int64_t *frame_off, int n_frames, int64_t n_total, int32_t *tile_cnt,
-                                 int32_t *tile_base, void *out_rows, int32_t *out_src, int64_t *out_counts,
-                                 int64_t *out_stats, const unsigned long long *diff2, const SgFov *fov, int64_t max_tiles, const SgPackOut *pack,
-                                 unsigned long long *tiles_done /* n_frames words, zero */, void *stream)
-{
-    (void)n_total;
-    hipStream_t st = (hipStream_t)stream;
-    dim3 grid((unsigned)max_tiles, (unsigned)n_frames);
-    SgFov fv{};
-    if (fov) fv = *fov;
-    int32_t *tile_mv = pack ? pack->tile_mv : nullptr;
-    int32_t *tmb = pack ? pack->tile_mv_base : nullptr;
-    int64_t *mvc = pack ? pack->mv_counts : nullptr;
-    if (dtype == 0) hipLaunchKernelGGL(k_compact_count<float>, grid, dim3(SG_BLOCK), 0, st, (const float *)rows, (const float *)srows, frame_unsorted, rec, rec_q, (const float *)rng, thr_poly, keep, frame_off, tile_cnt, max_tiles, fv, tile_mv,
-                                       tiles_done, tile_base, out_counts, out_stats, diff2, tmb, mvc);
-    else hipLaunchKernelGGL(k_compact_count<double>, grid, dim3(SG_BLOCK), 0, st, (const double *)rows, (const double *)srows, frame_unsorted, rec, rec_q, (const double *)rng, thr_poly, keep, frame_off, tile_cnt, max_tiles, fv, tile_mv,
-                            tiles_done, tile_base, out_counts, out_stats, diff2, tmb, mvc);
-    SG_CHECK_LAUNCH();
-    if (!tiles_done) {
-        hipLaunchKernelGGL(k_compact_scan, dim3(n_frames), dim3(64), 0, st, frame_off, tile_cnt, tile_base, out_counts, out_stats, diff2, max_tiles,
-                           (const int32_t *)tile_mv, tmb, mvc);
+    return sg_by_dtype(dtype, [&](auto t) {
+        hipLaunchKernelGGL(k_beams_huge<decltype(t)>, dim3(blocks), dim3(64), 0, (hipStream_t)stream, *a);
         SG_CHECK_LAUNCH();
-    }
-    SgPack pk{};
-    if (pack) { pk.meta = pack->meta; pk.inten = pack->inten; pk.mv = pack->mv; pk.tile_mv_base = pack->tile_mv_base; pk.mv_counts = pack->mv_counts; }
-    if (dtype == 0) {
-        if (pack) hipLaunchKernelGGL((k_compact_scatter<float, true>), grid, dim3(SG_BLOCK), 0, st, (const float *)rows, (const float *)srows, frame_unsorted, rec, rec_q, keep, perm, frame_off, tile_base, (float *)out_rows, out_src, out_stats, max_tiles, pk);
-        else hipLaunchKernelGGL((k_compact_scatter<float, false>), grid, dim3(SG_BLOCK), 0, st, (const float *)rows, (const float *)srows, frame_unsorted, rec, rec_q, keep, perm, frame_off, tile_base, (float *)out_rows, out_src, out_stats, max_tiles, pk);
-    } else {
-        if (pack) hipLaunchKernelGGL((k_compact_scatter<double, true>), grid, dim3(SG_BLOCK), 0, st, (const double *)rows, (const double *)srows, frame_unsorted, rec, rec_q, keep, perm, frame_off, tile_base, (double *)out_rows, out_src, out_stats, max_tiles, pk);
-        else hipLaunchKernelGGL((k_compact_scatter<double, false>), grid, dim3(SG_BLOCK), 0, st, (const double *)rows, (const double *)srows, frame_unsorted, rec, rec_q, keep, perm, frame_off, tile_base, (double *)out_rows, out_src, out_stats, max_tiles, pk);
-    }
-    SG_CHECK_LAUNCH();
-    return 0;
-}
-
-// pre-augment crop, stage 1: flags + per-frame counts (out_counts[f] = rows of frame f inside the camera's view)
-extern "C" int sg_launch_crop_count(const void *rows, int dtype, const int64_t *frame_off, int n_frames, uint8_t *keep, int32_t *tile_cnt,
-                                    int32_t *tile_base, int64_t *out_counts, int64_t *stats_scratch, const SgFov *fov, int64_t max_tiles,
-                                    void *stream)
-{
-    hipStream_t st = (hipStream_t)stream;
-    dim3 grid((unsigned)max_tiles, (unsigned)n_frames);
-    if (dtype == 0) hipLaunchKernelGGL(k_crop_flag<float>, grid, dim3(SG_BLOCK), 0, st, (const float *)rows, frame_off, keep, tile_cnt, max_tiles, *fov);
-    else hipLaunchKernelGGL(k_crop_flag<double>, grid, dim3(SG_BLOCK), 0, st, (const double *)rows, frame_off, keep, tile_cnt, max_tiles, *fov);
-    SG_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_compact_scan, dim3(n_frames), dim3(64), 0, st, frame_off, tile_cnt, tile_base, out_counts, stats_scratch, (const unsigned long long *)nullptr, max_tiles,
-                       (const int32_t *)nullptr, (int32_t *)nullptr, (int64_t *)nullptr);
-    SG_CHECK_LAUNCH();
-    return 0;
-}
-
-// stage 2: rows of frame f to new_off[f] .. (stable), crop_src = their rows in the original frame
-extern "C" int sg_launch_crop_scatter(const void *rows, int dtype, const uint8_t *keep, const int64_t *frame_off, const int64_t *new_off,
-                                      int n_frames, const int32_t *tile_base, void *out_rows, int32_t *crop_src, int64_t max_tiles, void *stream)
-{
-    hipStream_t st = (hipStream_t)stream;
-    dim3 grid((unsigned)max_tiles, (unsigned)n_frames);
-    if (dtype == 0) hipLaunchKernelGGL(k_crop_scatter<float>, grid, dim3(SG_BLOCK), 0, st, (const float *)rows, keep, frame_off, new_off, tile_base, (float *)out_rows, crop_src, max_tiles);
-    else hipLaunchKernelGGL(k_crop_scatter<double>, grid, dim3(SG_BLOCK), 0, st, (const double *)rows, keep, frame_off, new_off, tile_base, (double *)out_rows, crop_src, max_tiles);
-    SG_CHECK_LAUNCH();
-    return 0;
+        return 0;
+    });
 }

@@ -27,6 +27,7 @@
 #include "sg_common.h"
 #include "sg_philox.h"
 #include "sg_plane.h"
+#include "sg_launch.h"
 
 #define PLB 256
 #define PL_CHUNK 1536          /* points staged in LDS at a time by the RANSAC consensus loop (36 KB) */
@@ -398,8 +399,6 @@ extern "C" void sg_plane_release(SgPlaneScratch *s)
     for (int i = 0; i < 4; ++i) { if (s->buf[i]) (void)hipFree(s->buf[i]); s->buf[i] = nullptr; s->cap[i] = 0; }
 }
 
-#define PL_LCHK() do { hipError_t e__ = hipGetLastError(); if (e__ != hipSuccess) return (int)e__; } while (0)
-
 extern "C" int sg_plane_run(SgPlaneScratch *s, const SgPlaneParams *p, const void *rows, int dtype, const int64_t *frame_off,
                             const int64_t *frame_cnt, int n_frames, int64_t n_total, int64_t max_frame, double *plane, int32_t *info,
                             void *stream)
@@ -409,10 +408,10 @@ extern "C" int sg_plane_run(SgPlaneScratch *s, const SgPlaneParams *p, const voi
     const double std_height = p->std_height;
     if (p->method == SG_PLANE_REFERENCE || n_total <= 0) {
         hipLaunchKernelGGL(k_plane_const, dim3((unsigned)((n_frames + 63) / 64)), dim3(64), 0, st, plane, info, n_frames, std_height);
-        PL_LCHK();
+        SG_CHECK_LAUNCH();
         return 0;
     }
-    const int64_t max_tiles = (max_frame + SG_TILE - 1) / SG_TILE > 0 ? (max_frame + SG_TILE - 1) / SG_TILE : 1;
+    const int64_t max_tiles = sg_tiles(max_frame);
     const size_t n = (size_t)n_total, nf = (size_t)n_frames;
     if (pl_ensure(s, PB_TCNT, nf * (size_t)max_tiles * 4) || pl_ensure(s, PB_TIDX, (n + SG_TILE) * 4) || pl_ensure(s, PB_PTS, n * 3 * 8)) return -1;
     PlaneArgs a{};
@@ -423,11 +422,12 @@ extern "C" int sg_plane_run(SgPlaneScratch *s, const SgPlaneParams *p, const voi
     // tiles past the end of a short frame are never written by k_plane_crop: their counts must read 0
     if (hipMemsetAsync(a.tile_cnt, 0, nf * (size_t)max_tiles * 4, st) != hipSuccess) return (int)hipGetLastError();
     dim3 grid((unsigned)max_tiles, (unsigned)n_frames);
-    if (dtype == 0) hipLaunchKernelGGL(k_plane_crop<float>, grid, dim3(PLB), 0, st, a);
-    else hipLaunchKernelGGL(k_plane_crop<double>, grid, dim3(PLB), 0, st, a);
-    PL_LCHK();
-    if (dtype == 0) hipLaunchKernelGGL(k_plane_fit<float>, dim3((unsigned)n_frames), dim3(PLB), 0, st, a);
-    else hipLaunchKernelGGL(k_plane_fit<double>, dim3((unsigned)n_frames), dim3(PLB), 0, st, a);
-    PL_LCHK();
-    return 0;
+    return sg_by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(k_plane_crop<T>, grid, dim3(PLB), 0, st, a);
+        SG_CHECK_LAUNCH();
+        hipLaunchKernelGGL(k_plane_fit<T>, dim3((unsigned)n_frames), dim3(PLB), 0, st, a);
+        SG_CHECK_LAUNCH();
+        return 0;
+    });
 }

@@ -24,6 +24,7 @@
 #include <algorithm>
 #include "sg_beam.h"
 #include "sg_kutil.h"
+#include "sg_launch.h"
 
 #define RW_BLOCK 256
 #ifndef RW_WAVES
@@ -475,29 +476,23 @@ __global__ __launch_bounds__(RW_BLOCK, PAIRWISE ? 2 : RW_WAVES) void k_rows(SgBe
 
 
 // ------------------------------------------------------------------------------------------------
-#define RW_CHECK_LAUNCH() do { hipError_t e__ = hipGetLastError(); if (e__ != hipSuccess) return (int)e__; } while (0)
-
 template <typename T, int G>
 static int launch_rows_t(const SgBeamArgs *a, hipStream_t st)
 {
     const int64_t n = (int64_t)a->work_hi - a->work_lo;
     if (n <= 0) return 0;
-    int dev_id = 0, cus = 256;
-    (void)hipGetDevice(&dev_id);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev_id);
-    if (cus <= 0) cus = 256;
     constexpr int RPW = 64 / G, WPB = RW_BLOCK / 64;
     // persistent waves: what the chip holds (8 blocks of 256 per CU at most), fewer when the class cannot be longer
     const int64_t want = (n + (int64_t)RPW * WPB - 1) / ((int64_t)RPW * WPB);
-    const unsigned blocks = (unsigned)std::min<int64_t>(want, (int64_t)cus * 8);
+    const unsigned blocks = (unsigned)std::min<int64_t>(want, (int64_t)sg_cu_count() * 8);
     if (a->exact_math) hipLaunchKernelGGL((k_rows<T, G, true, false>), dim3(blocks), dim3(RW_BLOCK), 0, st, *a);
     else hipLaunchKernelGGL((k_rows<T, G, false, false>), dim3(blocks), dim3(RW_BLOCK), 0, st, *a);
-    RW_CHECK_LAUNCH();
+    SG_CHECK_LAUNCH();
     // the beams it deferred (an owner with 8 or more elementary slots): nearly always none -- a small grid that leaves at once
     const unsigned redo_blocks = std::min(blocks, 64u);
     if (a->exact_math) hipLaunchKernelGGL((k_rows<T, G, true, true>), dim3(redo_blocks), dim3(RW_BLOCK), 0, st, *a);
     else hipLaunchKernelGGL((k_rows<T, G, false, true>), dim3(redo_blocks), dim3(RW_BLOCK), 0, st, *a);
-    RW_CHECK_LAUNCH();
+    SG_CHECK_LAUNCH();
     return 0;
 }
 
@@ -505,12 +500,10 @@ static int launch_rows_t(const SgBeamArgs *a, hipStream_t st)
 extern "C" int sg_launch_rows(const SgBeamArgs *a, int dtype, int lmax, void *stream)
 {
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == 0) {
-        if (lmax <= 8) return launch_rows_t<float, 8>(a, st);
-        if (lmax <= 16) return launch_rows_t<float, 16>(a, st);
-        return launch_rows_t<float, 64>(a, st);
-    }
-    if (lmax <= 8) return launch_rows_t<double, 8>(a, st);
-    if (lmax <= 16) return launch_rows_t<double, 16>(a, st);
-    return launch_rows_t<double, 64>(a, st);
+    return sg_by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        if (lmax <= 8) return launch_rows_t<T, 8>(a, st);
+        if (lmax <= 16) return launch_rows_t<T, 16>(a, st);
+        return launch_rows_t<T, 64>(a, st);
+    });
 }

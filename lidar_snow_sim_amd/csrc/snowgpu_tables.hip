@@ -16,6 +16,7 @@
 #include <stdint.h>
 #include "sg_common.h"
 #include "sg_atan_cr.h"
+#include "sg_launch.h"
 
 #define TB 256
 
@@ -187,7 +188,6 @@ __global__ __launch_bounds__(TB) void k_table_dump(const SgEntry *__restrict__ e
     o[0] = e.rho; o[1] = e.phi; o[2] = e.t0; o[3] = e.t1;
 }
 
-#define TCHK() do { hipError_t e__ = hipGetLastError(); if (e__ != hipSuccess) return (int)e__; } while (0)
 
 // Stage A (derive + histogram + scan).  scratch: fl K records, b0 / span K ints, count / start / fill nb + 1 each,
 // misc[0] = bad-row marker, misc[1] = longest bin.  The caller then reads start[nb] (and misc) and allocates the bins.
@@ -199,10 +199,10 @@ extern "C" int sg_file_table_stage_a(const double *d_xyr, int64_t k, SgEntry *fl
     if (hipMemsetAsync(misc, 0, sizeof(int32_t) * 2, st) != hipSuccess) return (int)hipGetLastError();
     if (k > 0) {
         hipLaunchKernelGGL(k_file_derive, dim3((unsigned)((k + TB - 1) / TB)), dim3(TB), 0, st, d_xyr, k, fl, b0, span, count, misc);
-        TCHK();
+        SG_CHECK_LAUNCH();
     }
     hipLaunchKernelGGL(k_file_scan, dim3(1), dim3(1024), 0, st, count, start, fill, (uint32_t *)(misc + 1));
-    TCHK();
+    SG_CHECK_LAUNCH();
     return 0;
 }
 
@@ -213,17 +213,17 @@ extern "C" int sg_file_table_stage_b(int64_t k, const SgEntry *fl, const int32_t
     hipStream_t st = (hipStream_t)stream;
     if (k > 0) {
         hipLaunchKernelGGL(k_file_scatter, dim3((unsigned)((k + TB - 1) / TB)), dim3(TB), 0, st, k, fl, b0, span, start, fill, tmp);
-        TCHK();
+        SG_CHECK_LAUNCH();
     }
     hipLaunchKernelGGL(k_file_sort, dim3(SG_NBINS), dim3(64), 0, st, start, tmp, entries);
-    TCHK();
+    SG_CHECK_LAUNCH();
     return 0;
 }
 
 extern "C" int sg_table_index(const SgEntry *entries, const uint32_t *start, uint32_t *q, void *stream)
 {
     hipLaunchKernelGGL(k_table_index, dim3(SG_NBINS), dim3(64), 0, (hipStream_t)stream, entries, start, q);
-    TCHK();
+    SG_CHECK_LAUNCH();
     return 0;
 }
 
@@ -231,6 +231,6 @@ extern "C" int sg_table_dump(const SgEntry *entries, uint32_t n_entries, double 
 {
     if (n_entries == 0) return 0;
     hipLaunchKernelGGL(k_table_dump, dim3((n_entries + TB - 1) / TB), dim3(TB), 0, (hipStream_t)stream, entries, n_entries, d_out);
-    TCHK();
+    SG_CHECK_LAUNCH();
     return 0;
 }
