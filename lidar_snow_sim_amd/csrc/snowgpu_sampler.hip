@@ -24,6 +24,7 @@
 #define SB 256
 #define SG_SAMP_CELL 0.5
 #define SG_SAMP_MAXCONF 4
+#define SG_SAMP_NO_OVERFLOW 0x7f7f7f7f        /* flags[0] as hipMemset(0x7f) leaves it: above any candidate index (n <= 2^27) */
 
 struct SgCand { double x, y, r; int32_t valid; int32_t state; };   // state: 0 undecided, 1 accepted, 2 rejected
 
@@ -38,7 +39,7 @@ struct SampArgs {
     int32_t *cell_items;      // candidates grouped by cell
     int32_t *conf;            // per candidate: up to SG_SAMP_MAXCONF lower-index overlapping candidates (-1 = none)
     int32_t grid;             // cells per side
-    int32_t *flags;           // [0] conflict-list overflow, [1] undecided left, [2] changed in this sweep
+    int32_t *flags;           // [0] smallest candidate whose conflict list overflowed, [1] undecided left, [2] changed in this sweep
     double *area_scan;        // inclusive scan of accepted areas
     double target_area;
     int64_t *out_n;           // [0] rows produced, [1] cut index (-1: target not reached)
@@ -109,7 +110,10 @@ __global__ __launch_bounds__(SB) void k_samp_fill(SampArgs a)
     a.cell_items[a.cell_start[cell] + slot] = (int32_t)i;
 }
 
-// lower-index candidates whose disk overlaps candidate i (sampling.py:170)
+// lower-index candidates whose disk overlaps candidate i (sampling.py:170).  A candidate with more than SG_SAMP_MAXCONF of
+// them cannot be decided: it is marked rejected and the smallest such index is kept in flags[0].  Every decision for an
+// index below that one depends on earlier indices only, so it stays exact; the host refuses the table only if the stop
+// rule did not cut before it (most overflows are spare candidates far beyond the cut, where the disc is already full).
 __global__ __launch_bounds__(SB) void k_samp_overlap(SampArgs a)
 {
     const int64_t i = (int64_t)blockIdx.x * SB + threadIdx.x;
@@ -132,12 +136,13 @@ __global__ __launch_bounds__(SB) void k_samp_overlap(SampArgs a)
                 if (!o.valid) continue;
                 const double ddx = o.x - me.x, ddy = o.y - me.y, rr = o.r + me.r;
                 if (ddx * ddx + ddy * ddy <= rr * rr) {
-                    if (n < SG_SAMP_MAXCONF) cf[n] = j; else atomicExch(&a.flags[0], 1);
+                    if (n < SG_SAMP_MAXCONF) cf[n] = j;
                     ++n;
                 }
             }
         }
     if (n == 0) a.cand[i].state = 1;             // nothing earlier in the way: accepted whatever happens elsewhere
+    else if (n > SG_SAMP_MAXCONF) { a.cand[i].state = 2; atomicMin(&a.flags[0], (int32_t)i); }
 }
 
 // acc[i] = valid_i and no ACCEPTED earlier dart overlaps it; swept until nothing is undecided
@@ -228,7 +233,8 @@ __global__ __launch_bounds__(1024) void k_samp_emit(SampArgs a)
 #define SCHK(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { rc = (int)e__; goto done; } } while (0)
 
 // Returns 0 and *n_rows (rows written to d_xyr, capacity cap) ; -2: target area not reached with n_cand candidates;
-// -3: a candidate overlapped more than SG_SAMP_MAXCONF earlier ones; -4: acceptance did not settle; >0: hipError_t.
+// -3: a candidate at or before the cut overlapped more than SG_SAMP_MAXCONF earlier ones (more candidates cannot cure that:
+// it outranks -2); -4: acceptance did not settle; >0: hipError_t.
 extern "C" int sg_sample_table(double occupancy, double scale_mm, double R0, uint64_t seed, int64_t n_cand, double *d_xyr,
                                int64_t cap, int64_t *n_rows, void *stream)
 {
@@ -257,7 +263,7 @@ extern "C" int sg_sample_table(double occupancy, double scale_mm, double R0, uin
     a.cell_start = (int32_t *)bufs[3]; a.cell_items = (int32_t *)bufs[4]; a.conf = (int32_t *)bufs[5];
     a.flags = (int32_t *)bufs[6]; a.area_scan = (double *)bufs[7]; a.out_n = (int64_t *)bufs[8];
     SCHK(hipMemsetAsync(a.cell_count, 0, sizeof(int32_t) * (n_cells + 1), st));
-    SCHK(hipMemsetAsync(a.flags, 0, sizeof(int32_t) * 4, st));
+    SCHK(hipMemsetAsync(a.flags, 0x7f, sizeof(int32_t) * 4, st));      // [0] = SG_SAMP_NO_OVERFLOW; [1], [2] are cleared per sweep
     hipLaunchKernelGGL(k_samp_gen, dim3(blocks), dim3(SB), 0, st, a);
     hipLaunchKernelGGL(k_samp_scan_cells, dim3(1), dim3(1024), 0, st, a);
     hipLaunchKernelGGL(k_samp_fill, dim3(blocks), dim3(SB), 0, st, a);
@@ -268,7 +274,6 @@ extern "C" int sg_sample_table(double occupancy, double scale_mm, double R0, uin
         hipLaunchKernelGGL(k_samp_resolve, dim3(blocks), dim3(SB), 0, st, a);
         SCHK(hipMemcpyAsync(h_flags, a.flags, sizeof(h_flags), hipMemcpyDeviceToHost, st));
         SCHK(hipStreamSynchronize(st));
-        if (h_flags[0]) { rc = -3; goto done; }
         if (!h_flags[1]) break;                              // nothing undecided any more
         if (!h_flags[2] && sweep > 0) { rc = -4; goto done; }
     }
@@ -278,6 +283,7 @@ extern "C" int sg_sample_table(double occupancy, double scale_mm, double R0, uin
     SCHK(hipGetLastError());
     SCHK(hipMemcpyAsync(h_out, a.out_n, sizeof(h_out), hipMemcpyDeviceToHost, st));
     SCHK(hipStreamSynchronize(st));
+    if (h_flags[0] != SG_SAMP_NO_OVERFLOW && (h_out[1] < 0 || h_out[1] >= h_flags[0])) { rc = -3; goto done; }
     if (h_out[1] < 0) { rc = -2; goto done; }
     *n_rows = h_out[0];
 done:

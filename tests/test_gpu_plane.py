@@ -2,11 +2,14 @@
 
 The reference's own estimator is unpinned (unseeded RANSAC that raises with scikit-learn >= 1.2: SURVEY 8 c), so these tests
 hold the engine's estimators to what they claim: 'reference' = the plane the reference returns today, 'lsq' = NumPy's lstsq on
-the rows of the reference's crop, 'ransac' = deterministic per seed, robust to outliers, equal to 'lsq' on its consensus set.
+the rows of the reference's crop, 'ransac' = deterministic per seed, robust to outliers, equal to 'lsq' on its consensus set -- and,
+trial for trial, the plane of a NumPy restatement fed with the same Philox draws (tests/seeded_reference.py).
 """
 import numpy as np
 import pytest
 import torch  # noqa: F401  -- before libsnowgpu.so is loaded (see test_gpu_parity.py)
+
+import seeded_reference as sr
 
 pytestmark = pytest.mark.gpu
 
@@ -164,3 +167,37 @@ def test_fewer_than_three_strip_rows_give_the_flat_earth_plane_whatever_min_rows
         for k in (0, 1, 2):
             assert tuple(planes[k]) == (0.0, 0.0, 1.0, -1.55), (method, min_rows, k, planes[k])
         assert np.isfinite(planes[3]).all()
+
+
+@pytest.mark.parametrize("name", sr.PLANE_CASE_NAMES)
+def test_ransac_plane_equals_the_restatement_with_the_same_draws(eng, name):
+    """k_plane_fit's RANSAC against plane_ransac_restated: crop size, model, consensus size, valid trials and the plane.  In the
+    scenes the inlier count (in the tie cases the mean squared residual) separates the winner from the runner-up and the two refit
+    to planes further apart than the tolerance (tests/test_seeded_reference.py checks that without a GPU), so a wrong draw mapping,
+    collinearity test, tie order, arg-best reduction, PL_CHUNK staging or frame key picks another trial and fails here.  Cases:
+    both dtypes; trials below, at and above one block of 256 and no multiples of it; crops of 3, 4 and 10 rows and around and
+    above PL_CHUNK; a seed above 2^32; a cloud whose collinear samples leave valid_trials < trials; ragged batches of five frames
+    in one call, where frame f must equal the restatement keyed by f.
+
+    Observed on an MI355X over the 27 frames of these cases: info equal everywhere, the normal within 3.5e-15, h within 0.11 % of
+    its tolerance.  With the `if (i2 >= hi) ++i2;` shift of the draws removed from k_plane_fit (a variant built apart from the
+    tree), 12 of the 19 cases fail: another consensus size where the winner's sample changes (scene5000 t64: used 3456 for 3457),
+    fewer valid trials where the third row repeats the second (crop3: 71 of 100), more in collinear_f32 (911 for 899)."""
+    c = sr.plane_case(name)
+    frames = c["frames"]
+    off = np.concatenate(([0], np.cumsum([len(f) for f in frames])))
+    eng.ctx.set_plane_method("ransac", seed=c["seed"], trials=c["trials"], min_rows=c["min_rows"])
+    try:
+        planes, info = eng.ctx.estimate_planes(np.concatenate(frames), off)
+    finally:
+        eng.ctx.set_plane_method("reference")
+    for f, pc in enumerate(frames):
+        r = sr.plane_ransac_restated(pc, c["seed"], f, c["trials"], c["min_rows"])
+        print(f"\n[plane-exact] {name}[{f}]: device info {info[f].tolist()} plane {planes[f].tolist()}; restated crop {r.crop} used {r.used} "
+              f"valid {r.valid_trials} winner {r.winner} plane {r.plane.tolist()}")
+        assert info[f].tolist() == [r.crop, 2, r.used, r.valid_trials], (name, f, info[f], r.winner)
+        np.testing.assert_allclose(planes[f, :3], r.plane[:3], rtol=0, atol=1e-12)
+        np.testing.assert_allclose(planes[f, 3], r.plane[3], rtol=1e-12, atol=1e-12)
+    if c["kind"] == "batch":                               # the draws are keyed by the frame index: frame 2 is not frame 0's trial
+        r0 = sr.plane_ransac_restated(frames[2], c["seed"], 0, c["trials"], c["min_rows"])
+        assert not np.allclose(planes[2], r0.plane, rtol=1e-9, atol=1e-9)

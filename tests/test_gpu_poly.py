@@ -15,21 +15,11 @@ import numpy as np
 import pytest
 import torch  # noqa: F401  -- before libsnowgpu.so is loaded (one HIP runtime per process)
 
+from seeded_reference import philox4x32_10
+
 pytestmark = pytest.mark.gpu
 
 PLANE = (np.array([0.0, 0.0, -1.0]), -1.7)
-M32 = 0xFFFFFFFF
-
-
-def philox4x32_10(seed, idx, group, tag):
-    """Philox4x32-10 block (idx, group, tag) under key `seed` -- csrc/sg_philox.h::philox_u32x4 in Python integers."""
-    c = [idx & M32, (idx >> 32) & M32, group & M32, tag & M32]
-    k = [seed & M32, (seed >> 32) & M32]
-    for _ in range(10):
-        p0, p1 = 0xD2511F53 * c[0], 0xCD9E8D57 * c[2]
-        c = [(p1 >> 32) ^ c[1] ^ k[0], p1 & M32, (p0 >> 32) ^ c[3] ^ k[1], p0 & M32]
-        k = [(k[0] + 0x9E3779B9) & M32, (k[1] + 0xBB67AE85) & M32]
-    return c
 
 
 def ransac_polyfit_with_device_draws(x, y, seed, frame, n=15, k=100, t=0.1, d=15, f=0.8):
