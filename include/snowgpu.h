@@ -31,6 +31,9 @@
  *               (simulation.py:447), STABLY here (the reference's argsort is unstable, so its
  *               within-channel order is implementation-defined); out_src returns, per output
  *               row, the index of the input row it came from (frame-local)
+ *   aligned   : snowgpu_augment_batch_device_aligned returns the same rows in the INPUT's order instead -- every input row
+ *               at its own index, one keep flag per row (1: the reference returns the row) --, a result whose shape does not
+ *               depend on the data and which a consumer on the same stream (or in the same HIP graph) reads without the host
  */
 #ifndef SNOWGPU_H
 #define SNOWGPU_H
@@ -253,6 +256,30 @@ int snowgpu_augment_batch_device(snowgpu_ctx *ctx, int n_frames, int64_t n_total
                                  const int32_t *d_perm, void *d_out_rows, int32_t *d_out_src,
                                  int64_t *d_out_counts, int64_t *d_out_stats, double *d_out_thr_poly,
                                  int32_t *d_status, void *stream);
+
+/*
+ * snowgpu_augment_batch_device with the ALIGNED result layout.  The simulation never moves a point to another beam -- a beam is copied,
+ * attenuated, moved along its own ray or dropped (simulation.py:160-192, :516-523) -- so the result can keep the input's size and order:
+ *   d_out_rows  n_total x 5 rows (dtype of the input): row i of frame f (d_frame_offsets[f] + i) is the output row of INPUT row i.  EVERY
+ *               row is written, removed ones too: those hold what aug_pc held just before simulation.py:523 (the input's coordinates --
+ *               the moved ones for a scattered row only the camera crop removed --, np.round of the intensity for label 0, the
+ *               attenuated intensity for label 1, column 4 as in a kept row), so the bytes are deterministic.  May be d_rows ITSELF
+ *               (in place: the frames are overwritten by their augmented form); any other overlap with d_rows is SNOWGPU_E_INVALID.
+ *   d_out_keep  n_total bytes: 1 where the reference returns the row (noise-floor filter, camera crop if set), else 0.
+ *               d_out_rows[keep], taken in the order of snowgpu_augment_batch_device's d_out_src, are that entry's rows byte for byte.
+ *   d_out_counts, d_out_stats, d_out_thr_poly, d_status   as snowgpu_augment_batch_device (counts = flags set per frame).
+ * Same contract otherwise: asynchronous on `stream`, no allocation after the first call of a size, capturable into a HIP graph; on a
+ * non-zero status the rows are unspecified.  The last step is one kernel instead of the compaction's three.  A context with a threshold
+ * callback (snowgpu_set_threshold_callback) or the packed result transfer (snowgpu_set_result_transfer) set answers SNOWGPU_E_INVALID:
+ * both finish batches through the compaction.  The host-pointer entries and the fused wet-ground entry have no aligned form.
+ */
+int snowgpu_augment_batch_device_aligned(snowgpu_ctx *ctx, int n_frames, int64_t n_total,
+                                         int64_t max_frame_rows, const int64_t *d_frame_offsets, const void *d_rows, int dtype,
+                                         const int32_t *d_table_ids, double beam_divergence_deg,
+                                         const double *d_thr_poly, const double *d_plane, double noise_floor,
+                                         const int32_t *d_perm, void *d_out_rows /* n_total x 5, may be d_rows itself */,
+                                         uint8_t *d_out_keep /* n_total */, int64_t *d_out_counts, int64_t *d_out_stats,
+                                         double *d_out_thr_poly, int32_t *d_status, void *stream);
 
 /*
  * Debug/parity tap: the occlusion dicts of get_occlusions (simulation.py:298-424) for the rows of

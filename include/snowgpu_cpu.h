@@ -47,6 +47,20 @@ int snowgpu_cpu_augment_batch(int n_frames, const int64_t *frame_offsets, const 
                               const int32_t *max_intensity, double beam_divergence_deg, const double *thr_poly, double noise_floor,
                               int threads, void *out_rows, int32_t *out_src, int64_t *out_counts, int64_t *out_stats, int32_t *status);
 
+/*
+ * The same call with the ALIGNED result layout of snowgpu_augment_batch_device_aligned (include/snowgpu.h): out_rows (n_total x 5) holds the
+ * output row of EVERY input row at the input's own index -- removed rows too, as they stood just before simulation.py:523 --, out_keep
+ * (n_total bytes) is 1 where snowgpu_cpu_augment_batch returns the row.  The same finishing loop writing to perm[g] instead of the next
+ * free slot; everything else is shared.  out_rows must not be `rows` (the twin reads the input while it writes).  Bit for bit the rows
+ * and flags of the device entry, removed rows included (tests/test_aligned_twin.py, tests/test_gpu_aligned.py).
+ */
+typedef int snowcpu_aligned_fn(int n_frames, const int64_t *frame_offsets, const void *rows, int dtype, int n_tables,
+                               const double *const *tables_xyr, const int64_t *tables_k, const int32_t *table_ids, int n_lasers,
+                               const double *focal_slope, const double *focal_offset, const int32_t *min_intensity,
+                               const int32_t *max_intensity, double beam_divergence_deg, const double *thr_poly, double noise_floor,
+                               int threads, void *out_rows, uint8_t *out_keep, int64_t *out_counts, int64_t *out_stats, int32_t *status);
+snowcpu_aligned_fn snowgpu_cpu_augment_batch_aligned;     /* (the function itself, declared by its type: callers that dlopen the twin cast to it) */
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,14 +26,19 @@ def lib():
         L.snowgpu_cpu_version.restype = ctypes.c_char_p
         L.snowgpu_cpu_augment_batch.restype = ci
         L.snowgpu_cpu_augment_batch.argtypes = [ci, vp, vp, ci, ci, vp, vp, vp, ci, vp, vp, vp, vp, dbl, vp, dbl, ci, vp, vp, vp, vp, vp]
+        L.snowgpu_cpu_augment_batch_aligned.restype = ci
+        L.snowgpu_cpu_augment_batch_aligned.argtypes = L.snowgpu_cpu_augment_batch.argtypes      # (out_keep where out_src is)
         _lib = L
     return _lib
 
 
-def augment_batch(frames, tables, orders, beam_divergence, thr_polys, lasers=None, noise_floor=0.7, threads=0):
+def augment_batch(frames, tables, orders, beam_divergence, thr_polys, lasers=None, noise_floor=0.7, threads=0, layout='compact'):
     """frames: list of N_i x 5 float32 / float64 arrays; tables: sequence of K x 3 float64 tables (index = line - 1); orders: per frame the
     channel permutation (channel c reads tables[orders[f][c]], simulation.py:78); thr_polys: per frame (p0, p1, p2).
-    Returns [(stats, aug_pc, src)] like augment_batch(..., return_src=True) of the HIP path."""
+    Returns [(stats, aug_pc, src)] like augment_batch(..., return_src=True) of the HIP path -- or, with layout='aligned'
+    (snowgpu_cpu_augment_batch_aligned), [(stats, rows_f, keep_f)]: every input row's output row at its own index and a bool mask."""
+    if layout not in ('compact', 'aligned'):
+        raise ValueError("layout must be 'compact' or 'aligned'")
     from .engine import laser_constants, load_lasers
     L = lib()
     lasers = load_lasers() if lasers is None else lasers
@@ -67,7 +72,9 @@ def augment_batch(frames, tables, orders, beam_divergence, thr_polys, lasers=Non
     stats = np.zeros((nf, 3), np.int64)
     status = np.zeros(2, np.int32)
     p = lambda a: ctypes.c_void_p(a.ctypes.data)   # noqa: E731
-    rc = L.snowgpu_cpu_augment_batch(nf, p(off), p(rows), 0 if dt == np.float32 else 1, len(uniq), ctypes.cast(ptrs, ctypes.c_void_p), p(ks), p(ids), nl,
+    if layout == 'aligned':
+        src = np.empty(rows.shape[0], np.uint8)        # the keep flags take out_src's place
+    rc = (L.snowgpu_cpu_augment_batch_aligned if layout == 'aligned' else L.snowgpu_cpu_augment_batch)(nf, p(off), p(rows), 0 if dt == np.float32 else 1, len(uniq), ctypes.cast(ptrs, ctypes.c_void_p), p(ks), p(ids), nl,
                                      p(fs), p(fo), p(mi), p(ma), float(beam_divergence), p(thr), float(noise_floor), int(threads), p(out), p(src),
                                      p(counts), p(stats), p(status))
     if rc:
@@ -75,6 +82,10 @@ def augment_batch(frames, tables, orders, beam_divergence, thr_polys, lasers=Non
         raise kind(f"libsnowcpu status {rc} at {int(status[1])}")
     res = []
     for f in range(nf):
+        if layout == 'aligned':
+            a, b = int(off[f]), int(off[f + 1])
+            res.append(((np.int64(stats[f, 0]), np.int64(stats[f, 1]), int(stats[f, 2])), out[a:b], src[a:b].view(np.bool_)))
+            continue
         a, n = int(off[f]), int(counts[f])
         res.append(((np.int64(stats[f, 0]), np.int64(stats[f, 1]), int(stats[f, 2])), out[a:a + n], src[a:a + n]))
     return res

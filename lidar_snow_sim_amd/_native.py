@@ -27,6 +27,7 @@ EXPORTS = [
     "snowgpu_augment_wet_batch_device", "snowgpu_last_status", "snowgpu_free_table", "snowgpu_debug_table", "snowgpu_file_table_device", "snowgpu_set_fov_precrop",
     "snowgpu_set_pipeline", "snowgpu_set_wet_lines", "snowgpu_set_plane_method", "snowgpu_estimate_planes",
     "snowgpu_estimate_planes_device", "snowgpu_prepass_stats", "snowgpu_set_wet_estimation", "snowgpu_wet_last_fit", "snowgpu_debug_ransac_polyfit", "snowgpu_set_result_transfer", "snowgpu_debug_transfer_times", "snowgpu_status_error", "snowgpu_set_threshold_callback", "snowgpu_augment_batch_compact", "snowgpu_set_serial", "snowgpu_lane_stream", "snowgpu_device_numa_node",
+    "snowgpu_augment_batch_device_aligned",
 ]
 
 WET_ESTIMATION = {"linear": 0, "poly": 1}
@@ -81,6 +82,8 @@ def lib():
             L.snowgpu_augment_batch_device.restype = ctypes.c_int
             L.snowgpu_augment_batch_device.argtypes = [vp, ctypes.c_int, i64, i64, vp, vp, ctypes.c_int, vp, dbl, vp, vp,
                                                        dbl, vp, vp, vp, vp, vp, vp, vp, vp]
+            L.snowgpu_augment_batch_device_aligned.restype = ctypes.c_int
+            L.snowgpu_augment_batch_device_aligned.argtypes = L.snowgpu_augment_batch_device.argtypes      # (d_out_keep where d_out_src is)
             L.snowgpu_debug_occlusions.restype = ctypes.c_int
             L.snowgpu_debug_occlusions.argtypes = [vp, i64, vp, ctypes.c_int, vp, dbl, ctypes.c_int, vp, vp, vp, vp]
             L.snowgpu_wet_ground_batch.restype = ctypes.c_int
@@ -332,6 +335,19 @@ class Context:
                                                   vp(d_thr_poly or None), vp(d_plane or None), float(noise_floor),
                                                   vp(d_perm or None), vp(d_out_rows), vp(d_out_src), vp(d_out_counts),
                                                   vp(d_out_stats), vp(d_out_thr or None), vp(d_status), vp(stream or None))
+        self._check(rc)
+
+    def augment_batch_device_aligned(self, n_frames, n_total, max_frame_rows, d_frame_off, d_rows, dtype_code, d_table_ids, beam_divergence,
+                                     d_thr_poly, d_plane, noise_floor, d_perm, d_out_rows, d_out_keep, d_out_counts,
+                                     d_out_stats, d_out_thr, d_status, stream=0):
+        """Raw device-pointer entry with the aligned result layout (rows in input order + one keep byte per row; d_out_rows may be
+        d_rows); asynchronous on `stream`."""
+        vp = ctypes.c_void_p
+        rc = self._L.snowgpu_augment_batch_device_aligned(self._h, int(n_frames), int(n_total), int(max_frame_rows), vp(d_frame_off), vp(d_rows),
+                                                          int(dtype_code), vp(d_table_ids), float(beam_divergence),
+                                                          vp(d_thr_poly or None), vp(d_plane or None), float(noise_floor),
+                                                          vp(d_perm or None), vp(d_out_rows), vp(d_out_keep), vp(d_out_counts),
+                                                          vp(d_out_stats), vp(d_out_thr or None), vp(d_status), vp(stream or None))
         self._check(rc)
 
     def augment_wet_batch_device(self, n_frames, n_total, max_frame_rows, d_frame_off, d_rows, dtype_code, d_table_ids,

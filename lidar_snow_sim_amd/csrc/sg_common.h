@@ -239,6 +239,11 @@ int sg_launch_compact(const void *rows, const void *srows, const int32_t *frame_
                       int32_t *tile_base, void *out_rows, int32_t *out_src, int64_t *out_counts,
                       int64_t *out_stats, const unsigned long long *diff2, const SgFov *fov, int64_t max_tiles_per_frame,
                       const SgPackOut *pack /* or null: rows + out_src */, unsigned long long *tiles_done /* n_frames words, zero */, void *stream);
+// the aligned finish (k_finish_aligned): every row at its input index + a keep flag; out_rows may be `rows` itself
+int sg_launch_finish_aligned(const void *rows, const void *srows, const int32_t *frame_unsorted, int dtype, const uint32_t *rec, const uint32_t *rec_q, const void *rng,
+                             const double *thr_poly, const int32_t *perm, const int64_t *frame_off, int n_frames, int32_t *tile_cnt, int32_t *tile_base,
+                             void *out_rows, uint8_t *out_keep, int64_t *out_counts, int64_t *out_stats, const unsigned long long *diff2, const SgFov *fov,
+                             int64_t max_tiles_per_frame, unsigned long long *tiles_done /* n_frames words, zero */, void *stream);
 int sg_launch_crop_count(const void *rows, int dtype, const int64_t *frame_off, int n_frames, uint8_t *keep, int32_t *tile_cnt,
                          int32_t *tile_base, int64_t *out_counts, int64_t *stats_scratch, const SgFov *fov, int64_t max_tiles, void *stream);
 int sg_launch_crop_scatter(const void *rows, int dtype, const uint8_t *keep, const int64_t *frame_off, const int64_t *new_off,

@@ -253,6 +253,7 @@ struct BatchDev {
     const int32_t *perm;      // may be null -> device sort
     void *out_rows;
     int32_t *out_src;
+    uint8_t *out_keep = nullptr;   // non-null: the aligned finish -- every row at its input index in out_rows (which may be `rows`), its keep flag here; out_src unused
     int64_t *out_counts;
     int64_t *out_stats;
     double *out_thr_poly;     // may be null

@@ -76,7 +76,7 @@ void parallel_for(int64_t n_items, int threads, F &&body)
 
 template <typename T>
 int augment_batch(int n_frames, const int64_t *off, const T *rows, int n_tables, const double *const *xyr, const int64_t *tk, const int32_t *table_ids,
-                  const SgLasers &las, double div, const double *thr_poly, int threads, T *out_rows, int32_t *out_src, int64_t *out_counts,
+                  const SgLasers &las, double div, const double *thr_poly, int threads, T *out_rows, int32_t *out_src, uint8_t *out_keep, int64_t *out_counts,
                   int64_t *out_stats, int32_t *status)
 {
     const int n_las = las.n;
@@ -163,11 +163,18 @@ int augment_batch(int n_frames, const int64_t *off, const T *rows, int n_tables,
             const T dd2 = o.dd * o.dd;
             const double thr = (p0 * (double)dd2 + p1 * (double)o.dd) + p2;        // :465-469: d^2 in the row dtype
             const bool keep = (o.lab == (T)2) || ((double)o.i > thr);             // :518-520
+            if (out_keep) {                                                       // aligned: every row at its input index, the flag beside it
+                T *q = out_rows + (b + perm[(size_t)g]) * 5;
+                q[0] = o.x; q[1] = o.y; q[2] = o.z; q[3] = o.i; q[4] = o.lab;
+                out_keep[b + perm[(size_t)g]] = keep ? 1 : 0;
+            }
             if (!keep) continue;
             att += o.lab == (T)1;
-            T *q = out_rows + (b + kept) * 5;
-            q[0] = o.x; q[1] = o.y; q[2] = o.z; q[3] = o.i; q[4] = o.lab;
-            if (out_src) out_src[b + kept] = perm[(size_t)g];
+            if (!out_keep) {
+                T *q = out_rows + (b + kept) * 5;
+                q[0] = o.x; q[1] = o.y; q[2] = o.z; q[3] = o.i; q[4] = o.lab;
+                if (out_src) out_src[b + kept] = perm[(size_t)g];
+            }
             ++kept;
         }
         out_counts[f] = kept;
@@ -184,11 +191,12 @@ int augment_batch(int n_frames, const int64_t *off, const T *rows, int n_tables,
 
 extern "C" const char *snowgpu_cpu_version(void) { return "snowcpu 0.1.0 host (the kernels' device code compiled for the host; baseline, not a fallback)"; }
 
-extern "C" int snowgpu_cpu_augment_batch(int n_frames, const int64_t *frame_offsets, const void *rows, int dtype, int n_tables,
-                                         const double *const *tables_xyr, const int64_t *tables_k, const int32_t *table_ids, int n_lasers,
-                                         const double *focal_slope, const double *focal_offset, const int32_t *min_intensity,
-                                         const int32_t *max_intensity, double beam_divergence_deg, const double *thr_poly, double noise_floor,
-                                         int threads, void *out_rows, int32_t *out_src, int64_t *out_counts, int64_t *out_stats, int32_t *status)
+// both layouts of the result: out_keep null = compacted rows (+ out_src), else every row at its input index + its flag
+static int cpu_entry(int n_frames, const int64_t *frame_offsets, const void *rows, int dtype, int n_tables,
+                     const double *const *tables_xyr, const int64_t *tables_k, const int32_t *table_ids, int n_lasers,
+                     const double *focal_slope, const double *focal_offset, const int32_t *min_intensity,
+                     const int32_t *max_intensity, double beam_divergence_deg, const double *thr_poly, double noise_floor,
+                     int threads, void *out_rows, int32_t *out_src, uint8_t *out_keep, int64_t *out_counts, int64_t *out_stats, int32_t *status)
 {
     int32_t local[2] = {0, -1};
     if (!status) status = local;
@@ -204,7 +212,28 @@ extern "C" int snowgpu_cpu_augment_batch(int n_frames, const int64_t *frame_offs
     if (threads <= 0) threads = usable_cpus();
     if (dtype == 0)
         return augment_batch<float>(n_frames, frame_offsets, (const float *)rows, n_tables, tables_xyr, tables_k, table_ids, las, beam_divergence_deg,
-                                    thr_poly, threads, (float *)out_rows, out_src, out_counts, out_stats, status);
+                                    thr_poly, threads, (float *)out_rows, out_src, out_keep, out_counts, out_stats, status);
     return augment_batch<double>(n_frames, frame_offsets, (const double *)rows, n_tables, tables_xyr, tables_k, table_ids, las, beam_divergence_deg,
-                                 thr_poly, threads, (double *)out_rows, out_src, out_counts, out_stats, status);
+                                 thr_poly, threads, (double *)out_rows, out_src, out_keep, out_counts, out_stats, status);
+}
+
+extern "C" int snowgpu_cpu_augment_batch(int n_frames, const int64_t *frame_offsets, const void *rows, int dtype, int n_tables,
+                                         const double *const *tables_xyr, const int64_t *tables_k, const int32_t *table_ids, int n_lasers,
+                                         const double *focal_slope, const double *focal_offset, const int32_t *min_intensity,
+                                         const int32_t *max_intensity, double beam_divergence_deg, const double *thr_poly, double noise_floor,
+                                         int threads, void *out_rows, int32_t *out_src, int64_t *out_counts, int64_t *out_stats, int32_t *status)
+{
+    return cpu_entry(n_frames, frame_offsets, rows, dtype, n_tables, tables_xyr, tables_k, table_ids, n_lasers, focal_slope, focal_offset, min_intensity,
+                     max_intensity, beam_divergence_deg, thr_poly, noise_floor, threads, out_rows, out_src, nullptr, out_counts, out_stats, status);
+}
+
+extern "C" int snowgpu_cpu_augment_batch_aligned(int n_frames, const int64_t *frame_offsets, const void *rows, int dtype, int n_tables,
+                                                 const double *const *tables_xyr, const int64_t *tables_k, const int32_t *table_ids, int n_lasers,
+                                                 const double *focal_slope, const double *focal_offset, const int32_t *min_intensity,
+                                                 const int32_t *max_intensity, double beam_divergence_deg, const double *thr_poly, double noise_floor,
+                                                 int threads, void *out_rows, uint8_t *out_keep, int64_t *out_counts, int64_t *out_stats, int32_t *status)
+{
+    if (!out_keep || out_rows == rows) { if (status) { status[0] = 1; status[1] = -1; } return 1; }     /* SNOWGPU_E_INVALID (the twin is not in place) */
+    return cpu_entry(n_frames, frame_offsets, rows, dtype, n_tables, tables_xyr, tables_k, table_ids, n_lasers, focal_slope, focal_offset, min_intensity,
+                     max_intensity, beam_divergence_deg, thr_poly, noise_floor, threads, out_rows, nullptr, out_keep, out_counts, out_stats, status);
 }

@@ -367,6 +367,41 @@ extern "C" int snowgpu_augment_batch_device(snowgpu_ctx *ctx, int n_frames, int6
     return run_batch(ctx, b);
 }
 
+// snowgpu_augment_batch_device with the ALIGNED result layout: every row of the input comes back at its own index (d_out_rows, which may be
+// d_rows itself), d_out_keep says which of them the reference would have returned.  Same launch sequence up to the last step, which is one
+// kernel (k_finish_aligned) instead of the three of the compaction.
+extern "C" int snowgpu_augment_batch_device_aligned(snowgpu_ctx *ctx, int n_frames, int64_t n_total, int64_t max_frame_rows,
+                                                    const int64_t *d_frame_offsets, const void *d_rows, int dtype, const int32_t *d_table_ids,
+                                                    double beam_divergence_deg, const double *d_thr_poly, const double *d_plane,
+                                                    double noise_floor, const int32_t *d_perm, void *d_out_rows, uint8_t *d_out_keep,
+                                                    int64_t *d_out_counts, int64_t *d_out_stats, double *d_out_thr_poly,
+                                                    int32_t *d_status, void *stream)
+{
+    if (!ctx) return SNOWGPU_E_INVALID;
+    if (n_frames <= 0 || n_total < 0 || !d_frame_offsets || (n_total > 0 && !d_rows) || !d_table_ids || !d_out_rows ||
+        !d_out_keep || !d_out_counts || !d_out_stats || !d_status || (dtype != 0 && dtype != 1))
+        return fail(ctx, SNOWGPU_E_INVALID, "snowgpu_augment_batch_device_aligned: null pointer or bad dtype");
+    if (n_total >= ((int64_t)1 << 31)) return fail(ctx, SNOWGPU_E_INVALID, "batch too large: split it below 2^31 rows");
+    if (ctx->thr_fn) return fail(ctx, SNOWGPU_E_INVALID, "snowgpu_augment_batch_device_aligned: a threshold callback is set; it finishes batches through the compaction only");
+    if (ctx->result_mode != 0) return fail(ctx, SNOWGPU_E_INVALID, "snowgpu_augment_batch_device_aligned: the packed result transfer is set; it is a form of the compacted result");
+    {
+        const size_t bytes = (size_t)n_total * 5 * (dtype == 0 ? 4 : 8);
+        const char *a = (const char *)d_rows, *o = (const char *)d_out_rows;
+        if (o != a && o < a + bytes && a < o + bytes)
+            return fail(ctx, SNOWGPU_E_INVALID, "snowgpu_augment_batch_device_aligned: d_out_rows overlaps d_rows; pass d_rows itself (in place) or a buffer apart from it");
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    BatchDev b{};
+    b.n_frames = n_frames; b.n_total = n_total; b.max_frame = (max_frame_rows > 0 && max_frame_rows <= n_total) ? max_frame_rows : n_total;
+    b.frame_off = d_frame_offsets;
+    b.uniform_rows = (max_frame_rows > 0 && max_frame_rows * (int64_t)n_frames == n_total) ? max_frame_rows : 0; b.rows = d_rows;
+    b.dtype = dtype; b.table_ids = d_table_ids; b.beam_div_deg = beam_divergence_deg; b.thr_poly = d_thr_poly;
+    b.plane = d_plane; b.noise_floor = noise_floor; b.perm = d_perm; b.out_rows = d_out_rows; b.out_src = nullptr; b.out_keep = d_out_keep;
+    b.out_counts = d_out_counts; b.out_stats = d_out_stats; b.out_thr_poly = d_out_thr_poly; b.status = d_status;
+    b.stream = stream ? (hipStream_t)stream : ctx->stream;
+    return run_batch(ctx, b);
+}
+
 extern "C" int snowgpu_sample_table(snowgpu_ctx *ctx, int table_id, double occupancy_ratio, double diameter_scale_mm, double r_0,
                                     uint64_t seed, double *xyr_out, int64_t cap, int64_t *n_out)
 {

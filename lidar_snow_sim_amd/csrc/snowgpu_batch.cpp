@@ -457,6 +457,21 @@ static int launch_compaction(snowgpu_ctx *ctx, BatchDev &b, const int32_t *perm,
 {
     snowgpu_ctx *R = ctx->root ? ctx->root : ctx;
     hipStream_t st = b.stream;
+    // small batches: the per-frame scan inside the count kernel / the aligned finish
+    unsigned long long *tiles_done = b.n_total <= ((int64_t)1 << 19) ? ctx->qn.p + 3 * regions + (size_t)b.n_frames + 8 : nullptr;
+    if (b.out_keep) {
+        // Aligned finish (k_finish_aligned).  b.out_rows may be b.rows: this is the first WRITE to the caller's rows, and every reader of them
+        // is ordered ahead of it on `st` -- the sort (or the gather through a caller's permutation), the plane estimate of fuse_stats, the pass
+        // over all rows, the tier gather, the first later tier and (small batches) the rare tiers run on `st` itself; the segment builder,
+        // k_power_few / k_power and (large batches) the rare tiers on aux (ev_join, ev_join2); the other later tiers, among them
+        // k_tier_scan_direct, on aux3 (ev_join3); the histogram fill, k_lean_stats / k_lean_hist, the plane kernels and the prepass on aux2,
+        // whose last record is ev_join0 (launch_prepass runs whenever aux2 was forked), waited for by run_batch just ahead of this step.
+        int e = sg_launch_finish_aligned(b.rows, ctx->srows.p, ctx->frame_unsorted.p, b.dtype, ctx->rec.p, ctx->rec_q.p, ctx->rng.p, thr, perm, b.frame_off, b.n_frames,
+                                         ctx->ctile_cnt.p, ctx->ctile_base.p, b.out_rows, b.out_keep, b.out_counts, b.out_stats, ctx->qn.p + 3 * regions,
+                                         b.no_fov ? nullptr : &R->fov, max_tiles, tiles_done, st);
+        if (e) return fail(ctx, SNOWGPU_E_HIP, std::string("aligned finish launch: ") + hipGetErrorString((hipError_t)e));
+        return SNOWGPU_OK;
+    }
     if (b.pack) {
         ENSURE(ctx, ctx->pk_tile_mv, (size_t)b.n_frames * (size_t)max_tiles + 1);
         ENSURE(ctx, ctx->pk_tile_mv_base, (size_t)b.n_frames * (size_t)max_tiles + 1);
@@ -465,8 +480,7 @@ static int launch_compaction(snowgpu_ctx *ctx, BatchDev &b, const int32_t *perm,
     int e = sg_launch_compact(b.rows, ctx->srows.p, ctx->frame_unsorted.p, b.dtype, ctx->rec.p, ctx->rec_q.p, ctx->rng.p, thr, ctx->keep.p, perm, b.frame_off, b.n_frames, b.n_total,
                               ctx->ctile_cnt.p, ctx->ctile_base.p, b.out_rows, b.out_src, b.out_counts, b.out_stats,
                               ctx->qn.p + 3 * regions, b.no_fov ? nullptr : &R->fov, max_tiles, b.pack,
-                              b.n_total <= ((int64_t)1 << 19) ? ctx->qn.p + 3 * regions + (size_t)b.n_frames + 8 : nullptr,      // (small batches: the scan inside the count kernel)
-                              st);
+                              tiles_done, st);
     if (e) return fail(ctx, SNOWGPU_E_HIP, std::string("compaction launch: ") + hipGetErrorString((hipError_t)e));
     return SNOWGPU_OK;
 }

@@ -2,6 +2,7 @@
 //
 //   k_compact_*  output rows from original rows + 4-byte result records, noise-floor filter, camera-FOV crop, stable
 //                stream compaction, stats                                                   (simulation.py:516-540)
+//   k_finish_aligned  the same decision, but every row goes to the INPUT's own index with a keep flag beside it (no scatter pass)
 //   k_crop_*     the camera-FOV crop ahead of the augmentation (same flags, same per-frame scan: k_compact_scan)
 //
 // The result records come from the per-beam kernels (snowgpu_kernels.hip) in the channel-sorted order of snowgpu_sort.hip.
@@ -79,6 +80,71 @@ __global__ __launch_bounds__(64) void k_compact_scan(const int64_t *__restrict__
     sg_compact_scan_frame(f, frame_off[f + 1] - frame_off[f], tile_cnt, tile_base, out_counts, out_stats, diff2, max_tiles, tile_mv, tile_mv_base, out_mv_counts);
 }
 
+// The decision about one sorted position (simulation.py:518-520, :532-540), shared by k_compact_count and k_finish_aligned: the one place it
+// is written down.  keep = (label == 2) | (intensity > p0 d^2 + p1 d + p2), d the ORIGINAL range, d^2 in the row dtype (simulation.py:465,
+// :469).  `row` is the original row (global memory, or the caller's registers), rc the record (slot references resolved), dd_rng the range
+// the pass over all rows left (have_rng).
+struct SgDecision { bool keep, noise_ok, is_att; };
+
+template <typename T>
+__device__ __forceinline__ SgDecision sg_row_decision(const T *row, uint32_t rc, T dd_rng, bool have_rng, const SgFov &fov, double p0, double p1, double p2)
+{
+    const int lab_i = (int)((rc >> SG_REC_LABEL_SHIFT) & 3u);
+    // Without the camera crop the decision needs the label, the (new or original) intensity and the original range only: a
+    // beam the pass over all rows simulated left its range in rng, and the record holds the intensity unless the beam came
+    // back unchanged from a later kernel -- those, and rows without a laser, read the row as before.
+    const bool from_rec = have_rng && !fov.enabled && !(rc & SG_REC_COPY) && (lab_i != 0 || (rc & SG_REC_HAS_I));
+    SgDecision d;
+    if (from_rec) {
+        const T dd = dd_rng;
+        const T dd2 = dd * dd;
+        const double thr = (p0 * (double)dd2 + p1 * (double)dd) + p2;
+        d.noise_ok = (lab_i == 2) || ((double)(T)(int)(rc & 255u) > thr);
+        d.is_att = lab_i == 1;
+        d.keep = d.noise_ok;
+    } else {
+        const SgRow<T> o = sg_rebuild_row<T>(row, rc);
+        const T dd2 = o.dd * o.dd;
+        const double thr = (p0 * (double)dd2 + p1 * (double)o.dd) + p2;
+        d.noise_ok = (o.lab == (T)2) || ((double)o.i > thr);
+        d.is_att = o.lab == (T)1;
+        d.keep = d.noise_ok;
+        if (fov.enabled && d.keep) d.keep = sg_in_fov(fov, (double)o.x, (double)o.y, (double)o.z);   // :532-540
+    }
+    return d;
+}
+
+// What a block of k_compact_count / k_finish_aligned does once its threads have decided their rows: c = kept | attenuated << 16 and mv
+// (kept label-2 rows) summed over the block into the tile's words; for small batches the frame's scan by the block that completes it.
+__device__ __forceinline__ void sg_tile_counts_done(int f, int64_t n, int c, int mv, int32_t *__restrict__ tile_cnt, int64_t max_tiles, int32_t *__restrict__ tile_mv,
+                                                    unsigned long long *__restrict__ tiles_done, int32_t *__restrict__ tile_base, int64_t *__restrict__ out_counts,
+                                                    int64_t *__restrict__ out_stats, const unsigned long long *__restrict__ diff2,
+                                                    int32_t *__restrict__ tile_mv_base, int64_t *__restrict__ out_mv_counts)
+{
+    __shared__ int s[4], s2[4], s_last;
+    for (int o = 32; o > 0; o >>= 1) { c += __shfl_down(c, o); mv += __shfl_down(mv, o); }
+    if ((threadIdx.x & 63) == 0) { s[threadIdx.x >> 6] = c; s2[threadIdx.x >> 6] = mv; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        tile_cnt[(int64_t)f * max_tiles + blockIdx.x] = s[0] + s[1] + s[2] + s[3];   // kept | attenuated << 16 (a tile has 1024 rows)
+        if (tile_mv) tile_mv[(int64_t)f * max_tiles + blockIdx.x] = s2[0] + s2[1] + s2[2] + s2[3];
+        // Small batches (tiles_done != null): the block that completes a frame scans its tiles -- what k_compact_scan does as a launch of its
+        // own: one link less on the chain.  Not for large batches: the device-scope fence this needs writes back the L2 of the block's XCD
+        // (eight XCDs, eight L2s), and 32 768 of them made this kernel 1.37 ms long on 256 sweeps instead of 0.15.
+        if (tiles_done) {
+            __threadfence();
+            const unsigned long long tiles = (unsigned long long)((n + SG_TILE - 1) / SG_TILE);
+            s_last = atomicAdd(&tiles_done[f], 1ull) == tiles - 1;
+            if (s_last) __threadfence();
+        }
+    }
+    if (tiles_done) {                                 // (kernel argument: uniform)
+        __syncthreads();
+        if (s_last && threadIdx.x < 64)
+            sg_compact_scan_frame(f, n, tile_cnt, tile_base, out_counts, out_stats, diff2, max_tiles, tile_mv, tile_mv_base, out_mv_counts);
+    }
+}
+
 // Stable compaction of kept rows, per frame.  keep byte: bit 0 = row is in the output, bit 1 = row passed the noise filter
 // (num_attenuated counts those, before the camera crop: simulation.py:525 precedes :532-540).
 template <typename T>
@@ -121,59 +187,81 @@ __global__ __launch_bounds__(SG_BLOCK) void k_compact_count(const T *__restrict_
     for (int q = 0; q < 4; ++q) {
         const int64_t r = tile0 + q * SG_BLOCK + threadIdx.x;
         if (r >= n) continue;
-        // keep = (label == 2) | (intensity > p0 d^2 + p1 d + p2), d the ORIGINAL range, d^2 in the row dtype
-        // (simulation.py:465, :469, :518-520)
         const uint32_t rc = rcs[q];
         const int lab_i = (int)((rc >> SG_REC_LABEL_SHIFT) & 3u);
-        // Without the camera crop the decision needs the label, the (new or original) intensity and the original range only: a
-        // beam the pass over all rows simulated left its range in rng, and the record holds the intensity unless the beam came
-        // back unchanged from a later kernel -- those, and rows without a laser, read the row as before.
-        const bool from_rec = rng != nullptr && !fov.enabled && !(rc & SG_REC_COPY) && (lab_i != 0 || (rc & SG_REC_HAS_I));
-        bool noise_ok, is_att;
-        bool k;
-        if (from_rec) {
-            const T dd = dds[q];
-            const T dd2 = dd * dd;
-            const double thr = (p0 * (double)dd2 + p1 * (double)dd) + p2;
-            noise_ok = (lab_i == 2) || ((double)(T)(int)(rc & 255u) > thr);
-            is_att = lab_i == 1;
-            k = noise_ok;
-        } else {
-            const SgRow<T> o = sg_rebuild_row<T>(rows + (base + r) * 5, rc);
-            const T dd2 = o.dd * o.dd;
-            const double thr = (p0 * (double)dd2 + p1 * (double)o.dd) + p2;
-            noise_ok = (o.lab == (T)2) || ((double)o.i > thr);
-            is_att = o.lab == (T)1;
-            k = noise_ok;
-            if (fov.enabled && k) k = sg_in_fov(fov, (double)o.x, (double)o.y, (double)o.z);   // :532-540
+        const SgDecision d = sg_row_decision<T>(rows + (base + r) * 5, rc, dds[q], rng != nullptr, fov, p0, p1, p2);
+        keep[base + r] = (uint8_t)((d.keep ? 1 : 0) | (d.noise_ok ? 2 : 0));
+        c += d.keep;
+        mv += (d.keep && lab_i == 2) ? 1 : 0;
+        c += (d.noise_ok && d.is_att) ? (1 << 16) : 0;                      // high half: rows that count in num_attenuated (:525, before the crop)
+    }
+    sg_tile_counts_done(f, n, c, mv, tile_cnt, max_tiles, tile_mv, tiles_done, tile_base, out_counts, out_stats, diff2, tile_mv_base, out_mv_counts);
+}
+
+// Aligned finish: the decision of k_compact_count and the output row of k_compact_scatter in ONE pass, every row written to the index it has
+// in the caller's INPUT frame -- out_rows[base + i], i = perm[g] for frames in firing order, g for channel-sorted ones (what the scatter writes
+// to out_src) -- and out_keep[base + i] = 1 where the reference would have returned the row.  Removed rows are written too: what aug_pc
+// held just before simulation.py:523 (sg_rebuild_row), so the result is deterministic byte for byte.  tile_cnt as k_compact_count leaves it:
+// counts and statistics by the same scan.
+// out_rows may BE rows_in (in place; no __restrict__ on the three row pointers): a thread loads its four rows before its first store and
+// writes only where it (channel-sorted frame: i = g) or nobody (firing order: reads come from srows) reads.  In place the coordinates of a
+// row whose label is not 2 already lie there and are not stored again.
+template <typename T>
+__global__ __launch_bounds__(SG_BLOCK) void k_finish_aligned(const T *rows_in, const T *srows, const int32_t *__restrict__ frame_unsorted,
+                                                             const uint32_t *__restrict__ rec, const uint32_t *__restrict__ rec_q, const T *__restrict__ rng,
+                                                             const double *__restrict__ thr_poly, const int32_t *__restrict__ perm, const int64_t *__restrict__ frame_off,
+                                                             T *out_rows, uint8_t *__restrict__ out_keep, int32_t *__restrict__ tile_cnt, int64_t max_tiles, SgFov fov,
+                                                             unsigned long long *__restrict__ tiles_done, int32_t *__restrict__ tile_base, int64_t *__restrict__ out_counts,
+                                                             int64_t *__restrict__ out_stats, const unsigned long long *__restrict__ diff2)
+{
+    const int f = blockIdx.y;
+    const int64_t base = frame_off[f], n = frame_off[f + 1] - base;
+    const int64_t tile0 = (int64_t)blockIdx.x * SG_TILE;
+    if (tile0 >= n) {
+        if (tiles_done && blockIdx.x == 0 && threadIdx.x == 0) {       // an empty frame has no tile to complete it: its counts here
+            out_counts[f] = 0; out_stats[f * 3 + 0] = 0; out_stats[f * 3 + 1] = 0; out_stats[f * 3 + 2] = 0;
         }
-        keep[base + r] = (uint8_t)((k ? 1 : 0) | (noise_ok ? 2 : 0));
-        c += k;
-        mv += (k && lab_i == 2) ? 1 : 0;
-        c += (noise_ok && is_att) ? (1 << 16) : 0;                          // high half: rows that count in num_attenuated (:525, before the crop)
+        return;
     }
-    __shared__ int s[4], s2[4], s_last;
-    for (int o = 32; o > 0; o >>= 1) { c += __shfl_down(c, o); mv += __shfl_down(mv, o); }
-    if ((threadIdx.x & 63) == 0) { s[threadIdx.x >> 6] = c; s2[threadIdx.x >> 6] = mv; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        tile_cnt[(int64_t)f * max_tiles + blockIdx.x] = s[0] + s[1] + s[2] + s[3];   // kept | attenuated << 16 (a tile has 1024 rows)
-        if (tile_mv) tile_mv[(int64_t)f * max_tiles + blockIdx.x] = s2[0] + s2[1] + s2[2] + s2[3];
-        // Small batches (tiles_done != null): the block that completes a frame scans its tiles -- what k_compact_scan does as a launch of its
-        // own: one link less on the chain.  Not for large batches: the device-scope fence this needs writes back the L2 of the block's XCD
-        // (eight XCDs, eight L2s), and 32 768 of them made this kernel 1.37 ms long on 256 sweeps instead of 0.15.
-        if (tiles_done) {
-            __threadfence();
-            const unsigned long long tiles = (unsigned long long)((n + SG_TILE - 1) / SG_TILE);
-            s_last = atomicAdd(&tiles_done[f], 1ull) == tiles - 1;
-            if (s_last) __threadfence();
+    const bool uns = frame_unsorted[f] != 0;
+    const T *rows = uns ? srows : rows_in;                          // sorted position g = row g (see k_sort_scatter)
+    const bool in_place = out_rows == rows_in;
+    const double p0 = thr_poly[(int64_t)f * 3], p1 = thr_poly[(int64_t)f * 3 + 1], p2 = thr_poly[(int64_t)f * 3 + 2];
+    int c = 0;
+    // every load of the thread's four rows side by side (see k_compact_count), and ahead of its first store
+    uint32_t rcs[4];
+    T dds[4], rv[4][5];
+    int64_t dst[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int64_t r = tile0 + q * SG_BLOCK + threadIdx.x;
+        const bool in = r < n;
+        rcs[q] = in ? rec[base + r] : 0u;
+        dds[q] = (in && rng != nullptr) ? rng[base + r] : (T)0;
+        dst[q] = (in && uns) ? (int64_t)perm[base + r] : r;
+#pragma unroll
+        for (int j = 0; j < 5; ++j) rv[q][j] = in ? rows[(base + r) * 5 + j] : (T)0;
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+        if (rcs[q] & SG_REC_SLOT) rcs[q] = rec_q[rcs[q] & ~SG_REC_SLOT];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int64_t r = tile0 + q * SG_BLOCK + threadIdx.x;
+        if (r >= n) continue;
+        const uint32_t rc = rcs[q];
+        const SgDecision d = sg_row_decision<T>(rv[q], rc, dds[q], rng != nullptr, fov, p0, p1, p2);
+        const SgRow<T> o = sg_rebuild_row<T>(rv[q], rc);
+        if ((uint64_t)dst[q] < (uint64_t)n) {                       // (a caller's permutation is not trusted with a store)
+            T *w = out_rows + (base + dst[q]) * 5;
+            if (!in_place || ((rc >> SG_REC_LABEL_SHIFT) & 3u) == 2u) { w[0] = o.x; w[1] = o.y; w[2] = o.z; }
+            w[3] = o.i; w[4] = o.lab;
+            out_keep[base + dst[q]] = d.keep ? 1 : 0;
         }
+        c += d.keep;
+        c += (d.noise_ok && d.is_att) ? (1 << 16) : 0;
     }
-    if (tiles_done) {                                 // (kernel argument: uniform)
-        __syncthreads();
-        if (s_last && threadIdx.x < 64)
-            sg_compact_scan_frame(f, n, tile_cnt, tile_base, out_counts, out_stats, diff2, max_tiles, tile_mv, tile_mv_base, out_mv_counts);
-    }
+    sg_tile_counts_done(f, n, c, 0, tile_cnt, max_tiles, nullptr, tiles_done, tile_base, out_counts, out_stats, diff2, nullptr, nullptr);
 }
 
 // PACK (packed result transfer, snowgpu_set_result_transfer): instead of the 5-column output row, per kept row a 4-byte word -- source row
@@ -365,6 +453,31 @@ extern "C" int sg_launch_compact(const void *rows, const void *srows, const int3
         if (pack) hipLaunchKernelGGL((k_compact_scatter<T, true>), grid, dim3(SG_BLOCK), 0, st, (const T *)rows, (const T *)srows, frame_unsorted, rec, rec_q, keep, perm, frame_off, tile_base, (T *)out_rows, out_src, out_stats, max_tiles, pk);
         else hipLaunchKernelGGL((k_compact_scatter<T, false>), grid, dim3(SG_BLOCK), 0, st, (const T *)rows, (const T *)srows, frame_unsorted, rec, rec_q, keep, perm, frame_off, tile_base, (T *)out_rows, out_src, out_stats, max_tiles, pk);
         SG_CHECK_LAUNCH();
+        return 0;
+    });
+}
+
+// The aligned finish instead of the compaction: one pass (k_finish_aligned), then -- unless the pass scanned its frames itself (tiles_done) --
+// the per-frame scan for out_counts / out_stats.  No scatter pass, no out_src.
+extern "C" int sg_launch_finish_aligned(const void *rows, const void *srows, const int32_t *frame_unsorted, int dtype, const uint32_t *rec, const uint32_t *rec_q, const void *rng,
+                                        const double *thr_poly, const int32_t *perm, const int64_t *frame_off, int n_frames, int32_t *tile_cnt, int32_t *tile_base,
+                                        void *out_rows, uint8_t *out_keep, int64_t *out_counts, int64_t *out_stats, const unsigned long long *diff2, const SgFov *fov,
+                                        int64_t max_tiles, unsigned long long *tiles_done /* n_frames words, zero */, void *stream)
+{
+    hipStream_t st = (hipStream_t)stream;
+    dim3 grid((unsigned)max_tiles, (unsigned)n_frames);
+    SgFov fv{};
+    if (fov) fv = *fov;
+    return sg_by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(k_finish_aligned<T>, grid, dim3(SG_BLOCK), 0, st, (const T *)rows, (const T *)srows, frame_unsorted, rec, rec_q, (const T *)rng, thr_poly, perm, frame_off,
+                           (T *)out_rows, out_keep, tile_cnt, max_tiles, fv, tiles_done, tile_base, out_counts, out_stats, diff2);
+        SG_CHECK_LAUNCH();
+        if (!tiles_done) {
+            hipLaunchKernelGGL(k_compact_scan, dim3(n_frames), dim3(64), 0, st, frame_off, tile_cnt, tile_base, out_counts, out_stats, diff2, max_tiles,
+                               (const int32_t *)nullptr, (int32_t *)nullptr, (int64_t *)nullptr);
+            SG_CHECK_LAUNCH();
+        }
         return 0;
     });
 }

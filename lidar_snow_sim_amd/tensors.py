@@ -9,7 +9,10 @@ The reference's training-time caller (the OpenPCDet DENSE dataset: `root_path`, 
   * results are torch tensors on the same device, allocated by torch's caching allocator (no hipMalloc after the first call of a size);
   * `sync=False` returns a DeviceResult at once -- nothing has been waited for, the counts are still a device tensor -- so that the
     call can be chained in front of the consumer's kernels; `sync=True` (default) waits, checks the status words and returns
-    the reference-shaped list of (stats, aug_pc) with aug_pc a view of the result tensor.
+    the reference-shaped list of (stats, aug_pc) with aug_pc a view of the result tensor;
+  * `layout='aligned'` returns the rows in the INPUT's order with one keep flag per row (AlignedResult) instead of compacting them: a
+    result whose shape does not depend on the data, so a consumer on the same stream -- or in the same HIP graph -- reads it without a
+    host round trip, and per-point companions of the sweep (labels, timestamps, further columns) stay aligned with it.
 
 What crosses the link per call: the frame offsets, the n_frames x n_lasers table ids and the planes (a few KB, cached by value: a
 training loop that reshuffles `order` per frame uploads 64 int32 per frame).  PyTorch is plumbing here -- device memory and streams;
@@ -103,6 +106,36 @@ class DeviceResult:
         return out
 
 
+class AlignedResult(DeviceResult):
+    """What a `layout='aligned'` call leaves behind: `rows` (N_total x 5, input dtype: row i is the output row of INPUT row i -- removed
+    rows too, as they stood before the reference drops them), `keep` (N_total, torch.bool: True where the reference returns the row),
+    `counts` (n_frames: flags set per frame), `stats`, `status`, `offsets` as in a DeviceResult.  Nothing here has a data-dependent
+    shape: `(rows[:, 3] * keep).sum()` and the like can follow on the same stream, or in the same captured graph, without the host."""
+
+    def __init__(self, ctx, rows, keep_mask, counts, stats, status, offsets, stream, keep=()):
+        super().__init__(ctx, rows, None, counts, stats, status, offsets, stream, keep=keep)
+        self.keep = keep_mask
+
+    def wait(self):
+        """DeviceResult.wait(), with the status words raised as the reference's exception types (IndexError for a point at >= 120 m,
+        TypeError for a frame without ground rows), as the synchronous call raises them."""
+        from .tools.snowfall.simulation import _raise_like_reference
+        try:
+            return super().wait()
+        except _native.SnowGPUError as err:
+            _raise_like_reference(err)
+
+    def frames(self):
+        """[(stats, rows_f, keep_f)] per frame, rows_f / keep_f views of the result tensors (waits, as DeviceResult.frames does)."""
+        self.wait()
+        stats = self.stats.cpu().numpy()
+        out = []
+        for i in range(len(self.offsets) - 1):
+            a, b = int(self.offsets[i]), int(self.offsets[i + 1])
+            out.append(((np.int64(stats[i, 0]), np.int64(stats[i, 1]), int(stats[i, 2])), self.rows[a:b], self.keep[a:b]))
+        return out
+
+
 class _SmallUploads:
     """Device copies of the small per-call arrays (offsets, table ids, planes, polynomials), by value: a few KB each, least
     recently used first out."""
@@ -161,6 +194,26 @@ def _as_batch(torch, frames):
     return rows, offsets, (frames if extra else None)
 
 
+def _rows_where_they_lie(torch, frames):
+    """(rows, host offsets) of an input that is ALREADY one contiguous N_total x 5 float32 / float64 tensor -- a DeviceBatch, an F x N x 5
+    tensor, one N x 5 tensor (or a list of one) -- for in_place=True; anything that would have to be concatenated or converted raises."""
+    if isinstance(frames, DeviceBatch):
+        rows, offsets = frames.rows, frames.offsets
+    else:
+        t = frames[0] if isinstance(frames, (list, tuple)) and len(frames) == 1 else frames
+        if isinstance(t, (list, tuple)):
+            raise ValueError("in_place=True needs the frames in ONE tensor (a DeviceBatch, an F x N x 5 or an N x 5 tensor): a list is "
+                             "concatenated into a temporary, and the result would land there")
+        if t.dim() not in (2, 3) or t.shape[-1] != 5 or not t.is_contiguous():
+            raise ValueError("in_place=True needs a contiguous N x 5 or F x N x 5 tensor: the result is written over the input's five columns")
+        per = int(t.shape[-2])
+        offsets = np.arange((int(t.shape[0]) if t.dim() == 3 else 1) + 1, dtype=np.int64) * per
+        rows = t.reshape(-1, 5)
+    if rows.dtype not in (torch.float32, torch.float64):
+        raise ValueError("in_place=True needs float32 or float64 rows: other dtypes are converted into a temporary")
+    return rows, offsets
+
+
 def table_ids_for(eng, n_frames, particle_file_prefix, root_path, particles, orders, shuffle):
     """n_frames x n_lasers int32 device table ids: channel c of frame f reads line orders[f][c] + 1 (simulation.py:78, :482-486)."""
     from .tools.snowfall import simulation as _sim
@@ -187,7 +240,8 @@ def table_ids_for(eng, n_frames, particle_file_prefix, root_path, particles, ord
 
 def augment_batch(frames, particle_file_prefix, beam_divergence, shuffle=True, noise_floor=0.7, root_path=None, *, planes=None,
                   orders=None, particles=None, thr_polys=None, device=None, return_src=False, slot=0, calib=None, pre_crop=False,
-                  q8='first', plane_method='reference', plane_seed=0, plane_trials=1000, sync=True, wet=None, out=None, lane=None, **_ignored):
+                  q8='first', plane_method='reference', plane_seed=0, plane_trials=1000, sync=True, wet=None, out=None, lane=None,
+                  layout='compact', in_place=False, **_ignored):
     """augment_batch() of tools/snowfall/simulation.py for torch CUDA tensors (see that docstring for the shared arguments).
 
     frames   a list of N_i x 5 CUDA tensors (concatenated on the device), an F x N x 5 tensor, one N x 5 tensor, or a DeviceBatch
@@ -211,6 +265,17 @@ def augment_batch(frames, particle_file_prefix, beam_divergence, shuffle=True, n
              a time; with GPU_MAX_HW_QUEUES=32 in the environment before the process first touches the GPU all lanes run at one priority
              on queues of their own: three lanes 3.66 ms (profiles/r06_lanes_ab.txt).  Lanes are engine contexts of their own (slot
              LANE_SLOT0 + k): a plain call never runs on a lane's context.
+    layout   'compact' (default): the reference's return value, as above.  'aligned': nothing is compacted -- the result's `rows` hold
+             the output row of every input row at the input's own index and `keep` (torch.bool) says which of them the reference
+             returns (snowgpu_augment_batch_device_aligned).  sync=False returns an AlignedResult (rows, keep, counts, stats, status,
+             offsets; wait() / join() / frames() as a DeviceResult), sync=True its frames(): [(stats, rows_f, keep_f)], views.
+             rows_f[keep_f] are the compact rows in input order.  `out=` takes an earlier AlignedResult; lane=, calib=, planes=,
+             thr_polys=, orders=, particles=, plane_method= work as for the compact layout.  Frames with more than five columns:
+             the result has five, and the caller's further columns are ALREADY aligned with it, row for row -- nothing is gathered.
+             Not with wet= (the wet-ground estimator reads compacted rows) and not with return_src (row i IS input row i).
+    in_place with layout='aligned': the result's `rows` IS the input tensor, overwritten by its augmented form.  The input must be
+             read where it lies -- a DeviceBatch, one contiguous N x 5 tensor or an F x N x 5 tensor; a list that would have to be
+             concatenated raises ValueError (the result would land in a temporary).
     """
     import torch
     from . import engine as _engine
@@ -220,7 +285,21 @@ def augment_batch(frames, particle_file_prefix, beam_divergence, shuffle=True, n
         raise ValueError("pre_crop is a step of the host entry (precompute.py:96-99); crop the tensors before the call")
     if plane_method not in _native.PLANE_METHODS:
         raise ValueError("plane_method must be 'reference', 'lsq' or 'ransac'")
-    rows, offsets, extras = _as_batch(torch, frames)
+    if layout not in ('compact', 'aligned'):
+        raise ValueError("layout must be 'compact' or 'aligned'")
+    aligned = layout == 'aligned'
+    if in_place and not aligned:
+        raise ValueError("in_place=True needs layout='aligned': compacted rows do not lie where their input rows lay")
+    if aligned and wet is not None:
+        raise ValueError("wet= with layout='aligned': the wet-ground estimator reads the compacted snowfall rows and would have to skip "
+                         "masked ones; use the compact layout for the fused call")
+    if aligned and return_src:
+        raise ValueError("return_src with layout='aligned': there is no src, row i of the result is input row i")
+    if in_place:
+        rows, offsets = _rows_where_they_lie(torch, frames)
+        extras = None
+    else:
+        rows, offsets, extras = _as_batch(torch, frames)
     dev = rows.device
     if device is not None and int(device) != dev.index:
         raise ValueError(f"the tensors live on {dev}, device={device} was asked for")
@@ -241,9 +320,13 @@ def augment_batch(frames, particle_file_prefix, beam_divergence, shuffle=True, n
         if n == 0:                                   # nothing to simulate (the C ABI wants non-null buffers): empty frames come back empty
             zero = (np.int64(0), np.int64(0), 0)
             empty = [(zero, rows[:0], torch.empty(0, dtype=torch.int32, device=dev)) if return_src else (zero, rows[:0]) for _ in range(nf)]
+            z = lambda *shape, dt=torch.int64: torch.zeros(shape, dtype=dt, device=dev)   # noqa: E731
+            if aligned:
+                if sync:
+                    return [(zero, rows[:0], z(0, dt=torch.bool)) for _ in range(nf)]
+                return AlignedResult(eng.ctx, rows[:0], z(0, dt=torch.bool), z(nf), z(nf, 3), z(8, dt=torch.int32), offsets, torch.cuda.current_stream(dev))
             if sync:
                 return empty
-            z = lambda *shape, dt=torch.int64: torch.zeros(shape, dtype=dt, device=dev)   # noqa: E731
             return DeviceResult(eng.ctx, rows[:0], z(0, dt=torch.int32), z(nf), z(nf, 3), z(8, dt=torch.int32), offsets, torch.cuda.current_stream(dev))
         stream = torch.cuda.current_stream(dev)
         # The C ABI reads stream = NULL as "the context's own stream", which is not ordered against anything of torch's.  torch's legacy
@@ -282,7 +365,21 @@ def augment_batch(frames, particle_file_prefix, beam_divergence, shuffle=True, n
                 wp = [wp] * nf if len(wp) == 2 and np.ndim(wp[1]) == 0 else wp
                 d_wet_plane = up.get(torch, dev, np.asarray([[float(w[0]), float(w[1]), float(w[2]), float(h)] for w, h in wp], np.float64), run)
         out_dt = torch.float64 if wet is not None else rows.dtype
-        if out is not None and out.rows.shape[0] >= n and out.rows.dtype == out_dt and out.rows.device == dev and out.counts.shape[0] == nf:
+        o_keep = None
+        if aligned:
+            o_src = o_flags = None
+            if isinstance(out, AlignedResult) and out.keep.shape[0] == n and out.keep.device == dev and out.counts.shape[0] == nf and \
+                    (in_place or (out.rows.shape[0] == n and out.rows.dtype == out_dt and out.rows.data_ptr() != rows.data_ptr())):
+                o_rows, o_keep, o_cnt, o_st, o_status = out.rows, out.keep, out.counts, out.stats, out.status
+            else:
+                o_rows = None if in_place else torch.empty((n, 5), dtype=out_dt, device=dev)
+                o_keep = torch.empty(n, dtype=torch.bool, device=dev)              # (one byte per flag, 0 / 1: what the kernel writes)
+                o_cnt = torch.empty(nf, dtype=torch.int64, device=dev)
+                o_st = torch.empty((nf, 3), dtype=torch.int64, device=dev)
+                o_status = torch.empty(8, dtype=torch.int32, device=dev)
+            if in_place:
+                o_rows = rows
+        elif out is not None and not isinstance(out, AlignedResult) and out.rows.shape[0] >= n and out.rows.dtype == out_dt and out.rows.device == dev and out.counts.shape[0] == nf:
             o_rows, o_src, o_cnt, o_st, o_status, o_flags = out.rows, out.src, out.counts, out.stats, out.status, out.flags
         else:
             o_rows = torch.empty((n, 5), dtype=out_dt, device=dev)
@@ -296,7 +393,7 @@ def augment_batch(frames, particle_file_prefix, beam_divergence, shuffle=True, n
         if run is not stream:
             run.wait_stream(stream)
             if lane is not None:                    # (tensors of the caller's stream used on the lane's: the allocator must know)
-                for t in (rows, o_rows, o_src, o_cnt, o_st, o_status, o_flags):
+                for t in (rows, o_rows, o_src, o_keep, o_cnt, o_st, o_status, o_flags):
                     if t is not None:
                         t.record_stream(run)
         ptr = lambda t: 0 if t is None else t.data_ptr()   # noqa: E731
@@ -307,7 +404,11 @@ def augment_batch(frames, particle_file_prefix, beam_divergence, shuffle=True, n
             if device_plane or (wet is not None and d_wet_plane is None):
                 eng.ctx.set_plane_method(plane_method, seed=plane_seed, trials=plane_trials, min_rows=5)
             try:
-                if wet is None:
+                if aligned:
+                    eng.ctx.augment_batch_device_aligned(nf, n, max_rows, d_off.data_ptr(), rows.data_ptr(), code, d_tids.data_ptr(),
+                                                         float(beam_divergence), ptr(d_poly), ptr(d_plane), float(noise_floor), 0, o_rows.data_ptr(),
+                                                         o_keep.data_ptr(), o_cnt.data_ptr(), o_st.data_ptr(), 0, o_status.data_ptr(), run.cuda_stream)
+                elif wet is None:
                     eng.ctx.augment_batch_device(nf, n, max_rows, d_off.data_ptr(), rows.data_ptr(), code, d_tids.data_ptr(),
                                                  float(beam_divergence), ptr(d_poly), ptr(d_plane), float(noise_floor), 0, o_rows.data_ptr(),
                                                  o_src.data_ptr(), o_cnt.data_ptr(), o_st.data_ptr(), 0, o_status.data_ptr(), run.cuda_stream)
@@ -332,6 +433,9 @@ def augment_batch(frames, particle_file_prefix, beam_divergence, shuffle=True, n
                     eng.ctx.set_fov(None)
                 if plane_method != 'reference':
                     eng.ctx.set_plane_method('reference')
+    if aligned:
+        res = AlignedResult(eng.ctx, o_rows, o_keep, o_cnt, o_st, o_status, offsets, stream if lane is None else run, keep=(rows, d_off, d_tids, d_poly, d_plane))
+        return res.frames() if sync else res
     res = DeviceResult(eng.ctx, o_rows, o_src, o_cnt, o_st, o_status, offsets, stream if lane is None else run, flags=o_flags, keep=(rows, d_off, d_tids, d_poly, d_plane, d_wet_plane))
     if not sync:
         return res

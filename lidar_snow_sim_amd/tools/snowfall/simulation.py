@@ -173,7 +173,8 @@ def augment_batch(frames: Sequence[np.ndarray], particle_file_prefix: str, beam_
 
     torch CUDA tensors (a list of N_i x 5 tensors, an F x N x 5 tensor, or a lidar_snow_sim_amd.tensors.DeviceBatch) take the
     device-resident boundary instead: rows are read where they lie, the call runs on torch's current stream, aug_pc / src come back
-    as device tensors and no row crosses the link (lidar_snow_sim_amd/tensors.py, which also documents sync=False and wet=...).
+    as device tensors and no row crosses the link (lidar_snow_sim_amd/tensors.py, which also documents sync=False, wet=... and
+    layout='aligned' / in_place=True: the rows in the input's order with a keep mask instead of compacted rows).
     """
     from ... import tensors as _tensors
     if _tensors.is_device_input(frames):
@@ -183,6 +184,9 @@ def augment_batch(frames: Sequence[np.ndarray], particle_file_prefix: str, beam_
                                       root_path=root_path, planes=planes, orders=orders, particles=particles, thr_polys=thr_polys,
                                       device=None, return_src=return_src, slot=slot, calib=calib, pre_crop=pre_crop, q8=q8,
                                       plane_method=plane_method, plane_seed=plane_seed, plane_trials=plane_trials, **device_kw)
+    if device_kw.get('layout', 'compact') != 'compact' or device_kw.get('in_place'):
+        raise ValueError("layout='aligned' / in_place=True are a result layout of the torch-tensor boundary: the rows stay on the device "
+                         "in the input's order; host arrays get the reference's compacted return value")
     if device_kw:
         raise TypeError(f"{sorted(device_kw)}: arguments of the torch-tensor boundary only")
     eng = _engine.get_engine(device, slot)
