@@ -320,6 +320,33 @@ __global__ __launch_bounds__(PB) void k_lean_gather(PreArgs a)
     __shared__ int wc[4][4];
     const int tid = threadIdx.x, wv = tid >> 6;
     const unsigned long long lt = (1ull << (tid & 63)) - 1ull;
+    if (a.frame_unsorted && a.frame_unsorted[f]) {
+        // The reference sorts the frame by channel before it estimates (simulation.py:447), and NumPy's float32 sum depends on the order of
+        // its terms: a frame that came unsorted is gathered from the sort's sorted copy, in that order.  The tile prefixes count the tiles
+        // of the arrival order, so the frame's first block walks the whole sorted frame instead, 256 rows a trip (only frames whose noise
+        // line fell back come here).
+        if (blockIdx.x != 0) return;
+        const T *srows = (const T *)a.srows;
+        int run = 0;
+        for (int64_t r0 = 0; r0 < n; r0 += PB) {
+            const int64_t r = r0 + tid;
+            double gd = 0.0, gn, gc;
+            bool gr = false;
+            if (r < n) {
+                const T *p = srows + (base + r) * 5;
+                gr = lean_row<T>(a.delta, w0, w1, w2, h, wn, p[0], p[1], p[2], p[3], gd, gn, gc) && gn == gn;
+            }
+            const unsigned long long m = __ballot(gr);
+            if ((tid & 63) == 0) wc[0][wv] = __popcll(m);
+            __syncthreads();
+            int off = run;
+            for (int ww = 0; ww < wv; ++ww) off += wc[0][ww];
+            if (gr) a.cdist[base + off + __popcll(m & lt)] = (float)gd;
+            run += wc[0][0] + wc[0][1] + wc[0][2] + wc[0][3];
+            __syncthreads();
+        }
+        return;
+    }
     bool g[4];
     int pre[4];
     double gdv[4];
