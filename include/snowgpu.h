@@ -33,7 +33,9 @@
  *               row, the index of the input row it came from (frame-local)
  *   aligned   : snowgpu_augment_batch_device_aligned returns the same rows in the INPUT's order instead -- every input row
  *               at its own index, one keep flag per row (1: the reference returns the row) --, a result whose shape does not
- *               depend on the data and which a consumer on the same stream (or in the same HIP graph) reads without the host
+ *               depend on the data and which a consumer on the same stream (or in the same HIP graph) reads without the host;
+ *               snowgpu_wet_ground_batch_device_aligned / snowgpu_augment_wet_batch_device_aligned do the same for the wet-ground
+ *               model and for the snowfall + wet-ground chain
  */
 #ifndef SNOWGPU_H
 #define SNOWGPU_H
@@ -271,7 +273,8 @@ int snowgpu_augment_batch_device(snowgpu_ctx *ctx, int n_frames, int64_t n_total
  * Same contract otherwise: asynchronous on `stream`, no allocation after the first call of a size, capturable into a HIP graph; on a
  * non-zero status the rows are unspecified.  The last step is one kernel instead of the compaction's three.  A context with a threshold
  * callback (snowgpu_set_threshold_callback) or the packed result transfer (snowgpu_set_result_transfer) set answers SNOWGPU_E_INVALID:
- * both finish batches through the compaction.  The host-pointer entries and the fused wet-ground entry have no aligned form.
+ * both finish batches through the compaction.  The host-pointer entries have no aligned form; the wet-ground model and the fused
+ * snowfall + wet-ground chain have one of their own (snowgpu_wet_ground_batch_device_aligned, snowgpu_augment_wet_batch_device_aligned).
  */
 int snowgpu_augment_batch_device_aligned(snowgpu_ctx *ctx, int n_frames, int64_t n_total,
                                          int64_t max_frame_rows, const int64_t *d_frame_offsets, const void *d_rows, int dtype,
@@ -466,6 +469,67 @@ int snowgpu_augment_wet_batch_device(snowgpu_ctx *ctx, int n_frames, int64_t n_t
                                      double wet_noise_floor, double power_factor, int flat_earth, double delta, int replace,
                                      double *d_out_rows, int32_t *d_out_src, int64_t *d_out_counts, int64_t *d_out_stats,
                                      int32_t *d_out_flags, int32_t *d_status, void *stream);
+
+/*
+ * ground_water_augmentation() with the ALIGNED result, every array in DEVICE memory: the wet-ground model never moves a point -- a
+ * non-ground row is copied, a ground row gets a new intensity and label 1 or is dropped (augmentation.py:145-159) -- so the result can
+ * keep the input's size and order, as snowgpu_augment_batch_device_aligned's does, and the two chain: d_keep_in takes that entry's
+ * d_out_keep.
+ *   d_keep_in   n_total bytes or NULL (every row present): 0 = the row is not there.  The estimator skips it -- ground rows, sums,
+ *               histogram and the 1000-row rule (augmentation.py:51-52) see the present rows only -- and it comes back as it came.
+ *   d_plane     n_frames x 4, or NULL: calculate_plane (augmentation.py:41) by the plane method `reference`, which reads no row.  With
+ *               `lsq` or `ransac` set a NULL plane is SNOWGPU_E_INVALID: both crop the rows into a list, and under a mask that list --
+ *               and with it the RANSAC draws -- has another order.
+ *   d_out_rows  n_total x 5 rows in the INPUT's dtype; may be d_rows itself.  For a processed frame (d_out_flags[f] = 0) and input row i:
+ *                 keep-in 0            columns 0 - 4 as they came                                                               keep 0
+ *                 present, not ground  columns 0 - 3 unchanged, column 4 = 0 under `replace` (:155-156), else unchanged         keep 1
+ *                 ground, kept (:146)  columns 0 - 2 unchanged, the new intensity (:153), column 4 = 1 (:159)                   keep 1
+ *                 ground, dropped      columns 0 - 2 unchanged, the value new_intensities held after :131 (0 whenever it was
+ *                                      below the limit), column 4 = 1                                                           keep 0
+ *               A frame with fewer than 1000 present ground rows (d_out_flags[f] = 1) keeps rows and keep bytes exactly as they came.
+ *               Every byte is a function of the input.  Out of place every row is stored whole; in place only columns 3 and 4 of the
+ *               rows that change, and the keep bytes that change.
+ *               THE ONE PLACE the aligned form departs from the reference's dtype: the compact entries return float64 rows whatever came
+ *               in (augmentation.py:150); here a float32 row stays float32 and its new intensity is the float64 result rounded once to
+ *               float32 -- a result written in place cannot be wider than its input, and the consumer this layout is for trains in float32.
+ *   d_out_keep  n_total bytes; may be d_keep_in itself.  Any overlap of d_out_rows with d_rows, or of d_out_keep with d_keep_in, other
+ *               than identity is SNOWGPU_E_INVALID.
+ *   d_out_counts / d_out_flags   per frame: keep bytes set / 1 where the frame came back as it was.
+ *   d_status    device int32[8], cleared by the call; [0] = SNOWGPU_E_GROUND under 'poly' as snowgpu_wet_ground_batch reports it.
+ * Honours snowgpu_set_wet_estimation, snowgpu_set_wet_lines (one use; the call then waits for their upload) and leaves its curves for
+ * snowgpu_wet_last_fit.  The contract is the device entries': asynchronous on `stream`, no allocation after the first call of a size,
+ * capturable into a HIP graph.  A context with a threshold callback or the packed result transfer set answers SNOWGPU_E_INVALID, as for
+ * snowgpu_augment_batch_device_aligned.  The sums of the estimate run over the tiles of the frames as they are passed; the compact fused
+ * entry sums over the tiles of the COMPACTED snowfall rows, so the fitted power line of the two chains differs in its last bits.
+ */
+int snowgpu_wet_ground_batch_device_aligned(snowgpu_ctx *ctx, int n_frames, int64_t n_total, int64_t max_frame_rows,
+                                            const int64_t *d_frame_offsets, const void *d_rows, int dtype,
+                                            const uint8_t *d_keep_in /* NULL: all rows present */,
+                                            const double *d_plane /* n_frames x 4, or NULL */, double water_height,
+                                            double pavement_depth, double noise_floor, double power_factor, int flat_earth,
+                                            double delta, int replace, void *d_out_rows /* may be d_rows itself */,
+                                            uint8_t *d_out_keep /* may be d_keep_in itself */, int64_t *d_out_counts,
+                                            int32_t *d_out_flags, int32_t *d_status, void *stream);
+
+/*
+ * snowgpu_augment_batch_device_aligned followed by snowgpu_wet_ground_batch_device_aligned IN PLACE on its d_out_rows / d_out_keep, as one
+ * launch sequence on `stream`: the chain of snowgpu_augment_wet_batch_device without its five compaction passes (count, scan, scatter of
+ * the snowfall stage; scan and scatter of the wet stage) and without the snowfall stage's row scratch.  Arguments: those of
+ * snowgpu_augment_batch_device_aligned, then the wet arguments of snowgpu_augment_wet_batch_device, then d_out_flags.
+ *   d_out_rows / d_out_keep   the chain's result, rows in the input's dtype (see above); d_out_rows may be d_rows itself
+ *   d_out_stats               the snowfall statistics;   d_out_counts / d_out_flags   the wet stage's
+ *   d_wet_plane               n_frames x 4, or NULL under the plane method `reference` (SNOWGPU_E_INVALID under `lsq` / `ransac`)
+ * A frame whose wet stage finds fewer than 1000 present ground rows comes back as the aligned snowfall result with d_out_flags[f] = 1.
+ */
+int snowgpu_augment_wet_batch_device_aligned(snowgpu_ctx *ctx, int n_frames, int64_t n_total, int64_t max_frame_rows,
+                                             const int64_t *d_frame_offsets, const void *d_rows, int dtype,
+                                             const int32_t *d_table_ids, double beam_divergence_deg, const double *d_thr_poly,
+                                             const double *d_plane, double noise_floor, const int32_t *d_perm,
+                                             void *d_out_rows /* n_total x 5, may be d_rows itself */, uint8_t *d_out_keep /* n_total */,
+                                             int64_t *d_out_counts, int64_t *d_out_stats, double *d_out_thr_poly, int32_t *d_status,
+                                             void *stream, const double *d_wet_plane, double water_height, double pavement_depth,
+                                             double wet_noise_floor, double power_factor, int flat_earth, double delta, int replace,
+                                             int32_t *d_out_flags);
 
 #ifdef __cplusplus
 }

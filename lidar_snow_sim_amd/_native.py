@@ -27,7 +27,7 @@ EXPORTS = [
     "snowgpu_augment_wet_batch_device", "snowgpu_last_status", "snowgpu_free_table", "snowgpu_debug_table", "snowgpu_file_table_device", "snowgpu_set_fov_precrop",
     "snowgpu_set_pipeline", "snowgpu_set_wet_lines", "snowgpu_set_plane_method", "snowgpu_estimate_planes",
     "snowgpu_estimate_planes_device", "snowgpu_prepass_stats", "snowgpu_set_wet_estimation", "snowgpu_wet_last_fit", "snowgpu_debug_ransac_polyfit", "snowgpu_set_result_transfer", "snowgpu_debug_transfer_times", "snowgpu_status_error", "snowgpu_set_threshold_callback", "snowgpu_augment_batch_compact", "snowgpu_set_serial", "snowgpu_lane_stream", "snowgpu_device_numa_node",
-    "snowgpu_augment_batch_device_aligned",
+    "snowgpu_augment_batch_device_aligned", "snowgpu_wet_ground_batch_device_aligned", "snowgpu_augment_wet_batch_device_aligned",
 ]
 
 WET_ESTIMATION = {"linear": 0, "poly": 1}
@@ -96,6 +96,12 @@ def lib():
             L.snowgpu_augment_wet_batch_device.argtypes = [vp, ctypes.c_int, i64, i64, vp, vp, ctypes.c_int, vp, dbl, vp, vp, dbl, vp,
                                                            vp, dbl, dbl, dbl, dbl, ctypes.c_int, dbl, ctypes.c_int, vp, vp, vp, vp, vp,
                                                            vp, vp]
+            L.snowgpu_wet_ground_batch_device_aligned.restype = ctypes.c_int
+            L.snowgpu_wet_ground_batch_device_aligned.argtypes = [vp, ctypes.c_int, i64, i64, vp, vp, ctypes.c_int, vp, vp, dbl, dbl, dbl, dbl,
+                                                                  ctypes.c_int, dbl, ctypes.c_int, vp, vp, vp, vp, vp, vp]
+            L.snowgpu_augment_wet_batch_device_aligned.restype = ctypes.c_int
+            L.snowgpu_augment_wet_batch_device_aligned.argtypes = L.snowgpu_augment_batch_device_aligned.argtypes + [
+                vp, dbl, dbl, dbl, dbl, ctypes.c_int, dbl, ctypes.c_int, vp]
             L.snowgpu_set_fov_precrop.restype = ctypes.c_int
             L.snowgpu_set_fov_precrop.argtypes = [vp, ctypes.c_int]
             L.snowgpu_last_status.restype = ctypes.c_int
@@ -364,6 +370,35 @@ class Context:
             vp(d_out_counts), vp(d_out_stats), vp(d_out_flags), vp(d_status), vp(stream or None))
         self._check(rc)
 
+    def wet_ground_batch_device_aligned(self, n_frames, n_total, max_frame_rows, d_frame_off, d_rows, dtype_code, d_keep_in, d_plane,
+                                        water_height, pavement_depth, noise_floor, power_factor, flat_earth, delta, replace, d_out_rows,
+                                        d_out_keep, d_out_counts, d_out_flags, d_status, stream=0):
+        """Raw device-pointer entry of the wet-ground model with the aligned result (rows of the input's dtype in input order + one keep
+        byte per row; d_keep_in 0 = every row present; d_out_rows may be d_rows, d_out_keep d_keep_in); asynchronous on `stream`."""
+        vp = ctypes.c_void_p
+        rc = self._L.snowgpu_wet_ground_batch_device_aligned(
+            self._h, int(n_frames), int(n_total), int(max_frame_rows), vp(d_frame_off), vp(d_rows or None), int(dtype_code),
+            vp(d_keep_in or None), vp(d_plane or None), float(water_height), float(pavement_depth), float(noise_floor), float(power_factor),
+            int(bool(flat_earth)), float(delta), int(bool(replace)), vp(d_out_rows or None), vp(d_out_keep or None), vp(d_out_counts or None),
+            vp(d_out_flags or None), vp(d_status or None), vp(stream or None))
+        self._check(rc)
+
+    def augment_wet_batch_device_aligned(self, n_frames, n_total, max_frame_rows, d_frame_off, d_rows, dtype_code, d_table_ids,
+                                         beam_divergence, d_thr_poly, d_plane, noise_floor, d_perm, d_out_rows, d_out_keep, d_out_counts,
+                                         d_out_stats, d_out_thr, d_status, stream, d_wet_plane, water_height, pavement_depth,
+                                         wet_noise_floor, power_factor, flat_earth, delta, replace, d_out_flags):
+        """Raw device-pointer entry of the fused snowfall + wet-ground chain with the aligned result: augment_batch_device_aligned's
+        arguments, then the wet ones, then d_out_flags; asynchronous on `stream`."""
+        vp = ctypes.c_void_p
+        rc = self._L.snowgpu_augment_wet_batch_device_aligned(
+            self._h, int(n_frames), int(n_total), int(max_frame_rows), vp(d_frame_off), vp(d_rows or None), int(dtype_code),
+            vp(d_table_ids), float(beam_divergence), vp(d_thr_poly or None), vp(d_plane or None), float(noise_floor),
+            vp(d_perm or None), vp(d_out_rows or None), vp(d_out_keep or None), vp(d_out_counts or None), vp(d_out_stats or None),
+            vp(d_out_thr or None), vp(d_status or None), vp(stream or None), vp(d_wet_plane or None), float(water_height),
+            float(pavement_depth), float(wet_noise_floor), float(power_factor), int(bool(flat_earth)), float(delta), int(bool(replace)),
+            vp(d_out_flags or None))
+        self._check(rc)
+
     def set_fov(self, calib=None, img_shape=(1024, 1920), pre_crop=False):
         """Camera-FOV crop inside the compaction of every later batch (None switches it off).  `calib` carries V2C (3 x 4),
         R0 (3 x 3) and P2 (3 x 4), as lidar_snow_sim_amd.calibration.Calibration does.  pre_crop: also crop the input frames
@@ -568,6 +603,16 @@ class Context:
             raise ValueError("estimation_method must be 'linear' or 'poly'")
         with self._call_lock:
             self._check(self._L.snowgpu_set_wet_estimation(self._h, WET_ESTIMATION[method], int(seed) & 0xFFFFFFFFFFFFFFFF))
+
+    def set_wet_lines(self, lines=None):
+        """The two fitted lines (n_frames x 4: p slope, p intercept, noise-line slope, intercept) for the NEXT wet-ground call of this
+        context, fitted by the caller (quirk Q8); one use, None clears."""
+        with self._call_lock:
+            if lines is None:
+                self._check(self._L.snowgpu_set_wet_lines(self._h, 0, None))
+            else:
+                ln = np.ascontiguousarray(lines, np.float64).reshape(-1, 4)
+                self._check(self._L.snowgpu_set_wet_lines(self._h, ln.shape[0], _p(ln)))
 
     def debug_ransac_polyfit(self, x, y, seed=0, frame=0):
         """The device's ransac_polyfit(x, y, order=2) with the draws of (seed; frame): (coefficients[3], trial kept or -1)."""

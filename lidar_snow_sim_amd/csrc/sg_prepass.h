@@ -1,6 +1,6 @@
 // sg_prepass.h -- device noise-threshold prepass (simulation.py:449-467; wet_ground/augmentation.py:195-266)
 // and the wet-ground model (wet_ground/augmentation.py:25-161).  Implemented in snowgpu_prepass.hip (the snowfall path's
-// prepass, the scratch pool) and snowgpu_wet.hip (sg_wet_run, sg_launch_compose_src, sg_debug_ransac_quad).
+// prepass, the scratch pool) and snowgpu_wet.hip (sg_wet_run, sg_wet_run_aligned, sg_launch_compose_src, sg_debug_ransac_quad).
 #pragma once
 #include <stdint.h>
 
@@ -41,6 +41,12 @@ double *sg_prepass_reserve_tiles(SgPrepassScratch *s, int n_frames, int64_t max_
 int sg_wet_run(SgPrepassScratch *s, const void *rows, int dtype, const int64_t *frame_off,
                const int64_t *frame_cnt, int n_frames, int64_t n_total, int64_t max_frame, const double *plane, const SgWetParams *wp, double *out_rows, int32_t *out_src,
                int64_t *out_counts, int32_t *out_flags, int32_t *status, void *stream);
+// sg_wet_run with the aligned result: out_rows (the input's dtype; may be `rows`) holds the output row of every input row at its own index,
+// out_keep (may be keep_in) one byte per row: 1 = the reference returns the row.  keep_in: optional, 0 = the row is not there (an earlier
+// stage removed it): the estimator skips it and it comes back as it came.  Same estimate (wp: lines, estimation, seed, fit_out) as sg_wet_run.
+int sg_wet_run_aligned(SgPrepassScratch *s, const void *rows, int dtype, const int64_t *frame_off, const uint8_t *keep_in,
+                       int n_frames, int64_t n_total, int64_t max_frame, const double *plane, const SgWetParams *wp, void *out_rows,
+                       uint8_t *out_keep, int64_t *out_counts, int32_t *out_flags, int32_t *status, void *stream);
 // out[off[f] + i] = first[off[f] + second[off[f] + i]] for i < counts[f] (device arrays)
 int sg_launch_compose_src(const int64_t *frame_off, const int64_t *counts, int n_frames, int64_t max_frame,
                           const int32_t *second, const int32_t *first, int32_t *out, void *stream);

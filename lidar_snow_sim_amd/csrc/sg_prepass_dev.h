@@ -64,6 +64,8 @@ struct PreArgs {
     float *cdist;          // ground ranges compacted in row order (float32 rows only)
     PreFrame *fr;
     int32_t *status;
+    const uint8_t *keep;   // optional (aligned wet stage), indexed like the rows: 0 = the row is not there (an earlier stage removed it) and
+                           // k_pre_ground<T, true> takes it for a non-ground row; NULL: every row is present
 };
 
 __device__ __forceinline__ int64_t pre_rows(const PreArgs &a, int f)

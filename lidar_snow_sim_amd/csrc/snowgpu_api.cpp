@@ -692,6 +692,137 @@ extern "C" int snowgpu_augment_wet_batch_device(snowgpu_ctx *ctx, int n_frames, 
     return SNOWGPU_OK;
 }
 
+// ---- the wet-ground model with the ALIGNED result ------------------------------------------------------------------------------------
+// What the two aligned entries refuse alike (as snowgpu_augment_batch_device_aligned does): a context that finishes batches through the
+// compaction, and outputs that overlap their inputs without being them.
+static int aligned_wet_refusals(snowgpu_ctx *ctx, const char *who, int64_t n_total, int dtype, const void *rows, const void *out_rows,
+                                const uint8_t *keep_in, const uint8_t *out_keep)
+{
+    const std::string name(who);
+    if (ctx->thr_fn) return fail(ctx, SNOWGPU_E_INVALID, name + ": a threshold callback is set; it finishes batches through the compaction only");
+    if (ctx->result_mode != 0) return fail(ctx, SNOWGPU_E_INVALID, name + ": the packed result transfer is set; it is a form of the compacted result");
+    const size_t bytes = (size_t)n_total * 5 * (dtype == 0 ? 4 : 8);
+    const char *a = (const char *)rows, *o = (const char *)out_rows;
+    if (a && o != a && o < a + bytes && a < o + bytes)
+        return fail(ctx, SNOWGPU_E_INVALID, name + ": d_out_rows overlaps d_rows; pass d_rows itself (in place) or a buffer apart from it");
+    const uint8_t *k = keep_in, *ok = out_keep;
+    if (k && ok != k && ok < k + (size_t)n_total && k < ok + (size_t)n_total)
+        return fail(ctx, SNOWGPU_E_INVALID, name + ": d_out_keep overlaps d_keep_in; pass d_keep_in itself or a buffer apart from it");
+    return SNOWGPU_OK;
+}
+
+// The wet stage of both aligned entries, on `st`: the plane (the caller's, or the constant one of the plane method `reference`), the
+// context's wet settings (estimation method and seed, the caller's lines, the fit's export) and sg_wet_run_aligned.
+static int aligned_wet_stage(snowgpu_ctx *ctx, const char *who, int n_frames, int64_t n_total, int64_t max_frame, const int64_t *d_frame_offsets,
+                             const void *d_rows, int dtype, const uint8_t *d_keep_in, const double *d_plane, double water_height,
+                             double pavement_depth, double noise_floor, double power_factor, int flat_earth, double delta, int replace,
+                             void *d_out_rows, uint8_t *d_out_keep, int64_t *d_out_counts, int32_t *d_out_flags, int32_t *d_status, hipStream_t st)
+{
+    const std::string name(who);
+    SgWetParams wp{};
+    wp.water_height = water_height; wp.pavement_depth = pavement_depth; wp.noise_floor = noise_floor;
+    wp.power_factor = power_factor; wp.flat_earth = flat_earth; wp.delta = delta; wp.replace = replace;
+    wp.estimation = ctx->wet_estimation; wp.seed = ctx->wet_seed;
+    ENSURE(ctx, ctx->wet_fit, (size_t)n_frames * 8);
+    wp.fit_out = ctx->wet_fit.p; ctx->wet_fit_frames = n_frames;
+    if (!ctx->wet_lines.empty() && ctx->wet_estimation != 0) { ctx->wet_lines.clear(); return fail(ctx, SNOWGPU_E_INVALID, "snowgpu_set_wet_lines supplies LINES: not with estimation method 'poly'"); }
+    if (!ctx->wet_lines.empty()) {                      // the caller's lines (one use; the upload is waited for: they leave the context here)
+        if (ctx->wet_lines.size() != (size_t)n_frames * 4) { ctx->wet_lines.clear(); return fail(ctx, SNOWGPU_E_INVALID, "snowgpu_set_wet_lines was given another number of frames"); }
+        ENSURE(ctx, ctx->d_wet_lines, ctx->wet_lines.size());
+        HIPCHK(ctx, hipMemcpyAsync(ctx->d_wet_lines.p, ctx->wet_lines.data(), sizeof(double) * ctx->wet_lines.size(), hipMemcpyHostToDevice, st));
+        HIPCHK(ctx, hipStreamSynchronize(st));
+        wp.lines = ctx->d_wet_lines.p;
+        ctx->wet_lines.clear();
+    }
+    int e = 0;
+    if (!d_plane) {
+        // calculate_plane (augmentation.py:41) on the device: the method `reference` returns a constant and reads no row.  The two estimators
+        // crop the cloud into a list first; under a mask that list -- and with it the RANSAC draws -- has another order: a change of its own.
+        if (ctx->plane_par.method != SG_PLANE_REFERENCE)
+            return fail(ctx, SNOWGPU_E_INVALID, name + ": a NULL wet plane needs the plane method 'reference'; 'lsq' and 'ransac' crop the rows and have no masked form: pass the plane");
+        ENSURE(ctx, ctx->wet_plane_est, (size_t)n_frames * 4);
+        e = sg_plane_run(&ctx->plane_scr, &ctx->plane_par, d_rows, dtype, d_frame_offsets, nullptr, n_frames, n_total, max_frame, ctx->wet_plane_est.p, nullptr, st);
+        if (e) return fail(ctx, SNOWGPU_E_HIP, std::string("plane estimate: ") + (e > 0 ? hipGetErrorString((hipError_t)e) : "allocation"));
+        d_plane = ctx->wet_plane_est.p;
+    }
+    e = sg_wet_run_aligned(&ctx->prepass, d_rows, dtype, d_frame_offsets, d_keep_in, n_frames, n_total, max_frame, d_plane, &wp, d_out_rows,
+                           d_out_keep, d_out_counts, d_out_flags, d_status, st);
+    if (e) return fail(ctx, SNOWGPU_E_HIP, std::string("wet ground: ") + (e > 0 ? hipGetErrorString((hipError_t)e) : "allocation"));
+    return SNOWGPU_OK;
+}
+
+// a batch without rows: nothing kept, every frame "returned as it came" (what an empty frame inside a batch reports)
+static int aligned_wet_empty(snowgpu_ctx *ctx, int n_frames, int64_t *d_out_counts, int32_t *d_out_flags, hipStream_t st)
+{
+    HIPCHK(ctx, hipMemsetAsync(d_out_counts, 0, sizeof(int64_t) * (size_t)n_frames, st));
+    HIPCHK(ctx, hipMemsetD32Async((hipDeviceptr_t)d_out_flags, 1, (size_t)n_frames, st));
+    return SNOWGPU_OK;
+}
+
+// ground_water_augmentation() on frames in DEVICE memory with the aligned result: the first device-pointer entry of the wet model on its
+// own, and the second half of the fused aligned entry below.
+extern "C" int snowgpu_wet_ground_batch_device_aligned(snowgpu_ctx *ctx, int n_frames, int64_t n_total, int64_t max_frame_rows,
+                                                       const int64_t *d_frame_offsets, const void *d_rows, int dtype, const uint8_t *d_keep_in,
+                                                       const double *d_plane, double water_height, double pavement_depth, double noise_floor,
+                                                       double power_factor, int flat_earth, double delta, int replace, void *d_out_rows,
+                                                       uint8_t *d_out_keep, int64_t *d_out_counts, int32_t *d_out_flags, int32_t *d_status,
+                                                       void *stream)
+{
+    static const char *who = "snowgpu_wet_ground_batch_device_aligned";
+    if (!ctx) return SNOWGPU_E_INVALID;
+    if (n_frames <= 0 || n_total < 0 || !d_frame_offsets || (n_total > 0 && (!d_rows || !d_out_rows || !d_out_keep)) || !d_out_counts ||
+        !d_out_flags || !d_status || (dtype != 0 && dtype != 1))
+        return fail(ctx, SNOWGPU_E_INVALID, std::string(who) + ": null pointer or bad dtype");
+    if (n_total >= ((int64_t)1 << 31)) return fail(ctx, SNOWGPU_E_INVALID, "batch too large: split it below 2^31 rows");
+    if (int rc = aligned_wet_refusals(ctx, who, n_total, dtype, d_rows, d_out_rows, d_keep_in, d_out_keep)) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+    HIPCHK(ctx, hipMemsetAsync(d_status, 0, sizeof(int32_t) * 8, st));
+    if (n_total == 0) return aligned_wet_empty(ctx, n_frames, d_out_counts, d_out_flags, st);
+    const int64_t max_frame = (max_frame_rows > 0 && max_frame_rows <= n_total) ? max_frame_rows : n_total;
+    return aligned_wet_stage(ctx, who, n_frames, n_total, max_frame, d_frame_offsets, d_rows, dtype, d_keep_in, d_plane, water_height, pavement_depth,
+                             noise_floor, power_factor, flat_earth, delta, replace, d_out_rows, d_out_keep, d_out_counts, d_out_flags, d_status, st);
+}
+
+// augment() followed by ground_water_augmentation() (pointcloud_viewer.py:2807-2821) with the aligned result, as ONE launch sequence on the
+// caller's stream: run_batch with the aligned finish into d_out_rows / d_out_keep, then the wet stage IN PLACE on those two arrays.  No
+// compaction, no snow_rows / snow_src / snow_counts scratch, no source indices to compose.
+extern "C" int snowgpu_augment_wet_batch_device_aligned(snowgpu_ctx *ctx, int n_frames, int64_t n_total, int64_t max_frame_rows,
+                                                        const int64_t *d_frame_offsets, const void *d_rows, int dtype,
+                                                        const int32_t *d_table_ids, double beam_divergence_deg, const double *d_thr_poly,
+                                                        const double *d_plane, double noise_floor, const int32_t *d_perm, void *d_out_rows,
+                                                        uint8_t *d_out_keep, int64_t *d_out_counts, int64_t *d_out_stats, double *d_out_thr_poly,
+                                                        int32_t *d_status, void *stream, const double *d_wet_plane, double water_height,
+                                                        double pavement_depth, double wet_noise_floor, double power_factor, int flat_earth,
+                                                        double delta, int replace, int32_t *d_out_flags)
+{
+    static const char *who = "snowgpu_augment_wet_batch_device_aligned";
+    if (!ctx) return SNOWGPU_E_INVALID;
+    if (n_frames <= 0 || n_total < 0 || !d_frame_offsets || (n_total > 0 && !d_rows) || !d_table_ids || !d_out_rows ||
+        !d_out_keep || !d_out_counts || !d_out_stats || !d_out_flags || !d_status || (dtype != 0 && dtype != 1))
+        return fail(ctx, SNOWGPU_E_INVALID, std::string(who) + ": null pointer or bad dtype");
+    if (n_total >= ((int64_t)1 << 31)) return fail(ctx, SNOWGPU_E_INVALID, "batch too large: split it below 2^31 rows");
+    if (int rc = aligned_wet_refusals(ctx, who, n_total, dtype, d_rows, d_out_rows, nullptr, d_out_keep)) return rc;
+    if (!d_wet_plane && ctx->plane_par.method != SG_PLANE_REFERENCE)             // (before anything is launched)
+        return fail(ctx, SNOWGPU_E_INVALID, std::string(who) + ": a NULL wet plane needs the plane method 'reference'; 'lsq' and 'ransac' crop the rows and have no masked form: pass the plane");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    BatchDev b{};
+    b.n_frames = n_frames; b.n_total = n_total; b.max_frame = (max_frame_rows > 0 && max_frame_rows <= n_total) ? max_frame_rows : n_total;
+    b.frame_off = d_frame_offsets;
+    b.uniform_rows = (max_frame_rows > 0 && max_frame_rows * (int64_t)n_frames == n_total) ? max_frame_rows : 0; b.rows = d_rows;
+    b.dtype = dtype; b.table_ids = d_table_ids; b.beam_div_deg = beam_divergence_deg; b.thr_poly = d_thr_poly;
+    b.plane = d_plane; b.noise_floor = noise_floor; b.perm = d_perm; b.out_rows = d_out_rows; b.out_src = nullptr; b.out_keep = d_out_keep;
+    b.out_counts = d_out_counts; b.out_stats = d_out_stats; b.out_thr_poly = d_out_thr_poly; b.status = d_status;
+    b.stream = stream ? (hipStream_t)stream : ctx->stream;
+    int rc = run_batch(ctx, b);
+    if (rc) return rc;
+    if (n_total == 0) return aligned_wet_empty(ctx, n_frames, d_out_counts, d_out_flags, b.stream);
+    // (d_out_counts: the snowfall stage's counts are overwritten by the wet stage's, which count what is left of them)
+    return aligned_wet_stage(ctx, who, n_frames, n_total, b.max_frame, d_frame_offsets, d_out_rows, dtype, d_out_keep, d_wet_plane, water_height,
+                             pavement_depth, wet_noise_floor, power_factor, flat_earth, delta, replace, d_out_rows, d_out_keep, d_out_counts,
+                             d_out_flags, d_status, b.stream);
+}
+
 // Camera-FOV crop of augment(only_camera_fov=True) (simulation.py:39-47, :532-540): lidar_to_rect with
 // Tr_velo_to_cam (3 x 4) and R0_rect (3 x 3), rect_to_img with P2 (3 x 4), image img_h x img_w ((1024, 1920) in the
 // reference).  The crop is applied by the compaction of every later batch of this context (and num_removed counts it,

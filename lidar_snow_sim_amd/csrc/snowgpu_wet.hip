@@ -6,7 +6,8 @@
 // The estimate: ground rows by plane distance, incident angle, I / cos(angle) against range, a least-squares line, a 50 x 2555
 // (range x normalised intensity) histogram whose per-range-row sparsest occupied bin gives the noise line -- or the two quadratics of
 // 'poly'.  estimate() keeps range, angle and I / cos of every ground row in float64 scratch arrays, because the per-row rewrite
-// (k_wet_apply) needs them again.  Only sg_wet_run runs it; the snowfall path's noise threshold comes from the lean chain of
+// (k_wet_apply, k_wet_apply_aligned) needs them again.  Only sg_wet_run and sg_wet_run_aligned run it -- the second with the keep bytes
+// of an earlier stage as a mask over the rows (k_pre_ground<T, true>) --; the snowfall path's noise threshold comes from the lean chain of
 // snowgpu_prepass.hip, which keeps no per-row scratch.  The two kernels both chains run (k_pre_rowmin, k_pre_mean32) and the scratch
 // pool are that file's and are reached through sg_prepass_dev.h.  Reductions run in a fixed order, as there.
 #include <hip/hip_runtime.h>
@@ -21,7 +22,9 @@
 #include "sg_launch.h"
 
 // ---- P1: ground rows, incident angle, normalised intensity; tile partials (count, sum x, sum y, max y) ------
-template <typename T>
+// MASKED (the aligned wet stage: a.keep, one byte per row): a row whose byte is 0 is not there -- it is taken for a non-ground row, gets
+// g_norm = NaN and adds nothing to the tile's count, sums or maximum; everything downstream keys off g_norm != g_norm.
+template <typename T, bool MASKED>
 __global__ __launch_bounds__(PB) void k_pre_ground(PreArgs a)
 {
     const int f = blockIdx.y;
@@ -35,10 +38,12 @@ __global__ __launch_bounds__(PB) void k_pre_ground(PreArgs a)
     double v[3] = {0.0, 0.0, 0.0};
     double ymax = -INFINITY;
     T rx[4], ry[4], rz[4], ri[4];                // all loads of the tile in flight before the first use
+    uint8_t present[4] = {1, 1, 1, 1};
     for (int q = 0; q < 4; ++q) {
         const int64_t r = tile0 + q * PB + threadIdx.x;
         const T *p = rows + (base + (r < n ? r : 0)) * 5;
         rx[q] = p[0]; ry[q] = p[1]; rz[q] = p[2]; ri[q] = p[3];
+        if (MASKED) present[q] = a.keep[base + (r < n ? r : 0)];
     }
     for (int q = 0; q < 4; ++q) {
         const int64_t r = tile0 + q * PB + threadIdx.x;
@@ -47,7 +52,7 @@ __global__ __launch_bounds__(PB) void k_pre_ground(PreArgs a)
         const double dot = ((double)x * w0 + (double)y * w1) + (double)z * w2;   // np.matmul(pc[:, :3], w)
         const double hog = dot + h;
         double gn = NAN, gd = 0.0, ga = 0.0;
-        if (hog < a.delta && hog > -a.delta) {                           // simulation.py:450-451 / augmentation.py:46-47
+        if (hog < a.delta && hog > -a.delta && (!MASKED || present[q])) {   // simulation.py:450-451 / augmentation.py:46-47
             double nrm;
             if (sizeof(T) == 4 && !a.rows_as_f64) nrm = (double)sqrtf((float)((x * x + y * y) + z * z));   // float32 norm (simulation.py:455)
             else { const double xd = (double)x, yd = (double)y, zd = (double)z; nrm = sqrt((xd * xd + yd * yd) + zd * zd); }
@@ -546,6 +551,41 @@ struct WetArgs {
     const int32_t *src_first;   // SgWetParams::src_first
 };
 
+// The per-row chain of a ground row (augmentation.py:90-131, :146) from its range, incidence angle and intensity and the frame's fitted curves:
+// ni = what new_intensities holds after :131 (0 below the noise limit); returns whether the row is kept (:146).  Written down once for
+// k_wet_apply (compact result) and k_wet_apply_aligned (aligned result).
+__device__ __forceinline__ bool wet_row_chain(const PreArgs &a, const PreFrame &fr, double water_height, double pavement_depth, double gd,
+                                              double ang, double inten, double &ni)
+{
+    double gs, gc;
+    sg_sincos_0_2pi(ang, gs, gc);                                // the incidence angle lies in [0, pi] (an arccos)
+    double rel, thr;
+    if (fr.quad) {                                               // estimation_method = 'poly'
+        const double gd2 = gd * gd;
+        rel = a.power_factor * ((fr.pq[0] * gd2 + fr.pq[1] * gd) + fr.pq[2]);        // :228-229
+        thr = a.noise_floor * ((fr.mq[0] * gd2 + fr.mq[1] * gd) + fr.mq[2]);         // :245-246
+    } else {
+        rel = a.power_factor * (fr.p0 * gd + fr.p1);             // :221
+        thr = a.noise_floor * (fr.pmin0 * gd + fr.pmin1);        // :252-253
+    }
+    const double refl = inten / gc / rel;                        // :90
+    double rho = refl < 0.05 ? 0.05 : (refl > 1 ? 1 : refl);     // :109 np.clip(reflectivities, 0.05, 1)
+    const Fresnel aw = fresnel_power(gs, gc, 1.0003, 1.33);      // phy_equations.py:81
+    const Fresnel wa = fresnel_power(aw.s_out, aw.c_out, 1.33, 1.0003);   // :83 (the angle inside the water)
+    const double ts = aw.ts * rho * wa.ts / (1 - rho * wa.rs);   // :86
+    const double tp = aw.tp * rho * wa.tp / (1 - rho * wa.rp);   // :89
+    const double t = fmax(tp, ts);                               // augmentation.py:119
+    double fw = water_height / pavement_depth;                   // :122
+    fw = fw < 0 ? 0 : (fw > 1 ? 1 : fw);
+    const double tw = (1 - fw) * refl + fw * t / ang;            // :123
+    double v = rel * gc * tw;                                    // :126
+    v = v < 0 ? 0 : (v > inten ? inten : v);                     // np.clip(., 0, intensity)
+    const double lim = thr * gc;
+    if (v < lim) v = 0;                                          // :128, :131
+    ni = v;
+    return v > lim;                                              // :146
+}
+
 template <typename T>
 __global__ __launch_bounds__(PB) void k_wet_apply(WetArgs w)
 {
@@ -577,37 +617,7 @@ __global__ __launch_bounds__(PB) void k_wet_apply(WetArgs w)
         const double gn = gns[q];
         if (fr.unchanged) { cls = 1; }                                   // frame returned as is (augmentation.py:51-52)
         else if (gn != gn) { cls = 1; }
-        else {
-            const double gd = gds[q], ang = angs[q];
-            double gs, gc;
-            sg_sincos_0_2pi(ang, gs, gc);                                // the incidence angle lies in [0, pi] (an arccos)
-            const double inten = ins[q];
-            double rel, thr;
-            if (fr.quad) {                                               // estimation_method = 'poly'
-                const double gd2 = gd * gd;
-                rel = a.power_factor * ((fr.pq[0] * gd2 + fr.pq[1] * gd) + fr.pq[2]);        // :228-229
-                thr = a.noise_floor * ((fr.mq[0] * gd2 + fr.mq[1] * gd) + fr.mq[2]);         // :245-246
-            } else {
-                rel = a.power_factor * (fr.p0 * gd + fr.p1);             // :221
-                thr = a.noise_floor * (fr.pmin0 * gd + fr.pmin1);        // :252-253
-            }
-            const double refl = inten / gc / rel;                        // :90
-            double rho = refl < 0.05 ? 0.05 : (refl > 1 ? 1 : refl);     // :109 np.clip(reflectivities, 0.05, 1)
-            const Fresnel aw = fresnel_power(gs, gc, 1.0003, 1.33);      // phy_equations.py:81
-            const Fresnel wa = fresnel_power(aw.s_out, aw.c_out, 1.33, 1.0003);   // :83 (the angle inside the water)
-            const double ts = aw.ts * rho * wa.ts / (1 - rho * wa.rs);   // :86
-            const double tp = aw.tp * rho * wa.tp / (1 - rho * wa.rp);   // :89
-            const double t = fmax(tp, ts);                               // augmentation.py:119
-            double fw = w.water_height / w.pavement_depth;               // :122
-            fw = fw < 0 ? 0 : (fw > 1 ? 1 : fw);
-            const double tw = (1 - fw) * refl + fw * t / ang;            // :123
-            double v = rel * gc * tw;                                    // :126
-            v = v < 0 ? 0 : (v > inten ? inten : v);                     // np.clip(., 0, intensity)
-            const double lim = thr * gc;
-            if (v < lim) v = 0;                                          // :128, :131
-            ni = v;
-            cls = (v > lim) ? 2 : 0;                                     // :146
-        }
+        else cls = wet_row_chain(a, fr, w.water_height, w.pavement_depth, gds[q], angs[q], ins[q], ni) ? 2 : 0;
         w.cls[base + r] = cls;
         if (cls == 2) w.new_i[base + r] = ni;                            // (read back for kept ground rows only: k_wet_scatter)
         cnt_a += cls == 1; cnt_b += cls == 2;
@@ -712,6 +722,108 @@ __global__ __launch_bounds__(PB) void k_wet_scatter(WetArgs w)
     }
 }
 
+// ---- the aligned wet stage: every row stays where it lies ------------------------------------------------------------------------------
+// The wet model never moves a point (augmentation.py:145-159): a non-ground row is copied, a ground row gets a new intensity and label 1
+// or is dropped.  So the result can keep the input's size and order, one keep byte beside every row, and needs neither k_wet_scan /
+// k_wet_scatter (they only build the reference's [non-ground ; kept ground] order) nor the cls / new_i scratch.
+struct WetAlignedArgs {
+    PreArgs p;             // p.keep: the keep bytes that came in (NULL: every row present); p.frame_cnt = NULL (tiles of the full row range)
+    double water_height, pavement_depth;
+    int replace;
+    void *out_rows;        // rows of the input's dtype; may be p.rows itself (in place)
+    uint8_t *out_keep;     // may be p.keep itself
+    int32_t *tile_cnt;     // [frame][tile]: rows kept
+    int64_t *out_counts;
+    int32_t *out_flags;
+};
+
+// Per row (processed frame): keep-in 0 -> as it came, keep 0; not ground -> column 4 = 0 under `replace` (:155-156), keep 1; ground, kept
+// (:146) -> the new intensity (:153, rounded once to T), label 1 (:159), keep 1; ground, dropped -> the value new_intensities held after
+// :131, label 1, keep 0.  A frame with fewer than 1000 present ground rows (:51-52) keeps rows and keep bytes as they came.  Out of place
+// every row is stored whole; in place only columns 3 and 4 of the rows that change, and the keep bytes that change.
+template <typename T>
+__global__ __launch_bounds__(PB) void k_wet_apply_aligned(WetAlignedArgs w)
+{
+    const PreArgs &a = w.p;
+    const int f = blockIdx.y;
+    const int64_t base = a.frame_off[f], n = a.frame_off[f + 1] - base;
+    const int64_t tile0 = (int64_t)blockIdx.x * SG_TILE;
+    if (tile0 >= n) return;
+    const PreFrame fr = a.fr[f];
+    const T *rows = (const T *)a.rows;
+    T *out = (T *)w.out_rows;
+    const bool whole = (const void *)out != a.rows, same_keep = w.out_keep == a.keep;
+    // every load of the thread's four rows before the first store (the argument struct carries no `restrict`, and out_rows / out_keep may
+    // BE the input: see k_wet_scatter).  A thread reads and writes its own four rows only, so in place nothing is read after it was written.
+    double gns[4], gds[4], angs[4];
+    T sx[4], sy[4], sz[4], si[4], sl[4];
+    uint8_t kin[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int64_t r = tile0 + q * PB + threadIdx.x;
+        const bool in = r < n;
+        kin[q] = in ? (a.keep ? a.keep[base + r] : (uint8_t)1) : (uint8_t)0;
+        gns[q] = (in && !fr.unchanged) ? a.g_norm[base + r] : NAN;       // (NaN for a row that is not there, too: k_pre_ground<T, true>)
+        const bool ground = gns[q] == gns[q];
+        gds[q] = ground ? a.g_dist[base + r] : 0.0;
+        angs[q] = ground ? a.g_ang[base + r] : 1.0;
+        const T *s = rows + (base + (in ? r : 0)) * 5;
+        sx[q] = sy[q] = sz[q] = si[q] = sl[q] = (T)0;
+        if (whole) { sx[q] = s[0]; sy[q] = s[1]; sz[q] = s[2]; si[q] = s[3]; sl[q] = s[4]; }
+        else if (ground) si[q] = s[3];
+    }
+    int cnt = 0;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int64_t r = tile0 + q * PB + threadIdx.x;
+        if (r >= n) continue;
+        T inten = si[q], lab = sl[q];
+        uint8_t k = kin[q];
+        bool new_i = false, new_l = false;                               // column 3 / column 4 is rewritten (in place: the only stores)
+        if (!fr.unchanged && k) {
+            const double gn = gns[q];
+            if (gn != gn) {
+                if (w.replace) { lab = (T)0; new_l = true; }             // :155-156
+            } else {
+                double ni;
+                k = wet_row_chain(a, fr, w.water_height, w.pavement_depth, gds[q], angs[q], (double)si[q], ni) ? 1 : 0;
+                inten = (T)ni; lab = (T)1; new_i = new_l = true;         // :153, :159
+            }
+        }
+        T *d = out + (base + r) * 5;
+        if (whole) { d[0] = sx[q]; d[1] = sy[q]; d[2] = sz[q]; d[3] = inten; d[4] = lab; }
+        else {
+            if (new_i) d[3] = inten;                                     // (a non-ground row's intensity was not even loaded)
+            if (new_l) d[4] = lab;
+        }
+        if (!same_keep || k != kin[q]) w.out_keep[base + r] = k;
+        cnt += k != 0;
+    }
+    __shared__ int sc[4];
+    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_down(cnt, o);
+    if ((threadIdx.x & 63) == 0) sc[threadIdx.x >> 6] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) w.tile_cnt[(int64_t)f * a.max_tiles + blockIdx.x] = sc[0] + sc[1] + sc[2] + sc[3];
+}
+
+// per frame: rows kept and the "returned as it came" flag.  One wave per frame, lane l taking tiles l, l + 64, .. as k_wet_scan does;
+// integers in a fixed order, no atomics.
+__global__ __launch_bounds__(64) void k_wet_count(WetAlignedArgs w)
+{
+    const PreArgs &a = w.p;
+    const int f = blockIdx.x, lane = threadIdx.x;
+    const int64_t n = a.frame_off[f + 1] - a.frame_off[f];
+    const int64_t tiles = (n + SG_TILE - 1) / SG_TILE;
+    const int32_t *c = w.tile_cnt + (int64_t)f * a.max_tiles;
+    int sum = 0;                                                         // (a batch holds fewer than 2^31 rows)
+    for (int64_t t = lane; t < tiles; t += 64) sum += c[t];
+    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+    if (lane == 0) {
+        w.out_counts[f] = sum;
+        w.out_flags[f] = a.fr[f].unchanged;
+    }
+}
+
 // Source rows of a chained result (snowfall, then wet ground): final row -> snowfall row -> input row.
 __global__ __launch_bounds__(PB) void k_compose_src(const int64_t *__restrict__ frame_off, const int64_t *__restrict__ counts,
                                                    const int32_t *__restrict__ second, const int32_t *__restrict__ first,
@@ -745,7 +857,9 @@ static int estimate(SgPrepassScratch *s, PreArgs &a, int dtype, int64_t n_total,
     if (e != hipSuccess) return (int)e;
     dim3 grid((unsigned)max_tiles, (unsigned)a.n_frames);
     const int rc = sg_by_dtype(dtype, [&](auto t) {
-        hipLaunchKernelGGL(k_pre_ground<decltype(t)>, grid, dim3(PB), 0, st, a);
+        using T = decltype(t);
+        if (a.keep) hipLaunchKernelGGL((k_pre_ground<T, true>), grid, dim3(PB), 0, st, a);
+        else hipLaunchKernelGGL((k_pre_ground<T, false>), grid, dim3(PB), 0, st, a);
         SG_CHECK_LAUNCH();
         return 0;
     });
@@ -772,21 +886,19 @@ static int estimate(SgPrepassScratch *s, PreArgs &a, int dtype, int64_t n_total,
     return 0;
 }
 
-extern "C" int sg_wet_run(SgPrepassScratch *s, const void *rows, int dtype, const int64_t *frame_off,
-                          const int64_t *frame_cnt, int n_frames, int64_t n_total, int64_t max_frame, const double *plane, const SgWetParams *wp, double *out_rows, int32_t *out_src,
-                          int64_t *out_counts, int32_t *out_flags, int32_t *status, void *stream)
+// The estimate both wet entries start from: the argument block from the call's parameters, estimate(), the two quadratics of 'poly', the
+// export of the fitted curves.  keep: the aligned stage's keep bytes (NULL: every row present).
+static int wet_fit(SgPrepassScratch *s, PreArgs &a, const void *rows, int dtype, const int64_t *frame_off, const int64_t *frame_cnt,
+                   const uint8_t *keep, int n_frames, int64_t n_total, int64_t max_frame, const double *plane, const SgWetParams *wp,
+                   int32_t *status, hipStream_t st)
 {
-    hipStream_t st = (hipStream_t)stream;
-    WetArgs w{};
-    PreArgs &a = w.p;
     a.lines_override = wp->lines;
-    a.rows = rows; a.frame_off = frame_off; a.frame_cnt = frame_cnt; a.n_frames = n_frames; a.plane = plane; a.delta = wp->delta;
+    a.rows = rows; a.frame_off = frame_off; a.frame_cnt = frame_cnt; a.keep = keep; a.n_frames = n_frames; a.plane = plane; a.delta = wp->delta;
     a.flat_earth = wp->flat_earth; a.rows_as_f64 = 1; a.noise_floor = wp->noise_floor; a.power_factor = wp->power_factor; a.status = status;
     int rc = estimate(s, a, dtype, n_total, max_frame, 1000, 0, false, st);
     if (rc) return rc;
-    const size_t n = (size_t)(n_total > 0 ? n_total : 1), nf = (size_t)n_frames;
     if (wp->estimation == 1) {                       // 'poly': the two quadratics replace the two lines
-        if (sg_pre_ensure(s, B_QPART, nf * (size_t)a.max_tiles * PQ_COLS * 8)) return -1;
+        if (sg_pre_ensure(s, B_QPART, (size_t)n_frames * (size_t)a.max_tiles * PQ_COLS * 8)) return -1;
         a.qpart = (double *)s->buf[B_QPART]; a.seed = wp->seed;
         hipLaunchKernelGGL(k_pre_quad_part, dim3((unsigned)a.max_tiles, (unsigned)n_frames), dim3(PB), 0, st, a);
         SG_CHECK_LAUNCH();
@@ -797,6 +909,19 @@ extern "C" int sg_wet_run(SgPrepassScratch *s, const void *rows, int dtype, cons
         hipLaunchKernelGGL(k_pre_export_fit, dim3((unsigned)((n_frames + 63) / 64)), dim3(64), 0, st, a, wp->fit_out);
         SG_CHECK_LAUNCH();
     }
+    return 0;
+}
+
+extern "C" int sg_wet_run(SgPrepassScratch *s, const void *rows, int dtype, const int64_t *frame_off,
+                          const int64_t *frame_cnt, int n_frames, int64_t n_total, int64_t max_frame, const double *plane, const SgWetParams *wp, double *out_rows, int32_t *out_src,
+                          int64_t *out_counts, int32_t *out_flags, int32_t *status, void *stream)
+{
+    hipStream_t st = (hipStream_t)stream;
+    WetArgs w{};
+    PreArgs &a = w.p;
+    int rc = wet_fit(s, a, rows, dtype, frame_off, frame_cnt, nullptr, n_frames, n_total, max_frame, plane, wp, status, st);
+    if (rc) return rc;
+    const size_t n = (size_t)(n_total > 0 ? n_total : 1), nf = (size_t)n_frames;
     if (sg_pre_ensure(s, B_CLS, n) || sg_pre_ensure(s, B_NEWI, n * 8) || sg_pre_ensure(s, B_TCNT, nf * (size_t)a.max_tiles * 2 * 4) ||
         sg_pre_ensure(s, B_TBASE, nf * (size_t)a.max_tiles * 2 * 4))
         return -1;
@@ -812,6 +937,31 @@ extern "C" int sg_wet_run(SgPrepassScratch *s, const void *rows, int dtype, cons
         hipLaunchKernelGGL(k_wet_scan, dim3((unsigned)n_frames), dim3(64), 0, st, w);
         SG_CHECK_LAUNCH();
         hipLaunchKernelGGL(k_wet_scatter<T>, grid, dim3(PB), 0, st, w);
+        SG_CHECK_LAUNCH();
+        return 0;
+    });
+}
+
+// sg_wet_run with the ALIGNED result: rows of the input's dtype at the input's own index in out_rows (which may be `rows`), one keep
+// byte per row in out_keep (which may be keep_in).  keep_in: optional, 0 = the row is not there.  Frames are walked over their full row
+// range; src_first of wp is unused (row i IS input row i).
+extern "C" int sg_wet_run_aligned(SgPrepassScratch *s, const void *rows, int dtype, const int64_t *frame_off, const uint8_t *keep_in,
+                                  int n_frames, int64_t n_total, int64_t max_frame, const double *plane, const SgWetParams *wp, void *out_rows,
+                                  uint8_t *out_keep, int64_t *out_counts, int32_t *out_flags, int32_t *status, void *stream)
+{
+    hipStream_t st = (hipStream_t)stream;
+    WetAlignedArgs w{};
+    PreArgs &a = w.p;
+    int rc = wet_fit(s, a, rows, dtype, frame_off, nullptr, keep_in, n_frames, n_total, max_frame, plane, wp, status, st);
+    if (rc) return rc;
+    if (sg_pre_ensure(s, B_TCNT, (size_t)n_frames * (size_t)a.max_tiles * 4)) return -1;
+    w.water_height = wp->water_height; w.pavement_depth = wp->pavement_depth; w.replace = wp->replace;
+    w.out_rows = out_rows; w.out_keep = out_keep; w.tile_cnt = (int32_t *)s->buf[B_TCNT]; w.out_counts = out_counts; w.out_flags = out_flags;
+    dim3 grid((unsigned)a.max_tiles, (unsigned)n_frames);
+    return sg_by_dtype(dtype, [&](auto t) {
+        hipLaunchKernelGGL(k_wet_apply_aligned<decltype(t)>, grid, dim3(PB), 0, st, w);
+        SG_CHECK_LAUNCH();
+        hipLaunchKernelGGL(k_wet_count, dim3((unsigned)n_frames), dim3(64), 0, st, w);
         SG_CHECK_LAUNCH();
         return 0;
     });

@@ -13,6 +13,9 @@ The reference's training-time caller (the OpenPCDet DENSE dataset: `root_path`, 
   * `layout='aligned'` returns the rows in the INPUT's order with one keep flag per row (AlignedResult) instead of compacting them: a
     result whose shape does not depend on the data, so a consumer on the same stream -- or in the same HIP graph -- reads it without a
     host round trip, and per-point companions of the sweep (labels, timestamps, further columns) stay aligned with it.
+  * `augment_wet_batch_aligned(frames, ...)` is the snowfall + wet-ground chain with that aligned result (AlignedWetResult: per-frame
+    flags beside it; snowgpu_augment_wet_batch_device_aligned), `wet_ground_batch_aligned(frames, keep)` the wet-ground stage alone on rows
+    and a keep mask from any earlier stage (snowgpu_wet_ground_batch_device_aligned).
 
 What crosses the link per call: the frame offsets, the n_frames x n_lasers table ids and the planes (a few KB, cached by value: a
 training loop that reshuffles `order` per frame uploads 64 int32 per frame).  PyTorch is plumbing here -- device memory and streams;
@@ -136,6 +139,28 @@ class AlignedResult(DeviceResult):
         return out
 
 
+class AlignedWetResult(AlignedResult):
+    """An AlignedResult of the wet-ground stage (wet_ground_batch_aligned, augment_wet_batch_aligned): `flags` (n_frames, int32) is 1 where
+    a frame had fewer than 1000 present ground rows and came back as it was (augmentation.py:51-52), `counts` are the keep flags set after
+    the wet stage, `stats` the snowfall statistics (None for the wet-ground model on its own)."""
+
+    def __init__(self, ctx, rows, keep_mask, counts, stats, status, offsets, stream, flags, keep=()):
+        super().__init__(ctx, rows, keep_mask, counts, stats, status, offsets, stream, keep=keep)
+        self.flags = flags
+
+    def frames(self):
+        """[(stats, rows_f, keep_f, flag_f)] per frame, rows_f / keep_f views of the result tensors (waits)."""
+        self.wait()
+        stats = None if self.stats is None else self.stats.cpu().numpy()
+        flags = self.flags.cpu().numpy()
+        out = []
+        for i in range(len(self.offsets) - 1):
+            a, b = int(self.offsets[i]), int(self.offsets[i + 1])
+            st = None if stats is None else (np.int64(stats[i, 0]), np.int64(stats[i, 1]), int(stats[i, 2]))
+            out.append((st, self.rows[a:b], self.keep[a:b], int(flags[i])))
+        return out
+
+
 class _SmallUploads:
     """Device copies of the small per-call arrays (offsets, table ids, planes, polynomials), by value: a few KB each, least
     recently used first out."""
@@ -214,6 +239,34 @@ def _rows_where_they_lie(torch, frames):
     return rows, offsets
 
 
+def _run_stream(torch, eng, dev, stream, lane=None):
+    """The torch stream a call is launched on: the caller's `stream` itself, or -- for torch's legacy default stream (handle 0, which the C
+    ABI reads as "the context's own stream") and for a compute lane -- a side stream of the engine's, made on first use."""
+    if stream.cuda_stream != 0 and lane is None:
+        return stream
+    run = eng.__dict__.get("_torch_side_stream")
+    if run is None or run.device != dev:
+        if lane is not None:
+            # lanes k, k + 1, k + 2 on streams of three different priorities: three queue pools of the runtime, so three hardware
+            # queues whatever else the process has created (include/snowgpu.h: snowgpu_lane_stream)
+            many = int(os.environ.get("GPU_MAX_HW_QUEUES", "4") or 4) >= 16      # (then every stream has a queue anyway: one priority)
+            order = [int(v) for v in os.environ.get("SNOWGPU_LANE_LEVELS", "1" if many else "2,1,0").split(",")]
+            run = torch.cuda.ExternalStream(eng.ctx.lane_stream(order[int(lane) % len(order)]), device=dev)
+        else:
+            run = torch.cuda.Stream(device=dev)
+        eng.__dict__["_torch_side_stream"] = run
+    return run
+
+
+def _plane_rows(planes, nf):
+    """n_frames x 4 float64 (wx, wy, wz, h) from an n_frames x 4 array, per-frame (w, h) pairs, or ONE (w, h) pair for every frame."""
+    if isinstance(planes, np.ndarray) and planes.shape == (nf, 4):
+        return np.ascontiguousarray(planes, np.float64)
+    if len(planes) == 2 and np.ndim(planes[1]) == 0:
+        planes = [planes] * nf
+    return np.asarray([[float(w[0]), float(w[1]), float(w[2]), float(h)] for w, h in planes], np.float64).reshape(nf, 4)
+
+
 def table_ids_for(eng, n_frames, particle_file_prefix, root_path, particles, orders, shuffle):
     """n_frames x n_lasers int32 device table ids: channel c of frame f reads line orders[f][c] + 1 (simulation.py:78, :482-486)."""
     from .tools.snowfall import simulation as _sim
@@ -272,7 +325,7 @@ def augment_batch(frames, particle_file_prefix, beam_divergence, shuffle=True, n
              rows_f[keep_f] are the compact rows in input order.  `out=` takes an earlier AlignedResult; lane=, calib=, planes=,
              thr_polys=, orders=, particles=, plane_method= work as for the compact layout.  Frames with more than five columns:
              the result has five, and the caller's further columns are ALREADY aligned with it, row for row -- nothing is gathered.
-             Not with wet= (the wet-ground estimator reads compacted rows) and not with return_src (row i IS input row i).
+             Not with wet= (augment_wet_batch_aligned is the aligned chain) and not with return_src (row i IS input row i).
     in_place with layout='aligned': the result's `rows` IS the input tensor, overwritten by its augmented form.  The input must be
              read where it lies -- a DeviceBatch, one contiguous N x 5 tensor or an F x N x 5 tensor; a list that would have to be
              concatenated raises ValueError (the result would land in a temporary).
@@ -291,8 +344,8 @@ def augment_batch(frames, particle_file_prefix, beam_divergence, shuffle=True, n
     if in_place and not aligned:
         raise ValueError("in_place=True needs layout='aligned': compacted rows do not lie where their input rows lay")
     if aligned and wet is not None:
-        raise ValueError("wet= with layout='aligned': the wet-ground estimator reads the compacted snowfall rows and would have to skip "
-                         "masked ones; use the compact layout for the fused call")
+        raise ValueError("wet= with layout='aligned': layout='aligned' promises the compact call's bytes, and the aligned wet-ground stage "
+                         "sums over other tiles; call augment_wet_batch_aligned for the aligned chain, or use the compact layout")
     if aligned and return_src:
         raise ValueError("return_src with layout='aligned': there is no src, row i of the result is input row i")
     if in_place:
@@ -333,19 +386,7 @@ def augment_batch(frames, particle_file_prefix, beam_divergence, shuffle=True, n
         # default stream HAS the handle 0, so a call made on it runs on a side stream of the engine, forked from and joined back into the
         # default stream (two event waits): uploads queued before the call are seen, and whoever reads the results on the caller's stream
         # afterwards -- or synchronises it -- waits for the call.
-        run = stream
-        if stream.cuda_stream == 0 or lane is not None:
-            run = eng.__dict__.get("_torch_side_stream")
-            if run is None or run.device != dev:
-                if lane is not None:
-                    # lanes k, k + 1, k + 2 on streams of three different priorities: three queue pools of the runtime, so three hardware
-                    # queues whatever else the process has created (include/snowgpu.h: snowgpu_lane_stream)
-                    many = int(os.environ.get("GPU_MAX_HW_QUEUES", "4") or 4) >= 16      # (then every stream has a queue anyway: one priority)
-                    order = [int(v) for v in os.environ.get("SNOWGPU_LANE_LEVELS", "1" if many else "2,1,0").split(",")]
-                    run = torch.cuda.ExternalStream(eng.ctx.lane_stream(order[int(lane) % len(order)]), device=dev)
-                else:
-                    run = torch.cuda.Stream(device=dev)
-                eng.__dict__["_torch_side_stream"] = run
+        run = _run_stream(torch, eng, dev, stream, lane)
         d_off = up.get(torch, dev, offsets, run)
         d_tids = up.get(torch, dev, tids, run)
         d_poly = d_plane = None
@@ -450,3 +491,202 @@ def augment_batch(frames, particle_file_prefix, beam_divergence, shuffle=True, n
             aug = torch.cat((aug, extras[i][src.long(), 5:].to(aug.dtype)), dim=1)
         results.append((st, aug, src) if return_src else (st, aug))
     return results
+
+
+WET_DEFAULTS = dict(water_height=0.001, pavement_depth=0.0012, noise_floor=0.7, power_factor=15, flat_earth=False, delta=0.5, replace=True)
+
+
+def _wet_arguments(wet):
+    """(parameters, plane or None, estimation method, RANSAC seed) from ground_water_augmentation()'s keyword arguments."""
+    wet = dict(wet or {})
+    plane = wet.pop("plane", None)
+    method = wet.pop("estimation_method", "linear")
+    seed = wet.pop("poly_seed", 0)
+    wet.pop("debug", None)
+    unknown = set(wet) - set(WET_DEFAULTS)
+    if unknown:
+        raise TypeError(f"unknown wet-ground arguments: {sorted(unknown)}")
+    if method not in _native.WET_ESTIMATION:
+        raise ValueError("estimation_method must be 'linear' or 'poly' (augmentation.py:215, :223)")
+    return dict(WET_DEFAULTS, **wet), plane, method, seed
+
+
+def _aligned_outputs(torch, out, rows, n, nf, in_place, with_stats):
+    """(rows, keep, counts, stats, status, flags) tensors of an aligned wet call: those of `out` (an AlignedWetResult of the same shapes) or new ones."""
+    dev = rows.device
+    if isinstance(out, AlignedWetResult) and out.keep.shape[0] == n and out.keep.device == dev and out.counts.shape[0] == nf and \
+            (out.stats is not None) == with_stats and \
+            (in_place or (out.rows.shape[0] == n and out.rows.dtype == rows.dtype and out.rows.data_ptr() != rows.data_ptr())):
+        return (rows if in_place else out.rows), out.keep, out.counts, out.stats, out.status, out.flags
+    return (rows if in_place else torch.empty((n, 5), dtype=rows.dtype, device=dev), torch.empty(n, dtype=torch.bool, device=dev),
+            torch.empty(nf, dtype=torch.int64, device=dev), torch.empty((nf, 3), dtype=torch.int64, device=dev) if with_stats else None,
+            torch.empty(8, dtype=torch.int32, device=dev), torch.empty(nf, dtype=torch.int32, device=dev))
+
+
+def _empty_aligned_wet(torch, eng, rows, nf, offsets, with_stats, sync):
+    dev = rows.device
+    z = lambda *shape, dt=torch.int64: torch.zeros(shape, dtype=dt, device=dev)   # noqa: E731
+    res = AlignedWetResult(eng.ctx, rows[:0], z(0, dt=torch.bool), z(nf), z(nf, 3) if with_stats else None, z(8, dt=torch.int32), offsets,
+                           torch.cuda.current_stream(dev), torch.ones(nf, dtype=torch.int32, device=dev))
+    return res.frames() if sync else res
+
+
+def wet_ground_batch_aligned(frames, keep=None, *, plane=None, water_height=0.001, pavement_depth=0.0012, noise_floor=0.7, power_factor=15,
+                             flat_earth=False, delta=0.5, replace=True, estimation_method='linear', poly_seed=0, lines=None, device=None,
+                             slot=0, in_place=False, sync=True, out=None):
+    """ground_water_augmentation() (tools/wet_ground/augmentation.py:25-161) for torch CUDA tensors with the ALIGNED result
+    (snowgpu_wet_ground_batch_device_aligned): row i of the result is the output row of input row i, `keep` says which rows the reference
+    returns -- the wet-ground model never moves a point, so nothing needs compacting.
+
+    frames   as augment_batch: a list of N_i x 5 CUDA tensors, an F x N x 5 tensor, one N x 5 tensor or a DeviceBatch; float32 or float64.
+    keep     optional torch.bool (or uint8) tensor, one element per row of the batch: False = the row is not there (an earlier stage
+             removed it -- AlignedResult.keep of augment_batch(layout='aligned')).  The estimator skips such rows and they come back as
+             they came.  None: every row is present.
+    plane    (w, h) for every frame, per-frame pairs or an n_frames x 4 array; None: the flat-earth plane the reference returns today.
+    lines    optional n_frames x 4 (p slope, p intercept, noise-line slope, intercept) fitted by the caller instead of the device's fit.
+    in_place the result's `rows` IS the input tensor (which must be read where it lies, as for augment_batch) and `keep` the tensor passed
+             as keep (a new one when keep is None).
+    sync     True: wait, check, return [(None, rows_f, keep_f, flag_f)] (no statistics: the wet-ground model has none); False: an
+             AlignedWetResult at once, asynchronous on torch's current stream.  out: an earlier AlignedWetResult whose tensors are reused.
+    Rows come back in the INPUT's dtype -- a float32 row's new intensity is the float64 result rounded once --, unlike the compact entries,
+    which return float64 (augmentation.py:150).  flag_f = 1: fewer than 1000 present ground rows, the frame came back as it was.  NumPy
+    input raises ValueError: the aligned layout is a result layout of the torch-tensor boundary."""
+    if not is_device_input(frames):
+        raise ValueError("wet_ground_batch_aligned: the aligned layout is a result layout of the torch-tensor boundary (CUDA tensors); "
+                         "host arrays get the reference's compacted return value from ground_water_augmentation")
+    import torch
+    from . import engine as _engine
+    w, _, method, seed = _wet_arguments(dict(water_height=water_height, pavement_depth=pavement_depth, noise_floor=noise_floor,
+                                             power_factor=power_factor, flat_earth=flat_earth, delta=delta, replace=replace,
+                                             estimation_method=estimation_method, poly_seed=poly_seed))
+    rows, offsets = _rows_where_they_lie(torch, frames) if in_place else _as_batch(torch, frames)[:2]
+    dev = rows.device
+    if device is not None and int(device) != dev.index:
+        raise ValueError(f"the tensors live on {dev}, device={device} was asked for")
+    nf, n = len(offsets) - 1, int(offsets[-1])
+    if nf == 0:
+        return []
+    if keep is not None:
+        if keep.device != dev or keep.dim() != 1 or keep.shape[0] != n or keep.dtype not in (torch.bool, torch.uint8) or not keep.is_contiguous():
+            raise ValueError("keep must be a contiguous torch.bool (or uint8) CUDA tensor with one element per row of the batch")
+        if keep.dtype == torch.uint8:
+            keep = keep.view(torch.bool)
+    eng = _engine.get_engine(dev.index, slot)
+    if n == 0:
+        return _empty_aligned_wet(torch, eng, rows, nf, offsets, False, sync)
+    code = 0 if rows.dtype == torch.float32 else 1
+    up = _uploads(eng)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev)
+        run = _run_stream(torch, eng, dev, stream)
+        d_off = up.get(torch, dev, offsets, run)
+        d_plane = None if plane is None else up.get(torch, dev, _plane_rows(plane, nf), run)
+        o_rows, o_keep, o_cnt, _, o_status, o_flags = _aligned_outputs(torch, out, rows, n, nf, in_place, False)
+        if in_place and keep is not None:
+            o_keep = keep
+        if run is not stream:
+            run.wait_stream(stream)
+        with eng.batch_lock:
+            if method != 'linear':
+                eng.ctx.set_wet_estimation(method, seed)
+            if lines is not None:
+                eng.ctx.set_wet_lines(np.ascontiguousarray(lines, np.float64).reshape(nf, 4))
+            try:
+                eng.ctx.wet_ground_batch_device_aligned(nf, n, int(np.diff(offsets).max()), d_off.data_ptr(), rows.data_ptr(), code,
+                                                        0 if keep is None else keep.data_ptr(), 0 if d_plane is None else d_plane.data_ptr(),
+                                                        w["water_height"], w["pavement_depth"], w["noise_floor"], w["power_factor"],
+                                                        w["flat_earth"], w["delta"], w["replace"], o_rows.data_ptr(), o_keep.data_ptr(),
+                                                        o_cnt.data_ptr(), o_flags.data_ptr(), o_status.data_ptr(), run.cuda_stream)
+            finally:
+                if run is not stream:
+                    stream.wait_stream(run)
+                if method != 'linear':
+                    eng.ctx.set_wet_estimation('linear')
+                if lines is not None:
+                    eng.ctx.set_wet_lines(None)
+    res = AlignedWetResult(eng.ctx, o_rows, o_keep, o_cnt, None, o_status, offsets, stream, o_flags, keep=(rows, keep, d_off, d_plane))
+    return res.frames() if sync else res
+
+
+def augment_wet_batch_aligned(frames, particle_file_prefix, beam_divergence, shuffle=True, noise_floor=0.7, root_path=None, *, wet=None,
+                              planes=None, orders=None, particles=None, thr_polys=None, device=None, slot=0, calib=None, sync=True,
+                              out=None, lane=None, in_place=False, **_ignored):
+    """augment() followed by ground_water_augmentation() on its output (pointcloud_viewer.py:2807-2821) for torch CUDA tensors with the
+    ALIGNED result (snowgpu_augment_wet_batch_device_aligned): the snowfall stage finishes into rows in the input's order plus a keep
+    mask, and the wet-ground stage rewrites those two arrays in place, skipping the rows the snowfall stage removed.  No compaction, a
+    result of static shape in the input's dtype, nothing read on the host: the form a training step wants.
+
+    wet       dict of ground_water_augmentation()'s keyword arguments (water_height, pavement_depth, noise_floor, power_factor, flat_earth,
+              delta, replace, plane, estimation_method, poly_seed); plane=None: the flat-earth plane the reference returns today.
+    planes, thr_polys, orders, particles, calib, in_place, sync, out (an earlier AlignedWetResult), lane: as augment_batch(layout='aligned').
+    Returns an AlignedWetResult (sync=False) or its frames(): [(stats, rows_f, keep_f, flag_f)] -- stats the snowfall statistics,
+    keep_f true where the CHAIN returns the row, flag_f = 1 where the wet stage found fewer than 1000 present ground rows and left the
+    frame as the snowfall stage made it.
+
+    Why this is a function of its own and not augment_batch(layout='aligned', wet=...): layout='aligned' promises the bytes of the compact
+    call of the same arguments, in input order.  The wet-ground estimate is a set of sums over 1024-row tiles, and here the tiles are those
+    of the input's rows with the removed ones skipped, not those of the compacted snowfall rows -- so the fitted power line, and with it
+    the intensities, differ from the compact fused call's in their last bits; float32 rows also stay float32 here, where the compact
+    chain returns float64.  NumPy input raises ValueError, as for the aligned layout."""
+    if not is_device_input(frames):
+        raise ValueError("augment_wet_batch_aligned: the aligned layout is a result layout of the torch-tensor boundary (CUDA tensors); "
+                         "host arrays get the reference's compacted return value from augment_batch / ground_water_augmentation")
+    import torch
+    from . import engine as _engine
+    w, wet_plane, method, seed = _wet_arguments(wet)
+    rows, offsets = _rows_where_they_lie(torch, frames) if in_place else _as_batch(torch, frames)[:2]
+    dev = rows.device
+    if device is not None and int(device) != dev.index:
+        raise ValueError(f"the tensors live on {dev}, device={device} was asked for")
+    eng = _engine.get_engine(dev.index, slot if lane is None else LANE_SLOT0 + int(lane))
+    if lane is not None and not eng.__dict__.get("_lane_serial"):
+        eng.ctx.set_serial(True)                      # (a compute lane runs its batches on one stream: augment_batch)
+        eng.__dict__["_lane_serial"] = True
+    nf, n = len(offsets) - 1, int(offsets[-1])
+    if nf == 0:
+        return []
+    if n == 0:
+        return _empty_aligned_wet(torch, eng, rows, nf, offsets, True, sync)
+    code = 0 if rows.dtype == torch.float32 else 1
+    up = _uploads(eng)
+    with torch.cuda.device(dev):
+        tids = table_ids_for(eng, nf, particle_file_prefix, root_path, particles, orders, shuffle)
+        stream = torch.cuda.current_stream(dev)
+        run = _run_stream(torch, eng, dev, stream, lane)
+        d_off = up.get(torch, dev, offsets, run)
+        d_tids = up.get(torch, dev, tids, run)
+        d_poly = d_plane = None
+        if thr_polys is not None:
+            d_poly = up.get(torch, dev, np.ascontiguousarray(thr_polys, np.float64).reshape(nf, 3), run)
+        elif planes is not None:
+            d_plane = up.get(torch, dev, _plane_rows(planes, nf), run)
+        d_wet_plane = None if wet_plane is None else up.get(torch, dev, _plane_rows(wet_plane, nf), run)
+        o_rows, o_keep, o_cnt, o_st, o_status, o_flags = _aligned_outputs(torch, out, rows, n, nf, in_place, True)
+        if run is not stream:
+            run.wait_stream(stream)
+            if lane is not None:                    # (tensors of the caller's stream used on the lane's: the allocator must know)
+                for t in (rows, o_rows, o_keep, o_cnt, o_st, o_status, o_flags):
+                    t.record_stream(run)
+        ptr = lambda t: 0 if t is None else t.data_ptr()   # noqa: E731
+        with eng.batch_lock:
+            if calib is not None:
+                eng.ctx.set_fov(calib, (1024, 1920))
+            if method != 'linear':
+                eng.ctx.set_wet_estimation(method, seed)
+            try:
+                eng.ctx.augment_wet_batch_device_aligned(nf, n, int(np.diff(offsets).max()), d_off.data_ptr(), rows.data_ptr(), code,
+                                                         d_tids.data_ptr(), float(beam_divergence), ptr(d_poly), ptr(d_plane),
+                                                         float(noise_floor), 0, o_rows.data_ptr(), o_keep.data_ptr(), o_cnt.data_ptr(),
+                                                         o_st.data_ptr(), 0, o_status.data_ptr(), run.cuda_stream, ptr(d_wet_plane),
+                                                         w["water_height"], w["pavement_depth"], w["noise_floor"], w["power_factor"],
+                                                         w["flat_earth"], w["delta"], w["replace"], o_flags.data_ptr())
+            finally:
+                if run is not stream and lane is None:
+                    stream.wait_stream(run)
+                if calib is not None:
+                    eng.ctx.set_fov(None)
+                if method != 'linear':
+                    eng.ctx.set_wet_estimation('linear')
+    res = AlignedWetResult(eng.ctx, o_rows, o_keep, o_cnt, o_st, o_status, offsets, stream if lane is None else run, o_flags,
+                           keep=(rows, d_off, d_tids, d_poly, d_plane, d_wet_plane))
+    return res.frames() if sync else res

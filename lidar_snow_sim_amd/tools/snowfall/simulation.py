@@ -363,3 +363,11 @@ def augment(pc: np.ndarray, particle_file_prefix: str, beam_divergence: float, s
                         device_prepass=device_prepass, calib=cal, q8=q8, plane_method=plane_method, plane_seed=plane_seed,
                         plane_trials=plane_trials)[0]
     return res
+
+
+def augment_wet_batch_aligned(frames, particle_file_prefix: str, beam_divergence: float, *args, **kw):
+    """augment() followed by ground_water_augmentation() (pointcloud_viewer.py:2807-2821) on torch CUDA tensors with the aligned result:
+    rows in the input's order and dtype, a keep mask, per-frame flags, nothing read on the host.  lidar_snow_sim_amd.tensors
+    .augment_wet_batch_aligned, which documents the arguments; host arrays raise ValueError there."""
+    from ... import tensors as _tensors
+    return _tensors.augment_wet_batch_aligned(frames, particle_file_prefix, beam_divergence, *args, **kw)
