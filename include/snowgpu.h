@@ -531,6 +531,60 @@ int snowgpu_augment_wet_batch_device_aligned(snowgpu_ctx *ctx, int n_frames, int
                                              double wet_noise_floor, double power_factor, int flat_earth, double delta, int replace,
                                              int32_t *d_out_flags);
 
+/*
+ * snowgpu_augment_batch_device_aligned with an INPUT keep mask: a row whose d_keep_in byte is 0 is not there -- cropped away, padding of an
+ * F x Nmax batch, removed by an earlier stage.  For frame f let P be the indices of its present rows in input order.  The call returns,
+ * byte for byte, what snowgpu_augment_batch_device_aligned returns for the batch whose frame f holds exactly the rows P in that order
+ * (same tables, planes or plane method, polynomials, noise floor, camera crop):
+ *   d_out_rows[P[i]] / d_out_keep[P[i]]   that call's row i and its keep byte
+ *   d_out_stats, d_out_counts, d_out_thr_poly   that call's: num_removed counts against the PRESENT rows
+ *   an absent row      comes back as it came, all five columns bit for bit (out of place it is copied, in place it is not touched),
+ *                      keep byte 0.  It is never looked at: NaN coordinates, a range beyond the grid or a channel that is no laser
+ *                      in an absent row set no status word and change no byte of another row.
+ *   d_keep_in   n_total bytes, or NULL: all rows present -- the unmasked call itself.  A frame whose bytes are all 0 behaves as an empty frame.
+ *   d_out_keep  may be d_keep_in itself; any other overlap of the two, or of d_out_rows with d_rows, is SNOWGPU_E_INVALID.
+ *   d_perm      must be NULL with a mask (SNOWGPU_E_INVALID): a permutation indexes the rows of the frames it was made for.
+ *   d_status    as for the unmasked entry, except that [1] -- the first offending row -- indexes the sorted rows of the COMPACTED batch
+ *               (the present rows of all frames back to back), not the input's.
+ * How: the present rows are compacted, stably, into context scratch at offsets made on the device -- nothing is read on the host --, the
+ * launch sequence of the unmasked call runs on that scratch, and its last kernel writes every row at its index in the caller's frame.
+ * n_total and max_frame_rows are the INPUT's and bound the scratch (one more copy of the rows and 4 bytes per row).  The contract is the
+ * device entries': asynchronous on `stream`, no allocation after the first call of a size, no host read, capturable into a HIP graph.
+ * Needs at most 65536 tables and 2^22 frames (SNOWGPU_E_INVALID otherwise); refuses a threshold callback and the packed result transfer
+ * as the aligned entries do.
+ */
+int snowgpu_augment_batch_device_aligned_masked(snowgpu_ctx *ctx, int n_frames, int64_t n_total, int64_t max_frame_rows,
+                                                const int64_t *d_frame_offsets, const void *d_rows, int dtype, const int32_t *d_table_ids,
+                                                double beam_divergence_deg, const double *d_thr_poly, const double *d_plane,
+                                                double noise_floor, const int32_t *d_perm /* NULL */,
+                                                const uint8_t *d_keep_in /* NULL: all present */, void *d_out_rows /* may be d_rows itself */,
+                                                uint8_t *d_out_keep /* may be d_keep_in itself */, int64_t *d_out_counts, int64_t *d_out_stats,
+                                                double *d_out_thr_poly, int32_t *d_status, void *stream);
+
+/*
+ * snowgpu_augment_wet_batch_device_aligned whose snowfall stage is the masked one above.  The wet stage runs in place on d_out_rows /
+ * d_out_keep as in the unmasked chain: absent rows carry keep 0 there and are not there for it either.  The result equals the masked
+ * snowfall call followed by snowgpu_wet_ground_batch_device_aligned on its rows and keep bytes.
+ */
+int snowgpu_augment_wet_batch_device_aligned_masked(snowgpu_ctx *ctx, int n_frames, int64_t n_total, int64_t max_frame_rows,
+                                                    const int64_t *d_frame_offsets, const void *d_rows, int dtype,
+                                                    const int32_t *d_table_ids, double beam_divergence_deg, const double *d_thr_poly,
+                                                    const double *d_plane, double noise_floor, const int32_t *d_perm /* NULL */,
+                                                    const uint8_t *d_keep_in /* NULL: all present */, void *d_out_rows, uint8_t *d_out_keep,
+                                                    int64_t *d_out_counts, int64_t *d_out_stats, double *d_out_thr_poly, int32_t *d_status,
+                                                    void *stream, const double *d_wet_plane, double water_height, double pavement_depth,
+                                                    double wet_noise_floor, double power_factor, int flat_earth, double delta, int replace,
+                                                    int32_t *d_out_flags);
+
+/*
+ * The camera-FOV test of snowgpu_set_fov as a producer of a keep mask (precompute.py:96-99 as a mask instead of a compaction):
+ *   d_out_keep[i] = (d_keep_in ? d_keep_in[i] : 1) && get_fov_flag(lidar_to_rect(row i), (img_h, img_w))
+ * Matrices as snowgpu_set_fov takes them; the context's own crop setting is neither read nor changed.  A row whose keep-in byte is 0 is
+ * not loaded.  d_out_keep may be d_keep_in itself (any other overlap: SNOWGPU_E_INVALID).  Asynchronous on `stream`, no allocation, capturable.
+ */
+int snowgpu_fov_mask_device(snowgpu_ctx *ctx, int64_t n_total, const void *d_rows, int dtype, const double *v2c, const double *r0,
+                            const double *p2, int img_h, int img_w, const uint8_t *d_keep_in /* or NULL */, uint8_t *d_out_keep, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,6 +28,7 @@ EXPORTS = [
     "snowgpu_set_pipeline", "snowgpu_set_wet_lines", "snowgpu_set_plane_method", "snowgpu_estimate_planes",
     "snowgpu_estimate_planes_device", "snowgpu_prepass_stats", "snowgpu_set_wet_estimation", "snowgpu_wet_last_fit", "snowgpu_debug_ransac_polyfit", "snowgpu_set_result_transfer", "snowgpu_debug_transfer_times", "snowgpu_status_error", "snowgpu_set_threshold_callback", "snowgpu_augment_batch_compact", "snowgpu_set_serial", "snowgpu_lane_stream", "snowgpu_device_numa_node",
     "snowgpu_augment_batch_device_aligned", "snowgpu_wet_ground_batch_device_aligned", "snowgpu_augment_wet_batch_device_aligned",
+    "snowgpu_augment_batch_device_aligned_masked", "snowgpu_augment_wet_batch_device_aligned_masked", "snowgpu_fov_mask_device",
 ]
 
 WET_ESTIMATION = {"linear": 0, "poly": 1}
@@ -102,6 +103,14 @@ def lib():
             L.snowgpu_augment_wet_batch_device_aligned.restype = ctypes.c_int
             L.snowgpu_augment_wet_batch_device_aligned.argtypes = L.snowgpu_augment_batch_device_aligned.argtypes + [
                 vp, dbl, dbl, dbl, dbl, ctypes.c_int, dbl, ctypes.c_int, vp]
+            base = L.snowgpu_augment_batch_device_aligned.argtypes                  # (the masked forms: d_keep_in behind d_perm)
+            L.snowgpu_augment_batch_device_aligned_masked.restype = ctypes.c_int
+            L.snowgpu_augment_batch_device_aligned_masked.argtypes = base[:13] + [vp] + base[13:]
+            L.snowgpu_augment_wet_batch_device_aligned_masked.restype = ctypes.c_int
+            L.snowgpu_augment_wet_batch_device_aligned_masked.argtypes = base[:13] + [vp] + base[13:] + [
+                vp, dbl, dbl, dbl, dbl, ctypes.c_int, dbl, ctypes.c_int, vp]
+            L.snowgpu_fov_mask_device.restype = ctypes.c_int
+            L.snowgpu_fov_mask_device.argtypes = [vp, i64, vp, ctypes.c_int, vp, vp, vp, ctypes.c_int, ctypes.c_int, vp, vp, vp]
             L.snowgpu_set_fov_precrop.restype = ctypes.c_int
             L.snowgpu_set_fov_precrop.argtypes = [vp, ctypes.c_int]
             L.snowgpu_last_status.restype = ctypes.c_int
@@ -398,6 +407,44 @@ class Context:
             float(pavement_depth), float(wet_noise_floor), float(power_factor), int(bool(flat_earth)), float(delta), int(bool(replace)),
             vp(d_out_flags or None))
         self._check(rc)
+
+    def augment_batch_device_aligned_masked(self, n_frames, n_total, max_frame_rows, d_frame_off, d_rows, dtype_code, d_table_ids, beam_divergence,
+                                            d_thr_poly, d_plane, noise_floor, d_perm, d_keep_in, d_out_rows, d_out_keep, d_out_counts,
+                                            d_out_stats, d_out_thr, d_status, stream=0):
+        """augment_batch_device_aligned with an input keep mask (d_keep_in: one byte per row, 0 = the row is not there; 0 as the pointer =
+        all present; d_out_keep may be d_keep_in); asynchronous on `stream`."""
+        vp = ctypes.c_void_p
+        rc = self._L.snowgpu_augment_batch_device_aligned_masked(
+            self._h, int(n_frames), int(n_total), int(max_frame_rows), vp(d_frame_off), vp(d_rows or None), int(dtype_code), vp(d_table_ids),
+            float(beam_divergence), vp(d_thr_poly or None), vp(d_plane or None), float(noise_floor), vp(d_perm or None), vp(d_keep_in or None),
+            vp(d_out_rows or None), vp(d_out_keep or None), vp(d_out_counts), vp(d_out_stats), vp(d_out_thr or None), vp(d_status), vp(stream or None))
+        self._check(rc)
+
+    def augment_wet_batch_device_aligned_masked(self, n_frames, n_total, max_frame_rows, d_frame_off, d_rows, dtype_code, d_table_ids,
+                                                beam_divergence, d_thr_poly, d_plane, noise_floor, d_perm, d_keep_in, d_out_rows, d_out_keep,
+                                                d_out_counts, d_out_stats, d_out_thr, d_status, stream, d_wet_plane, water_height,
+                                                pavement_depth, wet_noise_floor, power_factor, flat_earth, delta, replace, d_out_flags):
+        """augment_wet_batch_device_aligned whose snowfall stage takes an input keep mask (d_keep_in behind d_perm); asynchronous on `stream`."""
+        vp = ctypes.c_void_p
+        rc = self._L.snowgpu_augment_wet_batch_device_aligned_masked(
+            self._h, int(n_frames), int(n_total), int(max_frame_rows), vp(d_frame_off), vp(d_rows or None), int(dtype_code),
+            vp(d_table_ids), float(beam_divergence), vp(d_thr_poly or None), vp(d_plane or None), float(noise_floor),
+            vp(d_perm or None), vp(d_keep_in or None), vp(d_out_rows or None), vp(d_out_keep or None), vp(d_out_counts or None),
+            vp(d_out_stats or None), vp(d_out_thr or None), vp(d_status or None), vp(stream or None), vp(d_wet_plane or None),
+            float(water_height), float(pavement_depth), float(wet_noise_floor), float(power_factor), int(bool(flat_earth)), float(delta),
+            int(bool(replace)), vp(d_out_flags or None))
+        self._check(rc)
+
+    def fov_mask_device(self, n_total, d_rows, dtype_code, calib, img_shape, d_keep_in, d_out_keep, stream=0):
+        """d_out_keep[i] = (d_keep_in ? d_keep_in[i] : 1) and the camera-FOV test of row i (calib: V2C, R0, P2 as for set_fov);
+        asynchronous on `stream`."""
+        vp = ctypes.c_void_p
+        v2c = np.ascontiguousarray(calib.V2C, np.float64).reshape(3, 4)
+        r0 = np.ascontiguousarray(calib.R0, np.float64).reshape(3, 3)
+        p2 = np.ascontiguousarray(calib.P2, np.float64).reshape(3, 4)
+        self._check(self._L.snowgpu_fov_mask_device(self._h, int(n_total), vp(d_rows or None), int(dtype_code), _p(v2c), _p(r0), _p(p2),
+                                                    int(img_shape[0]), int(img_shape[1]), vp(d_keep_in or None), vp(d_out_keep or None),
+                                                    vp(stream or None)))
 
     def set_fov(self, calib=None, img_shape=(1024, 1920), pre_crop=False):
         """Camera-FOV crop inside the compaction of every later batch (None switches it off).  `calib` carries V2C (3 x 4),

@@ -188,7 +188,7 @@ struct SgFov {
 
 // Launch wrappers (hipStream_t passed as void*), each implemented in the file that defines its kernels: snowgpu_sort.hip (expand_rows, sort,
 // gather_rows, segments*, resolve_tables), snowgpu_kernels.hip (beams, power*, tier_*, huge, sg_beams_block), snowgpu_rows.hip (rows),
-// snowgpu_compact.hip (compact, crop_*).  Every one of these files includes this header, so a definition cannot drift from its declaration.
+// snowgpu_compact.hip (compact, crop_*), snowgpu_mask.hip (mask_front, finish_aligned_masked, fov_mask).  Every one of these files includes this header, so a definition cannot drift from its declaration.
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -248,6 +248,19 @@ int sg_launch_crop_count(const void *rows, int dtype, const int64_t *frame_off, 
                          int32_t *tile_base, int64_t *out_counts, int64_t *stats_scratch, const SgFov *fov, int64_t max_tiles, void *stream);
 int sg_launch_crop_scatter(const void *rows, int dtype, const uint8_t *keep, const int64_t *frame_off, const int64_t *new_off,
                            int n_frames, const int32_t *tile_base, void *out_rows, int32_t *crop_src, int64_t max_tiles, void *stream);
+// An input keep mask for the aligned entry.  Front end: the present rows (keep_in byte != 0) of every frame compacted, stably, into crows at
+// the device-made offsets new_off[0 .. n_frames]; map = their frame-local input rows; the absent rows' keep bytes (and, out_rows != null,
+// their rows) written.  Masked finish: sg_launch_finish_aligned on the compacted batch, every row written at in_off[f] + map[.] of the input.
+int sg_launch_mask_front(const void *rows, int dtype, const uint8_t *keep_in, const int64_t *frame_off, int n_frames, void *out_rows /* null: in place */,
+                         uint8_t *out_keep, int32_t *tile_cnt, int32_t *tile_base, int64_t *counts, int64_t *new_off, void *crows, int32_t *map,
+                         int64_t max_tiles, void *stream);
+int sg_launch_finish_aligned_masked(const void *crows, const void *srows, const int32_t *frame_unsorted, int dtype, const uint32_t *rec, const uint32_t *rec_q,
+                                    const void *rng, const double *thr_poly, const int32_t *perm, const int64_t *c_off, const int64_t *in_off,
+                                    const int32_t *map, int n_frames, int32_t *tile_cnt, int32_t *tile_base, void *out_rows, uint8_t *out_keep,
+                                    int64_t *out_counts, int64_t *out_stats, const unsigned long long *diff2, const SgFov *fov, int64_t max_tiles_per_frame,
+                                    unsigned long long *tiles_done /* n_frames words, zero */, void *stream);
+// out_keep[i] = (keep_in ? keep_in[i] : 1) && the camera-FOV test of row i (out_keep may be keep_in)
+int sg_launch_fov_mask(const void *rows, int dtype, int64_t n, const uint8_t *keep_in, uint8_t *out_keep, const SgFov *fov, void *stream);
 #ifdef __cplusplus
 }
 #endif

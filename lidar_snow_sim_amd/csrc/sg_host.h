@@ -254,6 +254,10 @@ struct BatchDev {
     void *out_rows;
     int32_t *out_src;
     uint8_t *out_keep = nullptr;   // non-null: the aligned finish -- every row at its input index in out_rows (which may be `rows`), its keep flag here; out_src unused
+    // Masked aligned call (snowgpu_mask.hip): `rows` / `frame_off` are the COMPACTED batch in context scratch, n_total and max_frame only upper
+    // bounds of it; the aligned finish writes row j of compacted frame f to out_rows / out_keep at mask_in_off[f] + mask_map[frame_off[f] + j].
+    const int32_t *mask_map = nullptr;
+    const int64_t *mask_in_off = nullptr;
     int64_t *out_counts;
     int64_t *out_stats;
     double *out_thr_poly;     // may be null

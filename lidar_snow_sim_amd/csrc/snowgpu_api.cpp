@@ -4,6 +4,7 @@
 #include <dlfcn.h>
 
 #include "sg_host.h"
+#include "sg_launch.h"      // sg_tiles
 #include "sg_table_host.h"
 
 // simulation.py:106-116: R = np.round(np.linspace(0, 120 + c*tau_h, 1230), 2).
@@ -823,6 +824,106 @@ extern "C" int snowgpu_augment_wet_batch_device_aligned(snowgpu_ctx *ctx, int n_
                              d_out_flags, d_status, b.stream);
 }
 
+// ---- an input keep mask for the aligned snowfall stage (snowgpu_mask.hip) -------------------------------------------------------------
+// The snowfall stage of both masked entries, on b.stream.  Front end: the present rows of every frame are compacted, stably, into context
+// scratch (rows_crop, crop_src) at offsets made on the device (crop_off); the absent rows' keep bytes -- and, out of place, their rows --
+// are written on the way.  Then run_batch on that scratch: every kernel of the unmasked call, untouched, on the batch the caller would have
+// had to compact; n_total and max_frame are upper bounds to it, no frame-uniform shortcut.  Its last step is the masked aligned finish.
+static int masked_snow_stage(snowgpu_ctx *ctx, const char *who, BatchDev &b, const uint8_t *d_keep_in)
+{
+    const std::string name(who);
+    snowgpu_ctx *R = ctx->root ? ctx->root : ctx;
+    if (b.perm) return fail(ctx, SNOWGPU_E_INVALID, name + ": d_perm with d_keep_in; a caller's permutation indexes the rows of the frames it was made for, not the present ones");
+    // (what run_batch needs for the segment order of the pass over all rows; the linear order reads n_total as an exact count)
+    if (R->tables.size() > 65536 || b.n_frames > (1 << 22))
+        return fail(ctx, SNOWGPU_E_INVALID, name + ": a masked batch needs at most 65536 tables and 2^22 frames");
+    const size_t n = (size_t)b.n_total, esz = b.dtype == 0 ? 4 : 8;
+    const int64_t max_tiles = sg_tiles(b.max_frame);
+    ENSURE(ctx, ctx->ctile_cnt, (size_t)b.n_frames * (size_t)max_tiles + 1);
+    ENSURE(ctx, ctx->ctile_base, (size_t)b.n_frames * (size_t)max_tiles + 1);
+    ENSURE(ctx, ctx->crop_counts, (size_t)b.n_frames);
+    ENSURE(ctx, ctx->crop_off, (size_t)b.n_frames + 1);
+    ENSURE(ctx, ctx->rows_crop, n * 5 * esz);
+    ENSURE(ctx, ctx->crop_src, n);
+    int e = sg_launch_mask_front(b.rows, b.dtype, d_keep_in, b.frame_off, b.n_frames, b.out_rows == b.rows ? nullptr : b.out_rows, b.out_keep,
+                                 ctx->ctile_cnt.p, ctx->ctile_base.p, ctx->crop_counts.p, ctx->crop_off.p, ctx->rows_crop.p, ctx->crop_src.p, max_tiles, b.stream);
+    if (e) return fail(ctx, SNOWGPU_E_HIP, std::string("mask front end launch: ") + hipGetErrorString((hipError_t)e));
+    b.mask_in_off = b.frame_off; b.mask_map = ctx->crop_src.p;
+    b.rows = ctx->rows_crop.p; b.frame_off = ctx->crop_off.p; b.uniform_rows = 0;
+    return run_batch(ctx, b);
+}
+
+// snowgpu_augment_batch_device_aligned with an input keep mask: a row whose d_keep_in byte is 0 is not there.  See include/snowgpu.h.
+extern "C" int snowgpu_augment_batch_device_aligned_masked(snowgpu_ctx *ctx, int n_frames, int64_t n_total, int64_t max_frame_rows,
+                                                           const int64_t *d_frame_offsets, const void *d_rows, int dtype, const int32_t *d_table_ids,
+                                                           double beam_divergence_deg, const double *d_thr_poly, const double *d_plane,
+                                                           double noise_floor, const int32_t *d_perm, const uint8_t *d_keep_in, void *d_out_rows,
+                                                           uint8_t *d_out_keep, int64_t *d_out_counts, int64_t *d_out_stats, double *d_out_thr_poly,
+                                                           int32_t *d_status, void *stream)
+{
+    static const char *who = "snowgpu_augment_batch_device_aligned_masked";
+    if (!ctx) return SNOWGPU_E_INVALID;
+    if (!d_keep_in || n_total == 0)                  // all present: the unmasked call itself
+        return snowgpu_augment_batch_device_aligned(ctx, n_frames, n_total, max_frame_rows, d_frame_offsets, d_rows, dtype, d_table_ids, beam_divergence_deg,
+                                                    d_thr_poly, d_plane, noise_floor, d_perm, d_out_rows, d_out_keep, d_out_counts, d_out_stats, d_out_thr_poly,
+                                                    d_status, stream);
+    if (n_frames <= 0 || n_total < 0 || !d_frame_offsets || !d_rows || !d_table_ids || !d_out_rows ||
+        !d_out_keep || !d_out_counts || !d_out_stats || !d_status || (dtype != 0 && dtype != 1))
+        return fail(ctx, SNOWGPU_E_INVALID, std::string(who) + ": null pointer or bad dtype");
+    if (n_total >= ((int64_t)1 << 31)) return fail(ctx, SNOWGPU_E_INVALID, "batch too large: split it below 2^31 rows");
+    if (int rc = aligned_wet_refusals(ctx, who, n_total, dtype, d_rows, d_out_rows, d_keep_in, d_out_keep)) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    BatchDev b{};
+    b.n_frames = n_frames; b.n_total = n_total; b.max_frame = (max_frame_rows > 0 && max_frame_rows <= n_total) ? max_frame_rows : n_total;
+    b.frame_off = d_frame_offsets; b.rows = d_rows;
+    b.dtype = dtype; b.table_ids = d_table_ids; b.beam_div_deg = beam_divergence_deg; b.thr_poly = d_thr_poly;
+    b.plane = d_plane; b.noise_floor = noise_floor; b.perm = d_perm; b.out_rows = d_out_rows; b.out_src = nullptr; b.out_keep = d_out_keep;
+    b.out_counts = d_out_counts; b.out_stats = d_out_stats; b.out_thr_poly = d_out_thr_poly; b.status = d_status;
+    b.stream = stream ? (hipStream_t)stream : ctx->stream;
+    return masked_snow_stage(ctx, who, b, d_keep_in);
+}
+
+// snowgpu_augment_wet_batch_device_aligned whose snowfall stage is the masked one; the wet stage runs in place on d_out_rows / d_out_keep
+// as in the unmasked chain (absent rows carry keep 0 there: the wet stage treats them as not there, too).
+extern "C" int snowgpu_augment_wet_batch_device_aligned_masked(snowgpu_ctx *ctx, int n_frames, int64_t n_total, int64_t max_frame_rows,
+                                                               const int64_t *d_frame_offsets, const void *d_rows, int dtype,
+                                                               const int32_t *d_table_ids, double beam_divergence_deg, const double *d_thr_poly,
+                                                               const double *d_plane, double noise_floor, const int32_t *d_perm,
+                                                               const uint8_t *d_keep_in, void *d_out_rows, uint8_t *d_out_keep,
+                                                               int64_t *d_out_counts, int64_t *d_out_stats, double *d_out_thr_poly, int32_t *d_status,
+                                                               void *stream, const double *d_wet_plane, double water_height, double pavement_depth,
+                                                               double wet_noise_floor, double power_factor, int flat_earth, double delta, int replace,
+                                                               int32_t *d_out_flags)
+{
+    static const char *who = "snowgpu_augment_wet_batch_device_aligned_masked";
+    if (!ctx) return SNOWGPU_E_INVALID;
+    if (!d_keep_in || n_total == 0)
+        return snowgpu_augment_wet_batch_device_aligned(ctx, n_frames, n_total, max_frame_rows, d_frame_offsets, d_rows, dtype, d_table_ids, beam_divergence_deg,
+                                                        d_thr_poly, d_plane, noise_floor, d_perm, d_out_rows, d_out_keep, d_out_counts, d_out_stats, d_out_thr_poly,
+                                                        d_status, stream, d_wet_plane, water_height, pavement_depth, wet_noise_floor, power_factor, flat_earth,
+                                                        delta, replace, d_out_flags);
+    if (n_frames <= 0 || n_total < 0 || !d_frame_offsets || !d_rows || !d_table_ids || !d_out_rows ||
+        !d_out_keep || !d_out_counts || !d_out_stats || !d_out_flags || !d_status || (dtype != 0 && dtype != 1))
+        return fail(ctx, SNOWGPU_E_INVALID, std::string(who) + ": null pointer or bad dtype");
+    if (n_total >= ((int64_t)1 << 31)) return fail(ctx, SNOWGPU_E_INVALID, "batch too large: split it below 2^31 rows");
+    if (int rc = aligned_wet_refusals(ctx, who, n_total, dtype, d_rows, d_out_rows, d_keep_in, d_out_keep)) return rc;
+    if (!d_wet_plane && ctx->plane_par.method != SG_PLANE_REFERENCE)             // (before anything is launched)
+        return fail(ctx, SNOWGPU_E_INVALID, std::string(who) + ": a NULL wet plane needs the plane method 'reference'; 'lsq' and 'ransac' crop the rows and have no masked form: pass the plane");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    BatchDev b{};
+    b.n_frames = n_frames; b.n_total = n_total; b.max_frame = (max_frame_rows > 0 && max_frame_rows <= n_total) ? max_frame_rows : n_total;
+    b.frame_off = d_frame_offsets; b.rows = d_rows;
+    b.dtype = dtype; b.table_ids = d_table_ids; b.beam_div_deg = beam_divergence_deg; b.thr_poly = d_thr_poly;
+    b.plane = d_plane; b.noise_floor = noise_floor; b.perm = d_perm; b.out_rows = d_out_rows; b.out_src = nullptr; b.out_keep = d_out_keep;
+    b.out_counts = d_out_counts; b.out_stats = d_out_stats; b.out_thr_poly = d_out_thr_poly; b.status = d_status;
+    b.stream = stream ? (hipStream_t)stream : ctx->stream;
+    int rc = masked_snow_stage(ctx, who, b, d_keep_in);
+    if (rc) return rc;
+    return aligned_wet_stage(ctx, who, n_frames, n_total, b.max_frame, d_frame_offsets, d_out_rows, dtype, d_out_keep, d_wet_plane, water_height,
+                             pavement_depth, wet_noise_floor, power_factor, flat_earth, delta, replace, d_out_rows, d_out_keep, d_out_counts,
+                             d_out_flags, d_status, b.stream);
+}
+
 // Camera-FOV crop of augment(only_camera_fov=True) (simulation.py:39-47, :532-540): lidar_to_rect with
 // Tr_velo_to_cam (3 x 4) and R0_rect (3 x 3), rect_to_img with P2 (3 x 4), image img_h x img_w ((1024, 1920) in the
 // reference).  The crop is applied by the compaction of every later batch of this context (and num_removed counts it,
@@ -837,11 +938,9 @@ extern "C" int snowgpu_set_fov_precrop(snowgpu_ctx *ctx, int on)
     return SNOWGPU_OK;
 }
 
-extern "C" int snowgpu_set_fov(snowgpu_ctx *ctx, int enabled, const double *v2c, const double *r0, const double *p2, int img_h, int img_w)
+// the crop's matrices as the kernels take them (snowgpu_set_fov, snowgpu_fov_mask_device)
+static SgFov make_fov(const double *v2c, const double *r0, const double *p2, int img_h, int img_w)
 {
-    if (!ctx) return SNOWGPU_E_INVALID;
-    if (!enabled) { ctx->fov.enabled = 0; return SNOWGPU_OK; }
-    if (!v2c || !r0 || !p2 || img_h <= 0 || img_w <= 0) return fail(ctx, SNOWGPU_E_INVALID, "snowgpu_set_fov: need V2C, R0, P2 and an image size");
     SgFov f{};
     f.enabled = 1;
     for (int i = 0; i < 4; ++i)                      // M = V2C^T . R0^T  (4 x 3)
@@ -852,7 +951,15 @@ extern "C" int snowgpu_set_fov(snowgpu_ctx *ctx, int enabled, const double *v2c,
         }
     for (int i = 0; i < 12; ++i) f.p[i] = p2[i];
     f.img_h = img_h; f.img_w = img_w;
-    ctx->fov = f;
+    return f;
+}
+
+extern "C" int snowgpu_set_fov(snowgpu_ctx *ctx, int enabled, const double *v2c, const double *r0, const double *p2, int img_h, int img_w)
+{
+    if (!ctx) return SNOWGPU_E_INVALID;
+    if (!enabled) { ctx->fov.enabled = 0; return SNOWGPU_OK; }
+    if (!v2c || !r0 || !p2 || img_h <= 0 || img_w <= 0) return fail(ctx, SNOWGPU_E_INVALID, "snowgpu_set_fov: need V2C, R0, P2 and an image size");
+    ctx->fov = make_fov(v2c, r0, p2, img_h, img_w);
     return SNOWGPU_OK;
 }
 
@@ -890,5 +997,25 @@ extern "C" int snowgpu_set_threshold_callback(snowgpu_ctx *ctx, snowgpu_threshol
 {
     if (!ctx) return SNOWGPU_E_INVALID;
     ctx->thr_fn = fn; ctx->thr_user = fn ? user : nullptr;
+    return SNOWGPU_OK;
+}
+
+// The camera-FOV test as a producer of a keep mask: d_out_keep[i] = (d_keep_in ? d_keep_in[i] : 1) && get_fov_flag(row i), matrices and
+// image size as snowgpu_set_fov takes them (the context's own crop setting is neither read nor changed).  See include/snowgpu.h.
+extern "C" int snowgpu_fov_mask_device(snowgpu_ctx *ctx, int64_t n_total, const void *d_rows, int dtype, const double *v2c, const double *r0,
+                                       const double *p2, int img_h, int img_w, const uint8_t *d_keep_in, uint8_t *d_out_keep, void *stream)
+{
+    if (!ctx) return SNOWGPU_E_INVALID;
+    if (n_total < 0 || (n_total > 0 && (!d_rows || !d_out_keep)) || !v2c || !r0 || !p2 || img_h <= 0 || img_w <= 0 || (dtype != 0 && dtype != 1))
+        return fail(ctx, SNOWGPU_E_INVALID, "snowgpu_fov_mask_device: need rows, V2C, R0, P2, an image size and an output mask");
+    {
+        const uint8_t *k = d_keep_in, *ok = d_out_keep;
+        if (k && ok != k && ok < k + (size_t)n_total && k < ok + (size_t)n_total)
+            return fail(ctx, SNOWGPU_E_INVALID, "snowgpu_fov_mask_device: d_out_keep overlaps d_keep_in; pass d_keep_in itself or a buffer apart from it");
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const SgFov f = make_fov(v2c, r0, p2, img_h, img_w);
+    int e = sg_launch_fov_mask(d_rows, dtype, n_total, d_keep_in, d_out_keep, &f, stream ? (hipStream_t)stream : ctx->stream);
+    if (e) return fail(ctx, SNOWGPU_E_HIP, std::string("fov mask launch: ") + hipGetErrorString((hipError_t)e));
     return SNOWGPU_OK;
 }

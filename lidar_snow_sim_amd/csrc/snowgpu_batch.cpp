@@ -186,6 +186,8 @@ int run_batch(snowgpu_ctx *ctx, BatchDev &b)
     const int first_block = sg_beams_block(tiers[0]);
     const bool use_seg = !b.perm && R->tables.size() <= 65536 && b.n_frames <= (1 << 22)
                          && b.n_total < ((int64_t)1 << 31);
+    // (a masked batch knows n_total as an upper bound only; the linear order of the pass over all rows reads it as the exact count)
+    if (b.mask_map && !use_seg) return fail(ctx, SNOWGPU_E_INVALID, "a masked batch needs the segment order of the pass over all rows: at most 65536 tables and 2^22 frames");
     if (use_seg) {
         const size_t P = (size_t)b.n_frames * 256;
         ENSURE(ctx, ctx->seg_tbl_cnt, (R->tables.size() + 1) * SG_TBL_STRIDE); ENSURE(ctx, ctx->seg_tbl_base, R->tables.size() + 1);
@@ -459,6 +461,15 @@ static int launch_compaction(snowgpu_ctx *ctx, BatchDev &b, const int32_t *perm,
     hipStream_t st = b.stream;
     // small batches: the per-frame scan inside the count kernel / the aligned finish
     unsigned long long *tiles_done = b.n_total <= ((int64_t)1 << 19) ? ctx->qn.p + 3 * regions + (size_t)b.n_frames + 8 : nullptr;
+    if (b.out_keep && b.mask_map) {
+        // Masked aligned finish (k_finish_aligned_masked): it reads scratch only -- the compacted rows, their sorted copy, the records -- and
+        // writes the present rows of the caller's arrays; the front end, the one reader of the caller's rows, ran on `st` ahead of run_batch.
+        int e = sg_launch_finish_aligned_masked(b.rows, ctx->srows.p, ctx->frame_unsorted.p, b.dtype, ctx->rec.p, ctx->rec_q.p, ctx->rng.p, thr, perm, b.frame_off,
+                                                b.mask_in_off, b.mask_map, b.n_frames, ctx->ctile_cnt.p, ctx->ctile_base.p, b.out_rows, b.out_keep, b.out_counts,
+                                                b.out_stats, ctx->qn.p + 3 * regions, b.no_fov ? nullptr : &R->fov, max_tiles, tiles_done, st);
+        if (e) return fail(ctx, SNOWGPU_E_HIP, std::string("masked aligned finish launch: ") + hipGetErrorString((hipError_t)e));
+        return SNOWGPU_OK;
+    }
     if (b.out_keep) {
         // Aligned finish (k_finish_aligned).  b.out_rows may be b.rows: this is the first WRITE to the caller's rows, and every reader of them
         // is ordered ahead of it on `st` -- the sort (or the gather through a caller's permutation), the plane estimate of fuse_stats, the pass

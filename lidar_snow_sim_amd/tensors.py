@@ -13,6 +13,10 @@ The reference's training-time caller (the OpenPCDet DENSE dataset: `root_path`, 
   * `layout='aligned'` returns the rows in the INPUT's order with one keep flag per row (AlignedResult) instead of compacting them: a
     result whose shape does not depend on the data, so a consumer on the same stream -- or in the same HIP graph -- reads it without a
     host round trip, and per-point companions of the sweep (labels, timestamps, further columns) stay aligned with it.
+  * `keep=mask` with `layout='aligned'` (and on augment_wet_batch_aligned) is an INPUT keep mask: a row whose element is False is not there
+    -- cropped away, padding of an F x Nmax batch, removed by a stage in front -- and the result is, byte for byte, that of the call on the
+    frames compacted by the mask, at the present rows' own indices (snowgpu_augment_batch_device_aligned_masked).  `calib=c, pre_crop=True`
+    builds that mask on the device from the camera's view (`fov_keep`): precompute.py:96-104 without a boolean index or a host read.
   * `augment_wet_batch_aligned(frames, ...)` is the snowfall + wet-ground chain with that aligned result (AlignedWetResult: per-frame
     flags beside it; snowgpu_augment_wet_batch_device_aligned), `wet_ground_batch_aligned(frames, keep)` the wet-ground stage alone on rows
     and a keep mask from any earlier stage (snowgpu_wet_ground_batch_device_aligned).
@@ -291,10 +295,70 @@ def table_ids_for(eng, n_frames, particle_file_prefix, root_path, particles, ord
     return np.ascontiguousarray(ids[orders.reshape(-1)].reshape(n_frames, nl), np.int32)
 
 
+def _keep_mask(torch, keep, rows, offsets):
+    """One contiguous torch.bool element per row of the batch from `keep`: an N_total tensor, an F x N tensor or a list of per-frame
+    tensors, torch.bool or uint8 (non-zero = present)."""
+    n = int(offsets[-1])
+    if isinstance(keep, (list, tuple)):
+        if len(keep) != len(offsets) - 1 or any(int(k.shape[0]) != int(b - a) or k.dim() != 1 for k, a, b in zip(keep, offsets[:-1], offsets[1:])):
+            raise ValueError("keep as a list needs one 1-D tensor per frame with one element per row of it")
+        if any(k.dtype != keep[0].dtype for k in keep):
+            raise ValueError("all keep tensors of a batch must share one dtype")
+        keep = torch.cat(list(keep)) if len(keep) != 1 else keep[0]
+    if not (type(keep).__module__.startswith("torch") and getattr(keep, "is_cuda", False)) or keep.device != rows.device:
+        raise ValueError("keep must be a CUDA tensor on the device of the rows (or a list of them)")
+    if keep.dtype not in (torch.bool, torch.uint8):
+        raise ValueError("keep must be torch.bool or uint8")
+    if keep.dim() == 2:
+        keep = keep.reshape(-1)
+    if keep.dim() != 1 or keep.shape[0] != n:
+        raise ValueError("keep must have one element per row of the batch (N_total, F x N, or a list of per-frame tensors)")
+    keep = keep.contiguous()
+    return keep.view(torch.bool) if keep.dtype == torch.uint8 else keep
+
+
+def _fov_mask(torch, eng, rows, calib, img_shape, keep, run):
+    """keep AND the camera-FOV test of every row, as a new torch.bool tensor, launched on torch stream `run` (k_fov_mask)."""
+    out = torch.empty(rows.shape[0], dtype=torch.bool, device=rows.device)
+    if rows.shape[0]:
+        eng.ctx.fov_mask_device(rows.shape[0], rows.data_ptr(), 0 if rows.dtype == torch.float32 else 1, calib, img_shape,
+                                0 if keep is None else keep.data_ptr(), out.data_ptr(), run.cuda_stream)
+    return out
+
+
+def fov_keep(frames, calib, img_shape=(1024, 1920), keep=None, *, device=None, slot=0):
+    """get_fov_flag(calib.lidar_to_rect(pc[:, 0:3]), img_shape, calib) (simulation.py:39-47) for torch CUDA tensors, on the device: a
+    torch.bool mask with one element per row of the batch (frames as augment_batch takes them), ANDed with `keep` if given -- the crop of
+    precompute.py:96-99 as a keep mask for augment_batch(..., layout='aligned', keep=mask) or any other consumer.  Asynchronous on
+    torch's current stream."""
+    if not is_device_input(frames):
+        raise ValueError("fov_keep: torch CUDA tensors (host arrays: lidar_snow_sim_amd.calibration.get_fov_flag)")
+    import torch
+    from . import engine as _engine
+    rows, offsets, _ = _as_batch(torch, frames)
+    dev = rows.device
+    if device is not None and int(device) != dev.index:
+        raise ValueError(f"the tensors live on {dev}, device={device} was asked for")
+    if keep is not None:
+        keep = _keep_mask(torch, keep, rows, offsets)
+    eng = _engine.get_engine(dev.index, slot)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev)
+        run = _run_stream(torch, eng, dev, stream)
+        if run is not stream:
+            run.wait_stream(stream)
+        try:
+            out = _fov_mask(torch, eng, rows[:int(offsets[-1])], calib, img_shape, keep, run)
+        finally:
+            if run is not stream:
+                stream.wait_stream(run)
+    return out
+
+
 def augment_batch(frames, particle_file_prefix, beam_divergence, shuffle=True, noise_floor=0.7, root_path=None, *, planes=None,
                   orders=None, particles=None, thr_polys=None, device=None, return_src=False, slot=0, calib=None, pre_crop=False,
                   q8='first', plane_method='reference', plane_seed=0, plane_trials=1000, sync=True, wet=None, out=None, lane=None,
-                  layout='compact', in_place=False, **_ignored):
+                  layout='compact', in_place=False, keep=None, **_ignored):
     """augment_batch() of tools/snowfall/simulation.py for torch CUDA tensors (see that docstring for the shared arguments).
 
     frames   a list of N_i x 5 CUDA tensors (concatenated on the device), an F x N x 5 tensor, one N x 5 tensor, or a DeviceBatch
@@ -329,13 +393,26 @@ def augment_batch(frames, particle_file_prefix, beam_divergence, shuffle=True, n
     in_place with layout='aligned': the result's `rows` IS the input tensor, overwritten by its augmented form.  The input must be
              read where it lies -- a DeviceBatch, one contiguous N x 5 tensor or an F x N x 5 tensor; a list that would have to be
              concatenated raises ValueError (the result would land in a temporary).
+    keep     with layout='aligned': an INPUT keep mask -- a torch.bool (or uint8) CUDA tensor with one element per row of the batch, an
+             F x N tensor, or a list of per-frame tensors; False = the row is not there.  With P the present rows of a frame in input
+             order, rows_f[P] / keep_f[P] and the statistics are, byte for byte, those of the call on frame[P]; an absent row comes
+             back as it came with keep False and is never looked at (NaNs, far ranges, channels that are no laser do no harm there).
+             Nothing is compacted as the caller sees it and nothing is read on the host (snowgpu_augment_batch_device_aligned_masked):
+             the call stays capturable.  A padded F x Nmax x 5 batch: keep = torch.arange(Nmax, device=...) < lengths[:, None].
+             Not with the compact layout (ValueError), not with a caller's permutation.
+    pre_crop with layout='aligned' and calib: the frames are cropped to the camera's view BEFORE they are augmented (precompute.py:96-104)
+             -- as a keep mask built on the device (fov_keep), ANDed with `keep` if given; the camera crop of the result stays set as
+             well, as in the host entry.  The compact layout raises: its pre-crop is a step of the host entry.
     """
     import torch
     from . import engine as _engine
     if q8 != 'first':
         raise ValueError("q8='numpy' selects the histogram minima with the HOST's NumPy: it needs host arrays, not CUDA tensors")
-    if calib is not None and pre_crop:
-        raise ValueError("pre_crop is a step of the host entry (precompute.py:96-99); crop the tensors before the call")
+    if calib is not None and pre_crop and layout != 'aligned':
+        raise ValueError("pre_crop is a step of the host entry (precompute.py:96-99); crop the tensors before the call, or use "
+                         "layout='aligned', which crops by a keep mask on the device")
+    if keep is not None and layout != 'aligned':
+        raise ValueError("keep= is an input mask of layout='aligned': the compact layout returns compacted frames; index them before the call")
     if plane_method not in _native.PLANE_METHODS:
         raise ValueError("plane_method must be 'reference', 'lsq' or 'ransac'")
     if layout not in ('compact', 'aligned'):
@@ -365,6 +442,8 @@ def augment_batch(frames, particle_file_prefix, beam_divergence, shuffle=True, n
     nf, n = len(offsets) - 1, int(offsets[-1])
     if nf == 0:
         return []
+    if keep is not None:
+        keep = _keep_mask(torch, keep, rows, offsets)
     code = 0 if rows.dtype == torch.float32 else 1
     max_rows = int(np.diff(offsets).max())
     up = _uploads(eng)
@@ -434,18 +513,27 @@ def augment_batch(frames, particle_file_prefix, beam_divergence, shuffle=True, n
         if run is not stream:
             run.wait_stream(stream)
             if lane is not None:                    # (tensors of the caller's stream used on the lane's: the allocator must know)
-                for t in (rows, o_rows, o_src, o_keep, o_cnt, o_st, o_status, o_flags):
+                for t in (rows, o_rows, o_src, o_keep, o_cnt, o_st, o_status, o_flags, keep):
                     if t is not None:
                         t.record_stream(run)
         ptr = lambda t: 0 if t is None else t.data_ptr()   # noqa: E731
         with eng.batch_lock:
             if calib is not None:
                 eng.ctx.set_fov(calib, (1024, 1920))                                # simulation.py:536
+                if pre_crop:                                                        # precompute.py:96-99, as a mask
+                    keep = _fov_mask(torch, eng, rows[:n], calib, (1024, 1920), keep, run)
+                    if lane is not None:
+                        keep.record_stream(run)
             device_plane = d_poly is None and d_plane is None                       # calculate_plane (simulation.py:449) on the device
             if device_plane or (wet is not None and d_wet_plane is None):
                 eng.ctx.set_plane_method(plane_method, seed=plane_seed, trials=plane_trials, min_rows=5)
             try:
-                if aligned:
+                if aligned and keep is not None:
+                    eng.ctx.augment_batch_device_aligned_masked(nf, n, max_rows, d_off.data_ptr(), rows.data_ptr(), code, d_tids.data_ptr(),
+                                                                float(beam_divergence), ptr(d_poly), ptr(d_plane), float(noise_floor), 0, keep.data_ptr(),
+                                                                o_rows.data_ptr(), o_keep.data_ptr(), o_cnt.data_ptr(), o_st.data_ptr(), 0,
+                                                                o_status.data_ptr(), run.cuda_stream)
+                elif aligned:
                     eng.ctx.augment_batch_device_aligned(nf, n, max_rows, d_off.data_ptr(), rows.data_ptr(), code, d_tids.data_ptr(),
                                                          float(beam_divergence), ptr(d_poly), ptr(d_plane), float(noise_floor), 0, o_rows.data_ptr(),
                                                          o_keep.data_ptr(), o_cnt.data_ptr(), o_st.data_ptr(), 0, o_status.data_ptr(), run.cuda_stream)
@@ -475,7 +563,7 @@ def augment_batch(frames, particle_file_prefix, beam_divergence, shuffle=True, n
                 if plane_method != 'reference':
                     eng.ctx.set_plane_method('reference')
     if aligned:
-        res = AlignedResult(eng.ctx, o_rows, o_keep, o_cnt, o_st, o_status, offsets, stream if lane is None else run, keep=(rows, d_off, d_tids, d_poly, d_plane))
+        res = AlignedResult(eng.ctx, o_rows, o_keep, o_cnt, o_st, o_status, offsets, stream if lane is None else run, keep=(rows, d_off, d_tids, d_poly, d_plane, keep))
         return res.frames() if sync else res
     res = DeviceResult(eng.ctx, o_rows, o_src, o_cnt, o_st, o_status, offsets, stream if lane is None else run, flags=o_flags, keep=(rows, d_off, d_tids, d_poly, d_plane, d_wet_plane))
     if not sync:
@@ -610,7 +698,7 @@ def wet_ground_batch_aligned(frames, keep=None, *, plane=None, water_height=0.00
 
 def augment_wet_batch_aligned(frames, particle_file_prefix, beam_divergence, shuffle=True, noise_floor=0.7, root_path=None, *, wet=None,
                               planes=None, orders=None, particles=None, thr_polys=None, device=None, slot=0, calib=None, sync=True,
-                              out=None, lane=None, in_place=False, **_ignored):
+                              out=None, lane=None, in_place=False, keep=None, pre_crop=False, **_ignored):
     """augment() followed by ground_water_augmentation() on its output (pointcloud_viewer.py:2807-2821) for torch CUDA tensors with the
     ALIGNED result (snowgpu_augment_wet_batch_device_aligned): the snowfall stage finishes into rows in the input's order plus a keep
     mask, and the wet-ground stage rewrites those two arrays in place, skipping the rows the snowfall stage removed.  No compaction, a
@@ -619,6 +707,8 @@ def augment_wet_batch_aligned(frames, particle_file_prefix, beam_divergence, shu
     wet       dict of ground_water_augmentation()'s keyword arguments (water_height, pavement_depth, noise_floor, power_factor, flat_earth,
               delta, replace, plane, estimation_method, poly_seed); plane=None: the flat-earth plane the reference returns today.
     planes, thr_polys, orders, particles, calib, in_place, sync, out (an earlier AlignedWetResult), lane: as augment_batch(layout='aligned').
+    keep, pre_crop  as augment_batch(layout='aligned'): an input keep mask for the snowfall stage (and the camera's view as one).  The
+              result equals the masked snowfall call followed by wet_ground_batch_aligned(rows, keep) on its result.
     Returns an AlignedWetResult (sync=False) or its frames(): [(stats, rows_f, keep_f, flag_f)] -- stats the snowfall statistics,
     keep_f true where the CHAIN returns the row, flag_f = 1 where the wet stage found fewer than 1000 present ground rows and left the
     frame as the snowfall stage made it.
@@ -647,6 +737,8 @@ def augment_wet_batch_aligned(frames, particle_file_prefix, beam_divergence, shu
         return []
     if n == 0:
         return _empty_aligned_wet(torch, eng, rows, nf, offsets, True, sync)
+    if keep is not None:
+        keep = _keep_mask(torch, keep, rows, offsets)
     code = 0 if rows.dtype == torch.float32 else 1
     up = _uploads(eng)
     with torch.cuda.device(dev):
@@ -665,18 +757,22 @@ def augment_wet_batch_aligned(frames, particle_file_prefix, beam_divergence, shu
         if run is not stream:
             run.wait_stream(stream)
             if lane is not None:                    # (tensors of the caller's stream used on the lane's: the allocator must know)
-                for t in (rows, o_rows, o_keep, o_cnt, o_st, o_status, o_flags):
+                for t in (rows, o_rows, o_keep, o_cnt, o_st, o_status, o_flags) + (() if keep is None else (keep,)):
                     t.record_stream(run)
         ptr = lambda t: 0 if t is None else t.data_ptr()   # noqa: E731
         with eng.batch_lock:
             if calib is not None:
                 eng.ctx.set_fov(calib, (1024, 1920))
+                if pre_crop:                                                        # precompute.py:96-99, as a mask
+                    keep = _fov_mask(torch, eng, rows[:n], calib, (1024, 1920), keep, run)
+                    if lane is not None:
+                        keep.record_stream(run)
             if method != 'linear':
                 eng.ctx.set_wet_estimation(method, seed)
             try:
-                eng.ctx.augment_wet_batch_device_aligned(nf, n, int(np.diff(offsets).max()), d_off.data_ptr(), rows.data_ptr(), code,
+                eng.ctx.augment_wet_batch_device_aligned_masked(nf, n, int(np.diff(offsets).max()), d_off.data_ptr(), rows.data_ptr(), code,
                                                          d_tids.data_ptr(), float(beam_divergence), ptr(d_poly), ptr(d_plane),
-                                                         float(noise_floor), 0, o_rows.data_ptr(), o_keep.data_ptr(), o_cnt.data_ptr(),
+                                                         float(noise_floor), 0, ptr(keep), o_rows.data_ptr(), o_keep.data_ptr(), o_cnt.data_ptr(),
                                                          o_st.data_ptr(), 0, o_status.data_ptr(), run.cuda_stream, ptr(d_wet_plane),
                                                          w["water_height"], w["pavement_depth"], w["noise_floor"], w["power_factor"],
                                                          w["flat_earth"], w["delta"], w["replace"], o_flags.data_ptr())
@@ -688,5 +784,5 @@ def augment_wet_batch_aligned(frames, particle_file_prefix, beam_divergence, shu
                 if method != 'linear':
                     eng.ctx.set_wet_estimation('linear')
     res = AlignedWetResult(eng.ctx, o_rows, o_keep, o_cnt, o_st, o_status, offsets, stream if lane is None else run, o_flags,
-                           keep=(rows, d_off, d_tids, d_poly, d_plane, d_wet_plane))
+                           keep=(rows, d_off, d_tids, d_poly, d_plane, d_wet_plane, keep))
     return res.frames() if sync else res

@@ -174,7 +174,8 @@ def augment_batch(frames: Sequence[np.ndarray], particle_file_prefix: str, beam_
     torch CUDA tensors (a list of N_i x 5 tensors, an F x N x 5 tensor, or a lidar_snow_sim_amd.tensors.DeviceBatch) take the
     device-resident boundary instead: rows are read where they lie, the call runs on torch's current stream, aug_pc / src come back
     as device tensors and no row crosses the link (lidar_snow_sim_amd/tensors.py, which also documents sync=False, wet=... and
-    layout='aligned' / in_place=True: the rows in the input's order with a keep mask instead of compacted rows).
+    layout='aligned' / in_place=True: the rows in the input's order with a keep mask instead of compacted rows; with that layout keep=mask
+    is an INPUT keep mask -- rows that are not there -- and calib= with pre_crop=True crops by such a mask, built on the device).
     """
     from ... import tensors as _tensors
     if _tensors.is_device_input(frames):
