@@ -19,6 +19,7 @@
 #pragma once
 #include "sg_math.h"
 #include "sg_atan_cr.h"
+#include "sg_range_index.h"
 
 // A pointer that was itself read from memory (the members of an SgTable) is a GENERIC pointer to the compiler: loads through it are
 // flat_load, which count on the LDS counter as well as on the memory counter -- so every wait for a cross-lane read or an LDS list
@@ -417,6 +418,20 @@ __device__ __forceinline__ void sg_hit_angles_all(const uint32_t (&w)[N], int L,
 #endif
 }
 
+// Two neighbouring words of the step-major range index (sg_range_index.h) as ONE load.  The address is 4-byte aligned only, which a
+// global load of 8 bytes allows.
+struct SgQsPair { uint32_t x, y; };
+#if defined(__HIP_DEVICE_COMPILE__)
+typedef unsigned int SgQsRaw __attribute__((ext_vector_type(2), aligned(4)));
+__device__ __forceinline__ SgQsPair sg_qs_load(const SG_GLOBAL uint32_t *p)
+{
+    const SgQsRaw v = *reinterpret_cast<const SG_GLOBAL SgQsRaw *>(p);
+    return SgQsPair{v.x, v.y};
+}
+#else
+__device__ __forceinline__ SgQsPair sg_qs_load(const uint32_t *p) { return SgQsPair{p[0], p[1]}; }
+#endif
+
 // ---- the same scan, one WAVE for its 64 beams ---------------------------------------------------------------------------
 // A beam tests every record of its bins that is nearer than its target -- a handful for a ground return, dozens for a far
 // wall -- and with one beam per lane a wave is as slow as its farthest beam (SQ counters: 45 % of the lanes active).  Here the
@@ -459,30 +474,41 @@ __device__ __forceinline__ int sg_wave_scan(bool act, T px, T py, T pz, const Sg
         const int b_nx = (b_lo + 1 == nb) ? 0 : b_lo + 1;
         const SG_GLOBAL uint32_t *g_start = sg_gptr(tab.bin_start);
         const SG_GLOBAL SgEntry *g_ent = sg_gptr(tab.entries);
-        // Bin starts and the coarse range index: EIGHT independent loads, every one issued before the first is used -- no load
-        // under a condition of its own (the compiler kept such a load behind a wait for the earlier ones: bin starts, then the
-        // second bin's end, then the index -- three round trips where the addresses need none of the loaded values).
-        const uint32_t s0 = g_start[b_lo], s0e = g_start[b_lo + 1], s1 = g_start[b_nx], s1e = g_start[b_nx + 1];
-        const bool has_q = tab.bin_q != nullptr;
-        uint32_t c0 = 0, c1 = 0, u0 = 0, u1 = 0;
-        int kk = 0;
-        if (has_q) {       // the coarse range index brackets the prefix (counts below the multiples of SG_QSTEP_M around d): the search
-            // below then looks at the one or two records in between instead of halving the whole bin
-            const double dq = g.d * (1.0 / SG_QSTEP_M);
-            kk = dq < (double)(SG_QSTEPS - 1) ? (int)dq : SG_QSTEPS - 1;
-            const int k1 = kk < SG_QSTEPS - 1 ? kk + 1 : kk;      // (the last step has no upper count: its load repeats the lower one)
-            const SG_GLOBAL uint32_t *q0 = sg_gptr(tab.bin_q) + (size_t)b_lo * SG_QSTEPS, *q1 = sg_gptr(tab.bin_q) + (size_t)b_nx * SG_QSTEPS;
-            c0 = q0[kk]; u0 = q0[k1]; c1 = q1[kk]; u1 = q1[k1];
-        }
+        // The coarse range index brackets the prefix (counts below the multiples of SG_QSTEP_M around d): the search below then looks at
+        // the one or two records in between instead of halving the whole bin.  Step of the target's range (a NaN lands in the last):
+        const double dq = g.d * (1.0 / SG_QSTEP_M);
+        const int kk = dq < (double)(SG_QSTEPS - 1) ? (int)dq : SG_QSTEPS - 1;
+        const uint32_t s0 = g_start[b_lo], s1 = g_start[b_nx];
         st0 = s0; st2 = s1;
-        uint32_t hi0 = s0e, hi1 = span >= 1 ? s1e : s1;
-        uint32_t lo0 = st0, lo1 = st2;                          // records with rho < d: a prefix of each (sorted) bin
-        if (has_q) {
-            lo0 = st0 + c0;
-            if (kk < SG_QSTEPS - 1) hi0 = st0 + u0;
-            if (span >= 1) { lo1 = st2 + c1; if (kk < SG_QSTEPS - 1) hi1 = st2 + u1; }
-            if (!(g.d == g.d)) { lo0 = hi0 = st0; lo1 = hi1 = st2; }      // NaN target: no record is nearer
+        uint32_t lo0 = st0, lo1 = st2, hi0, hi1;               // records with rho < d: a prefix of each (sorted) bin
+        if (tab.bin_qs != nullptr) {
+            // Step-major index (sg_range_index.h): ONE 8-byte load returns lower | upper count of this step for bin b_lo and for the bin
+            // after it (the row's last word is bin 0 again) -- and the lanes of a wave, beams of neighbouring azimuth, share its lines.
+            // The upper count of the last step is the bin's length: neither the bins' ends nor a special case for that step.
+            const SgQsPair w = sg_qs_load(sg_gptr(tab.bin_qs) + (size_t)kk * SG_QS_ROW(nb) + b_lo);
+            lo0 = st0 + (w.x & 0xffffu); hi0 = st0 + (w.x >> 16);
+            hi1 = st2;
+            if (span >= 1) { lo1 = st2 + (w.y & 0xffffu); hi1 = st2 + (w.y >> 16); }
+        } else {
+            // Bin-major index or none (a table with a bin too long for 16-bit counts; a hand-made table): the bins' ends and four dword
+            // loads, every one issued before the first is used -- no load under a condition of its own (the compiler kept such a load
+            // behind a wait for the earlier ones).
+            const uint32_t s0e = g_start[b_lo + 1], s1e = g_start[b_nx + 1];
+            const bool has_q = tab.bin_q != nullptr;
+            uint32_t c0 = 0, c1 = 0, u0 = 0, u1 = 0;
+            if (has_q) {
+                const int k1 = kk < SG_QSTEPS - 1 ? kk + 1 : kk;      // (the last step has no upper count: its load repeats the lower one)
+                const SG_GLOBAL uint32_t *q0 = sg_gptr(tab.bin_q) + (size_t)b_lo * SG_QSTEPS, *q1 = sg_gptr(tab.bin_q) + (size_t)b_nx * SG_QSTEPS;
+                c0 = q0[kk]; u0 = q0[k1]; c1 = q1[kk]; u1 = q1[k1];
+            }
+            hi0 = s0e; hi1 = span >= 1 ? s1e : s1;
+            if (has_q) {
+                lo0 = st0 + c0;
+                if (kk < SG_QSTEPS - 1) hi0 = st0 + u0;
+                if (span >= 1) { lo1 = st2 + c1; if (kk < SG_QSTEPS - 1) hi1 = st2 + u1; }
+            }
         }
+        if (!(g.d == g.d)) { lo0 = hi0 = st0; lo1 = hi1 = st2; }          // NaN target: no record is nearer
         while (lo0 < hi0 || lo1 < hi1) {
             const uint32_t m0 = (lo0 + hi0) >> 1, m1 = (lo1 + hi1) >> 1;
             const double r0 = lo0 < hi0 ? g_ent[m0].rho : 0.0, r1 = lo1 < hi1 ? g_ent[m1].rho : 0.0;

@@ -46,6 +46,7 @@ struct SgTable {
     double inv_bin_w;           // n_bins / (2 pi)
     uint32_t n_flakes;
     uint32_t max_bin;           // longest bin (entries)
+    const uint32_t *bin_qs;     // SG_QSTEPS x (n_bins + 1): the same counts step-major, two to a word (sg_range_index.h), or null -- bin_q alone is used
 };
 
 struct SgLasers {

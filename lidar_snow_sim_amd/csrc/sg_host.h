@@ -27,6 +27,7 @@ struct DeviceTable {
     SgEntry *entries = nullptr;
     uint32_t *bin_start = nullptr;
     uint32_t *bin_q = nullptr;
+    uint32_t *bin_qs = nullptr;          // step-major twin of bin_q (sg_range_index.h), or null: a bin too long for its 16-bit counts
     SgTable desc{};
 };
 
@@ -284,7 +285,7 @@ int node_of_device(int device);                               // snowgpu_host.cp
 #pragma GCC visibility pop
 
 // snowgpu_tables.hip, snowgpu_sampler.hip
-extern "C" int sg_table_index(const SgEntry *entries, const uint32_t *start, uint32_t *q, void *stream);
+extern "C" int sg_table_index(const SgEntry *entries, const uint32_t *start, uint32_t *q, uint32_t *qs /* or null */, void *stream);
 extern "C" int sg_file_table_stage_a(const double *d_xyr, int64_t k, SgEntry *fl, int32_t *b0, int32_t *span, uint32_t *count,
                                      uint32_t *start, uint32_t *fill, int32_t *misc, void *stream);
 extern "C" int sg_file_table_stage_b(int64_t k, const SgEntry *fl, const int32_t *b0, const int32_t *span, const uint32_t *start,

@@ -6,6 +6,7 @@
 #include "sg_host.h"
 #include "sg_launch.h"      // sg_tiles
 #include "sg_table_host.h"
+#include "sg_range_index.h"  // SG_QS_FITS, SG_QS_WORDS
 
 // simulation.py:106-116: R = np.round(np.linspace(0, 120 + c*tau_h, 1230), 2).
 // linspace: k * step (+ 0.0), last element = stop; round(., 2): rint(v * 100) / 100.
@@ -118,6 +119,7 @@ extern "C" void snowgpu_destroy(snowgpu_ctx *ctx)
         if (t.entries) (void)hipFree(t.entries);
         if (t.bin_start) (void)hipFree(t.bin_start);
         if (t.bin_q) (void)hipFree(t.bin_q);
+        if (t.bin_qs) (void)hipFree(t.bin_qs);
     }
     if (ctx->d_tables) (void)hipFree(ctx->d_tables);
     if (ctx->d_las) (void)hipFree(ctx->d_las);
@@ -179,23 +181,30 @@ static int register_table(snowgpu_ctx *ctx, int table_id, SgEntry *entries, uint
     if (dt.entries) (void)hipFree(dt.entries);
     if (dt.bin_start) (void)hipFree(dt.bin_start);
     if (dt.bin_q) (void)hipFree(dt.bin_q);
-    dt.entries = entries; dt.bin_start = bin_start; dt.bin_q = nullptr;
+    if (dt.bin_qs) (void)hipFree(dt.bin_qs);
+    dt.entries = entries; dt.bin_start = bin_start; dt.bin_q = nullptr; dt.bin_qs = nullptr;
     dt.desc = SgTable{};
     ctx->tables_dirty = true;
-    uint32_t *q = nullptr;
+    uint32_t *q = nullptr, *qs = nullptr;
     int e = (int)hipMalloc((void **)&q, (size_t)SG_NBINS * SG_QSTEPS * sizeof(uint32_t));
-    if (!e) e = sg_table_index(entries, bin_start, q, ctx->stream);
+    // the step-major index packs two counts into a word: only for tables whose longest bin fits 16 bits (the scan then reads bin_q)
+    if (!e && SG_QS_FITS(max_bin)) e = (int)hipMalloc((void **)&qs, SG_QS_WORDS(SG_NBINS) * sizeof(uint32_t));
+    if (!e) e = sg_table_index(entries, bin_start, q, qs, ctx->stream);
     if (!e) e = (int)hipStreamSynchronize(ctx->stream);
     if (e) {
         if (q) (void)hipFree(q);
+        if (qs) (void)hipFree(qs);
         (void)hipFree(entries); (void)hipFree(bin_start);
         dt.entries = nullptr; dt.bin_start = nullptr;
         return fail(ctx, SNOWGPU_E_HIP, std::string("table index: ") + hipGetErrorString((hipError_t)e));
     }
-    dt.bin_q = q;
+    dt.bin_q = q; dt.bin_qs = qs;
     dt.desc.entries = entries;
     dt.desc.bin_start = bin_start;
     dt.desc.bin_q = q;
+    dt.desc.bin_qs = qs;
+    // must stay SG_NBINS: bin_q and bin_qs above are sized, and filed by k_table_index, with that constant, and the scan takes the row
+    // stride of bin_qs from n_bins (SG_QS_ROW(n_bins)) -- a descriptor with another n_bins would read past the arrays
     dt.desc.n_bins = (uint32_t)SG_NBINS;
     dt.desc.n_entries = n_entries;
     dt.desc.inv_bin_w = SG_NBINS / SG_TWO_PI;
@@ -324,6 +333,7 @@ extern "C" int snowgpu_free_table(snowgpu_ctx *ctx, int table_id)
     if (dt.entries) { (void)hipFree(dt.entries); dt.entries = nullptr; }
     if (dt.bin_start) { (void)hipFree(dt.bin_start); dt.bin_start = nullptr; }
     if (dt.bin_q) { (void)hipFree(dt.bin_q); dt.bin_q = nullptr; }
+    if (dt.bin_qs) { (void)hipFree(dt.bin_qs); dt.bin_qs = nullptr; }
     dt.desc = SgTable{};
     ctx->tables_dirty = true;
     return SNOWGPU_OK;

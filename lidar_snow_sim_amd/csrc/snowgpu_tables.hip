@@ -16,6 +16,7 @@
 #include <stdint.h>
 #include "sg_common.h"
 #include "sg_atan_cr.h"
+#include "sg_range_index.h"
 #include "sg_launch.h"
 
 #define TB 256
@@ -160,21 +161,15 @@ __global__ __launch_bounds__(64) void k_file_sort(const uint32_t *__restrict__ s
     }
 }
 
-// Coarse range index of a filed table: q[b][k] = records of bin b nearer than SG_QSTEP_M * k metres.  The scan pass starts
-// its search for "records nearer than the target" from the two entries around the target's range instead of the whole bin.
+// Coarse range index of a filed table, both layouts (sg_range_index.h): q[b][k] = records of bin b nearer than SG_QSTEP_M * k metres, and
+// the same counts step-major and paired (qs, or null).  The scan pass starts its search for "records nearer than the target" from the
+// two counts around the target's range instead of the whole bin.
 __global__ __launch_bounds__(64) void k_table_index(const SgEntry *__restrict__ entries, const uint32_t *__restrict__ start,
-                                                    uint32_t *__restrict__ q)
+                                                    uint32_t *__restrict__ q, uint32_t *__restrict__ qs)
 {
     const int b = blockIdx.x, k = threadIdx.x;
     if (k >= SG_QSTEPS) return;
-    const uint32_t e0 = start[b];
-    uint32_t lo = e0, hi = start[b + 1];
-    const double lim = SG_QSTEP_M * (double)k;
-    while (lo < hi) {
-        const uint32_t m = (lo + hi) >> 1;
-        if (entries[m].rho < lim) lo = m + 1; else hi = m;
-    }
-    q[b * SG_QSTEPS + k] = lo - e0;
+    sg_range_index_fill(entries, start, SG_NBINS, b, k, q, qs);
 }
 
 // per-flake quantities of a filed table by table row (debug tap): the copy filed under the flake's first bin
@@ -220,9 +215,9 @@ extern "C" int sg_file_table_stage_b(int64_t k, const SgEntry *fl, const int32_t
     return 0;
 }
 
-extern "C" int sg_table_index(const SgEntry *entries, const uint32_t *start, uint32_t *q, void *stream)
+extern "C" int sg_table_index(const SgEntry *entries, const uint32_t *start, uint32_t *q, uint32_t *qs /* or null */, void *stream)
 {
-    hipLaunchKernelGGL(k_table_index, dim3(SG_NBINS), dim3(64), 0, (hipStream_t)stream, entries, start, q);
+    hipLaunchKernelGGL(k_table_index, dim3(SG_NBINS), dim3(64), 0, (hipStream_t)stream, entries, start, q, qs);
     SG_CHECK_LAUNCH();
     return 0;
 }
