@@ -585,6 +585,78 @@ int snowgpu_augment_wet_batch_device_aligned_masked(snowgpu_ctx *ctx, int n_fram
 int snowgpu_fov_mask_device(snowgpu_ctx *ctx, int64_t n_total, const void *d_rows, int dtype, const double *v2c, const double *r0,
                             const double *p2, int img_h, int img_w, const uint8_t *d_keep_in /* or NULL */, uint8_t *d_out_keep, void *stream);
 
+/*
+ * PER-FRAME WEATHER in one aligned call.  snowgpu_augment_wet_batch_device_aligned_masked applies one weather to every frame, its wet
+ * settings host scalars that a captured graph bakes in.  Here every frame brings a record of 8 doubles in DEVICE memory,
+ *     d_weather[f] = [snow, wet, water_height, pavement_depth, wet_noise_floor, power_factor, delta, 0]
+ * snow and wet are the frame's gates, 0.0 or 1.0 -- anything else is UNDEFINED (the kernels only promise that +-0.0 is off); the five
+ * values after them replace the wet scalars of the masked chain.  flat_earth, replace, the beam divergence and the snowfall stage's
+ * noise_floor stay per call.  Arguments: those of snowgpu_augment_wet_batch_device_aligned_masked with d_weather (n_frames x 8) in place
+ * of the five wet doubles.  d_keep_in may be NULL (all rows present); d_weather NULL is SNOWGPU_E_INVALID; d_perm must be NULL.
+ *
+ * Frame f comes back, byte for byte -- rows, keep bytes, counts, statistics, d_out_thr_poly row and flag -- as an existing entry called
+ * on the same batch (same d_keep_in, tables, planes, polynomials, camera crop) with frame f's values as its scalars returns it:
+ *   snow wet   frame f equals                                                                              d_out_flags[f]
+ *    1    1    snowgpu_augment_wet_batch_device_aligned_masked                                             its flag (0 or 1)
+ *    1    0    snowgpu_augment_batch_device_aligned_masked; d_out_counts[f] = keep bytes set               2
+ *    0    1    snowgpu_wet_ground_batch_device_aligned on the input rows and d_keep_in; statistics (0, 0, 0)
+ *              and polynomial row as the masked entry returns them for a frame with no present row          its flag
+ *    0    0    every row bit for bit, keep = d_keep_in (1 if NULL), counts = present rows, statistics (0, 0, 0)   2
+ * Flag 2 is "wet stage not asked"; flag 1 keeps its meaning (asked, fewer than 1000 present ground rows).
+ * A frame with snow = 0 and wet = 0 is never looked at, as an absent row is not: NaN, a range beyond the grid or a channel that is no
+ * laser set no status word there.  A frame with snow = 0 is never looked at by the snowfall stage: SNOWGPU_E_GROUND of the device
+ * prepass can only come from snow = 1 frames.  Out of place (d_out_rows != d_rows) the rows of a gated frame are copied; in place with
+ * d_out_keep == d_keep_in nothing of it is touched.
+ *
+ * How: the snow gate joins the input mask in the masked front end -- a frame left out reaches the per-beam kernels as an empty frame and
+ * costs them nothing, its keep bytes are written as they came --, the wet kernels read their settings from the frame's record, and a
+ * frame whose wet gate is off takes the path of a frame with too few ground rows, without its rows being read.  Because the gates are
+ * device data the host cannot know that every frame is on: an all-on batch without a mask pays the masked front end too (one more copy
+ * of the rows and three small kernels) that snowgpu_augment_wet_batch_device_aligned does not.
+ * The wet stage honours snowgpu_set_wet_estimation ('poly' draws are keyed by the frame's index in the batch, which a gate does not
+ * change) and snowgpu_set_wet_lines, and keeps the NULL-wet-plane rule of the chain.  The contract is the device entries': asynchronous
+ * on `stream`, no allocation after the first call of a size, no host read, capturable into a HIP graph.  It refuses what the aligned
+ * entries refuse.
+ */
+int snowgpu_augment_weather_batch_device_aligned(snowgpu_ctx *ctx, int n_frames, int64_t n_total, int64_t max_frame_rows,
+                                                 const int64_t *d_frame_offsets, const void *d_rows, int dtype,
+                                                 const int32_t *d_table_ids, double beam_divergence_deg, const double *d_thr_poly,
+                                                 const double *d_plane, double noise_floor, const int32_t *d_perm /* NULL */,
+                                                 const uint8_t *d_keep_in /* NULL: all present */, void *d_out_rows, uint8_t *d_out_keep,
+                                                 int64_t *d_out_counts, int64_t *d_out_stats, double *d_out_thr_poly, int32_t *d_status,
+                                                 void *stream, const double *d_wet_plane, const double *d_weather /* n_frames x 8 */,
+                                                 int flat_earth, int replace, int32_t *d_out_flags);
+
+/*
+ * The draw of those records -- and of every frame's table ids -- on the device: what a training loader does per sample (the reference's
+ * production loop runs five (rate, velocity) pairs times two modes, precompute.py:20-21, :70-104; its viewer varies the wet settings,
+ * pointcloud_viewer.py:2814-2821) as one small kernel, one wave per frame.  Asynchronous on `stream` and capturable; the step is read
+ * from DEVICE memory, so a replayed graph that also holds a `step += 1` draws anew on every replay.
+ *   d_set_ids    n_sets x n_lasers table ids (snowgpu_upload_table): set s is one snowfall setting, one table per laser
+ *   plan         HOST memory, read during the call: the gates' probabilities, the choices of water height and pavement depth, the three
+ *                wet settings every frame shares, and whether the tables of the set are shuffled over the lasers (simulation.py:78, :482-486)
+ *   d_table_ids  n_frames x n_lasers;   d_weather  n_frames x 8 (see above)
+ * Limits: n_sets <= 64, n_lasers <= 128, n_frames <= 2^22, 1 <= n_water, n_pave <= 16, probabilities in [0, 1]; else SNOWGPU_E_INVALID.
+ * With W(b) the four words of Philox4x32-10 under key `seed` at counter (step, frame f, 0x57544852 + b):
+ *   block 0       snow = w0 < T(p_snow), wet = w1 < T(p_wet) with T(p) = min(2^32, floor(p 2^32)): 0 is never, 1 is always;
+ *                 set = (w2 n_sets) >> 32; water index = (w3 n_water) >> 32
+ *   block 1       pavement index = (w0 n_pave) >> 32
+ *   permutation   order = 0 .. L-1; for i = L-1 down to 1, k = L-1-i: r = word k % 4 of block 2 + k / 4, j = (r (i + 1)) >> 32, swap
+ *                 order[i], order[j]; shuffle = 0: the identity.  d_table_ids[f][c] = d_set_ids[set][order[c]]
+ * Every draw is made whether or not its gate is on: a gate never shifts another frame's or another field's draw.  The stream is Philox,
+ * not Python's random: parity with the reference's own shuffle is distributional.
+ */
+typedef struct snowgpu_weather_plan {
+    double p_snow, p_wet;
+    int32_t n_water, n_pave;
+    double water_heights[16], pavement_depths[16];
+    double wet_noise_floor, power_factor, delta;
+    int32_t shuffle;
+} snowgpu_weather_plan;
+int snowgpu_draw_weather_device(snowgpu_ctx *ctx, int n_frames, int n_lasers, int n_sets, const int32_t *d_set_ids /* n_sets x n_lasers */,
+                                const snowgpu_weather_plan *plan /* host */, uint64_t seed, const uint64_t *d_step,
+                                int32_t *d_table_ids /* n_frames x n_lasers */, double *d_weather /* n_frames x 8 */, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -29,11 +29,33 @@ EXPORTS = [
     "snowgpu_estimate_planes_device", "snowgpu_prepass_stats", "snowgpu_set_wet_estimation", "snowgpu_wet_last_fit", "snowgpu_debug_ransac_polyfit", "snowgpu_set_result_transfer", "snowgpu_debug_transfer_times", "snowgpu_status_error", "snowgpu_set_threshold_callback", "snowgpu_augment_batch_compact", "snowgpu_set_serial", "snowgpu_lane_stream", "snowgpu_device_numa_node",
     "snowgpu_augment_batch_device_aligned", "snowgpu_wet_ground_batch_device_aligned", "snowgpu_augment_wet_batch_device_aligned",
     "snowgpu_augment_batch_device_aligned_masked", "snowgpu_augment_wet_batch_device_aligned_masked", "snowgpu_fov_mask_device",
+    "snowgpu_augment_weather_batch_device_aligned", "snowgpu_draw_weather_device",
 ]
 
 WET_ESTIMATION = {"linear": 0, "poly": 1}
 
 PLANE_METHODS = {"reference": 0, "lsq": 1, "ransac": 2}
+
+
+class WeatherPlanStruct(ctypes.Structure):
+    """snowgpu_weather_plan (include/snowgpu.h)."""
+    _fields_ = [("p_snow", ctypes.c_double), ("p_wet", ctypes.c_double), ("n_water", ctypes.c_int32), ("n_pave", ctypes.c_int32),
+                ("water_heights", ctypes.c_double * 16), ("pavement_depths", ctypes.c_double * 16), ("wet_noise_floor", ctypes.c_double),
+                ("power_factor", ctypes.c_double), ("delta", ctypes.c_double), ("shuffle", ctypes.c_int32)]
+
+
+def weather_plan_struct(p_snow, p_wet, water_heights, pavement_depths, noise_floor, power_factor, delta, shuffle):
+    """The plan of snowgpu_draw_weather_device from Python values.  More than 16 choices are kept in n_water / n_pave as they are (the
+    first 16 stored): the entry refuses them."""
+    wh, pd = [float(v) for v in water_heights], [float(v) for v in pavement_depths]
+    s = WeatherPlanStruct()
+    s.p_snow, s.p_wet, s.n_water, s.n_pave = float(p_snow), float(p_wet), len(wh), len(pd)
+    for i, v in enumerate(wh[:16]):
+        s.water_heights[i] = v
+    for i, v in enumerate(pd[:16]):
+        s.pavement_depths[i] = v
+    s.wet_noise_floor, s.power_factor, s.delta, s.shuffle = float(noise_floor), float(power_factor), float(delta), int(bool(shuffle))
+    return s
 
 
 class SnowGPUError(RuntimeError):
@@ -109,6 +131,11 @@ def lib():
             L.snowgpu_augment_wet_batch_device_aligned_masked.restype = ctypes.c_int
             L.snowgpu_augment_wet_batch_device_aligned_masked.argtypes = base[:13] + [vp] + base[13:] + [
                 vp, dbl, dbl, dbl, dbl, ctypes.c_int, dbl, ctypes.c_int, vp]
+            L.snowgpu_augment_weather_batch_device_aligned.restype = ctypes.c_int               # (d_weather in place of the five wet doubles)
+            L.snowgpu_augment_weather_batch_device_aligned.argtypes = base[:13] + [vp] + base[13:] + [vp, vp, ctypes.c_int, ctypes.c_int, vp]
+            L.snowgpu_draw_weather_device.restype = ctypes.c_int
+            L.snowgpu_draw_weather_device.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, ctypes.POINTER(WeatherPlanStruct),
+                                                      ctypes.c_uint64, vp, vp, vp, vp]
             L.snowgpu_fov_mask_device.restype = ctypes.c_int
             L.snowgpu_fov_mask_device.argtypes = [vp, i64, vp, ctypes.c_int, vp, vp, vp, ctypes.c_int, ctypes.c_int, vp, vp, vp]
             L.snowgpu_set_fov_precrop.restype = ctypes.c_int
@@ -433,6 +460,31 @@ class Context:
             vp(d_out_stats or None), vp(d_out_thr or None), vp(d_status or None), vp(stream or None), vp(d_wet_plane or None),
             float(water_height), float(pavement_depth), float(wet_noise_floor), float(power_factor), int(bool(flat_earth)), float(delta),
             int(bool(replace)), vp(d_out_flags or None))
+        self._check(rc)
+
+    def augment_weather_batch_device_aligned(self, n_frames, n_total, max_frame_rows, d_frame_off, d_rows, dtype_code, d_table_ids,
+                                             beam_divergence, d_thr_poly, d_plane, noise_floor, d_perm, d_keep_in, d_out_rows, d_out_keep,
+                                             d_out_counts, d_out_stats, d_out_thr, d_status, stream, d_wet_plane, d_weather, flat_earth,
+                                             replace, d_out_flags):
+        """augment_wet_batch_device_aligned_masked with per-frame weather records in device memory (d_weather: n_frames x 8 float64 --
+        snow gate, wet gate, water height, pavement depth, wet noise floor, power factor, delta, 0) in place of its five wet scalars;
+        asynchronous on `stream`."""
+        vp = ctypes.c_void_p
+        rc = self._L.snowgpu_augment_weather_batch_device_aligned(
+            self._h, int(n_frames), int(n_total), int(max_frame_rows), vp(d_frame_off), vp(d_rows or None), int(dtype_code),
+            vp(d_table_ids), float(beam_divergence), vp(d_thr_poly or None), vp(d_plane or None), float(noise_floor),
+            vp(d_perm or None), vp(d_keep_in or None), vp(d_out_rows or None), vp(d_out_keep or None), vp(d_out_counts or None),
+            vp(d_out_stats or None), vp(d_out_thr or None), vp(d_status or None), vp(stream or None), vp(d_wet_plane or None),
+            vp(d_weather or None), int(bool(flat_earth)), int(bool(replace)), vp(d_out_flags or None))
+        self._check(rc)
+
+    def draw_weather_device(self, n_frames, n_lasers, n_sets, d_set_ids, plan, seed, d_step, d_table_ids, d_weather, stream=0):
+        """Draw every frame's table ids (n_frames x n_lasers int32) and weather record (n_frames x 8 float64) on the device from Philox keyed
+        by (seed; the step in device memory, frame).  plan: a WeatherPlanStruct (weather_plan_struct); asynchronous on `stream`."""
+        vp = ctypes.c_void_p
+        rc = self._L.snowgpu_draw_weather_device(self._h, int(n_frames), int(n_lasers), int(n_sets), vp(d_set_ids or None),
+                                                 ctypes.byref(plan) if plan is not None else None, ctypes.c_uint64(int(seed) & (2 ** 64 - 1)),
+                                                 vp(d_step or None), vp(d_table_ids or None), vp(d_weather or None), vp(stream or None))
         self._check(rc)
 
     def fov_mask_device(self, n_total, d_rows, dtype_code, calib, img_shape, d_keep_in, d_out_keep, stream=0):

@@ -247,12 +247,13 @@ int sg_launch_finish_aligned(const void *rows, const void *srows, const int32_t 
                              int64_t max_tiles_per_frame, unsigned long long *tiles_done /* n_frames words, zero */, void *stream);
 int sg_launch_crop_count(const void *rows, int dtype, const int64_t *frame_off, int n_frames, uint8_t *keep, int32_t *tile_cnt,
                          int32_t *tile_base, int64_t *out_counts, int64_t *stats_scratch, const SgFov *fov, int64_t max_tiles, void *stream);
-int sg_launch_crop_scatter(const void *rows, int dtype, const uint8_t *keep, const int64_t *frame_off, const int64_t *new_off,
+int sg_launch_crop_scatter(const void *rows, int dtype, const uint8_t *keep, const double *gate /* or null */, const int64_t *frame_off, const int64_t *new_off,
                            int n_frames, const int32_t *tile_base, void *out_rows, int32_t *crop_src, int64_t max_tiles, void *stream);
 // An input keep mask for the aligned entry.  Front end: the present rows (keep_in byte != 0) of every frame compacted, stably, into crows at
 // the device-made offsets new_off[0 .. n_frames]; map = their frame-local input rows; the absent rows' keep bytes (and, out_rows != null,
 // their rows) written.  Masked finish: sg_launch_finish_aligned on the compacted batch, every row written at in_off[f] + map[.] of the input.
-int sg_launch_mask_front(const void *rows, int dtype, const uint8_t *keep_in, const int64_t *frame_off, int n_frames, void *out_rows /* null: in place */,
+// weather (optional, n_frames x 8 records, sg_weather.h): a frame whose snow gate is 0 contributes no row and keeps its keep bytes (keep_in may then be null).
+int sg_launch_mask_front(const void *rows, int dtype, const uint8_t *keep_in, const double *weather, const int64_t *frame_off, int n_frames, void *out_rows /* null: in place */,
                          uint8_t *out_keep, int32_t *tile_cnt, int32_t *tile_base, int64_t *counts, int64_t *new_off, void *crows, int32_t *map,
                          int64_t max_tiles, void *stream);
 int sg_launch_finish_aligned_masked(const void *crows, const void *srows, const int32_t *frame_unsorted, int dtype, const uint32_t *rec, const uint32_t *rec_q,

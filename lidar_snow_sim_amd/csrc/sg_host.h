@@ -259,6 +259,8 @@ struct BatchDev {
     // bounds of it; the aligned finish writes row j of compacted frame f to out_rows / out_keep at mask_in_off[f] + mask_map[frame_off[f] + j].
     const int32_t *mask_map = nullptr;
     const int64_t *mask_in_off = nullptr;
+    const double *weather = nullptr;   // per-frame weather records (snowgpu_augment_weather_batch_device_aligned): a frame gated out of the snowfall
+                                       // stage arrives here empty, and the prepass reports no missing ground for it
     int64_t *out_counts;
     int64_t *out_stats;
     double *out_thr_poly;     // may be null
@@ -283,6 +285,13 @@ int status_to_error(snowgpu_ctx *ctx, const int32_t st[8]);
 int node_of_device(int device);                               // snowgpu_host.cpp
 
 #pragma GCC visibility pop
+
+// snowgpu_weather.hip
+struct SgWeatherDraw;
+extern "C" int sg_launch_draw_weather(const SgWeatherDraw *p, int n_frames, uint64_t seed, const uint64_t *d_step, const int32_t *d_set_ids,
+                                      int32_t *d_table_ids, double *d_weather, void *stream);
+// flags[f] = 2 where frame f's wet gate is off, else 1: the wet flags of a batch without a row
+extern "C" int sg_launch_weather_flags(const double *d_weather, int n_frames, int32_t *d_flags, void *stream);
 
 // snowgpu_tables.hip, snowgpu_sampler.hip
 extern "C" int sg_table_index(const SgEntry *entries, const uint32_t *start, uint32_t *q, uint32_t *qs /* or null */, void *stream);

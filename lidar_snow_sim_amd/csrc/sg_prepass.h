@@ -18,6 +18,8 @@ struct SgWetParams {
     double *fit_out;            // optional DEVICE array n_frames x 8: the fitted curves (k_pre_export_fit)
     const int32_t *src_first;   // optional DEVICE array, indexed like the rows: out_src gets src_first[row] instead of the row's index in its
                                 // frame (a chained call: the rows are an earlier stage's output, src_first its source rows)
+    const double *weather;      // optional DEVICE array n_frames x 8 (sg_weather.h): per frame the wet gate and water_height, pavement_depth,
+                                // noise_floor, power_factor, delta, which then replace the five scalars above (aligned stage only)
 };
 
 #define SG_PRE_REC 18      /* doubles per frame of sg_prepass_stats_run's record */
@@ -32,7 +34,8 @@ int sg_prepass_stats_run(SgPrepassScratch *s, const void *rows, int dtype, const
 // srows / frame_unsorted: optional -- the channel sort's sorted copy and the per-frame flags that say where it is valid
 int sg_prepass_run(SgPrepassScratch *s, const void *rows, int dtype, const int64_t *frame_off, int n_frames,
                    int64_t n_total, int64_t max_frame, const double *plane, double noise_floor, double *thr_poly, int32_t *status,
-                   void *stream, int tiles_done, const void *srows, const int32_t *frame_unsorted, int hist_cleared);
+                   void *stream, int tiles_done, const void *srows, const int32_t *frame_unsorted, int hist_cleared,
+                   const double *weather /* optional n_frames x 8: a frame whose snow gate is 0 reports no missing ground */);
 // clears the prepass' histogram on `stream` ahead of time (independent of the batch's data): sg_prepass_run(.., hist_cleared = 1) then skips its fill
 int sg_prepass_clear_hist(SgPrepassScratch *s, int n_frames, void *stream);
 int sg_prepass_stats_early(SgPrepassScratch *s, const void *rows, int dtype, const int64_t *frame_off, int n_frames, int64_t max_frame,

@@ -8,6 +8,7 @@
 #include "sg_common.h"
 #include "sg_prepass.h"
 #include "sg_lean.h"
+#include "sg_weather.h"
 
 #define PB 256
 #define HX 50     /* range rows of the histogram (augmentation.py:232) */
@@ -27,7 +28,7 @@ struct PreFrame {          // per-frame state shared by the kernels
     int32_t rows_done;     // lean chain: histogram rows whose minimum has been taken (k_lean_rowmin_solve: the block that completes the frame fits its lines)
     int32_t quad;          // 1: k_wet_apply evaluates pq / mq
     int32_t ransac_trial;  // the trial whose consensus refit was kept (-1: the fit over all points)
-    int32_t unchanged;     // wet path: < 1000 ground rows (augmentation.py:51-52)
+    int32_t unchanged;     // wet path: 1 = < 1000 ground rows (augmentation.py:51-52), 2 = the frame's wet gate is off (PreArgs::weather)
     int32_t need_mean32;   // float32 rows and the noise line falls back to p (augmentation.py:250-251)
     // lean snowfall prepass (k_lean_*): centred second moments of (range, I / cos) and the sums of the quadratic fit
     double sxx, sxy;
@@ -66,6 +67,9 @@ struct PreArgs {
     int32_t *status;
     const uint8_t *keep;   // optional (aligned wet stage), indexed like the rows: 0 = the row is not there (an earlier stage removed it) and
                            // k_pre_ground<T, true> takes it for a non-ground row; NULL: every row is present
+    const double *weather; // optional n_frames x SG_WEATHER_REC (sg_weather.h): per-frame gates and wet settings in DEVICE memory.  The wet stage
+                           // reads delta, noise_floor and power_factor there instead of above and skips a frame whose wet gate is 0
+                           // (fr.unchanged = 2); the snowfall prepass reports no missing ground for a frame whose snow gate is 0
 };
 
 __device__ __forceinline__ int64_t pre_rows(const PreArgs &a, int f)

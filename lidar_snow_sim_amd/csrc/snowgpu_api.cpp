@@ -7,6 +7,8 @@
 #include "sg_launch.h"      // sg_tiles
 #include "sg_table_host.h"
 #include "sg_range_index.h"  // SG_QS_FITS, SG_QS_WORDS
+#include "sg_weather.h"      // SgWeatherDraw and the limits of the draw
+#include <cmath>
 
 // simulation.py:106-116: R = np.round(np.linspace(0, 120 + c*tau_h, 1230), 2).
 // linspace: k * step (+ 0.0), last element = stop; round(., 2): rint(v * 100) / 100.
@@ -727,10 +729,12 @@ static int aligned_wet_refusals(snowgpu_ctx *ctx, const char *who, int64_t n_tot
 static int aligned_wet_stage(snowgpu_ctx *ctx, const char *who, int n_frames, int64_t n_total, int64_t max_frame, const int64_t *d_frame_offsets,
                              const void *d_rows, int dtype, const uint8_t *d_keep_in, const double *d_plane, double water_height,
                              double pavement_depth, double noise_floor, double power_factor, int flat_earth, double delta, int replace,
-                             void *d_out_rows, uint8_t *d_out_keep, int64_t *d_out_counts, int32_t *d_out_flags, int32_t *d_status, hipStream_t st)
+                             void *d_out_rows, uint8_t *d_out_keep, int64_t *d_out_counts, int32_t *d_out_flags, int32_t *d_status, hipStream_t st,
+                             const double *d_weather = nullptr /* per-frame records: they replace the five wet scalars */)
 {
     const std::string name(who);
     SgWetParams wp{};
+    wp.weather = d_weather;
     wp.water_height = water_height; wp.pavement_depth = pavement_depth; wp.noise_floor = noise_floor;
     wp.power_factor = power_factor; wp.flat_earth = flat_earth; wp.delta = delta; wp.replace = replace;
     wp.estimation = ctx->wet_estimation; wp.seed = ctx->wet_seed;
@@ -839,7 +843,8 @@ extern "C" int snowgpu_augment_wet_batch_device_aligned(snowgpu_ctx *ctx, int n_
 // scratch (rows_crop, crop_src) at offsets made on the device (crop_off); the absent rows' keep bytes -- and, out of place, their rows --
 // are written on the way.  Then run_batch on that scratch: every kernel of the unmasked call, untouched, on the batch the caller would have
 // had to compact; n_total and max_frame are upper bounds to it, no frame-uniform shortcut.  Its last step is the masked aligned finish.
-static int masked_snow_stage(snowgpu_ctx *ctx, const char *who, BatchDev &b, const uint8_t *d_keep_in)
+// d_weather (optional): the snow gate of every frame is part of the mask (d_keep_in may then be NULL); see sg_launch_mask_front.
+static int masked_snow_stage(snowgpu_ctx *ctx, const char *who, BatchDev &b, const uint8_t *d_keep_in, const double *d_weather = nullptr)
 {
     const std::string name(who);
     snowgpu_ctx *R = ctx->root ? ctx->root : ctx;
@@ -855,10 +860,10 @@ static int masked_snow_stage(snowgpu_ctx *ctx, const char *who, BatchDev &b, con
     ENSURE(ctx, ctx->crop_off, (size_t)b.n_frames + 1);
     ENSURE(ctx, ctx->rows_crop, n * 5 * esz);
     ENSURE(ctx, ctx->crop_src, n);
-    int e = sg_launch_mask_front(b.rows, b.dtype, d_keep_in, b.frame_off, b.n_frames, b.out_rows == b.rows ? nullptr : b.out_rows, b.out_keep,
+    int e = sg_launch_mask_front(b.rows, b.dtype, d_keep_in, d_weather, b.frame_off, b.n_frames, b.out_rows == b.rows ? nullptr : b.out_rows, b.out_keep,
                                  ctx->ctile_cnt.p, ctx->ctile_base.p, ctx->crop_counts.p, ctx->crop_off.p, ctx->rows_crop.p, ctx->crop_src.p, max_tiles, b.stream);
     if (e) return fail(ctx, SNOWGPU_E_HIP, std::string("mask front end launch: ") + hipGetErrorString((hipError_t)e));
-    b.mask_in_off = b.frame_off; b.mask_map = ctx->crop_src.p;
+    b.mask_in_off = b.frame_off; b.mask_map = ctx->crop_src.p; b.weather = d_weather;
     b.rows = ctx->rows_crop.p; b.frame_off = ctx->crop_off.p; b.uniform_rows = 0;
     return run_batch(ctx, b);
 }
@@ -932,6 +937,79 @@ extern "C" int snowgpu_augment_wet_batch_device_aligned_masked(snowgpu_ctx *ctx,
     return aligned_wet_stage(ctx, who, n_frames, n_total, b.max_frame, d_frame_offsets, d_out_rows, dtype, d_out_keep, d_wet_plane, water_height,
                              pavement_depth, wet_noise_floor, power_factor, flat_earth, delta, replace, d_out_rows, d_out_keep, d_out_counts,
                              d_out_flags, d_status, b.stream);
+}
+
+// ---- per-frame weather: gates and wet settings in device memory (include/snowgpu.h) ---------------------------------------------------
+// The masked fused chain with d_weather in place of its five wet scalars.  The snow gate joins the input mask in the front end (a frame
+// left out reaches run_batch empty and keeps its keep bytes), the wet gate and the wet settings are read per frame by the wet kernels.
+// Because the gates are device data the masked front end always runs, with or without d_keep_in.
+extern "C" int snowgpu_augment_weather_batch_device_aligned(snowgpu_ctx *ctx, int n_frames, int64_t n_total, int64_t max_frame_rows,
+                                                            const int64_t *d_frame_offsets, const void *d_rows, int dtype,
+                                                            const int32_t *d_table_ids, double beam_divergence_deg, const double *d_thr_poly,
+                                                            const double *d_plane, double noise_floor, const int32_t *d_perm,
+                                                            const uint8_t *d_keep_in, void *d_out_rows, uint8_t *d_out_keep,
+                                                            int64_t *d_out_counts, int64_t *d_out_stats, double *d_out_thr_poly, int32_t *d_status,
+                                                            void *stream, const double *d_wet_plane, const double *d_weather, int flat_earth,
+                                                            int replace, int32_t *d_out_flags)
+{
+    static const char *who = "snowgpu_augment_weather_batch_device_aligned";
+    if (!ctx) return SNOWGPU_E_INVALID;
+    if (!d_weather) return fail(ctx, SNOWGPU_E_INVALID, std::string(who) + ": d_weather is NULL; one record of 8 doubles per frame, in device memory");
+    if (n_frames <= 0 || n_total < 0 || !d_frame_offsets || (n_total > 0 && !d_rows) || !d_table_ids || !d_out_rows ||
+        !d_out_keep || !d_out_counts || !d_out_stats || !d_out_flags || !d_status || (dtype != 0 && dtype != 1))
+        return fail(ctx, SNOWGPU_E_INVALID, std::string(who) + ": null pointer or bad dtype");
+    if (n_total >= ((int64_t)1 << 31)) return fail(ctx, SNOWGPU_E_INVALID, "batch too large: split it below 2^31 rows");
+    if (int rc = aligned_wet_refusals(ctx, who, n_total, dtype, d_rows, d_out_rows, d_keep_in, d_out_keep)) return rc;
+    if (!d_wet_plane && ctx->plane_par.method != SG_PLANE_REFERENCE)             // (before anything is launched)
+        return fail(ctx, SNOWGPU_E_INVALID, std::string(who) + ": a NULL wet plane needs the plane method 'reference'; 'lsq' and 'ransac' crop the rows and have no masked form: pass the plane");
+    if (d_perm) return fail(ctx, SNOWGPU_E_INVALID, std::string(who) + ": d_perm with d_weather; a caller's permutation indexes the rows of the frames it was made for, not the present ones");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    BatchDev b{};
+    b.n_frames = n_frames; b.n_total = n_total; b.max_frame = (max_frame_rows > 0 && max_frame_rows <= n_total) ? max_frame_rows : n_total;
+    b.frame_off = d_frame_offsets; b.rows = d_rows;
+    b.dtype = dtype; b.table_ids = d_table_ids; b.beam_div_deg = beam_divergence_deg; b.thr_poly = d_thr_poly;
+    b.plane = d_plane; b.noise_floor = noise_floor; b.perm = d_perm; b.out_rows = d_out_rows; b.out_src = nullptr; b.out_keep = d_out_keep;
+    b.out_counts = d_out_counts; b.out_stats = d_out_stats; b.out_thr_poly = d_out_thr_poly; b.status = d_status;
+    b.stream = stream ? (hipStream_t)stream : ctx->stream;
+    if (n_total == 0) {                              // no row at all: the unmasked chain's answer, with "not asked" where the wet gate is off
+        int rc = run_batch(ctx, b);
+        if (rc) return rc;
+        rc = aligned_wet_empty(ctx, n_frames, d_out_counts, d_out_flags, b.stream);
+        if (rc) return rc;
+        int e = sg_launch_weather_flags(d_weather, n_frames, d_out_flags, b.stream);
+        if (e) return fail(ctx, SNOWGPU_E_HIP, std::string("weather flags launch: ") + hipGetErrorString((hipError_t)e));
+        return SNOWGPU_OK;
+    }
+    int rc = masked_snow_stage(ctx, who, b, d_keep_in, d_weather);
+    if (rc) return rc;
+    return aligned_wet_stage(ctx, who, n_frames, n_total, b.max_frame, d_frame_offsets, d_out_rows, dtype, d_out_keep, d_wet_plane, 0.0, 1.0, 0.0, 0.0,
+                             flat_earth, 0.0, replace, d_out_rows, d_out_keep, d_out_counts, d_out_flags, d_status, b.stream, d_weather);
+}
+
+// Which weather each frame gets, drawn on the device (snowgpu_weather.hip, sg_weather.h).  See include/snowgpu.h.
+extern "C" int snowgpu_draw_weather_device(snowgpu_ctx *ctx, int n_frames, int n_lasers, int n_sets, const int32_t *d_set_ids,
+                                           const snowgpu_weather_plan *plan, uint64_t seed, const uint64_t *d_step, int32_t *d_table_ids,
+                                           double *d_weather, void *stream)
+{
+    static const char *who = "snowgpu_draw_weather_device";
+    if (!ctx) return SNOWGPU_E_INVALID;
+    if (!plan || !d_set_ids || !d_step || !d_table_ids || !d_weather) return fail(ctx, SNOWGPU_E_INVALID, std::string(who) + ": null pointer");
+    if (n_frames <= 0 || n_frames > (1 << 22) || n_lasers <= 0 || n_lasers > SG_WEATHER_MAX_LASERS || n_sets <= 0 || n_sets > SG_WEATHER_MAX_SETS ||
+        plan->n_water <= 0 || plan->n_water > SG_WEATHER_MAX_CHOICES || plan->n_pave <= 0 || plan->n_pave > SG_WEATHER_MAX_CHOICES)
+        return fail(ctx, SNOWGPU_E_INVALID, std::string(who) + ": needs 1 .. 2^22 frames, 1 .. 128 lasers, 1 .. 64 table sets, 1 .. 16 water heights and pavement depths");
+    if (!(plan->p_snow >= 0.0 && plan->p_snow <= 1.0) || !(plan->p_wet >= 0.0 && plan->p_wet <= 1.0))
+        return fail(ctx, SNOWGPU_E_INVALID, std::string(who) + ": p_snow and p_wet are probabilities");
+    auto threshold = [](double p) { const double t = std::floor(p * 4294967296.0); return t >= 4294967296.0 ? (uint64_t)1 << 32 : (uint64_t)t; };
+    SgWeatherDraw d{};
+    d.t_snow = threshold(plan->p_snow); d.t_wet = threshold(plan->p_wet);
+    d.n_sets = n_sets; d.n_lasers = n_lasers; d.n_water = plan->n_water; d.n_pave = plan->n_pave; d.shuffle = plan->shuffle ? 1 : 0;
+    for (int i = 0; i < plan->n_water; ++i) d.water[i] = plan->water_heights[i];
+    for (int i = 0; i < plan->n_pave; ++i) d.pave[i] = plan->pavement_depths[i];
+    d.wet_noise_floor = plan->wet_noise_floor; d.power_factor = plan->power_factor; d.delta = plan->delta;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    int e = sg_launch_draw_weather(&d, n_frames, seed, d_step, d_set_ids, d_table_ids, d_weather, stream ? (hipStream_t)stream : ctx->stream);
+    if (e) return fail(ctx, SNOWGPU_E_HIP, std::string("weather draw launch: ") + hipGetErrorString((hipError_t)e));
+    return SNOWGPU_OK;
 }
 
 // Camera-FOV crop of augment(only_camera_fov=True) (simulation.py:39-47, :532-540): lidar_to_rect with

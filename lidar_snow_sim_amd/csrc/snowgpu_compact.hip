@@ -263,8 +263,10 @@ __global__ __launch_bounds__(SG_BLOCK) void k_crop_flag(const T *__restrict__ ro
     if (threadIdx.x == 0) tile_cnt[(int64_t)f * max_tiles + blockIdx.x] = s[0] + s[1] + s[2] + s[3];
 }
 
+// keep may be null (every row present) and gate (optional, n_frames x 8 weather records) leaves out the frames whose first value is 0, as
+// k_mask_count counted them (snowgpu_mask.hip).
 template <typename T>
-__global__ __launch_bounds__(SG_BLOCK) void k_crop_scatter(const T *__restrict__ rows, const uint8_t *__restrict__ keep,
+__global__ __launch_bounds__(SG_BLOCK) void k_crop_scatter(const T *__restrict__ rows, const uint8_t *__restrict__ keep, const double *__restrict__ gate,
                                                            const int64_t *__restrict__ frame_off, const int64_t *__restrict__ new_off,
                                                            const int32_t *__restrict__ tile_base, T *__restrict__ out_rows,
                                                            int32_t *__restrict__ crop_src, int64_t max_tiles)
@@ -273,13 +275,14 @@ __global__ __launch_bounds__(SG_BLOCK) void k_crop_scatter(const T *__restrict__
     const int64_t base = frame_off[f], n = frame_off[f + 1] - base;
     const int64_t tile0 = (int64_t)blockIdx.x * SG_TILE;
     if (tile0 >= n) return;
+    if (gate && gate[(int64_t)f * 8] == 0.0) return;
     __shared__ int wave_cnt[4][4];
     const int tid = threadIdx.x, w = tid >> 6;
     bool k[4];
     int pre[4];
     for (int q = 0; q < 4; ++q) {
         const int64_t r = tile0 + q * SG_BLOCK + tid;
-        k[q] = r < n && keep[base + r];
+        k[q] = r < n && (!keep || keep[base + r]);
         const unsigned long long m = __ballot(k[q]);
         pre[q] = __popcll(m & sg_lanemask_lt());
         if ((tid & 63) == 0) wave_cnt[q][w] = __popcll(m);
@@ -381,14 +384,14 @@ extern "C" int sg_launch_crop_count(const void *rows, int dtype, const int64_t *
 }
 
 // stage 2: rows of frame f to new_off[f] .. (stable), crop_src = their rows in the original frame
-extern "C" int sg_launch_crop_scatter(const void *rows, int dtype, const uint8_t *keep, const int64_t *frame_off, const int64_t *new_off,
+extern "C" int sg_launch_crop_scatter(const void *rows, int dtype, const uint8_t *keep, const double *gate, const int64_t *frame_off, const int64_t *new_off,
                                       int n_frames, const int32_t *tile_base, void *out_rows, int32_t *crop_src, int64_t max_tiles, void *stream)
 {
     hipStream_t st = (hipStream_t)stream;
     dim3 grid((unsigned)max_tiles, (unsigned)n_frames);
     return sg_by_dtype(dtype, [&](auto t) {
         using T = decltype(t);
-        hipLaunchKernelGGL(k_crop_scatter<T>, grid, dim3(SG_BLOCK), 0, st, (const T *)rows, keep, frame_off, new_off, tile_base, (T *)out_rows, crop_src, max_tiles);
+        hipLaunchKernelGGL(k_crop_scatter<T>, grid, dim3(SG_BLOCK), 0, st, (const T *)rows, keep, gate, frame_off, new_off, tile_base, (T *)out_rows, crop_src, max_tiles);
         SG_CHECK_LAUNCH();
         return 0;
     });

@@ -593,7 +593,7 @@ static int host_batch(snowgpu_ctx *ctx, int n_frames, const int64_t *frame_offse
         frame_extent(n_frames, crop_off.data(), &max_frame_used, &uniform);
         n_used = crop_off[(size_t)n_frames];
         HIPCHK(ctx, hipMemcpyAsync(ctx->crop_off.p, crop_off.data(), sizeof(int64_t) * ((size_t)n_frames + 1), hipMemcpyHostToDevice, st));
-        e = sg_launch_crop_scatter(ctx->rows_in.p, dtype, ctx->keep.p, d_frame_off, ctx->crop_off.p, n_frames, ctx->ctile_base.p,
+        e = sg_launch_crop_scatter(ctx->rows_in.p, dtype, ctx->keep.p, nullptr, d_frame_off, ctx->crop_off.p, n_frames, ctx->ctile_base.p,
                                    ctx->rows_crop.p, ctx->crop_src.p, max_tiles, st);
         if (e) return fail(ctx, SNOWGPU_E_HIP, std::string("crop launch: ") + hipGetErrorString((hipError_t)e));
         d_rows_used = ctx->rows_crop.p; d_off_used = ctx->crop_off.p;

@@ -2,7 +2,8 @@
 //
 //   k_mask_count / k_mask_scan / k_mask_offsets   the front end: present rows (keep-in byte != 0) per 1024-row tile, the per-frame scan of
 //                those counts, and the exclusive scan of the per-frame totals over the frames -- the offsets of the compacted batch, which
-//                never leave the device.  The scatter itself is k_crop_scatter (snowgpu_compact.hip: sg_launch_crop_scatter), unchanged.
+//                never leave the device.  The scatter itself is k_crop_scatter (snowgpu_compact.hip: sg_launch_crop_scatter).  With per-frame
+//                weather records (sg_weather.h) a frame's snow gate is part of the mask: k_mask_count and the scatter leave such a frame out.
 //   k_finish_aligned_masked   k_finish_aligned for a batch that was compacted by such a mask: the decision and the output row of every
 //                sorted position of the COMPACTED frame, written to the row's index in the caller's INPUT frame through the scatter's map.
 //   k_fov_mask   the camera-FOV test (sg_in_fov) as a producer of such a mask.
@@ -17,15 +18,21 @@
 #include "sg_row.h"
 #include "sg_finish.h"
 #include "sg_launch.h"
+#include "sg_weather.h"
 
 // Present rows per tile.  An absent row is finished here: its keep byte is 0 and -- out of place (out_rows != null) -- its five columns are
 // copied as they are (plain loads and stores of the row type: bit for bit, NaNs included).  out_keep may BE keep_in: the byte written is
 // the byte read.
+// weather (optional, n_frames x SG_WEATHER_REC): a frame whose snow gate is 0 has no present row for the snowfall stage -- it reaches the
+// per-beam kernels as an empty frame -- but its keep bytes stay the caller's (1 without a mask): the frame is not cropped, it is left out.
+// keep_in may be null only with weather (every row present).
 template <typename T>
-__global__ __launch_bounds__(SG_BLOCK) void k_mask_count(const T *__restrict__ rows, const uint8_t *keep_in, const int64_t *__restrict__ frame_off,
-                                                         T *__restrict__ out_rows, uint8_t *out_keep, int32_t *__restrict__ tile_cnt, int64_t max_tiles)
+__global__ __launch_bounds__(SG_BLOCK) void k_mask_count(const T *__restrict__ rows, const uint8_t *keep_in, const double *__restrict__ weather,
+                                                         const int64_t *__restrict__ frame_off, T *__restrict__ out_rows, uint8_t *out_keep,
+                                                         int32_t *__restrict__ tile_cnt, int64_t max_tiles)
 {
     const int f = blockIdx.y;
+    const bool gated = weather && weather[(int64_t)f * SG_WEATHER_REC + SG_W_SNOW] == 0.0;
     const int64_t base = frame_off[f], n = frame_off[f + 1] - base;
     const int64_t tile0 = (int64_t)blockIdx.x * SG_TILE;
     if (tile0 >= n) return;
@@ -34,8 +41,9 @@ __global__ __launch_bounds__(SG_BLOCK) void k_mask_count(const T *__restrict__ r
     for (int q = 0; q < 4; ++q) {
         const int64_t r = tile0 + q * SG_BLOCK + threadIdx.x;
         if (r >= n) continue;
-        if (keep_in[base + r]) { ++c; continue; }
-        out_keep[base + r] = 0;
+        const uint8_t k = keep_in ? keep_in[base + r] : (uint8_t)1;
+        if (k && !gated) { ++c; continue; }
+        out_keep[base + r] = k;                  // (0, or the byte that came in for a frame that is left out)
         if (out_rows) {
             const T *s = rows + (base + r) * 5;
             T *d = out_rows + (base + r) * 5;
@@ -184,7 +192,8 @@ __global__ __launch_bounds__(256) void k_fov_mask(const T *__restrict__ rows, in
 
 // The front end of a masked aligned call, on `stream`: new_off[0 .. n_frames] (device), the present rows of frame f at crows[new_off[f] ..]
 // in input order, map[new_off[f] + j] = frame-local input row of compacted row j.  out_rows: null in place, else the absent rows are copied.
-extern "C" int sg_launch_mask_front(const void *rows, int dtype, const uint8_t *keep_in, const int64_t *frame_off, int n_frames, void *out_rows,
+// weather: optional per-frame records; their snow gate is part of the mask (keep_in may then be null).
+extern "C" int sg_launch_mask_front(const void *rows, int dtype, const uint8_t *keep_in, const double *weather, const int64_t *frame_off, int n_frames, void *out_rows,
                                     uint8_t *out_keep, int32_t *tile_cnt, int32_t *tile_base, int64_t *counts, int64_t *new_off, void *crows,
                                     int32_t *map, int64_t max_tiles, void *stream)
 {
@@ -192,7 +201,7 @@ extern "C" int sg_launch_mask_front(const void *rows, int dtype, const uint8_t *
     dim3 grid((unsigned)max_tiles, (unsigned)n_frames);
     int e = sg_by_dtype(dtype, [&](auto t) {
         using T = decltype(t);
-        hipLaunchKernelGGL(k_mask_count<T>, grid, dim3(SG_BLOCK), 0, st, (const T *)rows, keep_in, frame_off, (T *)out_rows, out_keep, tile_cnt, max_tiles);
+        hipLaunchKernelGGL(k_mask_count<T>, grid, dim3(SG_BLOCK), 0, st, (const T *)rows, keep_in, weather, frame_off, (T *)out_rows, out_keep, tile_cnt, max_tiles);
         SG_CHECK_LAUNCH();
         return 0;
     });
@@ -201,7 +210,7 @@ extern "C" int sg_launch_mask_front(const void *rows, int dtype, const uint8_t *
     SG_CHECK_LAUNCH();
     hipLaunchKernelGGL(k_mask_offsets, dim3(1), dim3(256), 0, st, (const int64_t *)counts, n_frames, new_off);
     SG_CHECK_LAUNCH();
-    return sg_launch_crop_scatter(rows, dtype, keep_in, frame_off, new_off, n_frames, tile_base, crows, map, max_tiles, stream);
+    return sg_launch_crop_scatter(rows, dtype, keep_in, weather, frame_off, new_off, n_frames, tile_base, crows, map, max_tiles, stream);
 }
 
 extern "C" int sg_launch_finish_aligned_masked(const void *crows, const void *srows, const int32_t *frame_unsorted, int dtype, const uint32_t *rec, const uint32_t *rec_q,

@@ -34,7 +34,15 @@ __global__ __launch_bounds__(PB) void k_pre_mean32(PreArgs a, int *leaf_buf, int
 {
     const int f = blockIdx.x;
     const int n = (int)a.fr[f].n_ground;
-    if (n <= 0 || !a.fr[f].need_mean32) return;
+    if (n <= 0 || !a.fr[f].need_mean32) {
+        // A frame without a ground row waits for no mean, but its quadratic waited for this kernel (lean_lines_wave): the zeros
+        // lean_solve_frame gives fewer than 3 ground rows, instead of whatever an earlier batch left in the row.
+        if (n <= 0 && a.fr[f].need_mean32 && thr_poly_or_null && threadIdx.x == 0) {
+            double *out = thr_poly_or_null + 3 * f;
+            out[0] = out[1] = out[2] = 0.0;
+        }
+        return;
+    }
     const float *v = a.cdist + a.frame_off[f];
     int *leaf_off = leaf_buf + (int64_t)f * 3 * max_leaves;      // per frame: offsets, lengths, sums (as float bits)
     int *leaf_len = leaf_off + max_leaves;
@@ -210,7 +218,8 @@ __global__ __launch_bounds__(64) void k_lean_means(PreArgs a, int min_ground, in
         fr.rows_done = 0;
         for (int k = 0; k < 11; ++k) fr.q[k] = q[k];
         if (cnt < (double)min_ground) {
-            if (err_code) atomicCAS(&a.status[0], 0, err_code);          // TypeError in the reference (Q7)
+            // TypeError in the reference (Q7) -- unless the frame was gated out of the snowfall stage: it is empty because it was not asked
+            if (err_code && !(a.weather && a.weather[(int64_t)f * SG_WEATHER_REC + SG_W_SNOW] == 0.0)) atomicCAS(&a.status[0], 0, err_code);
             fr.unchanged = 1;
         }
     }
@@ -617,11 +626,12 @@ extern "C" int sg_prepass_clear_hist(SgPrepassScratch *s, int n_frames, void *st
 // Returns 0, a positive hipError_t, or -1 on allocation failure.  plane: n_frames x 4 (wx, wy, wz, h).
 extern "C" int sg_prepass_run(SgPrepassScratch *s, const void *rows, int dtype, const int64_t *frame_off, int n_frames,
                               int64_t n_total, int64_t max_frame, const double *plane, double noise_floor, double *thr_poly,
-                              int32_t *status, void *stream, int tiles_done, const void *srows, const int32_t *frame_unsorted, int hist_cleared)
+                              int32_t *status, void *stream, int tiles_done, const void *srows, const int32_t *frame_unsorted, int hist_cleared,
+                              const double *weather)
 {
     hipStream_t st = (hipStream_t)stream;
     PreArgs a = lean_args(rows, frame_off, n_frames, max_frame, plane);
-    a.noise_floor = noise_floor; a.power_factor = 15.0; a.status = status;
+    a.noise_floor = noise_floor; a.power_factor = 15.0; a.status = status; a.weather = weather;
     a.srows = srows; a.frame_unsorted = srows ? frame_unsorted : nullptr;
     if (lean_reserve(s, a, dtype, n_total, max_frame, nullptr)) return -1;
     if (!hist_cleared) {

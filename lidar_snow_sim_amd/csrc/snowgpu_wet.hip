@@ -31,6 +31,21 @@ __global__ __launch_bounds__(PB) void k_pre_ground(PreArgs a)
     const int64_t base = a.frame_off[f], n = pre_rows(a, f);
     const int64_t tile0 = (int64_t)blockIdx.x * SG_TILE;
     if (tile0 >= n) return;
+    const double *wr = a.weather ? a.weather + (int64_t)f * SG_WEATHER_REC : nullptr;
+    if (wr && wr[SG_W_WET] == 0.0) {
+        // The frame's wet gate is off: its rows are not looked at.  It leaves here as a frame without a ground row -- the state every later
+        // kernel of the estimate already meets for an empty or fully masked frame -- and k_pre_means marks it (fr.unchanged = 2).
+        for (int q = 0; q < 4; ++q) {
+            const int64_t r = tile0 + q * PB + threadIdx.x;
+            if (r < n) a.g_norm[base + r] = NAN;
+        }
+        if (threadIdx.x == 0) {
+            double *o = a.part + ((int64_t)f * a.max_tiles + blockIdx.x) * 12;
+            o[0] = 0.0; o[1] = 0.0; o[2] = 0.0; o[3] = -INFINITY;
+        }
+        return;
+    }
+    const double delta = wr ? wr[SG_W_DELTA] : a.delta;
     const double *pl = a.plane + 4 * f;
     const double w0 = pl[0], w1 = pl[1], w2 = pl[2], h = pl[3];
     const double wn = sqrt((w0 * w0 + w1 * w1) + w2 * w2);              // np.linalg.norm(w)
@@ -52,7 +67,7 @@ __global__ __launch_bounds__(PB) void k_pre_ground(PreArgs a)
         const double dot = ((double)x * w0 + (double)y * w1) + (double)z * w2;   // np.matmul(pc[:, :3], w)
         const double hog = dot + h;
         double gn = NAN, gd = 0.0, ga = 0.0;
-        if (hog < a.delta && hog > -a.delta && (!MASKED || present[q])) {   // simulation.py:450-451 / augmentation.py:46-47
+        if (hog < delta && hog > -delta && (!MASKED || present[q])) {   // simulation.py:450-451 / augmentation.py:46-47
             double nrm;
             if (sizeof(T) == 4 && !a.rows_as_f64) nrm = (double)sqrtf((float)((x * x + y * y) + z * z));   // float32 norm (simulation.py:455)
             else { const double xd = (double)x, yd = (double)y, zd = (double)z; nrm = sqrt((xd * xd + yd * yd) + zd * zd); }
@@ -125,6 +140,7 @@ __global__ __launch_bounds__(64) void k_pre_means(PreArgs a, int min_ground, int
             if (err_code) atomicCAS(&a.status[0], 0, err_code);          // snowfall: TypeError in the reference (Q7)
             fr.unchanged = 1;                                            // wet: frame returned unchanged
         }
+        if (a.weather && a.weather[(int64_t)f * SG_WEATHER_REC + SG_W_WET] == 0.0) fr.unchanged = 2;   // wet stage not asked: returned unchanged, too
     }
 }
 
@@ -554,19 +570,26 @@ struct WetArgs {
 // The per-row chain of a ground row (augmentation.py:90-131, :146) from its range, incidence angle and intensity and the frame's fitted curves:
 // ni = what new_intensities holds after :131 (0 below the noise limit); returns whether the row is kept (:146).  Written down once for
 // k_wet_apply (compact result) and k_wet_apply_aligned (aligned result).
-__device__ __forceinline__ bool wet_row_chain(const PreArgs &a, const PreFrame &fr, double water_height, double pavement_depth, double gd,
-                                              double ang, double inten, double &ni)
+struct WetFrame { double water_height, pavement_depth, noise_floor, power_factor; };     // the call's scalars, or the frame's weather record
+__device__ __forceinline__ WetFrame wet_frame(const PreArgs &a, int f, double water_height, double pavement_depth)
+{
+    if (!a.weather) return WetFrame{water_height, pavement_depth, a.noise_floor, a.power_factor};
+    const double *wr = a.weather + (int64_t)f * SG_WEATHER_REC;
+    return WetFrame{wr[SG_W_WATER], wr[SG_W_PAVE], wr[SG_W_NOISE], wr[SG_W_POWER]};
+}
+
+__device__ __forceinline__ bool wet_row_chain(const WetFrame &wf, const PreFrame &fr, double gd, double ang, double inten, double &ni)
 {
     double gs, gc;
     sg_sincos_0_2pi(ang, gs, gc);                                // the incidence angle lies in [0, pi] (an arccos)
     double rel, thr;
     if (fr.quad) {                                               // estimation_method = 'poly'
         const double gd2 = gd * gd;
-        rel = a.power_factor * ((fr.pq[0] * gd2 + fr.pq[1] * gd) + fr.pq[2]);        // :228-229
-        thr = a.noise_floor * ((fr.mq[0] * gd2 + fr.mq[1] * gd) + fr.mq[2]);         // :245-246
+        rel = wf.power_factor * ((fr.pq[0] * gd2 + fr.pq[1] * gd) + fr.pq[2]);        // :228-229
+        thr = wf.noise_floor * ((fr.mq[0] * gd2 + fr.mq[1] * gd) + fr.mq[2]);         // :245-246
     } else {
-        rel = a.power_factor * (fr.p0 * gd + fr.p1);             // :221
-        thr = a.noise_floor * (fr.pmin0 * gd + fr.pmin1);        // :252-253
+        rel = wf.power_factor * (fr.p0 * gd + fr.p1);             // :221
+        thr = wf.noise_floor * (fr.pmin0 * gd + fr.pmin1);        // :252-253
     }
     const double refl = inten / gc / rel;                        // :90
     double rho = refl < 0.05 ? 0.05 : (refl > 1 ? 1 : refl);     // :109 np.clip(reflectivities, 0.05, 1)
@@ -575,7 +598,7 @@ __device__ __forceinline__ bool wet_row_chain(const PreArgs &a, const PreFrame &
     const double ts = aw.ts * rho * wa.ts / (1 - rho * wa.rs);   // :86
     const double tp = aw.tp * rho * wa.tp / (1 - rho * wa.rp);   // :89
     const double t = fmax(tp, ts);                               // augmentation.py:119
-    double fw = water_height / pavement_depth;                   // :122
+    double fw = wf.water_height / wf.pavement_depth;                  // :122
     fw = fw < 0 ? 0 : (fw > 1 ? 1 : fw);
     const double tw = (1 - fw) * refl + fw * t / ang;            // :123
     double v = rel * gc * tw;                                    // :126
@@ -595,6 +618,7 @@ __global__ __launch_bounds__(PB) void k_wet_apply(WetArgs w)
     const int64_t tile0 = (int64_t)blockIdx.x * SG_TILE;
     if (tile0 >= n) return;
     const PreFrame fr = a.fr[f];
+    const WetFrame wf = wet_frame(a, f, w.water_height, w.pavement_depth);
     const T *rows = (const T *)a.rows;
     int cnt_a = 0, cnt_b = 0;
     double gns[4], gds[4], angs[4], ins[4];                              // the thread's four rows side by side: every load first
@@ -617,7 +641,7 @@ __global__ __launch_bounds__(PB) void k_wet_apply(WetArgs w)
         const double gn = gns[q];
         if (fr.unchanged) { cls = 1; }                                   // frame returned as is (augmentation.py:51-52)
         else if (gn != gn) { cls = 1; }
-        else cls = wet_row_chain(a, fr, w.water_height, w.pavement_depth, gds[q], angs[q], ins[q], ni) ? 2 : 0;
+        else cls = wet_row_chain(wf, fr, gds[q], angs[q], ins[q], ni) ? 2 : 0;
         w.cls[base + r] = cls;
         if (cls == 2) w.new_i[base + r] = ni;                            // (read back for kept ground rows only: k_wet_scatter)
         cnt_a += cls == 1; cnt_b += cls == 2;
@@ -750,6 +774,7 @@ __global__ __launch_bounds__(PB) void k_wet_apply_aligned(WetAlignedArgs w)
     const int64_t tile0 = (int64_t)blockIdx.x * SG_TILE;
     if (tile0 >= n) return;
     const PreFrame fr = a.fr[f];
+    const WetFrame wf = wet_frame(a, f, w.water_height, w.pavement_depth);
     const T *rows = (const T *)a.rows;
     T *out = (T *)w.out_rows;
     const bool whole = (const void *)out != a.rows, same_keep = w.out_keep == a.keep;
@@ -786,7 +811,7 @@ __global__ __launch_bounds__(PB) void k_wet_apply_aligned(WetAlignedArgs w)
                 if (w.replace) { lab = (T)0; new_l = true; }             // :155-156
             } else {
                 double ni;
-                k = wet_row_chain(a, fr, w.water_height, w.pavement_depth, gds[q], angs[q], (double)si[q], ni) ? 1 : 0;
+                k = wet_row_chain(wf, fr, gds[q], angs[q], (double)si[q], ni) ? 1 : 0;
                 inten = (T)ni; lab = (T)1; new_i = new_l = true;         // :153, :159
             }
         }
@@ -895,6 +920,7 @@ static int wet_fit(SgPrepassScratch *s, PreArgs &a, const void *rows, int dtype,
     a.lines_override = wp->lines;
     a.rows = rows; a.frame_off = frame_off; a.frame_cnt = frame_cnt; a.keep = keep; a.n_frames = n_frames; a.plane = plane; a.delta = wp->delta;
     a.flat_earth = wp->flat_earth; a.rows_as_f64 = 1; a.noise_floor = wp->noise_floor; a.power_factor = wp->power_factor; a.status = status;
+    a.weather = wp->weather;
     int rc = estimate(s, a, dtype, n_total, max_frame, 1000, 0, false, st);
     if (rc) return rc;
     if (wp->estimation == 1) {                       // 'poly': the two quadratics replace the two lines

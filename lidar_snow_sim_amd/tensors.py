@@ -145,7 +145,8 @@ class AlignedResult(DeviceResult):
 
 class AlignedWetResult(AlignedResult):
     """An AlignedResult of the wet-ground stage (wet_ground_batch_aligned, augment_wet_batch_aligned): `flags` (n_frames, int32) is 1 where
-    a frame had fewer than 1000 present ground rows and came back as it was (augmentation.py:51-52), `counts` are the keep flags set after
+    a frame had fewer than 1000 present ground rows and came back as it was (augmentation.py:51-52) and 2 where the wet stage was not
+    asked for the frame (augment_wet_batch_aligned(weather=...) with the frame's wet gate off); `counts` are the keep flags set after
     the wet stage, `stats` the snowfall statistics (None for the wet-ground model on its own)."""
 
     def __init__(self, ctx, rows, keep_mask, counts, stats, status, offsets, stream, flags, keep=()):
@@ -293,6 +294,120 @@ def table_ids_for(eng, n_frames, particle_file_prefix, root_path, particles, ord
     else:
         ids = _sim._ArrayIds(eng, particles) if particles is not None else _sim._LazyFileIds(eng, particle_file_prefix, root_path)
     return np.ascontiguousarray(ids[orders.reshape(-1)].reshape(n_frames, nl), np.int32)
+
+
+def _prefix_list(particle_file_prefix, n_frames):
+    """None for ONE prefix, else the list of n_frames prefixes."""
+    if isinstance(particle_file_prefix, (str, bytes, os.PathLike)) or particle_file_prefix is None:
+        return None
+    prefixes = list(particle_file_prefix)
+    if len(prefixes) != n_frames:
+        raise ValueError(f"particle_file_prefix as a sequence needs one prefix per frame: {len(prefixes)} given for {n_frames} frames")
+    return prefixes
+
+
+def table_ids_per_frame(eng, prefixes, root_path, particles, orders, shuffle):
+    """table_ids_for with one prefix per frame (particles: None, 'device' or 'missing'): frames of one prefix share its resolved lines."""
+    if particles is not None and not isinstance(particles, str):
+        raise ValueError("a sequence of prefixes names table files (or 'device' / 'missing' tables): caller-owned arrays have no prefix")
+    nf = len(prefixes)
+    if orders is not None and len(orders) != nf:
+        raise ValueError("orders must be n_frames permutations of the laser lines")
+    out = np.empty((nf, eng.n_lasers), np.int32)
+    for f, prefix in enumerate(prefixes):
+        out[f] = table_ids_for(eng, 1, prefix, root_path, particles, None if orders is None else [orders[f]], shuffle)[0]
+    return out
+
+
+def weather_records(n_frames, snow=True, wet=True, water_height=0.001, pavement_depth=0.0012, noise_floor=0.7, power_factor=15, delta=0.5,
+                    device=None):
+    """The per-frame weather records of augment_wet_batch_aligned(weather=...): an n_frames x 8 float64 CUDA tensor
+    [snow, wet, water_height, pavement_depth, wet noise_floor, power_factor, delta, 0] (include/snowgpu.h).  Every argument is a scalar
+    (all frames alike), a sequence of n_frames values or a tensor of them; snow and wet are truth values (the record holds 0.0 or 1.0)."""
+    import torch
+    nf = int(n_frames)
+    dev = torch.device("cuda", torch.cuda.current_device() if device is None else int(device)) if not isinstance(device, torch.device) else device
+    rec = torch.zeros((nf, 8), dtype=torch.float64, device=dev)
+    for col, (name, v) in enumerate((("snow", snow), ("wet", wet), ("water_height", water_height), ("pavement_depth", pavement_depth),
+                                     ("noise_floor", noise_floor), ("power_factor", power_factor), ("delta", delta))):
+        if torch.is_tensor(v):
+            v = v.to(device=dev)
+        else:
+            v = torch.as_tensor(np.asarray(v), device=dev)
+        if col < 2:
+            v = (v != 0)
+        v = v.to(torch.float64)
+        if v.dim() > 1 or (v.dim() == 1 and v.shape[0] != nf):
+            raise ValueError(f"weather_records: {name} must be a scalar or hold one value per frame ({nf})")
+        rec[:, col] = v
+    return rec
+
+
+WEATHER_PER_FRAME = ("water_height", "pavement_depth", "noise_floor", "power_factor", "delta")
+
+
+class WeatherPlan:
+    """Which weather every frame of a training batch gets, drawn ON THE DEVICE (snowgpu_draw_weather_device): the snow and the wet gate
+    with probabilities p_snow / p_wet, one of `prefixes` (a snowfall setting: one table per laser line), the order of its tables over
+    the lasers (simulation.py:482-486), one of water_heights and one of pavement_depths; noise_floor, power_factor and delta are shared.
+
+        plan = WeatherPlan(prefixes, root_path, p_snow=0.5, p_wet=0.5, water_heights=(0.0005, 0.001), pavement_depths=(0.0012,))
+        table_ids, weather = plan.draw(n_frames)
+        augment_wet_batch_aligned(frames, None, bd, table_ids=table_ids, weather=weather, ...)
+        plan.step += 1
+
+    prefixes   the table sets (at most 64); particles: None (files under root_path), 'device' / 'missing' (sampled on the device, as for
+               table_ids_for) or one sequence of n_lasers arrays per prefix.  Every line of every set is resolved to a resident table here.
+    step       an int64 tensor of one element ON THE DEVICE: the draw reads it there, so a captured graph that holds draw(), the
+               augmentation and `plan.step += 1` draws anew on every replay.  Draws are Philox4x32-10 keyed by (seed; step, frame): the
+               same plan, seed and step give the same batch on every run; parity with the reference's random.shuffle is distributional.
+    set_ids    n_sets x n_lasers int32 device tensor of table ids."""
+
+    def __init__(self, prefixes, root_path=None, particles=None, p_snow=0.5, p_wet=0.5, water_heights=(0.001,), pavement_depths=(0.0012,),
+                 noise_floor=0.7, power_factor=15, delta=0.5, shuffle=True, seed=0, device=None, slot=0):
+        import torch
+        from . import engine as _engine
+        prefixes = [prefixes] if isinstance(prefixes, (str, bytes, os.PathLike)) else list(prefixes)
+        if not prefixes:
+            raise ValueError("WeatherPlan needs at least one prefix (one table set)")
+        index = torch.cuda.current_device() if device is None else (device.index if isinstance(device, torch.device) else int(device))
+        self.device = torch.device("cuda", index)
+        self.eng = _engine.get_engine(index, slot)
+        nl = self.eng.n_lasers
+        if particles is not None and not isinstance(particles, str) and len(particles) != len(prefixes):
+            raise ValueError("particles as arrays needs one sequence of tables per prefix")
+        ident = [list(range(nl))]
+        sets = [table_ids_for(self.eng, 1, pf, root_path, particles if particles is None or isinstance(particles, str) else particles[i], ident, False)[0]
+                for i, pf in enumerate(prefixes)]
+        self.prefixes = prefixes
+        self.set_ids = torch.from_numpy(np.ascontiguousarray(sets, np.int32)).to(self.device)
+        self.step = torch.zeros(1, dtype=torch.int64, device=self.device)
+        self.seed = int(seed)
+        self.struct = _native.weather_plan_struct(p_snow, p_wet, water_heights, pavement_depths, noise_floor, power_factor, delta, shuffle)
+
+    def draw(self, n_frames, out=None):
+        """(table_ids: n_frames x n_lasers int32, weather: n_frames x 8 float64) for the plan's current step, launched on torch's current
+        stream; out: an earlier pair to write into (static addresses for a captured graph)."""
+        import torch
+        nf, nl = int(n_frames), int(self.set_ids.shape[1])
+        if out is None:
+            out = (torch.empty((nf, nl), dtype=torch.int32, device=self.device), torch.empty((nf, 8), dtype=torch.float64, device=self.device))
+        tids, weather = out
+        if tuple(tids.shape) != (nf, nl) or tids.dtype != torch.int32 or tuple(weather.shape) != (nf, 8) or weather.dtype != torch.float64 or \
+                not tids.is_contiguous() or not weather.is_contiguous() or tids.device != self.device or weather.device != self.device:
+            raise ValueError("out must be (n_frames x n_lasers int32, n_frames x 8 float64) contiguous tensors on the plan's device")
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device)
+            run = _run_stream(torch, self.eng, self.device, stream)
+            if run is not stream:
+                run.wait_stream(stream)
+            try:
+                self.eng.ctx.draw_weather_device(nf, nl, int(self.set_ids.shape[0]), self.set_ids.data_ptr(), self.struct, self.seed,
+                                                 self.step.data_ptr(), tids.data_ptr(), weather.data_ptr(), run.cuda_stream)
+            finally:
+                if run is not stream:
+                    stream.wait_stream(run)
+        return tids, weather
 
 
 def _keep_mask(torch, keep, rows, offsets):
@@ -698,7 +813,7 @@ def wet_ground_batch_aligned(frames, keep=None, *, plane=None, water_height=0.00
 
 def augment_wet_batch_aligned(frames, particle_file_prefix, beam_divergence, shuffle=True, noise_floor=0.7, root_path=None, *, wet=None,
                               planes=None, orders=None, particles=None, thr_polys=None, device=None, slot=0, calib=None, sync=True,
-                              out=None, lane=None, in_place=False, keep=None, pre_crop=False, **_ignored):
+                              out=None, lane=None, in_place=False, keep=None, pre_crop=False, weather=None, table_ids=None, **_ignored):
     """augment() followed by ground_water_augmentation() on its output (pointcloud_viewer.py:2807-2821) for torch CUDA tensors with the
     ALIGNED result (snowgpu_augment_wet_batch_device_aligned): the snowfall stage finishes into rows in the input's order plus a keep
     mask, and the wet-ground stage rewrites those two arrays in place, skipping the rows the snowfall stage removed.  No compaction, a
@@ -709,6 +824,14 @@ def augment_wet_batch_aligned(frames, particle_file_prefix, beam_divergence, shu
     planes, thr_polys, orders, particles, calib, in_place, sync, out (an earlier AlignedWetResult), lane: as augment_batch(layout='aligned').
     keep, pre_crop  as augment_batch(layout='aligned'): an input keep mask for the snowfall stage (and the camera's view as one).  The
               result equals the masked snowfall call followed by wet_ground_batch_aligned(rows, keep) on its result.
+    weather   an F x 8 float64 CUDA tensor of per-frame weather records (weather_records, WeatherPlan.draw): the gates `snow` and `wet`
+              and the frame's water_height, pavement_depth, noise_floor, power_factor and delta, read on the device
+              (snowgpu_augment_weather_batch_device_aligned).  A frame with both gates off comes back bit for bit, one with the snow gate
+              off as wet_ground_batch_aligned returns it, one with the wet gate off as the aligned snowfall call does, with flag_f = 2.
+              `wet` may then carry only flat_earth, replace, plane, estimation_method and poly_seed; a per-frame field raises ValueError.
+    table_ids an F x n_lasers int32 CUDA tensor of table ids used as it is (WeatherPlan.draw): no host shuffle, no upload; orders= or
+              particles= beside it raises ValueError.
+    particle_file_prefix  may also be a sequence of F prefixes: every frame reads its own table set (ids built on the host).
     Returns an AlignedWetResult (sync=False) or its frames(): [(stats, rows_f, keep_f, flag_f)] -- stats the snowfall statistics,
     keep_f true where the CHAIN returns the row, flag_f = 1 where the wet stage found fewer than 1000 present ground rows and left the
     frame as the snowfall stage made it.
@@ -723,12 +846,20 @@ def augment_wet_batch_aligned(frames, particle_file_prefix, beam_divergence, shu
                          "host arrays get the reference's compacted return value from augment_batch / ground_water_augmentation")
     import torch
     from . import engine as _engine
+    if weather is not None and wet is not None and set(wet) & set(WEATHER_PER_FRAME):
+        raise ValueError(f"with weather= the per-frame fields {sorted(set(wet) & set(WEATHER_PER_FRAME))} come from the weather records, not from wet=")
+    if table_ids is not None and (orders is not None or particles is not None):
+        raise ValueError("table_ids= are used as they are: orders= and particles= have nothing to act on")
     w, wet_plane, method, seed = _wet_arguments(wet)
     rows, offsets = _rows_where_they_lie(torch, frames) if in_place else _as_batch(torch, frames)[:2]
     dev = rows.device
     if device is not None and int(device) != dev.index:
         raise ValueError(f"the tensors live on {dev}, device={device} was asked for")
     eng = _engine.get_engine(dev.index, slot if lane is None else LANE_SLOT0 + int(lane))
+    for name, t, shape, dt in (("weather", weather, (len(offsets) - 1, 8), torch.float64), ("table_ids", table_ids, (len(offsets) - 1, eng.n_lasers), torch.int32)):
+        if t is not None and not (torch.is_tensor(t) and t.is_cuda and t.device == dev and tuple(t.shape) == shape and t.dtype == dt and t.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous {shape[0]} x {shape[1]} {dt} CUDA tensor on the device of the rows")
+    prefixes = None if table_ids is not None else _prefix_list(particle_file_prefix, len(offsets) - 1)
     if lane is not None and not eng.__dict__.get("_lane_serial"):
         eng.ctx.set_serial(True)                      # (a compute lane runs its batches on one stream: augment_batch)
         eng.__dict__["_lane_serial"] = True
@@ -736,17 +867,22 @@ def augment_wet_batch_aligned(frames, particle_file_prefix, beam_divergence, shu
     if nf == 0:
         return []
     if n == 0:
-        return _empty_aligned_wet(torch, eng, rows, nf, offsets, True, sync)
+        res = _empty_aligned_wet(torch, eng, rows, nf, offsets, True, False)
+        if weather is not None:                     # (no row anywhere: "not asked" where the wet gate is off)
+            res.flags = torch.where(weather[:, 1] == 0, 2, 1).to(torch.int32)
+        return res.frames() if sync else res
     if keep is not None:
         keep = _keep_mask(torch, keep, rows, offsets)
     code = 0 if rows.dtype == torch.float32 else 1
     up = _uploads(eng)
     with torch.cuda.device(dev):
-        tids = table_ids_for(eng, nf, particle_file_prefix, root_path, particles, orders, shuffle)
+        if table_ids is None:
+            tids = table_ids_for(eng, nf, particle_file_prefix, root_path, particles, orders, shuffle) if prefixes is None else \
+                table_ids_per_frame(eng, prefixes, root_path, particles, orders, shuffle)
         stream = torch.cuda.current_stream(dev)
         run = _run_stream(torch, eng, dev, stream, lane)
         d_off = up.get(torch, dev, offsets, run)
-        d_tids = up.get(torch, dev, tids, run)
+        d_tids = up.get(torch, dev, tids, run) if table_ids is None else table_ids
         d_poly = d_plane = None
         if thr_polys is not None:
             d_poly = up.get(torch, dev, np.ascontiguousarray(thr_polys, np.float64).reshape(nf, 3), run)
@@ -757,7 +893,7 @@ def augment_wet_batch_aligned(frames, particle_file_prefix, beam_divergence, shu
         if run is not stream:
             run.wait_stream(stream)
             if lane is not None:                    # (tensors of the caller's stream used on the lane's: the allocator must know)
-                for t in (rows, o_rows, o_keep, o_cnt, o_st, o_status, o_flags) + (() if keep is None else (keep,)):
+                for t in (rows, o_rows, o_keep, o_cnt, o_st, o_status, o_flags) + tuple(t for t in (keep, weather, table_ids) if t is not None):
                     t.record_stream(run)
         ptr = lambda t: 0 if t is None else t.data_ptr()   # noqa: E731
         with eng.batch_lock:
@@ -770,12 +906,20 @@ def augment_wet_batch_aligned(frames, particle_file_prefix, beam_divergence, shu
             if method != 'linear':
                 eng.ctx.set_wet_estimation(method, seed)
             try:
-                eng.ctx.augment_wet_batch_device_aligned_masked(nf, n, int(np.diff(offsets).max()), d_off.data_ptr(), rows.data_ptr(), code,
-                                                         d_tids.data_ptr(), float(beam_divergence), ptr(d_poly), ptr(d_plane),
-                                                         float(noise_floor), 0, ptr(keep), o_rows.data_ptr(), o_keep.data_ptr(), o_cnt.data_ptr(),
-                                                         o_st.data_ptr(), 0, o_status.data_ptr(), run.cuda_stream, ptr(d_wet_plane),
-                                                         w["water_height"], w["pavement_depth"], w["noise_floor"], w["power_factor"],
-                                                         w["flat_earth"], w["delta"], w["replace"], o_flags.data_ptr())
+                if weather is not None:
+                    eng.ctx.augment_weather_batch_device_aligned(nf, n, int(np.diff(offsets).max()), d_off.data_ptr(), rows.data_ptr(), code,
+                                                                 d_tids.data_ptr(), float(beam_divergence), ptr(d_poly), ptr(d_plane),
+                                                                 float(noise_floor), 0, ptr(keep), o_rows.data_ptr(), o_keep.data_ptr(),
+                                                                 o_cnt.data_ptr(), o_st.data_ptr(), 0, o_status.data_ptr(), run.cuda_stream,
+                                                                 ptr(d_wet_plane), weather.data_ptr(), w["flat_earth"], w["replace"],
+                                                                 o_flags.data_ptr())
+                else:
+                    eng.ctx.augment_wet_batch_device_aligned_masked(nf, n, int(np.diff(offsets).max()), d_off.data_ptr(), rows.data_ptr(), code,
+                                                                    d_tids.data_ptr(), float(beam_divergence), ptr(d_poly), ptr(d_plane),
+                                                                    float(noise_floor), 0, ptr(keep), o_rows.data_ptr(), o_keep.data_ptr(), o_cnt.data_ptr(),
+                                                                    o_st.data_ptr(), 0, o_status.data_ptr(), run.cuda_stream, ptr(d_wet_plane),
+                                                                    w["water_height"], w["pavement_depth"], w["noise_floor"], w["power_factor"],
+                                                                    w["flat_earth"], w["delta"], w["replace"], o_flags.data_ptr())
             finally:
                 if run is not stream and lane is None:
                     stream.wait_stream(run)
@@ -784,5 +928,5 @@ def augment_wet_batch_aligned(frames, particle_file_prefix, beam_divergence, shu
                 if method != 'linear':
                     eng.ctx.set_wet_estimation('linear')
     res = AlignedWetResult(eng.ctx, o_rows, o_keep, o_cnt, o_st, o_status, offsets, stream if lane is None else run, o_flags,
-                           keep=(rows, d_off, d_tids, d_poly, d_plane, d_wet_plane, keep))
+                           keep=(rows, d_off, d_tids, d_poly, d_plane, d_wet_plane, keep, weather))
     return res.frames() if sync else res

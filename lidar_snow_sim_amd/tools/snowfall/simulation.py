@@ -366,9 +366,11 @@ def augment(pc: np.ndarray, particle_file_prefix: str, beam_divergence: float, s
     return res
 
 
-def augment_wet_batch_aligned(frames, particle_file_prefix: str, beam_divergence: float, *args, **kw):
+def augment_wet_batch_aligned(frames, particle_file_prefix, beam_divergence: float, *args, **kw):
     """augment() followed by ground_water_augmentation() (pointcloud_viewer.py:2807-2821) on torch CUDA tensors with the aligned result:
     rows in the input's order and dtype, a keep mask, per-frame flags, nothing read on the host.  lidar_snow_sim_amd.tensors
-    .augment_wet_batch_aligned, which documents the arguments; host arrays raise ValueError there."""
+    .augment_wet_batch_aligned, which documents the arguments; host arrays raise ValueError there.  particle_file_prefix: one prefix, a
+    sequence of one prefix per frame, or None with table_ids=; weather= (tensors.weather_records, tensors.WeatherPlan) gives every frame
+    its own gates and wet settings."""
     from ... import tensors as _tensors
     return _tensors.augment_wet_batch_aligned(frames, particle_file_prefix, beam_divergence, *args, **kw)
