@@ -1,0 +1,133 @@
+// sg_device_args.h -- what the *_batch_device* entries (snowgpu_device.cpp) take in common, and the one place that refuses a call of
+// theirs: pure argument checks on plain data.  Nothing of HIP is included, so the whole refusal matrix runs on a machine without a device
+// (tests/host_harness/device_refusals.cpp).
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#include <string>
+
+// the scalars of ground_water_augmentation() (wet_ground/augmentation.py:25)
+struct SgWetScalars {
+    double water_height, pavement_depth, noise_floor, power_factor, delta;
+    int flat_earth, replace;
+};
+
+struct SgDeviceArgs {
+    const char *who;                  // the entry's name, as its messages begin
+    int n_frames;
+    int64_t n_total, max_frame_rows;
+    int dtype;
+    const int64_t *frame_off;
+    const void *rows;
+    const int32_t *table_ids;
+    double beam_div_deg;
+    const double *thr_poly, *plane;
+    double noise_floor;
+    const int32_t *perm;
+    const uint8_t *keep_in;
+    void *out_rows;
+    int32_t *out_src;                 // compact entries
+    uint8_t *out_keep;                // aligned entries
+    int64_t *out_counts, *out_stats;
+    double *out_thr_poly;
+    int32_t *out_flags, *status;
+    void *stream;
+    // the wet stage
+    const double *wet_plane;
+    SgWetScalars wet;
+    const double *weather;            // per-frame records: they replace the five wet scalars
+};
+
+// the context settings the checks read
+struct SgCtxView {
+    bool thr_fn;                      // a threshold callback is set
+    int result_mode;
+    int plane_method;                 // SG_PLANE_*: 0 is `reference`
+    size_t n_tables;
+};
+
+struct SgEntryShape {
+    bool tables;                      // a snowfall stage: table ids and statistics
+    bool aligned;                     // rows in input order with a keep mask (else the compact layout with source indices)
+    bool masked;                      // the masked front end runs
+    bool wet;                         // a wet stage: per-frame flags
+    bool weather;                     // per-frame weather records
+    bool empty_null_ok;               // rows and outputs may be NULL for a batch without rows
+};
+
+constexpr SgEntryShape SG_SHAPE_COMPACT      = {true,  false, false, false, false, false};   // snowgpu_augment_batch_device
+constexpr SgEntryShape SG_SHAPE_COMPACT_WET  = {true,  false, false, true,  false, false};   // snowgpu_augment_wet_batch_device
+constexpr SgEntryShape SG_SHAPE_ALIGNED      = {true,  true,  false, false, false, false};   // snowgpu_augment_batch_device_aligned
+constexpr SgEntryShape SG_SHAPE_WET_ONLY     = {false, true,  false, true,  false, true};    // snowgpu_wet_ground_batch_device_aligned
+constexpr SgEntryShape SG_SHAPE_ALIGNED_WET  = {true,  true,  false, true,  false, false};   // snowgpu_augment_wet_batch_device_aligned
+constexpr SgEntryShape SG_SHAPE_MASKED       = {true,  true,  true,  false, false, false};   // ..._aligned_masked with a mask and rows
+constexpr SgEntryShape SG_SHAPE_MASKED_WET   = {true,  true,  true,  true,  false, false};   // ..._wet_batch_device_aligned_masked, likewise
+constexpr SgEntryShape SG_SHAPE_WEATHER      = {true,  true,  true,  true,  true,  false};   // snowgpu_augment_weather_batch_device_aligned
+
+constexpr int SG_ARGS_INVALID = 1;    // SNOWGPU_E_INVALID (include/snowgpu.h; snowgpu_device.cpp asserts that they agree)
+
+static inline int64_t sg_max_frame(int64_t max_frame_rows, int64_t n_total)
+{
+    return (max_frame_rows > 0 && max_frame_rows <= n_total) ? max_frame_rows : n_total;
+}
+
+static inline int64_t sg_uniform_rows(int64_t max_frame_rows, int n_frames, int64_t n_total)
+{
+    return (max_frame_rows > 0 && max_frame_rows * (int64_t)n_frames == n_total) ? max_frame_rows : 0;
+}
+
+// two arrays of `bytes` bytes that share some of them without being the same array
+static inline bool sg_overlap(const void *in, const void *out, size_t bytes)
+{
+    const uintptr_t a = (uintptr_t)in, o = (uintptr_t)out;
+    return a && o != a && o < a + bytes && a < o + bytes;
+}
+
+static inline int sg_refuse(const char *who, const char *what, std::string *msg)
+{
+    if (msg) *msg = std::string(who) + what;
+    return SG_ARGS_INVALID;
+}
+
+// `beside`: what makes the batch a masked one
+static inline int sg_refuse_perm(const char *who, const char *beside, std::string *msg)
+{
+    if (msg) *msg = std::string(who) + ": d_perm with " + beside + "; a caller's permutation indexes the rows of the frames it was made for, not the present ones";
+    return SG_ARGS_INVALID;
+}
+
+// calculate_plane (augmentation.py:41) for an aligned wet stage: the method `reference` returns a constant and reads no row.  The two
+// estimators crop the cloud into a list first; under a mask that list -- and with it the RANSAC draws -- has another order.
+// The fused entries ask before anything is launched; the wet stage asks again where it needs the plane, which is the first time for
+// snowgpu_wet_ground_batch_device_aligned: behind its empty batch and behind the caller's lines.
+static inline int sg_check_wet_plane(const char *who, const double *wet_plane, int plane_method, std::string *msg)
+{
+    if (wet_plane || plane_method == 0) return 0;
+    return sg_refuse(who, ": a NULL wet plane needs the plane method 'reference'; 'lsq' and 'ransac' crop the rows and have no masked form: pass the plane", msg);
+}
+
+// 0, or SG_ARGS_INVALID with *msg (built on this path only).  The order is part of the ABI: it decides which message a doubly wrong call gets.
+static inline int sg_check_device_args(const SgDeviceArgs &a, const SgCtxView &c, const SgEntryShape &s, std::string *msg)
+{
+    if (s.weather && !a.weather) return sg_refuse(a.who, ": d_weather is NULL; one record of 8 doubles per frame, in device memory", msg);
+    const bool buffers = s.empty_null_ok ? (a.n_total > 0 && (!a.rows || !a.out_rows || !a.out_keep))
+                                         : ((a.n_total > 0 && !a.rows) || !a.out_rows || !(s.aligned ? (const void *)a.out_keep : (const void *)a.out_src));
+    if (a.n_frames <= 0 || a.n_total < 0 || !a.frame_off || buffers || (s.tables && (!a.table_ids || !a.out_stats)) || !a.out_counts ||
+        (s.wet && !a.out_flags) || !a.status || (a.dtype != 0 && a.dtype != 1))
+        return sg_refuse(a.who, ": null pointer or bad dtype", msg);
+    if (a.n_total >= ((int64_t)1 << 31)) return sg_refuse("", "batch too large: split it below 2^31 rows", msg);
+    if (!s.aligned) return 0;                      // the compact entries refuse nothing else
+    if (c.thr_fn) return sg_refuse(a.who, ": a threshold callback is set; it finishes batches through the compaction only", msg);
+    if (c.result_mode != 0) return sg_refuse(a.who, ": the packed result transfer is set; it is a form of the compacted result", msg);
+    if (sg_overlap(a.rows, a.out_rows, (size_t)a.n_total * 5 * (a.dtype == 0 ? 4 : 8)))
+        return sg_refuse(a.who, ": d_out_rows overlaps d_rows; pass d_rows itself (in place) or a buffer apart from it", msg);
+    if (sg_overlap(a.keep_in, a.out_keep, (size_t)a.n_total))
+        return sg_refuse(a.who, ": d_out_keep overlaps d_keep_in; pass d_keep_in itself or a buffer apart from it", msg);
+    if (s.tables && s.wet)                         // (before anything is launched)
+        if (int rc = sg_check_wet_plane(a.who, a.wet_plane, c.plane_method, msg)) return rc;
+    if (s.masked && a.perm) return sg_refuse_perm(a.who, s.weather ? "d_weather" : "d_keep_in", msg);
+    // (what run_batch needs for the segment order of the pass over all rows; the linear order reads n_total as an exact count)
+    if (s.masked && a.n_total > 0 && (c.n_tables > 65536 || a.n_frames > (1 << 22)))
+        return sg_refuse(a.who, ": a masked batch needs at most 65536 tables and 2^22 frames", msg);
+    return 0;
+}

@@ -1,6 +1,7 @@
-// sg_host.h -- what the three host translation units of libsnowgpu.so share: the context, the description of one batch on the
+// sg_host.h -- what the four host translation units of libsnowgpu.so share: the context, the description of one batch on the
 // device, the error macros, the guard of the host-pointer entries and the functions the parts call in each other.
-//   snowgpu_api.cpp    context, settings, tables, every *_device entry
+//   snowgpu_api.cpp    context, settings, tables, sampler, profile hooks
+//   snowgpu_device.cpp every entry that takes device pointers (their arguments and refusals: sg_device_args.h)
 //   snowgpu_batch.cpp  the launch sequence of one batch (run_batch)
 //   snowgpu_host.cpp   every entry that takes host pointers (uploads, the chunk pipeline, downloads)
 #pragma once
@@ -20,6 +21,7 @@
 #include "sg_prepass.h"
 #include "sg_plane.h"
 #include "sg_assemble.h"
+#include "sg_device_args.h"
 
 #pragma GCC visibility push(hidden)      // nothing below is part of the library's ABI
 
@@ -283,6 +285,9 @@ int run_batch(snowgpu_ctx *ctx, BatchDev &b);                 // snowgpu_batch.c
 int run_compaction(snowgpu_ctx *ctx, BatchDev &b);
 int status_to_error(snowgpu_ctx *ctx, const int32_t st[8]);
 int node_of_device(int device);                               // snowgpu_host.cpp
+SgFov make_fov(const double *v2c, const double *r0, const double *p2, int img_h, int img_w);      // snowgpu_api.cpp
+// snowgpu_device.cpp: the SgWetParams of one wet-ground call; take_lines: consume what snowgpu_set_wet_lines left (uploaded and waited for on st)
+int wet_settings(snowgpu_ctx *ctx, const SgWetScalars &w, int n_frames, bool take_lines, hipStream_t st, SgWetParams *wp);
 
 #pragma GCC visibility pop
 

@@ -1,13 +1,11 @@
-// snowgpu_api.cpp -- the C ABI of libsnowgpu.so (include/snowgpu.h) as far as it takes no host rows: context, streams, settings,
-// lasers, table filing, the sampler, the profile hooks and every *_device entry.  Host-side C++; the launch sequence of a batch is
-// snowgpu_batch.cpp, the host-pointer entries snowgpu_host.cpp, every kernel lives in a .hip file.
+// snowgpu_api.cpp -- the C ABI of libsnowgpu.so (include/snowgpu.h) as far as it takes no rows: context, streams, settings, lasers,
+// table filing, the sampler and the profile hooks.  Host-side C++; the launch sequence of a batch is snowgpu_batch.cpp, the
+// device-pointer entries snowgpu_device.cpp, the host-pointer entries snowgpu_host.cpp, every kernel lives in a .hip file.
 #include <dlfcn.h>
 
 #include "sg_host.h"
-#include "sg_launch.h"      // sg_tiles
 #include "sg_table_host.h"
 #include "sg_range_index.h"  // SG_QS_FITS, SG_QS_WORDS
-#include "sg_weather.h"      // SgWeatherDraw and the limits of the draw
 #include <cmath>
 
 // simulation.py:106-116: R = np.round(np.linspace(0, 120 + c*tau_h, 1230), 2).
@@ -355,66 +353,6 @@ extern "C" int snowgpu_status_error(snowgpu_ctx *ctx, const int32_t *status8)
     return status_to_error(ctx, status8);
 }
 
-extern "C" int snowgpu_augment_batch_device(snowgpu_ctx *ctx, int n_frames, int64_t n_total, int64_t max_frame_rows,
-                                            const int64_t *d_frame_offsets,
-                                            const void *d_rows, int dtype, const int32_t *d_table_ids,
-                                            double beam_divergence_deg, const double *d_thr_poly, const double *d_plane,
-                                            double noise_floor, const int32_t *d_perm, void *d_out_rows, int32_t *d_out_src,
-                                            int64_t *d_out_counts, int64_t *d_out_stats, double *d_out_thr_poly,
-                                            int32_t *d_status, void *stream)
-{
-    if (!ctx) return SNOWGPU_E_INVALID;
-    if (n_frames <= 0 || n_total < 0 || !d_frame_offsets || (n_total > 0 && !d_rows) || !d_table_ids || !d_out_rows ||
-        !d_out_src || !d_out_counts || !d_out_stats || !d_status || (dtype != 0 && dtype != 1))
-        return fail(ctx, SNOWGPU_E_INVALID, "snowgpu_augment_batch_device: null pointer or bad dtype");
-    if (n_total >= ((int64_t)1 << 31)) return fail(ctx, SNOWGPU_E_INVALID, "batch too large: split it below 2^31 rows");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    BatchDev b{};
-    b.n_frames = n_frames; b.n_total = n_total; b.max_frame = (max_frame_rows > 0 && max_frame_rows <= n_total) ? max_frame_rows : n_total;
-    b.frame_off = d_frame_offsets;
-    b.uniform_rows = (max_frame_rows > 0 && max_frame_rows * (int64_t)n_frames == n_total) ? max_frame_rows : 0; b.rows = d_rows;
-    b.dtype = dtype; b.table_ids = d_table_ids; b.beam_div_deg = beam_divergence_deg; b.thr_poly = d_thr_poly;
-    b.plane = d_plane; b.noise_floor = noise_floor; b.perm = d_perm; b.out_rows = d_out_rows; b.out_src = d_out_src;
-    b.out_counts = d_out_counts; b.out_stats = d_out_stats; b.out_thr_poly = d_out_thr_poly; b.status = d_status;
-    b.stream = stream ? (hipStream_t)stream : ctx->stream;
-    return run_batch(ctx, b);
-}
-
-// snowgpu_augment_batch_device with the ALIGNED result layout: every row of the input comes back at its own index (d_out_rows, which may be
-// d_rows itself), d_out_keep says which of them the reference would have returned.  Same launch sequence up to the last step, which is one
-// kernel (k_finish_aligned) instead of the three of the compaction.
-extern "C" int snowgpu_augment_batch_device_aligned(snowgpu_ctx *ctx, int n_frames, int64_t n_total, int64_t max_frame_rows,
-                                                    const int64_t *d_frame_offsets, const void *d_rows, int dtype, const int32_t *d_table_ids,
-                                                    double beam_divergence_deg, const double *d_thr_poly, const double *d_plane,
-                                                    double noise_floor, const int32_t *d_perm, void *d_out_rows, uint8_t *d_out_keep,
-                                                    int64_t *d_out_counts, int64_t *d_out_stats, double *d_out_thr_poly,
-                                                    int32_t *d_status, void *stream)
-{
-    if (!ctx) return SNOWGPU_E_INVALID;
-    if (n_frames <= 0 || n_total < 0 || !d_frame_offsets || (n_total > 0 && !d_rows) || !d_table_ids || !d_out_rows ||
-        !d_out_keep || !d_out_counts || !d_out_stats || !d_status || (dtype != 0 && dtype != 1))
-        return fail(ctx, SNOWGPU_E_INVALID, "snowgpu_augment_batch_device_aligned: null pointer or bad dtype");
-    if (n_total >= ((int64_t)1 << 31)) return fail(ctx, SNOWGPU_E_INVALID, "batch too large: split it below 2^31 rows");
-    if (ctx->thr_fn) return fail(ctx, SNOWGPU_E_INVALID, "snowgpu_augment_batch_device_aligned: a threshold callback is set; it finishes batches through the compaction only");
-    if (ctx->result_mode != 0) return fail(ctx, SNOWGPU_E_INVALID, "snowgpu_augment_batch_device_aligned: the packed result transfer is set; it is a form of the compacted result");
-    {
-        const size_t bytes = (size_t)n_total * 5 * (dtype == 0 ? 4 : 8);
-        const char *a = (const char *)d_rows, *o = (const char *)d_out_rows;
-        if (o != a && o < a + bytes && a < o + bytes)
-            return fail(ctx, SNOWGPU_E_INVALID, "snowgpu_augment_batch_device_aligned: d_out_rows overlaps d_rows; pass d_rows itself (in place) or a buffer apart from it");
-    }
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    BatchDev b{};
-    b.n_frames = n_frames; b.n_total = n_total; b.max_frame = (max_frame_rows > 0 && max_frame_rows <= n_total) ? max_frame_rows : n_total;
-    b.frame_off = d_frame_offsets;
-    b.uniform_rows = (max_frame_rows > 0 && max_frame_rows * (int64_t)n_frames == n_total) ? max_frame_rows : 0; b.rows = d_rows;
-    b.dtype = dtype; b.table_ids = d_table_ids; b.beam_div_deg = beam_divergence_deg; b.thr_poly = d_thr_poly;
-    b.plane = d_plane; b.noise_floor = noise_floor; b.perm = d_perm; b.out_rows = d_out_rows; b.out_src = nullptr; b.out_keep = d_out_keep;
-    b.out_counts = d_out_counts; b.out_stats = d_out_stats; b.out_thr_poly = d_out_thr_poly; b.status = d_status;
-    b.stream = stream ? (hipStream_t)stream : ctx->stream;
-    return run_batch(ctx, b);
-}
-
 extern "C" int snowgpu_sample_table(snowgpu_ctx *ctx, int table_id, double occupancy_ratio, double diameter_scale_mm, double r_0,
                                     uint64_t seed, double *xyr_out, int64_t cap, int64_t *n_out)
 {
@@ -571,7 +509,6 @@ extern "C" int snowgpu_set_exact_math(snowgpu_ctx *ctx, int on)
     return SNOWGPU_OK;
 }
 
-
 extern "C" int snowgpu_set_serial(snowgpu_ctx *ctx, int on)
 {
     if (!ctx) return SNOWGPU_E_INVALID;
@@ -646,372 +583,6 @@ extern "C" int snowgpu_profile_end(snowgpu_ctx *ctx, double *beam_kernel_ms, int
     return SNOWGPU_OK;
 }
 
-// augment() followed by ground_water_augmentation() on its output (pointcloud_viewer.py:2807-2821) as ONE launch
-// sequence on the caller's stream: the snowfall rows are compacted into context scratch, the wet-ground kernels read
-// them there (rows of frame f: [off[f], off[f] + snowfall count[f])), and a last kernel composes the source indices.
-// No host copy, no synchronisation, no allocation after the first call of a given size.
-extern "C" int snowgpu_augment_wet_batch_device(snowgpu_ctx *ctx, int n_frames, int64_t n_total, int64_t max_frame_rows,
-                                                const int64_t *d_frame_offsets, const void *d_rows, int dtype,
-                                                const int32_t *d_table_ids, double beam_divergence_deg, const double *d_thr_poly,
-                                                const double *d_plane, double noise_floor, const int32_t *d_perm,
-                                                const double *d_wet_plane, double water_height, double pavement_depth,
-                                                double wet_noise_floor, double power_factor, int flat_earth, double delta, int replace,
-                                                double *d_out_rows, int32_t *d_out_src, int64_t *d_out_counts, int64_t *d_out_stats,
-                                                int32_t *d_out_flags, int32_t *d_status, void *stream)
-{
-    if (!ctx) return SNOWGPU_E_INVALID;
-    if (n_frames <= 0 || n_total < 0 || !d_frame_offsets || (n_total > 0 && !d_rows) || !d_table_ids || !d_out_rows ||
-        !d_out_src || !d_out_counts || !d_out_stats || !d_out_flags || !d_status || (dtype != 0 && dtype != 1))
-        return fail(ctx, SNOWGPU_E_INVALID, "snowgpu_augment_wet_batch_device: null pointer or bad dtype");
-    if (n_total >= ((int64_t)1 << 31)) return fail(ctx, SNOWGPU_E_INVALID, "batch too large: split it below 2^31 rows");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    const size_t esz = dtype == 0 ? 4 : 8, n = (size_t)n_total;
-    ENSURE(ctx, ctx->snow_rows, std::max<size_t>(n * 5 * esz, 8));
-    ENSURE(ctx, ctx->snow_src, std::max<size_t>(n, 1));
-    ENSURE(ctx, ctx->snow_counts, (size_t)n_frames);
-    BatchDev b{};
-    b.n_frames = n_frames; b.n_total = n_total; b.max_frame = (max_frame_rows > 0 && max_frame_rows <= n_total) ? max_frame_rows : n_total;
-    b.frame_off = d_frame_offsets;
-    b.uniform_rows = (max_frame_rows > 0 && max_frame_rows * (int64_t)n_frames == n_total) ? max_frame_rows : 0; b.rows = d_rows;
-    b.dtype = dtype; b.table_ids = d_table_ids; b.beam_div_deg = beam_divergence_deg; b.thr_poly = d_thr_poly;
-    b.plane = d_plane; b.noise_floor = noise_floor; b.perm = d_perm; b.out_rows = ctx->snow_rows.p; b.out_src = ctx->snow_src.p;
-    b.out_counts = ctx->snow_counts.p; b.out_stats = d_out_stats; b.out_thr_poly = nullptr; b.status = d_status;
-    b.stream = stream ? (hipStream_t)stream : ctx->stream;
-    int rc = run_batch(ctx, b);
-    if (rc) return rc;
-    if (n == 0) {
-        HIPCHK(ctx, hipMemsetAsync(d_out_counts, 0, sizeof(int64_t) * (size_t)n_frames, b.stream));
-        HIPCHK(ctx, hipMemsetAsync(d_out_flags, 0, sizeof(int32_t) * (size_t)n_frames, b.stream));
-        return SNOWGPU_OK;
-    }
-    SgWetParams wp{};
-    wp.water_height = water_height; wp.pavement_depth = pavement_depth; wp.noise_floor = wet_noise_floor;
-    wp.power_factor = power_factor; wp.flat_earth = flat_earth; wp.delta = delta; wp.replace = replace;
-    wp.estimation = ctx->wet_estimation; wp.seed = ctx->wet_seed;
-    ENSURE(ctx, ctx->wet_fit, (size_t)n_frames * 8);
-    wp.fit_out = ctx->wet_fit.p; ctx->wet_fit_frames = n_frames;
-    int e = 0;
-    if (!d_wet_plane) {      // wet_ground/augmentation.py:41 calculate_plane(pointcloud) -- here the snowfall result -- on the device
-        ENSURE(ctx, ctx->wet_plane_est, (size_t)n_frames * 4);
-        e = sg_plane_run(&ctx->plane_scr, &ctx->plane_par, ctx->snow_rows.p, dtype, d_frame_offsets, ctx->snow_counts.p, n_frames, n_total, b.max_frame,
-                         ctx->wet_plane_est.p, nullptr, b.stream);
-        d_wet_plane = ctx->wet_plane_est.p;
-    }
-    // (the source rows of the chained result -- final row -> snowfall row -> input row -- are composed as the wet scatter writes them)
-    wp.src_first = ctx->snow_src.p;
-    if (!e) e = sg_wet_run(&ctx->prepass, ctx->snow_rows.p, dtype, d_frame_offsets, ctx->snow_counts.p, n_frames, n_total, b.max_frame,
-                       d_wet_plane, &wp, d_out_rows, d_out_src, d_out_counts, d_out_flags, d_status, b.stream);
-    if (e) return fail(ctx, SNOWGPU_E_HIP, std::string("wet ground: ") + (e > 0 ? hipGetErrorString((hipError_t)e) : "allocation"));
-    return SNOWGPU_OK;
-}
-
-// ---- the wet-ground model with the ALIGNED result ------------------------------------------------------------------------------------
-// What the two aligned entries refuse alike (as snowgpu_augment_batch_device_aligned does): a context that finishes batches through the
-// compaction, and outputs that overlap their inputs without being them.
-static int aligned_wet_refusals(snowgpu_ctx *ctx, const char *who, int64_t n_total, int dtype, const void *rows, const void *out_rows,
-                                const uint8_t *keep_in, const uint8_t *out_keep)
-{
-    const std::string name(who);
-    if (ctx->thr_fn) return fail(ctx, SNOWGPU_E_INVALID, name + ": a threshold callback is set; it finishes batches through the compaction only");
-    if (ctx->result_mode != 0) return fail(ctx, SNOWGPU_E_INVALID, name + ": the packed result transfer is set; it is a form of the compacted result");
-    const size_t bytes = (size_t)n_total * 5 * (dtype == 0 ? 4 : 8);
-    const char *a = (const char *)rows, *o = (const char *)out_rows;
-    if (a && o != a && o < a + bytes && a < o + bytes)
-        return fail(ctx, SNOWGPU_E_INVALID, name + ": d_out_rows overlaps d_rows; pass d_rows itself (in place) or a buffer apart from it");
-    const uint8_t *k = keep_in, *ok = out_keep;
-    if (k && ok != k && ok < k + (size_t)n_total && k < ok + (size_t)n_total)
-        return fail(ctx, SNOWGPU_E_INVALID, name + ": d_out_keep overlaps d_keep_in; pass d_keep_in itself or a buffer apart from it");
-    return SNOWGPU_OK;
-}
-
-// The wet stage of both aligned entries, on `st`: the plane (the caller's, or the constant one of the plane method `reference`), the
-// context's wet settings (estimation method and seed, the caller's lines, the fit's export) and sg_wet_run_aligned.
-static int aligned_wet_stage(snowgpu_ctx *ctx, const char *who, int n_frames, int64_t n_total, int64_t max_frame, const int64_t *d_frame_offsets,
-                             const void *d_rows, int dtype, const uint8_t *d_keep_in, const double *d_plane, double water_height,
-                             double pavement_depth, double noise_floor, double power_factor, int flat_earth, double delta, int replace,
-                             void *d_out_rows, uint8_t *d_out_keep, int64_t *d_out_counts, int32_t *d_out_flags, int32_t *d_status, hipStream_t st,
-                             const double *d_weather = nullptr /* per-frame records: they replace the five wet scalars */)
-{
-    const std::string name(who);
-    SgWetParams wp{};
-    wp.weather = d_weather;
-    wp.water_height = water_height; wp.pavement_depth = pavement_depth; wp.noise_floor = noise_floor;
-    wp.power_factor = power_factor; wp.flat_earth = flat_earth; wp.delta = delta; wp.replace = replace;
-    wp.estimation = ctx->wet_estimation; wp.seed = ctx->wet_seed;
-    ENSURE(ctx, ctx->wet_fit, (size_t)n_frames * 8);
-    wp.fit_out = ctx->wet_fit.p; ctx->wet_fit_frames = n_frames;
-    if (!ctx->wet_lines.empty() && ctx->wet_estimation != 0) { ctx->wet_lines.clear(); return fail(ctx, SNOWGPU_E_INVALID, "snowgpu_set_wet_lines supplies LINES: not with estimation method 'poly'"); }
-    if (!ctx->wet_lines.empty()) {                      // the caller's lines (one use; the upload is waited for: they leave the context here)
-        if (ctx->wet_lines.size() != (size_t)n_frames * 4) { ctx->wet_lines.clear(); return fail(ctx, SNOWGPU_E_INVALID, "snowgpu_set_wet_lines was given another number of frames"); }
-        ENSURE(ctx, ctx->d_wet_lines, ctx->wet_lines.size());
-        HIPCHK(ctx, hipMemcpyAsync(ctx->d_wet_lines.p, ctx->wet_lines.data(), sizeof(double) * ctx->wet_lines.size(), hipMemcpyHostToDevice, st));
-        HIPCHK(ctx, hipStreamSynchronize(st));
-        wp.lines = ctx->d_wet_lines.p;
-        ctx->wet_lines.clear();
-    }
-    int e = 0;
-    if (!d_plane) {
-        // calculate_plane (augmentation.py:41) on the device: the method `reference` returns a constant and reads no row.  The two estimators
-        // crop the cloud into a list first; under a mask that list -- and with it the RANSAC draws -- has another order: a change of its own.
-        if (ctx->plane_par.method != SG_PLANE_REFERENCE)
-            return fail(ctx, SNOWGPU_E_INVALID, name + ": a NULL wet plane needs the plane method 'reference'; 'lsq' and 'ransac' crop the rows and have no masked form: pass the plane");
-        ENSURE(ctx, ctx->wet_plane_est, (size_t)n_frames * 4);
-        e = sg_plane_run(&ctx->plane_scr, &ctx->plane_par, d_rows, dtype, d_frame_offsets, nullptr, n_frames, n_total, max_frame, ctx->wet_plane_est.p, nullptr, st);
-        if (e) return fail(ctx, SNOWGPU_E_HIP, std::string("plane estimate: ") + (e > 0 ? hipGetErrorString((hipError_t)e) : "allocation"));
-        d_plane = ctx->wet_plane_est.p;
-    }
-    e = sg_wet_run_aligned(&ctx->prepass, d_rows, dtype, d_frame_offsets, d_keep_in, n_frames, n_total, max_frame, d_plane, &wp, d_out_rows,
-                           d_out_keep, d_out_counts, d_out_flags, d_status, st);
-    if (e) return fail(ctx, SNOWGPU_E_HIP, std::string("wet ground: ") + (e > 0 ? hipGetErrorString((hipError_t)e) : "allocation"));
-    return SNOWGPU_OK;
-}
-
-// a batch without rows: nothing kept, every frame "returned as it came" (what an empty frame inside a batch reports)
-static int aligned_wet_empty(snowgpu_ctx *ctx, int n_frames, int64_t *d_out_counts, int32_t *d_out_flags, hipStream_t st)
-{
-    HIPCHK(ctx, hipMemsetAsync(d_out_counts, 0, sizeof(int64_t) * (size_t)n_frames, st));
-    HIPCHK(ctx, hipMemsetD32Async((hipDeviceptr_t)d_out_flags, 1, (size_t)n_frames, st));
-    return SNOWGPU_OK;
-}
-
-// ground_water_augmentation() on frames in DEVICE memory with the aligned result: the first device-pointer entry of the wet model on its
-// own, and the second half of the fused aligned entry below.
-extern "C" int snowgpu_wet_ground_batch_device_aligned(snowgpu_ctx *ctx, int n_frames, int64_t n_total, int64_t max_frame_rows,
-                                                       const int64_t *d_frame_offsets, const void *d_rows, int dtype, const uint8_t *d_keep_in,
-                                                       const double *d_plane, double water_height, double pavement_depth, double noise_floor,
-                                                       double power_factor, int flat_earth, double delta, int replace, void *d_out_rows,
-                                                       uint8_t *d_out_keep, int64_t *d_out_counts, int32_t *d_out_flags, int32_t *d_status,
-                                                       void *stream)
-{
-    static const char *who = "snowgpu_wet_ground_batch_device_aligned";
-    if (!ctx) return SNOWGPU_E_INVALID;
-    if (n_frames <= 0 || n_total < 0 || !d_frame_offsets || (n_total > 0 && (!d_rows || !d_out_rows || !d_out_keep)) || !d_out_counts ||
-        !d_out_flags || !d_status || (dtype != 0 && dtype != 1))
-        return fail(ctx, SNOWGPU_E_INVALID, std::string(who) + ": null pointer or bad dtype");
-    if (n_total >= ((int64_t)1 << 31)) return fail(ctx, SNOWGPU_E_INVALID, "batch too large: split it below 2^31 rows");
-    if (int rc = aligned_wet_refusals(ctx, who, n_total, dtype, d_rows, d_out_rows, d_keep_in, d_out_keep)) return rc;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-    HIPCHK(ctx, hipMemsetAsync(d_status, 0, sizeof(int32_t) * 8, st));
-    if (n_total == 0) return aligned_wet_empty(ctx, n_frames, d_out_counts, d_out_flags, st);
-    const int64_t max_frame = (max_frame_rows > 0 && max_frame_rows <= n_total) ? max_frame_rows : n_total;
-    return aligned_wet_stage(ctx, who, n_frames, n_total, max_frame, d_frame_offsets, d_rows, dtype, d_keep_in, d_plane, water_height, pavement_depth,
-                             noise_floor, power_factor, flat_earth, delta, replace, d_out_rows, d_out_keep, d_out_counts, d_out_flags, d_status, st);
-}
-
-// augment() followed by ground_water_augmentation() (pointcloud_viewer.py:2807-2821) with the aligned result, as ONE launch sequence on the
-// caller's stream: run_batch with the aligned finish into d_out_rows / d_out_keep, then the wet stage IN PLACE on those two arrays.  No
-// compaction, no snow_rows / snow_src / snow_counts scratch, no source indices to compose.
-extern "C" int snowgpu_augment_wet_batch_device_aligned(snowgpu_ctx *ctx, int n_frames, int64_t n_total, int64_t max_frame_rows,
-                                                        const int64_t *d_frame_offsets, const void *d_rows, int dtype,
-                                                        const int32_t *d_table_ids, double beam_divergence_deg, const double *d_thr_poly,
-                                                        const double *d_plane, double noise_floor, const int32_t *d_perm, void *d_out_rows,
-                                                        uint8_t *d_out_keep, int64_t *d_out_counts, int64_t *d_out_stats, double *d_out_thr_poly,
-                                                        int32_t *d_status, void *stream, const double *d_wet_plane, double water_height,
-                                                        double pavement_depth, double wet_noise_floor, double power_factor, int flat_earth,
-                                                        double delta, int replace, int32_t *d_out_flags)
-{
-    static const char *who = "snowgpu_augment_wet_batch_device_aligned";
-    if (!ctx) return SNOWGPU_E_INVALID;
-    if (n_frames <= 0 || n_total < 0 || !d_frame_offsets || (n_total > 0 && !d_rows) || !d_table_ids || !d_out_rows ||
-        !d_out_keep || !d_out_counts || !d_out_stats || !d_out_flags || !d_status || (dtype != 0 && dtype != 1))
-        return fail(ctx, SNOWGPU_E_INVALID, std::string(who) + ": null pointer or bad dtype");
-    if (n_total >= ((int64_t)1 << 31)) return fail(ctx, SNOWGPU_E_INVALID, "batch too large: split it below 2^31 rows");
-    if (int rc = aligned_wet_refusals(ctx, who, n_total, dtype, d_rows, d_out_rows, nullptr, d_out_keep)) return rc;
-    if (!d_wet_plane && ctx->plane_par.method != SG_PLANE_REFERENCE)             // (before anything is launched)
-        return fail(ctx, SNOWGPU_E_INVALID, std::string(who) + ": a NULL wet plane needs the plane method 'reference'; 'lsq' and 'ransac' crop the rows and have no masked form: pass the plane");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    BatchDev b{};
-    b.n_frames = n_frames; b.n_total = n_total; b.max_frame = (max_frame_rows > 0 && max_frame_rows <= n_total) ? max_frame_rows : n_total;
-    b.frame_off = d_frame_offsets;
-    b.uniform_rows = (max_frame_rows > 0 && max_frame_rows * (int64_t)n_frames == n_total) ? max_frame_rows : 0; b.rows = d_rows;
-    b.dtype = dtype; b.table_ids = d_table_ids; b.beam_div_deg = beam_divergence_deg; b.thr_poly = d_thr_poly;
-    b.plane = d_plane; b.noise_floor = noise_floor; b.perm = d_perm; b.out_rows = d_out_rows; b.out_src = nullptr; b.out_keep = d_out_keep;
-    b.out_counts = d_out_counts; b.out_stats = d_out_stats; b.out_thr_poly = d_out_thr_poly; b.status = d_status;
-    b.stream = stream ? (hipStream_t)stream : ctx->stream;
-    int rc = run_batch(ctx, b);
-    if (rc) return rc;
-    if (n_total == 0) return aligned_wet_empty(ctx, n_frames, d_out_counts, d_out_flags, b.stream);
-    // (d_out_counts: the snowfall stage's counts are overwritten by the wet stage's, which count what is left of them)
-    return aligned_wet_stage(ctx, who, n_frames, n_total, b.max_frame, d_frame_offsets, d_out_rows, dtype, d_out_keep, d_wet_plane, water_height,
-                             pavement_depth, wet_noise_floor, power_factor, flat_earth, delta, replace, d_out_rows, d_out_keep, d_out_counts,
-                             d_out_flags, d_status, b.stream);
-}
-
-// ---- an input keep mask for the aligned snowfall stage (snowgpu_mask.hip) -------------------------------------------------------------
-// The snowfall stage of both masked entries, on b.stream.  Front end: the present rows of every frame are compacted, stably, into context
-// scratch (rows_crop, crop_src) at offsets made on the device (crop_off); the absent rows' keep bytes -- and, out of place, their rows --
-// are written on the way.  Then run_batch on that scratch: every kernel of the unmasked call, untouched, on the batch the caller would have
-// had to compact; n_total and max_frame are upper bounds to it, no frame-uniform shortcut.  Its last step is the masked aligned finish.
-// d_weather (optional): the snow gate of every frame is part of the mask (d_keep_in may then be NULL); see sg_launch_mask_front.
-static int masked_snow_stage(snowgpu_ctx *ctx, const char *who, BatchDev &b, const uint8_t *d_keep_in, const double *d_weather = nullptr)
-{
-    const std::string name(who);
-    snowgpu_ctx *R = ctx->root ? ctx->root : ctx;
-    if (b.perm) return fail(ctx, SNOWGPU_E_INVALID, name + ": d_perm with d_keep_in; a caller's permutation indexes the rows of the frames it was made for, not the present ones");
-    // (what run_batch needs for the segment order of the pass over all rows; the linear order reads n_total as an exact count)
-    if (R->tables.size() > 65536 || b.n_frames > (1 << 22))
-        return fail(ctx, SNOWGPU_E_INVALID, name + ": a masked batch needs at most 65536 tables and 2^22 frames");
-    const size_t n = (size_t)b.n_total, esz = b.dtype == 0 ? 4 : 8;
-    const int64_t max_tiles = sg_tiles(b.max_frame);
-    ENSURE(ctx, ctx->ctile_cnt, (size_t)b.n_frames * (size_t)max_tiles + 1);
-    ENSURE(ctx, ctx->ctile_base, (size_t)b.n_frames * (size_t)max_tiles + 1);
-    ENSURE(ctx, ctx->crop_counts, (size_t)b.n_frames);
-    ENSURE(ctx, ctx->crop_off, (size_t)b.n_frames + 1);
-    ENSURE(ctx, ctx->rows_crop, n * 5 * esz);
-    ENSURE(ctx, ctx->crop_src, n);
-    int e = sg_launch_mask_front(b.rows, b.dtype, d_keep_in, d_weather, b.frame_off, b.n_frames, b.out_rows == b.rows ? nullptr : b.out_rows, b.out_keep,
-                                 ctx->ctile_cnt.p, ctx->ctile_base.p, ctx->crop_counts.p, ctx->crop_off.p, ctx->rows_crop.p, ctx->crop_src.p, max_tiles, b.stream);
-    if (e) return fail(ctx, SNOWGPU_E_HIP, std::string("mask front end launch: ") + hipGetErrorString((hipError_t)e));
-    b.mask_in_off = b.frame_off; b.mask_map = ctx->crop_src.p; b.weather = d_weather;
-    b.rows = ctx->rows_crop.p; b.frame_off = ctx->crop_off.p; b.uniform_rows = 0;
-    return run_batch(ctx, b);
-}
-
-// snowgpu_augment_batch_device_aligned with an input keep mask: a row whose d_keep_in byte is 0 is not there.  See include/snowgpu.h.
-extern "C" int snowgpu_augment_batch_device_aligned_masked(snowgpu_ctx *ctx, int n_frames, int64_t n_total, int64_t max_frame_rows,
-                                                           const int64_t *d_frame_offsets, const void *d_rows, int dtype, const int32_t *d_table_ids,
-                                                           double beam_divergence_deg, const double *d_thr_poly, const double *d_plane,
-                                                           double noise_floor, const int32_t *d_perm, const uint8_t *d_keep_in, void *d_out_rows,
-                                                           uint8_t *d_out_keep, int64_t *d_out_counts, int64_t *d_out_stats, double *d_out_thr_poly,
-                                                           int32_t *d_status, void *stream)
-{
-    static const char *who = "snowgpu_augment_batch_device_aligned_masked";
-    if (!ctx) return SNOWGPU_E_INVALID;
-    if (!d_keep_in || n_total == 0)                  // all present: the unmasked call itself
-        return snowgpu_augment_batch_device_aligned(ctx, n_frames, n_total, max_frame_rows, d_frame_offsets, d_rows, dtype, d_table_ids, beam_divergence_deg,
-                                                    d_thr_poly, d_plane, noise_floor, d_perm, d_out_rows, d_out_keep, d_out_counts, d_out_stats, d_out_thr_poly,
-                                                    d_status, stream);
-    if (n_frames <= 0 || n_total < 0 || !d_frame_offsets || !d_rows || !d_table_ids || !d_out_rows ||
-        !d_out_keep || !d_out_counts || !d_out_stats || !d_status || (dtype != 0 && dtype != 1))
-        return fail(ctx, SNOWGPU_E_INVALID, std::string(who) + ": null pointer or bad dtype");
-    if (n_total >= ((int64_t)1 << 31)) return fail(ctx, SNOWGPU_E_INVALID, "batch too large: split it below 2^31 rows");
-    if (int rc = aligned_wet_refusals(ctx, who, n_total, dtype, d_rows, d_out_rows, d_keep_in, d_out_keep)) return rc;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    BatchDev b{};
-    b.n_frames = n_frames; b.n_total = n_total; b.max_frame = (max_frame_rows > 0 && max_frame_rows <= n_total) ? max_frame_rows : n_total;
-    b.frame_off = d_frame_offsets; b.rows = d_rows;
-    b.dtype = dtype; b.table_ids = d_table_ids; b.beam_div_deg = beam_divergence_deg; b.thr_poly = d_thr_poly;
-    b.plane = d_plane; b.noise_floor = noise_floor; b.perm = d_perm; b.out_rows = d_out_rows; b.out_src = nullptr; b.out_keep = d_out_keep;
-    b.out_counts = d_out_counts; b.out_stats = d_out_stats; b.out_thr_poly = d_out_thr_poly; b.status = d_status;
-    b.stream = stream ? (hipStream_t)stream : ctx->stream;
-    return masked_snow_stage(ctx, who, b, d_keep_in);
-}
-
-// snowgpu_augment_wet_batch_device_aligned whose snowfall stage is the masked one; the wet stage runs in place on d_out_rows / d_out_keep
-// as in the unmasked chain (absent rows carry keep 0 there: the wet stage treats them as not there, too).
-extern "C" int snowgpu_augment_wet_batch_device_aligned_masked(snowgpu_ctx *ctx, int n_frames, int64_t n_total, int64_t max_frame_rows,
-                                                               const int64_t *d_frame_offsets, const void *d_rows, int dtype,
-                                                               const int32_t *d_table_ids, double beam_divergence_deg, const double *d_thr_poly,
-                                                               const double *d_plane, double noise_floor, const int32_t *d_perm,
-                                                               const uint8_t *d_keep_in, void *d_out_rows, uint8_t *d_out_keep,
-                                                               int64_t *d_out_counts, int64_t *d_out_stats, double *d_out_thr_poly, int32_t *d_status,
-                                                               void *stream, const double *d_wet_plane, double water_height, double pavement_depth,
-                                                               double wet_noise_floor, double power_factor, int flat_earth, double delta, int replace,
-                                                               int32_t *d_out_flags)
-{
-    static const char *who = "snowgpu_augment_wet_batch_device_aligned_masked";
-    if (!ctx) return SNOWGPU_E_INVALID;
-    if (!d_keep_in || n_total == 0)
-        return snowgpu_augment_wet_batch_device_aligned(ctx, n_frames, n_total, max_frame_rows, d_frame_offsets, d_rows, dtype, d_table_ids, beam_divergence_deg,
-                                                        d_thr_poly, d_plane, noise_floor, d_perm, d_out_rows, d_out_keep, d_out_counts, d_out_stats, d_out_thr_poly,
-                                                        d_status, stream, d_wet_plane, water_height, pavement_depth, wet_noise_floor, power_factor, flat_earth,
-                                                        delta, replace, d_out_flags);
-    if (n_frames <= 0 || n_total < 0 || !d_frame_offsets || !d_rows || !d_table_ids || !d_out_rows ||
-        !d_out_keep || !d_out_counts || !d_out_stats || !d_out_flags || !d_status || (dtype != 0 && dtype != 1))
-        return fail(ctx, SNOWGPU_E_INVALID, std::string(who) + ": null pointer or bad dtype");
-    if (n_total >= ((int64_t)1 << 31)) return fail(ctx, SNOWGPU_E_INVALID, "batch too large: split it below 2^31 rows");
-    if (int rc = aligned_wet_refusals(ctx, who, n_total, dtype, d_rows, d_out_rows, d_keep_in, d_out_keep)) return rc;
-    if (!d_wet_plane && ctx->plane_par.method != SG_PLANE_REFERENCE)             // (before anything is launched)
-        return fail(ctx, SNOWGPU_E_INVALID, std::string(who) + ": a NULL wet plane needs the plane method 'reference'; 'lsq' and 'ransac' crop the rows and have no masked form: pass the plane");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    BatchDev b{};
-    b.n_frames = n_frames; b.n_total = n_total; b.max_frame = (max_frame_rows > 0 && max_frame_rows <= n_total) ? max_frame_rows : n_total;
-    b.frame_off = d_frame_offsets; b.rows = d_rows;
-    b.dtype = dtype; b.table_ids = d_table_ids; b.beam_div_deg = beam_divergence_deg; b.thr_poly = d_thr_poly;
-    b.plane = d_plane; b.noise_floor = noise_floor; b.perm = d_perm; b.out_rows = d_out_rows; b.out_src = nullptr; b.out_keep = d_out_keep;
-    b.out_counts = d_out_counts; b.out_stats = d_out_stats; b.out_thr_poly = d_out_thr_poly; b.status = d_status;
-    b.stream = stream ? (hipStream_t)stream : ctx->stream;
-    int rc = masked_snow_stage(ctx, who, b, d_keep_in);
-    if (rc) return rc;
-    return aligned_wet_stage(ctx, who, n_frames, n_total, b.max_frame, d_frame_offsets, d_out_rows, dtype, d_out_keep, d_wet_plane, water_height,
-                             pavement_depth, wet_noise_floor, power_factor, flat_earth, delta, replace, d_out_rows, d_out_keep, d_out_counts,
-                             d_out_flags, d_status, b.stream);
-}
-
-// ---- per-frame weather: gates and wet settings in device memory (include/snowgpu.h) ---------------------------------------------------
-// The masked fused chain with d_weather in place of its five wet scalars.  The snow gate joins the input mask in the front end (a frame
-// left out reaches run_batch empty and keeps its keep bytes), the wet gate and the wet settings are read per frame by the wet kernels.
-// Because the gates are device data the masked front end always runs, with or without d_keep_in.
-extern "C" int snowgpu_augment_weather_batch_device_aligned(snowgpu_ctx *ctx, int n_frames, int64_t n_total, int64_t max_frame_rows,
-                                                            const int64_t *d_frame_offsets, const void *d_rows, int dtype,
-                                                            const int32_t *d_table_ids, double beam_divergence_deg, const double *d_thr_poly,
-                                                            const double *d_plane, double noise_floor, const int32_t *d_perm,
-                                                            const uint8_t *d_keep_in, void *d_out_rows, uint8_t *d_out_keep,
-                                                            int64_t *d_out_counts, int64_t *d_out_stats, double *d_out_thr_poly, int32_t *d_status,
-                                                            void *stream, const double *d_wet_plane, const double *d_weather, int flat_earth,
-                                                            int replace, int32_t *d_out_flags)
-{
-    static const char *who = "snowgpu_augment_weather_batch_device_aligned";
-    if (!ctx) return SNOWGPU_E_INVALID;
-    if (!d_weather) return fail(ctx, SNOWGPU_E_INVALID, std::string(who) + ": d_weather is NULL; one record of 8 doubles per frame, in device memory");
-    if (n_frames <= 0 || n_total < 0 || !d_frame_offsets || (n_total > 0 && !d_rows) || !d_table_ids || !d_out_rows ||
-        !d_out_keep || !d_out_counts || !d_out_stats || !d_out_flags || !d_status || (dtype != 0 && dtype != 1))
-        return fail(ctx, SNOWGPU_E_INVALID, std::string(who) + ": null pointer or bad dtype");
-    if (n_total >= ((int64_t)1 << 31)) return fail(ctx, SNOWGPU_E_INVALID, "batch too large: split it below 2^31 rows");
-    if (int rc = aligned_wet_refusals(ctx, who, n_total, dtype, d_rows, d_out_rows, d_keep_in, d_out_keep)) return rc;
-    if (!d_wet_plane && ctx->plane_par.method != SG_PLANE_REFERENCE)             // (before anything is launched)
-        return fail(ctx, SNOWGPU_E_INVALID, std::string(who) + ": a NULL wet plane needs the plane method 'reference'; 'lsq' and 'ransac' crop the rows and have no masked form: pass the plane");
-    if (d_perm) return fail(ctx, SNOWGPU_E_INVALID, std::string(who) + ": d_perm with d_weather; a caller's permutation indexes the rows of the frames it was made for, not the present ones");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    BatchDev b{};
-    b.n_frames = n_frames; b.n_total = n_total; b.max_frame = (max_frame_rows > 0 && max_frame_rows <= n_total) ? max_frame_rows : n_total;
-    b.frame_off = d_frame_offsets; b.rows = d_rows;
-    b.dtype = dtype; b.table_ids = d_table_ids; b.beam_div_deg = beam_divergence_deg; b.thr_poly = d_thr_poly;
-    b.plane = d_plane; b.noise_floor = noise_floor; b.perm = d_perm; b.out_rows = d_out_rows; b.out_src = nullptr; b.out_keep = d_out_keep;
-    b.out_counts = d_out_counts; b.out_stats = d_out_stats; b.out_thr_poly = d_out_thr_poly; b.status = d_status;
-    b.stream = stream ? (hipStream_t)stream : ctx->stream;
-    if (n_total == 0) {                              // no row at all: the unmasked chain's answer, with "not asked" where the wet gate is off
-        int rc = run_batch(ctx, b);
-        if (rc) return rc;
-        rc = aligned_wet_empty(ctx, n_frames, d_out_counts, d_out_flags, b.stream);
-        if (rc) return rc;
-        int e = sg_launch_weather_flags(d_weather, n_frames, d_out_flags, b.stream);
-        if (e) return fail(ctx, SNOWGPU_E_HIP, std::string("weather flags launch: ") + hipGetErrorString((hipError_t)e));
-        return SNOWGPU_OK;
-    }
-    int rc = masked_snow_stage(ctx, who, b, d_keep_in, d_weather);
-    if (rc) return rc;
-    return aligned_wet_stage(ctx, who, n_frames, n_total, b.max_frame, d_frame_offsets, d_out_rows, dtype, d_out_keep, d_wet_plane, 0.0, 1.0, 0.0, 0.0,
-                             flat_earth, 0.0, replace, d_out_rows, d_out_keep, d_out_counts, d_out_flags, d_status, b.stream, d_weather);
-}
-
-// Which weather each frame gets, drawn on the device (snowgpu_weather.hip, sg_weather.h).  See include/snowgpu.h.
-extern "C" int snowgpu_draw_weather_device(snowgpu_ctx *ctx, int n_frames, int n_lasers, int n_sets, const int32_t *d_set_ids,
-                                           const snowgpu_weather_plan *plan, uint64_t seed, const uint64_t *d_step, int32_t *d_table_ids,
-                                           double *d_weather, void *stream)
-{
-    static const char *who = "snowgpu_draw_weather_device";
-    if (!ctx) return SNOWGPU_E_INVALID;
-    if (!plan || !d_set_ids || !d_step || !d_table_ids || !d_weather) return fail(ctx, SNOWGPU_E_INVALID, std::string(who) + ": null pointer");
-    if (n_frames <= 0 || n_frames > (1 << 22) || n_lasers <= 0 || n_lasers > SG_WEATHER_MAX_LASERS || n_sets <= 0 || n_sets > SG_WEATHER_MAX_SETS ||
-        plan->n_water <= 0 || plan->n_water > SG_WEATHER_MAX_CHOICES || plan->n_pave <= 0 || plan->n_pave > SG_WEATHER_MAX_CHOICES)
-        return fail(ctx, SNOWGPU_E_INVALID, std::string(who) + ": needs 1 .. 2^22 frames, 1 .. 128 lasers, 1 .. 64 table sets, 1 .. 16 water heights and pavement depths");
-    if (!(plan->p_snow >= 0.0 && plan->p_snow <= 1.0) || !(plan->p_wet >= 0.0 && plan->p_wet <= 1.0))
-        return fail(ctx, SNOWGPU_E_INVALID, std::string(who) + ": p_snow and p_wet are probabilities");
-    auto threshold = [](double p) { const double t = std::floor(p * 4294967296.0); return t >= 4294967296.0 ? (uint64_t)1 << 32 : (uint64_t)t; };
-    SgWeatherDraw d{};
-    d.t_snow = threshold(plan->p_snow); d.t_wet = threshold(plan->p_wet);
-    d.n_sets = n_sets; d.n_lasers = n_lasers; d.n_water = plan->n_water; d.n_pave = plan->n_pave; d.shuffle = plan->shuffle ? 1 : 0;
-    for (int i = 0; i < plan->n_water; ++i) d.water[i] = plan->water_heights[i];
-    for (int i = 0; i < plan->n_pave; ++i) d.pave[i] = plan->pavement_depths[i];
-    d.wet_noise_floor = plan->wet_noise_floor; d.power_factor = plan->power_factor; d.delta = plan->delta;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    int e = sg_launch_draw_weather(&d, n_frames, seed, d_step, d_set_ids, d_table_ids, d_weather, stream ? (hipStream_t)stream : ctx->stream);
-    if (e) return fail(ctx, SNOWGPU_E_HIP, std::string("weather draw launch: ") + hipGetErrorString((hipError_t)e));
-    return SNOWGPU_OK;
-}
-
 // Camera-FOV crop of augment(only_camera_fov=True) (simulation.py:39-47, :532-540): lidar_to_rect with
 // Tr_velo_to_cam (3 x 4) and R0_rect (3 x 3), rect_to_img with P2 (3 x 4), image img_h x img_w ((1024, 1920) in the
 // reference).  The crop is applied by the compaction of every later batch of this context (and num_removed counts it,
@@ -1027,7 +598,7 @@ extern "C" int snowgpu_set_fov_precrop(snowgpu_ctx *ctx, int on)
 }
 
 // the crop's matrices as the kernels take them (snowgpu_set_fov, snowgpu_fov_mask_device)
-static SgFov make_fov(const double *v2c, const double *r0, const double *p2, int img_h, int img_w)
+SgFov make_fov(const double *v2c, const double *r0, const double *p2, int img_h, int img_w)
 {
     SgFov f{};
     f.enabled = 1;
@@ -1065,45 +636,9 @@ extern "C" int snowgpu_set_plane_method(snowgpu_ctx *ctx, int method, uint64_t s
     return SNOWGPU_OK;
 }
 
-extern "C" int snowgpu_estimate_planes_device(snowgpu_ctx *ctx, int n_frames, int64_t n_total, int64_t max_frame_rows,
-                                              const int64_t *d_frame_offsets, const void *d_rows, int dtype, double *d_out_planes,
-                                              int32_t *d_out_info, void *stream)
-{
-    if (!ctx) return SNOWGPU_E_INVALID;
-    if (n_frames <= 0 || n_total < 0 || !d_frame_offsets || (n_total > 0 && !d_rows) || !d_out_planes || (dtype != 0 && dtype != 1))
-        return fail(ctx, SNOWGPU_E_INVALID, "snowgpu_estimate_planes_device: null pointer or bad dtype");
-    if (n_total >= ((int64_t)1 << 31)) return fail(ctx, SNOWGPU_E_INVALID, "batch too large: split it below 2^31 rows");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    const int64_t mf = (max_frame_rows > 0 && max_frame_rows <= n_total) ? max_frame_rows : n_total;
-    int e = sg_plane_run(&ctx->plane_scr, &ctx->plane_par, d_rows, dtype, d_frame_offsets, nullptr, n_frames, n_total, mf, d_out_planes, d_out_info,
-                         stream ? (hipStream_t)stream : ctx->stream);
-    if (e) return fail(ctx, SNOWGPU_E_HIP, std::string("plane estimate: ") + (e > 0 ? hipGetErrorString((hipError_t)e) : "allocation"));
-    return SNOWGPU_OK;
-}
-
 extern "C" int snowgpu_set_threshold_callback(snowgpu_ctx *ctx, snowgpu_threshold_fn fn, void *user)
 {
     if (!ctx) return SNOWGPU_E_INVALID;
     ctx->thr_fn = fn; ctx->thr_user = fn ? user : nullptr;
-    return SNOWGPU_OK;
-}
-
-// The camera-FOV test as a producer of a keep mask: d_out_keep[i] = (d_keep_in ? d_keep_in[i] : 1) && get_fov_flag(row i), matrices and
-// image size as snowgpu_set_fov takes them (the context's own crop setting is neither read nor changed).  See include/snowgpu.h.
-extern "C" int snowgpu_fov_mask_device(snowgpu_ctx *ctx, int64_t n_total, const void *d_rows, int dtype, const double *v2c, const double *r0,
-                                       const double *p2, int img_h, int img_w, const uint8_t *d_keep_in, uint8_t *d_out_keep, void *stream)
-{
-    if (!ctx) return SNOWGPU_E_INVALID;
-    if (n_total < 0 || (n_total > 0 && (!d_rows || !d_out_keep)) || !v2c || !r0 || !p2 || img_h <= 0 || img_w <= 0 || (dtype != 0 && dtype != 1))
-        return fail(ctx, SNOWGPU_E_INVALID, "snowgpu_fov_mask_device: need rows, V2C, R0, P2, an image size and an output mask");
-    {
-        const uint8_t *k = d_keep_in, *ok = d_out_keep;
-        if (k && ok != k && ok < k + (size_t)n_total && k < ok + (size_t)n_total)
-            return fail(ctx, SNOWGPU_E_INVALID, "snowgpu_fov_mask_device: d_out_keep overlaps d_keep_in; pass d_keep_in itself or a buffer apart from it");
-    }
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    const SgFov f = make_fov(v2c, r0, p2, img_h, img_w);
-    int e = sg_launch_fov_mask(d_rows, dtype, n_total, d_keep_in, d_out_keep, &f, stream ? (hipStream_t)stream : ctx->stream);
-    if (e) return fail(ctx, SNOWGPU_E_HIP, std::string("fov mask launch: ") + hipGetErrorString((hipError_t)e));
     return SNOWGPU_OK;
 }

@@ -822,21 +822,8 @@ extern "C" int snowgpu_wet_ground_batch(snowgpu_ctx *ctx, int n_frames, const in
         if (pe) return fail(ctx, SNOWGPU_E_HIP, std::string("plane estimate: ") + (pe > 0 ? hipGetErrorString((hipError_t)pe) : "allocation"));
     }
     HIPCHK(ctx, hipMemsetAsync(ctx->d_status, 0, sizeof(int32_t) * 8, st));
-    SgWetParams wp{};
-    wp.water_height = water_height; wp.pavement_depth = pavement_depth; wp.noise_floor = noise_floor;
-    wp.power_factor = power_factor; wp.flat_earth = flat_earth; wp.delta = delta; wp.replace = replace;
-    wp.estimation = ctx->wet_estimation; wp.seed = ctx->wet_seed;
-    ENSURE(ctx, ctx->wet_fit, (size_t)n_frames * 8);
-    wp.fit_out = ctx->wet_fit.p; ctx->wet_fit_frames = n_frames;
-    if (!ctx->wet_lines.empty() && ctx->wet_estimation != 0) { ctx->wet_lines.clear(); return fail(ctx, SNOWGPU_E_INVALID, "snowgpu_set_wet_lines supplies LINES: not with estimation method 'poly'"); }
-    if (!ctx->wet_lines.empty()) {                      // the caller's lines (one use)
-        if (ctx->wet_lines.size() != (size_t)n_frames * 4) { ctx->wet_lines.clear(); return fail(ctx, SNOWGPU_E_INVALID, "snowgpu_set_wet_lines was given another number of frames"); }
-        ENSURE(ctx, ctx->d_wet_lines, ctx->wet_lines.size());
-        HIPCHK(ctx, hipMemcpyAsync(ctx->d_wet_lines.p, ctx->wet_lines.data(), sizeof(double) * ctx->wet_lines.size(), hipMemcpyHostToDevice, st));
-        HIPCHK(ctx, hipStreamSynchronize(st));
-        wp.lines = ctx->d_wet_lines.p;
-        ctx->wet_lines.clear();
-    }
+    SgWetParams wp;
+    if (int rc = wet_settings(ctx, SgWetScalars{water_height, pavement_depth, noise_floor, power_factor, delta, flat_earth, replace}, n_frames, true, st, &wp)) return rc;
     int e = sg_wet_run(&ctx->prepass, ctx->rows_in.p, dtype, ctx->frame_off.p, nullptr, n_frames, n_total, max_frame, ctx->plane.p, &wp,
                        (double *)ctx->rows_out.p, ctx->out_src.p, ctx->out_counts.p, ctx->dbg_count.p, ctx->d_status, st);
     if (e) return fail(ctx, SNOWGPU_E_HIP, std::string("wet ground: ") + (e > 0 ? hipGetErrorString((hipError_t)e) : "allocation"));

@@ -188,7 +188,7 @@ __global__ __launch_bounds__(256) void k_fov_mask(const T *__restrict__ rows, in
 }
 
 // ------------------------------------------------------------------------------------------------
-// launch wrappers (C linkage, called from snowgpu_batch.cpp and snowgpu_api.cpp)
+// launch wrappers (C linkage, called from snowgpu_batch.cpp and snowgpu_device.cpp)
 
 // The front end of a masked aligned call, on `stream`: new_off[0 .. n_frames] (device), the present rows of frame f at crows[new_off[f] ..]
 // in input order, map[new_off[f] + j] = frame-local input row of compacted row j.  out_rows: null in place, else the absent rows are copied.

@@ -30,6 +30,7 @@ from __future__ import annotations
 import os
 import random
 from collections import OrderedDict
+from contextlib import contextmanager
 
 import numpy as np
 
@@ -263,11 +264,79 @@ def _run_stream(torch, eng, dev, stream, lane=None):
     return run
 
 
+def _resolve_input(torch, frames, in_place, device, slot, lane=None):
+    """(rows, host offsets, extras or None, engine) of a call: the frames as one N_total x 5 tensor -- read where they lie for in_place --
+    on the device that `device` names if it names one, and the engine of `slot`, or of compute lane `lane`: an engine of its own whose
+    batches run on one stream (snowgpu_set_serial, once): they overlap OTHER lanes' batches, not their own side streams."""
+    from . import engine as _engine
+    rows, offsets, extras = _rows_where_they_lie(torch, frames) + (None,) if in_place else _as_batch(torch, frames)
+    dev = rows.device
+    if device is not None and int(device) != dev.index:
+        raise ValueError(f"the tensors live on {dev}, device={device} was asked for")
+    eng = _engine.get_engine(dev.index, slot if lane is None else LANE_SLOT0 + int(lane))
+    if lane is not None and not eng.__dict__.get("_lane_serial"):
+        eng.ctx.set_serial(True)      # (with GPU_MAX_HW_QUEUES >= 16 every lane's stream has a hardware queue of its own: include/snowgpu.h)
+        eng.__dict__["_lane_serial"] = True
+    return rows, offsets, extras, eng
+
+
+@contextmanager
+def _on_run_stream(torch, eng, dev, lane=None, used=()):
+    """(torch's current stream, the stream the call runs on) with the fork and the join around the body.  The C ABI reads stream = NULL as
+    "the context's own stream", which is not ordered against anything of torch's.  torch's legacy default stream HAS the handle 0, so a
+    call made on it runs on a side stream of the engine, forked from and joined back into the default stream (two event waits): work
+    queued before the call is seen, and whoever reads the results on the caller's stream afterwards -- or synchronises it -- waits for
+    the call.  A lane's stream forks alike and nothing waits for it (the result is claimed by wait() / join()); the tensors in `used`
+    are the caller's stream's, used on the lane's: the allocator must know."""
+    stream = torch.cuda.current_stream(dev)
+    run = _run_stream(torch, eng, dev, stream, lane)
+    if run is not stream:
+        run.wait_stream(stream)
+        if lane is not None:
+            for t in used:
+                if t is not None:
+                    t.record_stream(run)
+    try:
+        yield stream, run
+    finally:
+        if run is not stream and lane is None:
+            stream.wait_stream(run)
+
+
+@contextmanager
+def _temporary_settings(ctx, calib=None, plane=None, wet_estimation=None, lines=None):
+    """The settings of the context that one call sets and puts back; held under the engine's batch_lock.  calib: the camera crop of the
+    result (simulation.py:536); plane: (method, seed, trials) of the device's plane estimate; wet_estimation: (method, seed);
+    lines: n_frames x 4 fitted by the caller."""
+    if calib is not None:
+        ctx.set_fov(calib, (1024, 1920))
+    if plane is not None:
+        ctx.set_plane_method(plane[0], seed=plane[1], trials=plane[2], min_rows=5)
+    if wet_estimation is not None and wet_estimation[0] != 'linear':
+        ctx.set_wet_estimation(*wet_estimation)
+    if lines is not None:
+        ctx.set_wet_lines(lines)
+    try:
+        yield
+    finally:
+        if calib is not None:
+            ctx.set_fov(None)
+        if plane is not None and plane[0] != 'reference':
+            ctx.set_plane_method('reference')
+        if wet_estimation is not None and wet_estimation[0] != 'linear':
+            ctx.set_wet_estimation('linear')
+        if lines is not None:
+            ctx.set_wet_lines(None)
+
+
+WET_DEFAULTS = dict(water_height=0.001, pavement_depth=0.0012, noise_floor=0.7, power_factor=15, flat_earth=False, delta=0.5, replace=True)
+
+
 def _plane_rows(planes, nf):
     """n_frames x 4 float64 (wx, wy, wz, h) from an n_frames x 4 array, per-frame (w, h) pairs, or ONE (w, h) pair for every frame."""
     if isinstance(planes, np.ndarray) and planes.shape == (nf, 4):
         return np.ascontiguousarray(planes, np.float64)
-    if len(planes) == 2 and np.ndim(planes[1]) == 0:
+    if len(planes) == 2 and not isinstance(planes[1], (list, tuple)) and np.ndim(planes[1]) == 0:     # (two frames' pairs are not ONE pair)
         planes = [planes] * nf
     return np.asarray([[float(w[0]), float(w[1]), float(w[2]), float(h)] for w, h in planes], np.float64).reshape(nf, 4)
 
@@ -396,17 +465,9 @@ class WeatherPlan:
         if tuple(tids.shape) != (nf, nl) or tids.dtype != torch.int32 or tuple(weather.shape) != (nf, 8) or weather.dtype != torch.float64 or \
                 not tids.is_contiguous() or not weather.is_contiguous() or tids.device != self.device or weather.device != self.device:
             raise ValueError("out must be (n_frames x n_lasers int32, n_frames x 8 float64) contiguous tensors on the plan's device")
-        with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream(self.device)
-            run = _run_stream(torch, self.eng, self.device, stream)
-            if run is not stream:
-                run.wait_stream(stream)
-            try:
-                self.eng.ctx.draw_weather_device(nf, nl, int(self.set_ids.shape[0]), self.set_ids.data_ptr(), self.struct, self.seed,
-                                                 self.step.data_ptr(), tids.data_ptr(), weather.data_ptr(), run.cuda_stream)
-            finally:
-                if run is not stream:
-                    stream.wait_stream(run)
+        with torch.cuda.device(self.device), _on_run_stream(torch, self.eng, self.device) as (_, run):
+            self.eng.ctx.draw_weather_device(nf, nl, int(self.set_ids.shape[0]), self.set_ids.data_ptr(), self.struct, self.seed,
+                                             self.step.data_ptr(), tids.data_ptr(), weather.data_ptr(), run.cuda_stream)
         return tids, weather
 
 
@@ -449,25 +510,11 @@ def fov_keep(frames, calib, img_shape=(1024, 1920), keep=None, *, device=None, s
     if not is_device_input(frames):
         raise ValueError("fov_keep: torch CUDA tensors (host arrays: lidar_snow_sim_amd.calibration.get_fov_flag)")
     import torch
-    from . import engine as _engine
-    rows, offsets, _ = _as_batch(torch, frames)
-    dev = rows.device
-    if device is not None and int(device) != dev.index:
-        raise ValueError(f"the tensors live on {dev}, device={device} was asked for")
+    rows, offsets, _, eng = _resolve_input(torch, frames, False, device, slot)
     if keep is not None:
         keep = _keep_mask(torch, keep, rows, offsets)
-    eng = _engine.get_engine(dev.index, slot)
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev)
-        run = _run_stream(torch, eng, dev, stream)
-        if run is not stream:
-            run.wait_stream(stream)
-        try:
-            out = _fov_mask(torch, eng, rows[:int(offsets[-1])], calib, img_shape, keep, run)
-        finally:
-            if run is not stream:
-                stream.wait_stream(run)
-    return out
+    with torch.cuda.device(rows.device), _on_run_stream(torch, eng, rows.device) as (_, run):
+        return _fov_mask(torch, eng, rows[:int(offsets[-1])], calib, img_shape, keep, run)
 
 
 def augment_batch(frames, particle_file_prefix, beam_divergence, shuffle=True, noise_floor=0.7, root_path=None, *, planes=None,
@@ -520,7 +567,6 @@ def augment_batch(frames, particle_file_prefix, beam_divergence, shuffle=True, n
              well, as in the host entry.  The compact layout raises: its pre-crop is a step of the host entry.
     """
     import torch
-    from . import engine as _engine
     if q8 != 'first':
         raise ValueError("q8='numpy' selects the histogram minima with the HOST's NumPy: it needs host arrays, not CUDA tensors")
     if calib is not None and pre_crop and layout != 'aligned':
@@ -540,20 +586,8 @@ def augment_batch(frames, particle_file_prefix, beam_divergence, shuffle=True, n
                          "sums over other tiles; call augment_wet_batch_aligned for the aligned chain, or use the compact layout")
     if aligned and return_src:
         raise ValueError("return_src with layout='aligned': there is no src, row i of the result is input row i")
-    if in_place:
-        rows, offsets = _rows_where_they_lie(torch, frames)
-        extras = None
-    else:
-        rows, offsets, extras = _as_batch(torch, frames)
+    rows, offsets, extras, eng = _resolve_input(torch, frames, in_place, device, slot, lane)
     dev = rows.device
-    if device is not None and int(device) != dev.index:
-        raise ValueError(f"the tensors live on {dev}, device={device} was asked for")
-    eng = _engine.get_engine(dev.index, slot if lane is None else LANE_SLOT0 + int(lane))
-    if lane is not None and not eng.__dict__.get("_lane_serial"):
-        # a compute lane: its batches overlap OTHER lanes' batches, not their own side streams -- one stream per lane (snowgpu_set_serial; with
-        # GPU_MAX_HW_QUEUES >= 16 in the environment every lane's stream has a hardware queue of its own: include/snowgpu.h)
-        eng.ctx.set_serial(True)
-        eng.__dict__["_lane_serial"] = True
     nf, n = len(offsets) - 1, int(offsets[-1])
     if nf == 0:
         return []
@@ -562,6 +596,10 @@ def augment_batch(frames, particle_file_prefix, beam_divergence, shuffle=True, n
     code = 0 if rows.dtype == torch.float32 else 1
     max_rows = int(np.diff(offsets).max())
     up = _uploads(eng)
+    wet_plane = None
+    if wet is not None:
+        wet = dict(wet)
+        wet_plane = wet.pop("plane", None)
     with torch.cuda.device(dev):
         tids = table_ids_for(eng, nf, particle_file_prefix, root_path, particles, orders, shuffle)
         if n == 0:                                   # nothing to simulate (the C ABI wants non-null buffers): empty frames come back empty
@@ -575,45 +613,10 @@ def augment_batch(frames, particle_file_prefix, beam_divergence, shuffle=True, n
             if sync:
                 return empty
             return DeviceResult(eng.ctx, rows[:0], z(0, dt=torch.int32), z(nf), z(nf, 3), z(8, dt=torch.int32), offsets, torch.cuda.current_stream(dev))
-        stream = torch.cuda.current_stream(dev)
-        # The C ABI reads stream = NULL as "the context's own stream", which is not ordered against anything of torch's.  torch's legacy
-        # default stream HAS the handle 0, so a call made on it runs on a side stream of the engine, forked from and joined back into the
-        # default stream (two event waits): uploads queued before the call are seen, and whoever reads the results on the caller's stream
-        # afterwards -- or synchronises it -- waits for the call.
-        run = _run_stream(torch, eng, dev, stream, lane)
-        d_off = up.get(torch, dev, offsets, run)
-        d_tids = up.get(torch, dev, tids, run)
-        d_poly = d_plane = None
-        if thr_polys is not None:
-            d_poly = up.get(torch, dev, np.ascontiguousarray(thr_polys, np.float64).reshape(nf, 3), run)
-        elif planes is not None:
-            if isinstance(planes, np.ndarray) and planes.shape == (nf, 4):          # (wx, wy, wz, h) rows, as the C ABI takes them
-                pl = np.ascontiguousarray(planes, np.float64)
-            else:
-                pl = np.asarray([[float(w[0]), float(w[1]), float(w[2]), float(h)] for w, h in planes], np.float64).reshape(nf, 4)
-            d_plane = up.get(torch, dev, pl, run)
-        d_wet_plane = None
-        if wet is not None:
-            wet = dict(wet)
-            wp = wet.pop("plane", None)
-            if wp is not None:
-                wp = [wp] * nf if len(wp) == 2 and np.ndim(wp[1]) == 0 else wp
-                d_wet_plane = up.get(torch, dev, np.asarray([[float(w[0]), float(w[1]), float(w[2]), float(h)] for w, h in wp], np.float64), run)
         out_dt = torch.float64 if wet is not None else rows.dtype
-        o_keep = None
+        o_src = o_keep = None
         if aligned:
-            o_src = o_flags = None
-            if isinstance(out, AlignedResult) and out.keep.shape[0] == n and out.keep.device == dev and out.counts.shape[0] == nf and \
-                    (in_place or (out.rows.shape[0] == n and out.rows.dtype == out_dt and out.rows.data_ptr() != rows.data_ptr())):
-                o_rows, o_keep, o_cnt, o_st, o_status = out.rows, out.keep, out.counts, out.stats, out.status
-            else:
-                o_rows = None if in_place else torch.empty((n, 5), dtype=out_dt, device=dev)
-                o_keep = torch.empty(n, dtype=torch.bool, device=dev)              # (one byte per flag, 0 / 1: what the kernel writes)
-                o_cnt = torch.empty(nf, dtype=torch.int64, device=dev)
-                o_st = torch.empty((nf, 3), dtype=torch.int64, device=dev)
-                o_status = torch.empty(8, dtype=torch.int32, device=dev)
-            if in_place:
-                o_rows = rows
+            o_rows, o_keep, o_cnt, o_st, o_status, o_flags = _aligned_outputs(torch, out, AlignedResult, rows, n, nf, in_place)
         elif out is not None and not isinstance(out, AlignedResult) and out.rows.shape[0] >= n and out.rows.dtype == out_dt and out.rows.device == dev and out.counts.shape[0] == nf:
             o_rows, o_src, o_cnt, o_st, o_status, o_flags = out.rows, out.src, out.counts, out.stats, out.status, out.flags
         else:
@@ -625,58 +628,49 @@ def augment_batch(frames, particle_file_prefix, beam_divergence, shuffle=True, n
             o_flags = None
         if wet is not None and o_flags is None:
             o_flags = torch.empty(nf, dtype=torch.int32, device=dev)
-        if run is not stream:
-            run.wait_stream(stream)
-            if lane is not None:                    # (tensors of the caller's stream used on the lane's: the allocator must know)
-                for t in (rows, o_rows, o_src, o_keep, o_cnt, o_st, o_status, o_flags, keep):
-                    if t is not None:
-                        t.record_stream(run)
+        # calculate_plane (simulation.py:449; augmentation.py:41 for the wet stage) on the device where the call brings no plane
+        estimated = (thr_polys is None and planes is None) or (wet is not None and wet_plane is None)
+        used = (rows, o_rows, o_src, o_keep, o_cnt, o_st, o_status, o_flags, keep)
         ptr = lambda t: 0 if t is None else t.data_ptr()   # noqa: E731
-        with eng.batch_lock:
-            if calib is not None:
-                eng.ctx.set_fov(calib, (1024, 1920))                                # simulation.py:536
-                if pre_crop:                                                        # precompute.py:96-99, as a mask
-                    keep = _fov_mask(torch, eng, rows[:n], calib, (1024, 1920), keep, run)
-                    if lane is not None:
-                        keep.record_stream(run)
-            device_plane = d_poly is None and d_plane is None                       # calculate_plane (simulation.py:449) on the device
-            if device_plane or (wet is not None and d_wet_plane is None):
-                eng.ctx.set_plane_method(plane_method, seed=plane_seed, trials=plane_trials, min_rows=5)
-            try:
-                if aligned and keep is not None:
-                    eng.ctx.augment_batch_device_aligned_masked(nf, n, max_rows, d_off.data_ptr(), rows.data_ptr(), code, d_tids.data_ptr(),
-                                                                float(beam_divergence), ptr(d_poly), ptr(d_plane), float(noise_floor), 0, keep.data_ptr(),
-                                                                o_rows.data_ptr(), o_keep.data_ptr(), o_cnt.data_ptr(), o_st.data_ptr(), 0,
-                                                                o_status.data_ptr(), run.cuda_stream)
-                elif aligned:
-                    eng.ctx.augment_batch_device_aligned(nf, n, max_rows, d_off.data_ptr(), rows.data_ptr(), code, d_tids.data_ptr(),
-                                                         float(beam_divergence), ptr(d_poly), ptr(d_plane), float(noise_floor), 0, o_rows.data_ptr(),
-                                                         o_keep.data_ptr(), o_cnt.data_ptr(), o_st.data_ptr(), 0, o_status.data_ptr(), run.cuda_stream)
-                elif wet is None:
-                    eng.ctx.augment_batch_device(nf, n, max_rows, d_off.data_ptr(), rows.data_ptr(), code, d_tids.data_ptr(),
-                                                 float(beam_divergence), ptr(d_poly), ptr(d_plane), float(noise_floor), 0, o_rows.data_ptr(),
-                                                 o_src.data_ptr(), o_cnt.data_ptr(), o_st.data_ptr(), 0, o_status.data_ptr(), run.cuda_stream)
-                else:
-                    w = dict(water_height=0.001, pavement_depth=0.0012, noise_floor=0.7, power_factor=15, flat_earth=False, delta=0.5,
-                             replace=True)
-                    unknown = set(wet) - set(w) - {"estimation_method", "debug"}
-                    if unknown:
-                        raise TypeError(f"unknown wet-ground arguments: {sorted(unknown)}")
-                    if wet.get("estimation_method", "linear") != "linear":
-                        raise ValueError("the fused snowfall + wet-ground call fits estimation_method='linear'")
-                    w.update({k: v for k, v in wet.items() if k in w})
-                    eng.ctx.augment_wet_batch_device(nf, n, max_rows, d_off.data_ptr(), rows.data_ptr(), code, d_tids.data_ptr(),
-                                                     float(beam_divergence), ptr(d_poly), ptr(d_plane), float(noise_floor), 0, ptr(d_wet_plane),
-                                                     w["water_height"], w["pavement_depth"], w["noise_floor"], w["power_factor"],
-                                                     w["flat_earth"], w["delta"], w["replace"], o_rows.data_ptr(), o_src.data_ptr(),
-                                                     o_cnt.data_ptr(), o_st.data_ptr(), o_flags.data_ptr(), o_status.data_ptr(), run.cuda_stream)
-            finally:
-                if run is not stream and lane is None:
-                    stream.wait_stream(run)
-                if calib is not None:
-                    eng.ctx.set_fov(None)
-                if plane_method != 'reference':
-                    eng.ctx.set_plane_method('reference')
+        with eng.batch_lock, _temporary_settings(eng.ctx, calib=calib, plane=(plane_method, plane_seed, plane_trials) if estimated else None), \
+                _on_run_stream(torch, eng, dev, lane, used) as (stream, run):
+            d_off = up.get(torch, dev, offsets, run)
+            d_tids = up.get(torch, dev, tids, run)
+            d_poly = d_plane = None
+            if thr_polys is not None:
+                d_poly = up.get(torch, dev, np.ascontiguousarray(thr_polys, np.float64).reshape(nf, 3), run)
+            elif planes is not None:
+                d_plane = up.get(torch, dev, _plane_rows(planes, nf), run)
+            d_wet_plane = None if wet_plane is None else up.get(torch, dev, _plane_rows(wet_plane, nf), run)
+            if calib is not None and pre_crop:                                      # precompute.py:96-99, as a mask
+                keep = _fov_mask(torch, eng, rows[:n], calib, (1024, 1920), keep, run)
+                if lane is not None:
+                    keep.record_stream(run)
+            if aligned and keep is not None:
+                eng.ctx.augment_batch_device_aligned_masked(nf, n, max_rows, d_off.data_ptr(), rows.data_ptr(), code, d_tids.data_ptr(),
+                                                            float(beam_divergence), ptr(d_poly), ptr(d_plane), float(noise_floor), 0, keep.data_ptr(),
+                                                            o_rows.data_ptr(), o_keep.data_ptr(), o_cnt.data_ptr(), o_st.data_ptr(), 0,
+                                                            o_status.data_ptr(), run.cuda_stream)
+            elif aligned:
+                eng.ctx.augment_batch_device_aligned(nf, n, max_rows, d_off.data_ptr(), rows.data_ptr(), code, d_tids.data_ptr(),
+                                                     float(beam_divergence), ptr(d_poly), ptr(d_plane), float(noise_floor), 0, o_rows.data_ptr(),
+                                                     o_keep.data_ptr(), o_cnt.data_ptr(), o_st.data_ptr(), 0, o_status.data_ptr(), run.cuda_stream)
+            elif wet is None:
+                eng.ctx.augment_batch_device(nf, n, max_rows, d_off.data_ptr(), rows.data_ptr(), code, d_tids.data_ptr(),
+                                             float(beam_divergence), ptr(d_poly), ptr(d_plane), float(noise_floor), 0, o_rows.data_ptr(),
+                                             o_src.data_ptr(), o_cnt.data_ptr(), o_st.data_ptr(), 0, o_status.data_ptr(), run.cuda_stream)
+            else:                                   # (not _wet_arguments: the compact chain fits 'linear' only and knows no poly_seed)
+                unknown = set(wet) - set(WET_DEFAULTS) - {"estimation_method", "debug"}
+                if unknown:
+                    raise TypeError(f"unknown wet-ground arguments: {sorted(unknown)}")
+                if wet.get("estimation_method", "linear") != "linear":
+                    raise ValueError("the fused snowfall + wet-ground call fits estimation_method='linear'")
+                w = dict(WET_DEFAULTS, **{k: v for k, v in wet.items() if k in WET_DEFAULTS})
+                eng.ctx.augment_wet_batch_device(nf, n, max_rows, d_off.data_ptr(), rows.data_ptr(), code, d_tids.data_ptr(),
+                                                 float(beam_divergence), ptr(d_poly), ptr(d_plane), float(noise_floor), 0, ptr(d_wet_plane),
+                                                 w["water_height"], w["pavement_depth"], w["noise_floor"], w["power_factor"],
+                                                 w["flat_earth"], w["delta"], w["replace"], o_rows.data_ptr(), o_src.data_ptr(),
+                                                 o_cnt.data_ptr(), o_st.data_ptr(), o_flags.data_ptr(), o_status.data_ptr(), run.cuda_stream)
     if aligned:
         res = AlignedResult(eng.ctx, o_rows, o_keep, o_cnt, o_st, o_status, offsets, stream if lane is None else run, keep=(rows, d_off, d_tids, d_poly, d_plane, keep))
         return res.frames() if sync else res
@@ -696,9 +690,6 @@ def augment_batch(frames, particle_file_prefix, beam_divergence, shuffle=True, n
     return results
 
 
-WET_DEFAULTS = dict(water_height=0.001, pavement_depth=0.0012, noise_floor=0.7, power_factor=15, flat_earth=False, delta=0.5, replace=True)
-
-
 def _wet_arguments(wet):
     """(parameters, plane or None, estimation method, RANSAC seed) from ground_water_augmentation()'s keyword arguments."""
     wet = dict(wet or {})
@@ -714,16 +705,17 @@ def _wet_arguments(wet):
     return dict(WET_DEFAULTS, **wet), plane, method, seed
 
 
-def _aligned_outputs(torch, out, rows, n, nf, in_place, with_stats):
-    """(rows, keep, counts, stats, status, flags) tensors of an aligned wet call: those of `out` (an AlignedWetResult of the same shapes) or new ones."""
-    dev = rows.device
-    if isinstance(out, AlignedWetResult) and out.keep.shape[0] == n and out.keep.device == dev and out.counts.shape[0] == nf and \
+def _aligned_outputs(torch, out, kind, rows, n, nf, in_place, with_stats=True):
+    """(rows, keep, counts, stats, status, flags) tensors of an aligned call: those of `out` (a `kind` -- AlignedResult or AlignedWetResult --
+    of the same shapes) or new ones; keep holds one byte per flag, 0 / 1: what the kernels write.  flags: None for an AlignedResult."""
+    dev, wet = rows.device, kind is AlignedWetResult
+    if isinstance(out, kind) and out.keep.shape[0] == n and out.keep.device == dev and out.counts.shape[0] == nf and \
             (out.stats is not None) == with_stats and \
             (in_place or (out.rows.shape[0] == n and out.rows.dtype == rows.dtype and out.rows.data_ptr() != rows.data_ptr())):
-        return (rows if in_place else out.rows), out.keep, out.counts, out.stats, out.status, out.flags
+        return (rows if in_place else out.rows), out.keep, out.counts, out.stats, out.status, (out.flags if wet else None)
     return (rows if in_place else torch.empty((n, 5), dtype=rows.dtype, device=dev), torch.empty(n, dtype=torch.bool, device=dev),
             torch.empty(nf, dtype=torch.int64, device=dev), torch.empty((nf, 3), dtype=torch.int64, device=dev) if with_stats else None,
-            torch.empty(8, dtype=torch.int32, device=dev), torch.empty(nf, dtype=torch.int32, device=dev))
+            torch.empty(8, dtype=torch.int32, device=dev), torch.empty(nf, dtype=torch.int32, device=dev) if wet else None)
 
 
 def _empty_aligned_wet(torch, eng, rows, nf, offsets, with_stats, sync):
@@ -758,14 +750,11 @@ def wet_ground_batch_aligned(frames, keep=None, *, plane=None, water_height=0.00
         raise ValueError("wet_ground_batch_aligned: the aligned layout is a result layout of the torch-tensor boundary (CUDA tensors); "
                          "host arrays get the reference's compacted return value from ground_water_augmentation")
     import torch
-    from . import engine as _engine
     w, _, method, seed = _wet_arguments(dict(water_height=water_height, pavement_depth=pavement_depth, noise_floor=noise_floor,
                                              power_factor=power_factor, flat_earth=flat_earth, delta=delta, replace=replace,
                                              estimation_method=estimation_method, poly_seed=poly_seed))
-    rows, offsets = _rows_where_they_lie(torch, frames) if in_place else _as_batch(torch, frames)[:2]
+    rows, offsets, _, eng = _resolve_input(torch, frames, in_place, device, slot)
     dev = rows.device
-    if device is not None and int(device) != dev.index:
-        raise ValueError(f"the tensors live on {dev}, device={device} was asked for")
     nf, n = len(offsets) - 1, int(offsets[-1])
     if nf == 0:
         return []
@@ -774,39 +763,24 @@ def wet_ground_batch_aligned(frames, keep=None, *, plane=None, water_height=0.00
             raise ValueError("keep must be a contiguous torch.bool (or uint8) CUDA tensor with one element per row of the batch")
         if keep.dtype == torch.uint8:
             keep = keep.view(torch.bool)
-    eng = _engine.get_engine(dev.index, slot)
     if n == 0:
         return _empty_aligned_wet(torch, eng, rows, nf, offsets, False, sync)
     code = 0 if rows.dtype == torch.float32 else 1
     up = _uploads(eng)
+    if lines is not None:
+        lines = np.ascontiguousarray(lines, np.float64).reshape(nf, 4)
     with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev)
-        run = _run_stream(torch, eng, dev, stream)
-        d_off = up.get(torch, dev, offsets, run)
-        d_plane = None if plane is None else up.get(torch, dev, _plane_rows(plane, nf), run)
-        o_rows, o_keep, o_cnt, _, o_status, o_flags = _aligned_outputs(torch, out, rows, n, nf, in_place, False)
+        o_rows, o_keep, o_cnt, _, o_status, o_flags = _aligned_outputs(torch, out, AlignedWetResult, rows, n, nf, in_place, False)
         if in_place and keep is not None:
             o_keep = keep
-        if run is not stream:
-            run.wait_stream(stream)
-        with eng.batch_lock:
-            if method != 'linear':
-                eng.ctx.set_wet_estimation(method, seed)
-            if lines is not None:
-                eng.ctx.set_wet_lines(np.ascontiguousarray(lines, np.float64).reshape(nf, 4))
-            try:
-                eng.ctx.wet_ground_batch_device_aligned(nf, n, int(np.diff(offsets).max()), d_off.data_ptr(), rows.data_ptr(), code,
-                                                        0 if keep is None else keep.data_ptr(), 0 if d_plane is None else d_plane.data_ptr(),
-                                                        w["water_height"], w["pavement_depth"], w["noise_floor"], w["power_factor"],
-                                                        w["flat_earth"], w["delta"], w["replace"], o_rows.data_ptr(), o_keep.data_ptr(),
-                                                        o_cnt.data_ptr(), o_flags.data_ptr(), o_status.data_ptr(), run.cuda_stream)
-            finally:
-                if run is not stream:
-                    stream.wait_stream(run)
-                if method != 'linear':
-                    eng.ctx.set_wet_estimation('linear')
-                if lines is not None:
-                    eng.ctx.set_wet_lines(None)
+        with eng.batch_lock, _temporary_settings(eng.ctx, wet_estimation=(method, seed), lines=lines), _on_run_stream(torch, eng, dev) as (stream, run):
+            d_off = up.get(torch, dev, offsets, run)
+            d_plane = None if plane is None else up.get(torch, dev, _plane_rows(plane, nf), run)
+            eng.ctx.wet_ground_batch_device_aligned(nf, n, int(np.diff(offsets).max()), d_off.data_ptr(), rows.data_ptr(), code,
+                                                    0 if keep is None else keep.data_ptr(), 0 if d_plane is None else d_plane.data_ptr(),
+                                                    w["water_height"], w["pavement_depth"], w["noise_floor"], w["power_factor"],
+                                                    w["flat_earth"], w["delta"], w["replace"], o_rows.data_ptr(), o_keep.data_ptr(),
+                                                    o_cnt.data_ptr(), o_flags.data_ptr(), o_status.data_ptr(), run.cuda_stream)
     res = AlignedWetResult(eng.ctx, o_rows, o_keep, o_cnt, None, o_status, offsets, stream, o_flags, keep=(rows, keep, d_off, d_plane))
     return res.frames() if sync else res
 
@@ -845,24 +819,17 @@ def augment_wet_batch_aligned(frames, particle_file_prefix, beam_divergence, shu
         raise ValueError("augment_wet_batch_aligned: the aligned layout is a result layout of the torch-tensor boundary (CUDA tensors); "
                          "host arrays get the reference's compacted return value from augment_batch / ground_water_augmentation")
     import torch
-    from . import engine as _engine
     if weather is not None and wet is not None and set(wet) & set(WEATHER_PER_FRAME):
         raise ValueError(f"with weather= the per-frame fields {sorted(set(wet) & set(WEATHER_PER_FRAME))} come from the weather records, not from wet=")
     if table_ids is not None and (orders is not None or particles is not None):
         raise ValueError("table_ids= are used as they are: orders= and particles= have nothing to act on")
     w, wet_plane, method, seed = _wet_arguments(wet)
-    rows, offsets = _rows_where_they_lie(torch, frames) if in_place else _as_batch(torch, frames)[:2]
+    rows, offsets, _, eng = _resolve_input(torch, frames, in_place, device, slot, lane)
     dev = rows.device
-    if device is not None and int(device) != dev.index:
-        raise ValueError(f"the tensors live on {dev}, device={device} was asked for")
-    eng = _engine.get_engine(dev.index, slot if lane is None else LANE_SLOT0 + int(lane))
     for name, t, shape, dt in (("weather", weather, (len(offsets) - 1, 8), torch.float64), ("table_ids", table_ids, (len(offsets) - 1, eng.n_lasers), torch.int32)):
         if t is not None and not (torch.is_tensor(t) and t.is_cuda and t.device == dev and tuple(t.shape) == shape and t.dtype == dt and t.is_contiguous()):
             raise ValueError(f"{name} must be a contiguous {shape[0]} x {shape[1]} {dt} CUDA tensor on the device of the rows")
     prefixes = None if table_ids is not None else _prefix_list(particle_file_prefix, len(offsets) - 1)
-    if lane is not None and not eng.__dict__.get("_lane_serial"):
-        eng.ctx.set_serial(True)                      # (a compute lane runs its batches on one stream: augment_batch)
-        eng.__dict__["_lane_serial"] = True
     nf, n = len(offsets) - 1, int(offsets[-1])
     if nf == 0:
         return []
@@ -879,54 +846,31 @@ def augment_wet_batch_aligned(frames, particle_file_prefix, beam_divergence, shu
         if table_ids is None:
             tids = table_ids_for(eng, nf, particle_file_prefix, root_path, particles, orders, shuffle) if prefixes is None else \
                 table_ids_per_frame(eng, prefixes, root_path, particles, orders, shuffle)
-        stream = torch.cuda.current_stream(dev)
-        run = _run_stream(torch, eng, dev, stream, lane)
-        d_off = up.get(torch, dev, offsets, run)
-        d_tids = up.get(torch, dev, tids, run) if table_ids is None else table_ids
-        d_poly = d_plane = None
-        if thr_polys is not None:
-            d_poly = up.get(torch, dev, np.ascontiguousarray(thr_polys, np.float64).reshape(nf, 3), run)
-        elif planes is not None:
-            d_plane = up.get(torch, dev, _plane_rows(planes, nf), run)
-        d_wet_plane = None if wet_plane is None else up.get(torch, dev, _plane_rows(wet_plane, nf), run)
-        o_rows, o_keep, o_cnt, o_st, o_status, o_flags = _aligned_outputs(torch, out, rows, n, nf, in_place, True)
-        if run is not stream:
-            run.wait_stream(stream)
-            if lane is not None:                    # (tensors of the caller's stream used on the lane's: the allocator must know)
-                for t in (rows, o_rows, o_keep, o_cnt, o_st, o_status, o_flags) + tuple(t for t in (keep, weather, table_ids) if t is not None):
-                    t.record_stream(run)
+        o_rows, o_keep, o_cnt, o_st, o_status, o_flags = _aligned_outputs(torch, out, AlignedWetResult, rows, n, nf, in_place)
+        used = (rows, o_rows, o_keep, o_cnt, o_st, o_status, o_flags, keep, weather, table_ids)
         ptr = lambda t: 0 if t is None else t.data_ptr()   # noqa: E731
-        with eng.batch_lock:
-            if calib is not None:
-                eng.ctx.set_fov(calib, (1024, 1920))
-                if pre_crop:                                                        # precompute.py:96-99, as a mask
-                    keep = _fov_mask(torch, eng, rows[:n], calib, (1024, 1920), keep, run)
-                    if lane is not None:
-                        keep.record_stream(run)
-            if method != 'linear':
-                eng.ctx.set_wet_estimation(method, seed)
-            try:
-                if weather is not None:
-                    eng.ctx.augment_weather_batch_device_aligned(nf, n, int(np.diff(offsets).max()), d_off.data_ptr(), rows.data_ptr(), code,
-                                                                 d_tids.data_ptr(), float(beam_divergence), ptr(d_poly), ptr(d_plane),
-                                                                 float(noise_floor), 0, ptr(keep), o_rows.data_ptr(), o_keep.data_ptr(),
-                                                                 o_cnt.data_ptr(), o_st.data_ptr(), 0, o_status.data_ptr(), run.cuda_stream,
-                                                                 ptr(d_wet_plane), weather.data_ptr(), w["flat_earth"], w["replace"],
-                                                                 o_flags.data_ptr())
-                else:
-                    eng.ctx.augment_wet_batch_device_aligned_masked(nf, n, int(np.diff(offsets).max()), d_off.data_ptr(), rows.data_ptr(), code,
-                                                                    d_tids.data_ptr(), float(beam_divergence), ptr(d_poly), ptr(d_plane),
-                                                                    float(noise_floor), 0, ptr(keep), o_rows.data_ptr(), o_keep.data_ptr(), o_cnt.data_ptr(),
-                                                                    o_st.data_ptr(), 0, o_status.data_ptr(), run.cuda_stream, ptr(d_wet_plane),
-                                                                    w["water_height"], w["pavement_depth"], w["noise_floor"], w["power_factor"],
-                                                                    w["flat_earth"], w["delta"], w["replace"], o_flags.data_ptr())
-            finally:
-                if run is not stream and lane is None:
-                    stream.wait_stream(run)
-                if calib is not None:
-                    eng.ctx.set_fov(None)
-                if method != 'linear':
-                    eng.ctx.set_wet_estimation('linear')
+        with eng.batch_lock, _temporary_settings(eng.ctx, calib=calib, wet_estimation=(method, seed)), \
+                _on_run_stream(torch, eng, dev, lane, used) as (stream, run):
+            d_off = up.get(torch, dev, offsets, run)
+            d_tids = up.get(torch, dev, tids, run) if table_ids is None else table_ids
+            d_poly = d_plane = None
+            if thr_polys is not None:
+                d_poly = up.get(torch, dev, np.ascontiguousarray(thr_polys, np.float64).reshape(nf, 3), run)
+            elif planes is not None:
+                d_plane = up.get(torch, dev, _plane_rows(planes, nf), run)
+            d_wet_plane = None if wet_plane is None else up.get(torch, dev, _plane_rows(wet_plane, nf), run)
+            if calib is not None and pre_crop:                                      # precompute.py:96-99, as a mask
+                keep = _fov_mask(torch, eng, rows[:n], calib, (1024, 1920), keep, run)
+                if lane is not None:
+                    keep.record_stream(run)
+            snow = (nf, n, int(np.diff(offsets).max()), d_off.data_ptr(), rows.data_ptr(), code, d_tids.data_ptr(), float(beam_divergence), ptr(d_poly),
+                    ptr(d_plane), float(noise_floor), 0, ptr(keep), o_rows.data_ptr(), o_keep.data_ptr(), o_cnt.data_ptr(), o_st.data_ptr(), 0,
+                    o_status.data_ptr(), run.cuda_stream, ptr(d_wet_plane))
+            if weather is not None:
+                eng.ctx.augment_weather_batch_device_aligned(*snow, weather.data_ptr(), w["flat_earth"], w["replace"], o_flags.data_ptr())
+            else:
+                eng.ctx.augment_wet_batch_device_aligned_masked(*snow, w["water_height"], w["pavement_depth"], w["noise_floor"], w["power_factor"],
+                                                                w["flat_earth"], w["delta"], w["replace"], o_flags.data_ptr())
     res = AlignedWetResult(eng.ctx, o_rows, o_keep, o_cnt, o_st, o_status, offsets, stream if lane is None else run, o_flags,
                            keep=(rows, d_off, d_tids, d_poly, d_plane, d_wet_plane, keep, weather))
     return res.frames() if sync else res

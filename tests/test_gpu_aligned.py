@@ -287,3 +287,43 @@ def test_errors(tl):
         augment_batch([pc], "unused", BD, planes=[PLANE], particles=tl, layout="aligned")
     with pytest.raises(ValueError, match="layout"):
         augment_batch([torch.from_numpy(pc).cuda()], "unused", BD, planes=[PLANE], particles=tl, layout="sorted")
+
+
+def test_compact_fused_entry_ignores_wet_lines_and_the_aligned_wet_entry_takes_them(tl):
+    """Lines left by snowgpu_set_wet_lines: snowgpu_augment_wet_batch_device never looks at them -- rows, src, counts and flags of the compact
+    fused call are the same bytes with and without -- and they stay set; the next wet_ground_batch_aligned(lines=None) on the context
+    takes them (its result is that of lines=LINES, not that of the device's fit) and clears them.  Two float32 frames of 1 200 rows, all
+    of them ground rows (prepass_reference.road, the generator of the wet aligned tests' frames), under tables thinned to 40 flakes a
+    line: the snowfall stage removes the frames' dark rows (186 and 177) and scatters a dozen, so both keep more than 1 000 ground rows
+    and the wet model runs (flag 0; with 1 150 ground rows of 1 200 it does not)."""
+    import prepass_reference as pr
+    from lidar_snow_sim_amd import engine
+    from lidar_snow_sim_amd.tensors import augment_batch, wet_ground_batch_aligned
+    eng = engine.get_engine(0)
+    frames = [torch.from_numpy(pr.road(1200, 0, 430 + k, np.float32)).cuda() for k in (1, 2)]
+    thin = [np.ascontiguousarray(t[:40]) for t in tl]
+    lines = np.array([pr.LINES] * 2, np.float64)
+    kw = dict(planes=[PLANE] * 2, orders=[list(range(64))] * 2, particles=thin, return_src=True, wet=dict(pr.LINES_PARAMS, plane=PLANE), sync=True)
+
+    def fused():
+        out = augment_batch(frames, "unused", BD, **kw)
+        return [(tuple(int(v) for v in st), aug.cpu().numpy().tobytes(), src.cpu().numpy().tobytes(), int(aug.shape[0])) for st, aug, src in out]
+
+    def wet_only(given):
+        r = wet_ground_batch_aligned(frames, None, plane=PLANE, lines=given, sync=False, **pr.LINES_PARAMS).wait()
+        assert r.flags.tolist() == [0, 0]
+        return r
+    try:
+        flags = augment_batch(frames, "unused", BD, **dict(kw, sync=False)).wait().flags.tolist()
+        assert flags == [0, 0], flags                      # the wet model did run behind the snowfall
+        without = fused()
+        eng.ctx.set_wet_lines(lines)
+        with_lines = fused()
+        assert with_lines == without and all(0 < f[3] < 1000 for f in without)       # (fewer than the snowfall stage left: the wet stage dropped rows)
+        left = wet_only(None)                              # the lines are still there: this call consumes them
+        plain = wet_only(None)
+        given = wet_only(lines)
+    finally:
+        eng.ctx.set_wet_lines(None)
+    assert torch.equal(left.rows, given.rows) and torch.equal(left.keep, given.keep) and torch.equal(left.counts, given.counts)
+    assert not torch.equal(left.rows, plain.rows) and not torch.equal(given.counts, plain.counts)
