@@ -440,8 +440,7 @@ __device__ __forceinline__ SgQsPair sg_qs_load(const uint32_t *p) { return SgQsP
 // pairs at a time whichever beams they belong to -- the owner's geometry travels by cross-lane reads.  A hit is appended to
 // its owner's list through an LDS counter; every beam sorts its few entries by (range, scan order) afterwards, which is the
 // order the per-lane scan produces.  Bins beyond the second (wedges wider than a bin) keep the per-lane loop.
-// s_cnt: one int per lane of the block; s_key: LMAX ints per lane (the scan order of the stored entries); s_st: two ints per lane; s_mark: one
-// int per lane (sg_pair_owner; the host harness passes none).
+// s_cnt: one int per lane of the block; s_key: LMAX ints per lane (the scan order of the stored entries); s_st: two ints per lane.
 // DEFER (the pass over all rows in the default arithmetic): a beam one of whose distance tests falls inside the band of
 // sg_near_ray is not decided here: SG_HITS_UNDECIDED is set in its flake count (with `overflow`), nothing is kept of its list, and the
 // caller sends it to the global-list tier, whose scan carries the reference's expression.  About one test in 1e8 on ordinary input.
@@ -449,10 +448,15 @@ __device__ __forceinline__ SgQsPair sg_qs_load(const uint32_t *p) { return SgQsP
 // the record's index in the table | bit 30: the left angle is the beam's right limit | bit 31: the right angle is the beam's left limit
 // (geometry.py:26-27; otherwise they are the record's tangent angles t0 / t1) -- in the column s_a1 points to, read as uint32_t; s_a2 is
 // not used.  The caller resolves the word when it hands the list on (sg_hit_angles).  19 KB of LDS per 256 beams instead of 31.
-template <typename T, int LMAX, int STRIDE, bool DEFER = false, bool COMPACT = false>
-__device__ __forceinline__ int sg_wave_scan(bool act, T px, T py, T pz, const SgTable tab, double beam_div_deg, double *s_a1, double *s_a2,
-                                            double *s_rho, int *s_cnt, int *s_key, int *s_st, int tid, SgBeamOut &out, T &d_t, double &theta_c,
-                                            bool EXACT_TAN, double *ov_blk = nullptr, int ov_cap = 0, int *s_mark = nullptr)
+// UTAB (the segment order of the pass over all rows): every lane of the wave passes the SAME table -- the descriptor lives in scalar
+// registers and the owner's table pointer does not travel with its geometry.
+// theta_t: the beam's azimuth in the row dtype -- for float32 rows the float32 value the reference computes (simulation.py:91-92), whose
+// widening is theta_c.  Range and azimuth of a float32 row cross the lanes as one dword each and are widened on the receiving side: the
+// same bits as widening first, half the cross-lane reads and half the registers kept through the loop.
+template <typename T, int LMAX, int STRIDE, bool DEFER = false, bool COMPACT = false, bool UTAB = false>
+__device__ __forceinline__ int sg_wave_scan_t(bool act, T px, T py, T pz, const SgTable tab, double beam_div_deg, double *s_a1, double *s_a2,
+                                              double *s_rho, int *s_cnt, int *s_key, int *s_st, int tid, SgBeamOut &out, T &d_t, T &theta_t,
+                                              bool EXACT_TAN, double *ov_blk = nullptr, int ov_cap = 0)
 {
     // ov_blk: overflow slot of the block's column 0 (the slots follow the columns), or null.  Flakes LMAX .. ov_cap - 1 of a beam go
     // to its slot as they are met (the caller adds the first LMAX and the header if the beam ends up within ov_cap).
@@ -462,10 +466,10 @@ __device__ __forceinline__ int sg_wave_scan(bool act, T px, T py, T pz, const Sg
     SgBeamGeo g{};
     uint32_t st0 = 0, st2 = 0;
     int n0 = 0, n1 = 0, span = -1, b_lo = 0, nb = 1;
-    d_t = 0; theta_c = 0.0;
+    d_t = 0; theta_t = 0;
     if (act) {
         g = sg_beam_geometry<T>(px, py, pz, beam_div_deg, EXACT_TAN, d_t);
-        theta_c = g.theta_c;
+        theta_t = (T)g.theta_c;                                 // exact: float32 rows widened a float32 azimuth
         nb = (int)tab.n_bins;
         b_lo = sg_bin_of(g.theta_r - SG_BEAM_MARGIN, tab.inv_bin_w, nb);
         const int b_hi = sg_bin_of(g.theta_l + SG_BEAM_MARGIN, tab.inv_bin_w, nb);
@@ -526,13 +530,10 @@ __device__ __forceinline__ int sg_wave_scan(bool act, T px, T py, T pz, const Sg
     const int incl = sg_wave_incl_add(cnt);
     const int excl = incl - cnt;
     const int total = sg_wave_last(incl);
-    const unsigned long long ent_bits = (unsigned long long)tab.entries;
+    [[maybe_unused]] const unsigned long long ent_bits = (unsigned long long)tab.entries;
     for (int base = 0; base < total; base += SG_PAIR_WINDOW) {
         const int p = base + lane;
         const bool valid = p < total;
-#if defined(SG_SCAN_OWNER_MARKS)
-        const int o = sg_pair_owner(s_mark, tid, base, excl, incl);    // first lane whose inclusive count exceeds p
-#else
         // (sg_pair_owner here -- marks and a prefix maximum instead of the search -- was measured: the pass 6 % slower; the search's cross-lane
         // reads overlap the record loads of the trip before, the marks' LDS writes and 24 B of spilled registers did not pay for them)
         int lo = 0, hi = 63;                                    // owner = first lane whose inclusive count exceeds p
@@ -542,16 +543,18 @@ __device__ __forceinline__ int sg_wave_scan(bool act, T px, T py, T pz, const Sg
             if (v > p) hi = mid; else lo = mid + 1;
         }
         const int o = lo & 63;
-#endif
         const int j = p - __shfl(excl, o);
         const int n0o = __shfl(n0, o);
         const uint32_t st0o = (uint32_t)s_st[2 * (wbase + o)], st2o = (uint32_t)s_st[2 * (wbase + o) + 1];
         const uint32_t e = j < n0o ? st0o + (uint32_t)j : st2o + (uint32_t)(j - n0o);
         SgBeamGeo og;
-        og.d = __shfl(g.d, o); og.theta_c = __shfl(g.theta_c, o);
+        if constexpr (SgReal<T>::is_f32) { og.d = (double)__shfl(d_t, o); og.theta_c = (double)__shfl(theta_t, o); }
+        else { og.d = __shfl(g.d, o); og.theta_c = __shfl(g.theta_c, o); }
         og.sr = __shfl(g.sr, o); og.cr = __shfl(g.cr, o); og.sl = __shfl(g.sl, o); og.cl = __shfl(g.cl, o);
         og.exact = EXACT_TAN;
-        const SgEntry *oent = (const SgEntry *)(((unsigned long long)__shfl((unsigned)(ent_bits >> 32), o) << 32) | (unsigned long long)__shfl((unsigned)ent_bits, o));
+        const SgEntry *oent = tab.entries;
+        if constexpr (!UTAB)
+            oent = (const SgEntry *)(((unsigned long long)__shfl((unsigned)(ent_bits >> 32), o) << 32) | (unsigned long long)__shfl((unsigned)ent_bits, o));
         if (valid) {
             sg_geo_limits(og, beam_div_deg);
             const SG_GLOBAL SgEntry *fp = sg_gptr(oent) + e;
@@ -588,6 +591,10 @@ __device__ __forceinline__ int sg_wave_scan(bool act, T px, T py, T pz, const Sg
     if (undecided) hits &= ~SG_HITS_UNDECIDED;
     int L = hits < LMAX ? hits : LMAX;
     if (act && span >= 2) {                                     // wedges wider than a bin: the further bins, per lane
+        if constexpr (SgReal<T>::is_f32) {                      // (range, azimuth and limits as the preamble had them, from the two dwords kept)
+            g.d = (double)d_t; g.theta_c = (double)theta_t;
+            sg_geo_limits(g, beam_div_deg);
+        }
         int b = b_lo + 2 >= nb ? b_lo + 2 - nb : b_lo + 2;
         int key = 0x40000000;
         for (int s = 2; s <= span; ++s) {
@@ -645,6 +652,19 @@ __device__ __forceinline__ int sg_wave_scan(bool act, T px, T py, T pz, const Sg
     out.n_hits = hits;
     if (hits > LMAX) out.overflow = 1;
     if (undecided) { out.n_hits = hits | SG_HITS_UNDECIDED; out.overflow = 1; }
+    return L;
+}
+
+// the same with the azimuth widened, per-lane tables (the host harnesses and the CPU twin)
+template <typename T, int LMAX, int STRIDE, bool DEFER = false, bool COMPACT = false>
+__device__ __forceinline__ int sg_wave_scan(bool act, T px, T py, T pz, const SgTable tab, double beam_div_deg, double *s_a1, double *s_a2,
+                                            double *s_rho, int *s_cnt, int *s_key, int *s_st, int tid, SgBeamOut &out, T &d_t, double &theta_c,
+                                            bool EXACT_TAN, double *ov_blk = nullptr, int ov_cap = 0)
+{
+    T theta_t;
+    const int L = sg_wave_scan_t<T, LMAX, STRIDE, DEFER, COMPACT>(act, px, py, pz, tab, beam_div_deg, s_a1, s_a2, s_rho, s_cnt, s_key, s_st, tid, out, d_t,
+                                                                  theta_t, EXACT_TAN, ov_blk, ov_cap);
+    theta_c = (double)theta_t;
     return L;
 }
 

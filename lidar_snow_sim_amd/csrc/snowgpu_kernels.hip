@@ -25,7 +25,12 @@
 #define SG_KP_WIN 3       /* k_power: a work item of the multi-flake beams is this many waves' worth of slots, taken in order of flake count */
 #endif
 #ifndef SG_FP_WAVES
-#define SG_FP_WAVES 6     /* waves per SIMD the pass over all rows is compiled for (<= 80 VGPRs; its LDS -- 19 KB per block -- would allow 8) */
+#define SG_FP_WAVES 6     /* waves per SIMD the pass over all rows is compiled for in its general form (a caller's permutation: <= 80 VGPRs) ... */
+#endif
+#ifndef SG_FP_WAVES_SEG
+#define SG_FP_WAVES_SEG 7 /* ... and in the segment order, whose block-uniform state -- frame, channel, table descriptor, row base -- lives in scalar
+                             registers (float32 rows: 70 VGPRs, no scratch; its LDS -- 19 KB per block -- would allow 8.  float64 rows carry range
+                             and azimuth as register pairs and spill at seven waves: they keep SG_FP_WAVES) */
 #endif
 #ifndef SG_NB_TIERS
 #define SG_NB_TIERS 4     /* ... and by the later tiers (8 until the dict's endpoints moved into registers; since then, same box, 8 / 4 / 3 / 2:
@@ -112,10 +117,17 @@ __device__ __forceinline__ int64_t sg_qaddr(int64_t slot, int plane)
 //   BLOCK         beams per block = stride of the LDS lists.  BLOCK = 16 (the 63-entry tier) still launches one wave: 16
 //                 live lanes, 32 KB of LDS per block instead of 131 KB -- a block that needs most of a CU's LDS waits until
 //                 one has drained, and meanwhile holds up everything queued behind it.
-template <typename T, int LMAX, int BLOCK, bool LIST, int DICT>
-__global__ __launch_bounds__(BLOCK < 64 ? 64 : BLOCK, (!LIST && DICT == 1 && BLOCK == 256) ? SG_FP_WAVES : 1) void k_beams(SgBeamArgs a)
+//   SEG = true    the pass over all rows in the segment order (a.seg_blk: every batch without a caller's permutation): a block serves ONE
+//                 (frame, channel) segment, so its frame, channel, table descriptor and row base are the same for all its lanes.  They are
+//                 read by scalar loads and stay in scalar registers; a row is the block's scalar base plus a 32-bit lane offset; the wave
+//                 scan is told that the table is uniform (sg_wave_scan_t, UTAB).  The registers that frees are a seventh wave per SIMD.
+//   SEG = false   linear chunks of the sorted rows (a caller's permutation) and the LIST passes: frame and table per lane.
+template <typename T, int LMAX, int BLOCK, bool LIST, int DICT, bool SEG = false>
+__global__ __launch_bounds__(BLOCK < 64 ? 64 : BLOCK, (!LIST && DICT == 1 && BLOCK == 256) ? (SEG && sizeof(T) == 4 ? SG_FP_WAVES_SEG : SG_FP_WAVES) : 1) void k_beams(SgBeamArgs a)
 {
     static_assert(!LIST || DICT == 0, "a list-mode pass runs phases 1-3 in place");
+    static_assert(!SEG || (!LIST && DICT != 0), "the segment order is the hand-over pass over all rows");
+    using G = std::conditional_t<SEG, int32_t, int64_t>;     // a sorted position (segments exist for n_total < 2^31)
     extern __shared__ __attribute__((aligned(16))) char smem[];
     // the hand-over pass keeps LMAX-entry lists; the in-place passes four of LMAX + 1 entries
     // (the dict and the scatterer list of phase 3 carry the hard target as entry n_flakes <= LMAX)
@@ -130,7 +142,6 @@ __global__ __launch_bounds__(BLOCK < 64 ? 64 : BLOCK, (!LIST && DICT == 1 && BLO
     int *s_cnt = DICT ? (int *)(reinterpret_cast<uint32_t *>(s_a1) + ROWS * BLOCK) : nullptr;     // wave scan: flakes met per beam ...
     int *s_key = DICT ? s_cnt + (BLOCK < 64 ? 64 : BLOCK) : nullptr;      // ... and the scan order of the stored ones
     int *s_st = DICT ? s_key + LMAX * BLOCK : nullptr;                    // ... and where its two bins start (two ints per lane)
-    int *s_mark = DICT ? s_st + 2 * (BLOCK < 64 ? 64 : BLOCK) : nullptr;  // ... and the owner marks of a trip of its pair loop (sg_pair_owner)
     const int tid = threadIdx.x;
     const int n_las = a.las->n;
     int64_t work_n = 0, work_off = 0;
@@ -140,31 +151,30 @@ __global__ __launch_bounds__(BLOCK < 64 ? 64 : BLOCK, (!LIST && DICT == 1 && BLO
         work_off = (int64_t)a.cls * a.tier_stride;
     }
     const int64_t stride = (int64_t)gridDim.x * BLOCK;
-    int seg_f = -1, seg_ch = -1;                      // segment-ordered direct mode: the block's frame and channel
-    int64_t seg_g = -1, q_base = 0;
+    int64_t q_base = 0;                               // direct mode: the block's region -- its slice of the sorted positions and of the queue
     int q_size = 0, region = 0;
-    [[maybe_unused]] int seg_blk0 = 0;                // segment-ordered direct mode: first block of the block's segment
+    [[maybe_unused]] int seg_f = 0, seg_ch = 0;       // segment order: the block's frame and channel ...
+    [[maybe_unused]] int64_t seg_g0 = 0;              // ... the sorted position of its column 0 ...
+    [[maybe_unused]] int seg_rows = 0;                // ... and how many of its columns hold a row
     int64_t blk = blockIdx.x;                         // direct mode: this launch walks blocks [lo, hi) of the pass
     if (!LIST) {
         const int64_t lo = a.chunk_blk ? a.chunk_blk[a.chunk] : a.blk_lo, hi = a.chunk_blk ? a.chunk_blk[a.chunk + 1] : a.blk_hi;
         blk += lo;
         if (blk >= hi) return;                        // surplus block (the grid is an upper bound)
         blk = (int64_t)__builtin_amdgcn_readfirstlane((int)blk);   // (scalar: see below)
-        if (a.seg_blk) {
+        if constexpr (SEG) {
             // block-uniform values, pinned to scalar registers (left to itself the compiler kept the region index in a vector
             // register pair for the whole kernel -- and spilled it when the kernel was held to five waves per SIMD)
             // the block's record -- segment, its first sorted position, its rows, frame | channel, its first block: ONE round trip (block ->
             // segment -> the segment's four arrays were two, on the chain of a dozen that a wave of this pass is)
             const int32_t *br = a.seg_of_blk + blk * SG_BLKREC;
-            const int sg = __builtin_amdgcn_readfirstlane(br[0]);
-            const int blk0 = __builtin_amdgcn_readfirstlane(br[4]);
-            seg_blk0 = blk0;
-            const int off = ((int)blk - blk0) * BLOCK + tid;
+            region = __builtin_amdgcn_readfirstlane(br[0]);
+            const int off0 = ((int)blk - __builtin_amdgcn_readfirstlane(br[4])) * BLOCK;
             const int fc = __builtin_amdgcn_readfirstlane(br[3]);
             seg_f = fc & 0x3fffff; seg_ch = (int)((unsigned)fc >> 22);
             q_base = (int64_t)__builtin_amdgcn_readfirstlane(br[1]);      // segments exist for n_total < 2^31
-            q_size = __builtin_amdgcn_readfirstlane(br[2]); region = sg;
-            if (tid < BLOCK && off < q_size) seg_g = q_base + off;
+            q_size = __builtin_amdgcn_readfirstlane(br[2]);
+            seg_g0 = q_base + off0; seg_rows = q_size - off0;
         } else {
             region = (int)((blk * BLOCK) / a.q_chunk);
             q_base = (int64_t)region * a.q_chunk;
@@ -174,11 +184,11 @@ __global__ __launch_bounds__(BLOCK < 64 ? 64 : BLOCK, (!LIST && DICT == 1 && BLO
     int64_t chunk = LIST ? (int64_t)a.work_lo + (int64_t)blockIdx.x * BLOCK : blk * BLOCK;
     if (LIST && chunk >= work_n) return;
     do {                                              // direct mode: exactly one trip, and the compiler must see that
-    int64_t g = -1;
-    if (LIST) {
+    G g = -1;
+    if constexpr (LIST) {
         if (tid < BLOCK && chunk + tid < work_n) g = a.tier_list[work_off + chunk + tid];
-    } else if (seg_f >= 0) {
-        g = seg_g;
+    } else if constexpr (SEG) {
+        if (tid < BLOCK && tid < seg_rows) g = (G)seg_g0 + tid;
     } else {
         g = chunk + tid;
         if (tid >= BLOCK || g >= a.n_total) g = -1;
@@ -187,20 +197,46 @@ __global__ __launch_bounds__(BLOCK < 64 ? 64 : BLOCK, (!LIST && DICT == 1 && BLO
     const bool live = g >= 0;
     int f = 0, ch = 0;
     T px = 0, py = 0, pz = 0;
-    [[maybe_unused]] T pint = 0;
+    // the pass over all rows leaves range + intensity for the noise-floor pass: a beam it finishes itself (no flake met: label 0) carries its
+    // original intensity in the record, if that is an integer in [0, 255] as in every STF sweep -- that record, made where the row is read
+    [[maybe_unused]] uint32_t rec_clear = 0u;
+    auto clear_record = [](T pint) {
+        const int iv = (int)pint;
+        return ((T)iv == pint && iv >= 0 && iv <= 255) ? SG_REC_HAS_I | (uint32_t)iv : 0u;
+    };
     bool simulated = false;
-    if (live) {
-        f = (!LIST && seg_f >= 0) ? seg_f : sg_frame_of(a, g);
-        const T *row = sg_row<T>(a, f, g);
-        px = row[0]; py = row[1]; pz = row[2];
-        if constexpr (!LIST && DICT) pint = row[3];   // the pass over all rows leaves range + intensity for the noise-floor pass
-        if (!LIST && seg_f >= 0) {                    // the device sort only builds segments of integer channels
-            ch = seg_ch;
-            simulated = ch < n_las;
-        } else {
+    SgTable tab{};
+    bool act = false;                                 // this lane simulates a beam
+    if constexpr (SEG) {
+        // frame, channel, row base and table descriptor: scalar loads through block-uniform indices, no lane waits for a vector round trip
+        f = seg_f; ch = seg_ch;                       // (the device sort only builds segments of integer channels)
+        const bool has_laser = seg_ch < n_las;
+        const T *row0 = (const T *)(a.frame_unsorted[seg_f] ? a.srows : a.rows) + seg_g0 * 5;
+        if (live) {
+            const T *row = row0 + (unsigned)tid * 5u;
+            px = row[0]; py = row[1]; pz = row[2];
+            rec_clear = clear_record(row[3]);
+        }
+        simulated = live && has_laser;
+        if (has_laser) {
+            tab = a.frame_tables[(int64_t)seg_f * n_las + seg_ch];   // resolved per (frame, channel) by the segment builder
+            if (tab.entries != nullptr) act = live;
+            else if (live) atomicCAS(&a.status[0], 0, 1 /* SNOWGPU_E_INVALID */);
+        }
+    } else {
+        if (live) {
+            f = sg_frame_of(a, g);
+            const T *row = sg_row<T>(a, f, g);
+            px = row[0]; py = row[1]; pz = row[2];
+            if constexpr (!LIST && DICT) rec_clear = clear_record(row[3]);
             const T pch = row[4];
             ch = (int)pch;
             simulated = ((T)ch == pch) && ch >= 0 && ch < n_las;            // simulation.py:80, :482 (Q5)
+        }
+        if (simulated) {
+            tab = a.frame_tables[(int64_t)f * n_las + ch];   // resolved per (frame, channel) by k_resolve_tables
+            if (tab.entries == nullptr) atomicCAS(&a.status[0], 0, 1 /* SNOWGPU_E_INVALID */);
+            else act = true;
         }
     }
     SgBeamOut o;
@@ -209,31 +245,24 @@ __global__ __launch_bounds__(BLOCK < 64 ? 64 : BLOCK, (!LIST && DICT == 1 && BLO
     bool pending = false;                             // another kernel writes this row's record
     int L = 0;                                        // hand-over passes: flakes in the list
     T d_t = 0;
-    double theta_c = 0.0;
-    SgTable tab{};
-    bool act = false;                                 // this lane simulates a beam
+    [[maybe_unused]] T theta_t = 0;                   // azimuth in the row dtype (its widening is the reference's theta_c)
     [[maybe_unused]] int tier_k = -1;                 // the pass over all rows: the later tier this beam goes to
-    if (simulated) {
-        tab = a.frame_tables[(int64_t)f * n_las + ch];   // resolved per (frame, channel) by k_resolve_tables
-        if (tab.entries == nullptr) atomicCAS(&a.status[0], 0, 1 /* SNOWGPU_E_INVALID */);
-        else act = true;
-    }
     if constexpr (DICT) {
         // The pass over all rows scans as a wave (every lane takes part, whether it has a beam or not): its beams' lists
         // differ 20-fold in length.  The later tiers hold beams with long lists of similar length; one beam per lane is a
         // little faster there (k_tier_scan_direct; measured 0.37 vs 0.41 ms for tier 8).
         // overflow slot of this block's column 0 (sorted positions follow the columns)
         double *ov_blk = nullptr;
-        if (a.ov_cap > 0) ov_blk = a.ov + (size_t)(seg_f >= 0 ? q_base + (blk - seg_blk0) * BLOCK : chunk) * SG_OV_STRIDE;
+        if (a.ov_cap > 0) ov_blk = a.ov + (size_t)(SEG ? seg_g0 : chunk) * SG_OV_STRIDE;
         // DICT == 1: distance tests too close to call are not decided here (sg_beam.h: sg_near_ray); DICT == 2 (exact-math mode): every
         // test by the reference's expression, in place
-        L = sg_wave_scan<T, LMAX, BLOCK, DICT == 1, COMPACT>(act, px, py, pz, tab, a.beam_div_deg, s_a1, s_a2, s_rho, s_cnt, s_key, s_st, tid, o, d_t, theta_c,
-                                                             a.exact_math != 0, ov_blk, ov_blk ? a.ov_cap : 0, s_mark);
+        L = sg_wave_scan_t<T, LMAX, BLOCK, DICT == 1, COMPACT, SEG>(act, px, py, pz, tab, a.beam_div_deg, s_a1, s_a2, s_rho, s_cnt, s_key, s_st, tid, o, d_t,
+                                                                    theta_t, a.exact_math != 0, ov_blk, ov_blk ? a.ov_cap : 0);
         if (ov_blk && act && o.overflow && o.n_hits <= a.ov_cap) {   // header and the flakes the LDS list holds: the slot is complete
             double *sp = ov_blk + (size_t)tid * SG_OV_STRIDE;
-            sp[0] = (double)d_t; sp[1] = theta_c;
+            sp[0] = (double)d_t; sp[1] = (double)theta_t;
             double th_r, th_l;
-            sg_beam_limits(theta_c, a.beam_div_deg, th_r, th_l);
+            sg_beam_limits((double)theta_t, a.beam_div_deg, th_r, th_l);
 #pragma unroll
             for (int j = 0; j < LMAX; ++j) {
                 double x1, x2;
@@ -247,14 +276,14 @@ __global__ __launch_bounds__(BLOCK < 64 ? 64 : BLOCK, (!LIST && DICT == 1 && BLO
             o.has_power = !o.overflow && L > 0;       // k_power builds the dict (phase 2) and everything after it
             if (!o.overflow && L == 0 && a.dbg_count) {   // debug tap: the dict of a clear beam is its hard target alone
                 a.dbg_count[g] = 1;
-                a.dbg_rj[g * a.dbg_cap] = (double)d_t;
-                a.dbg_ratio[g * a.dbg_cap] = sg_clear_beam_ratio(theta_c, a.beam_div_deg);
+                a.dbg_rj[(int64_t)g * a.dbg_cap] = (double)d_t;
+                a.dbg_ratio[(int64_t)g * a.dbg_cap] = sg_clear_beam_ratio((double)theta_t, a.beam_div_deg);
             }
         }
     } else if (act) {
         int32_t *dc = a.dbg_count ? a.dbg_count + g : nullptr;
-        double *drj = a.dbg_count ? a.dbg_rj + g * a.dbg_cap : nullptr;
-        double *dra = a.dbg_count ? a.dbg_ratio + g * a.dbg_cap : nullptr;
+        double *drj = a.dbg_count ? a.dbg_rj + (int64_t)g * a.dbg_cap : nullptr;
+        double *dra = a.dbg_count ? a.dbg_ratio + (int64_t)g * a.dbg_cap : nullptr;
         sg_beam<T, LMAX, BLOCK>(px, py, pz, ch, tab, a.las, a.beam_div_deg, s_a1, s_a2, s_rho, s_ratio, tid, o, a.dbg_cap, dc, drj,
                                 dra, a.exact_math != 0);
     }
@@ -300,11 +329,11 @@ __global__ __launch_bounds__(BLOCK < 64 ? 64 : BLOCK, (!LIST && DICT == 1 && BLO
         constexpr int P = SG_QPLANES(LMAX);
         auto hand_over = [&](double *q, int64_t slot) {
             q[sg_qaddr<P>(slot, 0)] = (double)d_t;
-            q[sg_qaddr<P>(slot, 1)] = theta_c;
+            q[sg_qaddr<P>(slot, 1)] = (double)theta_t;
             // the interval angles from the words: the beam's limits, or the records' tangent angles (read here, by the few beams that
             // listed a flake -- the records' lines are what the scan just read)
             double th_r, th_l;
-            sg_beam_limits(theta_c, a.beam_div_deg, th_r, th_l);
+            sg_beam_limits((double)theta_t, a.beam_div_deg, th_r, th_l);
             if constexpr (LMAX <= 4) {
                 double x1[LMAX], x2[LMAX];
                 uint32_t hw[LMAX];
@@ -365,12 +394,8 @@ __global__ __launch_bounds__(BLOCK < 64 ? 64 : BLOCK, (!LIST && DICT == 1 && BLO
         sg_add_diff2(a.diff2, live, f, (long long)o.diff2);
     }
     if constexpr (DICT) {
-        // a beam this pass finishes itself (no flake met: label 0) carries its original intensity in the record, if that is an
-        // integer in [0, 255] as in every STF sweep: together with the range above the noise-floor pass then never reads the row
-        if (live && !pending && rec == 0u && act && a.rng) {
-            const int iv = (int)pint;
-            if ((T)iv == pint && iv >= 0 && iv <= 255) rec = SG_REC_HAS_I | (uint32_t)iv;
-        }
+        // a beam this pass finishes itself: together with the range above the noise-floor pass then never reads the row
+        if (live && !pending && rec == 0u && act && a.rng) rec = rec_clear;
     }
     if (live && !pending) a.rec[g] = rec;
     } while (LIST && (chunk += stride) < work_n);
@@ -1016,15 +1041,15 @@ __global__ __launch_bounds__(64) void k_beams_huge(SgBeamArgs a)
 // ------------------------------------------------------------------------------------------------
 // launch wrappers (C linkage, called from snowgpu_batch.cpp and snowgpu_host.cpp)
 
-template <typename T, int LMAX, int BLOCK, bool LIST, int DICT>
+template <typename T, int LMAX, int BLOCK, bool LIST, int DICT, bool SEG = false>
 static int launch_beams_t(const SgBeamArgs *a, hipStream_t st)
 {
-    // (the pass over all rows: ranges + one word per listed flake; the in-place passes: four double columns -- see k_beams)
+    // (the pass over all rows: ranges + one word per listed flake, counts, bin starts, scan order; the in-place passes: four double columns -- see k_beams)
     const size_t lds = DICT ? (sizeof(double) + sizeof(uint32_t)) * (size_t)BLOCK * (size_t)LMAX
-                                  + sizeof(int) * (4 * (size_t)(BLOCK < 64 ? 64 : BLOCK) + (size_t)LMAX * BLOCK)
+                                  + sizeof(int) * (3 * (size_t)(BLOCK < 64 ? 64 : BLOCK) + (size_t)LMAX * BLOCK)
                             : sizeof(double) * (size_t)BLOCK * 4 * ((size_t)LMAX + 1);
     static bool attr_set[64] = {};
-    if (int e = sg_set_lds(k_beams<T, LMAX, BLOCK, LIST, DICT>, lds, attr_set)) return e;
+    if (int e = sg_set_lds(k_beams<T, LMAX, BLOCK, LIST, DICT, SEG>, lds, attr_set)) return e;
     constexpr int THREADS = BLOCK < 64 ? 64 : BLOCK;
     unsigned blocks;
     if (LIST) {                                          // list mode: at most what the chip can hold at once
@@ -1039,7 +1064,7 @@ static int launch_beams_t(const SgBeamArgs *a, hipStream_t st)
         blocks = (unsigned)a->grid_blocks;               // blocks [blk_lo, blk_hi) or chunk a->chunk of the segment order
     }
     if (blocks == 0) return 0;
-    hipLaunchKernelGGL((k_beams<T, LMAX, BLOCK, LIST, DICT>), dim3(blocks), dim3(THREADS), lds, st, *a);
+    hipLaunchKernelGGL((k_beams<T, LMAX, BLOCK, LIST, DICT, SEG>), dim3(blocks), dim3(THREADS), lds, st, *a);
     SG_CHECK_LAUNCH();
     return 0;
 }
@@ -1125,8 +1150,10 @@ extern "C" int sg_launch_beams(const SgBeamArgs *a, int dtype, int lmax, int dir
         using T = decltype(t);
         constexpr int LMAX = decltype(tier)::LMAX, BLOCK = decltype(tier)::BLOCK;
         if (!direct) return launch_beams_t<T, LMAX, BLOCK, true, 0>(a, st);
-        if (a->exact_math) return launch_beams_t<T, LMAX, BLOCK, false, 2>(a, st);   // (registers to spare for tangent, root and quotient in its loop)
-        return launch_beams_t<T, LMAX, BLOCK, false, 1>(a, st);
+        // the segment order (every batch without a caller's permutation) has a form of its own: block-uniform state in scalar registers
+        if (a->exact_math) return a->seg_blk ? launch_beams_t<T, LMAX, BLOCK, false, 2, true>(a, st)     // (registers to spare for tangent, root and quotient in its loop)
+                                             : launch_beams_t<T, LMAX, BLOCK, false, 2>(a, st);
+        return a->seg_blk ? launch_beams_t<T, LMAX, BLOCK, false, 1, true>(a, st) : launch_beams_t<T, LMAX, BLOCK, false, 1>(a, st);
     });
 }
 
