@@ -586,6 +586,30 @@ int snowgpu_fov_mask_device(snowgpu_ctx *ctx, int64_t n_total, const void *d_row
                             const double *p2, int img_h, int img_w, const uint8_t *d_keep_in /* or NULL */, uint8_t *d_out_keep, void *stream);
 
 /*
+ * DYNAMIC RADIUS OUTLIER REMOVAL (DROR; Charron et al., CRV 2018 -- the de-noising filter in front of the reference's chain,
+ * pointcloud_viewer.py:2756-2758, defaults :267-270) as a producer of a keep mask, frames as the batch entries take them.
+ *   c = beta (alpha_deg pi / 180), c2 = c c, s2min = sr_min sr_min            (host, double, in this order)
+ *   row i is USABLE iff it is present (d_keep_in NULL or its byte non-zero) and |x|, |y|, |z| <= 1e6 (false for NaN)
+ *   s2_i = max(s2min, c2 (x_i x_i + y_i y_i))                                  (no square root, no fused multiply-add)
+ *   usable row j != i of the same frame is a neighbour of usable row i iff (dx dx + dy dy) + dz dz <= s2_i  (closed ball, the QUERY row's
+ *   radius; a duplicate point is a neighbour)
+ *   d_out_keep[i] = usable_i && count_i >= k_min;  d_out_neighbours[i] (int32, or NULL) = min(count_i, k_min), 0 for an unusable row
+ * An unusable row is nobody's neighbour and is never looked at beyond that test (NaN padding does no harm).  The edge conventions are this
+ * library's: cadc_devkit's dror.py is not part of the reference checkout, parity with it is not pinned.
+ * Domain: 0 < c <= 0.25, sr_min >= 0 and finite, 0 <= k_min <= 65535; anything else is SNOWGPU_E_INVALID.  d_out_keep must NOT overlap
+ * d_keep_in, not even as the same array (SNOWGPU_E_INVALID): the query of one row reads other rows' keep-in bytes.  An empty batch returns
+ * OK and launches nothing.
+ * The search files every usable row in a cell of a per-frame grid (Cartesian where the radius is sr_min, log-polar beyond; sg_dror.h) and
+ * counts exactly inside a conservative window of cells.  Scratch in the context, grown on first use: 4 bytes per cell -- at most
+ * min(max(4 max_frame_rows, 1024), 81920) + 1 cells per frame --, 4 bytes per row and one sorted copy of x, y, z in the row dtype.
+ * One memset and four kernels on `stream`; nothing is read on the host, nothing allocated after the first call of a size: capturable.
+ */
+int snowgpu_dror_mask_device(snowgpu_ctx *ctx, int n_frames, int64_t n_total, int64_t max_frame_rows, const int64_t *d_frame_offsets,
+                             const void *d_rows, int dtype, double alpha_deg, double beta, double sr_min, int64_t k_min,
+                             const uint8_t *d_keep_in /* or NULL: all present */, uint8_t *d_out_keep,
+                             int32_t *d_out_neighbours /* or NULL */, void *stream);
+
+/*
  * PER-FRAME WEATHER in one aligned call.  snowgpu_augment_wet_batch_device_aligned_masked applies one weather to every frame, its wet
  * settings host scalars that a captured graph bakes in.  Here every frame brings a record of 8 doubles in DEVICE memory,
  *     d_weather[f] = [snow, wet, water_height, pavement_depth, wet_noise_floor, power_factor, delta, 0]

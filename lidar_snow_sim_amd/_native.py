@@ -29,7 +29,7 @@ EXPORTS = [
     "snowgpu_estimate_planes_device", "snowgpu_prepass_stats", "snowgpu_set_wet_estimation", "snowgpu_wet_last_fit", "snowgpu_debug_ransac_polyfit", "snowgpu_set_result_transfer", "snowgpu_debug_transfer_times", "snowgpu_status_error", "snowgpu_set_threshold_callback", "snowgpu_augment_batch_compact", "snowgpu_set_serial", "snowgpu_lane_stream", "snowgpu_device_numa_node",
     "snowgpu_augment_batch_device_aligned", "snowgpu_wet_ground_batch_device_aligned", "snowgpu_augment_wet_batch_device_aligned",
     "snowgpu_augment_batch_device_aligned_masked", "snowgpu_augment_wet_batch_device_aligned_masked", "snowgpu_fov_mask_device",
-    "snowgpu_augment_weather_batch_device_aligned", "snowgpu_draw_weather_device",
+    "snowgpu_augment_weather_batch_device_aligned", "snowgpu_draw_weather_device", "snowgpu_dror_mask_device",
 ]
 
 WET_ESTIMATION = {"linear": 0, "poly": 1}
@@ -138,6 +138,8 @@ def lib():
                                                       ctypes.c_uint64, vp, vp, vp, vp]
             L.snowgpu_fov_mask_device.restype = ctypes.c_int
             L.snowgpu_fov_mask_device.argtypes = [vp, i64, vp, ctypes.c_int, vp, vp, vp, ctypes.c_int, ctypes.c_int, vp, vp, vp]
+            L.snowgpu_dror_mask_device.restype = ctypes.c_int
+            L.snowgpu_dror_mask_device.argtypes = [vp, ctypes.c_int, i64, i64, vp, vp, ctypes.c_int, dbl, dbl, dbl, i64, vp, vp, vp, vp]
             L.snowgpu_set_fov_precrop.restype = ctypes.c_int
             L.snowgpu_set_fov_precrop.argtypes = [vp, ctypes.c_int]
             L.snowgpu_last_status.restype = ctypes.c_int
@@ -497,6 +499,19 @@ class Context:
         self._check(self._L.snowgpu_fov_mask_device(self._h, int(n_total), vp(d_rows or None), int(dtype_code), _p(v2c), _p(r0), _p(p2),
                                                     int(img_shape[0]), int(img_shape[1]), vp(d_keep_in or None), vp(d_out_keep or None),
                                                     vp(stream or None)))
+
+    def dror_mask_device(self, n_frames, n_total, max_frame_rows, d_frame_off, d_rows, dtype_code, alpha, beta, sr_min, k_min, d_keep_in,
+                         d_out_keep, d_out_neighbours=0, stream=0):
+        """Dynamic radius outlier removal as a keep mask (include/snowgpu.h: snowgpu_dror_mask_device); asynchronous on `stream`.  A
+        parameter outside the domain, or d_out_keep overlapping d_keep_in, raises ValueError."""
+        vp = ctypes.c_void_p
+        k = int(k_min)
+        rc = self._L.snowgpu_dror_mask_device(self._h, int(n_frames), int(n_total), int(max_frame_rows), vp(d_frame_off or None), vp(d_rows or None),
+                                              int(dtype_code), float(alpha), float(beta), float(sr_min), max(-1, min(k, 1 << 62)), vp(d_keep_in or None),
+                                              vp(d_out_keep or None), vp(d_out_neighbours or None), vp(stream or None))
+        if rc == E_INVALID:
+            raise ValueError(self._L.snowgpu_last_error(self._h).decode())
+        self._check(rc)
 
     def set_fov(self, calib=None, img_shape=(1024, 1920), pre_crop=False):
         """Camera-FOV crop inside the compaction of every later batch (None switches it off).  `calib` carries V2C (3 x 4),

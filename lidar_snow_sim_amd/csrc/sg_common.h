@@ -189,7 +189,7 @@ struct SgFov {
 
 // Launch wrappers (hipStream_t passed as void*), each implemented in the file that defines its kernels: snowgpu_sort.hip (expand_rows, sort,
 // gather_rows, segments*, resolve_tables), snowgpu_kernels.hip (beams, power*, tier_*, huge, sg_beams_block), snowgpu_rows.hip (rows),
-// snowgpu_compact.hip (compact, crop_*), snowgpu_mask.hip (mask_front, finish_aligned_masked, fov_mask).  Every one of these files includes this header, so a definition cannot drift from its declaration.
+// snowgpu_compact.hip (compact, crop_*), snowgpu_mask.hip (mask_front, finish_aligned_masked, fov_mask), snowgpu_dror.hip (dror).  Every one of these files includes this header, so a definition cannot drift from its declaration.
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -263,6 +263,12 @@ int sg_launch_finish_aligned_masked(const void *crows, const void *srows, const 
                                     unsigned long long *tiles_done /* n_frames words, zero */, void *stream);
 // out_keep[i] = (keep_in ? keep_in[i] : 1) && the camera-FOV test of row i (out_keep may be keep_in)
 int sg_launch_fov_mask(const void *rows, int dtype, int64_t n, const uint8_t *keep_in, uint8_t *out_keep, const SgFov *fov, void *stream);
+// Dynamic radius outlier removal (sg_dror.h): out_keep[i] = row i is usable and has at least g->k_min neighbours, out_nb[i] (or null) = its
+// neighbours, counted up to k_min.  The memset of the cell entries and four kernels.  Scratch: entry n_frames (g->cells + 1) words,
+// cell_of n words, sorted 3 n values of the row dtype.  out_keep must not be keep_in: other rows' bytes are read while it is written.
+struct SgDrorGrid;
+int sg_launch_dror(const void *rows, int dtype, int64_t n, const int64_t *frame_off, int n_frames, const uint8_t *keep_in, const struct SgDrorGrid *g,
+                   uint32_t *entry, uint32_t *cell_of, void *sorted, uint8_t *out_keep, int32_t *out_nb, void *stream);
 #ifdef __cplusplus
 }
 #endif

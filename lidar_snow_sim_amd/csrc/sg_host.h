@@ -80,6 +80,9 @@ struct __attribute__((visibility("default"))) snowgpu_ctx {
     DevBuf<uint8_t> rows_crop;
     DevBuf<int32_t> crop_src, crop_out_src;
     DevBuf<int64_t> crop_counts, crop_off, crop_stats;
+    // dynamic radius outlier removal (snowgpu_dror_mask_device): cell entries, the cell of every row, x y z sorted by cell
+    DevBuf<uint32_t> dror_entry, dror_cell;
+    DevBuf<uint8_t> dror_sorted;
     // scratch shared by every batch
     DevBuf<int32_t> tile_hist, tile_base, perm, ctile_cnt, ctile_base, table_ids, out_src;
     DevBuf<uint8_t> srows;            // channel-sorted copy of the frames whose rows did not come channel-sorted (firing order)

@@ -1,10 +1,11 @@
 // snowgpu_device.cpp -- the entries of the C ABI (include/snowgpu.h) that take DEVICE pointers and enqueue on the caller's stream: every
-// *_batch_device* entry, the plane estimate, the FOV mask and the weather draw.  Each batch entry fills an SgDeviceArgs, has it checked
+// *_batch_device* entry, the plane estimate, the FOV mask, the outlier filter and the weather draw.  Each batch entry fills an SgDeviceArgs, has it checked
 // (sg_device_args.h: every refusal, in one order), sets the device and runs batch_from_args() and the stages it needs.  The launch
 // sequence of a batch is snowgpu_batch.cpp; no host copy, no synchronisation, no allocation after the first call of a given size.
 #include "sg_host.h"
 #include "sg_launch.h"      // sg_tiles
 #include "sg_weather.h"     // SgWeatherDraw and the limits of the draw
+#include "sg_dror.h"        // the grid of the outlier filter and its domain
 
 static_assert(SG_ARGS_INVALID == SNOWGPU_E_INVALID && SG_PLANE_REFERENCE == 0, "sg_device_args.h restates these two");
 
@@ -359,6 +360,36 @@ extern "C" int snowgpu_fov_mask_device(snowgpu_ctx *ctx, int64_t n_total, const 
     const SgFov f = make_fov(v2c, r0, p2, img_h, img_w);
     int e = sg_launch_fov_mask(d_rows, dtype, n_total, d_keep_in, d_out_keep, &f, stream ? (hipStream_t)stream : ctx->stream);
     if (e) return fail(ctx, SNOWGPU_E_HIP, std::string("fov mask launch: ") + hipGetErrorString((hipError_t)e));
+    return SNOWGPU_OK;
+}
+
+// Dynamic radius outlier removal as a producer of a keep mask (snowgpu_dror.hip; definition and grid: sg_dror.h).  See include/snowgpu.h.
+extern "C" int snowgpu_dror_mask_device(snowgpu_ctx *ctx, int n_frames, int64_t n_total, int64_t max_frame_rows, const int64_t *d_frame_offsets,
+                                        const void *d_rows, int dtype, double alpha_deg, double beta, double sr_min, int64_t k_min,
+                                        const uint8_t *d_keep_in, uint8_t *d_out_keep, int32_t *d_out_neighbours, void *stream)
+{
+    static const char *who = "snowgpu_dror_mask_device";
+    if (!ctx) return SNOWGPU_E_INVALID;
+    if (n_frames <= 0 || n_total < 0 || !d_frame_offsets || (n_total > 0 && (!d_rows || !d_out_keep)) || (dtype != 0 && dtype != 1))
+        return fail(ctx, SNOWGPU_E_INVALID, std::string(who) + ": null pointer or bad dtype");
+    if (n_total >= ((int64_t)1 << 31)) return fail(ctx, SNOWGPU_E_INVALID, "batch too large: split it below 2^31 rows");
+    SgDrorGrid g{};
+    if (sg_dror_make_grid(alpha_deg, beta, sr_min, k_min, sg_dror_cell_budget(sg_max_frame(max_frame_rows, n_total)), &g))
+        return fail(ctx, SNOWGPU_E_INVALID, std::string(who) + ": needs 0 < beta alpha pi / 180 <= 0.25, a finite sr_min >= 0 and 0 <= k_min <= 65535");
+    if (d_keep_in && (const uint8_t *)d_out_keep < d_keep_in + (size_t)n_total && d_keep_in < d_out_keep + (size_t)n_total)
+        return fail(ctx, SNOWGPU_E_INVALID, std::string(who) + ": d_out_keep overlaps d_keep_in (or is it); the query of one row reads the keep-in bytes "
+                                            "of other rows while out bytes are written: pass a buffer apart from it");
+    if (n_total == 0) return SNOWGPU_OK;
+    const size_t entries = (size_t)n_frames * (size_t)(g.cells + 1);
+    if (entries >= ((size_t)1 << 31)) return fail(ctx, SNOWGPU_E_INVALID, std::string(who) + ": too many frames for the cell lists; split the batch");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t n = (size_t)n_total;
+    ENSURE(ctx, ctx->dror_entry, entries);
+    ENSURE(ctx, ctx->dror_cell, n);
+    ENSURE(ctx, ctx->dror_sorted, n * 3 * (dtype == 0 ? 4 : 8));
+    int e = sg_launch_dror(d_rows, dtype, n_total, d_frame_offsets, n_frames, d_keep_in, &g, ctx->dror_entry.p, ctx->dror_cell.p, ctx->dror_sorted.p,
+                           d_out_keep, d_out_neighbours, stream ? (hipStream_t)stream : ctx->stream);
+    if (e) return fail(ctx, SNOWGPU_E_HIP, std::string("dror launch: ") + hipGetErrorString((hipError_t)e));
     return SNOWGPU_OK;
 }
 

@@ -17,6 +17,8 @@ The reference's training-time caller (the OpenPCDet DENSE dataset: `root_path`, 
     -- cropped away, padding of an F x Nmax batch, removed by a stage in front -- and the result is, byte for byte, that of the call on the
     frames compacted by the mask, at the present rows' own indices (snowgpu_augment_batch_device_aligned_masked).  `calib=c, pre_crop=True`
     builds that mask on the device from the camera's view (`fov_keep`): precompute.py:96-104 without a boolean index or a host read.
+  * `dror_keep(frames, ...)` is dynamic radius outlier removal (the de-noising filter in front of the viewer's chain) as one more producer
+    and consumer of such masks (snowgpu_dror_mask_device).
   * `augment_wet_batch_aligned(frames, ...)` is the snowfall + wet-ground chain with that aligned result (AlignedWetResult: per-frame
     flags beside it; snowgpu_augment_wet_batch_device_aligned), `wet_ground_batch_aligned(frames, keep)` the wet-ground stage alone on rows
     and a keep mask from any earlier stage (snowgpu_wet_ground_batch_device_aligned).
@@ -515,6 +517,51 @@ def fov_keep(frames, calib, img_shape=(1024, 1920), keep=None, *, device=None, s
         keep = _keep_mask(torch, keep, rows, offsets)
     with torch.cuda.device(rows.device), _on_run_stream(torch, eng, rows.device) as (_, run):
         return _fov_mask(torch, eng, rows[:int(offsets[-1])], calib, img_shape, keep, run)
+
+
+def dror_keep(frames, alpha=0.45, beta=3, k_min=3, sr_min=0.04, keep=None, *, out=None, return_neighbours=False, device=None, slot=0):
+    """Dynamic radius outlier removal (DROR, Charron et al. 2018; pointcloud_viewer.py:2756-2758 with the defaults of :267-270) for torch
+    CUDA tensors, on the device: a torch.bool mask with one element per row of the batch (frames as augment_batch takes them), True where
+    the row is usable -- present under `keep`, every coordinate finite and within 1e6 m -- and has at least k_min other usable rows of its
+    frame within max(sr_min, beta * radians(alpha) * r_xy) of it (the definition: include/snowgpu.h, snowgpu_dror_mask_device).
+
+    keep      an input keep mask as augment_batch(layout='aligned') takes it: an absent row is False, nobody's neighbour, never looked at.
+    out       a torch.bool tensor with one element per row to write into (static addresses for a captured graph); not the `keep` tensor.
+    return_neighbours   also return an int32 tensor: every row's neighbours, counted up to k_min.
+
+    The mask goes straight into augment_batch(..., layout='aligned', keep=mask), augment_wet_batch_aligned(..., keep=mask) or
+    fov_keep(..., keep=mask); dror_keep(res.rows, keep=res.keep) filters an augmented batch.  Asynchronous on torch's current stream."""
+    if not is_device_input(frames):
+        raise ValueError("dror_keep: torch CUDA tensors (host arrays: lidar_snow_sim_amd.dror.dynamic_radius_outlier_filter)")
+    import math
+    import torch
+    c = float(beta) * (float(alpha) * (math.pi / 180.0))
+    if not (0.0 < c <= 0.25):
+        raise ValueError("dror_keep: beta * radians(alpha) must lie in (0, 0.25]")
+    if not (float(sr_min) >= 0.0 and math.isfinite(float(sr_min))):
+        raise ValueError("dror_keep: sr_min must be finite and >= 0")
+    if int(k_min) != k_min or not (0 <= int(k_min) <= 65535):
+        raise ValueError("dror_keep: k_min must be an integer in 0 .. 65535")
+    rows, offsets, _, eng = _resolve_input(torch, frames, False, device, slot)
+    dev = rows.device
+    nf, n = len(offsets) - 1, int(offsets[-1])
+    if keep is not None:
+        keep = _keep_mask(torch, keep, rows, offsets)
+    if out is None:
+        out = torch.empty(n, dtype=torch.bool, device=dev)
+    elif not (torch.is_tensor(out) and out.dtype == torch.bool and out.dim() == 1 and out.shape[0] == n and out.is_contiguous() and out.device == dev):
+        raise ValueError("dror_keep: out must be a contiguous torch.bool tensor with one element per row, on the device of the rows")
+    if keep is not None and n and out.data_ptr() < keep.data_ptr() + n and keep.data_ptr() < out.data_ptr() + n:
+        raise ValueError("dror_keep: out must not be (or overlap) the keep tensor; the query of one row reads other rows' keep elements")
+    nb = torch.zeros(n, dtype=torch.int32, device=dev) if return_neighbours else None
+    if nf and n:
+        up = _uploads(eng)
+        with torch.cuda.device(dev), _on_run_stream(torch, eng, dev) as (_, run):
+            d_off = up.get(torch, dev, offsets, run)
+            eng.ctx.dror_mask_device(nf, n, int(np.diff(offsets).max()), d_off.data_ptr(), rows.data_ptr(), 0 if rows.dtype == torch.float32 else 1,
+                                     float(alpha), float(beta), float(sr_min), int(k_min), 0 if keep is None else keep.data_ptr(), out.data_ptr(),
+                                     0 if nb is None else nb.data_ptr(), run.cuda_stream)
+    return (out, nb) if return_neighbours else out
 
 
 def augment_batch(frames, particle_file_prefix, beam_divergence, shuffle=True, noise_floor=0.7, root_path=None, *, planes=None,
