@@ -610,6 +610,46 @@ int snowgpu_dror_mask_device(snowgpu_ctx *ctx, int n_frames, int64_t n_total, in
                              int32_t *d_out_neighbours /* or NULL */, void *stream);
 
 /*
+ * POINT-TO-VOXEL GROUPING of an aligned batch: the static-shape hand-off to a detector's first operation (SECOND, PV-RCNN, PointPillars).
+ * Frames, rows and the input keep mask as the aligned entries take them.  The reference has no voxelizer; the edge conventions are this
+ * library's, restated as a sequential NumPy walk by tests/voxel_reference.py.
+ *   Host constants, in double, j = x, y, z:  lo_j = range6[j], hi_j = range6[3 + j], size_j = size3[j],
+ *   n_j = llround((hi_j - lo_j) / size_j).
+ *   Row i of frame f is USABLE iff it is present (d_keep_in NULL or its byte non-zero), its x, y, z are finite and, for every j,
+ *   c_j = floor(((double)p_j - lo_j) / size_j) satisfies 0 <= c_j < n_j.  A true double division and a floor: no reciprocal, no fused
+ *   multiply-add.  A coordinate on hi_j is out (where (hi_j - lo_j) / size_j is exact; the formula decides); one on lo_j or on an inner
+ *   face belongs to the upper cell.
+ *   The usable rows of a frame are walked in input order, T = max_points, V = max_voxels.  The first row of a cell not seen before opens
+ *   voxel v = the voxels opened so far in this frame; if V are open already the cell is DROPPED, with every later row of it.  A row of an
+ *   open voxel is STORED in the voxel's next point slot while the voxel holds fewer than T rows; a later row still belongs to the voxel
+ *   and is not stored.
+ * Outputs, packed in frame order: m_f = min(cells of frame f, V), voxel_offsets[0] = 0, voxel_offsets[f + 1] = voxel_offsets[f] + m_f.
+ *   d_out_voxels         (F V, T, C) in the rows' dtype: voxel voxel_offsets[f] + v, slot t holds columns 0 .. C - 1 of its t-th stored
+ *                        row, bit for bit; unfilled slots and every voxel at or beyond voxel_offsets[F] are zero
+ *   d_out_coords         (F V, 4) int32: (f, c_z, c_y, c_x); -1 at or beyond voxel_offsets[F]
+ *   d_out_num_points     (F V) int32: min(rows of the voxel, T); 0 in the tail
+ *   d_out_voxel_offsets  (F + 1) int32, device memory
+ *   d_out_voxel_of       (N_total) int32 or NULL: the packed voxel of the row's cell, stored or not; -1 for absent, unusable and dropped rows
+ * Every element of every output is written by every call: a buffer that is reused, or a graph that is replayed, needs no clearing.
+ * Domain: C = n_features in 3 .. 5, T >= 1, V >= 1, every size_j > 0 and finite, every n_j >= 1 (the range finite),
+ * n_x n_y n_z <= 2^31 - 2, F V <= 2^31 - 1, no frame longer than 2^30 rows, dtype float32 or float64; anything else is SNOWGPU_E_INVALID.
+ * d_out_voxel_of must not overlap d_keep_in (SNOWGPU_E_INVALID).  An empty batch writes voxel_offsets = 0 and launches nothing else (its
+ * other outputs may be NULL).
+ * A dense counter per cell is not possible (1408 x 1600 x 40 cells for DENSE): every frame has an open-addressed table of
+ * cap = the power of two >= max(2 max_frame_rows, 64) slots of 8 bytes (cell << 32 | smallest row that hit it, by atomic min; sg_voxel.h),
+ * and a cell's voxel number is the rank of its first row among the frame's first rows.  Nothing in an output depends on where the hash put
+ * a cell or on the order in which atomics arrived: results are identical from run to run.
+ * Scratch in the context, grown on first use: 8 cap bytes per frame (16 .. 32 bytes per row of the longest frame), 9 bytes per row,
+ * 8 bytes per 1024 rows, 8 bytes per frame and 4 bytes per voxel (F V).  Two memsets and eleven kernels on `stream` (snowgpu_voxel.hip);
+ * nothing is read on the host, nothing allocated after the first call of a size: capturable.
+ */
+int snowgpu_voxelize_device(snowgpu_ctx *ctx, int n_frames, int64_t n_total, int64_t max_frame_rows, const int64_t *d_frame_offsets,
+                            const void *d_rows, int dtype, const double *range6 /* host: x0 y0 z0 x1 y1 z1 */,
+                            const double *size3 /* host: the voxel's x, y, z edges */, int max_points, int max_voxels, int n_features,
+                            const uint8_t *d_keep_in /* or NULL: all present */, void *d_out_voxels, int32_t *d_out_coords,
+                            int32_t *d_out_num_points, int32_t *d_out_voxel_offsets, int32_t *d_out_voxel_of /* or NULL */, void *stream);
+
+/*
  * PER-FRAME WEATHER in one aligned call.  snowgpu_augment_wet_batch_device_aligned_masked applies one weather to every frame, its wet
  * settings host scalars that a captured graph bakes in.  Here every frame brings a record of 8 doubles in DEVICE memory,
  *     d_weather[f] = [snow, wet, water_height, pavement_depth, wet_noise_floor, power_factor, delta, 0]

@@ -30,6 +30,7 @@ EXPORTS = [
     "snowgpu_augment_batch_device_aligned", "snowgpu_wet_ground_batch_device_aligned", "snowgpu_augment_wet_batch_device_aligned",
     "snowgpu_augment_batch_device_aligned_masked", "snowgpu_augment_wet_batch_device_aligned_masked", "snowgpu_fov_mask_device",
     "snowgpu_augment_weather_batch_device_aligned", "snowgpu_draw_weather_device", "snowgpu_dror_mask_device",
+    "snowgpu_voxelize_device",
 ]
 
 WET_ESTIMATION = {"linear": 0, "poly": 1}
@@ -140,6 +141,9 @@ def lib():
             L.snowgpu_fov_mask_device.argtypes = [vp, i64, vp, ctypes.c_int, vp, vp, vp, ctypes.c_int, ctypes.c_int, vp, vp, vp]
             L.snowgpu_dror_mask_device.restype = ctypes.c_int
             L.snowgpu_dror_mask_device.argtypes = [vp, ctypes.c_int, i64, i64, vp, vp, ctypes.c_int, dbl, dbl, dbl, i64, vp, vp, vp, vp]
+            L.snowgpu_voxelize_device.restype = ctypes.c_int
+            L.snowgpu_voxelize_device.argtypes = [vp, ctypes.c_int, i64, i64, vp, vp, ctypes.c_int, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                  vp, vp, vp, vp, vp, vp, vp]
             L.snowgpu_set_fov_precrop.restype = ctypes.c_int
             L.snowgpu_set_fov_precrop.argtypes = [vp, ctypes.c_int]
             L.snowgpu_last_status.restype = ctypes.c_int
@@ -509,6 +513,25 @@ class Context:
         rc = self._L.snowgpu_dror_mask_device(self._h, int(n_frames), int(n_total), int(max_frame_rows), vp(d_frame_off or None), vp(d_rows or None),
                                               int(dtype_code), float(alpha), float(beta), float(sr_min), max(-1, min(k, 1 << 62)), vp(d_keep_in or None),
                                               vp(d_out_keep or None), vp(d_out_neighbours or None), vp(stream or None))
+        if rc == E_INVALID:
+            raise ValueError(self._L.snowgpu_last_error(self._h).decode())
+        self._check(rc)
+
+    def voxelize_device(self, n_frames, n_total, max_frame_rows, d_frame_off, d_rows, dtype_code, point_cloud_range, voxel_size, max_points,
+                        max_voxels, n_features, d_keep_in, d_out_voxels, d_out_coords, d_out_num_points, d_out_voxel_offsets, d_out_voxel_of=0,
+                        stream=0):
+        """Point-to-voxel grouping of an aligned batch (include/snowgpu.h: snowgpu_voxelize_device); asynchronous on `stream`.  An argument
+        outside the domain, or d_out_voxel_of overlapping d_keep_in, raises ValueError with the entry's words."""
+        vp = ctypes.c_void_p
+        rng = np.ascontiguousarray(point_cloud_range, np.float64).reshape(-1)
+        size = np.ascontiguousarray(voxel_size, np.float64).reshape(-1)
+        if rng.shape != (6,) or size.shape != (3,):
+            raise ValueError("snowgpu_voxelize_device: point_cloud_range holds 6 numbers (x0, y0, z0, x1, y1, z1), voxel_size 3")
+        i32 = lambda v: max(-(2 ** 31), min(int(v), 2 ** 31 - 1))
+        rc = self._L.snowgpu_voxelize_device(self._h, int(n_frames), int(n_total), int(max_frame_rows), vp(d_frame_off or None), vp(d_rows or None),
+                                             int(dtype_code), _p(rng), _p(size), i32(max_points), i32(max_voxels), i32(n_features), vp(d_keep_in or None),
+                                             vp(d_out_voxels or None), vp(d_out_coords or None), vp(d_out_num_points or None),
+                                             vp(d_out_voxel_offsets or None), vp(d_out_voxel_of or None), vp(stream or None))
         if rc == E_INVALID:
             raise ValueError(self._L.snowgpu_last_error(self._h).decode())
         self._check(rc)

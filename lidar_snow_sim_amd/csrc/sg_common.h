@@ -189,7 +189,7 @@ struct SgFov {
 
 // Launch wrappers (hipStream_t passed as void*), each implemented in the file that defines its kernels: snowgpu_sort.hip (expand_rows, sort,
 // gather_rows, segments*, resolve_tables), snowgpu_kernels.hip (beams, power*, tier_*, huge, sg_beams_block), snowgpu_rows.hip (rows),
-// snowgpu_compact.hip (compact, crop_*), snowgpu_mask.hip (mask_front, finish_aligned_masked, fov_mask), snowgpu_dror.hip (dror).  Every one of these files includes this header, so a definition cannot drift from its declaration.
+// snowgpu_compact.hip (compact, crop_*), snowgpu_mask.hip (mask_front, finish_aligned_masked, fov_mask), snowgpu_dror.hip (dror), snowgpu_voxel.hip (voxelize).  Every one of these files includes this header, so a definition cannot drift from its declaration.
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -269,6 +269,14 @@ int sg_launch_fov_mask(const void *rows, int dtype, int64_t n, const uint8_t *ke
 struct SgDrorGrid;
 int sg_launch_dror(const void *rows, int dtype, int64_t n, const int64_t *frame_off, int n_frames, const uint8_t *keep_in, const struct SgDrorGrid *g,
                    uint32_t *entry, uint32_t *cell_of, void *sorted, uint8_t *out_keep, int32_t *out_nb, void *stream);
+// Point-to-voxel grouping (sg_voxel.h; the definition: include/snowgpu.h): two memsets and eleven kernels.  Scratch: table n_frames g->cap
+// words of 64 bits; slot_of and order n words, first n bytes; tile_cnt ceil(n / 1024) words and tile_base one more; fbase and m n_frames
+// words; span n_frames g->max_voxels words.  out_voxel_of may be null.
+struct SgVoxelGrid;
+int sg_launch_voxelize(const void *rows, int dtype, int64_t n, const int64_t *frame_off, int n_frames, const uint8_t *keep_in, const struct SgVoxelGrid *g,
+                       unsigned long long *table, uint32_t *slot_of, uint8_t *first, uint32_t *order, int32_t *tile_cnt, int32_t *tile_base, int32_t *fbase,
+                       int32_t *m, uint32_t *span, void *out_voxels, int32_t *out_coords, int32_t *out_num_points, int32_t *out_voxel_offsets,
+                       int32_t *out_voxel_of, void *stream);
 #ifdef __cplusplus
 }
 #endif

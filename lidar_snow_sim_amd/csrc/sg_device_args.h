@@ -2,6 +2,7 @@
 // theirs: pure argument checks on plain data.  Nothing of HIP is included, so the whole refusal matrix runs on a machine without a device
 // (tests/host_harness/device_refusals.cpp).
 #pragma once
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
 #include <string>
@@ -104,6 +105,68 @@ static inline int sg_check_wet_plane(const char *who, const double *wet_plane, i
 {
     if (wet_plane || plane_method == 0) return 0;
     return sg_refuse(who, ": a NULL wet plane needs the plane method 'reference'; 'lsq' and 'ransac' crop the rows and have no masked form: pass the plane", msg);
+}
+
+// ---- snowgpu_voxelize_device ------------------------------------------------------------------------------------------------------------
+struct SgVoxelArgs {
+    int n_frames;
+    int64_t n_total, max_frame_rows;
+    int dtype;
+    const int64_t *frame_off;
+    const void *rows;
+    const double *range6, *size3;     // (x0, y0, z0, x1, y1, z1) and the voxel's edges, host memory
+    int max_points, max_voxels, n_features;
+    const uint8_t *keep_in;
+    void *out_voxels;
+    int32_t *out_coords, *out_num_points, *out_voxel_offsets, *out_voxel_of;
+};
+
+constexpr int64_t SG_VOXEL_MAX_CELLS = ((int64_t)1 << 31) - 2;
+
+// n_j = llround((hi_j - lo_j) / size_j), in double.  0, 1: a size that is not positive and finite, 2: an axis without a cell (or a range
+// that is not finite), 3: more than SG_VOXEL_MAX_CELLS cells.
+static inline int sg_voxel_dims(const double *range6, const double *size3, int32_t n[3])
+{
+    for (int j = 0; j < 3; ++j)
+        if (!(size3[j] > 0.0) || !(size3[j] <= 1.7976931348623157e308)) return 1;
+    int64_t cells = 1;
+    bool too_many = false;
+    for (int j = 0; j < 3; ++j) {
+        const double q = (range6[3 + j] - range6[j]) / size3[j];
+        if (!(q >= 0.5) || !(q <= 1.7976931348623157e308)) return 2;      // (llround(q) >= 1 iff q >= 0.5; false for NaN)
+        if (q >= 2147483647.0) { too_many = true; continue; }
+        n[j] = (int32_t)std::llround(q);
+        cells = cells > SG_VOXEL_MAX_CELLS ? cells : cells * n[j];
+    }
+    return too_many || cells > SG_VOXEL_MAX_CELLS ? 3 : 0;
+}
+
+// 0 and the grid's n_x, n_y, n_z, or SG_ARGS_INVALID with *msg.  As above, the order is part of the ABI.
+static inline int sg_check_voxel_args(const SgVoxelArgs &a, int32_t n_cells[3], std::string *msg)
+{
+    static const char *who = "snowgpu_voxelize_device";
+    if (a.n_frames <= 0 || a.n_total < 0 || !a.frame_off || !a.range6 || !a.size3 || !a.out_voxel_offsets ||
+        (a.n_total > 0 && (!a.rows || !a.out_voxels || !a.out_coords || !a.out_num_points)) || (a.dtype != 0 && a.dtype != 1))
+        return sg_refuse(who, ": null pointer or bad dtype", msg);
+    if (a.n_total >= ((int64_t)1 << 31)) return sg_refuse("", "batch too large: split it below 2^31 rows", msg);
+    if (a.n_features < 3 || a.n_features > 5) return sg_refuse(who, ": n_features must be 3, 4 or 5: the columns of a row that a voxel stores", msg);
+    if (a.max_points < 1 || a.max_voxels < 1) return sg_refuse(who, ": max_points and max_voxels must be at least 1", msg);
+    switch (sg_voxel_dims(a.range6, a.size3, n_cells)) {
+    case 1: return sg_refuse(who, ": every voxel size must be positive and finite", msg);
+    case 2: return sg_refuse(who, ": the range must be finite and hold at least one voxel on every axis (llround((hi - lo) / size) >= 1)", msg);
+    case 3: return sg_refuse(who, ": the grid has more than 2^31 - 2 cells; a cell's index is kept in 31 bits", msg);
+    default: break;
+    }
+    if ((int64_t)a.n_frames * a.max_voxels > (((int64_t)1 << 31) - 1))
+        return sg_refuse(who, ": n_frames * max_voxels exceeds 2^31 - 1; split the batch", msg);
+    if (sg_max_frame(a.max_frame_rows, a.n_total) > ((int64_t)1 << 30))
+        return sg_refuse(who, ": a frame of more than 2^30 rows; split it", msg);
+    if (a.keep_in && a.out_voxel_of) {
+        const uintptr_t k = (uintptr_t)a.keep_in, o = (uintptr_t)a.out_voxel_of;
+        if (o < k + (size_t)a.n_total && k < o + (size_t)a.n_total * 4)
+            return sg_refuse(who, ": d_out_voxel_of overlaps d_keep_in; the keep-in bytes of other rows are read while it is written: pass a buffer apart from it", msg);
+    }
+    return 0;
 }
 
 // 0, or SG_ARGS_INVALID with *msg (built on this path only).  The order is part of the ABI: it decides which message a doubly wrong call gets.

@@ -83,6 +83,12 @@ struct __attribute__((visibility("default"))) snowgpu_ctx {
     // dynamic radius outlier removal (snowgpu_dror_mask_device): cell entries, the cell of every row, x y z sorted by cell
     DevBuf<uint32_t> dror_entry, dror_cell;
     DevBuf<uint8_t> dror_sorted;
+    // point-to-voxel grouping (snowgpu_voxelize_device): the frames' tables of open cells, per row its slot (then its voxel), whether it opens
+    // a cell and the row indices sorted by voxel, the opening rows per tile and per frame, the voxels' spans
+    DevBuf<unsigned long long> vox_table;
+    DevBuf<uint32_t> vox_slot, vox_order, vox_span;
+    DevBuf<uint8_t> vox_first;
+    DevBuf<int32_t> vox_tile_cnt, vox_tile_base, vox_fbase, vox_m;
     // scratch shared by every batch
     DevBuf<int32_t> tile_hist, tile_base, perm, ctile_cnt, ctile_base, table_ids, out_src;
     DevBuf<uint8_t> srows;            // channel-sorted copy of the frames whose rows did not come channel-sorted (firing order)

@@ -141,6 +141,8 @@ extern "C" void snowgpu_destroy(snowgpu_ctx *ctx)
     ctx->wet_counts.release(); ctx->wet_rows.release(); ctx->wet_plane.release();
     ctx->rows_crop.release(); ctx->crop_src.release(); ctx->crop_out_src.release(); ctx->crop_counts.release(); ctx->crop_off.release(); ctx->crop_stats.release();
     ctx->dror_entry.release(); ctx->dror_cell.release(); ctx->dror_sorted.release();
+    ctx->vox_table.release(); ctx->vox_slot.release(); ctx->vox_order.release(); ctx->vox_span.release(); ctx->vox_first.release();
+    ctx->vox_tile_cnt.release(); ctx->vox_tile_base.release(); ctx->vox_fbase.release(); ctx->vox_m.release();
     sg_prepass_release(&ctx->prepass);
     sg_plane_release(&ctx->plane_scr);
     ctx->plane_est.release(); ctx->wet_plane_est.release(); ctx->plane_info.release(); ctx->stats_hist.release(); ctx->stats_rec.release();

@@ -1,11 +1,12 @@
 // snowgpu_device.cpp -- the entries of the C ABI (include/snowgpu.h) that take DEVICE pointers and enqueue on the caller's stream: every
-// *_batch_device* entry, the plane estimate, the FOV mask, the outlier filter and the weather draw.  Each batch entry fills an SgDeviceArgs, has it checked
+// *_batch_device* entry, the plane estimate, the FOV mask, the outlier filter, the voxel stage and the weather draw.  Each batch entry fills an SgDeviceArgs, has it checked
 // (sg_device_args.h: every refusal, in one order), sets the device and runs batch_from_args() and the stages it needs.  The launch
 // sequence of a batch is snowgpu_batch.cpp; no host copy, no synchronisation, no allocation after the first call of a given size.
 #include "sg_host.h"
 #include "sg_launch.h"      // sg_tiles
 #include "sg_weather.h"     // SgWeatherDraw and the limits of the draw
 #include "sg_dror.h"        // the grid of the outlier filter and its domain
+#include "sg_voxel.h"       // the grid of the voxel stage and the capacity of its tables
 
 static_assert(SG_ARGS_INVALID == SNOWGPU_E_INVALID && SG_PLANE_REFERENCE == 0, "sg_device_args.h restates these two");
 
@@ -390,6 +391,47 @@ extern "C" int snowgpu_dror_mask_device(snowgpu_ctx *ctx, int n_frames, int64_t 
     int e = sg_launch_dror(d_rows, dtype, n_total, d_frame_offsets, n_frames, d_keep_in, &g, ctx->dror_entry.p, ctx->dror_cell.p, ctx->dror_sorted.p,
                            d_out_keep, d_out_neighbours, stream ? (hipStream_t)stream : ctx->stream);
     if (e) return fail(ctx, SNOWGPU_E_HIP, std::string("dror launch: ") + hipGetErrorString((hipError_t)e));
+    return SNOWGPU_OK;
+}
+
+// Point-to-voxel grouping of an aligned batch (snowgpu_voxel.hip; the cell and the tables: sg_voxel.h).  See include/snowgpu.h.
+extern "C" int snowgpu_voxelize_device(snowgpu_ctx *ctx, int n_frames, int64_t n_total, int64_t max_frame_rows, const int64_t *d_frame_offsets,
+                                       const void *d_rows, int dtype, const double *range6, const double *size3, int max_points, int max_voxels,
+                                       int n_features, const uint8_t *d_keep_in, void *d_out_voxels, int32_t *d_out_coords, int32_t *d_out_num_points,
+                                       int32_t *d_out_voxel_offsets, int32_t *d_out_voxel_of, void *stream)
+{
+    if (!ctx) return SNOWGPU_E_INVALID;
+    const SgVoxelArgs a{n_frames, n_total, max_frame_rows, dtype, d_frame_offsets, d_rows, range6, size3, max_points, max_voxels, n_features, d_keep_in,
+                        d_out_voxels, d_out_coords, d_out_num_points, d_out_voxel_offsets, d_out_voxel_of};
+    SgVoxelGrid g{};
+    {
+        std::string msg;
+        if (int rc = sg_check_voxel_args(a, g.n, &msg)) return fail(ctx, rc, msg);
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+    if (n_total == 0) {                                // no row: no voxel, and nothing else is launched
+        HIPCHK(ctx, hipMemsetAsync(d_out_voxel_offsets, 0, sizeof(int32_t) * ((size_t)n_frames + 1), st));
+        return SNOWGPU_OK;
+    }
+    for (int j = 0; j < 3; ++j) { g.lo[j] = range6[j]; g.size[j] = size3[j]; }
+    g.max_points = max_points; g.max_voxels = max_voxels; g.n_features = n_features;
+    g.cap = sg_voxel_capacity(sg_max_frame(max_frame_rows, n_total));
+    g.shift = sg_voxel_shift(g.cap);
+    const size_t n = (size_t)n_total, tiles = (n + 1023) / 1024;
+    ENSURE(ctx, ctx->vox_table, (size_t)n_frames * (size_t)g.cap);
+    ENSURE(ctx, ctx->vox_slot, n);
+    ENSURE(ctx, ctx->vox_order, n);
+    ENSURE(ctx, ctx->vox_first, n);
+    ENSURE(ctx, ctx->vox_tile_cnt, tiles);
+    ENSURE(ctx, ctx->vox_tile_base, tiles + 1);
+    ENSURE(ctx, ctx->vox_fbase, (size_t)n_frames);
+    ENSURE(ctx, ctx->vox_m, (size_t)n_frames);
+    ENSURE(ctx, ctx->vox_span, (size_t)n_frames * (size_t)max_voxels);
+    int e = sg_launch_voxelize(d_rows, dtype, n_total, d_frame_offsets, n_frames, d_keep_in, &g, ctx->vox_table.p, ctx->vox_slot.p, ctx->vox_first.p,
+                               ctx->vox_order.p, ctx->vox_tile_cnt.p, ctx->vox_tile_base.p, ctx->vox_fbase.p, ctx->vox_m.p, ctx->vox_span.p, d_out_voxels,
+                               d_out_coords, d_out_num_points, d_out_voxel_offsets, d_out_voxel_of, st);
+    if (e) return fail(ctx, SNOWGPU_E_HIP, std::string("voxelize launch: ") + hipGetErrorString((hipError_t)e));
     return SNOWGPU_OK;
 }
 

@@ -19,6 +19,8 @@ The reference's training-time caller (the OpenPCDet DENSE dataset: `root_path`, 
     builds that mask on the device from the camera's view (`fov_keep`): precompute.py:96-104 without a boolean index or a host read.
   * `dror_keep(frames, ...)` is dynamic radius outlier removal (the de-noising filter in front of the viewer's chain) as one more producer
     and consumer of such masks (snowgpu_dror_mask_device).
+  * `voxelize(frames_or_result, point_cloud_range, voxel_size, max_points, max_voxels)` groups the present rows of an aligned batch into
+    voxels of static shape (VoxelBatch; snowgpu_voxelize_device): the hand-off to a detector's first operation, in the same stream or graph.
   * `augment_wet_batch_aligned(frames, ...)` is the snowfall + wet-ground chain with that aligned result (AlignedWetResult: per-frame
     flags beside it; snowgpu_augment_wet_batch_device_aligned), `wet_ground_batch_aligned(frames, keep)` the wet-ground stage alone on rows
     and a keep mask from any earlier stage (snowgpu_wet_ground_batch_device_aligned).
@@ -562,6 +564,94 @@ def dror_keep(frames, alpha=0.45, beta=3, k_min=3, sr_min=0.04, keep=None, *, ou
                                      float(alpha), float(beta), float(sr_min), int(k_min), 0 if keep is None else keep.data_ptr(), out.data_ptr(),
                                      0 if nb is None else nb.data_ptr(), run.cuda_stream)
     return (out, nb) if return_neighbours else out
+
+
+class VoxelBatch:
+    """What voxelize() leaves behind, F = frames, V = max_voxels, T = max_points, C = num_features -- every shape static:
+    `voxels` (F V, T, C; the rows' dtype), `coords` (F V, 4 int32: frame, z, y, x cell), `num_points` (F V, int32), `voxel_offsets`
+    (F + 1 int32, ON THE DEVICE: frame f's voxels are [voxel_offsets[f], voxel_offsets[f + 1]), the packed voxels end at
+    voxel_offsets[F]; beyond it voxels are 0, coords -1, num_points 0) and `voxel_of` (N_total int32: every row's packed voxel, -1 without
+    one; None unless asked for).  All still being written until the stream the call was made on has caught up."""
+
+    def __init__(self, voxels, coords, num_points, voxel_offsets, voxel_of=None):
+        self.voxels, self.coords, self.num_points, self.voxel_offsets, self.voxel_of = voxels, coords, num_points, voxel_offsets, voxel_of
+
+    @classmethod
+    def empty(cls, n_frames, max_points, max_voxels, num_features=4, dtype=None, device=None, n_rows=None):
+        """Uninitialised buffers of the shapes voxelize() writes for such a call (out=): static addresses for a captured graph.
+        n_rows: also a `voxel_of` for a batch of that many rows."""
+        import torch
+        dev = torch.device("cuda", torch.cuda.current_device() if device is None else int(device)) if not isinstance(device, torch.device) else device
+        slots = int(n_frames) * int(max_voxels)
+        i32 = dict(dtype=torch.int32, device=dev)
+        return cls(torch.empty((slots, int(max_points), int(num_features)), dtype=dtype or torch.float32, device=dev), torch.empty((slots, 4), **i32),
+                   torch.empty(slots, **i32), torch.empty(int(n_frames) + 1, **i32), None if n_rows is None else torch.empty(int(n_rows), **i32))
+
+    def frames(self):
+        """[(voxels_f, coords_f, num_points_f)] per frame, trimmed views of the result tensors.  Reads the offsets: synchronizes."""
+        off = self.voxel_offsets.cpu().numpy()
+        return [(self.voxels[a:b], self.coords[a:b], self.num_points[a:b]) for a, b in zip(off[:-1].tolist(), off[1:].tolist())]
+
+
+def voxelize(frames, point_cloud_range, voxel_size, max_points, max_voxels, *, keep=None, num_features=4, out=None, return_voxel_of=False,
+             device=None, slot=0):
+    """Point-to-voxel grouping on the device (snowgpu_voxelize_device; the definition: include/snowgpu.h): the first operation of SECOND,
+    PV-RCNN and PointPillars, with static shapes.  Per frame, the rows that are present, finite and inside point_cloud_range
+    (x0, y0, z0, x1, y1, z1) are walked in input order; the first row of a new cell opens the frame's next voxel (cells beyond max_voxels
+    are dropped), and a voxel stores its first max_points rows, columns 0 .. num_features - 1, bit for bit.
+
+    frames    what dror_keep takes -- or an AlignedResult / AlignedWetResult: its rows, offsets and keep mask are used (nothing is waited for).
+    keep      an input keep mask as the aligned calls take it (with a result: ANDed with the result's own).
+    out       a VoxelBatch to write into (VoxelBatch.empty): every element is written, nothing needs clearing.
+    return_voxel_of   also fill `voxel_of`: every row's packed voxel index, -1 without one (dynamic voxelization's point-to-voxel map).
+
+    Returns a VoxelBatch.  Asynchronous on torch's current stream; nothing is read on the host: capturable after one warm-up call."""
+    import torch
+    if isinstance(frames, AlignedResult):
+        res = frames
+        own = res.keep if res.keep.dtype == torch.bool else res.keep.view(torch.bool)
+        frames = DeviceBatch(res.rows, res.offsets)
+        keep = own if keep is None else (_keep_mask(torch, keep, res.rows, res.offsets) & own)
+    if not is_device_input(frames):
+        raise ValueError("voxelize: torch CUDA tensors or an aligned result (host arrays: lidar_snow_sim_amd.voxel.points_to_voxels)")
+    for name, v in (("max_points", max_points), ("max_voxels", max_voxels), ("num_features", num_features)):
+        if isinstance(v, bool) or int(v) != v:
+            raise ValueError(f"voxelize: {name} must be an integer")
+    rng, size = np.asarray(point_cloud_range, np.float64).reshape(-1), np.asarray(voxel_size, np.float64).reshape(-1)
+    if rng.shape != (6,) or size.shape != (3,):
+        raise ValueError("voxelize: point_cloud_range holds 6 numbers (x0, y0, z0, x1, y1, z1), voxel_size 3")
+    rows, offsets, _, eng = _resolve_input(torch, frames, False, device, slot)
+    dev = rows.device
+    nf, n = len(offsets) - 1, int(offsets[-1])
+    T, V, C = int(max_points), int(max_voxels), int(num_features)
+    if keep is not None:
+        keep = _keep_mask(torch, keep, rows, offsets)
+    # (the shapes below need these three; the entry refuses them in the same words, and everything else of the domain)
+    if not 3 <= C <= 5:
+        raise ValueError("voxelize: n_features must be 3, 4 or 5: the columns of a row that a voxel stores")
+    if T < 1 or V < 1:
+        raise ValueError("voxelize: max_points and max_voxels must be at least 1")
+    if nf * V > 2 ** 31 - 1:
+        raise ValueError("voxelize: n_frames * max_voxels exceeds 2^31 - 1; split the batch")
+    if out is None:
+        out = VoxelBatch.empty(nf, T, V, C, rows.dtype, dev, n if return_voxel_of else None)
+    else:
+        want = (("voxels", (nf * V, T, C), rows.dtype), ("coords", (nf * V, 4), torch.int32), ("num_points", (nf * V,), torch.int32),
+                ("voxel_offsets", (nf + 1,), torch.int32)) + ((("voxel_of", (n,), torch.int32),) if return_voxel_of else ())
+        for name, shape, dtype in want:
+            t = getattr(out, name, None) if isinstance(out, VoxelBatch) else None
+            if not (torch.is_tensor(t) and tuple(t.shape) == shape and t.dtype == dtype and t.is_contiguous() and t.device == dev):
+                raise ValueError(f"voxelize: out must be a VoxelBatch whose {name} is a contiguous {tuple(shape)} {dtype} tensor on the device of the rows")
+    vof = out.voxel_of if return_voxel_of else None
+    if n == 0:                                          # no row: the entry writes the offsets alone
+        out.voxels.zero_(); out.coords.fill_(-1); out.num_points.zero_()
+    up = _uploads(eng)
+    with torch.cuda.device(dev), _on_run_stream(torch, eng, dev) as (_, run):
+        d_off = up.get(torch, dev, offsets, run)
+        eng.ctx.voxelize_device(nf, n, int(np.diff(offsets).max()), d_off.data_ptr(), rows.data_ptr() if n else 0, 0 if rows.dtype == torch.float32 else 1,
+                                rng, size, T, V, C, 0 if keep is None or not n else keep.data_ptr(), out.voxels.data_ptr(), out.coords.data_ptr(),
+                                out.num_points.data_ptr(), out.voxel_offsets.data_ptr(), 0 if vof is None or not n else vof.data_ptr(), run.cuda_stream)
+    return out if return_voxel_of or out.voxel_of is None else VoxelBatch(out.voxels, out.coords, out.num_points, out.voxel_offsets)
 
 
 def augment_batch(frames, particle_file_prefix, beam_divergence, shuffle=True, noise_floor=0.7, root_path=None, *, planes=None,
