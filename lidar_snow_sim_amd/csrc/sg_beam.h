@@ -435,9 +435,12 @@ __device__ __forceinline__ SgQsPair sg_qs_load(const uint32_t *p) { return SgQsP
 // ---- the same scan, one WAVE for its 64 beams ---------------------------------------------------------------------------
 // A beam tests every record of its bins that is nearer than its target -- a handful for a ground return, dozens for a far
 // wall -- and with one beam per lane a wave is as slow as its farthest beam (SQ counters: 45 % of the lanes active).  Here the
-// wave flattens the work: every lane finds how many records each of its (first two) bins holds before its target (binary
-// search: bins are sorted by range), a prefix sum over the wave numbers the (beam, record) pairs, and the lanes take 64
-// pairs at a time whichever beams they belong to -- the owner's geometry travels by cross-lane reads.  A hit is appended to
+// wave flattens the work: every lane finds how many records of each of its (first two) bins are candidates -- with the
+// step-major range index the upper count of the target's step, read with one load and no search, a few of them at or beyond
+// the target; without it the records before the target exactly, by binary search (bins are sorted by range) --, a prefix
+// sum over the wave numbers the (beam, record) pairs, and the lanes take 64 pairs at a time whichever beams they belong
+// to -- the owner's geometry travels by cross-lane reads, and a candidate at or beyond its owner's target is dropped
+// there.  A hit is appended to
 // its owner's list through an LDS counter; every beam sorts its few entries by (range, scan order) afterwards, which is the
 // order the per-lane scan produces.  Bins beyond the second (wedges wider than a bin) keep the per-lane loop.
 // s_cnt: one int per lane of the block; s_key: LMAX ints per lane (the scan order of the stored entries); s_st: two ints per lane.
@@ -468,6 +471,12 @@ __device__ __forceinline__ int sg_wave_scan_t(bool act, T px, T py, T pz, const 
     int n0 = 0, n1 = 0, span = -1, b_lo = 0, nb = 1;
     d_t = 0; theta_t = 0;
     if (act) {
+        // which index the table has, settled before the geometry: one pointer, the step count (0: not step-major) and the steps per metre
+        // are what stays live through it -- as many registers as the two pointers where the table is the lane's own
+        const bool stepmajor = tab.bin_qs != nullptr;
+        const SG_GLOBAL uint32_t *g_idx = sg_gptr(stepmajor ? tab.bin_qs : tab.bin_q);
+        const int qn = !stepmajor ? 0 : tab.qs_steps ? (int)tab.qs_steps : SG_QSTEPS;           // (a zero-initialised descriptor: the legacy shape)
+        const float q_per_m = tab.qs_steps ? tab.qs_per_m : (float)(1.0 / SG_QSTEP_M);
         g = sg_beam_geometry<T>(px, py, pz, beam_div_deg, EXACT_TAN, d_t);
         theta_t = (T)g.theta_c;                                 // exact: float32 rows widened a float32 azimuth
         nb = (int)tab.n_bins;
@@ -478,31 +487,37 @@ __device__ __forceinline__ int sg_wave_scan_t(bool act, T px, T py, T pz, const 
         const int b_nx = (b_lo + 1 == nb) ? 0 : b_lo + 1;
         const SG_GLOBAL uint32_t *g_start = sg_gptr(tab.bin_start);
         const SG_GLOBAL SgEntry *g_ent = sg_gptr(tab.entries);
-        // The coarse range index brackets the prefix (counts below the multiples of SG_QSTEP_M around d): the search below then looks at
-        // the one or two records in between instead of halving the whole bin.  Step of the target's range (a NaN lands in the last):
-        const double dq = g.d * (1.0 / SG_QSTEP_M);
-        const int kk = dq < (double)(SG_QSTEPS - 1) ? (int)dq : SG_QSTEPS - 1;
         const uint32_t s0 = g_start[b_lo], s1 = g_start[b_nx];
         st0 = s0; st2 = s1;
-        uint32_t lo0 = st0, lo1 = st2, hi0, hi1;               // records with rho < d: a prefix of each (sorted) bin
-        if (tab.bin_qs != nullptr) {
-            // Step-major index (sg_range_index.h): ONE 8-byte load returns lower | upper count of this step for bin b_lo and for the bin
-            // after it (the row's last word is bin 0 again) -- and the lanes of a wave, beams of neighbouring azimuth, share its lines.
-            // The upper count of the last step is the bin's length: neither the bins' ends nor a special case for that step.
-            const SgQsPair w = sg_qs_load(sg_gptr(tab.bin_qs) + (size_t)kk * SG_QS_ROW(nb) + b_lo);
-            lo0 = st0 + (w.x & 0xffffu); hi0 = st0 + (w.x >> 16);
-            hi1 = st2;
-            if (span >= 1) { lo1 = st2 + (w.y & 0xffffu); hi1 = st2 + (w.y >> 16); }
+        if (qn != 0) {
+            // Step-major index (sg_range_index.h): ONE 8-byte load returns lower | upper count of the target's step (a NaN lands in the
+            // last) for bin b_lo and for the bin after it (the row's last word is bin 0 again) -- and the lanes of a wave, beams of
+            // neighbouring azimuth, share its lines.  The upper count of the last step is the bin's length.
+            // NO search for the prefix "records nearer than the target": every record below the step's UPPER count is a candidate, and
+            // the pair loop, which reads a record's range with its first half anyway, drops those at or beyond the target (`nearer`
+            // below: the predicate the search used).  The search was one dependent round trip per trip on the chain this pass is, a
+            // per-lane 8-byte load out of a 64-byte record, as often as the wave's worst lane needed.
+            const double dq = g.d * (double)q_per_m;
+            const int kk = dq < (double)(qn - 1) ? (int)dq : qn - 1;
+            const SgQsPair w = sg_qs_load(g_idx + (size_t)kk * SG_QS_ROW(nb) + b_lo);
+            if (g.d == g.d) {                                                      // NaN target: no record is nearer
+                n0 = (int)(w.x >> 16);
+                if (span >= 1) n1 = (int)(w.y >> 16);
+            }
         } else {
-            // Bin-major index or none (a table with a bin too long for 16-bit counts; a hand-made table): the bins' ends and four dword
-            // loads, every one issued before the first is used -- no load under a condition of its own (the compiler kept such a load
-            // behind a wait for the earlier ones).
+            // Bin-major index or none (a table with a bin too long for 16-bit counts; a hand-made table): the coarse index brackets the
+            // prefix (counts below the multiples of SG_QSTEP_M around d) and a binary search looks at the records in between.  The bins'
+            // ends and four dword loads, every one issued before the first is used -- no load under a condition of its own (the compiler
+            // kept such a load behind a wait for the earlier ones).
+            const double dq = g.d * (1.0 / SG_QSTEP_M);
+            const int kk = dq < (double)(SG_QSTEPS - 1) ? (int)dq : SG_QSTEPS - 1;
+            uint32_t lo0 = st0, lo1 = st2, hi0, hi1;           // records with rho < d: a prefix of each (sorted) bin
             const uint32_t s0e = g_start[b_lo + 1], s1e = g_start[b_nx + 1];
-            const bool has_q = tab.bin_q != nullptr;
+            const bool has_q = g_idx != nullptr;
             uint32_t c0 = 0, c1 = 0, u0 = 0, u1 = 0;
             if (has_q) {
                 const int k1 = kk < SG_QSTEPS - 1 ? kk + 1 : kk;      // (the last step has no upper count: its load repeats the lower one)
-                const SG_GLOBAL uint32_t *q0 = sg_gptr(tab.bin_q) + (size_t)b_lo * SG_QSTEPS, *q1 = sg_gptr(tab.bin_q) + (size_t)b_nx * SG_QSTEPS;
+                const SG_GLOBAL uint32_t *q0 = g_idx + (size_t)b_lo * SG_QSTEPS, *q1 = g_idx + (size_t)b_nx * SG_QSTEPS;
                 c0 = q0[kk]; u0 = q0[k1]; c1 = q1[kk]; u1 = q1[k1];
             }
             hi0 = s0e; hi1 = span >= 1 ? s1e : s1;
@@ -511,15 +526,15 @@ __device__ __forceinline__ int sg_wave_scan_t(bool act, T px, T py, T pz, const 
                 if (kk < SG_QSTEPS - 1) hi0 = st0 + u0;
                 if (span >= 1) { lo1 = st2 + c1; if (kk < SG_QSTEPS - 1) hi1 = st2 + u1; }
             }
+            if (!(g.d == g.d)) { lo0 = hi0 = st0; lo1 = hi1 = st2; }      // NaN target: no record is nearer
+            while (lo0 < hi0 || lo1 < hi1) {
+                const uint32_t m0 = (lo0 + hi0) >> 1, m1 = (lo1 + hi1) >> 1;
+                const double r0 = lo0 < hi0 ? g_ent[m0].rho : 0.0, r1 = lo1 < hi1 ? g_ent[m1].rho : 0.0;
+                if (lo0 < hi0) { if (r0 < g.d) lo0 = m0 + 1; else hi0 = m0; }
+                if (lo1 < hi1) { if (r1 < g.d) lo1 = m1 + 1; else hi1 = m1; }
+            }
+            n0 = (int)(lo0 - st0); n1 = (int)(lo1 - st2);
         }
-        if (!(g.d == g.d)) { lo0 = hi0 = st0; lo1 = hi1 = st2; }          // NaN target: no record is nearer
-        while (lo0 < hi0 || lo1 < hi1) {
-            const uint32_t m0 = (lo0 + hi0) >> 1, m1 = (lo1 + hi1) >> 1;
-            const double r0 = lo0 < hi0 ? g_ent[m0].rho : 0.0, r1 = lo1 < hi1 ? g_ent[m1].rho : 0.0;
-            if (lo0 < hi0) { if (r0 < g.d) lo0 = m0 + 1; else hi0 = m0; }
-            if (lo1 < hi1) { if (r1 < g.d) lo1 = m1 + 1; else hi1 = m1; }
-        }
-        n0 = (int)(lo0 - st0); n1 = (int)(lo1 - st2);
     }
     s_cnt[tid] = 0;                                             // same wave writes and bumps it: LDS operations of a wave keep their order
     // first records of the beam's two bins: read by whichever lane tests one of its records -- through LDS, not a cross-lane
@@ -565,7 +580,10 @@ __device__ __forceinline__ int sg_wave_scan_t(bool act, T px, T py, T pz, const 
             bool und = false, hit_r, hit_l;
             const bool hit = sg_flake_test<DEFER>(og, phi, fx, fy, fr, hit_r, hit_l, und);
             const SgTail tl = sg_tail_pin(tl_raw);
-            if (hit) {
+            // The range test (simulation.py:345), on the doubles the search compares: a candidate of the step-major index may lie at or
+            // beyond the target, and such a record leaves nothing behind -- no hit, no count, no undecided mark, no list entry.
+            const bool nearer = tl.rho < og.d;
+            if (hit && nearer) {
                 const double rho = tl.rho;
                 const uint32_t flags = tl.flags;
                 if (!(j >= n0o && !(flags & 1u))) {                                 // a flake filed under both bins counts once
@@ -575,7 +593,9 @@ __device__ __forceinline__ int sg_wave_scan_t(bool act, T px, T py, T pz, const 
                         if constexpr (COMPACT) reinterpret_cast<uint32_t *>(s_a1)[pos * STRIDE + col] = sg_hit_word(e, hit_r, hit_l);
                         else { s_a1[pos * STRIDE + col] = hit_r ? og.theta_r : fp->t0; s_a2[pos * STRIDE + col] = hit_l ? og.theta_l : fp->t1; }
                         s_rho[pos * STRIDE + col] = rho;
-                        s_key[pos * STRIDE + col] = p;
+                        // scan order: the record's offset within its bin, the second bin after the first -- whatever the candidate count,
+                        // so whichever index bracketed the prefix; below the per-lane loop's 0x40000000
+                        s_key[pos * STRIDE + col] = j < n0o ? j : (j - n0o) | 0x20000000;
                     } else if (pos < ov_cap) {
                         double *sp = ov_blk + (size_t)col * SG_OV_STRIDE + 2 + 3 * pos;
                         sp[0] = hit_r ? og.theta_r : fp->t0; sp[1] = hit_l ? og.theta_l : fp->t1; sp[2] = rho;
@@ -583,7 +603,7 @@ __device__ __forceinline__ int sg_wave_scan_t(bool act, T px, T py, T pz, const 
                 }
             }
             // (an undecided test of a record that would not have counted -- filed under an earlier bin too -- sends the beam round as well: harmless)
-            if (DEFER && und) atomicOr(&s_cnt[wbase + o], SG_HITS_UNDECIDED);            // (later appends of this beam then land nowhere)
+            if (DEFER && und && nearer) atomicOr(&s_cnt[wbase + o], SG_HITS_UNDECIDED);            // (later appends of this beam then land nowhere)
         }
     }
     int hits = ((volatile int *)s_cnt)[tid];                    // bumped by other lanes of this wave

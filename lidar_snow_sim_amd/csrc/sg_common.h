@@ -46,7 +46,10 @@ struct SgTable {
     double inv_bin_w;           // n_bins / (2 pi)
     uint32_t n_flakes;
     uint32_t max_bin;           // longest bin (entries)
-    const uint32_t *bin_qs;     // SG_QSTEPS x (n_bins + 1): the same counts step-major, two to a word (sg_range_index.h), or null -- bin_q alone is used
+    const uint32_t *bin_qs;     // qs_steps x (n_bins + 1): counts step-major, two to a word (sg_range_index.h), or null -- bin_q alone is used
+    uint32_t qs_steps;          // shape of bin_qs: steps ...
+    float qs_per_m;             // ... and steps per metre (1 / step length; a power of two, so that range * qs_per_m is exact).
+                                // qs_steps == 0 (a zero-initialised descriptor): SG_QSTEPS steps of SG_QSTEP_M metres, the shape of bin_q
 };
 
 struct SgLasers {

@@ -308,7 +308,7 @@ extern "C" int sg_launch_draw_weather(const SgWeatherDraw *p, int n_frames, uint
 extern "C" int sg_launch_weather_flags(const double *d_weather, int n_frames, int32_t *d_flags, void *stream);
 
 // snowgpu_tables.hip, snowgpu_sampler.hip
-extern "C" int sg_table_index(const SgEntry *entries, const uint32_t *start, uint32_t *q, uint32_t *qs /* or null */, void *stream);
+extern "C" int sg_table_index(const SgEntry *entries, const uint32_t *start, uint32_t *q, uint32_t *qs /* or null */, int qs_steps, double qs_step_m, void *stream);
 extern "C" int sg_file_table_stage_a(const double *d_xyr, int64_t k, SgEntry *fl, int32_t *b0, int32_t *span, uint32_t *count,
                                      uint32_t *start, uint32_t *fill, int32_t *misc, void *stream);
 extern "C" int sg_file_table_stage_b(int64_t k, const SgEntry *fl, const int32_t *b0, const int32_t *span, const uint32_t *start,

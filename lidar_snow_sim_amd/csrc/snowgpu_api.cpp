@@ -190,9 +190,12 @@ static int register_table(snowgpu_ctx *ctx, int table_id, SgEntry *entries, uint
     ctx->tables_dirty = true;
     uint32_t *q = nullptr, *qs = nullptr;
     int e = (int)hipMalloc((void **)&q, (size_t)SG_NBINS * SG_QSTEPS * sizeof(uint32_t));
-    // the step-major index packs two counts into a word: only for tables whose longest bin fits 16 bits (the scan then reads bin_q)
-    if (!e && SG_QS_FITS(max_bin)) e = (int)hipMalloc((void **)&qs, SG_QS_WORDS(SG_NBINS) * sizeof(uint32_t));
-    if (!e) e = sg_table_index(entries, bin_start, q, qs, ctx->stream);
+    // the step-major index packs two counts into a word: only for tables whose longest bin fits 16 bits (the scan then reads bin_q).
+    // Its shape is the library's choice (sg_range_index.h: SG_QS_FILE_STEPS steps of SG_QS_FILE_STEP_M metres) and travels in the descriptor.
+    static_assert(SG_QS_FILE_STEPS >= 1 && SG_QS_FILE_STEPS <= 64, "k_table_index files one step per lane of a wave");
+    static_assert((float)(1.0 / SG_QS_FILE_STEP_M) * SG_QS_FILE_STEP_M == 1.0, "the step length is a power of two");
+    if (!e && SG_QS_FITS(max_bin)) e = (int)hipMalloc((void **)&qs, SG_QS_WORDS_OF(SG_QS_FILE_STEPS, SG_NBINS) * sizeof(uint32_t));
+    if (!e) e = sg_table_index(entries, bin_start, q, qs, SG_QS_FILE_STEPS, SG_QS_FILE_STEP_M, ctx->stream);
     if (!e) e = (int)hipStreamSynchronize(ctx->stream);
     if (e) {
         if (q) (void)hipFree(q);
@@ -206,6 +209,8 @@ static int register_table(snowgpu_ctx *ctx, int table_id, SgEntry *entries, uint
     dt.desc.bin_start = bin_start;
     dt.desc.bin_q = q;
     dt.desc.bin_qs = qs;
+    dt.desc.qs_steps = qs ? (uint32_t)SG_QS_FILE_STEPS : 0u;
+    dt.desc.qs_per_m = (float)(1.0 / SG_QS_FILE_STEP_M);
     // must stay SG_NBINS: bin_q and bin_qs above are sized, and filed by k_table_index, with that constant, and the scan takes the row
     // stride of bin_qs from n_bins (SG_QS_ROW(n_bins)) -- a descriptor with another n_bins would read past the arrays
     dt.desc.n_bins = (uint32_t)SG_NBINS;

@@ -258,6 +258,14 @@ __global__ __launch_bounds__(BLOCK < 64 ? 64 : BLOCK, (!LIST && DICT == 1 && BLO
         // test by the reference's expression, in place
         L = sg_wave_scan_t<T, LMAX, BLOCK, DICT == 1, COMPACT, SEG>(act, px, py, pz, tab, a.beam_div_deg, s_a1, s_a2, s_rho, s_cnt, s_key, s_st, tid, o, d_t,
                                                                     theta_t, a.exact_math != 0, ov_blk, ov_blk ? a.ov_cap : 0);
+        if constexpr (!LIST && !SEG) {
+            // the sorted position again, from the block's scalar base: as a register pair held through the scan it was spilled (float64 rows)
+#if defined(__HIP_DEVICE_COMPILE__)
+            int64_t c = chunk;
+            asm volatile("" : "+s"(c));
+            g = live ? c + tid : -1;
+#endif
+        }
         if (ov_blk && act && o.overflow && o.n_hits <= a.ov_cap) {   // header and the flakes the LDS list holds: the slot is complete
             double *sp = ov_blk + (size_t)tid * SG_OV_STRIDE;
             sp[0] = (double)d_t; sp[1] = (double)theta_t;

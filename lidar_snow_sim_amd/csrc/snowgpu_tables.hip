@@ -161,15 +161,15 @@ __global__ __launch_bounds__(64) void k_file_sort(const uint32_t *__restrict__ s
     }
 }
 
-// Coarse range index of a filed table, both layouts (sg_range_index.h): q[b][k] = records of bin b nearer than SG_QSTEP_M * k metres, and
-// the same counts step-major and paired (qs, or null).  The scan pass starts its search for "records nearer than the target" from the
-// two counts around the target's range instead of the whole bin.
+// Range index of a filed table (sg_range_index.h): the bin-major q[b][k] = records of bin b nearer than SG_QSTEP_M * k metres, and the
+// step-major, paired qs (or null) of qs_steps <= 64 steps of qs_step_m metres, whose upper counts are the scan pass's candidate counts.
+// One wave per bin, one lane per step of either.
 __global__ __launch_bounds__(64) void k_table_index(const SgEntry *__restrict__ entries, const uint32_t *__restrict__ start,
-                                                    uint32_t *__restrict__ q, uint32_t *__restrict__ qs)
+                                                    uint32_t *__restrict__ q, uint32_t *__restrict__ qs, int qs_steps, double qs_step_m)
 {
     const int b = blockIdx.x, k = threadIdx.x;
-    if (k >= SG_QSTEPS) return;
-    sg_range_index_fill(entries, start, SG_NBINS, b, k, q, qs);
+    if (k < SG_QSTEPS) sg_range_index_fill_steps(entries, start, SG_NBINS, b, k, SG_QSTEPS, SG_QSTEP_M, q, nullptr);
+    if (qs && k < qs_steps) sg_range_index_fill_steps(entries, start, SG_NBINS, b, k, qs_steps, qs_step_m, nullptr, qs);
 }
 
 // per-flake quantities of a filed table by table row (debug tap): the copy filed under the flake's first bin
@@ -215,9 +215,10 @@ extern "C" int sg_file_table_stage_b(int64_t k, const SgEntry *fl, const int32_t
     return 0;
 }
 
-extern "C" int sg_table_index(const SgEntry *entries, const uint32_t *start, uint32_t *q, uint32_t *qs /* or null */, void *stream)
+extern "C" int sg_table_index(const SgEntry *entries, const uint32_t *start, uint32_t *q, uint32_t *qs /* or null */, int qs_steps, double qs_step_m, void *stream)
 {
-    hipLaunchKernelGGL(k_table_index, dim3(SG_NBINS), dim3(64), 0, (hipStream_t)stream, entries, start, q, qs);
+    if (qs && (qs_steps < 1 || qs_steps > 64)) return (int)hipErrorInvalidValue;      // one lane per step
+    hipLaunchKernelGGL(k_table_index, dim3(SG_NBINS), dim3(64), 0, (hipStream_t)stream, entries, start, q, qs, qs_steps, qs_step_m);
     SG_CHECK_LAUNCH();
     return 0;
 }

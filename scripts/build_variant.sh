@@ -1,6 +1,7 @@
 #!/bin/bash
-# Build lidar_snow_sim_amd/_variants/libsnowgpu_<name>.so: snowgpu_kernels.hip (the per-beam kernels and their tunables) compiled with extra
-# -D flags, the other translation units of build.SOURCES as they are (same-box A/B runs copy a variant over libsnowgpu.so on the GPU side).
+# Build lidar_snow_sim_amd/_variants/libsnowgpu_<name>.so: snowgpu_kernels.hip (the per-beam kernels and their tunables) and snowgpu_api.cpp
+# (table registration: the shape of the step-major range index it files, sg_range_index.h) compiled with extra -D flags, the other
+# translation units of build.SOURCES as they are (same-box A/B runs copy a variant over libsnowgpu.so on the GPU side).
 # usage: scripts/build_variant.sh <name> [-DX=1 ...]
 set -e
 cd "$(dirname "$0")/.."
@@ -8,7 +9,9 @@ N=$1; shift
 C=lidar_snow_sim_amd/csrc; V=lidar_snow_sim_amd/_variants; mkdir -p $V $C/_obj
 python -m lidar_snow_sim_amd.build > /dev/null
 F="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-unused-function"
-hipcc $F "$@" -x hip -c $C/snowgpu_kernels.hip -o $C/_obj/kernels_$N.o
-OTHERS=$(python -c "from lidar_snow_sim_amd.build import SOURCES; print(' '.join('$C/_obj/' + s.rsplit('.', 1)[0] + '.o' for s in SOURCES if s != 'snowgpu_kernels.hip'))")
-hipcc --offload-arch=gfx950 -shared -fPIC -o $V/libsnowgpu_$N.so $C/_obj/kernels_$N.o $OTHERS -ldl
+hipcc $F "$@" -x hip -c $C/snowgpu_kernels.hip -o $C/_obj/kernels_$N.o &
+hipcc $F "$@" -x hip -c $C/snowgpu_api.cpp -o $C/_obj/api_$N.o
+wait %1
+OTHERS=$(python -c "from lidar_snow_sim_amd.build import SOURCES; print(' '.join('$C/_obj/' + s.rsplit('.', 1)[0] + '.o' for s in SOURCES if s not in ('snowgpu_kernels.hip', 'snowgpu_api.cpp')))")
+hipcc --offload-arch=gfx950 -shared -fPIC -o $V/libsnowgpu_$N.so $C/_obj/kernels_$N.o $C/_obj/api_$N.o $OTHERS -ldl
 echo $V/libsnowgpu_$N.so
