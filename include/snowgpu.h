@@ -650,6 +650,43 @@ int snowgpu_voxelize_device(snowgpu_ctx *ctx, int n_frames, int64_t n_total, int
                             int32_t *d_out_num_points, int32_t *d_out_voxel_offsets, int32_t *d_out_voxel_of /* or NULL */, void *stream);
 
 /*
+ * FARTHEST-POINT KEYPOINTS of an aligned batch: the fixed-size point set of the point-based detectors (PV-RCNN's keypoints in front of its
+ * voxel set abstraction, PointRCNN, Part-A2), with static shapes.  Frames, rows and the input keep mask as snowgpu_voxelize_device takes
+ * them; K = n_samples, C = n_features.  The reference has no sampler; the edge conventions are this library's, restated as a sequential
+ * NumPy program by tests/fps_reference.py.
+ *   Row i of frame f is USABLE iff it is present (d_keep_in NULL or its byte non-zero), |x|, |y|, |z| <= 1e6 (false for NaN) and, when a
+ *   range is given, lo_j <= (double)p_j < hi_j for j = x, y, z.  range6 may be NULL (no range test); its bounds may be infinite.
+ *   u_0 < u_1 < ... < u_{m-1} are the usable rows of the frame in input order.
+ *   All arithmetic is in the rows' dtype.  d(a, b) = ((dx dx) + (dy dy)) + (dz dz), dx = x_a - x_b and likewise y, z: every operation
+ *   rounded on its own, no fused multiply-add, no square root, no reciprocal.
+ *   The walk: t_i = +inf for every usable row; s_0 = u_0; for j = 1 .. K - 1: t_i = min(t_i, d(i, s_{j-1})) for every usable i, then
+ *   s_j = the usable row with the largest t_i, the SMALLEST row index among equals.
+ *   There are no special cases: a chosen row has t = 0 ever after; once every distinct position is taken all t are 0 and s_j = u_0; a
+ *   frame with m < K returns its m rows (if no two coincide) and then u_0 repeated; coincident rows are never both chosen before that.
+ * Outputs, every shape static, every element written by every call:
+ *   d_out_index   (F, K) int32: s_j as a row index into the whole batch (rows[index] gathers); -1 everywhere for a frame with m = 0
+ *   d_out_points  (F, K, C) in the rows' dtype, or NULL: columns 0 .. C - 1 of row s_j, bit for bit; zero for a frame with m = 0
+ *   d_out_dist    (F, K) in the rows' dtype, or NULL: t of s_j at the moment it was chosen; element 0 is +inf; -1 for a frame with m = 0
+ *   d_out_usable  (F) int32, device memory: m_f
+ * Domain: K >= 1, C in 3 .. 5, F K <= 2^31 - 1, n_total < 2^31, no frame above 2^30 rows, dtype 0 (float32) or 1 (float64); with a range:
+ * no NaN in it and lo_j < hi_j.  d_out_index, d_out_points and d_out_dist must not overlap d_keep_in or the rows.  Anything else is
+ * SNOWGPU_E_INVALID.  An empty batch writes usable = 0, index = -1, points = 0 and dist = -1 with one fill kernel and launches no sampler
+ * (d_rows may be NULL).
+ * ONE workgroup of 1024 threads walks a frame (its rounds cannot run side by side; the frames of a batch can): it compacts the frame's
+ * usable rows in input order into scratch and runs the K - 1 rounds without leaving the compute unit -- coordinates and running minima in
+ * registers for up to 16384 usable float32 rows (8192 float64 rows), the minima in LDS and the coordinates streamed from scratch for up to
+ * 39936 (19968), both streamed from scratch beyond (csrc/sg_fps.h: the tiers, chosen on the device per frame; snowgpu_fps.hip).  A
+ * candidate is (bits of t, ~position), folded by an integer maximum: nothing depends on how lanes and waves are combined, and results are
+ * identical from run to run.  A lone frame runs on one compute unit.
+ * Scratch in the context, grown on first use: four values of the rows' dtype and 4 bytes per row, plus 8 elements per frame.  Two kernels
+ * on `stream`; nothing is read on the host, nothing allocated after the first call of a size: capturable.
+ */
+int snowgpu_fps_device(snowgpu_ctx *ctx, int n_frames, int64_t n_total, int64_t max_frame_rows, const int64_t *d_frame_offsets,
+                       const void *d_rows, int dtype, const double *range6 /* host: x0 y0 z0 x1 y1 z1, or NULL */, int n_samples,
+                       int n_features, const uint8_t *d_keep_in /* or NULL: all present */, int32_t *d_out_index,
+                       void *d_out_points /* or NULL */, void *d_out_dist /* or NULL */, int32_t *d_out_usable, void *stream);
+
+/*
  * PER-FRAME WEATHER in one aligned call.  snowgpu_augment_wet_batch_device_aligned_masked applies one weather to every frame, its wet
  * settings host scalars that a captured graph bakes in.  Here every frame brings a record of 8 doubles in DEVICE memory,
  *     d_weather[f] = [snow, wet, water_height, pavement_depth, wet_noise_floor, power_factor, delta, 0]

@@ -192,7 +192,7 @@ struct SgFov {
 
 // Launch wrappers (hipStream_t passed as void*), each implemented in the file that defines its kernels: snowgpu_sort.hip (expand_rows, sort,
 // gather_rows, segments*, resolve_tables), snowgpu_kernels.hip (beams, power*, tier_*, huge, sg_beams_block), snowgpu_rows.hip (rows),
-// snowgpu_compact.hip (compact, crop_*), snowgpu_mask.hip (mask_front, finish_aligned_masked, fov_mask), snowgpu_dror.hip (dror), snowgpu_voxel.hip (voxelize).  Every one of these files includes this header, so a definition cannot drift from its declaration.
+// snowgpu_compact.hip (compact, crop_*), snowgpu_mask.hip (mask_front, finish_aligned_masked, fov_mask), snowgpu_dror.hip (dror), snowgpu_voxel.hip (voxelize), snowgpu_fps.hip (fps).  Every one of these files includes this header, so a definition cannot drift from its declaration.
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -280,6 +280,12 @@ int sg_launch_voxelize(const void *rows, int dtype, int64_t n, const int64_t *fr
                        unsigned long long *table, uint32_t *slot_of, uint8_t *first, uint32_t *order, int32_t *tile_cnt, int32_t *tile_base, int32_t *fbase,
                        int32_t *m, uint32_t *span, void *out_voxels, int32_t *out_coords, int32_t *out_num_points, int32_t *out_voxel_offsets,
                        int32_t *out_voxel_of, void *stream);
+// Farthest point sampling (sg_fps.h; the definition: include/snowgpu.h): two kernels.  Scratch: sx, sy, sz, st in the rows' dtype and ssrc,
+// sg_fps_scratch(n, n_frames) elements each.  out_points and out_dist may be null.
+struct SgFpsRange;
+int sg_launch_fps(const void *rows, int dtype, int64_t n, const int64_t *frame_off, int n_frames, const uint8_t *keep_in, const struct SgFpsRange *range,
+                  int32_t n_samples, int32_t n_features, void *sx, void *sy, void *sz, void *st, int32_t *ssrc, int32_t *out_index, void *out_points,
+                  void *out_dist, int32_t *out_usable, void *stream);
 #ifdef __cplusplus
 }
 #endif

@@ -169,6 +169,59 @@ static inline int sg_check_voxel_args(const SgVoxelArgs &a, int32_t n_cells[3], 
     return 0;
 }
 
+// ---- snowgpu_fps_device -----------------------------------------------------------------------------------------------------------------
+struct SgFpsArgs {
+    int n_frames;
+    int64_t n_total, max_frame_rows;
+    int dtype;
+    const int64_t *frame_off;
+    const void *rows;
+    const double *range6;             // (x0, y0, z0, x1, y1, z1), host memory, or NULL: no range test
+    int n_samples, n_features;
+    const uint8_t *keep_in;
+    int32_t *out_index;
+    void *out_points, *out_dist;      // or NULL
+    int32_t *out_usable;
+};
+
+// two arrays, `abytes` from a and `bbytes` from b, that share a byte (false where either is NULL or empty)
+static inline bool sg_ranges_meet(const void *a, size_t abytes, const void *b, size_t bbytes)
+{
+    const uintptr_t p = (uintptr_t)a, q = (uintptr_t)b;
+    return p && q && abytes && bbytes && p < q + bbytes && q < p + abytes;
+}
+
+// 0, or SG_ARGS_INVALID with *msg.  As above, the order is part of the ABI.
+static inline int sg_check_fps_args(const SgFpsArgs &a, std::string *msg)
+{
+    static const char *who = "snowgpu_fps_device";
+    if (a.n_frames <= 0 || a.n_total < 0 || !a.frame_off || !a.out_index || !a.out_usable || (a.n_total > 0 && !a.rows) || (a.dtype != 0 && a.dtype != 1))
+        return sg_refuse(who, ": null pointer or bad dtype", msg);
+    if (a.n_total >= ((int64_t)1 << 31)) return sg_refuse("", "batch too large: split it below 2^31 rows", msg);
+    if (a.n_features < 3 || a.n_features > 5) return sg_refuse(who, ": n_features must be 3, 4 or 5: the columns of a row that a keypoint carries", msg);
+    if (a.n_samples < 1) return sg_refuse(who, ": n_samples must be at least 1", msg);
+    if ((int64_t)a.n_frames * a.n_samples > (((int64_t)1 << 31) - 1))
+        return sg_refuse(who, ": n_frames * n_samples exceeds 2^31 - 1; split the batch", msg);
+    if (sg_max_frame(a.max_frame_rows, a.n_total) > ((int64_t)1 << 30))
+        return sg_refuse(who, ": a frame of more than 2^30 rows; split it", msg);
+    if (a.range6) {
+        for (int j = 0; j < 6; ++j)
+            if (a.range6[j] != a.range6[j]) return sg_refuse(who, ": a bound of the range is NaN; pass NULL for no range, or infinite bounds", msg);
+        for (int j = 0; j < 3; ++j)
+            if (!(a.range6[j] < a.range6[3 + j])) return sg_refuse(who, ": the range needs lo < hi on every axis", msg);
+    }
+    const size_t esz = a.dtype == 0 ? 4 : 8, elems = (size_t)a.n_frames * (size_t)a.n_samples, n = (size_t)a.n_total;
+    const struct { const void *p; size_t bytes; const char *name; } outs[3] = {
+        {a.out_index, elems * 4, "d_out_index"}, {a.out_points, elems * (size_t)a.n_features * esz, "d_out_points"}, {a.out_dist, elems * esz, "d_out_dist"}};
+    for (const auto &o : outs) {
+        if (sg_ranges_meet(o.p, o.bytes, a.keep_in, n))
+            return sg_refuse(who, (std::string(": ") + o.name + " overlaps d_keep_in; the mask is read while the samples are written: pass a buffer apart from it").c_str(), msg);
+        if (sg_ranges_meet(o.p, o.bytes, a.rows, n * 5 * esz))
+            return sg_refuse(who, (std::string(": ") + o.name + " overlaps d_rows; the rows are read while the samples are written: pass a buffer apart from them").c_str(), msg);
+    }
+    return 0;
+}
+
 // 0, or SG_ARGS_INVALID with *msg (built on this path only).  The order is part of the ABI: it decides which message a doubly wrong call gets.
 static inline int sg_check_device_args(const SgDeviceArgs &a, const SgCtxView &c, const SgEntryShape &s, std::string *msg)
 {

@@ -89,6 +89,10 @@ struct __attribute__((visibility("default"))) snowgpu_ctx {
     DevBuf<uint32_t> vox_slot, vox_order, vox_span;
     DevBuf<uint8_t> vox_first;
     DevBuf<int32_t> vox_tile_cnt, vox_tile_base, vox_fbase, vox_m;
+    // farthest point sampling (snowgpu_fps_device): the usable rows of every frame compacted in input order -- x, y, z and the running
+    // minimum t as four arrays in the rows' dtype -- and their source rows
+    DevBuf<uint8_t> fps_x, fps_y, fps_z, fps_t;
+    DevBuf<int32_t> fps_src;
     // scratch shared by every batch
     DevBuf<int32_t> tile_hist, tile_base, perm, ctile_cnt, ctile_base, table_ids, out_src;
     DevBuf<uint8_t> srows;            // channel-sorted copy of the frames whose rows did not come channel-sorted (firing order)

@@ -143,6 +143,7 @@ extern "C" void snowgpu_destroy(snowgpu_ctx *ctx)
     ctx->dror_entry.release(); ctx->dror_cell.release(); ctx->dror_sorted.release();
     ctx->vox_table.release(); ctx->vox_slot.release(); ctx->vox_order.release(); ctx->vox_span.release(); ctx->vox_first.release();
     ctx->vox_tile_cnt.release(); ctx->vox_tile_base.release(); ctx->vox_fbase.release(); ctx->vox_m.release();
+    ctx->fps_x.release(); ctx->fps_y.release(); ctx->fps_z.release(); ctx->fps_t.release(); ctx->fps_src.release();
     sg_prepass_release(&ctx->prepass);
     sg_plane_release(&ctx->plane_scr);
     ctx->plane_est.release(); ctx->wet_plane_est.release(); ctx->plane_info.release(); ctx->stats_hist.release(); ctx->stats_rec.release();

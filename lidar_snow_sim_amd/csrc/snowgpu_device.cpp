@@ -1,5 +1,5 @@
 // snowgpu_device.cpp -- the entries of the C ABI (include/snowgpu.h) that take DEVICE pointers and enqueue on the caller's stream: every
-// *_batch_device* entry, the plane estimate, the FOV mask, the outlier filter, the voxel stage and the weather draw.  Each batch entry fills an SgDeviceArgs, has it checked
+// *_batch_device* entry, the plane estimate, the FOV mask, the outlier filter, the voxel stage, the keypoint stage and the weather draw.  Each batch entry fills an SgDeviceArgs, has it checked
 // (sg_device_args.h: every refusal, in one order), sets the device and runs batch_from_args() and the stages it needs.  The launch
 // sequence of a batch is snowgpu_batch.cpp; no host copy, no synchronisation, no allocation after the first call of a given size.
 #include "sg_host.h"
@@ -7,6 +7,7 @@
 #include "sg_weather.h"     // SgWeatherDraw and the limits of the draw
 #include "sg_dror.h"        // the grid of the outlier filter and its domain
 #include "sg_voxel.h"       // the grid of the voxel stage and the capacity of its tables
+#include "sg_fps.h"         // the range of the keypoint stage and the size of its scratch
 
 static_assert(SG_ARGS_INVALID == SNOWGPU_E_INVALID && SG_PLANE_REFERENCE == 0, "sg_device_args.h restates these two");
 
@@ -432,6 +433,36 @@ extern "C" int snowgpu_voxelize_device(snowgpu_ctx *ctx, int n_frames, int64_t n
                                ctx->vox_order.p, ctx->vox_tile_cnt.p, ctx->vox_tile_base.p, ctx->vox_fbase.p, ctx->vox_m.p, ctx->vox_span.p, d_out_voxels,
                                d_out_coords, d_out_num_points, d_out_voxel_offsets, d_out_voxel_of, st);
     if (e) return fail(ctx, SNOWGPU_E_HIP, std::string("voxelize launch: ") + hipGetErrorString((hipError_t)e));
+    return SNOWGPU_OK;
+}
+
+// Farthest-point keypoints of an aligned batch (snowgpu_fps.hip; the usable test, the distance and the candidate key: sg_fps.h).  See
+// include/snowgpu.h.
+extern "C" int snowgpu_fps_device(snowgpu_ctx *ctx, int n_frames, int64_t n_total, int64_t max_frame_rows, const int64_t *d_frame_offsets, const void *d_rows,
+                                  int dtype, const double *range6, int n_samples, int n_features, const uint8_t *d_keep_in, int32_t *d_out_index,
+                                  void *d_out_points, void *d_out_dist, int32_t *d_out_usable, void *stream)
+{
+    if (!ctx) return SNOWGPU_E_INVALID;
+    const SgFpsArgs a{n_frames, n_total, max_frame_rows, dtype, d_frame_offsets, d_rows, range6, n_samples, n_features, d_keep_in,
+                      d_out_index, d_out_points, d_out_dist, d_out_usable};
+    {
+        std::string msg;
+        if (int rc = sg_check_fps_args(a, &msg)) return fail(ctx, rc, msg);
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    SgFpsRange r;
+    for (int j = 0; j < 3; ++j) { r.lo[j] = range6 ? range6[j] : -INFINITY; r.hi[j] = range6 ? range6[3 + j] : INFINITY; }
+    if (n_total > 0) {
+        const size_t elems = sg_fps_scratch(n_total, n_frames), bytes = elems * (dtype == 0 ? 4 : 8);
+        ENSURE(ctx, ctx->fps_x, bytes);
+        ENSURE(ctx, ctx->fps_y, bytes);
+        ENSURE(ctx, ctx->fps_z, bytes);
+        ENSURE(ctx, ctx->fps_t, bytes);
+        ENSURE(ctx, ctx->fps_src, elems);
+    }
+    int e = sg_launch_fps(d_rows, dtype, n_total, d_frame_offsets, n_frames, d_keep_in, &r, n_samples, n_features, ctx->fps_x.p, ctx->fps_y.p, ctx->fps_z.p,
+                          ctx->fps_t.p, ctx->fps_src.p, d_out_index, d_out_points, d_out_dist, d_out_usable, stream ? (hipStream_t)stream : ctx->stream);
+    if (e) return fail(ctx, SNOWGPU_E_HIP, std::string("fps launch: ") + hipGetErrorString((hipError_t)e));
     return SNOWGPU_OK;
 }
 

@@ -21,6 +21,8 @@ The reference's training-time caller (the OpenPCDet DENSE dataset: `root_path`, 
     and consumer of such masks (snowgpu_dror_mask_device).
   * `voxelize(frames_or_result, point_cloud_range, voxel_size, max_points, max_voxels)` groups the present rows of an aligned batch into
     voxels of static shape (VoxelBatch; snowgpu_voxelize_device): the hand-off to a detector's first operation, in the same stream or graph.
+  * `sample_keypoints(frames_or_result, n_samples)` takes a fixed number of farthest-point samples from the present rows of every frame
+    (KeypointBatch; snowgpu_fps_device): the hand-off to a point-based detector, likewise.
   * `augment_wet_batch_aligned(frames, ...)` is the snowfall + wet-ground chain with that aligned result (AlignedWetResult: per-frame
     flags beside it; snowgpu_augment_wet_batch_device_aligned), `wet_ground_batch_aligned(frames, keep)` the wet-ground stage alone on rows
     and a keep mask from any earlier stage (snowgpu_wet_ground_batch_device_aligned).
@@ -191,6 +193,10 @@ class _SmallUploads:
                 self.d.popitem(last=False)
         else:
             self.d.move_to_end(key)
+            if torch.cuda.is_current_stream_capturing():
+                # The runtime refuses to query an event whose stream is capturing now -- that of a warm-up call made on the stream of the
+                # capture.  The copy was made before the capture began, and torch.cuda.graph synchronises the device when it begins.
+                return hit[0]
         if not hit[1].query():
             user.wait_event(hit[1])
         return hit[0]
@@ -652,6 +658,88 @@ def voxelize(frames, point_cloud_range, voxel_size, max_points, max_voxels, *, k
                                 rng, size, T, V, C, 0 if keep is None or not n else keep.data_ptr(), out.voxels.data_ptr(), out.coords.data_ptr(),
                                 out.num_points.data_ptr(), out.voxel_offsets.data_ptr(), 0 if vof is None or not n else vof.data_ptr(), run.cuda_stream)
     return out if return_voxel_of or out.voxel_of is None else VoxelBatch(out.voxels, out.coords, out.num_points, out.voxel_offsets)
+
+
+class KeypointBatch:
+    """What sample_keypoints() leaves behind, F = frames, K = n_samples, C = num_features -- every shape static: `index` (F, K int32: the
+    sampled rows as indices into the whole batch, so rows[index] gathers; -1 for a frame without a usable row), `points` (F, K, C; the
+    rows' dtype; zero for such a frame), `usable` (F int32, ON THE DEVICE: the usable rows of every frame -- beyond them a frame's samples
+    repeat its first usable row) and `dist` (F, K; the rows' dtype: the squared distance of every sample to the samples before it at the
+    moment it was chosen, +inf for the first, -1 for a frame without a usable row; None unless asked for).  All still being written until
+    the stream the call was made on has caught up."""
+
+    def __init__(self, index, points, usable, dist=None):
+        self.index, self.points, self.usable, self.dist = index, points, usable, dist
+
+    @classmethod
+    def empty(cls, n_frames, n_samples, num_features=4, dtype=None, device=None, with_dist=False):
+        """Uninitialised buffers of the shapes sample_keypoints() writes for such a call (out=): static addresses for a captured graph."""
+        import torch
+        dev = torch.device("cuda", torch.cuda.current_device() if device is None else int(device)) if not isinstance(device, torch.device) else device
+        F, K, dt = int(n_frames), int(n_samples), dtype or torch.float32
+        return cls(torch.empty((F, K), dtype=torch.int32, device=dev), torch.empty((F, K, int(num_features)), dtype=dt, device=dev),
+                   torch.empty(F, dtype=torch.int32, device=dev), torch.empty((F, K), dtype=dt, device=dev) if with_dist else None)
+
+
+def sample_keypoints(frames, n_samples, *, point_cloud_range=None, keep=None, num_features=4, out=None, return_dist=False, device=None, slot=0):
+    """Farthest point sampling on the device (snowgpu_fps_device; the definition: include/snowgpu.h): the keypoints of PV-RCNN and the
+    fixed-size point set of PointRCNN / Part-A2, with static shapes.  Per frame, among the rows that are present, within 1e6 of the origin
+    on every axis and inside point_cloud_range (x0, y0, z0, x1, y1, z1; None: no range), the first is taken, then n_samples - 1 times the
+    row farthest from everything taken so far (squared distance in the rows' dtype; the smallest row index among equals).
+
+    frames    what voxelize takes -- torch CUDA tensors, a DeviceBatch, or an AlignedResult / AlignedWetResult: its rows, offsets and keep
+              mask are used (nothing is waited for).
+    keep      an input keep mask as the aligned calls take it (with a result: ANDed with the result's own).
+    out       a KeypointBatch to write into (KeypointBatch.empty): every element is written, nothing needs clearing.
+    return_dist   also fill `dist`.
+
+    Returns a KeypointBatch.  Asynchronous on torch's current stream; nothing is read on the host: capturable after one warm-up call."""
+    import torch
+    if isinstance(frames, AlignedResult):
+        res = frames
+        own = res.keep if res.keep.dtype == torch.bool else res.keep.view(torch.bool)
+        frames = DeviceBatch(res.rows, res.offsets)
+        keep = own if keep is None else (_keep_mask(torch, keep, res.rows, res.offsets) & own)
+    if not is_device_input(frames):
+        raise ValueError("sample_keypoints: torch CUDA tensors or an aligned result (host arrays: lidar_snow_sim_amd.fps.farthest_point_sample)")
+    for name, v in (("n_samples", n_samples), ("num_features", num_features)):
+        if isinstance(v, bool) or int(v) != v:
+            raise ValueError(f"sample_keypoints: {name} must be an integer")
+    rng = None
+    if point_cloud_range is not None:
+        rng = np.asarray(point_cloud_range, np.float64).reshape(-1)
+        if rng.shape != (6,):
+            raise ValueError("sample_keypoints: point_cloud_range holds 6 numbers (x0, y0, z0, x1, y1, z1)")
+    rows, offsets, _, eng = _resolve_input(torch, frames, False, device, slot)
+    dev = rows.device
+    nf, n = len(offsets) - 1, int(offsets[-1])
+    K, C = int(n_samples), int(num_features)
+    if keep is not None:
+        keep = _keep_mask(torch, keep, rows, offsets)
+    # (the shapes below need these; the entry refuses them in the same words, and everything else of the domain)
+    if not 3 <= C <= 5:
+        raise ValueError("sample_keypoints: n_features must be 3, 4 or 5: the columns of a row that a keypoint carries")
+    if K < 1:
+        raise ValueError("sample_keypoints: n_samples must be at least 1")
+    if nf * K > 2 ** 31 - 1:
+        raise ValueError("sample_keypoints: n_frames * n_samples exceeds 2^31 - 1; split the batch")
+    if out is None:
+        out = KeypointBatch.empty(nf, K, C, rows.dtype, dev, return_dist)
+    else:
+        want = (("index", (nf, K), torch.int32), ("points", (nf, K, C), rows.dtype), ("usable", (nf,), torch.int32)) + \
+               ((("dist", (nf, K), rows.dtype),) if return_dist else ())
+        for name, shape, dtype in want:
+            t = getattr(out, name, None) if isinstance(out, KeypointBatch) else None
+            if not (torch.is_tensor(t) and tuple(t.shape) == shape and t.dtype == dtype and t.is_contiguous() and t.device == dev):
+                raise ValueError(f"sample_keypoints: out must be a KeypointBatch whose {name} is a contiguous {tuple(shape)} {dtype} tensor on the device of the rows")
+    dist = out.dist if return_dist else None
+    up = _uploads(eng)
+    with torch.cuda.device(dev), _on_run_stream(torch, eng, dev) as (_, run):
+        d_off = up.get(torch, dev, offsets, run)
+        eng.ctx.fps_device(nf, n, int(np.diff(offsets).max()), d_off.data_ptr(), rows.data_ptr() if n else 0, 0 if rows.dtype == torch.float32 else 1,
+                           rng, K, C, 0 if keep is None or not n else keep.data_ptr(), out.index.data_ptr(), out.points.data_ptr(),
+                           0 if dist is None else dist.data_ptr(), out.usable.data_ptr(), run.cuda_stream)
+    return out if return_dist or out.dist is None else KeypointBatch(out.index, out.points, out.usable)
 
 
 def augment_batch(frames, particle_file_prefix, beam_divergence, shuffle=True, noise_floor=0.7, root_path=None, *, planes=None,
