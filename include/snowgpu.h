@@ -687,6 +687,46 @@ int snowgpu_fps_device(snowgpu_ctx *ctx, int n_frames, int64_t n_total, int64_t 
                        void *d_out_points /* or NULL */, void *d_out_dist /* or NULL */, int32_t *d_out_usable, void *stream);
 
 /*
+ * BALL-QUERY NEIGHBOUR GROUPS around centres of an aligned batch: for every centre the first rows of its frame within a radius, the
+ * grouping step of PV-RCNN's voxel set abstraction over the raw points and of the PointNet++ set-abstraction layers, with static shapes.
+ * Frames, rows (N_total x 5, float32 or float64), frame offsets and the input keep mask as snowgpu_fps_device takes them.  F = n_frames,
+ * K = n_centres per frame, R = n_radii (radius, samples) pairs, 1 <= R <= 4, S_i = n_samples[i], 1 <= S_i <= 64, S = sum of the S_i,
+ * C = n_features in 3 .. 5.  The reference has no such op; the edge conventions are this library's, restated as brute-force NumPy by
+ * tests/ball_reference.py, and chosen so that on ordinary data the result is what the pointnet2 ball_query op returns.
+ *   A row is USABLE exactly as for snowgpu_fps_device: present, |x|, |y|, |z| <= 1e6 (false for NaN) and, with a range,
+ *   lo_j <= (double)p_j < hi_j.  range6 may be NULL.
+ *   CENTRES: d_centres is (F, K, Cq) in the rows' dtype, Cq = centre_features in 3 .. 5, columns 0 .. 2 x, y, z (the points of the
+ *   keypoint stage go in as they are).  A centre is usable iff |x|, |y|, |z| <= 1e6; it need not lie in the range or be a row.
+ *   MEMBERSHIP: all arithmetic in the rows' dtype T.  d = ((dx dx) + (dy dy)) + (dz dz), every operation rounded on its own, no fused
+ *   multiply-add; r2_i = fl_T(fl_T(radius_i) fl_T(radius_i)).  Usable row j of frame f is in ball i of usable centre (f, k) iff
+ *   d < r2_i: STRICT, as in the pointnet2 op.  A keypoint is in its own ball, a row at d == r2_i is out.  No square root takes part.
+ *   RESULT: n = the rows in the ball.  count[f, k, i] = n, not saturated.  Slots 0 .. min(n, S_i) - 1 of the centre's segment i hold the
+ *   min(n, S_i) SMALLEST batch row indices in the ball, ascending; the remaining slots repeat slot 0 (pointnet2's padding).  With n = 0,
+ *   or an unusable centre, every slot is -1 and count is 0.  This is what a sequential walk in input order with an early stop returns;
+ *   it depends on neither a cell order nor the arrival of atomics: two calls give identical bytes.
+ * Outputs, every shape static, every element written by every call:
+ *   d_out_index   (F, K, S) int32: the segments of the R pairs side by side
+ *   d_out_count   (F, K, R) int32
+ *   d_out_points  (F, K, S, C) in the rows' dtype, or NULL: columns 0 .. C - 1 of the indexed row, bit for bit; zero where the index is -1
+ * Domain: radii finite, > 0 and <= 1e6; K >= 1 (K = 0 is refused: a call without a centre has nothing to write); F K S <= 2^31 - 1;
+ * n_total < 2^31; no frame above 2^30 rows; dtype 0 or 1; the range as for snowgpu_fps_device; the outputs must not overlap the rows,
+ * the keep mask or the centres.  Anything else is SNOWGPU_E_INVALID.  An empty batch writes index = -1, count = 0 and points = 0 with
+ * one fill kernel (d_rows may be NULL).
+ * The usable rows of every frame are filed in a uniform x-y grid (cell lists as snowgpu_dror_mask_device builds them; csrc/sg_ball.h:
+ * the domain, the cell edge -- half the largest radius, wider where the cell budget asks for it -- and the window of a centre), then ONE
+ * WAVE per centre walks the grid rows of its window, computes every distance once for all radii and keeps per pair its 64 smallest
+ * indices in one register per lane by a bitonic sort and merge across the wave (csrc/snowgpu_ball.hip).
+ * Scratch in the context, grown on first use: per frame one word per cell of the budget (1024 .. 81920) and one more, and per row two
+ * words and three values of the rows' dtype.  One memset and four kernels on `stream`; nothing is read on the host, nothing allocated
+ * after the first call of a size: capturable.
+ */
+int snowgpu_ball_query_device(snowgpu_ctx *ctx, int n_frames, int64_t n_total, int64_t max_frame_rows, const int64_t *d_frame_offsets,
+                              const void *d_rows, int dtype, const double *range6 /* host: x0 y0 z0 x1 y1 z1, or NULL */, int n_centres,
+                              const void *d_centres, int centre_features, int n_radii, const double *radii /* host */,
+                              const int *n_samples /* host */, int n_features, const uint8_t *d_keep_in /* or NULL: all present */,
+                              int32_t *d_out_index, int32_t *d_out_count, void *d_out_points /* or NULL */, void *stream);
+
+/*
  * PER-FRAME WEATHER in one aligned call.  snowgpu_augment_wet_batch_device_aligned_masked applies one weather to every frame, its wet
  * settings host scalars that a captured graph bakes in.  Here every frame brings a record of 8 doubles in DEVICE memory,
  *     d_weather[f] = [snow, wet, water_height, pavement_depth, wet_noise_floor, power_factor, delta, 0]

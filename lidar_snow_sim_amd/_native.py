@@ -30,7 +30,7 @@ EXPORTS = [
     "snowgpu_augment_batch_device_aligned", "snowgpu_wet_ground_batch_device_aligned", "snowgpu_augment_wet_batch_device_aligned",
     "snowgpu_augment_batch_device_aligned_masked", "snowgpu_augment_wet_batch_device_aligned_masked", "snowgpu_fov_mask_device",
     "snowgpu_augment_weather_batch_device_aligned", "snowgpu_draw_weather_device", "snowgpu_dror_mask_device",
-    "snowgpu_voxelize_device", "snowgpu_fps_device",
+    "snowgpu_voxelize_device", "snowgpu_fps_device", "snowgpu_ball_query_device",
 ]
 
 WET_ESTIMATION = {"linear": 0, "poly": 1}
@@ -146,6 +146,9 @@ def lib():
                                                   vp, vp, vp, vp, vp, vp, vp]
             L.snowgpu_fps_device.restype = ctypes.c_int
             L.snowgpu_fps_device.argtypes = [vp, ctypes.c_int, i64, i64, vp, vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp, vp]
+            L.snowgpu_ball_query_device.restype = ctypes.c_int
+            L.snowgpu_ball_query_device.argtypes = [vp, ctypes.c_int, i64, i64, vp, vp, ctypes.c_int, vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, vp, vp,
+                                                    ctypes.c_int, vp, vp, vp, vp, vp]
             L.snowgpu_set_fov_precrop.restype = ctypes.c_int
             L.snowgpu_set_fov_precrop.argtypes = [vp, ctypes.c_int]
             L.snowgpu_last_status.restype = ctypes.c_int
@@ -554,6 +557,30 @@ class Context:
                                         int(dtype_code), None if rng is None else _p(rng), i32(n_samples), i32(n_features), vp(d_keep_in or None),
                                         vp(d_out_index or None), vp(d_out_points or None), vp(d_out_dist or None), vp(d_out_usable or None),
                                         vp(stream or None))
+        if rc == E_INVALID:
+            raise ValueError(self._L.snowgpu_last_error(self._h).decode())
+        self._check(rc)
+
+    def ball_query_device(self, n_frames, n_total, max_frame_rows, d_frame_off, d_rows, dtype_code, point_cloud_range, n_centres, d_centres,
+                          centre_features, radii, n_samples, n_features, d_keep_in, d_out_index, d_out_count, d_out_points, stream=0):
+        """Ball-query neighbour groups around centres (include/snowgpu.h: snowgpu_ball_query_device); asynchronous on `stream`.
+        point_cloud_range: 6 numbers or None; radii and n_samples: sequences of equal length.  An argument outside the domain, or an
+        output overlapping the mask, the rows or the centres, raises ValueError with the entry's words."""
+        vp = ctypes.c_void_p
+        rng = None
+        if point_cloud_range is not None:
+            rng = np.ascontiguousarray(point_cloud_range, np.float64).reshape(-1)
+            if rng.shape != (6,):
+                raise ValueError("snowgpu_ball_query_device: point_cloud_range holds 6 numbers (x0, y0, z0, x1, y1, z1)")
+        i32 = lambda v: max(-(2 ** 31), min(int(v), 2 ** 31 - 1))
+        rad = np.ascontiguousarray(radii, np.float64).reshape(-1)
+        ns = np.ascontiguousarray([i32(v) for v in n_samples], np.int32).reshape(-1)
+        if len(rad) != len(ns):
+            raise ValueError("snowgpu_ball_query_device: as many radii as sample counts")
+        rc = self._L.snowgpu_ball_query_device(self._h, int(n_frames), int(n_total), int(max_frame_rows), vp(d_frame_off or None), vp(d_rows or None),
+                                               int(dtype_code), None if rng is None else _p(rng), i32(n_centres), vp(d_centres or None),
+                                               i32(centre_features), len(rad), _p(rad), _p(ns), i32(n_features), vp(d_keep_in or None),
+                                               vp(d_out_index or None), vp(d_out_count or None), vp(d_out_points or None), vp(stream or None))
         if rc == E_INVALID:
             raise ValueError(self._L.snowgpu_last_error(self._h).decode())
         self._check(rc)

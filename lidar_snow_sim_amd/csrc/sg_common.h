@@ -192,7 +192,7 @@ struct SgFov {
 
 // Launch wrappers (hipStream_t passed as void*), each implemented in the file that defines its kernels: snowgpu_sort.hip (expand_rows, sort,
 // gather_rows, segments*, resolve_tables), snowgpu_kernels.hip (beams, power*, tier_*, huge, sg_beams_block), snowgpu_rows.hip (rows),
-// snowgpu_compact.hip (compact, crop_*), snowgpu_mask.hip (mask_front, finish_aligned_masked, fov_mask), snowgpu_dror.hip (dror), snowgpu_voxel.hip (voxelize), snowgpu_fps.hip (fps).  Every one of these files includes this header, so a definition cannot drift from its declaration.
+// snowgpu_compact.hip (compact, crop_*), snowgpu_mask.hip (mask_front, finish_aligned_masked, fov_mask), snowgpu_dror.hip (dror), snowgpu_voxel.hip (voxelize), snowgpu_fps.hip (fps), snowgpu_ball.hip (ball).  Every one of these files includes this header, so a definition cannot drift from its declaration.
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -286,6 +286,14 @@ struct SgFpsRange;
 int sg_launch_fps(const void *rows, int dtype, int64_t n, const int64_t *frame_off, int n_frames, const uint8_t *keep_in, const struct SgFpsRange *range,
                   int32_t n_samples, int32_t n_features, void *sx, void *sy, void *sz, void *st, int32_t *ssrc, int32_t *out_index, void *out_points,
                   void *out_dist, int32_t *out_usable, void *stream);
+// Ball query around centres (sg_ball.h; the definition: include/snowgpu.h): a memset and four kernels.  Scratch: entry,
+// sg_ball_entries(n_frames, g->cells) words; cell_of and ssrc, sg_ball_scratch(n) words; sx, sy, sz as many values of the rows' dtype.
+// out_points may be null.
+struct SgBallGrid;
+int sg_launch_ball(const void *rows, int dtype, int64_t n, const int64_t *frame_off, int n_frames, const uint8_t *keep_in, const struct SgFpsRange *range,
+                   const struct SgBallGrid *g, int32_t n_centres, const void *centres, int32_t centre_features, int n_radii, const double *radii,
+                   const int *n_samples, int32_t n_features, uint32_t *entry, uint32_t *cell_of, void *sx, void *sy, void *sz, int32_t *ssrc,
+                   int32_t *out_index, int32_t *out_count, void *out_points, void *stream);
 #ifdef __cplusplus
 }
 #endif

@@ -222,6 +222,72 @@ static inline int sg_check_fps_args(const SgFpsArgs &a, std::string *msg)
     return 0;
 }
 
+// ---- snowgpu_ball_query_device ------------------------------------------------------------------------------------------------------------
+struct SgBallArgs {
+    int n_frames;
+    int64_t n_total, max_frame_rows;
+    int dtype;
+    const int64_t *frame_off;
+    const void *rows;
+    const double *range6;             // (x0, y0, z0, x1, y1, z1), host memory, or NULL: no range test
+    int n_centres;                    // K, per frame
+    const void *centres;
+    int centre_features;              // Cq
+    int n_radii;                      // R
+    const double *radii;              // host memory
+    const int *n_samples;             // host memory
+    int n_features;                   // C
+    const uint8_t *keep_in;
+    int32_t *out_index, *out_count;
+    void *out_points;                 // or NULL
+    int64_t max_cells;                // cells per frame that the grid may take (the cell budget of the batch)
+};
+
+// 0, or SG_ARGS_INVALID with *msg.  As above, the order is part of the ABI.  *total = the sum of the samples where the call is accepted.
+static inline int sg_check_ball_args(const SgBallArgs &a, int64_t *total, std::string *msg)
+{
+    static const char *who = "snowgpu_ball_query_device";
+    if (a.n_frames <= 0 || a.n_total < 0 || !a.frame_off || !a.centres || !a.radii || !a.n_samples || !a.out_index || !a.out_count ||
+        (a.n_total > 0 && !a.rows) || (a.dtype != 0 && a.dtype != 1))
+        return sg_refuse(who, ": null pointer or bad dtype", msg);
+    if (a.n_total >= ((int64_t)1 << 31)) return sg_refuse("", "batch too large: split it below 2^31 rows", msg);
+    if (a.n_features < 3 || a.n_features > 5) return sg_refuse(who, ": n_features must be 3, 4 or 5: the columns of a row that a neighbour carries", msg);
+    if (a.centre_features < 3 || a.centre_features > 5) return sg_refuse(who, ": centre_features must be 3, 4 or 5: x, y, z first", msg);
+    if (a.n_centres < 1) return sg_refuse(who, ": n_centres must be at least 1", msg);
+    if (a.n_radii < 1 || a.n_radii > 4) return sg_refuse(who, ": n_radii must lie in 1 .. 4", msg);
+    int64_t S = 0;
+    for (int i = 0; i < a.n_radii; ++i) {
+        if (!(a.radii[i] > 0.0 && a.radii[i] <= 1e6)) return sg_refuse(who, ": a radius must be finite, above 0 and at most 1e6", msg);
+        if (a.n_samples[i] < 1 || a.n_samples[i] > 64) return sg_refuse(who, ": the samples of a radius must lie in 1 .. 64", msg);
+        S += a.n_samples[i];
+    }
+    if ((int64_t)a.n_frames * a.n_centres > (((int64_t)1 << 31) - 1) / S)      // (F K S <= 2^31 - 1, without the product of three)
+        return sg_refuse(who, ": n_frames * n_centres * samples exceeds 2^31 - 1; split the batch", msg);
+    if (sg_max_frame(a.max_frame_rows, a.n_total) > ((int64_t)1 << 30))
+        return sg_refuse(who, ": a frame of more than 2^30 rows; split it", msg);
+    if ((int64_t)a.n_frames * (a.max_cells + 1) >= ((int64_t)1 << 31)) return sg_refuse(who, ": too many frames for the cell lists; split the batch", msg);
+    if (a.range6) {
+        for (int j = 0; j < 6; ++j)
+            if (a.range6[j] != a.range6[j]) return sg_refuse(who, ": a bound of the range is NaN; pass NULL for no range, or infinite bounds", msg);
+        for (int j = 0; j < 3; ++j)
+            if (!(a.range6[j] < a.range6[3 + j])) return sg_refuse(who, ": the range needs lo < hi on every axis", msg);
+    }
+    const size_t esz = a.dtype == 0 ? 4 : 8, q = (size_t)a.n_frames * (size_t)a.n_centres, n = (size_t)a.n_total;
+    const struct { const void *p; size_t bytes; const char *name; } outs[3] = {
+        {a.out_index, q * (size_t)S * 4, "d_out_index"}, {a.out_count, q * (size_t)a.n_radii * 4, "d_out_count"},
+        {a.out_points, q * (size_t)S * (size_t)a.n_features * esz, "d_out_points"}};
+    for (const auto &o : outs) {
+        if (sg_ranges_meet(o.p, o.bytes, a.keep_in, n))
+            return sg_refuse(who, (std::string(": ") + o.name + " overlaps d_keep_in; the mask is read while the groups are written: pass a buffer apart from it").c_str(), msg);
+        if (sg_ranges_meet(o.p, o.bytes, a.rows, n * 5 * esz))
+            return sg_refuse(who, (std::string(": ") + o.name + " overlaps d_rows; the rows are read while the groups are written: pass a buffer apart from them").c_str(), msg);
+        if (sg_ranges_meet(o.p, o.bytes, a.centres, q * (size_t)a.centre_features * esz))
+            return sg_refuse(who, (std::string(": ") + o.name + " overlaps d_centres; the centres are read while the groups are written: pass a buffer apart from them").c_str(), msg);
+    }
+    if (total) *total = S;
+    return 0;
+}
+
 // 0, or SG_ARGS_INVALID with *msg (built on this path only).  The order is part of the ABI: it decides which message a doubly wrong call gets.
 static inline int sg_check_device_args(const SgDeviceArgs &a, const SgCtxView &c, const SgEntryShape &s, std::string *msg)
 {

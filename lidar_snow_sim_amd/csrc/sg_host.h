@@ -93,6 +93,11 @@ struct __attribute__((visibility("default"))) snowgpu_ctx {
     // minimum t as four arrays in the rows' dtype -- and their source rows
     DevBuf<uint8_t> fps_x, fps_y, fps_z, fps_t;
     DevBuf<int32_t> fps_src;
+    // ball query (snowgpu_ball_query_device): the cell lists of every frame -- first positions, the cell of every row -- and the usable
+    // rows sorted by cell: x, y, z as three arrays in the rows' dtype and their source rows
+    DevBuf<uint32_t> ball_entry, ball_cell;
+    DevBuf<uint8_t> ball_x, ball_y, ball_z;
+    DevBuf<int32_t> ball_src;
     // scratch shared by every batch
     DevBuf<int32_t> tile_hist, tile_base, perm, ctile_cnt, ctile_base, table_ids, out_src;
     DevBuf<uint8_t> srows;            // channel-sorted copy of the frames whose rows did not come channel-sorted (firing order)

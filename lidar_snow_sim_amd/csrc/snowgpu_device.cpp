@@ -1,5 +1,5 @@
 // snowgpu_device.cpp -- the entries of the C ABI (include/snowgpu.h) that take DEVICE pointers and enqueue on the caller's stream: every
-// *_batch_device* entry, the plane estimate, the FOV mask, the outlier filter, the voxel stage, the keypoint stage and the weather draw.  Each batch entry fills an SgDeviceArgs, has it checked
+// *_batch_device* entry, the plane estimate, the FOV mask, the outlier filter, the voxel stage, the keypoint stage, the ball query and the weather draw.  Each batch entry fills an SgDeviceArgs, has it checked
 // (sg_device_args.h: every refusal, in one order), sets the device and runs batch_from_args() and the stages it needs.  The launch
 // sequence of a batch is snowgpu_batch.cpp; no host copy, no synchronisation, no allocation after the first call of a given size.
 #include "sg_host.h"
@@ -8,6 +8,7 @@
 #include "sg_dror.h"        // the grid of the outlier filter and its domain
 #include "sg_voxel.h"       // the grid of the voxel stage and the capacity of its tables
 #include "sg_fps.h"         // the range of the keypoint stage and the size of its scratch
+#include "sg_ball.h"        // the grid of the ball query and the sizes of its scratch
 
 static_assert(SG_ARGS_INVALID == SNOWGPU_E_INVALID && SG_PLANE_REFERENCE == 0, "sg_device_args.h restates these two");
 
@@ -463,6 +464,41 @@ extern "C" int snowgpu_fps_device(snowgpu_ctx *ctx, int n_frames, int64_t n_tota
     int e = sg_launch_fps(d_rows, dtype, n_total, d_frame_offsets, n_frames, d_keep_in, &r, n_samples, n_features, ctx->fps_x.p, ctx->fps_y.p, ctx->fps_z.p,
                           ctx->fps_t.p, ctx->fps_src.p, d_out_index, d_out_points, d_out_dist, d_out_usable, stream ? (hipStream_t)stream : ctx->stream);
     if (e) return fail(ctx, SNOWGPU_E_HIP, std::string("fps launch: ") + hipGetErrorString((hipError_t)e));
+    return SNOWGPU_OK;
+}
+
+// Ball-query neighbour groups around centres (snowgpu_ball.hip; the grid, the window and the selection: sg_ball.h).  See include/snowgpu.h.
+extern "C" int snowgpu_ball_query_device(snowgpu_ctx *ctx, int n_frames, int64_t n_total, int64_t max_frame_rows, const int64_t *d_frame_offsets,
+                                         const void *d_rows, int dtype, const double *range6, int n_centres, const void *d_centres, int centre_features,
+                                         int n_radii, const double *radii, const int *n_samples, int n_features, const uint8_t *d_keep_in,
+                                         int32_t *d_out_index, int32_t *d_out_count, void *d_out_points, void *stream)
+{
+    if (!ctx) return SNOWGPU_E_INVALID;
+    const int32_t budget = sg_ball_cell_budget(sg_max_frame(max_frame_rows, n_total));
+    const SgBallArgs a{n_frames, n_total, max_frame_rows, dtype, d_frame_offsets, d_rows, range6, n_centres, d_centres, centre_features, n_radii, radii,
+                       n_samples, n_features, d_keep_in, d_out_index, d_out_count, d_out_points, budget};
+    {
+        std::string msg;
+        if (int rc = sg_check_ball_args(a, nullptr, &msg)) return fail(ctx, rc, msg);
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    SgFpsRange r;
+    for (int j = 0; j < 3; ++j) { r.lo[j] = range6 ? range6[j] : -INFINITY; r.hi[j] = range6 ? range6[3 + j] : INFINITY; }
+    SgBallGrid g{};
+    sg_ball_make_grid(range6, n_radii, radii, budget, &g);
+    if (n_total > 0) {
+        const size_t elems = sg_ball_scratch(n_total), bytes = elems * (dtype == 0 ? 4 : 8);
+        ENSURE(ctx, ctx->ball_entry, sg_ball_entries(n_frames, budget));      // (by the budget, not the grid: the radii change no allocation)
+        ENSURE(ctx, ctx->ball_cell, elems);
+        ENSURE(ctx, ctx->ball_x, bytes);
+        ENSURE(ctx, ctx->ball_y, bytes);
+        ENSURE(ctx, ctx->ball_z, bytes);
+        ENSURE(ctx, ctx->ball_src, elems);
+    }
+    int e = sg_launch_ball(d_rows, dtype, n_total, d_frame_offsets, n_frames, d_keep_in, &r, &g, n_centres, d_centres, centre_features, n_radii, radii, n_samples,
+                           n_features, ctx->ball_entry.p, ctx->ball_cell.p, ctx->ball_x.p, ctx->ball_y.p, ctx->ball_z.p, ctx->ball_src.p, d_out_index, d_out_count,
+                           d_out_points, stream ? (hipStream_t)stream : ctx->stream);
+    if (e) return fail(ctx, SNOWGPU_E_HIP, std::string("ball query launch: ") + hipGetErrorString((hipError_t)e));
     return SNOWGPU_OK;
 }
 

@@ -23,6 +23,8 @@ The reference's training-time caller (the OpenPCDet DENSE dataset: `root_path`, 
     voxels of static shape (VoxelBatch; snowgpu_voxelize_device): the hand-off to a detector's first operation, in the same stream or graph.
   * `sample_keypoints(frames_or_result, n_samples)` takes a fixed number of farthest-point samples from the present rows of every frame
     (KeypointBatch; snowgpu_fps_device): the hand-off to a point-based detector, likewise.
+  * `ball_query(frames_or_result, centres, radius, n_neighbours)` groups, around every centre (a KeypointBatch, or any centres), the
+    first rows of its frame within each radius (NeighbourBatch; snowgpu_ball_query_device): the grouping step of a set-abstraction layer.
   * `augment_wet_batch_aligned(frames, ...)` is the snowfall + wet-ground chain with that aligned result (AlignedWetResult: per-frame
     flags beside it; snowgpu_augment_wet_batch_device_aligned), `wet_ground_batch_aligned(frames, keep)` the wet-ground stage alone on rows
     and a keep mask from any earlier stage (snowgpu_wet_ground_batch_device_aligned).
@@ -740,6 +742,106 @@ def sample_keypoints(frames, n_samples, *, point_cloud_range=None, keep=None, nu
                            rng, K, C, 0 if keep is None or not n else keep.data_ptr(), out.index.data_ptr(), out.points.data_ptr(),
                            0 if dist is None else dist.data_ptr(), out.usable.data_ptr(), run.cuda_stream)
     return out if return_dist or out.dist is None else KeypointBatch(out.index, out.points, out.usable)
+
+
+class NeighbourBatch:
+    """What ball_query() leaves behind, F = frames, K = centres per frame, R = (radius, samples) pairs, S = the sum of their samples,
+    C = num_features -- every shape static: `index` (F, K, S int32: per centre the segments of the R pairs side by side, each the smallest
+    row indices of the ball, ascending, as indices into the whole batch, padded with its first; -1 for an empty ball), `count` (F, K, R
+    int32: the rows in every ball, not saturated), `points` (F, K, S, C; the rows' dtype; zero where the index is -1; None unless asked
+    for) and `segments` (the samples of every pair, a tuple: index[..., sum(segments[:i]):sum(segments[:i + 1])] is pair i).  All still
+    being written until the stream the call was made on has caught up."""
+
+    def __init__(self, index, count, points=None, segments=()):
+        self.index, self.count, self.points, self.segments = index, count, points, tuple(int(s) for s in segments)
+
+    @classmethod
+    def empty(cls, n_frames, n_centres, n_neighbours, num_features=4, dtype=None, device=None, with_points=False):
+        """Uninitialised buffers of the shapes ball_query() writes for such a call (out=): static addresses for a captured graph."""
+        import torch
+        dev = torch.device("cuda", torch.cuda.current_device() if device is None else int(device)) if not isinstance(device, torch.device) else device
+        seg = tuple(int(s) for s in (n_neighbours if isinstance(n_neighbours, (tuple, list, np.ndarray)) else (n_neighbours,)))
+        F, K, S = int(n_frames), int(n_centres), sum(seg)
+        return cls(torch.empty((F, K, S), dtype=torch.int32, device=dev), torch.empty((F, K, len(seg)), dtype=torch.int32, device=dev),
+                   torch.empty((F, K, S, int(num_features)), dtype=dtype or torch.float32, device=dev) if with_points else None, seg)
+
+
+def ball_query(frames, centres, radius, n_neighbours, *, point_cloud_range=None, keep=None, num_features=4, out=None, return_points=False,
+               device=None, slot=0):
+    """Ball-query neighbour groups on the device (snowgpu_ball_query_device; the definition: include/snowgpu.h): for every centre the
+    n_neighbours smallest row indices of its frame among the rows that are present, within 1e6 of the origin on every axis, inside
+    point_cloud_range (None: no range) and STRICTLY within `radius` of the centre (squared distance in the rows' dtype), ascending and
+    padded with the first -- what the pointnet2 ball_query op returns --, -1 for an empty ball, and the full number of rows in the ball.
+
+    frames    what sample_keypoints takes -- torch CUDA tensors, a DeviceBatch, or an AlignedResult / AlignedWetResult: its rows, offsets
+              and keep mask are used (nothing is waited for).
+    centres   a KeypointBatch (its points), or an (F, K, 3 .. 5) tensor in the rows' dtype on their device: x, y, z first.
+    radius, n_neighbours   scalars, or sequences of equal length <= 4: several balls per centre from one walk, side by side in `index`.
+    keep      an input keep mask as the aligned calls take it (with a result: ANDed with the result's own).
+    out       a NeighbourBatch to write into (NeighbourBatch.empty): every element is written, nothing needs clearing.
+    return_points   also fill `points` with the first num_features columns of the indexed rows.
+
+    Returns a NeighbourBatch.  Asynchronous on torch's current stream; nothing is read on the host: capturable after one warm-up call."""
+    import torch
+    if isinstance(frames, AlignedResult):
+        res = frames
+        own = res.keep if res.keep.dtype == torch.bool else res.keep.view(torch.bool)
+        frames = DeviceBatch(res.rows, res.offsets)
+        keep = own if keep is None else (_keep_mask(torch, keep, res.rows, res.offsets) & own)
+    if not is_device_input(frames):
+        raise ValueError("ball_query: torch CUDA tensors or an aligned result (host arrays: lidar_snow_sim_amd.ball.ball_query)")
+    seq = lambda v: list(v) if isinstance(v, (tuple, list, np.ndarray)) else [v]
+    radii, seg = seq(radius), seq(n_neighbours)
+    if len(radii) != len(seg):
+        raise ValueError("ball_query: as many radii as sample counts")
+    for name, v in (("num_features", num_features),) + tuple(("n_neighbours", s) for s in seg):
+        if isinstance(v, bool) or int(v) != v:
+            raise ValueError(f"ball_query: {name} must be an integer")
+    rng = None
+    if point_cloud_range is not None:
+        rng = np.asarray(point_cloud_range, np.float64).reshape(-1)
+        if rng.shape != (6,):
+            raise ValueError("ball_query: point_cloud_range holds 6 numbers (x0, y0, z0, x1, y1, z1)")
+    rows, offsets, _, eng = _resolve_input(torch, frames, False, device, slot)
+    dev = rows.device
+    nf, n = len(offsets) - 1, int(offsets[-1])
+    if keep is not None:
+        keep = _keep_mask(torch, keep, rows, offsets)
+    cen = centres.points if isinstance(centres, KeypointBatch) else centres
+    if not (torch.is_tensor(cen) and cen.dim() == 3 and cen.shape[0] == nf and cen.dtype == rows.dtype and cen.device == dev and cen.is_contiguous()):
+        raise ValueError("ball_query: centres must be a KeypointBatch or a contiguous (frames, K, 3 .. 5) tensor in the rows' dtype on their device")
+    K, Cq, C, R = int(cen.shape[1]), int(cen.shape[2]), int(num_features), len(radii)
+    seg = [int(s) for s in seg]
+    # (the shapes below need these; the entry refuses them in the same words, and everything else of the domain)
+    if not 3 <= C <= 5:
+        raise ValueError("ball_query: n_features must be 3, 4 or 5: the columns of a row that a neighbour carries")
+    if not 3 <= Cq <= 5:
+        raise ValueError("ball_query: centre_features must be 3, 4 or 5: x, y, z first")
+    if K < 1:
+        raise ValueError("ball_query: n_centres must be at least 1")
+    if not 1 <= R <= 4:
+        raise ValueError("ball_query: n_radii must lie in 1 .. 4")
+    if any(not 1 <= s <= 64 for s in seg):
+        raise ValueError("ball_query: the samples of a radius must lie in 1 .. 64")
+    S = sum(seg)
+    if nf * K * S > 2 ** 31 - 1:
+        raise ValueError("ball_query: n_frames * n_centres * samples exceeds 2^31 - 1; split the batch")
+    if out is None:
+        out = NeighbourBatch.empty(nf, K, seg, C, rows.dtype, dev, return_points)
+    else:
+        want = (("index", (nf, K, S), torch.int32), ("count", (nf, K, R), torch.int32)) + ((("points", (nf, K, S, C), rows.dtype),) if return_points else ())
+        for name, shape, dtype in want:
+            t = getattr(out, name, None) if isinstance(out, NeighbourBatch) else None
+            if not (torch.is_tensor(t) and tuple(t.shape) == shape and t.dtype == dtype and t.is_contiguous() and t.device == dev):
+                raise ValueError(f"ball_query: out must be a NeighbourBatch whose {name} is a contiguous {tuple(shape)} {dtype} tensor on the device of the rows")
+    points = out.points if return_points else None
+    up = _uploads(eng)
+    with torch.cuda.device(dev), _on_run_stream(torch, eng, dev) as (_, run):
+        d_off = up.get(torch, dev, offsets, run)
+        eng.ctx.ball_query_device(nf, n, int(np.diff(offsets).max()), d_off.data_ptr(), rows.data_ptr() if n else 0, 0 if rows.dtype == torch.float32 else 1,
+                                  rng, K, cen.data_ptr(), Cq, radii, seg, C, 0 if keep is None or not n else keep.data_ptr(), out.index.data_ptr(),
+                                  out.count.data_ptr(), 0 if points is None else points.data_ptr(), run.cuda_stream)
+    return NeighbourBatch(out.index, out.count, points, seg) if (out.segments != tuple(seg) or (points is None) != (out.points is None)) else out
 
 
 def augment_batch(frames, particle_file_prefix, beam_divergence, shuffle=True, noise_floor=0.7, root_path=None, *, planes=None,
