@@ -727,6 +727,52 @@ int snowgpu_ball_query_device(snowgpu_ctx *ctx, int n_frames, int64_t n_total, i
                               int32_t *d_out_index, int32_t *d_out_count, void *d_out_points /* or NULL */, void *stream);
 
 /*
+ * RANGE-IMAGE PROJECTION of an aligned batch: every frame as an H x W image of its nearest returns, the first stage of the range-view
+ * networks (RangeNet++, SalsaNext) and of the snow de-noisers among them (WeatherNet, 4DenoiseNet, LiSnowNet), with static shapes.
+ * Frames, rows (N_total x 5, float32 or float64 = T), frame offsets and the input keep mask as snowgpu_voxelize_device takes them.
+ * F = n_frames, H = height, W = width, C = n_features in 3 .. 5.  The reference has no such op; the edge conventions are this library's,
+ * restated in NumPy by tests/range_reference.py, and chosen so that on ordinary data the result is what the RangeNet++ loader produces.
+ *   PER ROW, in float64 on (double)x, (double)y, (double)z, every operation rounded on its own (no fused multiply-add), atan2 correctly
+ *   rounded (csrc/sg_atan_cr.h), so that NumPy on glibc gives the same bits:
+ *     r    = T( sqrt((x*x + y*y) + z*z) )             rounded once more to the rows' dtype: the value the image stores
+ *     yaw  = -atan2(y, x)
+ *     px   = (0.5 * (yaw / pi + 1.0)) * W
+ *     col  = clip(floor(px), 0, W - 1)
+ *   image rows by elevation (d_ring NULL; fov2 = (fov_up, fov_down) in radians):
+ *     pitch = atan2(z, sqrt(x*x + y*y))               (= asin(z / r), without a function that is not correctly rounded)
+ *     py    = (1.0 - (pitch - fov_down) / (fov_up - fov_down)) * H
+ *     row   = clip(floor(py), 0, H - 1)               clamped as the RangeNet++ loader clamps, not dropped
+ *   image rows by channel (d_ring: N_total int32, e.g. the input's column 4, which an aligned result has kept beside every row):
+ *     row   = ring[i]
+ *   A row is USABLE iff it is present, |x|, |y|, |z| <= 1e6 (false for NaN), T(lo) < r < T(hi) for the limits (lo, hi) -- both strict,
+ *   compared in T; limits2 NULL is (0, +inf), which takes the origin out -- and, by channel, 0 <= ring < H.  x = y = 0 with z != 0 is
+ *   usable: atan2(0, 0) = 0.
+ *   Per pixel the WINNER is the usable row with the smallest r, compared as values of T; among equal r the smallest row index.
+ *   It depends on no arrival of atomics: two calls give identical bytes.
+ * Outputs, every shape static, every element written by every call:
+ *   d_out_image     (F, 1 + C, H, W) in T: plane 0 the winner's r, planes 1 .. C its columns 0 .. C - 1 bit for bit; -1 in an empty pixel
+ *   d_out_index     (F, H, W) int32: the winner as a row of the whole batch, -1 in an empty pixel
+ *   d_out_pixel_of  (N_total) int32: every row's flat pixel f H W + row W + col, whether it won or not; -1 for absent and unusable rows
+ *   d_out_count     (F, H, W) int32, or NULL: the usable rows that fell in the pixel
+ * Domain: H, W >= 1; F H W <= 2^31 - 1; C in 3 .. 5; fov_down < fov_up, both within [-pi/2, pi/2] (not read by channel); 0 <= lo < hi,
+ * neither NaN, hi may be +inf; n_total < 2^31; no frame above 2^30 rows; dtype 0 or 1; one of fov2 and d_ring; no output may overlap
+ * the rows, the mask, the channels or another output.  Anything else is SNOWGPU_E_INVALID.  A batch without a row fills the image, the
+ * index and the count and launches nothing else (d_rows and d_out_pixel_of may be NULL).
+ * One 8-byte key per pixel in the context (8 F H W bytes, grown on first use), preset by a memset; one thread per row folds
+ * bits(r) << 32 | row into its pixel by a 64-bit atomic min (float64 rows: bits(r), then a second pass over the rows for the smallest
+ * index at that r); one thread per pixel gathers the winner (csrc/snowgpu_range.hip, csrc/sg_range.h).  An angle is evaluated by the
+ * device library's atan2 where that provably decides the same pixel, by the correctly rounded one inside a guard band around every
+ * pixel edge (csrc/sg_range.h derives the band): the bits are those of the definition.  Up to three memsets and three
+ * kernels on `stream`; nothing is read on the host, nothing allocated after the first call of a size: capturable.
+ */
+int snowgpu_range_image_device(snowgpu_ctx *ctx, int n_frames, int64_t n_total, int64_t max_frame_rows, const int64_t *d_frame_offsets,
+                               const void *d_rows, int dtype, int height, int width,
+                               const double *fov2 /* host, radians: up, down; NULL in channel mode */, const int32_t *d_ring /* or NULL */,
+                               const double *limits2 /* host: lo, hi; NULL = (0, inf) */, int n_features,
+                               const uint8_t *d_keep_in /* or NULL: all present */, void *d_out_image, int32_t *d_out_index,
+                               int32_t *d_out_pixel_of, int32_t *d_out_count /* or NULL */, void *stream);
+
+/*
  * PER-FRAME WEATHER in one aligned call.  snowgpu_augment_wet_batch_device_aligned_masked applies one weather to every frame, its wet
  * settings host scalars that a captured graph bakes in.  Here every frame brings a record of 8 doubles in DEVICE memory,
  *     d_weather[f] = [snow, wet, water_height, pavement_depth, wet_noise_floor, power_factor, delta, 0]

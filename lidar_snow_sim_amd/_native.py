@@ -30,7 +30,7 @@ EXPORTS = [
     "snowgpu_augment_batch_device_aligned", "snowgpu_wet_ground_batch_device_aligned", "snowgpu_augment_wet_batch_device_aligned",
     "snowgpu_augment_batch_device_aligned_masked", "snowgpu_augment_wet_batch_device_aligned_masked", "snowgpu_fov_mask_device",
     "snowgpu_augment_weather_batch_device_aligned", "snowgpu_draw_weather_device", "snowgpu_dror_mask_device",
-    "snowgpu_voxelize_device", "snowgpu_fps_device", "snowgpu_ball_query_device",
+    "snowgpu_voxelize_device", "snowgpu_fps_device", "snowgpu_ball_query_device", "snowgpu_range_image_device",
 ]
 
 WET_ESTIMATION = {"linear": 0, "poly": 1}
@@ -149,6 +149,9 @@ def lib():
             L.snowgpu_ball_query_device.restype = ctypes.c_int
             L.snowgpu_ball_query_device.argtypes = [vp, ctypes.c_int, i64, i64, vp, vp, ctypes.c_int, vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, vp, vp,
                                                     ctypes.c_int, vp, vp, vp, vp, vp]
+            L.snowgpu_range_image_device.restype = ctypes.c_int
+            L.snowgpu_range_image_device.argtypes = [vp, ctypes.c_int, i64, i64, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp, ctypes.c_int,
+                                                     vp, vp, vp, vp, vp, vp]
             L.snowgpu_set_fov_precrop.restype = ctypes.c_int
             L.snowgpu_set_fov_precrop.argtypes = [vp, ctypes.c_int]
             L.snowgpu_last_status.restype = ctypes.c_int
@@ -581,6 +584,29 @@ class Context:
                                                int(dtype_code), None if rng is None else _p(rng), i32(n_centres), vp(d_centres or None),
                                                i32(centre_features), len(rad), _p(rad), _p(ns), i32(n_features), vp(d_keep_in or None),
                                                vp(d_out_index or None), vp(d_out_count or None), vp(d_out_points or None), vp(stream or None))
+        if rc == E_INVALID:
+            raise ValueError(self._L.snowgpu_last_error(self._h).decode())
+        self._check(rc)
+
+    def range_image_device(self, n_frames, n_total, max_frame_rows, d_frame_off, d_rows, dtype_code, height, width, fov, d_ring, range_limits,
+                           n_features, d_keep_in, d_out_image, d_out_index, d_out_pixel_of, d_out_count, stream=0):
+        """Range-image projection of an aligned batch (include/snowgpu.h: snowgpu_range_image_device); asynchronous on `stream`.
+        fov: (up, down) in RADIANS or None (image rows by channel: d_ring); range_limits: (lo, hi) or None.  An argument outside the
+        domain, or an output overlapping the rows, the mask, the channels or another output, raises ValueError with the entry's words."""
+        vp = ctypes.c_void_p
+        i32 = lambda v: max(-(2 ** 31), min(int(v), 2 ** 31 - 1))
+        pair = {}
+        for name, v in (("fov", fov), ("range_limits", range_limits)):
+            pair[name] = None
+            if v is not None:
+                pair[name] = np.ascontiguousarray(v, np.float64).reshape(-1)
+                if pair[name].shape != (2,):
+                    raise ValueError(f"snowgpu_range_image_device: {name} holds 2 numbers")
+        rc = self._L.snowgpu_range_image_device(self._h, int(n_frames), int(n_total), int(max_frame_rows), vp(d_frame_off or None), vp(d_rows or None),
+                                                int(dtype_code), i32(height), i32(width), None if pair["fov"] is None else _p(pair["fov"]),
+                                                vp(d_ring or None), None if pair["range_limits"] is None else _p(pair["range_limits"]), i32(n_features),
+                                                vp(d_keep_in or None), vp(d_out_image or None), vp(d_out_index or None), vp(d_out_pixel_of or None),
+                                                vp(d_out_count or None), vp(stream or None))
         if rc == E_INVALID:
             raise ValueError(self._L.snowgpu_last_error(self._h).decode())
         self._check(rc)

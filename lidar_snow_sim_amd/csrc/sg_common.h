@@ -192,7 +192,7 @@ struct SgFov {
 
 // Launch wrappers (hipStream_t passed as void*), each implemented in the file that defines its kernels: snowgpu_sort.hip (expand_rows, sort,
 // gather_rows, segments*, resolve_tables), snowgpu_kernels.hip (beams, power*, tier_*, huge, sg_beams_block), snowgpu_rows.hip (rows),
-// snowgpu_compact.hip (compact, crop_*), snowgpu_mask.hip (mask_front, finish_aligned_masked, fov_mask), snowgpu_dror.hip (dror), snowgpu_voxel.hip (voxelize), snowgpu_fps.hip (fps), snowgpu_ball.hip (ball).  Every one of these files includes this header, so a definition cannot drift from its declaration.
+// snowgpu_compact.hip (compact, crop_*), snowgpu_mask.hip (mask_front, finish_aligned_masked, fov_mask), snowgpu_dror.hip (dror), snowgpu_voxel.hip (voxelize), snowgpu_fps.hip (fps), snowgpu_ball.hip (ball), snowgpu_range.hip (range).  Every one of these files includes this header, so a definition cannot drift from its declaration.
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -294,6 +294,12 @@ int sg_launch_ball(const void *rows, int dtype, int64_t n, const int64_t *frame_
                    const struct SgBallGrid *g, int32_t n_centres, const void *centres, int32_t centre_features, int n_radii, const double *radii,
                    const int *n_samples, int32_t n_features, uint32_t *entry, uint32_t *cell_of, void *sx, void *sy, void *sz, int32_t *ssrc,
                    int32_t *out_index, int32_t *out_count, void *out_points, void *stream);
+// Range-image projection (sg_range.h; the definition: include/snowgpu.h): up to three memsets and up to three kernels.  Scratch: key,
+// n_frames H W 64-bit words (unused for a batch without a row).  ring is read with g->by_ring only; out_count may be null.
+struct SgRangeGeom;
+int sg_launch_range(const void *rows, int dtype, int64_t n, const int64_t *frame_off, int n_frames, const uint8_t *keep_in, const int32_t *ring,
+                    const struct SgRangeGeom *g, int32_t n_features, unsigned long long *key, void *out_image, int32_t *out_index,
+                    int32_t *out_pixel_of, int32_t *out_count, void *stream);
 #ifdef __cplusplus
 }
 #endif

@@ -288,6 +288,68 @@ static inline int sg_check_ball_args(const SgBallArgs &a, int64_t *total, std::s
     return 0;
 }
 
+// ---- snowgpu_range_image_device -----------------------------------------------------------------------------------------------------------
+struct SgRangeArgs {
+    int n_frames;
+    int64_t n_total, max_frame_rows;
+    int dtype;
+    const int64_t *frame_off;
+    const void *rows;
+    int H, W;
+    const double *fov2;               // (up, down) in radians, host memory; NULL in channel mode
+    const int32_t *ring;              // one channel per row, or NULL: rows by elevation
+    const double *limits2;            // (lo, hi), host memory, or NULL: (0, +inf)
+    int n_features;                   // C
+    const uint8_t *keep_in;
+    void *out_image;
+    int32_t *out_index, *out_pixel_of;
+    int32_t *out_count;               // or NULL
+};
+
+// 0, or SG_ARGS_INVALID with *msg.  As above, the order is part of the ABI.
+static inline int sg_check_range_args(const SgRangeArgs &a, std::string *msg)
+{
+    static const char *who = "snowgpu_range_image_device";
+    if (a.n_frames <= 0 || a.n_total < 0 || !a.frame_off || !a.out_image || !a.out_index || (a.n_total > 0 && (!a.rows || !a.out_pixel_of)) ||
+        (a.dtype != 0 && a.dtype != 1))
+        return sg_refuse(who, ": null pointer or bad dtype", msg);
+    if (!a.fov2 && !a.ring) return sg_refuse(who, ": needs fov2 (image rows by elevation) or d_ring (image rows by channel)", msg);
+    if (a.n_total >= ((int64_t)1 << 31)) return sg_refuse("", "batch too large: split it below 2^31 rows", msg);
+    if (a.n_features < 3 || a.n_features > 5) return sg_refuse(who, ": n_features must be 3, 4 or 5: the columns of a row that a pixel stores", msg);
+    if (a.H < 1 || a.W < 1) return sg_refuse(who, ": height and width must be at least 1", msg);
+    if ((int64_t)a.n_frames * a.H > (((int64_t)1 << 31) - 1) / a.W)       // (F H W <= 2^31 - 1, without the product of three)
+        return sg_refuse(who, ": n_frames * height * width exceeds 2^31 - 1; split the batch", msg);
+    if (sg_max_frame(a.max_frame_rows, a.n_total) > ((int64_t)1 << 30))
+        return sg_refuse(who, ": a frame of more than 2^30 rows; split it", msg);
+    if (!a.ring) {
+        const double half_pi = 1.5707963267948966;
+        for (int j = 0; j < 2; ++j)
+            if (!(a.fov2[j] >= -half_pi && a.fov2[j] <= half_pi)) return sg_refuse(who, ": fov_up and fov_down must lie within [-pi/2, pi/2] (radians)", msg);
+        if (!(a.fov2[1] < a.fov2[0])) return sg_refuse(who, ": the field of view needs fov_down < fov_up", msg);
+    }
+    if (a.limits2) {
+        if (a.limits2[0] != a.limits2[0] || a.limits2[1] != a.limits2[1]) return sg_refuse(who, ": a range limit is NaN; pass NULL for (0, +inf)", msg);
+        if (!(a.limits2[0] >= 0.0 && a.limits2[0] < a.limits2[1])) return sg_refuse(who, ": the range limits need 0 <= lo < hi", msg);
+    }
+    const size_t esz = a.dtype == 0 ? 4 : 8, px = (size_t)a.n_frames * (size_t)a.H * (size_t)a.W, n = (size_t)a.n_total;
+    const struct { const void *p; size_t bytes; const char *name; } outs[4] = {
+        {a.out_image, px * (size_t)(1 + a.n_features) * esz, "d_out_image"}, {a.out_index, px * 4, "d_out_index"},
+        {a.out_pixel_of, n * 4, "d_out_pixel_of"}, {a.out_count, px * 4, "d_out_count"}};
+    for (int i = 0; i < 4; ++i) {
+        const auto &o = outs[i];
+        if (sg_ranges_meet(o.p, o.bytes, a.keep_in, n))
+            return sg_refuse(who, (std::string(": ") + o.name + " overlaps d_keep_in; the mask is read while the image is written: pass a buffer apart from it").c_str(), msg);
+        if (sg_ranges_meet(o.p, o.bytes, a.rows, n * 5 * esz))
+            return sg_refuse(who, (std::string(": ") + o.name + " overlaps d_rows; the rows are read while the image is written: pass a buffer apart from them").c_str(), msg);
+        if (sg_ranges_meet(o.p, o.bytes, a.ring, n * 4))
+            return sg_refuse(who, (std::string(": ") + o.name + " overlaps d_ring; the channels are read while the image is written: pass a buffer apart from them").c_str(), msg);
+        for (int j = 0; j < i; ++j)
+            if (sg_ranges_meet(o.p, o.bytes, outs[j].p, outs[j].bytes))
+                return sg_refuse(who, (std::string(": ") + o.name + " overlaps " + outs[j].name + "; every output needs memory of its own").c_str(), msg);
+    }
+    return 0;
+}
+
 // 0, or SG_ARGS_INVALID with *msg (built on this path only).  The order is part of the ABI: it decides which message a doubly wrong call gets.
 static inline int sg_check_device_args(const SgDeviceArgs &a, const SgCtxView &c, const SgEntryShape &s, std::string *msg)
 {

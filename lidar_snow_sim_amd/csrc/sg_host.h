@@ -98,6 +98,8 @@ struct __attribute__((visibility("default"))) snowgpu_ctx {
     DevBuf<uint32_t> ball_entry, ball_cell;
     DevBuf<uint8_t> ball_x, ball_y, ball_z;
     DevBuf<int32_t> ball_src;
+    // range image (snowgpu_range_image_device): one key per pixel of every frame's image
+    DevBuf<unsigned long long> range_key;
     // scratch shared by every batch
     DevBuf<int32_t> tile_hist, tile_base, perm, ctile_cnt, ctile_base, table_ids, out_src;
     DevBuf<uint8_t> srows;            // channel-sorted copy of the frames whose rows did not come channel-sorted (firing order)

@@ -1,5 +1,5 @@
 // snowgpu_device.cpp -- the entries of the C ABI (include/snowgpu.h) that take DEVICE pointers and enqueue on the caller's stream: every
-// *_batch_device* entry, the plane estimate, the FOV mask, the outlier filter, the voxel stage, the keypoint stage, the ball query and the weather draw.  Each batch entry fills an SgDeviceArgs, has it checked
+// *_batch_device* entry, the plane estimate, the FOV mask, the outlier filter, the voxel stage, the keypoint stage, the ball query, the range image and the weather draw.  Each batch entry fills an SgDeviceArgs, has it checked
 // (sg_device_args.h: every refusal, in one order), sets the device and runs batch_from_args() and the stages it needs.  The launch
 // sequence of a batch is snowgpu_batch.cpp; no host copy, no synchronisation, no allocation after the first call of a given size.
 #include "sg_host.h"
@@ -9,6 +9,7 @@
 #include "sg_voxel.h"       // the grid of the voxel stage and the capacity of its tables
 #include "sg_fps.h"         // the range of the keypoint stage and the size of its scratch
 #include "sg_ball.h"        // the grid of the ball query and the sizes of its scratch
+#include "sg_range.h"       // the geometry of the range image and the limits in the rows' dtype
 
 static_assert(SG_ARGS_INVALID == SNOWGPU_E_INVALID && SG_PLANE_REFERENCE == 0, "sg_device_args.h restates these two");
 
@@ -499,6 +500,31 @@ extern "C" int snowgpu_ball_query_device(snowgpu_ctx *ctx, int n_frames, int64_t
                            n_features, ctx->ball_entry.p, ctx->ball_cell.p, ctx->ball_x.p, ctx->ball_y.p, ctx->ball_z.p, ctx->ball_src.p, d_out_index, d_out_count,
                            d_out_points, stream ? (hipStream_t)stream : ctx->stream);
     if (e) return fail(ctx, SNOWGPU_E_HIP, std::string("ball query launch: ") + hipGetErrorString((hipError_t)e));
+    return SNOWGPU_OK;
+}
+
+// Range-image projection of an aligned batch (snowgpu_range.hip; the pixel functions and the key: sg_range.h).  See include/snowgpu.h.
+extern "C" int snowgpu_range_image_device(snowgpu_ctx *ctx, int n_frames, int64_t n_total, int64_t max_frame_rows, const int64_t *d_frame_offsets,
+                                          const void *d_rows, int dtype, int height, int width, const double *fov2, const int32_t *d_ring,
+                                          const double *limits2, int n_features, const uint8_t *d_keep_in, void *d_out_image, int32_t *d_out_index,
+                                          int32_t *d_out_pixel_of, int32_t *d_out_count, void *stream)
+{
+    if (!ctx) return SNOWGPU_E_INVALID;
+    const SgRangeArgs a{n_frames, n_total, max_frame_rows, dtype, d_frame_offsets, d_rows, height, width, fov2, d_ring, limits2, n_features, d_keep_in,
+                        d_out_image, d_out_index, d_out_pixel_of, d_out_count};
+    {
+        std::string msg;
+        if (int rc = sg_check_range_args(a, &msg)) return fail(ctx, rc, msg);
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    SgRangeGeom g{};
+    g.H = height; g.W = width; g.by_ring = d_ring ? 1 : 0;
+    if (!d_ring) { g.fov_up = fov2[0]; g.fov_down = fov2[1]; }
+    sg_range_limits(dtype, limits2, &g.lo, &g.hi);
+    if (n_total > 0) ENSURE(ctx, ctx->range_key, (size_t)n_frames * (size_t)height * (size_t)width);
+    int e = sg_launch_range(d_rows, dtype, n_total, d_frame_offsets, n_frames, d_keep_in, d_ring, &g, n_features, ctx->range_key.p, d_out_image, d_out_index,
+                            d_out_pixel_of, d_out_count, stream ? (hipStream_t)stream : ctx->stream);
+    if (e) return fail(ctx, SNOWGPU_E_HIP, std::string("range image launch: ") + hipGetErrorString((hipError_t)e));
     return SNOWGPU_OK;
 }
 

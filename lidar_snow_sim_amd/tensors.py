@@ -25,6 +25,9 @@ The reference's training-time caller (the OpenPCDet DENSE dataset: `root_path`, 
     (KeypointBatch; snowgpu_fps_device): the hand-off to a point-based detector, likewise.
   * `ball_query(frames_or_result, centres, radius, n_neighbours)` groups, around every centre (a KeypointBatch, or any centres), the
     first rows of its frame within each radius (NeighbourBatch; snowgpu_ball_query_device): the grouping step of a set-abstraction layer.
+  * `range_image(frames_or_result, height, width)` projects the present rows of every frame into an H x W image of nearest returns
+    (RangeImageBatch; snowgpu_range_image_device): the hand-off to a range-view network or de-noiser; `to_rows` brings its per-pixel
+    prediction back to the rows as a keep mask for the next stage.
   * `augment_wet_batch_aligned(frames, ...)` is the snowfall + wet-ground chain with that aligned result (AlignedWetResult: per-frame
     flags beside it; snowgpu_augment_wet_batch_device_aligned), `wet_ground_batch_aligned(frames, keep)` the wet-ground stage alone on rows
     and a keep mask from any earlier stage (snowgpu_wet_ground_batch_device_aligned).
@@ -842,6 +845,117 @@ def ball_query(frames, centres, radius, n_neighbours, *, point_cloud_range=None,
                                   rng, K, cen.data_ptr(), Cq, radii, seg, C, 0 if keep is None or not n else keep.data_ptr(), out.index.data_ptr(),
                                   out.count.data_ptr(), 0 if points is None else points.data_ptr(), run.cuda_stream)
     return NeighbourBatch(out.index, out.count, points, seg) if (out.segments != tuple(seg) or (points is None) != (out.points is None)) else out
+
+
+class RangeImageBatch:
+    """What range_image() leaves behind, F = frames, H x W the image, C = num_features -- every shape static: `image` (F, 1 + C, H, W; the
+    rows' dtype: plane 0 the range of the pixel's nearest row, planes 1 .. C its columns 0 .. C - 1, bit for bit; -1 in an empty pixel),
+    `index` (F, H, W int32: that row as an index into the whole batch, so rows[index] gathers; -1 in an empty pixel), `pixel_of` (N_total
+    int32: every row's flat pixel f H W + row W + col, whether it won or not; -1 for absent and unusable rows) and `count` (F, H, W int32:
+    the usable rows that fell in the pixel; None unless asked for).  All still being written until the stream the call was made on has
+    caught up."""
+
+    def __init__(self, image, index, pixel_of, count=None):
+        self.image, self.index, self.pixel_of, self.count = image, index, pixel_of, count
+
+    @classmethod
+    def empty(cls, n_frames, height, width, n_rows, num_features=4, dtype=None, device=None, with_count=False):
+        """Uninitialised buffers of the shapes range_image() writes for such a call on a batch of n_rows rows (out=): static addresses
+        for a captured graph."""
+        import torch
+        dev = torch.device("cuda", torch.cuda.current_device() if device is None else int(device)) if not isinstance(device, torch.device) else device
+        F, H, W = int(n_frames), int(height), int(width)
+        i32 = dict(dtype=torch.int32, device=dev)
+        return cls(torch.empty((F, 1 + int(num_features), H, W), dtype=dtype or torch.float32, device=dev), torch.empty((F, H, W), **i32),
+                   torch.empty(int(n_rows), **i32), torch.empty((F, H, W), **i32) if with_count else None)
+
+    def to_rows(self, values, fill=0):
+        """The way back: a per-pixel tensor (F, H, W) or (F, X, H, W) -- a de-noiser's keep or class map -- as a per-row tensor (N,) or
+        (N, X): every row gets the value of its pixel, `fill` where pixel_of is -1.  Pure indexing on the device, nothing is read on
+        the host: a predicted mask goes straight into augment_batch(..., keep=) or dror_keep(..., keep=)."""
+        import torch
+        F, H, W = self.index.shape
+        if not (torch.is_tensor(values) and values.dim() in (3, 4) and values.shape[0] == F and tuple(values.shape[-2:]) == (H, W)):
+            raise ValueError(f"to_rows: values must be a ({F}, {H}, {W}) or ({F}, X, {H}, {W}) tensor: one value, or X of them, per pixel")
+        p = self.pixel_of.long()
+        at = p.clamp(min=0)
+        if values.dim() == 3:
+            got = values.reshape(-1)[at]
+            return torch.where(p >= 0, got, torch.full_like(got, fill))
+        f = torch.div(at, H * W, rounding_mode="floor")
+        got = values.reshape(F, values.shape[1], H * W)[f, :, at - f * (H * W)]
+        return torch.where((p >= 0)[:, None], got, torch.full_like(got, fill))
+
+
+def range_image(frames, height, width, *, fov_up=3.0, fov_down=-25.0, ring=None, range_limits=(0.0, float("inf")), keep=None, num_features=4,
+                out=None, return_count=False, device=None, slot=0):
+    """Range-image projection on the device (snowgpu_range_image_device; the definition: include/snowgpu.h): every frame as a height x
+    width image of its nearest returns, the input of the range-view networks (RangeNet++, SalsaNext) and of the snow de-noisers
+    (WeatherNet, 4DenoiseNet, LiSnowNet), with static shapes.  The column is the azimuth, the image row the elevation between fov_down and
+    fov_up (DEGREES, as the RangeNet++ configs give them; rows beyond are clamped to the first and last image row) -- or, with `ring`,
+    the row's laser channel.  Per pixel the usable row (present, within 1e6 of the origin on every axis, range strictly inside
+    range_limits) with the smallest range wins, the smallest row index among equals.
+
+    frames    what voxelize takes -- torch CUDA tensors, a DeviceBatch, or an AlignedResult / AlignedWetResult: its rows, offsets and keep
+              mask are used (nothing is waited for).
+    ring      an int32 CUDA tensor with one image row per row of the batch, e.g. the INPUT's column 4 as int32 beside an aligned result (a
+              scattered row moves along its own beam and keeps its channel); rows whose ring is outside 0 .. height - 1 are unusable.
+    keep      an input keep mask as the aligned calls take it (with a result: ANDed with the result's own).
+    out       a RangeImageBatch to write into (RangeImageBatch.empty): every element is written, nothing needs clearing.
+    return_count   also fill `count`.
+
+    Returns a RangeImageBatch; its to_rows() carries a per-pixel prediction back to the rows.  Asynchronous on torch's current stream;
+    nothing is read on the host: capturable after one warm-up call."""
+    import torch
+    if isinstance(frames, AlignedResult):
+        res = frames
+        own = res.keep if res.keep.dtype == torch.bool else res.keep.view(torch.bool)
+        frames = DeviceBatch(res.rows, res.offsets)
+        keep = own if keep is None else (_keep_mask(torch, keep, res.rows, res.offsets) & own)
+    if not is_device_input(frames):
+        raise ValueError("range_image: torch CUDA tensors or an aligned result (host arrays: lidar_snow_sim_amd.range_image.project)")
+    for name, v in (("height", height), ("width", width), ("num_features", num_features)):
+        if isinstance(v, bool) or int(v) != v:
+            raise ValueError(f"range_image: {name} must be an integer")
+    limits = np.asarray(range_limits, np.float64).reshape(-1)
+    if limits.shape != (2,):
+        raise ValueError("range_image: range_limits holds 2 numbers (lo, hi)")
+    rows, offsets, _, eng = _resolve_input(torch, frames, False, device, slot)
+    dev = rows.device
+    nf, n = len(offsets) - 1, int(offsets[-1])
+    H, W, C = int(height), int(width), int(num_features)
+    if keep is not None:
+        keep = _keep_mask(torch, keep, rows, offsets)
+    if ring is not None and not (torch.is_tensor(ring) and ring.dtype == torch.int32 and ring.dim() == 1 and ring.shape[0] == n and ring.device == dev and
+                                 ring.is_contiguous()):
+        raise ValueError("range_image: ring must be a contiguous int32 tensor with one element per row of the batch, on the device of the rows")
+    # (the shapes below need these; the entry refuses them in the same words, and everything else of the domain)
+    if not 3 <= C <= 5:
+        raise ValueError("range_image: n_features must be 3, 4 or 5: the columns of a row that a pixel stores")
+    if H < 1 or W < 1:
+        raise ValueError("range_image: height and width must be at least 1")
+    if nf * H * W > 2 ** 31 - 1:
+        raise ValueError("range_image: n_frames * height * width exceeds 2^31 - 1; split the batch")
+    if out is None:
+        out = RangeImageBatch.empty(nf, H, W, n, C, rows.dtype, dev, return_count)
+    else:
+        want = (("image", (nf, 1 + C, H, W), rows.dtype), ("index", (nf, H, W), torch.int32), ("pixel_of", (n,), torch.int32)) + \
+               ((("count", (nf, H, W), torch.int32),) if return_count else ())
+        for name, shape, dtype in want:
+            t = getattr(out, name, None) if isinstance(out, RangeImageBatch) else None
+            if not (torch.is_tensor(t) and tuple(t.shape) == shape and t.dtype == dtype and t.is_contiguous() and t.device == dev):
+                raise ValueError(f"range_image: out must be a RangeImageBatch whose {name} is a contiguous {tuple(shape)} {dtype} tensor on the device of the rows")
+    count = out.count if return_count else None
+    by_ring = ring is not None and n > 0          # (without a row there is no channel to read: either mode writes the empty image)
+    fov = None if by_ring else np.radians(np.array([fov_up, fov_down], np.float64))
+    up = _uploads(eng)
+    with torch.cuda.device(dev), _on_run_stream(torch, eng, dev) as (_, run):
+        d_off = up.get(torch, dev, offsets, run)
+        eng.ctx.range_image_device(nf, n, int(np.diff(offsets).max()), d_off.data_ptr(), rows.data_ptr() if n else 0, 0 if rows.dtype == torch.float32 else 1,
+                                   H, W, fov, ring.data_ptr() if by_ring else 0, limits, C, 0 if keep is None or not n else keep.data_ptr(),
+                                   out.image.data_ptr(), out.index.data_ptr(), out.pixel_of.data_ptr() if n else 0, 0 if count is None else count.data_ptr(),
+                                   run.cuda_stream)
+    return out if return_count or out.count is None else RangeImageBatch(out.image, out.index, out.pixel_of)
 
 
 def augment_batch(frames, particle_file_prefix, beam_divergence, shuffle=True, noise_floor=0.7, root_path=None, *, planes=None,
