@@ -773,6 +773,49 @@ int snowgpu_range_image_device(snowgpu_ctx *ctx, int n_frames, int64_t n_total, 
                                int32_t *d_out_pixel_of, int32_t *d_out_count /* or NULL */, void *stream);
 
 /*
+ * NEAREST CENTRES OF EVERY ROW of an aligned batch: for every row the k nearest centres of its frame and their inverse-distance weights,
+ * the way back from keypoints to rows -- pointnet2's three_nn + three_interpolate (k = 3), the feature-propagation half of PointNet++,
+ * and with k = 1 the Voronoi labelling of the rows by the keypoints --, with static shapes.  Frames, rows (N_total x 5, float32 or
+ * float64 = T), frame offsets and the input keep mask as snowgpu_ball_query_device takes them.  F = n_frames, K = n_centres per frame,
+ * 1 <= k <= 8.  The reference has no such op; the edge conventions are this library's, restated as brute-force NumPy by
+ * tests/nn_reference.py.
+ *   A row is USABLE exactly as for snowgpu_fps_device: present, |x|, |y|, |z| <= 1e6 (false for NaN) and, with a range,
+ *   lo_j <= (double)p_j < hi_j.  range6 may be NULL.
+ *   CENTRES: d_centres is (F, K, Cq) in T, Cq = centre_features in 3 .. 5, columns 0 .. 2 x, y, z (the points of the keypoint stage go
+ *   in as they are).  A centre is usable exactly as for snowgpu_ball_query_device: |x|, |y|, |z| <= 1e6; it need not lie in the range
+ *   or be a row.
+ *   DISTANCE: all arithmetic in T.  d = ((dx dx) + (dy dy)) + (dz dz), every operation rounded on its own, no fused multiply-add, no
+ *   square root.
+ *   RESULT for usable row i of frame f: order the usable centres of frame f by (d, centre number) lexicographically -- among equal
+ *   distances the smaller centre number first.  With m usable centres in the frame, slots 0 .. min(k, m) - 1 of the row hold the first
+ *   min(k, m) of them: index = the centre number in 0 .. K - 1 WITHIN THE FRAME, dist2 = d, bit for bit.  Slots beyond m hold index -1,
+ *   dist2 +inf and weight 0, and so do all slots of a row that is absent or not usable.  Duplicate centres are distinct centres at equal
+ *   d (a KeypointBatch of a short frame repeats its first): they come in centre order.
+ *   WEIGHTS (d_out_weight, may be NULL), in float64, every operation rounded on its own: u_j = 1.0 / (sqrt((double)d_j) + 1e-8) for the
+ *   filled slots, n = ((u_0 + u_1) + u_2) + ... in slot order, weight_j = T(u_j / n): pointnet2's 1 / (dist + 1e-8) normalisation.  A row
+ *   that coincides with a centre has u = 1e8 there.
+ * Outputs, every shape static, every element written by every call:
+ *   d_out_index   (N_total, k) int32
+ *   d_out_dist2   (N_total, k) T
+ *   d_out_weight  (N_total, k) T, or NULL
+ * Domain: K >= 1; 1 <= k <= 8; F K <= 2^31 - 1; n_total < 2^31; no frame above 2^30 rows; dtype 0 or 1; the range as for
+ * snowgpu_fps_device; the outputs must overlap neither each other nor the rows, the keep mask or the centres.  Anything else is
+ * SNOWGPU_E_INVALID.  A batch without a row has no element to write: nothing is launched (d_rows and the outputs may be NULL).
+ * The result depends on neither a cell order nor the arrival of atomics: two calls give identical bytes.
+ * The K centres of every frame are filed, not the rows: a uniform x-y grid of about K / 2 cells (16 .. 2048) over the range's x-y
+ * rectangle (+-120 m without one), one workgroup per frame counting, scanning and scattering in LDS, one 16-byte record per centre
+ * (32 for float64).  Then ONE LANE per row walks rings of growing Chebyshev radius around its cell, clipped to the occupied cells of
+ * the frame, keeps its k best in registers and stops when the k-th distance is strictly below the squared gap to the nearest open side
+ * of the visited block, deflated by 1e-6 (csrc/sg_nn.h: the grid rule, the bound and its derivation; csrc/snowgpu_nn.hip).
+ * Scratch in the context, grown on first use: per frame one word per cell and five more, and one record per centre.  Two kernels on
+ * `stream`; nothing is read on the host, nothing allocated after the first call of a size: capturable.
+ */
+int snowgpu_nearest_centres_device(snowgpu_ctx *ctx, int n_frames, int64_t n_total, int64_t max_frame_rows, const int64_t *d_frame_offsets,
+                                   const void *d_rows, int dtype, const double *range6 /* host: x0 y0 z0 x1 y1 z1, or NULL */, int n_centres,
+                                   const void *d_centres, int centre_features, int k, const uint8_t *d_keep_in /* or NULL: all present */,
+                                   int32_t *d_out_index, void *d_out_dist2, void *d_out_weight /* or NULL */, void *stream);
+
+/*
  * PER-FRAME WEATHER in one aligned call.  snowgpu_augment_wet_batch_device_aligned_masked applies one weather to every frame, its wet
  * settings host scalars that a captured graph bakes in.  Here every frame brings a record of 8 doubles in DEVICE memory,
  *     d_weather[f] = [snow, wet, water_height, pavement_depth, wet_noise_floor, power_factor, delta, 0]

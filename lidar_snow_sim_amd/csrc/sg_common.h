@@ -300,6 +300,13 @@ struct SgRangeGeom;
 int sg_launch_range(const void *rows, int dtype, int64_t n, const int64_t *frame_off, int n_frames, const uint8_t *keep_in, const int32_t *ring,
                     const struct SgRangeGeom *g, int32_t n_features, unsigned long long *key, void *out_image, int32_t *out_index,
                     int32_t *out_pixel_of, int32_t *out_count, void *stream);
+// Nearest centres of every row (sg_nn.h; the definition: include/snowgpu.h): two kernels.  Scratch: entry, sg_nn_entries(n_frames,
+// g->cells) words; box, sg_nn_boxes(n_frames) words; rec, sg_nn_records(n_frames, n_centres) records of the rows' dtype (SgNnRec).
+// out_weight may be null.  Nothing is launched for a batch without a row.
+struct SgNnGrid;
+int sg_launch_nn(const void *rows, int dtype, int64_t n, const int64_t *frame_off, int n_frames, const uint8_t *keep_in, const struct SgFpsRange *range,
+                 const struct SgNnGrid *g, int32_t n_centres, const void *centres, int32_t centre_features, int k, uint32_t *entry, int32_t *box, void *rec,
+                 int32_t *out_index, void *out_dist, void *out_weight, void *stream);
 #ifdef __cplusplus
 }
 #endif

@@ -350,6 +350,64 @@ static inline int sg_check_range_args(const SgRangeArgs &a, std::string *msg)
     return 0;
 }
 
+// ---- snowgpu_nearest_centres_device -------------------------------------------------------------------------------------------------------
+struct SgNnArgs {
+    int n_frames;
+    int64_t n_total, max_frame_rows;
+    int dtype;
+    const int64_t *frame_off;
+    const void *rows;
+    const double *range6;             // (x0, y0, z0, x1, y1, z1), host memory, or NULL: no range test
+    int n_centres;                    // K, per frame
+    const void *centres;
+    int centre_features;              // Cq
+    int k;                            // neighbours of a row
+    const uint8_t *keep_in;
+    int32_t *out_index;
+    void *out_dist2;
+    void *out_weight;                 // or NULL
+    int64_t max_cells;                // cells per frame that the grid may take
+};
+
+// 0, or SG_ARGS_INVALID with *msg.  As above, the order is part of the ABI.
+static inline int sg_check_nn_args(const SgNnArgs &a, std::string *msg)
+{
+    static const char *who = "snowgpu_nearest_centres_device";
+    if (a.n_frames <= 0 || a.n_total < 0 || !a.frame_off || !a.centres || (a.n_total > 0 && (!a.rows || !a.out_index || !a.out_dist2)) ||
+        (a.dtype != 0 && a.dtype != 1))
+        return sg_refuse(who, ": null pointer or bad dtype", msg);
+    if (a.n_total >= ((int64_t)1 << 31)) return sg_refuse("", "batch too large: split it below 2^31 rows", msg);
+    if (a.centre_features < 3 || a.centre_features > 5) return sg_refuse(who, ": centre_features must be 3, 4 or 5: x, y, z first", msg);
+    if (a.n_centres < 1) return sg_refuse(who, ": n_centres must be at least 1", msg);
+    if (a.k < 1 || a.k > 8) return sg_refuse(who, ": k must lie in 1 .. 8", msg);
+    if ((int64_t)a.n_frames * a.n_centres > ((int64_t)1 << 31) - 1) return sg_refuse(who, ": n_frames * n_centres exceeds 2^31 - 1; split the batch", msg);
+    if (sg_max_frame(a.max_frame_rows, a.n_total) > ((int64_t)1 << 30))
+        return sg_refuse(who, ": a frame of more than 2^30 rows; split it", msg);
+    if ((int64_t)a.n_frames * (a.max_cells + 1) >= ((int64_t)1 << 31)) return sg_refuse(who, ": too many frames for the cell lists; split the batch", msg);
+    if (a.range6) {
+        for (int j = 0; j < 6; ++j)
+            if (a.range6[j] != a.range6[j]) return sg_refuse(who, ": a bound of the range is NaN; pass NULL for no range, or infinite bounds", msg);
+        for (int j = 0; j < 3; ++j)
+            if (!(a.range6[j] < a.range6[3 + j])) return sg_refuse(who, ": the range needs lo < hi on every axis", msg);
+    }
+    const size_t esz = a.dtype == 0 ? 4 : 8, q = (size_t)a.n_frames * (size_t)a.n_centres, n = (size_t)a.n_total, slots = n * (size_t)a.k;
+    const struct { const void *p; size_t bytes; const char *name; } outs[3] = {
+        {a.out_index, slots * 4, "d_out_index"}, {a.out_dist2, slots * esz, "d_out_dist2"}, {a.out_weight, slots * esz, "d_out_weight"}};
+    for (int i = 0; i < 3; ++i) {
+        const auto &o = outs[i];
+        if (sg_ranges_meet(o.p, o.bytes, a.keep_in, n))
+            return sg_refuse(who, (std::string(": ") + o.name + " overlaps d_keep_in; the mask is read while the neighbours are written: pass a buffer apart from it").c_str(), msg);
+        if (sg_ranges_meet(o.p, o.bytes, a.rows, n * 5 * esz))
+            return sg_refuse(who, (std::string(": ") + o.name + " overlaps d_rows; the rows are read while the neighbours are written: pass a buffer apart from them").c_str(), msg);
+        if (sg_ranges_meet(o.p, o.bytes, a.centres, q * (size_t)a.centre_features * esz))
+            return sg_refuse(who, (std::string(": ") + o.name + " overlaps d_centres; the centres are read while the neighbours are written: pass a buffer apart from them").c_str(), msg);
+        for (int j = 0; j < i; ++j)
+            if (sg_ranges_meet(o.p, o.bytes, outs[j].p, outs[j].bytes))
+                return sg_refuse(who, (std::string(": ") + o.name + " overlaps " + outs[j].name + "; every output needs memory of its own").c_str(), msg);
+    }
+    return 0;
+}
+
 // 0, or SG_ARGS_INVALID with *msg (built on this path only).  The order is part of the ABI: it decides which message a doubly wrong call gets.
 static inline int sg_check_device_args(const SgDeviceArgs &a, const SgCtxView &c, const SgEntryShape &s, std::string *msg)
 {

@@ -100,6 +100,11 @@ struct __attribute__((visibility("default"))) snowgpu_ctx {
     DevBuf<int32_t> ball_src;
     // range image (snowgpu_range_image_device): one key per pixel of every frame's image
     DevBuf<unsigned long long> range_key;
+    // nearest centres (snowgpu_nearest_centres_device): the cell lists of every frame's centres -- first positions and the occupied box --
+    // and the usable centres sorted by cell, one record (x, y, z, centre number) each
+    DevBuf<uint32_t> nn_entry;
+    DevBuf<int32_t> nn_box;
+    DevBuf<uint8_t> nn_rec;
     // scratch shared by every batch
     DevBuf<int32_t> tile_hist, tile_base, perm, ctile_cnt, ctile_base, table_ids, out_src;
     DevBuf<uint8_t> srows;            // channel-sorted copy of the frames whose rows did not come channel-sorted (firing order)

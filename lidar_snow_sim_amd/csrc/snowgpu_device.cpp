@@ -1,5 +1,5 @@
 // snowgpu_device.cpp -- the entries of the C ABI (include/snowgpu.h) that take DEVICE pointers and enqueue on the caller's stream: every
-// *_batch_device* entry, the plane estimate, the FOV mask, the outlier filter, the voxel stage, the keypoint stage, the ball query, the range image and the weather draw.  Each batch entry fills an SgDeviceArgs, has it checked
+// *_batch_device* entry, the plane estimate, the FOV mask, the outlier filter, the voxel stage, the keypoint stage, the ball query, the range image, the nearest centres and the weather draw.  Each batch entry fills an SgDeviceArgs, has it checked
 // (sg_device_args.h: every refusal, in one order), sets the device and runs batch_from_args() and the stages it needs.  The launch
 // sequence of a batch is snowgpu_batch.cpp; no host copy, no synchronisation, no allocation after the first call of a given size.
 #include "sg_host.h"
@@ -9,6 +9,7 @@
 #include "sg_voxel.h"       // the grid of the voxel stage and the capacity of its tables
 #include "sg_fps.h"         // the range of the keypoint stage and the size of its scratch
 #include "sg_ball.h"        // the grid of the ball query and the sizes of its scratch
+#include "sg_nn.h"          // the grid of the nearest-centres stage and the sizes of its scratch
 #include "sg_range.h"       // the geometry of the range image and the limits in the rows' dtype
 
 static_assert(SG_ARGS_INVALID == SNOWGPU_E_INVALID && SG_PLANE_REFERENCE == 0, "sg_device_args.h restates these two");
@@ -525,6 +526,34 @@ extern "C" int snowgpu_range_image_device(snowgpu_ctx *ctx, int n_frames, int64_
     int e = sg_launch_range(d_rows, dtype, n_total, d_frame_offsets, n_frames, d_keep_in, d_ring, &g, n_features, ctx->range_key.p, d_out_image, d_out_index,
                             d_out_pixel_of, d_out_count, stream ? (hipStream_t)stream : ctx->stream);
     if (e) return fail(ctx, SNOWGPU_E_HIP, std::string("range image launch: ") + hipGetErrorString((hipError_t)e));
+    return SNOWGPU_OK;
+}
+
+// Nearest centres of every row (snowgpu_nn.hip; the grid, the walk and its stopping bound: sg_nn.h).  See include/snowgpu.h.
+extern "C" int snowgpu_nearest_centres_device(snowgpu_ctx *ctx, int n_frames, int64_t n_total, int64_t max_frame_rows, const int64_t *d_frame_offsets,
+                                              const void *d_rows, int dtype, const double *range6, int n_centres, const void *d_centres, int centre_features,
+                                              int k, const uint8_t *d_keep_in, int32_t *d_out_index, void *d_out_dist2, void *d_out_weight, void *stream)
+{
+    if (!ctx) return SNOWGPU_E_INVALID;
+    const SgNnArgs a{n_frames, n_total, max_frame_rows, dtype, d_frame_offsets, d_rows, range6, n_centres, d_centres, centre_features, k, d_keep_in,
+                     d_out_index, d_out_dist2, d_out_weight, SG_NN_MAX_CELLS};
+    {
+        std::string msg;
+        if (int rc = sg_check_nn_args(a, &msg)) return fail(ctx, rc, msg);
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    SgFpsRange r;
+    for (int j = 0; j < 3; ++j) { r.lo[j] = range6 ? range6[j] : -INFINITY; r.hi[j] = range6 ? range6[3 + j] : INFINITY; }
+    SgNnGrid g{};
+    sg_nn_make_grid(range6, n_centres, &g);
+    if (n_total > 0) {
+        ENSURE(ctx, ctx->nn_entry, sg_nn_entries(n_frames, sg_nn_cell_budget(n_centres)));      // (by the budget, not the grid: the range changes no allocation)
+        ENSURE(ctx, ctx->nn_box, sg_nn_boxes(n_frames));
+        ENSURE(ctx, ctx->nn_rec, sg_nn_records(n_frames, n_centres) * (dtype == 0 ? sizeof(SgNnRec<float>) : sizeof(SgNnRec<double>)));
+    }
+    int e = sg_launch_nn(d_rows, dtype, n_total, d_frame_offsets, n_frames, d_keep_in, &r, &g, n_centres, d_centres, centre_features, k, ctx->nn_entry.p,
+                         ctx->nn_box.p, ctx->nn_rec.p, d_out_index, d_out_dist2, d_out_weight, stream ? (hipStream_t)stream : ctx->stream);
+    if (e) return fail(ctx, SNOWGPU_E_HIP, std::string("nearest centres launch: ") + hipGetErrorString((hipError_t)e));
     return SNOWGPU_OK;
 }
 

@@ -28,6 +28,9 @@ The reference's training-time caller (the OpenPCDet DENSE dataset: `root_path`, 
   * `range_image(frames_or_result, height, width)` projects the present rows of every frame into an H x W image of nearest returns
     (RangeImageBatch; snowgpu_range_image_device): the hand-off to a range-view network or de-noiser; `to_rows` brings its per-pixel
     prediction back to the rows as a keep mask for the next stage.
+  * `nearest_keypoints(frames_or_result, centres, k)` gives every row the k nearest centres of its frame and their inverse-distance
+    weights (NearestBatch; snowgpu_nearest_centres_device): pointnet2's three_nn, the way back from a KeypointBatch to the rows;
+    `interpolate` and `nearest` carry per-keypoint features, or a keep decision, back to the rows.
   * `augment_wet_batch_aligned(frames, ...)` is the snowfall + wet-ground chain with that aligned result (AlignedWetResult: per-frame
     flags beside it; snowgpu_augment_wet_batch_device_aligned), `wet_ground_batch_aligned(frames, keep)` the wet-ground stage alone on rows
     and a keep mask from any earlier stage (snowgpu_wet_ground_batch_device_aligned).
@@ -956,6 +959,142 @@ def range_image(frames, height, width, *, fov_up=3.0, fov_down=-25.0, ring=None,
                                    out.image.data_ptr(), out.index.data_ptr(), out.pixel_of.data_ptr() if n else 0, 0 if count is None else count.data_ptr(),
                                    run.cuda_stream)
     return out if return_count or out.count is None else RangeImageBatch(out.image, out.index, out.pixel_of)
+
+
+class NearestBatch:
+    """What nearest_keypoints() leaves behind, N = rows of the batch, k = neighbours, K = centres per frame -- every shape static: `index`
+    (N, k int32: per row its k nearest usable centres of its frame by (squared distance, centre number), as centre numbers 0 .. K - 1
+    WITHIN THE FRAME; -1 in a slot beyond the frame's usable centres and in every slot of an absent or unusable row), `dist2` (N, k; the
+    rows' dtype; +inf where the index is -1) and `weight` (N, k; the rows' dtype: pointnet2's normalised 1 / (dist + 1e-8); 0 where the
+    index is -1; None unless asked for).  `offsets` (host) and `n_centres` say which frame a row belongs to and how many centres a frame
+    has: flat_index(), interpolate() and nearest() are the way back from per-keypoint values to the rows -- pure indexing, no kernel of
+    this library.  All still being written until the stream the call was made on has caught up."""
+
+    def __init__(self, index, dist2, weight=None, offsets=None, n_centres=0):
+        self.index, self.dist2, self.weight, self.n_centres = index, dist2, weight, int(n_centres)
+        self.offsets = np.array([0, index.shape[0]], np.int64) if offsets is None else np.asarray(offsets, np.int64)
+        self._base = None
+
+    @classmethod
+    def empty(cls, offsets, n_centres, k=3, dtype=None, device=None, with_weights=True):
+        """Uninitialised buffers of the shapes nearest_keypoints() writes for a batch with these frame offsets (or, for one frame, this
+        number of rows) (out=): static addresses for a captured graph."""
+        import torch
+        dev = torch.device("cuda", torch.cuda.current_device() if device is None else int(device)) if not isinstance(device, torch.device) else device
+        off = np.array([0, int(offsets)], np.int64) if np.ndim(offsets) == 0 else np.asarray(offsets, np.int64)
+        n, dt = int(off[-1]), dtype or torch.float32
+        return cls(torch.empty((n, int(k)), dtype=torch.int32, device=dev), torch.empty((n, int(k)), dtype=dt, device=dev),
+                   torch.empty((n, int(k)), dtype=dt, device=dev) if with_weights else None, off, n_centres)
+
+    def flat_index(self):
+        """index + frame * K, -1 kept (N, k int64): gathers from per-keypoint values flattened to (F K, ...).  The first call of a batch of
+        several frames uploads their row counts (a few bytes; make it before capturing a graph); later calls reuse the result."""
+        import torch
+        idx = self.index.long()
+        if len(self.offsets) <= 2:
+            return idx
+        if self._base is None:
+            counts = torch.from_numpy(np.diff(self.offsets)).to(idx.device)
+            first = torch.arange(len(counts), device=idx.device) * self.n_centres
+            self._base = torch.repeat_interleave(first, counts, output_size=int(self.offsets[-1]))[:, None]
+        return torch.where(idx >= 0, idx + self._base, idx)
+
+    def _values(self, values, what):
+        import torch
+        F, K = len(self.offsets) - 1, self.n_centres
+        if not (torch.is_tensor(values) and values.dim() in (2, 3) and tuple(values.shape[:2]) == (F, K) and values.device == self.index.device):
+            raise ValueError(f"{what}: values must be a ({F}, {K}) or ({F}, {K}, D) tensor on the device of the rows: one value, or D of them, per keypoint")
+        return values.reshape(F * K, -1) if values.dim() == 3 else values.reshape(F * K)
+
+    def interpolate(self, features):
+        """three_interpolate: per-keypoint features (F, K, D) or (F, K) as per-row features (N, D) or (N,): the sum over the slots of
+        weight * features[index], in the features' dtype.  A row without a neighbour gets 0."""
+        if self.weight is None:
+            raise ValueError("interpolate: this NearestBatch has no weights (nearest_keypoints(..., return_weights=True))")
+        flat = self._values(features, "interpolate")
+        at = self.flat_index().clamp(min=0)               # (the weight of a -1 slot is 0)
+        w = self.weight.to(flat.dtype)
+        return (flat[at] * (w[..., None] if flat.dim() == 2 else w)).sum(dim=1)
+
+    def nearest(self, values, default=0):
+        """Voronoi labelling: every row gets the value of its nearest keypoint (slot 0) from per-keypoint values (F, K) or (F, K, D) --
+        a keypoint-level keep decision becomes a per-row mask for augment_batch(..., keep=) or dror_keep(..., keep=); `default` for a
+        row without a neighbour."""
+        import torch
+        flat = self._values(values, "nearest")
+        first = self.flat_index()[:, 0]
+        got = flat[first.clamp(min=0)]
+        has = first >= 0
+        return torch.where(has[:, None] if got.dim() == 2 else has, got, torch.full_like(got, default))
+
+
+def nearest_keypoints(frames, centres, k=3, *, point_cloud_range=None, keep=None, out=None, return_weights=True, device=None, slot=0):
+    """The k nearest centres of every row on the device (snowgpu_nearest_centres_device; the definition: include/snowgpu.h): pointnet2's
+    three_nn with its interpolation weights, the way back from keypoints to the rows of the batch.  A row takes part if it is present,
+    within 1e6 of the origin on every axis and inside point_cloud_range (None: no range); its neighbours are the usable centres of its
+    frame in the order of (squared distance in the rows' dtype, centre number).
+
+    frames    what ball_query takes -- torch CUDA tensors, a DeviceBatch, or an AlignedResult / AlignedWetResult: its rows, offsets and
+              keep mask are used (nothing is waited for).
+    centres   a KeypointBatch (its points), or an (F, K, 3 .. 5) tensor in the rows' dtype on their device: x, y, z first.
+    k         1 .. 8 neighbours per row.
+    keep      an input keep mask as the aligned calls take it (with a result: ANDed with the result's own).
+    out       a NearestBatch to write into (NearestBatch.empty): every element is written, nothing needs clearing.
+    return_weights   also fill `weight`.
+
+    Returns a NearestBatch; its interpolate() and nearest() carry per-keypoint values back to the rows.  Asynchronous on torch's current
+    stream; nothing is read on the host: capturable after one warm-up call."""
+    import torch
+    if isinstance(frames, AlignedResult):
+        res = frames
+        own = res.keep if res.keep.dtype == torch.bool else res.keep.view(torch.bool)
+        frames = DeviceBatch(res.rows, res.offsets)
+        keep = own if keep is None else (_keep_mask(torch, keep, res.rows, res.offsets) & own)
+    if not is_device_input(frames):
+        raise ValueError("nearest_keypoints: torch CUDA tensors or an aligned result (host arrays: lidar_snow_sim_amd.nearest.three_nn)")
+    if isinstance(k, bool) or int(k) != k:
+        raise ValueError("nearest_keypoints: k must be an integer")
+    k = int(k)
+    if not 1 <= k <= 8:
+        raise ValueError("nearest_keypoints: k must lie in 1 .. 8")
+    rng = None
+    if point_cloud_range is not None:
+        rng = np.asarray(point_cloud_range, np.float64).reshape(-1)
+        if rng.shape != (6,):
+            raise ValueError("nearest_keypoints: point_cloud_range holds 6 numbers (x0, y0, z0, x1, y1, z1)")
+    rows, offsets, _, eng = _resolve_input(torch, frames, False, device, slot)
+    dev = rows.device
+    nf, n = len(offsets) - 1, int(offsets[-1])
+    if keep is not None:
+        keep = _keep_mask(torch, keep, rows, offsets)
+    cen = centres.points if isinstance(centres, KeypointBatch) else centres
+    if not (torch.is_tensor(cen) and cen.dim() == 3 and cen.shape[0] == nf and cen.dtype == rows.dtype and cen.device == dev and cen.is_contiguous()):
+        raise ValueError("nearest_keypoints: centres must be a KeypointBatch or a contiguous (frames, K, 3 .. 5) tensor in the rows' dtype on their device")
+    K, Cq = int(cen.shape[1]), int(cen.shape[2])
+    # (the shapes below need these; the entry refuses them in the same words, and everything else of the domain)
+    if not 3 <= Cq <= 5:
+        raise ValueError("nearest_keypoints: centre_features must be 3, 4 or 5: x, y, z first (centres)")
+    if K < 1:
+        raise ValueError("nearest_keypoints: n_centres must be at least 1 (centres)")
+    if nf * K > 2 ** 31 - 1:
+        raise ValueError("nearest_keypoints: n_frames * n_centres exceeds 2^31 - 1; split the batch")
+    if out is None:
+        out = NearestBatch.empty(offsets, K, k, rows.dtype, dev, return_weights)
+    else:
+        want = (("index", torch.int32), ("dist2", rows.dtype)) + ((("weight", rows.dtype),) if return_weights else ())
+        for name, dtype in want:
+            t = getattr(out, name, None) if isinstance(out, NearestBatch) else None
+            if not (torch.is_tensor(t) and tuple(t.shape) == (n, k) and t.dtype == dtype and t.is_contiguous() and t.device == dev):
+                raise ValueError(f"nearest_keypoints: out must be a NearestBatch whose {name} is a contiguous {(n, k)} {dtype} tensor on the device of the rows")
+    weight = out.weight if return_weights else None
+    up = _uploads(eng)
+    with torch.cuda.device(dev), _on_run_stream(torch, eng, dev) as (_, run):
+        d_off = up.get(torch, dev, offsets, run)
+        eng.ctx.nearest_centres_device(nf, n, int(np.diff(offsets).max()), d_off.data_ptr(), rows.data_ptr() if n else 0, 0 if rows.dtype == torch.float32 else 1,
+                                       rng, K, cen.data_ptr(), Cq, k, 0 if keep is None or not n else keep.data_ptr(), out.index.data_ptr() if n else 0,
+                                       out.dist2.data_ptr() if n else 0, 0 if weight is None or not n else weight.data_ptr(), run.cuda_stream)
+    same = out.n_centres == K and np.array_equal(out.offsets, np.asarray(offsets, np.int64)) and (weight is None) == (out.weight is None)
+    return out if same else NearestBatch(out.index, out.dist2, weight, offsets, K)
 
 
 def augment_batch(frames, particle_file_prefix, beam_divergence, shuffle=True, noise_floor=0.7, root_path=None, *, planes=None,
