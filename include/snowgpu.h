@@ -816,6 +816,53 @@ int snowgpu_nearest_centres_device(snowgpu_ctx *ctx, int n_frames, int64_t n_tot
                                    int32_t *d_out_index, void *d_out_dist2, void *d_out_weight /* or NULL */, void *stream);
 
 /*
+ * POINTS IN 3D BOXES of an aligned batch: for every row the labelled box of its frame that contains it, and for every box the number of
+ * rows inside -- roiaware_pool3d.points_in_boxes_gpu (the point heads' target assignment), num_points_in_gt / filter_by_min_points and
+ * the inside / outside mask of GT-sampling, recomputed after augmentation, with static shapes.  Frames, rows (N_total x 5, float32 or
+ * float64 = T), frame offsets and the input keep mask as snowgpu_nearest_centres_device takes them.  F = n_frames, B = n_boxes per frame.
+ * The definition is restated as brute-force NumPy by tests/box_reference.py.
+ *   A row is USABLE when it is present and |x|, |y|, |z| <= 1e6 (false for NaN).  There is no range: a box is a range of its own.
+ *   BOXES: d_boxes is (F, B, Cb) in T, Cb = box_features in 7 .. 10, 1 <= B <= 256; columns 0 .. 6 are cx, cy, cz, dx, dy, dz, heading
+ *   (OpenPCDet's gt_boxes); further columns (class, velocity) are ignored.  A box is PRESENT when all seven values are finite,
+ *   |cx|, |cy|, |cz| <= 1e6, 0 < dx, dy, dz <= 1e6, |heading| <= 1e6 and its pose passes the check below.  The zero rows that OpenPCDet
+ *   pads gt_boxes with are absent by this rule.
+ *   POSE: (c, s) per box, float64, (F, B, 2).  With d_pose_in NULL the device computes c = cos((double)heading), s = sin((double)heading)
+ *   with the device library; otherwise the caller's values are used as they are.  A box whose pose is not finite or has
+ *   |(c c + s s) - 1| > 1e-6 (float64, every operation rounded on its own) is absent.  d_out_pose, when given, receives the pose that
+ *   was used, (0, 0) for an absent box.  This is the one place where the device library's rounding enters: everything below is defined
+ *   from the pose, so it is exact whichever pose was used.
+ *   MEMBERSHIP: all arithmetic in float64, every operation rounded on its own, no fused multiply-add.  sx = x - cx, sy = y - cy,
+ *   sz = z - cz; lx = sx c + sy s, ly = sy c - sx s.  A usable row is inside a present box of its frame when |sz| <= dz / 2,
+ *   |lx| < dx / 2 + 1e-5 and |ly| < dy / 2 + 1e-5: check_pt_in_box3d of pcdet's roiaware_pool3d -- z closed, x and y strict with its 1e-5
+ *   margin, the box's z its CENTRE.  pcdet's op makes the same test in float32 with cosf / sinf of -heading: the two differ only for
+ *   rows within float32 rounding of a face.
+ * Outputs, every shape static, every element written by every call:
+ *   d_out_box_of  (N_total) int32: the SMALLEST present box number of the row's frame that contains it, 0 .. B - 1 ("first box wins", as
+ *                 pcdet's loop); -1 for a row in no box and for absent and unusable rows
+ *   d_out_count   (F, B) int32, or NULL: the usable rows of frame f inside box b -- every containing box counts, overlaps included; 0 for
+ *                 an absent box
+ *   d_out_local   (N_total, 3) T, or NULL: (T)lx, (T)ly, (T)sz with respect to box_of -- Part-A2's intra-object part location before its
+ *                 normalisation --, zeros where box_of is -1
+ *   d_out_pose    (F, B, 2) float64, or NULL
+ * Domain: 1 <= B <= 256; box_features in 7 .. 10; F B <= 2^31 - 1; n_total < 2^31; no frame above 2^30 rows; dtype 0 or 1; every output
+ * apart from the rows, the keep mask, the boxes, the given pose and every other output.  Anything else is SNOWGPU_E_INVALID.  A batch
+ * without a row writes zeros to the counts, writes the pose and launches nothing over rows (d_rows and d_out_box_of may be NULL).
+ * The result depends on neither a cell order nor the arrival of atomics: two calls give identical bytes.
+ * The B boxes of every frame are filed, not the rows: one workgroup per frame writes a record of eight doubles per box and marks every
+ * present box, by atomicOr, in each cell of a 64 x 64 x-y grid over +-120 m that its footprint -- inflated for the margin, the pose
+ * tolerance and the float64 rounding -- can touch; a cell is ceil(B / 64) 64-bit words, and the border cells reach to infinity.  Then
+ * ONE LANE per row reads its cell's words and makes the membership test for every set bit, ascending; the counts are integer atomic
+ * adds, equal boxes folded across the wave first (csrc/sg_box.h: the footprint bound and its derivation; csrc/snowgpu_box.hip).
+ * Scratch in the context, grown on first use: per frame 4097 ceil(B / 64) words and B records.  Two kernels on `stream`, no memset;
+ * nothing is read on the host, nothing allocated after the first call of a size: capturable as a linear graph.
+ */
+int snowgpu_points_in_boxes_device(snowgpu_ctx *ctx, int n_frames, int64_t n_total, int64_t max_frame_rows, const int64_t *d_frame_offsets,
+                                   const void *d_rows, int dtype, int n_boxes, const void *d_boxes, int box_features,
+                                   const double *d_pose_in /* or NULL */, const uint8_t *d_keep_in /* or NULL: all present */,
+                                   int32_t *d_out_box_of, int32_t *d_out_count /* or NULL */, void *d_out_local /* or NULL */,
+                                   double *d_out_pose /* or NULL */, void *stream);
+
+/*
  * PER-FRAME WEATHER in one aligned call.  snowgpu_augment_wet_batch_device_aligned_masked applies one weather to every frame, its wet
  * settings host scalars that a captured graph bakes in.  Here every frame brings a record of 8 doubles in DEVICE memory,
  *     d_weather[f] = [snow, wet, water_height, pavement_depth, wet_noise_floor, power_factor, delta, 0]

@@ -31,7 +31,7 @@ EXPORTS = [
     "snowgpu_augment_batch_device_aligned_masked", "snowgpu_augment_wet_batch_device_aligned_masked", "snowgpu_fov_mask_device",
     "snowgpu_augment_weather_batch_device_aligned", "snowgpu_draw_weather_device", "snowgpu_dror_mask_device",
     "snowgpu_voxelize_device", "snowgpu_fps_device", "snowgpu_ball_query_device", "snowgpu_range_image_device",
-    "snowgpu_nearest_centres_device",
+    "snowgpu_nearest_centres_device", "snowgpu_points_in_boxes_device",
 ]
 
 WET_ESTIMATION = {"linear": 0, "poly": 1}
@@ -156,6 +156,9 @@ def lib():
             L.snowgpu_nearest_centres_device.restype = ctypes.c_int
             L.snowgpu_nearest_centres_device.argtypes = [vp, ctypes.c_int, i64, i64, vp, vp, ctypes.c_int, vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int,
                                                          vp, vp, vp, vp, vp]
+            L.snowgpu_points_in_boxes_device.restype = ctypes.c_int
+            L.snowgpu_points_in_boxes_device.argtypes = [vp, ctypes.c_int, i64, i64, vp, vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, vp, vp, vp, vp, vp,
+                                                         vp, vp]
             L.snowgpu_set_fov_precrop.restype = ctypes.c_int
             L.snowgpu_set_fov_precrop.argtypes = [vp, ctypes.c_int]
             L.snowgpu_last_status.restype = ctypes.c_int
@@ -631,6 +634,21 @@ class Context:
                                                     int(dtype_code), None if rng is None else _p(rng), i32(n_centres), vp(d_centres or None),
                                                     i32(centre_features), i32(k), vp(d_keep_in or None), vp(d_out_index or None),
                                                     vp(d_out_dist2 or None), vp(d_out_weight or None), vp(stream or None))
+        if rc == E_INVALID:
+            raise ValueError(self._L.snowgpu_last_error(self._h).decode())
+        self._check(rc)
+
+    def points_in_boxes_device(self, n_frames, n_total, max_frame_rows, d_frame_off, d_rows, dtype_code, n_boxes, d_boxes, box_features, d_pose_in,
+                               d_keep_in, d_out_box_of, d_out_count, d_out_local, d_out_pose, stream=0):
+        """The box of every row and the rows of every box (include/snowgpu.h: snowgpu_points_in_boxes_device); asynchronous on `stream`.
+        d_pose_in, d_keep_in, d_out_count, d_out_local and d_out_pose may be 0.  An argument outside the domain, or an output overlapping
+        the mask, the rows, the boxes, the given pose or another output, raises ValueError with the entry's words."""
+        vp = ctypes.c_void_p
+        i32 = lambda v: max(-(2 ** 31), min(int(v), 2 ** 31 - 1))
+        rc = self._L.snowgpu_points_in_boxes_device(self._h, int(n_frames), int(n_total), int(max_frame_rows), vp(d_frame_off or None), vp(d_rows or None),
+                                                    int(dtype_code), i32(n_boxes), vp(d_boxes or None), i32(box_features), vp(d_pose_in or None),
+                                                    vp(d_keep_in or None), vp(d_out_box_of or None), vp(d_out_count or None), vp(d_out_local or None),
+                                                    vp(d_out_pose or None), vp(stream or None))
         if rc == E_INVALID:
             raise ValueError(self._L.snowgpu_last_error(self._h).decode())
         self._check(rc)

@@ -307,6 +307,13 @@ struct SgNnGrid;
 int sg_launch_nn(const void *rows, int dtype, int64_t n, const int64_t *frame_off, int n_frames, const uint8_t *keep_in, const struct SgFpsRange *range,
                  const struct SgNnGrid *g, int32_t n_centres, const void *centres, int32_t centre_features, int k, uint32_t *entry, int32_t *box, void *rec,
                  int32_t *out_index, void *out_dist, void *out_weight, void *stream);
+// Points in 3D boxes (sg_box.h; the definition: include/snowgpu.h): two kernels.  Scratch: rec, sg_box_records(n_frames, n_boxes) records;
+// table, sg_box_table(n_frames, n_boxes) words.  pose_in, out_count, out_local and out_pose may be null.  A batch without a row runs the
+// first kernel alone: the counts and the pose.
+struct SgBoxRec;
+int sg_launch_box(const void *rows, int dtype, int64_t n, const int64_t *frame_off, int n_frames, const uint8_t *keep_in, int32_t n_boxes,
+                  const void *boxes, int32_t box_features, const double *pose_in, struct SgBoxRec *rec, unsigned long long *table, int32_t *out_box_of,
+                  int32_t *out_count, void *out_local, double *out_pose, void *stream);
 #ifdef __cplusplus
 }
 #endif

@@ -408,6 +408,56 @@ static inline int sg_check_nn_args(const SgNnArgs &a, std::string *msg)
     return 0;
 }
 
+// ---- snowgpu_points_in_boxes_device -------------------------------------------------------------------------------------------------------
+struct SgBoxArgs {
+    int n_frames;
+    int64_t n_total, max_frame_rows;
+    int dtype;
+    const int64_t *frame_off;
+    const void *rows;
+    int n_boxes;                      // B, per frame
+    const void *boxes;
+    int box_features;                 // Cb
+    const double *pose_in;            // or NULL: cos / sin of the heading on the device
+    const uint8_t *keep_in;
+    int32_t *out_box_of;
+    int32_t *out_count;               // or NULL
+    void *out_local;                  // or NULL
+    double *out_pose;                 // or NULL
+};
+
+// 0, or SG_ARGS_INVALID with *msg.  As above, the order is part of the ABI.
+static inline int sg_check_box_args(const SgBoxArgs &a, std::string *msg)
+{
+    static const char *who = "snowgpu_points_in_boxes_device";
+    if (a.n_frames <= 0 || a.n_total < 0 || !a.frame_off || !a.boxes || (a.n_total > 0 && (!a.rows || !a.out_box_of)) || (a.dtype != 0 && a.dtype != 1))
+        return sg_refuse(who, ": null pointer or bad dtype", msg);
+    if (a.n_total >= ((int64_t)1 << 31)) return sg_refuse("", "batch too large: split it below 2^31 rows", msg);
+    if (a.n_boxes < 1 || a.n_boxes > 256) return sg_refuse(who, ": n_boxes must lie in 1 .. 256", msg);
+    if (a.box_features < 7 || a.box_features > 10) return sg_refuse(who, ": box_features must lie in 7 .. 10: cx, cy, cz, dx, dy, dz, heading first", msg);
+    if ((int64_t)a.n_frames * a.n_boxes > ((int64_t)1 << 31) - 1) return sg_refuse(who, ": n_frames * n_boxes exceeds 2^31 - 1; split the batch", msg);
+    if (sg_max_frame(a.max_frame_rows, a.n_total) > ((int64_t)1 << 30))
+        return sg_refuse(who, ": a frame of more than 2^30 rows; split it", msg);
+    const size_t esz = a.dtype == 0 ? 4 : 8, q = (size_t)a.n_frames * (size_t)a.n_boxes, n = (size_t)a.n_total;
+    const struct { const void *p; size_t bytes; const char *name; } outs[4] = {
+        {a.out_box_of, n * 4, "d_out_box_of"}, {a.out_count, q * 4, "d_out_count"}, {a.out_local, n * 3 * esz, "d_out_local"}, {a.out_pose, q * 16, "d_out_pose"}};
+    for (int i = 0; i < 4; ++i) {
+        const auto &o = outs[i];
+        if (sg_ranges_meet(o.p, o.bytes, a.keep_in, n))
+            return sg_refuse(who, (std::string(": ") + o.name + " overlaps d_keep_in; the mask is read while the labels are written: pass a buffer apart from it").c_str(), msg);
+        if (sg_ranges_meet(o.p, o.bytes, a.rows, n * 5 * esz))
+            return sg_refuse(who, (std::string(": ") + o.name + " overlaps d_rows; the rows are read while the labels are written: pass a buffer apart from them").c_str(), msg);
+        if (sg_ranges_meet(o.p, o.bytes, a.boxes, q * (size_t)a.box_features * esz))
+            return sg_refuse(who, (std::string(": ") + o.name + " overlaps d_boxes; the boxes are read while the labels are written: pass a buffer apart from them").c_str(), msg);
+        if (sg_ranges_meet(o.p, o.bytes, a.pose_in, q * 16))
+            return sg_refuse(who, (std::string(": ") + o.name + " overlaps d_pose_in; the pose is read while the labels are written: pass a buffer apart from it").c_str(), msg);
+        for (int j = 0; j < i; ++j)
+            if (sg_ranges_meet(o.p, o.bytes, outs[j].p, outs[j].bytes))
+                return sg_refuse(who, (std::string(": ") + o.name + " overlaps " + outs[j].name + "; every output needs memory of its own").c_str(), msg);
+    }
+    return 0;
+}
+
 // 0, or SG_ARGS_INVALID with *msg (built on this path only).  The order is part of the ABI: it decides which message a doubly wrong call gets.
 static inline int sg_check_device_args(const SgDeviceArgs &a, const SgCtxView &c, const SgEntryShape &s, std::string *msg)
 {

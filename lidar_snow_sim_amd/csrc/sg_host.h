@@ -105,6 +105,9 @@ struct __attribute__((visibility("default"))) snowgpu_ctx {
     DevBuf<uint32_t> nn_entry;
     DevBuf<int32_t> nn_box;
     DevBuf<uint8_t> nn_rec;
+    // points in boxes (snowgpu_points_in_boxes_device): one record of eight doubles per box, and per frame the bit table of its cells
+    DevBuf<double> box_rec;
+    DevBuf<unsigned long long> box_table;
     // scratch shared by every batch
     DevBuf<int32_t> tile_hist, tile_base, perm, ctile_cnt, ctile_base, table_ids, out_src;
     DevBuf<uint8_t> srows;            // channel-sorted copy of the frames whose rows did not come channel-sorted (firing order)

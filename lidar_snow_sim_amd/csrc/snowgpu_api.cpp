@@ -147,6 +147,7 @@ extern "C" void snowgpu_destroy(snowgpu_ctx *ctx)
     ctx->ball_entry.release(); ctx->ball_cell.release(); ctx->ball_x.release(); ctx->ball_y.release(); ctx->ball_z.release(); ctx->ball_src.release();
     ctx->range_key.release();
     ctx->nn_entry.release(); ctx->nn_box.release(); ctx->nn_rec.release();
+    ctx->box_rec.release(); ctx->box_table.release();
     sg_prepass_release(&ctx->prepass);
     sg_plane_release(&ctx->plane_scr);
     ctx->plane_est.release(); ctx->wet_plane_est.release(); ctx->plane_info.release(); ctx->stats_hist.release(); ctx->stats_rec.release();

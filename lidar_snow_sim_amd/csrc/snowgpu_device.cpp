@@ -1,5 +1,5 @@
 // snowgpu_device.cpp -- the entries of the C ABI (include/snowgpu.h) that take DEVICE pointers and enqueue on the caller's stream: every
-// *_batch_device* entry, the plane estimate, the FOV mask, the outlier filter, the voxel stage, the keypoint stage, the ball query, the range image, the nearest centres and the weather draw.  Each batch entry fills an SgDeviceArgs, has it checked
+// *_batch_device* entry, the plane estimate, the FOV mask, the outlier filter, the voxel stage, the keypoint stage, the ball query, the range image, the nearest centres, the points in boxes and the weather draw.  Each batch entry fills an SgDeviceArgs, has it checked
 // (sg_device_args.h: every refusal, in one order), sets the device and runs batch_from_args() and the stages it needs.  The launch
 // sequence of a batch is snowgpu_batch.cpp; no host copy, no synchronisation, no allocation after the first call of a given size.
 #include "sg_host.h"
@@ -10,6 +10,7 @@
 #include "sg_fps.h"         // the range of the keypoint stage and the size of its scratch
 #include "sg_ball.h"        // the grid of the ball query and the sizes of its scratch
 #include "sg_nn.h"          // the grid of the nearest-centres stage and the sizes of its scratch
+#include "sg_box.h"         // the record of a box and the sizes of the box stage's scratch
 #include "sg_range.h"       // the geometry of the range image and the limits in the rows' dtype
 
 static_assert(SG_ARGS_INVALID == SNOWGPU_E_INVALID && SG_PLANE_REFERENCE == 0, "sg_device_args.h restates these two");
@@ -554,6 +555,28 @@ extern "C" int snowgpu_nearest_centres_device(snowgpu_ctx *ctx, int n_frames, in
     int e = sg_launch_nn(d_rows, dtype, n_total, d_frame_offsets, n_frames, d_keep_in, &r, &g, n_centres, d_centres, centre_features, k, ctx->nn_entry.p,
                          ctx->nn_box.p, ctx->nn_rec.p, d_out_index, d_out_dist2, d_out_weight, stream ? (hipStream_t)stream : ctx->stream);
     if (e) return fail(ctx, SNOWGPU_E_HIP, std::string("nearest centres launch: ") + hipGetErrorString((hipError_t)e));
+    return SNOWGPU_OK;
+}
+
+// Points in 3D boxes (snowgpu_box.hip; presence, the record, the membership test, the grid and its footprint: sg_box.h).  See include/snowgpu.h.
+extern "C" int snowgpu_points_in_boxes_device(snowgpu_ctx *ctx, int n_frames, int64_t n_total, int64_t max_frame_rows, const int64_t *d_frame_offsets,
+                                              const void *d_rows, int dtype, int n_boxes, const void *d_boxes, int box_features, const double *d_pose_in,
+                                              const uint8_t *d_keep_in, int32_t *d_out_box_of, int32_t *d_out_count, void *d_out_local, double *d_out_pose,
+                                              void *stream)
+{
+    if (!ctx) return SNOWGPU_E_INVALID;
+    const SgBoxArgs a{n_frames, n_total, max_frame_rows, dtype, d_frame_offsets, d_rows, n_boxes, d_boxes, box_features, d_pose_in, d_keep_in,
+                      d_out_box_of, d_out_count, d_out_local, d_out_pose};
+    {
+        std::string msg;
+        if (int rc = sg_check_box_args(a, &msg)) return fail(ctx, rc, msg);
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    ENSURE(ctx, ctx->box_rec, sg_box_records(n_frames, n_boxes) * (sizeof(SgBoxRec) / sizeof(double)));
+    ENSURE(ctx, ctx->box_table, sg_box_table(n_frames, n_boxes));
+    int e = sg_launch_box(d_rows, dtype, n_total, d_frame_offsets, n_frames, d_keep_in, n_boxes, d_boxes, box_features, d_pose_in, (SgBoxRec *)ctx->box_rec.p,
+                          ctx->box_table.p, d_out_box_of, d_out_count, d_out_local, d_out_pose, stream ? (hipStream_t)stream : ctx->stream);
+    if (e) return fail(ctx, SNOWGPU_E_HIP, std::string("points in boxes launch: ") + hipGetErrorString((hipError_t)e));
     return SNOWGPU_OK;
 }
 

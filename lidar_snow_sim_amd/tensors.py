@@ -31,6 +31,9 @@ The reference's training-time caller (the OpenPCDet DENSE dataset: `root_path`, 
   * `nearest_keypoints(frames_or_result, centres, k)` gives every row the k nearest centres of its frame and their inverse-distance
     weights (NearestBatch; snowgpu_nearest_centres_device): pointnet2's three_nn, the way back from a KeypointBatch to the rows;
     `interpolate` and `nearest` carry per-keypoint features, or a keep decision, back to the rows.
+  * `points_in_boxes(frames_or_result, boxes)` labels every row with the 3D box of its frame that contains it and counts the rows of
+    every box (BoxLabelBatch; snowgpu_points_in_boxes_device): roiaware_pool3d's points_in_boxes_gpu and num_points_in_gt after the
+    augmentation; `labels`, `keep_boxes` and `rows_in` are the point heads' targets, filter_by_min_points and a keep mask of the objects.
   * `augment_wet_batch_aligned(frames, ...)` is the snowfall + wet-ground chain with that aligned result (AlignedWetResult: per-frame
     flags beside it; snowgpu_augment_wet_batch_device_aligned), `wet_ground_batch_aligned(frames, keep)` the wet-ground stage alone on rows
     and a keep mask from any earlier stage (snowgpu_wet_ground_batch_device_aligned).
@@ -1095,6 +1098,139 @@ def nearest_keypoints(frames, centres, k=3, *, point_cloud_range=None, keep=None
                                        out.dist2.data_ptr() if n else 0, 0 if weight is None or not n else weight.data_ptr(), run.cuda_stream)
     same = out.n_centres == K and np.array_equal(out.offsets, np.asarray(offsets, np.int64)) and (weight is None) == (out.weight is None)
     return out if same else NearestBatch(out.index, out.dist2, weight, offsets, K)
+
+
+class BoxLabelBatch:
+    """What points_in_boxes() leaves behind, N = rows of the batch, F = frames, B = boxes per frame -- every shape static: `box_of` (N
+    int32: the smallest present box number of the row's frame that contains the row, 0 .. B - 1; -1 for a row in no box and for an absent
+    or unusable row), `count` (F, B int32: the usable rows inside every box, overlaps included, 0 for an absent box; None unless asked
+    for), `local` (N, 3 in the rows' dtype: the row in the frame of its box -- along its length, its width, and up from its centre; zeros
+    where box_of is -1; None unless asked for) and `pose` (F, B, 2 float64: the (cos, sin) of the heading that was used, (0, 0) for an
+    absent box; None unless asked for).  `offsets` (host) and `n_boxes` say which frame a row belongs to: flat_index(), labels(),
+    keep_boxes() and rows_in() are pure indexing, no kernel of this library.  All still being written until the stream the call was made
+    on has caught up."""
+
+    def __init__(self, box_of, count, local=None, pose=None, offsets=None, n_boxes=0):
+        self.box_of, self.count, self.local, self.pose, self.n_boxes = box_of, count, local, pose, int(n_boxes)
+        self.offsets = np.array([0, box_of.shape[0]], np.int64) if offsets is None else np.asarray(offsets, np.int64)
+        self._base = None
+
+    @classmethod
+    def empty(cls, offsets, n_boxes, dtype=None, device=None, with_count=True, with_local=False, with_pose=False):
+        """Uninitialised buffers of the shapes points_in_boxes() writes for a batch with these frame offsets (or, for one frame, this
+        number of rows) (out=): static addresses for a captured graph."""
+        import torch
+        dev = torch.device("cuda", torch.cuda.current_device() if device is None else int(device)) if not isinstance(device, torch.device) else device
+        off = np.array([0, int(offsets)], np.int64) if np.ndim(offsets) == 0 else np.asarray(offsets, np.int64)
+        n, nf, B = int(off[-1]), len(off) - 1, int(n_boxes)
+        return cls(torch.empty(n, dtype=torch.int32, device=dev), torch.empty((nf, B), dtype=torch.int32, device=dev) if with_count else None,
+                   torch.empty((n, 3), dtype=dtype or torch.float32, device=dev) if with_local else None,
+                   torch.empty((nf, B, 2), dtype=torch.float64, device=dev) if with_pose else None, off, B)
+
+    def flat_index(self):
+        """box_of + frame * B, -1 kept (N int64): gathers from per-box values flattened to (F B, ...).  The first call of a batch of
+        several frames uploads their row counts (a few bytes; make it before capturing a graph); later calls reuse the result."""
+        import torch
+        idx = self.box_of.long()
+        if len(self.offsets) <= 2:
+            return idx
+        if self._base is None:
+            counts = torch.from_numpy(np.diff(self.offsets)).to(idx.device)
+            first = torch.arange(len(counts), device=idx.device) * self.n_boxes
+            self._base = torch.repeat_interleave(first, counts, output_size=int(self.offsets[-1]))
+        return torch.where(idx >= 0, idx + self._base, idx)
+
+    def labels(self, per_box, background=0):
+        """Per-box values (F, B) or (F, B, D) -- the class column of gt_boxes, say -- as per-row values (N,) or (N, D): the value of the
+        row's box, `background` for a row in no box.  The point heads' point_cls_labels."""
+        import torch
+        F, B = len(self.offsets) - 1, self.n_boxes
+        if not (torch.is_tensor(per_box) and per_box.dim() in (2, 3) and tuple(per_box.shape[:2]) == (F, B) and per_box.device == self.box_of.device):
+            raise ValueError(f"labels: per_box must be a ({F}, {B}) or ({F}, {B}, D) tensor on the device of the rows: one value, or D of them, per box")
+        flat = per_box.reshape(F * B, -1) if per_box.dim() == 3 else per_box.reshape(F * B)
+        at = self.flat_index()
+        got = flat[at.clamp(min=0)]
+        has = at >= 0
+        return torch.where(has[:, None] if got.dim() == 2 else has, got, torch.full_like(got, background))
+
+    def keep_boxes(self, min_points=1):
+        """(F, B) bool: count >= min_points, min_points >= 1 -- filter_by_min_points after the augmentation; an absent box is never kept."""
+        if self.count is None:
+            raise ValueError("keep_boxes: this BoxLabelBatch has no count (points_in_boxes(..., return_count=True))")
+        if isinstance(min_points, bool) or int(min_points) != min_points or int(min_points) < 1:
+            raise ValueError("keep_boxes: min_points must be an integer of at least 1")
+        return self.count >= int(min_points)
+
+    def rows_in(self, box_mask=None):
+        """(N,) bool: the rows inside a box -- with box_mask (F, B bool), inside a box whose entry is set, judged by the row's own box
+        (box_of).  A keep mask for augment_batch(..., keep=) or dror_keep(..., keep=); its negation clears a pasted object's place."""
+        import torch
+        if box_mask is None:
+            return self.box_of >= 0
+        F, B = len(self.offsets) - 1, self.n_boxes
+        if not (torch.is_tensor(box_mask) and box_mask.dtype == torch.bool and tuple(box_mask.shape) == (F, B) and box_mask.device == self.box_of.device):
+            raise ValueError(f"rows_in: box_mask must be a ({F}, {B}) bool tensor on the device of the rows")
+        at = self.flat_index()
+        return (at >= 0) & box_mask.reshape(F * B)[at.clamp(min=0)]
+
+
+def points_in_boxes(frames, boxes, *, pose=None, keep=None, out=None, return_count=True, return_local=False, return_pose=False, device=None, slot=0):
+    """The box of every row and the rows of every box on the device (snowgpu_points_in_boxes_device; the definition: include/snowgpu.h):
+    roiaware_pool3d's points_in_boxes_gpu with check_pt_in_box3d's faces -- z closed, x and y strict with the 1e-5 margin -- in float64.
+    A row takes part if it is present and within 1e6 of the origin on every axis.
+
+    frames    what nearest_keypoints takes -- torch CUDA tensors, a DeviceBatch, or an AlignedResult / AlignedWetResult: its rows,
+              offsets and keep mask are used (nothing is waited for).
+    boxes     a contiguous (F, B, 7 .. 10) tensor in the rows' dtype on their device, 1 <= B <= 256: cx, cy, cz, dx, dy, dz, heading
+              first (OpenPCDet's gt_boxes; its zero rows are absent boxes).
+    pose      None: cos / sin of the heading in float64 on the device; or a contiguous (F, B, 2) float64 tensor (cos, sin) used as it is.
+    keep      an input keep mask as the aligned calls take it (with a result: ANDed with the result's own).
+    out       a BoxLabelBatch to write into (BoxLabelBatch.empty): every element is written, nothing needs clearing.
+
+    Returns a BoxLabelBatch.  Asynchronous on torch's current stream; nothing is read on the host: capturable after one warm-up call."""
+    import torch
+    if isinstance(frames, AlignedResult):
+        res = frames
+        own = res.keep if res.keep.dtype == torch.bool else res.keep.view(torch.bool)
+        frames = DeviceBatch(res.rows, res.offsets)
+        keep = own if keep is None else (_keep_mask(torch, keep, res.rows, res.offsets) & own)
+    if not is_device_input(frames):
+        raise ValueError("points_in_boxes: torch CUDA tensors or an aligned result (host arrays: lidar_snow_sim_amd.boxes.points_in_boxes)")
+    rows, offsets, _, eng = _resolve_input(torch, frames, False, device, slot)
+    dev = rows.device
+    nf, n = len(offsets) - 1, int(offsets[-1])
+    if keep is not None:
+        keep = _keep_mask(torch, keep, rows, offsets)
+    if not (torch.is_tensor(boxes) and boxes.dim() == 3 and boxes.shape[0] == nf and boxes.dtype == rows.dtype and boxes.device == dev and boxes.is_contiguous()):
+        raise ValueError("points_in_boxes: boxes must be a contiguous (frames, B, 7 .. 10) tensor in the rows' dtype on their device")
+    B, Cb = int(boxes.shape[1]), int(boxes.shape[2])
+    # (the shapes below need these; the entry refuses them in the same words, and everything else of the domain)
+    if not 1 <= B <= 256:
+        raise ValueError("points_in_boxes: n_boxes must lie in 1 .. 256 (boxes)")
+    if not 7 <= Cb <= 10:
+        raise ValueError("points_in_boxes: box_features must lie in 7 .. 10: cx, cy, cz, dx, dy, dz, heading first (boxes)")
+    if pose is not None and not (torch.is_tensor(pose) and tuple(pose.shape) == (nf, B, 2) and pose.dtype == torch.float64 and pose.device == dev and pose.is_contiguous()):
+        raise ValueError(f"points_in_boxes: pose must be a contiguous {(nf, B, 2)} float64 tensor (cos, sin) on the device of the rows")
+    want = (("box_of", torch.int32, (n,), True), ("count", torch.int32, (nf, B), return_count), ("local", rows.dtype, (n, 3), return_local),
+            ("pose", torch.float64, (nf, B, 2), return_pose))
+    if out is None:
+        out = BoxLabelBatch.empty(offsets, B, rows.dtype, dev, return_count, return_local, return_pose)
+    else:
+        for name, dtype, shape, asked in want:
+            t = getattr(out, name, None) if isinstance(out, BoxLabelBatch) else None
+            if asked and not (torch.is_tensor(t) and tuple(t.shape) == shape and t.dtype == dtype and t.is_contiguous() and t.device == dev):
+                raise ValueError(f"points_in_boxes: out must be a BoxLabelBatch whose {name} is a contiguous {shape} {dtype} tensor on the device of the rows")
+    count, local, used = (out.count if return_count else None), (out.local if return_local else None), (out.pose if return_pose else None)
+    up = _uploads(eng)
+    with torch.cuda.device(dev), _on_run_stream(torch, eng, dev) as (_, run):
+        d_off = up.get(torch, dev, offsets, run)
+        eng.ctx.points_in_boxes_device(nf, n, int(np.diff(offsets).max()), d_off.data_ptr(), rows.data_ptr() if n else 0, 0 if rows.dtype == torch.float32 else 1,
+                                       B, boxes.data_ptr(), Cb, 0 if pose is None else pose.data_ptr(), 0 if keep is None or not n else keep.data_ptr(),
+                                       out.box_of.data_ptr() if n else 0, 0 if count is None else count.data_ptr(),
+                                       0 if local is None or not n else local.data_ptr(), 0 if used is None else used.data_ptr(), run.cuda_stream)
+    same = (out.n_boxes == B and np.array_equal(out.offsets, np.asarray(offsets, np.int64)) and (count is None) == (out.count is None) and
+            (local is None) == (out.local is None) and (used is None) == (out.pose is None))
+    return out if same else BoxLabelBatch(out.box_of, count, local, used, offsets, B)
 
 
 def augment_batch(frames, particle_file_prefix, beam_divergence, shuffle=True, noise_floor=0.7, root_path=None, *, planes=None,
