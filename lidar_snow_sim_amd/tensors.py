@@ -544,16 +544,26 @@ def dror_keep(frames, alpha=0.45, beta=3, k_min=3, sr_min=0.04, keep=None, *, ou
     the row is usable -- present under `keep`, every coordinate finite and within 1e6 m -- and has at least k_min other usable rows of its
     frame within max(sr_min, beta * radians(alpha) * r_xy) of it (the definition: include/snowgpu.h, snowgpu_dror_mask_device).
 
-    keep      an input keep mask as augment_batch(layout='aligned') takes it: an absent row is False, nobody's neighbour, never looked at.
+    frames    torch CUDA tensors, a DeviceBatch -- or an AlignedResult / AlignedWetResult: its rows, offsets and keep mask are used
+              (nothing is waited for), as voxelize and the stages behind it take one.
+    keep      an input keep mask as augment_batch(layout='aligned') takes it: an absent row is False, nobody's neighbour, never looked at
+              (with a result: ANDed with the result's own).
     out       a torch.bool tensor with one element per row to write into (static addresses for a captured graph); not the `keep` tensor.
     return_neighbours   also return an int32 tensor: every row's neighbours, counted up to k_min.
 
     The mask goes straight into augment_batch(..., layout='aligned', keep=mask), augment_wet_batch_aligned(..., keep=mask) or
-    fov_keep(..., keep=mask); dror_keep(res.rows, keep=res.keep) filters an augmented batch.  Asynchronous on torch's current stream."""
-    if not is_device_input(frames):
-        raise ValueError("dror_keep: torch CUDA tensors (host arrays: lidar_snow_sim_amd.dror.dynamic_radius_outlier_filter)")
+    fov_keep(..., keep=mask); dror_keep(res) filters an augmented batch frame by frame.  dror_keep(res.rows, keep=res.keep) is NOT that
+    for a batch of several frames: one N_total x 5 tensor is ONE frame, and rows of different frames become each other's neighbours.
+    Asynchronous on torch's current stream."""
     import math
     import torch
+    if isinstance(frames, AlignedResult):
+        res = frames
+        own = res.keep if res.keep.dtype == torch.bool else res.keep.view(torch.bool)
+        frames = DeviceBatch(res.rows, res.offsets)
+        keep = own if keep is None else (_keep_mask(torch, keep, res.rows, res.offsets) & own)
+    if not is_device_input(frames):
+        raise ValueError("dror_keep: torch CUDA tensors or an aligned result (host arrays: lidar_snow_sim_amd.dror.dynamic_radius_outlier_filter)")
     c = float(beta) * (float(alpha) * (math.pi / 180.0))
     if not (0.0 < c <= 0.25):
         raise ValueError("dror_keep: beta * radians(alpha) must lie in (0, 0.25]")
