@@ -687,6 +687,67 @@ int snowgpu_fps_device(snowgpu_ctx *ctx, int n_frames, int64_t n_total, int64_t 
                        void *d_out_points /* or NULL */, void *d_out_dist /* or NULL */, int32_t *d_out_usable, void *stream);
 
 /*
+ * SECTORIZED, PROPOSAL-CENTRIC KEYPOINTS of an aligned batch: PV-RCNN++'s replacement for the plain farthest-point walk -- keep the rows
+ * near a region proposal (its sample_points_with_roi), split them by azimuth into sectors, and walk every sector on its own with a quota
+ * proportional to its share of the rows (its sector_fps) --, with static shapes.  Frames, rows (N_total x 5, float32 or float64 = T),
+ * frame offsets, keep mask, range6, K = n_samples and C = n_features exactly as snowgpu_fps_device takes them; S = n_sectors, 1 <= S <= 16;
+ * d_rois NULL or (F, B, Cb) in T, B = n_rois in 1 .. 256, Cb = roi_features in 7 .. 10, columns 0 .. 5 cx, cy, cz, dx, dy, dz (OpenPCDet's
+ * rois / gt_boxes; the heading and everything behind it are ignored); roi_margin a host double, finite and >= 0 (PV-RCNN++'s
+ * SAMPLE_RADIUS_WITH_ROI is 1.6).  Without rois n_rois, roi_features and roi_margin are not read.  The definition is restated in NumPy
+ * by tests/fps_sectors_reference.py.
+ *   USABLE: as for snowgpu_fps_device -- present, |x|, |y|, |z| <= 1e6 (false for NaN), inside the range when there is one -- and, when
+ *   d_rois is given, NEAR A PRESENT ROI OF ITS FRAME.  A roi is present by the box stage's rule on its first six values: all finite,
+ *   |cx|, |cy|, |cz| <= 1e6, 0 < dx, dy, dz <= 1e6; the zero rows OpenPCDet pads with are absent.  In float64, every operation rounded on
+ *   its own, no fused multiply-add:
+ *     reach  = sqrt(((dx/2)(dx/2) + (dy/2)(dy/2)) + (dz/2)(dz/2)) + roi_margin        reach2 = reach reach
+ *     row near roi b  iff  ((sx sx) + (sy sy)) + (sz sz) < reach2_b,  sx = x - cx and likewise y, z: STRICT
+ *   Near ANY present roi counts.  pcdet tests the reach of the NEAREST roi only; ours is a superset of its rows that does not depend on
+ *   the order of the rois.  A frame whose rois are all absent has no usable row.  The device's float64 sqrt is IEEE's, correctly
+ *   rounded -- the range image relies on the same (sg_range_r, its pitch) --, so NumPy gives the same reach2: d_out_reach2 shows it.
+ *   SECTOR of a usable row, in float64: a = atan2((double)y, (double)x) + pi, atan2 correctly rounded (csrc/sg_atan_cr.h), pi the double
+ *   nearest pi; s = min((int)floor(a / ((2 pi) / S)), S - 1), the quotient as NumPy writes
+ *   np.floor(np.divide(np.add(atan2, np.pi), np.divide(2 * np.pi, S))).  The origin and the +-pi seam have no special case: atan2(+-0, x < 0)
+ *   = +-pi puts y = -0 into sector 0 and y = +0 into sector S - 1; the origin (atan2 = 0) falls where a = pi does.
+ *   QUOTA, int64: n_s = the usable rows of the frame in sector s, m = their sum.  m >= K: q_s = floor(n_s K / m), r_s = n_s K mod m,
+ *   L = K - sum q_s; the L sectors with the largest r_s get one more, among equal r_s the smaller s first (largest-remainder
+ *   apportionment).  0 < m < K: q_s = n_s.  Then (m >= K):
+ *     sum q_s = K      since sum n_s K = m K = m sum floor + sum r_s, sum r_s = m L with every r_s < m: 0 <= L < S, and L ones are added;
+ *     winners have r_s > 0   since sum r_s = m L and every r_s <= m - 1, more than L of the r_s are positive (L > 0), and they come first;
+ *     q_s <= n_s       since floor(n_s K / m) <= n_s K / m <= n_s, and for a winner n_s K / m is no integer: floor + 1 <= n_s.
+ *   pcdet's min(n_s, ceil(ratio K)) gives a total that varies from frame to frame; this is its static-shape form.
+ *   WALKS: sector s of frame f walks its own usable rows u_0 < u_1 < ... (input order) exactly as snowgpu_fps_device walks a frame --
+ *   the same distance in T, the same tie rule -- for q_s samples: s_0 = u_0, then q_s - 1 rounds.  The frame's K slots hold the sectors'
+ *   samples side by side, s = 0 .. S - 1.  With m < K the K - m trailing slots repeat the index of slot 0, with dist 0.  A frame with
+ *   m = 0 is -1 / 0 / -1 as for snowgpu_fps_device.
+ * Outputs, every shape static, every element written by every call:
+ *   d_out_index, d_out_points (or NULL), d_out_dist (or NULL), d_out_usable (= m): as for snowgpu_fps_device; the first sample of every
+ *                          sector has dist +inf
+ *   d_out_sector_offsets   (F, S + 1) int32: slots [o_s, o_{s+1}) of the frame are sector s; o_S = min(m, K)
+ *   d_out_sector_count     (F, S) int32: n_s
+ *   d_out_sector_of        (N_total) int8, or NULL: the row's sector, -1 for an absent or unusable row
+ *   d_out_reach2           (F, B) float64, or NULL (only with d_rois): reach2, 0 for an absent roi
+ * With S = 1 and no rois, index, points, dist and usable are byte for byte those of snowgpu_fps_device.
+ * Domain: that of snowgpu_fps_device and the bounds above; F B <= 2^31 - 1; F ceil(max_frame_rows / 1024) <= 2^27 - 1 (the tiles of the
+ * classification); every output apart from the rows, the keep mask, the rois and every other output.  Anything else is SNOWGPU_E_INVALID.
+ * An empty batch writes usable = 0, index = -1, points = 0, dist = -1, offsets and counts 0, and the reach.
+ * One thread per row decides usable, near (the frame's rois as records in LDS, every one tried) and sector, every angle from the
+ * correctly rounded atan2; the rows of a 1024-row tile are counted per sector by ballots, one workgroup per frame scans the tile counts
+ * and makes the quotas, a second pass over the rows scatters x, y, z into one segment of scratch per (frame, sector) in input order, and
+ * F S workgroups of 1024 threads run the walk of snowgpu_fps_device, each over its segment, in the tier its n_s asks for
+ * (csrc/snowgpu_fps.hip, csrc/sg_fps_sectors.h).  Nothing depends on the arrival of atomics -- there are none --: two calls give identical
+ * bytes.  Scratch in the context, grown on first use: that of snowgpu_fps_device (68 elements per frame instead of 8), one byte per row,
+ * 4 S bytes per 1024-row tile, 4 S bytes per frame and 32 bytes per roi.  Up to one memset and six kernels on `stream`; nothing is read
+ * on the host, nothing allocated after the first call of a size: capturable.
+ */
+int snowgpu_fps_sectors_device(snowgpu_ctx *ctx, int n_frames, int64_t n_total, int64_t max_frame_rows, const int64_t *d_frame_offsets,
+                               const void *d_rows, int dtype, const double *range6 /* host: x0 y0 z0 x1 y1 z1, or NULL */, int n_samples,
+                               int n_features, const uint8_t *d_keep_in /* or NULL: all present */, int n_sectors,
+                               const void *d_rois /* or NULL: no roi test */, int n_rois, int roi_features, double roi_margin,
+                               int32_t *d_out_index, void *d_out_points /* or NULL */, void *d_out_dist /* or NULL */, int32_t *d_out_usable,
+                               int32_t *d_out_sector_offsets, int32_t *d_out_sector_count, int8_t *d_out_sector_of /* or NULL */,
+                               double *d_out_reach2 /* or NULL */, void *stream);
+
+/*
  * BALL-QUERY NEIGHBOUR GROUPS around centres of an aligned batch: for every centre the first rows of its frame within a radius, the
  * grouping step of PV-RCNN's voxel set abstraction over the raw points and of the PointNet++ set-abstraction layers, with static shapes.
  * Frames, rows (N_total x 5, float32 or float64), frame offsets and the input keep mask as snowgpu_fps_device takes them.  F = n_frames,

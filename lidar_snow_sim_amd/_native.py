@@ -31,7 +31,7 @@ EXPORTS = [
     "snowgpu_augment_batch_device_aligned_masked", "snowgpu_augment_wet_batch_device_aligned_masked", "snowgpu_fov_mask_device",
     "snowgpu_augment_weather_batch_device_aligned", "snowgpu_draw_weather_device", "snowgpu_dror_mask_device",
     "snowgpu_voxelize_device", "snowgpu_fps_device", "snowgpu_ball_query_device", "snowgpu_range_image_device",
-    "snowgpu_nearest_centres_device", "snowgpu_points_in_boxes_device",
+    "snowgpu_nearest_centres_device", "snowgpu_points_in_boxes_device", "snowgpu_fps_sectors_device",
 ]
 
 WET_ESTIMATION = {"linear": 0, "poly": 1}
@@ -147,6 +147,9 @@ def lib():
                                                   vp, vp, vp, vp, vp, vp, vp]
             L.snowgpu_fps_device.restype = ctypes.c_int
             L.snowgpu_fps_device.argtypes = [vp, ctypes.c_int, i64, i64, vp, vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp, vp]
+            L.snowgpu_fps_sectors_device.restype = ctypes.c_int
+            L.snowgpu_fps_sectors_device.argtypes = [vp, ctypes.c_int, i64, i64, vp, vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, vp,
+                                                     ctypes.c_int, ctypes.c_int, dbl, vp, vp, vp, vp, vp, vp, vp, vp, vp]
             L.snowgpu_ball_query_device.restype = ctypes.c_int
             L.snowgpu_ball_query_device.argtypes = [vp, ctypes.c_int, i64, i64, vp, vp, ctypes.c_int, vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, vp, vp,
                                                     ctypes.c_int, vp, vp, vp, vp, vp]
@@ -567,6 +570,29 @@ class Context:
                                         int(dtype_code), None if rng is None else _p(rng), i32(n_samples), i32(n_features), vp(d_keep_in or None),
                                         vp(d_out_index or None), vp(d_out_points or None), vp(d_out_dist or None), vp(d_out_usable or None),
                                         vp(stream or None))
+        if rc == E_INVALID:
+            raise ValueError(self._L.snowgpu_last_error(self._h).decode())
+        self._check(rc)
+
+    def fps_sectors_device(self, n_frames, n_total, max_frame_rows, d_frame_off, d_rows, dtype_code, point_cloud_range, n_samples, n_features, d_keep_in,
+                           n_sectors, d_rois, n_rois, roi_features, roi_margin, d_out_index, d_out_points, d_out_dist, d_out_usable, d_out_sector_offsets,
+                           d_out_sector_count, d_out_sector_of=0, d_out_reach2=0, stream=0):
+        """Sectorized, proposal-centric keypoints of an aligned batch (include/snowgpu.h: snowgpu_fps_sectors_device); asynchronous on
+        `stream`.  point_cloud_range: 6 numbers or None; d_rois 0: no roi test.  An argument outside the domain, or an output overlapping
+        the mask, the rows, the rois or another output, raises ValueError with the entry's words."""
+        vp = ctypes.c_void_p
+        rng = None
+        if point_cloud_range is not None:
+            rng = np.ascontiguousarray(point_cloud_range, np.float64).reshape(-1)
+            if rng.shape != (6,):
+                raise ValueError("snowgpu_fps_sectors_device: point_cloud_range holds 6 numbers (x0, y0, z0, x1, y1, z1)")
+        i32 = lambda v: max(-(2 ** 31), min(int(v), 2 ** 31 - 1))
+        rc = self._L.snowgpu_fps_sectors_device(self._h, int(n_frames), int(n_total), int(max_frame_rows), vp(d_frame_off or None), vp(d_rows or None),
+                                                int(dtype_code), None if rng is None else _p(rng), i32(n_samples), i32(n_features), vp(d_keep_in or None),
+                                                i32(n_sectors), vp(d_rois or None), i32(n_rois), i32(roi_features), float(roi_margin),
+                                                vp(d_out_index or None), vp(d_out_points or None), vp(d_out_dist or None), vp(d_out_usable or None),
+                                                vp(d_out_sector_offsets or None), vp(d_out_sector_count or None), vp(d_out_sector_of or None),
+                                                vp(d_out_reach2 or None), vp(stream or None))
         if rc == E_INVALID:
             raise ValueError(self._L.snowgpu_last_error(self._h).decode())
         self._check(rc)

@@ -286,6 +286,15 @@ struct SgFpsRange;
 int sg_launch_fps(const void *rows, int dtype, int64_t n, const int64_t *frame_off, int n_frames, const uint8_t *keep_in, const struct SgFpsRange *range,
                   int32_t n_samples, int32_t n_features, void *sx, void *sy, void *sz, void *st, int32_t *ssrc, int32_t *out_index, void *out_points,
                   void *out_dist, int32_t *out_usable, void *stream);
+// Sectorized, proposal-centric sampling (sg_fps_sectors.h; the definition: include/snowgpu.h): up to one memset and six kernels.  Scratch:
+// sx, sy, sz, st and ssrc, sg_fpss_scratch(n, n_frames) elements each; sec n bytes; rec n_frames n_rois records of four doubles; tile
+// n_frames sg_tiles(max_frame) n_sectors words; seg n_frames n_sectors words.  rois, out_points, out_dist, out_sector_of and out_reach2
+// may be null.
+int sg_launch_fps_sectors(const void *rows, int dtype, int64_t n, int64_t max_frame, const int64_t *frame_off, int n_frames, const uint8_t *keep_in,
+                          const struct SgFpsRange *range, int32_t n_samples, int32_t n_features, int32_t n_sectors, const void *rois, int32_t n_rois,
+                          int32_t roi_features, double roi_margin, void *sx, void *sy, void *sz, void *st, int32_t *ssrc, int8_t *sec, void *rec,
+                          int32_t *tile, int32_t *seg, int32_t *out_index, void *out_points, void *out_dist, int32_t *out_usable,
+                          int32_t *out_offsets, int32_t *out_count, int8_t *out_sector_of, double *out_reach2, void *stream);
 // Ball query around centres (sg_ball.h; the definition: include/snowgpu.h): a memset and four kernels.  Scratch: entry,
 // sg_ball_entries(n_frames, g->cells) words; cell_of and ssrc, sg_ball_scratch(n) words; sx, sy, sz as many values of the rows' dtype.
 // out_points may be null.

@@ -222,6 +222,71 @@ static inline int sg_check_fps_args(const SgFpsArgs &a, std::string *msg)
     return 0;
 }
 
+// ---- snowgpu_fps_sectors_device -----------------------------------------------------------------------------------------------------------
+struct SgFpsSectorsArgs {
+    SgFpsArgs fps;                    // what snowgpu_fps_device takes, with the same meaning
+    int n_sectors;                    // S
+    const void *rois;                 // (F, B, Cb) in the rows' dtype, or NULL: no roi test (n_rois and roi_features are then not read)
+    int n_rois, roi_features;         // B, Cb
+    double roi_margin;
+    int32_t *out_sector_offsets, *out_sector_count;
+    int8_t *out_sector_of;            // or NULL
+    double *out_reach2;               // or NULL; only with rois
+};
+
+// 0, or SG_ARGS_INVALID with *msg.  As above, the order is part of the ABI.
+static inline int sg_check_fps_sectors_args(const SgFpsSectorsArgs &s, std::string *msg)
+{
+    static const char *who = "snowgpu_fps_sectors_device";
+    const SgFpsArgs &a = s.fps;
+    if (a.n_frames <= 0 || a.n_total < 0 || !a.frame_off || !a.out_index || !a.out_usable || !s.out_sector_offsets || !s.out_sector_count ||
+        (a.n_total > 0 && !a.rows) || (a.dtype != 0 && a.dtype != 1))
+        return sg_refuse(who, ": null pointer or bad dtype", msg);
+    if (a.n_total >= ((int64_t)1 << 31)) return sg_refuse("", "batch too large: split it below 2^31 rows", msg);
+    if (a.n_features < 3 || a.n_features > 5) return sg_refuse(who, ": n_features must be 3, 4 or 5: the columns of a row that a keypoint carries", msg);
+    if (a.n_samples < 1) return sg_refuse(who, ": n_samples must be at least 1", msg);
+    if ((int64_t)a.n_frames * a.n_samples > (((int64_t)1 << 31) - 1))
+        return sg_refuse(who, ": n_frames * n_samples exceeds 2^31 - 1; split the batch", msg);
+    if (sg_max_frame(a.max_frame_rows, a.n_total) > ((int64_t)1 << 30))
+        return sg_refuse(who, ": a frame of more than 2^30 rows; split it", msg);
+    if (a.range6) {
+        for (int j = 0; j < 6; ++j)
+            if (a.range6[j] != a.range6[j]) return sg_refuse(who, ": a bound of the range is NaN; pass NULL for no range, or infinite bounds", msg);
+        for (int j = 0; j < 3; ++j)
+            if (!(a.range6[j] < a.range6[3 + j])) return sg_refuse(who, ": the range needs lo < hi on every axis", msg);
+    }
+    if (s.n_sectors < 1 || s.n_sectors > 16) return sg_refuse(who, ": n_sectors must lie in 1 .. 16", msg);
+    if (s.rois) {
+        if (s.n_rois < 1 || s.n_rois > 256) return sg_refuse(who, ": n_rois must lie in 1 .. 256", msg);
+        if (s.roi_features < 7 || s.roi_features > 10) return sg_refuse(who, ": roi_features must lie in 7 .. 10: cx, cy, cz, dx, dy, dz, heading first", msg);
+        if (!(s.roi_margin >= 0.0 && s.roi_margin <= 1.7976931348623157e308)) return sg_refuse(who, ": roi_margin must be finite and at least 0", msg);
+        if ((int64_t)a.n_frames * s.n_rois > ((int64_t)1 << 31) - 1) return sg_refuse(who, ": n_frames * n_rois exceeds 2^31 - 1; split the batch", msg);
+    } else if (s.out_reach2)
+        return sg_refuse(who, ": d_out_reach2 without d_rois; there is no reach to write", msg);
+    // (one workgroup per 1024-row tile of every frame, as many tiles per frame as the longest has)
+    if ((int64_t)a.n_frames * ((sg_max_frame(a.max_frame_rows, a.n_total) + 1023) / 1024) > (((int64_t)1 << 31) - 1) / 16)
+        return sg_refuse(who, ": n_frames * ceil(max_frame_rows / 1024) exceeds 2^27 - 1; split the batch", msg);
+    const size_t esz = a.dtype == 0 ? 4 : 8, F = (size_t)a.n_frames, elems = F * (size_t)a.n_samples, n = (size_t)a.n_total, S = (size_t)s.n_sectors;
+    const size_t q = s.rois ? F * (size_t)s.n_rois : 0;
+    const struct { const void *p; size_t bytes; const char *name; } outs[8] = {
+        {a.out_index, elems * 4, "d_out_index"}, {a.out_points, elems * (size_t)a.n_features * esz, "d_out_points"}, {a.out_dist, elems * esz, "d_out_dist"},
+        {a.out_usable, F * 4, "d_out_usable"}, {s.out_sector_offsets, F * (S + 1) * 4, "d_out_sector_offsets"}, {s.out_sector_count, F * S * 4, "d_out_sector_count"},
+        {s.out_sector_of, n, "d_out_sector_of"}, {s.out_reach2, q * 8, "d_out_reach2"}};
+    for (int i = 0; i < 8; ++i) {
+        const auto &o = outs[i];
+        if (sg_ranges_meet(o.p, o.bytes, a.keep_in, n))
+            return sg_refuse(who, (std::string(": ") + o.name + " overlaps d_keep_in; the mask is read while the samples are written: pass a buffer apart from it").c_str(), msg);
+        if (sg_ranges_meet(o.p, o.bytes, a.rows, n * 5 * esz))
+            return sg_refuse(who, (std::string(": ") + o.name + " overlaps d_rows; the rows are read while the samples are written: pass a buffer apart from them").c_str(), msg);
+        if (sg_ranges_meet(o.p, o.bytes, s.rois, q * (size_t)s.roi_features * esz))
+            return sg_refuse(who, (std::string(": ") + o.name + " overlaps d_rois; the rois are read while the samples are written: pass a buffer apart from them").c_str(), msg);
+        for (int j = 0; j < i; ++j)
+            if (sg_ranges_meet(o.p, o.bytes, outs[j].p, outs[j].bytes))
+                return sg_refuse(who, (std::string(": ") + o.name + " overlaps " + outs[j].name + "; every output needs memory of its own").c_str(), msg);
+    }
+    return 0;
+}
+
 // ---- snowgpu_ball_query_device ------------------------------------------------------------------------------------------------------------
 struct SgBallArgs {
     int n_frames;

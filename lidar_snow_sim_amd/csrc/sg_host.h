@@ -93,6 +93,11 @@ struct __attribute__((visibility("default"))) snowgpu_ctx {
     // minimum t as four arrays in the rows' dtype -- and their source rows
     DevBuf<uint8_t> fps_x, fps_y, fps_z, fps_t;
     DevBuf<int32_t> fps_src;
+    // sectorized sampling (snowgpu_fps_sectors_device) compacts every (frame, sector) into the same five arrays; beside them the sector
+    // byte of every row, the rois' records (four doubles each), the tile counts / bases and the segments' places
+    DevBuf<int8_t> fpss_sec;
+    DevBuf<double> fpss_roi;
+    DevBuf<int32_t> fpss_tile, fpss_seg;
     // ball query (snowgpu_ball_query_device): the cell lists of every frame -- first positions, the cell of every row -- and the usable
     // rows sorted by cell: x, y, z as three arrays in the rows' dtype and their source rows
     DevBuf<uint32_t> ball_entry, ball_cell;

@@ -144,6 +144,7 @@ extern "C" void snowgpu_destroy(snowgpu_ctx *ctx)
     ctx->vox_table.release(); ctx->vox_slot.release(); ctx->vox_order.release(); ctx->vox_span.release(); ctx->vox_first.release();
     ctx->vox_tile_cnt.release(); ctx->vox_tile_base.release(); ctx->vox_fbase.release(); ctx->vox_m.release();
     ctx->fps_x.release(); ctx->fps_y.release(); ctx->fps_z.release(); ctx->fps_t.release(); ctx->fps_src.release();
+    ctx->fpss_sec.release(); ctx->fpss_roi.release(); ctx->fpss_tile.release(); ctx->fpss_seg.release();
     ctx->ball_entry.release(); ctx->ball_cell.release(); ctx->ball_x.release(); ctx->ball_y.release(); ctx->ball_z.release(); ctx->ball_src.release();
     ctx->range_key.release();
     ctx->nn_entry.release(); ctx->nn_box.release(); ctx->nn_rec.release();

@@ -1,5 +1,5 @@
 // snowgpu_device.cpp -- the entries of the C ABI (include/snowgpu.h) that take DEVICE pointers and enqueue on the caller's stream: every
-// *_batch_device* entry, the plane estimate, the FOV mask, the outlier filter, the voxel stage, the keypoint stage, the ball query, the range image, the nearest centres, the points in boxes and the weather draw.  Each batch entry fills an SgDeviceArgs, has it checked
+// *_batch_device* entry, the plane estimate, the FOV mask, the outlier filter, the voxel stage, the keypoint stage and its sectorized form, the ball query, the range image, the nearest centres, the points in boxes and the weather draw.  Each batch entry fills an SgDeviceArgs, has it checked
 // (sg_device_args.h: every refusal, in one order), sets the device and runs batch_from_args() and the stages it needs.  The launch
 // sequence of a batch is snowgpu_batch.cpp; no host copy, no synchronisation, no allocation after the first call of a given size.
 #include "sg_host.h"
@@ -8,6 +8,7 @@
 #include "sg_dror.h"        // the grid of the outlier filter and its domain
 #include "sg_voxel.h"       // the grid of the voxel stage and the capacity of its tables
 #include "sg_fps.h"         // the range of the keypoint stage and the size of its scratch
+#include "sg_fps_sectors.h" // the scratch of the sectorized keypoint stage
 #include "sg_ball.h"        // the grid of the ball query and the sizes of its scratch
 #include "sg_nn.h"          // the grid of the nearest-centres stage and the sizes of its scratch
 #include "sg_box.h"         // the record of a box and the sizes of the box stage's scratch
@@ -467,6 +468,46 @@ extern "C" int snowgpu_fps_device(snowgpu_ctx *ctx, int n_frames, int64_t n_tota
     int e = sg_launch_fps(d_rows, dtype, n_total, d_frame_offsets, n_frames, d_keep_in, &r, n_samples, n_features, ctx->fps_x.p, ctx->fps_y.p, ctx->fps_z.p,
                           ctx->fps_t.p, ctx->fps_src.p, d_out_index, d_out_points, d_out_dist, d_out_usable, stream ? (hipStream_t)stream : ctx->stream);
     if (e) return fail(ctx, SNOWGPU_E_HIP, std::string("fps launch: ") + hipGetErrorString((hipError_t)e));
+    return SNOWGPU_OK;
+}
+
+// Sectorized, proposal-centric keypoints of an aligned batch (snowgpu_fps.hip; the reach, the sector, the quota and the layout of the
+// scratch: sg_fps_sectors.h).  See include/snowgpu.h.
+extern "C" int snowgpu_fps_sectors_device(snowgpu_ctx *ctx, int n_frames, int64_t n_total, int64_t max_frame_rows, const int64_t *d_frame_offsets,
+                                          const void *d_rows, int dtype, const double *range6, int n_samples, int n_features, const uint8_t *d_keep_in,
+                                          int n_sectors, const void *d_rois, int n_rois, int roi_features, double roi_margin, int32_t *d_out_index,
+                                          void *d_out_points, void *d_out_dist, int32_t *d_out_usable, int32_t *d_out_sector_offsets,
+                                          int32_t *d_out_sector_count, int8_t *d_out_sector_of, double *d_out_reach2, void *stream)
+{
+    if (!ctx) return SNOWGPU_E_INVALID;
+    const SgFpsSectorsArgs a{{n_frames, n_total, max_frame_rows, dtype, d_frame_offsets, d_rows, range6, n_samples, n_features, d_keep_in, d_out_index,
+                              d_out_points, d_out_dist, d_out_usable},
+                             n_sectors, d_rois, n_rois, roi_features, roi_margin, d_out_sector_offsets, d_out_sector_count, d_out_sector_of, d_out_reach2};
+    {
+        std::string msg;
+        if (int rc = sg_check_fps_sectors_args(a, &msg)) return fail(ctx, rc, msg);
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    SgFpsRange r;
+    for (int j = 0; j < 3; ++j) { r.lo[j] = range6 ? range6[j] : -INFINITY; r.hi[j] = range6 ? range6[3 + j] : INFINITY; }
+    const int64_t max_frame = sg_max_frame(max_frame_rows, n_total);
+    if (d_rois) ENSURE(ctx, ctx->fpss_roi, (size_t)n_frames * (size_t)n_rois * 4);
+    if (n_total > 0) {
+        const size_t elems = sg_fpss_scratch(n_total, n_frames), bytes = elems * (dtype == 0 ? 4 : 8);
+        ENSURE(ctx, ctx->fps_x, bytes);
+        ENSURE(ctx, ctx->fps_y, bytes);
+        ENSURE(ctx, ctx->fps_z, bytes);
+        ENSURE(ctx, ctx->fps_t, bytes);
+        ENSURE(ctx, ctx->fps_src, elems);
+        if (!d_out_sector_of) ENSURE(ctx, ctx->fpss_sec, (size_t)n_total);
+        ENSURE(ctx, ctx->fpss_tile, (size_t)n_frames * (size_t)sg_tiles(max_frame) * (size_t)n_sectors);
+        ENSURE(ctx, ctx->fpss_seg, (size_t)n_frames * (size_t)n_sectors);
+    }
+    int e = sg_launch_fps_sectors(d_rows, dtype, n_total, max_frame, d_frame_offsets, n_frames, d_keep_in, &r, n_samples, n_features, n_sectors, d_rois, n_rois,
+                                  roi_features, roi_margin, ctx->fps_x.p, ctx->fps_y.p, ctx->fps_z.p, ctx->fps_t.p, ctx->fps_src.p, ctx->fpss_sec.p,
+                                  ctx->fpss_roi.p, ctx->fpss_tile.p, ctx->fpss_seg.p, d_out_index, d_out_points, d_out_dist, d_out_usable, d_out_sector_offsets,
+                                  d_out_sector_count, d_out_sector_of, d_out_reach2, stream ? (hipStream_t)stream : ctx->stream);
+    if (e) return fail(ctx, SNOWGPU_E_HIP, std::string("sectorized fps launch: ") + hipGetErrorString((hipError_t)e));
     return SNOWGPU_OK;
 }
 

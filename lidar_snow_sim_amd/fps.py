@@ -36,3 +36,34 @@ def farthest_point_sample(pc, n_samples, point_cloud_range=None, num_features=No
     t = torch.from_numpy(rows).to(torch.device("cuda", index))
     got = sample_keypoints(t, n_samples, point_cloud_range=point_cloud_range, num_features=c)
     return got.index[0].cpu().numpy(), got.points[0].cpu().numpy()
+
+
+def sectorized_sample(pc, n_samples, n_sectors=6, rois=None, roi_margin=1.6, point_cloud_range=None, num_features=None, device=None):
+    """PV-RCNN++'s sectorized, proposal-centric sampling of one cloud (include/snowgpu.h, snowgpu_fps_sectors_device): (index n_samples
+    int32, points n_samples x C, sector_offsets n_sectors + 1 int32).  `pc` as farthest_point_sample takes it; rois: B x 7 .. 10 boxes
+    (cx, cy, cz, dx, dy, dz, heading, ...; zero rows are padding) or None -- with rois only the rows within a box's half diagonal +
+    roi_margin of its centre are sampled.  The usable rows are split by azimuth into n_sectors sectors, and sector s fills the slots
+    sector_offsets[s] .. sector_offsets[s + 1] - 1 by a farthest-point walk of its own; slots from sector_offsets[-1] on repeat slot 0."""
+    import torch
+    from .tensors import sample_keypoints
+    pc = np.asarray(pc)
+    if pc.ndim != 2 or pc.shape[1] < 3:
+        raise ValueError("pc must be N x K with K >= 3 (x, y, z, ...)")
+    c = min(pc.shape[1], 5) if num_features is None else int(num_features)
+    if not 3 <= c <= min(pc.shape[1], 5):
+        raise ValueError("num_features must lie in 3 .. min(K, 5): the leading columns of pc that a keypoint carries")
+    if not torch.cuda.is_available():
+        raise RuntimeError("sectorized_sample runs on the GPU: no device is visible (there is no CPU fallback)")
+    k = min(pc.shape[1], 5)
+    rows = np.zeros((pc.shape[0], 5), np.float32 if pc.dtype == np.float32 else np.float64)
+    rows[:, :k] = pc[:, :k]
+    dev = torch.device("cuda", torch.cuda.current_device() if device is None else int(device))
+    d_rois = None
+    if rois is not None:
+        rois = np.asarray(rois)
+        if rois.ndim != 2 or not 7 <= rois.shape[1] <= 10 or not 1 <= rois.shape[0] <= 256:
+            raise ValueError("rois must be B x 7 .. 10 with 1 <= B <= 256 (cx, cy, cz, dx, dy, dz, heading, ...)")
+        d_rois = torch.from_numpy(np.array(rois[None], rows.dtype, order="C")).to(dev)          # (a copy: from_numpy wants a writable array)
+    got = sample_keypoints(torch.from_numpy(rows).to(dev), n_samples, point_cloud_range=point_cloud_range, num_features=c, sectors=n_sectors, rois=d_rois,
+                           roi_margin=roi_margin)
+    return got.index[0].cpu().numpy(), got.points[0].cpu().numpy(), got.sector_offsets[0].cpu().numpy()

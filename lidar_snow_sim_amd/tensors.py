@@ -689,20 +689,32 @@ class KeypointBatch:
     moment it was chosen, +inf for the first, -1 for a frame without a usable row; None unless asked for).  All still being written until
     the stream the call was made on has caught up."""
 
-    def __init__(self, index, points, usable, dist=None):
+    def __init__(self, index, points, usable, dist=None, sector_offsets=None, sector_count=None, sector_of=None):
         self.index, self.points, self.usable, self.dist = index, points, usable, dist
+        # set by the sectorized call alone (sample_keypoints(sectors=..., rois=...)): (F, S + 1) int32 -- slots [o_s, o_{s+1}) of a frame
+        # are its sector s, o_S = min(usable, K) --, (F, S) int32 -- the usable rows of every sector -- and, when asked for, (N) int8:
+        # every row's sector, -1 for an absent or unusable row
+        self.sector_offsets, self.sector_count, self.sector_of = sector_offsets, sector_count, sector_of
 
     @classmethod
-    def empty(cls, n_frames, n_samples, num_features=4, dtype=None, device=None, with_dist=False):
-        """Uninitialised buffers of the shapes sample_keypoints() writes for such a call (out=): static addresses for a captured graph."""
+    def empty(cls, n_frames, n_samples, num_features=4, dtype=None, device=None, with_dist=False, sectors=None, with_sector_of=None):
+        """Uninitialised buffers of the shapes sample_keypoints() writes for such a call (out=): static addresses for a captured graph.
+        sectors = S adds sector_offsets and sector_count, with_sector_of = the rows of the batch adds sector_of."""
         import torch
         dev = torch.device("cuda", torch.cuda.current_device() if device is None else int(device)) if not isinstance(device, torch.device) else device
         F, K, dt = int(n_frames), int(n_samples), dtype or torch.float32
-        return cls(torch.empty((F, K), dtype=torch.int32, device=dev), torch.empty((F, K, int(num_features)), dtype=dt, device=dev),
-                   torch.empty(F, dtype=torch.int32, device=dev), torch.empty((F, K), dtype=dt, device=dev) if with_dist else None)
+        out = cls(torch.empty((F, K), dtype=torch.int32, device=dev), torch.empty((F, K, int(num_features)), dtype=dt, device=dev),
+                  torch.empty(F, dtype=torch.int32, device=dev), torch.empty((F, K), dtype=dt, device=dev) if with_dist else None)
+        if sectors is not None:
+            out.sector_offsets = torch.empty((F, int(sectors) + 1), dtype=torch.int32, device=dev)
+            out.sector_count = torch.empty((F, int(sectors)), dtype=torch.int32, device=dev)
+            if with_sector_of is not None and with_sector_of is not False:
+                out.sector_of = torch.empty(int(with_sector_of), dtype=torch.int8, device=dev)
+        return out
 
 
-def sample_keypoints(frames, n_samples, *, point_cloud_range=None, keep=None, num_features=4, out=None, return_dist=False, device=None, slot=0):
+def sample_keypoints(frames, n_samples, *, point_cloud_range=None, keep=None, num_features=4, out=None, return_dist=False, device=None, slot=0,
+                     sectors=None, rois=None, roi_margin=1.6, return_sector_of=False):
     """Farthest point sampling on the device (snowgpu_fps_device; the definition: include/snowgpu.h): the keypoints of PV-RCNN and the
     fixed-size point set of PointRCNN / Part-A2, with static shapes.  Per frame, among the rows that are present, within 1e6 of the origin
     on every axis and inside point_cloud_range (x0, y0, z0, x1, y1, z1; None: no range), the first is taken, then n_samples - 1 times the
@@ -713,9 +725,18 @@ def sample_keypoints(frames, n_samples, *, point_cloud_range=None, keep=None, nu
     keep      an input keep mask as the aligned calls take it (with a result: ANDed with the result's own).
     out       a KeypointBatch to write into (KeypointBatch.empty): every element is written, nothing needs clearing.
     return_dist   also fill `dist`.
+    sectors, rois, roi_margin, return_sector_of
+              PV-RCNN++'s sectorized, proposal-centric sampling (snowgpu_fps_sectors_device): with rois -- an (F, B, 7 .. 10) device
+              tensor of the rows' dtype, OpenPCDet's rois / gt_boxes, zero rows are padding -- only the rows within a roi's half diagonal
+              + roi_margin of its centre are usable; the usable rows are split by azimuth into `sectors` sectors (1 .. 16; 1 when only
+              rois are given) and every sector is walked on its own for its share of n_samples.  The result carries sector_offsets and
+              sector_count, and with return_sector_of every row's sector.  With both None the plain walk runs, untouched.
 
     Returns a KeypointBatch.  Asynchronous on torch's current stream; nothing is read on the host: capturable after one warm-up call."""
     import torch
+    if sectors is not None or rois is not None:
+        return _sample_keypoints_sectors(torch, frames, n_samples, point_cloud_range, keep, num_features, out, return_dist, device, slot,
+                                         1 if sectors is None else sectors, rois, roi_margin, return_sector_of)
     if isinstance(frames, AlignedResult):
         res = frames
         own = res.keep if res.keep.dtype == torch.bool else res.keep.view(torch.bool)
@@ -761,6 +782,70 @@ def sample_keypoints(frames, n_samples, *, point_cloud_range=None, keep=None, nu
                            rng, K, C, 0 if keep is None or not n else keep.data_ptr(), out.index.data_ptr(), out.points.data_ptr(),
                            0 if dist is None else dist.data_ptr(), out.usable.data_ptr(), run.cuda_stream)
     return out if return_dist or out.dist is None else KeypointBatch(out.index, out.points, out.usable)
+
+
+def _sample_keypoints_sectors(torch, frames, n_samples, point_cloud_range, keep, num_features, out, return_dist, device, slot, sectors, rois, roi_margin,
+                              return_sector_of):
+    """sample_keypoints() with sectors or rois: snowgpu_fps_sectors_device."""
+    if isinstance(frames, AlignedResult):
+        res = frames
+        own = res.keep if res.keep.dtype == torch.bool else res.keep.view(torch.bool)
+        frames = DeviceBatch(res.rows, res.offsets)
+        keep = own if keep is None else (_keep_mask(torch, keep, res.rows, res.offsets) & own)
+    if not is_device_input(frames):
+        raise ValueError("sample_keypoints: torch CUDA tensors or an aligned result (host arrays: lidar_snow_sim_amd.fps.sectorized_sample)")
+    for name, v in (("n_samples", n_samples), ("num_features", num_features), ("sectors", sectors)):
+        if isinstance(v, bool) or int(v) != v:
+            raise ValueError(f"sample_keypoints: {name} must be an integer")
+    rng = None
+    if point_cloud_range is not None:
+        rng = np.asarray(point_cloud_range, np.float64).reshape(-1)
+        if rng.shape != (6,):
+            raise ValueError("sample_keypoints: point_cloud_range holds 6 numbers (x0, y0, z0, x1, y1, z1)")
+    rows, offsets, _, eng = _resolve_input(torch, frames, False, device, slot)
+    dev = rows.device
+    nf, n = len(offsets) - 1, int(offsets[-1])
+    K, C, S = int(n_samples), int(num_features), int(sectors)
+    if keep is not None:
+        keep = _keep_mask(torch, keep, rows, offsets)
+    # (the shapes below need these; the entry refuses them in the same words, and everything else of the domain)
+    if not 3 <= C <= 5:
+        raise ValueError("sample_keypoints: n_features must be 3, 4 or 5: the columns of a row that a keypoint carries")
+    if K < 1:
+        raise ValueError("sample_keypoints: n_samples must be at least 1")
+    if nf * K > 2 ** 31 - 1:
+        raise ValueError("sample_keypoints: n_frames * n_samples exceeds 2^31 - 1; split the batch")
+    if not 1 <= S <= 16:
+        raise ValueError("sample_keypoints: n_sectors must lie in 1 .. 16")
+    B = Cb = 0
+    if rois is not None:
+        if not (torch.is_tensor(rois) and rois.is_cuda and rois.device == dev and rois.dtype == rows.dtype and rois.dim() == 3 and rois.shape[0] == nf
+                and rois.is_contiguous()):
+            raise ValueError("sample_keypoints: rois must be a contiguous (frames, B, 7 .. 10) tensor of the rows' dtype on the device of the rows")
+        B, Cb = int(rois.shape[1]), int(rois.shape[2])
+    if out is None:
+        out = KeypointBatch.empty(nf, K, C, rows.dtype, dev, return_dist, S, n if return_sector_of else None)
+    else:
+        want = (("index", (nf, K), torch.int32), ("points", (nf, K, C), rows.dtype), ("usable", (nf,), torch.int32),
+                ("sector_offsets", (nf, S + 1), torch.int32), ("sector_count", (nf, S), torch.int32)) + \
+               ((("dist", (nf, K), rows.dtype),) if return_dist else ()) + ((("sector_of", (n,), torch.int8),) if return_sector_of else ())
+        for name, shape, dtype in want:
+            t = getattr(out, name, None) if isinstance(out, KeypointBatch) else None
+            if not (torch.is_tensor(t) and tuple(t.shape) == shape and t.dtype == dtype and t.is_contiguous() and t.device == dev):
+                raise ValueError(f"sample_keypoints: out must be a KeypointBatch whose {name} is a contiguous {tuple(shape)} {dtype} tensor on the device of the rows")
+    dist = out.dist if return_dist else None
+    sof = out.sector_of if return_sector_of else None
+    up = _uploads(eng)
+    with torch.cuda.device(dev), _on_run_stream(torch, eng, dev) as (_, run):
+        d_off = up.get(torch, dev, offsets, run)
+        eng.ctx.fps_sectors_device(nf, n, int(np.diff(offsets).max()), d_off.data_ptr(), rows.data_ptr() if n else 0, 0 if rows.dtype == torch.float32 else 1,
+                                   rng, K, C, 0 if keep is None or not n else keep.data_ptr(), S, 0 if rois is None else rois.data_ptr(), B, Cb,
+                                   roi_margin, out.index.data_ptr(), out.points.data_ptr(), 0 if dist is None else dist.data_ptr(), out.usable.data_ptr(),
+                                   out.sector_offsets.data_ptr(), out.sector_count.data_ptr(), 0 if sof is None or not n else sof.data_ptr(), 0,
+                                   run.cuda_stream)
+    if (dist is None) == (out.dist is None) and (sof is None) == (out.sector_of is None):
+        return out
+    return KeypointBatch(out.index, out.points, out.usable, dist, out.sector_offsets, out.sector_count, sof)      # (without what was not asked for)
 
 
 class NeighbourBatch:
