@@ -924,6 +924,73 @@ int snowgpu_points_in_boxes_device(snowgpu_ctx *ctx, int n_frames, int64_t n_tot
                                    double *d_out_pose /* or NULL */, void *stream);
 
 /*
+ * ROTATED BOX IoU AND NMS: pcdet's iou3d_nms family -- boxes_iou_bev, boxes_iou3d_gpu, nms_gpu -- with static shapes, nothing read on the
+ * host.  snowgpu_boxes_iou_device gives the overlap of every box of one set with every box of another (the target layer's rois against
+ * gt_boxes) and, without materialising the matrix, the best partner of every box; snowgpu_nms_device gives the keep list of scored
+ * proposals in the layout the rois of snowgpu_fps_sectors_device and the boxes of snowgpu_points_in_boxes_device have.  The definition is
+ * restated in NumPy by tests/iou_reference.py; csrc/sg_iou.h holds its C++, for the device and for the host.
+ *   BOXES AND POSE: (F, B, Cb) in T = float32 or float64, Cb in 7 .. 10, columns 0 .. 6 cx, cy, cz, dx, dy, dz, heading; PRESENT and POSE
+ *   exactly as for snowgpu_points_in_boxes_device: all seven finite, |cx|, |cy|, |cz| <= 1e6, 0 < dx, dy, dz <= 1e6, |heading| <= 1e6; the
+ *   pose (c, s) the caller's (F, B, 2) float64 as it is, or with NULL cos / sin of (double)heading from the device library; a box with
+ *   |(c c + s s) - 1| > 1e-6 is absent.  Zero rows are absent.  The half extents are hx = dx / 2, hy = dy / 2, hz = dz / 2 WITHOUT the
+ *   1e-5 margin of the membership test (pcdet's IoU has none); the box's z is its CENTRE.
+ *   Everything behind the pose is float64 with + - x /, comparisons and fabs only, every operation rounded on its own, no fused
+ *   multiply-add, in the order written here.  There is no atan2 and no angular sort of intersection points.
+ *   AREA(a, b), a clipped in b's frame:
+ *     1. the corners of a in the order (+,+), (-,+), (-,-), (+,-): x = cxa + (lx ca - ly sa), y = cya + (lx sa + ly ca), lx = +-hxa, ly = +-hya;
+ *     2. each into b's frame: sx = x - cxb, sy = y - cyb, u = sx cb + sy sb, v = sy cb - sx sb;
+ *     3. the polygon is clipped against four half-planes in the order u <= hxb, -u <= hxb, v <= hyb, -v <= hyb (Sutherland-Hodgman).  For
+ *        every edge (p, q) in order, q the next vertex and the first one behind the last: dp = +-p[axis], dq = +-q[axis]; a point is inside
+ *        iff d <= h (the boundary is inside); p is emitted if it is inside; then, if exactly one of p and q is inside, the crossing is
+ *        emitted: its clipped coordinate is exactly +-h, its other one p_o + t (q_o - p_o) with t = (h - dp) / (dq - dp) (the divisor is
+ *        not 0: one of dp, dq is <= h, the other > h).  An empty polygon: the area is 0.
+ *        CAPACITY: in exact arithmetic the polygon has at most 8 vertices.  In floating point it can have more (equal boxes, headings
+ *        1 ulp apart: up to 10 were seen), but a pass over n vertices emits at most n + floor(n / 2) -- 4, 6, 9, 13, 19 -- and a polygon
+ *        is held in 20 slots: no vertex is ever dropped, for any input (csrc/sg_iou.h; tests/host_harness/iou_clip.cpp asserts it).
+ *     4. area = 0.5 |sum_i (u_i v_(i+1) - u_(i+1) v_i)|, summed sequentially from i = 0, the last term closing to vertex 0.
+ *   area(a, b) and area(b, a) differ in their last bits: the IoU matrix uses area(a_m, b_b), NMS area(candidate, kept box).
+ *   IoU, with A = dx dy and inter = area(a, b): BEV (mode 0) inter / max(Aa + Ab - inter, 1e-8).  3D (mode 1):
+ *   h = max(min(cza + hza, czb + hzb) - max(cza - hza, czb - hzb), 0), I3 = inter h, V = (dx dy) dz, I3 / max(Va + Vb - I3, 1e-6) -- pcdet's
+ *   epsilons; sums left to right.  Either box absent: exactly 0.  The value is stored as (T)iou.
+ * snowgpu_boxes_iou_device, M = n_a boxes a and B = n_b boxes b per frame:
+ *   d_out_iou       (F, M, B) T, or NULL: iou(a_m, b_b)
+ *   d_out_best      (F, M) int32, or NULL: the smallest b with the largest IoU of a_m (compared in float64), provided that IoU is > 0;
+ *                   otherwise -1 -- the target layer's gt_assignment
+ *   d_out_best_iou  (F, M) T, or NULL: (T) of that IoU, 0 where best is -1 -- max_overlaps
+ *   Domain: 1 <= M, B <= 9216; both feature counts in 7 .. 10; F M B <= 2^31 - 1; dtype 0 or 1; mode 0 or 1; at least one output; every
+ *   output apart from the boxes, the given poses and every other output (the two box sets may be one).
+ * snowgpu_nms_device, class-agnostic rotated NMS as nms_gpu, B = n_boxes per frame, d_scores (F, B) T:
+ *   The CANDIDATES of a frame are its present boxes whose score is not NaN and has (double)score >= score_thresh.  They are RANKED by score
+ *   descending (compared in T; -0 and +0 are equal), the smallest box number first among equals.  Walking the ranking, candidate j is
+ *   suppressed iff some already KEPT box i has iou(j, i) > iou_thresh -- strict, compared in float64 before any rounding to T, with
+ *   area(j, i), in the mode asked for; otherwise it is kept.  The walk stops after post_max kept.  There is no pre_max: callers take
+ *   top-k first, as pcdet does in front of nms_gpu.
+ *   d_out_index   (F, post_max) int32: the kept box numbers in rank order, -1 behind the count
+ *   d_out_count   (F) int32: the kept boxes of the frame
+ *   d_out_boxes   (F, post_max, Cb) T, or NULL: the kept boxes with all their columns, ZERO rows behind the count: a valid rois / gt_boxes
+ *                 tensor as it stands
+ *   d_out_scores  (F, post_max) T, or NULL: their scores, 0 behind the count
+ *   d_out_kept    (F, B) uint8, or NULL: 1 for a kept box
+ *   Domain: 1 <= post_max <= B <= 9216; box_features in 7 .. 10; F B <= 2^31 - 1; neither threshold NaN (score_thresh -inf: every score
+ *   but NaN); dtype and mode as above; every output apart from the boxes, the scores, the given pose and every other output.
+ * Anything outside a domain is SNOWGPU_E_INVALID.  Every element of every output is written by every call; two calls give identical bytes;
+ * no atomic is used.  One lane per pair: the IoU runs one wave per box a over tiles of 64 records of b in LDS and folds best across the
+ * wave; NMS ranks by counting and then sweeps LAZILY, one workgroup per frame: blocks of 64 ranked candidates are tested against the
+ * boxes kept so far, then the block's own triangle is resolved in order -- candidates x kept pairs, no mask in memory
+ * (csrc/snowgpu_iou.hip).  Scratch in the context, grown on first use: nine doubles per box, and for NMS an int32 per box.  Both entries
+ * use the SAME record scratch: two calls on one context, of either entry, must be ordered on their streams; calls on streams that run
+ * concurrently need a context each.  Three kernels
+ * each on `stream`, no memset; nothing is read on the host, nothing allocated after the first call of a size: capturable as a linear graph.
+ */
+int snowgpu_boxes_iou_device(snowgpu_ctx *ctx, int n_frames, int n_a, const void *d_boxes_a, int a_features, int n_b, const void *d_boxes_b,
+                             int b_features, int dtype, int mode, const double *d_pose_a /* or NULL */, const double *d_pose_b /* or NULL */,
+                             void *d_out_iou /* or NULL */, int32_t *d_out_best /* or NULL */, void *d_out_best_iou /* or NULL */, void *stream);
+int snowgpu_nms_device(snowgpu_ctx *ctx, int n_frames, int n_boxes, const void *d_boxes, int box_features, const void *d_scores, int dtype, int mode,
+                       double iou_thresh, double score_thresh, int post_max, const double *d_pose_in /* or NULL */, int32_t *d_out_index,
+                       int32_t *d_out_count, void *d_out_boxes /* or NULL */, void *d_out_scores /* or NULL */, uint8_t *d_out_kept /* or NULL */,
+                       void *stream);
+
+/*
  * PER-FRAME WEATHER in one aligned call.  snowgpu_augment_wet_batch_device_aligned_masked applies one weather to every frame, its wet
  * settings host scalars that a captured graph bakes in.  Here every frame brings a record of 8 doubles in DEVICE memory,
  *     d_weather[f] = [snow, wet, water_height, pavement_depth, wet_noise_floor, power_factor, delta, 0]

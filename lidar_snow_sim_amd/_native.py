@@ -31,7 +31,7 @@ EXPORTS = [
     "snowgpu_augment_batch_device_aligned_masked", "snowgpu_augment_wet_batch_device_aligned_masked", "snowgpu_fov_mask_device",
     "snowgpu_augment_weather_batch_device_aligned", "snowgpu_draw_weather_device", "snowgpu_dror_mask_device",
     "snowgpu_voxelize_device", "snowgpu_fps_device", "snowgpu_ball_query_device", "snowgpu_range_image_device",
-    "snowgpu_nearest_centres_device", "snowgpu_points_in_boxes_device", "snowgpu_fps_sectors_device",
+    "snowgpu_nearest_centres_device", "snowgpu_points_in_boxes_device", "snowgpu_boxes_iou_device", "snowgpu_nms_device", "snowgpu_fps_sectors_device",
 ]
 
 WET_ESTIMATION = {"linear": 0, "poly": 1}
@@ -162,6 +162,12 @@ def lib():
             L.snowgpu_points_in_boxes_device.restype = ctypes.c_int
             L.snowgpu_points_in_boxes_device.argtypes = [vp, ctypes.c_int, i64, i64, vp, vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, vp, vp, vp, vp, vp,
                                                          vp, vp]
+            L.snowgpu_boxes_iou_device.restype = ctypes.c_int
+            L.snowgpu_boxes_iou_device.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                   vp, vp, vp, vp, vp, vp]
+            L.snowgpu_nms_device.restype = ctypes.c_int
+            L.snowgpu_nms_device.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double,
+                                             ctypes.c_int, vp, vp, vp, vp, vp, vp, vp]
             L.snowgpu_set_fov_precrop.restype = ctypes.c_int
             L.snowgpu_set_fov_precrop.argtypes = [vp, ctypes.c_int]
             L.snowgpu_last_status.restype = ctypes.c_int
@@ -675,6 +681,34 @@ class Context:
                                                     int(dtype_code), i32(n_boxes), vp(d_boxes or None), i32(box_features), vp(d_pose_in or None),
                                                     vp(d_keep_in or None), vp(d_out_box_of or None), vp(d_out_count or None), vp(d_out_local or None),
                                                     vp(d_out_pose or None), vp(stream or None))
+        if rc == E_INVALID:
+            raise ValueError(self._L.snowgpu_last_error(self._h).decode())
+        self._check(rc)
+
+    def boxes_iou_device(self, n_frames, n_a, d_boxes_a, a_features, n_b, d_boxes_b, b_features, dtype_code, mode, d_pose_a, d_pose_b, d_out_iou,
+                         d_out_best, d_out_best_iou, stream=0):
+        """The IoU of every box a with every box b of its frame and the best b of every a (include/snowgpu.h: snowgpu_boxes_iou_device);
+        asynchronous on `stream`.  mode 0: BEV, 1: 3D.  The poses and up to two of the outputs may be 0.  An argument outside the domain, or an
+        output overlapping an input or another output, raises ValueError with the entry's words."""
+        vp = ctypes.c_void_p
+        i32 = lambda v: max(-(2 ** 31), min(int(v), 2 ** 31 - 1))
+        rc = self._L.snowgpu_boxes_iou_device(self._h, i32(n_frames), i32(n_a), vp(d_boxes_a or None), i32(a_features), i32(n_b), vp(d_boxes_b or None),
+                                              i32(b_features), int(dtype_code), int(mode), vp(d_pose_a or None), vp(d_pose_b or None), vp(d_out_iou or None),
+                                              vp(d_out_best or None), vp(d_out_best_iou or None), vp(stream or None))
+        if rc == E_INVALID:
+            raise ValueError(self._L.snowgpu_last_error(self._h).decode())
+        self._check(rc)
+
+    def nms_device(self, n_frames, n_boxes, d_boxes, box_features, d_scores, dtype_code, mode, iou_thresh, score_thresh, post_max, d_pose_in, d_out_index,
+                   d_out_count, d_out_boxes, d_out_scores, d_out_kept, stream=0):
+        """The keep list of rotated NMS per frame (include/snowgpu.h: snowgpu_nms_device); asynchronous on `stream`.  d_pose_in, d_out_boxes,
+        d_out_scores and d_out_kept may be 0.  An argument outside the domain, or an output overlapping an input or another output, raises
+        ValueError with the entry's words."""
+        vp = ctypes.c_void_p
+        i32 = lambda v: max(-(2 ** 31), min(int(v), 2 ** 31 - 1))
+        rc = self._L.snowgpu_nms_device(self._h, i32(n_frames), i32(n_boxes), vp(d_boxes or None), i32(box_features), vp(d_scores or None), int(dtype_code),
+                                        int(mode), float(iou_thresh), float(score_thresh), i32(post_max), vp(d_pose_in or None), vp(d_out_index or None),
+                                        vp(d_out_count or None), vp(d_out_boxes or None), vp(d_out_scores or None), vp(d_out_kept or None), vp(stream or None))
         if rc == E_INVALID:
             raise ValueError(self._L.snowgpu_last_error(self._h).decode())
         self._check(rc)

@@ -323,6 +323,14 @@ struct SgBoxRec;
 int sg_launch_box(const void *rows, int dtype, int64_t n, const int64_t *frame_off, int n_frames, const uint8_t *keep_in, int32_t n_boxes,
                   const void *boxes, int32_t box_features, const double *pose_in, struct SgBoxRec *rec, unsigned long long *table, int32_t *out_box_of,
                   int32_t *out_count, void *out_local, double *out_pose, void *stream);
+// Rotated box IoU and NMS (sg_iou.h; the definition: include/snowgpu.h): three kernels each.  Scratch: rec, sg_iou_records() doubles for
+// n_frames (M + B) boxes (the IoU) or n_frames B (NMS); order, n_frames B; n_cand, n_frames.  The poses and every output but the NMS
+// index and count may be null (the IoU needs one output).
+int sg_launch_iou(int n_frames, int32_t M, const void *boxes_a, int32_t a_features, int32_t B, const void *boxes_b, int32_t b_features, int dtype, int mode,
+                  const double *pose_a, const double *pose_b, double *rec, void *out_iou, int32_t *out_best, void *out_best_iou, void *stream);
+int sg_launch_nms(int n_frames, int32_t B, const void *boxes, int32_t box_features, const void *scores, int dtype, int mode, double iou_thresh,
+                  double score_thresh, int32_t post_max, const double *pose_in, double *rec, int32_t *order, int32_t *n_cand, int32_t *out_index,
+                  int32_t *out_count, void *out_boxes, void *out_scores, uint8_t *out_kept, void *stream);
 #ifdef __cplusplus
 }
 #endif

@@ -523,6 +523,96 @@ static inline int sg_check_box_args(const SgBoxArgs &a, std::string *msg)
     return 0;
 }
 
+// ---- snowgpu_boxes_iou_device -------------------------------------------------------------------------------------------------------------
+struct SgIouArgs {
+    int n_frames;
+    int n_a;                          // M, per frame
+    const void *boxes_a;
+    int a_features;
+    int n_b;                          // B, per frame
+    const void *boxes_b;
+    int b_features;
+    int dtype, mode;
+    const double *pose_a, *pose_b;    // or NULL: cos / sin of the heading on the device
+    void *out_iou;                    // or NULL
+    int32_t *out_best;                // or NULL
+    void *out_best_iou;               // or NULL
+};
+
+// 0, or SG_ARGS_INVALID with *msg.  As above, the order is part of the ABI.
+static inline int sg_check_iou_args(const SgIouArgs &a, std::string *msg)
+{
+    static const char *who = "snowgpu_boxes_iou_device";
+    if (a.n_frames <= 0 || !a.boxes_a || !a.boxes_b || (a.dtype != 0 && a.dtype != 1)) return sg_refuse(who, ": null pointer or bad dtype", msg);
+    if (a.mode != 0 && a.mode != 1) return sg_refuse(who, ": mode must be 0 (BEV) or 1 (3D)", msg);
+    if (!a.out_iou && !a.out_best && !a.out_best_iou) return sg_refuse(who, ": no output: pass d_out_iou, d_out_best or d_out_best_iou", msg);
+    if (a.n_a < 1 || a.n_a > 9216 || a.n_b < 1 || a.n_b > 9216) return sg_refuse(who, ": the boxes per frame must lie in 1 .. 9216 on either side", msg);
+    if (a.a_features < 7 || a.a_features > 10 || a.b_features < 7 || a.b_features > 10)
+        return sg_refuse(who, ": box_features must lie in 7 .. 10: cx, cy, cz, dx, dy, dz, heading first", msg);
+    if ((int64_t)a.n_frames * a.n_a * a.n_b > ((int64_t)1 << 31) - 1) return sg_refuse(who, ": n_frames * M * B exceeds 2^31 - 1; split the batch", msg);
+    const size_t esz = a.dtype == 0 ? 4 : 8, qa = (size_t)a.n_frames * (size_t)a.n_a, qb = (size_t)a.n_frames * (size_t)a.n_b;
+    const struct { const void *p; size_t bytes; const char *name; } outs[3] = {
+        {a.out_iou, qa * (size_t)a.n_b * esz, "d_out_iou"}, {a.out_best, qa * 4, "d_out_best"}, {a.out_best_iou, qa * esz, "d_out_best_iou"}};
+    const struct { const void *p; size_t bytes; const char *name; } ins[4] = {
+        {a.boxes_a, qa * (size_t)a.a_features * esz, "d_boxes_a"}, {a.boxes_b, qb * (size_t)a.b_features * esz, "d_boxes_b"},
+        {a.pose_a, qa * 16, "d_pose_a"}, {a.pose_b, qb * 16, "d_pose_b"}};
+    for (int i = 0; i < 3; ++i) {
+        const auto &o = outs[i];
+        for (int k = 0; k < 4; ++k)
+            if (sg_ranges_meet(o.p, o.bytes, ins[k].p, ins[k].bytes))
+                return sg_refuse(who, (std::string(": ") + o.name + " overlaps " + ins[k].name + "; the boxes and poses are read while the overlaps are written: pass a buffer apart from them").c_str(), msg);
+        for (int j = 0; j < i; ++j)
+            if (sg_ranges_meet(o.p, o.bytes, outs[j].p, outs[j].bytes))
+                return sg_refuse(who, (std::string(": ") + o.name + " overlaps " + outs[j].name + "; every output needs memory of its own").c_str(), msg);
+    }
+    return 0;
+}
+
+// ---- snowgpu_nms_device -------------------------------------------------------------------------------------------------------------------
+struct SgNmsArgs {
+    int n_frames;
+    int n_boxes;                      // B, per frame
+    const void *boxes;
+    int box_features;
+    const void *scores;
+    int dtype, mode;
+    double iou_thresh, score_thresh;
+    int post_max;
+    const double *pose_in;            // or NULL
+    int32_t *out_index, *out_count;
+    void *out_boxes, *out_scores;     // or NULL
+    uint8_t *out_kept;                // or NULL
+};
+
+static inline int sg_check_nms_args(const SgNmsArgs &a, std::string *msg)
+{
+    static const char *who = "snowgpu_nms_device";
+    if (a.n_frames <= 0 || !a.boxes || !a.scores || !a.out_index || !a.out_count || (a.dtype != 0 && a.dtype != 1))
+        return sg_refuse(who, ": null pointer or bad dtype", msg);
+    if (a.mode != 0 && a.mode != 1) return sg_refuse(who, ": mode must be 0 (BEV) or 1 (3D)", msg);
+    if (a.n_boxes < 1 || a.n_boxes > 9216) return sg_refuse(who, ": n_boxes must lie in 1 .. 9216", msg);
+    if (a.box_features < 7 || a.box_features > 10) return sg_refuse(who, ": box_features must lie in 7 .. 10: cx, cy, cz, dx, dy, dz, heading first", msg);
+    if (a.post_max < 1 || a.post_max > a.n_boxes) return sg_refuse(who, ": post_max must lie in 1 .. n_boxes", msg);
+    if (a.iou_thresh != a.iou_thresh || a.score_thresh != a.score_thresh) return sg_refuse(who, ": a threshold is NaN", msg);
+    if ((int64_t)a.n_frames * a.n_boxes > ((int64_t)1 << 31) - 1) return sg_refuse(who, ": n_frames * n_boxes exceeds 2^31 - 1; split the batch", msg);
+    const size_t esz = a.dtype == 0 ? 4 : 8, q = (size_t)a.n_frames * (size_t)a.n_boxes, k = (size_t)a.n_frames * (size_t)a.post_max;
+    const struct { const void *p; size_t bytes; const char *name; } outs[5] = {
+        {a.out_index, k * 4, "d_out_index"}, {a.out_count, (size_t)a.n_frames * 4, "d_out_count"}, {a.out_boxes, k * (size_t)a.box_features * esz, "d_out_boxes"},
+        {a.out_scores, k * esz, "d_out_scores"}, {a.out_kept, q, "d_out_kept"}};
+    const struct { const void *p; size_t bytes; const char *name; } ins[3] = {
+        {a.boxes, q * (size_t)a.box_features * esz, "d_boxes"}, {a.scores, q * esz, "d_scores"}, {a.pose_in, q * 16, "d_pose_in"}};
+    for (int i = 0; i < 5; ++i) {
+        const auto &o = outs[i];
+        for (int j = 0; j < 3; ++j)
+            if (sg_ranges_meet(o.p, o.bytes, ins[j].p, ins[j].bytes))
+                return sg_refuse(who, (std::string(": ") + o.name + " overlaps " + ins[j].name + "; the boxes, scores and pose are read while the keep list is written: pass a buffer apart from them").c_str(), msg);
+        for (int j = 0; j < i; ++j)
+            if (sg_ranges_meet(o.p, o.bytes, outs[j].p, outs[j].bytes))
+                return sg_refuse(who, (std::string(": ") + o.name + " overlaps " + outs[j].name + "; every output needs memory of its own").c_str(), msg);
+    }
+    return 0;
+}
+
 // 0, or SG_ARGS_INVALID with *msg (built on this path only).  The order is part of the ABI: it decides which message a doubly wrong call gets.
 static inline int sg_check_device_args(const SgDeviceArgs &a, const SgCtxView &c, const SgEntryShape &s, std::string *msg)
 {

@@ -113,6 +113,9 @@ struct __attribute__((visibility("default"))) snowgpu_ctx {
     // points in boxes (snowgpu_points_in_boxes_device): one record of eight doubles per box, and per frame the bit table of its cells
     DevBuf<double> box_rec;
     DevBuf<unsigned long long> box_table;
+    // box IoU and NMS (snowgpu_boxes_iou_device, snowgpu_nms_device): one record of nine doubles per box; the ranking and its length
+    DevBuf<double> iou_rec;
+    DevBuf<int32_t> nms_order, nms_cand;
     // scratch shared by every batch
     DevBuf<int32_t> tile_hist, tile_base, perm, ctile_cnt, ctile_base, table_ids, out_src;
     DevBuf<uint8_t> srows;            // channel-sorted copy of the frames whose rows did not come channel-sorted (firing order)

@@ -1,5 +1,5 @@
 // snowgpu_device.cpp -- the entries of the C ABI (include/snowgpu.h) that take DEVICE pointers and enqueue on the caller's stream: every
-// *_batch_device* entry, the plane estimate, the FOV mask, the outlier filter, the voxel stage, the keypoint stage and its sectorized form, the ball query, the range image, the nearest centres, the points in boxes and the weather draw.  Each batch entry fills an SgDeviceArgs, has it checked
+// *_batch_device* entry, the plane estimate, the FOV mask, the outlier filter, the voxel stage, the keypoint stage and its sectorized form, the ball query, the range image, the nearest centres, the points in boxes, the box IoU and NMS and the weather draw.  Each batch entry fills an SgDeviceArgs, has it checked
 // (sg_device_args.h: every refusal, in one order), sets the device and runs batch_from_args() and the stages it needs.  The launch
 // sequence of a batch is snowgpu_batch.cpp; no host copy, no synchronisation, no allocation after the first call of a given size.
 #include "sg_host.h"
@@ -12,6 +12,7 @@
 #include "sg_ball.h"        // the grid of the ball query and the sizes of its scratch
 #include "sg_nn.h"          // the grid of the nearest-centres stage and the sizes of its scratch
 #include "sg_box.h"         // the record of a box and the sizes of the box stage's scratch
+#include "sg_iou.h"         // the record of the IoU and NMS stages and the size of their scratch
 #include "sg_range.h"       // the geometry of the range image and the limits in the rows' dtype
 
 static_assert(SG_ARGS_INVALID == SNOWGPU_E_INVALID && SG_PLANE_REFERENCE == 0, "sg_device_args.h restates these two");
@@ -618,6 +619,48 @@ extern "C" int snowgpu_points_in_boxes_device(snowgpu_ctx *ctx, int n_frames, in
     int e = sg_launch_box(d_rows, dtype, n_total, d_frame_offsets, n_frames, d_keep_in, n_boxes, d_boxes, box_features, d_pose_in, (SgBoxRec *)ctx->box_rec.p,
                           ctx->box_table.p, d_out_box_of, d_out_count, d_out_local, d_out_pose, stream ? (hipStream_t)stream : ctx->stream);
     if (e) return fail(ctx, SNOWGPU_E_HIP, std::string("points in boxes launch: ") + hipGetErrorString((hipError_t)e));
+    return SNOWGPU_OK;
+}
+
+// Rotated box IoU (snowgpu_iou.hip; presence, the record, the clip and the two IoUs: sg_iou.h).  See include/snowgpu.h.
+extern "C" int snowgpu_boxes_iou_device(snowgpu_ctx *ctx, int n_frames, int n_a, const void *d_boxes_a, int a_features, int n_b, const void *d_boxes_b,
+                                        int b_features, int dtype, int mode, const double *d_pose_a, const double *d_pose_b, void *d_out_iou,
+                                        int32_t *d_out_best, void *d_out_best_iou, void *stream)
+{
+    if (!ctx) return SNOWGPU_E_INVALID;
+    const SgIouArgs a{n_frames, n_a, d_boxes_a, a_features, n_b, d_boxes_b, b_features, dtype, mode, d_pose_a, d_pose_b, d_out_iou, d_out_best, d_out_best_iou};
+    {
+        std::string msg;
+        if (int rc = sg_check_iou_args(a, &msg)) return fail(ctx, rc, msg);
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    ENSURE(ctx, ctx->iou_rec, sg_iou_records((size_t)n_frames * ((size_t)n_a + (size_t)n_b)));
+    int e = sg_launch_iou(n_frames, n_a, d_boxes_a, a_features, n_b, d_boxes_b, b_features, dtype, mode, d_pose_a, d_pose_b, ctx->iou_rec.p, d_out_iou, d_out_best,
+                          d_out_best_iou, stream ? (hipStream_t)stream : ctx->stream);
+    if (e) return fail(ctx, SNOWGPU_E_HIP, std::string("box IoU launch: ") + hipGetErrorString((hipError_t)e));
+    return SNOWGPU_OK;
+}
+
+// Rotated NMS (snowgpu_iou.hip: the ranking by counting and the lazy sweep).  See include/snowgpu.h.
+extern "C" int snowgpu_nms_device(snowgpu_ctx *ctx, int n_frames, int n_boxes, const void *d_boxes, int box_features, const void *d_scores, int dtype, int mode,
+                                  double iou_thresh, double score_thresh, int post_max, const double *d_pose_in, int32_t *d_out_index, int32_t *d_out_count,
+                                  void *d_out_boxes, void *d_out_scores, uint8_t *d_out_kept, void *stream)
+{
+    if (!ctx) return SNOWGPU_E_INVALID;
+    const SgNmsArgs a{n_frames, n_boxes, d_boxes, box_features, d_scores, dtype, mode, iou_thresh, score_thresh, post_max, d_pose_in, d_out_index, d_out_count,
+                      d_out_boxes, d_out_scores, d_out_kept};
+    {
+        std::string msg;
+        if (int rc = sg_check_nms_args(a, &msg)) return fail(ctx, rc, msg);
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    ENSURE(ctx, ctx->iou_rec, sg_iou_records((size_t)n_frames * (size_t)n_boxes));
+    ENSURE(ctx, ctx->nms_order, (size_t)n_frames * (size_t)n_boxes);
+    ENSURE(ctx, ctx->nms_cand, (size_t)n_frames);
+    int e = sg_launch_nms(n_frames, n_boxes, d_boxes, box_features, d_scores, dtype, mode, iou_thresh, score_thresh, post_max, d_pose_in, ctx->iou_rec.p,
+                          ctx->nms_order.p, ctx->nms_cand.p, d_out_index, d_out_count, d_out_boxes, d_out_scores, d_out_kept,
+                          stream ? (hipStream_t)stream : ctx->stream);
+    if (e) return fail(ctx, SNOWGPU_E_HIP, std::string("NMS launch: ") + hipGetErrorString((hipError_t)e));
     return SNOWGPU_OK;
 }
 

@@ -34,6 +34,10 @@ The reference's training-time caller (the OpenPCDet DENSE dataset: `root_path`, 
   * `points_in_boxes(frames_or_result, boxes)` labels every row with the 3D box of its frame that contains it and counts the rows of
     every box (BoxLabelBatch; snowgpu_points_in_boxes_device): roiaware_pool3d's points_in_boxes_gpu and num_points_in_gt after the
     augmentation; `labels`, `keep_boxes` and `rows_in` are the point heads' targets, filter_by_min_points and a keep mask of the objects.
+  * `nms(boxes, scores, iou_thresh, post_max=)` keeps the proposals of every frame by rotated NMS (NmsBatch; snowgpu_nms_device): pcdet's
+    nms_gpu without its host sweep, its `boxes` the rois of `sample_keypoints(rois=)` as they stand; `boxes_iou(boxes_a, boxes_b)` is the
+    rotated IoU matrix and the best partner of every box (IouBatch; snowgpu_boxes_iou_device): boxes_iou3d_gpu / boxes_iou_bev and the
+    target layer's max_overlaps / gt_assignment.
   * `augment_wet_batch_aligned(frames, ...)` is the snowfall + wet-ground chain with that aligned result (AlignedWetResult: per-frame
     flags beside it; snowgpu_augment_wet_batch_device_aligned), `wet_ground_batch_aligned(frames, keep)` the wet-ground stage alone on rows
     and a keep mask from any earlier stage (snowgpu_wet_ground_batch_device_aligned).
@@ -44,6 +48,7 @@ no arithmetic of the simulation happens in this file.
 """
 from __future__ import annotations
 
+import math
 import os
 import random
 from collections import OrderedDict
@@ -1326,6 +1331,167 @@ def points_in_boxes(frames, boxes, *, pose=None, keep=None, out=None, return_cou
     same = (out.n_boxes == B and np.array_equal(out.offsets, np.asarray(offsets, np.int64)) and (count is None) == (out.count is None) and
             (local is None) == (out.local is None) and (used is None) == (out.pose is None))
     return out if same else BoxLabelBatch(out.box_of, count, local, used, offsets, B)
+
+
+IOU_MODES = {"bev": 0, "3d": 1}
+
+
+def _box_set(torch, who, name, boxes, limit, like=None):
+    """(F, B, Cb) of a box tensor after the checks the box entries share."""
+    if not (torch.is_tensor(boxes) and boxes.is_cuda and boxes.dim() == 3 and boxes.dtype in (torch.float32, torch.float64) and boxes.is_contiguous()):
+        raise ValueError(f"{who}: {name} must be a contiguous (frames, B, 7 .. 10) float32 or float64 CUDA tensor")
+    if like is not None and not (boxes.dtype == like.dtype and boxes.device == like.device and boxes.shape[0] == like.shape[0]):
+        raise ValueError(f"{who}: {name} must have the frames, the dtype and the device of the other boxes")
+    F, B, Cb = (int(v) for v in boxes.shape)
+    if F < 1 or not 1 <= B <= limit:
+        raise ValueError(f"{who}: the boxes per frame must lie in 1 .. {limit}, the frames be at least 1 ({name})")
+    if not 7 <= Cb <= 10:
+        raise ValueError(f"{who}: box_features must lie in 7 .. 10: cx, cy, cz, dx, dy, dz, heading first ({name})")
+    return F, B, Cb
+
+
+def _box_pose(torch, who, name, pose, boxes):
+    shape = tuple(boxes.shape[:2]) + (2,)
+    if pose is not None and not (torch.is_tensor(pose) and tuple(pose.shape) == shape and pose.dtype == torch.float64 and pose.device == boxes.device and pose.is_contiguous()):
+        raise ValueError(f"{who}: {name} must be a contiguous {shape} float64 tensor (cos, sin) on the device of the boxes")
+    return 0 if pose is None else pose.data_ptr()
+
+
+def _checked_out(torch, who, kind, out, want, dev):
+    for name, dtype, shape, asked in want:
+        t = getattr(out, name, None) if isinstance(out, kind) else None
+        if asked and not (torch.is_tensor(t) and tuple(t.shape) == shape and t.dtype == dtype and t.is_contiguous() and t.device == dev):
+            raise ValueError(f"{who}: out must be a {kind.__name__} whose {name} is a contiguous {shape} {dtype} tensor on the device of the boxes")
+
+
+class IouBatch:
+    """What boxes_iou() leaves behind, F frames, M boxes a and B boxes b per frame -- every shape static: `iou` (F, M, B in the boxes' dtype:
+    the IoU of a_m with b_b, 0 where either is absent; None unless asked for), `best` (F, M int32: the smallest b with the largest IoU of
+    a_m if that IoU is > 0, else -1 -- the target layer's gt_assignment; None unless asked for) and `best_iou` (F, M: that IoU, 0 where best
+    is -1 -- max_overlaps).  All still being written until the stream the call was made on has caught up."""
+
+    def __init__(self, iou=None, best=None, best_iou=None):
+        self.iou, self.best, self.best_iou = iou, best, best_iou
+
+    @classmethod
+    def empty(cls, n_frames, n_a, n_b, dtype=None, device=None, with_iou=True, with_best=False):
+        """Uninitialised buffers of the shapes boxes_iou() writes (out=): static addresses for a captured graph."""
+        import torch
+        dev = torch.device("cuda", torch.cuda.current_device() if device is None else int(device)) if not isinstance(device, torch.device) else device
+        F, M, B, dt = int(n_frames), int(n_a), int(n_b), dtype or torch.float32
+        return cls(torch.empty((F, M, B), dtype=dt, device=dev) if with_iou else None, torch.empty((F, M), dtype=torch.int32, device=dev) if with_best else None,
+                   torch.empty((F, M), dtype=dt, device=dev) if with_best else None)
+
+
+def boxes_iou(boxes_a, boxes_b, *, mode='3d', pose_a=None, pose_b=None, out=None, return_iou=True, return_best=False, slot=0):
+    """The rotated IoU of every box of `boxes_a` with every box of `boxes_b` of its frame on the device (snowgpu_boxes_iou_device; the
+    definition: include/snowgpu.h): pcdet's boxes_iou3d_gpu (mode '3d') and boxes_iou_bev (mode 'bev') in float64 by clipping in a fixed
+    order, and the best partner of every box a without materialising the matrix.
+
+    boxes_a   a contiguous (F, M, 7 .. 10) float32 or float64 CUDA tensor, 1 <= M <= 9216: cx, cy, cz, dx, dy, dz, heading first (rois; the
+              `boxes` of an NmsBatch as they stand: zero rows are absent boxes).
+    boxes_b   (F, B, 7 .. 10) likewise, same dtype and device, 1 <= B <= 9216 (gt_boxes); F M B < 2^31.
+    pose_a, pose_b   None: cos / sin of the heading in float64 on the device; or contiguous (F, M, 2) / (F, B, 2) float64 tensors used as they are.
+    out       an IouBatch to write into (IouBatch.empty): every element is written.
+    return_iou, return_best   which outputs to compute; at least one.
+    The records of the boxes are scratch of the engine of `slot`, shared by nms() and boxes_iou(): calls made on streams that are not ordered
+    against each other (torch's default stream runs on a side stream of the engine) need a `slot` each.
+
+    Returns an IouBatch.  Asynchronous on torch's current stream; nothing is read on the host: capturable after one warm-up call."""
+    import torch
+    from . import engine as _engine
+    who = "boxes_iou"
+    F, M, Ca = _box_set(torch, who, "boxes_a", boxes_a, 9216)
+    _, B, Cb = _box_set(torch, who, "boxes_b", boxes_b, 9216, boxes_a)
+    if mode not in IOU_MODES:
+        raise ValueError(f"{who}: mode must be 'bev' or '3d'")
+    if not (return_iou or return_best):
+        raise ValueError(f"{who}: nothing to compute: return_iou or return_best")
+    if F * M * B > 2 ** 31 - 1:
+        raise ValueError(f"{who}: frames * M * B exceeds 2^31 - 1; split the batch")
+    dev, dt = boxes_a.device, boxes_a.dtype
+    pa, pb = _box_pose(torch, who, "pose_a", pose_a, boxes_a), _box_pose(torch, who, "pose_b", pose_b, boxes_b)
+    want = (("iou", dt, (F, M, B), return_iou), ("best", torch.int32, (F, M), return_best), ("best_iou", dt, (F, M), return_best))
+    if out is None:
+        out = IouBatch.empty(F, M, B, dt, dev, return_iou, return_best)
+    else:
+        _checked_out(torch, who, IouBatch, out, want, dev)
+    iou, best, best_iou = (out.iou if return_iou else None), (out.best if return_best else None), (out.best_iou if return_best else None)
+    eng = _engine.get_engine(dev.index, slot)
+    with torch.cuda.device(dev), _on_run_stream(torch, eng, dev) as (_, run):
+        eng.ctx.boxes_iou_device(F, M, boxes_a.data_ptr(), Ca, B, boxes_b.data_ptr(), Cb, 0 if dt == torch.float32 else 1, IOU_MODES[mode], pa, pb,
+                                 0 if iou is None else iou.data_ptr(), 0 if best is None else best.data_ptr(), 0 if best_iou is None else best_iou.data_ptr(),
+                                 run.cuda_stream)
+    same = (iou is None) == (out.iou is None) and (best is None) == (out.best is None)
+    return out if same else IouBatch(iou, best, best_iou)
+
+
+class NmsBatch:
+    """What nms() leaves behind, F frames of B boxes, P = post_max -- every shape static: `index` (F, P int32: the kept box numbers in rank
+    order, -1 behind the count), `count` (F int32), `boxes` (F, P, Cb in the boxes' dtype: the kept boxes with all their columns and ZERO
+    rows behind the count -- rois for sample_keypoints(rois=), boxes for points_in_boxes and boxes_iou as they stand; None unless asked
+    for), `scores` (F, P: their scores, 0 behind the count; None unless asked for) and `kept` (F, B uint8: 1 for a kept box; None unless
+    asked for).  All still being written until the stream the call was made on has caught up."""
+
+    def __init__(self, index, count, boxes=None, scores=None, kept=None):
+        self.index, self.count, self.boxes, self.scores, self.kept = index, count, boxes, scores, kept
+
+    @classmethod
+    def empty(cls, n_frames, n_boxes, post_max, box_features=7, dtype=None, device=None, with_boxes=True, with_scores=False, with_kept=False):
+        """Uninitialised buffers of the shapes nms() writes (out=): static addresses for a captured graph."""
+        import torch
+        dev = torch.device("cuda", torch.cuda.current_device() if device is None else int(device)) if not isinstance(device, torch.device) else device
+        F, B, P, dt = int(n_frames), int(n_boxes), int(post_max), dtype or torch.float32
+        return cls(torch.empty((F, P), dtype=torch.int32, device=dev), torch.empty(F, dtype=torch.int32, device=dev),
+                   torch.empty((F, P, int(box_features)), dtype=dt, device=dev) if with_boxes else None,
+                   torch.empty((F, P), dtype=dt, device=dev) if with_scores else None, torch.empty((F, B), dtype=torch.uint8, device=dev) if with_kept else None)
+
+
+def nms(boxes, scores, iou_thresh, *, post_max, score_thresh=-math.inf, mode='bev', pose=None, out=None, return_boxes=True, return_scores=False,
+        return_kept=False, slot=0):
+    """Class-agnostic rotated NMS per frame on the device (snowgpu_nms_device; the definition: include/snowgpu.h): pcdet's nms_gpu without
+    its host sweep.  The present boxes whose score is not NaN and is >= score_thresh are ranked by score (the smallest number first among
+    equals); a candidate is suppressed iff an already kept box has IoU > iou_thresh with it; the walk stops after post_max kept.
+
+    boxes     a contiguous (F, B, 7 .. 10) float32 or float64 CUDA tensor, 1 <= B <= 9216 (take torch.topk first, as pcdet does).
+    scores    a contiguous (F, B) tensor of the same dtype and device.
+    post_max  1 .. B: the static length of the keep list.
+    mode      'bev' (nms_gpu) or '3d'.
+    pose      None, or a contiguous (F, B, 2) float64 tensor (cos, sin) used as it is.
+    out       an NmsBatch to write into (NmsBatch.empty): every element is written.
+    The records of the boxes are scratch of the engine of `slot`, shared by nms() and boxes_iou(): calls made on streams that are not ordered
+    against each other (torch's default stream runs on a side stream of the engine) need a `slot` each.
+
+    Returns an NmsBatch.  Asynchronous on torch's current stream; nothing is read on the host: capturable after one warm-up call."""
+    import torch
+    from . import engine as _engine
+    who = "nms"
+    F, B, Cb = _box_set(torch, who, "boxes", boxes, 9216)
+    dev, dt = boxes.device, boxes.dtype
+    if not (torch.is_tensor(scores) and tuple(scores.shape) == (F, B) and scores.dtype == dt and scores.device == dev and scores.is_contiguous()):
+        raise ValueError(f"{who}: scores must be a contiguous {(F, B)} tensor in the boxes' dtype on their device")
+    if mode not in IOU_MODES:
+        raise ValueError(f"{who}: mode must be 'bev' or '3d'")
+    if isinstance(post_max, bool) or int(post_max) != post_max or not 1 <= int(post_max) <= B:
+        raise ValueError(f"{who}: post_max must be an integer in 1 .. B")
+    if math.isnan(float(iou_thresh)) or math.isnan(float(score_thresh)):
+        raise ValueError(f"{who}: a threshold is NaN")
+    P = int(post_max)
+    pp = _box_pose(torch, who, "pose", pose, boxes)
+    want = (("index", torch.int32, (F, P), True), ("count", torch.int32, (F,), True), ("boxes", dt, (F, P, Cb), return_boxes),
+            ("scores", dt, (F, P), return_scores), ("kept", torch.uint8, (F, B), return_kept))
+    if out is None:
+        out = NmsBatch.empty(F, B, P, Cb, dt, dev, return_boxes, return_scores, return_kept)
+    else:
+        _checked_out(torch, who, NmsBatch, out, want, dev)
+    kb, ks, kk = (out.boxes if return_boxes else None), (out.scores if return_scores else None), (out.kept if return_kept else None)
+    eng = _engine.get_engine(dev.index, slot)
+    with torch.cuda.device(dev), _on_run_stream(torch, eng, dev) as (_, run):
+        eng.ctx.nms_device(F, B, boxes.data_ptr(), Cb, scores.data_ptr(), 0 if dt == torch.float32 else 1, IOU_MODES[mode], float(iou_thresh), float(score_thresh),
+                           P, pp, out.index.data_ptr(), out.count.data_ptr(), 0 if kb is None else kb.data_ptr(), 0 if ks is None else ks.data_ptr(),
+                           0 if kk is None else kk.data_ptr(), run.cuda_stream)
+    same = (kb is None) == (out.boxes is None) and (ks is None) == (out.scores is None) and (kk is None) == (out.kept is None)
+    return out if same else NmsBatch(out.index, out.count, kb, ks, kk)
 
 
 def augment_batch(frames, particle_file_prefix, beam_divergence, shuffle=True, noise_floor=0.7, root_path=None, *, planes=None,

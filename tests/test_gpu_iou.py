@@ -1,0 +1,347 @@
+"""-m gpu: rotated box IoU and NMS on the device (tensors.boxes_iou, tensors.nms, lidar_snow_sim_amd.iou, snowgpu_boxes_iou_device,
+snowgpu_nms_device; csrc/snowgpu_iou.hip, csrc/sg_iou.h) against the NumPy restatement of their definition (tests/iou_reference.py, whose
+inputs tests/test_iou_reference.py holds to the conditions that keep these comparisons from being vacuous).  The restatement takes the pose
+as an input and everything behind the pose is separately rounded float64 arithmetic in the definition's order: every output is compared
+byte for byte, for both dtypes, with no element left out -- under a given pose, and under the pose the device computed, which
+points_in_boxes returns (the same device library, the same rule of presence)."""
+import numpy as np
+import pytest
+import torch
+
+import box_reference as br
+import iou_reference as ir
+
+pytestmark = pytest.mark.gpu
+
+DTYPES = ir.DTYPES
+IOU_FIELDS = ("iou", "best", "best_iou")
+NMS_FIELDS = ("index", "count", "boxes", "scores", "kept")
+
+
+def _t(a):
+    return torch.from_numpy(np.array(a, order="C")).cuda()          # (a copy: the shared inputs are read-only)
+
+
+def _iou(*args, **kw):
+    from lidar_snow_sim_amd.tensors import boxes_iou
+    return boxes_iou(*args, **kw)
+
+
+def _nms(*args, **kw):
+    from lidar_snow_sim_amd.tensors import nms
+    return nms(*args, **kw)
+
+
+def _same(got, want, what, fields):
+    for name in fields:
+        g = getattr(got, name).cpu().numpy()
+        assert g.dtype == want[name].dtype and g.shape == want[name].shape, (what, name, g.dtype, g.shape)
+        if g.tobytes() != want[name].tobytes():
+            bad = np.flatnonzero((g.view(np.uint8).reshape(g.size, -1) != want[name].view(np.uint8).reshape(g.size, -1)).any(axis=1))
+            raise AssertionError((what, name, len(bad), "first differing elements", bad[:8].tolist(), g.reshape(-1)[bad[:4]], want[name].reshape(-1)[bad[:4]]))
+
+
+def _device_pose(boxes):
+    """The (cos, sin) the device library gives for the headings of `boxes` (..., Cb), (0, 0) for an absent box: points_in_boxes returns the
+    pose it used; the boxes go through it 256 at a time, one row per frame."""
+    from lidar_snow_sim_amd.tensors import DeviceBatch, points_in_boxes
+    flat = np.asarray(boxes).reshape(-1, boxes.shape[-1])
+    G = (len(flat) + 255) // 256
+    padded = np.zeros((G * 256, flat.shape[1]), flat.dtype)
+    padded[:len(flat)] = flat
+    rows = DeviceBatch(_t(np.zeros((G, 5), flat.dtype)), np.arange(G + 1, dtype=np.int64))
+    pose = points_in_boxes(rows, _t(padded.reshape(G, 256, -1)), return_count=False, return_pose=True).pose.cpu().numpy()
+    return np.ascontiguousarray(pose.reshape(-1, 2)[:len(flat)].reshape(boxes.shape[:-1] + (2,)))
+
+
+def _run_nms(c, pose="given", **kw):
+    args = dict(post_max=c["post_max"], score_thresh=c["score_thresh"], mode=c["mode"], pose=_t(c["pose"]) if pose == "given" else None,
+                return_scores=True, return_kept=True)
+    args.update(kw)
+    return _nms(_t(c["boxes"]), _t(c["scores"]), c["iou_thresh"], **args)
+
+
+def _want_nms(c, pose=None, **kw):
+    a = dict(c, **kw)
+    return ir.nms(a["boxes"], a["scores"], a["pose"] if pose is None else pose, a["iou_thresh"], a["post_max"], a["score_thresh"], a["mode"])
+
+
+# ---- 1. the IoU matrix and the best partner ---------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("name", ir.IOU_CASES)
+def test_iou_cases_under_a_given_pose(name, dtype):
+    c = ir.iou_case(name, dtype)
+    a, b, pa, pb = _t(c["a"]), _t(c["b"]), _t(c["pose_a"]), _t(c["pose_b"])
+    for mode in ir.MODES:
+        _same(_iou(a, b, mode=mode, pose_a=pa, pose_b=pb, return_best=True), ir.iou_expected(name, dtype, mode), (name, dtype, mode), IOU_FIELDS)
+    want = ir.iou_expected(name, dtype, "3d")
+    alone = _iou(a, b, pose_a=pa, pose_b=pb, return_iou=False, return_best=True)
+    assert alone.iou is None
+    _same(alone, want, (name, dtype, "best alone"), IOU_FIELDS[1:])
+    alone = _iou(a, b, pose_a=pa, pose_b=pb)
+    assert alone.best is None and alone.best_iou is None
+    _same(alone, want, (name, dtype, "iou alone"), IOU_FIELDS[:1])
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("name", ir.IOU_CASES)
+def test_iou_cases_under_the_device_pose(name, dtype):
+    c = ir.iou_case(name, dtype)
+    pa, pb = _device_pose(c["a"]), _device_pose(c["b"])
+    assert np.abs(pa - br.used_pose(c["a"], c["pose_a"])).max() < 1e-15 and np.array_equal(pb != 0, br.used_pose(c["b"], c["pose_b"]) != 0)
+    for mode in ir.MODES:
+        _same(_iou(_t(c["a"]), _t(c["b"]), mode=mode, return_best=True), ir.boxes_iou(c["a"], c["b"], pa, pb, mode), (name, dtype, mode), IOU_FIELDS)
+
+
+# ---- 2. NMS ---------------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("name", ir.NMS_CASES)
+def test_nms_cases_under_a_given_pose(name, dtype):
+    c = ir.nms_case(name, dtype)
+    got = _run_nms(c)
+    _same(got, ir.nms_expected(name, dtype), (name, dtype), NMS_FIELDS)
+    index, kept = got.index.cpu().numpy(), got.kept.cpu().numpy()
+    for f in range(len(index)):                                        # return_kept says what index says
+        assert np.array_equal(np.flatnonzero(kept[f]), np.sort(index[f][index[f] >= 0]))
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("name", ir.NMS_CASES)
+def test_nms_cases_under_the_device_pose(name, dtype):
+    c = ir.nms_case(name, dtype)
+    pose = _device_pose(c["boxes"])
+    _same(_run_nms(c, pose=None), _want_nms(c, pose), (name, dtype), NMS_FIELDS)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_post_max_and_modes(dtype):
+    """post_max = 1, the number kept without a limit, and B; both modes; three frames of different content in one call."""
+    for name in ("b129", "mixed"):
+        c = ir.nms_case(name, dtype)
+        B = c["boxes"].shape[1]
+        free = _want_nms(c, post_max=B)
+        natural = int(free["count"].max())
+        assert 1 < natural < B
+        for mode in ir.MODES:
+            for post_max in (1, natural, B):
+                _same(_run_nms(c, post_max=post_max, mode=mode), _want_nms(c, post_max=post_max, mode=mode), (name, dtype, mode, post_max), NMS_FIELDS)
+    bare = _run_nms(c, return_boxes=False, return_scores=False, return_kept=False)
+    assert bare.boxes is None and bare.scores is None and bare.kept is None
+    _same(bare, ir.nms_expected("mixed", dtype), dtype, NMS_FIELDS[:2])
+    c = ir.nms_case("b129", dtype)                                     # a threshold above every IoU: all are kept; below every IoU: the first box suppresses all
+    assert _nms(_t(c["boxes"]), _t(c["scores"]), 2.0, post_max=129, pose=_t(c["pose"])).count.tolist() == [129]
+    assert _nms(_t(c["boxes"]), _t(c["scores"]), -1.0, post_max=129, pose=_t(c["pose"])).count.tolist() == [1]
+
+
+# ---- 3. buffers, runs, streams ----------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_every_element_is_written_in_place(dtype):
+    from lidar_snow_sim_amd.tensors import IouBatch, NmsBatch
+    td = getattr(torch, dtype)
+    for name in ("mixed", "b65"):
+        c = ir.nms_case(name, dtype)
+        F, B, Cb = c["boxes"].shape
+        out = NmsBatch.empty(F, B, c["post_max"], Cb, td, with_scores=True, with_kept=True)
+        for f in NMS_FIELDS:
+            getattr(out, f).view(torch.uint8).fill_(0x7f)
+        assert _run_nms(c, out=out) is out
+        _same(out, ir.nms_expected(name, dtype), (name, dtype), NMS_FIELDS)
+    c = ir.iou_case("m65b129", dtype)
+    out = IouBatch.empty(3, 65, 129, td, with_best=True)
+    for f in IOU_FIELDS:
+        getattr(out, f).view(torch.uint8).fill_(0x7f)
+    assert _iou(_t(c["a"]), _t(c["b"]), pose_a=_t(c["pose_a"]), pose_b=_t(c["pose_b"]), out=out, return_best=True) is out
+    _same(out, ir.iou_expected("m65b129", dtype, "3d"), dtype, IOU_FIELDS)
+
+
+def test_two_calls_and_two_streams_give_identical_bytes():
+    c = ir.nms_case("b4160")
+    runs = [_run_nms(c), _run_nms(c)]
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())                      # (one engine slot: its record scratch is shared, so the calls are ordered)
+    with torch.cuda.stream(side):
+        runs.append(_run_nms(c))
+    side.synchronize()
+    for f in NMS_FIELDS:
+        for other in runs[1:]:
+            assert getattr(runs[0], f).data_ptr() != getattr(other, f).data_ptr() and torch.equal(getattr(runs[0], f).view(torch.uint8), getattr(other, f).view(torch.uint8)), f
+    _same(runs[2], ir.nms_expected("b4160"), "side stream", NMS_FIELDS)
+    c = ir.iou_case("m3b9216")
+    args = (_t(c["a"]), _t(c["b"]))
+    kw = dict(pose_a=_t(c["pose_a"]), pose_b=_t(c["pose_b"]), return_best=True)
+    runs = [_iou(*args, **kw), _iou(*args, **kw)]
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        runs.append(_iou(*args, **kw))
+    side.synchronize()
+    for f in IOU_FIELDS:
+        for other in runs[1:]:
+            assert torch.equal(getattr(runs[0], f).view(torch.uint8), getattr(other, f).view(torch.uint8)), f
+    _same(runs[2], ir.iou_expected("m3b9216", "float32", "3d"), "side stream", IOU_FIELDS)
+
+
+# ---- 4. one graph: nms -> proposal-centric keypoints -> points in the kept boxes -> roi-to-gt IoU ------------------------------------------------
+def test_graph_capture():
+    """One capture after a warm-up, replayed on boxes, scores and gt rewritten in place, every output filled with 0x7f before: each
+    replay equals the restatements composed -- NMS, then fps_sectors_reference and box_reference on the kept boxes, then the IoU of the
+    kept boxes with gt.  The kept boxes' pose is the device's (points_in_boxes returns it); the given poses are NumPy's."""
+    import fps_sectors_reference as sr
+    from lidar_snow_sim_amd.tensors import BoxLabelBatch, DeviceBatch, IouBatch, KeypointBatch, NmsBatch, points_in_boxes, sample_keypoints
+    F, n, B, P, G, K, S = 2, 2500, 96, 24, 12, 48, 4
+    rng = np.random.default_rng(4300)
+    inputs = []
+    for _ in range(2):
+        boxes = np.stack([ir.clustered(rng, B, 10) for _ in range(F)]).astype(np.float32)
+        scores = rng.uniform(0.05, 1.0, (F, B)).astype(np.float32)
+        gt = np.stack([ir.clustered(rng, G, G, Cb=8, spread=0.0) for _ in range(F)]).astype(np.float32)
+        gt[:, :G - 2, :7] = boxes[:, 3:3 + G - 2, :7] + np.float32(0.3) * rng.normal(0, 1, (F, G - 2, 7)).astype(np.float32) * np.array([1, 1, 0.2, 0, 0, 0, 0.3], np.float32)
+        gt[:, G - 1] = 0.0
+        inputs.append((boxes, scores, gt))
+    frames = []
+    for f in range(F):                                                     # rows about the proposals of both inputs
+        at = np.concatenate((inputs[0][0][f, :, :3], inputs[1][0][f, :, :3]))[rng.integers(0, 2 * B, n)]
+        frames.append(np.column_stack((at + rng.normal(0, 1.5, (n, 3)) * np.array([1, 1, 0.4]), rng.integers(1, 255, n), rng.integers(0, 64, n))))
+    cloud = np.concatenate(frames).astype(np.float32)
+    offsets = np.arange(F + 1, dtype=np.int64) * n
+    rows = DeviceBatch(_t(cloud), offsets)
+    boxes, scores, gt = (_t(x) for x in inputs[0])
+    pose = _t(ir.numpy_pose(inputs[0][0]))
+    pose_gt = _t(ir.numpy_pose(inputs[0][2]))
+    nb_out = NmsBatch.empty(F, B, P, 8, torch.float32, with_scores=True, with_kept=True)
+    kp_out = KeypointBatch.empty(F, K, 4, torch.float32, sectors=S)
+    lb_out = BoxLabelBatch.empty(offsets, P, torch.float32, with_pose=True)
+    io_out = IouBatch.empty(F, P, G, torch.float32, with_best=True)
+    s = torch.cuda.Stream()
+
+    def chain():
+        nb = _nms(boxes, scores, 0.45, post_max=P, score_thresh=0.1, pose=pose, out=nb_out, return_scores=True, return_kept=True)
+        kp = sample_keypoints(rows, K, sectors=S, rois=nb.boxes, out=kp_out)
+        lb = points_in_boxes(rows, nb.boxes, out=lb_out, return_pose=True)
+        return nb, kp, lb, _iou(nb.boxes, gt, pose_b=pose_gt, out=io_out, return_best=True)
+
+    outputs = ([getattr(nb_out, f) for f in NMS_FIELDS] + [kp_out.index, kp_out.points, kp_out.usable, lb_out.box_of, lb_out.count, lb_out.pose] +
+               [getattr(io_out, f) for f in IOU_FIELDS])
+    with torch.cuda.stream(s):
+        chain()                                                            # warm-up: the captured calls allocate nothing
+        s.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, stream=s):
+            got = chain()
+        assert got[0] is nb_out and got[1] is kp_out and got[2] is lb_out and got[3] is io_out
+        snaps = []
+        for k in (1, 0):
+            for dst, src in zip((boxes, scores, gt), inputs[k]):
+                dst.copy_(_t(src))
+            pose.copy_(_t(ir.numpy_pose(inputs[k][0])))
+            pose_gt.copy_(_t(ir.numpy_pose(inputs[k][2])))
+            for t in outputs:
+                t.view(torch.uint8).fill_(0x7f)
+            g.replay()
+            snaps.append((k, [t.clone() for t in outputs]))
+        s.synchronize()
+    names = NMS_FIELDS + ("kp_index", "kp_points", "kp_usable", "box_of", "box_count", "box_pose") + IOU_FIELDS
+    counts = []
+    for k, snap in snaps:
+        got = dict(zip(names, (t.cpu().numpy() for t in snap)))
+        b, sc, g_ = inputs[k]
+        want = ir.nms(b, sc, ir.numpy_pose(b), 0.45, P, 0.1, "bev")
+        counts.append(want["count"].tolist())
+        assert (want["count"] > 2).all() and (want["count"] < P).any()
+        for f in NMS_FIELDS:
+            assert got[f].tobytes() == want[f].tobytes(), (k, f)
+        kp = sr.fps_sectors(cloud, K, S, None, 4, None, offsets, rois=want["boxes"], roi_margin=1.6)
+        assert (kp["usable"] >= K).all() and (kp["usable"] < n).all()
+        for f in ("index", "points", "usable"):
+            assert got["kp_" + f].tobytes() == kp[f].tobytes(), (k, "keypoints", f)
+        used = got["box_pose"]
+        assert np.array_equal(used.any(axis=-1), ir.present(want["boxes"], ir.numpy_pose(want["boxes"])))
+        lb = br.points_in_boxes(cloud, want["boxes"], used, None, offsets)
+        assert got["box_of"].tobytes() == lb["box_of"].tobytes() and got["box_count"].tobytes() == lb["count"].tobytes() and (lb["box_of"] >= 0).sum() > 100
+        io = ir.boxes_iou(want["boxes"], g_, used, ir.numpy_pose(g_), "3d")
+        assert (io["best"] >= 0).sum() >= 4 and (io["best"] == -1).sum() >= 1
+        for f in IOU_FIELDS:
+            assert got[f].tobytes() == io[f].tobytes(), (k, f)
+    assert counts[0] != counts[1]
+
+
+# ---- 5. the NumPy entries ---------------------------------------------------------------------------------------------------------------------
+def test_numpy_entries():
+    from lidar_snow_sim_amd import iou
+    for dtype in DTYPES:
+        c = ir.iou_case("m63b65", dtype)
+        for fn, mode in ((iou.boxes_iou_bev, "bev"), (iou.boxes_iou3d, "3d")):
+            got = fn(c["a"][1], c["b"][1])
+            assert got.dtype == c["a"].dtype and got.tobytes() == ir.iou_expected("m63b65", dtype, mode)["iou"][1].tobytes()
+        c, e = ir.nms_case("b129", dtype), ir.nms_expected("b129", dtype)
+        keep = iou.nms(c["boxes"][0], c["scores"][0], c["iou_thresh"])
+        assert keep.dtype == np.int32 and np.array_equal(keep, e["index"][0, :e["count"][0]])
+        assert np.array_equal(iou.nms(c["boxes"][0], c["scores"][0], c["iou_thresh"], post_max=5), e["index"][0, :5])
+    with pytest.raises(ValueError):
+        iou.boxes_iou_bev(c["boxes"][0][:, :6], c["boxes"][0])
+    with pytest.raises(ValueError):
+        iou.nms(c["boxes"][0], c["scores"][0][:5], 0.5)
+
+
+# ---- 6. refusals ------------------------------------------------------------------------------------------------------------------------------
+def test_refusals():
+    from lidar_snow_sim_amd.tensors import IouBatch, NmsBatch
+    c = ir.nms_case("mixed")
+    bx, sc, ps = _t(c["boxes"]), _t(c["scores"]), _t(c["pose"])
+    F, B, Cb = c["boxes"].shape
+    wide = _t(np.concatenate((c["boxes"], c["boxes"]), axis=2))
+    for kw, words in ((dict(boxes=bx.double()), "scores must be a contiguous"), (dict(boxes=bx.cpu()), "boxes must be a contiguous"), (dict(boxes=bx[0]), "boxes must be a contiguous"),
+                      (dict(boxes=wide[:, :, :8]), "boxes must be a contiguous"), (dict(boxes=bx[:, :, :6].contiguous()), "box_features must lie in 7 .. 10"),
+                      (dict(boxes=wide[:, :, :11].contiguous()), "box_features must lie in 7 .. 10"), (dict(boxes=_t(np.zeros((1, 9217, 7), np.float32))), "boxes per frame must lie in 1 .. 9216"),
+                      (dict(scores=sc[:, :5].contiguous()), "scores must be a contiguous"), (dict(scores=sc.double()), "scores must be a contiguous"),
+                      (dict(post_max=0), "post_max must be an integer in 1 .. B"), (dict(post_max=B + 1), "post_max must be an integer in 1 .. B"), (dict(post_max=2.5), "post_max must be"),
+                      (dict(mode="aligned"), "mode must be 'bev' or '3d'"), (dict(iou_thresh=float("nan")), "a threshold is NaN"), (dict(score_thresh=float("nan")), "a threshold is NaN"),
+                      (dict(pose=ps.float()), "pose must be a contiguous"), (dict(pose=ps[:, :5].contiguous()), "pose must be a contiguous"),
+                      (dict(out=NmsBatch.empty(F, B, 9, Cb)), "out must be a NmsBatch whose index"), (dict(out=NmsBatch.empty(F, B, 10, 7)), "out must be a NmsBatch whose boxes"),
+                      (dict(out=NmsBatch.empty(F, B, 10, Cb), return_kept=True), "out must be a NmsBatch whose kept")):
+        args = dict(boxes=bx, scores=sc, iou_thresh=0.5, post_max=10, pose=ps)
+        args.update(kw)
+        with pytest.raises(ValueError, match=words.replace("..", r"\.\.")):
+            _nms(args.pop("boxes"), args.pop("scores"), args.pop("iou_thresh"), **args)
+    g = _t(ir.iou_case("m63b65")["b"])
+    for kw, words in ((dict(b=g[:2].contiguous()), "boxes_b must have the frames"), (dict(b=g.double()), "boxes_b must have the frames"), (dict(a=c["boxes"]), "boxes_a must be a contiguous"),
+                      (dict(mode="2d"), "mode must be"), (dict(return_iou=False), "nothing to compute"), (dict(pose_a=ps[:, :3].contiguous()), "pose_a must be a contiguous"),
+                      (dict(out=IouBatch.empty(F, B, 64)), "out must be a IouBatch whose iou"), (dict(out=IouBatch.empty(F, B, 65), return_best=True), "out must be a IouBatch whose best")):
+        args = dict(a=bx, b=g)
+        args.update(kw)
+        with pytest.raises(ValueError, match=words):
+            _iou(args.pop("a"), args.pop("b"), **args)
+    # the C entries refuse on their own, at every edge of the domain
+    from lidar_snow_sim_amd import engine
+    ctx = engine.get_engine(0).ctx
+    out = NmsBatch.empty(F, B, 10, Cb, with_scores=True, with_kept=True)
+    io = IouBatch.empty(F, B, 65, with_best=True)
+
+    def call_nms(n_frames=F, n_boxes=B, feats=Cb, dtype=0, mode=0, iou_thresh=0.5, score_thresh=0.0, post_max=10, boxes=bx.data_ptr(), scores=sc.data_ptr(),
+                 index=out.index.data_ptr(), count=out.count.data_ptr(), kboxes=out.boxes.data_ptr(), kept=out.kept.data_ptr()):
+        ctx.nms_device(n_frames, n_boxes, boxes, feats, scores, dtype, mode, iou_thresh, score_thresh, post_max, ps.data_ptr(), index, count, kboxes,
+                       out.scores.data_ptr(), kept)
+
+    def call_iou(n_frames=F, n_a=B, n_b=65, fa=Cb, fb=9, dtype=0, mode=1, a=bx.data_ptr(), iou=io.iou.data_ptr(), best=io.best.data_ptr(), best_iou=io.best_iou.data_ptr()):
+        ctx.boxes_iou_device(n_frames, n_a, a, fa, n_b, g.data_ptr(), fb, dtype, mode, 0, 0, iou, best, best_iou)
+
+    who = "snowgpu_nms_device: "
+    for kw, words in ((dict(n_boxes=0), "n_boxes must lie in 1 .. 9216"), (dict(n_boxes=9217), "n_boxes must lie in 1 .. 9216"), (dict(feats=6), "box_features must lie in 7 .. 10"),
+                      (dict(feats=11), "box_features must lie in 7 .. 10"), (dict(post_max=0), "post_max must lie in 1 .. n_boxes"), (dict(post_max=B + 1), "post_max must lie in 1 .. n_boxes"),
+                      (dict(mode=2), "mode must be 0"), (dict(dtype=2), "null pointer or bad dtype"), (dict(n_frames=0), "null pointer or bad dtype"), (dict(scores=0), "null pointer or bad dtype"),
+                      (dict(index=0), "null pointer or bad dtype"), (dict(count=0), "null pointer or bad dtype"), (dict(iou_thresh=float("nan")), "a threshold is NaN"),
+                      (dict(score_thresh=float("nan")), "a threshold is NaN"), (dict(n_frames=2 ** 20, n_boxes=2048), "n_frames \\* n_boxes exceeds"),
+                      (dict(kboxes=bx.data_ptr()), "d_out_boxes overlaps d_boxes"), (dict(kept=sc.data_ptr() + 4), "d_out_kept overlaps d_scores"),
+                      (dict(kept=out.index.data_ptr()), "d_out_kept overlaps d_out_index; every output needs memory of its own")):
+        with pytest.raises(ValueError, match=who + words.replace("..", r"\.\.")):
+            call_nms(**kw)
+    who = "snowgpu_boxes_iou_device: "
+    for kw, words in ((dict(n_a=0), "the boxes per frame must lie in 1 .. 9216"), (dict(n_b=9217), "the boxes per frame must lie in 1 .. 9216"), (dict(fa=6), "box_features must lie in 7 .. 10"),
+                      (dict(fb=11), "box_features must lie in 7 .. 10"), (dict(mode=-1), "mode must be 0"), (dict(dtype=3), "null pointer or bad dtype"), (dict(a=0), "null pointer or bad dtype"),
+                      (dict(iou=0, best=0, best_iou=0), "no output"), (dict(n_frames=2 ** 15, n_a=256, n_b=256), "n_frames \\* M \\* B exceeds"),
+                      (dict(iou=g.data_ptr()), "d_out_iou overlaps d_boxes_b"), (dict(best_iou=io.best.data_ptr()), "d_out_best_iou overlaps d_out_best; every output needs memory of its own")):
+        with pytest.raises(ValueError, match=who + words.replace("..", r"\.\.")):
+            call_iou(**kw)
+    call_nms(kboxes=0, kept=0)                                         # the nullable outputs may be null
+    torch.cuda.synchronize()
+    want = ir.nms(c["boxes"], c["scores"], c["pose"], 0.5, 10, 0.0, "bev")
+    assert out.index.cpu().numpy().tobytes() == want["index"].tobytes() and out.count.cpu().numpy().tobytes() == want["count"].tobytes()

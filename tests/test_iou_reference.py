@@ -1,0 +1,320 @@
+"""No GPU: the conditions that keep the comparisons of tests/test_gpu_iou.py from being vacuous.  The NumPy restatement of rotated box IoU
+and NMS (tests/iou_reference.py) on analytic cases; against an independent method (edge intersections, contained corners, an angular sort)
+on every shared case, within the tolerance derived there, with every NMS and best decision further from its threshold and its runner-up
+than that tolerance, so that the independent method gives the same index lists; what each case must contain; csrc/sg_iou.h compiled for
+the host (tests/host_harness/iou_clip.cpp) on millions of adversarial pairs and byte for byte against the restatement; the refusals of
+both entries."""
+import math
+import shutil
+import subprocess
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+import iou_reference as ir
+
+ROOT = Path(__file__).resolve().parent.parent
+HIPCC = "/opt/rocm/bin/hipcc"
+TOL_A, TOL_I = ir.case_tol_area(), ir.case_tol_iou()
+
+
+def _box(cx, cy, dx, dy, h, cz=0.0, dz=2.0):
+    return np.array([[cx, cy, cz, dx, dy, dz, h]], np.float64)
+
+
+def _area(a, b, method=ir.clip_area):
+    return float(method(a, ir.numpy_pose(a), b, ir.numpy_pose(b))[0])
+
+
+# ---- 1. analytic cases ------------------------------------------------------------------------------------------------------------------------
+def test_the_tolerance_is_what_the_derivation_says():
+    assert 1.0e-11 < TOL_A < 1.1e-11 and TOL_I == 2 * TOL_A / 4.5 + 8 * ir.EPS and TOL_I < 5e-12
+
+
+def test_axis_aligned_overlap_is_the_product_of_interval_overlaps_exactly():
+    rng = np.random.default_rng(5)
+    n = 400
+    a = np.column_stack((rng.integers(-40, 40, n) / 4, rng.integers(-40, 40, n) / 4, np.zeros(n), rng.integers(1, 24, n) / 2, rng.integers(1, 24, n) / 2, np.ones(n), np.zeros(n)))
+    b = np.column_stack((rng.integers(-40, 40, n) / 4, rng.integers(-40, 40, n) / 4, np.zeros(n), rng.integers(1, 24, n) / 2, rng.integers(1, 24, n) / 2, np.ones(n), np.zeros(n)))
+    ox = np.maximum(np.minimum(a[:, 0] + a[:, 3] / 2, b[:, 0] + b[:, 3] / 2) - np.maximum(a[:, 0] - a[:, 3] / 2, b[:, 0] - b[:, 3] / 2), 0)
+    oy = np.maximum(np.minimum(a[:, 1] + a[:, 4] / 2, b[:, 1] + b[:, 4] / 2) - np.maximum(a[:, 1] - a[:, 4] / 2, b[:, 1] - b[:, 4] / 2), 0)
+    got = ir.clip_area(a, ir.numpy_pose(a), b, ir.numpy_pose(b))                  # (quarters and halves: every operation is exact)
+    assert np.array_equal(got, ox * oy) and (got > 0).sum() > 50 and (got == 0).sum() > 50
+
+
+def test_analytic_cases():
+    sq = _box(0, 0, 2, 2, 0)
+    for method in (ir.clip_area, ir.area_independent):
+        assert abs(_area(sq, _box(0, 0, 2, 2, math.pi / 4), method) - 8 * (math.sqrt(2) - 1)) <= TOL_A
+        assert abs(_area(_box(0, 0, 2, 2, math.pi / 4), sq, method) - 8 * (math.sqrt(2) - 1)) <= TOL_A
+        assert _area(sq, _box(5, 0, 2, 2, 0.3), method) == 0.0 and _area(sq, _box(1.5, 1.9, 1, 1, math.pi / 4), method) == 0.0       # disjoint
+        assert abs(_area(_box(0.2, -0.1, 1, 0.5, 0.7), sq, method) - 0.5) <= TOL_A and abs(_area(sq, _box(0.2, -0.1, 1, 0.5, 0.7), method) - 0.5) <= TOL_A
+        assert abs(_area(sq, sq, method) - 4.0) <= TOL_A
+        assert _area(sq, _box(2, 0, 2, 2, 0), method) <= TOL_A and _area(sq, _box(2, 2, 2, 2, 0), method) <= TOL_A                   # a shared edge, a shared corner
+        assert _area(sq, _box(1 + math.sqrt(0.5), 0, 1, 1, math.pi / 4), method) <= TOL_A                                            # a corner on an edge
+    a, b = _box(0, 0, 4, 2, 0, cz=0.0, dz=2.0), _box(1, 0, 4, 2, 0, cz=1.5, dz=2.0)
+    ok = np.ones(1, bool)
+    assert ir.pair_iou(a, ir.numpy_pose(a), ok, b, ir.numpy_pose(b), ok, "bev")[0] == 6.0 / 10.0
+    assert ir.pair_iou(a, ir.numpy_pose(a), ok, b, ir.numpy_pose(b), ok, "3d")[0] == 3.0 / 29.0                                      # h = 0.5: 3 / (16 + 16 - 3)
+    far = _box(1, 0, 4, 2, 0, cz=5.0)
+    assert ir.pair_iou(a, ir.numpy_pose(a), ok, far, ir.numpy_pose(far), ok, "3d")[0] == 0.0
+    assert ir.pair_iou(a, ir.numpy_pose(a), ok, far, ir.numpy_pose(far), ~ok, "bev")[0] == 0.0                                       # an absent box
+
+
+def test_the_loop_and_the_vectors_agree():
+    rng = np.random.default_rng(6)
+    n = 600
+    a = ir.clustered(rng, n, 40)[:, :7]
+    b = a.copy()
+    b[:, :2] += rng.normal(0, 1.5, (n, 2))
+    b[:, 6] += rng.normal(0, 0.5, n)
+    b[:60] = a[:60]
+    b[60:120, 6] = np.nextafter(a[60:120, 6], 9.0)
+    b[120:180, 6] += math.pi / 2
+    pa, pb = ir.numpy_pose(a), ir.numpy_pose(b)
+    vec, most = ir.clip_area(a, pa, b, pb, return_most=True)
+    assert vec.tobytes() == np.array([ir.area_scalar(a[i], pa[i], b[i], pb[i]) for i in range(n)]).tobytes() and (vec > 0).sum() > 200
+    assert 8 <= most.max() <= 19                                      # (equal boxes: more vertices than geometry has, fewer than the slots)
+    ind = ir.area_independent(a, pa, b, pb)
+    assert np.abs(ind - np.array([ir.area_independent_one(a[i], pa[i], b[i], pb[i]) for i in range(n)])).max() <= TOL_A
+    assert np.abs(ind - vec).max() <= TOL_A
+
+
+# ---- 2. the shared cases: the independent method, the margins, the content -------------------------------------------------------------------
+def _frame_trace(c, f):
+    trace = []
+    kept = ir.nms_frame(c["boxes"][f], c["scores"][f], c["pose"][f], c["iou_thresh"], c["post_max"], c["score_thresh"], c["mode"], trace=trace)
+    return kept, trace
+
+
+def _find_chain(c, f, limit=256):
+    """(A, B, C): A kept and suppresses B; B alone would suppress the later C; C is kept.  Among the first `limit` ranked candidates."""
+    boxes, pose, th = c["boxes"][f], c["pose"][f], c["iou_thresh"]
+    order = ir.ranking(boxes, c["scores"][f], pose, c["score_thresh"])[:limit]
+    kept = set(ir.nms_frame(boxes, c["scores"][f], pose, th, c["post_max"], c["score_thresh"], c["mode"]).tolist())
+    b, n = boxes[:, :7].astype(np.float64), len(order)
+    jj, ii = np.tril_indices(n, -1)
+    ok = np.ones(len(jj), bool)
+    v = np.zeros((n, n))
+    v[jj, ii] = ir.pair_iou(b[order[jj]], pose[order[jj]], ok, b[order[ii]], pose[order[ii]], ok, c["mode"])
+    for rb in range(n):
+        if order[rb] in kept:
+            continue
+        sup = [ra for ra in range(rb) if order[ra] in kept and v[rb, ra] > th]
+        later = [rc for rc in range(rb + 1, n) if order[rc] in kept and v[rc, rb] > th]
+        if sup and later:
+            return int(order[sup[0]]), int(order[rb]), int(order[later[0]])
+    return None
+
+
+@pytest.mark.parametrize("dtype", ir.DTYPES)
+@pytest.mark.parametrize("name", ir.NMS_CASES)
+def test_nms_cases(name, dtype):
+    c, e = ir.nms_case(name, dtype), ir.nms_expected(name, dtype)
+    other = ir.nms(c["boxes"], c["scores"], c["pose"], c["iou_thresh"], c["post_max"], c["score_thresh"], c["mode"], area=ir.area_independent)
+    for k in e:
+        assert e[k].tobytes() == other[k].tobytes(), (name, dtype, k)          # the same lists by the independent method, nothing left out
+    b = c["boxes"][..., :7].astype(np.float64)
+    pres = ir.present(c["boxes"], c["pose"])
+    assert np.abs(b[pres][:, :2]).max() <= 50 and (b[pres][:, 3] <= 6).all() and (b[pres][:, 4] <= 3).all() and (b[pres][:, 3] * b[pres][:, 4]).min() >= ir.CASE_AMIN
+    for f in range(len(b)):
+        kept, trace = _frame_trace(c, f)
+        assert np.array_equal(kept, e["index"][f, :e["count"][f]])
+        decided = np.concatenate(trace) if trace else np.zeros(0)
+        if decided.size:                                                       # every decision keeps its distance from the threshold
+            assert np.abs(decided - c["iou_thresh"]).min() > TOL_I, (name, dtype, f)
+        cand = len(ir.ranking(c["boxes"][f], c["scores"][f], c["pose"][f], c["score_thresh"]))
+        if cand >= 60:
+            assert 1 < len(kept) < cand and _find_chain(c, f) is not None, (name, dtype, f, len(kept), cand)
+    assert (e["kept"].sum(axis=1) == e["count"]).all() and (e["index"] >= 0).sum() == e["count"].sum()
+
+
+@pytest.mark.parametrize("dtype", ir.DTYPES)
+@pytest.mark.parametrize("name", ir.NMS_CASES)
+def test_the_blocked_walk_equals_the_plain_walk(name, dtype):
+    """nms_frame() walks the ranking in blocks, as the device's sweep does; here it is held to the definition's own walk, one candidate
+    at a time, on every case and frame -- a mistake in the block logic that both shared would show here."""
+    c, e = ir.nms_case(name, dtype), ir.nms_expected(name, dtype)
+    for f in range(len(c["boxes"])):
+        plain = ir.nms_frame_plain(c["boxes"][f], c["scores"][f], c["pose"][f], c["iou_thresh"], c["post_max"], c["score_thresh"], c["mode"])
+        assert np.array_equal(plain, e["index"][f, :e["count"][f]]), (name, dtype, f)
+    if name == "b129":                                                         # and where post_max cuts inside a block, and at 1
+        for post_max in (1, 5, 70):
+            want = ir.nms(c["boxes"], c["scores"], c["pose"], c["iou_thresh"], post_max)
+            plain = ir.nms_frame_plain(c["boxes"][0], c["scores"][0], c["pose"][0], c["iou_thresh"], post_max)
+            assert np.array_equal(plain, want["index"][0, :want["count"][0]])
+
+
+def test_what_the_nms_cases_contain():
+    natural = {n: ir.nms(*(ir.nms_case(n)[k] for k in ("boxes", "scores", "pose", "iou_thresh")), ir.nms_case(n)["boxes"].shape[1])["count"] for n in ("b64", "mixed")}
+    assert natural["b64"][0] > ir.nms_case("b64")["post_max"] == ir.nms_expected("b64")["count"][0]           # post_max cuts here
+    assert (ir.nms_expected("mixed")["count"] < ir.nms_case("mixed")["post_max"]).all()                        # and not here
+    assert ir.nms_expected("b1")["index"].tolist() == [[0]] and ir.nms_expected("b2")["index"].tolist() == [[int(np.argmax(ir.nms_case("b2")["scores"][0])), -1]]
+    e = ir.nms_expected("chain")                                               # A suppresses B; B alone would suppress C; C and the loner are kept
+    assert e["index"].tolist() == [[0, 2, 3, -1]] and _find_chain(ir.nms_case("chain"), 0) == (0, 1, 2)
+    for dtype in ir.DTYPES:
+        c, e = ir.nms_case("mixed", dtype), ir.nms_expected("mixed", dtype)
+        s, pres = c["scores"], ir.present(c["boxes"], c["pose"])
+        assert np.isnan(s[0, 40]) and not e["kept"][0, 40] and np.isinf(s[0, 41]) and e["index"][0, 0] == 41
+        assert not pres[1].any() and e["count"][1] == 0 and (e["index"][1] == -1).all() and not e["boxes"][1].any()
+        assert not pres[0, 5] and not pres[0, 6] and not e["kept"][0, [5, 6]].any()
+        assert ((s[0] < ir.SCORE_CUT) & pres[0]).sum() >= 3 and not e["kept"][0][s[0] < ir.SCORE_CUT].any()
+        assert np.signbit(s[0, 30]) and s[0, 30] == s[0, 31] and len(set(s[2, :60].tolist())) <= 11
+        order = ir.ranking(c["boxes"][0], s[0], c["pose"][0], c["score_thresh"])
+        at = [int(np.flatnonzero(order == k)[0]) for k in (20, 21, 22, 23)]
+        assert at == list(range(at[0], at[0] + 4))                             # equal scores: ascending box numbers
+        assert e["kept"][0, 8] + e["kept"][0, 9] <= 1                          # of two equal boxes at most one stays
+    big = ir.nms_expected("b4160")
+    assert big["count"][0] > 64 and ir.nms_expected("b9216")["count"][0] > 20
+
+
+@pytest.mark.parametrize("dtype", ir.DTYPES)
+@pytest.mark.parametrize("mode", ir.MODES)
+@pytest.mark.parametrize("name", ir.IOU_CASES)
+def test_iou_cases(name, mode, dtype):
+    c, e = ir.iou_case(name, dtype), ir.iou_expected(name, dtype, mode)
+    other = ir.boxes_iou(c["a"], c["b"], c["pose_a"], c["pose_b"], mode, area=ir.area_independent)
+    assert np.abs(other["iou64"] - e["iou64"]).max() <= TOL_I
+    assert np.array_equal(other["best"], e["best"]), (name, mode, dtype)       # the same partners by the independent method, no row left out
+    v = e["iou64"]
+    bb = c["b"][..., :7]
+    for f in range(3):
+        for m in range(v.shape[1]):
+            k = e["best"][f, m]
+            if k < 0:
+                assert not v[f, m].any() and not other["iou64"][f, m].any()
+                continue
+            rivals = ~(bb[f] == bb[f, k]).all(axis=1)                          # (an equal box gives an equal value by either method: the smallest number wins)
+            assert v[f, m, k] > TOL_I and (not rivals.any() or v[f, m, k] - v[f, m, rivals].max() > TOL_I), (name, mode, dtype, f, m)
+    pa, pb = ir.present(c["a"], c["pose_a"]), ir.present(c["b"], c["pose_b"])
+    assert pb[0].all() and not pb[2].any() and not e["iou64"][2].any() and (e["best"][2] == -1).all()
+    if v.shape[2] >= 2:
+        assert 0 < pb[1].sum() < pb[0].sum() and e["best"][0, 1] == 0 and v[0, 1, 0] == v[0, 1, 1] > 0.5          # the tie: the smallest number
+    if v.shape[1] >= 63:
+        assert not pa[1].all() and (e["best"] >= 0).sum() > 20
+        bev = ir.iou_expected(name, dtype, "bev")["iou64"]
+        assert ((bev > 0) & (ir.iou_expected(name, dtype, "3d")["iou64"] == 0)).sum() >= 3                         # apart in z only
+
+
+# ---- 3. csrc/sg_iou.h on the host -------------------------------------------------------------------------------------------------------------
+def _compile(tmp, name, extra=()):
+    if not Path(HIPCC).exists():
+        pytest.skip("hipcc not available")
+    exe = tmp / name
+    cmd = [HIPCC, "--cuda-host-only", "-x", "hip", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-w", *extra,
+           "-I", str(ROOT / "lidar_snow_sim_amd" / "csrc"), "-I", str(ROOT / "include"), str(ROOT / "tests" / "host_harness" / "iou_clip.cpp"),
+           "-o", str(exe), "-lm"]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    return exe
+
+
+@pytest.fixture(scope="module")
+def harness(tmp_path_factory):
+    return _compile(tmp_path_factory.mktemp("iou"), "iou_clip")
+
+
+def _fixed_pairs():
+    """A fixed few thousand pairs (a, pose a, b, pose b): clustered, equal, 1 ulp apart, right angles, shared faces, absent ones, and one
+    under a pose that is not NumPy's."""
+    rng = np.random.default_rng(7)
+    n = 4000
+    a = ir.clustered(rng, n, 250)[:, :7]
+    b = a.copy()
+    b[:, :2] += rng.normal(0, 1.5, (n, 2))
+    b[:, 6] += rng.normal(0, 0.5, n)
+    b[:200] = a[:200]
+    b[200:400, 6] = np.nextafter(a[200:400, 6], 9.0)
+    a[400:600, 6] = np.round(a[400:600, 6] / (math.pi / 2)) * (math.pi / 2)
+    b[400:600] = a[400:600]
+    b[400:600, 6] += math.pi / 2
+    b[600:800] = a[600:800]
+    b[600:800, 0] += a[600:800, 3] * np.cos(a[600:800, 6])
+    b[600:800, 1] += a[600:800, 3] * np.sin(a[600:800, 6])
+    a[800:820] = 0.0
+    b[820:840, 3] = -1.0
+    a[840:860, 0] = np.nan
+    pa, pb = ir.numpy_pose(a), ir.numpy_pose(b)
+    pa[860:880] = 2.0, 0.0                                            # not a rotation: absent
+    pb[880:900] *= 1.0 + 4e-7                                         # within the pose tolerance: used as it is
+    return a, pa, b, pb
+
+
+def test_host_clip_equals_the_restatement_byte_for_byte(harness, tmp_path):
+    a, pa, b, pb = _fixed_pairs()
+    n = len(a)
+    np.ascontiguousarray(np.concatenate((a, pa, b, pb), axis=1)).tofile(tmp_path / "in")
+    r = subprocess.run([str(harness), "areas", str(n), str(tmp_path / "in"), str(tmp_path / "out")], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    got = np.fromfile(tmp_path / "out", np.float64).reshape(n, 3)
+    oka, okb = ir.present(a, pa), ir.present(b, pb)
+    assert (~oka).sum() == 60 and (~okb).sum() == 20 and okb[880:900].all()
+    both = oka & okb
+    area = np.zeros(n)
+    area[both] = ir.clip_area(a[both], pa[both], b[both], pb[both])
+    assert got[:, 0].tobytes() == area.tobytes() and (area > 0).sum() > 1500 and (area == 0).sum() > 500
+    for k, mode in ((1, "bev"), (2, "3d")):
+        assert got[:, k].tobytes() == ir.pair_iou(a, pa, oka, b, pb, okb, mode).tobytes(), mode
+    assert not got[~both].any()
+
+
+def test_millions_of_adversarial_pairs(harness):
+    r = subprocess.run([str(harness), "stress", "1", "4000000"], capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    word, pairs, most, excess, asym = r.stdout.split()
+    print("clip on the host:", r.stdout.strip())
+    assert word == "stress" and int(pairs) >= 3_900_000 and 8 < int(most) <= 19 and float(excess) <= 1.0 and float(asym) <= 1.0
+
+
+def test_harness_under_sanitizers(tmp_path):
+    """The same program under AddressSanitizer and UBSan: host code only, a stand-alone program."""
+    exe = _compile(tmp_path, "iou_clip_san", ("-Xarch_host", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"))
+    r = subprocess.run([str(exe), "stress", "2", "200000"], capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0 and r.stdout.split()[0] == "stress" and not r.stderr.strip(), r.stdout[-2000:] + r.stderr[-2000:]
+
+
+# ---- 4. the refusals, the declarations ------------------------------------------------------------------------------------------------------
+IOU, NMS = "snowgpu_boxes_iou_device", "snowgpu_nms_device"
+FEATS = ": box_features must lie in 7 .. 10: cx, cy, cz, dx, dy, dz, heading first"
+REFUSALS = {
+    "iou_clean": "0|OK", "iou_best_only": "0|OK", "iou_m_9216": "0|OK", "iou_same_set": "0|OK", "iou_slots_2p31_minus_1": "0|OK",
+    "iou_null_a": f"1|{IOU}: null pointer or bad dtype", "iou_dtype_2": f"1|{IOU}: null pointer or bad dtype", "iou_no_frames": f"1|{IOU}: null pointer or bad dtype",
+    "iou_mode_2": f"1|{IOU}: mode must be 0 (BEV) or 1 (3D)", "iou_no_output": f"1|{IOU}: no output: pass d_out_iou, d_out_best or d_out_best_iou",
+    "iou_m_0": f"1|{IOU}: the boxes per frame must lie in 1 .. 9216 on either side", "iou_b_9217": f"1|{IOU}: the boxes per frame must lie in 1 .. 9216 on either side",
+    "iou_feats_6": f"1|{IOU}{FEATS}", "iou_feats_11": f"1|{IOU}{FEATS}", "iou_slots_2p31": f"1|{IOU}: n_frames * M * B exceeds 2^31 - 1; split the batch",
+    "iou_out_is_boxes_b": f"1|{IOU}: d_out_iou overlaps d_boxes_b; the boxes and poses are read while the overlaps are written: pass a buffer apart from them",
+    "iou_best_is_iou": f"1|{IOU}: d_out_best overlaps d_out_iou; every output needs memory of its own",
+    "nms_clean": "0|OK", "nms_bare": "0|OK", "nms_b_9216": "0|OK", "nms_post_max_b": "0|OK", "nms_minus_inf": "0|OK",
+    "nms_null_scores": f"1|{NMS}: null pointer or bad dtype", "nms_null_index": f"1|{NMS}: null pointer or bad dtype", "nms_null_count": f"1|{NMS}: null pointer or bad dtype",
+    "nms_mode_m1": f"1|{NMS}: mode must be 0 (BEV) or 1 (3D)", "nms_b_0": f"1|{NMS}: n_boxes must lie in 1 .. 9216", "nms_b_9217": f"1|{NMS}: n_boxes must lie in 1 .. 9216",
+    "nms_feats_6": f"1|{NMS}{FEATS}", "nms_feats_11": f"1|{NMS}{FEATS}", "nms_post_max_0": f"1|{NMS}: post_max must lie in 1 .. n_boxes",
+    "nms_post_max_b_plus_1": f"1|{NMS}: post_max must lie in 1 .. n_boxes", "nms_nan_iou_thresh": f"1|{NMS}: a threshold is NaN", "nms_nan_score_thresh": f"1|{NMS}: a threshold is NaN",
+    "nms_slots_2p31": f"1|{NMS}: n_frames * n_boxes exceeds 2^31 - 1; split the batch",
+    "nms_boxes_out_is_boxes": f"1|{NMS}: d_out_boxes overlaps d_boxes; the boxes, scores and pose are read while the keep list is written: pass a buffer apart from them",
+    "nms_kept_overlaps_index": f"1|{NMS}: d_out_kept overlaps d_out_index; every output needs memory of its own",
+}
+
+
+def test_refusal_walk(tmp_path):
+    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++") or HIPCC
+    exe = tmp_path / "iou_refusals"
+    cmd = [cxx, "-x", "c++", "-std=c++17", "-O1", "-Wall", "-I", str(ROOT / "lidar_snow_sim_amd" / "csrc"),
+           str(ROOT / "tests" / "host_harness" / "iou_refusals.cpp"), "-o", str(exe)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr
+    assert dict(ln.split("|", 1) for ln in r.stdout.splitlines()) == REFUSALS
+
+
+def test_the_entries_are_declared_and_bound():
+    from lidar_snow_sim_amd import _native
+    header = (ROOT / "include" / "snowgpu.h").read_text()
+    for name in (IOU, NMS):
+        assert f"int {name}(" in header and name in _native.EXPORTS and hasattr(_native.lib(), name)
+    assert hasattr(_native.Context, "boxes_iou_device") and hasattr(_native.Context, "nms_device")
+    assert "snowgpu_iou.hip" in __import__("lidar_snow_sim_amd.build", fromlist=["SOURCES"]).SOURCES
+    from lidar_snow_sim_amd import iou, tensors
+    assert callable(tensors.boxes_iou) and callable(tensors.nms) and callable(tensors.IouBatch.empty) and callable(tensors.NmsBatch.empty)
+    assert callable(iou.boxes_iou_bev) and callable(iou.boxes_iou3d) and callable(iou.nms)
