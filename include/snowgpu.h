@@ -173,6 +173,20 @@ int snowgpu_lane_stream(snowgpu_ctx *ctx, int level, void **stream);
  * [0, 2 pi] (:351-352) and the two tangent angles ordered (right, left) (geometry.py:138-190, :32-80).  out: K x 4 doubles. */
 int snowgpu_debug_table(snowgpu_ctx *ctx, int table_id, double *out, int64_t cap_rows);
 
+/* Debug tap: the WHOLE filed table as the scan reads it, copied to host buffers (plain copies on the context's stream, no kernel):
+ *   bin_start  SG_NBINS + 1 = 2049 words: bin b holds records bin_start[b] .. bin_start[b + 1]
+ *   entries    n_entries + 1 records of 64 bytes (SgEntry: phi, x, y, r, t0, t1, rho as float64, then flags and src as uint32), the bins
+ *              concatenated, each ordered by (rho, src); the last one is the spare record behind the last bin
+ *   bin_q      2048 x 16 words, bin-major: records of the bin nearer than 8 k metres
+ *   bin_qs     qs_steps x 2049 words, step-major, two 16-bit counts to a word, word 2048 of a row bin 0 again; a table whose longest bin
+ *              exceeds 65 535 records has none (nothing is written, info[4] = 0)
+ *   info       int64[5]: n_flakes, n_entries, max_bin, qs_steps, 1 if the table has a bin_qs else 0;  *qs_per_m: steps per metre of bin_qs
+ * The capacities count words (records for entries).  info and *qs_per_m are written BEFORE the capacities are checked: a caller that
+ * does not know the sizes calls once with capacities of 0 (SNOWGPU_E_INVALID, "buffer too small"), reads info and calls again.  An unknown
+ * table id, a null pointer and a buffer that is too small return SNOWGPU_E_INVALID. */
+int snowgpu_debug_table_bins(snowgpu_ctx *ctx, int table_id, uint32_t *bin_start, int64_t cap_start, void *entries, int64_t cap_entries,
+                             uint32_t *bin_q, int64_t cap_q, uint32_t *bin_qs, int64_t cap_qs, int64_t *info, double *qs_per_m);
+
 /* Status words (int32[8], layout under snowgpu_augment_batch_device) of the last batch that went through a host-pointer
  * entry of this context: e.g. out8[2..5] = beams each later list capacity took (summed over the chunks of a pipelined batch). */
 int snowgpu_last_status(snowgpu_ctx *ctx, int32_t *out8);

@@ -24,7 +24,7 @@ EXPORTS = [
     "snowgpu_augment_batch_device", "snowgpu_debug_occlusions", "snowgpu_wet_ground_batch",
     "snowgpu_profile_begin", "snowgpu_profile_end", "snowgpu_set_exact_math", "snowgpu_augment_wet_batch",
     "snowgpu_sample_table", "snowgpu_host_alloc", "snowgpu_host_free", "snowgpu_set_fov",
-    "snowgpu_augment_wet_batch_device", "snowgpu_last_status", "snowgpu_free_table", "snowgpu_debug_table", "snowgpu_file_table_device", "snowgpu_set_fov_precrop",
+    "snowgpu_augment_wet_batch_device", "snowgpu_last_status", "snowgpu_free_table", "snowgpu_debug_table", "snowgpu_debug_table_bins", "snowgpu_file_table_device", "snowgpu_set_fov_precrop",
     "snowgpu_set_pipeline", "snowgpu_set_wet_lines", "snowgpu_set_plane_method", "snowgpu_estimate_planes",
     "snowgpu_estimate_planes_device", "snowgpu_prepass_stats", "snowgpu_set_wet_estimation", "snowgpu_wet_last_fit", "snowgpu_debug_ransac_polyfit", "snowgpu_set_result_transfer", "snowgpu_debug_transfer_times", "snowgpu_status_error", "snowgpu_set_threshold_callback", "snowgpu_augment_batch_compact", "snowgpu_set_serial", "snowgpu_lane_stream", "snowgpu_device_numa_node",
     "snowgpu_augment_batch_device_aligned", "snowgpu_wet_ground_batch_device_aligned", "snowgpu_augment_wet_batch_device_aligned",
@@ -93,6 +93,8 @@ def lib():
             L.snowgpu_file_table_device.argtypes = [vp, ctypes.c_int, vp, i64]
             L.snowgpu_debug_table.restype = ctypes.c_int
             L.snowgpu_debug_table.argtypes = [vp, ctypes.c_int, vp, i64]
+            L.snowgpu_debug_table_bins.restype = ctypes.c_int
+            L.snowgpu_debug_table_bins.argtypes = [vp, ctypes.c_int, vp, i64, vp, i64, vp, i64, vp, i64, vp, vp]
             L.snowgpu_free_table.restype = ctypes.c_int
             L.snowgpu_free_table.argtypes = [vp, ctypes.c_int]
             L.snowgpu_table_count.restype = ctypes.c_int
@@ -791,6 +793,31 @@ class Context:
         with self._call_lock:
             self._check(self._L.snowgpu_debug_table(self._h, int(table_id), _p(out), int(n_flakes)))
         return out
+
+    ENTRY_DTYPE = np.dtype([("phi", "f8"), ("x", "f8"), ("y", "f8"), ("r", "f8"), ("t0", "f8"), ("t1", "f8"), ("rho", "f8"),
+                            ("flags", "u4"), ("src", "u4")])        # SgEntry (csrc/sg_common.h), 64 bytes
+
+    def debug_table_bins(self, table_id):
+        """The whole filed table as the scan reads it (snowgpu_debug_table_bins): dict of bin_start (2049 uint32), entries (n_entries + 1
+        records of ENTRY_DTYPE, the last one the spare record), bin_q (2048 x 16 uint32), bin_qs (qs_steps x 2049 uint32, or None for a
+        table without one), n_flakes, n_entries, max_bin, qs_steps, qs_per_m."""
+        info, per_m = np.full(5, -1, np.int64), np.zeros(1, np.float64)
+        n_bins, q_steps = 2048, 16                                  # SG_NBINS, SG_QSTEPS
+        start, q = np.zeros(n_bins + 1, np.uint32), np.zeros((n_bins, q_steps), np.uint32)
+        ent, qs = np.zeros(1, self.ENTRY_DTYPE), np.zeros(1, np.uint32)
+        with self._call_lock:
+            # sizes first: the entry writes info before it checks the capacities
+            rc = self._L.snowgpu_debug_table_bins(self._h, int(table_id), _p(start), 0, _p(ent), 0, _p(q), 0, _p(qs), 0, _p(info), _p(per_m))
+            if rc != E_INVALID or info[1] < 0:
+                self._check(rc)
+                raise SnowGPUError(E_INVALID, "snowgpu_debug_table_bins accepted buffers of no capacity")
+            n_entries, qs_steps, has_qs = int(info[1]), int(info[3]), bool(info[4])
+            ent = np.zeros(n_entries + 1, self.ENTRY_DTYPE)
+            qs = np.zeros((qs_steps, n_bins + 1) if has_qs else (1, 1), np.uint32)
+            self._check(self._L.snowgpu_debug_table_bins(self._h, int(table_id), _p(start), start.size, _p(ent), ent.size, _p(q), q.size,
+                                                         _p(qs), qs.size if has_qs else 0, _p(info), _p(per_m)))
+        return dict(bin_start=start, entries=ent, bin_q=q, bin_qs=qs if has_qs else None, n_flakes=int(info[0]), n_entries=int(info[1]),
+                    max_bin=int(info[2]), qs_steps=int(info[3]), qs_per_m=float(per_m[0]))
 
     def last_status(self):
         """int32[8] status words of the last host-entry batch ([2..5]: beams per later capacity tier)."""

@@ -309,6 +309,32 @@ extern "C" int snowgpu_debug_table(snowgpu_ctx *ctx, int table_id, double *out, 
     return SNOWGPU_OK;
 }
 
+// Debug tap: the whole filed table -- bin offsets, every record of every bin and the spare one, both range indexes, and the descriptor's
+// counts (include/snowgpu.h).  Copies only: what the scan would read is what comes back.
+extern "C" int snowgpu_debug_table_bins(snowgpu_ctx *ctx, int table_id, uint32_t *bin_start, int64_t cap_start, void *entries, int64_t cap_entries,
+                                        uint32_t *bin_q, int64_t cap_q, uint32_t *bin_qs, int64_t cap_qs, int64_t *info, double *qs_per_m)
+{
+    if (!ctx || !bin_start || !entries || !bin_q || !bin_qs || !info || !qs_per_m) return SNOWGPU_E_INVALID;
+    if (table_id < 0 || (size_t)table_id >= ctx->tables.size() || !ctx->tables[(size_t)table_id].entries)
+        return fail(ctx, SNOWGPU_E_INVALID, "snowgpu_debug_table_bins: unknown table id");
+    const DeviceTable &dt = ctx->tables[(size_t)table_id];
+    const size_t n_start = (size_t)SG_NBINS + 1, n_rec = (size_t)dt.desc.n_entries + 1, n_q = (size_t)SG_NBINS * SG_QSTEPS;
+    const size_t n_qs = dt.bin_qs ? SG_QS_WORDS_OF(dt.desc.qs_steps, SG_NBINS) : 0;
+    info[0] = dt.desc.n_flakes; info[1] = dt.desc.n_entries; info[2] = dt.desc.max_bin; info[3] = dt.desc.qs_steps; info[4] = dt.bin_qs ? 1 : 0;
+    *qs_per_m = (double)dt.desc.qs_per_m;
+    if (cap_start < (int64_t)n_start || cap_entries < (int64_t)n_rec || cap_q < (int64_t)n_q || cap_qs < (int64_t)n_qs)
+        return fail(ctx, SNOWGPU_E_INVALID, "snowgpu_debug_table_bins: buffer too small (see info)");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    int e = (int)hipMemcpyAsync(bin_start, dt.bin_start, sizeof(uint32_t) * n_start, hipMemcpyDeviceToHost, ctx->stream);
+    if (!e) e = (int)hipMemcpyAsync(entries, dt.entries, sizeof(SgEntry) * n_rec, hipMemcpyDeviceToHost, ctx->stream);
+    if (!e) e = (int)hipMemcpyAsync(bin_q, dt.bin_q, sizeof(uint32_t) * n_q, hipMemcpyDeviceToHost, ctx->stream);
+    if (!e && n_qs) e = (int)hipMemcpyAsync(bin_qs, dt.bin_qs, sizeof(uint32_t) * n_qs, hipMemcpyDeviceToHost, ctx->stream);
+    const int es = (int)hipStreamSynchronize(ctx->stream);       // also after a failed copy: nothing may still write the caller's buffers
+    if (!e) e = es;
+    if (e) return fail(ctx, SNOWGPU_E_HIP, std::string("table bins: ") + hipGetErrorString((hipError_t)e));
+    return SNOWGPU_OK;
+}
+
 extern "C" int snowgpu_upload_table(snowgpu_ctx *ctx, int table_id, const double *xyr, int64_t k)
 {
     if (!ctx) return SNOWGPU_E_INVALID;

@@ -98,7 +98,8 @@ def test_filed_per_flake_quantities_match_the_reference_geometry(golden):
     :32-80) -- read back through the debug tap against the reference's own L1 outputs: bit for bit when the table is filed on
     the host (snowgpu_upload_table, glibc libm); when it is filed by the device kernels, whose atan2 / atan are rounded correctly
     (csrc/sg_atan_cr.h) where glibc's are off by up to 0.506 ULP, all but a few values in a thousand are identical and the rest
-    differ by one ULP."""
+    differ by one ULP.  (The bin structure itself -- every copy of every flake, the order inside the bins, the range indexes -- is
+    compared whole and exactly in tests/test_gpu_table_filing.py; the sweep below stays as the end-to-end check.)"""
     import torch
     from lidar_snow_sim_amd import engine
     d = golden("L1_geometry")

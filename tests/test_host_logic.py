@@ -47,6 +47,8 @@ def test_null_and_bad_arguments_return_status_codes():
     assert lib.snowgpu_range_grid(None) == _native.E_INVALID
     assert lib.snowgpu_set_lasers(None, 0, None, None, None, None) == _native.E_INVALID
     assert lib.snowgpu_upload_table(None, 0, None, 0) == _native.E_INVALID
+    assert lib.snowgpu_debug_table(None, 0, None, 0) == _native.E_INVALID
+    assert lib.snowgpu_debug_table_bins(None, 0, None, 0, None, 0, None, 0, None, 0, None, None) == _native.E_INVALID
     assert lib.snowgpu_last_error(None) == b"null context"
 
 
