@@ -236,6 +236,21 @@ def _dtype_code(dt):
     raise TypeError(f"rows must be float32 or float64, not {dt}")
 
 
+def _i32(v):
+    """int(v) clamped to int32: a count beyond it reaches the entry as one it refuses, not as a ctypes error."""
+    return max(-(2 ** 31), min(int(v), 2 ** 31 - 1))
+
+
+def _range6(who, rng):
+    """point_cloud_range as 6 contiguous float64, None for None."""
+    if rng is None:
+        return None
+    rng = np.ascontiguousarray(rng, np.float64).reshape(-1)
+    if rng.shape != (6,):
+        raise ValueError(f"{who}: point_cloud_range holds 6 numbers (x0, y0, z0, x1, y1, z1)")
+    return rng
+
+
 def range_grid():
     out = np.zeros(1230)
     rc = lib().snowgpu_range_grid(_p(out))
@@ -276,6 +291,12 @@ class Context:
     def _check(self, rc):
         if rc:
             raise SnowGPUError(rc, self._L.snowgpu_last_error(self._h).decode())
+
+    def _check_args(self, rc):
+        """_check() for the stage entries: an argument outside the domain (E_INVALID) raises ValueError with the entry's words."""
+        if rc == E_INVALID:
+            raise ValueError(self._L.snowgpu_last_error(self._h).decode())
+        self._check(rc)
 
     @property
     def handle(self):
@@ -539,9 +560,7 @@ class Context:
         rc = self._L.snowgpu_dror_mask_device(self._h, int(n_frames), int(n_total), int(max_frame_rows), vp(d_frame_off or None), vp(d_rows or None),
                                               int(dtype_code), float(alpha), float(beta), float(sr_min), max(-1, min(k, 1 << 62)), vp(d_keep_in or None),
                                               vp(d_out_keep or None), vp(d_out_neighbours or None), vp(stream or None))
-        if rc == E_INVALID:
-            raise ValueError(self._L.snowgpu_last_error(self._h).decode())
-        self._check(rc)
+        self._check_args(rc)
 
     def voxelize_device(self, n_frames, n_total, max_frame_rows, d_frame_off, d_rows, dtype_code, point_cloud_range, voxel_size, max_points,
                         max_voxels, n_features, d_keep_in, d_out_voxels, d_out_coords, d_out_num_points, d_out_voxel_offsets, d_out_voxel_of=0,
@@ -553,14 +572,11 @@ class Context:
         size = np.ascontiguousarray(voxel_size, np.float64).reshape(-1)
         if rng.shape != (6,) or size.shape != (3,):
             raise ValueError("snowgpu_voxelize_device: point_cloud_range holds 6 numbers (x0, y0, z0, x1, y1, z1), voxel_size 3")
-        i32 = lambda v: max(-(2 ** 31), min(int(v), 2 ** 31 - 1))
         rc = self._L.snowgpu_voxelize_device(self._h, int(n_frames), int(n_total), int(max_frame_rows), vp(d_frame_off or None), vp(d_rows or None),
-                                             int(dtype_code), _p(rng), _p(size), i32(max_points), i32(max_voxels), i32(n_features), vp(d_keep_in or None),
+                                             int(dtype_code), _p(rng), _p(size), _i32(max_points), _i32(max_voxels), _i32(n_features), vp(d_keep_in or None),
                                              vp(d_out_voxels or None), vp(d_out_coords or None), vp(d_out_num_points or None),
                                              vp(d_out_voxel_offsets or None), vp(d_out_voxel_of or None), vp(stream or None))
-        if rc == E_INVALID:
-            raise ValueError(self._L.snowgpu_last_error(self._h).decode())
-        self._check(rc)
+        self._check_args(rc)
 
     def fps_device(self, n_frames, n_total, max_frame_rows, d_frame_off, d_rows, dtype_code, point_cloud_range, n_samples, n_features, d_keep_in,
                    d_out_index, d_out_points, d_out_dist, d_out_usable, stream=0):
@@ -568,19 +584,12 @@ class Context:
         point_cloud_range: 6 numbers or None.  An argument outside the domain, or an output overlapping the mask or the rows, raises
         ValueError with the entry's words."""
         vp = ctypes.c_void_p
-        rng = None
-        if point_cloud_range is not None:
-            rng = np.ascontiguousarray(point_cloud_range, np.float64).reshape(-1)
-            if rng.shape != (6,):
-                raise ValueError("snowgpu_fps_device: point_cloud_range holds 6 numbers (x0, y0, z0, x1, y1, z1)")
-        i32 = lambda v: max(-(2 ** 31), min(int(v), 2 ** 31 - 1))
+        rng = _range6("snowgpu_fps_device", point_cloud_range)
         rc = self._L.snowgpu_fps_device(self._h, int(n_frames), int(n_total), int(max_frame_rows), vp(d_frame_off or None), vp(d_rows or None),
-                                        int(dtype_code), None if rng is None else _p(rng), i32(n_samples), i32(n_features), vp(d_keep_in or None),
+                                        int(dtype_code), _p(rng), _i32(n_samples), _i32(n_features), vp(d_keep_in or None),
                                         vp(d_out_index or None), vp(d_out_points or None), vp(d_out_dist or None), vp(d_out_usable or None),
                                         vp(stream or None))
-        if rc == E_INVALID:
-            raise ValueError(self._L.snowgpu_last_error(self._h).decode())
-        self._check(rc)
+        self._check_args(rc)
 
     def fps_sectors_device(self, n_frames, n_total, max_frame_rows, d_frame_off, d_rows, dtype_code, point_cloud_range, n_samples, n_features, d_keep_in,
                            n_sectors, d_rois, n_rois, roi_features, roi_margin, d_out_index, d_out_points, d_out_dist, d_out_usable, d_out_sector_offsets,
@@ -589,21 +598,14 @@ class Context:
         `stream`.  point_cloud_range: 6 numbers or None; d_rois 0: no roi test.  An argument outside the domain, or an output overlapping
         the mask, the rows, the rois or another output, raises ValueError with the entry's words."""
         vp = ctypes.c_void_p
-        rng = None
-        if point_cloud_range is not None:
-            rng = np.ascontiguousarray(point_cloud_range, np.float64).reshape(-1)
-            if rng.shape != (6,):
-                raise ValueError("snowgpu_fps_sectors_device: point_cloud_range holds 6 numbers (x0, y0, z0, x1, y1, z1)")
-        i32 = lambda v: max(-(2 ** 31), min(int(v), 2 ** 31 - 1))
+        rng = _range6("snowgpu_fps_sectors_device", point_cloud_range)
         rc = self._L.snowgpu_fps_sectors_device(self._h, int(n_frames), int(n_total), int(max_frame_rows), vp(d_frame_off or None), vp(d_rows or None),
-                                                int(dtype_code), None if rng is None else _p(rng), i32(n_samples), i32(n_features), vp(d_keep_in or None),
-                                                i32(n_sectors), vp(d_rois or None), i32(n_rois), i32(roi_features), float(roi_margin),
+                                                int(dtype_code), _p(rng), _i32(n_samples), _i32(n_features), vp(d_keep_in or None),
+                                                _i32(n_sectors), vp(d_rois or None), _i32(n_rois), _i32(roi_features), float(roi_margin),
                                                 vp(d_out_index or None), vp(d_out_points or None), vp(d_out_dist or None), vp(d_out_usable or None),
                                                 vp(d_out_sector_offsets or None), vp(d_out_sector_count or None), vp(d_out_sector_of or None),
                                                 vp(d_out_reach2 or None), vp(stream or None))
-        if rc == E_INVALID:
-            raise ValueError(self._L.snowgpu_last_error(self._h).decode())
-        self._check(rc)
+        self._check_args(rc)
 
     def ball_query_device(self, n_frames, n_total, max_frame_rows, d_frame_off, d_rows, dtype_code, point_cloud_range, n_centres, d_centres,
                           centre_features, radii, n_samples, n_features, d_keep_in, d_out_index, d_out_count, d_out_points, stream=0):
@@ -611,23 +613,16 @@ class Context:
         point_cloud_range: 6 numbers or None; radii and n_samples: sequences of equal length.  An argument outside the domain, or an
         output overlapping the mask, the rows or the centres, raises ValueError with the entry's words."""
         vp = ctypes.c_void_p
-        rng = None
-        if point_cloud_range is not None:
-            rng = np.ascontiguousarray(point_cloud_range, np.float64).reshape(-1)
-            if rng.shape != (6,):
-                raise ValueError("snowgpu_ball_query_device: point_cloud_range holds 6 numbers (x0, y0, z0, x1, y1, z1)")
-        i32 = lambda v: max(-(2 ** 31), min(int(v), 2 ** 31 - 1))
+        rng = _range6("snowgpu_ball_query_device", point_cloud_range)
         rad = np.ascontiguousarray(radii, np.float64).reshape(-1)
-        ns = np.ascontiguousarray([i32(v) for v in n_samples], np.int32).reshape(-1)
+        ns = np.ascontiguousarray([_i32(v) for v in n_samples], np.int32).reshape(-1)
         if len(rad) != len(ns):
             raise ValueError("snowgpu_ball_query_device: as many radii as sample counts")
         rc = self._L.snowgpu_ball_query_device(self._h, int(n_frames), int(n_total), int(max_frame_rows), vp(d_frame_off or None), vp(d_rows or None),
-                                               int(dtype_code), None if rng is None else _p(rng), i32(n_centres), vp(d_centres or None),
-                                               i32(centre_features), len(rad), _p(rad), _p(ns), i32(n_features), vp(d_keep_in or None),
+                                               int(dtype_code), _p(rng), _i32(n_centres), vp(d_centres or None),
+                                               _i32(centre_features), len(rad), _p(rad), _p(ns), _i32(n_features), vp(d_keep_in or None),
                                                vp(d_out_index or None), vp(d_out_count or None), vp(d_out_points or None), vp(stream or None))
-        if rc == E_INVALID:
-            raise ValueError(self._L.snowgpu_last_error(self._h).decode())
-        self._check(rc)
+        self._check_args(rc)
 
     def range_image_device(self, n_frames, n_total, max_frame_rows, d_frame_off, d_rows, dtype_code, height, width, fov, d_ring, range_limits,
                            n_features, d_keep_in, d_out_image, d_out_index, d_out_pixel_of, d_out_count, stream=0):
@@ -635,7 +630,6 @@ class Context:
         fov: (up, down) in RADIANS or None (image rows by channel: d_ring); range_limits: (lo, hi) or None.  An argument outside the
         domain, or an output overlapping the rows, the mask, the channels or another output, raises ValueError with the entry's words."""
         vp = ctypes.c_void_p
-        i32 = lambda v: max(-(2 ** 31), min(int(v), 2 ** 31 - 1))
         pair = {}
         for name, v in (("fov", fov), ("range_limits", range_limits)):
             pair[name] = None
@@ -644,13 +638,11 @@ class Context:
                 if pair[name].shape != (2,):
                     raise ValueError(f"snowgpu_range_image_device: {name} holds 2 numbers")
         rc = self._L.snowgpu_range_image_device(self._h, int(n_frames), int(n_total), int(max_frame_rows), vp(d_frame_off or None), vp(d_rows or None),
-                                                int(dtype_code), i32(height), i32(width), None if pair["fov"] is None else _p(pair["fov"]),
-                                                vp(d_ring or None), None if pair["range_limits"] is None else _p(pair["range_limits"]), i32(n_features),
+                                                int(dtype_code), _i32(height), _i32(width), None if pair["fov"] is None else _p(pair["fov"]),
+                                                vp(d_ring or None), None if pair["range_limits"] is None else _p(pair["range_limits"]), _i32(n_features),
                                                 vp(d_keep_in or None), vp(d_out_image or None), vp(d_out_index or None), vp(d_out_pixel_of or None),
                                                 vp(d_out_count or None), vp(stream or None))
-        if rc == E_INVALID:
-            raise ValueError(self._L.snowgpu_last_error(self._h).decode())
-        self._check(rc)
+        self._check_args(rc)
 
     def nearest_centres_device(self, n_frames, n_total, max_frame_rows, d_frame_off, d_rows, dtype_code, point_cloud_range, n_centres, d_centres,
                                centre_features, k, d_keep_in, d_out_index, d_out_dist2, d_out_weight, stream=0):
@@ -658,19 +650,12 @@ class Context:
         point_cloud_range: 6 numbers or None.  An argument outside the domain, or an output overlapping the mask, the rows, the centres
         or another output, raises ValueError with the entry's words."""
         vp = ctypes.c_void_p
-        rng = None
-        if point_cloud_range is not None:
-            rng = np.ascontiguousarray(point_cloud_range, np.float64).reshape(-1)
-            if rng.shape != (6,):
-                raise ValueError("snowgpu_nearest_centres_device: point_cloud_range holds 6 numbers (x0, y0, z0, x1, y1, z1)")
-        i32 = lambda v: max(-(2 ** 31), min(int(v), 2 ** 31 - 1))
+        rng = _range6("snowgpu_nearest_centres_device", point_cloud_range)
         rc = self._L.snowgpu_nearest_centres_device(self._h, int(n_frames), int(n_total), int(max_frame_rows), vp(d_frame_off or None), vp(d_rows or None),
-                                                    int(dtype_code), None if rng is None else _p(rng), i32(n_centres), vp(d_centres or None),
-                                                    i32(centre_features), i32(k), vp(d_keep_in or None), vp(d_out_index or None),
+                                                    int(dtype_code), _p(rng), _i32(n_centres), vp(d_centres or None),
+                                                    _i32(centre_features), _i32(k), vp(d_keep_in or None), vp(d_out_index or None),
                                                     vp(d_out_dist2 or None), vp(d_out_weight or None), vp(stream or None))
-        if rc == E_INVALID:
-            raise ValueError(self._L.snowgpu_last_error(self._h).decode())
-        self._check(rc)
+        self._check_args(rc)
 
     def points_in_boxes_device(self, n_frames, n_total, max_frame_rows, d_frame_off, d_rows, dtype_code, n_boxes, d_boxes, box_features, d_pose_in,
                                d_keep_in, d_out_box_of, d_out_count, d_out_local, d_out_pose, stream=0):
@@ -678,14 +663,11 @@ class Context:
         d_pose_in, d_keep_in, d_out_count, d_out_local and d_out_pose may be 0.  An argument outside the domain, or an output overlapping
         the mask, the rows, the boxes, the given pose or another output, raises ValueError with the entry's words."""
         vp = ctypes.c_void_p
-        i32 = lambda v: max(-(2 ** 31), min(int(v), 2 ** 31 - 1))
         rc = self._L.snowgpu_points_in_boxes_device(self._h, int(n_frames), int(n_total), int(max_frame_rows), vp(d_frame_off or None), vp(d_rows or None),
-                                                    int(dtype_code), i32(n_boxes), vp(d_boxes or None), i32(box_features), vp(d_pose_in or None),
+                                                    int(dtype_code), _i32(n_boxes), vp(d_boxes or None), _i32(box_features), vp(d_pose_in or None),
                                                     vp(d_keep_in or None), vp(d_out_box_of or None), vp(d_out_count or None), vp(d_out_local or None),
                                                     vp(d_out_pose or None), vp(stream or None))
-        if rc == E_INVALID:
-            raise ValueError(self._L.snowgpu_last_error(self._h).decode())
-        self._check(rc)
+        self._check_args(rc)
 
     def boxes_iou_device(self, n_frames, n_a, d_boxes_a, a_features, n_b, d_boxes_b, b_features, dtype_code, mode, d_pose_a, d_pose_b, d_out_iou,
                          d_out_best, d_out_best_iou, stream=0):
@@ -693,13 +675,10 @@ class Context:
         asynchronous on `stream`.  mode 0: BEV, 1: 3D.  The poses and up to two of the outputs may be 0.  An argument outside the domain, or an
         output overlapping an input or another output, raises ValueError with the entry's words."""
         vp = ctypes.c_void_p
-        i32 = lambda v: max(-(2 ** 31), min(int(v), 2 ** 31 - 1))
-        rc = self._L.snowgpu_boxes_iou_device(self._h, i32(n_frames), i32(n_a), vp(d_boxes_a or None), i32(a_features), i32(n_b), vp(d_boxes_b or None),
-                                              i32(b_features), int(dtype_code), int(mode), vp(d_pose_a or None), vp(d_pose_b or None), vp(d_out_iou or None),
+        rc = self._L.snowgpu_boxes_iou_device(self._h, _i32(n_frames), _i32(n_a), vp(d_boxes_a or None), _i32(a_features), _i32(n_b), vp(d_boxes_b or None),
+                                              _i32(b_features), int(dtype_code), int(mode), vp(d_pose_a or None), vp(d_pose_b or None), vp(d_out_iou or None),
                                               vp(d_out_best or None), vp(d_out_best_iou or None), vp(stream or None))
-        if rc == E_INVALID:
-            raise ValueError(self._L.snowgpu_last_error(self._h).decode())
-        self._check(rc)
+        self._check_args(rc)
 
     def nms_device(self, n_frames, n_boxes, d_boxes, box_features, d_scores, dtype_code, mode, iou_thresh, score_thresh, post_max, d_pose_in, d_out_index,
                    d_out_count, d_out_boxes, d_out_scores, d_out_kept, stream=0):
@@ -707,13 +686,10 @@ class Context:
         d_out_scores and d_out_kept may be 0.  An argument outside the domain, or an output overlapping an input or another output, raises
         ValueError with the entry's words."""
         vp = ctypes.c_void_p
-        i32 = lambda v: max(-(2 ** 31), min(int(v), 2 ** 31 - 1))
-        rc = self._L.snowgpu_nms_device(self._h, i32(n_frames), i32(n_boxes), vp(d_boxes or None), i32(box_features), vp(d_scores or None), int(dtype_code),
-                                        int(mode), float(iou_thresh), float(score_thresh), i32(post_max), vp(d_pose_in or None), vp(d_out_index or None),
+        rc = self._L.snowgpu_nms_device(self._h, _i32(n_frames), _i32(n_boxes), vp(d_boxes or None), _i32(box_features), vp(d_scores or None), int(dtype_code),
+                                        int(mode), float(iou_thresh), float(score_thresh), _i32(post_max), vp(d_pose_in or None), vp(d_out_index or None),
                                         vp(d_out_count or None), vp(d_out_boxes or None), vp(d_out_scores or None), vp(d_out_kept or None), vp(stream or None))
-        if rc == E_INVALID:
-            raise ValueError(self._L.snowgpu_last_error(self._h).decode())
-        self._check(rc)
+        self._check_args(rc)
 
     def set_fov(self, calib=None, img_shape=(1024, 1920), pre_crop=False):
         """Camera-FOV crop inside the compaction of every later batch (None switches it off).  `calib` carries V2C (3 x 4),

@@ -1,0 +1,810 @@
+"""The device stages of the torch-tensor boundary (tensors.py is the documented import path and lists what each is for) and the batches
+of static shape they leave behind: fov_keep, dror_keep, voxelize, sample_keypoints, ball_query, range_image, nearest_keypoints,
+points_in_boxes, boxes_iou, nms.  Every stage goes through the same steps, in this order -- it is the order in which a call that is wrong
+in two ways is refused: the aligned unwrap and the device-input refusal (_stage_frames), the scalar and range checks (_whole, _range6),
+the batch and its keep mask (_stage_batch), the stage's own tensors, the checks of the shapes' domain, out= (_checked_out), the launch
+(_stage_launch).  PyTorch is plumbing here; the work is the C entries'."""
+from __future__ import annotations
+
+import math
+
+import numpy as np
+
+from .batch import (_checked_out, _cuda_device, _keep_mask, _on_run_stream, _range6, _resolve_input, _stage_batch, _stage_frames, _stage_launch,
+                    _whole, is_device_input)
+
+_ROWS = "rows"               # (the last word of an out= refusal: the seven row stages' tensors share the device of the rows)
+
+
+def _fov_mask(torch, eng, rows, calib, img_shape, keep, run):
+    """keep AND the camera-FOV test of every row, as a new torch.bool tensor, launched on torch stream `run` (k_fov_mask)."""
+    out = torch.empty(rows.shape[0], dtype=torch.bool, device=rows.device)
+    if rows.shape[0]:
+        eng.ctx.fov_mask_device(rows.shape[0], rows.data_ptr(), 0 if rows.dtype == torch.float32 else 1, calib, img_shape,
+                                0 if keep is None else keep.data_ptr(), out.data_ptr(), run.cuda_stream)
+    return out
+
+
+def fov_keep(frames, calib, img_shape=(1024, 1920), keep=None, *, device=None, slot=0):
+    """get_fov_flag(calib.lidar_to_rect(pc[:, 0:3]), img_shape, calib) (simulation.py:39-47) for torch CUDA tensors, on the device: a
+    torch.bool mask with one element per row of the batch (frames as augment_batch takes them), ANDed with `keep` if given -- the crop of
+    precompute.py:96-99 as a keep mask for augment_batch(..., layout='aligned', keep=mask) or any other consumer.  Asynchronous on
+    torch's current stream."""
+    if not is_device_input(frames):
+        raise ValueError("fov_keep: torch CUDA tensors (host arrays: lidar_snow_sim_amd.calibration.get_fov_flag)")
+    import torch
+    rows, offsets, _, eng = _resolve_input(torch, frames, False, device, slot)
+    if keep is not None:
+        keep = _keep_mask(torch, keep, rows, offsets)
+    with torch.cuda.device(rows.device), _on_run_stream(torch, eng, rows.device) as (_, run):
+        return _fov_mask(torch, eng, rows[:int(offsets[-1])], calib, img_shape, keep, run)
+
+
+def dror_keep(frames, alpha=0.45, beta=3, k_min=3, sr_min=0.04, keep=None, *, out=None, return_neighbours=False, device=None, slot=0):
+    """Dynamic radius outlier removal (DROR, Charron et al. 2018; pointcloud_viewer.py:2756-2758 with the defaults of :267-270) for torch
+    CUDA tensors, on the device: a torch.bool mask with one element per row of the batch (frames as augment_batch takes them), True where
+    the row is usable -- present under `keep`, every coordinate finite and within 1e6 m -- and has at least k_min other usable rows of its
+    frame within max(sr_min, beta * radians(alpha) * r_xy) of it (the definition: include/snowgpu.h, snowgpu_dror_mask_device).
+
+    frames    torch CUDA tensors, a DeviceBatch -- or an AlignedResult / AlignedWetResult: its rows, offsets and keep mask are used
+              (nothing is waited for), as voxelize and the stages behind it take one.
+    keep      an input keep mask as augment_batch(layout='aligned') takes it: an absent row is False, nobody's neighbour, never looked at
+              (with a result: ANDed with the result's own).
+    out       a torch.bool tensor with one element per row to write into (static addresses for a captured graph); not the `keep` tensor.
+    return_neighbours   also return an int32 tensor: every row's neighbours, counted up to k_min.
+
+    The mask goes straight into augment_batch(..., layout='aligned', keep=mask), augment_wet_batch_aligned(..., keep=mask) or
+    fov_keep(..., keep=mask); dror_keep(res) filters an augmented batch frame by frame.  dror_keep(res.rows, keep=res.keep) is NOT that
+    for a batch of several frames: one N_total x 5 tensor is ONE frame, and rows of different frames become each other's neighbours.
+    Asynchronous on torch's current stream."""
+    import torch
+    frames, keep = _stage_frames(torch, "dror_keep", "lidar_snow_sim_amd.dror.dynamic_radius_outlier_filter", frames, keep)
+    c = float(beta) * (float(alpha) * (math.pi / 180.0))
+    if not (0.0 < c <= 0.25):
+        raise ValueError("dror_keep: beta * radians(alpha) must lie in (0, 0.25]")
+    if not (float(sr_min) >= 0.0 and math.isfinite(float(sr_min))):
+        raise ValueError("dror_keep: sr_min must be finite and >= 0")
+    if int(k_min) != k_min or not (0 <= int(k_min) <= 65535):
+        raise ValueError("dror_keep: k_min must be an integer in 0 .. 65535")
+    rows, offsets, eng, dev, nf, n, keep = _stage_batch(torch, frames, keep, device, slot)
+    if out is None:
+        out = torch.empty(n, dtype=torch.bool, device=dev)
+    elif not (torch.is_tensor(out) and out.dtype == torch.bool and out.dim() == 1 and out.shape[0] == n and out.is_contiguous() and out.device == dev):
+        raise ValueError("dror_keep: out must be a contiguous torch.bool tensor with one element per row, on the device of the rows")
+    if keep is not None and n and out.data_ptr() < keep.data_ptr() + n and keep.data_ptr() < out.data_ptr() + n:
+        raise ValueError("dror_keep: out must not be (or overlap) the keep tensor; the query of one row reads other rows' keep elements")
+    nb = torch.zeros(n, dtype=torch.int32, device=dev) if return_neighbours else None
+    if nf and n:
+        _stage_launch(torch, eng, dev, nf, n, offsets, rows, eng.ctx.dror_mask_device, float(alpha), float(beta), float(sr_min), int(k_min),
+                      0 if keep is None else keep.data_ptr(), out.data_ptr(), 0 if nb is None else nb.data_ptr())
+    return (out, nb) if return_neighbours else out
+
+
+class VoxelBatch:
+    """What voxelize() leaves behind, F = frames, V = max_voxels, T = max_points, C = num_features -- every shape static:
+    `voxels` (F V, T, C; the rows' dtype), `coords` (F V, 4 int32: frame, z, y, x cell), `num_points` (F V, int32), `voxel_offsets`
+    (F + 1 int32, ON THE DEVICE: frame f's voxels are [voxel_offsets[f], voxel_offsets[f + 1]), the packed voxels end at
+    voxel_offsets[F]; beyond it voxels are 0, coords -1, num_points 0) and `voxel_of` (N_total int32: every row's packed voxel, -1 without
+    one; None unless asked for).  All still being written until the stream the call was made on has caught up."""
+
+    def __init__(self, voxels, coords, num_points, voxel_offsets, voxel_of=None):
+        self.voxels, self.coords, self.num_points, self.voxel_offsets, self.voxel_of = voxels, coords, num_points, voxel_offsets, voxel_of
+
+    @classmethod
+    def empty(cls, n_frames, max_points, max_voxels, num_features=4, dtype=None, device=None, n_rows=None):
+        """Uninitialised buffers of the shapes voxelize() writes for such a call (out=): static addresses for a captured graph.
+        n_rows: also a `voxel_of` for a batch of that many rows."""
+        import torch
+        dev = _cuda_device(torch, device)
+        slots = int(n_frames) * int(max_voxels)
+        i32 = dict(dtype=torch.int32, device=dev)
+        return cls(torch.empty((slots, int(max_points), int(num_features)), dtype=dtype or torch.float32, device=dev), torch.empty((slots, 4), **i32),
+                   torch.empty(slots, **i32), torch.empty(int(n_frames) + 1, **i32), None if n_rows is None else torch.empty(int(n_rows), **i32))
+
+    def frames(self):
+        """[(voxels_f, coords_f, num_points_f)] per frame, trimmed views of the result tensors.  Reads the offsets: synchronizes."""
+        off = self.voxel_offsets.cpu().numpy()
+        return [(self.voxels[a:b], self.coords[a:b], self.num_points[a:b]) for a, b in zip(off[:-1].tolist(), off[1:].tolist())]
+
+
+def voxelize(frames, point_cloud_range, voxel_size, max_points, max_voxels, *, keep=None, num_features=4, out=None, return_voxel_of=False,
+             device=None, slot=0):
+    """Point-to-voxel grouping on the device (snowgpu_voxelize_device; the definition: include/snowgpu.h): the first operation of SECOND,
+    PV-RCNN and PointPillars, with static shapes.  Per frame, the rows that are present, finite and inside point_cloud_range
+    (x0, y0, z0, x1, y1, z1) are walked in input order; the first row of a new cell opens the frame's next voxel (cells beyond max_voxels
+    are dropped), and a voxel stores its first max_points rows, columns 0 .. num_features - 1, bit for bit.
+
+    frames    what dror_keep takes -- or an AlignedResult / AlignedWetResult: its rows, offsets and keep mask are used (nothing is waited for).
+    keep      an input keep mask as the aligned calls take it (with a result: ANDed with the result's own).
+    out       a VoxelBatch to write into (VoxelBatch.empty): every element is written, nothing needs clearing.
+    return_voxel_of   also fill `voxel_of`: every row's packed voxel index, -1 without one (dynamic voxelization's point-to-voxel map).
+
+    Returns a VoxelBatch.  Asynchronous on torch's current stream; nothing is read on the host: capturable after one warm-up call."""
+    import torch
+    who = "voxelize"
+    frames, keep = _stage_frames(torch, who, "lidar_snow_sim_amd.voxel.points_to_voxels", frames, keep)
+    _whole(who, max_points=max_points, max_voxels=max_voxels, num_features=num_features)
+    rng, size = np.asarray(point_cloud_range, np.float64).reshape(-1), np.asarray(voxel_size, np.float64).reshape(-1)
+    if rng.shape != (6,) or size.shape != (3,):                  # (not _range6: the range is no option here, and the sentence names the size too)
+        raise ValueError("voxelize: point_cloud_range holds 6 numbers (x0, y0, z0, x1, y1, z1), voxel_size 3")
+    rows, offsets, eng, dev, nf, n, keep = _stage_batch(torch, frames, keep, device, slot)
+    T, V, C = int(max_points), int(max_voxels), int(num_features)
+    # (the shapes below need these three; the entry refuses them in the same words, and everything else of the domain)
+    if not 3 <= C <= 5:
+        raise ValueError("voxelize: n_features must be 3, 4 or 5: the columns of a row that a voxel stores")
+    if T < 1 or V < 1:
+        raise ValueError("voxelize: max_points and max_voxels must be at least 1")
+    if nf * V > 2 ** 31 - 1:
+        raise ValueError("voxelize: n_frames * max_voxels exceeds 2^31 - 1; split the batch")
+    if out is None:
+        out = VoxelBatch.empty(nf, T, V, C, rows.dtype, dev, n if return_voxel_of else None)
+    else:
+        _checked_out(torch, who, VoxelBatch, out, (("voxels", rows.dtype, (nf * V, T, C), True), ("coords", torch.int32, (nf * V, 4), True),
+                                                   ("num_points", torch.int32, (nf * V,), True), ("voxel_offsets", torch.int32, (nf + 1,), True),
+                                                   ("voxel_of", torch.int32, (n,), return_voxel_of)), dev, _ROWS)
+    vof = out.voxel_of if return_voxel_of else None
+    if n == 0:                                          # no row: the entry writes the offsets alone
+        out.voxels.zero_(); out.coords.fill_(-1); out.num_points.zero_()
+    _stage_launch(torch, eng, dev, nf, n, offsets, rows, eng.ctx.voxelize_device, rng, size, T, V, C, 0 if keep is None or not n else keep.data_ptr(),
+                  out.voxels.data_ptr(), out.coords.data_ptr(), out.num_points.data_ptr(), out.voxel_offsets.data_ptr(),
+                  0 if vof is None or not n else vof.data_ptr())
+    return out if return_voxel_of or out.voxel_of is None else VoxelBatch(out.voxels, out.coords, out.num_points, out.voxel_offsets)
+
+
+class KeypointBatch:
+    """What sample_keypoints() leaves behind, F = frames, K = n_samples, C = num_features -- every shape static: `index` (F, K int32: the
+    sampled rows as indices into the whole batch, so rows[index] gathers; -1 for a frame without a usable row), `points` (F, K, C; the
+    rows' dtype; zero for such a frame), `usable` (F int32, ON THE DEVICE: the usable rows of every frame -- beyond them a frame's samples
+    repeat its first usable row) and `dist` (F, K; the rows' dtype: the squared distance of every sample to the samples before it at the
+    moment it was chosen, +inf for the first, -1 for a frame without a usable row; None unless asked for).  All still being written until
+    the stream the call was made on has caught up."""
+
+    def __init__(self, index, points, usable, dist=None, sector_offsets=None, sector_count=None, sector_of=None):
+        self.index, self.points, self.usable, self.dist = index, points, usable, dist
+        # set by the sectorized call alone (sample_keypoints(sectors=..., rois=...)): (F, S + 1) int32 -- slots [o_s, o_{s+1}) of a frame
+        # are its sector s, o_S = min(usable, K) --, (F, S) int32 -- the usable rows of every sector -- and, when asked for, (N) int8:
+        # every row's sector, -1 for an absent or unusable row
+        self.sector_offsets, self.sector_count, self.sector_of = sector_offsets, sector_count, sector_of
+
+    @classmethod
+    def empty(cls, n_frames, n_samples, num_features=4, dtype=None, device=None, with_dist=False, sectors=None, with_sector_of=None):
+        """Uninitialised buffers of the shapes sample_keypoints() writes for such a call (out=): static addresses for a captured graph.
+        sectors = S adds sector_offsets and sector_count, with_sector_of = the rows of the batch adds sector_of."""
+        import torch
+        dev = _cuda_device(torch, device)
+        F, K, dt = int(n_frames), int(n_samples), dtype or torch.float32
+        out = cls(torch.empty((F, K), dtype=torch.int32, device=dev), torch.empty((F, K, int(num_features)), dtype=dt, device=dev),
+                  torch.empty(F, dtype=torch.int32, device=dev), torch.empty((F, K), dtype=dt, device=dev) if with_dist else None)
+        if sectors is not None:
+            out.sector_offsets = torch.empty((F, int(sectors) + 1), dtype=torch.int32, device=dev)
+            out.sector_count = torch.empty((F, int(sectors)), dtype=torch.int32, device=dev)
+            if with_sector_of is not None and with_sector_of is not False:
+                out.sector_of = torch.empty(int(with_sector_of), dtype=torch.int8, device=dev)
+        return out
+
+
+def sample_keypoints(frames, n_samples, *, point_cloud_range=None, keep=None, num_features=4, out=None, return_dist=False, device=None, slot=0,
+                     sectors=None, rois=None, roi_margin=1.6, return_sector_of=False):
+    """Farthest point sampling on the device (snowgpu_fps_device; the definition: include/snowgpu.h): the keypoints of PV-RCNN and the
+    fixed-size point set of PointRCNN / Part-A2, with static shapes.  Per frame, among the rows that are present, within 1e6 of the origin
+    on every axis and inside point_cloud_range (x0, y0, z0, x1, y1, z1; None: no range), the first is taken, then n_samples - 1 times the
+    row farthest from everything taken so far (squared distance in the rows' dtype; the smallest row index among equals).
+
+    frames    what voxelize takes -- torch CUDA tensors, a DeviceBatch, or an AlignedResult / AlignedWetResult: its rows, offsets and keep
+              mask are used (nothing is waited for).
+    keep      an input keep mask as the aligned calls take it (with a result: ANDed with the result's own).
+    out       a KeypointBatch to write into (KeypointBatch.empty): every element is written, nothing needs clearing.
+    return_dist   also fill `dist`.
+    sectors, rois, roi_margin, return_sector_of
+              PV-RCNN++'s sectorized, proposal-centric sampling (snowgpu_fps_sectors_device): with rois -- an (F, B, 7 .. 10) device
+              tensor of the rows' dtype, OpenPCDet's rois / gt_boxes, zero rows are padding -- only the rows within a roi's half diagonal
+              + roi_margin of its centre are usable; the usable rows are split by azimuth into `sectors` sectors (1 .. 16; 1 when only
+              rois are given) and every sector is walked on its own for its share of n_samples.  The result carries sector_offsets and
+              sector_count, and with return_sector_of every row's sector.  With both None the plain walk runs, untouched.
+
+    Returns a KeypointBatch.  Asynchronous on torch's current stream; nothing is read on the host: capturable after one warm-up call."""
+    import torch
+    who = "sample_keypoints"
+    plain = sectors is None and rois is None          # the plain walk; else the sectorized one, in one sector when only rois are given
+    if not plain and sectors is None:
+        sectors = 1
+    frames, keep = _stage_frames(torch, who, "lidar_snow_sim_amd.fps." + ("farthest_point_sample" if plain else "sectorized_sample"), frames, keep)
+    _whole(who, n_samples=n_samples, num_features=num_features, **({} if plain else {"sectors": sectors}))
+    rng = _range6(who, point_cloud_range)
+    rows, offsets, eng, dev, nf, n, keep = _stage_batch(torch, frames, keep, device, slot)
+    K, C, S = int(n_samples), int(num_features), None if plain else int(sectors)
+    # (the shapes below need these; the entry refuses them in the same words, and everything else of the domain)
+    if not 3 <= C <= 5:
+        raise ValueError("sample_keypoints: n_features must be 3, 4 or 5: the columns of a row that a keypoint carries")
+    if K < 1:
+        raise ValueError("sample_keypoints: n_samples must be at least 1")
+    if nf * K > 2 ** 31 - 1:
+        raise ValueError("sample_keypoints: n_frames * n_samples exceeds 2^31 - 1; split the batch")
+    if not plain and not 1 <= S <= 16:
+        raise ValueError("sample_keypoints: n_sectors must lie in 1 .. 16")
+    B = Cb = 0
+    if rois is not None:
+        if not (torch.is_tensor(rois) and rois.is_cuda and rois.device == dev and rois.dtype == rows.dtype and rois.dim() == 3 and rois.shape[0] == nf
+                and rois.is_contiguous()):
+            raise ValueError("sample_keypoints: rois must be a contiguous (frames, B, 7 .. 10) tensor of the rows' dtype on the device of the rows")
+        B, Cb = int(rois.shape[1]), int(rois.shape[2])
+    return_sector_of = return_sector_of and not plain
+    if out is None:
+        out = KeypointBatch.empty(nf, K, C, rows.dtype, dev, return_dist, S, n if return_sector_of else None)
+    else:
+        want = (("index", torch.int32, (nf, K), True), ("points", rows.dtype, (nf, K, C), True), ("usable", torch.int32, (nf,), True)) + \
+               (() if plain else (("sector_offsets", torch.int32, (nf, S + 1), True), ("sector_count", torch.int32, (nf, S), True))) + \
+               (("dist", rows.dtype, (nf, K), return_dist), ("sector_of", torch.int8, (n,), return_sector_of))
+        _checked_out(torch, who, KeypointBatch, out, want, dev, _ROWS)
+    dist = out.dist if return_dist else None
+    sof = out.sector_of if return_sector_of else None
+    if plain:
+        _stage_launch(torch, eng, dev, nf, n, offsets, rows, eng.ctx.fps_device, rng, K, C, 0 if keep is None or not n else keep.data_ptr(),
+                      out.index.data_ptr(), out.points.data_ptr(), 0 if dist is None else dist.data_ptr(), out.usable.data_ptr())
+        return out if return_dist or out.dist is None else KeypointBatch(out.index, out.points, out.usable)
+    _stage_launch(torch, eng, dev, nf, n, offsets, rows, eng.ctx.fps_sectors_device, rng, K, C, 0 if keep is None or not n else keep.data_ptr(), S,
+                  0 if rois is None else rois.data_ptr(), B, Cb, roi_margin, out.index.data_ptr(), out.points.data_ptr(),
+                  0 if dist is None else dist.data_ptr(), out.usable.data_ptr(), out.sector_offsets.data_ptr(), out.sector_count.data_ptr(),
+                  0 if sof is None or not n else sof.data_ptr(), 0)
+    if (dist is None) == (out.dist is None) and (sof is None) == (out.sector_of is None):
+        return out
+    return KeypointBatch(out.index, out.points, out.usable, dist, out.sector_offsets, out.sector_count, sof)      # (without what was not asked for)
+
+
+class NeighbourBatch:
+    """What ball_query() leaves behind, F = frames, K = centres per frame, R = (radius, samples) pairs, S = the sum of their samples,
+    C = num_features -- every shape static: `index` (F, K, S int32: per centre the segments of the R pairs side by side, each the smallest
+    row indices of the ball, ascending, as indices into the whole batch, padded with its first; -1 for an empty ball), `count` (F, K, R
+    int32: the rows in every ball, not saturated), `points` (F, K, S, C; the rows' dtype; zero where the index is -1; None unless asked
+    for) and `segments` (the samples of every pair, a tuple: index[..., sum(segments[:i]):sum(segments[:i + 1])] is pair i).  All still
+    being written until the stream the call was made on has caught up."""
+
+    def __init__(self, index, count, points=None, segments=()):
+        self.index, self.count, self.points, self.segments = index, count, points, tuple(int(s) for s in segments)
+
+    @classmethod
+    def empty(cls, n_frames, n_centres, n_neighbours, num_features=4, dtype=None, device=None, with_points=False):
+        """Uninitialised buffers of the shapes ball_query() writes for such a call (out=): static addresses for a captured graph."""
+        import torch
+        dev = _cuda_device(torch, device)
+        seg = tuple(int(s) for s in (n_neighbours if isinstance(n_neighbours, (tuple, list, np.ndarray)) else (n_neighbours,)))
+        F, K, S = int(n_frames), int(n_centres), sum(seg)
+        return cls(torch.empty((F, K, S), dtype=torch.int32, device=dev), torch.empty((F, K, len(seg)), dtype=torch.int32, device=dev),
+                   torch.empty((F, K, S, int(num_features)), dtype=dtype or torch.float32, device=dev) if with_points else None, seg)
+
+
+def ball_query(frames, centres, radius, n_neighbours, *, point_cloud_range=None, keep=None, num_features=4, out=None, return_points=False,
+               device=None, slot=0):
+    """Ball-query neighbour groups on the device (snowgpu_ball_query_device; the definition: include/snowgpu.h): for every centre the
+    n_neighbours smallest row indices of its frame among the rows that are present, within 1e6 of the origin on every axis, inside
+    point_cloud_range (None: no range) and STRICTLY within `radius` of the centre (squared distance in the rows' dtype), ascending and
+    padded with the first -- what the pointnet2 ball_query op returns --, -1 for an empty ball, and the full number of rows in the ball.
+
+    frames    what sample_keypoints takes -- torch CUDA tensors, a DeviceBatch, or an AlignedResult / AlignedWetResult: its rows, offsets
+              and keep mask are used (nothing is waited for).
+    centres   a KeypointBatch (its points), or an (F, K, 3 .. 5) tensor in the rows' dtype on their device: x, y, z first.
+    radius, n_neighbours   scalars, or sequences of equal length <= 4: several balls per centre from one walk, side by side in `index`.
+    keep      an input keep mask as the aligned calls take it (with a result: ANDed with the result's own).
+    out       a NeighbourBatch to write into (NeighbourBatch.empty): every element is written, nothing needs clearing.
+    return_points   also fill `points` with the first num_features columns of the indexed rows.
+
+    Returns a NeighbourBatch.  Asynchronous on torch's current stream; nothing is read on the host: capturable after one warm-up call."""
+    import torch
+    who = "ball_query"
+    frames, keep = _stage_frames(torch, who, "lidar_snow_sim_amd.ball.ball_query", frames, keep)
+    seq = lambda v: list(v) if isinstance(v, (tuple, list, np.ndarray)) else [v]
+    radii, seg = seq(radius), seq(n_neighbours)
+    if len(radii) != len(seg):
+        raise ValueError("ball_query: as many radii as sample counts")
+    _whole(who, num_features=num_features)
+    for s in seg:
+        _whole(who, n_neighbours=s)
+    rng = _range6(who, point_cloud_range)
+    rows, offsets, eng, dev, nf, n, keep = _stage_batch(torch, frames, keep, device, slot)
+    cen = centres.points if isinstance(centres, KeypointBatch) else centres
+    if not (torch.is_tensor(cen) and cen.dim() == 3 and cen.shape[0] == nf and cen.dtype == rows.dtype and cen.device == dev and cen.is_contiguous()):
+        raise ValueError("ball_query: centres must be a KeypointBatch or a contiguous (frames, K, 3 .. 5) tensor in the rows' dtype on their device")
+    K, Cq, C, R = int(cen.shape[1]), int(cen.shape[2]), int(num_features), len(radii)
+    seg = [int(s) for s in seg]
+    # (the shapes below need these; the entry refuses them in the same words, and everything else of the domain)
+    if not 3 <= C <= 5:
+        raise ValueError("ball_query: n_features must be 3, 4 or 5: the columns of a row that a neighbour carries")
+    if not 3 <= Cq <= 5:
+        raise ValueError("ball_query: centre_features must be 3, 4 or 5: x, y, z first")
+    if K < 1:
+        raise ValueError("ball_query: n_centres must be at least 1")
+    if not 1 <= R <= 4:
+        raise ValueError("ball_query: n_radii must lie in 1 .. 4")
+    if any(not 1 <= s <= 64 for s in seg):
+        raise ValueError("ball_query: the samples of a radius must lie in 1 .. 64")
+    S = sum(seg)
+    if nf * K * S > 2 ** 31 - 1:
+        raise ValueError("ball_query: n_frames * n_centres * samples exceeds 2^31 - 1; split the batch")
+    if out is None:
+        out = NeighbourBatch.empty(nf, K, seg, C, rows.dtype, dev, return_points)
+    else:
+        _checked_out(torch, who, NeighbourBatch, out, (("index", torch.int32, (nf, K, S), True), ("count", torch.int32, (nf, K, R), True),
+                                                       ("points", rows.dtype, (nf, K, S, C), return_points)), dev, _ROWS)
+    points = out.points if return_points else None
+    _stage_launch(torch, eng, dev, nf, n, offsets, rows, eng.ctx.ball_query_device, rng, K, cen.data_ptr(), Cq, radii, seg, C,
+                  0 if keep is None or not n else keep.data_ptr(), out.index.data_ptr(), out.count.data_ptr(), 0 if points is None else points.data_ptr())
+    return NeighbourBatch(out.index, out.count, points, seg) if (out.segments != tuple(seg) or (points is None) != (out.points is None)) else out
+
+
+class RangeImageBatch:
+    """What range_image() leaves behind, F = frames, H x W the image, C = num_features -- every shape static: `image` (F, 1 + C, H, W; the
+    rows' dtype: plane 0 the range of the pixel's nearest row, planes 1 .. C its columns 0 .. C - 1, bit for bit; -1 in an empty pixel),
+    `index` (F, H, W int32: that row as an index into the whole batch, so rows[index] gathers; -1 in an empty pixel), `pixel_of` (N_total
+    int32: every row's flat pixel f H W + row W + col, whether it won or not; -1 for absent and unusable rows) and `count` (F, H, W int32:
+    the usable rows that fell in the pixel; None unless asked for).  All still being written until the stream the call was made on has
+    caught up."""
+
+    def __init__(self, image, index, pixel_of, count=None):
+        self.image, self.index, self.pixel_of, self.count = image, index, pixel_of, count
+
+    @classmethod
+    def empty(cls, n_frames, height, width, n_rows, num_features=4, dtype=None, device=None, with_count=False):
+        """Uninitialised buffers of the shapes range_image() writes for such a call on a batch of n_rows rows (out=): static addresses
+        for a captured graph."""
+        import torch
+        dev = _cuda_device(torch, device)
+        F, H, W = int(n_frames), int(height), int(width)
+        i32 = dict(dtype=torch.int32, device=dev)
+        return cls(torch.empty((F, 1 + int(num_features), H, W), dtype=dtype or torch.float32, device=dev), torch.empty((F, H, W), **i32),
+                   torch.empty(int(n_rows), **i32), torch.empty((F, H, W), **i32) if with_count else None)
+
+    def to_rows(self, values, fill=0):
+        """The way back: a per-pixel tensor (F, H, W) or (F, X, H, W) -- a de-noiser's keep or class map -- as a per-row tensor (N,) or
+        (N, X): every row gets the value of its pixel, `fill` where pixel_of is -1.  Pure indexing on the device, nothing is read on
+        the host: a predicted mask goes straight into augment_batch(..., keep=) or dror_keep(..., keep=)."""
+        import torch
+        F, H, W = self.index.shape
+        if not (torch.is_tensor(values) and values.dim() in (3, 4) and values.shape[0] == F and tuple(values.shape[-2:]) == (H, W)):
+            raise ValueError(f"to_rows: values must be a ({F}, {H}, {W}) or ({F}, X, {H}, {W}) tensor: one value, or X of them, per pixel")
+        p = self.pixel_of.long()
+        at = p.clamp(min=0)
+        if values.dim() == 3:
+            got = values.reshape(-1)[at]
+            return torch.where(p >= 0, got, torch.full_like(got, fill))
+        f = torch.div(at, H * W, rounding_mode="floor")
+        got = values.reshape(F, values.shape[1], H * W)[f, :, at - f * (H * W)]
+        return torch.where((p >= 0)[:, None], got, torch.full_like(got, fill))
+
+
+def range_image(frames, height, width, *, fov_up=3.0, fov_down=-25.0, ring=None, range_limits=(0.0, float("inf")), keep=None, num_features=4,
+                out=None, return_count=False, device=None, slot=0):
+    """Range-image projection on the device (snowgpu_range_image_device; the definition: include/snowgpu.h): every frame as a height x
+    width image of its nearest returns, the input of the range-view networks (RangeNet++, SalsaNext) and of the snow de-noisers
+    (WeatherNet, 4DenoiseNet, LiSnowNet), with static shapes.  The column is the azimuth, the image row the elevation between fov_down and
+    fov_up (DEGREES, as the RangeNet++ configs give them; rows beyond are clamped to the first and last image row) -- or, with `ring`,
+    the row's laser channel.  Per pixel the usable row (present, within 1e6 of the origin on every axis, range strictly inside
+    range_limits) with the smallest range wins, the smallest row index among equals.
+
+    frames    what voxelize takes -- torch CUDA tensors, a DeviceBatch, or an AlignedResult / AlignedWetResult: its rows, offsets and keep
+              mask are used (nothing is waited for).
+    ring      an int32 CUDA tensor with one image row per row of the batch, e.g. the INPUT's column 4 as int32 beside an aligned result (a
+              scattered row moves along its own beam and keeps its channel); rows whose ring is outside 0 .. height - 1 are unusable.
+    keep      an input keep mask as the aligned calls take it (with a result: ANDed with the result's own).
+    out       a RangeImageBatch to write into (RangeImageBatch.empty): every element is written, nothing needs clearing.
+    return_count   also fill `count`.
+
+    Returns a RangeImageBatch; its to_rows() carries a per-pixel prediction back to the rows.  Asynchronous on torch's current stream;
+    nothing is read on the host: capturable after one warm-up call."""
+    import torch
+    who = "range_image"
+    frames, keep = _stage_frames(torch, who, "lidar_snow_sim_amd.range_image.project", frames, keep)
+    _whole(who, height=height, width=width, num_features=num_features)
+    limits = np.asarray(range_limits, np.float64).reshape(-1)
+    if limits.shape != (2,):
+        raise ValueError("range_image: range_limits holds 2 numbers (lo, hi)")
+    rows, offsets, eng, dev, nf, n, keep = _stage_batch(torch, frames, keep, device, slot)
+    H, W, C = int(height), int(width), int(num_features)
+    if ring is not None and not (torch.is_tensor(ring) and ring.dtype == torch.int32 and ring.dim() == 1 and ring.shape[0] == n and ring.device == dev and
+                                 ring.is_contiguous()):
+        raise ValueError("range_image: ring must be a contiguous int32 tensor with one element per row of the batch, on the device of the rows")
+    # (the shapes below need these; the entry refuses them in the same words, and everything else of the domain)
+    if not 3 <= C <= 5:
+        raise ValueError("range_image: n_features must be 3, 4 or 5: the columns of a row that a pixel stores")
+    if H < 1 or W < 1:
+        raise ValueError("range_image: height and width must be at least 1")
+    if nf * H * W > 2 ** 31 - 1:
+        raise ValueError("range_image: n_frames * height * width exceeds 2^31 - 1; split the batch")
+    if out is None:
+        out = RangeImageBatch.empty(nf, H, W, n, C, rows.dtype, dev, return_count)
+    else:
+        _checked_out(torch, who, RangeImageBatch, out, (("image", rows.dtype, (nf, 1 + C, H, W), True), ("index", torch.int32, (nf, H, W), True),
+                                                        ("pixel_of", torch.int32, (n,), True), ("count", torch.int32, (nf, H, W), return_count)), dev, _ROWS)
+    count = out.count if return_count else None
+    by_ring = ring is not None and n > 0          # (without a row there is no channel to read: either mode writes the empty image)
+    fov = None if by_ring else np.radians(np.array([fov_up, fov_down], np.float64))
+    _stage_launch(torch, eng, dev, nf, n, offsets, rows, eng.ctx.range_image_device, H, W, fov, ring.data_ptr() if by_ring else 0, limits, C,
+                  0 if keep is None or not n else keep.data_ptr(), out.image.data_ptr(), out.index.data_ptr(), out.pixel_of.data_ptr() if n else 0,
+                  0 if count is None else count.data_ptr())
+    return out if return_count or out.count is None else RangeImageBatch(out.image, out.index, out.pixel_of)
+
+
+class NearestBatch:
+    """What nearest_keypoints() leaves behind, N = rows of the batch, k = neighbours, K = centres per frame -- every shape static: `index`
+    (N, k int32: per row its k nearest usable centres of its frame by (squared distance, centre number), as centre numbers 0 .. K - 1
+    WITHIN THE FRAME; -1 in a slot beyond the frame's usable centres and in every slot of an absent or unusable row), `dist2` (N, k; the
+    rows' dtype; +inf where the index is -1) and `weight` (N, k; the rows' dtype: pointnet2's normalised 1 / (dist + 1e-8); 0 where the
+    index is -1; None unless asked for).  `offsets` (host) and `n_centres` say which frame a row belongs to and how many centres a frame
+    has: flat_index(), interpolate() and nearest() are the way back from per-keypoint values to the rows -- pure indexing, no kernel of
+    this library.  All still being written until the stream the call was made on has caught up."""
+
+    def __init__(self, index, dist2, weight=None, offsets=None, n_centres=0):
+        self.index, self.dist2, self.weight, self.n_centres = index, dist2, weight, int(n_centres)
+        self.offsets = np.array([0, index.shape[0]], np.int64) if offsets is None else np.asarray(offsets, np.int64)
+        self._base = None
+
+    @classmethod
+    def empty(cls, offsets, n_centres, k=3, dtype=None, device=None, with_weights=True):
+        """Uninitialised buffers of the shapes nearest_keypoints() writes for a batch with these frame offsets (or, for one frame, this
+        number of rows) (out=): static addresses for a captured graph."""
+        import torch
+        dev = _cuda_device(torch, device)
+        off = np.array([0, int(offsets)], np.int64) if np.ndim(offsets) == 0 else np.asarray(offsets, np.int64)
+        n, dt = int(off[-1]), dtype or torch.float32
+        return cls(torch.empty((n, int(k)), dtype=torch.int32, device=dev), torch.empty((n, int(k)), dtype=dt, device=dev),
+                   torch.empty((n, int(k)), dtype=dt, device=dev) if with_weights else None, off, n_centres)
+
+    def flat_index(self):
+        """index + frame * K, -1 kept (N, k int64): gathers from per-keypoint values flattened to (F K, ...).  The first call of a batch of
+        several frames uploads their row counts (a few bytes; make it before capturing a graph); later calls reuse the result."""
+        import torch
+        idx = self.index.long()
+        if len(self.offsets) <= 2:
+            return idx
+        if self._base is None:
+            counts = torch.from_numpy(np.diff(self.offsets)).to(idx.device)
+            first = torch.arange(len(counts), device=idx.device) * self.n_centres
+            self._base = torch.repeat_interleave(first, counts, output_size=int(self.offsets[-1]))[:, None]
+        return torch.where(idx >= 0, idx + self._base, idx)
+
+    def _values(self, values, what):
+        import torch
+        F, K = len(self.offsets) - 1, self.n_centres
+        if not (torch.is_tensor(values) and values.dim() in (2, 3) and tuple(values.shape[:2]) == (F, K) and values.device == self.index.device):
+            raise ValueError(f"{what}: values must be a ({F}, {K}) or ({F}, {K}, D) tensor on the device of the rows: one value, or D of them, per keypoint")
+        return values.reshape(F * K, -1) if values.dim() == 3 else values.reshape(F * K)
+
+    def interpolate(self, features):
+        """three_interpolate: per-keypoint features (F, K, D) or (F, K) as per-row features (N, D) or (N,): the sum over the slots of
+        weight * features[index], in the features' dtype.  A row without a neighbour gets 0."""
+        if self.weight is None:
+            raise ValueError("interpolate: this NearestBatch has no weights (nearest_keypoints(..., return_weights=True))")
+        flat = self._values(features, "interpolate")
+        at = self.flat_index().clamp(min=0)               # (the weight of a -1 slot is 0)
+        w = self.weight.to(flat.dtype)
+        return (flat[at] * (w[..., None] if flat.dim() == 2 else w)).sum(dim=1)
+
+    def nearest(self, values, default=0):
+        """Voronoi labelling: every row gets the value of its nearest keypoint (slot 0) from per-keypoint values (F, K) or (F, K, D) --
+        a keypoint-level keep decision becomes a per-row mask for augment_batch(..., keep=) or dror_keep(..., keep=); `default` for a
+        row without a neighbour."""
+        import torch
+        flat = self._values(values, "nearest")
+        first = self.flat_index()[:, 0]
+        got = flat[first.clamp(min=0)]
+        has = first >= 0
+        return torch.where(has[:, None] if got.dim() == 2 else has, got, torch.full_like(got, default))
+
+
+def nearest_keypoints(frames, centres, k=3, *, point_cloud_range=None, keep=None, out=None, return_weights=True, device=None, slot=0):
+    """The k nearest centres of every row on the device (snowgpu_nearest_centres_device; the definition: include/snowgpu.h): pointnet2's
+    three_nn with its interpolation weights, the way back from keypoints to the rows of the batch.  A row takes part if it is present,
+    within 1e6 of the origin on every axis and inside point_cloud_range (None: no range); its neighbours are the usable centres of its
+    frame in the order of (squared distance in the rows' dtype, centre number).
+
+    frames    what ball_query takes -- torch CUDA tensors, a DeviceBatch, or an AlignedResult / AlignedWetResult: its rows, offsets and
+              keep mask are used (nothing is waited for).
+    centres   a KeypointBatch (its points), or an (F, K, 3 .. 5) tensor in the rows' dtype on their device: x, y, z first.
+    k         1 .. 8 neighbours per row.
+    keep      an input keep mask as the aligned calls take it (with a result: ANDed with the result's own).
+    out       a NearestBatch to write into (NearestBatch.empty): every element is written, nothing needs clearing.
+    return_weights   also fill `weight`.
+
+    Returns a NearestBatch; its interpolate() and nearest() carry per-keypoint values back to the rows.  Asynchronous on torch's current
+    stream; nothing is read on the host: capturable after one warm-up call."""
+    import torch
+    who = "nearest_keypoints"
+    frames, keep = _stage_frames(torch, who, "lidar_snow_sim_amd.nearest.three_nn", frames, keep)
+    _whole(who, k=k)
+    k = int(k)
+    if not 1 <= k <= 8:
+        raise ValueError("nearest_keypoints: k must lie in 1 .. 8")
+    rng = _range6(who, point_cloud_range)
+    rows, offsets, eng, dev, nf, n, keep = _stage_batch(torch, frames, keep, device, slot)
+    cen = centres.points if isinstance(centres, KeypointBatch) else centres
+    if not (torch.is_tensor(cen) and cen.dim() == 3 and cen.shape[0] == nf and cen.dtype == rows.dtype and cen.device == dev and cen.is_contiguous()):
+        raise ValueError("nearest_keypoints: centres must be a KeypointBatch or a contiguous (frames, K, 3 .. 5) tensor in the rows' dtype on their device")
+    K, Cq = int(cen.shape[1]), int(cen.shape[2])
+    # (the shapes below need these; the entry refuses them in the same words, and everything else of the domain)
+    if not 3 <= Cq <= 5:
+        raise ValueError("nearest_keypoints: centre_features must be 3, 4 or 5: x, y, z first (centres)")
+    if K < 1:
+        raise ValueError("nearest_keypoints: n_centres must be at least 1 (centres)")
+    if nf * K > 2 ** 31 - 1:
+        raise ValueError("nearest_keypoints: n_frames * n_centres exceeds 2^31 - 1; split the batch")
+    if out is None:
+        out = NearestBatch.empty(offsets, K, k, rows.dtype, dev, return_weights)
+    else:
+        _checked_out(torch, who, NearestBatch, out, (("index", torch.int32, (n, k), True), ("dist2", rows.dtype, (n, k), True),
+                                                     ("weight", rows.dtype, (n, k), return_weights)), dev, _ROWS)
+    weight = out.weight if return_weights else None
+    _stage_launch(torch, eng, dev, nf, n, offsets, rows, eng.ctx.nearest_centres_device, rng, K, cen.data_ptr(), Cq, k,
+                  0 if keep is None or not n else keep.data_ptr(), out.index.data_ptr() if n else 0, out.dist2.data_ptr() if n else 0,
+                  0 if weight is None or not n else weight.data_ptr())
+    same = out.n_centres == K and np.array_equal(out.offsets, np.asarray(offsets, np.int64)) and (weight is None) == (out.weight is None)
+    return out if same else NearestBatch(out.index, out.dist2, weight, offsets, K)
+
+
+class BoxLabelBatch:
+    """What points_in_boxes() leaves behind, N = rows of the batch, F = frames, B = boxes per frame -- every shape static: `box_of` (N
+    int32: the smallest present box number of the row's frame that contains the row, 0 .. B - 1; -1 for a row in no box and for an absent
+    or unusable row), `count` (F, B int32: the usable rows inside every box, overlaps included, 0 for an absent box; None unless asked
+    for), `local` (N, 3 in the rows' dtype: the row in the frame of its box -- along its length, its width, and up from its centre; zeros
+    where box_of is -1; None unless asked for) and `pose` (F, B, 2 float64: the (cos, sin) of the heading that was used, (0, 0) for an
+    absent box; None unless asked for).  `offsets` (host) and `n_boxes` say which frame a row belongs to: flat_index(), labels(),
+    keep_boxes() and rows_in() are pure indexing, no kernel of this library.  All still being written until the stream the call was made
+    on has caught up."""
+
+    def __init__(self, box_of, count, local=None, pose=None, offsets=None, n_boxes=0):
+        self.box_of, self.count, self.local, self.pose, self.n_boxes = box_of, count, local, pose, int(n_boxes)
+        self.offsets = np.array([0, box_of.shape[0]], np.int64) if offsets is None else np.asarray(offsets, np.int64)
+        self._base = None
+
+    @classmethod
+    def empty(cls, offsets, n_boxes, dtype=None, device=None, with_count=True, with_local=False, with_pose=False):
+        """Uninitialised buffers of the shapes points_in_boxes() writes for a batch with these frame offsets (or, for one frame, this
+        number of rows) (out=): static addresses for a captured graph."""
+        import torch
+        dev = _cuda_device(torch, device)
+        off = np.array([0, int(offsets)], np.int64) if np.ndim(offsets) == 0 else np.asarray(offsets, np.int64)
+        n, nf, B = int(off[-1]), len(off) - 1, int(n_boxes)
+        return cls(torch.empty(n, dtype=torch.int32, device=dev), torch.empty((nf, B), dtype=torch.int32, device=dev) if with_count else None,
+                   torch.empty((n, 3), dtype=dtype or torch.float32, device=dev) if with_local else None,
+                   torch.empty((nf, B, 2), dtype=torch.float64, device=dev) if with_pose else None, off, B)
+
+    def flat_index(self):
+        """box_of + frame * B, -1 kept (N int64): gathers from per-box values flattened to (F B, ...).  The first call of a batch of
+        several frames uploads their row counts (a few bytes; make it before capturing a graph); later calls reuse the result."""
+        import torch
+        idx = self.box_of.long()
+        if len(self.offsets) <= 2:
+            return idx
+        if self._base is None:
+            counts = torch.from_numpy(np.diff(self.offsets)).to(idx.device)
+            first = torch.arange(len(counts), device=idx.device) * self.n_boxes
+            self._base = torch.repeat_interleave(first, counts, output_size=int(self.offsets[-1]))
+        return torch.where(idx >= 0, idx + self._base, idx)
+
+    def labels(self, per_box, background=0):
+        """Per-box values (F, B) or (F, B, D) -- the class column of gt_boxes, say -- as per-row values (N,) or (N, D): the value of the
+        row's box, `background` for a row in no box.  The point heads' point_cls_labels."""
+        import torch
+        F, B = len(self.offsets) - 1, self.n_boxes
+        if not (torch.is_tensor(per_box) and per_box.dim() in (2, 3) and tuple(per_box.shape[:2]) == (F, B) and per_box.device == self.box_of.device):
+            raise ValueError(f"labels: per_box must be a ({F}, {B}) or ({F}, {B}, D) tensor on the device of the rows: one value, or D of them, per box")
+        flat = per_box.reshape(F * B, -1) if per_box.dim() == 3 else per_box.reshape(F * B)
+        at = self.flat_index()
+        got = flat[at.clamp(min=0)]
+        has = at >= 0
+        return torch.where(has[:, None] if got.dim() == 2 else has, got, torch.full_like(got, background))
+
+    def keep_boxes(self, min_points=1):
+        """(F, B) bool: count >= min_points, min_points >= 1 -- filter_by_min_points after the augmentation; an absent box is never kept."""
+        if self.count is None:
+            raise ValueError("keep_boxes: this BoxLabelBatch has no count (points_in_boxes(..., return_count=True))")
+        if isinstance(min_points, bool) or int(min_points) != min_points or int(min_points) < 1:
+            raise ValueError("keep_boxes: min_points must be an integer of at least 1")
+        return self.count >= int(min_points)
+
+    def rows_in(self, box_mask=None):
+        """(N,) bool: the rows inside a box -- with box_mask (F, B bool), inside a box whose entry is set, judged by the row's own box
+        (box_of).  A keep mask for augment_batch(..., keep=) or dror_keep(..., keep=); its negation clears a pasted object's place."""
+        import torch
+        if box_mask is None:
+            return self.box_of >= 0
+        F, B = len(self.offsets) - 1, self.n_boxes
+        if not (torch.is_tensor(box_mask) and box_mask.dtype == torch.bool and tuple(box_mask.shape) == (F, B) and box_mask.device == self.box_of.device):
+            raise ValueError(f"rows_in: box_mask must be a ({F}, {B}) bool tensor on the device of the rows")
+        at = self.flat_index()
+        return (at >= 0) & box_mask.reshape(F * B)[at.clamp(min=0)]
+
+
+def points_in_boxes(frames, boxes, *, pose=None, keep=None, out=None, return_count=True, return_local=False, return_pose=False, device=None, slot=0):
+    """The box of every row and the rows of every box on the device (snowgpu_points_in_boxes_device; the definition: include/snowgpu.h):
+    roiaware_pool3d's points_in_boxes_gpu with check_pt_in_box3d's faces -- z closed, x and y strict with the 1e-5 margin -- in float64.
+    A row takes part if it is present and within 1e6 of the origin on every axis.
+
+    frames    what nearest_keypoints takes -- torch CUDA tensors, a DeviceBatch, or an AlignedResult / AlignedWetResult: its rows,
+              offsets and keep mask are used (nothing is waited for).
+    boxes     a contiguous (F, B, 7 .. 10) tensor in the rows' dtype on their device, 1 <= B <= 256: cx, cy, cz, dx, dy, dz, heading
+              first (OpenPCDet's gt_boxes; its zero rows are absent boxes).
+    pose      None: cos / sin of the heading in float64 on the device; or a contiguous (F, B, 2) float64 tensor (cos, sin) used as it is.
+    keep      an input keep mask as the aligned calls take it (with a result: ANDed with the result's own).
+    out       a BoxLabelBatch to write into (BoxLabelBatch.empty): every element is written, nothing needs clearing.
+
+    Returns a BoxLabelBatch.  Asynchronous on torch's current stream; nothing is read on the host: capturable after one warm-up call."""
+    import torch
+    who = "points_in_boxes"
+    frames, keep = _stage_frames(torch, who, "lidar_snow_sim_amd.boxes.points_in_boxes", frames, keep)
+    rows, offsets, eng, dev, nf, n, keep = _stage_batch(torch, frames, keep, device, slot)
+    if not (torch.is_tensor(boxes) and boxes.dim() == 3 and boxes.shape[0] == nf and boxes.dtype == rows.dtype and boxes.device == dev and boxes.is_contiguous()):
+        raise ValueError("points_in_boxes: boxes must be a contiguous (frames, B, 7 .. 10) tensor in the rows' dtype on their device")
+    B, Cb = int(boxes.shape[1]), int(boxes.shape[2])
+    # (the shapes below need these; the entry refuses them in the same words, and everything else of the domain)
+    if not 1 <= B <= 256:
+        raise ValueError("points_in_boxes: n_boxes must lie in 1 .. 256 (boxes)")
+    if not 7 <= Cb <= 10:
+        raise ValueError("points_in_boxes: box_features must lie in 7 .. 10: cx, cy, cz, dx, dy, dz, heading first (boxes)")
+    if pose is not None and not (torch.is_tensor(pose) and tuple(pose.shape) == (nf, B, 2) and pose.dtype == torch.float64 and pose.device == dev and pose.is_contiguous()):
+        raise ValueError(f"points_in_boxes: pose must be a contiguous {(nf, B, 2)} float64 tensor (cos, sin) on the device of the rows")
+    want = (("box_of", torch.int32, (n,), True), ("count", torch.int32, (nf, B), return_count), ("local", rows.dtype, (n, 3), return_local),
+            ("pose", torch.float64, (nf, B, 2), return_pose))
+    if out is None:
+        out = BoxLabelBatch.empty(offsets, B, rows.dtype, dev, return_count, return_local, return_pose)
+    else:
+        _checked_out(torch, who, BoxLabelBatch, out, want, dev, _ROWS)
+    count, local, used = (out.count if return_count else None), (out.local if return_local else None), (out.pose if return_pose else None)
+    _stage_launch(torch, eng, dev, nf, n, offsets, rows, eng.ctx.points_in_boxes_device, B, boxes.data_ptr(), Cb, 0 if pose is None else pose.data_ptr(),
+                  0 if keep is None or not n else keep.data_ptr(), out.box_of.data_ptr() if n else 0, 0 if count is None else count.data_ptr(),
+                  0 if local is None or not n else local.data_ptr(), 0 if used is None else used.data_ptr())
+    same = (out.n_boxes == B and np.array_equal(out.offsets, np.asarray(offsets, np.int64)) and (count is None) == (out.count is None) and
+            (local is None) == (out.local is None) and (used is None) == (out.pose is None))
+    return out if same else BoxLabelBatch(out.box_of, count, local, used, offsets, B)
+
+
+IOU_MODES = {"bev": 0, "3d": 1}
+
+
+def _box_set(torch, who, name, boxes, limit, like=None):
+    """(F, B, Cb) of a box tensor after the checks the box entries share."""
+    if not (torch.is_tensor(boxes) and boxes.is_cuda and boxes.dim() == 3 and boxes.dtype in (torch.float32, torch.float64) and boxes.is_contiguous()):
+        raise ValueError(f"{who}: {name} must be a contiguous (frames, B, 7 .. 10) float32 or float64 CUDA tensor")
+    if like is not None and not (boxes.dtype == like.dtype and boxes.device == like.device and boxes.shape[0] == like.shape[0]):
+        raise ValueError(f"{who}: {name} must have the frames, the dtype and the device of the other boxes")
+    F, B, Cb = (int(v) for v in boxes.shape)
+    if F < 1 or not 1 <= B <= limit:
+        raise ValueError(f"{who}: the boxes per frame must lie in 1 .. {limit}, the frames be at least 1 ({name})")
+    if not 7 <= Cb <= 10:
+        raise ValueError(f"{who}: box_features must lie in 7 .. 10: cx, cy, cz, dx, dy, dz, heading first ({name})")
+    return F, B, Cb
+
+
+def _box_pose(torch, who, name, pose, boxes):
+    shape = tuple(boxes.shape[:2]) + (2,)
+    if pose is not None and not (torch.is_tensor(pose) and tuple(pose.shape) == shape and pose.dtype == torch.float64 and pose.device == boxes.device and pose.is_contiguous()):
+        raise ValueError(f"{who}: {name} must be a contiguous {shape} float64 tensor (cos, sin) on the device of the boxes")
+    return 0 if pose is None else pose.data_ptr()
+
+
+class IouBatch:
+    """What boxes_iou() leaves behind, F frames, M boxes a and B boxes b per frame -- every shape static: `iou` (F, M, B in the boxes' dtype:
+    the IoU of a_m with b_b, 0 where either is absent; None unless asked for), `best` (F, M int32: the smallest b with the largest IoU of
+    a_m if that IoU is > 0, else -1 -- the target layer's gt_assignment; None unless asked for) and `best_iou` (F, M: that IoU, 0 where best
+    is -1 -- max_overlaps).  All still being written until the stream the call was made on has caught up."""
+
+    def __init__(self, iou=None, best=None, best_iou=None):
+        self.iou, self.best, self.best_iou = iou, best, best_iou
+
+    @classmethod
+    def empty(cls, n_frames, n_a, n_b, dtype=None, device=None, with_iou=True, with_best=False):
+        """Uninitialised buffers of the shapes boxes_iou() writes (out=): static addresses for a captured graph."""
+        import torch
+        dev = _cuda_device(torch, device)
+        F, M, B, dt = int(n_frames), int(n_a), int(n_b), dtype or torch.float32
+        return cls(torch.empty((F, M, B), dtype=dt, device=dev) if with_iou else None, torch.empty((F, M), dtype=torch.int32, device=dev) if with_best else None,
+                   torch.empty((F, M), dtype=dt, device=dev) if with_best else None)
+
+
+def boxes_iou(boxes_a, boxes_b, *, mode='3d', pose_a=None, pose_b=None, out=None, return_iou=True, return_best=False, slot=0):
+    """The rotated IoU of every box of `boxes_a` with every box of `boxes_b` of its frame on the device (snowgpu_boxes_iou_device; the
+    definition: include/snowgpu.h): pcdet's boxes_iou3d_gpu (mode '3d') and boxes_iou_bev (mode 'bev') in float64 by clipping in a fixed
+    order, and the best partner of every box a without materialising the matrix.
+
+    boxes_a   a contiguous (F, M, 7 .. 10) float32 or float64 CUDA tensor, 1 <= M <= 9216: cx, cy, cz, dx, dy, dz, heading first (rois; the
+              `boxes` of an NmsBatch as they stand: zero rows are absent boxes).
+    boxes_b   (F, B, 7 .. 10) likewise, same dtype and device, 1 <= B <= 9216 (gt_boxes); F M B < 2^31.
+    pose_a, pose_b   None: cos / sin of the heading in float64 on the device; or contiguous (F, M, 2) / (F, B, 2) float64 tensors used as they are.
+    out       an IouBatch to write into (IouBatch.empty): every element is written.
+    return_iou, return_best   which outputs to compute; at least one.
+    The records of the boxes are scratch of the engine of `slot`, shared by nms() and boxes_iou(): calls made on streams that are not ordered
+    against each other (torch's default stream runs on a side stream of the engine) need a `slot` each.
+
+    Returns an IouBatch.  Asynchronous on torch's current stream; nothing is read on the host: capturable after one warm-up call."""
+    import torch
+    from . import engine as _engine
+    who = "boxes_iou"
+    F, M, Ca = _box_set(torch, who, "boxes_a", boxes_a, 9216)
+    _, B, Cb = _box_set(torch, who, "boxes_b", boxes_b, 9216, boxes_a)
+    if mode not in IOU_MODES:
+        raise ValueError(f"{who}: mode must be 'bev' or '3d'")
+    if not (return_iou or return_best):
+        raise ValueError(f"{who}: nothing to compute: return_iou or return_best")
+    if F * M * B > 2 ** 31 - 1:
+        raise ValueError(f"{who}: frames * M * B exceeds 2^31 - 1; split the batch")
+    dev, dt = boxes_a.device, boxes_a.dtype
+    pa, pb = _box_pose(torch, who, "pose_a", pose_a, boxes_a), _box_pose(torch, who, "pose_b", pose_b, boxes_b)
+    want = (("iou", dt, (F, M, B), return_iou), ("best", torch.int32, (F, M), return_best), ("best_iou", dt, (F, M), return_best))
+    if out is None:
+        out = IouBatch.empty(F, M, B, dt, dev, return_iou, return_best)
+    else:
+        _checked_out(torch, who, IouBatch, out, want, dev)
+    iou, best, best_iou = (out.iou if return_iou else None), (out.best if return_best else None), (out.best_iou if return_best else None)
+    eng = _engine.get_engine(dev.index, slot)
+    with torch.cuda.device(dev), _on_run_stream(torch, eng, dev) as (_, run):
+        eng.ctx.boxes_iou_device(F, M, boxes_a.data_ptr(), Ca, B, boxes_b.data_ptr(), Cb, 0 if dt == torch.float32 else 1, IOU_MODES[mode], pa, pb,
+                                 0 if iou is None else iou.data_ptr(), 0 if best is None else best.data_ptr(), 0 if best_iou is None else best_iou.data_ptr(),
+                                 run.cuda_stream)
+    same = (iou is None) == (out.iou is None) and (best is None) == (out.best is None)
+    return out if same else IouBatch(iou, best, best_iou)
+
+
+class NmsBatch:
+    """What nms() leaves behind, F frames of B boxes, P = post_max -- every shape static: `index` (F, P int32: the kept box numbers in rank
+    order, -1 behind the count), `count` (F int32), `boxes` (F, P, Cb in the boxes' dtype: the kept boxes with all their columns and ZERO
+    rows behind the count -- rois for sample_keypoints(rois=), boxes for points_in_boxes and boxes_iou as they stand; None unless asked
+    for), `scores` (F, P: their scores, 0 behind the count; None unless asked for) and `kept` (F, B uint8: 1 for a kept box; None unless
+    asked for).  All still being written until the stream the call was made on has caught up."""
+
+    def __init__(self, index, count, boxes=None, scores=None, kept=None):
+        self.index, self.count, self.boxes, self.scores, self.kept = index, count, boxes, scores, kept
+
+    @classmethod
+    def empty(cls, n_frames, n_boxes, post_max, box_features=7, dtype=None, device=None, with_boxes=True, with_scores=False, with_kept=False):
+        """Uninitialised buffers of the shapes nms() writes (out=): static addresses for a captured graph."""
+        import torch
+        dev = _cuda_device(torch, device)
+        F, B, P, dt = int(n_frames), int(n_boxes), int(post_max), dtype or torch.float32
+        return cls(torch.empty((F, P), dtype=torch.int32, device=dev), torch.empty(F, dtype=torch.int32, device=dev),
+                   torch.empty((F, P, int(box_features)), dtype=dt, device=dev) if with_boxes else None,
+                   torch.empty((F, P), dtype=dt, device=dev) if with_scores else None, torch.empty((F, B), dtype=torch.uint8, device=dev) if with_kept else None)
+
+
+def nms(boxes, scores, iou_thresh, *, post_max, score_thresh=-math.inf, mode='bev', pose=None, out=None, return_boxes=True, return_scores=False,
+        return_kept=False, slot=0):
+    """Class-agnostic rotated NMS per frame on the device (snowgpu_nms_device; the definition: include/snowgpu.h): pcdet's nms_gpu without
+    its host sweep.  The present boxes whose score is not NaN and is >= score_thresh are ranked by score (the smallest number first among
+    equals); a candidate is suppressed iff an already kept box has IoU > iou_thresh with it; the walk stops after post_max kept.
+
+    boxes     a contiguous (F, B, 7 .. 10) float32 or float64 CUDA tensor, 1 <= B <= 9216 (take torch.topk first, as pcdet does).
+    scores    a contiguous (F, B) tensor of the same dtype and device.
+    post_max  1 .. B: the static length of the keep list.
+    mode      'bev' (nms_gpu) or '3d'.
+    pose      None, or a contiguous (F, B, 2) float64 tensor (cos, sin) used as it is.
+    out       an NmsBatch to write into (NmsBatch.empty): every element is written.
+    The records of the boxes are scratch of the engine of `slot`, shared by nms() and boxes_iou(): calls made on streams that are not ordered
+    against each other (torch's default stream runs on a side stream of the engine) need a `slot` each.
+
+    Returns an NmsBatch.  Asynchronous on torch's current stream; nothing is read on the host: capturable after one warm-up call."""
+    import torch
+    from . import engine as _engine
+    who = "nms"
+    F, B, Cb = _box_set(torch, who, "boxes", boxes, 9216)
+    dev, dt = boxes.device, boxes.dtype
+    if not (torch.is_tensor(scores) and tuple(scores.shape) == (F, B) and scores.dtype == dt and scores.device == dev and scores.is_contiguous()):
+        raise ValueError(f"{who}: scores must be a contiguous {(F, B)} tensor in the boxes' dtype on their device")
+    if mode not in IOU_MODES:
+        raise ValueError(f"{who}: mode must be 'bev' or '3d'")
+    if isinstance(post_max, bool) or int(post_max) != post_max or not 1 <= int(post_max) <= B:
+        raise ValueError(f"{who}: post_max must be an integer in 1 .. B")
+    if math.isnan(float(iou_thresh)) or math.isnan(float(score_thresh)):
+        raise ValueError(f"{who}: a threshold is NaN")
+    P = int(post_max)
+    pp = _box_pose(torch, who, "pose", pose, boxes)
+    want = (("index", torch.int32, (F, P), True), ("count", torch.int32, (F,), True), ("boxes", dt, (F, P, Cb), return_boxes),
+            ("scores", dt, (F, P), return_scores), ("kept", torch.uint8, (F, B), return_kept))
+    if out is None:
+        out = NmsBatch.empty(F, B, P, Cb, dt, dev, return_boxes, return_scores, return_kept)
+    else:
+        _checked_out(torch, who, NmsBatch, out, want, dev)
+    kb, ks, kk = (out.boxes if return_boxes else None), (out.scores if return_scores else None), (out.kept if return_kept else None)
+    eng = _engine.get_engine(dev.index, slot)
+    with torch.cuda.device(dev), _on_run_stream(torch, eng, dev) as (_, run):
+        eng.ctx.nms_device(F, B, boxes.data_ptr(), Cb, scores.data_ptr(), 0 if dt == torch.float32 else 1, IOU_MODES[mode], float(iou_thresh), float(score_thresh),
+                           P, pp, out.index.data_ptr(), out.count.data_ptr(), 0 if kb is None else kb.data_ptr(), 0 if ks is None else ks.data_ptr(),
+                           0 if kk is None else kk.data_ptr(), run.cuda_stream)
+    same = (kb is None) == (out.boxes is None) and (ks is None) == (out.scores is None) and (kk is None) == (out.kept is None)
+    return out if same else NmsBatch(out.index, out.count, kb, ks, kk)

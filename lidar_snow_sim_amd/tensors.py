@@ -45,288 +45,24 @@ The reference's training-time caller (the OpenPCDet DENSE dataset: `root_path`, 
 What crosses the link per call: the frame offsets, the n_frames x n_lasers table ids and the planes (a few KB, cached by value: a
 training loop that reshuffles `order` per frame uploads 64 int32 per frame).  PyTorch is plumbing here -- device memory and streams;
 no arithmetic of the simulation happens in this file.
+
+This module is the import path of all of it and holds the augmentation entries.  How a batch is read and a result handed back lives in
+batch.py, the stages from `fov_keep` to `nms` with their result classes in stages.py; every public name of both is re-exported here.
 """
 from __future__ import annotations
 
-import math
 import os
 import random
-from collections import OrderedDict
 from contextlib import contextmanager
 
 import numpy as np
 
 from . import _native
-
-
-LANE_SLOT0 = 1000           # compute lane k is engine slot LANE_SLOT0 + k: lanes never share a context with plain calls (slot=)
-
-
-def is_device_input(frames) -> bool:
-    """True for a torch CUDA tensor, a DeviceBatch, or a non-empty sequence whose first element is a torch CUDA tensor."""
-    if isinstance(frames, DeviceBatch):
-        return True
-    t = frames
-    if isinstance(frames, (list, tuple)):
-        if not frames:
-            return False
-        t = frames[0]
-    return type(t).__module__.startswith("torch") and bool(getattr(t, "is_cuda", False))
-
-
-class DeviceBatch:
-    """Frames that lie back to back in ONE N_total x 5 CUDA tensor, with their (host) offsets -- the device twin of FlatBatch.
-    `frame_rows=n`: every frame has n rows (a stack of sweeps); else `offsets` (n_frames + 1, host integers)."""
-
-    def __init__(self, rows, offsets=None, frame_rows=None):
-        if rows.dim() == 3:                                    # F x N x 5
-            frame_rows = int(rows.shape[1])
-            rows = rows.reshape(-1, rows.shape[2])
-        if rows.dim() != 2 or rows.shape[1] != 5 or not rows.is_cuda or not rows.is_contiguous():
-            raise ValueError("a DeviceBatch is a contiguous N x 5 (or F x N x 5) CUDA tensor")
-        self.rows = rows
-        if offsets is None:
-            if not frame_rows or rows.shape[0] % int(frame_rows):
-                raise ValueError("give `offsets`, or `frame_rows` dividing the row count")
-            offsets = np.arange(rows.shape[0] // int(frame_rows) + 1, dtype=np.int64) * int(frame_rows)
-        self.offsets = np.ascontiguousarray(offsets, np.int64)
-        if self.offsets[0] != 0 or self.offsets[-1] > rows.shape[0] or np.any(np.diff(self.offsets) < 0):
-            raise ValueError("bad frame offsets")
-
-    def __len__(self):
-        return len(self.offsets) - 1
-
-
-class DeviceResult:
-    """What an asynchronous device call leaves behind: `rows` (N_total x 5; the first counts[f] rows of frame f's slot
-    [offsets[f], offsets[f + 1]) are its output), `src` (input row of every output row, frame-local), `counts` (n_frames, int64),
-    `stats` (n_frames x 3: num_attenuated, num_removed, avg_intensity_diff -- simulation.py:516-538), `status` (8 int32 words),
-    `flags` (fused wet ground: 1 where a frame had fewer than 1000 ground rows and came back as the snowfall result) -- all device
-    tensors, all still being written until the stream the call was made on has caught up."""
-
-    def __init__(self, ctx, rows, src, counts, stats, status, offsets, stream, flags=None, keep=()):
-        self.ctx, self.rows, self.src, self.counts, self.stats, self.status = ctx, rows, src, counts, stats, status
-        self.offsets, self.stream, self.flags = offsets, stream, flags
-        self._keep = keep                                      # inputs of the call: alive until the result has been waited for
-
-    def wait(self):
-        """Wait for the call, raise what the status words say (as the host entry does) and drop the references to the inputs."""
-        self.stream.synchronize()
-        st = self.status.cpu().numpy()
-        self._keep = ()
-        self.ctx.check_status(st)                              # SnowGPUError with the library's message
-        return self
-
-    def join(self, stream=None):
-        """torch's current stream (or `stream`) waits for the call; the host does not.  For results of a lane call (lane=k)."""
-        import torch
-        (stream or torch.cuda.current_stream(self.rows.device)).wait_stream(self.stream)
-        return self
-
-    def frames(self, return_src=False):
-        """The reference-shaped result: [(stats, aug_pc)] (or (stats, aug_pc, src)), aug_pc / src views of the result tensors."""
-        self.wait()
-        counts = self.counts.cpu().numpy()
-        stats = self.stats.cpu().numpy()
-        out = []
-        for i in range(len(self.offsets) - 1):
-            a, n = int(self.offsets[i]), int(counts[i])
-            st = (np.int64(stats[i, 0]), np.int64(stats[i, 1]), int(stats[i, 2]))
-            out.append((st, self.rows[a:a + n], self.src[a:a + n]) if return_src else (st, self.rows[a:a + n]))
-        return out
-
-
-class AlignedResult(DeviceResult):
-    """What a `layout='aligned'` call leaves behind: `rows` (N_total x 5, input dtype: row i is the output row of INPUT row i -- removed
-    rows too, as they stood before the reference drops them), `keep` (N_total, torch.bool: True where the reference returns the row),
-    `counts` (n_frames: flags set per frame), `stats`, `status`, `offsets` as in a DeviceResult.  Nothing here has a data-dependent
-    shape: `(rows[:, 3] * keep).sum()` and the like can follow on the same stream, or in the same captured graph, without the host."""
-
-    def __init__(self, ctx, rows, keep_mask, counts, stats, status, offsets, stream, keep=()):
-        super().__init__(ctx, rows, None, counts, stats, status, offsets, stream, keep=keep)
-        self.keep = keep_mask
-
-    def wait(self):
-        """DeviceResult.wait(), with the status words raised as the reference's exception types (IndexError for a point at >= 120 m,
-        TypeError for a frame without ground rows), as the synchronous call raises them."""
-        from .tools.snowfall.simulation import _raise_like_reference
-        try:
-            return super().wait()
-        except _native.SnowGPUError as err:
-            _raise_like_reference(err)
-
-    def frames(self):
-        """[(stats, rows_f, keep_f)] per frame, rows_f / keep_f views of the result tensors (waits, as DeviceResult.frames does)."""
-        self.wait()
-        stats = self.stats.cpu().numpy()
-        out = []
-        for i in range(len(self.offsets) - 1):
-            a, b = int(self.offsets[i]), int(self.offsets[i + 1])
-            out.append(((np.int64(stats[i, 0]), np.int64(stats[i, 1]), int(stats[i, 2])), self.rows[a:b], self.keep[a:b]))
-        return out
-
-
-class AlignedWetResult(AlignedResult):
-    """An AlignedResult of the wet-ground stage (wet_ground_batch_aligned, augment_wet_batch_aligned): `flags` (n_frames, int32) is 1 where
-    a frame had fewer than 1000 present ground rows and came back as it was (augmentation.py:51-52) and 2 where the wet stage was not
-    asked for the frame (augment_wet_batch_aligned(weather=...) with the frame's wet gate off); `counts` are the keep flags set after
-    the wet stage, `stats` the snowfall statistics (None for the wet-ground model on its own)."""
-
-    def __init__(self, ctx, rows, keep_mask, counts, stats, status, offsets, stream, flags, keep=()):
-        super().__init__(ctx, rows, keep_mask, counts, stats, status, offsets, stream, keep=keep)
-        self.flags = flags
-
-    def frames(self):
-        """[(stats, rows_f, keep_f, flag_f)] per frame, rows_f / keep_f views of the result tensors (waits)."""
-        self.wait()
-        stats = None if self.stats is None else self.stats.cpu().numpy()
-        flags = self.flags.cpu().numpy()
-        out = []
-        for i in range(len(self.offsets) - 1):
-            a, b = int(self.offsets[i]), int(self.offsets[i + 1])
-            st = None if stats is None else (np.int64(stats[i, 0]), np.int64(stats[i, 1]), int(stats[i, 2]))
-            out.append((st, self.rows[a:b], self.keep[a:b], int(flags[i])))
-        return out
-
-
-class _SmallUploads:
-    """Device copies of the small per-call arrays (offsets, table ids, planes, polynomials), by value: a few KB each, least
-    recently used first out."""
-
-    def __init__(self, cap=64):
-        self.cap, self.d = cap, OrderedDict()
-
-    def get(self, torch, dev, arr, user):
-        """The device copy of `arr`, safe to read on stream `user`: a copy made by an earlier call on another stream is waited for by event."""
-        key = (str(dev), arr.dtype.str, arr.shape, arr.tobytes())
-        hit = self.d.get(key)
-        if hit is None:
-            t = torch.from_numpy(np.ascontiguousarray(arr)).to(dev)                # (on torch's current stream)
-            ev = torch.cuda.Event()
-            ev.record(torch.cuda.current_stream(dev))
-            hit = self.d[key] = (t, ev)
-            while len(self.d) > self.cap:
-                self.d.popitem(last=False)
-        else:
-            self.d.move_to_end(key)
-            if torch.cuda.is_current_stream_capturing():
-                # The runtime refuses to query an event whose stream is capturing now -- that of a warm-up call made on the stream of the
-                # capture.  The copy was made before the capture began, and torch.cuda.graph synchronises the device when it begins.
-                return hit[0]
-        if not hit[1].query():
-            user.wait_event(hit[1])
-        return hit[0]
-
-
-def _uploads(eng):
-    u = eng.__dict__.get("_small_uploads")
-    if u is None:
-        u = eng.__dict__["_small_uploads"] = _SmallUploads()
-    return u
-
-
-def _as_batch(torch, frames):
-    """(rows N_total x 5 contiguous, host offsets, extras or None) from a DeviceBatch, an F x N x C tensor or a list of N_i x C tensors."""
-    if isinstance(frames, DeviceBatch):
-        return frames.rows, frames.offsets, None
-    if not isinstance(frames, (list, tuple)):
-        if frames.dim() == 3:
-            frames = list(frames.unbind(0))
-        else:
-            frames = [frames]
-    for f in frames:
-        if f.dim() != 2 or f.shape[1] < 5:
-            raise ValueError("pc must be N x 5 (x, y, z, intensity, channel)")
-        if f.dtype != frames[0].dtype or f.device != frames[0].device:
-            raise TypeError("all frames of a batch must share one dtype and device")
-    if frames[0].dtype not in (torch.float32, torch.float64):
-        frames = [f.to(torch.float64) for f in frames]
-    offsets = np.zeros(len(frames) + 1, np.int64)
-    offsets[1:] = np.cumsum([int(f.shape[0]) for f in frames])
-    extra = any(f.shape[1] > 5 for f in frames)
-    if len(frames) == 1 and frames[0].shape[1] == 5 and frames[0].is_contiguous():
-        rows = frames[0]                                                          # read in place
-    else:
-        rows = torch.cat([f[:, :5] for f in frames]).contiguous()                 # device-to-device; never through the host
-    return rows, offsets, (frames if extra else None)
-
-
-def _rows_where_they_lie(torch, frames):
-    """(rows, host offsets) of an input that is ALREADY one contiguous N_total x 5 float32 / float64 tensor -- a DeviceBatch, an F x N x 5
-    tensor, one N x 5 tensor (or a list of one) -- for in_place=True; anything that would have to be concatenated or converted raises."""
-    if isinstance(frames, DeviceBatch):
-        rows, offsets = frames.rows, frames.offsets
-    else:
-        t = frames[0] if isinstance(frames, (list, tuple)) and len(frames) == 1 else frames
-        if isinstance(t, (list, tuple)):
-            raise ValueError("in_place=True needs the frames in ONE tensor (a DeviceBatch, an F x N x 5 or an N x 5 tensor): a list is "
-                             "concatenated into a temporary, and the result would land there")
-        if t.dim() not in (2, 3) or t.shape[-1] != 5 or not t.is_contiguous():
-            raise ValueError("in_place=True needs a contiguous N x 5 or F x N x 5 tensor: the result is written over the input's five columns")
-        per = int(t.shape[-2])
-        offsets = np.arange((int(t.shape[0]) if t.dim() == 3 else 1) + 1, dtype=np.int64) * per
-        rows = t.reshape(-1, 5)
-    if rows.dtype not in (torch.float32, torch.float64):
-        raise ValueError("in_place=True needs float32 or float64 rows: other dtypes are converted into a temporary")
-    return rows, offsets
-
-
-def _run_stream(torch, eng, dev, stream, lane=None):
-    """The torch stream a call is launched on: the caller's `stream` itself, or -- for torch's legacy default stream (handle 0, which the C
-    ABI reads as "the context's own stream") and for a compute lane -- a side stream of the engine's, made on first use."""
-    if stream.cuda_stream != 0 and lane is None:
-        return stream
-    run = eng.__dict__.get("_torch_side_stream")
-    if run is None or run.device != dev:
-        if lane is not None:
-            # lanes k, k + 1, k + 2 on streams of three different priorities: three queue pools of the runtime, so three hardware
-            # queues whatever else the process has created (include/snowgpu.h: snowgpu_lane_stream)
-            many = int(os.environ.get("GPU_MAX_HW_QUEUES", "4") or 4) >= 16      # (then every stream has a queue anyway: one priority)
-            order = [int(v) for v in os.environ.get("SNOWGPU_LANE_LEVELS", "1" if many else "2,1,0").split(",")]
-            run = torch.cuda.ExternalStream(eng.ctx.lane_stream(order[int(lane) % len(order)]), device=dev)
-        else:
-            run = torch.cuda.Stream(device=dev)
-        eng.__dict__["_torch_side_stream"] = run
-    return run
-
-
-def _resolve_input(torch, frames, in_place, device, slot, lane=None):
-    """(rows, host offsets, extras or None, engine) of a call: the frames as one N_total x 5 tensor -- read where they lie for in_place --
-    on the device that `device` names if it names one, and the engine of `slot`, or of compute lane `lane`: an engine of its own whose
-    batches run on one stream (snowgpu_set_serial, once): they overlap OTHER lanes' batches, not their own side streams."""
-    from . import engine as _engine
-    rows, offsets, extras = _rows_where_they_lie(torch, frames) + (None,) if in_place else _as_batch(torch, frames)
-    dev = rows.device
-    if device is not None and int(device) != dev.index:
-        raise ValueError(f"the tensors live on {dev}, device={device} was asked for")
-    eng = _engine.get_engine(dev.index, slot if lane is None else LANE_SLOT0 + int(lane))
-    if lane is not None and not eng.__dict__.get("_lane_serial"):
-        eng.ctx.set_serial(True)      # (with GPU_MAX_HW_QUEUES >= 16 every lane's stream has a hardware queue of its own: include/snowgpu.h)
-        eng.__dict__["_lane_serial"] = True
-    return rows, offsets, extras, eng
-
-
-@contextmanager
-def _on_run_stream(torch, eng, dev, lane=None, used=()):
-    """(torch's current stream, the stream the call runs on) with the fork and the join around the body.  The C ABI reads stream = NULL as
-    "the context's own stream", which is not ordered against anything of torch's.  torch's legacy default stream HAS the handle 0, so a
-    call made on it runs on a side stream of the engine, forked from and joined back into the default stream (two event waits): work
-    queued before the call is seen, and whoever reads the results on the caller's stream afterwards -- or synchronises it -- waits for
-    the call.  A lane's stream forks alike and nothing waits for it (the result is claimed by wait() / join()); the tensors in `used`
-    are the caller's stream's, used on the lane's: the allocator must know."""
-    stream = torch.cuda.current_stream(dev)
-    run = _run_stream(torch, eng, dev, stream, lane)
-    if run is not stream:
-        run.wait_stream(stream)
-        if lane is not None:
-            for t in used:
-                if t is not None:
-                    t.record_stream(run)
-    try:
-        yield stream, run
-    finally:
-        if run is not stream and lane is None:
-            stream.wait_stream(run)
+from .batch import (LANE_SLOT0, AlignedResult, AlignedWetResult, DeviceBatch, DeviceResult, _cuda_device, _keep_mask, _on_run_stream,  # noqa: F401
+                    _resolve_input, _uploads, is_device_input)
+from .stages import (IOU_MODES, BoxLabelBatch, IouBatch, KeypointBatch, NearestBatch, NeighbourBatch, NmsBatch, RangeImageBatch, VoxelBatch,  # noqa: F401
+                     _fov_mask, ball_query, boxes_iou, dror_keep, fov_keep, nearest_keypoints, nms, points_in_boxes, range_image, sample_keypoints,
+                     voxelize)
 
 
 @contextmanager
@@ -421,7 +157,7 @@ def weather_records(n_frames, snow=True, wet=True, water_height=0.001, pavement_
     (all frames alike), a sequence of n_frames values or a tensor of them; snow and wet are truth values (the record holds 0.0 or 1.0)."""
     import torch
     nf = int(n_frames)
-    dev = torch.device("cuda", torch.cuda.current_device() if device is None else int(device)) if not isinstance(device, torch.device) else device
+    dev = _cuda_device(torch, device)
     rec = torch.zeros((nf, 8), dtype=torch.float64, device=dev)
     for col, (name, v) in enumerate((("snow", snow), ("wet", wet), ("water_height", water_height), ("pavement_depth", pavement_depth),
                                      ("noise_floor", noise_floor), ("power_factor", power_factor), ("delta", delta))):
@@ -465,9 +201,8 @@ class WeatherPlan:
         prefixes = [prefixes] if isinstance(prefixes, (str, bytes, os.PathLike)) else list(prefixes)
         if not prefixes:
             raise ValueError("WeatherPlan needs at least one prefix (one table set)")
-        index = torch.cuda.current_device() if device is None else (device.index if isinstance(device, torch.device) else int(device))
-        self.device = torch.device("cuda", index)
-        self.eng = _engine.get_engine(index, slot)
+        self.device = _cuda_device(torch, device)
+        self.eng = _engine.get_engine(self.device.index, slot)
         nl = self.eng.n_lasers
         if particles is not None and not isinstance(particles, str) and len(particles) != len(prefixes):
             raise ValueError("particles as arrays needs one sequence of tables per prefix")
@@ -495,1003 +230,6 @@ class WeatherPlan:
             self.eng.ctx.draw_weather_device(nf, nl, int(self.set_ids.shape[0]), self.set_ids.data_ptr(), self.struct, self.seed,
                                              self.step.data_ptr(), tids.data_ptr(), weather.data_ptr(), run.cuda_stream)
         return tids, weather
-
-
-def _keep_mask(torch, keep, rows, offsets):
-    """One contiguous torch.bool element per row of the batch from `keep`: an N_total tensor, an F x N tensor or a list of per-frame
-    tensors, torch.bool or uint8 (non-zero = present)."""
-    n = int(offsets[-1])
-    if isinstance(keep, (list, tuple)):
-        if len(keep) != len(offsets) - 1 or any(int(k.shape[0]) != int(b - a) or k.dim() != 1 for k, a, b in zip(keep, offsets[:-1], offsets[1:])):
-            raise ValueError("keep as a list needs one 1-D tensor per frame with one element per row of it")
-        if any(k.dtype != keep[0].dtype for k in keep):
-            raise ValueError("all keep tensors of a batch must share one dtype")
-        keep = torch.cat(list(keep)) if len(keep) != 1 else keep[0]
-    if not (type(keep).__module__.startswith("torch") and getattr(keep, "is_cuda", False)) or keep.device != rows.device:
-        raise ValueError("keep must be a CUDA tensor on the device of the rows (or a list of them)")
-    if keep.dtype not in (torch.bool, torch.uint8):
-        raise ValueError("keep must be torch.bool or uint8")
-    if keep.dim() == 2:
-        keep = keep.reshape(-1)
-    if keep.dim() != 1 or keep.shape[0] != n:
-        raise ValueError("keep must have one element per row of the batch (N_total, F x N, or a list of per-frame tensors)")
-    keep = keep.contiguous()
-    return keep.view(torch.bool) if keep.dtype == torch.uint8 else keep
-
-
-def _fov_mask(torch, eng, rows, calib, img_shape, keep, run):
-    """keep AND the camera-FOV test of every row, as a new torch.bool tensor, launched on torch stream `run` (k_fov_mask)."""
-    out = torch.empty(rows.shape[0], dtype=torch.bool, device=rows.device)
-    if rows.shape[0]:
-        eng.ctx.fov_mask_device(rows.shape[0], rows.data_ptr(), 0 if rows.dtype == torch.float32 else 1, calib, img_shape,
-                                0 if keep is None else keep.data_ptr(), out.data_ptr(), run.cuda_stream)
-    return out
-
-
-def fov_keep(frames, calib, img_shape=(1024, 1920), keep=None, *, device=None, slot=0):
-    """get_fov_flag(calib.lidar_to_rect(pc[:, 0:3]), img_shape, calib) (simulation.py:39-47) for torch CUDA tensors, on the device: a
-    torch.bool mask with one element per row of the batch (frames as augment_batch takes them), ANDed with `keep` if given -- the crop of
-    precompute.py:96-99 as a keep mask for augment_batch(..., layout='aligned', keep=mask) or any other consumer.  Asynchronous on
-    torch's current stream."""
-    if not is_device_input(frames):
-        raise ValueError("fov_keep: torch CUDA tensors (host arrays: lidar_snow_sim_amd.calibration.get_fov_flag)")
-    import torch
-    rows, offsets, _, eng = _resolve_input(torch, frames, False, device, slot)
-    if keep is not None:
-        keep = _keep_mask(torch, keep, rows, offsets)
-    with torch.cuda.device(rows.device), _on_run_stream(torch, eng, rows.device) as (_, run):
-        return _fov_mask(torch, eng, rows[:int(offsets[-1])], calib, img_shape, keep, run)
-
-
-def dror_keep(frames, alpha=0.45, beta=3, k_min=3, sr_min=0.04, keep=None, *, out=None, return_neighbours=False, device=None, slot=0):
-    """Dynamic radius outlier removal (DROR, Charron et al. 2018; pointcloud_viewer.py:2756-2758 with the defaults of :267-270) for torch
-    CUDA tensors, on the device: a torch.bool mask with one element per row of the batch (frames as augment_batch takes them), True where
-    the row is usable -- present under `keep`, every coordinate finite and within 1e6 m -- and has at least k_min other usable rows of its
-    frame within max(sr_min, beta * radians(alpha) * r_xy) of it (the definition: include/snowgpu.h, snowgpu_dror_mask_device).
-
-    frames    torch CUDA tensors, a DeviceBatch -- or an AlignedResult / AlignedWetResult: its rows, offsets and keep mask are used
-              (nothing is waited for), as voxelize and the stages behind it take one.
-    keep      an input keep mask as augment_batch(layout='aligned') takes it: an absent row is False, nobody's neighbour, never looked at
-              (with a result: ANDed with the result's own).
-    out       a torch.bool tensor with one element per row to write into (static addresses for a captured graph); not the `keep` tensor.
-    return_neighbours   also return an int32 tensor: every row's neighbours, counted up to k_min.
-
-    The mask goes straight into augment_batch(..., layout='aligned', keep=mask), augment_wet_batch_aligned(..., keep=mask) or
-    fov_keep(..., keep=mask); dror_keep(res) filters an augmented batch frame by frame.  dror_keep(res.rows, keep=res.keep) is NOT that
-    for a batch of several frames: one N_total x 5 tensor is ONE frame, and rows of different frames become each other's neighbours.
-    Asynchronous on torch's current stream."""
-    import math
-    import torch
-    if isinstance(frames, AlignedResult):
-        res = frames
-        own = res.keep if res.keep.dtype == torch.bool else res.keep.view(torch.bool)
-        frames = DeviceBatch(res.rows, res.offsets)
-        keep = own if keep is None else (_keep_mask(torch, keep, res.rows, res.offsets) & own)
-    if not is_device_input(frames):
-        raise ValueError("dror_keep: torch CUDA tensors or an aligned result (host arrays: lidar_snow_sim_amd.dror.dynamic_radius_outlier_filter)")
-    c = float(beta) * (float(alpha) * (math.pi / 180.0))
-    if not (0.0 < c <= 0.25):
-        raise ValueError("dror_keep: beta * radians(alpha) must lie in (0, 0.25]")
-    if not (float(sr_min) >= 0.0 and math.isfinite(float(sr_min))):
-        raise ValueError("dror_keep: sr_min must be finite and >= 0")
-    if int(k_min) != k_min or not (0 <= int(k_min) <= 65535):
-        raise ValueError("dror_keep: k_min must be an integer in 0 .. 65535")
-    rows, offsets, _, eng = _resolve_input(torch, frames, False, device, slot)
-    dev = rows.device
-    nf, n = len(offsets) - 1, int(offsets[-1])
-    if keep is not None:
-        keep = _keep_mask(torch, keep, rows, offsets)
-    if out is None:
-        out = torch.empty(n, dtype=torch.bool, device=dev)
-    elif not (torch.is_tensor(out) and out.dtype == torch.bool and out.dim() == 1 and out.shape[0] == n and out.is_contiguous() and out.device == dev):
-        raise ValueError("dror_keep: out must be a contiguous torch.bool tensor with one element per row, on the device of the rows")
-    if keep is not None and n and out.data_ptr() < keep.data_ptr() + n and keep.data_ptr() < out.data_ptr() + n:
-        raise ValueError("dror_keep: out must not be (or overlap) the keep tensor; the query of one row reads other rows' keep elements")
-    nb = torch.zeros(n, dtype=torch.int32, device=dev) if return_neighbours else None
-    if nf and n:
-        up = _uploads(eng)
-        with torch.cuda.device(dev), _on_run_stream(torch, eng, dev) as (_, run):
-            d_off = up.get(torch, dev, offsets, run)
-            eng.ctx.dror_mask_device(nf, n, int(np.diff(offsets).max()), d_off.data_ptr(), rows.data_ptr(), 0 if rows.dtype == torch.float32 else 1,
-                                     float(alpha), float(beta), float(sr_min), int(k_min), 0 if keep is None else keep.data_ptr(), out.data_ptr(),
-                                     0 if nb is None else nb.data_ptr(), run.cuda_stream)
-    return (out, nb) if return_neighbours else out
-
-
-class VoxelBatch:
-    """What voxelize() leaves behind, F = frames, V = max_voxels, T = max_points, C = num_features -- every shape static:
-    `voxels` (F V, T, C; the rows' dtype), `coords` (F V, 4 int32: frame, z, y, x cell), `num_points` (F V, int32), `voxel_offsets`
-    (F + 1 int32, ON THE DEVICE: frame f's voxels are [voxel_offsets[f], voxel_offsets[f + 1]), the packed voxels end at
-    voxel_offsets[F]; beyond it voxels are 0, coords -1, num_points 0) and `voxel_of` (N_total int32: every row's packed voxel, -1 without
-    one; None unless asked for).  All still being written until the stream the call was made on has caught up."""
-
-    def __init__(self, voxels, coords, num_points, voxel_offsets, voxel_of=None):
-        self.voxels, self.coords, self.num_points, self.voxel_offsets, self.voxel_of = voxels, coords, num_points, voxel_offsets, voxel_of
-
-    @classmethod
-    def empty(cls, n_frames, max_points, max_voxels, num_features=4, dtype=None, device=None, n_rows=None):
-        """Uninitialised buffers of the shapes voxelize() writes for such a call (out=): static addresses for a captured graph.
-        n_rows: also a `voxel_of` for a batch of that many rows."""
-        import torch
-        dev = torch.device("cuda", torch.cuda.current_device() if device is None else int(device)) if not isinstance(device, torch.device) else device
-        slots = int(n_frames) * int(max_voxels)
-        i32 = dict(dtype=torch.int32, device=dev)
-        return cls(torch.empty((slots, int(max_points), int(num_features)), dtype=dtype or torch.float32, device=dev), torch.empty((slots, 4), **i32),
-                   torch.empty(slots, **i32), torch.empty(int(n_frames) + 1, **i32), None if n_rows is None else torch.empty(int(n_rows), **i32))
-
-    def frames(self):
-        """[(voxels_f, coords_f, num_points_f)] per frame, trimmed views of the result tensors.  Reads the offsets: synchronizes."""
-        off = self.voxel_offsets.cpu().numpy()
-        return [(self.voxels[a:b], self.coords[a:b], self.num_points[a:b]) for a, b in zip(off[:-1].tolist(), off[1:].tolist())]
-
-
-def voxelize(frames, point_cloud_range, voxel_size, max_points, max_voxels, *, keep=None, num_features=4, out=None, return_voxel_of=False,
-             device=None, slot=0):
-    """Point-to-voxel grouping on the device (snowgpu_voxelize_device; the definition: include/snowgpu.h): the first operation of SECOND,
-    PV-RCNN and PointPillars, with static shapes.  Per frame, the rows that are present, finite and inside point_cloud_range
-    (x0, y0, z0, x1, y1, z1) are walked in input order; the first row of a new cell opens the frame's next voxel (cells beyond max_voxels
-    are dropped), and a voxel stores its first max_points rows, columns 0 .. num_features - 1, bit for bit.
-
-    frames    what dror_keep takes -- or an AlignedResult / AlignedWetResult: its rows, offsets and keep mask are used (nothing is waited for).
-    keep      an input keep mask as the aligned calls take it (with a result: ANDed with the result's own).
-    out       a VoxelBatch to write into (VoxelBatch.empty): every element is written, nothing needs clearing.
-    return_voxel_of   also fill `voxel_of`: every row's packed voxel index, -1 without one (dynamic voxelization's point-to-voxel map).
-
-    Returns a VoxelBatch.  Asynchronous on torch's current stream; nothing is read on the host: capturable after one warm-up call."""
-    import torch
-    if isinstance(frames, AlignedResult):
-        res = frames
-        own = res.keep if res.keep.dtype == torch.bool else res.keep.view(torch.bool)
-        frames = DeviceBatch(res.rows, res.offsets)
-        keep = own if keep is None else (_keep_mask(torch, keep, res.rows, res.offsets) & own)
-    if not is_device_input(frames):
-        raise ValueError("voxelize: torch CUDA tensors or an aligned result (host arrays: lidar_snow_sim_amd.voxel.points_to_voxels)")
-    for name, v in (("max_points", max_points), ("max_voxels", max_voxels), ("num_features", num_features)):
-        if isinstance(v, bool) or int(v) != v:
-            raise ValueError(f"voxelize: {name} must be an integer")
-    rng, size = np.asarray(point_cloud_range, np.float64).reshape(-1), np.asarray(voxel_size, np.float64).reshape(-1)
-    if rng.shape != (6,) or size.shape != (3,):
-        raise ValueError("voxelize: point_cloud_range holds 6 numbers (x0, y0, z0, x1, y1, z1), voxel_size 3")
-    rows, offsets, _, eng = _resolve_input(torch, frames, False, device, slot)
-    dev = rows.device
-    nf, n = len(offsets) - 1, int(offsets[-1])
-    T, V, C = int(max_points), int(max_voxels), int(num_features)
-    if keep is not None:
-        keep = _keep_mask(torch, keep, rows, offsets)
-    # (the shapes below need these three; the entry refuses them in the same words, and everything else of the domain)
-    if not 3 <= C <= 5:
-        raise ValueError("voxelize: n_features must be 3, 4 or 5: the columns of a row that a voxel stores")
-    if T < 1 or V < 1:
-        raise ValueError("voxelize: max_points and max_voxels must be at least 1")
-    if nf * V > 2 ** 31 - 1:
-        raise ValueError("voxelize: n_frames * max_voxels exceeds 2^31 - 1; split the batch")
-    if out is None:
-        out = VoxelBatch.empty(nf, T, V, C, rows.dtype, dev, n if return_voxel_of else None)
-    else:
-        want = (("voxels", (nf * V, T, C), rows.dtype), ("coords", (nf * V, 4), torch.int32), ("num_points", (nf * V,), torch.int32),
-                ("voxel_offsets", (nf + 1,), torch.int32)) + ((("voxel_of", (n,), torch.int32),) if return_voxel_of else ())
-        for name, shape, dtype in want:
-            t = getattr(out, name, None) if isinstance(out, VoxelBatch) else None
-            if not (torch.is_tensor(t) and tuple(t.shape) == shape and t.dtype == dtype and t.is_contiguous() and t.device == dev):
-                raise ValueError(f"voxelize: out must be a VoxelBatch whose {name} is a contiguous {tuple(shape)} {dtype} tensor on the device of the rows")
-    vof = out.voxel_of if return_voxel_of else None
-    if n == 0:                                          # no row: the entry writes the offsets alone
-        out.voxels.zero_(); out.coords.fill_(-1); out.num_points.zero_()
-    up = _uploads(eng)
-    with torch.cuda.device(dev), _on_run_stream(torch, eng, dev) as (_, run):
-        d_off = up.get(torch, dev, offsets, run)
-        eng.ctx.voxelize_device(nf, n, int(np.diff(offsets).max()), d_off.data_ptr(), rows.data_ptr() if n else 0, 0 if rows.dtype == torch.float32 else 1,
-                                rng, size, T, V, C, 0 if keep is None or not n else keep.data_ptr(), out.voxels.data_ptr(), out.coords.data_ptr(),
-                                out.num_points.data_ptr(), out.voxel_offsets.data_ptr(), 0 if vof is None or not n else vof.data_ptr(), run.cuda_stream)
-    return out if return_voxel_of or out.voxel_of is None else VoxelBatch(out.voxels, out.coords, out.num_points, out.voxel_offsets)
-
-
-class KeypointBatch:
-    """What sample_keypoints() leaves behind, F = frames, K = n_samples, C = num_features -- every shape static: `index` (F, K int32: the
-    sampled rows as indices into the whole batch, so rows[index] gathers; -1 for a frame without a usable row), `points` (F, K, C; the
-    rows' dtype; zero for such a frame), `usable` (F int32, ON THE DEVICE: the usable rows of every frame -- beyond them a frame's samples
-    repeat its first usable row) and `dist` (F, K; the rows' dtype: the squared distance of every sample to the samples before it at the
-    moment it was chosen, +inf for the first, -1 for a frame without a usable row; None unless asked for).  All still being written until
-    the stream the call was made on has caught up."""
-
-    def __init__(self, index, points, usable, dist=None, sector_offsets=None, sector_count=None, sector_of=None):
-        self.index, self.points, self.usable, self.dist = index, points, usable, dist
-        # set by the sectorized call alone (sample_keypoints(sectors=..., rois=...)): (F, S + 1) int32 -- slots [o_s, o_{s+1}) of a frame
-        # are its sector s, o_S = min(usable, K) --, (F, S) int32 -- the usable rows of every sector -- and, when asked for, (N) int8:
-        # every row's sector, -1 for an absent or unusable row
-        self.sector_offsets, self.sector_count, self.sector_of = sector_offsets, sector_count, sector_of
-
-    @classmethod
-    def empty(cls, n_frames, n_samples, num_features=4, dtype=None, device=None, with_dist=False, sectors=None, with_sector_of=None):
-        """Uninitialised buffers of the shapes sample_keypoints() writes for such a call (out=): static addresses for a captured graph.
-        sectors = S adds sector_offsets and sector_count, with_sector_of = the rows of the batch adds sector_of."""
-        import torch
-        dev = torch.device("cuda", torch.cuda.current_device() if device is None else int(device)) if not isinstance(device, torch.device) else device
-        F, K, dt = int(n_frames), int(n_samples), dtype or torch.float32
-        out = cls(torch.empty((F, K), dtype=torch.int32, device=dev), torch.empty((F, K, int(num_features)), dtype=dt, device=dev),
-                  torch.empty(F, dtype=torch.int32, device=dev), torch.empty((F, K), dtype=dt, device=dev) if with_dist else None)
-        if sectors is not None:
-            out.sector_offsets = torch.empty((F, int(sectors) + 1), dtype=torch.int32, device=dev)
-            out.sector_count = torch.empty((F, int(sectors)), dtype=torch.int32, device=dev)
-            if with_sector_of is not None and with_sector_of is not False:
-                out.sector_of = torch.empty(int(with_sector_of), dtype=torch.int8, device=dev)
-        return out
-
-
-def sample_keypoints(frames, n_samples, *, point_cloud_range=None, keep=None, num_features=4, out=None, return_dist=False, device=None, slot=0,
-                     sectors=None, rois=None, roi_margin=1.6, return_sector_of=False):
-    """Farthest point sampling on the device (snowgpu_fps_device; the definition: include/snowgpu.h): the keypoints of PV-RCNN and the
-    fixed-size point set of PointRCNN / Part-A2, with static shapes.  Per frame, among the rows that are present, within 1e6 of the origin
-    on every axis and inside point_cloud_range (x0, y0, z0, x1, y1, z1; None: no range), the first is taken, then n_samples - 1 times the
-    row farthest from everything taken so far (squared distance in the rows' dtype; the smallest row index among equals).
-
-    frames    what voxelize takes -- torch CUDA tensors, a DeviceBatch, or an AlignedResult / AlignedWetResult: its rows, offsets and keep
-              mask are used (nothing is waited for).
-    keep      an input keep mask as the aligned calls take it (with a result: ANDed with the result's own).
-    out       a KeypointBatch to write into (KeypointBatch.empty): every element is written, nothing needs clearing.
-    return_dist   also fill `dist`.
-    sectors, rois, roi_margin, return_sector_of
-              PV-RCNN++'s sectorized, proposal-centric sampling (snowgpu_fps_sectors_device): with rois -- an (F, B, 7 .. 10) device
-              tensor of the rows' dtype, OpenPCDet's rois / gt_boxes, zero rows are padding -- only the rows within a roi's half diagonal
-              + roi_margin of its centre are usable; the usable rows are split by azimuth into `sectors` sectors (1 .. 16; 1 when only
-              rois are given) and every sector is walked on its own for its share of n_samples.  The result carries sector_offsets and
-              sector_count, and with return_sector_of every row's sector.  With both None the plain walk runs, untouched.
-
-    Returns a KeypointBatch.  Asynchronous on torch's current stream; nothing is read on the host: capturable after one warm-up call."""
-    import torch
-    if sectors is not None or rois is not None:
-        return _sample_keypoints_sectors(torch, frames, n_samples, point_cloud_range, keep, num_features, out, return_dist, device, slot,
-                                         1 if sectors is None else sectors, rois, roi_margin, return_sector_of)
-    if isinstance(frames, AlignedResult):
-        res = frames
-        own = res.keep if res.keep.dtype == torch.bool else res.keep.view(torch.bool)
-        frames = DeviceBatch(res.rows, res.offsets)
-        keep = own if keep is None else (_keep_mask(torch, keep, res.rows, res.offsets) & own)
-    if not is_device_input(frames):
-        raise ValueError("sample_keypoints: torch CUDA tensors or an aligned result (host arrays: lidar_snow_sim_amd.fps.farthest_point_sample)")
-    for name, v in (("n_samples", n_samples), ("num_features", num_features)):
-        if isinstance(v, bool) or int(v) != v:
-            raise ValueError(f"sample_keypoints: {name} must be an integer")
-    rng = None
-    if point_cloud_range is not None:
-        rng = np.asarray(point_cloud_range, np.float64).reshape(-1)
-        if rng.shape != (6,):
-            raise ValueError("sample_keypoints: point_cloud_range holds 6 numbers (x0, y0, z0, x1, y1, z1)")
-    rows, offsets, _, eng = _resolve_input(torch, frames, False, device, slot)
-    dev = rows.device
-    nf, n = len(offsets) - 1, int(offsets[-1])
-    K, C = int(n_samples), int(num_features)
-    if keep is not None:
-        keep = _keep_mask(torch, keep, rows, offsets)
-    # (the shapes below need these; the entry refuses them in the same words, and everything else of the domain)
-    if not 3 <= C <= 5:
-        raise ValueError("sample_keypoints: n_features must be 3, 4 or 5: the columns of a row that a keypoint carries")
-    if K < 1:
-        raise ValueError("sample_keypoints: n_samples must be at least 1")
-    if nf * K > 2 ** 31 - 1:
-        raise ValueError("sample_keypoints: n_frames * n_samples exceeds 2^31 - 1; split the batch")
-    if out is None:
-        out = KeypointBatch.empty(nf, K, C, rows.dtype, dev, return_dist)
-    else:
-        want = (("index", (nf, K), torch.int32), ("points", (nf, K, C), rows.dtype), ("usable", (nf,), torch.int32)) + \
-               ((("dist", (nf, K), rows.dtype),) if return_dist else ())
-        for name, shape, dtype in want:
-            t = getattr(out, name, None) if isinstance(out, KeypointBatch) else None
-            if not (torch.is_tensor(t) and tuple(t.shape) == shape and t.dtype == dtype and t.is_contiguous() and t.device == dev):
-                raise ValueError(f"sample_keypoints: out must be a KeypointBatch whose {name} is a contiguous {tuple(shape)} {dtype} tensor on the device of the rows")
-    dist = out.dist if return_dist else None
-    up = _uploads(eng)
-    with torch.cuda.device(dev), _on_run_stream(torch, eng, dev) as (_, run):
-        d_off = up.get(torch, dev, offsets, run)
-        eng.ctx.fps_device(nf, n, int(np.diff(offsets).max()), d_off.data_ptr(), rows.data_ptr() if n else 0, 0 if rows.dtype == torch.float32 else 1,
-                           rng, K, C, 0 if keep is None or not n else keep.data_ptr(), out.index.data_ptr(), out.points.data_ptr(),
-                           0 if dist is None else dist.data_ptr(), out.usable.data_ptr(), run.cuda_stream)
-    return out if return_dist or out.dist is None else KeypointBatch(out.index, out.points, out.usable)
-
-
-def _sample_keypoints_sectors(torch, frames, n_samples, point_cloud_range, keep, num_features, out, return_dist, device, slot, sectors, rois, roi_margin,
-                              return_sector_of):
-    """sample_keypoints() with sectors or rois: snowgpu_fps_sectors_device."""
-    if isinstance(frames, AlignedResult):
-        res = frames
-        own = res.keep if res.keep.dtype == torch.bool else res.keep.view(torch.bool)
-        frames = DeviceBatch(res.rows, res.offsets)
-        keep = own if keep is None else (_keep_mask(torch, keep, res.rows, res.offsets) & own)
-    if not is_device_input(frames):
-        raise ValueError("sample_keypoints: torch CUDA tensors or an aligned result (host arrays: lidar_snow_sim_amd.fps.sectorized_sample)")
-    for name, v in (("n_samples", n_samples), ("num_features", num_features), ("sectors", sectors)):
-        if isinstance(v, bool) or int(v) != v:
-            raise ValueError(f"sample_keypoints: {name} must be an integer")
-    rng = None
-    if point_cloud_range is not None:
-        rng = np.asarray(point_cloud_range, np.float64).reshape(-1)
-        if rng.shape != (6,):
-            raise ValueError("sample_keypoints: point_cloud_range holds 6 numbers (x0, y0, z0, x1, y1, z1)")
-    rows, offsets, _, eng = _resolve_input(torch, frames, False, device, slot)
-    dev = rows.device
-    nf, n = len(offsets) - 1, int(offsets[-1])
-    K, C, S = int(n_samples), int(num_features), int(sectors)
-    if keep is not None:
-        keep = _keep_mask(torch, keep, rows, offsets)
-    # (the shapes below need these; the entry refuses them in the same words, and everything else of the domain)
-    if not 3 <= C <= 5:
-        raise ValueError("sample_keypoints: n_features must be 3, 4 or 5: the columns of a row that a keypoint carries")
-    if K < 1:
-        raise ValueError("sample_keypoints: n_samples must be at least 1")
-    if nf * K > 2 ** 31 - 1:
-        raise ValueError("sample_keypoints: n_frames * n_samples exceeds 2^31 - 1; split the batch")
-    if not 1 <= S <= 16:
-        raise ValueError("sample_keypoints: n_sectors must lie in 1 .. 16")
-    B = Cb = 0
-    if rois is not None:
-        if not (torch.is_tensor(rois) and rois.is_cuda and rois.device == dev and rois.dtype == rows.dtype and rois.dim() == 3 and rois.shape[0] == nf
-                and rois.is_contiguous()):
-            raise ValueError("sample_keypoints: rois must be a contiguous (frames, B, 7 .. 10) tensor of the rows' dtype on the device of the rows")
-        B, Cb = int(rois.shape[1]), int(rois.shape[2])
-    if out is None:
-        out = KeypointBatch.empty(nf, K, C, rows.dtype, dev, return_dist, S, n if return_sector_of else None)
-    else:
-        want = (("index", (nf, K), torch.int32), ("points", (nf, K, C), rows.dtype), ("usable", (nf,), torch.int32),
-                ("sector_offsets", (nf, S + 1), torch.int32), ("sector_count", (nf, S), torch.int32)) + \
-               ((("dist", (nf, K), rows.dtype),) if return_dist else ()) + ((("sector_of", (n,), torch.int8),) if return_sector_of else ())
-        for name, shape, dtype in want:
-            t = getattr(out, name, None) if isinstance(out, KeypointBatch) else None
-            if not (torch.is_tensor(t) and tuple(t.shape) == shape and t.dtype == dtype and t.is_contiguous() and t.device == dev):
-                raise ValueError(f"sample_keypoints: out must be a KeypointBatch whose {name} is a contiguous {tuple(shape)} {dtype} tensor on the device of the rows")
-    dist = out.dist if return_dist else None
-    sof = out.sector_of if return_sector_of else None
-    up = _uploads(eng)
-    with torch.cuda.device(dev), _on_run_stream(torch, eng, dev) as (_, run):
-        d_off = up.get(torch, dev, offsets, run)
-        eng.ctx.fps_sectors_device(nf, n, int(np.diff(offsets).max()), d_off.data_ptr(), rows.data_ptr() if n else 0, 0 if rows.dtype == torch.float32 else 1,
-                                   rng, K, C, 0 if keep is None or not n else keep.data_ptr(), S, 0 if rois is None else rois.data_ptr(), B, Cb,
-                                   roi_margin, out.index.data_ptr(), out.points.data_ptr(), 0 if dist is None else dist.data_ptr(), out.usable.data_ptr(),
-                                   out.sector_offsets.data_ptr(), out.sector_count.data_ptr(), 0 if sof is None or not n else sof.data_ptr(), 0,
-                                   run.cuda_stream)
-    if (dist is None) == (out.dist is None) and (sof is None) == (out.sector_of is None):
-        return out
-    return KeypointBatch(out.index, out.points, out.usable, dist, out.sector_offsets, out.sector_count, sof)      # (without what was not asked for)
-
-
-class NeighbourBatch:
-    """What ball_query() leaves behind, F = frames, K = centres per frame, R = (radius, samples) pairs, S = the sum of their samples,
-    C = num_features -- every shape static: `index` (F, K, S int32: per centre the segments of the R pairs side by side, each the smallest
-    row indices of the ball, ascending, as indices into the whole batch, padded with its first; -1 for an empty ball), `count` (F, K, R
-    int32: the rows in every ball, not saturated), `points` (F, K, S, C; the rows' dtype; zero where the index is -1; None unless asked
-    for) and `segments` (the samples of every pair, a tuple: index[..., sum(segments[:i]):sum(segments[:i + 1])] is pair i).  All still
-    being written until the stream the call was made on has caught up."""
-
-    def __init__(self, index, count, points=None, segments=()):
-        self.index, self.count, self.points, self.segments = index, count, points, tuple(int(s) for s in segments)
-
-    @classmethod
-    def empty(cls, n_frames, n_centres, n_neighbours, num_features=4, dtype=None, device=None, with_points=False):
-        """Uninitialised buffers of the shapes ball_query() writes for such a call (out=): static addresses for a captured graph."""
-        import torch
-        dev = torch.device("cuda", torch.cuda.current_device() if device is None else int(device)) if not isinstance(device, torch.device) else device
-        seg = tuple(int(s) for s in (n_neighbours if isinstance(n_neighbours, (tuple, list, np.ndarray)) else (n_neighbours,)))
-        F, K, S = int(n_frames), int(n_centres), sum(seg)
-        return cls(torch.empty((F, K, S), dtype=torch.int32, device=dev), torch.empty((F, K, len(seg)), dtype=torch.int32, device=dev),
-                   torch.empty((F, K, S, int(num_features)), dtype=dtype or torch.float32, device=dev) if with_points else None, seg)
-
-
-def ball_query(frames, centres, radius, n_neighbours, *, point_cloud_range=None, keep=None, num_features=4, out=None, return_points=False,
-               device=None, slot=0):
-    """Ball-query neighbour groups on the device (snowgpu_ball_query_device; the definition: include/snowgpu.h): for every centre the
-    n_neighbours smallest row indices of its frame among the rows that are present, within 1e6 of the origin on every axis, inside
-    point_cloud_range (None: no range) and STRICTLY within `radius` of the centre (squared distance in the rows' dtype), ascending and
-    padded with the first -- what the pointnet2 ball_query op returns --, -1 for an empty ball, and the full number of rows in the ball.
-
-    frames    what sample_keypoints takes -- torch CUDA tensors, a DeviceBatch, or an AlignedResult / AlignedWetResult: its rows, offsets
-              and keep mask are used (nothing is waited for).
-    centres   a KeypointBatch (its points), or an (F, K, 3 .. 5) tensor in the rows' dtype on their device: x, y, z first.
-    radius, n_neighbours   scalars, or sequences of equal length <= 4: several balls per centre from one walk, side by side in `index`.
-    keep      an input keep mask as the aligned calls take it (with a result: ANDed with the result's own).
-    out       a NeighbourBatch to write into (NeighbourBatch.empty): every element is written, nothing needs clearing.
-    return_points   also fill `points` with the first num_features columns of the indexed rows.
-
-    Returns a NeighbourBatch.  Asynchronous on torch's current stream; nothing is read on the host: capturable after one warm-up call."""
-    import torch
-    if isinstance(frames, AlignedResult):
-        res = frames
-        own = res.keep if res.keep.dtype == torch.bool else res.keep.view(torch.bool)
-        frames = DeviceBatch(res.rows, res.offsets)
-        keep = own if keep is None else (_keep_mask(torch, keep, res.rows, res.offsets) & own)
-    if not is_device_input(frames):
-        raise ValueError("ball_query: torch CUDA tensors or an aligned result (host arrays: lidar_snow_sim_amd.ball.ball_query)")
-    seq = lambda v: list(v) if isinstance(v, (tuple, list, np.ndarray)) else [v]
-    radii, seg = seq(radius), seq(n_neighbours)
-    if len(radii) != len(seg):
-        raise ValueError("ball_query: as many radii as sample counts")
-    for name, v in (("num_features", num_features),) + tuple(("n_neighbours", s) for s in seg):
-        if isinstance(v, bool) or int(v) != v:
-            raise ValueError(f"ball_query: {name} must be an integer")
-    rng = None
-    if point_cloud_range is not None:
-        rng = np.asarray(point_cloud_range, np.float64).reshape(-1)
-        if rng.shape != (6,):
-            raise ValueError("ball_query: point_cloud_range holds 6 numbers (x0, y0, z0, x1, y1, z1)")
-    rows, offsets, _, eng = _resolve_input(torch, frames, False, device, slot)
-    dev = rows.device
-    nf, n = len(offsets) - 1, int(offsets[-1])
-    if keep is not None:
-        keep = _keep_mask(torch, keep, rows, offsets)
-    cen = centres.points if isinstance(centres, KeypointBatch) else centres
-    if not (torch.is_tensor(cen) and cen.dim() == 3 and cen.shape[0] == nf and cen.dtype == rows.dtype and cen.device == dev and cen.is_contiguous()):
-        raise ValueError("ball_query: centres must be a KeypointBatch or a contiguous (frames, K, 3 .. 5) tensor in the rows' dtype on their device")
-    K, Cq, C, R = int(cen.shape[1]), int(cen.shape[2]), int(num_features), len(radii)
-    seg = [int(s) for s in seg]
-    # (the shapes below need these; the entry refuses them in the same words, and everything else of the domain)
-    if not 3 <= C <= 5:
-        raise ValueError("ball_query: n_features must be 3, 4 or 5: the columns of a row that a neighbour carries")
-    if not 3 <= Cq <= 5:
-        raise ValueError("ball_query: centre_features must be 3, 4 or 5: x, y, z first")
-    if K < 1:
-        raise ValueError("ball_query: n_centres must be at least 1")
-    if not 1 <= R <= 4:
-        raise ValueError("ball_query: n_radii must lie in 1 .. 4")
-    if any(not 1 <= s <= 64 for s in seg):
-        raise ValueError("ball_query: the samples of a radius must lie in 1 .. 64")
-    S = sum(seg)
-    if nf * K * S > 2 ** 31 - 1:
-        raise ValueError("ball_query: n_frames * n_centres * samples exceeds 2^31 - 1; split the batch")
-    if out is None:
-        out = NeighbourBatch.empty(nf, K, seg, C, rows.dtype, dev, return_points)
-    else:
-        want = (("index", (nf, K, S), torch.int32), ("count", (nf, K, R), torch.int32)) + ((("points", (nf, K, S, C), rows.dtype),) if return_points else ())
-        for name, shape, dtype in want:
-            t = getattr(out, name, None) if isinstance(out, NeighbourBatch) else None
-            if not (torch.is_tensor(t) and tuple(t.shape) == shape and t.dtype == dtype and t.is_contiguous() and t.device == dev):
-                raise ValueError(f"ball_query: out must be a NeighbourBatch whose {name} is a contiguous {tuple(shape)} {dtype} tensor on the device of the rows")
-    points = out.points if return_points else None
-    up = _uploads(eng)
-    with torch.cuda.device(dev), _on_run_stream(torch, eng, dev) as (_, run):
-        d_off = up.get(torch, dev, offsets, run)
-        eng.ctx.ball_query_device(nf, n, int(np.diff(offsets).max()), d_off.data_ptr(), rows.data_ptr() if n else 0, 0 if rows.dtype == torch.float32 else 1,
-                                  rng, K, cen.data_ptr(), Cq, radii, seg, C, 0 if keep is None or not n else keep.data_ptr(), out.index.data_ptr(),
-                                  out.count.data_ptr(), 0 if points is None else points.data_ptr(), run.cuda_stream)
-    return NeighbourBatch(out.index, out.count, points, seg) if (out.segments != tuple(seg) or (points is None) != (out.points is None)) else out
-
-
-class RangeImageBatch:
-    """What range_image() leaves behind, F = frames, H x W the image, C = num_features -- every shape static: `image` (F, 1 + C, H, W; the
-    rows' dtype: plane 0 the range of the pixel's nearest row, planes 1 .. C its columns 0 .. C - 1, bit for bit; -1 in an empty pixel),
-    `index` (F, H, W int32: that row as an index into the whole batch, so rows[index] gathers; -1 in an empty pixel), `pixel_of` (N_total
-    int32: every row's flat pixel f H W + row W + col, whether it won or not; -1 for absent and unusable rows) and `count` (F, H, W int32:
-    the usable rows that fell in the pixel; None unless asked for).  All still being written until the stream the call was made on has
-    caught up."""
-
-    def __init__(self, image, index, pixel_of, count=None):
-        self.image, self.index, self.pixel_of, self.count = image, index, pixel_of, count
-
-    @classmethod
-    def empty(cls, n_frames, height, width, n_rows, num_features=4, dtype=None, device=None, with_count=False):
-        """Uninitialised buffers of the shapes range_image() writes for such a call on a batch of n_rows rows (out=): static addresses
-        for a captured graph."""
-        import torch
-        dev = torch.device("cuda", torch.cuda.current_device() if device is None else int(device)) if not isinstance(device, torch.device) else device
-        F, H, W = int(n_frames), int(height), int(width)
-        i32 = dict(dtype=torch.int32, device=dev)
-        return cls(torch.empty((F, 1 + int(num_features), H, W), dtype=dtype or torch.float32, device=dev), torch.empty((F, H, W), **i32),
-                   torch.empty(int(n_rows), **i32), torch.empty((F, H, W), **i32) if with_count else None)
-
-    def to_rows(self, values, fill=0):
-        """The way back: a per-pixel tensor (F, H, W) or (F, X, H, W) -- a de-noiser's keep or class map -- as a per-row tensor (N,) or
-        (N, X): every row gets the value of its pixel, `fill` where pixel_of is -1.  Pure indexing on the device, nothing is read on
-        the host: a predicted mask goes straight into augment_batch(..., keep=) or dror_keep(..., keep=)."""
-        import torch
-        F, H, W = self.index.shape
-        if not (torch.is_tensor(values) and values.dim() in (3, 4) and values.shape[0] == F and tuple(values.shape[-2:]) == (H, W)):
-            raise ValueError(f"to_rows: values must be a ({F}, {H}, {W}) or ({F}, X, {H}, {W}) tensor: one value, or X of them, per pixel")
-        p = self.pixel_of.long()
-        at = p.clamp(min=0)
-        if values.dim() == 3:
-            got = values.reshape(-1)[at]
-            return torch.where(p >= 0, got, torch.full_like(got, fill))
-        f = torch.div(at, H * W, rounding_mode="floor")
-        got = values.reshape(F, values.shape[1], H * W)[f, :, at - f * (H * W)]
-        return torch.where((p >= 0)[:, None], got, torch.full_like(got, fill))
-
-
-def range_image(frames, height, width, *, fov_up=3.0, fov_down=-25.0, ring=None, range_limits=(0.0, float("inf")), keep=None, num_features=4,
-                out=None, return_count=False, device=None, slot=0):
-    """Range-image projection on the device (snowgpu_range_image_device; the definition: include/snowgpu.h): every frame as a height x
-    width image of its nearest returns, the input of the range-view networks (RangeNet++, SalsaNext) and of the snow de-noisers
-    (WeatherNet, 4DenoiseNet, LiSnowNet), with static shapes.  The column is the azimuth, the image row the elevation between fov_down and
-    fov_up (DEGREES, as the RangeNet++ configs give them; rows beyond are clamped to the first and last image row) -- or, with `ring`,
-    the row's laser channel.  Per pixel the usable row (present, within 1e6 of the origin on every axis, range strictly inside
-    range_limits) with the smallest range wins, the smallest row index among equals.
-
-    frames    what voxelize takes -- torch CUDA tensors, a DeviceBatch, or an AlignedResult / AlignedWetResult: its rows, offsets and keep
-              mask are used (nothing is waited for).
-    ring      an int32 CUDA tensor with one image row per row of the batch, e.g. the INPUT's column 4 as int32 beside an aligned result (a
-              scattered row moves along its own beam and keeps its channel); rows whose ring is outside 0 .. height - 1 are unusable.
-    keep      an input keep mask as the aligned calls take it (with a result: ANDed with the result's own).
-    out       a RangeImageBatch to write into (RangeImageBatch.empty): every element is written, nothing needs clearing.
-    return_count   also fill `count`.
-
-    Returns a RangeImageBatch; its to_rows() carries a per-pixel prediction back to the rows.  Asynchronous on torch's current stream;
-    nothing is read on the host: capturable after one warm-up call."""
-    import torch
-    if isinstance(frames, AlignedResult):
-        res = frames
-        own = res.keep if res.keep.dtype == torch.bool else res.keep.view(torch.bool)
-        frames = DeviceBatch(res.rows, res.offsets)
-        keep = own if keep is None else (_keep_mask(torch, keep, res.rows, res.offsets) & own)
-    if not is_device_input(frames):
-        raise ValueError("range_image: torch CUDA tensors or an aligned result (host arrays: lidar_snow_sim_amd.range_image.project)")
-    for name, v in (("height", height), ("width", width), ("num_features", num_features)):
-        if isinstance(v, bool) or int(v) != v:
-            raise ValueError(f"range_image: {name} must be an integer")
-    limits = np.asarray(range_limits, np.float64).reshape(-1)
-    if limits.shape != (2,):
-        raise ValueError("range_image: range_limits holds 2 numbers (lo, hi)")
-    rows, offsets, _, eng = _resolve_input(torch, frames, False, device, slot)
-    dev = rows.device
-    nf, n = len(offsets) - 1, int(offsets[-1])
-    H, W, C = int(height), int(width), int(num_features)
-    if keep is not None:
-        keep = _keep_mask(torch, keep, rows, offsets)
-    if ring is not None and not (torch.is_tensor(ring) and ring.dtype == torch.int32 and ring.dim() == 1 and ring.shape[0] == n and ring.device == dev and
-                                 ring.is_contiguous()):
-        raise ValueError("range_image: ring must be a contiguous int32 tensor with one element per row of the batch, on the device of the rows")
-    # (the shapes below need these; the entry refuses them in the same words, and everything else of the domain)
-    if not 3 <= C <= 5:
-        raise ValueError("range_image: n_features must be 3, 4 or 5: the columns of a row that a pixel stores")
-    if H < 1 or W < 1:
-        raise ValueError("range_image: height and width must be at least 1")
-    if nf * H * W > 2 ** 31 - 1:
-        raise ValueError("range_image: n_frames * height * width exceeds 2^31 - 1; split the batch")
-    if out is None:
-        out = RangeImageBatch.empty(nf, H, W, n, C, rows.dtype, dev, return_count)
-    else:
-        want = (("image", (nf, 1 + C, H, W), rows.dtype), ("index", (nf, H, W), torch.int32), ("pixel_of", (n,), torch.int32)) + \
-               ((("count", (nf, H, W), torch.int32),) if return_count else ())
-        for name, shape, dtype in want:
-            t = getattr(out, name, None) if isinstance(out, RangeImageBatch) else None
-            if not (torch.is_tensor(t) and tuple(t.shape) == shape and t.dtype == dtype and t.is_contiguous() and t.device == dev):
-                raise ValueError(f"range_image: out must be a RangeImageBatch whose {name} is a contiguous {tuple(shape)} {dtype} tensor on the device of the rows")
-    count = out.count if return_count else None
-    by_ring = ring is not None and n > 0          # (without a row there is no channel to read: either mode writes the empty image)
-    fov = None if by_ring else np.radians(np.array([fov_up, fov_down], np.float64))
-    up = _uploads(eng)
-    with torch.cuda.device(dev), _on_run_stream(torch, eng, dev) as (_, run):
-        d_off = up.get(torch, dev, offsets, run)
-        eng.ctx.range_image_device(nf, n, int(np.diff(offsets).max()), d_off.data_ptr(), rows.data_ptr() if n else 0, 0 if rows.dtype == torch.float32 else 1,
-                                   H, W, fov, ring.data_ptr() if by_ring else 0, limits, C, 0 if keep is None or not n else keep.data_ptr(),
-                                   out.image.data_ptr(), out.index.data_ptr(), out.pixel_of.data_ptr() if n else 0, 0 if count is None else count.data_ptr(),
-                                   run.cuda_stream)
-    return out if return_count or out.count is None else RangeImageBatch(out.image, out.index, out.pixel_of)
-
-
-class NearestBatch:
-    """What nearest_keypoints() leaves behind, N = rows of the batch, k = neighbours, K = centres per frame -- every shape static: `index`
-    (N, k int32: per row its k nearest usable centres of its frame by (squared distance, centre number), as centre numbers 0 .. K - 1
-    WITHIN THE FRAME; -1 in a slot beyond the frame's usable centres and in every slot of an absent or unusable row), `dist2` (N, k; the
-    rows' dtype; +inf where the index is -1) and `weight` (N, k; the rows' dtype: pointnet2's normalised 1 / (dist + 1e-8); 0 where the
-    index is -1; None unless asked for).  `offsets` (host) and `n_centres` say which frame a row belongs to and how many centres a frame
-    has: flat_index(), interpolate() and nearest() are the way back from per-keypoint values to the rows -- pure indexing, no kernel of
-    this library.  All still being written until the stream the call was made on has caught up."""
-
-    def __init__(self, index, dist2, weight=None, offsets=None, n_centres=0):
-        self.index, self.dist2, self.weight, self.n_centres = index, dist2, weight, int(n_centres)
-        self.offsets = np.array([0, index.shape[0]], np.int64) if offsets is None else np.asarray(offsets, np.int64)
-        self._base = None
-
-    @classmethod
-    def empty(cls, offsets, n_centres, k=3, dtype=None, device=None, with_weights=True):
-        """Uninitialised buffers of the shapes nearest_keypoints() writes for a batch with these frame offsets (or, for one frame, this
-        number of rows) (out=): static addresses for a captured graph."""
-        import torch
-        dev = torch.device("cuda", torch.cuda.current_device() if device is None else int(device)) if not isinstance(device, torch.device) else device
-        off = np.array([0, int(offsets)], np.int64) if np.ndim(offsets) == 0 else np.asarray(offsets, np.int64)
-        n, dt = int(off[-1]), dtype or torch.float32
-        return cls(torch.empty((n, int(k)), dtype=torch.int32, device=dev), torch.empty((n, int(k)), dtype=dt, device=dev),
-                   torch.empty((n, int(k)), dtype=dt, device=dev) if with_weights else None, off, n_centres)
-
-    def flat_index(self):
-        """index + frame * K, -1 kept (N, k int64): gathers from per-keypoint values flattened to (F K, ...).  The first call of a batch of
-        several frames uploads their row counts (a few bytes; make it before capturing a graph); later calls reuse the result."""
-        import torch
-        idx = self.index.long()
-        if len(self.offsets) <= 2:
-            return idx
-        if self._base is None:
-            counts = torch.from_numpy(np.diff(self.offsets)).to(idx.device)
-            first = torch.arange(len(counts), device=idx.device) * self.n_centres
-            self._base = torch.repeat_interleave(first, counts, output_size=int(self.offsets[-1]))[:, None]
-        return torch.where(idx >= 0, idx + self._base, idx)
-
-    def _values(self, values, what):
-        import torch
-        F, K = len(self.offsets) - 1, self.n_centres
-        if not (torch.is_tensor(values) and values.dim() in (2, 3) and tuple(values.shape[:2]) == (F, K) and values.device == self.index.device):
-            raise ValueError(f"{what}: values must be a ({F}, {K}) or ({F}, {K}, D) tensor on the device of the rows: one value, or D of them, per keypoint")
-        return values.reshape(F * K, -1) if values.dim() == 3 else values.reshape(F * K)
-
-    def interpolate(self, features):
-        """three_interpolate: per-keypoint features (F, K, D) or (F, K) as per-row features (N, D) or (N,): the sum over the slots of
-        weight * features[index], in the features' dtype.  A row without a neighbour gets 0."""
-        if self.weight is None:
-            raise ValueError("interpolate: this NearestBatch has no weights (nearest_keypoints(..., return_weights=True))")
-        flat = self._values(features, "interpolate")
-        at = self.flat_index().clamp(min=0)               # (the weight of a -1 slot is 0)
-        w = self.weight.to(flat.dtype)
-        return (flat[at] * (w[..., None] if flat.dim() == 2 else w)).sum(dim=1)
-
-    def nearest(self, values, default=0):
-        """Voronoi labelling: every row gets the value of its nearest keypoint (slot 0) from per-keypoint values (F, K) or (F, K, D) --
-        a keypoint-level keep decision becomes a per-row mask for augment_batch(..., keep=) or dror_keep(..., keep=); `default` for a
-        row without a neighbour."""
-        import torch
-        flat = self._values(values, "nearest")
-        first = self.flat_index()[:, 0]
-        got = flat[first.clamp(min=0)]
-        has = first >= 0
-        return torch.where(has[:, None] if got.dim() == 2 else has, got, torch.full_like(got, default))
-
-
-def nearest_keypoints(frames, centres, k=3, *, point_cloud_range=None, keep=None, out=None, return_weights=True, device=None, slot=0):
-    """The k nearest centres of every row on the device (snowgpu_nearest_centres_device; the definition: include/snowgpu.h): pointnet2's
-    three_nn with its interpolation weights, the way back from keypoints to the rows of the batch.  A row takes part if it is present,
-    within 1e6 of the origin on every axis and inside point_cloud_range (None: no range); its neighbours are the usable centres of its
-    frame in the order of (squared distance in the rows' dtype, centre number).
-
-    frames    what ball_query takes -- torch CUDA tensors, a DeviceBatch, or an AlignedResult / AlignedWetResult: its rows, offsets and
-              keep mask are used (nothing is waited for).
-    centres   a KeypointBatch (its points), or an (F, K, 3 .. 5) tensor in the rows' dtype on their device: x, y, z first.
-    k         1 .. 8 neighbours per row.
-    keep      an input keep mask as the aligned calls take it (with a result: ANDed with the result's own).
-    out       a NearestBatch to write into (NearestBatch.empty): every element is written, nothing needs clearing.
-    return_weights   also fill `weight`.
-
-    Returns a NearestBatch; its interpolate() and nearest() carry per-keypoint values back to the rows.  Asynchronous on torch's current
-    stream; nothing is read on the host: capturable after one warm-up call."""
-    import torch
-    if isinstance(frames, AlignedResult):
-        res = frames
-        own = res.keep if res.keep.dtype == torch.bool else res.keep.view(torch.bool)
-        frames = DeviceBatch(res.rows, res.offsets)
-        keep = own if keep is None else (_keep_mask(torch, keep, res.rows, res.offsets) & own)
-    if not is_device_input(frames):
-        raise ValueError("nearest_keypoints: torch CUDA tensors or an aligned result (host arrays: lidar_snow_sim_amd.nearest.three_nn)")
-    if isinstance(k, bool) or int(k) != k:
-        raise ValueError("nearest_keypoints: k must be an integer")
-    k = int(k)
-    if not 1 <= k <= 8:
-        raise ValueError("nearest_keypoints: k must lie in 1 .. 8")
-    rng = None
-    if point_cloud_range is not None:
-        rng = np.asarray(point_cloud_range, np.float64).reshape(-1)
-        if rng.shape != (6,):
-            raise ValueError("nearest_keypoints: point_cloud_range holds 6 numbers (x0, y0, z0, x1, y1, z1)")
-    rows, offsets, _, eng = _resolve_input(torch, frames, False, device, slot)
-    dev = rows.device
-    nf, n = len(offsets) - 1, int(offsets[-1])
-    if keep is not None:
-        keep = _keep_mask(torch, keep, rows, offsets)
-    cen = centres.points if isinstance(centres, KeypointBatch) else centres
-    if not (torch.is_tensor(cen) and cen.dim() == 3 and cen.shape[0] == nf and cen.dtype == rows.dtype and cen.device == dev and cen.is_contiguous()):
-        raise ValueError("nearest_keypoints: centres must be a KeypointBatch or a contiguous (frames, K, 3 .. 5) tensor in the rows' dtype on their device")
-    K, Cq = int(cen.shape[1]), int(cen.shape[2])
-    # (the shapes below need these; the entry refuses them in the same words, and everything else of the domain)
-    if not 3 <= Cq <= 5:
-        raise ValueError("nearest_keypoints: centre_features must be 3, 4 or 5: x, y, z first (centres)")
-    if K < 1:
-        raise ValueError("nearest_keypoints: n_centres must be at least 1 (centres)")
-    if nf * K > 2 ** 31 - 1:
-        raise ValueError("nearest_keypoints: n_frames * n_centres exceeds 2^31 - 1; split the batch")
-    if out is None:
-        out = NearestBatch.empty(offsets, K, k, rows.dtype, dev, return_weights)
-    else:
-        want = (("index", torch.int32), ("dist2", rows.dtype)) + ((("weight", rows.dtype),) if return_weights else ())
-        for name, dtype in want:
-            t = getattr(out, name, None) if isinstance(out, NearestBatch) else None
-            if not (torch.is_tensor(t) and tuple(t.shape) == (n, k) and t.dtype == dtype and t.is_contiguous() and t.device == dev):
-                raise ValueError(f"nearest_keypoints: out must be a NearestBatch whose {name} is a contiguous {(n, k)} {dtype} tensor on the device of the rows")
-    weight = out.weight if return_weights else None
-    up = _uploads(eng)
-    with torch.cuda.device(dev), _on_run_stream(torch, eng, dev) as (_, run):
-        d_off = up.get(torch, dev, offsets, run)
-        eng.ctx.nearest_centres_device(nf, n, int(np.diff(offsets).max()), d_off.data_ptr(), rows.data_ptr() if n else 0, 0 if rows.dtype == torch.float32 else 1,
-                                       rng, K, cen.data_ptr(), Cq, k, 0 if keep is None or not n else keep.data_ptr(), out.index.data_ptr() if n else 0,
-                                       out.dist2.data_ptr() if n else 0, 0 if weight is None or not n else weight.data_ptr(), run.cuda_stream)
-    same = out.n_centres == K and np.array_equal(out.offsets, np.asarray(offsets, np.int64)) and (weight is None) == (out.weight is None)
-    return out if same else NearestBatch(out.index, out.dist2, weight, offsets, K)
-
-
-class BoxLabelBatch:
-    """What points_in_boxes() leaves behind, N = rows of the batch, F = frames, B = boxes per frame -- every shape static: `box_of` (N
-    int32: the smallest present box number of the row's frame that contains the row, 0 .. B - 1; -1 for a row in no box and for an absent
-    or unusable row), `count` (F, B int32: the usable rows inside every box, overlaps included, 0 for an absent box; None unless asked
-    for), `local` (N, 3 in the rows' dtype: the row in the frame of its box -- along its length, its width, and up from its centre; zeros
-    where box_of is -1; None unless asked for) and `pose` (F, B, 2 float64: the (cos, sin) of the heading that was used, (0, 0) for an
-    absent box; None unless asked for).  `offsets` (host) and `n_boxes` say which frame a row belongs to: flat_index(), labels(),
-    keep_boxes() and rows_in() are pure indexing, no kernel of this library.  All still being written until the stream the call was made
-    on has caught up."""
-
-    def __init__(self, box_of, count, local=None, pose=None, offsets=None, n_boxes=0):
-        self.box_of, self.count, self.local, self.pose, self.n_boxes = box_of, count, local, pose, int(n_boxes)
-        self.offsets = np.array([0, box_of.shape[0]], np.int64) if offsets is None else np.asarray(offsets, np.int64)
-        self._base = None
-
-    @classmethod
-    def empty(cls, offsets, n_boxes, dtype=None, device=None, with_count=True, with_local=False, with_pose=False):
-        """Uninitialised buffers of the shapes points_in_boxes() writes for a batch with these frame offsets (or, for one frame, this
-        number of rows) (out=): static addresses for a captured graph."""
-        import torch
-        dev = torch.device("cuda", torch.cuda.current_device() if device is None else int(device)) if not isinstance(device, torch.device) else device
-        off = np.array([0, int(offsets)], np.int64) if np.ndim(offsets) == 0 else np.asarray(offsets, np.int64)
-        n, nf, B = int(off[-1]), len(off) - 1, int(n_boxes)
-        return cls(torch.empty(n, dtype=torch.int32, device=dev), torch.empty((nf, B), dtype=torch.int32, device=dev) if with_count else None,
-                   torch.empty((n, 3), dtype=dtype or torch.float32, device=dev) if with_local else None,
-                   torch.empty((nf, B, 2), dtype=torch.float64, device=dev) if with_pose else None, off, B)
-
-    def flat_index(self):
-        """box_of + frame * B, -1 kept (N int64): gathers from per-box values flattened to (F B, ...).  The first call of a batch of
-        several frames uploads their row counts (a few bytes; make it before capturing a graph); later calls reuse the result."""
-        import torch
-        idx = self.box_of.long()
-        if len(self.offsets) <= 2:
-            return idx
-        if self._base is None:
-            counts = torch.from_numpy(np.diff(self.offsets)).to(idx.device)
-            first = torch.arange(len(counts), device=idx.device) * self.n_boxes
-            self._base = torch.repeat_interleave(first, counts, output_size=int(self.offsets[-1]))
-        return torch.where(idx >= 0, idx + self._base, idx)
-
-    def labels(self, per_box, background=0):
-        """Per-box values (F, B) or (F, B, D) -- the class column of gt_boxes, say -- as per-row values (N,) or (N, D): the value of the
-        row's box, `background` for a row in no box.  The point heads' point_cls_labels."""
-        import torch
-        F, B = len(self.offsets) - 1, self.n_boxes
-        if not (torch.is_tensor(per_box) and per_box.dim() in (2, 3) and tuple(per_box.shape[:2]) == (F, B) and per_box.device == self.box_of.device):
-            raise ValueError(f"labels: per_box must be a ({F}, {B}) or ({F}, {B}, D) tensor on the device of the rows: one value, or D of them, per box")
-        flat = per_box.reshape(F * B, -1) if per_box.dim() == 3 else per_box.reshape(F * B)
-        at = self.flat_index()
-        got = flat[at.clamp(min=0)]
-        has = at >= 0
-        return torch.where(has[:, None] if got.dim() == 2 else has, got, torch.full_like(got, background))
-
-    def keep_boxes(self, min_points=1):
-        """(F, B) bool: count >= min_points, min_points >= 1 -- filter_by_min_points after the augmentation; an absent box is never kept."""
-        if self.count is None:
-            raise ValueError("keep_boxes: this BoxLabelBatch has no count (points_in_boxes(..., return_count=True))")
-        if isinstance(min_points, bool) or int(min_points) != min_points or int(min_points) < 1:
-            raise ValueError("keep_boxes: min_points must be an integer of at least 1")
-        return self.count >= int(min_points)
-
-    def rows_in(self, box_mask=None):
-        """(N,) bool: the rows inside a box -- with box_mask (F, B bool), inside a box whose entry is set, judged by the row's own box
-        (box_of).  A keep mask for augment_batch(..., keep=) or dror_keep(..., keep=); its negation clears a pasted object's place."""
-        import torch
-        if box_mask is None:
-            return self.box_of >= 0
-        F, B = len(self.offsets) - 1, self.n_boxes
-        if not (torch.is_tensor(box_mask) and box_mask.dtype == torch.bool and tuple(box_mask.shape) == (F, B) and box_mask.device == self.box_of.device):
-            raise ValueError(f"rows_in: box_mask must be a ({F}, {B}) bool tensor on the device of the rows")
-        at = self.flat_index()
-        return (at >= 0) & box_mask.reshape(F * B)[at.clamp(min=0)]
-
-
-def points_in_boxes(frames, boxes, *, pose=None, keep=None, out=None, return_count=True, return_local=False, return_pose=False, device=None, slot=0):
-    """The box of every row and the rows of every box on the device (snowgpu_points_in_boxes_device; the definition: include/snowgpu.h):
-    roiaware_pool3d's points_in_boxes_gpu with check_pt_in_box3d's faces -- z closed, x and y strict with the 1e-5 margin -- in float64.
-    A row takes part if it is present and within 1e6 of the origin on every axis.
-
-    frames    what nearest_keypoints takes -- torch CUDA tensors, a DeviceBatch, or an AlignedResult / AlignedWetResult: its rows,
-              offsets and keep mask are used (nothing is waited for).
-    boxes     a contiguous (F, B, 7 .. 10) tensor in the rows' dtype on their device, 1 <= B <= 256: cx, cy, cz, dx, dy, dz, heading
-              first (OpenPCDet's gt_boxes; its zero rows are absent boxes).
-    pose      None: cos / sin of the heading in float64 on the device; or a contiguous (F, B, 2) float64 tensor (cos, sin) used as it is.
-    keep      an input keep mask as the aligned calls take it (with a result: ANDed with the result's own).
-    out       a BoxLabelBatch to write into (BoxLabelBatch.empty): every element is written, nothing needs clearing.
-
-    Returns a BoxLabelBatch.  Asynchronous on torch's current stream; nothing is read on the host: capturable after one warm-up call."""
-    import torch
-    if isinstance(frames, AlignedResult):
-        res = frames
-        own = res.keep if res.keep.dtype == torch.bool else res.keep.view(torch.bool)
-        frames = DeviceBatch(res.rows, res.offsets)
-        keep = own if keep is None else (_keep_mask(torch, keep, res.rows, res.offsets) & own)
-    if not is_device_input(frames):
-        raise ValueError("points_in_boxes: torch CUDA tensors or an aligned result (host arrays: lidar_snow_sim_amd.boxes.points_in_boxes)")
-    rows, offsets, _, eng = _resolve_input(torch, frames, False, device, slot)
-    dev = rows.device
-    nf, n = len(offsets) - 1, int(offsets[-1])
-    if keep is not None:
-        keep = _keep_mask(torch, keep, rows, offsets)
-    if not (torch.is_tensor(boxes) and boxes.dim() == 3 and boxes.shape[0] == nf and boxes.dtype == rows.dtype and boxes.device == dev and boxes.is_contiguous()):
-        raise ValueError("points_in_boxes: boxes must be a contiguous (frames, B, 7 .. 10) tensor in the rows' dtype on their device")
-    B, Cb = int(boxes.shape[1]), int(boxes.shape[2])
-    # (the shapes below need these; the entry refuses them in the same words, and everything else of the domain)
-    if not 1 <= B <= 256:
-        raise ValueError("points_in_boxes: n_boxes must lie in 1 .. 256 (boxes)")
-    if not 7 <= Cb <= 10:
-        raise ValueError("points_in_boxes: box_features must lie in 7 .. 10: cx, cy, cz, dx, dy, dz, heading first (boxes)")
-    if pose is not None and not (torch.is_tensor(pose) and tuple(pose.shape) == (nf, B, 2) and pose.dtype == torch.float64 and pose.device == dev and pose.is_contiguous()):
-        raise ValueError(f"points_in_boxes: pose must be a contiguous {(nf, B, 2)} float64 tensor (cos, sin) on the device of the rows")
-    want = (("box_of", torch.int32, (n,), True), ("count", torch.int32, (nf, B), return_count), ("local", rows.dtype, (n, 3), return_local),
-            ("pose", torch.float64, (nf, B, 2), return_pose))
-    if out is None:
-        out = BoxLabelBatch.empty(offsets, B, rows.dtype, dev, return_count, return_local, return_pose)
-    else:
-        for name, dtype, shape, asked in want:
-            t = getattr(out, name, None) if isinstance(out, BoxLabelBatch) else None
-            if asked and not (torch.is_tensor(t) and tuple(t.shape) == shape and t.dtype == dtype and t.is_contiguous() and t.device == dev):
-                raise ValueError(f"points_in_boxes: out must be a BoxLabelBatch whose {name} is a contiguous {shape} {dtype} tensor on the device of the rows")
-    count, local, used = (out.count if return_count else None), (out.local if return_local else None), (out.pose if return_pose else None)
-    up = _uploads(eng)
-    with torch.cuda.device(dev), _on_run_stream(torch, eng, dev) as (_, run):
-        d_off = up.get(torch, dev, offsets, run)
-        eng.ctx.points_in_boxes_device(nf, n, int(np.diff(offsets).max()), d_off.data_ptr(), rows.data_ptr() if n else 0, 0 if rows.dtype == torch.float32 else 1,
-                                       B, boxes.data_ptr(), Cb, 0 if pose is None else pose.data_ptr(), 0 if keep is None or not n else keep.data_ptr(),
-                                       out.box_of.data_ptr() if n else 0, 0 if count is None else count.data_ptr(),
-                                       0 if local is None or not n else local.data_ptr(), 0 if used is None else used.data_ptr(), run.cuda_stream)
-    same = (out.n_boxes == B and np.array_equal(out.offsets, np.asarray(offsets, np.int64)) and (count is None) == (out.count is None) and
-            (local is None) == (out.local is None) and (used is None) == (out.pose is None))
-    return out if same else BoxLabelBatch(out.box_of, count, local, used, offsets, B)
-
-
-IOU_MODES = {"bev": 0, "3d": 1}
-
-
-def _box_set(torch, who, name, boxes, limit, like=None):
-    """(F, B, Cb) of a box tensor after the checks the box entries share."""
-    if not (torch.is_tensor(boxes) and boxes.is_cuda and boxes.dim() == 3 and boxes.dtype in (torch.float32, torch.float64) and boxes.is_contiguous()):
-        raise ValueError(f"{who}: {name} must be a contiguous (frames, B, 7 .. 10) float32 or float64 CUDA tensor")
-    if like is not None and not (boxes.dtype == like.dtype and boxes.device == like.device and boxes.shape[0] == like.shape[0]):
-        raise ValueError(f"{who}: {name} must have the frames, the dtype and the device of the other boxes")
-    F, B, Cb = (int(v) for v in boxes.shape)
-    if F < 1 or not 1 <= B <= limit:
-        raise ValueError(f"{who}: the boxes per frame must lie in 1 .. {limit}, the frames be at least 1 ({name})")
-    if not 7 <= Cb <= 10:
-        raise ValueError(f"{who}: box_features must lie in 7 .. 10: cx, cy, cz, dx, dy, dz, heading first ({name})")
-    return F, B, Cb
-
-
-def _box_pose(torch, who, name, pose, boxes):
-    shape = tuple(boxes.shape[:2]) + (2,)
-    if pose is not None and not (torch.is_tensor(pose) and tuple(pose.shape) == shape and pose.dtype == torch.float64 and pose.device == boxes.device and pose.is_contiguous()):
-        raise ValueError(f"{who}: {name} must be a contiguous {shape} float64 tensor (cos, sin) on the device of the boxes")
-    return 0 if pose is None else pose.data_ptr()
-
-
-def _checked_out(torch, who, kind, out, want, dev):
-    for name, dtype, shape, asked in want:
-        t = getattr(out, name, None) if isinstance(out, kind) else None
-        if asked and not (torch.is_tensor(t) and tuple(t.shape) == shape and t.dtype == dtype and t.is_contiguous() and t.device == dev):
-            raise ValueError(f"{who}: out must be a {kind.__name__} whose {name} is a contiguous {shape} {dtype} tensor on the device of the boxes")
-
-
-class IouBatch:
-    """What boxes_iou() leaves behind, F frames, M boxes a and B boxes b per frame -- every shape static: `iou` (F, M, B in the boxes' dtype:
-    the IoU of a_m with b_b, 0 where either is absent; None unless asked for), `best` (F, M int32: the smallest b with the largest IoU of
-    a_m if that IoU is > 0, else -1 -- the target layer's gt_assignment; None unless asked for) and `best_iou` (F, M: that IoU, 0 where best
-    is -1 -- max_overlaps).  All still being written until the stream the call was made on has caught up."""
-
-    def __init__(self, iou=None, best=None, best_iou=None):
-        self.iou, self.best, self.best_iou = iou, best, best_iou
-
-    @classmethod
-    def empty(cls, n_frames, n_a, n_b, dtype=None, device=None, with_iou=True, with_best=False):
-        """Uninitialised buffers of the shapes boxes_iou() writes (out=): static addresses for a captured graph."""
-        import torch
-        dev = torch.device("cuda", torch.cuda.current_device() if device is None else int(device)) if not isinstance(device, torch.device) else device
-        F, M, B, dt = int(n_frames), int(n_a), int(n_b), dtype or torch.float32
-        return cls(torch.empty((F, M, B), dtype=dt, device=dev) if with_iou else None, torch.empty((F, M), dtype=torch.int32, device=dev) if with_best else None,
-                   torch.empty((F, M), dtype=dt, device=dev) if with_best else None)
-
-
-def boxes_iou(boxes_a, boxes_b, *, mode='3d', pose_a=None, pose_b=None, out=None, return_iou=True, return_best=False, slot=0):
-    """The rotated IoU of every box of `boxes_a` with every box of `boxes_b` of its frame on the device (snowgpu_boxes_iou_device; the
-    definition: include/snowgpu.h): pcdet's boxes_iou3d_gpu (mode '3d') and boxes_iou_bev (mode 'bev') in float64 by clipping in a fixed
-    order, and the best partner of every box a without materialising the matrix.
-
-    boxes_a   a contiguous (F, M, 7 .. 10) float32 or float64 CUDA tensor, 1 <= M <= 9216: cx, cy, cz, dx, dy, dz, heading first (rois; the
-              `boxes` of an NmsBatch as they stand: zero rows are absent boxes).
-    boxes_b   (F, B, 7 .. 10) likewise, same dtype and device, 1 <= B <= 9216 (gt_boxes); F M B < 2^31.
-    pose_a, pose_b   None: cos / sin of the heading in float64 on the device; or contiguous (F, M, 2) / (F, B, 2) float64 tensors used as they are.
-    out       an IouBatch to write into (IouBatch.empty): every element is written.
-    return_iou, return_best   which outputs to compute; at least one.
-    The records of the boxes are scratch of the engine of `slot`, shared by nms() and boxes_iou(): calls made on streams that are not ordered
-    against each other (torch's default stream runs on a side stream of the engine) need a `slot` each.
-
-    Returns an IouBatch.  Asynchronous on torch's current stream; nothing is read on the host: capturable after one warm-up call."""
-    import torch
-    from . import engine as _engine
-    who = "boxes_iou"
-    F, M, Ca = _box_set(torch, who, "boxes_a", boxes_a, 9216)
-    _, B, Cb = _box_set(torch, who, "boxes_b", boxes_b, 9216, boxes_a)
-    if mode not in IOU_MODES:
-        raise ValueError(f"{who}: mode must be 'bev' or '3d'")
-    if not (return_iou or return_best):
-        raise ValueError(f"{who}: nothing to compute: return_iou or return_best")
-    if F * M * B > 2 ** 31 - 1:
-        raise ValueError(f"{who}: frames * M * B exceeds 2^31 - 1; split the batch")
-    dev, dt = boxes_a.device, boxes_a.dtype
-    pa, pb = _box_pose(torch, who, "pose_a", pose_a, boxes_a), _box_pose(torch, who, "pose_b", pose_b, boxes_b)
-    want = (("iou", dt, (F, M, B), return_iou), ("best", torch.int32, (F, M), return_best), ("best_iou", dt, (F, M), return_best))
-    if out is None:
-        out = IouBatch.empty(F, M, B, dt, dev, return_iou, return_best)
-    else:
-        _checked_out(torch, who, IouBatch, out, want, dev)
-    iou, best, best_iou = (out.iou if return_iou else None), (out.best if return_best else None), (out.best_iou if return_best else None)
-    eng = _engine.get_engine(dev.index, slot)
-    with torch.cuda.device(dev), _on_run_stream(torch, eng, dev) as (_, run):
-        eng.ctx.boxes_iou_device(F, M, boxes_a.data_ptr(), Ca, B, boxes_b.data_ptr(), Cb, 0 if dt == torch.float32 else 1, IOU_MODES[mode], pa, pb,
-                                 0 if iou is None else iou.data_ptr(), 0 if best is None else best.data_ptr(), 0 if best_iou is None else best_iou.data_ptr(),
-                                 run.cuda_stream)
-    same = (iou is None) == (out.iou is None) and (best is None) == (out.best is None)
-    return out if same else IouBatch(iou, best, best_iou)
-
-
-class NmsBatch:
-    """What nms() leaves behind, F frames of B boxes, P = post_max -- every shape static: `index` (F, P int32: the kept box numbers in rank
-    order, -1 behind the count), `count` (F int32), `boxes` (F, P, Cb in the boxes' dtype: the kept boxes with all their columns and ZERO
-    rows behind the count -- rois for sample_keypoints(rois=), boxes for points_in_boxes and boxes_iou as they stand; None unless asked
-    for), `scores` (F, P: their scores, 0 behind the count; None unless asked for) and `kept` (F, B uint8: 1 for a kept box; None unless
-    asked for).  All still being written until the stream the call was made on has caught up."""
-
-    def __init__(self, index, count, boxes=None, scores=None, kept=None):
-        self.index, self.count, self.boxes, self.scores, self.kept = index, count, boxes, scores, kept
-
-    @classmethod
-    def empty(cls, n_frames, n_boxes, post_max, box_features=7, dtype=None, device=None, with_boxes=True, with_scores=False, with_kept=False):
-        """Uninitialised buffers of the shapes nms() writes (out=): static addresses for a captured graph."""
-        import torch
-        dev = torch.device("cuda", torch.cuda.current_device() if device is None else int(device)) if not isinstance(device, torch.device) else device
-        F, B, P, dt = int(n_frames), int(n_boxes), int(post_max), dtype or torch.float32
-        return cls(torch.empty((F, P), dtype=torch.int32, device=dev), torch.empty(F, dtype=torch.int32, device=dev),
-                   torch.empty((F, P, int(box_features)), dtype=dt, device=dev) if with_boxes else None,
-                   torch.empty((F, P), dtype=dt, device=dev) if with_scores else None, torch.empty((F, B), dtype=torch.uint8, device=dev) if with_kept else None)
-
-
-def nms(boxes, scores, iou_thresh, *, post_max, score_thresh=-math.inf, mode='bev', pose=None, out=None, return_boxes=True, return_scores=False,
-        return_kept=False, slot=0):
-    """Class-agnostic rotated NMS per frame on the device (snowgpu_nms_device; the definition: include/snowgpu.h): pcdet's nms_gpu without
-    its host sweep.  The present boxes whose score is not NaN and is >= score_thresh are ranked by score (the smallest number first among
-    equals); a candidate is suppressed iff an already kept box has IoU > iou_thresh with it; the walk stops after post_max kept.
-
-    boxes     a contiguous (F, B, 7 .. 10) float32 or float64 CUDA tensor, 1 <= B <= 9216 (take torch.topk first, as pcdet does).
-    scores    a contiguous (F, B) tensor of the same dtype and device.
-    post_max  1 .. B: the static length of the keep list.
-    mode      'bev' (nms_gpu) or '3d'.
-    pose      None, or a contiguous (F, B, 2) float64 tensor (cos, sin) used as it is.
-    out       an NmsBatch to write into (NmsBatch.empty): every element is written.
-    The records of the boxes are scratch of the engine of `slot`, shared by nms() and boxes_iou(): calls made on streams that are not ordered
-    against each other (torch's default stream runs on a side stream of the engine) need a `slot` each.
-
-    Returns an NmsBatch.  Asynchronous on torch's current stream; nothing is read on the host: capturable after one warm-up call."""
-    import torch
-    from . import engine as _engine
-    who = "nms"
-    F, B, Cb = _box_set(torch, who, "boxes", boxes, 9216)
-    dev, dt = boxes.device, boxes.dtype
-    if not (torch.is_tensor(scores) and tuple(scores.shape) == (F, B) and scores.dtype == dt and scores.device == dev and scores.is_contiguous()):
-        raise ValueError(f"{who}: scores must be a contiguous {(F, B)} tensor in the boxes' dtype on their device")
-    if mode not in IOU_MODES:
-        raise ValueError(f"{who}: mode must be 'bev' or '3d'")
-    if isinstance(post_max, bool) or int(post_max) != post_max or not 1 <= int(post_max) <= B:
-        raise ValueError(f"{who}: post_max must be an integer in 1 .. B")
-    if math.isnan(float(iou_thresh)) or math.isnan(float(score_thresh)):
-        raise ValueError(f"{who}: a threshold is NaN")
-    P = int(post_max)
-    pp = _box_pose(torch, who, "pose", pose, boxes)
-    want = (("index", torch.int32, (F, P), True), ("count", torch.int32, (F,), True), ("boxes", dt, (F, P, Cb), return_boxes),
-            ("scores", dt, (F, P), return_scores), ("kept", torch.uint8, (F, B), return_kept))
-    if out is None:
-        out = NmsBatch.empty(F, B, P, Cb, dt, dev, return_boxes, return_scores, return_kept)
-    else:
-        _checked_out(torch, who, NmsBatch, out, want, dev)
-    kb, ks, kk = (out.boxes if return_boxes else None), (out.scores if return_scores else None), (out.kept if return_kept else None)
-    eng = _engine.get_engine(dev.index, slot)
-    with torch.cuda.device(dev), _on_run_stream(torch, eng, dev) as (_, run):
-        eng.ctx.nms_device(F, B, boxes.data_ptr(), Cb, scores.data_ptr(), 0 if dt == torch.float32 else 1, IOU_MODES[mode], float(iou_thresh), float(score_thresh),
-                           P, pp, out.index.data_ptr(), out.count.data_ptr(), 0 if kb is None else kb.data_ptr(), 0 if ks is None else ks.data_ptr(),
-                           0 if kk is None else kk.data_ptr(), run.cuda_stream)
-    same = (kb is None) == (out.boxes is None) and (ks is None) == (out.scores is None) and (kk is None) == (out.kept is None)
-    return out if same else NmsBatch(out.index, out.count, kb, ks, kk)
 
 
 def augment_batch(frames, particle_file_prefix, beam_divergence, shuffle=True, noise_floor=0.7, root_path=None, *, planes=None,

@@ -378,6 +378,12 @@ def test_fov_keep_against_numpy(tl):
     assert np.array_equal(both[decided], (flag & m)[decided]) and not both[~m].any()
 
 
+def test_fov_keep_refuses_host_rows_word_for_word():
+    from lidar_snow_sim_amd.tensors import fov_keep
+    with pytest.raises(ValueError, match=r"^fov_keep: torch CUDA tensors \(host arrays: lidar_snow_sim_amd\.calibration\.get_fov_flag\)$"):
+        fov_keep(np.zeros((4, 5), np.float32), None)
+
+
 # ---- 11. the fused chain ------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("dtype", [np.float32, np.float64], ids=["float32", "float64"])
 def test_fused_chain_equals_the_two_masked_stages(tl, dtype):

@@ -3,6 +3,8 @@ csrc/snowgpu_ball.hip, csrc/sg_ball.h) against the brute-force NumPy restatement
 tests/test_ball_reference.py holds to the conditions that keep these comparisons from being vacuous).  The outputs are integers and
 copied bits, membership is decided by separately rounded operations that the restatement makes in the same order: every comparison is
 equality of bytes."""
+import re
+
 import numpy as np
 import pytest
 import torch
@@ -359,3 +361,72 @@ def test_refusals():
     assert np.array_equal(out.index.cpu().numpy(), want["index"]) and np.array_equal(out.count.cpu().numpy(), want["count"])
     no_points = _query(pc, cen, r, s, point_cloud_range=rng, return_points=False)
     assert no_points.points is None and np.array_equal(no_points.index.cpu().numpy(), want["index"])
+
+
+# ---- every refusal of the Python boundary word for word, and which of two faults is reported -----------------------------------------------------
+def _pin_batch():
+    """Two float32 frames of 64 rows."""
+    from lidar_snow_sim_amd.tensors import DeviceBatch
+    rows = (torch.arange(640, dtype=torch.float32, device="cuda:0").reshape(128, 5) % 17) / 4
+    return DeviceBatch(rows, np.array([0, 64, 128], np.int64))
+
+
+def _centres(n=8, features=3, dtype=torch.float32):
+    return torch.empty((2, n, features), dtype=dtype, device="cuda:0")
+
+
+def _neighbour_out(*args, **kw):
+    from lidar_snow_sim_amd.tensors import NeighbourBatch
+    return NeighbourBatch.empty(2, 8, *args, **kw)
+
+
+HOST_WORDS = "ball_query: torch CUDA tensors or an aligned result (host arrays: lidar_snow_sim_amd.ball.ball_query)"
+CENTRE_WORDS = "ball_query: centres must be a KeypointBatch or a contiguous (frames, K, 3 .. 5) tensor in the rows' dtype on their device"
+KEEP_WORDS = "keep must have one element per row of the batch (N_total, F x N, or a list of per-frame tensors)"
+OUT_WORDS = "ball_query: out must be a NeighbourBatch whose %s tensor on the device of the rows"
+PINNED = (
+    ("host rows", lambda: dict(frames=np.zeros((4, 5), np.float32)), HOST_WORDS),
+    ("two radii, one count", lambda: dict(radius=(1.0, 2.0)), "ball_query: as many radii as sample counts"),
+    ("n_neighbours 2.5", lambda: dict(n_neighbours=2.5), "ball_query: n_neighbours must be an integer"),
+    ("num_features True", lambda: dict(num_features=True), "ball_query: num_features must be an integer"),
+    ("range of 5", lambda: dict(point_cloud_range=(0, 0, 0, 4, 4)), "ball_query: point_cloud_range holds 6 numbers (x0, y0, z0, x1, y1, z1)"),
+    ("centres of another dtype", lambda: dict(centres=_centres(dtype=torch.float64)), CENTRE_WORDS),
+    ("num_features 6", lambda: dict(num_features=6), "ball_query: n_features must be 3, 4 or 5: the columns of a row that a neighbour carries"),
+    ("centres of 6 columns", lambda: dict(centres=_centres(features=6)), "ball_query: centre_features must be 3, 4 or 5: x, y, z first"),
+    ("no centre", lambda: dict(centres=_centres(0)), "ball_query: n_centres must be at least 1"),
+    ("five radii", lambda: dict(radius=(1.0,) * 5, n_neighbours=(4,) * 5), "ball_query: n_radii must lie in 1 .. 4"),
+    ("n_neighbours 65", lambda: dict(n_neighbours=65), "ball_query: the samples of a radius must lie in 1 .. 64"),
+    ("2^31 slots", lambda: dict(centres=_centres(2 ** 22), radius=(1.0,) * 4, n_neighbours=(64,) * 4),
+     "ball_query: n_frames * n_centres * samples exceeds 2^31 - 1; split the batch"),
+    ("out of another shape", lambda: dict(out=_neighbour_out(5)), OUT_WORDS % "index is a contiguous (2, 8, 4) torch.int32"),
+    ("out of another kind", lambda: dict(out=object()), OUT_WORDS % "index is a contiguous (2, 8, 4) torch.int32"),
+    ("out of other radii", lambda: dict(out=_neighbour_out((2, 2))), OUT_WORDS % "count is a contiguous (2, 8, 1) torch.int32"),
+    ("out without points", lambda: dict(out=_neighbour_out(4), return_points=True), OUT_WORDS % "points is a contiguous (2, 8, 4, 4) torch.float32"),
+    # two faults: the earlier step of the call reports
+    ("host rows before the radii", lambda: dict(frames=np.zeros((4, 5), np.float32), radius=(1.0, 2.0)), HOST_WORDS),
+    ("the radii before a count", lambda: dict(radius=(1.0, 2.0), num_features=True), "ball_query: as many radii as sample counts"),
+    ("a count before out", lambda: dict(n_neighbours=2.5, out=object()), "ball_query: n_neighbours must be an integer"),
+    ("the device before the centres", lambda: dict(device=1, centres=_centres(dtype=torch.float64)), "the tensors live on cuda:0, device=1 was asked for"),
+    ("keep before the centres", lambda: dict(keep=torch.ones(127, dtype=torch.bool, device="cuda:0"), centres=_centres(dtype=torch.float64)), KEEP_WORDS),
+    ("the centres before the domain", lambda: dict(centres=_centres(dtype=torch.float64), num_features=6), CENTRE_WORDS),
+    ("the domain before out", lambda: dict(n_neighbours=65, out=object()), "ball_query: the samples of a radius must lie in 1 .. 64"),
+)
+
+
+@pytest.mark.parametrize("overrides, words", [c[1:] for c in PINNED], ids=[c[0] for c in PINNED])
+def test_every_refusal_word_for_word(overrides, words):
+    from lidar_snow_sim_amd.tensors import ball_query
+    args = dict(frames=_pin_batch(), centres=_centres(), radius=1.0, n_neighbours=4)
+    args.update(overrides())
+    with pytest.raises(ValueError, match="^" + re.escape(words) + "$"):
+        ball_query(**args)
+
+
+@pytest.mark.parametrize("overrides, words", ((dict(rng=(0, 0, 0, 4, 4)), "snowgpu_ball_query_device: point_cloud_range holds 6 numbers (x0, y0, z0, x1, y1, z1)"),
+                                              (dict(radii=(1.0, 2.0)), "snowgpu_ball_query_device: as many radii as sample counts")), ids=("range of 5", "two radii, one count"))
+def test_the_wrapper_refuses_word_for_word(overrides, words):
+    from lidar_snow_sim_amd import engine
+    args = dict(rng=None, radii=(1.0,))
+    args.update(overrides)
+    with pytest.raises(ValueError, match="^" + re.escape(words) + "$"):
+        engine.get_engine(0).ctx.ball_query_device(2, 128, 64, 0, 0, 0, args["rng"], 8, 0, 3, args["radii"], (4,), 4, 0, 0, 0, 0)

@@ -3,6 +3,8 @@ csrc/snowgpu_box.hip, csrc/sg_box.h) against the brute-force NumPy restatement o
 tests/test_box_reference.py holds to the conditions that keep these comparisons from being vacuous).  The restatement takes the pose as an
 input and everything behind the pose is separately rounded float64 arithmetic in the definition's order: box_of, count and local are
 compared byte for byte, for both dtypes, with no row and no box left out.  The device library's cos / sin is compared on its own."""
+import re
+
 import numpy as np
 import pytest
 import torch
@@ -320,3 +322,57 @@ def test_refusals():
     call(count=0, local=0, pose=0)
     torch.cuda.synchronize()
     assert np.array_equal(out.box_of.cpu().numpy(), want["box_of"])
+
+
+# ---- every refusal of the Python boundary word for word, and which of two faults is reported -----------------------------------------------------
+def _pin_batch():
+    """Two float32 frames of 64 rows."""
+    from lidar_snow_sim_amd.tensors import DeviceBatch
+    rows = (torch.arange(640, dtype=torch.float32, device="cuda:0").reshape(128, 5) % 17) / 4
+    return DeviceBatch(rows, np.array([0, 64, 128], np.int64))
+
+
+def _pin_boxes(n=2, features=7, dtype=torch.float32):
+    return torch.ones((2, n, features), dtype=dtype, device="cuda:0")
+
+
+def _label_out(rows=128, **kw):
+    from lidar_snow_sim_amd.tensors import BoxLabelBatch
+    return BoxLabelBatch.empty(np.array([0, rows // 2, rows]), 2, **kw)
+
+
+HOST_WORDS = "points_in_boxes: torch CUDA tensors or an aligned result (host arrays: lidar_snow_sim_amd.boxes.points_in_boxes)"
+BOX_WORDS = "points_in_boxes: boxes must be a contiguous (frames, B, 7 .. 10) tensor in the rows' dtype on their device"
+POSE_WORDS = "points_in_boxes: pose must be a contiguous (2, 2, 2) float64 tensor (cos, sin) on the device of the rows"
+KEEP_WORDS = "keep must have one element per row of the batch (N_total, F x N, or a list of per-frame tensors)"
+OUT_WORDS = "points_in_boxes: out must be a BoxLabelBatch whose %s tensor on the device of the rows"
+PINNED = (
+    ("host rows", lambda: dict(frames=np.zeros((4, 5), np.float32)), HOST_WORDS),
+    ("boxes of another dtype", lambda: dict(boxes=_pin_boxes(dtype=torch.float64)), BOX_WORDS),
+    ("boxes of one frame", lambda: dict(boxes=_pin_boxes()[:1]), BOX_WORDS),
+    ("257 boxes", lambda: dict(boxes=_pin_boxes(257)), "points_in_boxes: n_boxes must lie in 1 .. 256 (boxes)"),
+    ("no box", lambda: dict(boxes=_pin_boxes(0)), "points_in_boxes: n_boxes must lie in 1 .. 256 (boxes)"),
+    ("boxes of 6 columns", lambda: dict(boxes=_pin_boxes(features=6)), "points_in_boxes: box_features must lie in 7 .. 10: cx, cy, cz, dx, dy, dz, heading first (boxes)"),
+    ("pose of float32", lambda: dict(pose=torch.ones((2, 2, 2), device="cuda:0")), POSE_WORDS),
+    ("out for other rows", lambda: dict(out=_label_out(126)), OUT_WORDS % "box_of is a contiguous (128,) torch.int32"),
+    ("out of another kind", lambda: dict(out=object()), OUT_WORDS % "box_of is a contiguous (128,) torch.int32"),
+    ("out without count", lambda: dict(out=_label_out(with_count=False)), OUT_WORDS % "count is a contiguous (2, 2) torch.int32"),
+    ("out without local", lambda: dict(out=_label_out(), return_local=True), OUT_WORDS % "local is a contiguous (128, 3) torch.float32"),
+    ("out without pose", lambda: dict(out=_label_out(), return_pose=True), OUT_WORDS % "pose is a contiguous (2, 2, 2) torch.float64"),
+    # two faults: the earlier step of the call reports
+    ("host rows before the boxes", lambda: dict(frames=np.zeros((4, 5), np.float32), boxes=_pin_boxes(features=6)), HOST_WORDS),
+    ("the device before the boxes", lambda: dict(device=1, boxes=_pin_boxes(features=6)), "the tensors live on cuda:0, device=1 was asked for"),
+    ("keep before the boxes", lambda: dict(keep=torch.ones(127, dtype=torch.bool, device="cuda:0"), boxes=_pin_boxes(features=6)), KEEP_WORDS),
+    ("the boxes before the pose", lambda: dict(boxes=_pin_boxes(features=6), pose=torch.ones((2, 2, 2), device="cuda:0")),
+     "points_in_boxes: box_features must lie in 7 .. 10: cx, cy, cz, dx, dy, dz, heading first (boxes)"),
+    ("the pose before out", lambda: dict(pose=torch.ones((2, 2, 2), device="cuda:0"), out=object()), POSE_WORDS),
+)
+
+
+@pytest.mark.parametrize("overrides, words", [c[1:] for c in PINNED], ids=[c[0] for c in PINNED])
+def test_every_refusal_word_for_word(overrides, words):
+    from lidar_snow_sim_amd.tensors import points_in_boxes
+    args = dict(frames=_pin_batch(), boxes=_pin_boxes())
+    args.update(overrides())
+    with pytest.raises(ValueError, match="^" + re.escape(words) + "$"):
+        points_in_boxes(**args)

@@ -2,6 +2,8 @@
 snowgpu_dror_mask_device; csrc/snowgpu_dror.hip, csrc/sg_dror.h) against the float64 NumPy restatement of its definition
 (tests/dror_reference.py, held to SciPy's kd-tree by tests/test_dror_reference.py).  Masks and counts are integers: every comparison is
 equality."""
+import re
+
 import numpy as np
 import pytest
 import torch
@@ -215,3 +217,53 @@ def test_numpy_entry():
         assert got.dtype == np.bool_ and np.array_equal(got, want)
     got = dynamic_radius_outlier_filter(pc[:, :3], 0.16, 3, 3, 0.04)
     assert np.array_equal(got, dr.expected("sector1", "float32", dr.SETTINGS[1])[0])
+
+
+# ---- every refusal of the Python boundary word for word, and which of two faults is reported -----------------------------------------------------
+def _pin_batch():
+    """Two float32 frames of 64 rows."""
+    from lidar_snow_sim_amd.tensors import DeviceBatch
+    rows = (torch.arange(640, dtype=torch.float32, device="cuda:0").reshape(128, 5) % 17) / 4
+    return DeviceBatch(rows, np.array([0, 64, 128], np.int64))
+
+
+def _mask(n=128, dtype=torch.bool):
+    return torch.ones(n, dtype=dtype, device="cuda:0")
+
+
+def _out_is_keep():
+    m = _mask()
+    return dict(keep=m, out=m)
+
+
+HOST_WORDS = "dror_keep: torch CUDA tensors or an aligned result (host arrays: lidar_snow_sim_amd.dror.dynamic_radius_outlier_filter)"
+OUT_WORDS = "dror_keep: out must be a contiguous torch.bool tensor with one element per row, on the device of the rows"
+KEEP_WORDS = "keep must have one element per row of the batch (N_total, F x N, or a list of per-frame tensors)"
+PINNED = (
+    ("host rows", lambda: dict(frames=np.zeros((4, 5), np.float32)), HOST_WORDS),
+    ("alpha 0", lambda: dict(alpha=0.0), "dror_keep: beta * radians(alpha) must lie in (0, 0.25]"),
+    ("beta 40", lambda: dict(beta=40), "dror_keep: beta * radians(alpha) must lie in (0, 0.25]"),
+    ("sr_min -1", lambda: dict(sr_min=-1.0), "dror_keep: sr_min must be finite and >= 0"),
+    ("sr_min inf", lambda: dict(sr_min=float("inf")), "dror_keep: sr_min must be finite and >= 0"),
+    ("k_min 2.5", lambda: dict(k_min=2.5), "dror_keep: k_min must be an integer in 0 .. 65535"),
+    ("k_min 65536", lambda: dict(k_min=65536), "dror_keep: k_min must be an integer in 0 .. 65535"),
+    ("a short out", lambda: dict(out=_mask(127)), OUT_WORDS),
+    ("out of uint8", lambda: dict(out=_mask(dtype=torch.uint8)), OUT_WORDS),
+    ("out is keep", _out_is_keep, "dror_keep: out must not be (or overlap) the keep tensor; the query of one row reads other rows' keep elements"),
+    # two faults: the earlier step of the call reports
+    ("host rows before alpha", lambda: dict(frames=np.zeros((4, 5), np.float32), alpha=0.0), HOST_WORDS),
+    ("alpha before sr_min", lambda: dict(alpha=0.0, sr_min=-1.0), "dror_keep: beta * radians(alpha) must lie in (0, 0.25]"),
+    ("sr_min before k_min", lambda: dict(sr_min=-1.0, k_min=2.5), "dror_keep: sr_min must be finite and >= 0"),
+    ("k_min before the device", lambda: dict(k_min=2.5, device=1), "dror_keep: k_min must be an integer in 0 .. 65535"),
+    ("the device before out", lambda: dict(device=1, out=_mask(127)), "the tensors live on cuda:0, device=1 was asked for"),
+    ("keep before out", lambda: dict(keep=_mask(127), out=_mask(127)), KEEP_WORDS),
+)
+
+
+@pytest.mark.parametrize("overrides, words", [c[1:] for c in PINNED], ids=[c[0] for c in PINNED])
+def test_every_refusal_word_for_word(overrides, words):
+    from lidar_snow_sim_amd.tensors import dror_keep
+    args = dict(frames=_pin_batch())
+    args.update(overrides())
+    with pytest.raises(ValueError, match="^" + re.escape(words) + "$"):
+        dror_keep(**args)

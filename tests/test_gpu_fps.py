@@ -2,6 +2,8 @@
 csrc/snowgpu_fps.hip, csrc/sg_fps.h) against the sequential NumPy restatement of its definition (tests/fps_reference.py, whose inputs
 tests/test_fps_reference.py holds to the conditions that keep these comparisons from being vacuous).  The outputs are integers, copied
 bits and separately rounded sums that the restatement makes in the same order: every comparison is equality."""
+import re
+
 import numpy as np
 import pytest
 import torch
@@ -297,3 +299,61 @@ def test_refusals():
     empty = _sample(pc[:0], K, return_dist=True)
     assert empty.usable.tolist() == [0] and bool((empty.index == -1).all()) and not empty.points.any() and bool((empty.dist == -1).all())
     assert empty.index.shape == (1, K) and empty.points.shape == (1, K, 4)
+
+
+# ---- every refusal of the Python boundary word for word, and which of two faults is reported -----------------------------------------------------
+def _pin_batch():
+    """Two float32 frames of 64 rows."""
+    from lidar_snow_sim_amd.tensors import DeviceBatch
+    rows = (torch.arange(640, dtype=torch.float32, device="cuda:0").reshape(128, 5) % 17) / 4
+    return DeviceBatch(rows, np.array([0, 64, 128], np.int64))
+
+
+def _short_keep():
+    return torch.ones(127, dtype=torch.bool, device="cuda:0")
+
+
+def _keypoint_out(*args, **kw):
+    from lidar_snow_sim_amd.tensors import KeypointBatch
+    return KeypointBatch.empty(2, *args, **kw)
+
+
+HOST_WORDS = "sample_keypoints: torch CUDA tensors or an aligned result (host arrays: lidar_snow_sim_amd.fps.farthest_point_sample)"
+KEEP_WORDS = "keep must have one element per row of the batch (N_total, F x N, or a list of per-frame tensors)"
+DEVICE_WORDS = "the tensors live on cuda:0, device=1 was asked for"
+OUT_WORDS = "sample_keypoints: out must be a KeypointBatch whose %s tensor on the device of the rows"
+PINNED = (
+    ("host rows", lambda: dict(frames=np.zeros((4, 5), np.float32)), HOST_WORDS),
+    ("n_samples 2.5", lambda: dict(n_samples=2.5), "sample_keypoints: n_samples must be an integer"),
+    ("num_features True", lambda: dict(num_features=True), "sample_keypoints: num_features must be an integer"),
+    ("range of 5", lambda: dict(point_cloud_range=(0, 0, 0, 4, 4)), "sample_keypoints: point_cloud_range holds 6 numbers (x0, y0, z0, x1, y1, z1)"),
+    ("num_features 2", lambda: dict(num_features=2), "sample_keypoints: n_features must be 3, 4 or 5: the columns of a row that a keypoint carries"),
+    ("n_samples 0", lambda: dict(n_samples=0), "sample_keypoints: n_samples must be at least 1"),
+    ("n_samples 2^31", lambda: dict(n_samples=2 ** 31), "sample_keypoints: n_frames * n_samples exceeds 2^31 - 1; split the batch"),
+    ("out of another shape", lambda: dict(out=_keypoint_out(9)), OUT_WORDS % "index is a contiguous (2, 8) torch.int32"),
+    ("out of another kind", lambda: dict(out=object()), OUT_WORDS % "index is a contiguous (2, 8) torch.int32"),
+    ("out of another dtype", lambda: dict(out=_keypoint_out(8, dtype=torch.float64)), OUT_WORDS % "points is a contiguous (2, 8, 4) torch.float32"),
+    ("out without dist", lambda: dict(out=_keypoint_out(8), return_dist=True), OUT_WORDS % "dist is a contiguous (2, 8) torch.float32"),
+    # two faults: the earlier step of the call reports
+    ("host rows before a count", lambda: dict(frames=np.zeros((4, 5), np.float32), n_samples=2.5), HOST_WORDS),
+    ("a count before out", lambda: dict(n_samples=2.5, out=object()), "sample_keypoints: n_samples must be an integer"),
+    ("the range before the device", lambda: dict(point_cloud_range=(0, 0, 0, 4, 4), device=1), "sample_keypoints: point_cloud_range holds 6 numbers (x0, y0, z0, x1, y1, z1)"),
+    ("the device before the domain", lambda: dict(device=1, n_samples=0), DEVICE_WORDS),
+    ("keep before the domain", lambda: dict(keep=_short_keep(), num_features=2), KEEP_WORDS),
+    ("the domain before out", lambda: dict(n_samples=0, out=object()), "sample_keypoints: n_samples must be at least 1"),
+)
+
+
+@pytest.mark.parametrize("overrides, words", [c[1:] for c in PINNED], ids=[c[0] for c in PINNED])
+def test_every_refusal_word_for_word(overrides, words):
+    from lidar_snow_sim_amd.tensors import sample_keypoints
+    args = dict(frames=_pin_batch(), n_samples=8)
+    args.update(overrides())
+    with pytest.raises(ValueError, match="^" + re.escape(words) + "$"):
+        sample_keypoints(**args)
+
+
+def test_the_wrapper_refuses_a_short_range_word_for_word():
+    from lidar_snow_sim_amd import engine
+    with pytest.raises(ValueError, match="^" + re.escape("snowgpu_fps_device: point_cloud_range holds 6 numbers (x0, y0, z0, x1, y1, z1)") + "$"):
+        engine.get_engine(0).ctx.fps_device(2, 128, 64, 0, 0, 0, (0, 0, 0, 4, 4), 8, 4, 0, 0, 0, 0, 0)

@@ -3,6 +3,8 @@ fps.sectorized_sample, snowgpu_fps_sectors_device; csrc/snowgpu_fps.hip, csrc/sg
 definition (tests/fps_sectors_reference.py, whose inputs tests/test_fps_sectors_reference.py holds to the conditions that keep these
 comparisons from being vacuous).  The outputs are integers, copied bits and separately rounded sums that the restatement makes in the
 same order: every comparison is equality of bytes."""
+import re
+
 import numpy as np
 import pytest
 import torch
@@ -257,3 +259,67 @@ def test_refusals():
     # rois alone: one sector
     got = _sample(pc, K, rois=d_rois, roi_margin=margin, return_dist=True, return_sector_of=True)
     _same(got, sr.expected("roi", "float32", 1), "rois alone")
+
+
+# ---- every refusal of the sectorized call word for word, and which of two faults is reported ---------------------------------------------------
+def _pin_batch():
+    """Two float32 frames of 64 rows."""
+    from lidar_snow_sim_amd.tensors import DeviceBatch
+    rows = (torch.arange(640, dtype=torch.float32, device="cuda:0").reshape(128, 5) % 17) / 4
+    return DeviceBatch(rows, np.array([0, 64, 128], np.int64))
+
+
+def _keypoint_out(*args, **kw):
+    from lidar_snow_sim_amd.tensors import KeypointBatch
+    return KeypointBatch.empty(2, *args, **kw)
+
+
+def _rois(dtype=torch.float32):
+    return torch.ones((2, 2, 7), dtype=dtype, device="cuda:0")
+
+
+HOST_WORDS = "sample_keypoints: torch CUDA tensors or an aligned result (host arrays: lidar_snow_sim_amd.fps.sectorized_sample)"
+ROI_WORDS = "sample_keypoints: rois must be a contiguous (frames, B, 7 .. 10) tensor of the rows' dtype on the device of the rows"
+OUT_WORDS = "sample_keypoints: out must be a KeypointBatch whose %s tensor on the device of the rows"
+PINNED = (
+    ("host rows", lambda: dict(frames=np.zeros((4, 5), np.float32)), HOST_WORDS),
+    ("host rows with rois alone", lambda: dict(frames=np.zeros((4, 5), np.float32), sectors=None, rois=_rois()), HOST_WORDS),
+    ("n_samples 2.5", lambda: dict(n_samples=2.5), "sample_keypoints: n_samples must be an integer"),
+    ("num_features True", lambda: dict(num_features=True), "sample_keypoints: num_features must be an integer"),
+    ("sectors 2.5", lambda: dict(sectors=2.5), "sample_keypoints: sectors must be an integer"),
+    ("range of 5", lambda: dict(point_cloud_range=(0, 0, 0, 4, 4)), "sample_keypoints: point_cloud_range holds 6 numbers (x0, y0, z0, x1, y1, z1)"),
+    ("num_features 6", lambda: dict(num_features=6), "sample_keypoints: n_features must be 3, 4 or 5: the columns of a row that a keypoint carries"),
+    ("n_samples 0", lambda: dict(n_samples=0), "sample_keypoints: n_samples must be at least 1"),
+    ("n_samples 2^31", lambda: dict(n_samples=2 ** 31), "sample_keypoints: n_frames * n_samples exceeds 2^31 - 1; split the batch"),
+    ("sectors 17", lambda: dict(sectors=17), "sample_keypoints: n_sectors must lie in 1 .. 16"),
+    ("sectors 0", lambda: dict(sectors=0), "sample_keypoints: n_sectors must lie in 1 .. 16"),
+    ("rois of another dtype", lambda: dict(rois=_rois(torch.float64)), ROI_WORDS),
+    ("rois of another frame count", lambda: dict(rois=_rois()[:1]), ROI_WORDS),
+    ("out without sectors", lambda: dict(out=_keypoint_out(8)), OUT_WORDS % "sector_offsets is a contiguous (2, 5) torch.int32"),
+    ("out of another kind", lambda: dict(out=object()), OUT_WORDS % "index is a contiguous (2, 8) torch.int32"),
+    ("out of other sectors", lambda: dict(out=_keypoint_out(8, sectors=5)), OUT_WORDS % "sector_offsets is a contiguous (2, 5) torch.int32"),
+    ("out without dist", lambda: dict(out=_keypoint_out(8, sectors=4), return_dist=True), OUT_WORDS % "dist is a contiguous (2, 8) torch.float32"),
+    ("out without sector_of", lambda: dict(out=_keypoint_out(8, sectors=4), return_sector_of=True), OUT_WORDS % "sector_of is a contiguous (128,) torch.int8"),
+    # two faults: the earlier step of the call reports
+    ("a count before out", lambda: dict(sectors=2.5, out=object()), "sample_keypoints: sectors must be an integer"),
+    ("the device before the domain", lambda: dict(device=1, sectors=17), "the tensors live on cuda:0, device=1 was asked for"),
+    ("the samples before the sectors", lambda: dict(n_samples=0, sectors=17), "sample_keypoints: n_samples must be at least 1"),
+    ("the sectors before the rois", lambda: dict(sectors=17, rois=_rois(torch.float64)), "sample_keypoints: n_sectors must lie in 1 .. 16"),
+    ("the rois before out", lambda: dict(rois=_rois(torch.float64), out=object()), ROI_WORDS),
+    ("dist before sector_of", lambda: dict(out=_keypoint_out(8, sectors=4), return_dist=True, return_sector_of=True), OUT_WORDS % "dist is a contiguous (2, 8) torch.float32"),
+)
+
+
+@pytest.mark.parametrize("overrides, words", [c[1:] for c in PINNED], ids=[c[0] for c in PINNED])
+def test_every_refusal_word_for_word(overrides, words):
+    from lidar_snow_sim_amd.tensors import sample_keypoints
+    args = dict(frames=_pin_batch(), n_samples=8, sectors=4)
+    args.update(overrides())
+    with pytest.raises(ValueError, match="^" + re.escape(words) + "$"):
+        sample_keypoints(**args)
+
+
+def test_the_wrapper_refuses_a_short_range_word_for_word():
+    from lidar_snow_sim_amd import engine
+    with pytest.raises(ValueError, match="^" + re.escape("snowgpu_fps_sectors_device: point_cloud_range holds 6 numbers (x0, y0, z0, x1, y1, z1)") + "$"):
+        engine.get_engine(0).ctx.fps_sectors_device(2, 128, 64, 0, 0, 0, (0, 0, 0, 4, 4), 8, 4, 0, 4, 0, 0, 0, 1.6, 0, 0, 0, 0, 0, 0)

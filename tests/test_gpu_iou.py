@@ -4,6 +4,8 @@ inputs tests/test_iou_reference.py holds to the conditions that keep these compa
 as an input and everything behind the pose is separately rounded float64 arithmetic in the definition's order: every output is compared
 byte for byte, for both dtypes, with no element left out -- under a given pose, and under the pose the device computed, which
 points_in_boxes returns (the same device library, the same rule of presence)."""
+import re
+
 import numpy as np
 import pytest
 import torch
@@ -345,3 +347,99 @@ def test_refusals():
     torch.cuda.synchronize()
     want = ir.nms(c["boxes"], c["scores"], c["pose"], 0.5, 10, 0.0, "bev")
     assert out.index.cpu().numpy().tobytes() == want["index"].tobytes() and out.count.cpu().numpy().tobytes() == want["count"].tobytes()
+
+
+# ---- every refusal of the Python boundary word for word, and which of two faults is reported -----------------------------------------------------
+def _pin_boxes(n=2, features=7, dtype=torch.float32, frames=2):
+    return torch.ones((frames, n, features), dtype=dtype, device="cuda:0")
+
+
+def _pin_pose(dtype=torch.float64):
+    return torch.ones((2, 2, 2), dtype=dtype, device="cuda:0")
+
+
+def _iou_out(*args, **kw):
+    from lidar_snow_sim_amd.tensors import IouBatch
+    return IouBatch.empty(2, *args, **kw)
+
+
+def _nms_out(*args, **kw):
+    from lidar_snow_sim_amd.tensors import NmsBatch
+    return NmsBatch.empty(2, 2, *args, **kw)
+
+
+SET_WORDS = "boxes_iou: %s must be a contiguous (frames, B, 7 .. 10) float32 or float64 CUDA tensor"
+LIKE_WORDS = "boxes_iou: boxes_b must have the frames, the dtype and the device of the other boxes"
+IOU_OUT_WORDS = "boxes_iou: out must be a IouBatch whose %s tensor on the device of the boxes"
+PINNED_IOU = (
+    ("boxes_a on the host", lambda: dict(boxes_a=np.ones((2, 2, 7), np.float32)), SET_WORDS % "boxes_a"),
+    ("boxes_b of two dimensions", lambda: dict(boxes_b=_pin_boxes()[0]), SET_WORDS % "boxes_b"),
+    ("boxes_b of another dtype", lambda: dict(boxes_b=_pin_boxes(dtype=torch.float64)), LIKE_WORDS),
+    ("boxes_b of other frames", lambda: dict(boxes_b=_pin_boxes(frames=3)), LIKE_WORDS),
+    ("no box a", lambda: dict(boxes_a=_pin_boxes(0)), "boxes_iou: the boxes per frame must lie in 1 .. 9216, the frames be at least 1 (boxes_a)"),
+    ("9217 boxes b", lambda: dict(boxes_b=_pin_boxes(9217)), "boxes_iou: the boxes per frame must lie in 1 .. 9216, the frames be at least 1 (boxes_b)"),
+    ("boxes_b of 11 columns", lambda: dict(boxes_b=_pin_boxes(features=11)), "boxes_iou: box_features must lie in 7 .. 10: cx, cy, cz, dx, dy, dz, heading first (boxes_b)"),
+    ("mode", lambda: dict(mode="2d"), "boxes_iou: mode must be 'bev' or '3d'"),
+    ("nothing asked for", lambda: dict(return_iou=False), "boxes_iou: nothing to compute: return_iou or return_best"),
+    ("2^31 pairs", lambda: dict(boxes_a=torch.empty((26, 9216, 7), device="cuda:0"), boxes_b=torch.empty((26, 9216, 7), device="cuda:0")),
+     "boxes_iou: frames * M * B exceeds 2^31 - 1; split the batch"),
+    ("pose_a of float32", lambda: dict(pose_a=_pin_pose(torch.float32)), "boxes_iou: pose_a must be a contiguous (2, 2, 2) float64 tensor (cos, sin) on the device of the boxes"),
+    ("pose_b of another shape", lambda: dict(pose_b=_pin_pose()[:, :1].contiguous()), "boxes_iou: pose_b must be a contiguous (2, 2, 2) float64 tensor (cos, sin) on the device of the boxes"),
+    ("out of another shape", lambda: dict(out=_iou_out(2, 3)), IOU_OUT_WORDS % "iou is a contiguous (2, 2, 2) torch.float32"),
+    ("out of another kind", lambda: dict(out=object()), IOU_OUT_WORDS % "iou is a contiguous (2, 2, 2) torch.float32"),
+    ("out without best", lambda: dict(out=_iou_out(2, 2), return_best=True), IOU_OUT_WORDS % "best is a contiguous (2, 2) torch.int32"),
+    # two faults: the earlier step of the call reports
+    ("boxes_a before boxes_b", lambda: dict(boxes_a=_pin_boxes(features=6), boxes_b=_pin_boxes(features=6)),
+     "boxes_iou: box_features must lie in 7 .. 10: cx, cy, cz, dx, dy, dz, heading first (boxes_a)"),
+    ("the boxes before the mode", lambda: dict(boxes_b=_pin_boxes(features=11), mode="2d"), "boxes_iou: box_features must lie in 7 .. 10: cx, cy, cz, dx, dy, dz, heading first (boxes_b)"),
+    ("the mode before the outputs", lambda: dict(mode="2d", return_iou=False), "boxes_iou: mode must be 'bev' or '3d'"),
+    ("the outputs before the pose", lambda: dict(return_iou=False, pose_a=_pin_pose(torch.float32)), "boxes_iou: nothing to compute: return_iou or return_best"),
+    ("the pose before out", lambda: dict(pose_a=_pin_pose(torch.float32), out=object()), "boxes_iou: pose_a must be a contiguous (2, 2, 2) float64 tensor (cos, sin) on the device of the boxes"),
+)
+
+
+@pytest.mark.parametrize("overrides, words", [c[1:] for c in PINNED_IOU], ids=[c[0] for c in PINNED_IOU])
+def test_every_refusal_of_boxes_iou_word_for_word(overrides, words):
+    args = dict(boxes_a=_pin_boxes(), boxes_b=_pin_boxes())
+    args.update(overrides())
+    with pytest.raises(ValueError, match="^" + re.escape(words) + "$"):
+        _iou(args.pop("boxes_a"), args.pop("boxes_b"), **args)
+
+
+SCORE_WORDS = "nms: scores must be a contiguous (2, 2) tensor in the boxes' dtype on their device"
+NMS_OUT_WORDS = "nms: out must be a NmsBatch whose %s tensor on the device of the boxes"
+PINNED_NMS = (
+    ("boxes on the host", lambda: dict(boxes=np.ones((2, 2, 7), np.float32)), "nms: boxes must be a contiguous (frames, B, 7 .. 10) float32 or float64 CUDA tensor"),
+    ("no box", lambda: dict(boxes=_pin_boxes(0)), "nms: the boxes per frame must lie in 1 .. 9216, the frames be at least 1 (boxes)"),
+    ("boxes of 6 columns", lambda: dict(boxes=_pin_boxes(features=6)), "nms: box_features must lie in 7 .. 10: cx, cy, cz, dx, dy, dz, heading first (boxes)"),
+    ("scores of another dtype", lambda: dict(scores=torch.ones((2, 2), dtype=torch.float64, device="cuda:0")), SCORE_WORDS),
+    ("scores of another shape", lambda: dict(scores=torch.ones((2, 3), device="cuda:0")), SCORE_WORDS),
+    ("mode", lambda: dict(mode="aligned"), "nms: mode must be 'bev' or '3d'"),
+    ("post_max 1.5", lambda: dict(post_max=1.5), "nms: post_max must be an integer in 1 .. B"),
+    ("post_max True", lambda: dict(post_max=True), "nms: post_max must be an integer in 1 .. B"),
+    ("post_max 3", lambda: dict(post_max=3), "nms: post_max must be an integer in 1 .. B"),
+    ("iou_thresh NaN", lambda: dict(iou_thresh=float("nan")), "nms: a threshold is NaN"),
+    ("score_thresh NaN", lambda: dict(score_thresh=float("nan")), "nms: a threshold is NaN"),
+    ("pose of float32", lambda: dict(pose=_pin_pose(torch.float32)), "nms: pose must be a contiguous (2, 2, 2) float64 tensor (cos, sin) on the device of the boxes"),
+    ("out of another length", lambda: dict(out=_nms_out(1)), NMS_OUT_WORDS % "index is a contiguous (2, 2) torch.int32"),
+    ("out of another kind", lambda: dict(out=object()), NMS_OUT_WORDS % "index is a contiguous (2, 2) torch.int32"),
+    ("out of other columns", lambda: dict(out=_nms_out(2, 8)), NMS_OUT_WORDS % "boxes is a contiguous (2, 2, 7) torch.float32"),
+    ("out without scores", lambda: dict(out=_nms_out(2), return_scores=True), NMS_OUT_WORDS % "scores is a contiguous (2, 2) torch.float32"),
+    ("out without kept", lambda: dict(out=_nms_out(2), return_kept=True), NMS_OUT_WORDS % "kept is a contiguous (2, 2) torch.uint8"),
+    # two faults: the earlier step of the call reports
+    ("the boxes before the scores", lambda: dict(boxes=_pin_boxes(features=6), scores=torch.ones((2, 3), device="cuda:0")),
+     "nms: box_features must lie in 7 .. 10: cx, cy, cz, dx, dy, dz, heading first (boxes)"),
+    ("the scores before the mode", lambda: dict(scores=torch.ones((2, 3), device="cuda:0"), mode="aligned"), SCORE_WORDS),
+    ("the mode before post_max", lambda: dict(mode="aligned", post_max=1.5), "nms: mode must be 'bev' or '3d'"),
+    ("post_max before a threshold", lambda: dict(post_max=1.5, iou_thresh=float("nan")), "nms: post_max must be an integer in 1 .. B"),
+    ("a threshold before the pose", lambda: dict(iou_thresh=float("nan"), pose=_pin_pose(torch.float32)), "nms: a threshold is NaN"),
+    ("the pose before out", lambda: dict(pose=_pin_pose(torch.float32), out=object()), "nms: pose must be a contiguous (2, 2, 2) float64 tensor (cos, sin) on the device of the boxes"),
+)
+
+
+@pytest.mark.parametrize("overrides, words", [c[1:] for c in PINNED_NMS], ids=[c[0] for c in PINNED_NMS])
+def test_every_refusal_of_nms_word_for_word(overrides, words):
+    args = dict(boxes=_pin_boxes(), scores=torch.ones((2, 2), device="cuda:0"), iou_thresh=0.5, post_max=2)
+    args.update(overrides())
+    with pytest.raises(ValueError, match="^" + re.escape(words) + "$"):
+        _nms(args.pop("boxes"), args.pop("scores"), args.pop("iou_thresh"), **args)

@@ -3,6 +3,8 @@ csrc/snowgpu_nn.hip, csrc/sg_nn.h) against the brute-force NumPy restatement of 
 tests/test_nn_reference.py holds to the conditions that keep these comparisons from being vacuous).  Indices are integers, distances are
 separately rounded operations that the restatement makes in the same order, and the weights are correctly rounded float64 operations in
 the definition's order: every comparison is equality of bytes, for both dtypes."""
+import re
+
 import numpy as np
 import pytest
 import torch
@@ -284,3 +286,64 @@ def test_refusals():
     ctx.nearest_centres_device(*args, 0, out.index.data_ptr(), out.dist2.data_ptr(), 0)
     torch.cuda.synchronize()
     assert np.array_equal(out.index.cpu().numpy(), want["index"]) and out.dist2.cpu().numpy().tobytes() == want["dist2"].tobytes()
+
+
+# ---- every refusal of the Python boundary word for word, and which of two faults is reported -----------------------------------------------------
+# (the one refusal left out, n_frames * n_centres beyond 2^31 - 1, needs centres of 24 GiB)
+def _pin_batch():
+    """Two float32 frames of 64 rows."""
+    from lidar_snow_sim_amd.tensors import DeviceBatch
+    rows = (torch.arange(640, dtype=torch.float32, device="cuda:0").reshape(128, 5) % 17) / 4
+    return DeviceBatch(rows, np.array([0, 64, 128], np.int64))
+
+
+def _centres(n=8, features=3, dtype=torch.float32):
+    return torch.empty((2, n, features), dtype=dtype, device="cuda:0")
+
+
+def _nearest_out(*args, **kw):
+    from lidar_snow_sim_amd.tensors import NearestBatch
+    return NearestBatch.empty(np.array([0, 64, 128]), 8, *args, **kw)
+
+
+HOST_WORDS = "nearest_keypoints: torch CUDA tensors or an aligned result (host arrays: lidar_snow_sim_amd.nearest.three_nn)"
+CENTRE_WORDS = "nearest_keypoints: centres must be a KeypointBatch or a contiguous (frames, K, 3 .. 5) tensor in the rows' dtype on their device"
+KEEP_WORDS = "keep must have one element per row of the batch (N_total, F x N, or a list of per-frame tensors)"
+OUT_WORDS = "nearest_keypoints: out must be a NearestBatch whose %s tensor on the device of the rows"
+PINNED = (
+    ("host rows", lambda: dict(frames=np.zeros((4, 5), np.float32)), HOST_WORDS),
+    ("k 2.5", lambda: dict(k=2.5), "nearest_keypoints: k must be an integer"),
+    ("k True", lambda: dict(k=True), "nearest_keypoints: k must be an integer"),
+    ("k 9", lambda: dict(k=9), "nearest_keypoints: k must lie in 1 .. 8"),
+    ("range of 5", lambda: dict(point_cloud_range=(0, 0, 0, 4, 4)), "nearest_keypoints: point_cloud_range holds 6 numbers (x0, y0, z0, x1, y1, z1)"),
+    ("centres of another dtype", lambda: dict(centres=_centres(dtype=torch.float64)), CENTRE_WORDS),
+    ("centres of 6 columns", lambda: dict(centres=_centres(features=6)), "nearest_keypoints: centre_features must be 3, 4 or 5: x, y, z first (centres)"),
+    ("no centre", lambda: dict(centres=_centres(0)), "nearest_keypoints: n_centres must be at least 1 (centres)"),
+    ("out of another k", lambda: dict(out=_nearest_out(2)), OUT_WORDS % "index is a contiguous (128, 3) torch.int32"),
+    ("out of another kind", lambda: dict(out=object()), OUT_WORDS % "index is a contiguous (128, 3) torch.int32"),
+    ("out of another dtype", lambda: dict(out=_nearest_out(3, torch.float64)), OUT_WORDS % "dist2 is a contiguous (128, 3) torch.float32"),
+    ("out without weights", lambda: dict(out=_nearest_out(3, with_weights=False)), OUT_WORDS % "weight is a contiguous (128, 3) torch.float32"),
+    # two faults: the earlier step of the call reports
+    ("host rows before k", lambda: dict(frames=np.zeros((4, 5), np.float32), k=2.5), HOST_WORDS),
+    ("k before the range", lambda: dict(k=9, point_cloud_range=(0, 0, 0, 4, 4)), "nearest_keypoints: k must lie in 1 .. 8"),
+    ("the range before the device", lambda: dict(point_cloud_range=(0, 0, 0, 4, 4), device=1), "nearest_keypoints: point_cloud_range holds 6 numbers (x0, y0, z0, x1, y1, z1)"),
+    ("the device before the centres", lambda: dict(device=1, centres=_centres(dtype=torch.float64)), "the tensors live on cuda:0, device=1 was asked for"),
+    ("keep before the centres", lambda: dict(keep=torch.ones(127, dtype=torch.bool, device="cuda:0"), centres=_centres(dtype=torch.float64)), KEEP_WORDS),
+    ("the centres before out", lambda: dict(centres=_centres(features=6), out=object()), "nearest_keypoints: centre_features must be 3, 4 or 5: x, y, z first (centres)"),
+    ("k before out", lambda: dict(k=2.5, out=object()), "nearest_keypoints: k must be an integer"),
+)
+
+
+@pytest.mark.parametrize("overrides, words", [c[1:] for c in PINNED], ids=[c[0] for c in PINNED])
+def test_every_refusal_word_for_word(overrides, words):
+    from lidar_snow_sim_amd.tensors import nearest_keypoints
+    args = dict(frames=_pin_batch(), centres=_centres(), k=3)
+    args.update(overrides())
+    with pytest.raises(ValueError, match="^" + re.escape(words) + "$"):
+        nearest_keypoints(**args)
+
+
+def test_the_wrapper_refuses_a_short_range_word_for_word():
+    from lidar_snow_sim_amd import engine
+    with pytest.raises(ValueError, match="^" + re.escape("snowgpu_nearest_centres_device: point_cloud_range holds 6 numbers (x0, y0, z0, x1, y1, z1)") + "$"):
+        engine.get_engine(0).ctx.nearest_centres_device(2, 128, 64, 0, 0, 0, (0, 0, 0, 4, 4), 8, 0, 3, 3, 0, 0, 0, 0)

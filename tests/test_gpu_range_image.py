@@ -355,3 +355,63 @@ def test_refusals():
     ctx.range_image_device(*args, fov, 0, *tail, 0, out.image.data_ptr(), out.index.data_ptr(), out.pixel_of.data_ptr(), 0)
     torch.cuda.synchronize()
     _same(out, want, "no count", FIELDS[:3])
+
+
+# ---- every refusal of the Python boundary word for word, and which of two faults is reported -----------------------------------------------------
+def _pin_batch():
+    """Two float32 frames of 64 rows."""
+    from lidar_snow_sim_amd.tensors import DeviceBatch
+    rows = (torch.arange(640, dtype=torch.float32, device="cuda:0").reshape(128, 5) % 17) / 4
+    return DeviceBatch(rows, np.array([0, 64, 128], np.int64))
+
+
+def _image_out(*args, **kw):
+    from lidar_snow_sim_amd.tensors import RangeImageBatch
+    return RangeImageBatch.empty(2, *args, **kw)
+
+
+HOST_WORDS = "range_image: torch CUDA tensors or an aligned result (host arrays: lidar_snow_sim_amd.range_image.project)"
+RING_WORDS = "range_image: ring must be a contiguous int32 tensor with one element per row of the batch, on the device of the rows"
+KEEP_WORDS = "keep must have one element per row of the batch (N_total, F x N, or a list of per-frame tensors)"
+OUT_WORDS = "range_image: out must be a RangeImageBatch whose %s tensor on the device of the rows"
+PINNED = (
+    ("host rows", lambda: dict(frames=np.zeros((4, 5), np.float32)), HOST_WORDS),
+    ("height 2.5", lambda: dict(height=2.5), "range_image: height must be an integer"),
+    ("width True", lambda: dict(width=True), "range_image: width must be an integer"),
+    ("num_features 4.5", lambda: dict(num_features=4.5), "range_image: num_features must be an integer"),
+    ("three limits", lambda: dict(range_limits=(0.0, 1.0, 2.0)), "range_image: range_limits holds 2 numbers (lo, hi)"),
+    ("a short ring", lambda: dict(ring=torch.zeros(127, dtype=torch.int32, device="cuda:0")), RING_WORDS),
+    ("a ring of int64", lambda: dict(ring=torch.zeros(128, dtype=torch.int64, device="cuda:0")), RING_WORDS),
+    ("num_features 6", lambda: dict(num_features=6), "range_image: n_features must be 3, 4 or 5: the columns of a row that a pixel stores"),
+    ("height 0", lambda: dict(height=0), "range_image: height and width must be at least 1"),
+    ("2^31 pixels", lambda: dict(height=2 ** 15, width=2 ** 15), "range_image: n_frames * height * width exceeds 2^31 - 1; split the batch"),
+    ("out of another shape", lambda: dict(out=_image_out(5, 8, 128)), OUT_WORDS % "image is a contiguous (2, 5, 4, 8) torch.float32"),
+    ("out of another kind", lambda: dict(out=object()), OUT_WORDS % "image is a contiguous (2, 5, 4, 8) torch.float32"),
+    ("out for other rows", lambda: dict(out=_image_out(4, 8, 127)), OUT_WORDS % "pixel_of is a contiguous (128,) torch.int32"),
+    ("out without count", lambda: dict(out=_image_out(4, 8, 128), return_count=True), OUT_WORDS % "count is a contiguous (2, 4, 8) torch.int32"),
+    # two faults: the earlier step of the call reports
+    ("host rows before a count", lambda: dict(frames=np.zeros((4, 5), np.float32), height=2.5), HOST_WORDS),
+    ("a count before the limits", lambda: dict(height=2.5, range_limits=(0.0,)), "range_image: height must be an integer"),
+    ("the limits before the device", lambda: dict(range_limits=(0.0,), device=1), "range_image: range_limits holds 2 numbers (lo, hi)"),
+    ("the device before the ring", lambda: dict(device=1, ring=torch.zeros(127, dtype=torch.int32, device="cuda:0")), "the tensors live on cuda:0, device=1 was asked for"),
+    ("keep before the ring", lambda: dict(keep=torch.ones(127, dtype=torch.bool, device="cuda:0"), ring=torch.zeros(127, dtype=torch.int32, device="cuda:0")), KEEP_WORDS),
+    ("the ring before the domain", lambda: dict(ring=torch.zeros(127, dtype=torch.int32, device="cuda:0"), height=0), RING_WORDS),
+    ("the domain before out", lambda: dict(height=0, out=object()), "range_image: height and width must be at least 1"),
+)
+
+
+@pytest.mark.parametrize("overrides, words", [c[1:] for c in PINNED], ids=[c[0] for c in PINNED])
+def test_every_refusal_word_for_word(overrides, words):
+    from lidar_snow_sim_amd.tensors import range_image
+    args = dict(frames=_pin_batch(), height=4, width=8)
+    args.update(overrides())
+    with pytest.raises(ValueError, match="^" + re.escape(words) + "$"):
+        range_image(**args)
+
+
+@pytest.mark.parametrize("fov, limits, words", (((0.1,), (0.0, 1.0), "snowgpu_range_image_device: fov holds 2 numbers"),
+                                                ((0.1, -0.4), (0.0, 1.0, 2.0), "snowgpu_range_image_device: range_limits holds 2 numbers")), ids=("fov", "limits"))
+def test_the_wrapper_refuses_a_pair_of_another_length_word_for_word(fov, limits, words):
+    from lidar_snow_sim_amd import engine
+    with pytest.raises(ValueError, match="^" + re.escape(words) + "$"):
+        engine.get_engine(0).ctx.range_image_device(2, 128, 64, 0, 0, 0, 4, 8, fov, 0, limits, 4, 0, 0, 0, 0, 0)

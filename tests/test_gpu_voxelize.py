@@ -2,6 +2,8 @@
 csrc/snowgpu_voxel.hip, csrc/sg_voxel.h) against the sequential NumPy restatement of its definition (tests/voxel_reference.py, whose
 inputs tests/test_voxel_reference.py holds to the conditions that keep these comparisons from being vacuous).  The outputs are integers
 and copied bits: every comparison is equality."""
+import re
+
 import numpy as np
 import pytest
 import torch
@@ -226,3 +228,61 @@ def test_refusals():
     empty = _voxelize(pc[:0], rng, size, T, V, return_voxel_of=True)
     assert empty.voxel_offsets.tolist() == [0, 0] and not empty.voxels.any() and bool((empty.coords == -1).all()) and not empty.num_points.any()
     assert empty.voxel_of.shape == (0,) and [tuple(v.shape) for v in empty.frames()[0]] == [(0, T, 4), (0, 4), (0,)]
+
+
+# ---- 9. every refusal of the Python boundary word for word, and which of two faults is reported --------------------------------------------------
+def _pin_batch():
+    """Two float32 frames of 64 rows."""
+    from lidar_snow_sim_amd.tensors import DeviceBatch
+    rows = (torch.arange(640, dtype=torch.float32, device="cuda:0").reshape(128, 5) % 17) / 4
+    return DeviceBatch(rows, np.array([0, 64, 128], np.int64))
+
+
+def _short_keep():
+    return torch.ones(127, dtype=torch.bool, device="cuda:0")
+
+
+def _voxel_out(**kw):
+    from lidar_snow_sim_amd.tensors import VoxelBatch
+    return VoxelBatch.empty(2, **kw)
+
+
+KEEP_WORDS = "keep must have one element per row of the batch (N_total, F x N, or a list of per-frame tensors)"
+DEVICE_WORDS = "the tensors live on cuda:0, device=1 was asked for"
+OUT_WORDS = "voxelize: out must be a VoxelBatch whose %s tensor on the device of the rows"
+PINNED = (
+    ("host rows", lambda: dict(frames=np.zeros((4, 5), np.float32)),
+     "voxelize: torch CUDA tensors or an aligned result (host arrays: lidar_snow_sim_amd.voxel.points_to_voxels)"),
+    ("max_points 2.5", lambda: dict(max_points=2.5), "voxelize: max_points must be an integer"),
+    ("max_voxels True", lambda: dict(max_voxels=True), "voxelize: max_voxels must be an integer"),
+    ("num_features 4.5", lambda: dict(num_features=4.5), "voxelize: num_features must be an integer"),
+    ("range of 5", lambda: dict(point_cloud_range=(0, 0, 0, 4, 4)), "voxelize: point_cloud_range holds 6 numbers (x0, y0, z0, x1, y1, z1), voxel_size 3"),
+    ("size of 2", lambda: dict(voxel_size=(1, 1)), "voxelize: point_cloud_range holds 6 numbers (x0, y0, z0, x1, y1, z1), voxel_size 3"),
+    ("num_features 6", lambda: dict(num_features=6), "voxelize: n_features must be 3, 4 or 5: the columns of a row that a voxel stores"),
+    ("max_points 0", lambda: dict(max_points=0), "voxelize: max_points and max_voxels must be at least 1"),
+    ("max_voxels 2^31", lambda: dict(max_voxels=2 ** 31), "voxelize: n_frames * max_voxels exceeds 2^31 - 1; split the batch"),
+    ("out of another shape", lambda: dict(out=_voxel_out(max_points=5, max_voxels=8)), OUT_WORDS % "voxels is a contiguous (16, 4, 4) torch.float32"),
+    ("out of another kind", lambda: dict(out=object()), OUT_WORDS % "voxels is a contiguous (16, 4, 4) torch.float32"),
+    ("out without voxel_of", lambda: dict(out=_voxel_out(max_points=4, max_voxels=8), return_voxel_of=True), OUT_WORDS % "voxel_of is a contiguous (128,) torch.int32"),
+    # two faults: the earlier step of the call reports
+    ("host rows before a count", lambda: dict(frames=np.zeros((4, 5), np.float32), max_points=2.5),
+     "voxelize: torch CUDA tensors or an aligned result (host arrays: lidar_snow_sim_amd.voxel.points_to_voxels)"),
+    ("a count before out", lambda: dict(max_points=2.5, out=object()), "voxelize: max_points must be an integer"),
+    ("the device before the domain", lambda: dict(device=1, max_points=0), DEVICE_WORDS),
+    ("keep before the domain", lambda: dict(keep=_short_keep(), num_features=6), KEEP_WORDS),
+    ("the domain before out", lambda: dict(max_points=0, out=object()), "voxelize: max_points and max_voxels must be at least 1"),
+)
+
+
+@pytest.mark.parametrize("overrides, words", [c[1:] for c in PINNED], ids=[c[0] for c in PINNED])
+def test_every_refusal_word_for_word(overrides, words):
+    args = dict(frames=_pin_batch(), point_cloud_range=(0, 0, 0, 4, 4, 4), voxel_size=(1, 1, 1), max_points=4, max_voxels=8)
+    args.update(overrides())
+    with pytest.raises(ValueError, match="^" + re.escape(words) + "$"):
+        _voxelize(**args)
+
+
+def test_the_wrapper_refuses_a_short_range_word_for_word():
+    from lidar_snow_sim_amd import engine
+    with pytest.raises(ValueError, match="^" + re.escape("snowgpu_voxelize_device: point_cloud_range holds 6 numbers (x0, y0, z0, x1, y1, z1), voxel_size 3") + "$"):
+        engine.get_engine(0).ctx.voxelize_device(2, 128, 64, 0, 0, 0, (0, 0, 0, 4, 4), (1, 1, 1), 4, 8, 4, 0, 0, 0, 0, 0)
