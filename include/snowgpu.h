@@ -938,6 +938,60 @@ int snowgpu_points_in_boxes_device(snowgpu_ctx *ctx, int n_frames, int64_t n_tot
                                    double *d_out_pose /* or NULL */, void *stream);
 
 /*
+ * RoI POINT POOLING of an aligned batch: for every roi of a frame the first S rows inside the slightly enlarged box, in row order, and
+ * each of them in the roi's own frame -- pcdet's roipoint_pool3d as PointRCNNHead.roipool3d_gpu calls it, the input of a point-based
+ * second stage, with static shapes and nothing read on the host.  snowgpu_points_in_boxes_device cannot stand in for it: its box_of names
+ * only the smallest containing box, and proposals overlap.  Frames, rows (N_total x 5, float32 or float64 = T), frame offsets and the input
+ * keep mask as snowgpu_points_in_boxes_device takes them.  F = n_frames, M = n_rois per frame, S = n_samples, C = num_features.  The
+ * definition is restated as brute-force NumPy by tests/roipool_reference.py.
+ *   A row is USABLE exactly as for snowgpu_points_in_boxes_device: present and |x|, |y|, |z| <= 1e6 (false for NaN).
+ *   ROIS: d_rois is (F, M, Cb) in T, Cb = roi_features in 7 .. 10, 1 <= M <= 512; columns 0 .. 6 are cx, cy, cz, dx, dy, dz, heading: the
+ *   layout of gt_boxes, of the kept boxes of snowgpu_nms_device and of the rois of snowgpu_fps_sectors_device.
+ *   ENLARGED BOX: centre and heading are kept; dx' = (double)dx + ew[0], dy' = (double)dy + ew[1], dz' = (double)dz + ew[2], each one
+ *   float64 add -- pcdet's enlarge_box3d, where the width is added ONCE to each size.  extra_width3 NULL: zeros.
+ *   A roi is PRESENT when the presence rule of snowgpu_points_in_boxes_device holds for the ENLARGED box -- all seven values finite, the
+ *   1e6 bounds, 0 < dx', dy', dz' <= 1e6, the pose check -- AND its original dx, dy and dz are > 0.  Zero padding rows and the zero rows
+ *   behind the count of snowgpu_nms_device are absent by the first rule when ew = 0; with ew > 0 a zero row would become a box of size ew,
+ *   which the second rule forbids.
+ *   POSE: as for snowgpu_points_in_boxes_device -- the caller's (F, M, 2) float64 (cos, sin) used as it is, or with NULL cos / sin of
+ *   (double)heading from the device library; |(c c + s s) - 1| > 1e-6 makes the roi absent.  d_out_pose receives the pose that was used,
+ *   (0, 0) for an absent roi.
+ *   MEMBERSHIP: the library's one rule, on the enlarged record -- float64, every operation rounded on its own, no fused multiply-add:
+ *   sx = x - cx, sy = y - cy, sz = z - cz; lx = sx c + sy s, ly = sy c - sx s; inside iff |sz| <= dz' / 2, |lx| < dx' / 2 + 1e-5 and
+ *   |ly| < dy' / 2 + 1e-5.  pcdet's roipoint op makes its test in float32 with cosf / sinf of -heading: the two differ only for rows within
+ *   float32 rounding of a face.  The 1e-5 margin is this library's rule as it stands (check_pt_in_box3d of roiaware_pool3d has it).  As far as
+ *   recalled, roipoint_pool3d's own check_pt_in_box3d compares with dx / 2 and dy / 2 WITHOUT a margin; this was NOT CHECKED against
+ *   pcdet's source.  If so, the two differ for rows within 1e-5 m of an x or y face as well.
+ *   ORDER: the members of roi (f, m) are the usable rows of frame f inside it in ASCENDING ROW INDEX, cnt their number.
+ * Outputs, every shape static, every element written by every call, nothing needs clearing:
+ *   d_out_index   (F, M, S) int32: slot j < S holds the global row index of member j mod cnt when cnt > 0 -- pcdet's wrap-around fill,
+ *                 idx[k] = idx[k % cnt]; every slot is -1 when cnt = 0, an absent roi or an empty one
+ *   d_out_count   (F, M) int32: cnt, the full number of members, NOT clipped at S; 0 for an absent roi
+ *   d_out_points  (F, M, S, C) T, or NULL: the first C columns of rows[index], bit copies; zeros where index is -1
+ *   d_out_local   (F, M, S, 3) T, or NULL: (T)lx, (T)ly, (T)sz of that row with respect to its roi -- the head's canonical transformation,
+ *                 centre subtracted and rotated by -heading, as d_out_local of snowgpu_points_in_boxes_device; zeros where index is -1
+ *   d_out_pose    (F, M, 2) float64, or NULL
+ *   Sizes: at F = 256, M = 128, S = 512 the index is 67 MB and the points at C = 4 float32 268 MB.
+ * Domain: 1 <= M <= 512; 1 <= S <= 2048; C in 3 .. 5; Cb in 7 .. 10; every component of ew finite and in 0 .. 100; F M S max(C, 3) <=
+ * 2^31 - 1; n_total < 2^31; no frame above 2^30 rows; F M (the 512-row runs of the longest frame) <= 2^31 - 1; dtype 0 or 1; every output
+ * apart from the rows, the keep mask, the rois, the given pose and every other output.  Anything else is SNOWGPU_E_INVALID with a message.
+ * A batch without a row writes -1, zeros and the pose and launches nothing over rows (d_rows may be NULL).  The result depends on neither
+ * a cell order nor the arrival of atomics: two calls give identical bytes.
+ * The enlarged rois are filed as the boxes of snowgpu_points_in_boxes_device are.  The rows of a frame are cut into runs of 512; one wave
+ * owns a run, visits every roi marked in its rows' cells once per 64 rows and takes the ballot of the member lanes: lane order is row
+ * order.  The walk runs twice -- the runs' counts, a scan over the runs of every (frame, roi), then the ranks -- which is the price of row
+ * order without a sort; a last kernel resolves the wrap-around and writes points and local (csrc/sg_roipool.h, csrc/snowgpu_roipool.hip).
+ * Scratch in the context, grown on first use: per frame 4097 ceil(M / 64) words, M records and M int32 per run.  Five kernels on `stream`,
+ * no memset; nothing is read on the host, nothing allocated after the first call of a size: capturable as a linear graph.
+ */
+int snowgpu_roi_point_pool_device(snowgpu_ctx *ctx, int n_frames, int64_t n_total, int64_t max_frame_rows, const int64_t *d_frame_offsets,
+                                  const void *d_rows, int dtype, int n_rois, const void *d_rois, int roi_features,
+                                  const double *extra_width3 /* host, 3 doubles, or NULL = zeros */, int n_samples, int num_features,
+                                  const double *d_pose_in /* or NULL */, const uint8_t *d_keep_in /* or NULL: all present */,
+                                  int32_t *d_out_index, int32_t *d_out_count, void *d_out_points /* or NULL */, void *d_out_local /* or NULL */,
+                                  double *d_out_pose /* or NULL */, void *stream);
+
+/*
  * ROTATED BOX IoU AND NMS: pcdet's iou3d_nms family -- boxes_iou_bev, boxes_iou3d_gpu, nms_gpu -- with static shapes, nothing read on the
  * host.  snowgpu_boxes_iou_device gives the overlap of every box of one set with every box of another (the target layer's rois against
  * gt_boxes) and, without materialising the matrix, the best partner of every box; snowgpu_nms_device gives the keep list of scored

@@ -323,6 +323,13 @@ struct SgBoxRec;
 int sg_launch_box(const void *rows, int dtype, int64_t n, const int64_t *frame_off, int n_frames, const uint8_t *keep_in, int32_t n_boxes,
                   const void *boxes, int32_t box_features, const double *pose_in, struct SgBoxRec *rec, unsigned long long *table, int32_t *out_box_of,
                   int32_t *out_count, void *out_local, double *out_pose, void *stream);
+// RoI point pooling (sg_roipool.h; the definition: include/snowgpu.h): five kernels.  Scratch: rec and table as above for n_rois; run_cnt,
+// sg_roi_table(n_frames, max_frame, n_rois) int32.  ew: 3 host doubles.  pose_in, out_points, out_local and out_pose may be null.  A batch
+// without a row runs the first and the last kernel.
+int sg_launch_roipool(const void *rows, int dtype, int64_t n, int64_t max_frame, const int64_t *frame_off, int n_frames, const uint8_t *keep_in,
+                      int32_t n_rois, const void *rois, int32_t roi_features, const double *ew, int32_t n_samples, int32_t num_features,
+                      const double *pose_in, struct SgBoxRec *rec, unsigned long long *table, int32_t *run_cnt, int32_t *out_index, int32_t *out_count,
+                      void *out_points, void *out_local, double *out_pose, void *stream);
 // Rotated box IoU and NMS (sg_iou.h; the definition: include/snowgpu.h): three kernels each.  Scratch: rec, sg_iou_records() doubles for
 // n_frames (M + B) boxes (the IoU) or n_frames B (NMS); order, n_frames B; n_cand, n_frames.  The poses and every output but the NMS
 // index and count may be null (the IoU needs one output).

@@ -523,6 +523,66 @@ static inline int sg_check_box_args(const SgBoxArgs &a, std::string *msg)
     return 0;
 }
 
+// ---- snowgpu_roi_point_pool_device --------------------------------------------------------------------------------------------------------
+struct SgRoiPoolArgs {
+    int n_frames;
+    int64_t n_total, max_frame_rows;
+    int dtype;
+    const int64_t *frame_off;
+    const void *rows;
+    int n_rois;                       // M, per frame
+    const void *rois;
+    int roi_features;                 // Cb
+    const double *extra_width;        // host, 3 doubles, or NULL: zeros
+    int n_samples;                    // S
+    int num_features;                 // C
+    const double *pose_in;            // or NULL: cos / sin of the heading on the device
+    const uint8_t *keep_in;
+    int32_t *out_index;
+    int32_t *out_count;
+    void *out_points;                 // or NULL
+    void *out_local;                  // or NULL
+    double *out_pose;                 // or NULL
+};
+
+// 0, or SG_ARGS_INVALID with *msg.  As above, the order is part of the ABI.
+static inline int sg_check_roipool_args(const SgRoiPoolArgs &a, std::string *msg)
+{
+    static const char *who = "snowgpu_roi_point_pool_device";
+    if (a.n_frames <= 0 || a.n_total < 0 || !a.frame_off || !a.rois || !a.out_index || !a.out_count || (a.n_total > 0 && !a.rows) || (a.dtype != 0 && a.dtype != 1))
+        return sg_refuse(who, ": null pointer or bad dtype", msg);
+    if (a.n_total >= ((int64_t)1 << 31)) return sg_refuse("", "batch too large: split it below 2^31 rows", msg);
+    if (a.n_rois < 1 || a.n_rois > 512) return sg_refuse(who, ": n_rois must lie in 1 .. 512", msg);
+    if (a.roi_features < 7 || a.roi_features > 10) return sg_refuse(who, ": roi_features must lie in 7 .. 10: cx, cy, cz, dx, dy, dz, heading first", msg);
+    if (a.n_samples < 1 || a.n_samples > 2048) return sg_refuse(who, ": n_samples must lie in 1 .. 2048", msg);
+    if (a.num_features < 3 || a.num_features > 5) return sg_refuse(who, ": num_features must be 3, 4 or 5: the columns of a row that a roi stores", msg);
+    for (int j = 0; a.extra_width && j < 3; ++j)
+        if (!(a.extra_width[j] >= 0.0 && a.extra_width[j] <= 100.0))                         // (false for NaN)
+            return sg_refuse(who, ": every component of extra_width must be finite and lie in 0 .. 100", msg);
+    if ((int64_t)a.n_frames * a.n_rois * a.n_samples * (a.num_features > 3 ? a.num_features : 3) > ((int64_t)1 << 31) - 1)
+        return sg_refuse(who, ": n_frames * n_rois * n_samples * max(num_features, 3) exceeds 2^31 - 1; split the batch", msg);
+    const int64_t longest = sg_max_frame(a.max_frame_rows, a.n_total);
+    if (longest > ((int64_t)1 << 30)) return sg_refuse(who, ": a frame of more than 2^30 rows; split it", msg);
+    if ((int64_t)a.n_frames * a.n_rois * (longest / 512 + 1) > ((int64_t)1 << 31) - 1)    // (n_frames n_rois < 2^31 by the sample check)
+        return sg_refuse(who, ": n_frames * n_rois * the 512-row runs of the longest frame exceeds 2^31 - 1; split the batch", msg);
+    const size_t esz = a.dtype == 0 ? 4 : 8, q = (size_t)a.n_frames * (size_t)a.n_rois, n = (size_t)a.n_total, k = q * (size_t)a.n_samples;
+    const struct { const void *p; size_t bytes; const char *name; } outs[5] = {
+        {a.out_index, k * 4, "d_out_index"}, {a.out_count, q * 4, "d_out_count"}, {a.out_points, k * (size_t)a.num_features * esz, "d_out_points"},
+        {a.out_local, k * 3 * esz, "d_out_local"}, {a.out_pose, q * 16, "d_out_pose"}};
+    const struct { const void *p; size_t bytes; const char *name; } ins[4] = {
+        {a.keep_in, n, "d_keep_in"}, {a.rows, n * 5 * esz, "d_rows"}, {a.rois, q * (size_t)a.roi_features * esz, "d_rois"}, {a.pose_in, q * 16, "d_pose_in"}};
+    for (int i = 0; i < 5; ++i) {
+        const auto &o = outs[i];
+        for (int j = 0; j < 4; ++j)
+            if (sg_ranges_meet(o.p, o.bytes, ins[j].p, ins[j].bytes))
+                return sg_refuse(who, (std::string(": ") + o.name + " overlaps " + ins[j].name + "; the mask, the rows, the rois and the pose are read while the pool is written: pass a buffer apart from them").c_str(), msg);
+        for (int j = 0; j < i; ++j)
+            if (sg_ranges_meet(o.p, o.bytes, outs[j].p, outs[j].bytes))
+                return sg_refuse(who, (std::string(": ") + o.name + " overlaps " + outs[j].name + "; every output needs memory of its own").c_str(), msg);
+    }
+    return 0;
+}
+
 // ---- snowgpu_boxes_iou_device -------------------------------------------------------------------------------------------------------------
 struct SgIouArgs {
     int n_frames;

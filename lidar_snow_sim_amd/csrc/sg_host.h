@@ -113,6 +113,11 @@ struct __attribute__((visibility("default"))) snowgpu_ctx {
     // points in boxes (snowgpu_points_in_boxes_device): one record of eight doubles per box, and per frame the bit table of its cells
     DevBuf<double> box_rec;
     DevBuf<unsigned long long> box_table;
+    // RoI point pooling (snowgpu_roi_point_pool_device): the records and the bit table of the enlarged rois, as above, and one int32 per
+    // (frame, run of 512 rows, roi): the roi's members in the run, then in the runs before it
+    DevBuf<double> roi_rec;
+    DevBuf<unsigned long long> roi_table;
+    DevBuf<int32_t> roi_runs;
     // box IoU and NMS (snowgpu_boxes_iou_device, snowgpu_nms_device): one record of nine doubles per box; the ranking and its length
     DevBuf<double> iou_rec;
     DevBuf<int32_t> nms_order, nms_cand;

@@ -1,5 +1,5 @@
 // snowgpu_device.cpp -- the entries of the C ABI (include/snowgpu.h) that take DEVICE pointers and enqueue on the caller's stream: every
-// *_batch_device* entry, the plane estimate, the FOV mask, the outlier filter, the voxel stage, the keypoint stage and its sectorized form, the ball query, the range image, the nearest centres, the points in boxes, the box IoU and NMS and the weather draw.  Each batch entry fills an SgDeviceArgs, has it checked
+// *_batch_device* entry, the plane estimate, the FOV mask, the outlier filter, the voxel stage, the keypoint stage and its sectorized form, the ball query, the range image, the nearest centres, the points in boxes, the RoI point pooling, the box IoU and NMS and the weather draw.  Each batch entry fills an SgDeviceArgs, has it checked
 // (sg_device_args.h: every refusal, in one order), sets the device and runs batch_from_args() and the stages it needs.  The launch
 // sequence of a batch is snowgpu_batch.cpp; no host copy, no synchronisation, no allocation after the first call of a given size.
 #include "sg_host.h"
@@ -12,6 +12,7 @@
 #include "sg_ball.h"        // the grid of the ball query and the sizes of its scratch
 #include "sg_nn.h"          // the grid of the nearest-centres stage and the sizes of its scratch
 #include "sg_box.h"         // the record of a box and the sizes of the box stage's scratch
+#include "sg_roipool.h"     // the enlarged roi and the size of the pooling stage's run table
 #include "sg_iou.h"         // the record of the IoU and NMS stages and the size of their scratch
 #include "sg_range.h"       // the geometry of the range image and the limits in the rows' dtype
 
@@ -619,6 +620,32 @@ extern "C" int snowgpu_points_in_boxes_device(snowgpu_ctx *ctx, int n_frames, in
     int e = sg_launch_box(d_rows, dtype, n_total, d_frame_offsets, n_frames, d_keep_in, n_boxes, d_boxes, box_features, d_pose_in, (SgBoxRec *)ctx->box_rec.p,
                           ctx->box_table.p, d_out_box_of, d_out_count, d_out_local, d_out_pose, stream ? (hipStream_t)stream : ctx->stream);
     if (e) return fail(ctx, SNOWGPU_E_HIP, std::string("points in boxes launch: ") + hipGetErrorString((hipError_t)e));
+    return SNOWGPU_OK;
+}
+
+// RoI point pooling (snowgpu_roipool.hip; the enlarged roi, the runs and the scratch: sg_roipool.h).  See include/snowgpu.h.
+extern "C" int snowgpu_roi_point_pool_device(snowgpu_ctx *ctx, int n_frames, int64_t n_total, int64_t max_frame_rows, const int64_t *d_frame_offsets,
+                                             const void *d_rows, int dtype, int n_rois, const void *d_rois, int roi_features, const double *extra_width3,
+                                             int n_samples, int num_features, const double *d_pose_in, const uint8_t *d_keep_in, int32_t *d_out_index,
+                                             int32_t *d_out_count, void *d_out_points, void *d_out_local, double *d_out_pose, void *stream)
+{
+    if (!ctx) return SNOWGPU_E_INVALID;
+    const SgRoiPoolArgs a{n_frames, n_total, max_frame_rows, dtype, d_frame_offsets, d_rows, n_rois, d_rois, roi_features, extra_width3, n_samples, num_features,
+                          d_pose_in, d_keep_in, d_out_index, d_out_count, d_out_points, d_out_local, d_out_pose};
+    {
+        std::string msg;
+        if (int rc = sg_check_roipool_args(a, &msg)) return fail(ctx, rc, msg);
+    }
+    const double ew[3] = {extra_width3 ? extra_width3[0] : 0.0, extra_width3 ? extra_width3[1] : 0.0, extra_width3 ? extra_width3[2] : 0.0};
+    const int64_t longest = sg_max_frame(max_frame_rows, n_total);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    ENSURE(ctx, ctx->roi_rec, sg_box_records(n_frames, n_rois) * (sizeof(SgBoxRec) / sizeof(double)));
+    ENSURE(ctx, ctx->roi_table, sg_box_table(n_frames, n_rois));
+    if (n_total > 0) ENSURE(ctx, ctx->roi_runs, sg_roi_table(n_frames, longest, n_rois));
+    int e = sg_launch_roipool(d_rows, dtype, n_total, longest, d_frame_offsets, n_frames, d_keep_in, n_rois, d_rois, roi_features, ew, n_samples, num_features,
+                              d_pose_in, (SgBoxRec *)ctx->roi_rec.p, ctx->roi_table.p, ctx->roi_runs.p, d_out_index, d_out_count, d_out_points, d_out_local,
+                              d_out_pose, stream ? (hipStream_t)stream : ctx->stream);
+    if (e) return fail(ctx, SNOWGPU_E_HIP, std::string("roi point pool launch: ") + hipGetErrorString((hipError_t)e));
     return SNOWGPU_OK;
 }
 

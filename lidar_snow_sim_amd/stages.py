@@ -1,6 +1,6 @@
 """The device stages of the torch-tensor boundary (tensors.py is the documented import path and lists what each is for) and the batches
 of static shape they leave behind: fov_keep, dror_keep, voxelize, sample_keypoints, ball_query, range_image, nearest_keypoints,
-points_in_boxes, boxes_iou, nms.  Every stage goes through the same steps, in this order -- it is the order in which a call that is wrong
+points_in_boxes, boxes_iou, nms, roi_point_pool.  Every stage goes through the same steps, in this order -- it is the order in which a call that is wrong
 in two ways is refused: the aligned unwrap and the device-input refusal (_stage_frames), the scalar and range checks (_whole, _range6),
 the batch and its keep mask (_stage_batch), the stage's own tensors, the checks of the shapes' domain, out= (_checked_out), the launch
 (_stage_launch).  PyTorch is plumbing here; the work is the C entries'."""
@@ -808,3 +808,114 @@ def nms(boxes, scores, iou_thresh, *, post_max, score_thresh=-math.inf, mode='be
                            0 if kk is None else kk.data_ptr(), run.cuda_stream)
     same = (kb is None) == (out.boxes is None) and (ks is None) == (out.scores is None) and (kk is None) == (out.kept is None)
     return out if same else NmsBatch(out.index, out.count, kb, ks, kk)
+
+
+class RoiPointBatch:
+    """What roi_point_pool() leaves behind, F = frames, M = rois per frame, S = n_samples, C = num_features -- every shape static: `index`
+    (F, M, S int32: the global row index of the roi's member j mod cnt, members in ascending row order -- pcdet's wrap-around fill; -1
+    in every slot of an absent or empty roi), `count` (F, M int32: the members of the roi, NOT clipped at S; 0 for an absent roi), `points`
+    (F, M, S, C in the rows' dtype: the first C columns of rows[index], zeros where index is -1; None unless asked for), `local` (F, M, S, 3:
+    the row in the frame of its roi -- along its length, its width, and up from its centre --, zeros where index is -1; None unless asked
+    for) and `pose` (F, M, 2 float64: the (cos, sin) of the heading that was used, (0, 0) for an absent roi; None unless asked for).
+    gather() and labels() are pure indexing, no kernel of this library.  At F = 256, M = 128, S = 512 `index` is 67 MB and `points` at
+    C = 4 float32 268 MB.  All still being written until the stream the call was made on has caught up."""
+
+    def __init__(self, index, count, points=None, local=None, pose=None):
+        self.index, self.count, self.points, self.local, self.pose = index, count, points, local, pose
+
+    @classmethod
+    def empty(cls, n_frames, n_rois, n_samples=512, num_features=4, dtype=None, device=None, with_points=True, with_local=False, with_pose=False):
+        """Uninitialised buffers of the shapes roi_point_pool() writes (out=): static addresses for a captured graph."""
+        import torch
+        dev = _cuda_device(torch, device)
+        F, M, S, C, dt = int(n_frames), int(n_rois), int(n_samples), int(num_features), dtype or torch.float32
+        return cls(torch.empty((F, M, S), dtype=torch.int32, device=dev), torch.empty((F, M), dtype=torch.int32, device=dev),
+                   torch.empty((F, M, S, C), dtype=dt, device=dev) if with_points else None,
+                   torch.empty((F, M, S, 3), dtype=dt, device=dev) if with_local else None,
+                   torch.empty((F, M, 2), dtype=torch.float64, device=dev) if with_pose else None)
+
+    @property
+    def empty_flag(self):
+        """(F, M) bool: count == 0 -- roipoint_pool3d's pooled_empty_flag; an absent roi is empty."""
+        return self.count == 0
+
+    def gather(self, per_row):
+        """Per-row values (N,) or (N, D) -- per-point features, the depth, the first stage's segmentation score -- as (F, M, S) or
+        (F, M, S, D): the value of the pooled row, zeros where index is -1.  What joins `points` and `local` to pooled_features."""
+        import torch
+        if not (torch.is_tensor(per_row) and per_row.dim() in (1, 2) and per_row.device == self.index.device):
+            raise ValueError("gather: per_row must be an (N,) or (N, D) tensor on the device of the rows: one value, or D of them, per row")
+        at = self.index.long()
+        got = per_row[at.clamp(min=0)]
+        has = at >= 0
+        return torch.where(has[..., None] if got.dim() == 4 else has, got, torch.zeros_like(got))
+
+    def labels(self, box_labels):
+        """box_labels.box_of[index] (F, M, S int32) with -1 kept: the points_in_boxes label of every pooled row."""
+        import torch
+        if not isinstance(box_labels, BoxLabelBatch) or box_labels.box_of.device != self.index.device:
+            raise ValueError("labels: box_labels must be a BoxLabelBatch on the device of the rows")
+        at = self.index.long()
+        return torch.where(at >= 0, box_labels.box_of[at.clamp(min=0)], torch.full_like(self.index, -1))
+
+
+def roi_point_pool(frames, rois, n_samples=512, *, extra_width=(0., 0., 0.), pose=None, keep=None, num_features=4, out=None, return_points=True,
+                   return_local=False, return_pose=False, device=None, slot=0):
+    """The first n_samples rows inside every slightly enlarged roi, in row order, on the device (snowgpu_roi_point_pool_device; the
+    definition: include/snowgpu.h): pcdet's roipoint_pool3d as PointRCNNHead.roipool3d_gpu calls it, with points_in_boxes' membership test
+    in float64 and static shapes.  A row takes part if it is present and within 1e6 of the origin on every axis.
+
+    frames    what points_in_boxes takes -- torch CUDA tensors, a DeviceBatch, or an AlignedResult / AlignedWetResult: its rows, offsets
+              and keep mask are used (nothing is waited for).
+    rois      a contiguous (F, M, 7 .. 10) tensor in the rows' dtype on their device, 1 <= M <= 512: cx, cy, cz, dx, dy, dz, heading
+              first -- or an NmsBatch, whose `boxes` are used (the zero rows behind its count are absent rois).
+    n_samples 1 .. 2048: S, the rows a roi stores; a roi of fewer members repeats them (slot j holds member j mod count).
+    extra_width   a number or three (x, y, z), each in 0 .. 100: added once to dx, dy, dz (enlarge_box3d).
+    pose      None: cos / sin of the heading in float64 on the device; or a contiguous (F, M, 2) float64 tensor (cos, sin) used as it is.
+    keep      an input keep mask as the aligned calls take it (with a result: ANDed with the result's own).
+    num_features  3, 4 or 5: the columns of a row that `points` stores.
+    out       a RoiPointBatch to write into (RoiPointBatch.empty): every element is written, nothing needs clearing.
+
+    Returns a RoiPointBatch.  Asynchronous on torch's current stream; nothing is read on the host: capturable after one warm-up call."""
+    import torch
+    who = "roi_point_pool"
+    frames, keep = _stage_frames(torch, who, "lidar_snow_sim_amd.roipool.roipoint_pool3d", frames, keep)
+    _whole(who, n_samples=n_samples, num_features=num_features)
+    ew = np.asarray(extra_width, np.float64).reshape(-1)
+    if ew.shape == (1,):
+        ew = np.repeat(ew, 3)
+    if ew.shape != (3,) or not ((ew >= 0.0) & (ew <= 100.0)).all():
+        raise ValueError("roi_point_pool: extra_width is a number or three (x, y, z), each finite and in 0 .. 100")
+    rows, offsets, eng, dev, nf, n, keep = _stage_batch(torch, frames, keep, device, slot)
+    if isinstance(rois, NmsBatch):
+        if rois.boxes is None:
+            raise ValueError("roi_point_pool: this NmsBatch has no boxes (nms(..., return_boxes=True))")
+        rois = rois.boxes
+    if not (torch.is_tensor(rois) and rois.dim() == 3 and rois.shape[0] == nf and rois.dtype == rows.dtype and rois.device == dev and rois.is_contiguous()):
+        raise ValueError("roi_point_pool: rois must be a contiguous (frames, M, 7 .. 10) tensor in the rows' dtype on their device, or an NmsBatch of such boxes")
+    M, Cb, S, C = int(rois.shape[1]), int(rois.shape[2]), int(n_samples), int(num_features)
+    # (the shapes below need these; the entry refuses them in the same words, and everything else of the domain)
+    if not 1 <= M <= 512:
+        raise ValueError("roi_point_pool: n_rois must lie in 1 .. 512 (rois)")
+    if not 7 <= Cb <= 10:
+        raise ValueError("roi_point_pool: roi_features must lie in 7 .. 10: cx, cy, cz, dx, dy, dz, heading first (rois)")
+    if not 1 <= S <= 2048:
+        raise ValueError("roi_point_pool: n_samples must lie in 1 .. 2048")
+    if not 3 <= C <= 5:
+        raise ValueError("roi_point_pool: num_features must be 3, 4 or 5: the columns of a row that a roi stores")
+    if nf * M * S * max(C, 3) > 2 ** 31 - 1:
+        raise ValueError("roi_point_pool: n_frames * n_rois * n_samples * max(num_features, 3) exceeds 2^31 - 1; split the batch")
+    if pose is not None and not (torch.is_tensor(pose) and tuple(pose.shape) == (nf, M, 2) and pose.dtype == torch.float64 and pose.device == dev and pose.is_contiguous()):
+        raise ValueError(f"roi_point_pool: pose must be a contiguous {(nf, M, 2)} float64 tensor (cos, sin) on the device of the rows")
+    want = (("index", torch.int32, (nf, M, S), True), ("count", torch.int32, (nf, M), True), ("points", rows.dtype, (nf, M, S, C), return_points),
+            ("local", rows.dtype, (nf, M, S, 3), return_local), ("pose", torch.float64, (nf, M, 2), return_pose))
+    if out is None:
+        out = RoiPointBatch.empty(nf, M, S, C, rows.dtype, dev, return_points, return_local, return_pose)
+    else:
+        _checked_out(torch, who, RoiPointBatch, out, want, dev, _ROWS)
+    points, local, used = (out.points if return_points else None), (out.local if return_local else None), (out.pose if return_pose else None)
+    _stage_launch(torch, eng, dev, nf, n, offsets, rows, eng.ctx.roi_point_pool_device, M, rois.data_ptr(), Cb, ew, S, C, 0 if pose is None else pose.data_ptr(),
+                  0 if keep is None or not n else keep.data_ptr(), out.index.data_ptr(), out.count.data_ptr(), 0 if points is None else points.data_ptr(),
+                  0 if local is None else local.data_ptr(), 0 if used is None else used.data_ptr())
+    same = (points is None) == (out.points is None) and (local is None) == (out.local is None) and (used is None) == (out.pose is None)
+    return out if same else RoiPointBatch(out.index, out.count, points, local, used)
