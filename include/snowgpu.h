@@ -188,7 +188,8 @@ int snowgpu_debug_table_bins(snowgpu_ctx *ctx, int table_id, uint32_t *bin_start
                              uint32_t *bin_q, int64_t cap_q, uint32_t *bin_qs, int64_t cap_qs, int64_t *info, double *qs_per_m);
 
 /* Status words (int32[8], layout under snowgpu_augment_batch_device) of the last batch that went through a host-pointer
- * entry of this context: e.g. out8[2..5] = beams each later list capacity took (summed over the chunks of a pipelined batch). */
+ * entry of this context: e.g. out8[2..5] = beams each later list capacity took, out8[6] = beams the row kernels redid with the
+ * pairwise sum (each summed over the chunks of a pipelined batch). */
 int snowgpu_last_status(snowgpu_ctx *ctx, int32_t *out8);
 
 /* What the status words of a DEVICE-pointer entry mean: the caller of snowgpu_augment_batch_device / snowgpu_augment_wet_batch_device
@@ -260,7 +261,8 @@ int snowgpu_augment_batch_compact(snowgpu_ctx *ctx, int n_frames, const int64_t 
  * the entry point bench.py times.  max_frame_rows = rows of the largest frame (sizes the per-frame grids;
  * 0 = unknown, n_total is used; when max_frame_rows * n_frames == n_total all frames are taken to be that size).
  * d_status (device int32[8]) receives {[0] error code, [1] first offending sorted row or -1, [2] [3] [4] [5] beams handed
- * to the 2nd / 3rd / 4th / 5th list capacity (the last one in use is the global-list tier), [6] [7] unused}; check it
+ * to the 2nd / 3rd / 4th / 5th list capacity (the last one in use is the global-list tier), [6] beams the row kernels redid with the pairwise sum; 0 in list mode
+ * (a count like [2] .. [5]: snowgpu_status_error ignores it), [7] unused}; check it
  * after synchronising the stream.  The call forks work onto the context's side streams and joins
  * them back before the compaction kernels, so everything is ordered after earlier work and before later work on
  * `stream`; one batch at a time per context (its scratch buffers are reused).

@@ -815,7 +815,7 @@ class Context:
                     max_bin=int(info[2]), qs_steps=int(info[3]), qs_per_m=float(per_m[0]))
 
     def last_status(self):
-        """int32[8] status words of the last host-entry batch ([2..5]: beams per later capacity tier)."""
+        """int32[8] status words of the last host-entry batch ([2..5]: beams per later capacity tier; [6]: beams the row kernels redid with the pairwise sum)."""
         out = np.zeros(8, np.int32)
         self._check(self._L.snowgpu_last_status(self._h, _p(out)))
         return out

@@ -482,7 +482,7 @@ static int host_batch_pipelined(snowgpu_ctx *ctx, int n_frames, const int64_t *f
             agg[0] = s8[0];
             agg[1] = s8[1] >= 0 ? (int32_t)std::min<int64_t>(s8[1] + frame_offsets[c_first[(size_t)c]], INT32_MAX) : -1;
         }
-        for (int k = 2; k < 6; ++k) agg[k] += s8[k];
+        for (int k = 2; k < 7; ++k) agg[k] += s8[k];        // tier populations and the row kernels' redone beams
     }
     std::memcpy(ctx->h_status, agg, sizeof agg);
     return status_to_error(ctx, agg);

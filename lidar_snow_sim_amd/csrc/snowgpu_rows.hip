@@ -271,6 +271,9 @@ __global__ __launch_bounds__(RW_BLOCK, PAIRWISE ? 2 : RW_WAVES) void k_rows(SgBe
     const int n_las = a.las->n;
     int64_t work_n = PAIRWISE ? a.redo_cnt[a.cls] : a.tier_info[a.cls];      // PAIRWISE: the beams the first instantiation deferred
     if (work_n > a.work_hi) work_n = a.work_hi;
+    if constexpr (PAIRWISE) {                                             // status word 6: the beams redone, summed over the class launches
+        if (blockIdx.x == 0 && tid == 0 && work_n > 0) atomicAdd(&a.status[6], (int32_t)work_n);
+    }
     const int64_t work_off = (int64_t)a.cls * a.tier_stride;
     const int32_t *work_list = PAIRWISE ? a.redo_list : a.tier_list;
     const int waves = (int)gridDim.x * (RW_BLOCK / 64);
