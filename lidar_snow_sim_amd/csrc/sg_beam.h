@@ -394,30 +394,6 @@ __device__ __forceinline__ void sg_hit_angles(uint32_t w, const SgEntry *__restr
     a2 = (w & 0x80000000u) ? theta_l : f->t1;                   // geometry.py:27
 }
 
-// The same for a whole short list with ONE round of loads: the tangent angles of every listed record (16 bytes each, one load) are
-// requested before the first is used, whether the word's bits will want them or not -- with the loads under those bits the compiler
-// waited for each entry's pair before it asked for the next (four round trips for a four-entry list).  w[j], j >= L: any word (entry 0 is read).
-template <int N>
-__device__ __forceinline__ void sg_hit_angles_all(const uint32_t (&w)[N], int L, const SgEntry *__restrict__ entries, double theta_r, double theta_l,
-                                                  double (&a1)[N], double (&a2)[N])
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    SgTailRaw raw[N];
-#pragma unroll
-    for (int j = 0; j < N; ++j) {
-        const SG_GLOBAL SgEntry *f = sg_gptr(entries) + (j < L ? (w[j] & 0x3fffffffu) : 0u);
-        raw[j] = *reinterpret_cast<const SG_GLOBAL SgTailRaw *>(&f->t0);
-    }
-#pragma unroll
-    for (int j = 0; j < N; ++j) {
-        a1[j] = (w[j] & 0x40000000u) ? theta_r : __hiloint2double((int)raw[j].y, (int)raw[j].x);      // geometry.py:26
-        a2[j] = (w[j] & 0x80000000u) ? theta_l : __hiloint2double((int)raw[j].w, (int)raw[j].z);      // geometry.py:27
-    }
-#else
-    for (int j = 0; j < N; ++j) if (j < L) sg_hit_angles(w[j], entries, theta_r, theta_l, a1[j], a2[j]);
-#endif
-}
-
 // Two neighbouring words of the step-major range index (sg_range_index.h) as ONE load.  The address is 4-byte aligned only, which a
 // global load of 8 bytes allows.
 struct SgQsPair { uint32_t x, y; };
@@ -450,7 +426,8 @@ __device__ __forceinline__ SgQsPair sg_qs_load(const uint32_t *p) { return SgQsP
 // COMPACT (the pass over all rows): the list keeps, per flake, its range (the sort key) and ONE word instead of the two interval angles --
 // the record's index in the table | bit 30: the left angle is the beam's right limit | bit 31: the right angle is the beam's left limit
 // (geometry.py:26-27; otherwise they are the record's tangent angles t0 / t1) -- in the column s_a1 points to, read as uint32_t; s_a2 is
-// not used.  The caller resolves the word when it hands the list on (sg_hit_angles).  19 KB of LDS per 256 beams instead of 31.
+// not used.  The word is resolved later: by the readers of the dict queue the list is handed to (sg_queue.h), by the caller for an overflow
+// slot (sg_hit_angles).  19 KB of LDS per 256 beams instead of 31.
 // UTAB (the segment order of the pass over all rows): every lane of the wave passes the SAME table -- the descriptor lives in scalar
 // registers and the owner's table pointer does not travel with its geometry.
 // theta_t: the beam's azimuth in the row dtype -- for float32 rows the float32 value the reference computes (simulation.py:91-92), whose

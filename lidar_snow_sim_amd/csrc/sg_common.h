@@ -128,10 +128,11 @@ struct SgBeamArgs {
     const int32_t *chunk_blk;
     int32_t chunk;
     // Hand-over queue of the direct-mode pass: a beam that met flakes hands its range, azimuth and flake list to k_power,
-    // which builds the occlusion dict and everything after it.  Blocked SoA (groups of 64 slots, snowgpu_kernels.hip).
+    // which builds the occlusion dict and everything after it.  Blocked SoA of 32-bit words (groups of 64 slots): range, azimuth and
+    // one word per listed flake -- record index | limit-ray bits --, resolved by the reader (sg_queue.h).
     // A region's beams with ONE flake fill its slice from the front, the others from the back (waves of uniform loop
     // length in k_power); qn[region] = front count | back count << 32, bumped once per wave.
-    double *dq;
+    uint32_t *dq;
     int32_t *dq_g;               // per slot: sorted position of the beam
     uint16_t *dq_sc;             // per slot: flakes in the list | channel << 8
     unsigned long long *qn;      // per region

@@ -130,7 +130,7 @@ struct __attribute__((visibility("default"))) snowgpu_ctx {
     DevBuf<int64_t> seg_start;
     DevBuf<uint32_t> rec, rec_q;      // result records: one per sorted position / per queue slot
     DevBuf<uint8_t> rng;              // range of every simulated beam, per sorted position, in the row dtype
-    DevBuf<double> dq;                // dict queue of the first pass (SoA planes)
+    DevBuf<uint32_t> dq;              // dict queue of the first pass (blocked SoA of 32-bit words: sg_queue.h)
     DevBuf<int32_t> dq_g;
     DevBuf<uint16_t> dq_sc;
     DevBuf<unsigned long long> qn;    // per region: front | back << 32

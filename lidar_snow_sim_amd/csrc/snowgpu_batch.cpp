@@ -2,6 +2,7 @@
 // which order, and the scratch it needs.  Every order and every stream choice below is a measurement; the comments say which.
 #include "sg_host.h"
 #include "sg_launch.h"      // sg_tiles
+#include "sg_queue.h"       // the dict queue's layout
 
 static int sync_tables(snowgpu_ctx *ctx)
 {
@@ -293,11 +294,12 @@ int run_batch(snowgpu_ctx *ctx, BatchDev &b)
     // Regions of the first pass = slices of its dict queue: the segments, or plain chunks of 8 blocks in linear order.
     a.q_chunk = (int32_t)q_chunk;
     {
-        const size_t planes = 3 * (size_t)tiers[0] + 2;        // range, azimuth, three values per flake
-        if (n * planes * sizeof(double) > ((size_t)64 << 30))
+        // 32-bit words per slot: range, azimuth (in the row dtype), one word per flake (sg_queue.h)
+        const size_t slot_words = (size_t)sg_dq_slot_words(tiers[0], sg_dq_hdr(b.dtype == 0 ? 4 : 8));
+        if (n * slot_words * sizeof(uint32_t) > ((size_t)64 << 30))
             return fail(ctx, SNOWGPU_E_INVALID, "batch too large for the dict queue of this table density: split it");
         if (b.n_frames >= (1 << 22)) return fail(ctx, SNOWGPU_E_INVALID, "too many frames in one batch");
-        ENSURE(ctx, ctx->dq, (n + 64) * planes);          // blocked SoA: groups of 64 slots
+        ENSURE(ctx, ctx->dq, (n + 64) * slot_words);      // blocked SoA: groups of 64 slots
         ENSURE(ctx, ctx->dq_g, n);
         ENSURE(ctx, ctx->dq_sc, n);
         if (!seg_small) HIPCHK(ctx, hipMemsetAsync(ctx->qn.p, 0, sizeof(unsigned long long) * zero_words, st));     // (else k_seg_small cleared it)

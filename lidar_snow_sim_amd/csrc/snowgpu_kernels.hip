@@ -15,6 +15,7 @@
 #include <algorithm>
 #include "sg_beam.h"
 #include "sg_few.h"
+#include "sg_queue.h"
 #include "sg_kutil.h"
 #include "sg_launch.h"
 
@@ -92,10 +93,13 @@ static inline int sg_by_dtype_tier(int dtype, int lmax, F &&f)
 }
 
 // ------------------------------------------------------------------------------------------------
-// Hand-over queues (scan -> k_power) are "blocked SoA": 64 consecutive slots form a group, a group holds its P planes back to
-// back.  A beam hands over what phase 2 needs: plane 0 = its range, plane 1 = its azimuth, planes 2 + 3 j .. 4 + 3 j = the
-// interval angles and the range of its j-th intersecting flake (near -> far); P = 3 capacity + 2.  A wave reads / writes 512
-// contiguous bytes per plane (coalesced like plain SoA), and everything one beam needs sits within P x 512 bytes.
+// Hand-over queues (scan -> k_power) are "blocked SoA": 64 consecutive slots form a group, a group holds its planes back to back, so
+// a wave reads / writes a contiguous run per plane (coalesced like plain SoA) and everything one beam needs sits within one group.
+//   The dict queue of the pass over all rows (dq): range, azimuth and ONE 32-bit word per listed flake -- the record's index and two
+//   limit-ray bits, as the scan's LDS list holds it; the readers (k_power_few, k_power) resolve the words against the table's records.
+//   The layout, its store and its load / resolution are sg_queue.h.
+//   The hand-over buffer of a later tier's scan (tq), float64 planes: plane 0 = the beam's range, plane 1 = its azimuth, planes
+//   2 + 3 j .. 4 + 3 j = the interval angles and the range of its j-th intersecting flake; P = 3 capacity + 2 planes of 512 bytes per group.
 #define SG_QPLANES(LMAX) (3 * (LMAX) + 2)
 template <int P>
 __device__ __forceinline__ int64_t sg_qaddr(int64_t slot, int plane)
@@ -334,35 +338,17 @@ __global__ __launch_bounds__(BLOCK < 64 ? 64 : BLOCK, (!LIST && DICT == 1 && BLO
         // ---- hand the beams that met a flake, with their flake lists, to k_power ------------------------------------
         // Only a fraction of the beams gets here; walking phases 2-3 in place would keep most lanes of every wave idle
         // (measured: phase 2 alone was 30 % of this pass at 28 % of the lanes).
-        constexpr int P = SG_QPLANES(LMAX);
-        auto hand_over = [&](double *q, int64_t slot) {
-            q[sg_qaddr<P>(slot, 0)] = (double)d_t;
-            q[sg_qaddr<P>(slot, 1)] = (double)theta_t;
-            // the interval angles from the words: the beam's limits, or the records' tangent angles (read here, by the few beams that
-            // listed a flake -- the records' lines are what the scan just read)
-            double th_r, th_l;
-            sg_beam_limits((double)theta_t, a.beam_div_deg, th_r, th_l);
+        // The slot holds what the LDS list holds: range, azimuth, one word per flake (sg_queue.h).  The words' resolution -- the beam's limits, the
+        // records' tangent angles and ranges -- is the readers' work: this kernel is bound by its vector-memory path, they are not.
+        auto hand_over = [&](uint32_t *q, int64_t slot) {
+            sg_dq_store_header<T>(q, slot, LMAX, d_t, theta_t);
+            const uint32_t *s_w = reinterpret_cast<const uint32_t *>(s_a1);
             if constexpr (LMAX <= 4) {
-                double x1[LMAX], x2[LMAX];
-                uint32_t hw[LMAX];
-#pragma unroll
-                for (int j = 0; j < LMAX; ++j) hw[j] = reinterpret_cast<const uint32_t *>(s_a1)[j * BLOCK + tid];
-                sg_hit_angles_all<LMAX>(hw, L, tab.entries, th_r, th_l, x1, x2);
 #pragma unroll
                 for (int j = 0; j < LMAX; ++j)
-                    if (j < L) {
-                        q[sg_qaddr<P>(slot, 2 + 3 * j)] = x1[j];
-                        q[sg_qaddr<P>(slot, 3 + 3 * j)] = x2[j];
-                        q[sg_qaddr<P>(slot, 4 + 3 * j)] = s_rho[j * BLOCK + tid];
-                    }
+                    if (j < L) sg_dq_store_word<T>(q, slot, LMAX, j, s_w[j * BLOCK + tid]);
             } else {
-                for (int j = 0; j < L; ++j) {
-                    double x1, x2;
-                    sg_hit_angles(reinterpret_cast<const uint32_t *>(s_a1)[j * BLOCK + tid], tab.entries, th_r, th_l, x1, x2);
-                    q[sg_qaddr<P>(slot, 2 + 3 * j)] = x1;
-                    q[sg_qaddr<P>(slot, 3 + 3 * j)] = x2;
-                    q[sg_qaddr<P>(slot, 4 + 3 * j)] = s_rho[j * BLOCK + tid];
-                }
+                for (int j = 0; j < L; ++j) sg_dq_store_word<T>(q, slot, LMAX, j, s_w[j * BLOCK + tid]);
             }
         };
         // The region's slice of the queue: beams with one flake from the front, the others from the back -- one
@@ -570,6 +556,14 @@ __global__ __launch_bounds__(256) void k_tier_gather(SgBeamArgs a, int n_regions
     }
 }
 
+// The records that the words of a dict-queue slot name (sg_queue.h): the table of the beam's (frame, channel), one pointer of its descriptor.
+// (The items of a segment region share frame and channel, and the pointer can then be a scalar load through the first lane's channel:
+// measured, no difference -- profiles/r10_queue_words_ab.txt, variant s.)
+__device__ __forceinline__ const SgEntry *sg_dq_entries(const SgBeamArgs &a, int f, int ch)
+{
+    return a.frame_tables[(int64_t)f * a.las->n + ch].entries;
+}
+
 // ------------------------------------------------------------------------------------------------
 // Everything after the scan for the beams a hand-over pass queued: one lane per queue slot, every lane busy.
 // Phase 2 (occlusion dict), 3a (amplitudes, windows), 3b (pruned power profile and its first maximum), 3c (decision),
@@ -600,7 +594,7 @@ __device__ __forceinline__ void sg_kp_item(const SgBeamArgs &a, char *smem, cons
     double *s_work = THREE ? s_a2 : s_ratio;                              // stage-A work list: low words of the window column / own column
     const int tid = threadIdx.x, lane = tid & 63;
     const int ltid = BLOCK < 64 ? lane : tid;          // column of the LDS lists
-    const double *planes = LISTQ ? a.tq : a.dq;
+    const double *planes = a.tq;                       // (LISTQ; the dict queue of the pass over all rows holds words: sg_queue.h)
     const uint16_t *scs = LISTQ ? a.tq_sc : a.dq_sc;
     static_assert(WIN <= 4, "the window's permutation passes through one 64-double row segment of the wave");
     uint16_t *s_perm = (uint16_t *)(s_ratio + (BLOCK < 64 ? 0 : (tid & ~63)));   // dead between two beams: this wave's columns of row 0
@@ -667,18 +661,32 @@ __device__ __forceinline__ void sg_kp_item(const SgBeamArgs &a, char *smem, cons
         const int64_t slot = (int64_t)start + pos;
         unsigned sc = 0xffffu;
         int32_t g = 0;
-        double d = 0.0, tc = 0.0, f_a1 = 0.0, f_a2 = 0.0, f_rho = 0.0;
+        double d = 0.0, tc = 0.0, f_rho = 0.0;
+        [[maybe_unused]] double f_a1 = 0.0, f_a2 = 0.0;
         // where the beam's hand-over data lies: plane p at qb[p * qs] -- a slot of a blocked-SoA queue (stride 64), or the
         // overflow slot of its sorted position (stride 1)
-        const double *qb = planes;
-        int qs = 64;
+        [[maybe_unused]] const double *qb = planes;
+        [[maybe_unused]] int qs = 64;
+        // the dict queue: the slot's words -- a short list whole (every cell of a slot exists, filled or not), of a longer one the first
+        constexpr int NW = LMAX <= 4 ? LMAX : 1;
+        [[maybe_unused]] uint32_t hw[NW];
+#pragma unroll
+        for (int j = 0; j < NW; ++j) hw[j] = 0u;
         if (in) {                                         // everything a beam surely has, in one round of loads
-            g = LISTQ ? a.tier_list[work_off + slot] : a.dq_g[slot];
-            if (LISTQ && ov_list) { qb = a.ov + (size_t)g * SG_OV_STRIDE; qs = 1; sc = a.ov_sc[g]; }
-            else { qb = planes + sg_qaddr<P>(slot, 0); sc = scs[slot]; }
-            d = qb[0];                                    // the beam's range (simulation.py:89), widened from the row dtype
-            tc = qb[qs];
-            f_a1 = qb[2 * qs]; f_a2 = qb[3 * qs]; f_rho = qb[4 * qs];
+            if constexpr (LISTQ) {
+                g = a.tier_list[work_off + slot];
+                if (ov_list) { qb = a.ov + (size_t)g * SG_OV_STRIDE; qs = 1; sc = a.ov_sc[g]; }
+                else { qb = planes + sg_qaddr<P>(slot, 0); sc = scs[slot]; }
+                d = qb[0];                                // the beam's range (simulation.py:89), widened from the row dtype
+                tc = qb[qs];
+                f_a1 = qb[2 * qs]; f_a2 = qb[3 * qs]; f_rho = qb[4 * qs];
+            } else {
+                g = a.dq_g[slot];
+                sc = scs[slot];
+                sg_dq_load_header<T>(a.dq, slot, LMAX, d, tc);
+#pragma unroll
+                for (int j = 0; j < NW; ++j) hw[j] = sg_dq_load_word<T>(a.dq, slot, LMAX, j);
+            }
         }
         const bool live = in && sc != 0xffffu;            // 0xffff: a listed beam without a flake (its record is final)
         const int L = (int)(sc & 255u), ch = (int)(sc >> 8);
@@ -692,7 +700,8 @@ __device__ __forceinline__ void sg_kp_item(const SgBeamArgs &a, char *smem, cons
             f = item_f >= 0 ? item_f : sg_frame_of(a, g);
             // ord: 4 bits per list entry -- the hit (scan order) it came from; identity unless the scan left the flakes unsorted
             unsigned long long ord = 0xfedcba9876543210ull;
-            if (LISTQ) {
+            [[maybe_unused]] const SgEntry *ent = nullptr;   // the dict queue: the records its words name
+            if constexpr (LISTQ) {
                 // the flakes as the scan met them: insertion by range, scan order on equal ranges (simulation.py:413-417).  The
                 // ranges pass through the ratio / range column (free until the dict); THREE: they go back to being fetched from
                 // the queue afterwards, through `ord`.
@@ -732,27 +741,43 @@ __device__ __forceinline__ void sg_kp_item(const SgBeamArgs &a, char *smem, cons
                     }
                 }
             } else {
-                s_a1[ltid] = f_a1; s_a2[ltid] = f_a2;
-                if constexpr (!THREE) s_rho[ltid] = f_rho;
-                if constexpr (LMAX <= 4 && !THREE) {
-                    // every plane of a slot exists, filled or not: the whole list in ONE round of loads (a loop of L - 1 trips waited for each trip's three)
-                    double xa[LMAX - 1], xb[LMAX - 1], xr[LMAX - 1];
+                // the words resolved: the table's records (their tails: tangent angles, range) through the descriptor of the beam's (frame,
+                // channel), the beam's limits where a bit says so -- all records of a round in one flight
+                ent = sg_dq_entries(a, f, ch);
+                double th_r, th_l;
+                sg_beam_limits(tc, a.beam_div_deg, th_r, th_l);
+                if constexpr (LMAX <= 4) {
+                    double xa[LMAX], xb[LMAX], xr[LMAX];
+                    sg_dq_resolve_all<LMAX>(hw, L, ent, th_r, th_l, xa, xb, xr);
+                    f_rho = xr[0];
 #pragma unroll
-                    for (int j = 1; j < LMAX; ++j) { xa[j - 1] = qb[(2 + 3 * j) * qs]; xb[j - 1] = qb[(3 + 3 * j) * qs]; xr[j - 1] = qb[(4 + 3 * j) * qs]; }
-#pragma unroll
-                    for (int j = 1; j < LMAX; ++j)
-                        if (j < L) { s_a1[j * BLOCK + ltid] = xa[j - 1]; s_a2[j * BLOCK + ltid] = xb[j - 1]; s_rho[j * BLOCK + ltid] = xr[j - 1]; }
+                    for (int j = 0; j < LMAX; ++j)
+                        if (j < L) {
+                            s_a1[j * BLOCK + ltid] = xa[j]; s_a2[j * BLOCK + ltid] = xb[j];
+                            if constexpr (!THREE) s_rho[j * BLOCK + ltid] = xr[j];
+                        }
                 } else {
-                    for (int j = 1; j < L; ++j) {
-                        s_a1[j * BLOCK + ltid] = qb[(2 + 3 * j) * qs];
-                        s_a2[j * BLOCK + ltid] = qb[(3 + 3 * j) * qs];
-                        if constexpr (!THREE) s_rho[j * BLOCK + ltid] = qb[(4 + 3 * j) * qs];
+                    for (int j0 = 0; j0 < L; j0 += 8) {
+                        uint32_t w8[8];
+                        double xa[8], xb[8], xr[8];
+                        w8[0] = j0 == 0 ? hw[0] : sg_dq_load_word<T>(a.dq, slot, LMAX, j0);
+#pragma unroll
+                        for (int c = 1; c < 8; ++c) w8[c] = sg_dq_load_word<T>(a.dq, slot, LMAX, j0 + c < L ? j0 + c : 0);   // (past the list: word 0 again, not stored)
+                        sg_dq_resolve_all<8>(w8, L - j0, ent, th_r, th_l, xa, xb, xr);
+                        if (j0 == 0) f_rho = xr[0];
+#pragma unroll
+                        for (int c = 0; c < 8; ++c)
+                            if (j0 + c < L) {
+                                s_a1[(j0 + c) * BLOCK + ltid] = xa[c]; s_a2[(j0 + c) * BLOCK + ltid] = xb[c];
+                                if constexpr (!THREE) s_rho[(j0 + c) * BLOCK + ltid] = xr[c];
+                            }
                     }
                 }
             }
-            auto queue_rho = [&](int j) -> double {       // range of list entry j (THREE: from the queue)
+            auto queue_rho = [&](int j) -> double {       // range of list entry j (THREE: from the queue -- the dict queue: from the record its word names)
                 const int h = (int)((ord >> (4 * j)) & 15ull);
-                return h == 0 ? f_rho : qb[(4 + 3 * h) * qs];
+                if constexpr (LISTQ) return h == 0 ? f_rho : qb[(4 + 3 * h) * qs];
+                else return h == 0 ? f_rho : sg_dq_rho(sg_dq_load_word<T>(a.dq, slot, LMAX, h), ent);
             };
             int32_t *dc = a.dbg_count ? a.dbg_count + g : nullptr;
             double *drj = a.dbg_count ? a.dbg_rj + (int64_t)g * a.dbg_cap : nullptr;
@@ -861,7 +886,7 @@ __global__ __launch_bounds__(BLOCK < 64 ? 64 : BLOCK, LMAX <= 4 ? SG_KP_WAVES : 
 // Tried and dropped: the kernel beside k_power on another stream, two or three blocks per CU instead of four (all 1 - 10 % slower:
 // the persistent kernels of this phase do best when each has the chip to itself for its turn).
 template <typename T, int N>
-__global__ __launch_bounds__(256, 4) void k_power_few(SgBeamArgs a, int qplanes)   // (N = 3: 127 registers and eight spilled; at three waves per SIMD, 143 registers, it was slower on every workload)
+__global__ __launch_bounds__(256, 4) void k_power_few(SgBeamArgs a, int lmax)   // (N = 3: 127 registers and eight spilled; at three waves per SIMD, 143 registers, it was slower on every workload)
 {
     __shared__ double s_amp[N + 1][256], s_rho[N + 1][256], s_best[256];      // scatterer N: the hard target
     __shared__ int s_win[N + 1][256], s_zone[N + 1][256], s_k[256];           // k0 | k1 << 16;  first bin | bins << 16
@@ -883,17 +908,20 @@ __global__ __launch_bounds__(256, 4) void k_power_few(SgBeamArgs a, int qplanes)
 #pragma unroll
         for (int z = 0; z <= N; ++z) zone[z] = 0;
         if (live) {
-            const double *q = a.dq + (slot >> 6) * (int64_t)(qplanes * 64) + (slot & 63);
             const unsigned sc = a.dq_sc[slot];
-            const double d = q[0], tc = q[64];
-            double a1[N], a2[N], rho[N];
+            double d, tc;
+            sg_dq_load_header<T>(a.dq, slot, lmax, d, tc);
+            uint32_t w[N];
 #pragma unroll
-            for (int j = 0; j < N; ++j) {             // every plane of the slot exists, filled or not: all loads in one flight
-                a1[j] = q[(2 + 3 * j) * 64]; a2[j] = q[(3 + 3 * j) * 64]; rho[j] = q[(4 + 3 * j) * 64];
-            }
+            for (int j = 0; j < N; ++j) w[j] = sg_dq_load_word<T>(a.dq, slot, lmax, j);   // every cell of the slot exists, filled or not: all loads in one flight
             ch = (int)(sc >> 8);
             g = a.dq_g[slot];
             f = item_f >= 0 ? item_f : sg_frame_of(a, g);
+            // the words resolved (sg_queue.h): the records of the beam's table, their tails in one flight, and the beam's limits
+            const SgEntry *ent = sg_dq_entries(a, f, ch);
+            double th_r, th_l, a1[N], a2[N], rho[N];
+            sg_beam_limits(tc, a.beam_div_deg, th_r, th_l);
+            sg_dq_resolve_all<N>(w, (int)(sc & 255u), ent, th_r, th_l, a1, a2, rho);
             S = sg_few_prep<T, N>(d, tc, (int)(sc & 255u), a1, a2, rho, ch, a.las, a.beam_div_deg, P, o);
             if (S) {                                  // stage A: the bins of every scatterer's window that can hold the maximum
                 int ka, kb;
@@ -1112,9 +1140,9 @@ static int launch_power_t(const SgBeamArgs *a, hipStream_t st, bool plan_only = 
             hipStream_t s1 = st;                      // tiers' stream, was measured: 4.67 instead of 4.59 ms)
             const unsigned g1 = (unsigned)std::min<int64_t>((int64_t)cus * 4, (a->n_total / LANES + a->n_regions_ub + 3) / 4);
             if (g1 > 0) {
-                if (a->front_max == 1) hipLaunchKernelGGL((k_power_few<T, 1>), dim3(g1), dim3(256), 0, s1, *a, SG_QPLANES(LMAX));
-                else if (a->front_max == 2) hipLaunchKernelGGL((k_power_few<T, 2>), dim3(g1), dim3(256), 0, s1, *a, SG_QPLANES(LMAX));
-                else hipLaunchKernelGGL((k_power_few<T, 3>), dim3(g1), dim3(256), 0, s1, *a, SG_QPLANES(LMAX));
+                if (a->front_max == 1) hipLaunchKernelGGL((k_power_few<T, 1>), dim3(g1), dim3(256), 0, s1, *a, LMAX);
+                else if (a->front_max == 2) hipLaunchKernelGGL((k_power_few<T, 2>), dim3(g1), dim3(256), 0, s1, *a, LMAX);
+                else hipLaunchKernelGGL((k_power_few<T, 3>), dim3(g1), dim3(256), 0, s1, *a, LMAX);
             }
             SG_CHECK_LAUNCH();
             if (ev_few && hipEventRecord(ev_few, st) != hipSuccess) return (int)hipGetLastError();
