@@ -994,6 +994,60 @@ int snowgpu_roi_point_pool_device(snowgpu_ctx *ctx, int n_frames, int64_t n_tota
                                   double *d_out_pose /* or NULL */, void *stream);
 
 /*
+ * RoI-AWARE VOXEL POOLING of an aligned batch: every roi of a frame is cut into Gx Gy Gz sub-voxels along its own axes, and the features of
+ * the rows inside each sub-voxel are max- and average-pooled -- pcdet's roiaware_pool3d (RoIAwarePool3d), the input of a Part-A2-style second
+ * stage, with static shapes and nothing read on the host.  snowgpu_roi_point_pool_device cannot stand in for it: it keeps a roi's first S
+ * rows as one list, and this op needs the members of every sub-voxel.  F = n_frames, M = n_rois per frame, G = Gx Gy Gz, T = max_points,
+ * P = roi_capacity, Cf = feature_channels.  The definition is restated as brute-force NumPy by tests/roiaware_reference.py.
+ *   SHARED RULES: frames, rows, frame offsets, the keep mask, USABLE rows, ROIS (1 <= M <= 512, Cb in 7 .. 10), the ENLARGED BOX
+ *   (extra_width3 NULL: zeros -- Part-A2 passes none), PRESENCE, POSE and MEMBERSHIP are, word for word, those of
+ *   snowgpu_roi_point_pool_device above (sg_roi_make, sg_box_inside).
+ *   SUB-VOXEL OF A MEMBER: out_size3 = (Gx, Gy, Gz), each in 1 .. 16.  With lx, ly, sz the values the membership test saw and dx', dy', dz'
+ *   the enlarged sizes THEMSELVES (not the test's half extents, whose x and y carry the 1e-5 margin), in float64, every operation rounded
+ *   on its own, no fused multiply-add:
+ *     ux = (lx + dx' / 2) / (dx' / Gx),  ix = min(max((int)floor(ux), 0), Gx - 1);   uy, iy likewise;   uz = (sz + dz' / 2) / (dz' / Gz), iz.
+ *   The clamp is pcdet's: a member inside the 1e-5 margin beyond an x / y face lands in the edge voxel, a member on the closed upper z face
+ *   in Gz - 1.  (The clamp is made on the floor before the conversion; a NaN quotient, which takes a dx' / Gx that underflows to 0, gives 0.)
+ *   Flat voxel g = (ix Gy + iy) Gz + iz: pcdet's (out_x, out_y, out_z) layout.
+ *   ORDER AND CAPS: the members of roi (f, m) are the usable rows of frame f inside it in ASCENDING ROW INDEX.  Only the FIRST P of them are
+ *   distributed to voxels, 64 <= P <= 65536; within a voxel they stay in row order, and the first T of those are pooled, 1 <= T <= 128
+ *   (pcdet's max_pts_each_voxel = 128 stores 127 rows beside their count: its default is T = 127).
+ *   FEATURES: d_features is (N_total, Cf) float32, contiguous, one row per row of the batch, 1 <= Cf <= 256; or NULL -- then d_out_max,
+ *   d_out_argmax and d_out_avg must be NULL too (but for a batch without a row, which has no feature to point to and writes them by Cf).
+ * Outputs, every shape static, every element written by every call, nothing needs clearing:
+ *   d_out_roi_count (F, M) int32: all members of the roi, clipped by neither cap; 0 for an absent roi
+ *   d_out_count     (F, M, G) int32: the voxel's members among the roi's first P, NOT clipped at T
+ *   d_out_index     (F, M, G, T) int32, or NULL: the global row numbers of the voxel's first T members, -1 behind them (no wrap-around)
+ *   d_out_max       (F, M, G, Cf) float32, or NULL, and d_out_argmax (F, M, G, Cf) int32, or NULL: pcdet's loop per channel -- no winner at
+ *                   the start; the pooled members are walked in order; a value wins when there is no winner and it is not NaN, or when it
+ *                   is > the current maximum.  So the first of equal maxima wins, NaN never wins, -inf can win.  argmax is the winner's
+ *                   global row, -1 without one; max is 0 where argmax is -1.
+ *   d_out_avg       (F, M, G, Cf) float32, or NULL: the float32 sum of the pooled members' values, added one by one in row order starting
+ *                   from +0, divided by (float)min(count, T), the division correctly rounded; 0 for an empty voxel.  NaN and inf propagate
+ *                   as IEEE gives them.
+ *   d_out_pose      (F, M, 2) float64, or NULL: as for snowgpu_roi_point_pool_device
+ *   Sizes: at F = 16, M = 128, G = 12^3, Cf = 128 max, argmax and avg are 1.8 GB each; at T = 127 the index is 1.8 GB.
+ * Domain: the ranges above; Cb in 7 .. 10; every component of ew finite and in 0 .. 100; F M G max(T, Cf) <= 2^31 - 1; F M P <= 2^31 - 1;
+ * n_total < 2^31; no frame above 2^30 rows; F M (the 512-row runs of the longest frame) <= 2^31 - 1; dtype 0 or 1; every output apart from
+ * the rows, the keep mask, the rois, the given pose, the features and every other output.  Anything else is SNOWGPU_E_INVALID with a message.
+ * A batch without a row writes zeros, -1 and the pose and launches nothing over rows (d_rows may be NULL).  Nothing depends on the arrival
+ * of an atomic: two calls give identical bytes.
+ * The rois are filed, counted and ranked by the kernels of snowgpu_roi_point_pool_device, which leave every roi's first P members in row
+ * order in scratch; one wave per roi then groups that list by voxel -- counts in LDS, a scan, and a second pass that places 64 members at
+ * a time behind per-voxel cursors by ballots, lane order being row order --; one lane per (voxel, channel) pools (csrc/sg_roiaware.h,
+ * csrc/snowgpu_roiaware.hip).  Scratch in the context, grown on first use: that of the pooling stage, twice F M P int32 (at F = 16, M = 128,
+ * P = 8192: 67 MB each) and F M G int32.  Up to seven kernels on `stream`, no memset; nothing is read on the host, nothing allocated after
+ * the first call of a size: capturable as a linear graph.
+ */
+int snowgpu_roi_voxel_pool_device(snowgpu_ctx *ctx, int n_frames, int64_t n_total, int64_t max_frame_rows, const int64_t *d_frame_offsets,
+                                  const void *d_rows, int dtype, int n_rois, const void *d_rois, int roi_features,
+                                  const double *extra_width3 /* host, 3 doubles, or NULL = zeros */, const int32_t *out_size3 /* host, 3 ints */,
+                                  int max_points, int roi_capacity, const float *d_features /* or NULL */, int feature_channels,
+                                  const double *d_pose_in /* or NULL */, const uint8_t *d_keep_in /* or NULL: all present */,
+                                  int32_t *d_out_roi_count, int32_t *d_out_count, int32_t *d_out_index /* or NULL */, float *d_out_max /* or NULL */,
+                                  int32_t *d_out_argmax /* or NULL */, float *d_out_avg /* or NULL */, double *d_out_pose /* or NULL */, void *stream);
+
+/*
  * ROTATED BOX IoU AND NMS: pcdet's iou3d_nms family -- boxes_iou_bev, boxes_iou3d_gpu, nms_gpu -- with static shapes, nothing read on the
  * host.  snowgpu_boxes_iou_device gives the overlap of every box of one set with every box of another (the target layer's rois against
  * gt_boxes) and, without materialising the matrix, the best partner of every box; snowgpu_nms_device gives the keep list of scored

@@ -32,7 +32,7 @@ EXPORTS = [
     "snowgpu_augment_weather_batch_device_aligned", "snowgpu_draw_weather_device", "snowgpu_dror_mask_device",
     "snowgpu_voxelize_device", "snowgpu_fps_device", "snowgpu_ball_query_device", "snowgpu_range_image_device",
     "snowgpu_nearest_centres_device", "snowgpu_points_in_boxes_device", "snowgpu_boxes_iou_device", "snowgpu_nms_device", "snowgpu_fps_sectors_device",
-    "snowgpu_roi_point_pool_device",
+    "snowgpu_roi_point_pool_device", "snowgpu_roi_voxel_pool_device",
 ]
 
 WET_ESTIMATION = {"linear": 0, "poly": 1}
@@ -168,6 +168,9 @@ def lib():
             L.snowgpu_roi_point_pool_device.restype = ctypes.c_int
             L.snowgpu_roi_point_pool_device.argtypes = [vp, ctypes.c_int, i64, i64, vp, vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, vp, ctypes.c_int,
                                                         ctypes.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
+            L.snowgpu_roi_voxel_pool_device.restype = ctypes.c_int
+            L.snowgpu_roi_voxel_pool_device.argtypes = [vp, ctypes.c_int, i64, i64, vp, vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, vp, vp, ctypes.c_int,
+                                                        ctypes.c_int, vp, ctypes.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
             L.snowgpu_boxes_iou_device.restype = ctypes.c_int
             L.snowgpu_boxes_iou_device.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                    vp, vp, vp, vp, vp, vp]
@@ -685,6 +688,24 @@ class Context:
                                                    int(dtype_code), _i32(n_rois), vp(d_rois or None), _i32(roi_features), None if ew is None else _p(ew),
                                                    _i32(n_samples), _i32(num_features), vp(d_pose_in or None), vp(d_keep_in or None),
                                                    vp(d_out_index or None), vp(d_out_count or None), vp(d_out_points or None), vp(d_out_local or None),
+                                                   vp(d_out_pose or None), vp(stream or None))
+        self._check_args(rc)
+
+    def roi_voxel_pool_device(self, n_frames, n_total, max_frame_rows, d_frame_off, d_rows, dtype_code, n_rois, d_rois, roi_features, extra_width,
+                              out_size, max_points, roi_capacity, d_features, feature_channels, d_pose_in, d_keep_in, d_out_roi_count, d_out_count,
+                              d_out_index, d_out_max, d_out_argmax, d_out_avg, d_out_pose, stream=0):
+        """The members of every sub-voxel of every enlarged roi and their pooled features (include/snowgpu.h: snowgpu_roi_voxel_pool_device);
+        asynchronous on `stream`.  extra_width: None or three numbers (host); out_size: three whole numbers (host).  d_features, d_pose_in,
+        d_keep_in, d_out_index, d_out_max, d_out_argmax, d_out_avg and d_out_pose may be 0.  An argument outside the domain, or an output
+        overlapping the mask, the rows, the rois, the given pose, the features or another output, raises ValueError with the entry's words."""
+        vp = ctypes.c_void_p
+        ew = None if extra_width is None else np.ascontiguousarray(extra_width, np.float64).reshape(3)
+        grid = np.ascontiguousarray(out_size, np.int32).reshape(3)
+        rc = self._L.snowgpu_roi_voxel_pool_device(self._h, int(n_frames), int(n_total), int(max_frame_rows), vp(d_frame_off or None), vp(d_rows or None),
+                                                   int(dtype_code), _i32(n_rois), vp(d_rois or None), _i32(roi_features), None if ew is None else _p(ew),
+                                                   _p(grid), _i32(max_points), _i32(roi_capacity), vp(d_features or None), _i32(feature_channels),
+                                                   vp(d_pose_in or None), vp(d_keep_in or None), vp(d_out_roi_count or None), vp(d_out_count or None),
+                                                   vp(d_out_index or None), vp(d_out_max or None), vp(d_out_argmax or None), vp(d_out_avg or None),
                                                    vp(d_out_pose or None), vp(stream or None))
         self._check_args(rc)
 

@@ -331,6 +331,22 @@ int sg_launch_roipool(const void *rows, int dtype, int64_t n, int64_t max_frame,
                       int32_t n_rois, const void *rois, int32_t roi_features, const double *ew, int32_t n_samples, int32_t num_features,
                       const double *pose_in, struct SgBoxRec *rec, unsigned long long *table, int32_t *run_cnt, int32_t *out_index, int32_t *out_count,
                       void *out_points, void *out_local, double *out_pose, void *stream);
+// Its first four kernels alone: count (n_frames, n_rois) and the first n_slots members of every roi in row order in index (n_frames, n_rois,
+// n_slots), the slots behind the count left as they were; for a batch without a row the first kernel alone, count not written.
+int sg_launch_roi_members(const void *rows, int dtype, int64_t n, int64_t max_frame, const int64_t *frame_off, int n_frames, const uint8_t *keep_in,
+                          int32_t n_rois, const void *rois, int32_t roi_features, const double *ew, int32_t n_slots, const double *pose_in,
+                          struct SgBoxRec *rec, unsigned long long *table, int32_t *run_cnt, int32_t *out_index, int32_t *out_count, double *out_pose,
+                          void *stream);
+// RoI-aware voxel pooling (sg_roiaware.h; the definition: include/snowgpu.h): sg_launch_roi_members into `list` with n_slots = cap, then
+// k_roiaware_bucket and, for what was asked, k_roiaware_pool and k_roiaware_index.  Scratch of its own: rec, table and run_cnt as above;
+// list and sorted, sg_roiaware_list(n_frames, n_rois, cap) int32 each (at F = 16, M = 128, P = 8192: 67 MB each); offset,
+// sg_roiaware_offsets(n_frames, n_rois, G) int32.  grid: 3 host ints.  features, pose_in and every output but roi_count and count may be
+// null.  A batch without a row runs the first kernel, one that writes the zero counts, and the last two.
+int sg_launch_roiaware(const void *rows, int dtype, int64_t n, int64_t max_frame, const int64_t *frame_off, int n_frames, const uint8_t *keep_in,
+                       int32_t n_rois, const void *rois, int32_t roi_features, const double *ew, const int32_t *grid, int32_t max_points, int32_t cap,
+                       const float *features, int32_t channels, const double *pose_in, struct SgBoxRec *rec, unsigned long long *table, int32_t *run_cnt,
+                       int32_t *list, int32_t *sorted, int32_t *offset, int32_t *out_roi_count, int32_t *out_count, int32_t *out_index, float *out_max,
+                       int32_t *out_argmax, float *out_avg, double *out_pose, void *stream);
 // Rotated box IoU and NMS (sg_iou.h; the definition: include/snowgpu.h): three kernels each.  Scratch: rec, sg_iou_records() doubles for
 // n_frames (M + B) boxes (the IoU) or n_frames B (NMS); order, n_frames B; n_cand, n_frames.  The poses and every output but the NMS
 // index and count may be null (the IoU needs one output).

@@ -583,6 +583,82 @@ static inline int sg_check_roipool_args(const SgRoiPoolArgs &a, std::string *msg
     return 0;
 }
 
+// ---- snowgpu_roi_voxel_pool_device --------------------------------------------------------------------------------------------------------
+struct SgRoiAwareArgs {
+    int n_frames;
+    int64_t n_total, max_frame_rows;
+    int dtype;
+    const int64_t *frame_off;
+    const void *rows;
+    int n_rois;                       // M, per frame
+    const void *rois;
+    int roi_features;                 // Cb
+    const double *extra_width;        // host, 3 doubles, or NULL: zeros
+    const int32_t *out_size;          // host, 3 ints: Gx, Gy, Gz
+    int max_points;                   // T
+    int roi_capacity;                 // P
+    const float *features;            // (N_total, Cf) float32, or NULL: no pooled output
+    int feature_channels;             // Cf (not read without features)
+    const double *pose_in;            // or NULL: cos / sin of the heading on the device
+    const uint8_t *keep_in;
+    int32_t *out_roi_count;
+    int32_t *out_count;
+    int32_t *out_index;               // or NULL
+    float *out_max;                   // or NULL
+    int32_t *out_argmax;              // or NULL
+    float *out_avg;                   // or NULL
+    double *out_pose;                 // or NULL
+};
+
+// 0, or SG_ARGS_INVALID with *msg.  As above, the order is part of the ABI.
+static inline int sg_check_roiaware_args(const SgRoiAwareArgs &a, std::string *msg)
+{
+    static const char *who = "snowgpu_roi_voxel_pool_device";
+    if (a.n_frames <= 0 || a.n_total < 0 || !a.frame_off || !a.rois || !a.out_size || !a.out_roi_count || !a.out_count || (a.n_total > 0 && !a.rows) ||
+        (a.dtype != 0 && a.dtype != 1))
+        return sg_refuse(who, ": null pointer or bad dtype", msg);
+    if (a.n_total >= ((int64_t)1 << 31)) return sg_refuse("", "batch too large: split it below 2^31 rows", msg);
+    if (a.n_rois < 1 || a.n_rois > 512) return sg_refuse(who, ": n_rois must lie in 1 .. 512", msg);
+    if (a.roi_features < 7 || a.roi_features > 10) return sg_refuse(who, ": roi_features must lie in 7 .. 10: cx, cy, cz, dx, dy, dz, heading first", msg);
+    for (int j = 0; a.extra_width && j < 3; ++j)
+        if (!(a.extra_width[j] >= 0.0 && a.extra_width[j] <= 100.0))                         // (false for NaN)
+            return sg_refuse(who, ": every component of extra_width must be finite and lie in 0 .. 100", msg);
+    for (int j = 0; j < 3; ++j)
+        if (a.out_size[j] < 1 || a.out_size[j] > 16) return sg_refuse(who, ": every component of out_size must lie in 1 .. 16", msg);
+    if (a.max_points < 1 || a.max_points > 128) return sg_refuse(who, ": max_points must lie in 1 .. 128", msg);
+    if (a.roi_capacity < 64 || a.roi_capacity > 65536) return sg_refuse(who, ": roi_capacity must lie in 64 .. 65536", msg);
+    const bool pooled = a.out_max || a.out_argmax || a.out_avg;
+    if (pooled && !a.features && a.n_total > 0)                                              // (a batch without a row has no feature to point to)
+        return sg_refuse(who, ": d_out_max, d_out_argmax and d_out_avg need d_features; there is nothing to pool", msg);
+    if ((pooled || a.features) && (a.feature_channels < 1 || a.feature_channels > 256)) return sg_refuse(who, ": feature_channels must lie in 1 .. 256", msg);
+    const int64_t G = (int64_t)a.out_size[0] * a.out_size[1] * a.out_size[2], Cf = (pooled || a.features) ? a.feature_channels : 1;
+    if ((int64_t)a.n_frames * a.n_rois * G * (a.max_points > Cf ? (int64_t)a.max_points : Cf) > ((int64_t)1 << 31) - 1)       // (each factor is small: no overflow)
+        return sg_refuse(who, ": n_frames * n_rois * the voxels of a roi * max(max_points, feature_channels) exceeds 2^31 - 1; split the batch", msg);
+    if ((int64_t)a.n_frames * a.n_rois * a.roi_capacity > ((int64_t)1 << 31) - 1)
+        return sg_refuse(who, ": n_frames * n_rois * roi_capacity exceeds 2^31 - 1; split the batch or lower the capacity", msg);
+    const int64_t longest = sg_max_frame(a.max_frame_rows, a.n_total);
+    if (longest > ((int64_t)1 << 30)) return sg_refuse(who, ": a frame of more than 2^30 rows; split it", msg);
+    if ((int64_t)a.n_frames * a.n_rois * (longest / 512 + 1) > ((int64_t)1 << 31) - 1)    // (n_frames n_rois < 2^31 by the element check)
+        return sg_refuse(who, ": n_frames * n_rois * the 512-row runs of the longest frame exceeds 2^31 - 1; split the batch", msg);
+    const size_t esz = a.dtype == 0 ? 4 : 8, q = (size_t)a.n_frames * (size_t)a.n_rois, n = (size_t)a.n_total, v = q * (size_t)G, k = v * (size_t)Cf;
+    const struct { const void *p; size_t bytes; const char *name; } outs[7] = {
+        {a.out_roi_count, q * 4, "d_out_roi_count"}, {a.out_count, v * 4, "d_out_count"}, {a.out_index, v * (size_t)a.max_points * 4, "d_out_index"},
+        {a.out_max, k * 4, "d_out_max"}, {a.out_argmax, k * 4, "d_out_argmax"}, {a.out_avg, k * 4, "d_out_avg"}, {a.out_pose, q * 16, "d_out_pose"}};
+    const struct { const void *p; size_t bytes; const char *name; } ins[5] = {
+        {a.keep_in, n, "d_keep_in"}, {a.rows, n * 5 * esz, "d_rows"}, {a.rois, q * (size_t)a.roi_features * esz, "d_rois"}, {a.pose_in, q * 16, "d_pose_in"},
+        {a.features, n * (size_t)Cf * 4, "d_features"}};
+    for (int i = 0; i < 7; ++i) {
+        const auto &o = outs[i];
+        for (int j = 0; j < 5; ++j)
+            if (sg_ranges_meet(o.p, o.bytes, ins[j].p, ins[j].bytes))
+                return sg_refuse(who, (std::string(": ") + o.name + " overlaps " + ins[j].name + "; the mask, the rows, the rois, the pose and the features are read while the voxels are written: pass a buffer apart from them").c_str(), msg);
+        for (int j = 0; j < i; ++j)
+            if (sg_ranges_meet(o.p, o.bytes, outs[j].p, outs[j].bytes))
+                return sg_refuse(who, (std::string(": ") + o.name + " overlaps " + outs[j].name + "; every output needs memory of its own").c_str(), msg);
+    }
+    return 0;
+}
+
 // ---- snowgpu_boxes_iou_device -------------------------------------------------------------------------------------------------------------
 struct SgIouArgs {
     int n_frames;

@@ -118,6 +118,11 @@ struct __attribute__((visibility("default"))) snowgpu_ctx {
     DevBuf<double> roi_rec;
     DevBuf<unsigned long long> roi_table;
     DevBuf<int32_t> roi_runs;
+    // RoI-aware voxel pooling (snowgpu_roi_voxel_pool_device): the same three of its own, a roi's first roi_capacity members in row order
+    // and grouped by voxel (F M P int32 each: 67 MB each at F = 16, M = 128, P = 8192), and where every voxel's rows begin (F M G int32)
+    DevBuf<double> rv_rec;
+    DevBuf<unsigned long long> rv_table;
+    DevBuf<int32_t> rv_runs, rv_list, rv_sorted, rv_offset;
     // box IoU and NMS (snowgpu_boxes_iou_device, snowgpu_nms_device): one record of nine doubles per box; the ranking and its length
     DevBuf<double> iou_rec;
     DevBuf<int32_t> nms_order, nms_cand;

@@ -150,6 +150,7 @@ extern "C" void snowgpu_destroy(snowgpu_ctx *ctx)
     ctx->nn_entry.release(); ctx->nn_box.release(); ctx->nn_rec.release();
     ctx->box_rec.release(); ctx->box_table.release();
     ctx->roi_rec.release(); ctx->roi_table.release(); ctx->roi_runs.release();
+    ctx->rv_rec.release(); ctx->rv_table.release(); ctx->rv_runs.release(); ctx->rv_list.release(); ctx->rv_sorted.release(); ctx->rv_offset.release();
     ctx->iou_rec.release(); ctx->nms_order.release(); ctx->nms_cand.release();
     sg_prepass_release(&ctx->prepass);
     sg_plane_release(&ctx->plane_scr);

@@ -1,5 +1,5 @@
 // snowgpu_device.cpp -- the entries of the C ABI (include/snowgpu.h) that take DEVICE pointers and enqueue on the caller's stream: every
-// *_batch_device* entry, the plane estimate, the FOV mask, the outlier filter, the voxel stage, the keypoint stage and its sectorized form, the ball query, the range image, the nearest centres, the points in boxes, the RoI point pooling, the box IoU and NMS and the weather draw.  Each batch entry fills an SgDeviceArgs, has it checked
+// *_batch_device* entry, the plane estimate, the FOV mask, the outlier filter, the voxel stage, the keypoint stage and its sectorized form, the ball query, the range image, the nearest centres, the points in boxes, the RoI point pooling, the RoI-aware voxel pooling, the box IoU and NMS and the weather draw.  Each batch entry fills an SgDeviceArgs, has it checked
 // (sg_device_args.h: every refusal, in one order), sets the device and runs batch_from_args() and the stages it needs.  The launch
 // sequence of a batch is snowgpu_batch.cpp; no host copy, no synchronisation, no allocation after the first call of a given size.
 #include "sg_host.h"
@@ -13,6 +13,7 @@
 #include "sg_nn.h"          // the grid of the nearest-centres stage and the sizes of its scratch
 #include "sg_box.h"         // the record of a box and the sizes of the box stage's scratch
 #include "sg_roipool.h"     // the enlarged roi and the size of the pooling stage's run table
+#include "sg_roiaware.h"    // the limits of the RoI-aware voxel pooling and the sizes of its lists
 #include "sg_iou.h"         // the record of the IoU and NMS stages and the size of their scratch
 #include "sg_range.h"       // the geometry of the range image and the limits in the rows' dtype
 
@@ -646,6 +647,41 @@ extern "C" int snowgpu_roi_point_pool_device(snowgpu_ctx *ctx, int n_frames, int
                               d_pose_in, (SgBoxRec *)ctx->roi_rec.p, ctx->roi_table.p, ctx->roi_runs.p, d_out_index, d_out_count, d_out_points, d_out_local,
                               d_out_pose, stream ? (hipStream_t)stream : ctx->stream);
     if (e) return fail(ctx, SNOWGPU_E_HIP, std::string("roi point pool launch: ") + hipGetErrorString((hipError_t)e));
+    return SNOWGPU_OK;
+}
+
+// RoI-aware voxel pooling (snowgpu_roiaware.hip; the sub-voxel of a member and the scratch: sg_roiaware.h).  See include/snowgpu.h.
+extern "C" int snowgpu_roi_voxel_pool_device(snowgpu_ctx *ctx, int n_frames, int64_t n_total, int64_t max_frame_rows, const int64_t *d_frame_offsets,
+                                             const void *d_rows, int dtype, int n_rois, const void *d_rois, int roi_features, const double *extra_width3,
+                                             const int32_t *out_size3, int max_points, int roi_capacity, const float *d_features, int feature_channels,
+                                             const double *d_pose_in, const uint8_t *d_keep_in, int32_t *d_out_roi_count, int32_t *d_out_count,
+                                             int32_t *d_out_index, float *d_out_max, int32_t *d_out_argmax, float *d_out_avg, double *d_out_pose, void *stream)
+{
+    if (!ctx) return SNOWGPU_E_INVALID;
+    const SgRoiAwareArgs a{n_frames, n_total, max_frame_rows, dtype, d_frame_offsets, d_rows, n_rois, d_rois, roi_features, extra_width3, out_size3, max_points,
+                           roi_capacity, d_features, feature_channels, d_pose_in, d_keep_in, d_out_roi_count, d_out_count, d_out_index, d_out_max, d_out_argmax,
+                           d_out_avg, d_out_pose};
+    {
+        std::string msg;
+        if (int rc = sg_check_roiaware_args(a, &msg)) return fail(ctx, rc, msg);
+    }
+    const double ew[3] = {extra_width3 ? extra_width3[0] : 0.0, extra_width3 ? extra_width3[1] : 0.0, extra_width3 ? extra_width3[2] : 0.0};
+    const int32_t grid[3] = {out_size3[0], out_size3[1], out_size3[2]};
+    const int64_t longest = sg_max_frame(max_frame_rows, n_total);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    ENSURE(ctx, ctx->rv_rec, sg_box_records(n_frames, n_rois) * (sizeof(SgBoxRec) / sizeof(double)));
+    ENSURE(ctx, ctx->rv_table, sg_box_table(n_frames, n_rois));
+    if (n_total > 0) {
+        ENSURE(ctx, ctx->rv_runs, sg_roi_table(n_frames, longest, n_rois));
+        ENSURE(ctx, ctx->rv_list, sg_roiaware_list(n_frames, n_rois, roi_capacity));
+        ENSURE(ctx, ctx->rv_sorted, sg_roiaware_list(n_frames, n_rois, roi_capacity));
+        ENSURE(ctx, ctx->rv_offset, sg_roiaware_offsets(n_frames, n_rois, grid[0] * grid[1] * grid[2]));
+    }
+    int e = sg_launch_roiaware(d_rows, dtype, n_total, longest, d_frame_offsets, n_frames, d_keep_in, n_rois, d_rois, roi_features, ew, grid, max_points, roi_capacity,
+                               d_features, (d_features || d_out_max || d_out_argmax || d_out_avg) ? feature_channels : 1, d_pose_in, (SgBoxRec *)ctx->rv_rec.p, ctx->rv_table.p, ctx->rv_runs.p, ctx->rv_list.p,
+                               ctx->rv_sorted.p, ctx->rv_offset.p, d_out_roi_count, d_out_count, d_out_index, d_out_max, d_out_argmax, d_out_avg, d_out_pose,
+                               stream ? (hipStream_t)stream : ctx->stream);
+    if (e) return fail(ctx, SNOWGPU_E_HIP, std::string("roi voxel pool launch: ") + hipGetErrorString((hipError_t)e));
     return SNOWGPU_OK;
 }
 

@@ -18,7 +18,8 @@
 // The walk visits a roi ONCE per step for the whole wave (not every lane its own lowest bit, as k_box_rows does): only then do the members
 // of one roi meet in one ballot, which is what makes the lane order the row order.  A wave owns its run, so there is no scan across the
 // waves of a block and no barrier inside the walk.  The marks are ORs, the counts integer sums in a fixed order: two calls give identical
-// bytes.
+// bytes.  The first four kernels are a launcher of their own, sg_launch_roi_members: the RoI-aware voxel pooling (snowgpu_roiaware.hip) starts
+// from the same members in the same order.
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off (see lidar_snow_sim_amd/build.py).
 #include <hip/hip_runtime.h>
 
@@ -226,16 +227,17 @@ __global__ __launch_bounds__(SG_ROI_BLOCK) void k_roi_finish(const T *__restrict
     }
 }
 
-// The whole sequence on `stream`.  rec: sg_box_records(n_frames, n_rois) records; table: sg_box_table(n_frames, n_rois) words; run_cnt:
-// sg_roi_table(n_frames, max_frame, n_rois) int32.  A batch without a row has its pose written by the first kernel and everything else
-// by the last; nothing is launched over rows.
-extern "C" int sg_launch_roipool(const void *rows, int dtype, int64_t n, int64_t max_frame, const int64_t *frame_off, int n_frames, const uint8_t *keep_in,
-                                 int32_t n_rois, const void *rois, int32_t roi_features, const double *ew, int32_t n_samples, int32_t num_features,
-                                 const double *pose_in, SgBoxRec *rec, unsigned long long *table, int32_t *run_cnt, int32_t *out_index, int32_t *out_count,
-                                 void *out_points, void *out_local, double *out_pose, void *stream)
+// The members of every roi on `stream`: the rois filed, the walk twice with the scan between.  count receives every roi's members, index
+// (n_frames, n_rois, n_slots) its first n_slots of them in row order; slots from the count on are NOT written.  rec: sg_box_records(n_frames,
+// n_rois) records; table: sg_box_table(n_frames, n_rois) words; run_cnt: sg_roi_table(n_frames, max_frame, n_rois) int32.  A batch without a
+// row has the rois filed and the pose written; nothing is launched over rows and count is not written.  snowgpu_roiaware.hip starts here too.
+extern "C" int sg_launch_roi_members(const void *rows, int dtype, int64_t n, int64_t max_frame, const int64_t *frame_off, int n_frames, const uint8_t *keep_in,
+                                     int32_t n_rois, const void *rois, int32_t roi_features, const double *ew, int32_t n_slots, const double *pose_in,
+                                     SgBoxRec *rec, unsigned long long *table, int32_t *run_cnt, int32_t *out_index, int32_t *out_count, double *out_pose,
+                                     void *stream)
 {
     hipStream_t st = (hipStream_t)stream;
-    const int64_t runs = sg_roi_runs(max_frame), slots = (int64_t)n_frames * n_rois, total = slots * n_samples;
+    const int64_t runs = sg_roi_runs(max_frame), slots = (int64_t)n_frames * n_rois;
     const dim3 walk((unsigned)((runs + SG_ROI_WAVES - 1) / SG_ROI_WAVES * n_frames));          // (below 2^31: sg_check_roipool_args)
     return sg_by_dtype(dtype, [&](auto t) {
         using T = decltype(t);
@@ -247,10 +249,28 @@ extern "C" int sg_launch_roipool(const void *rows, int dtype, int64_t n, int64_t
             SG_CHECK_LAUNCH();
             hipLaunchKernelGGL(k_roi_scan, dim3((unsigned)((slots + SG_ROI_BLOCK - 1) / SG_ROI_BLOCK)), dim3(SG_ROI_BLOCK), 0, st, run_cnt, runs, n_rois, slots, out_count);
             SG_CHECK_LAUNCH();
-            hipLaunchKernelGGL(k_roi_rank<T>, walk, dim3(SG_ROI_BLOCK), 0, st, (const T *)rows, n, frame_off, runs, keep_in, n_rois, n_samples, rec, table, run_cnt,
+            hipLaunchKernelGGL(k_roi_rank<T>, walk, dim3(SG_ROI_BLOCK), 0, st, (const T *)rows, n, frame_off, runs, keep_in, n_rois, n_slots, rec, table, run_cnt,
                                out_index);
             SG_CHECK_LAUNCH();
         }
+        return 0;
+    });
+}
+
+// The whole sequence on `stream`: the members, then the finish.  A batch without a row has its pose written by the first kernel and
+// everything else by the last; nothing is launched over rows.
+extern "C" int sg_launch_roipool(const void *rows, int dtype, int64_t n, int64_t max_frame, const int64_t *frame_off, int n_frames, const uint8_t *keep_in,
+                                 int32_t n_rois, const void *rois, int32_t roi_features, const double *ew, int32_t n_samples, int32_t num_features,
+                                 const double *pose_in, SgBoxRec *rec, unsigned long long *table, int32_t *run_cnt, int32_t *out_index, int32_t *out_count,
+                                 void *out_points, void *out_local, double *out_pose, void *stream)
+{
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t total = (int64_t)n_frames * n_rois * n_samples;
+    if (int e = sg_launch_roi_members(rows, dtype, n, max_frame, frame_off, n_frames, keep_in, n_rois, rois, roi_features, ew, n_samples, pose_in, rec, table, run_cnt,
+                                      out_index, out_count, out_pose, stream))
+        return e;
+    return sg_by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
         hipLaunchKernelGGL(k_roi_finish<T>, dim3((unsigned)((total + SG_ROI_BLOCK - 1) / SG_ROI_BLOCK)), dim3(SG_ROI_BLOCK), 0, st, (const T *)rows, n, n_samples,
                            num_features, total, rec, n > 0 ? 0 : 1, out_count, out_index, (T *)out_points, (T *)out_local);
         SG_CHECK_LAUNCH();

@@ -1,6 +1,6 @@
 """The device stages of the torch-tensor boundary (tensors.py is the documented import path and lists what each is for) and the batches
 of static shape they leave behind: fov_keep, dror_keep, voxelize, sample_keypoints, ball_query, range_image, nearest_keypoints,
-points_in_boxes, boxes_iou, nms, roi_point_pool.  Every stage goes through the same steps, in this order -- it is the order in which a call that is wrong
+points_in_boxes, boxes_iou, nms, roi_point_pool, roi_voxel_pool.  Every stage goes through the same steps, in this order -- it is the order in which a call that is wrong
 in two ways is refused: the aligned unwrap and the device-input refusal (_stage_frames), the scalar and range checks (_whole, _range6),
 the batch and its keep mask (_stage_batch), the stage's own tensors, the checks of the shapes' domain, out= (_checked_out), the launch
 (_stage_launch).  PyTorch is plumbing here; the work is the C entries'."""
@@ -919,3 +919,167 @@ def roi_point_pool(frames, rois, n_samples=512, *, extra_width=(0., 0., 0.), pos
                   0 if local is None else local.data_ptr(), 0 if used is None else used.data_ptr())
     same = (points is None) == (out.points is None) and (local is None) == (out.local is None) and (used is None) == (out.pose is None)
     return out if same else RoiPointBatch(out.index, out.count, points, local, used)
+
+
+class RoiVoxelBatch:
+    """What roi_voxel_pool() leaves behind, F = frames, M = rois per frame, G = Gx Gy Gz sub-voxels of a roi in pcdet's (out_x, out_y, out_z)
+    order, T = max_points, Cf = feature channels -- every shape static: `roi_count` (F, M int32: all members of the roi, clipped by no cap),
+    `count` (F, M, G int32: the voxel's members among the roi's first roi_capacity, NOT clipped at T), `index` (F, M, G, T int32: the global
+    rows of the voxel's first T members in row order, -1 behind them; None unless asked for), `max` and `argmax` (F, M, G, Cf float32 /
+    int32: the maximum of every channel over those members and the row that holds it -- the first of equal maxima, never a NaN; 0 and -1
+    without one; None unless pooled), `avg` (F, M, G, Cf float32: their float32 sum in row order over their number, 0 for an empty voxel;
+    None unless pooled) and `pose` (F, M, 2 float64: the (cos, sin) that was used, (0, 0) for an absent roi).  `out_size` is (Gx, Gy, Gz);
+    as_grid() views a field as (F, M, Gx, Gy, Gz, ...).  max_features() and avg_features() are pure indexing, no kernel of this library.
+    At F = 16, M = 128, G = 12^3, Cf = 128 each pooled field is 1.8 GB.  All still being written until the stream the call was made on has
+    caught up."""
+
+    def __init__(self, roi_count, count, index=None, max=None, argmax=None, avg=None, pose=None, out_size=None, max_points=None):
+        self.roi_count, self.count, self.index, self.max, self.argmax, self.avg, self.pose = roi_count, count, index, max, argmax, avg, pose
+        self.out_size, self.max_points = out_size, max_points
+
+    @classmethod
+    def empty(cls, n_frames, n_rois, out_size=12, max_points=127, channels=None, device=None, with_index=False, pool=('max', 'avg')):
+        """Uninitialised buffers of the shapes roi_voxel_pool() writes (out=): static addresses for a captured graph.  channels: Cf of the
+        features that will be pooled, None for none."""
+        import torch
+        dev = _cuda_device(torch, device)
+        grid = _out_size3("RoiVoxelBatch.empty", out_size)
+        F, M, G, T = int(n_frames), int(n_rois), grid[0] * grid[1] * grid[2], int(max_points)
+        i32, f32 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.float32, device=dev)
+        Cf = None if channels is None else int(channels)
+        mx, av = Cf is not None and 'max' in pool, Cf is not None and 'avg' in pool
+        return cls(torch.empty((F, M), **i32), torch.empty((F, M, G), **i32), torch.empty((F, M, G, T), **i32) if with_index else None,
+                   torch.empty((F, M, G, Cf), **f32) if mx else None, torch.empty((F, M, G, Cf), **i32) if mx else None,
+                   torch.empty((F, M, G, Cf), **f32) if av else None, torch.empty((F, M, 2), dtype=torch.float64, device=dev), grid, T)
+
+    @property
+    def nonempty(self):
+        """(F, M, G) bool: count > 0."""
+        return self.count > 0
+
+    def as_grid(self, field):
+        """A field of (F, M, G, ...) viewed as (F, M, Gx, Gy, Gz, ...): pcdet's pooled_features layout per roi."""
+        return field.view(field.shape[0], field.shape[1], *self.out_size, *field.shape[3:])
+
+    def _features(self, who, features):
+        import torch
+        if not (torch.is_tensor(features) and features.dim() == 2 and features.device == self.count.device and features.is_floating_point()):
+            raise ValueError(f"{who}: features must be an (N, Cf) floating-point tensor on the device of the rows: Cf values per row")
+        return features
+
+    def max_features(self, features):
+        """features[argmax] per channel as (F, M, G, Cf), zeros where argmax is -1: bit-equal to `max` for the features that were pooled, and
+        differentiable with respect to `features` through torch's own indexing (the gradient of a voxel goes to the row that won)."""
+        import torch
+        features = self._features("max_features", features)
+        if self.argmax is None or self.argmax.shape[-1] != features.shape[1]:
+            raise ValueError("max_features: this batch has no argmax for features of that many channels (roi_voxel_pool(..., features=, pool=('max', ...)))")
+        at = self.argmax.long()
+        got = features[at.clamp(min=0), torch.arange(features.shape[1], device=features.device)]
+        return torch.where(at >= 0, got, torch.zeros_like(got))
+
+    def avg_features(self, features):
+        """The mean of `features` over every voxel's pooled rows as (F, M, G, Cf), zeros for an empty voxel: the gather over `index`, summed
+        slot after slot -- the order in which `avg` was summed -- and divided by the number of rows; differentiable with respect to
+        `features`.  One gather and one add per slot: T of each."""
+        import torch
+        features = self._features("avg_features", features)
+        if self.index is None:
+            raise ValueError("avg_features: this batch has no index (roi_voxel_pool(..., return_index=True))")
+        at = self.index.long()
+        has = at >= 0
+        total = torch.zeros(at.shape[:3] + (features.shape[1],), dtype=features.dtype, device=features.device)
+        for t in range(at.shape[3]):
+            got = features[at[..., t].clamp(min=0)]                           # (F, M, G, Cf)
+            total = total + torch.where(has[..., t, None], got, torch.zeros_like(got))
+        return total / has.sum(dim=3).clamp(min=1)[..., None].to(total.dtype)
+
+
+def _out_size3(who, out_size):
+    """out_size as (Gx, Gy, Gz) ints: a whole number for all three, or three of them, each in 1 .. 16."""
+    g = np.asarray(out_size).reshape(-1)
+    if g.shape == (1,):
+        g = np.repeat(g, 3)
+    if g.shape != (3,) or g.dtype == bool or not np.all(g == np.floor(g)) or not ((g >= 1) & (g <= 16)).all():
+        raise ValueError(f"{who}: out_size is a whole number or three (x, y, z), each in 1 .. 16")
+    return tuple(int(v) for v in g)
+
+
+def roi_voxel_pool(frames, rois, out_size=12, max_points=127, features=None, extra_width=0.0, roi_capacity=8192, pose=None, keep=None, return_index=False,
+                   pool=('max', 'avg'), out=None, *, device=None, slot=0):
+    """RoI-aware voxel pooling on the device (snowgpu_roi_voxel_pool_device; the definition: include/snowgpu.h): pcdet's roiaware_pool3d --
+    every slightly enlarged roi cut into out_size sub-voxels along its own axes, the rows inside each listed in row order and their
+    features max- and average-pooled -- with points_in_boxes' membership test in float64 and static shapes.
+
+    frames    what roi_point_pool takes -- torch CUDA tensors, a DeviceBatch, or an AlignedResult / AlignedWetResult: its rows, offsets and
+              keep mask are used (nothing is waited for).
+    rois      a contiguous (F, M, 7 .. 10) tensor in the rows' dtype on their device, 1 <= M <= 512 -- or an NmsBatch, whose `boxes` are
+              used (the zero rows behind its count are absent rois).
+    out_size  a whole number or three (x, y, z), each in 1 .. 16: the sub-voxels along the roi's length, width and height.
+    max_points    1 .. 128: T, the members of a voxel that are pooled and indexed (pcdet's max_pts_each_voxel = 128 keeps 127).
+    features  None, or a contiguous (N, Cf) float32 tensor on the device of the rows, one row per row of the batch, 1 <= Cf <= 256.
+    extra_width   a number or three (x, y, z), each in 0 .. 100: added once to dx, dy, dz (Part-A2 passes none).
+    roi_capacity  64 .. 65536: only a roi's first roi_capacity members are distributed to voxels (scratch: two int32 per roi and slot).
+    pose      None: cos / sin of the heading in float64 on the device; or a contiguous (F, M, 2) float64 tensor (cos, sin) used as it is.
+    keep      an input keep mask as the aligned calls take it (with a result: ANDed with the result's own).
+    return_index  also fill `index` (F, M, G, T).
+    pool      which of 'max' (max and argmax) and 'avg' to compute from `features`.
+    out       a RoiVoxelBatch to write into (RoiVoxelBatch.empty): every element is written, nothing needs clearing.
+
+    Returns a RoiVoxelBatch.  Asynchronous on torch's current stream; nothing is read on the host: capturable after one warm-up call."""
+    import torch
+    who = "roi_voxel_pool"
+    frames, keep = _stage_frames(torch, who, "lidar_snow_sim_amd.roiaware.roiaware_pool3d", frames, keep)
+    _whole(who, max_points=max_points, roi_capacity=roi_capacity)
+    grid = _out_size3(who, out_size)
+    ew = np.asarray(extra_width, np.float64).reshape(-1)
+    if ew.shape == (1,):
+        ew = np.repeat(ew, 3)
+    if ew.shape != (3,) or not ((ew >= 0.0) & (ew <= 100.0)).all():
+        raise ValueError("roi_voxel_pool: extra_width is a number or three (x, y, z), each finite and in 0 .. 100")
+    pool = (pool,) if isinstance(pool, str) else tuple(pool)
+    if any(p not in ('max', 'avg') for p in pool):
+        raise ValueError("roi_voxel_pool: pool holds 'max', 'avg' or both")
+    rows, offsets, eng, dev, nf, n, keep = _stage_batch(torch, frames, keep, device, slot)
+    if isinstance(rois, NmsBatch):
+        if rois.boxes is None:
+            raise ValueError("roi_voxel_pool: this NmsBatch has no boxes (nms(..., return_boxes=True))")
+        rois = rois.boxes
+    if not (torch.is_tensor(rois) and rois.dim() == 3 and rois.shape[0] == nf and rois.dtype == rows.dtype and rois.device == dev and rois.is_contiguous()):
+        raise ValueError("roi_voxel_pool: rois must be a contiguous (frames, M, 7 .. 10) tensor in the rows' dtype on their device, or an NmsBatch of such boxes")
+    if features is not None and not (torch.is_tensor(features) and features.dim() == 2 and features.shape[0] == rows.shape[0] and features.dtype == torch.float32
+                                     and features.device == dev and features.is_contiguous()):
+        raise ValueError("roi_voxel_pool: features must be a contiguous (N, Cf) float32 tensor on the device of the rows, one row per row of the batch")
+    M, Cb, T, P, G = int(rois.shape[1]), int(rois.shape[2]), int(max_points), int(roi_capacity), grid[0] * grid[1] * grid[2]
+    Cf = None if features is None else int(features.shape[1])
+    # (the shapes below need these; the entry refuses them in the same words, and everything else of the domain)
+    if not 1 <= M <= 512:
+        raise ValueError("roi_voxel_pool: n_rois must lie in 1 .. 512 (rois)")
+    if not 7 <= Cb <= 10:
+        raise ValueError("roi_voxel_pool: roi_features must lie in 7 .. 10: cx, cy, cz, dx, dy, dz, heading first (rois)")
+    if not 1 <= T <= 128:
+        raise ValueError("roi_voxel_pool: max_points must lie in 1 .. 128")
+    if not 64 <= P <= 65536:
+        raise ValueError("roi_voxel_pool: roi_capacity must lie in 64 .. 65536")
+    if Cf is not None and not 1 <= Cf <= 256:
+        raise ValueError("roi_voxel_pool: feature_channels must lie in 1 .. 256 (features)")
+    if nf * M * G * max(T, Cf or 1) > 2 ** 31 - 1:
+        raise ValueError("roi_voxel_pool: n_frames * n_rois * the voxels of a roi * max(max_points, feature_channels) exceeds 2^31 - 1; split the batch")
+    if pose is not None and not (torch.is_tensor(pose) and tuple(pose.shape) == (nf, M, 2) and pose.dtype == torch.float64 and pose.device == dev and pose.is_contiguous()):
+        raise ValueError(f"roi_voxel_pool: pose must be a contiguous {(nf, M, 2)} float64 tensor (cos, sin) on the device of the rows")
+    do_max, do_avg = Cf is not None and 'max' in pool, Cf is not None and 'avg' in pool
+    want = (("roi_count", torch.int32, (nf, M), True), ("count", torch.int32, (nf, M, G), True), ("index", torch.int32, (nf, M, G, T), bool(return_index)),
+            ("max", torch.float32, (nf, M, G, Cf), do_max), ("argmax", torch.int32, (nf, M, G, Cf), do_max), ("avg", torch.float32, (nf, M, G, Cf), do_avg),
+            ("pose", torch.float64, (nf, M, 2), True))
+    if out is None:
+        out = RoiVoxelBatch.empty(nf, M, grid, T, Cf, dev, return_index, pool)
+    else:
+        _checked_out(torch, who, RoiVoxelBatch, out, want, dev, _ROWS)
+    index, mx, am, av = (out.index if return_index else None), (out.max if do_max else None), (out.argmax if do_max else None), (out.avg if do_avg else None)
+    ptr = lambda t: 0 if t is None else t.data_ptr()
+    _stage_launch(torch, eng, dev, nf, n, offsets, rows, eng.ctx.roi_voxel_pool_device, M, rois.data_ptr(), Cb, ew, grid, T, P,
+                  ptr(features) if (do_max or do_avg) else 0, Cf or 0, ptr(pose), 0 if keep is None or not n else keep.data_ptr(), out.roi_count.data_ptr(),
+                  out.count.data_ptr(), ptr(index), ptr(mx), ptr(am), ptr(av), out.pose.data_ptr())
+    same = (index is None) == (out.index is None) and (mx is None) == (out.max is None) and (av is None) == (out.avg is None) and out.out_size == grid \
+        and out.max_points == T
+    return out if same else RoiVoxelBatch(out.roi_count, out.count, index, mx, am, av, out.pose, grid, T)
