@@ -1186,6 +1186,77 @@ int snowgpu_draw_weather_device(snowgpu_ctx *ctx, int n_frames, int n_lasers, in
                                 const snowgpu_weather_plan *plan /* host */, uint64_t seed, const uint64_t *d_step,
                                 int32_t *d_table_ids /* n_frames x n_lasers */, double *d_weather /* n_frames x 8 */, void *stream);
 
+/*
+ * PROPOSAL TARGET SAMPLING: which S = roi_per_image of a frame's M rois the second stage trains on, and their targets -- the step of
+ * OpenPCDet's ProposalTargetLayer (sample_rois_for_rcnn, subsample_rois, sample_bg_inds) between the best overlaps of
+ * snowgpu_boxes_iou_device and the two pooling stages, with static shapes, nothing read on the host and a seeded draw.  pcdet is not part
+ * of the reference checkout: the definition below is THIS LIBRARY'S, modelled on pcdet's layer as recalled, and was NOT CHECKED against
+ * pcdet's source.  pcdet draws from torch's global generator (randperm / randint); here the draws are Philox words, so parity with
+ * pcdet's random stream is distributional, as for the weather draw.  The definition is restated in NumPy and Python integers by
+ * tests/targets_reference.py; csrc/sg_targets.h holds its C++, for the device and for the host.
+ *   INPUTS, F = n_frames, M = n_rois, B = n_gt, T = float32 or float64: d_rois (F, M, Cb) T and d_gt_boxes (F, B, Cg) T, Cb and Cg in 7 .. 10,
+ *   columns 0 .. 6 cx, cy, cz, dx, dy, dz, heading; d_overlap (F, M) T and d_assignment (F, M) int32 -- d_out_best_iou and d_out_best of
+ *   snowgpu_boxes_iou_device as they stand (max_overlaps, gt_assignment); d_pose (F, M, 2) float64 (cos, sin) or NULL; cfg in HOST memory,
+ *   read during the call; seed; d_step, a uint64 in DEVICE memory read by the kernel.
+ *   CANDIDATES: roi m is a candidate iff it is PRESENT by the rule of snowgpu_points_in_boxes_device (all seven finite, the 1e6 bounds,
+ *   0 < dx, dy, dz <= 1e6, the pose check -- under the given pose or cos / sin of (double)heading from the device library) and its overlap
+ *   is not NaN.  The zero rows behind the count of snowgpu_nms_device are therefore NEVER sampled; pcdet samples its zero padding as easy
+ *   background.  An assignment outside 0 .. B - 1 counts as -1.
+ *   CLASSES, ov = (double)overlap, fg_thresh = min(reg_fg_thresh, cls_fg_thresh): FG ov >= fg_thresh; HARD ov < reg_fg_thresh and
+ *   ov >= cls_bg_thresh_lo; EASY ov < cls_bg_thresh_lo.  Each class is the list of its candidates in ASCENDING roi number, n_fg, n_hard,
+ *   n_easy their lengths, n_bg = n_hard + n_easy.  FG and HARD overlap when reg_fg_thresh > cls_fg_thresh, as in pcdet.
+ *   DRAWS: r_k = word k % 4 of Philox4x32-10 under key `seed` at counter (step, frame f, 0x524F4953 + k / 4), the argument positions of
+ *   the weather draw above.  Slot k always uses r_k, whatever the other slots do.  A pick WITH REPLACEMENT from a list of n is
+ *   list[(r_k n) >> 32].
+ *   SLOTS hold fg picks, then hard picks, then easy picks:
+ *     (a) n_fg > 0 and n_bg > 0: fg_this = min(fg_per_image, n_fg) picks WITHOUT replacement by a forward Fisher-Yates walk -- for
+ *         i = 0 .. fg_this - 1: j = i + ((r_i (n_fg - i)) >> 32), swap list[i] and list[j], the pick is list[i] --; bg_this = S - fg_this;
+ *     (b) n_fg > 0, n_bg = 0: S fg picks with replacement;
+ *     (c) n_fg = 0, n_bg > 0: bg_this = S;
+ *     (d) no candidate: every slot is empty.
+ *   BACKGROUND PICKS of count n, all with replacement: with both lists non-empty hard_this = min((int)((double)n hard_bg_ratio), n_hard)
+ *   -- one float64 product, truncated -- and the rest easy picks; with one list non-empty all n from it.
+ * Outputs, every shape static, every element written by every call; an empty slot gives -1 / 0:
+ *   d_out_index       (F, S) int32: the roi number
+ *   d_out_rois        (F, S, Cb) T: bit copies of the picked rois, zero rows in empty slots: a rois tensor as it stands
+ *   d_out_roi_iou     (F, S) T: the pick's overlap
+ *   d_out_gt_index    (F, S) int32: its assignment
+ *   d_out_gt_of_rois  (F, S, Cg) T: a bit copy of gt_boxes[f, gt_index], a ZERO row where gt_index is -1 (pcdet hands back gt 0 there;
+ *                     only reg_valid slots use the gt, and those have one when the overlaps are the IoU stage's)
+ *   d_out_reg_valid   (F, S) uint8: ov > reg_fg_thresh
+ *   d_out_cls_label   (F, S) T, -1 in an empty slot.  cls_mode 0 ('roi_iou'): 1 if ov > cls_fg_thresh; 0 if ov < cls_bg_thresh; otherwise
+ *                     (ov - cls_bg_thresh) / (cls_fg_thresh - cls_bg_thresh) in float64, each operation rounded on its own, then (T).
+ *                     cls_mode 1 ('cls'): 1 if ov > cls_fg_thresh; -1 if cls_bg_thresh < ov < cls_fg_thresh; otherwise 0
+ *   d_out_segments    (F, 3) int32: (fg_this, hard_this, easy_this);   d_out_class_count (F, 3) int32: (n_fg, n_hard, n_easy)
+ *   d_out_pose        (F, S, 2) float64, or NULL: the pose used for the pick, (0, 0) in an empty slot
+ *   d_out_gt_local    (F, S, 7) T, or NULL: the head's canonical transformation of the gt into the roi's frame, [lx, ly, lz, dx, dy, dz,
+ *                     heading_label]; zeros where the slot is empty, gt_index is -1 or one of the gt's seven values is not within 1e6 (NaN
+ *                     and inf included).  sx = gx - cx, sy = gy - cy, lz = gz - cz; lx = sx c + sy s, ly = sy c - sx s -- float64, every
+ *                     operation rounded on its own, no fused multiply-add; dx, dy, dz the gt's, bit copies.  With pmod(x) = fmod(x, 2 pi),
+ *                     plus 2 pi when that is negative, +0 when it is zero: ry = pmod(h_roi); hl = pmod(h_gt - ry); if pi / 2 < hl < 3 pi / 2
+ *                     then hl = pmod(hl + pi); if hl > pi then hl -= 2 pi; hl clamped to [-pi / 2, pi / 2]; stored as (T)hl.  The constants
+ *                     are the doubles nearest pi, 2 pi, pi / 2 and 3 pi / 2 (NumPy's np.pi, 2 * np.pi, 0.5 * np.pi, 1.5 * np.pi).
+ * Domain: 1 <= M, B <= 9216; Cb, Cg in 7 .. 10; 1 <= S <= 1024; 0 <= fg_per_image <= S; the five thresholds finite;
+ * cls_fg_thresh > cls_bg_thresh; hard_bg_ratio in [0, 1]; cls_mode 0 or 1; F S max(Cb, Cg) <= 2^31 - 1; dtype 0 or 1; every output apart
+ * from every input and every other output.  Anything else is SNOWGPU_E_INVALID with a message.
+ * One kernel on `stream`, one workgroup per frame: the classes of every roi, the three ordered lists by wave ballots and prefix sums in
+ * LDS (uint16 entries), the Philox blocks one per lane, the walk without replacement on one lane in LDS (at most S dependent steps),
+ * then one lane per slot (csrc/snowgpu_targets.hip).  No atomics, no memset, no scratch, nothing read on the host, nothing allocated:
+ * capturable as a linear graph; a replayed graph that also holds a `step += 1` draws anew on every replay.  Two calls with one step give
+ * identical bytes.  The frame's position in the batch is part of the counter: frame f of a batch equals a one-frame call only at f = 0.
+ */
+typedef struct snowgpu_roi_sampler {
+    int32_t roi_per_image, fg_per_image;
+    double reg_fg_thresh, cls_fg_thresh, cls_bg_thresh, cls_bg_thresh_lo, hard_bg_ratio;
+    int32_t cls_mode;
+} snowgpu_roi_sampler;
+int snowgpu_sample_rois_device(snowgpu_ctx *ctx, int n_frames, int n_rois, const void *d_rois, int roi_features, const void *d_overlap,
+                               const int32_t *d_assignment, int n_gt, const void *d_gt_boxes, int gt_features, int dtype,
+                               const snowgpu_roi_sampler *cfg /* host */, uint64_t seed, const uint64_t *d_step, const double *d_pose /* or NULL */,
+                               int32_t *d_out_index, void *d_out_rois, void *d_out_roi_iou, int32_t *d_out_gt_index, void *d_out_gt_of_rois,
+                               uint8_t *d_out_reg_valid, void *d_out_cls_label, int32_t *d_out_segments, int32_t *d_out_class_count,
+                               double *d_out_pose /* or NULL */, void *d_out_gt_local /* or NULL */, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

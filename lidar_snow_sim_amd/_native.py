@@ -32,7 +32,7 @@ EXPORTS = [
     "snowgpu_augment_weather_batch_device_aligned", "snowgpu_draw_weather_device", "snowgpu_dror_mask_device",
     "snowgpu_voxelize_device", "snowgpu_fps_device", "snowgpu_ball_query_device", "snowgpu_range_image_device",
     "snowgpu_nearest_centres_device", "snowgpu_points_in_boxes_device", "snowgpu_boxes_iou_device", "snowgpu_nms_device", "snowgpu_fps_sectors_device",
-    "snowgpu_roi_point_pool_device", "snowgpu_roi_voxel_pool_device",
+    "snowgpu_roi_point_pool_device", "snowgpu_roi_voxel_pool_device", "snowgpu_sample_rois_device",
 ]
 
 WET_ESTIMATION = {"linear": 0, "poly": 1}
@@ -58,6 +58,24 @@ def weather_plan_struct(p_snow, p_wet, water_heights, pavement_depths, noise_flo
     for i, v in enumerate(pd[:16]):
         s.pavement_depths[i] = v
     s.wet_noise_floor, s.power_factor, s.delta, s.shuffle = float(noise_floor), float(power_factor), float(delta), int(bool(shuffle))
+    return s
+
+
+CLS_SCORE_TYPES = {"roi_iou": 0, "cls": 1}
+
+
+class RoiSamplerStruct(ctypes.Structure):
+    """snowgpu_roi_sampler (include/snowgpu.h)."""
+    _fields_ = [("roi_per_image", ctypes.c_int32), ("fg_per_image", ctypes.c_int32), ("reg_fg_thresh", ctypes.c_double), ("cls_fg_thresh", ctypes.c_double),
+                ("cls_bg_thresh", ctypes.c_double), ("cls_bg_thresh_lo", ctypes.c_double), ("hard_bg_ratio", ctypes.c_double), ("cls_mode", ctypes.c_int32)]
+
+
+def roi_sampler_struct(roi_per_image, fg_per_image, reg_fg_thresh, cls_fg_thresh, cls_bg_thresh, cls_bg_thresh_lo, hard_bg_ratio, cls_mode):
+    """The settings of snowgpu_sample_rois_device from Python values; a count beyond int32 reaches the entry as one it refuses."""
+    s = RoiSamplerStruct()
+    s.roi_per_image, s.fg_per_image, s.cls_mode = _i32(roi_per_image), _i32(fg_per_image), _i32(cls_mode)
+    s.reg_fg_thresh, s.cls_fg_thresh, s.cls_bg_thresh = float(reg_fg_thresh), float(cls_fg_thresh), float(cls_bg_thresh)
+    s.cls_bg_thresh_lo, s.hard_bg_ratio = float(cls_bg_thresh_lo), float(hard_bg_ratio)
     return s
 
 
@@ -141,6 +159,9 @@ def lib():
             L.snowgpu_draw_weather_device.restype = ctypes.c_int
             L.snowgpu_draw_weather_device.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, ctypes.POINTER(WeatherPlanStruct),
                                                       ctypes.c_uint64, vp, vp, vp, vp]
+            L.snowgpu_sample_rois_device.restype = ctypes.c_int
+            L.snowgpu_sample_rois_device.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, vp, vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int,
+                                                     ctypes.POINTER(RoiSamplerStruct), ctypes.c_uint64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
             L.snowgpu_fov_mask_device.restype = ctypes.c_int
             L.snowgpu_fov_mask_device.argtypes = [vp, i64, vp, ctypes.c_int, vp, vp, vp, ctypes.c_int, ctypes.c_int, vp, vp, vp]
             L.snowgpu_dror_mask_device.restype = ctypes.c_int
@@ -729,6 +750,23 @@ class Context:
         rc = self._L.snowgpu_nms_device(self._h, _i32(n_frames), _i32(n_boxes), vp(d_boxes or None), _i32(box_features), vp(d_scores or None), int(dtype_code),
                                         int(mode), float(iou_thresh), float(score_thresh), _i32(post_max), vp(d_pose_in or None), vp(d_out_index or None),
                                         vp(d_out_count or None), vp(d_out_boxes or None), vp(d_out_scores or None), vp(d_out_kept or None), vp(stream or None))
+        self._check_args(rc)
+
+    def sample_rois_device(self, n_frames, n_rois, d_rois, roi_features, d_overlap, d_assignment, n_gt, d_gt_boxes, gt_features, dtype_code, cfg, seed, d_step,
+                           d_pose, d_out_index, d_out_rois, d_out_roi_iou, d_out_gt_index, d_out_gt_of_rois, d_out_reg_valid, d_out_cls_label, d_out_segments,
+                           d_out_class_count, d_out_pose, d_out_gt_local, stream=0):
+        """The sampled rois of every frame and their targets (include/snowgpu.h: snowgpu_sample_rois_device); asynchronous on `stream`.
+        cfg: a RoiSamplerStruct (roi_sampler_struct), read during the call; d_step: a uint64 in device memory, read by the kernel.  d_pose,
+        d_out_pose and d_out_gt_local may be 0.  An argument outside the domain, or an output overlapping an input or another output,
+        raises ValueError with the entry's words."""
+        vp = ctypes.c_void_p
+        rc = self._L.snowgpu_sample_rois_device(self._h, _i32(n_frames), _i32(n_rois), vp(d_rois or None), _i32(roi_features), vp(d_overlap or None),
+                                                vp(d_assignment or None), _i32(n_gt), vp(d_gt_boxes or None), _i32(gt_features), int(dtype_code),
+                                                ctypes.byref(cfg) if cfg is not None else None, ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), vp(d_step or None),
+                                                vp(d_pose or None), vp(d_out_index or None), vp(d_out_rois or None), vp(d_out_roi_iou or None),
+                                                vp(d_out_gt_index or None), vp(d_out_gt_of_rois or None), vp(d_out_reg_valid or None),
+                                                vp(d_out_cls_label or None), vp(d_out_segments or None), vp(d_out_class_count or None),
+                                                vp(d_out_pose or None), vp(d_out_gt_local or None), vp(stream or None))
         self._check_args(rc)
 
     def set_fov(self, calib=None, img_shape=(1024, 1920), pre_crop=False):

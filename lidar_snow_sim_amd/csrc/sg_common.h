@@ -355,6 +355,14 @@ int sg_launch_iou(int n_frames, int32_t M, const void *boxes_a, int32_t a_featur
 int sg_launch_nms(int n_frames, int32_t B, const void *boxes, int32_t box_features, const void *scores, int dtype, int mode, double iou_thresh,
                   double score_thresh, int32_t post_max, const double *pose_in, double *rec, int32_t *order, int32_t *n_cand, int32_t *out_index,
                   int32_t *out_count, void *out_boxes, void *out_scores, uint8_t *out_kept, void *stream);
+// Proposal target sampling (sg_targets.h; the definition: include/snowgpu.h): one kernel, no scratch.  cfg: host.  pose_in, out_pose and
+// out_gt_local may be null.
+struct SgTargetCfg;
+int sg_launch_sample_rois(const struct SgTargetCfg *cfg, int n_frames, int32_t n_rois, const void *rois, int32_t roi_features, const void *overlap,
+                          const int32_t *assign, int32_t n_gt, const void *gt, int32_t gt_features, int dtype, uint64_t seed, const uint64_t *d_step,
+                          const double *pose_in, int32_t *out_index, void *out_rois, void *out_roi_iou, int32_t *out_gt_index, void *out_gt_of_rois,
+                          uint8_t *out_reg_valid, void *out_cls_label, int32_t *out_segments, int32_t *out_class_count, double *out_pose,
+                          void *out_gt_local, void *stream);
 #ifdef __cplusplus
 }
 #endif

@@ -749,6 +749,81 @@ static inline int sg_check_nms_args(const SgNmsArgs &a, std::string *msg)
     return 0;
 }
 
+// ---- snowgpu_sample_rois_device -----------------------------------------------------------------------------------------------------------
+struct SgSamplerCfg {                 // snowgpu_roi_sampler (include/snowgpu.h), field for field
+    int roi_per_image, fg_per_image;
+    double reg_fg_thresh, cls_fg_thresh, cls_bg_thresh, cls_bg_thresh_lo, hard_bg_ratio;
+    int cls_mode;
+};
+
+struct SgTargetsArgs {
+    int n_frames;
+    int n_rois;                       // M, per frame
+    const void *rois;
+    int roi_features;                 // Cb
+    const void *overlap;
+    const int32_t *assignment;
+    int n_gt;                         // B, per frame
+    const void *gt_boxes;
+    int gt_features;                  // Cg
+    int dtype;
+    const SgSamplerCfg *cfg;          // host
+    const uint64_t *step;             // device
+    const double *pose_in;            // or NULL: cos / sin of the heading on the device
+    int32_t *out_index;
+    void *out_rois, *out_roi_iou;
+    int32_t *out_gt_index;
+    void *out_gt_of_rois;
+    uint8_t *out_reg_valid;
+    void *out_cls_label;
+    int32_t *out_segments, *out_class_count;
+    double *out_pose;                 // or NULL
+    void *out_gt_local;               // or NULL
+};
+
+// 0, or SG_ARGS_INVALID with *msg.  As above, the order is part of the ABI.
+static inline int sg_check_targets_args(const SgTargetsArgs &a, std::string *msg)
+{
+    static const char *who = "snowgpu_sample_rois_device";
+    if (a.n_frames <= 0 || !a.rois || !a.overlap || !a.assignment || !a.gt_boxes || !a.cfg || !a.step || !a.out_index || !a.out_rois || !a.out_roi_iou ||
+        !a.out_gt_index || !a.out_gt_of_rois || !a.out_reg_valid || !a.out_cls_label || !a.out_segments || !a.out_class_count || (a.dtype != 0 && a.dtype != 1))
+        return sg_refuse(who, ": null pointer or bad dtype", msg);
+    const SgSamplerCfg &c = *a.cfg;
+    if (a.n_rois < 1 || a.n_rois > 9216 || a.n_gt < 1 || a.n_gt > 9216) return sg_refuse(who, ": n_rois and n_gt must lie in 1 .. 9216", msg);
+    if (a.roi_features < 7 || a.roi_features > 10 || a.gt_features < 7 || a.gt_features > 10)
+        return sg_refuse(who, ": roi_features and gt_features must lie in 7 .. 10: cx, cy, cz, dx, dy, dz, heading first", msg);
+    if (c.roi_per_image < 1 || c.roi_per_image > 1024) return sg_refuse(who, ": roi_per_image must lie in 1 .. 1024", msg);
+    if (c.fg_per_image < 0 || c.fg_per_image > c.roi_per_image) return sg_refuse(who, ": fg_per_image must lie in 0 .. roi_per_image", msg);
+    if (!std::isfinite(c.reg_fg_thresh) || !std::isfinite(c.cls_fg_thresh) || !std::isfinite(c.cls_bg_thresh) || !std::isfinite(c.cls_bg_thresh_lo))
+        return sg_refuse(who, ": a threshold is NaN or infinite", msg);
+    if (!(c.cls_fg_thresh > c.cls_bg_thresh)) return sg_refuse(who, ": cls_fg_thresh must be above cls_bg_thresh", msg);
+    if (!(c.hard_bg_ratio >= 0.0 && c.hard_bg_ratio <= 1.0)) return sg_refuse(who, ": hard_bg_ratio must lie in 0 .. 1", msg);      // (false for NaN)
+    if (c.cls_mode != 0 && c.cls_mode != 1) return sg_refuse(who, ": cls_mode must be 0 (roi_iou) or 1 (cls)", msg);
+    const int64_t widest = a.roi_features > a.gt_features ? a.roi_features : a.gt_features;
+    if ((int64_t)a.n_frames * c.roi_per_image * widest > ((int64_t)1 << 31) - 1)
+        return sg_refuse(who, ": n_frames * roi_per_image * max(roi_features, gt_features) exceeds 2^31 - 1; split the batch", msg);
+    const size_t esz = a.dtype == 0 ? 4 : 8, q = (size_t)a.n_frames * (size_t)a.n_rois, g = (size_t)a.n_frames * (size_t)a.n_gt,
+                 k = (size_t)a.n_frames * (size_t)c.roi_per_image;
+    const struct { const void *p; size_t bytes; const char *name; } outs[11] = {
+        {a.out_index, k * 4, "d_out_index"}, {a.out_rois, k * (size_t)a.roi_features * esz, "d_out_rois"}, {a.out_roi_iou, k * esz, "d_out_roi_iou"},
+        {a.out_gt_index, k * 4, "d_out_gt_index"}, {a.out_gt_of_rois, k * (size_t)a.gt_features * esz, "d_out_gt_of_rois"}, {a.out_reg_valid, k, "d_out_reg_valid"},
+        {a.out_cls_label, k * esz, "d_out_cls_label"}, {a.out_segments, (size_t)a.n_frames * 12, "d_out_segments"},
+        {a.out_class_count, (size_t)a.n_frames * 12, "d_out_class_count"}, {a.out_pose, k * 16, "d_out_pose"}, {a.out_gt_local, k * 7 * esz, "d_out_gt_local"}};
+    const struct { const void *p; size_t bytes; const char *name; } ins[6] = {
+        {a.rois, q * (size_t)a.roi_features * esz, "d_rois"}, {a.overlap, q * esz, "d_overlap"}, {a.assignment, q * 4, "d_assignment"},
+        {a.gt_boxes, g * (size_t)a.gt_features * esz, "d_gt_boxes"}, {a.step, 8, "d_step"}, {a.pose_in, q * 16, "d_pose"}};
+    for (int i = 0; i < 11; ++i) {
+        const auto &o = outs[i];
+        for (int j = 0; j < 6; ++j)
+            if (sg_ranges_meet(o.p, o.bytes, ins[j].p, ins[j].bytes))
+                return sg_refuse(who, (std::string(": ") + o.name + " overlaps " + ins[j].name + "; the rois, overlaps, assignments, gt boxes, step and pose are read while the targets are written: pass a buffer apart from them").c_str(), msg);
+        for (int j = 0; j < i; ++j)
+            if (sg_ranges_meet(o.p, o.bytes, outs[j].p, outs[j].bytes))
+                return sg_refuse(who, (std::string(": ") + o.name + " overlaps " + outs[j].name + "; every output needs memory of its own").c_str(), msg);
+    }
+    return 0;
+}
+
 // 0, or SG_ARGS_INVALID with *msg (built on this path only).  The order is part of the ABI: it decides which message a doubly wrong call gets.
 static inline int sg_check_device_args(const SgDeviceArgs &a, const SgCtxView &c, const SgEntryShape &s, std::string *msg)
 {

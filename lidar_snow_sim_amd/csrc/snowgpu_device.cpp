@@ -1,5 +1,5 @@
 // snowgpu_device.cpp -- the entries of the C ABI (include/snowgpu.h) that take DEVICE pointers and enqueue on the caller's stream: every
-// *_batch_device* entry, the plane estimate, the FOV mask, the outlier filter, the voxel stage, the keypoint stage and its sectorized form, the ball query, the range image, the nearest centres, the points in boxes, the RoI point pooling, the RoI-aware voxel pooling, the box IoU and NMS and the weather draw.  Each batch entry fills an SgDeviceArgs, has it checked
+// *_batch_device* entry, the plane estimate, the FOV mask, the outlier filter, the voxel stage, the keypoint stage and its sectorized form, the ball query, the range image, the nearest centres, the points in boxes, the RoI point pooling, the RoI-aware voxel pooling, the box IoU and NMS, the proposal target sampling and the weather draw.  Each batch entry fills an SgDeviceArgs, has it checked
 // (sg_device_args.h: every refusal, in one order), sets the device and runs batch_from_args() and the stages it needs.  The launch
 // sequence of a batch is snowgpu_batch.cpp; no host copy, no synchronisation, no allocation after the first call of a given size.
 #include "sg_host.h"
@@ -16,6 +16,7 @@
 #include "sg_roiaware.h"    // the limits of the RoI-aware voxel pooling and the sizes of its lists
 #include "sg_iou.h"         // the record of the IoU and NMS stages and the size of their scratch
 #include "sg_range.h"       // the geometry of the range image and the limits in the rows' dtype
+#include "sg_targets.h"     // SgTargetCfg of the proposal target sampling
 
 static_assert(SG_ARGS_INVALID == SNOWGPU_E_INVALID && SG_PLANE_REFERENCE == 0, "sg_device_args.h restates these two");
 
@@ -724,6 +725,34 @@ extern "C" int snowgpu_nms_device(snowgpu_ctx *ctx, int n_frames, int n_boxes, c
                           ctx->nms_order.p, ctx->nms_cand.p, d_out_index, d_out_count, d_out_boxes, d_out_scores, d_out_kept,
                           stream ? (hipStream_t)stream : ctx->stream);
     if (e) return fail(ctx, SNOWGPU_E_HIP, std::string("NMS launch: ") + hipGetErrorString((hipError_t)e));
+    return SNOWGPU_OK;
+}
+
+// Proposal target sampling (snowgpu_targets.hip; the classes, the draws and what a slot stores: sg_targets.h).  See include/snowgpu.h.
+extern "C" int snowgpu_sample_rois_device(snowgpu_ctx *ctx, int n_frames, int n_rois, const void *d_rois, int roi_features, const void *d_overlap,
+                                          const int32_t *d_assignment, int n_gt, const void *d_gt_boxes, int gt_features, int dtype,
+                                          const snowgpu_roi_sampler *cfg, uint64_t seed, const uint64_t *d_step, const double *d_pose, int32_t *d_out_index,
+                                          void *d_out_rois, void *d_out_roi_iou, int32_t *d_out_gt_index, void *d_out_gt_of_rois, uint8_t *d_out_reg_valid,
+                                          void *d_out_cls_label, int32_t *d_out_segments, int32_t *d_out_class_count, double *d_out_pose,
+                                          void *d_out_gt_local, void *stream)
+{
+    if (!ctx) return SNOWGPU_E_INVALID;
+    SgSamplerCfg c{};
+    if (cfg) c = SgSamplerCfg{cfg->roi_per_image, cfg->fg_per_image, cfg->reg_fg_thresh, cfg->cls_fg_thresh, cfg->cls_bg_thresh, cfg->cls_bg_thresh_lo,
+                              cfg->hard_bg_ratio, cfg->cls_mode};
+    const SgTargetsArgs a{n_frames, n_rois, d_rois, roi_features, d_overlap, d_assignment, n_gt, d_gt_boxes, gt_features, dtype, cfg ? &c : nullptr, d_step, d_pose,
+                          d_out_index, d_out_rois, d_out_roi_iou, d_out_gt_index, d_out_gt_of_rois, d_out_reg_valid, d_out_cls_label, d_out_segments,
+                          d_out_class_count, d_out_pose, d_out_gt_local};
+    {
+        std::string msg;
+        if (int rc = sg_check_targets_args(a, &msg)) return fail(ctx, rc, msg);
+    }
+    const SgTargetCfg k{c.roi_per_image, c.fg_per_image, c.reg_fg_thresh, c.cls_fg_thresh, c.cls_bg_thresh, c.cls_bg_thresh_lo, c.hard_bg_ratio, c.cls_mode};
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    int e = sg_launch_sample_rois(&k, n_frames, n_rois, d_rois, roi_features, d_overlap, d_assignment, n_gt, d_gt_boxes, gt_features, dtype, seed, d_step, d_pose,
+                                  d_out_index, d_out_rois, d_out_roi_iou, d_out_gt_index, d_out_gt_of_rois, d_out_reg_valid, d_out_cls_label, d_out_segments,
+                                  d_out_class_count, d_out_pose, d_out_gt_local, stream ? (hipStream_t)stream : ctx->stream);
+    if (e) return fail(ctx, SNOWGPU_E_HIP, std::string("target sampling launch: ") + hipGetErrorString((hipError_t)e));
     return SNOWGPU_OK;
 }
 

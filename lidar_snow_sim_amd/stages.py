@@ -1,6 +1,6 @@
 """The device stages of the torch-tensor boundary (tensors.py is the documented import path and lists what each is for) and the batches
 of static shape they leave behind: fov_keep, dror_keep, voxelize, sample_keypoints, ball_query, range_image, nearest_keypoints,
-points_in_boxes, boxes_iou, nms, roi_point_pool, roi_voxel_pool.  Every stage goes through the same steps, in this order -- it is the order in which a call that is wrong
+points_in_boxes, boxes_iou, nms, roi_point_pool, roi_voxel_pool, sample_rois.  Every stage goes through the same steps, in this order -- it is the order in which a call that is wrong
 in two ways is refused: the aligned unwrap and the device-input refusal (_stage_frames), the scalar and range checks (_whole, _range6),
 the batch and its keep mask (_stage_batch), the stage's own tensors, the checks of the shapes' domain, out= (_checked_out), the launch
 (_stage_launch).  PyTorch is plumbing here; the work is the C entries'."""
@@ -1083,3 +1083,132 @@ def roi_voxel_pool(frames, rois, out_size=12, max_points=127, features=None, ext
     same = (index is None) == (out.index is None) and (mx is None) == (out.max is None) and (av is None) == (out.avg is None) and out.out_size == grid \
         and out.max_points == T
     return out if same else RoiVoxelBatch(out.roi_count, out.count, index, mx, am, av, out.pose, grid, T)
+
+
+class RoiTargetBatch:
+    """What sample_rois() leaves behind, F = frames, S = roi_per_image -- every shape static, an empty slot (a frame without a candidate)
+    holds -1 / 0: `index` (F, S int32: the sampled roi's number), `rois` (F, S, Cb in the boxes' dtype: bit copies of the sampled rois, zero
+    rows in empty slots -- a rois tensor for roi_point_pool, roi_voxel_pool, points_in_boxes and boxes_iou as it stands), `roi_iou` (F, S:
+    the roi's overlap), `gt_index` (F, S int32: its gt, -1 for none), `gt_of_rois` (F, S, Cg: that gt box, a zero row for none), `reg_valid`
+    (F, S uint8: overlap > reg_fg_thresh), `cls_label` (F, S: the classification target, -1 in an empty slot), `segments` (F, 3 int32: the
+    slots of fg, hard and easy picks, in this order), `class_count` (F, 3 int32: the candidates of each class), `pose` (F, S, 2 float64: the
+    (cos, sin) used for the pick; None unless asked for) and `gt_local` (F, S, 7: the gt in its roi's frame, [lx, ly, lz, dx, dy, dz,
+    heading label]; None unless asked for).  gather() is pure indexing, no kernel of this library.  All still being written until the
+    stream the call was made on has caught up."""
+
+    def __init__(self, index, rois, roi_iou, gt_index, gt_of_rois, reg_valid, cls_label, segments, class_count, pose=None, gt_local=None):
+        self.index, self.rois, self.roi_iou, self.gt_index, self.gt_of_rois = index, rois, roi_iou, gt_index, gt_of_rois
+        self.reg_valid, self.cls_label, self.segments, self.class_count, self.pose, self.gt_local = reg_valid, cls_label, segments, class_count, pose, gt_local
+
+    @classmethod
+    def empty(cls, n_frames, roi_per_image=128, roi_features=7, gt_features=8, dtype=None, device=None, with_pose=False, with_local=False):
+        """Uninitialised buffers of the shapes sample_rois() writes (out=): static addresses for a captured graph."""
+        import torch
+        dev = _cuda_device(torch, device)
+        F, S, Cb, Cg, dt = int(n_frames), int(roi_per_image), int(roi_features), int(gt_features), dtype or torch.float32
+
+        def new(shape, kind):
+            return torch.empty(shape, dtype=kind, device=dev)
+        return cls(new((F, S), torch.int32), new((F, S, Cb), dt), new((F, S), dt), new((F, S), torch.int32), new((F, S, Cg), dt), new((F, S), torch.uint8),
+                   new((F, S), dt), new((F, 3), torch.int32), new((F, 3), torch.int32), new((F, S, 2), torch.float64) if with_pose else None,
+                   new((F, S, 7), dt) if with_local else None)
+
+    @property
+    def valid(self):
+        """(F, S) bool: index >= 0 -- the slot holds a roi."""
+        return self.index >= 0
+
+    def gather(self, per_roi, fill=0):
+        """Per-roi values (F, M) or (F, M, D) -- roi_scores, roi_labels -- as (F, S) or (F, S, D): the value of the sampled roi, `fill` in
+        empty slots."""
+        import torch
+        if not (torch.is_tensor(per_roi) and per_roi.dim() in (2, 3) and per_roi.shape[0] == self.index.shape[0] and per_roi.device == self.index.device):
+            raise ValueError("gather: per_roi must be an (F, M) or (F, M, D) tensor on the device of the rois: one value, or D of them, per roi")
+        at = self.index.long()
+        has = at >= 0
+        at = at.clamp(min=0)
+        got = torch.gather(per_roi, 1, at if per_roi.dim() == 2 else at[..., None].expand(-1, -1, per_roi.shape[2]))
+        return torch.where(has if got.dim() == 2 else has[..., None], got, torch.full_like(got, fill))
+
+
+def sample_rois(rois, gt_boxes, overlaps, *, step, seed=0, roi_per_image=128, fg_ratio=0.5, reg_fg_thresh=0.55, cls_fg_thresh=0.75, cls_bg_thresh=0.25,
+                cls_bg_thresh_lo=0.1, hard_bg_ratio=0.8, cls_score_type='roi_iou', pose=None, out=None, return_local=False, return_pose=False, slot=0):
+    """Which roi_per_image rois of every frame the second stage trains on, and their targets, on the device (snowgpu_sample_rois_device; the
+    definition: include/snowgpu.h): the sampling of pcdet's ProposalTargetLayer with static shapes, nothing read on the host and a seeded
+    draw -- foreground rois without replacement, hard and easy background with replacement.  The definition is this library's, modelled on
+    pcdet's layer; parity with pcdet's random stream is distributional.  Rois that are absent (zero rows) or whose overlap is NaN are never
+    sampled.
+
+    rois       a contiguous (F, M, 7 .. 10) float32 or float64 CUDA tensor, 1 <= M <= 9216 -- or an NmsBatch, whose `boxes` are used.
+    gt_boxes   (F, B, 7 .. 10) likewise, same dtype and device, 1 <= B <= 9216.
+    overlaps   the IouBatch of boxes_iou(rois, gt_boxes, return_best=True), whose best / best_iou are used, or a pair (max_overlaps,
+               gt_assignment): contiguous (F, M) tensors in the boxes' dtype and in int32.
+    step       a one-element int64 tensor on the device of the boxes (WeatherPlan.step as it stands): read by the kernel, so a captured
+               graph that also holds `step += 1` draws anew on every replay.
+    seed       the key of the draw; the picks of frame f depend on (seed, step, f) and the frame's own data.
+    roi_per_image   1 .. 1024: S.    fg_ratio   fg_per_image = int(np.round(fg_ratio * roi_per_image)), in 0 .. S.
+    reg_fg_thresh, cls_fg_thresh, cls_bg_thresh, cls_bg_thresh_lo, hard_bg_ratio   pcdet's TARGET_CONFIG values of the same names.
+    cls_score_type  'roi_iou' or 'cls'.
+    pose       None: cos / sin of the heading in float64 on the device; or a contiguous (F, M, 2) float64 tensor (cos, sin) used as it is.
+    out        a RoiTargetBatch to write into (RoiTargetBatch.empty): every element is written, nothing needs clearing.
+
+    Returns a RoiTargetBatch.  Asynchronous on torch's current stream; nothing is read on the host: capturable after one warm-up call."""
+    import torch
+    from . import _native
+    from . import engine as _engine
+    who = "sample_rois"
+    _whole(who, roi_per_image=roi_per_image)
+    values = [float(v) for v in (fg_ratio, reg_fg_thresh, cls_fg_thresh, cls_bg_thresh, cls_bg_thresh_lo, hard_bg_ratio)]
+    if not all(math.isfinite(v) for v in values):
+        raise ValueError(f"{who}: fg_ratio, the thresholds and hard_bg_ratio must be finite")
+    if cls_score_type not in _native.CLS_SCORE_TYPES:
+        raise ValueError(f"{who}: cls_score_type must be 'roi_iou' or 'cls'")
+    if isinstance(rois, NmsBatch):
+        if rois.boxes is None:
+            raise ValueError(f"{who}: this NmsBatch has no boxes (nms(..., return_boxes=True))")
+        rois = rois.boxes
+    F, M, Cb = _box_set(torch, who, "rois", rois, 9216)
+    _, B, Cg = _box_set(torch, who, "gt_boxes", gt_boxes, 9216, rois)
+    dev, dt = rois.device, rois.dtype
+    if isinstance(overlaps, IouBatch):
+        if overlaps.best is None or overlaps.best_iou is None:
+            raise ValueError(f"{who}: this IouBatch has no best partner (boxes_iou(..., return_best=True))")
+        overlaps = (overlaps.best_iou, overlaps.best)
+    if not (isinstance(overlaps, (tuple, list)) and len(overlaps) == 2):
+        raise ValueError(f"{who}: overlaps must be an IouBatch or a pair (max_overlaps, gt_assignment)")
+    ov, assign = overlaps
+    if not (torch.is_tensor(ov) and tuple(ov.shape) == (F, M) and ov.dtype == dt and ov.device == dev and ov.is_contiguous()):
+        raise ValueError(f"{who}: max_overlaps must be a contiguous {(F, M)} tensor in the boxes' dtype on their device")
+    if not (torch.is_tensor(assign) and tuple(assign.shape) == (F, M) and assign.dtype == torch.int32 and assign.device == dev and assign.is_contiguous()):
+        raise ValueError(f"{who}: gt_assignment must be a contiguous {(F, M)} int32 tensor on the device of the boxes")
+    if not (torch.is_tensor(step) and step.numel() == 1 and step.dtype == torch.int64 and step.device == dev):
+        raise ValueError(f"{who}: step must be a one-element int64 tensor on the device of the boxes")
+    S = int(roi_per_image)
+    # (the shapes below need these; the entry refuses them in the same words, and everything else of the domain)
+    if not 1 <= S <= 1024:
+        raise ValueError(f"{who}: roi_per_image must lie in 1 .. 1024")
+    fg_per_image = int(np.round(values[0] * S))
+    if not 0 <= fg_per_image <= S:
+        raise ValueError(f"{who}: fg_per_image must lie in 0 .. roi_per_image (fg_ratio in 0 .. 1)")
+    if F * S * max(Cb, Cg) > 2 ** 31 - 1:
+        raise ValueError(f"{who}: n_frames * roi_per_image * max(roi_features, gt_features) exceeds 2^31 - 1; split the batch")
+    pp = _box_pose(torch, who, "pose", pose, rois)
+    want = (("index", torch.int32, (F, S), True), ("rois", dt, (F, S, Cb), True), ("roi_iou", dt, (F, S), True), ("gt_index", torch.int32, (F, S), True),
+            ("gt_of_rois", dt, (F, S, Cg), True), ("reg_valid", torch.uint8, (F, S), True), ("cls_label", dt, (F, S), True),
+            ("segments", torch.int32, (F, 3), True), ("class_count", torch.int32, (F, 3), True), ("pose", torch.float64, (F, S, 2), return_pose),
+            ("gt_local", dt, (F, S, 7), return_local))
+    if out is None:
+        out = RoiTargetBatch.empty(F, S, Cb, Cg, dt, dev, return_pose, return_local)
+    else:
+        _checked_out(torch, who, RoiTargetBatch, out, want, dev)
+    used, local = (out.pose if return_pose else None), (out.gt_local if return_local else None)
+    cfg = _native.roi_sampler_struct(S, fg_per_image, *values[1:], _native.CLS_SCORE_TYPES[cls_score_type])
+    eng = _engine.get_engine(dev.index, slot)
+    with torch.cuda.device(dev), _on_run_stream(torch, eng, dev) as (_, run):
+        eng.ctx.sample_rois_device(F, M, rois.data_ptr(), Cb, ov.data_ptr(), assign.data_ptr(), B, gt_boxes.data_ptr(), Cg, 0 if dt == torch.float32 else 1,
+                                   cfg, seed, step.data_ptr(), pp, out.index.data_ptr(), out.rois.data_ptr(), out.roi_iou.data_ptr(), out.gt_index.data_ptr(),
+                                   out.gt_of_rois.data_ptr(), out.reg_valid.data_ptr(), out.cls_label.data_ptr(), out.segments.data_ptr(),
+                                   out.class_count.data_ptr(), 0 if used is None else used.data_ptr(), 0 if local is None else local.data_ptr(), run.cuda_stream)
+    same = (used is None) == (out.pose is None) and (local is None) == (out.gt_local is None)
+    return out if same else RoiTargetBatch(out.index, out.rois, out.roi_iou, out.gt_index, out.gt_of_rois, out.reg_valid, out.cls_label, out.segments,
+                                           out.class_count, used, local)

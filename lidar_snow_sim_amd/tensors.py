@@ -44,6 +44,10 @@ The reference's training-time caller (the OpenPCDet DENSE dataset: `root_path`, 
   * `roi_voxel_pool(frames_or_result, rois, out_size, max_points, features)` cuts every slightly enlarged roi into out_size sub-voxels
     and max- / average-pools the features of the rows inside each, members in row order (RoiVoxelBatch; snowgpu_roi_voxel_pool_device):
     pcdet's roiaware_pool3d, the input of a Part-A2-style second stage; `max_features` / `avg_features` are the differentiable gathers.
+  * `sample_rois(rois, gt_boxes, overlaps, step=...)` draws the roi_per_image rois of every frame that the second stage trains on --
+    foreground without replacement, hard and easy background with replacement, seeded by (seed, step, frame) -- and their targets
+    (RoiTargetBatch; snowgpu_sample_rois_device): the sampling of pcdet's ProposalTargetLayer between `boxes_iou(return_best=True)` and
+    the two pooling stages, which take its `rois` as they stand.
   * `augment_wet_batch_aligned(frames, ...)` is the snowfall + wet-ground chain with that aligned result (AlignedWetResult: per-frame
     flags beside it; snowgpu_augment_wet_batch_device_aligned), `wet_ground_batch_aligned(frames, keep)` the wet-ground stage alone on rows
     and a keep mask from any earlier stage (snowgpu_wet_ground_batch_device_aligned).
@@ -53,7 +57,7 @@ training loop that reshuffles `order` per frame uploads 64 int32 per frame).  Py
 no arithmetic of the simulation happens in this file.
 
 This module is the import path of all of it and holds the augmentation entries.  How a batch is read and a result handed back lives in
-batch.py, the stages from `fov_keep` to `roi_voxel_pool` with their result classes in stages.py; every public name of both is re-exported here.
+batch.py, the stages from `fov_keep` to `sample_rois` with their result classes in stages.py; every public name of both is re-exported here.
 """
 from __future__ import annotations
 
@@ -66,9 +70,9 @@ import numpy as np
 from . import _native
 from .batch import (LANE_SLOT0, AlignedResult, AlignedWetResult, DeviceBatch, DeviceResult, _cuda_device, _keep_mask, _on_run_stream,  # noqa: F401
                     _resolve_input, _uploads, is_device_input)
-from .stages import (IOU_MODES, BoxLabelBatch, IouBatch, KeypointBatch, NearestBatch, NeighbourBatch, NmsBatch, RangeImageBatch, RoiPointBatch, RoiVoxelBatch, VoxelBatch,  # noqa: F401
+from .stages import (IOU_MODES, BoxLabelBatch, IouBatch, KeypointBatch, NearestBatch, NeighbourBatch, NmsBatch, RangeImageBatch, RoiPointBatch, RoiTargetBatch, RoiVoxelBatch, VoxelBatch,  # noqa: F401
                      _fov_mask, ball_query, boxes_iou, dror_keep, fov_keep, nearest_keypoints, nms, points_in_boxes, range_image, roi_point_pool,
-                     roi_voxel_pool, sample_keypoints, voxelize)
+                     roi_voxel_pool, sample_keypoints, sample_rois, voxelize)
 
 
 @contextmanager

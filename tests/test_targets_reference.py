@@ -1,0 +1,367 @@
+"""Proposal target sampling without a GPU: the conditions under which the comparisons of tests/test_gpu_targets.py are not vacuous,
+asserted on the shared cases of tests/targets_reference.py; csrc/sg_targets.h compiled for the host (tests/host_harness/targets_walk.cpp)
+against the restatement, byte for byte; what snowgpu_sample_rois_device refuses, in which words and in which order
+(tests/host_harness/targets_refusals.cpp); and that the entry is declared and bound."""
+import shutil
+import subprocess
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+import box_reference as br
+import targets_reference as tr
+from conftest import ROOT
+from lidar_snow_sim_amd.stages import RoiTargetBatch, sample_rois  # noqa: F401  (the stage all of this is about: without it nothing here runs)
+
+DTYPES = tr.DTYPES
+HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+
+
+# ---- the restatement itself -------------------------------------------------------------------------------------------------------------------
+def test_the_restatement_on_a_case_by_hand():
+    """Two fg rois, one hard, one easy, one absent, one NaN; S = 4, fg_per_image = 1: one fg pick, then hard_this = min((int)(3 x 0.8), 1) = 1
+    and two easy picks of the only easy roi."""
+    rois = np.array([[[0, 0, 0, 4, 2, 2, 0.5], [1, 1, 0, 4, 2, 2, 0.0], [2, 0, 0, 4, 2, 2, 0.0], [0, 0, 0, 0, 0, 0, 0], [3, 0, 0, 4, 2, 2, 0.0],
+                      [5, 0, 0, 4, 2, 2, 0.0]]], np.float64)
+    gt = np.array([[[1, 0, 0.5, 4, 2, 2, 0.5 + np.pi, 1], [0, 0, 0, 4, 2, 2, 0.0, 2]]], np.float64)
+    ov = np.array([[0.9, 0.6, 0.3, 0.95, 0.05, np.nan]])
+    assign = np.array([[0, 1, 1, 0, -1, 0]], np.int32)
+    cfg = tr.settings(roi_per_image=4, fg_ratio=0.25)
+    e = tr.sample_rois(rois, gt, ov, assign, br.numpy_pose(rois), cfg, 1, 0)
+    assert e["class_count"].tolist() == [[2, 1, 1]] and e["segments"].tolist() == [[1, 1, 2]] and e["branch"] == ["a"]
+    assert e["index"][0, 0] in (0, 1) and e["index"][0, 1:].tolist() == [2, 4, 4]
+    assert e["gt_index"][0, 1:].tolist() == [1, -1, -1] and not e["gt_of_rois"][0, 2:].any() and not e["gt_local"][0, 2:].any()
+    assert e["reg_valid"][0, 1:].tolist() == [0, 0, 0] and e["reg_valid"][0, 0] == 1
+    assert np.allclose(e["cls_label"][0, 1:], [(0.3 - 0.25) / 0.5, 0, 0]) and e["roi_iou"][0, 1:].tolist() == [0.3, 0.05, 0.05]
+    assert e["rois"][0, 1].tolist() == rois[0, 2].tolist() and e["gt_of_rois"][0, 1].tolist() == gt[0, 1].tolist()
+    assert np.allclose(e["gt_local"][0, 1], [-2, 0, 0, 4, 2, 2, 0])
+    # roi 0 (heading 0.5) against gt 0 (heading 0.5 + pi, one metre ahead in x): the flipped heading gives a label of 0
+    l0 = tr.gt_local(rois[0, 0], np.cos(0.5), np.sin(0.5), gt[0, 0], np.float64)
+    assert np.allclose(l0, [np.cos(0.5), -np.sin(0.5), 0.5, 4, 2, 2, 0.0], atol=1e-15)
+
+
+def test_words_are_the_weather_draws_positions():
+    """r_k is word k % 4 of block (step, frame, tag + k / 4): step in the index, the frame in the group."""
+    from seeded_reference import philox4x32_10
+    w = tr.words(7, (1 << 40) + 3, 5, 9)
+    assert w[:4] == philox4x32_10(7, (1 << 40) + 3, 5, 0x524F4953) and w[8] == philox4x32_10(7, (1 << 40) + 3, 5, 0x524F4953 + 2)[0] and len(w) == 9
+
+
+def test_pmod_is_numpys_mod():
+    rng = np.random.default_rng(3)
+    for x in list(rng.uniform(-1e6, 1e6, 2000)) + [0.0, -0.0, tr.TWO_PI, -tr.TWO_PI, 1e-300, -1e-300, -1e-20]:
+        got, want = tr.pmod(float(x)), float(np.mod(np.float64(x), tr.TWO_PI))
+        assert got == want and not np.signbit(got), x
+
+
+# ---- the shared cases meet the conditions -----------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_branches(dtype):
+    c, e = tr.case("branches", dtype), tr.expected("branches", dtype)
+    fr, cfg = tr.BRANCH_FRAMES, c["cfg"]
+    S, fg_max = cfg["roi_per_image"], tr.fg_per_image(cfg)
+    assert e["branch"] == ["a", "a", "b", "c", "d", "c"] and (S, fg_max) == (128, 32)
+    n_fg, n_hard, n_easy = e["class_count"].T
+    assert n_fg[fr["many_fg"]] > fg_max > n_fg[fr["few_fg"]] > 0                             # n_fg on either side of fg_per_image
+    seg = e["segments"]
+    assert seg[fr["many_fg"]].tolist() == [32, int(96 * 0.4), 96 - int(96 * 0.4)] and n_hard[fr["many_fg"]] > int(96 * 0.4)      # clipped by the ratio
+    few = fr["few_fg"]
+    assert seg[few].tolist() == [n_fg[few], n_hard[few], S - n_fg[few] - n_hard[few]] and n_hard[few] < int((S - n_fg[few]) * 0.4)   # ... by n_hard
+    assert seg[fr["fg_only"]].tolist() == [S, 0, 0] and seg[fr["hard_only"]].tolist() == [0, S, 0] and seg[fr["easy_only"]].tolist() == [0, 0, S]
+    assert n_easy[fr["hard_only"]] == 0 and n_hard[fr["easy_only"]] == 0 and n_fg[fr["hard_only"]] == 0
+    assert seg[fr["nothing"]].tolist() == [0, 0, 0] and not e["class_count"][fr["nothing"]].any()
+    assert (e["index"][fr["nothing"]] == -1).all() and (e["cls_label"][fr["nothing"]] == -1).all() and not e["rois"][fr["nothing"]].any()
+    assert (e["index"][[f for f in range(6) if f != fr["nothing"]]] >= 0).all()
+    # what is no candidate is never picked: NaN overlaps, absent rois -- all of which would have been foreground
+    many = fr["many_fg"]
+    assert np.isnan(c["overlap"][many, [1, 4]]).all() and not br.present(c["rois"], c["pose"])[many, [7, 10]].any() and (c["overlap"][many, [7, 10]] > 0.55).all()
+    assert not set(e["index"][many].tolist()) & {1, 4, 7, 10} and not br.present(c["rois"], c["pose"])[few, 15]
+    # assignments of -1 and of B are -1; one of them is among the picks of this seed
+    assert c["assignment"][many, 13] == -1 and c["assignment"][many, 16] == 65 and c["gt_boxes"].shape[1] == 65
+    picked = {int(m): int(g) for m, g in zip(e["index"][many], e["gt_index"][many])}
+    assert any(picked.get(m) == -1 for m in (13, 16))
+    # the picks without replacement are pairwise distinct, those with replacement are not
+    for f in (many, few):
+        head = e["index"][f, :seg[f, 0]]
+        assert len(set(head.tolist())) == len(head)
+    assert len(set(e["index"][fr["fg_only"]].tolist())) < S
+    # slots are fg, then hard, then easy
+    fg, hard, easy = (set(x) for x in tr.class_lists(cfg, c["rois"][many], c["overlap"][many], c["pose"][many]))
+    a, b = seg[many, 0], seg[many, 0] + seg[many, 1]
+    assert set(e["index"][many, :a].tolist()) <= fg and set(e["index"][many, a:b].tolist()) <= hard and set(e["index"][many, b:].tolist()) <= easy
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_overlaps_on_the_thresholds(dtype):
+    c = tr.case("edges", dtype)
+    cfg, t = c["cfg"], np.dtype(dtype).type
+    values = tr.edge_overlaps(dtype).astype(np.float64)
+    for name in ("reg_fg_thresh", "cls_fg_thresh", "cls_bg_thresh", "cls_bg_thresh_lo"):
+        v = cfg[name]
+        assert float(t(v)) == v and v in tr.EDGE_VALUES and {v, float(np.nextafter(t(v), t(0))), float(np.nextafter(t(v), t(1)))} <= set(values.tolist())
+    n = len(values)
+    assert np.array_equal(c["overlap"][0, :n][values >= 0.125], values[values >= 0.125].astype(dtype))
+    assert np.array_equal(c["overlap"][1, :n][(values < 0.125) | (values >= 0.5)], values[(values < 0.125) | (values >= 0.5)].astype(dtype))
+    fg, hard, easy = tr.class_lists(cfg, c["rois"][0], c["overlap"][0], c["pose"][0])
+    at = {float(v): m for m, v in enumerate(c["overlap"][0, :n].astype(np.float64))}
+    assert at[0.5] in fg and at[0.5] not in hard and at[0.125] in hard and not easy                         # the boundaries are closed upwards
+    assert not tr.class_lists(cfg, c["rois"][1], c["overlap"][1], c["pose"][1])[1]
+    above, below = (lambda v: float(np.nextafter(t(v), t(1)))), (lambda v: float(np.nextafter(t(v), t(0))))
+    for kind in ("roi_iou", "cls"):
+        e = tr.expected_of(c, cfg={**cfg, "cls_score_type": kind})
+        assert e["branch"] == ["a", "a"] and e["segments"][0, 2] == 0 and e["segments"][1, 1] == 0
+        seen = {float(o): (float(l), int(v)) for o, l, v in zip(e["roi_iou"].reshape(-1), e["cls_label"].reshape(-1), e["reg_valid"].reshape(-1))}
+        assert set(values.tolist()) <= set(seen)                                                          # every value was picked in one of the frames
+        soft = kind == "roi_iou"
+        assert seen[0.5] == (0.5 if soft else -1.0, 0) and seen[above(0.5)][1] == 1 and seen[below(0.5)][1] == 0
+        assert seen[0.75][0] == (1.0 if soft else 0.0) and seen[above(0.75)][0] == 1.0 and seen[below(0.75)][0] == (pytest.approx(1.0, abs=1e-6) if soft else -1.0)
+        assert seen[0.25][0] == 0.0 and seen[below(0.25)][0] == 0.0 and seen[above(0.25)][0] == (pytest.approx(0.0, abs=1e-6) if soft else -1.0)
+        assert 0.0 < seen[above(0.25)][0] if soft else True
+        assert seen[0.125][0] == 0.0 and seen[float("inf")] == (1.0, 1) and seen[float("-inf")] == (0.0, 0)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_fg_meets_hard(dtype):
+    """reg_fg_thresh > cls_fg_thresh: rois with 0.5 <= overlap < 0.75 are foreground and hard background."""
+    c, e = tr.case("m129", dtype), tr.expected("m129", dtype)
+    assert c["cfg"]["reg_fg_thresh"] > c["cfg"]["cls_fg_thresh"]
+    for f in range(c["rois"].shape[0]):
+        fg, hard, easy = (set(x) for x in tr.class_lists(c["cfg"], c["rois"][f], c["overlap"][f], c["pose"][f]))
+        assert len(fg & hard) >= 10 and not hard & easy and not fg & easy
+    assert e["branch"] == ["a", "a"]
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_heading_rule_from_either_side(dtype):
+    c, e = tr.case("headings", dtype), tr.expected("headings", dtype)
+    seen, zeros = set(), 0
+    picked = sorted(set(e["index"][0].tolist()))
+    assert picked == list(range(64))                                                          # every roi is in some slot
+    for m in picked:
+        trace = []
+        g = c["gt_boxes"][0, m]
+        if np.isfinite(g[:7].astype(np.float64)).all() and (np.abs(g[:7].astype(np.float64)) <= 1e6).all():
+            tr.heading_label(float(c["rois"][0, m, 6]), float(g[6]), trace)
+            seen.update(trace)
+    assert {"flipped", "kept", "wrapped", "unwrapped"} <= seen
+    for m in (59, 60, 61, 62):                                                                 # no gt, or a gt beyond the bounds: zeros
+        slots = np.flatnonzero(e["index"][0] == m)
+        assert len(slots) and not e["gt_local"][0, slots].any()
+        zeros += len(slots)
+    slots = np.flatnonzero(e["index"][0] == 63)
+    assert (e["gt_local"][0, slots, 3] == -1).all() and e["gt_local"][0, slots].any()          # a negative size is copied, not judged
+    assert (np.abs(e["gt_local"][0, :, 6].astype(np.float64)) <= tr.HALF_PI + 1e-6).all()
+    assert tr.pmod(-1e-20) == tr.TWO_PI and str(tr.pmod(0.0 - tr.TWO_PI)) == "0.0"              # the sum that rounds to 2 pi, and the +0
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_full_walk(dtype):
+    c, e = tr.case("full_walk", dtype), tr.expected("full_walk", dtype)
+    assert c["rois"].shape[:2] == (2, 9216) and e["branch"] == ["a", "a"]
+    for f in range(2):
+        assert e["class_count"][f, 0] > 1024 and e["class_count"][f, 1:].sum() > 0 and e["segments"][f].tolist() == [1024, 0, 0]
+        assert len(set(e["index"][f].tolist())) == 1024 and e["index"][f].max() > 9000
+    assert e["index"][0].tolist() != e["index"][1].tolist()
+
+
+@pytest.mark.parametrize("name", tr.RANDOM_NAMES)
+def test_random_cases_pick_something(name):
+    c, e = tr.case(name, "float32"), tr.expected(name, "float32")
+    F, M = c["rois"].shape[:2]
+    assert e["index"].shape == (F, c["cfg"]["roi_per_image"]) and e["index"].max() < M
+    if name == "m2":
+        assert tr.fg_per_image(c["cfg"]) == 0 and (e["segments"][:, 0] == 0)[[b == "a" for b in e["branch"]]].all()
+    if name in ("m64", "m129"):
+        assert (e["index"] >= 0).all() and (e["gt_index"] == -1).any() and (e["gt_index"] >= 0).any() and e["reg_valid"].any()
+
+
+def test_step_seed_and_frame_change_the_picks():
+    c = tr.case("branches", "float32")
+    f = tr.BRANCH_FRAMES["few_fg"]
+    one = {k: v[f:f + 1] for k, v in c.items() if isinstance(v, np.ndarray)}
+    base = dict(c, **one)
+
+    def index(**changed):
+        return tr.expected_of(base, **changed)["index"][0].tolist()
+    here = index(frames=[f])
+    assert here == tr.expected("branches", "float32")["index"][f].tolist()                   # the batch's frame f IS the one-frame call keyed f
+    assert index() != here and index(frames=[f + 1]) != here                                   # ... and no other frame number
+    assert index(frames=[f], step=c["step"] + 1) != here and index(frames=[f], seed=c["seed"] + 1) != here
+    assert index(frames=[f], step=c["step"] + (1 << 32)) != here                               # the high half of the step is in the counter
+
+
+def test_picks_are_uniform_over_the_steps():
+    """2 000 steps of a fixed seed, 7 fg rois, 3 fg picks without replacement each: every roi is picked 3 / 7 of the time within 4 sigma;
+    the first pick alone and a pick with replacement likewise 1 / 7."""
+    cfg = tr.settings(roi_per_image=8, fg_ratio=3 / 8)
+    fg, hard = [3, 5, 8, 13, 21, 34, 55], [1, 2]
+    steps = 2000
+    count, first, with_rep = {m: 0 for m in fg}, {m: 0 for m in fg}, {m: 0 for m in fg}
+    for step in range(steps):
+        r = tr.words(99, step, 2, 8)
+        slots, seg, branch = tr.picks(cfg, fg, hard, [], r)
+        assert seg == (3, 5, 0) and branch == "a"
+        for m in slots[:3]:
+            count[m] += 1
+        first[slots[0]] += 1
+        with_rep[tr.picks(cfg, fg, [], [], r)[0][7]] += 1
+    for tally, p in ((count, 3 / 7), (first, 1 / 7), (with_rep, 1 / 7)):
+        sigma = (steps * p * (1 - p)) ** 0.5
+        assert sum(tally.values()) == round(steps * p * 7) and all(abs(n - steps * p) <= 4 * sigma for n in tally.values()), tally
+
+
+# ---- csrc/sg_targets.h on the host --------------------------------------------------------------------------------------------------------------
+def _compile(tmp, name, extra=()):
+    if not Path(HIPCC).exists():
+        pytest.skip("hipcc not available")
+    exe = tmp / name
+    cmd = [HIPCC, "--cuda-host-only", "-x", "hip", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-w", *extra, "-I", str(ROOT / "lidar_snow_sim_amd" / "csrc"),
+           "-I", str(ROOT / "include"), str(ROOT / "tests" / "host_harness" / "targets_walk.cpp"), "-o", str(exe), "-lm"]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    return exe
+
+
+@pytest.fixture(scope="module")
+def walk(tmp_path_factory):
+    return _compile(tmp_path_factory.mktemp("targets"), "targets_walk")
+
+
+def _walk(exe, tmp_path, c):
+    """The outputs of the harness on case c, as a dict of arrays shaped like the restatement's."""
+    from lidar_snow_sim_amd._native import CLS_SCORE_TYPES
+    cfg = c["cfg"]
+    F, M, Cb = c["rois"].shape
+    B, Cg = c["gt_boxes"].shape[1:]
+    S, dt = cfg["roi_per_image"], c["rois"].dtype
+    fin, fout = tmp_path / "case.in", tmp_path / "case.out"
+    with open(fin, "wb") as fp:
+        for a in (c["rois"], c["gt_boxes"], c["overlap"], c["assignment"], c["pose"]):
+            fp.write(np.ascontiguousarray(a).tobytes())
+    args = [int(dt == np.float64), F, M, B, Cb, Cg, S, tr.fg_per_image(cfg), *(repr(float(cfg[k])) for k in
+            ("reg_fg_thresh", "cls_fg_thresh", "cls_bg_thresh", "cls_bg_thresh_lo", "hard_bg_ratio")), CLS_SCORE_TYPES[cfg["cls_score_type"]], c["seed"], c["step"]]
+    r = subprocess.run([str(exe), *(str(a) for a in args), str(fin), str(fout)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, (r.returncode, r.stderr[-2000:])
+    shapes = dict(index=((F, S), np.int32), rois=((F, S, Cb), dt), roi_iou=((F, S), dt), gt_index=((F, S), np.int32), gt_of_rois=((F, S, Cg), dt),
+                  reg_valid=((F, S), np.uint8), cls_label=((F, S), dt), segments=((F, 3), np.int32), class_count=((F, 3), np.int32),
+                  pose=((F, S, 2), np.float64), gt_local=((F, S, 7), dt))
+    blob, at, got = fout.read_bytes(), 0, {}
+    for name in tr.FIELDS:
+        shape, kind = shapes[name]
+        n = int(np.prod(shape)) * np.dtype(kind).itemsize
+        got[name] = np.frombuffer(blob[at:at + n], kind).reshape(shape)
+        at += n
+    assert at == len(blob)
+    return got
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("name", tr.CASE_NAMES)
+def test_the_header_on_the_host_equals_the_restatement(walk, tmp_path, name, dtype):
+    c, e = tr.case(name, dtype), tr.expected(name, dtype)
+    got = _walk(walk, tmp_path, c)
+    for field in tr.FIELDS:
+        assert got[field].tobytes() == e[field].tobytes(), field
+
+
+def test_the_header_under_the_other_score_type(walk, tmp_path):
+    c = tr.case("edges", "float32")
+    c = dict(c, cfg={**c["cfg"], "cls_score_type": "cls"})
+    got, e = _walk(walk, tmp_path, c), tr.expected_of(c)
+    for field in tr.FIELDS:
+        assert got[field].tobytes() == e[field].tobytes(), field
+
+
+def test_the_header_under_sanitizers(tmp_path):
+    """The same program under AddressSanitizer and UBSan -- host code only, a stand-alone program: the lists, the words and the walk stay
+    inside their arrays at M = 9216 with S = 1024 and at the branch frames."""
+    exe = _compile(tmp_path, "targets_walk_san", ("-Xarch_host", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"))
+    for name, dtype in (("full_walk", "float64"), ("branches", "float32"), ("m1", "float32")):
+        c, e = tr.case(name, dtype), tr.expected(name, dtype)
+        got = _walk(exe, tmp_path, c)
+        assert got["index"].tobytes() == e["index"].tobytes() and got["gt_local"].tobytes() == e["gt_local"].tobytes(), (name, dtype)
+
+
+# ---- the refusal walk -------------------------------------------------------------------------------------------------------------------------
+WHO = "snowgpu_sample_rois_device"
+APART = "; the rois, overlaps, assignments, gt boxes, step and pose are read while the targets are written: pass a buffer apart from them"
+OWN = "; every output needs memory of its own"
+MESSAGES = {
+    "null": WHO + ": null pointer or bad dtype",
+    "boxes": WHO + ": n_rois and n_gt must lie in 1 .. 9216",
+    "features": WHO + ": roi_features and gt_features must lie in 7 .. 10: cx, cy, cz, dx, dy, dz, heading first",
+    "slots": WHO + ": roi_per_image must lie in 1 .. 1024",
+    "fg": WHO + ": fg_per_image must lie in 0 .. roi_per_image",
+    "threshold": WHO + ": a threshold is NaN or infinite",
+    "cls": WHO + ": cls_fg_thresh must be above cls_bg_thresh",
+    "ratio": WHO + ": hard_bg_ratio must lie in 0 .. 1",
+    "mode": WHO + ": cls_mode must be 0 (roi_iou) or 1 (cls)",
+    "elements": WHO + ": n_frames * roi_per_image * max(roi_features, gt_features) exceeds 2^31 - 1; split the batch",
+}
+ORDER = tuple(MESSAGES)              # the order of the checks: a call wrong in two ways gets the earlier message
+PAIRS = {("index", "rois"): ("index_is_rois", "index_overlaps_rois"), ("rois", "overlap"): ("rois_overlaps_overlap",), ("roi_iou", "assignment"): ("roi_iou_is_assignment",),
+         ("gt_index", "gt_boxes"): ("gt_index_overlaps_gt_boxes",), ("cls_label", "step"): ("cls_label_is_step",), ("pose", "pose"): ("pose_is_pose_in",),
+         ("gt_local", "pose"): ("gt_local_overlaps_pose_in",)}
+OUTS = {("rois", "index"): ("rois_is_index",), ("roi_iou", "rois"): ("roi_iou_overlaps_rois",), ("gt_of_rois", "gt_index"): ("gt_of_rois_is_gt_index",),
+        ("reg_valid", "gt_of_rois"): ("reg_valid_overlaps_gt_of_rois",), ("cls_label", "reg_valid"): ("cls_label_is_reg_valid",),
+        ("segments", "index"): ("segments_overlaps_index",), ("class_count", "segments"): ("class_count_is_segments",),
+        ("pose", "class_count"): ("pose_overlaps_class_count",), ("gt_local", "pose"): ("gt_local_is_pose",)}
+ACCEPTED = ("clean", "null_pose_in", "null_out_pose", "null_out_gt_local", "float64", "rois_1", "rois_9216", "gt_1", "gt_9216", "roi_features_7", "roi_features_10",
+            "gt_features_7", "gt_features_10", "slots_1", "slots_1024", "fg_0", "fg_all", "thresholds_negative", "ratio_0", "ratio_1", "cls_mode_1",
+            "elements_below_2p31", "index_behind_rois", "step_behind_cls_label", "roi_iou_behind_rois", "class_count_behind_segments")
+REFUSED = {
+    "null": ("null_rois", "null_overlap", "null_assignment", "null_gt_boxes", "null_cfg", "null_step", "null_out_index", "null_out_rois", "null_out_roi_iou",
+             "null_out_gt_index", "null_out_gt_of_rois", "null_out_reg_valid", "null_out_cls_label", "null_out_segments", "null_out_class_count", "bad_dtype",
+             "no_frames"),
+    "boxes": ("rois_0", "rois_9217", "gt_0", "gt_9217", "gt_negative"),
+    "features": ("roi_features_6", "roi_features_11", "gt_features_6", "gt_features_11"),
+    "slots": ("slots_0", "slots_1025"),
+    "fg": ("fg_negative", "fg_above_slots"),
+    "threshold": ("reg_fg_nan", "cls_fg_inf", "cls_bg_minus_inf", "cls_bg_lo_nan"),
+    "cls": ("cls_fg_equals_cls_bg", "cls_fg_below_cls_bg"),
+    "ratio": ("ratio_negative", "ratio_above_1", "ratio_nan"),
+    "mode": ("cls_mode_negative", "cls_mode_2"),
+    "elements": ("elements_above_2p31", "elements_overflowing"),
+}
+
+
+def test_refusal_walk(tmp_path):
+    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    exe = tmp_path / "targets_refusals"
+    cmd = [cxx, "-x", "c++", "-std=c++17", "-O1", "-Wall", "-I", str(ROOT / "lidar_snow_sim_amd" / "csrc"),
+           str(ROOT / "tests" / "host_harness" / "targets_refusals.cpp"), "-o", str(exe)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr
+    got = dict(ln.split("|", 1) for ln in r.stdout.splitlines())
+    want = {case: "0|OK" for case in ACCEPTED}
+    for key, cases in REFUSED.items():
+        want.update({case: "1|" + MESSAGES[key] for case in cases})
+    for (out, inp), cases in PAIRS.items():
+        want.update({case: f"1|{WHO}: d_out_{out} overlaps d_{inp}{APART}" for case in cases})
+    for (out, other), cases in OUTS.items():
+        want.update({case: f"1|{WHO}: d_out_{out} overlaps d_out_{other}{OWN}" for case in cases})
+    assert got == want
+    assert set(MESSAGES) == set(REFUSED)              # every message is reached
+    # the order: the checks stand in sg_check_targets_args in the order of MESSAGES, the overlaps behind them
+    text = (ROOT / "lidar_snow_sim_amd" / "csrc" / "sg_device_args.h").read_text()
+    body = text[text.index("sg_check_targets_args("):]
+    places = [body.index('"' + MESSAGES[k][len(WHO):] + '"') for k in ORDER]
+    assert places == sorted(places) and places[-1] < body.index("every output needs memory of its own")
+
+
+def test_the_entry_is_declared_and_bound():
+    from lidar_snow_sim_amd import _native
+    header = (ROOT / "include" / "snowgpu.h").read_text()
+    assert "int snowgpu_sample_rois_device(" in header and "typedef struct snowgpu_roi_sampler {" in header and "snowgpu_sample_rois_device" in _native.EXPORTS
+    assert hasattr(_native.lib(), "snowgpu_sample_rois_device") and hasattr(_native.Context, "sample_rois_device")
+    assert "snowgpu_targets.hip" in __import__("lidar_snow_sim_amd.build", fromlist=["SOURCES"]).SOURCES
+    import ctypes
+    s = _native.roi_sampler_struct(128, 64, 0.55, 0.75, 0.25, 0.1, 0.8, 1)
+    assert ctypes.sizeof(s) == 56 and (s.roi_per_image, s.fg_per_image, s.cls_bg_thresh_lo, s.cls_mode) == (128, 64, 0.1, 1)
+    from lidar_snow_sim_amd import stages, targets, tensors
+    assert tensors.sample_rois is stages.sample_rois and tensors.RoiTargetBatch is stages.RoiTargetBatch and callable(targets.sample_rois)
+    assert callable(tensors.RoiTargetBatch.empty) and isinstance(tensors.RoiTargetBatch.valid, property) and callable(tensors.RoiTargetBatch.gather)
+    assert tuple(targets.FIELDS) == tuple(tr.FIELDS)
