@@ -1257,6 +1257,58 @@ int snowgpu_sample_rois_device(snowgpu_ctx *ctx, int n_frames, int n_rois, const
                                uint8_t *d_out_reg_valid, void *d_out_cls_label, int32_t *d_out_segments, int32_t *d_out_class_count,
                                double *d_out_pose /* or NULL */, void *d_out_gt_local /* or NULL */, void *stream);
 
+/*
+ * ANCHOR TARGET ASSIGNMENT: which anchors of a first stage are positive, background or ignored in every frame, and which gt a positive
+ * regresses to -- the step of OpenPCDet's AxisAlignedTargetAssigner (assign_targets, assign_targets_single) between the augmentation and
+ * the anchor head's loss, with static shapes and nothing read on the host.  pcdet is not part of the reference checkout: the definition
+ * below is THIS LIBRARY'S, modelled on pcdet's assigner as recalled, and was NOT CHECKED against pcdet's source.  It is restated as
+ * brute-force NumPy by tests/anchors_reference.py; csrc/sg_anchors.h holds its C++, for the device and for the host.
+ *   INPUTS, F = n_frames, A = n_anchors, B = n_gt, NC = n_classes, T = float32 or float64: d_anchors (A, Ca) T, Ca in 7 .. 10, SHARED by all
+ *   frames, columns 0 .. 6 cx, cy, cz, dx, dy, dz, heading; d_anchor_class (A) int32, the class number of each anchor; d_gt_boxes
+ *   (F, B, Cg) T, Cg in 8 .. 10, column 7 the class; matched and unmatched, NC doubles each in HOST memory, read during the call, class c at
+ *   [c - 1].
+ *   ARITHMETIC: float64 computed from (double) of the inputs, every operation rounded on its own, no fused multiply-add, no transcendental
+ *   function: NumPy gives the same bytes.
+ *   PRESENCE: an anchor is present iff the presence rule of snowgpu_points_in_boxes_device holds for its seven columns (all finite, the
+ *   1e6 bounds, 0 < dx, dy, dz <= 1e6; no pose is involved) and 1 <= anchor_class <= NC.  A gt is present iff the same rule holds and its
+ *   column 7 is integral with a value in 1 .. NC; zero rows are padding.  An absent anchor has label -1, gt_index -1 and iou 0 and takes
+ *   part in nothing; an absent gt takes part in nothing, its gt_count is 0.
+ *   NEAREST AXIS-ALIGNED BEV BOX of a box (cx, cy, ., dx, dy, ., h), PI the double nearest pi: r = |h - floor(h / PI + 0.5) PI|;
+ *   (ex, ey) = (dx, dy) if r < PI / 4 (the double 0.7853981633974483), else (dy, dx); x0 = cx - ex / 2, x1 = cx + ex / 2, y0 and y1 likewise.
+ *   OVERLAP of anchor a and gt g: ix = max(min(ax1, gx1) - max(ax0, gx0), 0), iy likewise, inter = ix iy; area = (x1 - x0) (y1 - y0);
+ *   iou = inter / max((area_a + area_g) - inter, 1e-6).
+ *   PER PRESENT ANCHOR of class c: over the frame's present gts of class c in ascending g, best is the largest iou (0 without such a gt),
+ *   arg the SMALLEST g that reaches it; arg = -1 if best is not > 0.
+ *   PER PRESENT GT of class c: top is the largest iou over the present anchors of class c; if top > 0, every such anchor with
+ *   iou(a, g) == top is FORCED.
+ *   LABEL: positive (label c, gt_index arg) iff forced or best >= matched[c]; a forced anchor is assigned ITS OWN arg, not the gt that
+ *   forced it (pcdet's behaviour).  Otherwise background iff best < unmatched[c]; otherwise ignored.  A class without a present gt in the
+ *   frame is all background.
+ * Outputs, every shape static, every element written by every call:
+ *   d_out_label     (F, A) int32: the class for a positive, 0 for background, -1 for ignored or absent
+ *   d_out_gt_index  (F, A) int32: the gt number for a positive, -1 otherwise
+ *   d_out_count     (F, 3) int32: positives, backgrounds, ignored; absent anchors are in none of them
+ *   d_out_gt_count  (F, B) int32: the positives assigned to each gt
+ *   d_out_iou       (F, A) T, or NULL: best, rounded once to T; 0 for an absent anchor
+ * Domain: 1 <= A; 1 <= B <= 256; Ca in 7 .. 10; Cg in 8 .. 10; 1 <= NC <= 16; 0 < unmatched[c] <= matched[c] <= 1; F A <= 2^31 - 1; dtype 0
+ * or 1; every output apart from every input and every other output.  Anything else is SNOWGPU_E_INVALID with a message.
+ * Departures from pcdet: float64 instead of float32; the smallest gt among equal maxima, where torch's argmax is unspecified; absent
+ * anchors and gts; no pos_fraction sampling and no match_height (3D IoU); the box coder and the direction targets stay the caller's
+ * arithmetic on the matched gts.
+ * Four kernels on `stream` (csrc/snowgpu_anchors.hip): the gt records (48 bytes each) into context scratch with the frame's top words and
+ * gt_count zeroed -- no memset --; one lane per (frame, anchor) walking, in LDS, the frame's gts near the box around its workgroup's 256
+ * anchors (every other gt meets them at exactly 0), the wave's maximum per gt by a cross-lane reduction and one 64-bit integer atomicMax
+ * on the bits of the non-negative double per (wave, gt), which does not depend on the order of arrival; the same walk again by the same
+ * function, compared with top, gt_count by integer atomic adds, the workgroup's three label counts stored to scratch; their sums per
+ * frame.  No sort, nothing read on the host, nothing allocated after the first call of a size, no floating-point atomic: capturable as
+ * a linear graph, and two calls give identical bytes.  The records are scratch of the context: calls on streams that are not ordered
+ * against each other need a context each.
+ */
+int snowgpu_assign_anchors_device(snowgpu_ctx *ctx, int n_frames, int n_anchors, const void *d_anchors, int anchor_features,
+                                  const int32_t *d_anchor_class, int n_gt, const void *d_gt_boxes, int gt_features, int dtype, int n_classes,
+                                  const double *matched /* host */, const double *unmatched /* host */, int32_t *d_out_label, int32_t *d_out_gt_index,
+                                  int32_t *d_out_count, int32_t *d_out_gt_count, void *d_out_iou /* or NULL */, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -33,6 +33,7 @@ EXPORTS = [
     "snowgpu_voxelize_device", "snowgpu_fps_device", "snowgpu_ball_query_device", "snowgpu_range_image_device",
     "snowgpu_nearest_centres_device", "snowgpu_points_in_boxes_device", "snowgpu_boxes_iou_device", "snowgpu_nms_device", "snowgpu_fps_sectors_device",
     "snowgpu_roi_point_pool_device", "snowgpu_roi_voxel_pool_device", "snowgpu_sample_rois_device",
+    "snowgpu_assign_anchors_device",
 ]
 
 WET_ESTIMATION = {"linear": 0, "poly": 1}
@@ -162,6 +163,9 @@ def lib():
             L.snowgpu_sample_rois_device.restype = ctypes.c_int
             L.snowgpu_sample_rois_device.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, vp, vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int,
                                                      ctypes.POINTER(RoiSamplerStruct), ctypes.c_uint64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+            L.snowgpu_assign_anchors_device.restype = ctypes.c_int
+            L.snowgpu_assign_anchors_device.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                        ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), vp, vp, vp, vp, vp, vp]
             L.snowgpu_fov_mask_device.restype = ctypes.c_int
             L.snowgpu_fov_mask_device.argtypes = [vp, i64, vp, ctypes.c_int, vp, vp, vp, ctypes.c_int, ctypes.c_int, vp, vp, vp]
             L.snowgpu_dror_mask_device.restype = ctypes.c_int
@@ -767,6 +771,22 @@ class Context:
                                                 vp(d_out_gt_index or None), vp(d_out_gt_of_rois or None), vp(d_out_reg_valid or None),
                                                 vp(d_out_cls_label or None), vp(d_out_segments or None), vp(d_out_class_count or None),
                                                 vp(d_out_pose or None), vp(d_out_gt_local or None), vp(stream or None))
+        self._check_args(rc)
+
+    def assign_anchors_device(self, n_frames, n_anchors, d_anchors, anchor_features, d_anchor_class, n_gt, d_gt_boxes, gt_features, dtype_code, matched, unmatched,
+                              d_out_label, d_out_gt_index, d_out_count, d_out_gt_count, d_out_iou, stream=0):
+        """The anchor targets of every frame (include/snowgpu.h: snowgpu_assign_anchors_device); asynchronous on `stream`.  matched and
+        unmatched: one host float per class, read during the call; their common length is n_classes.  d_out_iou may be 0.  An argument
+        outside the domain, or an output overlapping an input or another output, raises ValueError with the entry's words."""
+        vp = ctypes.c_void_p
+        m, u = [float(v) for v in matched], [float(v) for v in unmatched]
+        if len(m) != len(u):
+            raise ValueError("assign_anchors_device: matched and unmatched hold one value per class each")
+        rc = self._L.snowgpu_assign_anchors_device(self._h, _i32(n_frames), _i32(n_anchors), vp(d_anchors or None), _i32(anchor_features), vp(d_anchor_class or None),
+                                                   _i32(n_gt), vp(d_gt_boxes or None), _i32(gt_features), int(dtype_code), _i32(len(m)),
+                                                   (ctypes.c_double * max(len(m), 1))(*m), (ctypes.c_double * max(len(u), 1))(*u), vp(d_out_label or None),
+                                                   vp(d_out_gt_index or None), vp(d_out_count or None), vp(d_out_gt_count or None), vp(d_out_iou or None),
+                                                   vp(stream or None))
         self._check_args(rc)
 
     def set_fov(self, calib=None, img_shape=(1024, 1920), pre_crop=False):

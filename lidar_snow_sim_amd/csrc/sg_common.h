@@ -363,6 +363,13 @@ int sg_launch_sample_rois(const struct SgTargetCfg *cfg, int n_frames, int32_t n
                           const double *pose_in, int32_t *out_index, void *out_rois, void *out_roi_iou, int32_t *out_gt_index, void *out_gt_of_rois,
                           uint8_t *out_reg_valid, void *out_cls_label, int32_t *out_segments, int32_t *out_class_count, double *out_pose,
                           void *out_gt_local, void *stream);
+// Anchor target assignment (sg_anchors.h; the definition: include/snowgpu.h): four kernels.  cfg: host.  recs: n_frames x n_gt records of
+// 48 bytes, top: n_frames x n_gt words, blk: n_frames x sg_anchors_groups(n_anchors) x 3 int32, all scratch.  out_iou may be null.
+struct SgAnchorCfg;
+int sg_launch_assign_anchors(const struct SgAnchorCfg *cfg, int n_frames, int32_t n_anchors, const void *anchors, int32_t anchor_features,
+                             const int32_t *anchor_class, int32_t n_gt, const void *gt, int32_t gt_features, int dtype, void *recs,
+                             unsigned long long *top, int32_t *blk, int32_t *out_label, int32_t *out_gt_index, int32_t *out_count,
+                             int32_t *out_gt_count, void *out_iou, void *stream);
 #ifdef __cplusplus
 }
 #endif

@@ -824,6 +824,60 @@ static inline int sg_check_targets_args(const SgTargetsArgs &a, std::string *msg
     return 0;
 }
 
+// ---- snowgpu_assign_anchors_device --------------------------------------------------------------------------------------------------------
+struct SgAnchorsArgs {
+    int n_frames;
+    int n_anchors;                    // A, shared by all frames
+    const void *anchors;
+    int anchor_features;              // Ca
+    const int32_t *anchor_class;
+    int n_gt;                         // B, per frame
+    const void *gt_boxes;
+    int gt_features;                  // Cg: column 7 is the class
+    int dtype;
+    int n_classes;                    // NC
+    const double *matched, *unmatched;        // host, NC each
+    int32_t *out_label, *out_gt_index, *out_count, *out_gt_count;
+    void *out_iou;                    // or NULL
+};
+
+// 0, or SG_ARGS_INVALID with *msg.  As above, the order is part of the ABI.
+static inline int sg_check_anchors_args(const SgAnchorsArgs &a, std::string *msg)
+{
+    static const char *who = "snowgpu_assign_anchors_device";
+    if (a.n_frames <= 0 || !a.anchors || !a.anchor_class || !a.gt_boxes || !a.matched || !a.unmatched || !a.out_label || !a.out_gt_index || !a.out_count ||
+        !a.out_gt_count || (a.dtype != 0 && a.dtype != 1))
+        return sg_refuse(who, ": null pointer or bad dtype", msg);
+    if (a.n_anchors < 1) return sg_refuse(who, ": n_anchors must be at least 1", msg);
+    if (a.n_gt < 1 || a.n_gt > 256) return sg_refuse(who, ": n_gt must lie in 1 .. 256", msg);
+    if (a.anchor_features < 7 || a.anchor_features > 10)
+        return sg_refuse(who, ": anchor_features must lie in 7 .. 10: cx, cy, cz, dx, dy, dz, heading first", msg);
+    if (a.gt_features < 8 || a.gt_features > 10)
+        return sg_refuse(who, ": gt_features must lie in 8 .. 10: cx, cy, cz, dx, dy, dz, heading, class first", msg);
+    if (a.n_classes < 1 || a.n_classes > 16) return sg_refuse(who, ": n_classes must lie in 1 .. 16", msg);
+    for (int c = 0; c < a.n_classes; ++c)
+        if (!(0.0 < a.unmatched[c] && a.unmatched[c] <= a.matched[c] && a.matched[c] <= 1.0))                                  // (false for NaN)
+            return sg_refuse(who, ": every class needs 0 < unmatched <= matched <= 1", msg);
+    if ((int64_t)a.n_frames * a.n_anchors > ((int64_t)1 << 31) - 1) return sg_refuse(who, ": n_frames * n_anchors exceeds 2^31 - 1; split the batch", msg);
+    const size_t esz = a.dtype == 0 ? 4 : 8, q = (size_t)a.n_frames * (size_t)a.n_anchors, g = (size_t)a.n_frames * (size_t)a.n_gt;
+    const struct { const void *p; size_t bytes; const char *name; } outs[5] = {
+        {a.out_label, q * 4, "d_out_label"}, {a.out_gt_index, q * 4, "d_out_gt_index"}, {a.out_count, (size_t)a.n_frames * 12, "d_out_count"},
+        {a.out_gt_count, g * 4, "d_out_gt_count"}, {a.out_iou, q * esz, "d_out_iou"}};
+    const struct { const void *p; size_t bytes; const char *name; } ins[3] = {
+        {a.anchors, (size_t)a.n_anchors * (size_t)a.anchor_features * esz, "d_anchors"}, {a.anchor_class, (size_t)a.n_anchors * 4, "d_anchor_class"},
+        {a.gt_boxes, g * (size_t)a.gt_features * esz, "d_gt_boxes"}};
+    for (int i = 0; i < 5; ++i) {
+        const auto &o = outs[i];
+        for (int j = 0; j < 3; ++j)
+            if (sg_ranges_meet(o.p, o.bytes, ins[j].p, ins[j].bytes))
+                return sg_refuse(who, (std::string(": ") + o.name + " overlaps " + ins[j].name + "; the anchors, their classes and the gt boxes are read while the targets are written: pass a buffer apart from them").c_str(), msg);
+        for (int j = 0; j < i; ++j)
+            if (sg_ranges_meet(o.p, o.bytes, outs[j].p, outs[j].bytes))
+                return sg_refuse(who, (std::string(": ") + o.name + " overlaps " + outs[j].name + "; every output needs memory of its own").c_str(), msg);
+    }
+    return 0;
+}
+
 // 0, or SG_ARGS_INVALID with *msg (built on this path only).  The order is part of the ABI: it decides which message a doubly wrong call gets.
 static inline int sg_check_device_args(const SgDeviceArgs &a, const SgCtxView &c, const SgEntryShape &s, std::string *msg)
 {

@@ -126,6 +126,11 @@ struct __attribute__((visibility("default"))) snowgpu_ctx {
     // box IoU and NMS (snowgpu_boxes_iou_device, snowgpu_nms_device): one record of nine doubles per box; the ranking and its length
     DevBuf<double> iou_rec;
     DevBuf<int32_t> nms_order, nms_cand;
+    // anchor target assignment (snowgpu_assign_anchors_device): one record of six doubles per gt, the bits of its largest overlap, and per
+    // (frame, workgroup of 256 anchors) the three label counts
+    DevBuf<double> anchor_rec;
+    DevBuf<unsigned long long> anchor_top;
+    DevBuf<int32_t> anchor_blk;
     // scratch shared by every batch
     DevBuf<int32_t> tile_hist, tile_base, perm, ctile_cnt, ctile_base, table_ids, out_src;
     DevBuf<uint8_t> srows;            // channel-sorted copy of the frames whose rows did not come channel-sorted (firing order)

@@ -1,5 +1,5 @@
 // snowgpu_device.cpp -- the entries of the C ABI (include/snowgpu.h) that take DEVICE pointers and enqueue on the caller's stream: every
-// *_batch_device* entry, the plane estimate, the FOV mask, the outlier filter, the voxel stage, the keypoint stage and its sectorized form, the ball query, the range image, the nearest centres, the points in boxes, the RoI point pooling, the RoI-aware voxel pooling, the box IoU and NMS, the proposal target sampling and the weather draw.  Each batch entry fills an SgDeviceArgs, has it checked
+// *_batch_device* entry, the plane estimate, the FOV mask, the outlier filter, the voxel stage, the keypoint stage and its sectorized form, the ball query, the range image, the nearest centres, the points in boxes, the RoI point pooling, the RoI-aware voxel pooling, the box IoU and NMS, the proposal target sampling, the anchor target assignment and the weather draw.  Each batch entry fills an SgDeviceArgs, has it checked
 // (sg_device_args.h: every refusal, in one order), sets the device and runs batch_from_args() and the stages it needs.  The launch
 // sequence of a batch is snowgpu_batch.cpp; no host copy, no synchronisation, no allocation after the first call of a given size.
 #include "sg_host.h"
@@ -17,6 +17,7 @@
 #include "sg_iou.h"         // the record of the IoU and NMS stages and the size of their scratch
 #include "sg_range.h"       // the geometry of the range image and the limits in the rows' dtype
 #include "sg_targets.h"     // SgTargetCfg of the proposal target sampling
+#include "sg_anchors.h"     // SgAnchorCfg and the record of the anchor target assignment
 
 static_assert(SG_ARGS_INVALID == SNOWGPU_E_INVALID && SG_PLANE_REFERENCE == 0, "sg_device_args.h restates these two");
 
@@ -753,6 +754,33 @@ extern "C" int snowgpu_sample_rois_device(snowgpu_ctx *ctx, int n_frames, int n_
                                   d_out_index, d_out_rois, d_out_roi_iou, d_out_gt_index, d_out_gt_of_rois, d_out_reg_valid, d_out_cls_label, d_out_segments,
                                   d_out_class_count, d_out_pose, d_out_gt_local, stream ? (hipStream_t)stream : ctx->stream);
     if (e) return fail(ctx, SNOWGPU_E_HIP, std::string("target sampling launch: ") + hipGetErrorString((hipError_t)e));
+    return SNOWGPU_OK;
+}
+
+// Anchor target assignment (snowgpu_anchors.hip; presence, the BEV box, the overlap, the walk and the label rule: sg_anchors.h).  See include/snowgpu.h.
+extern "C" int snowgpu_assign_anchors_device(snowgpu_ctx *ctx, int n_frames, int n_anchors, const void *d_anchors, int anchor_features,
+                                             const int32_t *d_anchor_class, int n_gt, const void *d_gt_boxes, int gt_features, int dtype, int n_classes,
+                                             const double *matched, const double *unmatched, int32_t *d_out_label, int32_t *d_out_gt_index,
+                                             int32_t *d_out_count, int32_t *d_out_gt_count, void *d_out_iou, void *stream)
+{
+    if (!ctx) return SNOWGPU_E_INVALID;
+    const SgAnchorsArgs a{n_frames, n_anchors, d_anchors, anchor_features, d_anchor_class, n_gt, d_gt_boxes, gt_features, dtype, n_classes, matched, unmatched,
+                          d_out_label, d_out_gt_index, d_out_count, d_out_gt_count, d_out_iou};
+    {
+        std::string msg;
+        if (int rc = sg_check_anchors_args(a, &msg)) return fail(ctx, rc, msg);
+    }
+    SgAnchorCfg k{};
+    k.n_classes = n_classes;
+    for (int c = 0; c < n_classes; ++c) { k.matched[c] = matched[c]; k.unmatched[c] = unmatched[c]; }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    ENSURE(ctx, ctx->anchor_rec, (size_t)n_frames * (size_t)n_gt * (sizeof(SgAnchorRec) / sizeof(double)));
+    ENSURE(ctx, ctx->anchor_top, (size_t)n_frames * (size_t)n_gt);
+    ENSURE(ctx, ctx->anchor_blk, (size_t)n_frames * (size_t)sg_anchors_groups(n_anchors) * 3);
+    int e = sg_launch_assign_anchors(&k, n_frames, n_anchors, d_anchors, anchor_features, d_anchor_class, n_gt, d_gt_boxes, gt_features, dtype, ctx->anchor_rec.p,
+                                     ctx->anchor_top.p, ctx->anchor_blk.p, d_out_label, d_out_gt_index, d_out_count, d_out_gt_count, d_out_iou,
+                                     stream ? (hipStream_t)stream : ctx->stream);
+    if (e) return fail(ctx, SNOWGPU_E_HIP, std::string("anchor assignment launch: ") + hipGetErrorString((hipError_t)e));
     return SNOWGPU_OK;
 }
 

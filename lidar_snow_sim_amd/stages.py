@@ -1,6 +1,6 @@
 """The device stages of the torch-tensor boundary (tensors.py is the documented import path and lists what each is for) and the batches
 of static shape they leave behind: fov_keep, dror_keep, voxelize, sample_keypoints, ball_query, range_image, nearest_keypoints,
-points_in_boxes, boxes_iou, nms, roi_point_pool, roi_voxel_pool, sample_rois.  Every stage goes through the same steps, in this order -- it is the order in which a call that is wrong
+points_in_boxes, boxes_iou, nms, roi_point_pool, roi_voxel_pool, sample_rois, assign_anchors.  Every stage goes through the same steps, in this order -- it is the order in which a call that is wrong
 in two ways is refused: the aligned unwrap and the device-input refusal (_stage_frames), the scalar and range checks (_whole, _range6),
 the batch and its keep mask (_stage_batch), the stage's own tensors, the checks of the shapes' domain, out= (_checked_out), the launch
 (_stage_launch).  PyTorch is plumbing here; the work is the C entries'."""
@@ -1212,3 +1212,149 @@ def sample_rois(rois, gt_boxes, overlaps, *, step, seed=0, roi_per_image=128, fg
     same = (used is None) == (out.pose is None) and (local is None) == (out.gt_local is None)
     return out if same else RoiTargetBatch(out.index, out.rois, out.roi_iou, out.gt_index, out.gt_of_rois, out.reg_valid, out.cls_label, out.segments,
                                            out.class_count, used, local)
+
+
+class AnchorTargetBatch:
+    """What assign_anchors() leaves behind, F = frames, A = anchors, B = gt boxes per frame -- every shape static, every element written by
+    every call: `label` (F, A int32: the class for a positive, 0 for background, -1 for an ignored or absent anchor), `gt_index` (F, A
+    int32: the gt number of a positive, -1 otherwise), `count` (F, 3 int32: positives, backgrounds, ignored; absent anchors are in none of
+    them), `gt_count` (F, B int32: the positives assigned to each gt) and `iou` (F, A in the boxes' dtype: the anchor's best overlap; None
+    unless asked for).  positive, matched(), reg_weights() and cls_weights() are pure indexing, no kernel of this library.  All still being
+    written until the stream the call was made on has caught up."""
+
+    def __init__(self, label, gt_index, count, gt_count, iou=None):
+        self.label, self.gt_index, self.count, self.gt_count, self.iou = label, gt_index, count, gt_count, iou
+
+    @classmethod
+    def empty(cls, n_frames, n_anchors, n_gt, dtype=None, device=None, with_iou=False):
+        """Uninitialised buffers of the shapes assign_anchors() writes (out=): static addresses for a captured graph."""
+        import torch
+        dev = _cuda_device(torch, device)
+        F, A, B = int(n_frames), int(n_anchors), int(n_gt)
+
+        def new(shape, kind):
+            return torch.empty(shape, dtype=kind, device=dev)
+        return cls(new((F, A), torch.int32), new((F, A), torch.int32), new((F, 3), torch.int32), new((F, B), torch.int32),
+                   new((F, A), dtype or torch.float32) if with_iou else None)
+
+    @property
+    def positive(self):
+        """(F, A) bool: label > 0."""
+        return self.label > 0
+
+    def matched(self, gt_boxes):
+        """(F, A, Cg): the gt box of every positive anchor, a zero row where the anchor is not positive -- what a ResidualCoder encodes
+        against the anchors, and whose heading gives the direction targets."""
+        import torch
+        F, A = self.label.shape
+        if not (torch.is_tensor(gt_boxes) and gt_boxes.dim() == 3 and gt_boxes.shape[0] == F and gt_boxes.shape[1] == self.gt_count.shape[1] and
+                gt_boxes.device == self.label.device):
+            raise ValueError(f"matched: gt_boxes must be the ({F}, {self.gt_count.shape[1]}, Cg) tensor the anchors were assigned to, on their device")
+        at = self.gt_index.long()
+        got = torch.gather(gt_boxes, 1, at.clamp(min=0)[..., None].expand(-1, -1, gt_boxes.shape[2]))
+        return torch.where((at >= 0)[..., None], got, torch.zeros_like(got))
+
+    def reg_weights(self, norm_by_num_examples=True):
+        """(F, A) float32: 1 on positives -- with norm_by_num_examples 1 / max(positives + backgrounds, 1) of the frame --, 0 elsewhere."""
+        w = self.positive.float()
+        if norm_by_num_examples:
+            w = w / (self.count[:, 0] + self.count[:, 1]).clamp(min=1).float()[:, None]
+        return w
+
+    def cls_weights(self):
+        """(F, A) float32: 1 on positives and backgrounds, 0 on ignored and absent anchors."""
+        return (self.label >= 0).float()
+
+
+def anchor_grid(point_cloud_range, grid_size, sizes, rotations, bottom_heights, align_center=False, dtype=None, device=None):
+    """The anchors of pcdet's AnchorGenerator and their class numbers, plain torch arithmetic run once at set-up (no kernel): one class per
+    entry of `sizes` ((dx, dy, dz) each) with its entry of `bottom_heights`, every rotation of `rotations` at every position of the
+    nx x ny grid.  Centres are range_lo + i (range_hi - range_lo) / (n - 1) -- with align_center range_lo + (i + 0.5) stride,
+    stride = (range_hi - range_lo) / n --, z is bottom_height + dz / 2.  Anchor number a = ((y nx + x) NC + c) R + r: the order in which an
+    anchor head's cls_preds.view(F, -1, NC) lies.  Returns (anchors (A, 7) in `dtype`, anchor_class (A) int32 = c + 1), computed in float64."""
+    import torch
+    who = "anchor_grid"
+    rng = _range6(who, point_cloud_range)
+    if rng is None:
+        raise ValueError(f"{who}: point_cloud_range holds 6 numbers (x0, y0, z0, x1, y1, z1)")
+    nx, ny = grid_size
+    _whole(who, nx=nx, ny=ny)
+    nx, ny = int(nx), int(ny)
+    sz = np.asarray(sizes, np.float64)
+    rot, low = np.asarray(rotations, np.float64).reshape(-1), np.asarray(bottom_heights, np.float64).reshape(-1)
+    if sz.ndim != 2 or sz.shape[1] != 3 or len(sz) < 1 or len(low) != len(sz) or len(rot) < 1:
+        raise ValueError(f"{who}: sizes holds one (dx, dy, dz) per class, bottom_heights one number per class, rotations at least one")
+    if nx < 1 or ny < 1 or (not align_center and (nx < 2 or ny < 2)):
+        raise ValueError(f"{who}: the grid needs at least 2 positions per axis (1 with align_center)")
+
+    def centres(lo, hi, n):
+        i = np.arange(n, dtype=np.float64)
+        return lo + (i + 0.5) * ((hi - lo) / n) if align_center else lo + i * ((hi - lo) / (n - 1))
+    NC, R = len(sz), len(rot)
+    out = np.zeros((ny, nx, NC, R, 7), np.float64)
+    out[..., 0] = centres(rng[0], rng[3], nx)[None, :, None, None]
+    out[..., 1] = centres(rng[1], rng[4], ny)[:, None, None, None]
+    out[..., 2] = (low + sz[:, 2] / 2)[None, None, :, None]
+    out[..., 3:6] = sz[None, None, :, None, :]
+    out[..., 6] = rot[None, None, None, :]
+    cls = np.broadcast_to(np.arange(1, NC + 1, dtype=np.int32)[None, None, :, None], (ny, nx, NC, R))
+    dev = torch.device(device) if isinstance(device, str) else _cuda_device(torch, device)       # ("cpu" is fine: nothing here needs the GPU)
+    return (torch.from_numpy(out.reshape(-1, 7)).to(dtype or torch.float32).to(dev).contiguous(),
+            torch.from_numpy(np.ascontiguousarray(cls).reshape(-1)).to(dev))
+
+
+def assign_anchors(anchors, anchor_class, gt_boxes, matched=(0.6, 0.5, 0.5), unmatched=(0.45, 0.35, 0.35), *, out=None, return_iou=False, slot=0):
+    """The anchor targets of every frame on the device (snowgpu_assign_anchors_device; the definition: include/snowgpu.h): the assignment
+    of pcdet's AxisAlignedTargetAssigner with static shapes and nothing read on the host -- per class the nearest axis-aligned BEV overlap
+    of every anchor with every gt in float64, positives by the matched threshold and by being a gt's best anchor, backgrounds by the
+    unmatched threshold, the rest ignored.  The definition is this library's, modelled on pcdet's assigner.
+
+    anchors       a contiguous (A, 7 .. 10) float32 or float64 CUDA tensor shared by all frames (anchor_grid): cx, cy, cz, dx, dy, dz,
+                  heading first; F A < 2^31.
+    anchor_class  a contiguous (A) int32 tensor on their device: the class number, 1 .. NC, of each anchor; anything else is an absent anchor.
+    gt_boxes      a contiguous (F, B, 8 .. 10) tensor of the anchors' dtype on their device, 1 <= B <= 256: column 7 is the class; zero rows
+                  are padding (zero the gts an augmentation emptied: points_in_boxes(res, gt).keep_boxes(min_points)).
+    matched, unmatched   one number per class, 1 <= NC <= 16 of them, 0 < unmatched[c] <= matched[c] <= 1.
+    out           an AnchorTargetBatch to write into (AnchorTargetBatch.empty): every element is written, nothing needs clearing.
+    The gt records are scratch of the engine of `slot`: calls made on streams that are not ordered against each other need a `slot` each.
+
+    Returns an AnchorTargetBatch.  Asynchronous on torch's current stream; nothing is read on the host: capturable after one warm-up call."""
+    import torch
+    from . import engine as _engine
+    who = "assign_anchors"
+    try:
+        m, u = [float(v) for v in matched], [float(v) for v in unmatched]
+    except TypeError:
+        raise ValueError(f"{who}: matched and unmatched hold one number per class") from None
+    if len(m) != len(u):
+        raise ValueError(f"{who}: matched and unmatched hold one number per class")
+    if not (torch.is_tensor(anchors) and anchors.is_cuda and anchors.dim() == 2 and anchors.dtype in (torch.float32, torch.float64) and anchors.is_contiguous()):
+        raise ValueError(f"{who}: anchors must be a contiguous (A, 7 .. 10) float32 or float64 CUDA tensor")
+    A, Ca = (int(v) for v in anchors.shape)
+    dev, dt = anchors.device, anchors.dtype
+    if not (torch.is_tensor(anchor_class) and tuple(anchor_class.shape) == (A,) and anchor_class.dtype == torch.int32 and anchor_class.device == dev and
+            anchor_class.is_contiguous()):
+        raise ValueError(f"{who}: anchor_class must be a contiguous ({A},) int32 tensor on the device of the anchors")
+    if not (torch.is_tensor(gt_boxes) and gt_boxes.dim() == 3 and gt_boxes.dtype == dt and gt_boxes.device == dev and gt_boxes.is_contiguous()):
+        raise ValueError(f"{who}: gt_boxes must be a contiguous (frames, B, 8 .. 10) tensor of the anchors' dtype on their device")
+    F, B, Cg = (int(v) for v in gt_boxes.shape)
+    # (the shapes below need these; the entry refuses them in the same words, and everything else of the domain)
+    if F < 1 or A < 1:
+        raise ValueError(f"{who}: the frames and the anchors must be at least 1")
+    if not 1 <= B <= 256:
+        raise ValueError(f"{who}: n_gt must lie in 1 .. 256")
+    if F * A > 2 ** 31 - 1:
+        raise ValueError(f"{who}: n_frames * n_anchors exceeds 2^31 - 1; split the batch")
+    want = (("label", torch.int32, (F, A), True), ("gt_index", torch.int32, (F, A), True), ("count", torch.int32, (F, 3), True),
+            ("gt_count", torch.int32, (F, B), True), ("iou", dt, (F, A), return_iou))
+    if out is None:
+        out = AnchorTargetBatch.empty(F, A, B, dt, dev, return_iou)
+    else:
+        _checked_out(torch, who, AnchorTargetBatch, out, want, dev, "anchors")
+    iou = out.iou if return_iou else None
+    eng = _engine.get_engine(dev.index, slot)
+    with torch.cuda.device(dev), _on_run_stream(torch, eng, dev) as (_, run):
+        eng.ctx.assign_anchors_device(F, A, anchors.data_ptr(), Ca, anchor_class.data_ptr(), B, gt_boxes.data_ptr(), Cg, 0 if dt == torch.float32 else 1, m, u,
+                                      out.label.data_ptr(), out.gt_index.data_ptr(), out.count.data_ptr(), out.gt_count.data_ptr(),
+                                      0 if iou is None else iou.data_ptr(), run.cuda_stream)
+    return out if (iou is None) == (out.iou is None) else AnchorTargetBatch(out.label, out.gt_index, out.count, out.gt_count, iou)
