@@ -1,4 +1,4 @@
-// sg_common.h -- types shared by the host API (snowgpu_api.cpp, snowgpu_device.cpp, snowgpu_batch.cpp, snowgpu_host.cpp; their own header is sg_host.h) and the gfx950 kernels.
+// sg_common.h -- types shared by the host API (snowgpu_api.cpp, snowgpu_device.cpp, snowgpu_stages.cpp, snowgpu_batch.cpp, snowgpu_host.cpp; their own header is sg_host.h) and the gfx950 kernels.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>

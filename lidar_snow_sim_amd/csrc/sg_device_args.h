@@ -1,6 +1,7 @@
-// sg_device_args.h -- what the *_batch_device* entries (snowgpu_device.cpp) take in common, and the one place that refuses a call of
-// theirs: pure argument checks on plain data.  Nothing of HIP is included, so the whole refusal matrix runs on a machine without a device
-// (tests/host_harness/device_refusals.cpp).
+// sg_device_args.h -- what the entries that take device pointers take in common, and the one place that refuses a call of theirs: pure
+// argument checks on plain data.  sg_check_device_args is for the *_batch_device* entries (snowgpu_device.cpp), the sg_check_*_args above it
+// for the stage entries (snowgpu_stages.cpp), and what those share stands once, ahead of them.  Nothing of HIP is included, so the whole
+// refusal matrix runs on a machine without a device (tests/host_harness/*_refusals.cpp).
 #pragma once
 #include <cmath>
 #include <cstddef>
@@ -107,6 +108,85 @@ static inline int sg_check_wet_plane(const char *who, const double *wet_plane, i
     return sg_refuse(who, ": a NULL wet plane needs the plane method 'reference'; 'lsq' and 'ransac' crop the rows and have no masked form: pass the plane", msg);
 }
 
+// ---- what the checks of the stage entries share -------------------------------------------------------------------------------------------
+// Each is 0, or SG_ARGS_INVALID with *msg (built on this path only).  Where a stage calls them is its own business: the order of a
+// stage's checks is part of the ABI, since it decides which message a doubly wrong call gets (the "_and_" cases of the harnesses).
+
+// `missing`: the stage's own "something required is NULL"
+static inline int sg_check_head(const char *who, int n_frames, int dtype, bool missing, std::string *msg)
+{
+    return (n_frames <= 0 || missing || (dtype != 0 && dtype != 1)) ? sg_refuse(who, ": null pointer or bad dtype", msg) : 0;
+}
+
+static inline int sg_check_rows(int64_t n_total, std::string *msg)
+{
+    return n_total >= ((int64_t)1 << 31) ? sg_refuse("", "batch too large: split it below 2^31 rows", msg) : 0;
+}
+
+// the head of a stage that takes the rows of a batch
+template <class Args>
+static inline int sg_check_batch_head(const char *who, const Args &a, bool missing, std::string *msg)
+{
+    if (int rc = sg_check_head(who, a.n_frames, a.dtype, a.n_total < 0 || !a.frame_off || missing, msg)) return rc;
+    return sg_check_rows(a.n_total, msg);
+}
+
+// `longest`: sg_max_frame() of the batch
+static inline int sg_check_frame(const char *who, int64_t longest, std::string *msg)
+{
+    return longest > ((int64_t)1 << 30) ? sg_refuse(who, ": a frame of more than 2^30 rows; split it", msg) : 0;
+}
+
+// (x0, y0, z0, x1, y1, z1) or NULL: no range test
+static inline int sg_check_range6(const char *who, const double *range6, std::string *msg)
+{
+    if (!range6) return 0;
+    for (int j = 0; j < 6; ++j)
+        if (range6[j] != range6[j]) return sg_refuse(who, ": a bound of the range is NaN; pass NULL for no range, or infinite bounds", msg);
+    for (int j = 0; j < 3; ++j)
+        if (!(range6[j] < range6[3 + j])) return sg_refuse(who, ": the range needs lo < hi on every axis", msg);
+    return 0;
+}
+
+// 3 doubles or NULL: zeros
+static inline int sg_check_extra_width(const char *who, const double *extra_width, std::string *msg)
+{
+    for (int j = 0; extra_width && j < 3; ++j)
+        if (!(extra_width[j] >= 0.0 && extra_width[j] <= 100.0))                             // (false for NaN)
+            return sg_refuse(who, ": every component of extra_width must be finite and lie in 0 .. 100", msg);
+    return 0;
+}
+
+// two arrays, `abytes` from a and `bbytes` from b, that share a byte (false where either is NULL or empty)
+static inline bool sg_ranges_meet(const void *a, size_t abytes, const void *b, size_t bbytes)
+{
+    const uintptr_t p = (uintptr_t)a, q = (uintptr_t)b;
+    return p && q && abytes && bbytes && p < q + bbytes && q < p + abytes;
+}
+
+struct SgOutSpan { const void *p; size_t bytes; const char *name; };
+// `read`, `apart`: "the mask is" and "it", or "the rows are" and "them" -- or one phrase for all inputs of the stage
+struct SgInSpan { const void *p; size_t bytes; const char *name, *read, *apart; };
+
+// No output may share a byte with an input nor, with `among_outputs`, with an output before it: for output i the inputs in table order, then
+// the outputs 0 .. i - 1.  `written`: "the samples are", "the image is".
+template <size_t N_OUT, size_t N_IN>
+static inline int sg_check_overlaps(const char *who, const SgOutSpan (&outs)[N_OUT], const SgInSpan (&ins)[N_IN], const char *written, bool among_outputs,
+                                    std::string *msg)
+{
+    for (size_t i = 0; i < N_OUT; ++i) {
+        const SgOutSpan &o = outs[i];
+        for (const SgInSpan &in : ins)
+            if (sg_ranges_meet(o.p, o.bytes, in.p, in.bytes))
+                return sg_refuse(who, (std::string(": ") + o.name + " overlaps " + in.name + "; " + in.read + " read while " + written +
+                                       " written: pass a buffer apart from " + in.apart).c_str(), msg);
+        for (size_t j = 0; among_outputs && j < i; ++j)
+            if (sg_ranges_meet(o.p, o.bytes, outs[j].p, outs[j].bytes))
+                return sg_refuse(who, (std::string(": ") + o.name + " overlaps " + outs[j].name + "; every output needs memory of its own").c_str(), msg);
+    }
+    return 0;
+}
+
 // ---- snowgpu_voxelize_device ------------------------------------------------------------------------------------------------------------
 struct SgVoxelArgs {
     int n_frames;
@@ -141,14 +221,13 @@ static inline int sg_voxel_dims(const double *range6, const double *size3, int32
     return too_many || cells > SG_VOXEL_MAX_CELLS ? 3 : 0;
 }
 
-// 0 and the grid's n_x, n_y, n_z, or SG_ARGS_INVALID with *msg.  As above, the order is part of the ABI.
+// 0 and the grid's n_x, n_y, n_z, or SG_ARGS_INVALID with *msg.  As above, the order is part of the ABI.  Of the overlaps only
+// d_out_voxel_of against d_keep_in is looked for.
 static inline int sg_check_voxel_args(const SgVoxelArgs &a, int32_t n_cells[3], std::string *msg)
 {
     static const char *who = "snowgpu_voxelize_device";
-    if (a.n_frames <= 0 || a.n_total < 0 || !a.frame_off || !a.range6 || !a.size3 || !a.out_voxel_offsets ||
-        (a.n_total > 0 && (!a.rows || !a.out_voxels || !a.out_coords || !a.out_num_points)) || (a.dtype != 0 && a.dtype != 1))
-        return sg_refuse(who, ": null pointer or bad dtype", msg);
-    if (a.n_total >= ((int64_t)1 << 31)) return sg_refuse("", "batch too large: split it below 2^31 rows", msg);
+    if (int rc = sg_check_batch_head(who, a, !a.range6 || !a.size3 || !a.out_voxel_offsets ||
+                                                 (a.n_total > 0 && (!a.rows || !a.out_voxels || !a.out_coords || !a.out_num_points)), msg)) return rc;
     if (a.n_features < 3 || a.n_features > 5) return sg_refuse(who, ": n_features must be 3, 4 or 5: the columns of a row that a voxel stores", msg);
     if (a.max_points < 1 || a.max_voxels < 1) return sg_refuse(who, ": max_points and max_voxels must be at least 1", msg);
     switch (sg_voxel_dims(a.range6, a.size3, n_cells)) {
@@ -159,13 +238,9 @@ static inline int sg_check_voxel_args(const SgVoxelArgs &a, int32_t n_cells[3], 
     }
     if ((int64_t)a.n_frames * a.max_voxels > (((int64_t)1 << 31) - 1))
         return sg_refuse(who, ": n_frames * max_voxels exceeds 2^31 - 1; split the batch", msg);
-    if (sg_max_frame(a.max_frame_rows, a.n_total) > ((int64_t)1 << 30))
-        return sg_refuse(who, ": a frame of more than 2^30 rows; split it", msg);
-    if (a.keep_in && a.out_voxel_of) {
-        const uintptr_t k = (uintptr_t)a.keep_in, o = (uintptr_t)a.out_voxel_of;
-        if (o < k + (size_t)a.n_total && k < o + (size_t)a.n_total * 4)
-            return sg_refuse(who, ": d_out_voxel_of overlaps d_keep_in; the keep-in bytes of other rows are read while it is written: pass a buffer apart from it", msg);
-    }
+    if (int rc = sg_check_frame(who, sg_max_frame(a.max_frame_rows, a.n_total), msg)) return rc;
+    if (sg_ranges_meet(a.out_voxel_of, (size_t)a.n_total * 4, a.keep_in, (size_t)a.n_total))
+        return sg_refuse(who, ": d_out_voxel_of overlaps d_keep_in; the keep-in bytes of other rows are read while it is written: pass a buffer apart from it", msg);
     return 0;
 }
 
@@ -184,42 +259,28 @@ struct SgFpsArgs {
     int32_t *out_usable;
 };
 
-// two arrays, `abytes` from a and `bbytes` from b, that share a byte (false where either is NULL or empty)
-static inline bool sg_ranges_meet(const void *a, size_t abytes, const void *b, size_t bbytes)
+// what snowgpu_fps_device and snowgpu_fps_sectors_device check alike, behind their heads
+static inline int sg_check_fps_domain(const char *who, const SgFpsArgs &a, std::string *msg)
 {
-    const uintptr_t p = (uintptr_t)a, q = (uintptr_t)b;
-    return p && q && abytes && bbytes && p < q + bbytes && q < p + abytes;
-}
-
-// 0, or SG_ARGS_INVALID with *msg.  As above, the order is part of the ABI.
-static inline int sg_check_fps_args(const SgFpsArgs &a, std::string *msg)
-{
-    static const char *who = "snowgpu_fps_device";
-    if (a.n_frames <= 0 || a.n_total < 0 || !a.frame_off || !a.out_index || !a.out_usable || (a.n_total > 0 && !a.rows) || (a.dtype != 0 && a.dtype != 1))
-        return sg_refuse(who, ": null pointer or bad dtype", msg);
-    if (a.n_total >= ((int64_t)1 << 31)) return sg_refuse("", "batch too large: split it below 2^31 rows", msg);
     if (a.n_features < 3 || a.n_features > 5) return sg_refuse(who, ": n_features must be 3, 4 or 5: the columns of a row that a keypoint carries", msg);
     if (a.n_samples < 1) return sg_refuse(who, ": n_samples must be at least 1", msg);
     if ((int64_t)a.n_frames * a.n_samples > (((int64_t)1 << 31) - 1))
         return sg_refuse(who, ": n_frames * n_samples exceeds 2^31 - 1; split the batch", msg);
-    if (sg_max_frame(a.max_frame_rows, a.n_total) > ((int64_t)1 << 30))
-        return sg_refuse(who, ": a frame of more than 2^30 rows; split it", msg);
-    if (a.range6) {
-        for (int j = 0; j < 6; ++j)
-            if (a.range6[j] != a.range6[j]) return sg_refuse(who, ": a bound of the range is NaN; pass NULL for no range, or infinite bounds", msg);
-        for (int j = 0; j < 3; ++j)
-            if (!(a.range6[j] < a.range6[3 + j])) return sg_refuse(who, ": the range needs lo < hi on every axis", msg);
-    }
+    if (int rc = sg_check_frame(who, sg_max_frame(a.max_frame_rows, a.n_total), msg)) return rc;
+    return sg_check_range6(who, a.range6, msg);
+}
+
+// 0, or SG_ARGS_INVALID with *msg.  As above, the order is part of the ABI.  The outputs are not compared with each other.
+static inline int sg_check_fps_args(const SgFpsArgs &a, std::string *msg)
+{
+    static const char *who = "snowgpu_fps_device";
+    if (int rc = sg_check_batch_head(who, a, !a.out_index || !a.out_usable || (a.n_total > 0 && !a.rows), msg)) return rc;
+    if (int rc = sg_check_fps_domain(who, a, msg)) return rc;
     const size_t esz = a.dtype == 0 ? 4 : 8, elems = (size_t)a.n_frames * (size_t)a.n_samples, n = (size_t)a.n_total;
-    const struct { const void *p; size_t bytes; const char *name; } outs[3] = {
+    const SgOutSpan outs[3] = {
         {a.out_index, elems * 4, "d_out_index"}, {a.out_points, elems * (size_t)a.n_features * esz, "d_out_points"}, {a.out_dist, elems * esz, "d_out_dist"}};
-    for (const auto &o : outs) {
-        if (sg_ranges_meet(o.p, o.bytes, a.keep_in, n))
-            return sg_refuse(who, (std::string(": ") + o.name + " overlaps d_keep_in; the mask is read while the samples are written: pass a buffer apart from it").c_str(), msg);
-        if (sg_ranges_meet(o.p, o.bytes, a.rows, n * 5 * esz))
-            return sg_refuse(who, (std::string(": ") + o.name + " overlaps d_rows; the rows are read while the samples are written: pass a buffer apart from them").c_str(), msg);
-    }
-    return 0;
+    const SgInSpan ins[2] = {{a.keep_in, n, "d_keep_in", "the mask is", "it"}, {a.rows, n * 5 * esz, "d_rows", "the rows are", "them"}};
+    return sg_check_overlaps(who, outs, ins, "the samples are", false, msg);
 }
 
 // ---- snowgpu_fps_sectors_device -----------------------------------------------------------------------------------------------------------
@@ -239,22 +300,8 @@ static inline int sg_check_fps_sectors_args(const SgFpsSectorsArgs &s, std::stri
 {
     static const char *who = "snowgpu_fps_sectors_device";
     const SgFpsArgs &a = s.fps;
-    if (a.n_frames <= 0 || a.n_total < 0 || !a.frame_off || !a.out_index || !a.out_usable || !s.out_sector_offsets || !s.out_sector_count ||
-        (a.n_total > 0 && !a.rows) || (a.dtype != 0 && a.dtype != 1))
-        return sg_refuse(who, ": null pointer or bad dtype", msg);
-    if (a.n_total >= ((int64_t)1 << 31)) return sg_refuse("", "batch too large: split it below 2^31 rows", msg);
-    if (a.n_features < 3 || a.n_features > 5) return sg_refuse(who, ": n_features must be 3, 4 or 5: the columns of a row that a keypoint carries", msg);
-    if (a.n_samples < 1) return sg_refuse(who, ": n_samples must be at least 1", msg);
-    if ((int64_t)a.n_frames * a.n_samples > (((int64_t)1 << 31) - 1))
-        return sg_refuse(who, ": n_frames * n_samples exceeds 2^31 - 1; split the batch", msg);
-    if (sg_max_frame(a.max_frame_rows, a.n_total) > ((int64_t)1 << 30))
-        return sg_refuse(who, ": a frame of more than 2^30 rows; split it", msg);
-    if (a.range6) {
-        for (int j = 0; j < 6; ++j)
-            if (a.range6[j] != a.range6[j]) return sg_refuse(who, ": a bound of the range is NaN; pass NULL for no range, or infinite bounds", msg);
-        for (int j = 0; j < 3; ++j)
-            if (!(a.range6[j] < a.range6[3 + j])) return sg_refuse(who, ": the range needs lo < hi on every axis", msg);
-    }
+    if (int rc = sg_check_batch_head(who, a, !a.out_index || !a.out_usable || !s.out_sector_offsets || !s.out_sector_count || (a.n_total > 0 && !a.rows), msg)) return rc;
+    if (int rc = sg_check_fps_domain(who, a, msg)) return rc;
     if (s.n_sectors < 1 || s.n_sectors > 16) return sg_refuse(who, ": n_sectors must lie in 1 .. 16", msg);
     if (s.rois) {
         if (s.n_rois < 1 || s.n_rois > 256) return sg_refuse(who, ": n_rois must lie in 1 .. 256", msg);
@@ -268,23 +315,13 @@ static inline int sg_check_fps_sectors_args(const SgFpsSectorsArgs &s, std::stri
         return sg_refuse(who, ": n_frames * ceil(max_frame_rows / 1024) exceeds 2^27 - 1; split the batch", msg);
     const size_t esz = a.dtype == 0 ? 4 : 8, F = (size_t)a.n_frames, elems = F * (size_t)a.n_samples, n = (size_t)a.n_total, S = (size_t)s.n_sectors;
     const size_t q = s.rois ? F * (size_t)s.n_rois : 0;
-    const struct { const void *p; size_t bytes; const char *name; } outs[8] = {
+    const SgOutSpan outs[8] = {
         {a.out_index, elems * 4, "d_out_index"}, {a.out_points, elems * (size_t)a.n_features * esz, "d_out_points"}, {a.out_dist, elems * esz, "d_out_dist"},
         {a.out_usable, F * 4, "d_out_usable"}, {s.out_sector_offsets, F * (S + 1) * 4, "d_out_sector_offsets"}, {s.out_sector_count, F * S * 4, "d_out_sector_count"},
         {s.out_sector_of, n, "d_out_sector_of"}, {s.out_reach2, q * 8, "d_out_reach2"}};
-    for (int i = 0; i < 8; ++i) {
-        const auto &o = outs[i];
-        if (sg_ranges_meet(o.p, o.bytes, a.keep_in, n))
-            return sg_refuse(who, (std::string(": ") + o.name + " overlaps d_keep_in; the mask is read while the samples are written: pass a buffer apart from it").c_str(), msg);
-        if (sg_ranges_meet(o.p, o.bytes, a.rows, n * 5 * esz))
-            return sg_refuse(who, (std::string(": ") + o.name + " overlaps d_rows; the rows are read while the samples are written: pass a buffer apart from them").c_str(), msg);
-        if (sg_ranges_meet(o.p, o.bytes, s.rois, q * (size_t)s.roi_features * esz))
-            return sg_refuse(who, (std::string(": ") + o.name + " overlaps d_rois; the rois are read while the samples are written: pass a buffer apart from them").c_str(), msg);
-        for (int j = 0; j < i; ++j)
-            if (sg_ranges_meet(o.p, o.bytes, outs[j].p, outs[j].bytes))
-                return sg_refuse(who, (std::string(": ") + o.name + " overlaps " + outs[j].name + "; every output needs memory of its own").c_str(), msg);
-    }
-    return 0;
+    const SgInSpan ins[3] = {{a.keep_in, n, "d_keep_in", "the mask is", "it"}, {a.rows, n * 5 * esz, "d_rows", "the rows are", "them"},
+                             {s.rois, q * (size_t)s.roi_features * esz, "d_rois", "the rois are", "them"}};
+    return sg_check_overlaps(who, outs, ins, "the samples are", true, msg);
 }
 
 // ---- snowgpu_ball_query_device ------------------------------------------------------------------------------------------------------------
@@ -309,13 +346,11 @@ struct SgBallArgs {
 };
 
 // 0, or SG_ARGS_INVALID with *msg.  As above, the order is part of the ABI.  *total = the sum of the samples where the call is accepted.
+// The outputs are not compared with each other.
 static inline int sg_check_ball_args(const SgBallArgs &a, int64_t *total, std::string *msg)
 {
     static const char *who = "snowgpu_ball_query_device";
-    if (a.n_frames <= 0 || a.n_total < 0 || !a.frame_off || !a.centres || !a.radii || !a.n_samples || !a.out_index || !a.out_count ||
-        (a.n_total > 0 && !a.rows) || (a.dtype != 0 && a.dtype != 1))
-        return sg_refuse(who, ": null pointer or bad dtype", msg);
-    if (a.n_total >= ((int64_t)1 << 31)) return sg_refuse("", "batch too large: split it below 2^31 rows", msg);
+    if (int rc = sg_check_batch_head(who, a, !a.centres || !a.radii || !a.n_samples || !a.out_index || !a.out_count || (a.n_total > 0 && !a.rows), msg)) return rc;
     if (a.n_features < 3 || a.n_features > 5) return sg_refuse(who, ": n_features must be 3, 4 or 5: the columns of a row that a neighbour carries", msg);
     if (a.centre_features < 3 || a.centre_features > 5) return sg_refuse(who, ": centre_features must be 3, 4 or 5: x, y, z first", msg);
     if (a.n_centres < 1) return sg_refuse(who, ": n_centres must be at least 1", msg);
@@ -328,27 +363,16 @@ static inline int sg_check_ball_args(const SgBallArgs &a, int64_t *total, std::s
     }
     if ((int64_t)a.n_frames * a.n_centres > (((int64_t)1 << 31) - 1) / S)      // (F K S <= 2^31 - 1, without the product of three)
         return sg_refuse(who, ": n_frames * n_centres * samples exceeds 2^31 - 1; split the batch", msg);
-    if (sg_max_frame(a.max_frame_rows, a.n_total) > ((int64_t)1 << 30))
-        return sg_refuse(who, ": a frame of more than 2^30 rows; split it", msg);
+    if (int rc = sg_check_frame(who, sg_max_frame(a.max_frame_rows, a.n_total), msg)) return rc;
     if ((int64_t)a.n_frames * (a.max_cells + 1) >= ((int64_t)1 << 31)) return sg_refuse(who, ": too many frames for the cell lists; split the batch", msg);
-    if (a.range6) {
-        for (int j = 0; j < 6; ++j)
-            if (a.range6[j] != a.range6[j]) return sg_refuse(who, ": a bound of the range is NaN; pass NULL for no range, or infinite bounds", msg);
-        for (int j = 0; j < 3; ++j)
-            if (!(a.range6[j] < a.range6[3 + j])) return sg_refuse(who, ": the range needs lo < hi on every axis", msg);
-    }
+    if (int rc = sg_check_range6(who, a.range6, msg)) return rc;
     const size_t esz = a.dtype == 0 ? 4 : 8, q = (size_t)a.n_frames * (size_t)a.n_centres, n = (size_t)a.n_total;
-    const struct { const void *p; size_t bytes; const char *name; } outs[3] = {
+    const SgOutSpan outs[3] = {
         {a.out_index, q * (size_t)S * 4, "d_out_index"}, {a.out_count, q * (size_t)a.n_radii * 4, "d_out_count"},
         {a.out_points, q * (size_t)S * (size_t)a.n_features * esz, "d_out_points"}};
-    for (const auto &o : outs) {
-        if (sg_ranges_meet(o.p, o.bytes, a.keep_in, n))
-            return sg_refuse(who, (std::string(": ") + o.name + " overlaps d_keep_in; the mask is read while the groups are written: pass a buffer apart from it").c_str(), msg);
-        if (sg_ranges_meet(o.p, o.bytes, a.rows, n * 5 * esz))
-            return sg_refuse(who, (std::string(": ") + o.name + " overlaps d_rows; the rows are read while the groups are written: pass a buffer apart from them").c_str(), msg);
-        if (sg_ranges_meet(o.p, o.bytes, a.centres, q * (size_t)a.centre_features * esz))
-            return sg_refuse(who, (std::string(": ") + o.name + " overlaps d_centres; the centres are read while the groups are written: pass a buffer apart from them").c_str(), msg);
-    }
+    const SgInSpan ins[3] = {{a.keep_in, n, "d_keep_in", "the mask is", "it"}, {a.rows, n * 5 * esz, "d_rows", "the rows are", "them"},
+                             {a.centres, q * (size_t)a.centre_features * esz, "d_centres", "the centres are", "them"}};
+    if (int rc = sg_check_overlaps(who, outs, ins, "the groups are", false, msg)) return rc;
     if (total) *total = S;
     return 0;
 }
@@ -371,21 +395,19 @@ struct SgRangeArgs {
     int32_t *out_count;               // or NULL
 };
 
-// 0, or SG_ARGS_INVALID with *msg.  As above, the order is part of the ABI.
+// 0, or SG_ARGS_INVALID with *msg.  As above, the order is part of the ABI: here the mode is asked for between the two halves of the head.
 static inline int sg_check_range_args(const SgRangeArgs &a, std::string *msg)
 {
     static const char *who = "snowgpu_range_image_device";
-    if (a.n_frames <= 0 || a.n_total < 0 || !a.frame_off || !a.out_image || !a.out_index || (a.n_total > 0 && (!a.rows || !a.out_pixel_of)) ||
-        (a.dtype != 0 && a.dtype != 1))
-        return sg_refuse(who, ": null pointer or bad dtype", msg);
+    if (int rc = sg_check_head(who, a.n_frames, a.dtype, a.n_total < 0 || !a.frame_off || !a.out_image || !a.out_index || (a.n_total > 0 && (!a.rows || !a.out_pixel_of)), msg))
+        return rc;
     if (!a.fov2 && !a.ring) return sg_refuse(who, ": needs fov2 (image rows by elevation) or d_ring (image rows by channel)", msg);
-    if (a.n_total >= ((int64_t)1 << 31)) return sg_refuse("", "batch too large: split it below 2^31 rows", msg);
+    if (int rc = sg_check_rows(a.n_total, msg)) return rc;
     if (a.n_features < 3 || a.n_features > 5) return sg_refuse(who, ": n_features must be 3, 4 or 5: the columns of a row that a pixel stores", msg);
     if (a.H < 1 || a.W < 1) return sg_refuse(who, ": height and width must be at least 1", msg);
     if ((int64_t)a.n_frames * a.H > (((int64_t)1 << 31) - 1) / a.W)       // (F H W <= 2^31 - 1, without the product of three)
         return sg_refuse(who, ": n_frames * height * width exceeds 2^31 - 1; split the batch", msg);
-    if (sg_max_frame(a.max_frame_rows, a.n_total) > ((int64_t)1 << 30))
-        return sg_refuse(who, ": a frame of more than 2^30 rows; split it", msg);
+    if (int rc = sg_check_frame(who, sg_max_frame(a.max_frame_rows, a.n_total), msg)) return rc;
     if (!a.ring) {
         const double half_pi = 1.5707963267948966;
         for (int j = 0; j < 2; ++j)
@@ -397,22 +419,12 @@ static inline int sg_check_range_args(const SgRangeArgs &a, std::string *msg)
         if (!(a.limits2[0] >= 0.0 && a.limits2[0] < a.limits2[1])) return sg_refuse(who, ": the range limits need 0 <= lo < hi", msg);
     }
     const size_t esz = a.dtype == 0 ? 4 : 8, px = (size_t)a.n_frames * (size_t)a.H * (size_t)a.W, n = (size_t)a.n_total;
-    const struct { const void *p; size_t bytes; const char *name; } outs[4] = {
+    const SgOutSpan outs[4] = {
         {a.out_image, px * (size_t)(1 + a.n_features) * esz, "d_out_image"}, {a.out_index, px * 4, "d_out_index"},
         {a.out_pixel_of, n * 4, "d_out_pixel_of"}, {a.out_count, px * 4, "d_out_count"}};
-    for (int i = 0; i < 4; ++i) {
-        const auto &o = outs[i];
-        if (sg_ranges_meet(o.p, o.bytes, a.keep_in, n))
-            return sg_refuse(who, (std::string(": ") + o.name + " overlaps d_keep_in; the mask is read while the image is written: pass a buffer apart from it").c_str(), msg);
-        if (sg_ranges_meet(o.p, o.bytes, a.rows, n * 5 * esz))
-            return sg_refuse(who, (std::string(": ") + o.name + " overlaps d_rows; the rows are read while the image is written: pass a buffer apart from them").c_str(), msg);
-        if (sg_ranges_meet(o.p, o.bytes, a.ring, n * 4))
-            return sg_refuse(who, (std::string(": ") + o.name + " overlaps d_ring; the channels are read while the image is written: pass a buffer apart from them").c_str(), msg);
-        for (int j = 0; j < i; ++j)
-            if (sg_ranges_meet(o.p, o.bytes, outs[j].p, outs[j].bytes))
-                return sg_refuse(who, (std::string(": ") + o.name + " overlaps " + outs[j].name + "; every output needs memory of its own").c_str(), msg);
-    }
-    return 0;
+    const SgInSpan ins[3] = {{a.keep_in, n, "d_keep_in", "the mask is", "it"}, {a.rows, n * 5 * esz, "d_rows", "the rows are", "them"},
+                             {a.ring, n * 4, "d_ring", "the channels are", "them"}};
+    return sg_check_overlaps(who, outs, ins, "the image is", true, msg);
 }
 
 // ---- snowgpu_nearest_centres_device -------------------------------------------------------------------------------------------------------
@@ -438,39 +450,19 @@ struct SgNnArgs {
 static inline int sg_check_nn_args(const SgNnArgs &a, std::string *msg)
 {
     static const char *who = "snowgpu_nearest_centres_device";
-    if (a.n_frames <= 0 || a.n_total < 0 || !a.frame_off || !a.centres || (a.n_total > 0 && (!a.rows || !a.out_index || !a.out_dist2)) ||
-        (a.dtype != 0 && a.dtype != 1))
-        return sg_refuse(who, ": null pointer or bad dtype", msg);
-    if (a.n_total >= ((int64_t)1 << 31)) return sg_refuse("", "batch too large: split it below 2^31 rows", msg);
+    if (int rc = sg_check_batch_head(who, a, !a.centres || (a.n_total > 0 && (!a.rows || !a.out_index || !a.out_dist2)), msg)) return rc;
     if (a.centre_features < 3 || a.centre_features > 5) return sg_refuse(who, ": centre_features must be 3, 4 or 5: x, y, z first", msg);
     if (a.n_centres < 1) return sg_refuse(who, ": n_centres must be at least 1", msg);
     if (a.k < 1 || a.k > 8) return sg_refuse(who, ": k must lie in 1 .. 8", msg);
     if ((int64_t)a.n_frames * a.n_centres > ((int64_t)1 << 31) - 1) return sg_refuse(who, ": n_frames * n_centres exceeds 2^31 - 1; split the batch", msg);
-    if (sg_max_frame(a.max_frame_rows, a.n_total) > ((int64_t)1 << 30))
-        return sg_refuse(who, ": a frame of more than 2^30 rows; split it", msg);
+    if (int rc = sg_check_frame(who, sg_max_frame(a.max_frame_rows, a.n_total), msg)) return rc;
     if ((int64_t)a.n_frames * (a.max_cells + 1) >= ((int64_t)1 << 31)) return sg_refuse(who, ": too many frames for the cell lists; split the batch", msg);
-    if (a.range6) {
-        for (int j = 0; j < 6; ++j)
-            if (a.range6[j] != a.range6[j]) return sg_refuse(who, ": a bound of the range is NaN; pass NULL for no range, or infinite bounds", msg);
-        for (int j = 0; j < 3; ++j)
-            if (!(a.range6[j] < a.range6[3 + j])) return sg_refuse(who, ": the range needs lo < hi on every axis", msg);
-    }
+    if (int rc = sg_check_range6(who, a.range6, msg)) return rc;
     const size_t esz = a.dtype == 0 ? 4 : 8, q = (size_t)a.n_frames * (size_t)a.n_centres, n = (size_t)a.n_total, slots = n * (size_t)a.k;
-    const struct { const void *p; size_t bytes; const char *name; } outs[3] = {
-        {a.out_index, slots * 4, "d_out_index"}, {a.out_dist2, slots * esz, "d_out_dist2"}, {a.out_weight, slots * esz, "d_out_weight"}};
-    for (int i = 0; i < 3; ++i) {
-        const auto &o = outs[i];
-        if (sg_ranges_meet(o.p, o.bytes, a.keep_in, n))
-            return sg_refuse(who, (std::string(": ") + o.name + " overlaps d_keep_in; the mask is read while the neighbours are written: pass a buffer apart from it").c_str(), msg);
-        if (sg_ranges_meet(o.p, o.bytes, a.rows, n * 5 * esz))
-            return sg_refuse(who, (std::string(": ") + o.name + " overlaps d_rows; the rows are read while the neighbours are written: pass a buffer apart from them").c_str(), msg);
-        if (sg_ranges_meet(o.p, o.bytes, a.centres, q * (size_t)a.centre_features * esz))
-            return sg_refuse(who, (std::string(": ") + o.name + " overlaps d_centres; the centres are read while the neighbours are written: pass a buffer apart from them").c_str(), msg);
-        for (int j = 0; j < i; ++j)
-            if (sg_ranges_meet(o.p, o.bytes, outs[j].p, outs[j].bytes))
-                return sg_refuse(who, (std::string(": ") + o.name + " overlaps " + outs[j].name + "; every output needs memory of its own").c_str(), msg);
-    }
-    return 0;
+    const SgOutSpan outs[3] = {{a.out_index, slots * 4, "d_out_index"}, {a.out_dist2, slots * esz, "d_out_dist2"}, {a.out_weight, slots * esz, "d_out_weight"}};
+    const SgInSpan ins[3] = {{a.keep_in, n, "d_keep_in", "the mask is", "it"}, {a.rows, n * 5 * esz, "d_rows", "the rows are", "them"},
+                             {a.centres, q * (size_t)a.centre_features * esz, "d_centres", "the centres are", "them"}};
+    return sg_check_overlaps(who, outs, ins, "the neighbours are", true, msg);
 }
 
 // ---- snowgpu_points_in_boxes_device -------------------------------------------------------------------------------------------------------
@@ -495,32 +487,17 @@ struct SgBoxArgs {
 static inline int sg_check_box_args(const SgBoxArgs &a, std::string *msg)
 {
     static const char *who = "snowgpu_points_in_boxes_device";
-    if (a.n_frames <= 0 || a.n_total < 0 || !a.frame_off || !a.boxes || (a.n_total > 0 && (!a.rows || !a.out_box_of)) || (a.dtype != 0 && a.dtype != 1))
-        return sg_refuse(who, ": null pointer or bad dtype", msg);
-    if (a.n_total >= ((int64_t)1 << 31)) return sg_refuse("", "batch too large: split it below 2^31 rows", msg);
+    if (int rc = sg_check_batch_head(who, a, !a.boxes || (a.n_total > 0 && (!a.rows || !a.out_box_of)), msg)) return rc;
     if (a.n_boxes < 1 || a.n_boxes > 256) return sg_refuse(who, ": n_boxes must lie in 1 .. 256", msg);
     if (a.box_features < 7 || a.box_features > 10) return sg_refuse(who, ": box_features must lie in 7 .. 10: cx, cy, cz, dx, dy, dz, heading first", msg);
     if ((int64_t)a.n_frames * a.n_boxes > ((int64_t)1 << 31) - 1) return sg_refuse(who, ": n_frames * n_boxes exceeds 2^31 - 1; split the batch", msg);
-    if (sg_max_frame(a.max_frame_rows, a.n_total) > ((int64_t)1 << 30))
-        return sg_refuse(who, ": a frame of more than 2^30 rows; split it", msg);
+    if (int rc = sg_check_frame(who, sg_max_frame(a.max_frame_rows, a.n_total), msg)) return rc;
     const size_t esz = a.dtype == 0 ? 4 : 8, q = (size_t)a.n_frames * (size_t)a.n_boxes, n = (size_t)a.n_total;
-    const struct { const void *p; size_t bytes; const char *name; } outs[4] = {
+    const SgOutSpan outs[4] = {
         {a.out_box_of, n * 4, "d_out_box_of"}, {a.out_count, q * 4, "d_out_count"}, {a.out_local, n * 3 * esz, "d_out_local"}, {a.out_pose, q * 16, "d_out_pose"}};
-    for (int i = 0; i < 4; ++i) {
-        const auto &o = outs[i];
-        if (sg_ranges_meet(o.p, o.bytes, a.keep_in, n))
-            return sg_refuse(who, (std::string(": ") + o.name + " overlaps d_keep_in; the mask is read while the labels are written: pass a buffer apart from it").c_str(), msg);
-        if (sg_ranges_meet(o.p, o.bytes, a.rows, n * 5 * esz))
-            return sg_refuse(who, (std::string(": ") + o.name + " overlaps d_rows; the rows are read while the labels are written: pass a buffer apart from them").c_str(), msg);
-        if (sg_ranges_meet(o.p, o.bytes, a.boxes, q * (size_t)a.box_features * esz))
-            return sg_refuse(who, (std::string(": ") + o.name + " overlaps d_boxes; the boxes are read while the labels are written: pass a buffer apart from them").c_str(), msg);
-        if (sg_ranges_meet(o.p, o.bytes, a.pose_in, q * 16))
-            return sg_refuse(who, (std::string(": ") + o.name + " overlaps d_pose_in; the pose is read while the labels are written: pass a buffer apart from it").c_str(), msg);
-        for (int j = 0; j < i; ++j)
-            if (sg_ranges_meet(o.p, o.bytes, outs[j].p, outs[j].bytes))
-                return sg_refuse(who, (std::string(": ") + o.name + " overlaps " + outs[j].name + "; every output needs memory of its own").c_str(), msg);
-    }
-    return 0;
+    const SgInSpan ins[4] = {{a.keep_in, n, "d_keep_in", "the mask is", "it"}, {a.rows, n * 5 * esz, "d_rows", "the rows are", "them"},
+                             {a.boxes, q * (size_t)a.box_features * esz, "d_boxes", "the boxes are", "them"}, {a.pose_in, q * 16, "d_pose_in", "the pose is", "it"}};
+    return sg_check_overlaps(who, outs, ins, "the labels are", true, msg);
 }
 
 // ---- snowgpu_roi_point_pool_device --------------------------------------------------------------------------------------------------------
@@ -548,39 +525,26 @@ struct SgRoiPoolArgs {
 // 0, or SG_ARGS_INVALID with *msg.  As above, the order is part of the ABI.
 static inline int sg_check_roipool_args(const SgRoiPoolArgs &a, std::string *msg)
 {
-    static const char *who = "snowgpu_roi_point_pool_device";
-    if (a.n_frames <= 0 || a.n_total < 0 || !a.frame_off || !a.rois || !a.out_index || !a.out_count || (a.n_total > 0 && !a.rows) || (a.dtype != 0 && a.dtype != 1))
-        return sg_refuse(who, ": null pointer or bad dtype", msg);
-    if (a.n_total >= ((int64_t)1 << 31)) return sg_refuse("", "batch too large: split it below 2^31 rows", msg);
+    static const char *who = "snowgpu_roi_point_pool_device", *read = "the mask, the rows, the rois and the pose are";
+    if (int rc = sg_check_batch_head(who, a, !a.rois || !a.out_index || !a.out_count || (a.n_total > 0 && !a.rows), msg)) return rc;
     if (a.n_rois < 1 || a.n_rois > 512) return sg_refuse(who, ": n_rois must lie in 1 .. 512", msg);
     if (a.roi_features < 7 || a.roi_features > 10) return sg_refuse(who, ": roi_features must lie in 7 .. 10: cx, cy, cz, dx, dy, dz, heading first", msg);
     if (a.n_samples < 1 || a.n_samples > 2048) return sg_refuse(who, ": n_samples must lie in 1 .. 2048", msg);
     if (a.num_features < 3 || a.num_features > 5) return sg_refuse(who, ": num_features must be 3, 4 or 5: the columns of a row that a roi stores", msg);
-    for (int j = 0; a.extra_width && j < 3; ++j)
-        if (!(a.extra_width[j] >= 0.0 && a.extra_width[j] <= 100.0))                         // (false for NaN)
-            return sg_refuse(who, ": every component of extra_width must be finite and lie in 0 .. 100", msg);
+    if (int rc = sg_check_extra_width(who, a.extra_width, msg)) return rc;
     if ((int64_t)a.n_frames * a.n_rois * a.n_samples * (a.num_features > 3 ? a.num_features : 3) > ((int64_t)1 << 31) - 1)
         return sg_refuse(who, ": n_frames * n_rois * n_samples * max(num_features, 3) exceeds 2^31 - 1; split the batch", msg);
     const int64_t longest = sg_max_frame(a.max_frame_rows, a.n_total);
-    if (longest > ((int64_t)1 << 30)) return sg_refuse(who, ": a frame of more than 2^30 rows; split it", msg);
+    if (int rc = sg_check_frame(who, longest, msg)) return rc;
     if ((int64_t)a.n_frames * a.n_rois * (longest / 512 + 1) > ((int64_t)1 << 31) - 1)    // (n_frames n_rois < 2^31 by the sample check)
         return sg_refuse(who, ": n_frames * n_rois * the 512-row runs of the longest frame exceeds 2^31 - 1; split the batch", msg);
     const size_t esz = a.dtype == 0 ? 4 : 8, q = (size_t)a.n_frames * (size_t)a.n_rois, n = (size_t)a.n_total, k = q * (size_t)a.n_samples;
-    const struct { const void *p; size_t bytes; const char *name; } outs[5] = {
+    const SgOutSpan outs[5] = {
         {a.out_index, k * 4, "d_out_index"}, {a.out_count, q * 4, "d_out_count"}, {a.out_points, k * (size_t)a.num_features * esz, "d_out_points"},
         {a.out_local, k * 3 * esz, "d_out_local"}, {a.out_pose, q * 16, "d_out_pose"}};
-    const struct { const void *p; size_t bytes; const char *name; } ins[4] = {
-        {a.keep_in, n, "d_keep_in"}, {a.rows, n * 5 * esz, "d_rows"}, {a.rois, q * (size_t)a.roi_features * esz, "d_rois"}, {a.pose_in, q * 16, "d_pose_in"}};
-    for (int i = 0; i < 5; ++i) {
-        const auto &o = outs[i];
-        for (int j = 0; j < 4; ++j)
-            if (sg_ranges_meet(o.p, o.bytes, ins[j].p, ins[j].bytes))
-                return sg_refuse(who, (std::string(": ") + o.name + " overlaps " + ins[j].name + "; the mask, the rows, the rois and the pose are read while the pool is written: pass a buffer apart from them").c_str(), msg);
-        for (int j = 0; j < i; ++j)
-            if (sg_ranges_meet(o.p, o.bytes, outs[j].p, outs[j].bytes))
-                return sg_refuse(who, (std::string(": ") + o.name + " overlaps " + outs[j].name + "; every output needs memory of its own").c_str(), msg);
-    }
-    return 0;
+    const SgInSpan ins[4] = {{a.keep_in, n, "d_keep_in", read, "them"}, {a.rows, n * 5 * esz, "d_rows", read, "them"},
+                             {a.rois, q * (size_t)a.roi_features * esz, "d_rois", read, "them"}, {a.pose_in, q * 16, "d_pose_in", read, "them"}};
+    return sg_check_overlaps(who, outs, ins, "the pool is", true, msg);
 }
 
 // ---- snowgpu_roi_voxel_pool_device --------------------------------------------------------------------------------------------------------
@@ -613,16 +577,11 @@ struct SgRoiAwareArgs {
 // 0, or SG_ARGS_INVALID with *msg.  As above, the order is part of the ABI.
 static inline int sg_check_roiaware_args(const SgRoiAwareArgs &a, std::string *msg)
 {
-    static const char *who = "snowgpu_roi_voxel_pool_device";
-    if (a.n_frames <= 0 || a.n_total < 0 || !a.frame_off || !a.rois || !a.out_size || !a.out_roi_count || !a.out_count || (a.n_total > 0 && !a.rows) ||
-        (a.dtype != 0 && a.dtype != 1))
-        return sg_refuse(who, ": null pointer or bad dtype", msg);
-    if (a.n_total >= ((int64_t)1 << 31)) return sg_refuse("", "batch too large: split it below 2^31 rows", msg);
+    static const char *who = "snowgpu_roi_voxel_pool_device", *read = "the mask, the rows, the rois, the pose and the features are";
+    if (int rc = sg_check_batch_head(who, a, !a.rois || !a.out_size || !a.out_roi_count || !a.out_count || (a.n_total > 0 && !a.rows), msg)) return rc;
     if (a.n_rois < 1 || a.n_rois > 512) return sg_refuse(who, ": n_rois must lie in 1 .. 512", msg);
     if (a.roi_features < 7 || a.roi_features > 10) return sg_refuse(who, ": roi_features must lie in 7 .. 10: cx, cy, cz, dx, dy, dz, heading first", msg);
-    for (int j = 0; a.extra_width && j < 3; ++j)
-        if (!(a.extra_width[j] >= 0.0 && a.extra_width[j] <= 100.0))                         // (false for NaN)
-            return sg_refuse(who, ": every component of extra_width must be finite and lie in 0 .. 100", msg);
+    if (int rc = sg_check_extra_width(who, a.extra_width, msg)) return rc;
     for (int j = 0; j < 3; ++j)
         if (a.out_size[j] < 1 || a.out_size[j] > 16) return sg_refuse(who, ": every component of out_size must lie in 1 .. 16", msg);
     if (a.max_points < 1 || a.max_points > 128) return sg_refuse(who, ": max_points must lie in 1 .. 128", msg);
@@ -637,26 +596,17 @@ static inline int sg_check_roiaware_args(const SgRoiAwareArgs &a, std::string *m
     if ((int64_t)a.n_frames * a.n_rois * a.roi_capacity > ((int64_t)1 << 31) - 1)
         return sg_refuse(who, ": n_frames * n_rois * roi_capacity exceeds 2^31 - 1; split the batch or lower the capacity", msg);
     const int64_t longest = sg_max_frame(a.max_frame_rows, a.n_total);
-    if (longest > ((int64_t)1 << 30)) return sg_refuse(who, ": a frame of more than 2^30 rows; split it", msg);
+    if (int rc = sg_check_frame(who, longest, msg)) return rc;
     if ((int64_t)a.n_frames * a.n_rois * (longest / 512 + 1) > ((int64_t)1 << 31) - 1)    // (n_frames n_rois < 2^31 by the element check)
         return sg_refuse(who, ": n_frames * n_rois * the 512-row runs of the longest frame exceeds 2^31 - 1; split the batch", msg);
     const size_t esz = a.dtype == 0 ? 4 : 8, q = (size_t)a.n_frames * (size_t)a.n_rois, n = (size_t)a.n_total, v = q * (size_t)G, k = v * (size_t)Cf;
-    const struct { const void *p; size_t bytes; const char *name; } outs[7] = {
+    const SgOutSpan outs[7] = {
         {a.out_roi_count, q * 4, "d_out_roi_count"}, {a.out_count, v * 4, "d_out_count"}, {a.out_index, v * (size_t)a.max_points * 4, "d_out_index"},
         {a.out_max, k * 4, "d_out_max"}, {a.out_argmax, k * 4, "d_out_argmax"}, {a.out_avg, k * 4, "d_out_avg"}, {a.out_pose, q * 16, "d_out_pose"}};
-    const struct { const void *p; size_t bytes; const char *name; } ins[5] = {
-        {a.keep_in, n, "d_keep_in"}, {a.rows, n * 5 * esz, "d_rows"}, {a.rois, q * (size_t)a.roi_features * esz, "d_rois"}, {a.pose_in, q * 16, "d_pose_in"},
-        {a.features, n * (size_t)Cf * 4, "d_features"}};
-    for (int i = 0; i < 7; ++i) {
-        const auto &o = outs[i];
-        for (int j = 0; j < 5; ++j)
-            if (sg_ranges_meet(o.p, o.bytes, ins[j].p, ins[j].bytes))
-                return sg_refuse(who, (std::string(": ") + o.name + " overlaps " + ins[j].name + "; the mask, the rows, the rois, the pose and the features are read while the voxels are written: pass a buffer apart from them").c_str(), msg);
-        for (int j = 0; j < i; ++j)
-            if (sg_ranges_meet(o.p, o.bytes, outs[j].p, outs[j].bytes))
-                return sg_refuse(who, (std::string(": ") + o.name + " overlaps " + outs[j].name + "; every output needs memory of its own").c_str(), msg);
-    }
-    return 0;
+    const SgInSpan ins[5] = {{a.keep_in, n, "d_keep_in", read, "them"}, {a.rows, n * 5 * esz, "d_rows", read, "them"},
+                             {a.rois, q * (size_t)a.roi_features * esz, "d_rois", read, "them"}, {a.pose_in, q * 16, "d_pose_in", read, "them"},
+                             {a.features, n * (size_t)Cf * 4, "d_features", read, "them"}};
+    return sg_check_overlaps(who, outs, ins, "the voxels are", true, msg);
 }
 
 // ---- snowgpu_boxes_iou_device -------------------------------------------------------------------------------------------------------------
@@ -678,8 +628,8 @@ struct SgIouArgs {
 // 0, or SG_ARGS_INVALID with *msg.  As above, the order is part of the ABI.
 static inline int sg_check_iou_args(const SgIouArgs &a, std::string *msg)
 {
-    static const char *who = "snowgpu_boxes_iou_device";
-    if (a.n_frames <= 0 || !a.boxes_a || !a.boxes_b || (a.dtype != 0 && a.dtype != 1)) return sg_refuse(who, ": null pointer or bad dtype", msg);
+    static const char *who = "snowgpu_boxes_iou_device", *read = "the boxes and poses are";
+    if (int rc = sg_check_head(who, a.n_frames, a.dtype, !a.boxes_a || !a.boxes_b, msg)) return rc;
     if (a.mode != 0 && a.mode != 1) return sg_refuse(who, ": mode must be 0 (BEV) or 1 (3D)", msg);
     if (!a.out_iou && !a.out_best && !a.out_best_iou) return sg_refuse(who, ": no output: pass d_out_iou, d_out_best or d_out_best_iou", msg);
     if (a.n_a < 1 || a.n_a > 9216 || a.n_b < 1 || a.n_b > 9216) return sg_refuse(who, ": the boxes per frame must lie in 1 .. 9216 on either side", msg);
@@ -687,21 +637,10 @@ static inline int sg_check_iou_args(const SgIouArgs &a, std::string *msg)
         return sg_refuse(who, ": box_features must lie in 7 .. 10: cx, cy, cz, dx, dy, dz, heading first", msg);
     if ((int64_t)a.n_frames * a.n_a * a.n_b > ((int64_t)1 << 31) - 1) return sg_refuse(who, ": n_frames * M * B exceeds 2^31 - 1; split the batch", msg);
     const size_t esz = a.dtype == 0 ? 4 : 8, qa = (size_t)a.n_frames * (size_t)a.n_a, qb = (size_t)a.n_frames * (size_t)a.n_b;
-    const struct { const void *p; size_t bytes; const char *name; } outs[3] = {
-        {a.out_iou, qa * (size_t)a.n_b * esz, "d_out_iou"}, {a.out_best, qa * 4, "d_out_best"}, {a.out_best_iou, qa * esz, "d_out_best_iou"}};
-    const struct { const void *p; size_t bytes; const char *name; } ins[4] = {
-        {a.boxes_a, qa * (size_t)a.a_features * esz, "d_boxes_a"}, {a.boxes_b, qb * (size_t)a.b_features * esz, "d_boxes_b"},
-        {a.pose_a, qa * 16, "d_pose_a"}, {a.pose_b, qb * 16, "d_pose_b"}};
-    for (int i = 0; i < 3; ++i) {
-        const auto &o = outs[i];
-        for (int k = 0; k < 4; ++k)
-            if (sg_ranges_meet(o.p, o.bytes, ins[k].p, ins[k].bytes))
-                return sg_refuse(who, (std::string(": ") + o.name + " overlaps " + ins[k].name + "; the boxes and poses are read while the overlaps are written: pass a buffer apart from them").c_str(), msg);
-        for (int j = 0; j < i; ++j)
-            if (sg_ranges_meet(o.p, o.bytes, outs[j].p, outs[j].bytes))
-                return sg_refuse(who, (std::string(": ") + o.name + " overlaps " + outs[j].name + "; every output needs memory of its own").c_str(), msg);
-    }
-    return 0;
+    const SgOutSpan outs[3] = {{a.out_iou, qa * (size_t)a.n_b * esz, "d_out_iou"}, {a.out_best, qa * 4, "d_out_best"}, {a.out_best_iou, qa * esz, "d_out_best_iou"}};
+    const SgInSpan ins[4] = {{a.boxes_a, qa * (size_t)a.a_features * esz, "d_boxes_a", read, "them"}, {a.boxes_b, qb * (size_t)a.b_features * esz, "d_boxes_b", read, "them"},
+                             {a.pose_a, qa * 16, "d_pose_a", read, "them"}, {a.pose_b, qb * 16, "d_pose_b", read, "them"}};
+    return sg_check_overlaps(who, outs, ins, "the overlaps are", true, msg);
 }
 
 // ---- snowgpu_nms_device -------------------------------------------------------------------------------------------------------------------
@@ -722,9 +661,8 @@ struct SgNmsArgs {
 
 static inline int sg_check_nms_args(const SgNmsArgs &a, std::string *msg)
 {
-    static const char *who = "snowgpu_nms_device";
-    if (a.n_frames <= 0 || !a.boxes || !a.scores || !a.out_index || !a.out_count || (a.dtype != 0 && a.dtype != 1))
-        return sg_refuse(who, ": null pointer or bad dtype", msg);
+    static const char *who = "snowgpu_nms_device", *read = "the boxes, scores and pose are";
+    if (int rc = sg_check_head(who, a.n_frames, a.dtype, !a.boxes || !a.scores || !a.out_index || !a.out_count, msg)) return rc;
     if (a.mode != 0 && a.mode != 1) return sg_refuse(who, ": mode must be 0 (BEV) or 1 (3D)", msg);
     if (a.n_boxes < 1 || a.n_boxes > 9216) return sg_refuse(who, ": n_boxes must lie in 1 .. 9216", msg);
     if (a.box_features < 7 || a.box_features > 10) return sg_refuse(who, ": box_features must lie in 7 .. 10: cx, cy, cz, dx, dy, dz, heading first", msg);
@@ -732,21 +670,12 @@ static inline int sg_check_nms_args(const SgNmsArgs &a, std::string *msg)
     if (a.iou_thresh != a.iou_thresh || a.score_thresh != a.score_thresh) return sg_refuse(who, ": a threshold is NaN", msg);
     if ((int64_t)a.n_frames * a.n_boxes > ((int64_t)1 << 31) - 1) return sg_refuse(who, ": n_frames * n_boxes exceeds 2^31 - 1; split the batch", msg);
     const size_t esz = a.dtype == 0 ? 4 : 8, q = (size_t)a.n_frames * (size_t)a.n_boxes, k = (size_t)a.n_frames * (size_t)a.post_max;
-    const struct { const void *p; size_t bytes; const char *name; } outs[5] = {
+    const SgOutSpan outs[5] = {
         {a.out_index, k * 4, "d_out_index"}, {a.out_count, (size_t)a.n_frames * 4, "d_out_count"}, {a.out_boxes, k * (size_t)a.box_features * esz, "d_out_boxes"},
         {a.out_scores, k * esz, "d_out_scores"}, {a.out_kept, q, "d_out_kept"}};
-    const struct { const void *p; size_t bytes; const char *name; } ins[3] = {
-        {a.boxes, q * (size_t)a.box_features * esz, "d_boxes"}, {a.scores, q * esz, "d_scores"}, {a.pose_in, q * 16, "d_pose_in"}};
-    for (int i = 0; i < 5; ++i) {
-        const auto &o = outs[i];
-        for (int j = 0; j < 3; ++j)
-            if (sg_ranges_meet(o.p, o.bytes, ins[j].p, ins[j].bytes))
-                return sg_refuse(who, (std::string(": ") + o.name + " overlaps " + ins[j].name + "; the boxes, scores and pose are read while the keep list is written: pass a buffer apart from them").c_str(), msg);
-        for (int j = 0; j < i; ++j)
-            if (sg_ranges_meet(o.p, o.bytes, outs[j].p, outs[j].bytes))
-                return sg_refuse(who, (std::string(": ") + o.name + " overlaps " + outs[j].name + "; every output needs memory of its own").c_str(), msg);
-    }
-    return 0;
+    const SgInSpan ins[3] = {{a.boxes, q * (size_t)a.box_features * esz, "d_boxes", read, "them"}, {a.scores, q * esz, "d_scores", read, "them"},
+                             {a.pose_in, q * 16, "d_pose_in", read, "them"}};
+    return sg_check_overlaps(who, outs, ins, "the keep list is", true, msg);
 }
 
 // ---- snowgpu_sample_rois_device -----------------------------------------------------------------------------------------------------------
@@ -784,10 +713,10 @@ struct SgTargetsArgs {
 // 0, or SG_ARGS_INVALID with *msg.  As above, the order is part of the ABI.
 static inline int sg_check_targets_args(const SgTargetsArgs &a, std::string *msg)
 {
-    static const char *who = "snowgpu_sample_rois_device";
-    if (a.n_frames <= 0 || !a.rois || !a.overlap || !a.assignment || !a.gt_boxes || !a.cfg || !a.step || !a.out_index || !a.out_rois || !a.out_roi_iou ||
-        !a.out_gt_index || !a.out_gt_of_rois || !a.out_reg_valid || !a.out_cls_label || !a.out_segments || !a.out_class_count || (a.dtype != 0 && a.dtype != 1))
-        return sg_refuse(who, ": null pointer or bad dtype", msg);
+    static const char *who = "snowgpu_sample_rois_device", *read = "the rois, overlaps, assignments, gt boxes, step and pose are";
+    if (int rc = sg_check_head(who, a.n_frames, a.dtype, !a.rois || !a.overlap || !a.assignment || !a.gt_boxes || !a.cfg || !a.step || !a.out_index || !a.out_rois ||
+                                   !a.out_roi_iou || !a.out_gt_index || !a.out_gt_of_rois || !a.out_reg_valid || !a.out_cls_label || !a.out_segments || !a.out_class_count, msg))
+        return rc;
     const SgSamplerCfg &c = *a.cfg;
     if (a.n_rois < 1 || a.n_rois > 9216 || a.n_gt < 1 || a.n_gt > 9216) return sg_refuse(who, ": n_rois and n_gt must lie in 1 .. 9216", msg);
     if (a.roi_features < 7 || a.roi_features > 10 || a.gt_features < 7 || a.gt_features > 10)
@@ -804,24 +733,15 @@ static inline int sg_check_targets_args(const SgTargetsArgs &a, std::string *msg
         return sg_refuse(who, ": n_frames * roi_per_image * max(roi_features, gt_features) exceeds 2^31 - 1; split the batch", msg);
     const size_t esz = a.dtype == 0 ? 4 : 8, q = (size_t)a.n_frames * (size_t)a.n_rois, g = (size_t)a.n_frames * (size_t)a.n_gt,
                  k = (size_t)a.n_frames * (size_t)c.roi_per_image;
-    const struct { const void *p; size_t bytes; const char *name; } outs[11] = {
+    const SgOutSpan outs[11] = {
         {a.out_index, k * 4, "d_out_index"}, {a.out_rois, k * (size_t)a.roi_features * esz, "d_out_rois"}, {a.out_roi_iou, k * esz, "d_out_roi_iou"},
         {a.out_gt_index, k * 4, "d_out_gt_index"}, {a.out_gt_of_rois, k * (size_t)a.gt_features * esz, "d_out_gt_of_rois"}, {a.out_reg_valid, k, "d_out_reg_valid"},
         {a.out_cls_label, k * esz, "d_out_cls_label"}, {a.out_segments, (size_t)a.n_frames * 12, "d_out_segments"},
         {a.out_class_count, (size_t)a.n_frames * 12, "d_out_class_count"}, {a.out_pose, k * 16, "d_out_pose"}, {a.out_gt_local, k * 7 * esz, "d_out_gt_local"}};
-    const struct { const void *p; size_t bytes; const char *name; } ins[6] = {
-        {a.rois, q * (size_t)a.roi_features * esz, "d_rois"}, {a.overlap, q * esz, "d_overlap"}, {a.assignment, q * 4, "d_assignment"},
-        {a.gt_boxes, g * (size_t)a.gt_features * esz, "d_gt_boxes"}, {a.step, 8, "d_step"}, {a.pose_in, q * 16, "d_pose"}};
-    for (int i = 0; i < 11; ++i) {
-        const auto &o = outs[i];
-        for (int j = 0; j < 6; ++j)
-            if (sg_ranges_meet(o.p, o.bytes, ins[j].p, ins[j].bytes))
-                return sg_refuse(who, (std::string(": ") + o.name + " overlaps " + ins[j].name + "; the rois, overlaps, assignments, gt boxes, step and pose are read while the targets are written: pass a buffer apart from them").c_str(), msg);
-        for (int j = 0; j < i; ++j)
-            if (sg_ranges_meet(o.p, o.bytes, outs[j].p, outs[j].bytes))
-                return sg_refuse(who, (std::string(": ") + o.name + " overlaps " + outs[j].name + "; every output needs memory of its own").c_str(), msg);
-    }
-    return 0;
+    const SgInSpan ins[6] = {{a.rois, q * (size_t)a.roi_features * esz, "d_rois", read, "them"}, {a.overlap, q * esz, "d_overlap", read, "them"},
+                             {a.assignment, q * 4, "d_assignment", read, "them"}, {a.gt_boxes, g * (size_t)a.gt_features * esz, "d_gt_boxes", read, "them"},
+                             {a.step, 8, "d_step", read, "them"}, {a.pose_in, q * 16, "d_pose", read, "them"}};
+    return sg_check_overlaps(who, outs, ins, "the targets are", true, msg);
 }
 
 // ---- snowgpu_assign_anchors_device --------------------------------------------------------------------------------------------------------
@@ -844,10 +764,10 @@ struct SgAnchorsArgs {
 // 0, or SG_ARGS_INVALID with *msg.  As above, the order is part of the ABI.
 static inline int sg_check_anchors_args(const SgAnchorsArgs &a, std::string *msg)
 {
-    static const char *who = "snowgpu_assign_anchors_device";
-    if (a.n_frames <= 0 || !a.anchors || !a.anchor_class || !a.gt_boxes || !a.matched || !a.unmatched || !a.out_label || !a.out_gt_index || !a.out_count ||
-        !a.out_gt_count || (a.dtype != 0 && a.dtype != 1))
-        return sg_refuse(who, ": null pointer or bad dtype", msg);
+    static const char *who = "snowgpu_assign_anchors_device", *read = "the anchors, their classes and the gt boxes are";
+    if (int rc = sg_check_head(who, a.n_frames, a.dtype, !a.anchors || !a.anchor_class || !a.gt_boxes || !a.matched || !a.unmatched || !a.out_label || !a.out_gt_index ||
+                                   !a.out_count || !a.out_gt_count, msg))
+        return rc;
     if (a.n_anchors < 1) return sg_refuse(who, ": n_anchors must be at least 1", msg);
     if (a.n_gt < 1 || a.n_gt > 256) return sg_refuse(who, ": n_gt must lie in 1 .. 256", msg);
     if (a.anchor_features < 7 || a.anchor_features > 10)
@@ -860,22 +780,12 @@ static inline int sg_check_anchors_args(const SgAnchorsArgs &a, std::string *msg
             return sg_refuse(who, ": every class needs 0 < unmatched <= matched <= 1", msg);
     if ((int64_t)a.n_frames * a.n_anchors > ((int64_t)1 << 31) - 1) return sg_refuse(who, ": n_frames * n_anchors exceeds 2^31 - 1; split the batch", msg);
     const size_t esz = a.dtype == 0 ? 4 : 8, q = (size_t)a.n_frames * (size_t)a.n_anchors, g = (size_t)a.n_frames * (size_t)a.n_gt;
-    const struct { const void *p; size_t bytes; const char *name; } outs[5] = {
+    const SgOutSpan outs[5] = {
         {a.out_label, q * 4, "d_out_label"}, {a.out_gt_index, q * 4, "d_out_gt_index"}, {a.out_count, (size_t)a.n_frames * 12, "d_out_count"},
         {a.out_gt_count, g * 4, "d_out_gt_count"}, {a.out_iou, q * esz, "d_out_iou"}};
-    const struct { const void *p; size_t bytes; const char *name; } ins[3] = {
-        {a.anchors, (size_t)a.n_anchors * (size_t)a.anchor_features * esz, "d_anchors"}, {a.anchor_class, (size_t)a.n_anchors * 4, "d_anchor_class"},
-        {a.gt_boxes, g * (size_t)a.gt_features * esz, "d_gt_boxes"}};
-    for (int i = 0; i < 5; ++i) {
-        const auto &o = outs[i];
-        for (int j = 0; j < 3; ++j)
-            if (sg_ranges_meet(o.p, o.bytes, ins[j].p, ins[j].bytes))
-                return sg_refuse(who, (std::string(": ") + o.name + " overlaps " + ins[j].name + "; the anchors, their classes and the gt boxes are read while the targets are written: pass a buffer apart from them").c_str(), msg);
-        for (int j = 0; j < i; ++j)
-            if (sg_ranges_meet(o.p, o.bytes, outs[j].p, outs[j].bytes))
-                return sg_refuse(who, (std::string(": ") + o.name + " overlaps " + outs[j].name + "; every output needs memory of its own").c_str(), msg);
-    }
-    return 0;
+    const SgInSpan ins[3] = {{a.anchors, (size_t)a.n_anchors * (size_t)a.anchor_features * esz, "d_anchors", read, "them"},
+                             {a.anchor_class, (size_t)a.n_anchors * 4, "d_anchor_class", read, "them"}, {a.gt_boxes, g * (size_t)a.gt_features * esz, "d_gt_boxes", read, "them"}};
+    return sg_check_overlaps(who, outs, ins, "the targets are", true, msg);
 }
 
 // 0, or SG_ARGS_INVALID with *msg (built on this path only).  The order is part of the ABI: it decides which message a doubly wrong call gets.

@@ -1,7 +1,9 @@
-// sg_host.h -- what the four host translation units of libsnowgpu.so share: the context, the description of one batch on the
+// sg_host.h -- what the five host translation units of libsnowgpu.so share: the context, the description of one batch on the
 // device, the error macros, the guard of the host-pointer entries and the functions the parts call in each other.
 //   snowgpu_api.cpp    context, settings, tables, sampler, profile hooks
-//   snowgpu_device.cpp every entry that takes device pointers (their arguments and refusals: sg_device_args.h)
+//   snowgpu_device.cpp the *_batch_device* entries, the plane estimate, the FOV mask, the weather draw (device pointers; arguments and
+//                      refusals: sg_device_args.h)
+//   snowgpu_stages.cpp the stage entries on device pointers, from the outlier filter to the anchor targets (likewise sg_device_args.h)
 //   snowgpu_batch.cpp  the launch sequence of one batch (run_batch)
 //   snowgpu_host.cpp   every entry that takes host pointers (uploads, the chunk pipeline, downloads)
 #pragma once

@@ -1,6 +1,7 @@
 // snowgpu_api.cpp -- the C ABI of libsnowgpu.so (include/snowgpu.h) as far as it takes no rows: context, streams, settings, lasers,
 // table filing, the sampler and the profile hooks.  Host-side C++; the launch sequence of a batch is snowgpu_batch.cpp, the
-// device-pointer entries snowgpu_device.cpp, the host-pointer entries snowgpu_host.cpp, every kernel lives in a .hip file.
+// device-pointer entries snowgpu_device.cpp (batches) and snowgpu_stages.cpp (stages), the host-pointer entries snowgpu_host.cpp, every
+// kernel lives in a .hip file.
 #include <dlfcn.h>
 
 #include "sg_host.h"

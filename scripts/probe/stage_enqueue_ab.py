@@ -6,7 +6,7 @@ the host's time per call.  Per stage: five warm-up calls, then the wall clock ar
 after them.
 
     fov_keep dror_keep voxelize sample_keypoints sample_keypoints_sectors ball_query range_image nearest_keypoints points_in_boxes
-    boxes_iou nms
+    boxes_iou nms roi_point_pool roi_voxel_pool sample_rois assign_anchors
 
 `--tree DIR` imports the package of another checkout (an A/B of two trees: one process per run, the trees alternating).  Prints one JSON
 line: milliseconds per call by stage.
@@ -48,6 +48,14 @@ def stages(torch, T):
     lab = T.BoxLabelBatch.empty(offsets, 2)
     iou = T.IouBatch.empty(2, 2, 2)
     kept = T.NmsBatch.empty(2, 2, 2)
+    pooled = T.RoiPointBatch.empty(2, 2, 16)
+    voxels = T.RoiVoxelBatch.empty(2, 2, 2, 8)
+    best = (torch.tensor([[0.9, 0.2]] * 2, device=dev), torch.tensor([[0, 1]] * 2, dtype=torch.int32, device=dev))
+    step = torch.zeros(1, dtype=torch.int64, device=dev)
+    targets = T.RoiTargetBatch.empty(2, 8, 7, 7)
+    anchors, anchor_class = boxes[0].contiguous(), torch.tensor([1, 2], dtype=torch.int32, device=dev)
+    gt = torch.cat([boxes, torch.tensor([[[1.0], [2.0]]] * 2, device=dev)], dim=2).contiguous()
+    labels = T.AnchorTargetBatch.empty(2, 2, 2)
     return {
         "fov_keep": lambda: T.fov_keep(fr, calib),
         "dror_keep": lambda: T.dror_keep(fr, out=mask),
@@ -60,6 +68,10 @@ def stages(torch, T):
         "points_in_boxes": lambda: T.points_in_boxes(fr, boxes, out=lab),
         "boxes_iou": lambda: T.boxes_iou(boxes, boxes, out=iou),
         "nms": lambda: T.nms(boxes, scores, 0.5, post_max=2, out=kept),
+        "roi_point_pool": lambda: T.roi_point_pool(fr, boxes, 16, out=pooled),
+        "roi_voxel_pool": lambda: T.roi_voxel_pool(fr, boxes, 2, 8, out=voxels),
+        "sample_rois": lambda: T.sample_rois(boxes, boxes, best, step=step, roi_per_image=8, out=targets),
+        "assign_anchors": lambda: T.assign_anchors(anchors, anchor_class, gt, out=labels),
     }
 
 

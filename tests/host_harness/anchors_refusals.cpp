@@ -92,6 +92,15 @@ int main()
         {"gt_count_is_count", [](SgAnchorsArgs &a) { a.out_gt_count = g_count; }},
         {"iou_overlaps_gt_count", [](SgAnchorsArgs &a) { a.out_iou = g_gt_count + 5; }},
         {"iou_is_gt_index", [](SgAnchorsArgs &a) { a.out_iou = g_gt_index; }},
+        // two defects, of checks that stand next to each other: the earlier check's message
+        {"null_anchors_and_anchors_0", [](SgAnchorsArgs &a) { a.anchors = nullptr; a.n_anchors = 0; }},
+        {"anchors_0_and_gt_0", [](SgAnchorsArgs &a) { a.n_anchors = 0; a.n_gt = 0; }},
+        {"gt_0_and_anchor_features_6", [](SgAnchorsArgs &a) { a.n_gt = 0; a.anchor_features = 6; }},
+        {"anchor_features_6_and_gt_features_7", [](SgAnchorsArgs &a) { a.anchor_features = 6; a.gt_features = 7; }},
+        {"gt_features_7_and_classes_0", [](SgAnchorsArgs &a) { a.gt_features = 7; a.n_classes = 0; }},
+        {"classes_17_and_unmatched_0", [](SgAnchorsArgs &a) { a.n_classes = 17; g_unmatched[1] = 0.0; }},
+        {"unmatched_0_and_elements_at_2p31", [](SgAnchorsArgs &a) { g_unmatched[1] = 0.0; a.n_frames = 2; a.n_anchors = 1073741824; bare(a); }},
+        {"elements_at_2p31_and_label_is_anchors", [](SgAnchorsArgs &a) { a.n_frames = 2; a.n_anchors = 1073741824; bare(a); a.out_label = (int32_t *)a.anchors; }},
     };
     for (const auto &cs : cases) {
         SgAnchorsArgs a;

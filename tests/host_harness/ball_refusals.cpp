@@ -105,6 +105,22 @@ int main()
         {"index_behind_centres", [](Call &k) { k.a.out_index = (int32_t *)g_centres + 18; }},
         {"count_is_centres", [](Call &k) { k.a.out_count = (int32_t *)g_centres; }},
         {"points_overlap_centres", [](Call &k) { k.a.centres = g_points + 100; }},
+        // two defects, of checks that stand next to each other: the earlier check's message
+        {"null_and_rows_2p31", [](Call &k) { k.a.frame_off = nullptr; k.a.n_total = (int64_t)1 << 31; k.a.keep_in = nullptr; }},
+        {"rows_2p31_and_features_2", [](Call &k) { k.a.n_total = (int64_t)1 << 31; k.a.keep_in = nullptr; k.a.n_features = 2; }},
+        {"features_2_and_centre_features_2", [](Call &k) { k.a.n_features = 2; k.a.centre_features = 2; }},
+        {"centre_features_2_and_centres_0", [](Call &k) { k.a.centre_features = 2; k.a.n_centres = 0; }},
+        {"centres_0_and_radii_0", [](Call &k) { k.a.n_centres = 0; k.a.n_radii = 0; }},
+        {"radii_5_and_radius_0", [](Call &k) { k.a.n_radii = 5; k.radii[0] = 0.0; }},
+        {"radius_0_and_samples_0", [](Call &k) { k.radii[1] = 0.0; k.samples[1] = 0; }},                  // (of one pair: the radius is looked at first)
+        // (no samples_0 with slots_2p31: the product check divides by the sum of the samples, which the sample check has to let through)
+        {"slots_2p31_and_frame_2p30_plus_1_rows", [](Call &k) { k.a.n_frames = 1; k.a.n_centres = 1 << 30; k.a.n_radii = 1; k.samples[0] = 2; bare(k); k.a.n_total = ((int64_t)1 << 30) + 1; k.a.max_frame_rows = 0; k.a.rows = g_rows; }},
+        {"frame_2p30_plus_1_rows_and_cell_lists_too_large", [](Call &k) { k.a.n_frames = 26215; k.a.max_cells = 81920; k.a.n_centres = 1; bare(k); k.a.n_total = ((int64_t)1 << 30) + 1; k.a.max_frame_rows = 0; k.a.rows = g_rows; }},
+        {"cell_lists_too_large_and_range_nan", [&](Call &k) { k.a.n_frames = 26215; k.a.max_cells = 81920; k.a.n_centres = 1; bare(k); k.range6[5] = nan; }},
+        {"range_nan_and_range_reversed", [&](Call &k) { k.range6[5] = nan; k.range6[4] = -3.0; }},
+        {"range_reversed_and_index_is_keep_in", [](Call &k) { k.range6[4] = -3.0; k.a.out_index = (int32_t *)g_keep; }},
+        // The current contract: the outputs are not compared with each other.  Refusing this call is a change of behaviour, not a tidying.
+        {"count_is_index", [](Call &k) { k.a.out_count = k.a.out_index; }},
     };
     for (const auto &cs : cases) {
         Call k;

@@ -90,6 +90,13 @@ int main()
         {"pose_overlaps_box_of", [](SgBoxArgs &a) { a.out_box_of = (int32_t *)g_pose + 10; }},
         {"pose_overlaps_count", [](SgBoxArgs &a) { a.out_count = (int32_t *)g_pose + 23; }},
         {"pose_is_local", [](SgBoxArgs &a) { a.out_pose = (double *)g_local; }},
+        // two defects, of checks that stand next to each other: the earlier check's message
+        {"null_and_rows_2p31", [](SgBoxArgs &a) { a.frame_off = nullptr; a.n_total = (int64_t)1 << 31; a.keep_in = nullptr; }},
+        {"rows_2p31_and_boxes_0", [](SgBoxArgs &a) { a.n_total = (int64_t)1 << 31; a.keep_in = nullptr; a.n_boxes = 0; }},
+        {"boxes_0_and_box_features_6", [](SgBoxArgs &a) { a.n_boxes = 0; a.box_features = 6; }},
+        {"box_features_6_and_slots_2p31", [](SgBoxArgs &a) { a.box_features = 6; a.n_frames = 8388608; a.n_boxes = 256; bare(a); }},
+        {"slots_2p31_and_frame_2p30_plus_1_rows", [](SgBoxArgs &a) { a.n_frames = 8388608; a.n_boxes = 256; a.n_total = ((int64_t)1 << 30) + 1; a.max_frame_rows = 0; }},
+        {"frame_2p30_plus_1_rows_and_box_of_is_keep_in", [](SgBoxArgs &a) { a.n_total = ((int64_t)1 << 30) + 1; a.max_frame_rows = 0; a.out_box_of = (int32_t *)g_keep; }},
     };
     for (const auto &cs : cases) {
         SgBoxArgs a;

@@ -76,6 +76,17 @@ int main()
         {"index_behind_rows", [](Call &k) { k.a.out_index = (int32_t *)g_rows + 40; }},
         {"points_are_rows", [](Call &k) { k.a.out_points = g_rows; }},
         {"dist_overlaps_rows", [](Call &k) { k.a.rows = g_dist + 5; k.a.n_total = 1; }},              // one row: bytes 20 .. 39 of g_dist
+        // two defects, of checks that stand next to each other: the earlier check's message
+        {"null_and_rows_2p31", [](Call &k) { k.a.frame_off = nullptr; k.a.n_total = (int64_t)1 << 31; k.a.keep_in = nullptr; }},
+        {"rows_2p31_and_features_2", [](Call &k) { k.a.n_total = (int64_t)1 << 31; k.a.keep_in = nullptr; k.a.n_features = 2; }},
+        {"features_2_and_samples_0", [](Call &k) { k.a.n_features = 2; k.a.n_samples = 0; }},
+        // (no samples_0 with frames_times_samples_2p31: a product above 2^31 - 1 needs n_samples >= 1)
+        {"frames_times_samples_2p31_and_frame_2p30_plus_1_rows", [](Call &k) { k.a.n_frames = 2; k.a.n_samples = 1 << 30; k.a.n_total = ((int64_t)1 << 30) + 1; k.a.max_frame_rows = 0; }},
+        {"frame_2p30_plus_1_rows_and_range_nan", [&](Call &k) { k.a.n_total = ((int64_t)1 << 30) + 1; k.a.max_frame_rows = 0; k.range6[5] = nan; }},
+        {"range_nan_and_range_reversed", [&](Call &k) { k.range6[5] = nan; k.range6[4] = -3.0; }},
+        {"range_reversed_and_index_is_keep_in", [](Call &k) { k.range6[4] = -3.0; k.a.out_index = (int32_t *)g_keep; }},
+        // The current contract: the outputs are not compared with each other.  Refusing this call is a change of behaviour, not a tidying.
+        {"dist_is_points", [](Call &k) { k.a.out_dist = k.a.out_points; }},
     };
     for (const auto &cs : cases) {
         Call k;

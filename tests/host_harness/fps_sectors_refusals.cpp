@@ -97,6 +97,25 @@ int main()
         {"count_behind_offsets", [](Call &k) { k.a.out_sector_count = g_offsets + 6; }},
         {"sector_of_overlaps_count", [](Call &k) { k.a.out_sector_of = (int8_t *)g_count + 15; }},
         {"reach2_overlaps_sector_of", [](Call &k) { k.a.out_sector_of = (int8_t *)g_reach2 + 31; }},
+        {"frames_times_rois_2p31", [](Call &k) { k.a.fps.n_frames = 1 << 23; k.a.fps.n_samples = 1; k.a.n_rois = 256; }},
+        // two defects, of checks that stand next to each other: the earlier check's message
+        {"null_and_rows_2p31", [](Call &k) { k.a.fps.frame_off = nullptr; k.a.fps.n_total = (int64_t)1 << 31; k.a.fps.keep_in = nullptr; }},
+        {"rows_2p31_and_features_2", [](Call &k) { k.a.fps.n_total = (int64_t)1 << 31; k.a.fps.keep_in = nullptr; k.a.fps.n_features = 2; }},
+        {"features_2_and_samples_0", [](Call &k) { k.a.fps.n_features = 2; k.a.fps.n_samples = 0; }},
+        // (no samples_0 with frames_times_samples_2p31: a product above 2^31 - 1 needs n_samples >= 1)
+        {"frames_times_samples_2p31_and_frame_2p30_plus_1_rows", [](Call &k) { k.a.fps.n_frames = 2; k.a.fps.n_samples = 1 << 30; k.a.fps.n_total = ((int64_t)1 << 30) + 1; k.a.fps.max_frame_rows = 0; }},
+        {"frame_2p30_plus_1_rows_and_range_nan", [&](Call &k) { k.a.fps.n_total = ((int64_t)1 << 30) + 1; k.a.fps.max_frame_rows = 0; k.range6[5] = nan; }},
+        {"range_nan_and_range_lo_is_hi", [&](Call &k) { k.range6[5] = nan; k.range6[3] = 0.0; }},
+        {"range_lo_is_hi_and_sectors_0", [](Call &k) { k.range6[3] = 0.0; k.a.n_sectors = 0; }},
+        {"sectors_0_and_rois_0", [](Call &k) { k.a.n_sectors = 0; k.a.n_rois = 0; }},
+        {"rois_0_and_roi_features_6", [](Call &k) { k.a.n_rois = 0; k.a.roi_features = 6; }},
+        {"roi_features_6_and_margin_nan", [&](Call &k) { k.a.roi_features = 6; k.a.roi_margin = nan; }},
+        {"margin_nan_and_frames_times_rois_2p31", [&](Call &k) { k.a.roi_margin = nan; k.a.fps.n_frames = 1 << 23; k.a.fps.n_samples = 1; k.a.n_rois = 256; }},
+        // (2^23 frames of 16 tiles each)
+        {"frames_times_rois_2p31_and_tiles_2p27", [](Call &k) { k.a.fps.n_frames = 1 << 23; k.a.fps.n_samples = 1; k.a.n_rois = 256; k.a.fps.n_total = (int64_t)1 << 30; k.a.fps.max_frame_rows = 16384; k.a.fps.keep_in = nullptr; }},
+        // (no reach2_without_rois with the four roi checks before it: those are made with d_rois, this one without)
+        {"reach2_without_rois_and_tiles_2p27", [](Call &k) { k.a.rois = nullptr; k.a.fps.n_frames = 1 << 17; k.a.fps.n_samples = 1; k.a.fps.n_total = (int64_t)1 << 30; k.a.fps.max_frame_rows = 1 << 20; k.a.fps.keep_in = nullptr; }},
+        {"tiles_2p27_and_index_overlaps_rows", [](Call &k) { k.a.fps.n_frames = 1 << 17; k.a.fps.n_samples = 1; k.a.fps.n_total = (int64_t)1 << 30; k.a.fps.max_frame_rows = 1 << 20; k.a.fps.keep_in = nullptr; k.a.fps.out_index = (int32_t *)g_rows; }},
     };
     for (const auto &cs : cases) {
         Call k;

@@ -37,6 +37,13 @@ int main()
         {"iou_slots_2p31", [](SgIouArgs &a) { a.n_frames = 32768; a.n_a = 256; a.n_b = 256; }},
         {"iou_out_is_boxes_b", [](SgIouArgs &a) { a.out_iou = (void *)a.boxes_b; }},
         {"iou_best_is_iou", [](SgIouArgs &a) { a.out_best = (int32_t *)a.out_iou; }},
+        // two defects, of checks that stand next to each other: the earlier check's message
+        {"iou_null_a_and_mode_2", [](SgIouArgs &a) { a.boxes_a = nullptr; a.mode = 2; }},
+        {"iou_mode_2_and_no_output", [](SgIouArgs &a) { a.mode = 2; a.out_iou = nullptr; a.out_best = nullptr; a.out_best_iou = nullptr; }},
+        {"iou_no_output_and_m_0", [](SgIouArgs &a) { a.out_iou = nullptr; a.out_best = nullptr; a.out_best_iou = nullptr; a.n_a = 0; }},
+        {"iou_m_0_and_feats_6", [](SgIouArgs &a) { a.n_a = 0; a.a_features = 6; }},
+        {"iou_feats_6_and_slots_2p31", [](SgIouArgs &a) { a.a_features = 6; a.n_frames = 32768; a.n_a = 256; a.n_b = 256; }},
+        {"iou_slots_2p31_and_out_is_boxes_b", [](SgIouArgs &a) { a.n_frames = 32768; a.n_a = 256; a.n_b = 256; a.out_iou = (void *)a.boxes_b; }},
     };
     const std::vector<std::pair<const char *, N>> nc = {
         {"nms_clean", [](SgNmsArgs &) {}},
@@ -59,6 +66,14 @@ int main()
         {"nms_slots_2p31", [](SgNmsArgs &a) { a.n_frames = 1 << 20; a.n_boxes = 2048; a.post_max = 1; }},
         {"nms_boxes_out_is_boxes", [](SgNmsArgs &a) { a.out_boxes = (void *)a.boxes; }},
         {"nms_kept_overlaps_index", [](SgNmsArgs &a) { a.out_kept = (uint8_t *)a.out_index + 8; }},
+        // two defects, of checks that stand next to each other: the earlier check's message
+        {"nms_null_scores_and_mode_m1", [](SgNmsArgs &a) { a.scores = nullptr; a.mode = -1; }},
+        {"nms_mode_m1_and_b_0", [](SgNmsArgs &a) { a.mode = -1; a.n_boxes = 0; }},
+        {"nms_b_0_and_feats_6", [](SgNmsArgs &a) { a.n_boxes = 0; a.box_features = 6; }},
+        {"nms_feats_6_and_post_max_0", [](SgNmsArgs &a) { a.box_features = 6; a.post_max = 0; }},
+        {"nms_post_max_0_and_nan_iou_thresh", [](SgNmsArgs &a) { a.post_max = 0; a.iou_thresh = NAN; }},
+        {"nms_nan_iou_thresh_and_slots_2p31", [](SgNmsArgs &a) { a.iou_thresh = NAN; a.n_frames = 1 << 20; a.n_boxes = 2048; a.post_max = 1; }},
+        {"nms_slots_2p31_and_boxes_out_is_boxes", [](SgNmsArgs &a) { a.n_frames = 1 << 20; a.n_boxes = 2048; a.post_max = 1; a.out_boxes = (void *)a.boxes; }},
     };
     for (const auto &cs : ic) {
         SgIouArgs a = iou;

@@ -95,6 +95,17 @@ int main()
         {"weight_overlaps_index", [](Call &k) { k.a.out_weight = (float *)g_index + 8; }},          // inside the index array's padding
         {"weight_is_dist2", [](Call &k) { k.a.out_weight = g_dist2; }},
         {"weight_behind_dist2", [](Call &k) { k.a.out_weight = g_dist2 + 24; k.a.out_dist2 = g_dist2; k.a.k = 1; }},
+        // two defects, of checks that stand next to each other: the earlier check's message
+        {"null_and_rows_2p31", [](Call &k) { k.a.frame_off = nullptr; k.a.n_total = (int64_t)1 << 31; k.a.keep_in = nullptr; }},
+        {"rows_2p31_and_centre_features_2", [](Call &k) { k.a.n_total = (int64_t)1 << 31; k.a.keep_in = nullptr; k.a.centre_features = 2; }},
+        {"centre_features_2_and_centres_0", [](Call &k) { k.a.centre_features = 2; k.a.n_centres = 0; }},
+        {"centres_0_and_k_0", [](Call &k) { k.a.n_centres = 0; k.a.k = 0; }},
+        {"k_0_and_centres_2p31", [](Call &k) { k.a.k = 0; k.a.n_frames = 2; k.a.n_centres = 1 << 30; bare(k); }},
+        {"centres_2p31_and_frame_2p30_plus_1_rows", [](Call &k) { k.a.n_frames = 2; k.a.n_centres = 1 << 30; k.a.n_total = ((int64_t)1 << 30) + 1; k.a.max_frame_rows = 0; }},
+        {"frame_2p30_plus_1_rows_and_cell_lists_too_large", [](Call &k) { k.a.n_total = ((int64_t)1 << 30) + 1; k.a.max_frame_rows = 0; k.a.n_frames = 1048065; k.a.n_centres = 1; }},
+        {"cell_lists_too_large_and_range_nan", [&](Call &k) { k.a.n_frames = 1048065; k.a.n_centres = 1; bare(k); k.range6[5] = nan; }},
+        {"range_nan_and_range_reversed", [&](Call &k) { k.range6[5] = nan; k.range6[4] = -3.0; }},
+        {"range_reversed_and_index_is_keep_in", [](Call &k) { k.range6[4] = -3.0; k.a.out_index = (int32_t *)g_keep; }},
     };
     for (const auto &cs : cases) {
         Call k;

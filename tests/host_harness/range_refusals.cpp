@@ -110,6 +110,19 @@ int main()
         {"count_overlaps_image", [](Call &k) { k.a.out_count = (int32_t *)g_image + 30; }},
         {"count_is_index", [](Call &k) { k.a.out_count = g_index; }},
         {"count_overlaps_pixel_of", [](Call &k) { k.a.out_count = g_pixel_of + 7; }},
+        // two defects, of checks that stand next to each other: the earlier check's message
+        {"null_and_no_mode", [](Call &k) { k.a.frame_off = nullptr; k.a.fov2 = nullptr; }},
+        {"no_mode_and_rows_2p31", [](Call &k) { k.a.fov2 = nullptr; k.a.n_total = (int64_t)1 << 31; k.a.keep_in = nullptr; }},
+        {"rows_2p31_and_features_2", [](Call &k) { k.a.n_total = (int64_t)1 << 31; k.a.keep_in = nullptr; k.a.n_features = 2; }},
+        {"features_2_and_height_0", [](Call &k) { k.a.n_features = 2; k.a.H = 0; }},
+        // (no height_0 with pixels_2p31: a product above 2^31 - 1 needs a height and a width of at least 1)
+        {"pixels_2p31_and_frame_2p30_plus_1_rows", [](Call &k) { k.a.n_frames = 2; k.a.H = 1 << 15; k.a.W = 1 << 15; bare(k); k.a.n_total = ((int64_t)1 << 30) + 1; k.a.max_frame_rows = 0;
+                                                                 k.a.rows = g_rows; k.a.out_pixel_of = g_pixel_of; }},
+        {"frame_2p30_plus_1_rows_and_fov_nan", [&](Call &k) { k.a.n_total = ((int64_t)1 << 30) + 1; k.a.max_frame_rows = 0; k.fov2[0] = nan; }},
+        {"fov_degrees_and_fov_reversed", [](Call &k) { k.fov2[0] = -25.0; k.fov2[1] = 3.0; }},
+        {"fov_reversed_and_limit_nan_lo", [&](Call &k) { k.fov2[0] = -0.43; k.fov2[1] = 0.05; k.limits2[0] = nan; }},
+        {"limit_nan_hi_and_limit_lo_negative", [&](Call &k) { k.limits2[1] = nan; k.limits2[0] = -0.5; }},
+        {"limit_reversed_and_index_is_keep_in", [](Call &k) { k.limits2[0] = 121.0; k.a.out_index = (int32_t *)g_keep; }},
     };
     for (const auto &cs : cases) {
         Call k;

@@ -133,6 +133,26 @@ int main()
         {"avg_behind_argmax", [](SgRoiAwareArgs &a) { a.out_avg = (float *)g_argmax + 72; }},
         {"pose_overlaps_avg", [](SgRoiAwareArgs &a) { a.out_pose = (double *)g_avg + 35; }},
         {"pose_overlaps_roi_count", [](SgRoiAwareArgs &a) { a.out_roi_count = (int32_t *)g_pose + 23; }},
+        // two defects, of checks that stand next to each other: the earlier check's message
+        {"null_and_rows_2p31", [](SgRoiAwareArgs &a) { a.frame_off = nullptr; a.n_total = (int64_t)1 << 31; a.keep_in = nullptr; a.features = nullptr; }},
+        {"rows_2p31_and_rois_0", [](SgRoiAwareArgs &a) { a.n_total = (int64_t)1 << 31; a.keep_in = nullptr; a.features = nullptr; a.n_rois = 0; }},
+        {"rois_0_and_roi_features_6", [](SgRoiAwareArgs &a) { a.n_rois = 0; a.roi_features = 6; }},
+        {"roi_features_6_and_extra_width_nan", [](SgRoiAwareArgs &a) { a.roi_features = 6; a.extra_width = ew_nan; }},
+        {"extra_width_nan_and_out_size_0", [](SgRoiAwareArgs &a) { a.extra_width = ew_nan; a.out_size = grid_0; }},
+        {"out_size_0_and_points_0", [](SgRoiAwareArgs &a) { a.out_size = grid_0; a.max_points = 0; }},
+        {"points_0_and_capacity_63", [](SgRoiAwareArgs &a) { a.max_points = 0; a.roi_capacity = 63; }},
+        {"capacity_63_and_no_features_max", [](SgRoiAwareArgs &a) { a.roi_capacity = 63; a.features = nullptr; a.out_argmax = nullptr; a.out_avg = nullptr; }},
+        {"no_features_max_and_channels_0", [](SgRoiAwareArgs &a) { a.features = nullptr; a.out_argmax = nullptr; a.out_avg = nullptr; a.feature_channels = 0; }},
+        {"channels_257_and_elements_above_2p31", [](SgRoiAwareArgs &a) { bare(a); a.features = (const float *)(uintptr_t)((uint64_t)1 << 43); a.feature_channels = 257;
+                                                                         a.n_frames = 1024; a.n_rois = 4; a.out_size = grid_16; a.max_points = 128; }},
+        {"elements_above_2p31_and_list_above_2p31", [](SgRoiAwareArgs &a) { bare(a); a.n_frames = 64; a.n_rois = 512; a.out_size = grid_16; a.max_points = 128; a.roi_capacity = 65536; }},
+        {"list_above_2p31_and_frame_2p30_plus_1_rows", [](SgRoiAwareArgs &a) { bare(a); a.n_frames = 64; a.n_rois = 512; a.out_size = grid_1; a.roi_capacity = 65536;
+                                                                               a.n_total = ((int64_t)1 << 30) + 1; a.max_frame_rows = 0; a.rows = (const void *)(uintptr_t)((uint64_t)1 << 40); }},
+        {"frame_2p30_plus_1_rows_and_runs_above_2p31", [](SgRoiAwareArgs &a) { bare(a); a.n_frames = 2; a.n_rois = 512; a.out_size = grid_1; a.n_total = ((int64_t)1 << 31) - 1;
+                                                                               a.max_frame_rows = ((int64_t)1 << 30) + 1; a.rows = (const void *)(uintptr_t)((uint64_t)1 << 40); }},
+        {"runs_above_2p31_and_roi_count_is_rows", [](SgRoiAwareArgs &a) { bare(a); a.n_frames = 2; a.n_rois = 512; a.out_size = grid_1; a.n_total = ((int64_t)1 << 31) - 1;
+                                                                          a.max_frame_rows = (int64_t)1 << 30; a.rows = (const void *)(uintptr_t)((uint64_t)1 << 40);
+                                                                          a.out_roi_count = (int32_t *)(uintptr_t)((uint64_t)1 << 40); }},
     };
     for (const auto &cs : cases) {
         SgRoiAwareArgs a;

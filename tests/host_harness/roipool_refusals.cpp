@@ -105,6 +105,20 @@ int main()
         {"local_behind_points", [](SgRoiPoolArgs &a) { a.out_local = g_points + 48; }},
         {"pose_overlaps_local", [](SgRoiPoolArgs &a) { a.out_pose = (double *)g_local + 17; }},
         {"pose_overlaps_count", [](SgRoiPoolArgs &a) { a.out_count = (int32_t *)g_pose + 23; }},
+        // two defects, of checks that stand next to each other: the earlier check's message
+        {"null_and_rows_2p31", [](SgRoiPoolArgs &a) { a.frame_off = nullptr; a.n_total = (int64_t)1 << 31; a.keep_in = nullptr; }},
+        {"rows_2p31_and_rois_0", [](SgRoiPoolArgs &a) { a.n_total = (int64_t)1 << 31; a.keep_in = nullptr; a.n_rois = 0; }},
+        {"rois_0_and_roi_features_6", [](SgRoiPoolArgs &a) { a.n_rois = 0; a.roi_features = 6; }},
+        {"roi_features_6_and_samples_0", [](SgRoiPoolArgs &a) { a.roi_features = 6; a.n_samples = 0; }},
+        {"samples_0_and_features_2", [](SgRoiPoolArgs &a) { a.n_samples = 0; a.num_features = 2; }},
+        {"features_2_and_extra_width_nan", [](SgRoiPoolArgs &a) { a.num_features = 2; a.extra_width = ew_nan; }},
+        {"extra_width_nan_and_elements_above_2p31", [](SgRoiPoolArgs &a) { a.extra_width = ew_nan; a.n_frames = 1024; a.n_rois = 342; a.n_samples = 2048; a.num_features = 3; bare(a); }},
+        {"elements_above_2p31_and_frame_2p30_plus_1_rows", [](SgRoiPoolArgs &a) { a.n_frames = 1024; a.n_rois = 342; a.n_samples = 2048; a.num_features = 3; bare(a);
+                                                                                  a.n_total = ((int64_t)1 << 30) + 1; a.max_frame_rows = 0; a.rows = (const void *)(uintptr_t)((uint64_t)1 << 40); }},
+        {"frame_2p30_plus_1_rows_and_runs_above_2p31", [](SgRoiPoolArgs &a) { bare(a); a.n_frames = 2; a.n_rois = 512; a.n_samples = 1; a.n_total = ((int64_t)1 << 31) - 1;
+                                                                              a.max_frame_rows = ((int64_t)1 << 30) + 1; a.rows = (const void *)(uintptr_t)((uint64_t)1 << 40); }},
+        {"runs_above_2p31_and_index_is_rows", [](SgRoiPoolArgs &a) { bare(a); a.n_frames = 2; a.n_rois = 512; a.n_samples = 1; a.n_total = ((int64_t)1 << 31) - 1; a.max_frame_rows = (int64_t)1 << 30;
+                                                                     a.rows = (const void *)(uintptr_t)((uint64_t)1 << 40); a.out_index = (int32_t *)(uintptr_t)((uint64_t)1 << 40); }},
     };
     for (const auto &cs : cases) {
         SgRoiPoolArgs a;

@@ -129,6 +129,17 @@ int main()
         {"class_count_behind_segments", [](SgTargetsArgs &a) { a.out_class_count = g_segments + 6; }},
         {"pose_overlaps_class_count", [](SgTargetsArgs &a) { a.out_pose = (double *)g_class_count + 2; }},
         {"gt_local_is_pose", [](SgTargetsArgs &a) { a.out_gt_local = g_pose; }},
+        // two defects, of checks that stand next to each other: the earlier check's message
+        {"null_rois_and_rois_0", [](SgTargetsArgs &a) { a.rois = nullptr; a.n_rois = 0; }},
+        {"rois_0_and_roi_features_6", [](SgTargetsArgs &a) { a.n_rois = 0; a.roi_features = 6; }},
+        {"roi_features_6_and_slots_0", [](SgTargetsArgs &a) { a.roi_features = 6; g_cfg.roi_per_image = 0; }},
+        {"slots_0_and_fg_negative", [](SgTargetsArgs &) { g_cfg.roi_per_image = 0; g_cfg.fg_per_image = -1; }},
+        {"fg_negative_and_reg_fg_nan", [nan](SgTargetsArgs &) { g_cfg.fg_per_image = -1; g_cfg.reg_fg_thresh = nan; }},
+        {"reg_fg_nan_and_cls_fg_below_cls_bg", [nan](SgTargetsArgs &) { g_cfg.reg_fg_thresh = nan; g_cfg.cls_fg_thresh = 0.2; }},
+        {"cls_fg_below_cls_bg_and_ratio_nan", [nan](SgTargetsArgs &) { g_cfg.cls_fg_thresh = 0.2; g_cfg.hard_bg_ratio = nan; }},
+        {"ratio_nan_and_cls_mode_2", [nan](SgTargetsArgs &) { g_cfg.hard_bg_ratio = nan; g_cfg.cls_mode = 2; }},
+        {"cls_mode_2_and_elements_above_2p31", [](SgTargetsArgs &a) { g_cfg.cls_mode = 2; a.n_frames = 209716; g_cfg.roi_per_image = 1024; a.roi_features = 10; bare(a); }},
+        {"elements_above_2p31_and_index_is_rois", [](SgTargetsArgs &a) { a.n_frames = 209716; g_cfg.roi_per_image = 1024; a.roi_features = 10; bare(a); a.out_index = (int32_t *)a.rois; }},
     };
     for (const auto &cs : cases) {
         SgTargetsArgs a;

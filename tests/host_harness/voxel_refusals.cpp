@@ -83,6 +83,19 @@ int main()
         {"voxel_of_overlaps_keep_in", [](Call &k) { k.a.keep_in = (const uint8_t *)g_vof + 31; }},      // its last byte
         {"voxel_of_behind_keep_in", [](Call &k) { k.a.out_voxel_of = (int32_t *)(g_keep + 8); }},
         {"keep_in_behind_voxel_of", [](Call &k) { k.a.keep_in = (const uint8_t *)g_vof + 32; }},
+        // two defects, of checks that stand next to each other: the earlier check's message
+        {"null_and_rows_2p31", [](Call &k) { k.a.frame_off = nullptr; k.a.n_total = (int64_t)1 << 31; k.a.keep_in = nullptr; }},
+        {"rows_2p31_and_features_2", [](Call &k) { k.a.n_total = (int64_t)1 << 31; k.a.keep_in = nullptr; k.a.n_features = 2; }},
+        {"features_2_and_points_0", [](Call &k) { k.a.n_features = 2; k.a.max_points = 0; }},
+        {"points_0_and_size_zero", [](Call &k) { k.a.max_points = 0; k.size3[1] = 0.0; }},
+        {"size_zero_and_axis_without_cell", [](Call &k) { k.size3[1] = 0.0; k.range6[3] = 0.25; }},
+        {"range_reversed_and_cells_1e30", [](Call &k) { k.range6[4] = -3.0; k.range6[3] = 1e30; }},      // (the cells' axis comes first)
+        {"cells_1e30_and_frames_times_voxels_2p31", [](Call &k) { k.range6[3] = 1e30; k.a.n_frames = 2; k.a.max_voxels = 1 << 30; }},
+        {"frames_times_voxels_2p31_and_frame_2p30_plus_1_rows", [](Call &k) { k.a.n_frames = 2; k.a.max_voxels = 1 << 30; k.a.n_total = ((int64_t)1 << 30) + 1; k.a.max_frame_rows = 0; k.a.keep_in = nullptr; }},
+        {"frame_2p30_plus_1_rows_and_voxel_of_is_keep_in", [](Call &k) { k.a.n_total = ((int64_t)1 << 30) + 1; k.a.max_frame_rows = 0; k.a.out_voxel_of = (int32_t *)g_keep; }},
+        // The current contract: d_out_voxel_of against d_keep_in is the only overlap looked for.  Refusing this call is a change of
+        // behaviour, not a tidying.
+        {"coords_are_num_points", [](Call &k) { k.a.out_coords = k.a.out_num_points; }},
     };
     for (const auto &cs : cases) {
         Call k;

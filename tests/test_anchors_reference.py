@@ -244,6 +244,8 @@ MESSAGES = {
     "elements": WHO + ": n_frames * n_anchors exceeds 2^31 - 1; split the batch",
 }
 ORDER = tuple(MESSAGES)              # the order of the checks: a call wrong in two ways gets the earlier message
+DOUBLY = ("null_anchors_and_anchors_0", "anchors_0_and_gt_0", "gt_0_and_anchor_features_6", "anchor_features_6_and_gt_features_7", "gt_features_7_and_classes_0",
+          "classes_17_and_unmatched_0", "unmatched_0_and_elements_at_2p31", "elements_at_2p31_and_label_is_anchors")              # one per check and the one behind it
 PAIRS = {("label", "anchors"): ("label_is_anchors", "label_overlaps_anchors"), ("gt_index", "anchor_class"): ("gt_index_is_anchor_class",),
          ("count", "gt_boxes"): ("count_overlaps_gt_boxes",), ("gt_count", "gt_boxes"): ("gt_count_is_gt_boxes",), ("iou", "anchor_class"): ("iou_overlaps_anchor_class",)}
 OUTS = {("gt_index", "label"): ("gt_index_is_label",), ("count", "label"): ("count_overlaps_label",), ("gt_count", "count"): ("gt_count_is_count",),
@@ -253,14 +255,14 @@ ACCEPTED = ("clean", "null_out_iou", "float64", "anchors_1", "gt_1", "gt_256", "
             "iou_behind_anchor_class", "count_behind_label")
 REFUSED = {
     "null": ("null_anchors", "null_anchor_class", "null_gt_boxes", "null_matched", "null_unmatched", "null_out_label", "null_out_gt_index", "null_out_count",
-             "null_out_gt_count", "bad_dtype", "no_frames"),
-    "anchors": ("anchors_0", "anchors_negative"),
-    "gt": ("gt_0", "gt_257"),
-    "anchor_features": ("anchor_features_6", "anchor_features_11"),
-    "gt_features": ("gt_features_7", "gt_features_11"),
-    "classes": ("classes_0", "classes_17"),
-    "thresholds": ("unmatched_0", "unmatched_negative", "unmatched_above_matched", "matched_above_1", "matched_nan", "unmatched_nan"),
-    "elements": ("elements_at_2p31", "elements_overflowing"),
+             "null_out_gt_count", "bad_dtype", "no_frames", "null_anchors_and_anchors_0"),
+    "anchors": ("anchors_0", "anchors_negative", "anchors_0_and_gt_0"),
+    "gt": ("gt_0", "gt_257", "gt_0_and_anchor_features_6"),
+    "anchor_features": ("anchor_features_6", "anchor_features_11", "anchor_features_6_and_gt_features_7"),
+    "gt_features": ("gt_features_7", "gt_features_11", "gt_features_7_and_classes_0"),
+    "classes": ("classes_0", "classes_17", "classes_17_and_unmatched_0"),
+    "thresholds": ("unmatched_0", "unmatched_negative", "unmatched_above_matched", "matched_above_1", "matched_nan", "unmatched_nan", "unmatched_0_and_elements_at_2p31"),
+    "elements": ("elements_at_2p31", "elements_overflowing", "elements_at_2p31_and_label_is_anchors"),
 }
 
 
@@ -283,11 +285,12 @@ def test_refusal_walk(tmp_path):
         want.update({case: f"1|{WHO}: d_out_{out} overlaps d_out_{other}{OWN}" for case in cases})
     assert got == want
     assert set(MESSAGES) == set(REFUSED)              # every message is reached
-    # the order: the checks stand in sg_check_anchors_args in the order of MESSAGES, the overlaps behind them
-    text = (ROOT / "lidar_snow_sim_amd" / "csrc" / "sg_device_args.h").read_text()
-    body = text[text.index("sg_check_anchors_args("):]
-    places = [body.index('"' + MESSAGES[k][len(WHO):] + '"') for k in ORDER]
-    assert places == sorted(places) and places[-1] < body.index("every output needs memory of its own")
+    # the order: the checks stand in sg_check_anchors_args in the order of MESSAGES, the overlaps behind them -- every "<first>_and_<second>"
+    # case of the harness is wrong in two ways, of checks next to each other, and is filed above under the earlier one
+    for key, later, case in zip(ORDER, ORDER[1:] + (None,), DOUBLY):
+        first, second = case.split("_and_")
+        assert first in REFUSED[key] and case in REFUSED[key], case
+        assert second in REFUSED[later] if later else any(second in cases for cases in PAIRS.values()), case
 
 
 def test_the_entry_is_declared_and_bound():

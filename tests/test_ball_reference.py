@@ -224,22 +224,22 @@ MESSAGES = {
 }
 ACCEPTED = ("clean", "null_out_points", "null_keep_in", "null_range", "float64", "empty_null_rows", "features_3", "features_5", "centre_features_5",
             "radii_1", "radii_4", "radius_1e6", "radius_tiny", "samples_1", "samples_64", "slots_2p31_minus_1", "frame_2p30_rows", "cell_lists_fit",
-            "range_infinite", "keep_in_behind_index", "index_behind_rows", "index_behind_centres")
+            "range_infinite", "keep_in_behind_index", "index_behind_rows", "index_behind_centres", "count_is_index")
 REFUSED = {
     "null": ("null_frame_offsets", "null_rows", "null_centres", "null_radii", "null_samples", "null_out_index", "null_out_count", "bad_dtype", "no_frames",
-             "negative_rows"),
-    "rows": ("rows_2p31",),
-    "features": ("features_2", "features_6"),
-    "centre_features": ("centre_features_2", "centre_features_6"),
-    "centres": ("centres_0", "centres_negative"),
-    "n_radii": ("radii_0", "radii_5"),
-    "radius": ("radius_0", "radius_negative", "radius_nan", "radius_inf", "radius_above_1e6"),
+             "negative_rows", "null_and_rows_2p31"),
+    "rows": ("rows_2p31", "rows_2p31_and_features_2"),
+    "features": ("features_2", "features_6", "features_2_and_centre_features_2"),
+    "centre_features": ("centre_features_2", "centre_features_6", "centre_features_2_and_centres_0"),
+    "centres": ("centres_0", "centres_negative", "centres_0_and_radii_0"),
+    "n_radii": ("radii_0", "radii_5", "radii_5_and_radius_0"),
+    "radius": ("radius_0", "radius_negative", "radius_nan", "radius_inf", "radius_above_1e6", "radius_0_and_samples_0"),
     "samples": ("samples_0", "samples_65"),
-    "slots": ("slots_2p31", "slots_overflowing"),
-    "frame": ("frame_2p30_plus_1_rows",),
-    "cells": ("cell_lists_too_large",),
-    "nan": ("range_nan_lo", "range_nan_hi"),
-    "order": ("range_reversed", "range_lo_is_hi"),
+    "slots": ("slots_2p31", "slots_overflowing", "slots_2p31_and_frame_2p30_plus_1_rows"),
+    "frame": ("frame_2p30_plus_1_rows", "frame_2p30_plus_1_rows_and_cell_lists_too_large"),
+    "cells": ("cell_lists_too_large", "cell_lists_too_large_and_range_nan"),
+    "nan": ("range_nan_lo", "range_nan_hi", "range_nan_and_range_reversed"),
+    "order": ("range_reversed", "range_lo_is_hi", "range_reversed_and_index_is_keep_in"),
     "index_keep": ("index_is_keep_in", "index_overlaps_keep_in"),
     "count_keep": ("count_overlaps_keep_in",),
     "points_keep": ("points_overlap_keep_in",),

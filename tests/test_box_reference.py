@@ -228,12 +228,12 @@ ACCEPTED = ("clean", "null_out_count", "null_out_local", "null_out_pose", "null_
             "boxes_1", "boxes_256", "box_features_7", "box_features_10", "slots_2p31_minus_256", "frame_2p30_rows", "keep_in_behind_box_of",
             "box_of_behind_rows", "box_of_behind_boxes", "box_of_behind_pose_in", "count_behind_box_of")
 REFUSED = {
-    "null": ("null_frame_offsets", "null_rows", "null_boxes", "null_out_box_of", "bad_dtype", "no_frames", "negative_rows"),
-    "rows": ("rows_2p31",),
-    "boxes": ("boxes_0", "boxes_257", "boxes_negative"),
-    "box_features": ("box_features_6", "box_features_11"),
-    "slots": ("slots_2p31", "slots_overflowing"),
-    "frame": ("frame_2p30_plus_1_rows",),
+    "null": ("null_frame_offsets", "null_rows", "null_boxes", "null_out_box_of", "bad_dtype", "no_frames", "negative_rows", "null_and_rows_2p31"),
+    "rows": ("rows_2p31", "rows_2p31_and_boxes_0"),
+    "boxes": ("boxes_0", "boxes_257", "boxes_negative", "boxes_0_and_box_features_6"),
+    "box_features": ("box_features_6", "box_features_11", "box_features_6_and_slots_2p31"),
+    "slots": ("slots_2p31", "slots_overflowing", "slots_2p31_and_frame_2p30_plus_1_rows"),
+    "frame": ("frame_2p30_plus_1_rows", "frame_2p30_plus_1_rows_and_box_of_is_keep_in"),
     "box_of_keep_in": ("box_of_is_keep_in", "box_of_overlaps_keep_in"),
     "count_keep_in": ("count_overlaps_keep_in",),
     "local_keep_in": ("local_overlaps_keep_in",),

@@ -187,16 +187,16 @@ MESSAGES = {
 }
 ACCEPTED = ("clean", "null_out_points", "null_out_dist", "null_keep_in", "null_range", "float64", "empty_null_rows", "features_3", "features_5",
             "samples_1", "frames_times_samples_2p31_minus_1", "frame_2p30_rows", "range_infinite", "keep_in_behind_index", "index_behind_keep_in",
-            "index_behind_rows")
+            "index_behind_rows", "dist_is_points")
 REFUSED = {
-    "null": ("null_frame_offsets", "null_rows", "null_out_index", "null_out_usable", "bad_dtype", "no_frames", "negative_rows", "empty_null_out_index"),
-    "rows": ("rows_2p31",),
-    "features": ("features_2", "features_6"),
+    "null": ("null_frame_offsets", "null_rows", "null_out_index", "null_out_usable", "bad_dtype", "no_frames", "negative_rows", "empty_null_out_index", "null_and_rows_2p31"),
+    "rows": ("rows_2p31", "rows_2p31_and_features_2"),
+    "features": ("features_2", "features_6", "features_2_and_samples_0"),
     "least_1": ("samples_0", "samples_negative"),
-    "slots": ("frames_times_samples_2p31",),
-    "frame": ("frame_2p30_plus_1_rows",),
-    "nan": ("range_nan_lo", "range_nan_hi"),
-    "order": ("range_reversed", "range_lo_is_hi", "range_inf_lo_is_hi"),
+    "slots": ("frames_times_samples_2p31", "frames_times_samples_2p31_and_frame_2p30_plus_1_rows"),
+    "frame": ("frame_2p30_plus_1_rows", "frame_2p30_plus_1_rows_and_range_nan"),
+    "nan": ("range_nan_lo", "range_nan_hi", "range_nan_and_range_reversed"),
+    "order": ("range_reversed", "range_lo_is_hi", "range_inf_lo_is_hi", "range_reversed_and_index_is_keep_in"),
     "index_keep": ("index_is_keep_in", "index_overlaps_keep_in"),
     "points_keep": ("points_overlap_keep_in",),
     "dist_keep": ("dist_overlaps_keep_in",),

@@ -267,6 +267,7 @@ MESSAGES = {
     "n_rois": WHO + ": n_rois must lie in 1 .. 256",
     "roi_features": WHO + ": roi_features must lie in 7 .. 10: cx, cy, cz, dx, dy, dz, heading first",
     "margin": WHO + ": roi_margin must be finite and at least 0",
+    "roi_slots": WHO + ": n_frames * n_rois exceeds 2^31 - 1; split the batch",
     "reach2": WHO + ": d_out_reach2 without d_rois; there is no reach to write",
     "tiles": WHO + ": n_frames * ceil(max_frame_rows / 1024) exceeds 2^27 - 1; split the batch",
     "index_keep": WHO + ": d_out_index" + APART["keep_in"],
@@ -287,20 +288,21 @@ ACCEPTED = ("clean", "null_out_points", "null_out_dist", "null_out_sector_of", "
             "sector_of_behind_keep_in", "dist_behind_rois", "count_behind_offsets")
 REFUSED = {
     "null": ("null_frame_offsets", "null_rows", "null_out_index", "null_out_usable", "null_out_sector_offsets", "null_out_sector_count", "bad_dtype",
-             "no_frames", "negative_rows"),
-    "rows": ("rows_2p31",),
-    "features": ("features_2", "features_6"),
+             "no_frames", "negative_rows", "null_and_rows_2p31"),
+    "rows": ("rows_2p31", "rows_2p31_and_features_2"),
+    "features": ("features_2", "features_6", "features_2_and_samples_0"),
     "least_1": ("samples_0",),
-    "slots": ("frames_times_samples_2p31",),
-    "frame": ("frame_2p30_plus_1_rows",),
-    "nan": ("range_nan_lo",),
-    "order": ("range_lo_is_hi",),
-    "sectors": ("sectors_0", "sectors_17"),
-    "n_rois": ("rois_0", "rois_257"),
-    "roi_features": ("roi_features_6", "roi_features_11"),
-    "margin": ("margin_negative", "margin_nan", "margin_inf"),
-    "reach2": ("reach2_without_rois",),
-    "tiles": ("tiles_2p27",),
+    "slots": ("frames_times_samples_2p31", "frames_times_samples_2p31_and_frame_2p30_plus_1_rows"),
+    "frame": ("frame_2p30_plus_1_rows", "frame_2p30_plus_1_rows_and_range_nan"),
+    "nan": ("range_nan_lo", "range_nan_and_range_lo_is_hi"),
+    "order": ("range_lo_is_hi", "range_lo_is_hi_and_sectors_0"),
+    "sectors": ("sectors_0", "sectors_17", "sectors_0_and_rois_0"),
+    "n_rois": ("rois_0", "rois_257", "rois_0_and_roi_features_6"),
+    "roi_features": ("roi_features_6", "roi_features_11", "roi_features_6_and_margin_nan"),
+    "margin": ("margin_negative", "margin_nan", "margin_inf", "margin_nan_and_frames_times_rois_2p31"),
+    "roi_slots": ("frames_times_rois_2p31", "frames_times_rois_2p31_and_tiles_2p27"),
+    "reach2": ("reach2_without_rois", "reach2_without_rois_and_tiles_2p27"),
+    "tiles": ("tiles_2p27", "tiles_2p27_and_index_overlaps_rows"),
     "index_keep": ("index_is_keep_in",),
     "sector_of_keep": ("sector_of_overlaps_keep_in",),
     "points_rows": ("points_are_rows",),

@@ -294,6 +294,13 @@ REFUSALS = {
     "nms_boxes_out_is_boxes": f"1|{NMS}: d_out_boxes overlaps d_boxes; the boxes, scores and pose are read while the keep list is written: pass a buffer apart from them",
     "nms_kept_overlaps_index": f"1|{NMS}: d_out_kept overlaps d_out_index; every output needs memory of its own",
 }
+# a call wrong in two ways, of checks that stand next to each other, gets the earlier check's message: "<first>_and_<second>"
+REFUSALS.update({case: REFUSALS[first] for first, case in (
+    ("iou_null_a", "iou_null_a_and_mode_2"), ("iou_mode_2", "iou_mode_2_and_no_output"), ("iou_no_output", "iou_no_output_and_m_0"),
+    ("iou_m_0", "iou_m_0_and_feats_6"), ("iou_feats_6", "iou_feats_6_and_slots_2p31"), ("iou_slots_2p31", "iou_slots_2p31_and_out_is_boxes_b"),
+    ("nms_null_scores", "nms_null_scores_and_mode_m1"), ("nms_mode_m1", "nms_mode_m1_and_b_0"), ("nms_b_0", "nms_b_0_and_feats_6"),
+    ("nms_feats_6", "nms_feats_6_and_post_max_0"), ("nms_post_max_0", "nms_post_max_0_and_nan_iou_thresh"),
+    ("nms_nan_iou_thresh", "nms_nan_iou_thresh_and_slots_2p31"), ("nms_slots_2p31", "nms_slots_2p31_and_boxes_out_is_boxes"))})
 
 
 def test_refusal_walk(tmp_path):

@@ -239,16 +239,16 @@ ACCEPTED = ("clean", "null_out_weight", "null_keep_in", "null_range", "float64",
             "centres_2p31_minus_1", "frame_2p30_rows", "cell_lists_fit", "range_infinite", "keep_in_behind_index", "index_behind_rows",
             "index_behind_centres", "weight_behind_dist2")
 REFUSED = {
-    "null": ("null_frame_offsets", "null_rows", "null_centres", "null_out_index", "null_out_dist2", "bad_dtype", "no_frames", "negative_rows"),
-    "rows": ("rows_2p31",),
-    "centre_features": ("centre_features_2", "centre_features_6"),
-    "centres": ("centres_0", "centres_negative"),
-    "k": ("k_0", "k_9", "k_negative"),
-    "slots": ("centres_2p31", "centres_overflowing"),
-    "frame": ("frame_2p30_plus_1_rows",),
-    "cells": ("cell_lists_too_large",),
-    "nan": ("range_nan_lo", "range_nan_hi"),
-    "order": ("range_reversed", "range_lo_is_hi"),
+    "null": ("null_frame_offsets", "null_rows", "null_centres", "null_out_index", "null_out_dist2", "bad_dtype", "no_frames", "negative_rows", "null_and_rows_2p31"),
+    "rows": ("rows_2p31", "rows_2p31_and_centre_features_2"),
+    "centre_features": ("centre_features_2", "centre_features_6", "centre_features_2_and_centres_0"),
+    "centres": ("centres_0", "centres_negative", "centres_0_and_k_0"),
+    "k": ("k_0", "k_9", "k_negative", "k_0_and_centres_2p31"),
+    "slots": ("centres_2p31", "centres_overflowing", "centres_2p31_and_frame_2p30_plus_1_rows"),
+    "frame": ("frame_2p30_plus_1_rows", "frame_2p30_plus_1_rows_and_cell_lists_too_large"),
+    "cells": ("cell_lists_too_large", "cell_lists_too_large_and_range_nan"),
+    "nan": ("range_nan_lo", "range_nan_hi", "range_nan_and_range_reversed"),
+    "order": ("range_reversed", "range_lo_is_hi", "range_reversed_and_index_is_keep_in"),
     "index_keep": ("index_is_keep_in", "index_overlaps_keep_in"),
     "dist2_keep": ("dist2_overlaps_keep_in",),
     "weight_keep": ("weight_overlaps_keep_in",),

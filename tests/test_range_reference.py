@@ -262,17 +262,17 @@ ACCEPTED = ("clean", "null_out_count", "null_keep_in", "null_limits", "float64",
             "features_3", "features_5", "one_pixel", "pixels_2p31_minus_1", "frame_2p30_rows", "fov_half_pi", "limit_hi_inf", "limit_lo_zero_hi_tiny",
             "keep_in_behind_image", "index_behind_rows", "pixel_of_behind_ring", "index_behind_image")
 REFUSED = {
-    "null": ("null_frame_offsets", "null_rows", "null_out_image", "null_out_index", "null_out_pixel_of", "bad_dtype", "no_frames", "negative_rows"),
-    "mode": ("no_mode",),
-    "rows": ("rows_2p31",),
-    "features": ("features_2", "features_6"),
+    "null": ("null_frame_offsets", "null_rows", "null_out_image", "null_out_index", "null_out_pixel_of", "bad_dtype", "no_frames", "negative_rows", "null_and_no_mode"),
+    "mode": ("no_mode", "no_mode_and_rows_2p31"),
+    "rows": ("rows_2p31", "rows_2p31_and_features_2"),
+    "features": ("features_2", "features_6", "features_2_and_height_0"),
     "size": ("height_0", "width_0", "height_negative"),
-    "pixels": ("pixels_2p31", "pixels_overflowing"),
-    "frame": ("frame_2p30_plus_1_rows",),
-    "fov_domain": ("fov_up_above_half_pi", "fov_down_below_half_pi", "fov_nan", "fov_inf", "fov_degrees"),
-    "fov_order": ("fov_reversed", "fov_up_is_down"),
-    "limit_nan": ("limit_nan_lo", "limit_nan_hi"),
-    "limit_order": ("limit_lo_negative", "limit_lo_is_hi", "limit_reversed", "limit_lo_inf"),
+    "pixels": ("pixels_2p31", "pixels_overflowing", "pixels_2p31_and_frame_2p30_plus_1_rows"),
+    "frame": ("frame_2p30_plus_1_rows", "frame_2p30_plus_1_rows_and_fov_nan"),
+    "fov_domain": ("fov_up_above_half_pi", "fov_down_below_half_pi", "fov_nan", "fov_inf", "fov_degrees", "fov_degrees_and_fov_reversed"),
+    "fov_order": ("fov_reversed", "fov_up_is_down", "fov_reversed_and_limit_nan_lo"),
+    "limit_nan": ("limit_nan_lo", "limit_nan_hi", "limit_nan_hi_and_limit_lo_negative"),
+    "limit_order": ("limit_lo_negative", "limit_lo_is_hi", "limit_reversed", "limit_lo_inf", "limit_reversed_and_index_is_keep_in"),
     "image_keep": ("image_overlaps_keep_in",),
     "index_keep": ("index_is_keep_in",),
     "pixel_of_keep": ("pixel_of_overlaps_keep_in",),

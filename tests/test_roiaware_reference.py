@@ -282,20 +282,20 @@ ACCEPTED = ("clean", "null_out_index", "null_out_max", "null_out_argmax", "null_
             "out_size_16", "points_1", "points_128", "capacity_65536", "channels_1", "channels_256", "elements_below_2p31", "list_below_2p31", "frame_2p30_rows",
             "runs_below_2p31", "keep_in_behind_count", "index_behind_rows", "max_behind_features", "count_behind_roi_count", "avg_behind_argmax")
 REFUSED = {
-    "null": ("null_frame_offsets", "null_rows", "null_rois", "null_out_size", "null_out_roi_count", "null_out_count", "bad_dtype", "no_frames", "negative_rows"),
-    "rows": ("rows_2p31",),
-    "rois": ("rois_0", "rois_513", "rois_negative"),
-    "roi_features": ("roi_features_6", "roi_features_11"),
-    "extra_width": ("extra_width_negative", "extra_width_above_100", "extra_width_nan", "extra_width_inf"),
-    "out_size": ("out_size_0", "out_size_17", "out_size_negative"),
-    "points": ("points_0", "points_129"),
-    "capacity": ("capacity_63", "capacity_65537"),
-    "pool": ("no_features_max", "no_features_argmax", "no_features_avg"),
-    "channels": ("channels_0", "channels_257"),
-    "elements": ("elements_above_2p31", "elements_by_channels", "elements_overflowing"),
-    "list": ("list_above_2p31",),
-    "frame": ("frame_2p30_plus_1_rows",),
-    "runs": ("runs_above_2p31",),
+    "null": ("null_frame_offsets", "null_rows", "null_rois", "null_out_size", "null_out_roi_count", "null_out_count", "bad_dtype", "no_frames", "negative_rows", "null_and_rows_2p31"),
+    "rows": ("rows_2p31", "rows_2p31_and_rois_0"),
+    "rois": ("rois_0", "rois_513", "rois_negative", "rois_0_and_roi_features_6"),
+    "roi_features": ("roi_features_6", "roi_features_11", "roi_features_6_and_extra_width_nan"),
+    "extra_width": ("extra_width_negative", "extra_width_above_100", "extra_width_nan", "extra_width_inf", "extra_width_nan_and_out_size_0"),
+    "out_size": ("out_size_0", "out_size_17", "out_size_negative", "out_size_0_and_points_0"),
+    "points": ("points_0", "points_129", "points_0_and_capacity_63"),
+    "capacity": ("capacity_63", "capacity_65537", "capacity_63_and_no_features_max"),
+    "pool": ("no_features_max", "no_features_argmax", "no_features_avg", "no_features_max_and_channels_0"),
+    "channels": ("channels_0", "channels_257", "channels_257_and_elements_above_2p31"),
+    "elements": ("elements_above_2p31", "elements_by_channels", "elements_overflowing", "elements_above_2p31_and_list_above_2p31"),
+    "list": ("list_above_2p31", "list_above_2p31_and_frame_2p30_plus_1_rows"),
+    "frame": ("frame_2p30_plus_1_rows", "frame_2p30_plus_1_rows_and_runs_above_2p31"),
+    "runs": ("runs_above_2p31", "runs_above_2p31_and_roi_count_is_rows"),
     **PAIRS, **OUTS,
 }
 

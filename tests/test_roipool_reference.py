@@ -175,16 +175,16 @@ ACCEPTED = ("clean", "null_out_points", "null_out_local", "null_out_pose", "null
             "elements_below_2p31", "frame_2p30_rows", "runs_below_2p31", "keep_in_behind_index", "count_behind_rows", "count_behind_index",
             "local_behind_points")
 REFUSED = {
-    "null": ("null_frame_offsets", "null_rows", "null_rois", "null_out_index", "null_out_count", "bad_dtype", "no_frames", "negative_rows"),
-    "rows": ("rows_2p31",),
-    "rois": ("rois_0", "rois_513", "rois_negative"),
-    "roi_features": ("roi_features_6", "roi_features_11"),
-    "samples": ("samples_0", "samples_2049"),
-    "features": ("features_2", "features_6"),
-    "extra_width": ("extra_width_negative", "extra_width_above_100", "extra_width_nan", "extra_width_inf"),
-    "elements": ("elements_above_2p31", "elements_overflowing"),
-    "frame": ("frame_2p30_plus_1_rows",),
-    "runs": ("runs_above_2p31",),
+    "null": ("null_frame_offsets", "null_rows", "null_rois", "null_out_index", "null_out_count", "bad_dtype", "no_frames", "negative_rows", "null_and_rows_2p31"),
+    "rows": ("rows_2p31", "rows_2p31_and_rois_0"),
+    "rois": ("rois_0", "rois_513", "rois_negative", "rois_0_and_roi_features_6"),
+    "roi_features": ("roi_features_6", "roi_features_11", "roi_features_6_and_samples_0"),
+    "samples": ("samples_0", "samples_2049", "samples_0_and_features_2"),
+    "features": ("features_2", "features_6", "features_2_and_extra_width_nan"),
+    "extra_width": ("extra_width_negative", "extra_width_above_100", "extra_width_nan", "extra_width_inf", "extra_width_nan_and_elements_above_2p31"),
+    "elements": ("elements_above_2p31", "elements_overflowing", "elements_above_2p31_and_frame_2p30_plus_1_rows"),
+    "frame": ("frame_2p30_plus_1_rows", "frame_2p30_plus_1_rows_and_runs_above_2p31"),
+    "runs": ("runs_above_2p31", "runs_above_2p31_and_index_is_rows"),
     **PAIRS, **OUTS,
 }
 

@@ -300,6 +300,9 @@ MESSAGES = {
     "elements": WHO + ": n_frames * roi_per_image * max(roi_features, gt_features) exceeds 2^31 - 1; split the batch",
 }
 ORDER = tuple(MESSAGES)              # the order of the checks: a call wrong in two ways gets the earlier message
+DOUBLY = ("null_rois_and_rois_0", "rois_0_and_roi_features_6", "roi_features_6_and_slots_0", "slots_0_and_fg_negative", "fg_negative_and_reg_fg_nan",
+          "reg_fg_nan_and_cls_fg_below_cls_bg", "cls_fg_below_cls_bg_and_ratio_nan", "ratio_nan_and_cls_mode_2", "cls_mode_2_and_elements_above_2p31",
+          "elements_above_2p31_and_index_is_rois")              # one per check and the one behind it, in that order
 PAIRS = {("index", "rois"): ("index_is_rois", "index_overlaps_rois"), ("rois", "overlap"): ("rois_overlaps_overlap",), ("roi_iou", "assignment"): ("roi_iou_is_assignment",),
          ("gt_index", "gt_boxes"): ("gt_index_overlaps_gt_boxes",), ("cls_label", "step"): ("cls_label_is_step",), ("pose", "pose"): ("pose_is_pose_in",),
          ("gt_local", "pose"): ("gt_local_overlaps_pose_in",)}
@@ -313,16 +316,16 @@ ACCEPTED = ("clean", "null_pose_in", "null_out_pose", "null_out_gt_local", "floa
 REFUSED = {
     "null": ("null_rois", "null_overlap", "null_assignment", "null_gt_boxes", "null_cfg", "null_step", "null_out_index", "null_out_rois", "null_out_roi_iou",
              "null_out_gt_index", "null_out_gt_of_rois", "null_out_reg_valid", "null_out_cls_label", "null_out_segments", "null_out_class_count", "bad_dtype",
-             "no_frames"),
-    "boxes": ("rois_0", "rois_9217", "gt_0", "gt_9217", "gt_negative"),
-    "features": ("roi_features_6", "roi_features_11", "gt_features_6", "gt_features_11"),
-    "slots": ("slots_0", "slots_1025"),
-    "fg": ("fg_negative", "fg_above_slots"),
-    "threshold": ("reg_fg_nan", "cls_fg_inf", "cls_bg_minus_inf", "cls_bg_lo_nan"),
-    "cls": ("cls_fg_equals_cls_bg", "cls_fg_below_cls_bg"),
-    "ratio": ("ratio_negative", "ratio_above_1", "ratio_nan"),
-    "mode": ("cls_mode_negative", "cls_mode_2"),
-    "elements": ("elements_above_2p31", "elements_overflowing"),
+             "no_frames", "null_rois_and_rois_0"),
+    "boxes": ("rois_0", "rois_9217", "gt_0", "gt_9217", "gt_negative", "rois_0_and_roi_features_6"),
+    "features": ("roi_features_6", "roi_features_11", "gt_features_6", "gt_features_11", "roi_features_6_and_slots_0"),
+    "slots": ("slots_0", "slots_1025", "slots_0_and_fg_negative"),
+    "fg": ("fg_negative", "fg_above_slots", "fg_negative_and_reg_fg_nan"),
+    "threshold": ("reg_fg_nan", "cls_fg_inf", "cls_bg_minus_inf", "cls_bg_lo_nan", "reg_fg_nan_and_cls_fg_below_cls_bg"),
+    "cls": ("cls_fg_equals_cls_bg", "cls_fg_below_cls_bg", "cls_fg_below_cls_bg_and_ratio_nan"),
+    "ratio": ("ratio_negative", "ratio_above_1", "ratio_nan", "ratio_nan_and_cls_mode_2"),
+    "mode": ("cls_mode_negative", "cls_mode_2", "cls_mode_2_and_elements_above_2p31"),
+    "elements": ("elements_above_2p31", "elements_overflowing", "elements_above_2p31_and_index_is_rois"),
 }
 
 
@@ -345,11 +348,12 @@ def test_refusal_walk(tmp_path):
         want.update({case: f"1|{WHO}: d_out_{out} overlaps d_out_{other}{OWN}" for case in cases})
     assert got == want
     assert set(MESSAGES) == set(REFUSED)              # every message is reached
-    # the order: the checks stand in sg_check_targets_args in the order of MESSAGES, the overlaps behind them
-    text = (ROOT / "lidar_snow_sim_amd" / "csrc" / "sg_device_args.h").read_text()
-    body = text[text.index("sg_check_targets_args("):]
-    places = [body.index('"' + MESSAGES[k][len(WHO):] + '"') for k in ORDER]
-    assert places == sorted(places) and places[-1] < body.index("every output needs memory of its own")
+    # the order: the checks stand in sg_check_targets_args in the order of MESSAGES, the overlaps behind them -- every "<first>_and_<second>"
+    # case of the harness is wrong in two ways, of checks next to each other, and is filed above under the earlier one
+    for key, later, case in zip(ORDER, ORDER[1:] + (None,), DOUBLY):
+        first, second = case.split("_and_")
+        assert first in REFUSED[key] and case in REFUSED[key], case
+        assert second in REFUSED[later] if later else any(second in cases for cases in PAIRS.values()), case
 
 
 def test_the_entry_is_declared_and_bound():

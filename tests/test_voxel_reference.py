@@ -196,19 +196,19 @@ MESSAGES = {
     "overlap": WHO + ": d_out_voxel_of overlaps d_keep_in; the keep-in bytes of other rows are read while it is written: pass a buffer apart from it",
 }
 OK_4_4_2 = ("clean", "null_out_voxel_of", "null_keep_in", "float64", "empty_null_buffers", "features_3", "features_5", "points_1", "voxels_1",
-            "frames_times_voxels_2p31_minus_1", "frame_2p30_rows", "voxel_of_behind_keep_in", "keep_in_behind_voxel_of")
+            "frames_times_voxels_2p31_minus_1", "frame_2p30_rows", "voxel_of_behind_keep_in", "keep_in_behind_voxel_of", "coords_are_num_points")
 OK_OTHER = {"axis_half_cell": "1 4 2", "cells_2p31_minus_2": "2147483646 1 1", "cells_2p31_minus_2_as_product": "46341 46339 1"}
 REFUSED = {
     "null": ("null_frame_offsets", "null_rows", "null_range", "null_size", "null_out_voxels", "null_out_coords", "null_out_num_points",
-             "null_out_voxel_offsets", "bad_dtype", "no_frames", "negative_rows", "empty_null_voxel_offsets"),
-    "rows": ("rows_2p31",),
-    "features": ("features_2", "features_6"),
-    "least_1": ("points_0", "voxels_0", "voxels_negative"),
-    "size": ("size_zero", "size_negative", "size_inf", "size_nan"),
-    "axis": ("axis_without_cell", "range_reversed", "range_inf", "range_nan"),
-    "cells": ("cells_2p31_minus_1", "cells_product_too_large", "cells_1e30"),
-    "slots": ("frames_times_voxels_2p31",),
-    "frame": ("frame_2p30_plus_1_rows",),
+             "null_out_voxel_offsets", "bad_dtype", "no_frames", "negative_rows", "empty_null_voxel_offsets", "null_and_rows_2p31"),
+    "rows": ("rows_2p31", "rows_2p31_and_features_2"),
+    "features": ("features_2", "features_6", "features_2_and_points_0"),
+    "least_1": ("points_0", "voxels_0", "voxels_negative", "points_0_and_size_zero"),
+    "size": ("size_zero", "size_negative", "size_inf", "size_nan", "size_zero_and_axis_without_cell"),
+    "axis": ("axis_without_cell", "range_reversed", "range_inf", "range_nan", "range_reversed_and_cells_1e30"),
+    "cells": ("cells_2p31_minus_1", "cells_product_too_large", "cells_1e30", "cells_1e30_and_frames_times_voxels_2p31"),
+    "slots": ("frames_times_voxels_2p31", "frames_times_voxels_2p31_and_frame_2p30_plus_1_rows"),
+    "frame": ("frame_2p30_plus_1_rows", "frame_2p30_plus_1_rows_and_voxel_of_is_keep_in"),
     "overlap": ("voxel_of_is_keep_in", "voxel_of_overlaps_keep_in"),
 }
 
