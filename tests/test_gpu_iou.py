@@ -3,7 +3,39 @@ snowgpu_nms_device; csrc/snowgpu_iou.hip, csrc/sg_iou.h) against the NumPy resta
 inputs tests/test_iou_reference.py holds to the conditions that keep these comparisons from being vacuous).  The restatement takes the pose
 as an input and everything behind the pose is separately rounded float64 arithmetic in the definition's order: every output is compared
 byte for byte, for both dtypes, with no element left out -- under a given pose, and under the pose the device computed, which
-points_in_boxes returns (the same device library, the same rule of presence)."""
+points_in_boxes returns (the same device library, the same rule of presence).
+
+Beside the shared cases, which keep every decision away from its threshold on purpose, the device meets the hard inputs (2a, 2b):
+the ten adversarial families of iou_reference.family_case -- the eight adversarial kinds of tests/host_harness/iou_clip.cpp (equal
+boxes, right angles, headings 1 ulp apart, shared faces, slivers, coordinates to 1e6, 1 cm to 100 m, boxes a few ulps wide), z_sliver
+(heights that meet or miss by 1 ulp of T or 1e-15 .. 1e-10 of dz) and clamped (unions on both sides of 1e-8 m^2 and 1e-6 m^3, overlaps
+whose IoU is a float32 subnormal) --, each built in the dtype under test, one frame of 130 x 130 per family with the designed partners
+on the diagonal, and the 1300 designed pairs again as M = B = 1 frames; IoUs that tie for best across the 64-wide tiles of the b side;
+equal scores across the groups and tiles of k_nms_rank; iou_thresh equal to an IoU the call computes, and the doubles beside it; stacks
+of one box.  tests/test_iou_reference.py holds the host build of sg_iou.h equal to the restatement on every one of these pairs, and the
+inputs to what they must contain.
+
+Measured on an MI355X: float32-subnormal IoUs COME BACK AS SUBNORMALS -- the (T)v store does not flush them: of the 10 x 130 x 130 float32
+IoUs of the family call 729 (BEV) and 498 (3D) are subnormal in the definition and the same 729 and 498 on the device, equal bytes.
+Nothing differed between device and restatement on any new input, so neither the kernels nor the restatement changed.
+
+That the new tests bite.  Each one-line variant changes a comparison or a constant only.  Header variants of csrc/sg_iou.h, on the host
+harness (no GPU; both fail test_iou_reference.py::test_host_clip_equals_the_restatement_on_every_family[float32, float64]; in brackets
+the DESIGNED pairs of 130 per family whose area or IoU changes, float32 / float64 frame):
+  - a boundary point is outside (`dp < h`): equal [16 / 17], right_angle [10 / 16], one_ulp [0 / 16], shared_face [1 / 17] -- the
+    changes are last bits of float64: rounded to float32 none survives, so on the device the float64 frames decide it;
+  - both union clamps ten times smaller (1e-9, 1e-7): clamped [111 / 111] and 2667 of its 16 900 pairs, collapsed [120 / 82];
+  - a height overlap of at most 1e-9 counts as none: z_sliver [22 / 56].
+Kernel variants of csrc/snowgpu_iou.hip, each built apart from the tree and run once against this file on the same device:
+  - k_iou_pairs `v > best_v || (v == best_v && v > 0.0)`: test_best_among_equal_ious_across_tiles[float32, float64], nothing else
+    (the tie of the shared cases sits in two lanes of one tile);
+  - k_nms_sweep `>=` for `>` in both tests: test_suppression_at_equality[equal_bev, equal_3d x float32, float64] (count 70 at
+    equality where 140 are kept), no test of before;
+  - k_nms_rank `i < j` for `t0 + i < j`: test_rank_ties_across_tiles_and_groups[float32, float64] -- and the b4160 and b9216 cases
+    of before, because behind the first tile that form also counts a candidate before itself; built with `order` zero-filled and its
+    store guarded, so that the colliding ranks stayed inside the buffers;
+  - SG_IOU_CAP 8 for 20 (tried, not required to fail): all 131 tests pass, the 8 / 6 designed equal pairs that emit more than 8
+    vertices included -- the dropped vertices coincide with kept ones to within rounding, on the device as on the host."""
 import re
 
 import numpy as np
@@ -133,6 +165,89 @@ def test_post_max_and_modes(dtype):
     c = ir.nms_case("b129", dtype)                                     # a threshold above every IoU: all are kept; below every IoU: the first box suppresses all
     assert _nms(_t(c["boxes"]), _t(c["scores"]), 2.0, post_max=129, pose=_t(c["pose"])).count.tolist() == [129]
     assert _nms(_t(c["boxes"]), _t(c["scores"]), -1.0, post_max=129, pose=_t(c["pose"])).count.tolist() == [1]
+
+
+# ---- 2a. the adversarial families: the kinds of the host harness, z_sliver and clamped ---------------------------------------------------------
+def _subnormals(x):
+    return int(((x != 0) & (np.abs(x) < ir.F32_TINY)).sum())
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_families_under_a_given_pose(dtype):
+    """One frame per family, 130 x 130 (two full tiles of b and a partial one), designed partners on the diagonal; both modes."""
+    c = ir.family_case(dtype)
+    a, b, pa, pb = _t(c["a"]), _t(c["b"]), _t(c["pose_a"]), _t(c["pose_b"])
+    for mode in ir.MODES:
+        got, want = _iou(a, b, mode=mode, pose_a=pa, pose_b=pb, return_best=True), ir.family_expected(dtype, mode)
+        if dtype == "float32":
+            print(f"float32 subnormal IoUs, {mode}: the device returns {_subnormals(got.iou.cpu().numpy())}, the definition has {_subnormals(want['iou'])}")
+        _same(got, want, (dtype, mode), IOU_FIELDS)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_families_under_the_device_pose(dtype):
+    c = ir.family_case(dtype)
+    pa, pb = _device_pose(c["a"]), _device_pose(c["b"])
+    assert np.array_equal(pa.any(axis=-1), ir.present(c["a"], c["pose_a"])) and np.array_equal(pb.any(axis=-1), ir.present(c["b"], c["pose_b"]))
+    for mode in ir.MODES:
+        _same(_iou(_t(c["a"]), _t(c["b"]), mode=mode, return_best=True), ir.boxes_iou(c["a"], c["b"], pa, pb, mode), (dtype, mode), IOU_FIELDS)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_designed_pairs_one_per_frame(dtype):
+    """The 1300 designed pairs as frames of M = B = 1: one lane of one wave per frame, a tile with one record."""
+    p = ir.family_pairs(ir.family_case(dtype))
+    for mode in ir.MODES:
+        got = _iou(_t(p["a"]), _t(p["b"]), mode=mode, pose_a=_t(p["pose_a"]), pose_b=_t(p["pose_b"]), return_best=True)
+        _same(got, ir.pairs_expected(p, mode), (dtype, mode, "given pose"), IOU_FIELDS)
+    q = dict(p, pose_a=_device_pose(p["a"]), pose_b=_device_pose(p["b"]))
+    _same(_iou(_t(p["a"]), _t(p["b"]), mode="3d", return_best=True), ir.pairs_expected(q, "3d"), (dtype, "device pose"), IOU_FIELDS)
+
+
+# ---- 2b. exact ties and thresholds at equality ----------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_best_among_equal_ious_across_tiles(dtype):
+    """Equal b boxes in one lane of three tiles, in a later tile, and in a later tile and a smaller lane: best is the smallest number."""
+    c = ir.best_tie_case(dtype)
+    for mode in ir.MODES:
+        got = _iou(_t(c["a"]), _t(c["b"]), mode=mode, pose_a=_t(c["pose_a"]), pose_b=_t(c["pose_b"]), return_best=True)
+        assert got.best.cpu().numpy()[:, :3].tolist() == [[min(g) for g in ir.BEST_TIE_GROUPS]] * 2
+        _same(got, ir.boxes_iou(c["a"], c["b"], c["pose_a"], c["pose_b"], mode), (dtype, mode), IOU_FIELDS)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_rank_ties_across_tiles_and_groups(dtype):
+    """2100 disjoint boxes, all kept: the kept order is the ranking, equal scores in ascending numbers across 255 | 256, 1023 | 1024,
+    2047 | 2048 and at (5, 1029)."""
+    c = ir.tie_case("rank_ties", dtype)
+    got = _run_nms(c)
+    _same(got, ir.tie_expected("rank_ties", dtype), dtype, NMS_FIELDS)
+    assert got.count.tolist() == [2100] and sorted(got.index.cpu().numpy()[0].tolist()) == list(range(2100))
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("name", ("equal_bev", "equal_3d"))
+def test_suppression_at_equality(name, dtype):
+    """iou_thresh equal to the IoU of every partner with its box: nothing is suppressed (the test is >); the double below: every partner is,
+    against a box kept in an earlier block and against one of its own block; the double above: nothing."""
+    c = ir.tie_case(name, dtype)
+    n = ir.EQ_PAIRS
+    for (word, t), count in zip(ir.tie_thresholds(c), (2 * n, n, 2 * n)):
+        got = _run_nms(c, pose="given") if word == "at" else _nms(_t(c["boxes"]), _t(c["scores"]), t, post_max=c["post_max"], mode=c["mode"], pose=_t(c["pose"]),
+                                                               return_scores=True, return_kept=True)
+        assert got.count.tolist() == [count], (name, dtype, word, got.count.tolist())
+        _same(got, ir.tie_expected(name, dtype, t), (name, dtype, word), NMS_FIELDS)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_stacks_of_one_box(dtype):
+    """130 copies of one box, some turned by 1 ulp: one is kept, the best scored; the same with score_thresh at the median."""
+    for name in ("stack", "stack_cut"):
+        c = ir.tie_case(name, dtype)
+        for pose in ("given", None):
+            got = _run_nms(c, pose=pose)
+            assert got.count.tolist() == [1] and got.index[0, 0].item() == int(np.argmax(c["scores"][0]))
+            _same(got, ir.tie_expected(name, dtype) if pose else _want_nms(c, _device_pose(c["boxes"])), (name, dtype, pose), NMS_FIELDS)
 
 
 # ---- 3. buffers, runs, streams ----------------------------------------------------------------------------------------------------------------
