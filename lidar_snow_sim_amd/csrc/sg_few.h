@@ -1,11 +1,25 @@
-// sg_few.h -- a beam that met a FEW flakes (1 .. N, N <= 3), start to finish in registers (k_power_few).
+// sg_few.h -- a beam that met a FEW flakes (1 .. N, N <= 4), start to finish in registers (k_power_few).
 //
 // Phases 2, 3a and 3b of the general path (sg_beam.h: sg_beam_dict, sg_beam_amp, sg_power_plan + sg_eval_group) written out for
 // lists of at most N flakes with every loop unrolled and every index a compile-time constant: the same expressions in the same
 // order, so every intermediate is the value the general path computes (tests/test_kernel_math.py runs both on the host over
 // millions of random beams and compares bit for bit).  What the short list buys:
-//   * compute_occlusion_dict (simulation.py:252-295) walks at most 2 N + 1 elementary slots, fewer than eight per owner: np.sum of
-//     an owner's slot widths is a running sum (sg_math.h: SgNpSum only blocks from eight addends on);
+//   * compute_occlusion_dict (simulation.py:252-295) walks at most 2 N + 1 elementary slots (2 N + 2 distinct endpoints at most: the
+//     flakes' and the two limit rays).  N <= 3: fewer than eight, so np.sum of an owner's slot widths is a running sum (sg_math.h:
+//     SgNpSum only blocks from eight addends on).  N = 4: nine slots at most, and ONE scatterer can own eight or nine of them --
+//       - the nearest flake, when its interval holds the six endpoints of the other three and both limit rays: nine;
+//       - a farther flake, eight where the nearest covers one slot inside it -- and nine where every nearer flake's interval is
+//         inverted (a1 >= a2: a wedge across azimuth 0 seen by a beam whose own limits do not wrap, simulation.py:260-263): such a
+//         flake covers nothing (:284) but its endpoints still cut slots;
+//       - the hard target.  The union of the L intervals has c <= L connected parts, so what it leaves of [e_min, e_max] has c - 1 inner
+//         gaps and up to two outer ones; an outer gap exists only where a limit ray is its far end, and each of the two rays either
+//         ends an outer gap or cuts one gap in two: at most c + 1 <= 5 uncovered slots -- as long as every interval covers something.
+//         Inverted intervals cover nothing and only cut: with four of them all nine slots are the target's.
+//     So for N = 4 the walk counts the slots of every owner and of the target, four bits each, and a scatterer that reached eight is
+//     summed again through SgNpSum (NumPy's blocked pairwise sum) in a rarely taken branch, as sg_beam_dict does with owner_walk.
+//     (get_occlusions clips an interval that crosses a limit ray to it, so the lists of a real table keep the rays out of every
+//     interval and stay at seven slots per owner: the branch is the guard that makes the functions exact for ANY list, which is what
+//     tests/host_harness/few4_vs_general.cpp feeds them);
 //   * stage A (which bins can hold the first maximum of the received power) looks at <= N neighbours of a scatterer;
 //   * stage B evaluates single bins, not groups of four: the kernel spreads the (beam, bin) pairs of a wave over its lanes.
 // Exactness of the pruning: sg_beam.h, "phase 3b".  A bin outside every zone can neither hold nor tie the maximum, and the zones
@@ -29,7 +43,8 @@ __device__ __forceinline__ int sg_few_prep(double d, double theta_c, int L, cons
                                            int channel, const SgLasers *__restrict__ las, double beam_div_deg, SgFew<N> &p, SgBeamOut &out)
 {
     constexpr bool F32 = SgReal<T>::is_f32;
-    static_assert(N >= 1 && N <= 3, "an owner must stay below eight slots (2 N + 1 <= 7)");
+    static_assert(N >= 1 && N <= 4, "2 N + 1 <= 9 slots: four bits count an owner's, and one block of eight addends is all SgNpSum sees");
+    constexpr bool COUNT = 2 * N + 1 >= 8;                      // a scatterer can reach eight slots: count them (the header's argument)
     const int max_i = las->max_i[channel];                     // (asked for here, used in phase 3a: the load flies while phase 2 computes)
     // -- phase 2
     double a1[N], a2[N];
@@ -57,27 +72,54 @@ __device__ __forceinline__ int sg_few_prep(double d, double theta_c, int L, cons
     }
     double R[N], tsum = -0.0;                                   // slot widths per owner, of the hard target: running sums
     bool has[N];
+    [[maybe_unused]] unsigned cnt = 0;                          // COUNT: slots per owner, four bits each (at most nine); the target's in bits 4 N ..
 #pragma unroll
     for (int j = 0; j < N; ++j) { R[j] = 0.0; has[j] = false; }
-    for (double e = e_min; e < e_max;) {
-        int own = -1;
+    // the slot that starts at e: its owner (nearest flake covering it, :284; -1: nobody, the hard target's) and its end
+    auto slot_at = [&](double e, int &own) -> double {
+        own = -1;
         double nxt = e_max;
 #pragma unroll
         for (int j = 0; j < N; ++j) {
             if (j < L) {
-                if (own < 0 && a1[j] <= e && e < a2[j]) own = j;    // nearest flake covering the slot (:284)
+                if (own < 0 && a1[j] <= e && e < a2[j]) own = j;
                 if (a1[j] > e && a1[j] < nxt) nxt = a1[j];
                 if (a2[j] > e && a2[j] < nxt) nxt = a2[j];
             }
         }
         if (ra > e && ra < nxt) nxt = ra;
         if (la > e && la < nxt) nxt = la;
+        return nxt;
+    };
+    for (double e = e_min; e < e_max;) {
+        int own;
+        const double nxt = slot_at(e, own);
         const double w = nxt - e;
         if (own < 0) tsum += w;                                 // :292-293
 #pragma unroll
         for (int j = 0; j < N; ++j)
             if (own == j) { R[j] = has[j] ? R[j] + w : w; has[j] = true; }
+        if constexpr (COUNT) cnt += 1u << (4 * (own < 0 ? N : own));
         e = nxt;
+    }
+    if constexpr (COUNT) {
+        if (cnt & (0x88888888u >> (28 - 4 * N))) {              // somebody has eight or nine: np.sum blocks (sg_math.h: SgNpSum)
+#pragma unroll
+            for (int t = 0; t <= N; ++t) {
+                if (((cnt >> (4 * t)) & 15u) < 8u) continue;
+                SgNpSum acc;
+                acc.reset();
+                for (double e = e_min; e < e_max;) {            // the same slots again, this scatterer's alone
+                    int own;
+                    const double nxt = slot_at(e, own);
+                    if ((own < 0 ? N : own) == t) acc.push(nxt - e);
+                    e = nxt;
+                }
+                if (t == N) tsum = acc.result();
+#pragma unroll
+                for (int j = 0; j < N; ++j) if (j == t) R[j] = acc.result();
+            }
+        }
     }
     // -- phase 3a for the owners, closed up near -> far (simulation.py:137-146)
     const double c_tau = 299792458.0 * 1e-8;

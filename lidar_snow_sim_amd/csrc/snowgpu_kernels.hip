@@ -6,7 +6,7 @@
 //   k_tier_scan_direct  the scan of a later tier whose lists the first pass could not keep
 //   k_power_plan, k_tier_gather  work items of k_power / k_power_few; the tier lists closed up
 //   k_power      received power on the 10 cm grid, first maximum, attenuate-or-scatter        (simulation.py:135-188)
-//   k_power_few  the same for the beams with one to three flakes
+//   k_power_few  the same for the beams with one to four flakes
 //   k_beams_huge the global-list tier (more than 63 flakes in one beam)
 //
 // The rows come channel-sorted and in segment order from snowgpu_sort.hip; snowgpu_compact.hip turns the result records into output rows.
@@ -885,17 +885,24 @@ __global__ __launch_bounds__(BLOCK < 64 ? 64 : BLOCK, LMAX <= 4 ? SG_KP_WAVES : 
 // 9.58 / 11.03 without any such kernel); N = 3: 4.32, 9.77, 9.48 (and C1: 8.98 without, 8.58 with N = 2, 8.78 with N = 3).
 // Tried and dropped: the kernel beside k_power on another stream, two or three blocks per CU instead of four (all 1 - 10 % slower:
 // the persistent kernels of this phase do best when each has the chip to itself for its turn).
-template <typename T, int N>
-__global__ __launch_bounds__(256, 4) void k_power_few(SgBeamArgs a, int lmax)   // (N = 3: 127 registers and eight spilled; at three waves per SIMD, 143 registers, it was slower on every workload)
+// N = 3 above is the FRONT run taken up to three flakes -- the kernel of eight in ten queued beams then carries a third flake's registers
+// for all of them (127 registers and eight spilled at four waves per SIMD; 143 at three waves, slower on every workload).
+// BACK = true: the same kernel over the BACK run of every region (the items k_power_plan files in pw_items: beams with more flakes than
+// the front run takes, up to the four a slot of the pass over all rows holds), N = 4, in place of k_power<T, 4, 256, false>: no list
+// columns in LDS, no window sorted by flake count, single bins in stage B.  WPS: the waves per SIMD it is compiled for (the front run's
+// kernels: four; N = 4: sg_few.h keeps 4 x 5 doubles of intervals, ranges and slot sums per lane).
+template <typename T, int N, int WPS = 4, bool BACK = false>
+__global__ __launch_bounds__(256, WPS) void k_power_few(SgBeamArgs a, int lmax)
 {
     __shared__ double s_amp[N + 1][256], s_rho[N + 1][256], s_best[256];      // scatterer N: the hard target
     __shared__ int s_win[N + 1][256], s_zone[N + 1][256], s_k[256];           // k0 | k1 << 16;  first bin | bins << 16
     __shared__ int s_mark[256];                                               // owner marks of a trip of the pair loop (sg_pair_owner)
     const int tid = (int)threadIdx.x, lane = tid & 63, wbase = tid & ~63;
-    const int n_items = a.pw_count[1];
+    const int n_items = a.pw_count[BACK ? 0 : 1];
+    const int2 *__restrict__ items = BACK ? a.pw_items : a.pw_items1;
     const int step = (int)gridDim.x * 4;
     for (int i = (int)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(tid >> 6); i < n_items; i += step) {
-        const int2 it = a.pw_items1[i];
+        const int2 it = items[i];
         const int start = __builtin_amdgcn_readfirstlane(it.x), dy = __builtin_amdgcn_readfirstlane(it.y);
         const int cnt = dy & 1023, item_f = (dy >> 10) - 1;
         const bool live = lane < cnt;
@@ -929,6 +936,7 @@ __global__ __launch_bounds__(256, 4) void k_power_few(SgBeamArgs a, int lmax)   
                 if (kb >= ka) { zone[0] = ka | ((kb - ka + 1) << 16); n += kb - ka + 1; }
                 if constexpr (N >= 2) { sg_few_zone<N, 1>(P, 0.0, ka, kb); if (kb >= ka) { zone[1] = ka | ((kb - ka + 1) << 16); n += kb - ka + 1; } }
                 if constexpr (N >= 3) { sg_few_zone<N, 2>(P, 0.0, ka, kb); if (kb >= ka) { zone[2] = ka | ((kb - ka + 1) << 16); n += kb - ka + 1; } }
+                if constexpr (N >= 4) { sg_few_zone<N, 3>(P, 0.0, ka, kb); if (kb >= ka) { zone[3] = ka | ((kb - ka + 1) << 16); n += kb - ka + 1; } }
                 sg_few_zone<N, N>(P, 0.0, ka, kb);
                 if (kb >= ka) { zone[N] = ka | ((kb - ka + 1) << 16); n += kb - ka + 1; }
             }
@@ -1112,6 +1120,10 @@ static int launch_power_t(const SgBeamArgs *a, hipStream_t st, bool plan_only = 
     static bool attr_set[64] = {};
     if (int e = sg_set_lds(k_power<T, LMAX, BLOCK, LISTQ>, lds, attr_set)) return e;
     constexpr int THREADS = BLOCK < 64 ? 64 : BLOCK, LANES = BLOCK < 64 ? BLOCK : 64;
+    // the back runs of a 4-entry queue whose front runs have their own kernel go through k_power_few<T, 4>; without pw_items1 (SNOWGPU_FEW=0, the
+    // occlusion tap) k_power<T, 4, 256, false> takes front and back runs alike
+    constexpr bool BACK_FEW = !LISTQ && LMAX == 4 && BLOCK == 256;
+    const bool back_few = BACK_FEW && a->pw_items1;
     const int cus = sg_cu_count();
     // persistent waves: what the chip holds at once (LDS and the 32-waves-per-CU limit), fewer if the queue cannot be longer
     unsigned per_cu = (unsigned)std::min<size_t>(32 * 64 / THREADS, std::max<size_t>(1, (size_t)(160 * 1024) / lds));
@@ -1129,8 +1141,9 @@ static int launch_power_t(const SgBeamArgs *a, hipStream_t st, bool plan_only = 
         // back runs (beams with several flakes, ~7 % of the rows of a sweep) as windows of SG_KP_WIN waves' worth of slots, taken
         // in order of flake count -- unless the resident waves take them all in about two rounds of single-wave items anyway
         // (small batches: a wave walking a window would serialise what the idle rest of the chip could do at once)
+        // (the register kernel takes 64-slot items whatever the batch: a wave whose lists are all three or four long has nothing to sort)
         const int64_t back_est = a->n_total / 10;
-        const int lanes_back = (BLOCK < 64 || back_est <= (int64_t)blocks * (THREADS / 64) * LANES * 5 / 2) ? LANES : LANES * SG_KP_WIN;
+        const int lanes_back = (BLOCK < 64 || back_few || back_est <= (int64_t)blocks * (THREADS / 64) * LANES * 5 / 2) ? LANES : LANES * SG_KP_WIN;
         if (plan_only) {                              // (its own call: the plan runs on the scan's stream, the kernels it feeds beside the tiers)
             hipLaunchKernelGGL(k_power_plan, dim3(pg), dim3(256), 0, st, *a, LANES, lanes_back, (int)a->n_regions_ub);
             SG_CHECK_LAUNCH();
@@ -1149,6 +1162,18 @@ static int launch_power_t(const SgBeamArgs *a, hipStream_t st, bool plan_only = 
         }
     }
     if (!(which & 2)) return 0;
+    if constexpr (BACK_FEW) {
+        if (back_few) {
+            // the back runs in registers: a persistent kernel of its own residency -- compiled for two waves per SIMD (171 VGPRs, none spilled), so two
+            // blocks of four waves per CU --, capped by the items there can be.  Measured on one box (profiles/r11_back_few_ab.txt), C2 per step: 3.203 ms
+            // so; one block per CU 3.234; compiled for three waves per SIMD (168 VGPRs) with three / two / one block 3.249 (against 3.230 in that run) /
+            // 3.198 / 3.210, none ahead in every round; a THIRD block queued on every CU behind the two resident ones 3.50, slower than k_power<4>
+            const unsigned g4 = (unsigned)std::min<int64_t>((int64_t)cus * 2, (a->n_total / LANES + a->n_regions_ub + 3) / 4);
+            if (g4 > 0) hipLaunchKernelGGL((k_power_few<T, 4, 2, true>), dim3(g4), dim3(256), 0, st, *a, LMAX);
+            SG_CHECK_LAUNCH();
+            return 0;
+        }
+    }
     hipLaunchKernelGGL((k_power<T, LMAX, BLOCK, LISTQ>), dim3((unsigned)blocks), dim3(THREADS), lds, st, *a);
     SG_CHECK_LAUNCH();
     return 0;
