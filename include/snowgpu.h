@@ -1309,6 +1309,76 @@ int snowgpu_assign_anchors_device(snowgpu_ctx *ctx, int n_frames, int n_anchors,
                                   const double *matched /* host */, const double *unmatched /* host */, int32_t *d_out_label, int32_t *d_out_gt_index,
                                   int32_t *d_out_count, int32_t *d_out_gt_count, void *d_out_iou /* or NULL */, void *stream);
 
+/*
+ * GROUND-TRUTH OBJECT PASTE: database objects written into the absent slots of an aligned batch, with their boxes appended to the gt
+ * boxes and the scene rows in their place cleared -- the step of OpenPCDet's DataBaseSampler (the gt_sampling augmentor) in front of the
+ * snowfall stage, with static shapes, nothing read on the host and a seeded draw.  pcdet is not part of the reference checkout: the
+ * definition below is THIS LIBRARY'S, modelled on pcdet's sampler as recalled, and was NOT CHECKED against pcdet's source.  It is restated
+ * in NumPy and Python integers by tests/paste_reference.py; csrc/sg_paste.h holds its C++, for the device and for the host.
+ *   INPUTS, F = n_frames, B = n_gt, T = float32 or float64: the aligned batch (d_rows (N, 5) T, d_frame_offsets, d_keep_in (N) bytes or NULL:
+ *   every row present); d_gt_boxes (F, B, Cb) T, Cb in 8 .. 10, columns 0 .. 6 cx, cy, cz, dx, dy, dz, heading, column 7 the class; d_pose_in
+ *   (F, B, 2) float64 (cos, sin) or NULL; THE BANK, O objects of P points: d_bank_points (P, 5) T -- x, y, z, intensity, channel as cropped
+ *   from real sweeps, positions kept --, d_bank_offsets (O + 1) int64, d_bank_boxes (O, 8) T with the class in column 7, classes ascending
+ *   over the objects, d_bank_pose (O, 2) float64, d_class_offsets 18 int32: the objects of class c = 1 .. 16 are
+ *   [class_offsets[c], class_offsets[c + 1]), L_c their number; sample_groups, NC = n_classes int32 in HOST memory, n_c = sample_groups[c - 1]
+ *   the number of objects of class c a frame should hold (pcdet's SAMPLE_GROUPS), Q = sum n_c; extra_width3 in HOST memory or NULL (zeros);
+ *   seed; d_step, a uint64 in DEVICE memory read by the kernel.
+ *   ARITHMETIC: float64 from (double) of the inputs, every operation rounded on its own, no fused multiply-add.
+ *   PRESENT: a gt or a bank box is present by the rule of snowgpu_points_in_boxes_device under its pose -- for a gt the given pose, or
+ *   cos / sin of (double)heading from the device library when d_pose_in is NULL; for a bank box the bank's.  cnt_c = the present gts of the
+ *   frame whose column 7 is integral and equals c.
+ *   SLOTS: class c owns slots s_c .. s_c + n_c - 1 in ascending class order, s_c the prefix sum of the n_c.  Slot q = s_c + j is ACTIVE
+ *   iff j < max(n_c - cnt_c, 0) and L_c > 0.  Its object is class_offsets[c] + ((r_q L_c) >> 32), r_q = word q % 4 of Philox4x32-10 under
+ *   key `seed` at counter (step, frame f, 0x50415354 + q / 4), the argument positions of the weather draw above.  Objects are drawn WITH
+ *   replacement; duplicates collide and are settled by the sweep.
+ *   COLLISION: candidate a collides with box b iff AREA(a, b) > 0, AREA the BEV clip of a in b's frame of snowgpu_boxes_iou_device (half
+ *   extents, no margin); both boxes present.
+ *   SWEEP over q ascending, free_left starting as the number of rows of the frame that are absent on input.  A slot that is not inactive
+ *   takes the LOWEST-NUMBERED of the states 2 .. 5 whose condition holds, else 1:
+ *     0  the slot is inactive (its object is -1);
+ *     5  the drawn bank box is not present (it collides with nothing);
+ *     2  the candidate collides with a present gt of the frame;
+ *     3  the candidate collides with an earlier PASTED candidate;
+ *     4  the object's point count exceeds free_left;
+ *     1  otherwise: the object is pasted and free_left decreases by its point count.
+ *   This is greedy in slot order.  It is NOT pcdet's all-pairs rejection, which also rejects a candidate for a neighbour that is itself
+ *   rejected.
+ *   REMOVAL: a row that is present on input and usable (|x|, |y|, |z| <= 1e6) is tested against every pasted box, enlarged ONCE by the
+ *   extra width as snowgpu_roi_point_pool_device enlarges a roi (pcdet's REMOVE_EXTRA_WIDTH; a box the enlargement makes absent removes
+ *   nothing), by the membership rule of snowgpu_points_in_boxes_device.  A row inside any such box gets keep 0; its row bytes stay.  Pasted
+ *   rows are never tested.
+ *   PLACEMENT: the frame's rows that are absent on input, in ascending row index, are its free list.  The pasted objects take it front to
+ *   back in slot order, each object's points in bank order as bit copies of all five columns, keep 1, source B + q.  Unused free slots keep
+ *   their input bytes and keep 0.  Absent rows are never read as numbers.
+ * Outputs, every shape static, every element written by every call:
+ *   d_out_rows      (N, 5) T and d_out_keep (N) bytes: the batch after the paste, same offsets
+ *   d_out_gt_boxes  (F, B + Q, Cb) T: rows 0 .. B - 1 bit copies of the input; row B + q the 8 bank columns of slot q's object when it was
+ *                   pasted, zeros in columns 8 and 9; otherwise a zero row
+ *   d_out_object    (F, Q) int32: the bank object slot q drew, -1 for an inactive slot
+ *   d_out_state     (F, Q) int32: as numbered above
+ *   d_out_source    (N) int32, or NULL: B + q for a pasted row, -1 for every other row
+ *   d_out_count     (F, 4) int32: objects pasted, rows pasted, scene rows removed, free slots on input
+ *   d_out_pose      (F, B + Q, 2) float64, or NULL: the pose used, (0, 0) for absent boxes and unpasted slots
+ * Domain: 1 <= Q <= 64; 1 <= NC <= 16; 1 <= B, B + Q <= 256; Cb in 8 .. 10; n_c >= 0; the extra width finite, in 0 .. 100;
+ * F (B + Q) Cb <= 2^31 - 1; N, P, O < 2^31; a frame of at most 2^30 rows; d_step not NULL; dtype 0 or 1; every output apart from every input
+ * and every other output -- there is no in-place form.  Anything else is SNOWGPU_E_INVALID with a message.  The bank's offsets and class
+ * offsets are device data and are trusted: they must ascend and end at P and O.
+ * Three kernels on `stream` (csrc/snowgpu_paste.hip): one wave per 512-row run counts the absent rows (only with a mask); one workgroup
+ * per frame scans the counts, counts the gt classes, draws, clips the Q x B and Q x Q pairs into one 64-bit word per side by LDS
+ * atomicOr, sweeps on one lane and writes the per-slot outputs and the frame's scratch record; one lane per row copies, tests or fills.
+ * The removed count is an integer add per workgroup.  No memset, no floating-point atomic, nothing read on the host, nothing allocated
+ * after the first call of a size: capturable as a linear graph, and two calls give identical bytes.  The scratch is the context's: calls on
+ * streams that are not ordered against each other need a context each.  The frame's position in the batch is part of the counter.
+ */
+int snowgpu_paste_objects_device(snowgpu_ctx *ctx, int n_frames, int64_t n_total, int64_t max_frame_rows, const int64_t *d_frame_offsets,
+                                 const void *d_rows, int dtype, int n_gt, const void *d_gt_boxes, int gt_features, const double *d_pose_in /* or NULL */,
+                                 int64_t n_bank_points, int64_t n_bank_objects, const void *d_bank_points, const int64_t *d_bank_offsets,
+                                 const void *d_bank_boxes, const double *d_bank_pose, const int32_t *d_class_offsets, int n_classes,
+                                 const int32_t *sample_groups /* host */, const double *extra_width3 /* host, or NULL */, uint64_t seed,
+                                 const uint64_t *d_step, const uint8_t *d_keep_in /* or NULL */, void *d_out_rows, uint8_t *d_out_keep,
+                                 void *d_out_gt_boxes, int32_t *d_out_object, int32_t *d_out_state, int32_t *d_out_source /* or NULL */,
+                                 int32_t *d_out_count, double *d_out_pose /* or NULL */, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

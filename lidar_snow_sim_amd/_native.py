@@ -33,7 +33,7 @@ EXPORTS = [
     "snowgpu_voxelize_device", "snowgpu_fps_device", "snowgpu_ball_query_device", "snowgpu_range_image_device",
     "snowgpu_nearest_centres_device", "snowgpu_points_in_boxes_device", "snowgpu_boxes_iou_device", "snowgpu_nms_device", "snowgpu_fps_sectors_device",
     "snowgpu_roi_point_pool_device", "snowgpu_roi_voxel_pool_device", "snowgpu_sample_rois_device",
-    "snowgpu_assign_anchors_device",
+    "snowgpu_assign_anchors_device", "snowgpu_paste_objects_device",
 ]
 
 WET_ESTIMATION = {"linear": 0, "poly": 1}
@@ -166,6 +166,9 @@ def lib():
             L.snowgpu_assign_anchors_device.restype = ctypes.c_int
             L.snowgpu_assign_anchors_device.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                         ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), vp, vp, vp, vp, vp, vp]
+            L.snowgpu_paste_objects_device.restype = ctypes.c_int
+            L.snowgpu_paste_objects_device.argtypes = [vp, ctypes.c_int, i64, i64, vp, vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, vp, i64, i64, vp, vp, vp, vp, vp,
+                                                       ctypes.c_int, vp, vp, ctypes.c_uint64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
             L.snowgpu_fov_mask_device.restype = ctypes.c_int
             L.snowgpu_fov_mask_device.argtypes = [vp, i64, vp, ctypes.c_int, vp, vp, vp, ctypes.c_int, ctypes.c_int, vp, vp, vp]
             L.snowgpu_dror_mask_device.restype = ctypes.c_int
@@ -787,6 +790,26 @@ class Context:
                                                    (ctypes.c_double * max(len(m), 1))(*m), (ctypes.c_double * max(len(u), 1))(*u), vp(d_out_label or None),
                                                    vp(d_out_gt_index or None), vp(d_out_count or None), vp(d_out_gt_count or None), vp(d_out_iou or None),
                                                    vp(stream or None))
+        self._check_args(rc)
+
+    def paste_objects_device(self, n_frames, n_total, max_frame_rows, d_frame_off, d_rows, dtype_code, n_gt, d_gt_boxes, gt_features, d_pose_in, n_bank_points,
+                             n_bank_objects, d_bank_points, d_bank_offsets, d_bank_boxes, d_bank_pose, d_class_offsets, sample_groups, extra_width, seed, d_step,
+                             d_keep_in, d_out_rows, d_out_keep, d_out_gt_boxes, d_out_object, d_out_state, d_out_source, d_out_count, d_out_pose, stream=0):
+        """Database objects pasted into the absent slots of an aligned batch (include/snowgpu.h: snowgpu_paste_objects_device); asynchronous
+        on `stream`.  sample_groups: one whole number per class (host), their number is n_classes; extra_width: None or three numbers (host);
+        d_step: a uint64 in device memory, read by the kernel.  d_pose_in, d_keep_in, d_out_source and d_out_pose may be 0.  An argument
+        outside the domain, or an output overlapping an input or another output, raises ValueError with the entry's words."""
+        vp = ctypes.c_void_p
+        groups = np.ascontiguousarray([_i32(v) for v in sample_groups], np.int32).reshape(-1)
+        ew = None if extra_width is None else np.ascontiguousarray(extra_width, np.float64).reshape(3)
+        rc = self._L.snowgpu_paste_objects_device(self._h, int(n_frames), int(n_total), int(max_frame_rows), vp(d_frame_off or None), vp(d_rows or None),
+                                                  int(dtype_code), _i32(n_gt), vp(d_gt_boxes or None), _i32(gt_features), vp(d_pose_in or None),
+                                                  int(n_bank_points), int(n_bank_objects), vp(d_bank_points or None), vp(d_bank_offsets or None),
+                                                  vp(d_bank_boxes or None), vp(d_bank_pose or None), vp(d_class_offsets or None), _i32(len(groups)),
+                                                  _p(groups if len(groups) else np.zeros(1, np.int32)), None if ew is None else _p(ew), ctypes.c_uint64(int(seed) & (2 ** 64 - 1)),
+                                                  vp(d_step or None), vp(d_keep_in or None), vp(d_out_rows or None), vp(d_out_keep or None),
+                                                  vp(d_out_gt_boxes or None), vp(d_out_object or None), vp(d_out_state or None), vp(d_out_source or None),
+                                                  vp(d_out_count or None), vp(d_out_pose or None), vp(stream or None))
         self._check_args(rc)
 
     def set_fov(self, calib=None, img_shape=(1024, 1920), pre_crop=False):

@@ -370,6 +370,16 @@ int sg_launch_assign_anchors(const struct SgAnchorCfg *cfg, int n_frames, int32_
                              const int32_t *anchor_class, int32_t n_gt, const void *gt, int32_t gt_features, int dtype, void *recs,
                              unsigned long long *top, int32_t *blk, int32_t *out_label, int32_t *out_gt_index, int32_t *out_count,
                              int32_t *out_gt_count, void *out_iou, void *stream);
+// Ground-truth object paste (sg_paste.h; the definition: include/snowgpu.h): three kernels, the first only with a keep mask.  groups and ew
+// (3 doubles): host.  table: sg_paste_table() int32, frames: sg_paste_frames() records, grid: sg_paste_grid() words, all scratch.  keep,
+// pose_in, out_source and out_pose may be null.
+struct SgPasteGroups;
+struct SgPasteFrame;
+int sg_launch_paste(const void *rows, int dtype, int64_t n_total, int64_t max_frame, const int64_t *off, int n_frames, const uint8_t *keep, int32_t n_gt,
+                    const void *gt, int32_t gt_features, const double *pose_in, const void *bank_points, const int64_t *bank_off, const void *bank_boxes,
+                    const double *bank_pose, const int32_t *class_off, const struct SgPasteGroups *groups, const double *ew, uint64_t seed,
+                    const uint64_t *d_step, int32_t *table, struct SgPasteFrame *frames, unsigned long long *grid, void *out_rows, uint8_t *out_keep, void *out_gt, int32_t *out_object,
+                    int32_t *out_state, int32_t *out_source, int32_t *out_count, double *out_pose, void *stream);
 #ifdef __cplusplus
 }
 #endif

@@ -788,6 +788,82 @@ static inline int sg_check_anchors_args(const SgAnchorsArgs &a, std::string *msg
     return sg_check_overlaps(who, outs, ins, "the targets are", true, msg);
 }
 
+// ---- snowgpu_paste_objects_device ---------------------------------------------------------------------------------------------------------
+struct SgPasteArgs {
+    int n_frames;
+    int64_t n_total, max_frame_rows;
+    int dtype;
+    const int64_t *frame_off;
+    const void *rows;
+    int n_gt;                         // B, per frame
+    const void *gt_boxes;
+    int gt_features;                  // Cb: column 7 is the class
+    const double *pose_in;            // or NULL: cos / sin of the heading on the device
+    int64_t bank_points_n, bank_objects_n;        // P, O
+    const void *bank_points;
+    const int64_t *bank_off;
+    const void *bank_boxes;
+    const double *bank_pose;
+    const int32_t *class_off;         // 18 int32
+    int n_classes;                    // NC
+    const int32_t *groups;            // host, NC counts
+    const double *extra_width;        // host, 3 doubles, or NULL: zeros
+    const uint64_t *step;             // device
+    const uint8_t *keep_in;           // or NULL: every row is present
+    void *out_rows;
+    uint8_t *out_keep;
+    void *out_gt_boxes;
+    int32_t *out_object, *out_state;
+    int32_t *out_source;              // or NULL
+    int32_t *out_count;
+    double *out_pose;                 // or NULL
+};
+
+// the sum of the first min(NC, 16) sample groups, 0 without any
+static inline int64_t sg_paste_slots(int n_classes, const int32_t *groups)
+{
+    int64_t Q = 0;
+    for (int c = 0; groups && c < n_classes && c < 16; ++c) Q += groups[c];
+    return Q;
+}
+
+// 0, or SG_ARGS_INVALID with *msg.  As above, the order is part of the ABI.
+static inline int sg_check_paste_args(const SgPasteArgs &a, std::string *msg)
+{
+    static const char *who = "snowgpu_paste_objects_device", *read = "the mask, the rows, the gt boxes, the pose, the bank and the step are";
+    if (int rc = sg_check_head(who, a.n_frames, a.dtype, a.n_total < 0 || !a.frame_off || !a.gt_boxes || !a.bank_off || !a.bank_boxes || !a.bank_pose || !a.class_off ||
+                                   !a.groups || !a.out_gt_boxes || !a.out_object || !a.out_state || !a.out_count || a.bank_points_n < 0 || a.bank_objects_n < 0 ||
+                                   (a.bank_points_n > 0 && !a.bank_points) || (a.n_total > 0 && (!a.rows || !a.out_rows || !a.out_keep)), msg))
+        return rc;
+    const int64_t Q = sg_paste_slots(a.n_classes, a.groups);
+    if (Q < 1 || Q > 64) return sg_refuse(who, ": the sample groups must add up to 1 .. 64 slots", msg);
+    if (a.n_classes < 1 || a.n_classes > 16) return sg_refuse(who, ": n_classes must lie in 1 .. 16", msg);
+    if (a.n_gt < 1 || (int64_t)a.n_gt + Q > 256) return sg_refuse(who, ": n_gt must be at least 1 and n_gt plus the slots at most 256", msg);
+    if (a.gt_features < 8 || a.gt_features > 10)
+        return sg_refuse(who, ": gt_features must lie in 8 .. 10: cx, cy, cz, dx, dy, dz, heading, class first", msg);
+    for (int c = 0; c < a.n_classes; ++c)
+        if (a.groups[c] < 0) return sg_refuse(who, ": a sample group is negative", msg);
+    if (int rc = sg_check_extra_width(who, a.extra_width, msg)) return rc;
+    if ((int64_t)a.n_frames * (a.n_gt + Q) * a.gt_features > ((int64_t)1 << 31) - 1)
+        return sg_refuse(who, ": n_frames * (n_gt + slots) * gt_features exceeds 2^31 - 1; split the batch", msg);
+    if (int rc = sg_check_rows(a.n_total, msg)) return rc;
+    if (a.bank_points_n >= ((int64_t)1 << 31) || a.bank_objects_n >= ((int64_t)1 << 31)) return sg_refuse(who, ": the bank must stay below 2^31 points and objects", msg);
+    if (int rc = sg_check_frame(who, sg_max_frame(a.max_frame_rows, a.n_total), msg)) return rc;
+    if (!a.step) return sg_refuse(who, ": d_step is NULL; one uint64 in device memory", msg);
+    const size_t esz = a.dtype == 0 ? 4 : 8, n = (size_t)a.n_total, F = (size_t)a.n_frames, g = F * (size_t)a.n_gt, k = F * (size_t)(a.n_gt + Q),
+                 P = (size_t)a.bank_points_n, O = (size_t)a.bank_objects_n;
+    const SgOutSpan outs[8] = {
+        {a.out_rows, n * 5 * esz, "d_out_rows"}, {a.out_keep, n, "d_out_keep"}, {a.out_gt_boxes, k * (size_t)a.gt_features * esz, "d_out_gt_boxes"},
+        {a.out_object, F * (size_t)Q * 4, "d_out_object"}, {a.out_state, F * (size_t)Q * 4, "d_out_state"}, {a.out_source, n * 4, "d_out_source"},
+        {a.out_count, F * 16, "d_out_count"}, {a.out_pose, k * 16, "d_out_pose"}};
+    const SgInSpan ins[11] = {{a.keep_in, n, "d_keep_in", read, "them"}, {a.rows, n * 5 * esz, "d_rows", read, "them"}, {a.frame_off, (F + 1) * 8, "d_frame_offsets", read, "them"},
+                              {a.gt_boxes, g * (size_t)a.gt_features * esz, "d_gt_boxes", read, "them"}, {a.pose_in, g * 16, "d_pose_in", read, "them"},
+                              {a.bank_points, P * 5 * esz, "d_bank_points", read, "them"}, {a.bank_off, (O + 1) * 8, "d_bank_offsets", read, "them"},
+                              {a.bank_boxes, O * 8 * esz, "d_bank_boxes", read, "them"}, {a.bank_pose, O * 16, "d_bank_pose", read, "them"},
+                              {a.class_off, 18 * 4, "d_class_offsets", read, "them"}, {a.step, 8, "d_step", read, "them"}};
+    return sg_check_overlaps(who, outs, ins, "the batch is", true, msg);
+}
+
 // 0, or SG_ARGS_INVALID with *msg (built on this path only).  The order is part of the ABI: it decides which message a doubly wrong call gets.
 static inline int sg_check_device_args(const SgDeviceArgs &a, const SgCtxView &c, const SgEntryShape &s, std::string *msg)
 {

@@ -133,6 +133,12 @@ struct __attribute__((visibility("default"))) snowgpu_ctx {
     DevBuf<double> anchor_rec;
     DevBuf<unsigned long long> anchor_top;
     DevBuf<int32_t> anchor_blk;
+    // object paste (snowgpu_paste_objects_device): one int32 per (frame, run of 512 rows) -- the run's absent rows, then those of the runs
+    // before it --, one SgPasteFrame (bytes) per frame: the pasted slots' bases and enlarged boxes, and one word per (frame, grid cell):
+    // the pasted boxes that can reach the cell (32 KB a frame)
+    DevBuf<int32_t> paste_runs;
+    DevBuf<uint8_t> paste_frames;
+    DevBuf<unsigned long long> paste_grid;
     // scratch shared by every batch
     DevBuf<int32_t> tile_hist, tile_base, perm, ctile_cnt, ctile_base, table_ids, out_src;
     DevBuf<uint8_t> srows;            // channel-sorted copy of the frames whose rows did not come channel-sorted (firing order)

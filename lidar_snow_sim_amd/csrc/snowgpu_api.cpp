@@ -154,6 +154,7 @@ extern "C" void snowgpu_destroy(snowgpu_ctx *ctx)
     ctx->rv_rec.release(); ctx->rv_table.release(); ctx->rv_runs.release(); ctx->rv_list.release(); ctx->rv_sorted.release(); ctx->rv_offset.release();
     ctx->iou_rec.release(); ctx->nms_order.release(); ctx->nms_cand.release();
     ctx->anchor_rec.release(); ctx->anchor_top.release(); ctx->anchor_blk.release();
+    ctx->paste_runs.release(); ctx->paste_frames.release(); ctx->paste_grid.release();
     sg_prepass_release(&ctx->prepass);
     sg_plane_release(&ctx->plane_scr);
     ctx->plane_est.release(); ctx->wet_plane_est.release(); ctx->plane_info.release(); ctx->stats_hist.release(); ctx->stats_rec.release();

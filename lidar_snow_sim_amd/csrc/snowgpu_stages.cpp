@@ -19,6 +19,7 @@
 #include "sg_range.h"       // the geometry of the range image and the limits in the rows' dtype
 #include "sg_targets.h"     // SgTargetCfg of the proposal target sampling
 #include "sg_anchors.h"     // SgAnchorCfg and the record of the anchor target assignment
+#include "sg_paste.h"       // SgPasteGroups and the scratch of the object paste
 
 // one of the sg_check_*_args on its arguments: SNOWGPU_OK, or the refusal with its message in the context
 template <class... Params, class... Args>
@@ -399,4 +400,35 @@ extern "C" int snowgpu_assign_anchors_device(snowgpu_ctx *ctx, int n_frames, int
                     sg_launch_assign_anchors(&k, n_frames, n_anchors, d_anchors, anchor_features, d_anchor_class, n_gt, d_gt_boxes, gt_features, dtype, ctx->anchor_rec.p,
                                              ctx->anchor_top.p, ctx->anchor_blk.p, d_out_label, d_out_gt_index, d_out_count, d_out_gt_count, d_out_iou,
                                              stream_of(ctx, stream)));
+}
+
+// Ground-truth object paste (snowgpu_paste.hip; the slots, the draw, the sweep and the scratch: sg_paste.h).  See include/snowgpu.h.
+extern "C" int snowgpu_paste_objects_device(snowgpu_ctx *ctx, int n_frames, int64_t n_total, int64_t max_frame_rows, const int64_t *d_frame_offsets,
+                                            const void *d_rows, int dtype, int n_gt, const void *d_gt_boxes, int gt_features, const double *d_pose_in,
+                                            int64_t n_bank_points, int64_t n_bank_objects, const void *d_bank_points, const int64_t *d_bank_offsets,
+                                            const void *d_bank_boxes, const double *d_bank_pose, const int32_t *d_class_offsets, int n_classes,
+                                            const int32_t *sample_groups, const double *extra_width3, uint64_t seed, const uint64_t *d_step,
+                                            const uint8_t *d_keep_in, void *d_out_rows, uint8_t *d_out_keep, void *d_out_gt_boxes, int32_t *d_out_object,
+                                            int32_t *d_out_state, int32_t *d_out_source, int32_t *d_out_count, double *d_out_pose, void *stream)
+{
+    if (!ctx) return SNOWGPU_E_INVALID;
+    const SgPasteArgs a{n_frames, n_total, max_frame_rows, dtype, d_frame_offsets, d_rows, n_gt, d_gt_boxes, gt_features, d_pose_in, n_bank_points, n_bank_objects,
+                        d_bank_points, d_bank_offsets, d_bank_boxes, d_bank_pose, d_class_offsets, n_classes, sample_groups, extra_width3, d_step, d_keep_in,
+                        d_out_rows, d_out_keep, d_out_gt_boxes, d_out_object, d_out_state, d_out_source, d_out_count, d_out_pose};
+    if (int rc = checked(ctx, sg_check_paste_args, a)) return rc;
+    double ew[3];
+    extra_width_of(extra_width3, ew);
+    SgPasteGroups g{};
+    g.n_classes = n_classes;
+    for (int c = 0; c < n_classes; ++c) { g.n[c] = sample_groups[c]; g.Q += sample_groups[c]; }
+    const int64_t longest = sg_max_frame(max_frame_rows, n_total);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    ENSURE(ctx, ctx->paste_runs, sg_paste_table(n_frames, longest));
+    ENSURE(ctx, ctx->paste_frames, sg_paste_frames(n_frames) * sizeof(SgPasteFrame));
+    ENSURE(ctx, ctx->paste_grid, sg_paste_grid(n_frames));
+    return launched(ctx, "object paste",
+                    sg_launch_paste(d_rows, dtype, n_total, longest, d_frame_offsets, n_frames, d_keep_in, n_gt, d_gt_boxes, gt_features, d_pose_in, d_bank_points,
+                                    d_bank_offsets, d_bank_boxes, d_bank_pose, d_class_offsets, &g, ew, seed, d_step, ctx->paste_runs.p,
+                                    (SgPasteFrame *)ctx->paste_frames.p, ctx->paste_grid.p, d_out_rows, d_out_keep, d_out_gt_boxes, d_out_object, d_out_state, d_out_source, d_out_count,
+                                    d_out_pose, stream_of(ctx, stream)));
 }

@@ -1,6 +1,6 @@
 """The device stages of the torch-tensor boundary (tensors.py is the documented import path and lists what each is for) and the batches
 of static shape they leave behind: fov_keep, dror_keep, voxelize, sample_keypoints, ball_query, range_image, nearest_keypoints,
-points_in_boxes, boxes_iou, nms, roi_point_pool, roi_voxel_pool, sample_rois, assign_anchors.  Every stage goes through the same steps, in this order -- it is the order in which a call that is wrong
+points_in_boxes, boxes_iou, nms, roi_point_pool, roi_voxel_pool, sample_rois, assign_anchors, paste_objects.  Every stage goes through the same steps, in this order -- it is the order in which a call that is wrong
 in two ways is refused: the aligned unwrap and the device-input refusal (_stage_frames), the scalar and range checks (_whole, _range6),
 the batch and its keep mask (_stage_batch), the stage's own tensors, the checks of the shapes' domain, out= (_checked_out), the launch
 (_stage_launch).  PyTorch is plumbing here; the work is the C entries'."""
@@ -1358,3 +1358,176 @@ def assign_anchors(anchors, anchor_class, gt_boxes, matched=(0.6, 0.5, 0.5), unm
                                       out.label.data_ptr(), out.gt_index.data_ptr(), out.count.data_ptr(), out.gt_count.data_ptr(),
                                       0 if iou is None else iou.data_ptr(), run.cuda_stream)
     return out if (iou is None) == (out.iou is None) else AnchorTargetBatch(out.label, out.gt_index, out.count, out.gt_count, iou)
+
+
+PASTE_STATES = {"inactive": 0, "pasted": 1, "hit_gt": 2, "hit_pasted": 3, "no_room": 4, "absent": 5}
+
+
+class ObjectBank:
+    """A database of objects for paste_objects(), resident on the device and made once, outside any capture: `points` (P, 5 in the rows'
+    dtype: x, y, z, intensity, channel as cropped from real sweeps -- positions are kept, so channel and range stay valid for the snowfall
+    stage), `offsets` (O + 1 int64: object o's points are [offsets[o], offsets[o + 1])), `boxes` (O, 8: the seven box columns and the class
+    in column 7), `pose` (O, 2 float64 (cos, sin); None: cos / sin of the heading on the device, computed here once) and `class_offsets` (18
+    int32 on the device: the objects of class c = 1 .. 16 are [class_offsets[c], class_offsets[c + 1])).  The constructor reads the offsets
+    and the classes on the host: offsets must start at 0, ascend and end at P; classes must be integral, in 1 .. 16 and ascending over the
+    objects (lidar_snow_sim_amd.paste.build_bank sorts them).  P and O stay below 2^31."""
+
+    def __init__(self, points, offsets, boxes, pose=None):
+        import torch
+        who = "ObjectBank"
+        if not (torch.is_tensor(points) and points.is_cuda and points.dim() == 2 and points.shape[1] == 5 and points.dtype in (torch.float32, torch.float64) and
+                points.is_contiguous()):
+            raise ValueError(f"{who}: points must be a contiguous (P, 5) float32 or float64 CUDA tensor")
+        dev, dt = points.device, points.dtype
+        if not (torch.is_tensor(boxes) and boxes.dim() == 2 and boxes.shape[1] == 8 and boxes.dtype == dt and boxes.device == dev and boxes.is_contiguous()):
+            raise ValueError(f"{who}: boxes must be a contiguous (O, 8) tensor of the points' dtype on their device: seven box columns and the class")
+        P, O = int(points.shape[0]), int(boxes.shape[0])
+        if O < 1 or P >= 2 ** 31 or O >= 2 ** 31:
+            raise ValueError(f"{who}: the bank must hold an object and stay below 2^31 points and objects")
+        off = offsets.detach().cpu().numpy() if torch.is_tensor(offsets) else np.asarray(offsets)
+        if off.dtype.kind not in "iu" or off.shape != (O + 1,):
+            raise ValueError(f"{who}: offsets must hold O + 1 = {O + 1} whole numbers")
+        off = off.astype(np.int64)
+        if off[0] != 0 or off[-1] != P or (np.diff(off) < 0).any():
+            raise ValueError(f"{who}: offsets must start at 0, ascend and end at the number of points")
+        cls = boxes[:, 7].detach().cpu().numpy().astype(np.float64)
+        if not (np.isfinite(cls).all() and (cls == np.floor(cls)).all() and (cls >= 1).all() and (cls <= 16).all() and (np.diff(cls) >= 0).all()):
+            raise ValueError(f"{who}: the classes (column 7 of boxes) must be integral, in 1 .. 16 and ascending over the objects")
+        if pose is None:
+            h = boxes[:, 6].to(torch.float64)
+            pose = torch.stack((torch.cos(h), torch.sin(h)), dim=1).contiguous()
+        elif not (torch.is_tensor(pose) and tuple(pose.shape) == (O, 2) and pose.dtype == torch.float64 and pose.device == dev and pose.is_contiguous()):
+            raise ValueError(f"{who}: pose must be a contiguous {(O, 2)} float64 tensor (cos, sin) on the device of the points")
+        self.points, self.boxes, self.pose = points, boxes, pose
+        self.offsets = torch.from_numpy(off).to(dev)
+        self.classes = cls.astype(np.int64)
+        self.class_offsets_host = np.searchsorted(self.classes, np.arange(18), side="left").astype(np.int32)
+        self.class_offsets = torch.from_numpy(self.class_offsets_host).to(dev)
+        self.n_points, self.n_objects = P, O
+
+
+class PasteBatch:
+    """What paste_objects() leaves behind, N = rows of the batch, F = frames, B = gt boxes per frame on input, Q = slots -- every shape
+    static: `rows` (N, 5) and `keep` (N bool): the batch after the paste, same offsets -- with `gt_boxes` they go straight into
+    augment_batch(..., layout='aligned', keep=) and every later stage; `gt_boxes` (F, B + Q, Cb: the input's rows, then the box of every
+    pasted slot, a zero row for every other slot); `object` (F, Q int32: the bank object a slot drew, -1 for an inactive slot); `state`
+    (F, Q int32: PASTE_STATES); `source` (N int32: B + q for a pasted row, -1 otherwise; None unless asked for); `count` (F, 4 int32:
+    objects pasted, rows pasted, scene rows removed, free slots on input) and `pose` (F, B + Q, 2 float64: the pose used, (0, 0) for absent
+    boxes; None unless asked for).  All still being written until the stream the call was made on has caught up."""
+
+    def __init__(self, rows, keep, gt_boxes, object, state, count, source=None, pose=None, offsets=None):
+        self.rows, self.keep, self.gt_boxes, self.object, self.state, self.count, self.source, self.pose = rows, keep, gt_boxes, object, state, count, source, pose
+        self.offsets = np.array([0, rows.shape[0]], np.int64) if offsets is None else np.asarray(offsets, np.int64)
+        self._base = None
+
+    @classmethod
+    def empty(cls, offsets, n_gt, n_slots, gt_features=8, dtype=None, device=None, with_source=True, with_pose=False):
+        """Uninitialised buffers of the shapes paste_objects() writes for a batch with these frame offsets (or, for one frame, this number
+        of rows) (out=): static addresses for a captured graph."""
+        import torch
+        dev, dt = _cuda_device(torch, device), dtype or torch.float32
+        off = np.array([0, int(offsets)], np.int64) if np.ndim(offsets) == 0 else np.asarray(offsets, np.int64)
+        n, F, BQ, Q = int(off[-1]), len(off) - 1, int(n_gt) + int(n_slots), int(n_slots)
+
+        def new(shape, kind):
+            return torch.empty(shape, dtype=kind, device=dev)
+        return cls(new((n, 5), dt), new((n,), torch.bool), new((F, BQ, int(gt_features)), dt), new((F, Q), torch.int32), new((F, Q), torch.int32),
+                   new((F, 4), torch.int32), new((n,), torch.int32) if with_source else None, new((F, BQ, 2), torch.float64) if with_pose else None, off)
+
+    @property
+    def pasted(self):
+        """(F, Q) bool: state == 1 -- the slot's object is in the batch."""
+        return self.state == 1
+
+    def labels(self, background=0):
+        """(N,) in the boxes' dtype: the class (column 7 of gt_boxes) of every pasted row's object, `background` for every other row.
+        Plain indexing; the first call of a batch of several frames uploads their row counts (make it before capturing a graph)."""
+        import torch
+        if self.source is None:
+            raise ValueError("labels: this PasteBatch has no source (paste_objects(..., return_source=True))")
+        at = self.source.long()
+        if len(self.offsets) > 2:
+            if self._base is None:
+                counts = torch.from_numpy(np.diff(self.offsets)).to(at.device)
+                first = torch.arange(len(counts), device=at.device) * self.gt_boxes.shape[1]
+                self._base = torch.repeat_interleave(first, counts, output_size=int(self.offsets[-1]))
+            at = torch.where(at >= 0, at + self._base, at)
+        cls = self.gt_boxes[:, :, 7].reshape(-1)[at.clamp(min=0)]
+        return torch.where(at >= 0, cls, torch.full_like(cls, background))
+
+
+def paste_objects(frames, gt_boxes, bank, sample_groups, *, step, seed=0, keep=None, remove_extra_width=(0., 0., 0.), pose=None, out=None,
+                  return_source=True, return_pose=False, device=None, slot=0):
+    """Ground-truth sampling on the device (snowgpu_paste_objects_device; the definition: include/snowgpu.h): pcdet's DataBaseSampler with
+    static shapes, nothing read on the host and a seeded draw.  Per frame and class, as many bank objects are drawn as the frame lacks of
+    sample_groups; a candidate that overlaps a gt or an earlier pasted candidate in the BEV, or has more points than the frame has absent
+    rows left, is dropped; the others are written into the frame's ABSENT rows (keep False on input: the padding of an F x Nmax x 5 batch),
+    their boxes appended to the gt boxes, and the scene rows inside them cleared from the keep mask.  No shape changes.  The definition is
+    this library's, modelled on pcdet's sampler: greedy in slot order, no road-plane correction, no occlusion of the scene behind an object.
+    Paste BEFORE the snowfall stage, so that flakes occlude and attenuate the objects as they do the scene.
+
+    frames     what points_in_boxes takes -- torch CUDA tensors, a DeviceBatch, or an AlignedResult / AlignedWetResult (its keep is ANDed).
+    gt_boxes   a contiguous (F, B, 8 .. 10) tensor in the rows' dtype on their device: column 7 is the class; zero rows are padding.
+    bank       an ObjectBank of the rows' dtype on their device.
+    sample_groups   one whole number n_c >= 0 per class c = 1 .. NC, NC <= 16 (pcdet's SAMPLE_GROUPS); Q = sum n_c in 1 .. 64, B + Q <= 256.
+    step       a one-element int64 tensor on the device of the rows (WeatherPlan.step as it stands), read by the kernel.
+    seed       the key of the draw; the objects of frame f depend on (seed, step, f) and the frame's own gts.
+    keep       an input keep mask as the aligned calls take it; None: every row is present, so nothing with points can be pasted.
+    remove_extra_width   a number or three (x, y, z), each in 0 .. 100 (pcdet's REMOVE_EXTRA_WIDTH).
+    pose       None: cos / sin of the gts' heading in float64 on the device; or a contiguous (F, B, 2) float64 tensor used as it is.
+    out        a PasteBatch to write into (PasteBatch.empty): every element is written; its rows and keep must not be the inputs.
+
+    Returns a PasteBatch.  Asynchronous on torch's current stream; nothing is read on the host: capturable after one warm-up call."""
+    import torch
+    who = "paste_objects"
+    frames, keep = _stage_frames(torch, who, "lidar_snow_sim_amd.paste.paste_objects", frames, keep)
+    try:
+        groups = list(sample_groups)
+    except TypeError:
+        raise ValueError(f"{who}: sample_groups holds one whole number per class") from None
+    _whole(who, **{f"sample_groups[{c}]": v for c, v in enumerate(groups)})
+    groups = [int(v) for v in groups]
+    ew = np.asarray(remove_extra_width, np.float64).reshape(-1)
+    if ew.shape == (1,):
+        ew = np.repeat(ew, 3)
+    if ew.shape != (3,) or not ((ew >= 0.0) & (ew <= 100.0)).all():
+        raise ValueError(f"{who}: remove_extra_width is a number or three (x, y, z), each finite and in 0 .. 100")
+    rows, offsets, eng, dev, nf, n, keep = _stage_batch(torch, frames, keep, device, slot)
+    if not (torch.is_tensor(gt_boxes) and gt_boxes.dim() == 3 and gt_boxes.shape[0] == nf and gt_boxes.dtype == rows.dtype and gt_boxes.device == dev and
+            gt_boxes.is_contiguous()):
+        raise ValueError(f"{who}: gt_boxes must be a contiguous (frames, B, 8 .. 10) tensor in the rows' dtype on their device")
+    if not (isinstance(bank, ObjectBank) and bank.points.dtype == rows.dtype and bank.points.device == dev):
+        raise ValueError(f"{who}: bank must be an ObjectBank in the rows' dtype on their device")
+    if not (torch.is_tensor(step) and step.numel() == 1 and step.dtype == torch.int64 and step.device == dev):
+        raise ValueError(f"{who}: step must be a one-element int64 tensor on the device of the rows")
+    B, Cb, NC, Q = int(gt_boxes.shape[1]), int(gt_boxes.shape[2]), len(groups), sum(groups[:16])
+    # (the shapes below need these; the entry refuses them in the same words, and everything else of the domain)
+    if not 1 <= Q <= 64:
+        raise ValueError(f"{who}: the sample groups must add up to 1 .. 64 slots")
+    if not 1 <= NC <= 16:
+        raise ValueError(f"{who}: n_classes must lie in 1 .. 16 (sample_groups)")
+    if B < 1 or B + Q > 256:
+        raise ValueError(f"{who}: n_gt must be at least 1 and n_gt plus the slots at most 256")
+    if not 8 <= Cb <= 10:
+        raise ValueError(f"{who}: gt_features must lie in 8 .. 10: cx, cy, cz, dx, dy, dz, heading, class first (gt_boxes)")
+    if min(groups) < 0:
+        raise ValueError(f"{who}: a sample group is negative")
+    if nf * (B + Q) * Cb > 2 ** 31 - 1:
+        raise ValueError(f"{who}: n_frames * (n_gt + slots) * gt_features exceeds 2^31 - 1; split the batch")
+    if pose is not None and not (torch.is_tensor(pose) and tuple(pose.shape) == (nf, B, 2) and pose.dtype == torch.float64 and pose.device == dev and pose.is_contiguous()):
+        raise ValueError(f"{who}: pose must be a contiguous {(nf, B, 2)} float64 tensor (cos, sin) on the device of the rows")
+    want = (("rows", rows.dtype, (n, 5), True), ("keep", torch.bool, (n,), True), ("gt_boxes", rows.dtype, (nf, B + Q, Cb), True),
+            ("object", torch.int32, (nf, Q), True), ("state", torch.int32, (nf, Q), True), ("count", torch.int32, (nf, 4), True),
+            ("source", torch.int32, (n,), return_source), ("pose", torch.float64, (nf, B + Q, 2), return_pose))
+    if out is None:
+        out = PasteBatch.empty(offsets, B, Q, Cb, rows.dtype, dev, return_source, return_pose)
+    else:
+        _checked_out(torch, who, PasteBatch, out, want, dev, _ROWS)
+    source, used = (out.source if return_source else None), (out.pose if return_pose else None)
+    _stage_launch(torch, eng, dev, nf, n, offsets, rows, eng.ctx.paste_objects_device, B, gt_boxes.data_ptr(), Cb, 0 if pose is None else pose.data_ptr(),
+                  bank.n_points, bank.n_objects, bank.points.data_ptr() if bank.n_points else 0, bank.offsets.data_ptr(), bank.boxes.data_ptr(),
+                  bank.pose.data_ptr(), bank.class_offsets.data_ptr(), groups, ew, seed, step.data_ptr(), 0 if keep is None or not n else keep.data_ptr(),
+                  out.rows.data_ptr() if n else 0, out.keep.data_ptr() if n else 0, out.gt_boxes.data_ptr(), out.object.data_ptr(), out.state.data_ptr(),
+                  0 if source is None or not n else source.data_ptr(), out.count.data_ptr(), 0 if used is None else used.data_ptr())
+    same = np.array_equal(out.offsets, np.asarray(offsets, np.int64)) and (source is None) == (out.source is None) and (used is None) == (out.pose is None)
+    return out if same else PasteBatch(out.rows, out.keep, out.gt_boxes, out.object, out.state, out.count, source, used, offsets)

@@ -52,6 +52,11 @@ The reference's training-time caller (the OpenPCDet DENSE dataset: `root_path`, 
     for a positive, 0 for background, -1 for ignored -- by the nearest axis-aligned BEV overlap per class, with the gt a positive regresses
     to (AnchorTargetBatch; snowgpu_assign_anchors_device): the assignment of pcdet's AxisAlignedTargetAssigner, fed the gts that
     `points_in_boxes(res, gt).keep_boxes(min_points)` left; `anchor_grid(...)` lays the anchors out as pcdet's AnchorGenerator does.
+  * `paste_objects(frames, gt_boxes, bank, sample_groups, step=...)` pastes database objects into the ABSENT rows of a padded batch, in
+    front of the snowfall stage -- per class as many as the frame lacks, drawn from an `ObjectBank` by (seed, step, frame), dropped where
+    they overlap a gt or an earlier object, their boxes appended to the gts and the scene rows inside them cleared (PasteBatch;
+    snowgpu_paste_objects_device): pcdet's DataBaseSampler; its `rows`, `keep` and `gt_boxes` feed `augment_batch(..., layout='aligned',
+    keep=)` and every stage behind it.
   * `augment_wet_batch_aligned(frames, ...)` is the snowfall + wet-ground chain with that aligned result (AlignedWetResult: per-frame
     flags beside it; snowgpu_augment_wet_batch_device_aligned), `wet_ground_batch_aligned(frames, keep)` the wet-ground stage alone on rows
     and a keep mask from any earlier stage (snowgpu_wet_ground_batch_device_aligned).
@@ -61,7 +66,7 @@ training loop that reshuffles `order` per frame uploads 64 int32 per frame).  Py
 no arithmetic of the simulation happens in this file.
 
 This module is the import path of all of it and holds the augmentation entries.  How a batch is read and a result handed back lives in
-batch.py, the stages from `fov_keep` to `assign_anchors` with their result classes in stages.py; every public name of both is re-exported here.
+batch.py, the stages from `fov_keep` to `paste_objects` with their result classes in stages.py; every public name of both is re-exported here.
 """
 from __future__ import annotations
 
@@ -74,8 +79,8 @@ import numpy as np
 from . import _native
 from .batch import (LANE_SLOT0, AlignedResult, AlignedWetResult, DeviceBatch, DeviceResult, _cuda_device, _keep_mask, _on_run_stream,  # noqa: F401
                     _resolve_input, _uploads, is_device_input)
-from .stages import (IOU_MODES, AnchorTargetBatch, BoxLabelBatch, IouBatch, KeypointBatch, NearestBatch, NeighbourBatch, NmsBatch, RangeImageBatch, RoiPointBatch, RoiTargetBatch, RoiVoxelBatch, VoxelBatch,  # noqa: F401
-                     _fov_mask, anchor_grid, assign_anchors, ball_query, boxes_iou, dror_keep, fov_keep, nearest_keypoints, nms, points_in_boxes, range_image, roi_point_pool,
+from .stages import (IOU_MODES, PASTE_STATES, AnchorTargetBatch, BoxLabelBatch, IouBatch, KeypointBatch, NearestBatch, NeighbourBatch, NmsBatch, ObjectBank, PasteBatch, RangeImageBatch, RoiPointBatch, RoiTargetBatch, RoiVoxelBatch, VoxelBatch,  # noqa: F401
+                     _fov_mask, anchor_grid, assign_anchors, ball_query, boxes_iou, dror_keep, fov_keep, nearest_keypoints, nms, paste_objects, points_in_boxes, range_image, roi_point_pool,
                      roi_voxel_pool, sample_keypoints, sample_rois, voxelize)
 
 
