@@ -1379,6 +1379,81 @@ int snowgpu_paste_objects_device(snowgpu_ctx *ctx, int n_frames, int64_t n_total
                                  void *d_out_gt_boxes, int32_t *d_out_object, int32_t *d_out_state, int32_t *d_out_source /* or NULL */,
                                  int32_t *d_out_count, double *d_out_pose /* or NULL */, void *stream);
 
+/*
+ * SCENE TRANSFORMS: the geometric augmentation behind gt_sampling -- OpenPCDet's random_world_flip, random_world_rotation and
+ * random_world_scaling and, per object, the noise of random_local_translation / rotation / scaling and of SECOND's noise_per_object -- on
+ * an aligned batch and its gt boxes, with static shapes, nothing read on the host and a seeded draw.  pcdet and SECOND are not part of the
+ * reference checkout: the definition below is THIS LIBRARY'S, modelled on pcdet's augmentor_utils and SECOND's per-object noise as
+ * recalled, and was NOT CHECKED against their source.  It is restated in NumPy and Python integers by tests/scene_reference.py;
+ * csrc/sg_scene.h holds its C++, for the device and for the host.
+ *   PLACE IN THE CHAIN: BEHIND the weather stages and range_image(ring=), which need rows in the sensor frame (range, beam and channel),
+ *   and IN FRONT of everything that groups or labels: voxelize, the keypoint stages, ball_query, points_in_boxes for labels, assign_anchors.
+ *   INPUTS, F = n_frames, B = n_boxes, T = float32 or float64: the aligned batch (d_rows (N, 5) T, d_frame_offsets, d_keep_in (N) bytes or
+ *   NULL: every row present); d_gt_boxes (F, B, Cb) T, Cb in 7 .. 10, columns 0 .. 6 cx, cy, cz, dx, dy, dz, heading; d_pose_in (F, B, 2)
+ *   float64 (cos, sin) or NULL; in HOST memory: flip (bit 0: the x axis is asked for, bit 1: the y axis), rotation2 and scaling2 (lo, hi;
+ *   NULL: the part is off), tries (the tries per box, 0: NO LOCAL PART, the next three are not read), local_translation3 (ax, ay, az: a
+ *   component is uniform in -a .. a), local_rotation2 and local_scaling2 (lo, hi), NULL each: off; seed; d_step, a uint64 in DEVICE
+ *   memory read by the kernel; d_box_of (N) int32 or NULL: the box of every row as snowgpu_points_in_boxes_device gives it for THESE
+ *   boxes under THIS pose -- with NULL and a local part the stage runs that stage's kernels itself, into scratch.
+ *   ARITHMETIC: float64 from (double) of the inputs, every operation rounded on its own, no fused multiply-add; one rounding to T at the
+ *   store.  A part that is off has the identity's values -- 0, (cos, sin) = (1, 0), 1 -- and goes through the same arithmetic, so it changes
+ *   no value (a -0 may become +0).
+ *   DRAWS: Philox4x32-10 under key `seed` at counter (step, frame f, 0x5846524D + b), the argument positions of the weather draw above.
+ *   Block 0 is the world block: flip_x iff the x axis is asked for and w0 < 2^31, flip_y likewise with w1, theta from w2, sigma from w3.
+ *   Blocks 1 + 2 (i T + t) and the next hold the five words of try t of box i: tx, ty, tz, delta from the first, s from w0 of the second.
+ *   A uniform value is lo + ((double)w 2^-32) (hi - lo), the difference, the product and the sum rounded each.  A part that is off draws
+ *   nothing but keeps its word positions.  cos / sin of theta and of every delta come from the device library; they are the only
+ *   transcendental calls, and what they returned is in d_out_world and d_out_tries.
+ *   PRESENT: a gt is present by the rule of snowgpu_points_in_boxes_device under its pose -- the given pose, or cos / sin of
+ *   (double)heading from the device library when d_pose_in is NULL.
+ *   OBJECT SWEEP, per frame, i ascending over the present gts: candidate (i, t) is box i with centre + (tx, ty, tz), dims s and the pose
+ *   (c cos delta - s sin delta, s cos delta + c sin delta), all float64, nothing rounded to T.  It COLLIDES iff AREA(candidate, current_j)
+ *   > 0 for some present j != i, AREA the BEV clip of snowgpu_boxes_iou_device (half extents, no margin, no test in z); current_j is the
+ *   settled float64 record of box j for j < i -- moved or not -- and its original record for j > i.  The smallest t that does not collide
+ *   is taken: state 1, and the candidate becomes the settled record.  If every try collides the box stays: state 2.  Every try of a
+ *   present box is tested, also those behind the one taken.  This is greedy in box order, as SECOND's loop is; it is NOT a joint search,
+ *   and a box is never tested against its own original place.
+ *   ROWS: a row that is absent (keep 0) or unusable (not |x|, |y|, |z| <= 1e6) is a bit copy; an absent row is never read as a number.
+ *   Any other row: (1) if box_of[row] = i >= 0 and box i has state 1, subtract the ORIGINAL centre, rotate by delta (x' = x cos - y sin,
+ *   y' = x sin + y cos), multiply x, y, z by s, add the centre, then the translation; (2) the world part in pcdet's order: flip x
+ *   (y = -y), flip y (x = -x), rotate by theta, multiply x, y, z by sigma.  Columns 3 and 4 are bit copies.
+ *   BOXES: a present box: the local part where the state is 1 -- centre + t, dims s, heading + delta --, then flip x: cy = -cy, heading =
+ *   -heading; flip y: cx = -cx, heading = -(heading + pi), pi the float64 nearest; the centre rotated by theta and heading + theta; columns
+ *   0 .. 5 multiplied by sigma.  The heading is NOT wrapped.  Columns 7 and up are bit copies: the class is in column 7 here; VELOCITY
+ *   COLUMNS ARE OUT OF SCOPE and are not rotated.  An absent box is a bit copy with state 0.  The output pose is composed from the pose
+ *   used: the angle-addition formulas for delta and theta, exact sign changes for the flips ((c, s) -> (c, -s) about x, (-c, s) about y);
+ *   no new transcendental call.
+ * Outputs, every shape static, every element written by every call:
+ *   d_out_rows      (N, 5) T; may BE d_rows, the in-place form: a row is read and written by its own lane only
+ *   d_out_keep      (N) bytes: 1 for a row present on input, else 0 -- the input mask, carried for the next stage
+ *   d_out_gt_boxes  (F, B, Cb) T
+ *   d_out_world     (F, 8) float64: flip_x, flip_y (0 or 1), cos theta, sin theta, theta, sigma, 0, 0
+ *   d_out_state     (F, B) int32: 0 absent, or no local part; 1 moved; 2 every try collided
+ *   d_out_tried     (F, B) int32: the try taken, -1 otherwise
+ *   d_out_local     (F, B, 8) float64: tx, ty, tz, cos delta, sin delta, delta, s, 0 of the try taken; the identity otherwise
+ *   d_out_pose      (F, B, 2) float64, or NULL: the pose of the OUTPUT boxes, (0, 0) for an absent box
+ *   d_out_tries     (F, B, tries, 8) float64, or NULL: per try tx, ty, tz, cos delta, sin delta, delta, s, collided (0 or 1); the
+ *                   identity for an absent box
+ * Domain: 1 <= B <= 256; Cb in 7 .. 10; flip in 0 .. 3; tries in 0 .. 16; every range finite with lo <= hi; scaling ranges above 0; the
+ * local translation finite, in 0 .. 100; F B max(tries, 1) 10 <= 2^31 - 1; N < 2^31; a frame of at most 2^30 rows; d_step not NULL; dtype 0
+ * or 1; every output apart from every input and every other output, but d_out_rows, which may be d_rows itself (not a part of it).
+ * Anything else is SNOWGPU_E_INVALID with a message.  d_box_of is device data and is trusted to be this batch's; a value outside
+ * 0 .. B - 1 is a row in no box.
+ * Kernels on `stream` (csrc/snowgpu_scene.hip): with a local part, a row and no d_box_of, the two of snowgpu_points_in_boxes_device; one
+ * workgroup per frame for the records, the draws and the sweep (the (t, j) pairs of a box spread over the lanes, an LDS OR per try); one
+ * lane per row.  No memset, no atomic whose arrival shows, nothing read on the host, nothing allocated after the first call of a size:
+ * capturable as a linear graph, and two calls give identical bytes.  The scratch is the context's: calls on streams that are not ordered
+ * against each other need a context each.  The frame's position in the batch is part of the counter.
+ */
+int snowgpu_transform_scene_device(snowgpu_ctx *ctx, int n_frames, int64_t n_total, int64_t max_frame_rows, const int64_t *d_frame_offsets,
+                                   const void *d_rows, int dtype, int n_boxes, const void *d_gt_boxes, int box_features, const double *d_pose_in /* or NULL */,
+                                   int flip, const double *rotation2 /* host, or NULL */, const double *scaling2 /* host, or NULL */, int tries,
+                                   const double *local_translation3 /* host, or NULL */, const double *local_rotation2 /* host, or NULL */,
+                                   const double *local_scaling2 /* host, or NULL */, uint64_t seed, const uint64_t *d_step,
+                                   const int32_t *d_box_of /* or NULL */, const uint8_t *d_keep_in /* or NULL */, void *d_out_rows, uint8_t *d_out_keep,
+                                   void *d_out_gt_boxes, double *d_out_world, int32_t *d_out_state, int32_t *d_out_tried, double *d_out_local,
+                                   double *d_out_pose /* or NULL */, double *d_out_tries /* or NULL */, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

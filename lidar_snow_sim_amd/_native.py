@@ -33,7 +33,7 @@ EXPORTS = [
     "snowgpu_voxelize_device", "snowgpu_fps_device", "snowgpu_ball_query_device", "snowgpu_range_image_device",
     "snowgpu_nearest_centres_device", "snowgpu_points_in_boxes_device", "snowgpu_boxes_iou_device", "snowgpu_nms_device", "snowgpu_fps_sectors_device",
     "snowgpu_roi_point_pool_device", "snowgpu_roi_voxel_pool_device", "snowgpu_sample_rois_device",
-    "snowgpu_assign_anchors_device", "snowgpu_paste_objects_device",
+    "snowgpu_assign_anchors_device", "snowgpu_paste_objects_device", "snowgpu_transform_scene_device",
 ]
 
 WET_ESTIMATION = {"linear": 0, "poly": 1}
@@ -169,6 +169,9 @@ def lib():
             L.snowgpu_paste_objects_device.restype = ctypes.c_int
             L.snowgpu_paste_objects_device.argtypes = [vp, ctypes.c_int, i64, i64, vp, vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, vp, i64, i64, vp, vp, vp, vp, vp,
                                                        ctypes.c_int, vp, vp, ctypes.c_uint64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+            L.snowgpu_transform_scene_device.restype = ctypes.c_int
+            L.snowgpu_transform_scene_device.argtypes = [vp, ctypes.c_int, i64, i64, vp, vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, vp, ctypes.c_int, vp, vp,
+                                                         ctypes.c_int, vp, vp, vp, ctypes.c_uint64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
             L.snowgpu_fov_mask_device.restype = ctypes.c_int
             L.snowgpu_fov_mask_device.argtypes = [vp, i64, vp, ctypes.c_int, vp, vp, vp, ctypes.c_int, ctypes.c_int, vp, vp, vp]
             L.snowgpu_dror_mask_device.restype = ctypes.c_int
@@ -810,6 +813,27 @@ class Context:
                                                   vp(d_step or None), vp(d_keep_in or None), vp(d_out_rows or None), vp(d_out_keep or None),
                                                   vp(d_out_gt_boxes or None), vp(d_out_object or None), vp(d_out_state or None), vp(d_out_source or None),
                                                   vp(d_out_count or None), vp(d_out_pose or None), vp(stream or None))
+        self._check_args(rc)
+
+    def transform_scene_device(self, n_frames, n_total, max_frame_rows, d_frame_off, d_rows, dtype_code, n_boxes, d_gt_boxes, box_features, d_pose_in, flip,
+                               rotation, scaling, tries, local_translation, local_rotation, local_scaling, seed, d_step, d_box_of, d_keep_in, d_out_rows,
+                               d_out_keep, d_out_gt_boxes, d_out_world, d_out_state, d_out_tried, d_out_local, d_out_pose, d_out_tries, stream=0):
+        """World flip, rotation and scaling and per-object noise of an aligned batch and its gt boxes (include/snowgpu.h:
+        snowgpu_transform_scene_device); asynchronous on `stream`.  flip: bit 0 the x axis, bit 1 the y axis; rotation, scaling,
+        local_rotation, local_scaling: None or (lo, hi), local_translation: None or three numbers (all host); tries 0: no local part; d_step:
+        a uint64 in device memory, read by the kernel.  d_pose_in, d_box_of, d_keep_in, d_out_pose and d_out_tries may be 0; d_out_rows may
+        be d_rows.  An argument outside the domain, or an output overlapping an input or another output, raises ValueError with the
+        entry's words."""
+        vp = ctypes.c_void_p
+        held = [None if v is None else np.ascontiguousarray(v, np.float64).reshape(n) for v, n in
+                ((rotation, 2), (scaling, 2), (local_translation, 3), (local_rotation, 2), (local_scaling, 2))]
+        rot, sc, lt, lr, ls = (None if v is None else _p(v) for v in held)
+        rc = self._L.snowgpu_transform_scene_device(self._h, int(n_frames), int(n_total), int(max_frame_rows), vp(d_frame_off or None), vp(d_rows or None),
+                                                    int(dtype_code), _i32(n_boxes), vp(d_gt_boxes or None), _i32(box_features), vp(d_pose_in or None), _i32(flip),
+                                                    rot, sc, _i32(tries), lt, lr, ls, ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), vp(d_step or None),
+                                                    vp(d_box_of or None), vp(d_keep_in or None), vp(d_out_rows or None), vp(d_out_keep or None),
+                                                    vp(d_out_gt_boxes or None), vp(d_out_world or None), vp(d_out_state or None), vp(d_out_tried or None),
+                                                    vp(d_out_local or None), vp(d_out_pose or None), vp(d_out_tries or None), vp(stream or None))
         self._check_args(rc)
 
     def set_fov(self, calib=None, img_shape=(1024, 1920), pre_crop=False):

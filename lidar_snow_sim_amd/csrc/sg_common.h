@@ -380,6 +380,15 @@ int sg_launch_paste(const void *rows, int dtype, int64_t n_total, int64_t max_fr
                     const double *bank_pose, const int32_t *class_off, const struct SgPasteGroups *groups, const double *ew, uint64_t seed,
                     const uint64_t *d_step, int32_t *table, struct SgPasteFrame *frames, unsigned long long *grid, void *out_rows, uint8_t *out_keep, void *out_gt, int32_t *out_object,
                     int32_t *out_state, int32_t *out_source, int32_t *out_count, double *out_pose, void *stream);
+// Scene transforms (sg_scene.h; the definition: include/snowgpu.h): two kernels, sg_launch_box in front of them when there is a local part, a
+// row and no box_of.  cfg: host.  Scratch: rowrec, sg_scene_rowrecs() doubles; tries, sg_scene_tries() doubles (used without out_tries);
+// box_rec, box_table and box_of_own (n_total int32) for sg_launch_box.  keep, pose_in, box_of, out_pose and out_tries may be null.
+struct SgSceneCfg;
+int sg_launch_scene(const void *rows, int dtype, int64_t n_total, int64_t max_frame, const int64_t *off, int n_frames, const uint8_t *keep, int32_t B,
+                    const void *gt, int32_t Cb, const double *pose_in, const struct SgSceneCfg *cfg, uint64_t seed, const uint64_t *d_step, const int32_t *box_of,
+                    struct SgBoxRec *box_rec, unsigned long long *box_table, int32_t *box_of_own, double *tries, double *rowrec, void *out_rows, uint8_t *out_keep,
+                    void *out_gt, double *out_world, int32_t *out_state, int32_t *out_tried, double *out_local, double *out_pose, double *out_tries,
+                    void *stream);
 #ifdef __cplusplus
 }
 #endif

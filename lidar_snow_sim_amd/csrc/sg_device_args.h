@@ -864,6 +864,73 @@ static inline int sg_check_paste_args(const SgPasteArgs &a, std::string *msg)
     return sg_check_overlaps(who, outs, ins, "the batch is", true, msg);
 }
 
+// ---- snowgpu_transform_scene_device -------------------------------------------------------------------------------------------------------
+struct SgSceneArgs {
+    int n_frames;
+    int64_t n_total, max_frame_rows;
+    int dtype;
+    const int64_t *frame_off;
+    const void *rows;
+    int n_boxes;                      // B, per frame
+    const void *gt_boxes;
+    int box_features;                 // Cb
+    const double *pose_in;            // or NULL: cos / sin of the heading on the device
+    int flip;                         // bit 0: x, bit 1: y
+    const double *rotation, *scaling; // host, 2 doubles (lo, hi) each, or NULL: the part is off
+    int tries;                        // T; 0: no local part, and the three below are not read
+    const double *local_translation;  // host, 3 doubles, or NULL
+    const double *local_rotation, *local_scaling;     // host, 2 doubles each, or NULL
+    const uint64_t *step;             // device
+    const int32_t *box_of;            // or NULL: made in scratch when there is a local part
+    const uint8_t *keep_in;           // or NULL: every row is present
+    void *out_rows;                   // may BE rows: the in-place form
+    uint8_t *out_keep;
+    void *out_gt_boxes;
+    double *out_world;
+    int32_t *out_state, *out_tried;
+    double *out_local;
+    double *out_pose;                 // or NULL
+    double *out_tries;                // or NULL
+};
+
+// lo, hi of a range, or NULL: off
+static inline bool sg_scene_range_ok(const double *r) { return !r || (std::isfinite(r[0]) && std::isfinite(r[1]) && r[0] <= r[1]); }
+
+// 0, or SG_ARGS_INVALID with *msg.  As above, the order is part of the ABI.
+static inline int sg_check_scene_args(const SgSceneArgs &a, std::string *msg)
+{
+    static const char *who = "snowgpu_transform_scene_device", *read = "the mask, the rows, the boxes, the pose, box_of and the step are";
+    if (int rc = sg_check_head(who, a.n_frames, a.dtype, a.n_total < 0 || !a.frame_off || !a.gt_boxes || !a.out_gt_boxes || !a.out_world || !a.out_state || !a.out_tried ||
+                                   !a.out_local || (a.n_total > 0 && (!a.rows || !a.out_rows || !a.out_keep)), msg))
+        return rc;
+    if (a.n_boxes < 1 || a.n_boxes > 256) return sg_refuse(who, ": n_boxes must lie in 1 .. 256", msg);
+    if (a.box_features < 7 || a.box_features > 10) return sg_refuse(who, ": box_features must lie in 7 .. 10: cx, cy, cz, dx, dy, dz, heading first", msg);
+    if (a.flip < 0 || a.flip > 3) return sg_refuse(who, ": flip must lie in 0 .. 3: bit 0 the x axis, bit 1 the y axis", msg);
+    if (a.tries < 0 || a.tries > 16) return sg_refuse(who, ": tries must lie in 0 .. 16", msg);
+    const bool local = a.tries > 0;
+    if (!sg_scene_range_ok(a.rotation) || !sg_scene_range_ok(a.scaling) || (local && (!sg_scene_range_ok(a.local_rotation) || !sg_scene_range_ok(a.local_scaling))))
+        return sg_refuse(who, ": a range must be finite with lo <= hi", msg);
+    if ((a.scaling && !(a.scaling[0] > 0.0)) || (local && a.local_scaling && !(a.local_scaling[0] > 0.0))) return sg_refuse(who, ": a scaling range must be above 0", msg);
+    for (int j = 0; local && a.local_translation && j < 3; ++j)
+        if (!(a.local_translation[j] >= 0.0 && a.local_translation[j] <= 100.0))             // (false for NaN)
+            return sg_refuse(who, ": every component of the local translation must be finite and lie in 0 .. 100", msg);
+    if ((int64_t)a.n_frames * a.n_boxes * (a.tries > 0 ? a.tries : 1) * 10 > ((int64_t)1 << 31) - 1)
+        return sg_refuse(who, ": n_frames * n_boxes * max(tries, 1) * 10 exceeds 2^31 - 1; split the batch", msg);
+    if (int rc = sg_check_rows(a.n_total, msg)) return rc;
+    if (int rc = sg_check_frame(who, sg_max_frame(a.max_frame_rows, a.n_total), msg)) return rc;
+    if (!a.step) return sg_refuse(who, ": d_step is NULL; one uint64 in device memory", msg);
+    const size_t esz = a.dtype == 0 ? 4 : 8, n = (size_t)a.n_total, F = (size_t)a.n_frames, q = F * (size_t)a.n_boxes;
+    const bool in_place = a.out_rows && a.out_rows == a.rows;                                // (the row kernel reads and writes its own row only)
+    const SgOutSpan outs[9] = {
+        {a.out_rows, n * 5 * esz, "d_out_rows"}, {a.out_keep, n, "d_out_keep"}, {a.out_gt_boxes, q * (size_t)a.box_features * esz, "d_out_gt_boxes"},
+        {a.out_world, F * 64, "d_out_world"}, {a.out_state, q * 4, "d_out_state"}, {a.out_tried, q * 4, "d_out_tried"}, {a.out_local, q * 64, "d_out_local"},
+        {a.out_pose, q * 16, "d_out_pose"}, {a.out_tries, q * (size_t)a.tries * 64, "d_out_tries"}};
+    const SgInSpan ins[7] = {{a.keep_in, n, "d_keep_in", read, "them"}, {in_place ? nullptr : a.rows, n * 5 * esz, "d_rows", read, "them"},
+                             {a.frame_off, (F + 1) * 8, "d_frame_offsets", read, "them"}, {a.gt_boxes, q * (size_t)a.box_features * esz, "d_gt_boxes", read, "them"},
+                             {a.pose_in, q * 16, "d_pose_in", read, "them"}, {local ? a.box_of : nullptr, n * 4, "d_box_of", read, "them"}, {a.step, 8, "d_step", read, "them"}};
+    return sg_check_overlaps(who, outs, ins, "the scene is", true, msg);
+}
+
 // 0, or SG_ARGS_INVALID with *msg (built on this path only).  The order is part of the ABI: it decides which message a doubly wrong call gets.
 static inline int sg_check_device_args(const SgDeviceArgs &a, const SgCtxView &c, const SgEntryShape &s, std::string *msg)
 {

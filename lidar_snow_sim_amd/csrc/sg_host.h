@@ -139,6 +139,11 @@ struct __attribute__((visibility("default"))) snowgpu_ctx {
     DevBuf<int32_t> paste_runs;
     DevBuf<uint8_t> paste_frames;
     DevBuf<unsigned long long> paste_grid;
+    // scene transforms (snowgpu_transform_scene_device): ten doubles per box for the row kernel, eight per (box, try) when the caller takes
+    // no d_out_tries, and -- when the stage makes box_of itself -- the records and the bit table of points in boxes and one int32 per row
+    DevBuf<double> scene_rowrec, scene_tries, scene_box_rec;
+    DevBuf<unsigned long long> scene_box_table;
+    DevBuf<int32_t> scene_box_of;
     // scratch shared by every batch
     DevBuf<int32_t> tile_hist, tile_base, perm, ctile_cnt, ctile_base, table_ids, out_src;
     DevBuf<uint8_t> srows;            // channel-sorted copy of the frames whose rows did not come channel-sorted (firing order)

@@ -155,6 +155,7 @@ extern "C" void snowgpu_destroy(snowgpu_ctx *ctx)
     ctx->iou_rec.release(); ctx->nms_order.release(); ctx->nms_cand.release();
     ctx->anchor_rec.release(); ctx->anchor_top.release(); ctx->anchor_blk.release();
     ctx->paste_runs.release(); ctx->paste_frames.release(); ctx->paste_grid.release();
+    ctx->scene_rowrec.release(); ctx->scene_tries.release(); ctx->scene_box_rec.release(); ctx->scene_box_table.release(); ctx->scene_box_of.release();
     sg_prepass_release(&ctx->prepass);
     sg_plane_release(&ctx->plane_scr);
     ctx->plane_est.release(); ctx->wet_plane_est.release(); ctx->plane_info.release(); ctx->stats_hist.release(); ctx->stats_rec.release();

@@ -20,6 +20,7 @@
 #include "sg_targets.h"     // SgTargetCfg of the proposal target sampling
 #include "sg_anchors.h"     // SgAnchorCfg and the record of the anchor target assignment
 #include "sg_paste.h"       // SgPasteGroups and the scratch of the object paste
+#include "sg_scene.h"       // SgSceneCfg and the scratch of the scene transforms
 
 // one of the sg_check_*_args on its arguments: SNOWGPU_OK, or the refusal with its message in the context
 template <class... Params, class... Args>
@@ -431,4 +432,41 @@ extern "C" int snowgpu_paste_objects_device(snowgpu_ctx *ctx, int n_frames, int6
                                     d_bank_offsets, d_bank_boxes, d_bank_pose, d_class_offsets, &g, ew, seed, d_step, ctx->paste_runs.p,
                                     (SgPasteFrame *)ctx->paste_frames.p, ctx->paste_grid.p, d_out_rows, d_out_keep, d_out_gt_boxes, d_out_object, d_out_state, d_out_source, d_out_count,
                                     d_out_pose, stream_of(ctx, stream)));
+}
+
+// Scene transforms (snowgpu_scene.hip; the draws, the sweep, what a row and a box become and the scratch: sg_scene.h).  See include/snowgpu.h.
+extern "C" int snowgpu_transform_scene_device(snowgpu_ctx *ctx, int n_frames, int64_t n_total, int64_t max_frame_rows, const int64_t *d_frame_offsets,
+                                              const void *d_rows, int dtype, int n_boxes, const void *d_gt_boxes, int box_features, const double *d_pose_in,
+                                              int flip, const double *rotation2, const double *scaling2, int tries, const double *local_translation3,
+                                              const double *local_rotation2, const double *local_scaling2, uint64_t seed, const uint64_t *d_step,
+                                              const int32_t *d_box_of, const uint8_t *d_keep_in, void *d_out_rows, uint8_t *d_out_keep, void *d_out_gt_boxes,
+                                              double *d_out_world, int32_t *d_out_state, int32_t *d_out_tried, double *d_out_local, double *d_out_pose,
+                                              double *d_out_tries, void *stream)
+{
+    if (!ctx) return SNOWGPU_E_INVALID;
+    const SgSceneArgs a{n_frames, n_total, max_frame_rows, dtype, d_frame_offsets, d_rows, n_boxes, d_gt_boxes, box_features, d_pose_in, flip, rotation2, scaling2,
+                        tries, local_translation3, local_rotation2, local_scaling2, d_step, d_box_of, d_keep_in, d_out_rows, d_out_keep, d_out_gt_boxes, d_out_world,
+                        d_out_state, d_out_tried, d_out_local, d_out_pose, d_out_tries};
+    if (int rc = checked(ctx, sg_check_scene_args, a)) return rc;
+    SgSceneCfg k{};
+    k.flip = flip; k.tries = tries;
+    if (rotation2) { k.rot_on = 1; k.rot[0] = rotation2[0]; k.rot[1] = rotation2[1]; }
+    if (scaling2) { k.scale_on = 1; k.scale[0] = scaling2[0]; k.scale[1] = scaling2[1]; }
+    if (tries > 0 && local_translation3) { k.ltrans_on = 1; for (int j = 0; j < 3; ++j) k.ltrans[j] = local_translation3[j]; }
+    if (tries > 0 && local_rotation2) { k.lrot_on = 1; k.lrot[0] = local_rotation2[0]; k.lrot[1] = local_rotation2[1]; }
+    if (tries > 0 && local_scaling2) { k.lscale_on = 1; k.lscale[0] = local_scaling2[0]; k.lscale[1] = local_scaling2[1]; }
+    const bool own_box_of = tries > 0 && !d_box_of && n_total > 0;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    ENSURE(ctx, ctx->scene_rowrec, sg_scene_rowrecs(n_frames, n_boxes));
+    if (tries > 0 && !d_out_tries) ENSURE(ctx, ctx->scene_tries, sg_scene_tries(n_frames, n_boxes, tries));
+    if (own_box_of) {
+        ENSURE(ctx, ctx->scene_box_rec, sg_box_records(n_frames, n_boxes) * (sizeof(SgBoxRec) / sizeof(double)));
+        ENSURE(ctx, ctx->scene_box_table, sg_box_table(n_frames, n_boxes));
+        ENSURE(ctx, ctx->scene_box_of, (size_t)n_total);
+    }
+    return launched(ctx, "scene transforms",
+                    sg_launch_scene(d_rows, dtype, n_total, sg_max_frame(max_frame_rows, n_total), d_frame_offsets, n_frames, d_keep_in, n_boxes, d_gt_boxes, box_features,
+                                    d_pose_in, &k, seed, d_step, tries > 0 ? d_box_of : nullptr, (SgBoxRec *)ctx->scene_box_rec.p, ctx->scene_box_table.p,
+                                    ctx->scene_box_of.p, ctx->scene_tries.p, ctx->scene_rowrec.p, d_out_rows, d_out_keep, d_out_gt_boxes, d_out_world, d_out_state,
+                                    d_out_tried, d_out_local, d_out_pose, d_out_tries, stream_of(ctx, stream)));
 }

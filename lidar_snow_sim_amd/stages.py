@@ -1,6 +1,6 @@
 """The device stages of the torch-tensor boundary (tensors.py is the documented import path and lists what each is for) and the batches
 of static shape they leave behind: fov_keep, dror_keep, voxelize, sample_keypoints, ball_query, range_image, nearest_keypoints,
-points_in_boxes, boxes_iou, nms, roi_point_pool, roi_voxel_pool, sample_rois, assign_anchors, paste_objects.  Every stage goes through the same steps, in this order -- it is the order in which a call that is wrong
+points_in_boxes, boxes_iou, nms, roi_point_pool, roi_voxel_pool, sample_rois, assign_anchors, paste_objects, transform_scene.  Every stage goes through the same steps, in this order -- it is the order in which a call that is wrong
 in two ways is refused: the aligned unwrap and the device-input refusal (_stage_frames), the scalar and range checks (_whole, _range6),
 the batch and its keep mask (_stage_batch), the stage's own tensors, the checks of the shapes' domain, out= (_checked_out), the launch
 (_stage_launch).  PyTorch is plumbing here; the work is the C entries'."""
@@ -1531,3 +1531,201 @@ def paste_objects(frames, gt_boxes, bank, sample_groups, *, step, seed=0, keep=N
                   0 if source is None or not n else source.data_ptr(), out.count.data_ptr(), 0 if used is None else used.data_ptr())
     same = np.array_equal(out.offsets, np.asarray(offsets, np.int64)) and (source is None) == (out.source is None) and (used is None) == (out.pose is None)
     return out if same else PasteBatch(out.rows, out.keep, out.gt_boxes, out.object, out.state, out.count, source, used, offsets)
+
+
+SCENE_STATES = {"still": 0, "moved": 1, "blocked": 2}
+_FLIP_BITS = {"x": 1, "y": 2}
+
+
+class SceneBatch:
+    """What transform_scene() leaves behind, N = rows of the batch, F = frames, B = gt boxes per frame, T = tries -- every shape static:
+    `rows` (N, 5: x, y, z transformed, columns 3 and 4 bit copies) and `keep` (N bool: the input mask, carried so that the batch goes
+    straight into voxelize and the stages behind it); `gt_boxes` (F, B, Cb: the transformed boxes, absent ones as they came); `world`
+    (F, 8 float64: flip_x, flip_y, cos theta, sin theta, theta, sigma, 0, 0); `state` (F, B int32: SCENE_STATES -- 0 absent or no local
+    part, 1 moved, 2 every try collided); `tried` (F, B int32: the try taken, -1 otherwise); `local` (F, B, 8 float64: tx, ty, tz,
+    cos delta, sin delta, delta, s, 0 of the try taken, the identity otherwise); `pose` (F, B, 2 float64: the pose of the OUTPUT boxes, as
+    points_in_boxes(pose=), boxes_iou and the pooling stages take it; None unless asked for) and `tries` (F, B, T, 8 float64: every
+    candidate's record, column 7 its collision bit; None unless asked for).  invert_points(), invert_boxes() and apply_boxes() are plain
+    indexing and arithmetic in torch, no kernel of this library, and carry gradients.  All still being written until the stream the call
+    was made on has caught up."""
+
+    def __init__(self, rows, keep, gt_boxes, world, state, tried, local, pose=None, tries=None, offsets=None):
+        self.rows, self.keep, self.gt_boxes, self.world, self.state, self.tried, self.local, self.pose, self.tries = (rows, keep, gt_boxes, world, state, tried, local,
+                                                                                                                      pose, tries)
+        self.offsets = np.array([0, rows.shape[0]], np.int64) if offsets is None else np.asarray(offsets, np.int64)
+        self._frame = None
+
+    @classmethod
+    def empty(cls, offsets, n_boxes, box_features=8, tries=0, dtype=None, device=None, with_pose=False, with_tries=False):
+        """Uninitialised buffers of the shapes transform_scene() writes for a batch with these frame offsets (or, for one frame, this number
+        of rows) (out=): static addresses for a captured graph."""
+        import torch
+        dev, dt = _cuda_device(torch, device), dtype or torch.float32
+        off = np.array([0, int(offsets)], np.int64) if np.ndim(offsets) == 0 else np.asarray(offsets, np.int64)
+        n, F, B = int(off[-1]), len(off) - 1, int(n_boxes)
+
+        def new(shape, kind):
+            return torch.empty(shape, dtype=kind, device=dev)
+        return cls(new((n, 5), dt), new((n,), torch.bool), new((F, B, int(box_features)), dt), new((F, 8), torch.float64), new((F, B), torch.int32),
+                   new((F, B), torch.int32), new((F, B, 8), torch.float64), new((F, B, 2), torch.float64) if with_pose else None,
+                   new((F, B, int(tries), 8), torch.float64) if with_tries else None, off)
+
+    @property
+    def moved(self):
+        """(F, B) bool: state == 1 -- the box and its rows took a try."""
+        return self.state == 1
+
+    def _frame_of_rows(self):
+        """(N) int64: the frame of every row.  The first call of a batch of several frames uploads their row counts (make it before
+        capturing a graph); later calls reuse the result."""
+        import torch
+        if self._frame is None:
+            counts = torch.from_numpy(np.diff(self.offsets)).to(self.world.device)
+            self._frame = torch.repeat_interleave(torch.arange(len(counts), device=counts.device), counts, output_size=int(self.offsets[-1]))
+        return self._frame
+
+    def _world_of(self, like, per_row):
+        """The six world values per row (N) or per frame (F, 1), after the shape check of a helper's argument."""
+        import torch
+        n, F = int(self.offsets[-1]), int(self.world.shape[0])
+        fits = torch.is_tensor(like) and like.device == self.world.device and like.is_floating_point() and (
+            (like.dim() == 2 and like.shape[0] == n and like.shape[1] >= 3) if per_row else (like.dim() == 3 and like.shape[0] == F and like.shape[2] >= 7))
+        if not fits:
+            raise ValueError("SceneBatch: one point per row of the batch (N, 3 ..), or boxes per frame (F, M, 7 ..), floating point, on the device of the rows")
+        w = self.world[self._frame_of_rows()] if per_row else self.world[:, None, :]
+        return (w[..., j] for j in range(6))
+
+    def invert_points(self, xyz):
+        """The inverse of the WORLD part on points (N, 3 or more columns; one per row of the batch, in its order): divide by sigma, rotate by
+        -theta, undo the flips.  Computed in float64, returned in the dtype of `xyz`; columns 3 and up are copied.  Predictions per point
+        go back to the sensor frame with it; the local part is not undone."""
+        import torch
+        fx, fy, c, s, _, sg = self._world_of(xyz, True)
+        p = xyz[..., :3].to(torch.float64) / sg[..., None]
+        x, y = p[..., 0] * c + p[..., 1] * s, p[..., 1] * c - p[..., 0] * s
+        x, y = torch.where(fy != 0, -x, x), torch.where(fx != 0, -y, y)
+        return torch.cat((torch.stack((x, y, p[..., 2]), dim=-1).to(xyz.dtype), xyz[..., 3:]), dim=-1)
+
+    def invert_boxes(self, boxes):
+        """The inverse of the WORLD part on boxes (F, M, 7 or more columns) of the same frames: predictions made in the augmented frame go
+        back to the sensor frame.  Computed in float64, returned in the dtype of `boxes`; columns 7 and up are copied; the heading is not
+        wrapped."""
+        import torch
+        fx, fy, c, s, th, sg = self._world_of(boxes, False)
+        b = boxes[..., :7].to(torch.float64)
+        ctr, dims, h = b[..., :3] / sg[..., None], b[..., 3:6] / sg[..., None], b[..., 6] - th
+        x, y = ctr[..., 0] * c + ctr[..., 1] * s, ctr[..., 1] * c - ctr[..., 0] * s
+        x, h = torch.where(fy != 0, -x, x), torch.where(fy != 0, -h - math.pi, h)
+        y, h = torch.where(fx != 0, -y, y), torch.where(fx != 0, -h, h)
+        return torch.cat((torch.stack((x, y, ctr[..., 2]), dim=-1).to(boxes.dtype), dims.to(boxes.dtype), h[..., None].to(boxes.dtype), boxes[..., 7:]), dim=-1)
+
+    def apply_boxes(self, boxes):
+        """The WORLD part forward on other boxes (F, M, 7 or more columns) of the same frames -- proposals made before the augmentation, say
+        -- in the stage's order: flip x, flip y, rotate, scale.  Computed in float64, returned in the dtype of `boxes`; columns 7 and up are
+        copied; the heading is not wrapped."""
+        import torch
+        fx, fy, c, s, th, sg = self._world_of(boxes, False)
+        b = boxes[..., :7].to(torch.float64)
+        x, y, h = b[..., 0], b[..., 1], b[..., 6]
+        y, h = torch.where(fx != 0, -y, y), torch.where(fx != 0, -h, h)
+        x, h = torch.where(fy != 0, -x, x), torch.where(fy != 0, -(h + math.pi), h)
+        x, y, h = x * c - y * s, x * s + y * c, h + th
+        ctr = torch.stack((x, y, b[..., 2]), dim=-1) * sg[..., None]
+        return torch.cat((ctr.to(boxes.dtype), (b[..., 3:6] * sg[..., None]).to(boxes.dtype), h[..., None].to(boxes.dtype), boxes[..., 7:]), dim=-1)
+
+
+def _scene_range(who, name, value, n=2):
+    """None / () for a part that is off, else n float64 (lo, hi -- or the three half widths of the translation)."""
+    if value is None or (np.ndim(value) == 1 and len(value) == 0):
+        return None
+    v = np.asarray(value, np.float64).reshape(-1)
+    if v.shape != (n,):
+        raise ValueError(f"{who}: {name} holds {n} numbers" + (" (lo, hi)" if n == 2 else "") + ", or None for a part that is off")
+    return v
+
+
+def transform_scene(frames, gt_boxes, *, step, seed=0, flip=('x',), rotation=(-math.pi / 4, math.pi / 4), scaling=(0.95, 1.05), local=None, box_of=None, pose=None,
+                    keep=None, in_place=False, out=None, return_pose=False, return_tried=False, device=None, slot=0):
+    """The geometric augmentation behind gt_sampling on the device (snowgpu_transform_scene_device; the definition: include/snowgpu.h):
+    pcdet's random_world_flip, random_world_rotation and random_world_scaling and, with `local`, per-object noise (pcdet's
+    random_local_translation / rotation / scaling, SECOND's noise_per_object) with its collision test, for rows and gt boxes alike -- static
+    shapes, nothing read on the host, draws keyed by (seed, step, frame).  The definition is this library's, modelled on those two.
+    ITS PLACE IN THE CHAIN: BEHIND the weather stages and range_image(ring=), which need rows in the sensor frame, and IN FRONT of
+    voxelize, the keypoint stages, ball_query, points_in_boxes for labels and assign_anchors.
+
+    frames     what points_in_boxes takes -- torch CUDA tensors, a DeviceBatch, or an AlignedResult / AlignedWetResult (its keep is ANDed).
+    gt_boxes   a contiguous (F, B, 7 .. 10) tensor in the rows' dtype on their device; zero rows are padding.  Columns 7 and up are copied:
+               the class is in column 7 here, velocity columns are out of scope.
+    step       a one-element int64 tensor on the device of the rows (WeatherPlan.step as it stands), read by the kernel.
+    seed       the key of the draw.
+    flip       the axes a frame may be flipped about, each with probability 1 / 2: any of 'x', 'y'; None or (): off.
+    rotation   (lo, hi) of the world angle theta; None or (): off.       scaling   (lo, hi) > 0 of the world scale sigma; None or (): off.
+    local      None: no object noise.  Or a dict: translation (ax, ay, az: uniform in -a .. a, each in 0 .. 100), rotation (lo, hi),
+               scaling (lo, hi) > 0 -- None or () each: off -- and tries (1 .. 16, default 8): per present box, the first try that overlaps
+               no other box in the BEV is taken, greedy in box order; a box whose every try collides stays as it is.
+    box_of     with a local part: the box of every row, (N) int32 from points_in_boxes on THESE boxes (BoxLabelBatch.box_of); None: made
+               here, in scratch, by that stage's own kernels.
+    pose       None: cos / sin of the gts' heading in float64 on the device; or a contiguous (F, B, 2) float64 tensor used as it is.
+    keep       an input keep mask as the aligned calls take it; None: every row is present.
+    in_place   write the rows over the input rows (a row is read and written by its own lane only); every other output is new memory.
+    out        a SceneBatch to write into (SceneBatch.empty): every element is written.  With in_place its rows must be the input rows.
+
+    Returns a SceneBatch.  Asynchronous on torch's current stream; nothing is read on the host: capturable after one warm-up call."""
+    import torch
+    who = "transform_scene"
+    frames, keep = _stage_frames(torch, who, "lidar_snow_sim_amd.scene.transform_scene", frames, keep)
+    axes = () if flip is None else ((flip,) if isinstance(flip, str) else tuple(flip))
+    if any(a not in _FLIP_BITS for a in axes):
+        raise ValueError(f"{who}: flip holds any of 'x' and 'y', or None")
+    flip_bits = sum(_FLIP_BITS[a] for a in set(axes))
+    rot, sc = _scene_range(who, "rotation", rotation), _scene_range(who, "scaling", scaling)
+    T, ltr, lrot, lsc = 0, None, None, None
+    if local is not None:
+        if not isinstance(local, dict) or set(local) - {"translation", "rotation", "scaling", "tries"}:
+            raise ValueError(f"{who}: local is None or a dict of translation, rotation, scaling and tries")
+        T = local.get("tries", 8)
+        _whole(who, **{"local['tries']": T})
+        T = int(T)
+        if not 1 <= T <= 16:
+            raise ValueError(f"{who}: local['tries'] must lie in 1 .. 16")
+        ltr, lrot, lsc = (_scene_range(who, "local['translation']", local.get("translation"), 3), _scene_range(who, "local['rotation']", local.get("rotation")),
+                          _scene_range(who, "local['scaling']", local.get("scaling")))
+    rows, offsets, eng, dev, nf, n, keep = _stage_batch(torch, frames, keep, device, slot)
+    if not (torch.is_tensor(gt_boxes) and gt_boxes.dim() == 3 and gt_boxes.shape[0] == nf and gt_boxes.dtype == rows.dtype and gt_boxes.device == dev and
+            gt_boxes.is_contiguous()):
+        raise ValueError(f"{who}: gt_boxes must be a contiguous (frames, B, 7 .. 10) tensor in the rows' dtype on their device")
+    if not (torch.is_tensor(step) and step.numel() == 1 and step.dtype == torch.int64 and step.device == dev):
+        raise ValueError(f"{who}: step must be a one-element int64 tensor on the device of the rows")
+    B, Cb = int(gt_boxes.shape[1]), int(gt_boxes.shape[2])
+    # (the shapes below need these; the entry refuses them in the same words, and everything else of the domain)
+    if not 1 <= B <= 256:
+        raise ValueError(f"{who}: n_boxes must lie in 1 .. 256 (gt_boxes)")
+    if not 7 <= Cb <= 10:
+        raise ValueError(f"{who}: box_features must lie in 7 .. 10: cx, cy, cz, dx, dy, dz, heading first (gt_boxes)")
+    if pose is not None and not (torch.is_tensor(pose) and tuple(pose.shape) == (nf, B, 2) and pose.dtype == torch.float64 and pose.device == dev and pose.is_contiguous()):
+        raise ValueError(f"{who}: pose must be a contiguous {(nf, B, 2)} float64 tensor (cos, sin) on the device of the rows")
+    if box_of is not None and not (torch.is_tensor(box_of) and tuple(box_of.shape) == (n,) and box_of.dtype == torch.int32 and box_of.device == dev and
+                                   box_of.is_contiguous()):
+        raise ValueError(f"{who}: box_of must be a contiguous ({n},) int32 tensor on the device of the rows (BoxLabelBatch.box_of)")
+    tried = return_tried and T > 0
+    if return_tried and not T:
+        raise ValueError(f"{who}: return_tried needs a local part")
+    want = (("rows", rows.dtype, (n, 5), True), ("keep", torch.bool, (n,), True), ("gt_boxes", rows.dtype, (nf, B, Cb), True), ("world", torch.float64, (nf, 8), True),
+            ("state", torch.int32, (nf, B), True), ("tried", torch.int32, (nf, B), True), ("local", torch.float64, (nf, B, 8), True),
+            ("pose", torch.float64, (nf, B, 2), return_pose), ("tries", torch.float64, (nf, B, T, 8), tried))
+    if out is None:
+        out = SceneBatch.empty(offsets, B, Cb, T, rows.dtype, dev, return_pose, tried)
+        if in_place:
+            out.rows = rows[:n]
+    else:
+        _checked_out(torch, who, SceneBatch, out, want, dev, _ROWS)
+        if in_place and n and out.rows.data_ptr() != rows.data_ptr():
+            raise ValueError(f"{who}: with in_place, out.rows must be the input rows")
+    used, tries = (out.pose if return_pose else None), (out.tries if tried else None)
+    _stage_launch(torch, eng, dev, nf, n, offsets, rows, eng.ctx.transform_scene_device, B, gt_boxes.data_ptr(), Cb, 0 if pose is None else pose.data_ptr(), flip_bits,
+                  rot, sc, T, ltr, lrot, lsc, seed, step.data_ptr(), 0 if box_of is None or not n or not T else box_of.data_ptr(),
+                  0 if keep is None or not n else keep.data_ptr(), out.rows.data_ptr() if n else 0, out.keep.data_ptr() if n else 0, out.gt_boxes.data_ptr(),
+                  out.world.data_ptr(), out.state.data_ptr(), out.tried.data_ptr(), out.local.data_ptr(), 0 if used is None else used.data_ptr(),
+                  0 if tries is None else tries.data_ptr())
+    same = np.array_equal(out.offsets, np.asarray(offsets, np.int64)) and (used is None) == (out.pose is None) and (tries is None) == (out.tries is None)
+    return out if same else SceneBatch(out.rows, out.keep, out.gt_boxes, out.world, out.state, out.tried, out.local, used, tries, offsets)

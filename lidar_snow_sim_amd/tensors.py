@@ -57,6 +57,10 @@ The reference's training-time caller (the OpenPCDet DENSE dataset: `root_path`, 
     they overlap a gt or an earlier object, their boxes appended to the gts and the scene rows inside them cleared (PasteBatch;
     snowgpu_paste_objects_device): pcdet's DataBaseSampler; its `rows`, `keep` and `gt_boxes` feed `augment_batch(..., layout='aligned',
     keep=)` and every stage behind it.
+  * `transform_scene(frames, gt_boxes, step=...)` is the geometric augmentation behind gt_sampling: world flip, rotation and scaling and,
+    with `local=`, per-object translation, rotation and scaling with their collision test, on rows and gt boxes alike, drawn by (seed, step,
+    frame) (SceneBatch; snowgpu_transform_scene_device).  Its place: BEHIND the weather stages and `range_image(ring=)`, which need rows in
+    the sensor frame, IN FRONT of `voxelize`, the keypoint stages, `ball_query`, `points_in_boxes` for labels and `assign_anchors`.
   * `augment_wet_batch_aligned(frames, ...)` is the snowfall + wet-ground chain with that aligned result (AlignedWetResult: per-frame
     flags beside it; snowgpu_augment_wet_batch_device_aligned), `wet_ground_batch_aligned(frames, keep)` the wet-ground stage alone on rows
     and a keep mask from any earlier stage (snowgpu_wet_ground_batch_device_aligned).
@@ -66,7 +70,7 @@ training loop that reshuffles `order` per frame uploads 64 int32 per frame).  Py
 no arithmetic of the simulation happens in this file.
 
 This module is the import path of all of it and holds the augmentation entries.  How a batch is read and a result handed back lives in
-batch.py, the stages from `fov_keep` to `paste_objects` with their result classes in stages.py; every public name of both is re-exported here.
+batch.py, the stages from `fov_keep` to `transform_scene` with their result classes in stages.py; every public name of both is re-exported here.
 """
 from __future__ import annotations
 
@@ -79,9 +83,9 @@ import numpy as np
 from . import _native
 from .batch import (LANE_SLOT0, AlignedResult, AlignedWetResult, DeviceBatch, DeviceResult, _cuda_device, _keep_mask, _on_run_stream,  # noqa: F401
                     _resolve_input, _uploads, is_device_input)
-from .stages import (IOU_MODES, PASTE_STATES, AnchorTargetBatch, BoxLabelBatch, IouBatch, KeypointBatch, NearestBatch, NeighbourBatch, NmsBatch, ObjectBank, PasteBatch, RangeImageBatch, RoiPointBatch, RoiTargetBatch, RoiVoxelBatch, VoxelBatch,  # noqa: F401
+from .stages import (IOU_MODES, PASTE_STATES, SCENE_STATES, AnchorTargetBatch, BoxLabelBatch, IouBatch, KeypointBatch, NearestBatch, NeighbourBatch, NmsBatch, ObjectBank, PasteBatch, RangeImageBatch, RoiPointBatch, RoiTargetBatch, RoiVoxelBatch, SceneBatch, VoxelBatch,  # noqa: F401
                      _fov_mask, anchor_grid, assign_anchors, ball_query, boxes_iou, dror_keep, fov_keep, nearest_keypoints, nms, paste_objects, points_in_boxes, range_image, roi_point_pool,
-                     roi_voxel_pool, sample_keypoints, sample_rois, voxelize)
+                     roi_voxel_pool, sample_keypoints, sample_rois, transform_scene, voxelize)
 
 
 @contextmanager
