@@ -1310,6 +1310,82 @@ int snowgpu_assign_anchors_device(snowgpu_ctx *ctx, int n_frames, int n_anchors,
                                   int32_t *d_out_count, int32_t *d_out_gt_count, void *d_out_iou /* or NULL */, void *stream);
 
 /*
+ * CENTRE HEATMAP TARGETS: the class heatmaps, the centre pixels with their fractional offsets and the slots of the gts of every frame --
+ * the step of OpenPCDet's CenterHead (assign_targets, assign_target_of_single_head, with centernet_utils' gaussian_radius and
+ * draw_gaussian_to_heatmap) between the augmentation and a centre head's loss, with static shapes and nothing read on the host.  pcdet is
+ * not part of the reference checkout: the definition below is THIS LIBRARY'S, modelled on pcdet's CenterHead and centernet_utils as
+ * recalled, and was NOT CHECKED against pcdet's source.  It is restated as sequential NumPy by tests/centers_reference.py;
+ * csrc/sg_centers.h holds its C++, for the device and for the host.
+ *   INPUTS, F = n_frames, B = n_gt, T = float32 or float64: d_gt_boxes (F, B, Cg) T, Cg in 8 .. 10, columns 0 .. 6 cx, cy, cz, dx, dy, dz,
+ *   heading, column 7 the class; cfg in HOST memory, read during the call: (x0, y0) the origin of the point-cloud range, (vx, vy) the
+ *   voxel's edges, stride the feature map's stride, (W, H) = (width, height) the feature map, NC = n_classes, NH = n_heads,
+ *   class_head[c - 1] the head of class c, M = max_objs, o = gaussian_overlap, min_radius, outside (0 clamp, 1 drop).
+ *   ARITHMETIC: float64 computed from (double) of the inputs, every operation rounded on its own, no fused multiply-add, in exactly the
+ *   parenthesisation written here (a b c is (a b) c, as C and Python read it).
+ *   PRESENCE: a gt is present iff the presence rule of snowgpu_points_in_boxes_device holds for its seven columns (all finite, the 1e6
+ *   bounds, 0 < dx, dy, dz <= 1e6; no pose is involved) and its column 7 is integral with a value in 1 .. NC -- the rule of
+ *   snowgpu_assign_anchors_device; zero rows are padding.  An absent gt has state 0 and takes part in nothing.  The head of a present gt
+ *   of class c is class_head[c - 1].
+ *   CENTRE: coord_x = ((x - x0) / vx) / stride, coord_y = ((y - y0) / vy) / stride.  With outside = drop, a gt that is not in
+ *   0 <= coord_x < W and 0 <= coord_y < H has state 2 and takes part in nothing.  Otherwise, and always with outside = clamp,
+ *   c = min(max(coord, 0), size - 0.5) on either axis (size = W or H); ci = trunc(c); offset = c - ci, which is exact, rounded once to T.
+ *   RADIUS: h = (dx / vx) / stride, w = (dy / vy) / stride and
+ *     b1 = h + w;            c1 = w * h * (1 - o) / (1 + o);   r1 = (b1 + sqrt(b1 * b1 - 4 * c1)) / 2
+ *     b2 = 2 * (h + w);      c2 = (1 - o) * w * h;             r2 = (b2 + sqrt(b2 * b2 - 16 * c2)) / 2
+ *     b3 = -2 * o * (h + w); c3 = (o - 1) * w * h;             r3 = (b3 + sqrt(b3 * b3 - 16 * o * c3)) / 2
+ *   (r3 keeps pcdet's division by 2, not by 2 a); m = r1, then r2 if r2 < m, then r3 if r3 < m; radius = min_radius unless m >= min_radius
+ *   (so also for a NaN), else 512 if m >= 512, else trunc(m): radius = min(max(trunc(min(r1, r2, r3)), min_radius), 512).  For 0 < o < 1,
+ *   r3 <= 2 sqrt(o (1 - o) w h) <= sqrt(w h) <= (h + w) / 2 <= r1 <= r2: in exact arithmetic r3 is always the minimum.
+ *   SLOTS: per frame and head, the present gts of that head that were not dropped take the slots 0, 1, ... in ascending g; those beyond M
+ *   have state 3 and are not drawn (pcdet does not draw them either); the others have state 1.
+ *   HEAT: for a drawn gt of class c with d = 2 radius + 1, sigma = d / 6, den = 2 * sigma * sigma: at every pixel (px, py) of the map with
+ *   |px - cix| <= radius and |py - ciy| <= radius, ex = px - cix, ey = py - ciy, v = float32(exp(-(ex * ex + ey * ey) / den)).
+ *   heatmap[f, c - 1, py, px] is the maximum of v over the frame's drawn gts of class c, 0 where there is none.
+ *   WHY THE BYTES AGREE WITH AN exp IN IT: the argument of exp is the same double on the device and in NumPy; both exps are faithful, not
+ *   correctly rounded, so the float32 agree as long as the float64 value stays away from the float32 rounding midpoints.  For every radius
+ *   0 .. 512 and every distinct ex ex + ey ey of its patch (14.6 million values) the nearest value lies 15.0 float64 ulp from a midpoint
+ *   (radius 473, ex ex + ey ey = 147293); tests/test_centers_reference.py repeats the walk and asks for more than 4 ulp: one for NumPy's
+ *   exp, one for the device library's, two spare.  The 1 ulp of the device library's double exp is SUPPOSED: the figure is recalled from
+ *   the table of ROCm's HIP math API documentation, not read from a copy of it.  The cap of 512 is what makes the walk exhaustive: it is
+ *   not to be raised without walking again.
+ * Outputs, every shape static, every element written by every call:
+ *   d_out_heatmap   (F, NC, H, W) float32 whatever T: channel c - 1 is class c; a head's map is the channels of its classes
+ *   d_out_gt_index  (F, NH, M) int32: the gt of the slot, -1 when empty
+ *   d_out_ind       (F, NH, M) int32: ciy W + cix, 0 when empty
+ *   d_out_mask      (F, NH, M) uint8: 1 in a filled slot
+ *   d_out_offset    (F, NH, M, 2) T: the fractional part of the centre, x then y; 0 when empty
+ *   d_out_radius    (F, NH, M) int32: the Gaussian radius, 0 when empty
+ *   d_out_count     (F, NH) int32: the filled slots
+ *   d_out_state     (F, B) uint8: 0 absent, 1 drawn, 2 outside and dropped, 3 no slot left
+ * The regression targets of a slot -- offset, z, the logarithms of the sizes, cos and sin of the heading, the extra columns -- are the
+ * caller's arithmetic on d_out_gt_index: log, cos and sin stay out of the kernels and out of the byte-for-byte claim.
+ * Domain: 1 <= B <= 256; Cg in 8 .. 10; 1 <= NC <= 16; 1 <= NH <= 16; 0 <= class_head[c - 1] < NH; 1 <= M <= 512; 1 <= W, H and
+ * F NC H W <= 2^31 - 1; x0, y0 finite; vx, vy positive and finite; stride >= 1; 0 < o < 1; 0 <= min_radius <= 512; outside 0 or 1; dtype 0
+ * or 1; every output apart from the gt boxes and from every other output.  Anything else is SNOWGPU_E_INVALID with a message.
+ * Departures from pcdet: float64 where pcdet computes in float32, so a radius can differ by one where pcdet's float32 truncates on the
+ * other side; the cap of 512 on the radius; absent gts (pcdet stops at the first zero row of a frame's padding); the `outside` option
+ * (pcdet always clamps the centre and, separately, skips a gt whose clamped pixel leaves the map, which cannot happen after the clamp);
+ * the heat channels by global class, not re-labelled per head; gaussian2D's rule "h < eps max -> 0" is omitted because it is vacuous: the
+ * smallest value over all radii up to 512 is about 1.26e-4, far above 2^-52 (the no-GPU test asserts it).
+ * Two kernels on `stream` (csrc/snowgpu_centers.hip): one workgroup of 256 per frame, lane = gt -- presence, centre, radius, head, the
+ * rank within the head by wave ballots and a prefix over the four waves in LDS, the frame's slot table cleared and filled in LDS and then
+ * written out one store per element, state, count and a record of 24 bytes per gt into context scratch --; then one workgroup per
+ * (tile of 64 x 16 pixels, class, frame): the frame's records in LDS, the ascending list of the class's drawn gts whose patch meets the
+ * tile by a ballot and a prefix sum, every lane the maximum over that list for its four pixels, 0 included.  No memset, no atomics, no
+ * sort, nothing read on the host, nothing allocated after the first call of a size: capturable as a linear graph, and two calls give
+ * identical bytes.  The records are scratch of the context: calls on streams that are not ordered against each other need a context each.
+ */
+typedef struct snowgpu_center_cfg {
+    double x0, y0, vx, vy, gaussian_overlap;
+    int32_t stride, width, height, n_classes, n_heads, max_objs, min_radius, outside;
+    int32_t class_head[16];
+} snowgpu_center_cfg;
+int snowgpu_assign_centers_device(snowgpu_ctx *ctx, int n_frames, int n_gt, const void *d_gt_boxes, int gt_features, int dtype,
+                                  const snowgpu_center_cfg *cfg /* host */, float *d_out_heatmap, int32_t *d_out_gt_index, int32_t *d_out_ind,
+                                  uint8_t *d_out_mask, void *d_out_offset, int32_t *d_out_radius, int32_t *d_out_count, uint8_t *d_out_state,
+                                  void *stream);
+
+/*
  * GROUND-TRUTH OBJECT PASTE: database objects written into the absent slots of an aligned batch, with their boxes appended to the gt
  * boxes and the scene rows in their place cleared -- the step of OpenPCDet's DataBaseSampler (the gt_sampling augmentor) in front of the
  * snowfall stage, with static shapes, nothing read on the host and a seeded draw.  pcdet is not part of the reference checkout: the

@@ -33,7 +33,7 @@ EXPORTS = [
     "snowgpu_voxelize_device", "snowgpu_fps_device", "snowgpu_ball_query_device", "snowgpu_range_image_device",
     "snowgpu_nearest_centres_device", "snowgpu_points_in_boxes_device", "snowgpu_boxes_iou_device", "snowgpu_nms_device", "snowgpu_fps_sectors_device",
     "snowgpu_roi_point_pool_device", "snowgpu_roi_voxel_pool_device", "snowgpu_sample_rois_device",
-    "snowgpu_assign_anchors_device", "snowgpu_paste_objects_device", "snowgpu_transform_scene_device",
+    "snowgpu_assign_anchors_device", "snowgpu_paste_objects_device", "snowgpu_transform_scene_device", "snowgpu_assign_centers_device",
 ]
 
 WET_ESTIMATION = {"linear": 0, "poly": 1}
@@ -77,6 +77,28 @@ def roi_sampler_struct(roi_per_image, fg_per_image, reg_fg_thresh, cls_fg_thresh
     s.roi_per_image, s.fg_per_image, s.cls_mode = _i32(roi_per_image), _i32(fg_per_image), _i32(cls_mode)
     s.reg_fg_thresh, s.cls_fg_thresh, s.cls_bg_thresh = float(reg_fg_thresh), float(cls_fg_thresh), float(cls_bg_thresh)
     s.cls_bg_thresh_lo, s.hard_bg_ratio = float(cls_bg_thresh_lo), float(hard_bg_ratio)
+    return s
+
+
+OUTSIDE_MODES = {"clamp": 0, "drop": 1}
+
+
+class CenterCfgStruct(ctypes.Structure):
+    """snowgpu_center_cfg (include/snowgpu.h)."""
+    _fields_ = [("x0", ctypes.c_double), ("y0", ctypes.c_double), ("vx", ctypes.c_double), ("vy", ctypes.c_double), ("gaussian_overlap", ctypes.c_double),
+                ("stride", ctypes.c_int32), ("width", ctypes.c_int32), ("height", ctypes.c_int32), ("n_classes", ctypes.c_int32), ("n_heads", ctypes.c_int32),
+                ("max_objs", ctypes.c_int32), ("min_radius", ctypes.c_int32), ("outside", ctypes.c_int32), ("class_head", ctypes.c_int32 * 16)]
+
+
+def center_cfg_struct(x0, y0, vx, vy, stride, width, height, n_classes, n_heads, class_head, max_objs, gaussian_overlap, min_radius, outside):
+    """The settings of snowgpu_assign_centers_device from Python values; a count beyond int32 reaches the entry as one it refuses.  More
+    than 16 classes are kept in n_classes as they are (the first 16 heads stored): the entry refuses them."""
+    s = CenterCfgStruct()
+    s.x0, s.y0, s.vx, s.vy, s.gaussian_overlap = float(x0), float(y0), float(vx), float(vy), float(gaussian_overlap)
+    s.stride, s.width, s.height, s.n_classes, s.n_heads = _i32(stride), _i32(width), _i32(height), _i32(n_classes), _i32(n_heads)
+    s.max_objs, s.min_radius, s.outside = _i32(max_objs), _i32(min_radius), _i32(outside)
+    for i, h in enumerate(list(class_head)[:16]):
+        s.class_head[i] = _i32(h)
     return s
 
 
@@ -166,6 +188,9 @@ def lib():
             L.snowgpu_assign_anchors_device.restype = ctypes.c_int
             L.snowgpu_assign_anchors_device.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                         ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), vp, vp, vp, vp, vp, vp]
+            L.snowgpu_assign_centers_device.restype = ctypes.c_int
+            L.snowgpu_assign_centers_device.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(CenterCfgStruct), vp, vp, vp, vp,
+                                                        vp, vp, vp, vp, vp]
             L.snowgpu_paste_objects_device.restype = ctypes.c_int
             L.snowgpu_paste_objects_device.argtypes = [vp, ctypes.c_int, i64, i64, vp, vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, vp, i64, i64, vp, vp, vp, vp, vp,
                                                        ctypes.c_int, vp, vp, ctypes.c_uint64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
@@ -793,6 +818,18 @@ class Context:
                                                    (ctypes.c_double * max(len(m), 1))(*m), (ctypes.c_double * max(len(u), 1))(*u), vp(d_out_label or None),
                                                    vp(d_out_gt_index or None), vp(d_out_count or None), vp(d_out_gt_count or None), vp(d_out_iou or None),
                                                    vp(stream or None))
+        self._check_args(rc)
+
+    def assign_centers_device(self, n_frames, n_gt, d_gt_boxes, gt_features, dtype_code, cfg, d_out_heatmap, d_out_gt_index, d_out_ind, d_out_mask, d_out_offset,
+                              d_out_radius, d_out_count, d_out_state, stream=0):
+        """The centre heatmap targets of every frame (include/snowgpu.h: snowgpu_assign_centers_device); asynchronous on `stream`.  cfg: a
+        CenterCfgStruct (center_cfg_struct), read during the call.  An argument outside the domain, or an output overlapping the gt boxes
+        or another output, raises ValueError with the entry's words."""
+        vp = ctypes.c_void_p
+        rc = self._L.snowgpu_assign_centers_device(self._h, _i32(n_frames), _i32(n_gt), vp(d_gt_boxes or None), _i32(gt_features), int(dtype_code),
+                                                   ctypes.byref(cfg) if cfg is not None else None, vp(d_out_heatmap or None), vp(d_out_gt_index or None),
+                                                   vp(d_out_ind or None), vp(d_out_mask or None), vp(d_out_offset or None), vp(d_out_radius or None),
+                                                   vp(d_out_count or None), vp(d_out_state or None), vp(stream or None))
         self._check_args(rc)
 
     def paste_objects_device(self, n_frames, n_total, max_frame_rows, d_frame_off, d_rows, dtype_code, n_gt, d_gt_boxes, gt_features, d_pose_in, n_bank_points,

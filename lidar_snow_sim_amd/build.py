@@ -16,7 +16,7 @@ from pathlib import Path
 PKG = Path(__file__).resolve().parent
 CSRC = PKG / "csrc"
 LIB = PKG / "libsnowgpu.so"
-SOURCES = ["snowgpu_kernels.hip", "snowgpu_sort.hip", "snowgpu_compact.hip", "snowgpu_mask.hip", "snowgpu_dror.hip", "snowgpu_voxel.hip", "snowgpu_fps.hip", "snowgpu_ball.hip", "snowgpu_nn.hip", "snowgpu_box.hip", "snowgpu_roipool.hip", "snowgpu_roiaware.hip", "snowgpu_iou.hip", "snowgpu_targets.hip", "snowgpu_anchors.hip", "snowgpu_paste.hip", "snowgpu_scene.hip", "snowgpu_range.hip", "snowgpu_rows.hip", "snowgpu_prepass.hip", "snowgpu_wet.hip", "snowgpu_plane.hip", "snowgpu_sampler.hip", "snowgpu_weather.hip", "snowgpu_tables.hip", "snowgpu_api.cpp", "snowgpu_device.cpp", "snowgpu_stages.cpp", "snowgpu_batch.cpp", "snowgpu_host.cpp"]
+SOURCES = ["snowgpu_kernels.hip", "snowgpu_sort.hip", "snowgpu_compact.hip", "snowgpu_mask.hip", "snowgpu_dror.hip", "snowgpu_voxel.hip", "snowgpu_fps.hip", "snowgpu_ball.hip", "snowgpu_nn.hip", "snowgpu_box.hip", "snowgpu_roipool.hip", "snowgpu_roiaware.hip", "snowgpu_iou.hip", "snowgpu_targets.hip", "snowgpu_anchors.hip", "snowgpu_centers.hip", "snowgpu_paste.hip", "snowgpu_scene.hip", "snowgpu_range.hip", "snowgpu_rows.hip", "snowgpu_prepass.hip", "snowgpu_wet.hip", "snowgpu_plane.hip", "snowgpu_sampler.hip", "snowgpu_weather.hip", "snowgpu_tables.hip", "snowgpu_api.cpp", "snowgpu_device.cpp", "snowgpu_stages.cpp", "snowgpu_batch.cpp", "snowgpu_host.cpp"]
 # -ffp-contract=off: every decision of the reference is made on separately rounded float64/float32
 # operations (NumPy never fuses a multiply into an add); a contracted FMA would change them.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function"]

@@ -370,6 +370,12 @@ int sg_launch_assign_anchors(const struct SgAnchorCfg *cfg, int n_frames, int32_
                              const int32_t *anchor_class, int32_t n_gt, const void *gt, int32_t gt_features, int dtype, void *recs,
                              unsigned long long *top, int32_t *blk, int32_t *out_label, int32_t *out_gt_index, int32_t *out_count,
                              int32_t *out_gt_count, void *out_iou, void *stream);
+// Centre heatmap targets (sg_centers.h; the definition: include/snowgpu.h): two kernels.  cfg: host.  recs: n_frames x n_gt records of 24 bytes,
+// scratch.
+struct SgCenterCfg;
+int sg_launch_assign_centers(const struct SgCenterCfg *cfg, int n_frames, int32_t n_gt, const void *gt, int32_t gt_features, int dtype, void *recs,
+                             float *out_heatmap, int32_t *out_gt_index, int32_t *out_ind, uint8_t *out_mask, void *out_offset, int32_t *out_radius,
+                             int32_t *out_count, uint8_t *out_state, void *stream);
 // Ground-truth object paste (sg_paste.h; the definition: include/snowgpu.h): three kernels, the first only with a keep mask.  groups and ew
 // (3 doubles): host.  table: sg_paste_table() int32, frames: sg_paste_frames() records, grid: sg_paste_grid() words, all scratch.  keep,
 // pose_in, out_source and out_pose may be null.

@@ -788,6 +788,62 @@ static inline int sg_check_anchors_args(const SgAnchorsArgs &a, std::string *msg
     return sg_check_overlaps(who, outs, ins, "the targets are", true, msg);
 }
 
+// ---- snowgpu_assign_centers_device --------------------------------------------------------------------------------------------------------
+struct SgCentersCfg {                 // snowgpu_center_cfg (include/snowgpu.h), field for field
+    double x0, y0, vx, vy, gaussian_overlap;
+    int32_t stride, width, height, n_classes, n_heads, max_objs, min_radius, outside;
+    int32_t class_head[16];
+};
+
+struct SgCentersArgs {
+    int n_frames;
+    int n_gt;                         // B, per frame
+    const void *gt_boxes;
+    int gt_features;                  // Cg: column 7 is the class
+    int dtype;
+    const SgCentersCfg *cfg;          // host
+    float *out_heatmap;
+    int32_t *out_gt_index, *out_ind;
+    uint8_t *out_mask;
+    void *out_offset;
+    int32_t *out_radius, *out_count;
+    uint8_t *out_state;
+};
+
+// 0, or SG_ARGS_INVALID with *msg.  As above, the order is part of the ABI.
+static inline int sg_check_centers_args(const SgCentersArgs &a, std::string *msg)
+{
+    static const char *who = "snowgpu_assign_centers_device", *read = "the gt boxes are";
+    if (int rc = sg_check_head(who, a.n_frames, a.dtype, !a.gt_boxes || !a.cfg || !a.out_heatmap || !a.out_gt_index || !a.out_ind || !a.out_mask || !a.out_offset ||
+                                   !a.out_radius || !a.out_count || !a.out_state, msg))
+        return rc;
+    const SgCentersCfg &c = *a.cfg;
+    if (a.n_gt < 1 || a.n_gt > 256) return sg_refuse(who, ": n_gt must lie in 1 .. 256", msg);
+    if (a.gt_features < 8 || a.gt_features > 10)
+        return sg_refuse(who, ": gt_features must lie in 8 .. 10: cx, cy, cz, dx, dy, dz, heading, class first", msg);
+    if (c.n_classes < 1 || c.n_classes > 16) return sg_refuse(who, ": n_classes must lie in 1 .. 16", msg);
+    if (c.n_heads < 1 || c.n_heads > 16) return sg_refuse(who, ": n_heads must lie in 1 .. 16", msg);
+    for (int k = 0; k < c.n_classes; ++k)
+        if (c.class_head[k] < 0 || c.class_head[k] >= c.n_heads) return sg_refuse(who, ": every class needs a head in 0 .. n_heads - 1", msg);
+    if (c.max_objs < 1 || c.max_objs > 512) return sg_refuse(who, ": max_objs must lie in 1 .. 512", msg);
+    if (c.width < 1 || c.height < 1) return sg_refuse(who, ": the feature map needs at least one pixel on either axis", msg);
+    if ((int64_t)c.width * c.height > ((int64_t)1 << 31) - 1 || (int64_t)a.n_frames * c.n_classes * ((int64_t)c.width * c.height) > ((int64_t)1 << 31) - 1)
+        return sg_refuse(who, ": n_frames * n_classes * height * width exceeds 2^31 - 1; split the batch", msg);
+    if (!std::isfinite(c.x0) || !std::isfinite(c.y0) || !(c.vx > 0.0) || !(c.vy > 0.0) || !std::isfinite(c.vx) || !std::isfinite(c.vy))          // (false for NaN)
+        return sg_refuse(who, ": the origin of the range must be finite, the voxel's x and y edges positive and finite", msg);
+    if (c.stride < 1) return sg_refuse(who, ": stride must be at least 1", msg);
+    if (!(c.gaussian_overlap > 0.0 && c.gaussian_overlap < 1.0)) return sg_refuse(who, ": gaussian_overlap must lie strictly between 0 and 1", msg);      // (false for NaN)
+    if (c.min_radius < 0 || c.min_radius > 512) return sg_refuse(who, ": min_radius must lie in 0 .. 512", msg);
+    if (c.outside != 0 && c.outside != 1) return sg_refuse(who, ": outside must be 0 (clamp) or 1 (drop)", msg);
+    const size_t esz = a.dtype == 0 ? 4 : 8, q = (size_t)a.n_frames * (size_t)c.n_heads * (size_t)c.max_objs, g = (size_t)a.n_frames * (size_t)a.n_gt;
+    const SgOutSpan outs[8] = {
+        {a.out_heatmap, (size_t)a.n_frames * (size_t)c.n_classes * (size_t)c.height * (size_t)c.width * 4, "d_out_heatmap"}, {a.out_gt_index, q * 4, "d_out_gt_index"},
+        {a.out_ind, q * 4, "d_out_ind"}, {a.out_mask, q, "d_out_mask"}, {a.out_offset, q * 2 * esz, "d_out_offset"}, {a.out_radius, q * 4, "d_out_radius"},
+        {a.out_count, (size_t)a.n_frames * (size_t)c.n_heads * 4, "d_out_count"}, {a.out_state, g, "d_out_state"}};
+    const SgInSpan ins[1] = {{a.gt_boxes, g * (size_t)a.gt_features * esz, "d_gt_boxes", read, "them"}};
+    return sg_check_overlaps(who, outs, ins, "the targets are", true, msg);
+}
+
 // ---- snowgpu_paste_objects_device ---------------------------------------------------------------------------------------------------------
 struct SgPasteArgs {
     int n_frames;

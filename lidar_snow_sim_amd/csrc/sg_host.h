@@ -133,6 +133,8 @@ struct __attribute__((visibility("default"))) snowgpu_ctx {
     DevBuf<double> anchor_rec;
     DevBuf<unsigned long long> anchor_top;
     DevBuf<int32_t> anchor_blk;
+    // centre heatmap targets (snowgpu_assign_centers_device): one record of three doubles per gt
+    DevBuf<double> center_rec;
     // object paste (snowgpu_paste_objects_device): one int32 per (frame, run of 512 rows) -- the run's absent rows, then those of the runs
     // before it --, one SgPasteFrame (bytes) per frame: the pasted slots' bases and enlarged boxes, and one word per (frame, grid cell):
     // the pasted boxes that can reach the cell (32 KB a frame)

@@ -19,6 +19,7 @@
 #include "sg_range.h"       // the geometry of the range image and the limits in the rows' dtype
 #include "sg_targets.h"     // SgTargetCfg of the proposal target sampling
 #include "sg_anchors.h"     // SgAnchorCfg and the record of the anchor target assignment
+#include "sg_centers.h"     // SgCenterCfg and the record of the centre heatmap targets
 #include "sg_paste.h"       // SgPasteGroups and the scratch of the object paste
 #include "sg_scene.h"       // SgSceneCfg and the scratch of the scene transforms
 
@@ -401,6 +402,34 @@ extern "C" int snowgpu_assign_anchors_device(snowgpu_ctx *ctx, int n_frames, int
                     sg_launch_assign_anchors(&k, n_frames, n_anchors, d_anchors, anchor_features, d_anchor_class, n_gt, d_gt_boxes, gt_features, dtype, ctx->anchor_rec.p,
                                              ctx->anchor_top.p, ctx->anchor_blk.p, d_out_label, d_out_gt_index, d_out_count, d_out_gt_count, d_out_iou,
                                              stream_of(ctx, stream)));
+}
+
+// Centre heatmap targets (snowgpu_centers.hip; presence, the centre, the radius, the record and the value of a pixel: sg_centers.h).  See
+// include/snowgpu.h.
+extern "C" int snowgpu_assign_centers_device(snowgpu_ctx *ctx, int n_frames, int n_gt, const void *d_gt_boxes, int gt_features, int dtype,
+                                             const snowgpu_center_cfg *cfg, float *d_out_heatmap, int32_t *d_out_gt_index, int32_t *d_out_ind,
+                                             uint8_t *d_out_mask, void *d_out_offset, int32_t *d_out_radius, int32_t *d_out_count, uint8_t *d_out_state,
+                                             void *stream)
+{
+    if (!ctx) return SNOWGPU_E_INVALID;
+    SgCentersCfg c{};
+    if (cfg) {
+        c = SgCentersCfg{cfg->x0, cfg->y0, cfg->vx, cfg->vy, cfg->gaussian_overlap, cfg->stride, cfg->width, cfg->height, cfg->n_classes, cfg->n_heads,
+                         cfg->max_objs, cfg->min_radius, cfg->outside, {}};
+        for (int k = 0; k < 16; ++k) c.class_head[k] = cfg->class_head[k];
+    }
+    const SgCentersArgs a{n_frames, n_gt, d_gt_boxes, gt_features, dtype, cfg ? &c : nullptr, d_out_heatmap, d_out_gt_index, d_out_ind, d_out_mask, d_out_offset,
+                          d_out_radius, d_out_count, d_out_state};
+    if (int rc = checked(ctx, sg_check_centers_args, a)) return rc;
+    SgCenterCfg k{};
+    k.x0 = c.x0; k.y0 = c.y0; k.vx = c.vx; k.vy = c.vy; k.stride = (double)c.stride; k.overlap = c.gaussian_overlap;
+    k.W = c.width; k.H = c.height; k.n_classes = c.n_classes; k.n_heads = c.n_heads; k.max_objs = c.max_objs; k.min_radius = c.min_radius; k.drop = c.outside;
+    for (int j = 0; j < c.n_classes; ++j) k.class_head[j] = c.class_head[j];
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    ENSURE(ctx, ctx->center_rec, (size_t)n_frames * (size_t)n_gt * (sizeof(SgCenterRec) / sizeof(double)));
+    return launched(ctx, "centre targets",
+                    sg_launch_assign_centers(&k, n_frames, n_gt, d_gt_boxes, gt_features, dtype, ctx->center_rec.p, d_out_heatmap, d_out_gt_index, d_out_ind, d_out_mask,
+                                             d_out_offset, d_out_radius, d_out_count, d_out_state, stream_of(ctx, stream)));
 }
 
 // Ground-truth object paste (snowgpu_paste.hip; the slots, the draw, the sweep and the scratch: sg_paste.h).  See include/snowgpu.h.

@@ -1,6 +1,6 @@
 """The device stages of the torch-tensor boundary (tensors.py is the documented import path and lists what each is for) and the batches
 of static shape they leave behind: fov_keep, dror_keep, voxelize, sample_keypoints, ball_query, range_image, nearest_keypoints,
-points_in_boxes, boxes_iou, nms, roi_point_pool, roi_voxel_pool, sample_rois, assign_anchors, paste_objects, transform_scene.  Every stage goes through the same steps, in this order -- it is the order in which a call that is wrong
+points_in_boxes, boxes_iou, nms, roi_point_pool, roi_voxel_pool, sample_rois, assign_anchors, assign_centers, paste_objects, transform_scene.  Every stage goes through the same steps, in this order -- it is the order in which a call that is wrong
 in two ways is refused: the aligned unwrap and the device-input refusal (_stage_frames), the scalar and range checks (_whole, _range6),
 the batch and its keep mask (_stage_batch), the stage's own tensors, the checks of the shapes' domain, out= (_checked_out), the launch
 (_stage_launch).  PyTorch is plumbing here; the work is the C entries'."""
@@ -1358,6 +1358,137 @@ def assign_anchors(anchors, anchor_class, gt_boxes, matched=(0.6, 0.5, 0.5), unm
                                       out.label.data_ptr(), out.gt_index.data_ptr(), out.count.data_ptr(), out.gt_count.data_ptr(),
                                       0 if iou is None else iou.data_ptr(), run.cuda_stream)
     return out if (iou is None) == (out.iou is None) else AnchorTargetBatch(out.label, out.gt_index, out.count, out.gt_count, iou)
+
+
+CENTER_STATES = {"absent": 0, "drawn": 1, "dropped": 2, "no_slot": 3}
+
+
+class CenterTargetBatch:
+    """What assign_centers() leaves behind, F = frames, B = gt boxes per frame, NC = classes, NH = heads, M = max_objs, (W, H) the feature
+    map -- every shape static, every element written by every call: `heatmap` (F, NC, H, W float32: channel c - 1 is class c), `gt_index`
+    (F, NH, M int32: the gt of each slot, -1 when empty), `ind` (F, NH, M int32: ciy * W + cix, 0 when empty), `mask` (F, NH, M bool),
+    `offset` (F, NH, M, 2 in the boxes' dtype: the fractional part of the centre), `radius` (F, NH, M int32), `count` (F, NH int32: the
+    filled slots) and `state` (F, B uint8: CENTER_STATES).  head_heatmap() and target_boxes() are pure indexing and torch arithmetic, no
+    kernel of this library.  All still being written until the stream the call was made on has caught up."""
+
+    FIELDS = ("heatmap", "gt_index", "ind", "mask", "offset", "radius", "count", "state")
+
+    def __init__(self, heatmap, gt_index, ind, mask, offset, radius, count, state, class_head=None):
+        self.heatmap, self.gt_index, self.ind, self.mask, self.offset, self.radius, self.count, self.state = heatmap, gt_index, ind, mask, offset, radius, count, state
+        self.class_head = None if class_head is None else tuple(int(h) for h in class_head)
+
+    @classmethod
+    def empty(cls, n_frames, n_gt, n_classes, n_heads, max_objs, feature_map_size, dtype=None, device=None):
+        """Uninitialised buffers of the shapes assign_centers() writes (out=): static addresses for a captured graph.  feature_map_size: (W, H)."""
+        import torch
+        dev = _cuda_device(torch, device)
+        F, B, NC, NH, M = int(n_frames), int(n_gt), int(n_classes), int(n_heads), int(max_objs)
+        W, H = (int(v) for v in feature_map_size)
+
+        def new(shape, kind):
+            return torch.empty(shape, dtype=kind, device=dev)
+        return cls(new((F, NC, H, W), torch.float32), new((F, NH, M), torch.int32), new((F, NH, M), torch.int32), new((F, NH, M), torch.bool),
+                   new((F, NH, M, 2), dtype or torch.float32), new((F, NH, M), torch.int32), new((F, NH), torch.int32), new((F, B), torch.uint8))
+
+    def head_heatmap(self, head):
+        """(F, the head's classes, H, W): the channels of the classes whose head is `head`, in ascending class -- a view when they are
+        adjacent, as a head's classes usually are."""
+        if self.class_head is None:
+            raise ValueError("head_heatmap: this batch was not filled by assign_centers() yet: the classes of a head are not known")
+        at = [c for c, h in enumerate(self.class_head) if h == int(head)]
+        if not at:
+            raise ValueError(f"head_heatmap: no class has head {head}")
+        return self.heatmap[:, at[0]:at[-1] + 1] if at == list(range(at[0], at[-1] + 1)) else self.heatmap[:, at]
+
+    def target_boxes(self, gt_boxes):
+        """(F, NH, M, Cg): per slot the regression targets of a centre head -- offset x, offset y, z, log dx, log dy, log dz, cos and sin of the
+        heading, then the columns behind the class -- and a zero row in an empty slot.  Torch arithmetic on `gt_index`."""
+        import torch
+        F, NH, M = self.gt_index.shape
+        if not (torch.is_tensor(gt_boxes) and gt_boxes.dim() == 3 and gt_boxes.shape[0] == F and gt_boxes.shape[1] == self.state.shape[1] and
+                gt_boxes.shape[2] >= 8 and gt_boxes.device == self.gt_index.device):
+            raise ValueError(f"target_boxes: gt_boxes must be the ({F}, {self.state.shape[1]}, Cg) tensor the centres were assigned to, on their device")
+        Cg = gt_boxes.shape[2]
+        at = self.gt_index.long().reshape(F, NH * M)
+        full = (at >= 0)[..., None]
+        got = torch.gather(gt_boxes, 1, at.clamp(min=0)[..., None].expand(-1, -1, Cg))
+        safe = torch.where(full, got[..., 3:6], torch.ones_like(got[..., 3:6]))                  # (no log of a padding row's zeros)
+        out = torch.cat((self.offset.reshape(F, NH * M, 2).to(got.dtype), got[..., 2:3], torch.log(safe), torch.cos(got[..., 6:7]), torch.sin(got[..., 6:7]),
+                         got[..., 8:]), dim=2)
+        return torch.where(full, out, torch.zeros_like(out)).reshape(F, NH, M, Cg)
+
+
+def assign_centers(gt_boxes, point_cloud_range, voxel_size, stride, feature_map_size, n_classes=3, class_head=None, max_objs=500, gaussian_overlap=0.1,
+                   min_radius=2, outside="clamp", *, out=None, slot=0):
+    """The centre heatmap targets of every frame on the device (snowgpu_assign_centers_device; the definition: include/snowgpu.h): the
+    assignment of pcdet's CenterHead with static shapes and nothing read on the host -- per gt the centre pixel, its fractional offset and
+    the Gaussian radius in float64, per head the gts' slots in ascending gt number, per class the maximum of the gts' Gaussians.  The
+    definition is this library's, modelled on pcdet's CenterHead and centernet_utils.
+
+    gt_boxes           a contiguous (F, B, 8 .. 10) float32 or float64 CUDA tensor, 1 <= B <= 256: cx, cy, cz, dx, dy, dz, heading, class
+                       first; zero rows are padding (zero the gts an augmentation emptied: points_in_boxes(res, gt).keep_boxes(min_points)).
+    point_cloud_range  6 numbers (x0, y0, z0, x1, y1, z1): x0 and y0 are used.   voxel_size  3 numbers: vx and vy are used.
+    stride             the feature map's stride, a whole number >= 1.   feature_map_size  (W, H).
+    class_head         the head of every class, n_classes whole numbers from 0; None: one head.  NH is the largest + 1.
+    max_objs           the slots of a head, 1 .. 512.   min_radius  0 .. 512.   outside  'clamp' (pcdet) or 'drop'.
+    out                a CenterTargetBatch to write into (CenterTargetBatch.empty): every element is written, nothing needs clearing.
+    The gt records are scratch of the engine of `slot`: calls made on streams that are not ordered against each other need a `slot` each.
+
+    Returns a CenterTargetBatch.  Asynchronous on torch's current stream; nothing is read on the host: capturable after one warm-up call."""
+    import torch
+    from . import engine as _engine
+    from ._native import OUTSIDE_MODES, center_cfg_struct
+    who = "assign_centers"
+    rng, size = np.asarray(point_cloud_range, np.float64).reshape(-1), np.asarray(voxel_size, np.float64).reshape(-1)
+    if rng.shape != (6,) or size.shape != (3,):
+        raise ValueError(f"{who}: point_cloud_range holds 6 numbers (x0, y0, z0, x1, y1, z1), voxel_size 3")
+    try:
+        W, H = feature_map_size
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: feature_map_size holds 2 whole numbers (W, H)") from None
+    _whole(who, stride=stride, W=W, H=H, n_classes=n_classes, max_objs=max_objs, min_radius=min_radius)
+    W, H, NC, M = int(W), int(H), int(n_classes), int(max_objs)
+    if outside not in OUTSIDE_MODES:
+        raise ValueError(f"{who}: outside must be 'clamp' or 'drop'")
+    heads = [0] * max(NC, 0) if class_head is None else list(class_head)
+    if len(heads) != NC or any(int(h) != h for h in heads):
+        raise ValueError(f"{who}: class_head holds one whole number per class")
+    heads = [int(h) for h in heads]
+    NH = max(heads, default=0) + 1
+    if not (torch.is_tensor(gt_boxes) and gt_boxes.is_cuda and gt_boxes.dim() == 3 and gt_boxes.dtype in (torch.float32, torch.float64) and gt_boxes.is_contiguous()):
+        raise ValueError(f"{who}: gt_boxes must be a contiguous (frames, B, 8 .. 10) float32 or float64 CUDA tensor")
+    F, B, Cg = (int(v) for v in gt_boxes.shape)
+    dev, dt = gt_boxes.device, gt_boxes.dtype
+    # (the shapes below need these; the entry refuses them in the same words, and everything else of the domain)
+    if F < 1:
+        raise ValueError(f"{who}: the frames must be at least 1")
+    if not 1 <= B <= 256:
+        raise ValueError(f"{who}: n_gt must lie in 1 .. 256")
+    if not 1 <= NC <= 16:
+        raise ValueError(f"{who}: n_classes must lie in 1 .. 16")
+    if not 1 <= NH <= 16 or min(heads) < 0:
+        raise ValueError(f"{who}: every class needs a head in 0 .. 15")
+    if not 1 <= M <= 512:
+        raise ValueError(f"{who}: max_objs must lie in 1 .. 512")
+    if W < 1 or H < 1:
+        raise ValueError(f"{who}: the feature map needs at least one pixel on either axis")
+    if F * NC * H * W > 2 ** 31 - 1:
+        raise ValueError(f"{who}: n_frames * n_classes * height * width exceeds 2^31 - 1; split the batch")
+    want = (("heatmap", torch.float32, (F, NC, H, W), True), ("gt_index", torch.int32, (F, NH, M), True), ("ind", torch.int32, (F, NH, M), True),
+            ("mask", torch.bool, (F, NH, M), True), ("offset", dt, (F, NH, M, 2), True), ("radius", torch.int32, (F, NH, M), True),
+            ("count", torch.int32, (F, NH), True), ("state", torch.uint8, (F, B), True))
+    if out is None:
+        out = CenterTargetBatch.empty(F, B, NC, NH, M, (W, H), dt, dev)
+    else:
+        _checked_out(torch, who, CenterTargetBatch, out, want, dev, "gt boxes")
+    out.class_head = tuple(heads)
+    cfg = center_cfg_struct(rng[0], rng[1], size[0], size[1], stride, W, H, NC, NH, heads, M, gaussian_overlap, min_radius, OUTSIDE_MODES[outside])
+    eng = _engine.get_engine(dev.index, slot)
+    with torch.cuda.device(dev), _on_run_stream(torch, eng, dev) as (_, run):
+        eng.ctx.assign_centers_device(F, B, gt_boxes.data_ptr(), Cg, 0 if dt == torch.float32 else 1, cfg, out.heatmap.data_ptr(), out.gt_index.data_ptr(),
+                                      out.ind.data_ptr(), out.mask.data_ptr(), out.offset.data_ptr(), out.radius.data_ptr(), out.count.data_ptr(),
+                                      out.state.data_ptr(), run.cuda_stream)
+    return out
 
 
 PASTE_STATES = {"inactive": 0, "pasted": 1, "hit_gt": 2, "hit_pasted": 3, "no_room": 4, "absent": 5}

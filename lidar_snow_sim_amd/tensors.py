@@ -52,6 +52,10 @@ The reference's training-time caller (the OpenPCDet DENSE dataset: `root_path`, 
     for a positive, 0 for background, -1 for ignored -- by the nearest axis-aligned BEV overlap per class, with the gt a positive regresses
     to (AnchorTargetBatch; snowgpu_assign_anchors_device): the assignment of pcdet's AxisAlignedTargetAssigner, fed the gts that
     `points_in_boxes(res, gt).keep_boxes(min_points)` left; `anchor_grid(...)` lays the anchors out as pcdet's AnchorGenerator does.
+  * `assign_centers(gt_boxes, point_cloud_range, voxel_size, stride, feature_map_size=(W, H))` makes the targets of a centre-based first
+    stage in every frame -- the class heatmaps as the maximum of the gts' Gaussians, and per head and slot the gt, its centre pixel, the
+    fractional offset and the radius (CenterTargetBatch; snowgpu_assign_centers_device): the assignment of pcdet's CenterHead, fed the
+    gts that `points_in_boxes(res, gt).keep_boxes(min_points)` left; `.target_boxes(gt_boxes)` gives the regression targets.
   * `paste_objects(frames, gt_boxes, bank, sample_groups, step=...)` pastes database objects into the ABSENT rows of a padded batch, in
     front of the snowfall stage -- per class as many as the frame lacks, drawn from an `ObjectBank` by (seed, step, frame), dropped where
     they overlap a gt or an earlier object, their boxes appended to the gts and the scene rows inside them cleared (PasteBatch;
@@ -83,8 +87,8 @@ import numpy as np
 from . import _native
 from .batch import (LANE_SLOT0, AlignedResult, AlignedWetResult, DeviceBatch, DeviceResult, _cuda_device, _keep_mask, _on_run_stream,  # noqa: F401
                     _resolve_input, _uploads, is_device_input)
-from .stages import (IOU_MODES, PASTE_STATES, SCENE_STATES, AnchorTargetBatch, BoxLabelBatch, IouBatch, KeypointBatch, NearestBatch, NeighbourBatch, NmsBatch, ObjectBank, PasteBatch, RangeImageBatch, RoiPointBatch, RoiTargetBatch, RoiVoxelBatch, SceneBatch, VoxelBatch,  # noqa: F401
-                     _fov_mask, anchor_grid, assign_anchors, ball_query, boxes_iou, dror_keep, fov_keep, nearest_keypoints, nms, paste_objects, points_in_boxes, range_image, roi_point_pool,
+from .stages import (CENTER_STATES, IOU_MODES, PASTE_STATES, SCENE_STATES, AnchorTargetBatch, BoxLabelBatch, CenterTargetBatch, IouBatch, KeypointBatch, NearestBatch, NeighbourBatch, NmsBatch, ObjectBank, PasteBatch, RangeImageBatch, RoiPointBatch, RoiTargetBatch, RoiVoxelBatch, SceneBatch, VoxelBatch,  # noqa: F401
+                     _fov_mask, anchor_grid, assign_anchors, assign_centers, ball_query, boxes_iou, dror_keep, fov_keep, nearest_keypoints, nms, paste_objects, points_in_boxes, range_image, roi_point_pool,
                      roi_voxel_pool, sample_keypoints, sample_rois, transform_scene, voxelize)
 
 
