@@ -35,7 +35,8 @@
 #define SG_DROR_SR_GRID_MAX 4e6    /* m: a larger sr_min reaches every usable row of the frame; the grid is laid out for this one */
 #define SG_DROR_MIN_CELLS 1024     /* cell budget per frame: at least this, */
 #define SG_DROR_MAX_CELLS 81920    /* at most this (sg_dror_cell_budget): 4 bytes of scratch per cell and frame */
-#define SG_DROR_NO_CELL 0xffffffffu
+#define SG_NO_CELL 0xffffffffu     /* in a per-row cell entry: this row files nowhere (here and in sg_ball.h's cells, which include this header) */
+#define SG_DROR_NO_CELL SG_NO_CELL /* the name the host harnesses (tests/host_harness/dror_cells.cpp, ball_cells.cpp) know it by */
 
 struct SgDrorGrid {
     double c2, s2min;              // the definition's constants

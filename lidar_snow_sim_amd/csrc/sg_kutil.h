@@ -1,20 +1,12 @@
-// sg_kutil.h -- small device helpers shared by the kernel files (snowgpu_sort.hip, snowgpu_kernels.hip, snowgpu_compact.hip, snowgpu_rows.hip).
+// sg_kutil.h -- small device helpers shared by the snowfall kernel files (snowgpu_kernels.hip, snowgpu_sort.hip, snowgpu_compact.hip, snowgpu_mask.hip,
+// snowgpu_rows.hip); the offsets search sg_find_frame comes from sg_rowkit.h, which the row stages share with them.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "sg_common.h"
 #include "sg_beam.h"
+#include "sg_rowkit.h"
 
 #define SG_BLOCK 256      /* threads per block of the kernels that walk a frame by 1024-row tiles (four rows per thread) */
-
-__device__ __forceinline__ int sg_find_frame(const int64_t *__restrict__ off, int n_frames, int64_t g)
-{
-    int lo = 0, hi = n_frames - 1;   // largest f with off[f] <= g
-    while (lo < hi) {
-        int mid = (lo + hi + 1) >> 1;
-        if (off[mid] <= g) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
 
 __device__ __forceinline__ unsigned long long sg_lanemask_lt()
 {

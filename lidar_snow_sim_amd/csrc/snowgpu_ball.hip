@@ -1,6 +1,7 @@
 // snowgpu_ball.hip -- ball-query neighbour groups around keypoints (snowgpu_ball_query_device; definition: include/snowgpu.h; the grid, the
-// window, the selection network and the scratch sizes: sg_ball.h).  Cell lists as the outlier filter builds them (snowgpu_dror.hip), then
-// one wave per centre; four kernels behind one memset, on one stream:
+// window, the selection network and the scratch sizes: sg_ball.h).  Cell lists by count, scan and scatter -- the frame of a row, the
+// presence test, the atomic per run of lanes and the scan are sg_rowkit.h's -- then one wave per centre; four kernels behind one memset,
+// on one stream:
 //   k_ball_count    every usable row: its cell (sg_ball_cell), kept per row, and one atomic on the cell's counter per run of lanes in it
 //   k_ball_scan     one block per frame: the counters become the cells' first positions in the frame's slot of the sorted copy
 //   k_ball_scatter  x, y, z AND THE SOURCE ROW of every usable row into its cell's span (the atomic that hands out the position turns the
@@ -20,85 +21,39 @@
 #include "sg_ball.h"
 #include "sg_common.h"
 #include "sg_launch.h"
+#include "sg_rowkit.h"
 
 #define SG_BALL_BLOCK 256
 #define SG_BALL_SCAN_BLOCK 1024
 #define SG_BALL_QUERY_WAVES 4       /* centres per block of k_ball_query */
 
-// largest f with off[f] <= i (off[0] <= i < off[n_frames])
-__device__ __forceinline__ int ball_frame(const int64_t *__restrict__ off, int n_frames, int64_t i)
-{
-    int lo = 0, hi = n_frames - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (off[mid] <= i) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
-
-// A run of consecutive lanes with the same entry is ONE atomic, made by its first lane (as snowgpu_dror.hip's dror_run): *head = the
-// run's first lane, *len = its lanes.  Every lane of the wave must call this.
-__device__ __forceinline__ void ball_run(uint32_t e, int lane, int *head, int *len)
-{
-    const uint32_t prev = __shfl_up(e, 1);
-    const unsigned long long heads = __ballot(lane == 0 || prev != e);
-    const unsigned long long upto = lane == 63 ? ~0ull : (2ull << lane) - 1ull;
-    *head = 63 - __clzll((long long)(heads & upto));
-    const unsigned long long after = heads & ~upto;
-    *len = (after ? __ffsll((long long)after) - 1 : 64) - *head;
-}
-
-// cell_of[i] = the entry of row i's cell (frame f, cell c: f (cells + 1) + 1 + c), or SG_DROR_NO_CELL for a row that is not usable
+// cell_of[i] = the entry of row i's cell (frame f, cell c: f (cells + 1) + 1 + c), or SG_NO_CELL for a row that is not usable
 template <typename T>
 __global__ __launch_bounds__(SG_BALL_BLOCK) void k_ball_count(const T *__restrict__ rows, int64_t n, const int64_t *__restrict__ frame_off, int n_frames,
                                                              const uint8_t *__restrict__ keep_in, SgFpsRange range, SgBallGrid g,
                                                              uint32_t *__restrict__ entry, uint32_t *__restrict__ cell_of)
 {
     const int64_t i = (int64_t)blockIdx.x * SG_BALL_BLOCK + threadIdx.x;
-    uint32_t e = SG_DROR_NO_CELL;
-    if (i < n && i >= frame_off[0] && i < frame_off[n_frames] && (!keep_in || keep_in[i] != 0)) {
+    uint32_t e = SG_NO_CELL;
+    if (sg_row_present(frame_off, n_frames, keep_in, i, n)) {
         const T *row = rows + i * 5;
         const T x = row[0], y = row[1], z = row[2];
         if (sg_fps_usable<T>(range, x, y, z)) {
-            const int f = ball_frame(frame_off, n_frames, i);
+            const int f = sg_find_frame(frame_off, n_frames, i);
             e = (uint32_t)((int64_t)f * (g.cells + 1) + 1 + sg_ball_cell(g, (double)x, (double)y));
         }
     }
-    const int lane = threadIdx.x & 63;
-    int head, len;
-    ball_run(e, lane, &head, &len);
-    if (lane == head && e != SG_DROR_NO_CELL) atomicAdd(&entry[e], (uint32_t)len);
+    sg_run_add(entry, e, SG_NO_CELL, threadIdx.x & 63);
     if (i < n) cell_of[i] = e;
 }
 
 // entry[f (cells + 1)] = frame_off[f]; entry[.. + 1 + c] = frame_off[f] + the rows filed in the cells before c
 __global__ __launch_bounds__(SG_BALL_SCAN_BLOCK) void k_ball_scan(const int64_t *__restrict__ frame_off, int32_t cells, uint32_t *__restrict__ entry)
 {
-    __shared__ uint32_t wave_sum[SG_BALL_SCAN_BLOCK / 64];
-    const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    uint32_t *e = entry + (int64_t)f * (cells + 1);
-    uint32_t carry = (uint32_t)frame_off[f];
-    if (tid == 0) e[0] = carry;
-    for (int32_t c0 = 0; c0 < cells; c0 += SG_BALL_SCAN_BLOCK) {
-        const int32_t c = c0 + tid;
-        const uint32_t v = c < cells ? e[1 + c] : 0u;
-        uint32_t incl = v;
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t up = __shfl_up(incl, d);
-            if (lane >= d) incl += up;
-        }
-        if (lane == 63) wave_sum[wave] = incl;
-        __syncthreads();
-        uint32_t before = 0, total = 0;
-        for (int w = 0; w < SG_BALL_SCAN_BLOCK / 64; ++w) {
-            const uint32_t s = wave_sum[w];
-            before += w < wave ? s : 0u;
-            total += s;
-        }
-        if (c < cells) e[1 + c] = carry + before + incl - v;
-        carry += total;
-        __syncthreads();
-    }
+    uint32_t *e = entry + (int64_t)blockIdx.x * (cells + 1);
+    const uint32_t first = (uint32_t)frame_off[blockIdx.x];
+    if (threadIdx.x == 0) e[0] = first;
+    sg_block_scan_excl<SG_BALL_SCAN_BLOCK>(e + 1, e + 1, cells, first);
 }
 
 template <typename T>
@@ -107,16 +62,10 @@ __global__ __launch_bounds__(SG_BALL_BLOCK) void k_ball_scatter(const T *__restr
                                                                int32_t *__restrict__ ssrc)
 {
     const int64_t i = (int64_t)blockIdx.x * SG_BALL_BLOCK + threadIdx.x;
-    const uint32_t e = i < n ? cell_of[i] : SG_DROR_NO_CELL;
-    const int lane = threadIdx.x & 63;
-    int head, len;
-    ball_run(e, lane, &head, &len);
-    uint32_t base = 0;
-    if (lane == head && e != SG_DROR_NO_CELL) base = atomicAdd(&entry[e], (uint32_t)len);      // the run's positions: consecutive
-    base = __shfl(base, head);
-    if (e == SG_DROR_NO_CELL) return;
-    const T *row = rows + i * 5;
-    const int64_t p = (int64_t)(base + (uint32_t)(lane - head));      // (below the frame's end: a frame files no more rows than it has)
+    const uint32_t e = i < n ? cell_of[i] : SG_NO_CELL;
+    const int64_t p = (int64_t)sg_run_claim(entry, e, SG_NO_CELL, threadIdx.x & 63);
+    if (e == SG_NO_CELL) return;
+    const T *row = rows + i * 5;                                      // (p below the frame's end: a frame files no more rows than it has)
     sx[p] = row[0]; sy[p] = row[1]; sz[p] = row[2];
     ssrc[p] = (int32_t)i;
 }

@@ -5,8 +5,9 @@
 //                pose and the zeroed counts written, the frame's bit table cleared by the workgroup itself and then every present box
 //                marked by atomicOr in every cell its footprint can touch -- box after box, the lanes over the cells of its rectangle,
 //                so a box that covers the whole frame costs 16 steps -- and in the frame's word of present boxes.
-//   k_box_rows   one LANE per row: the frame by the offsets search, the usable test, the words of the row's cell, and for every set bit
-//                ascending the membership test from the box record.  The first hit is box_of and gives the local coordinates; every hit
+//   k_box_rows   one LANE per row: the presence test and the frame by the offsets search (both sg_rowkit.h's), the usable test, the words
+//                of the row's cell, and for every set bit ascending the membership test from the box record.
+//                The first hit is box_of and gives the local coordinates; every hit
 //                counts.  The loop over candidates is uniform across the wave, so equal boxes are folded by ballot before one lane adds
 //                their number to the count: rows of one object are neighbours in the sensor's order, and 64 adds become one.
 // The counts are integer sums and the marks are ORs: the result depends on no arrival order.
@@ -17,6 +18,7 @@
 #include "sg_box.h"
 #include "sg_common.h"
 #include "sg_launch.h"
+#include "sg_rowkit.h"
 
 #define SG_BOX_BLOCK 256
 
@@ -61,17 +63,6 @@ __global__ __launch_bounds__(SG_BOX_BLOCK) void k_box_file(const T *__restrict__
 #endif
 }
 
-// largest f with off[f] <= i (off[0] <= i < off[n_frames])
-__device__ __forceinline__ int box_frame(const int64_t *__restrict__ off, int n_frames, int64_t i)
-{
-    int lo = 0, hi = n_frames - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (off[mid] <= i) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
-
 template <typename T>
 __global__ __launch_bounds__(SG_BOX_BLOCK) void k_box_rows(const T *__restrict__ rows, int64_t n, const int64_t *__restrict__ frame_off, int n_frames,
                                                            const uint8_t *__restrict__ keep_in, int32_t B, const SgBoxRec *__restrict__ rec,
@@ -81,7 +72,7 @@ __global__ __launch_bounds__(SG_BOX_BLOCK) void k_box_rows(const T *__restrict__
     const int64_t i = (int64_t)blockIdx.x * SG_BOX_BLOCK + threadIdx.x;
     const int lane = threadIdx.x & 63;
     const int32_t W = sg_box_words(B);
-    bool usable = i < n && i >= frame_off[0] && i < frame_off[n_frames] && (!keep_in || keep_in[i] != 0);
+    bool usable = sg_row_present(frame_off, n_frames, keep_in, i, n);
     double x = 0.0, y = 0.0, z = 0.0;
     if (usable) {
         const T *row = rows + i * 5;
@@ -92,7 +83,7 @@ __global__ __launch_bounds__(SG_BOX_BLOCK) void k_box_rows(const T *__restrict__
     int f = 0;
     const unsigned long long *words = table;
     if (usable) {
-        f = box_frame(frame_off, n_frames, i);
+        f = sg_find_frame(frame_off, n_frames, i);
 #ifdef SG_BOX_BRUTE
         const int32_t cell = SG_BOX_CELLS;
 #else

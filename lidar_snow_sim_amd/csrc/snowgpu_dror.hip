@@ -6,6 +6,7 @@
 //                   its END: cell c of a frame then spans [entry[c], entry[c + 1]), entry[0] the frame's first position)
 //   k_dror_query    one thread per row: the spans of its window, the exact test, out as soon as k_min neighbours (and itself) are counted
 // Counts are integers: neither the order of a span nor that of the walk changes a result.
+// The frame of a row, the presence test, the atomic per run of lanes and the scan are sg_rowkit.h's.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -13,85 +14,38 @@
 #include "sg_common.h"
 #include "sg_dror.h"
 #include "sg_launch.h"
+#include "sg_rowkit.h"
 
 #define SG_DROR_BLOCK 256
 #define SG_DROR_SCAN_BLOCK 1024
 
-// largest f with off[f] <= i (off[0] <= i < off[n_frames])
-__device__ __forceinline__ int dror_frame(const int64_t *__restrict__ off, int n_frames, int64_t i)
-{
-    int lo = 0, hi = n_frames - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (off[mid] <= i) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
-
-// Rows that follow one another in a sweep fall into the same cell, and atomics of one wave on one address queue behind one another in L2:
-// a run of consecutive lanes with the same entry is ONE atomic, made by its first lane.  *head = the run's first lane, *len = its lanes
-// (a lane without a cell, SG_DROR_NO_CELL, is part of such runs too).  Every lane of the wave must call this.
-__device__ __forceinline__ void dror_run(uint32_t e, int lane, int *head, int *len)
-{
-    const uint32_t prev = __shfl_up(e, 1);
-    const unsigned long long heads = __ballot(lane == 0 || prev != e);
-    const unsigned long long upto = lane == 63 ? ~0ull : (2ull << lane) - 1ull;
-    *head = 63 - __clzll((long long)(heads & upto));
-    const unsigned long long after = heads & ~upto;
-    *len = (after ? __ffsll((long long)after) - 1 : 64) - *head;
-}
-
-// cell_of[i] = the entry of row i's cell (frame f, cell c: f (cells + 1) + 1 + c), or SG_DROR_NO_CELL for a row that is not usable
+// cell_of[i] = the entry of row i's cell (frame f, cell c: f (cells + 1) + 1 + c), or SG_NO_CELL for a row that is not usable
 template <typename T>
 __global__ __launch_bounds__(SG_DROR_BLOCK) void k_dror_count(const T *__restrict__ rows, int64_t n, const int64_t *__restrict__ frame_off, int n_frames,
                                                              const uint8_t *__restrict__ keep_in, SgDrorGrid g, uint32_t *__restrict__ entry,
                                                              uint32_t *__restrict__ cell_of)
 {
     const int64_t i = (int64_t)blockIdx.x * SG_DROR_BLOCK + threadIdx.x;
-    uint32_t e = SG_DROR_NO_CELL;
-    if (i < n && i >= frame_off[0] && i < frame_off[n_frames] && (!keep_in || keep_in[i] != 0)) {
+    uint32_t e = SG_NO_CELL;
+    if (sg_row_present(frame_off, n_frames, keep_in, i, n)) {
         const T *row = rows + i * 5;
         const double x = (double)row[0], y = (double)row[1], z = (double)row[2];
         if (sg_dror_usable(x, y, z)) {
-            const int f = dror_frame(frame_off, n_frames, i);
+            const int f = sg_find_frame(frame_off, n_frames, i);
             e = (uint32_t)((int64_t)f * (g.cells + 1) + 1 + sg_dror_cell(g, x, y));
         }
     }
-    const int lane = threadIdx.x & 63;
-    int head, len;
-    dror_run(e, lane, &head, &len);
-    if (lane == head && e != SG_DROR_NO_CELL) atomicAdd(&entry[e], (uint32_t)len);
+    sg_run_add(entry, e, SG_NO_CELL, threadIdx.x & 63);
     if (i < n) cell_of[i] = e;
 }
 
 // entry[f (cells + 1)] = frame_off[f]; entry[.. + 1 + c] = frame_off[f] + the rows filed in the cells before c
 __global__ __launch_bounds__(SG_DROR_SCAN_BLOCK) void k_dror_scan(const int64_t *__restrict__ frame_off, int32_t cells, uint32_t *__restrict__ entry)
 {
-    __shared__ uint32_t wave_sum[SG_DROR_SCAN_BLOCK / 64];
-    const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    uint32_t *e = entry + (int64_t)f * (cells + 1);
-    uint32_t carry = (uint32_t)frame_off[f];
-    if (tid == 0) e[0] = carry;
-    for (int32_t c0 = 0; c0 < cells; c0 += SG_DROR_SCAN_BLOCK) {
-        const int32_t c = c0 + tid;
-        const uint32_t v = c < cells ? e[1 + c] : 0u;
-        uint32_t incl = v;
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t up = __shfl_up(incl, d);
-            if (lane >= d) incl += up;
-        }
-        if (lane == 63) wave_sum[wave] = incl;
-        __syncthreads();
-        uint32_t before = 0, total = 0;
-        for (int w = 0; w < SG_DROR_SCAN_BLOCK / 64; ++w) {
-            const uint32_t s = wave_sum[w];
-            before += w < wave ? s : 0u;
-            total += s;
-        }
-        if (c < cells) e[1 + c] = carry + before + incl - v;
-        carry += total;
-        __syncthreads();
-    }
+    uint32_t *e = entry + (int64_t)blockIdx.x * (cells + 1);
+    const uint32_t first = (uint32_t)frame_off[blockIdx.x];
+    if (threadIdx.x == 0) e[0] = first;
+    sg_block_scan_excl<SG_DROR_SCAN_BLOCK>(e + 1, e + 1, cells, first);
 }
 
 template <typename T>
@@ -99,16 +53,11 @@ __global__ __launch_bounds__(SG_DROR_BLOCK) void k_dror_scatter(const T *__restr
                                                                uint32_t *__restrict__ entry, T *__restrict__ sorted)
 {
     const int64_t i = (int64_t)blockIdx.x * SG_DROR_BLOCK + threadIdx.x;
-    const uint32_t e = i < n ? cell_of[i] : SG_DROR_NO_CELL;
-    const int lane = threadIdx.x & 63;
-    int head, len;
-    dror_run(e, lane, &head, &len);
-    uint32_t base = 0;
-    if (lane == head && e != SG_DROR_NO_CELL) base = atomicAdd(&entry[e], (uint32_t)len);      // the run's positions: consecutive
-    base = __shfl(base, head);
-    if (e == SG_DROR_NO_CELL) return;
+    const uint32_t e = i < n ? cell_of[i] : SG_NO_CELL;
+    const uint32_t p = sg_run_claim(entry, e, SG_NO_CELL, threadIdx.x & 63);
+    if (e == SG_NO_CELL) return;
     const T *row = rows + i * 5;
-    T *dst = sorted + (int64_t)(base + (uint32_t)(lane - head)) * 3;      // (below the frame's end: a frame files no more rows than it has)
+    T *dst = sorted + (int64_t)p * 3;     // (below the frame's end: a frame files no more rows than it has)
     dst[0] = row[0]; dst[1] = row[1]; dst[2] = row[2];
 }
 
@@ -136,7 +85,7 @@ __global__ __launch_bounds__(SG_DROR_BLOCK) void k_dror_query(const T *__restric
     int nb = 0;
     bool keep = false;
     const uint32_t own = cell_of[i];
-    if (own != SG_DROR_NO_CELL) {                      // usable: present, finite and within the limit
+    if (own != SG_NO_CELL) {                     // usable: present, finite and within the limit
         const T *row = rows + i * 5;
         const double x = (double)row[0], y = (double)row[1], z = (double)row[2];
         const double s2 = sg_dror_s2(g, x * x + y * y);
@@ -146,7 +95,7 @@ __global__ __launch_bounds__(SG_DROR_BLOCK) void k_dror_query(const T *__restric
         else {
             SgDrorWindow w;
             sg_dror_window(g, x, y, s2, &w);
-            const uint32_t *e = entry + (int64_t)dror_frame(frame_off, n_frames, i) * (g.cells + 1);
+            const uint32_t *e = entry + (int64_t)sg_find_frame(frame_off, n_frames, i) * (g.cells + 1);
             if (w.cart)
                 for (int iy = w.iy0; iy <= w.iy1 && cnt < need; ++iy) {
                     const uint32_t *er = e + iy * g.cart_m;

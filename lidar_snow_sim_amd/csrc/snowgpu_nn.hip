@@ -7,7 +7,8 @@
 //               within the frame's K records; entry[cells] = its usable centres.
 //   k_nn_walk   one LANE per row: sg_nn_walk over rings around the row's cell, the k best in registers (KK = k slots, one instance per k, every
 //               loop over them unrolled), then index, dist2 and the weights.  Neighbouring lanes are neighbouring rows of the sensor's order
-//               and walk neighbouring cells.  A row that is absent or not usable writes -1, +inf and 0.
+//               and walk neighbouring cells.  A row that is absent or not usable writes -1, +inf and 0.  Whether a row is present and
+//               which frame it lies in: sg_rowkit.h.
 // The order inside a span depends on the arrival of LDS atomics; the result does not (sg_nn.h: the bound is strict).
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off (see lidar_snow_sim_amd/build.py).
 #include <hip/hip_runtime.h>
@@ -15,6 +16,7 @@
 #include "sg_nn.h"
 #include "sg_common.h"
 #include "sg_launch.h"
+#include "sg_rowkit.h"
 
 #define SG_NN_BLOCK 256
 
@@ -73,17 +75,6 @@ __global__ __launch_bounds__(SG_NN_BLOCK) void k_nn_file(const T *__restrict__ c
     }
 }
 
-// largest f with off[f] <= i (off[0] <= i < off[n_frames])
-__device__ __forceinline__ int nn_frame(const int64_t *__restrict__ off, int n_frames, int64_t i)
-{
-    int lo = 0, hi = n_frames - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (off[mid] <= i) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
-
 template <typename T, int KK>
 __global__ __launch_bounds__(SG_NN_BLOCK) void k_nn_walk(const T *__restrict__ rows, int64_t n, const int64_t *__restrict__ frame_off, int n_frames,
                                                          const uint8_t *__restrict__ keep_in, SgFpsRange range, SgNnGrid g, int32_t K,
@@ -95,11 +86,11 @@ __global__ __launch_bounds__(SG_NN_BLOCK) void k_nn_walk(const T *__restrict__ r
     if (i >= n) return;
     SgNnKey<T> best[KK];
     sg_nn_clear<T, KK>(best);
-    if (i >= frame_off[0] && i < frame_off[n_frames] && (!keep_in || keep_in[i] != 0)) {
+    if (sg_row_present(frame_off, n_frames, keep_in, i, n)) {
         const T *row = rows + i * 5;
         const T x = row[0], y = row[1], z = row[2];
         if (sg_fps_usable<T>(range, x, y, z)) {
-            const int f = nn_frame(frame_off, n_frames, i);
+            const int f = sg_find_frame(frame_off, n_frames, i);
             const SgNnBox b{box[f * 4], box[f * 4 + 1], box[f * 4 + 2], box[f * 4 + 3]};
             sg_nn_walk<T, KK>(g, b, entry + (int64_t)f * (g.cells + 1), rec + (int64_t)f * K, x, y, z, best);
         }

@@ -9,26 +9,17 @@
 //                    memset of the index output) by a 32-bit atomic min.  The pixel comes from pixel_of: no angle is evaluated twice.
 //   k_range_finish   one thread per pixel: decodes the winner, gathers its row and writes the 1 + C planes and the index, every plane
 //                    coalesced along W; -1 in an empty pixel.  Without keys (a batch without a row) every pixel is empty.
-// Minima of integers: the result does not depend on the arrival of the atomics.
+// Minima of integers: the result does not depend on the arrival of the atomics.  Whether a row is present and which frame it lies in:
+// sg_rowkit.h.
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off (see lidar_snow_sim_amd/build.py).
 #include <hip/hip_runtime.h>
 
 #include "sg_common.h"
 #include "sg_launch.h"
 #include "sg_range.h"
+#include "sg_rowkit.h"
 
 #define SG_RANGE_BLOCK 256
-
-// largest f with off[f] <= i (off[0] <= i < off[n_frames])
-__device__ __forceinline__ int range_frame(const int64_t *__restrict__ off, int n_frames, int64_t i)
-{
-    int lo = 0, hi = n_frames - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (off[mid] <= i) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
 
 template <typename T>
 __global__ __launch_bounds__(SG_RANGE_BLOCK) void k_range_project(const T *__restrict__ rows, int64_t n, const int64_t *__restrict__ frame_off, int n_frames,
@@ -39,12 +30,12 @@ __global__ __launch_bounds__(SG_RANGE_BLOCK) void k_range_project(const T *__res
     const int64_t i = (int64_t)blockIdx.x * SG_RANGE_BLOCK + threadIdx.x;
     if (i >= n) return;
     int32_t p = -1;
-    if (i >= frame_off[0] && i < frame_off[n_frames] && (!keep_in || keep_in[i] != 0)) {
+    if (sg_row_present(frame_off, n_frames, keep_in, i, n)) {
         const T *row = rows + i * 5;
         T r;
         const int32_t q = sg_range_pixel<T>(g, row[0], row[1], row[2], g.by_ring ? ring[i] : 0, &r);
         if (q >= 0) {
-            p = range_frame(frame_off, n_frames, i) * (g.H * g.W) + q;      // (below F H W <= 2^31 - 1)
+            p = sg_find_frame(frame_off, n_frames, i) * (g.H * g.W) + q;      // (below F H W <= 2^31 - 1)
             sg_range_lower(&key[p], sg_range_key(r, (uint32_t)i));
             if (count) atomicAdd(&count[p], 1);
         }

@@ -15,6 +15,8 @@
 //   k_voxel_finish      every packed index below F V: num_points = min(rows of the span, T); beyond voxel_offsets[F]: coords -1, 0 points
 // A span's ORDER depends on the arrival of atomics; what is read from it -- how many of its row indices are smaller than a given one --
 // does not.  Every output element is a function of integer row indices: results are identical from run to run.
+// The offsets search, the in-batch test, the runs of lanes (sg_lane_run, sg_run_add, sg_run_claim) and the three scans
+// (sg_block_scan_excl) are sg_rowkit.h's.
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off (see lidar_snow_sim_amd/build.py).
 #include <hip/hip_runtime.h>
 
@@ -23,46 +25,18 @@
 #include "sg_common.h"
 #include "sg_voxel.h"
 #include "sg_launch.h"
+#include "sg_rowkit.h"
 
 #define SG_VOX_BLOCK 256
 #define SG_VOX_TILE 1024          /* rows per tile: four per thread */
 #define SG_VOX_SCAN_BLOCK 1024
 
-// largest f with off[f] <= i (0 if there is none)
-__device__ __forceinline__ int vox_frame_search(const int64_t *__restrict__ off, int n_frames, int64_t i)
-{
-    int lo = 0, hi = n_frames - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (off[mid] <= i) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
-
 // The frame of row i (off[0] <= i < off[n_frames]) where the lanes of a wave hold consecutive rows: the frame of the wave's first row
 // serves every lane in front of that frame's end.
 __device__ __forceinline__ int vox_frame(const int64_t *__restrict__ off, int n_frames, int64_t i, int lane)
 {
-    const int f0 = vox_frame_search(off, n_frames, i - lane);
-    return i < off[f0 + 1] && i >= off[f0] ? f0 : vox_frame_search(off, n_frames, i);
-}
-
-// A run of consecutive lanes with the same id is served by ONE atomic, made by its first lane (rows that follow one another in a sweep
-// share cells, and atomics of one wave on one address queue behind one another in L2).  *head = the run's first lane, *len = its lanes.
-// Every lane of the wave must call this.
-__device__ __forceinline__ void vox_run(uint32_t a, uint32_t b, int lane, int *head, int *len)
-{
-    const uint32_t pa = __shfl_up(a, 1), pb = __shfl_up(b, 1);
-    const unsigned long long heads = __ballot(lane == 0 || pa != a || pb != b);
-    const unsigned long long upto = lane == 63 ? ~0ull : (2ull << lane) - 1ull;
-    *head = 63 - __clzll((long long)(heads & upto));
-    const unsigned long long after = heads & ~upto;
-    *len = (after ? __ffsll((long long)after) - 1 : 64) - *head;
-}
-
-__device__ __forceinline__ bool vox_in_batch(const int64_t *__restrict__ off, int n_frames, int64_t i, int64_t n)
-{
-    return i < n && i >= off[0] && i < off[n_frames];
+    const int f0 = sg_find_frame(off, n_frames, i - lane);
+    return i < off[f0 + 1] && i >= off[f0] ? f0 : sg_find_frame(off, n_frames, i);
 }
 
 // slot_of[i] = the slot of row i's cell in its frame's table, SG_VOXEL_NONE for a row that is not usable
@@ -74,13 +48,13 @@ __global__ __launch_bounds__(SG_VOX_BLOCK) void k_voxel_insert(const T *__restri
     const int64_t i = (int64_t)blockIdx.x * SG_VOX_BLOCK + threadIdx.x;
     const int lane = threadIdx.x & 63;
     uint32_t key = SG_VOXEL_NONE, f = 0;
-    if (vox_in_batch(frame_off, n_frames, i, n) && (!keep_in || keep_in[i] != 0)) {
+    if (sg_row_present(frame_off, n_frames, keep_in, i, n)) {
         const T *row = rows + i * 5;
         key = sg_voxel_key(g, (double)row[0], (double)row[1], (double)row[2]);
         if (key != SG_VOXEL_NONE) f = (uint32_t)vox_frame(frame_off, n_frames, i, lane);
     }
     int head, len;
-    vox_run(key, f, lane, &head, &len);
+    sg_lane_run(key, f, lane, &head, &len);
     uint32_t slot = SG_VOXEL_NONE;
     if (lane == head && key != SG_VOXEL_NONE)          // the run's first lane holds its smallest row
         slot = sg_voxel_insert(table + (int64_t)f * g.cap, g.cap, g.shift, key, (uint32_t)i);
@@ -120,30 +94,8 @@ __global__ __launch_bounds__(SG_VOX_BLOCK) void k_voxel_first(int64_t n, const i
 // tile_base[t] = the firsts in the tiles in front of tile t, t = 0 .. n_tiles (the last: all of them)
 __global__ __launch_bounds__(SG_VOX_SCAN_BLOCK) void k_voxel_tile_scan(const int32_t *__restrict__ tile_cnt, int64_t n_tiles, int32_t *__restrict__ tile_base)
 {
-    __shared__ int32_t wave_sum[SG_VOX_SCAN_BLOCK / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    int32_t carry = 0;
-    for (int64_t t0 = 0; t0 < n_tiles; t0 += SG_VOX_SCAN_BLOCK) {
-        const int64_t t = t0 + tid;
-        const int32_t v = t < n_tiles ? tile_cnt[t] : 0;
-        int32_t incl = v;
-        for (int d = 1; d < 64; d <<= 1) {
-            const int32_t up = __shfl_up(incl, d);
-            if (lane >= d) incl += up;
-        }
-        if (lane == 63) wave_sum[wave] = incl;
-        __syncthreads();
-        int32_t before = 0, total = 0;
-        for (int w = 0; w < SG_VOX_SCAN_BLOCK / 64; ++w) {
-            const int32_t s = wave_sum[w];
-            before += w < wave ? s : 0;
-            total += s;
-        }
-        if (t < n_tiles) tile_base[t] = carry + before + incl - v;
-        carry += total;
-        __syncthreads();
-    }
-    if (tid == 0) tile_base[n_tiles] = carry;
+    const int32_t all = sg_block_scan_excl<SG_VOX_SCAN_BLOCK>(tile_cnt, tile_base, n_tiles, (int32_t)0);
+    if (threadIdx.x == 0) tile_base[n_tiles] = all;
 }
 
 // the firsts among the rows [0, x) of the batch, 0 <= x <= n; the whole wave calls it and every lane gets the sum
@@ -174,23 +126,8 @@ __global__ __launch_bounds__(64) void k_voxel_frame_cells(int64_t n, const int64
 // (F V <= 2^31 - 1 by the entry's domain: the sums fit).
 __global__ __launch_bounds__(256) void k_voxel_offsets(const int32_t *__restrict__ m, int n_frames, int32_t *__restrict__ voxel_offsets)
 {
-    __shared__ int32_t s_wave[4];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    int32_t carry = 0;
-    for (int f0 = 0; f0 < n_frames; f0 += 256) {
-        const int f = f0 + tid;
-        const int32_t c = f < n_frames ? m[f] : 0;
-        int32_t inc = c;
-        for (int o = 1; o < 64; o <<= 1) { const int32_t v = __shfl_up(inc, o); if (lane >= o) inc += v; }
-        if (lane == 63) s_wave[w] = inc;
-        __syncthreads();
-        int32_t before = carry;
-        for (int ww = 0; ww < w; ++ww) before += s_wave[ww];
-        if (f < n_frames) voxel_offsets[f] = before + inc - c;
-        carry += s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
-        __syncthreads();
-    }
-    if (tid == 0) voxel_offsets[n_frames] = carry;
+    const int32_t all = sg_block_scan_excl<256>(m, voxel_offsets, n_frames, (int32_t)0);
+    if (threadIdx.x == 0) voxel_offsets[n_frames] = all;
 }
 
 // Every first row: v = its rank among the firsts of its frame, in row order.  The low word of its cell's slot becomes the packed voxel
@@ -220,7 +157,7 @@ __global__ __launch_bounds__(SG_VOX_BLOCK) void k_voxel_assign(int64_t n, const 
         const int64_t i = (int64_t)blockIdx.x * SG_VOX_TILE + q * SG_VOX_BLOCK + threadIdx.x;
         int before = in_wave[q];
         for (int k = 0; k < q * 4 + wave; ++k) before += s_cnt[k];
-        const int f = vox_frame_search(frame_off, n_frames, i);
+        const int f = sg_find_frame(frame_off, n_frames, i);
         const int32_t v = tile_base[blockIdx.x] + before - fbase[f];
         unsigned long long *slot = table + (int64_t)f * g.cap + slot_of[i];
         const uint32_t key = (uint32_t)(*slot >> 32);
@@ -249,9 +186,7 @@ __global__ __launch_bounds__(SG_VOX_BLOCK) void k_voxel_count(int64_t n, const i
         const uint32_t slot = slot_of[i];
         if (slot != SG_VOXEL_NONE) v = vox_slot_low(table, cap, vox_frame(frame_off, n_frames, i, lane), slot);
     }
-    int head, len;
-    vox_run(v, 0u, lane, &head, &len);
-    if (lane == head && v != SG_VOXEL_NONE) atomicAdd(&span[v], (uint32_t)len);
+    sg_run_add(span, v, SG_VOXEL_NONE, lane);
     if (i < n) {
         vox[i] = v;
         if (out_voxel_of) out_voxel_of[i] = (int32_t)v;
@@ -262,31 +197,9 @@ __global__ __launch_bounds__(SG_VOX_BLOCK) void k_voxel_count(int64_t n, const i
 __global__ __launch_bounds__(SG_VOX_SCAN_BLOCK) void k_voxel_span_scan(const int64_t *__restrict__ frame_off, const int32_t *__restrict__ voxel_offsets,
                                                                       uint32_t *__restrict__ span)
 {
-    __shared__ uint32_t wave_sum[SG_VOX_SCAN_BLOCK / 64];
-    const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int32_t m = voxel_offsets[f + 1] - voxel_offsets[f];
+    const int f = blockIdx.x;
     uint32_t *e = span + voxel_offsets[f];
-    uint32_t carry = (uint32_t)frame_off[f];
-    for (int32_t c0 = 0; c0 < m; c0 += SG_VOX_SCAN_BLOCK) {
-        const int32_t c = c0 + tid;
-        const uint32_t v = c < m ? e[c] : 0u;
-        uint32_t incl = v;
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t up = __shfl_up(incl, d);
-            if (lane >= d) incl += up;
-        }
-        if (lane == 63) wave_sum[wave] = incl;
-        __syncthreads();
-        uint32_t before = 0, total = 0;
-        for (int w = 0; w < SG_VOX_SCAN_BLOCK / 64; ++w) {
-            const uint32_t s = wave_sum[w];
-            before += w < wave ? s : 0u;
-            total += s;
-        }
-        if (c < m) e[c] = carry + before + incl - v;
-        carry += total;
-        __syncthreads();
-    }
+    sg_block_scan_excl<SG_VOX_SCAN_BLOCK>(e, e, voxel_offsets[f + 1] - voxel_offsets[f], (uint32_t)frame_off[f]);
 }
 
 // (a frame's voxels hold no more rows than the frame has: every position lies inside the frame's slice of `order`)
@@ -295,13 +208,8 @@ __global__ __launch_bounds__(SG_VOX_BLOCK) void k_voxel_scatter(int64_t n, const
     const int64_t i = (int64_t)blockIdx.x * SG_VOX_BLOCK + threadIdx.x;
     const int lane = threadIdx.x & 63;
     const uint32_t v = i < n ? vox[i] : SG_VOXEL_NONE;
-    int head, len;
-    vox_run(v, 0u, lane, &head, &len);
-    uint32_t base = 0;
-    if (lane == head && v != SG_VOXEL_NONE) base = atomicAdd(&span[v], (uint32_t)len);      // the run's positions: consecutive
-    base = __shfl(base, head);
+    const uint32_t pos = sg_run_claim(span, v, SG_VOXEL_NONE, lane);
     if (v == SG_VOXEL_NONE) return;
-    const uint32_t pos = base + (uint32_t)(lane - head);
     if ((int64_t)pos < n) order[pos] = (uint32_t)i;
 }
 

@@ -6,7 +6,7 @@ scan that carries a running total from trip to trip, which the other GPU tests n
   k_mask_offsets (snowgpu_mask.hip)             64 frames a wave (s_wave[]), 256 a trip       many(65 / 256 / 257 / 321)
   k_voxel_offsets (snowgpu_voxel.hip)           the same                                      many(65 / 256 / 257 / 321)
   k_voxel_tile_scan (snowgpu_voxel.hip)         64 tiles a wave (wave_sum[]), 1024 a trip     many(F): 80 and more tiles; voxel_batch(): 1025 tiles
-  vox_frame_search / vox_firsts_before          frames that start inside a tile               many(F): hundreds of frames, empty ones in a row
+  sg_find_frame / vox_firsts_before             frames that start inside a tile               many(F): hundreds of frames, empty ones in a row
   run bases of k_paste_frame (snowgpu_paste.hip) ceil(runs / 256) runs a thread               paste_long(): 257 runs, chunk = 2, the lo / hi clamps
   k_roi_count / k_roi_scan / k_roi_rank         a table row per 512-row run                   roi_long(): 257 runs, a frame of 129 beside it
   k_pre_means as the aligned wet entry runs it  64 tiles a trip                               long()
@@ -158,7 +158,7 @@ def _voxel_case(rows, off, keep, V, what):
 def test_voxelize_past_a_wave_and_a_trip_of_frames(F):
     """k_voxel_offsets (64 frames a wave, 256 a trip, `carry`) under STRADDLE and with max_voxels = 40 -- frames above, below and at zero
     cells on both sides of frame 256 --, with and without the mask; k_voxel_tile_scan's sum over earlier waves (more than 64 tiles in the
-    call); vox_frame_search and vox_firsts_before over hundreds of frames that start inside a tile, empty ones in a row.  All five
+    call); sg_find_frame and vox_firsts_before over hundreds of frames that start inside a tile, empty ones in a row.  All five
     outputs equal the sequential walk byte for byte; voxel_offsets[F] is the walk's total."""
     frames, masks = bsi.many(F)
     rows, keep, off = np.concatenate(frames), np.concatenate(masks), bsi.offsets(frames)
